@@ -16,6 +16,8 @@ through the last bounce, the reduce over ranks, and the write of the W*H mean co
         --master-port P bench.py --gpus N --steps K --warmup W      # the same under an outer launcher
     python bench.py --scene dragon --spp 16          # another BASELINE config at ITS frame size, nothing else
     python bench.py --scene simple_video             # scene rebuilt per frame (examples/simple_video.rs): frames/s
+    python bench.py --dump-outputs DIR               # also write the last timed step's frames as DIR/<scene>.npy, so that
+                                                     # two builds can be compared output for output (same arguments, same inputs)
 
 The default 1-GPU run prints ONE JSON line.  Besides the headline it carries
   * `other_configs`: BASELINE configs[2-4] (dragon-class mesh at its 256 spp, fractal spheres, wine glass — mesh and
@@ -66,6 +68,10 @@ CPU_MIN_SPP, CPU_REPS = 16, 3
 PMC_A = "FETCH_SIZE SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU"
 PMC_B = "WRITE_SIZE SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INST_LEVEL_VMEM"
 PMC_C = "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE"
+# --dump-outputs: the headline frame is written whole up to DUMP_HEADLINE_PIXELS (1920x1080 fits), every other frame as a
+# fixed seeded sample of at most DUMP_OTHER_PIXELS pixels, so that the default run's files stay under DUMP_MAX_BYTES
+DUMP_HEADLINE_PIXELS, DUMP_OTHER_PIXELS, DUMP_MAX_BYTES = 2 ** 21, 2 ** 19, 64 * 2 ** 20
+DUMP_SAMPLE_SEED = 0x44554D50
 
 
 def algorithmic_bytes(c, env_is_hdri):
@@ -269,6 +275,28 @@ class Workload:
         self.gpu.close()
 
 
+def frame_output(frame, W, H, max_pixels):
+    """The f32 mean colours of one frame as its caller receives them, shaped (H, W, 3); a frame of more than max_pixels
+    pixels as the rows (max_pixels, 3) of a fixed seeded sample of its pixels, in pixel order."""
+    import numpy as np
+    px = np.array(frame, dtype=np.float32, copy=True).reshape(H * W, 3)
+    if H * W <= max_pixels:
+        return px.reshape(H, W, 3)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, max_pixels, replace=False))
+    return px[idx]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def committed_n1_line(scene, W, H, B, spp):
     """The newest committed bench line (profiles/rNN_bench_default.json, profiles/rNN_<scene>_bench_line.json) of the same
     workload on ONE GPU, for an N-GPU line to carry along; None when there is none.  Informational: a different build."""
@@ -451,7 +479,7 @@ def run_simple_video(args, local_rank):
     import numpy as np
     import rpt_amd
     from rpt_amd import _abi, make_params, scenes
-    frames = max(1, args.steps if args.steps != 3 else 30)
+    frames = args.steps if args.steps is not None else 30
     out, t_create, t_render = None, 0.0, 0.0
     sc0, cam0, cfg = scenes.simple_video(0)
     W, H = args.width or cfg["width"], args.height or cfg["height"]
@@ -476,6 +504,8 @@ def run_simple_video(args, local_rank):
         t_render += t2 - t1
         per_frame.append((t1 - t0) * 1e3)
     total = time.perf_counter() - t_all
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"simple_video": frame_output(out, W, H, DUMP_HEADLINE_PIXELS)})
     print(json.dumps({"metric": "frames/s (scene rebuilt per frame)", "value": frames / total, "unit": "frames/s", "n_gpus": 1,
                       "steps": frames, "warmup": args.warmup, "ms_per_step": total / frames * 1e3, "higher_is_better": True,
                       "dtype": "f64", "data": "synthetic",
@@ -665,7 +695,7 @@ SCALAR_KEYS = {"dragon": "c3_msamples", "fractal_spheres": "c4_msamples", "wine_
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 3; 30 frames for simple_video)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--spp", type=int, default=None, help="samples per pixel per step (default: the config's own)")
     ap.add_argument("--scene", default=None, help="one workload only (default: cornell = the headline, plus the other configs)")
@@ -678,6 +708,9 @@ def main():
     ap.add_argument("--no-live-pmc", action="store_true", help="do not re-run a step under rocprofv3 for the counter fields")
     ap.add_argument("--cpu-spp", type=int, default=None, help="spp of the CPU-baseline sample (default and minimum: 16)")
     ap.add_argument("--dump-frame", default=None, help="rank 0 saves the last step's reduced f32 frame (.npy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's frame of every timed workload as DIR/<scene>.npy (f32; large "
+                         "frames as a fixed seeded sample of their pixels)")
     ap.add_argument("--fixed-samples", action="store_true", help="every step renders the same samples (tests)")
     ap.add_argument("--emulate-part-of", type=int, default=0, metavar="N",
                     help="single process: render only the tiles rank 0 would own among N ranks (no collective) and report "
@@ -693,6 +726,10 @@ def main():
         return pmc_worker(args)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.emulate_part_of > 1:
+        ap.error("--dump-outputs: --emulate-part-of is not a bench run")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))  # no launcher around us: be our own (one rank per GPU, this file again)
 
@@ -734,6 +771,8 @@ def main():
     dev = rk.dev
     if args.scene == "simple_video" and world == 1:
         return run_simple_video(args, local_rank)
+    if args.steps is None:
+        args.steps = 3
 
     torch.cuda.synchronize()
     wl = Workload(args.scene, args, rank, world, local_rank, backend)
@@ -768,6 +807,7 @@ def main():
 
     if rank == 0 and args.dump_frame:
         np.save(args.dump_frame, host_frame.numpy())
+    outputs = {args.scene: frame_output(host_frame.numpy(), W, H, DUMP_HEADLINE_PIXELS)} if rank == 0 and args.dump_outputs else None
     out = None
     if rank == 0:
         total_samples = float(W) * H * spp * args.steps
@@ -848,8 +888,10 @@ def main():
             entry = None
             try:
                 o = Workload(name, args, rank, world, local_rank, backend, spp=ospp, is_headline=False)
-                ostep, olib, onote_x, _ = setup_exchange(rk, o)
+                ostep, olib, onote_x, oframe = setup_exchange(rk, o)
                 dt, oeach, ost, oper_rank = timed_steps(rk, o, ostep, osteps, owarm)
+                if outputs is not None:
+                    outputs[name] = frame_output(oframe.numpy(), o.W, o.H, DUMP_OTHER_PIXELS)
                 if rank == 0:
                     ob, oosc = accounting(o, ost)
                     ok, odom, okn = kernel_table(o, ost, ob)
@@ -889,6 +931,8 @@ def main():
                 if key and "value" in e:
                     out[key] = e["value"]
                     out[key + "_spp_per_step"] = e["spp"]
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         print(json.dumps(out))
         sys.stdout.flush()

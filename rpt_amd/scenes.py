@@ -373,9 +373,10 @@ def compound():
 
 
 # ----------------------------------------------------------------------------- the asset-driven examples
-# The reference reads these files from its own examples/ directory; they are not redistributed here.  `asset(name)`
-# finds them in the directories of $RPT_ASSETS (os.pathsep-separated); every scene below takes the loaded mesh as an
-# argument and falls back to a seeded procedural stand-in of about the same size and extent.
+# The reference reads these files from its own examples/ directory; the package does not ship them (tests/golden/assets
+# holds copies for the tests only).  `asset(name)` finds them in the directories of $RPT_ASSETS (os.pathsep-separated);
+# every scene below takes the loaded mesh as an argument and falls back to a seeded procedural stand-in of about the
+# same size and extent.
 def asset(name):
     """path of an asset file of the reference's examples/ (or of `name` inside pegasus.zip -> an open text file), or None"""
     import os

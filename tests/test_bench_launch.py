@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
@@ -59,3 +61,37 @@ def test_self_launch_builds_one_rank_per_gpu(monkeypatch):
     assert os.path.samefile(cmd[cmd.index("--master-port") + 2], BENCH)
     assert cmd[-6:] == ["--gpus", "8", "--steps", "5", "--warmup", "2"]
     assert seen["env"]["RPT_BENCH_SELF_LAUNCHED"] == "1" and seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_writes_whole_small_frames_and_a_fixed_sample_of_large_ones(tmp_path):
+    """--dump-outputs: a frame within the pixel limit is written whole as (H, W, 3) f32; a larger one as the same
+    seeded sample of its pixels on every call; more than the byte limit in all is refused"""
+    import numpy as np
+    bench = _bench_module()
+    W, H = 40, 30
+    frame = np.random.default_rng(1).random(W * H * 3).astype(np.float32)
+    whole = bench.frame_output(frame, W, H, W * H)
+    assert whole.shape == (H, W, 3) and whole.dtype == np.float32 and (whole.reshape(-1) == frame).all()
+    part = bench.frame_output(frame, W, H, 100)
+    assert part.shape == (100, 3) and (part == bench.frame_output(frame.copy(), W, H, 100)).all()
+    rows = frame.reshape(-1, 3)
+    idx = [int(np.flatnonzero((rows == r).all(axis=1))[0]) for r in part]
+    assert idx == sorted(set(idx))  # distinct pixels, in pixel order
+    bench.dump_outputs(str(tmp_path / "d"), {"a": whole, "b": part})
+    assert (np.load(str(tmp_path / "d" / "a.npy")) == whole).all() and (np.load(str(tmp_path / "d" / "b.npy")) == part).all()
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "e"), {"big": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, dtype=np.float32)})
+    assert not (tmp_path / "e").exists()
+
+
+def test_steps_below_one_is_refused():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], capture_output=True, text=True, env=_env(), timeout=600)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr, r.stderr[-500:]

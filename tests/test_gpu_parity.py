@@ -665,6 +665,7 @@ def test_error_paths_on_device(built):
 def test_bench_two_ranks_equal_one_rank(tmp_path):
     """bench.py's N>1 path on the real GPU: two ranks (gloo stands in for RCCL, both on device 0)
     shard the tiles and reduce; the reduced f32 frame equals the single-rank frame bit for bit."""
+    import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -672,16 +673,16 @@ def test_bench_two_ranks_equal_one_rank(tmp_path):
               "--no-cpu-baseline", "--no-live-pmc", "--fixed-samples"]
     one = str(tmp_path / "one.npy")
     two = str(tmp_path / "two.npy")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dump-frame", one] + common,
-                       capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--dump-frame", one,
+                        "--dump-outputs", str(tmp_path / "out1")] + common, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["steps"] == 1
     # NO launcher: `python bench.py --gpus 2` starts its own two ranks (the driver's form of the call)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["RPT_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dump-frame", two] + common,
-                       capture_output=True, text=True, env=env, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dump-frame", two,
+                        "--dump-outputs", str(tmp_path / "out2")] + common, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
-    import json
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines  # ONE JSON line, from rank 0
     out = json.loads(lines[0])
@@ -694,6 +695,10 @@ def test_bench_two_ranks_equal_one_rank(tmp_path):
     assert "n1_reference" in out and out["n1_reference"] is None
     a, b = np.load(one), np.load(two)
     assert a.shape == b.shape == (320 * 180 * 3,) and (a == b).all() and a.max() > 0
+    for d in ("out1", "out2"):  # --dump-outputs: the same last frame, shaped (H, W, 3)
+        assert os.listdir(str(tmp_path / d)) == ["cornell.npy"]
+        c = np.load(str(tmp_path / d / "cornell.npy"))
+        assert c.shape == (180, 320, 3) and c.dtype == np.float32 and (c.reshape(-1) == a).all()
 
 
 @pytest.mark.parametrize("failing_rank", ["1", "all"])

@@ -1,5 +1,6 @@
 """Asset import mirrors reference src/io.rs: fan triangulation, negative indices, per-corner
 normals vs flat fallback, usemtl grouping, MTL conversions, binary / ASCII STL detection."""
+import os
 import struct
 
 import numpy as np
@@ -97,19 +98,31 @@ def test_load_stl_binary_and_ascii(tmp_path):
         load_stl(str(tmp_path / "c.stl"))
 
 
-# ---- the reference's own asset files, when the reference tree is present (this container only;
-# ---- the GPU box has no /root/reference, and these tests need no GPU)
-REF_EXAMPLES = "/root/reference/examples"
+# ---- the reference's own asset files, stored under tests/golden/assets (tests/golden/assets/make_assets.py says how)
+ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "assets")
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir(REF_EXAMPLES), reason="reference tree not present")
+@pytest.fixture(scope="module")
+def ref_examples(tmp_path_factory):
+    """a directory holding the asset files as the reference's examples/ has them (unpacked from tests/golden/assets)"""
+    import lzma
+    import shutil
+    d = tmp_path_factory.mktemp("examples")
+    for name in os.listdir(ASSETS):
+        if name.endswith(".xz"):
+            with lzma.open(os.path.join(ASSETS, name)) as f, open(str(d / name[:-3]), "wb") as g:
+                g.write(f.read())
+    shutil.copy(os.path.join(ASSETS, "pegasus.zip"), str(d))
+    return str(d)
+
+
 @pytest.mark.parametrize("name,kind", [("teapot.obj", "obj"), ("wine_glass.obj", "obj"), ("rustacean.obj", "obj"),
                                        ("monomial.obj", "obj"), ("cylinder.stl", "stl")])
-def test_reference_assets_load_and_build(name, kind):
+def test_reference_assets_load_and_build(name, kind, ref_examples):
     import os
 
     from oracle import oracle_ffi as O
-    path = os.path.join(REF_EXAMPLES, name)
+    path = os.path.join(ref_examples, name)
     mesh = load_obj(path) if kind == "obj" else load_stl(path)
     t = mesh.triangles
     assert t.ndim == 2 and t.shape[1] == 18 and len(t) > 50
@@ -156,7 +169,7 @@ def _cpp_rows(path):
     return rows
 
 
-def test_cpp_mirror_loaders_equal_the_python_mirror(tmp_path):
+def test_cpp_mirror_loaders_equal_the_python_mirror(tmp_path, ref_examples):
     # include/rpt.hpp load_obj / load_stl (reference src/io.rs) against rpt_amd.io, bit for bit
     p = tmp_path / "a.obj"
     p.write_text(OBJ)
@@ -174,18 +187,16 @@ def test_cpp_mirror_loaders_equal_the_python_mirror(tmp_path):
         % tuple(float(x) for x in np.concatenate([r[9:12], r[0:9]])) for r in rows[:7]) + "endsolid t\n")
     assert (_cpp_rows(a) == load_stl(str(a)).triangles).all()
     import os
-    for name in ("teapot.obj", "cylinder.stl"):  # the reference's own assets, when present
-        path = os.path.join(REF_EXAMPLES, name)
-        if os.path.exists(path):
-            ref = (load_obj(path) if name.endswith(".obj") else load_stl(path)).triangles
-            assert (_cpp_rows(path) == ref).all(), name
+    for name in ("teapot.obj", "cylinder.stl"):  # the reference's own assets
+        path = os.path.join(ref_examples, name)
+        ref = (load_obj(path) if name.endswith(".obj") else load_stl(path)).triangles
+        assert (_cpp_rows(path) == ref).all(), name
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir(REF_EXAMPLES), reason="reference tree not present")
 @pytest.mark.parametrize("name,asset", [("teapot", "teapot.obj"), ("cylinder", "cylinder.stl"), ("rustacean", "rustacean.obj"),
                                         ("metal", "teapot.obj"), ("wine_glass", "wine_glass.obj"), ("fractal_teapots", "teapot.obj"),
                                         ("pegasus", "pegasus.obj")])
-def test_example_scenes_accept_the_reference_assets(name, asset, monkeypatch):
+def test_example_scenes_accept_the_reference_assets(name, asset, monkeypatch, ref_examples):
     """rpt_amd.scenes' transcriptions of the asset-driven examples, fed the reference's OWN files through
     scenes.load_asset ($RPT_ASSETS; pegasus.obj comes out of pegasus.zip as in examples/pegasus.rs:17-32): the scene
     passes the product's flattener (scene_create answers NO_DEVICE here, i.e. validation went through) and the oracle
@@ -193,7 +204,7 @@ def test_example_scenes_accept_the_reference_assets(name, asset, monkeypatch):
     import rpt_amd
     from oracle import oracle_ffi as O
     from rpt_amd import GpuScene, _abi, make_params, scenes
-    monkeypatch.setenv("RPT_ASSETS", REF_EXAMPLES)
+    monkeypatch.setenv("RPT_ASSETS", ref_examples)
     mesh = scenes.load_asset(asset)
     assert mesh is not None and len(mesh.triangles) > 300
     kw = dict(hdri_size=(64, 32)) if name in ("metal", "wine_glass", "pegasus") else {}

@@ -68,16 +68,18 @@ def test_the_pinning_tools_work_end_to_end_on_a_stand_in_dump(oracle, tmp_path):
     """The plumbing of scripts/compare_rust_golden.py, exercised WITHOUT Rust: frames the oracle itself rendered are written
     in dump_golden.rs's file format and compared — this proves nothing about parity (the oracle agrees with itself), only
     that the day a real dump exists the tool reads it, compares, and says PASS / FAIL.  The teapot scene needs the crate's
-    examples/teapot.obj: taken from /root/reference when this container has it."""
+    examples/teapot.obj: unpacked from tests/golden/assets into a stand-in crate directory."""
+    import lzma
     d = tmp_path / "golden"
     d.mkdir()
-    rpt_root = "/root/reference" if os.path.exists("/root/reference/examples/teapot.obj") else None
+    rpt_root = str(tmp_path / "rpt")
+    os.makedirs(os.path.join(rpt_root, "examples"))
+    with lzma.open(os.path.join(GOLDEN, "assets", "teapot.obj.xz")) as f, open(os.path.join(rpt_root, "examples", "teapot.obj"), "wb") as g:
+        g.write(f.read())
     cfg = {"sphere": (64, 36, 2, 8, 101), "cornell": (64, 36, 8, 8, 102), "teapot": (64, 64, 6, 8, 103)}
     for name, (w, h, b, n, seed) in cfg.items():
         extra = {}
         if name == "teapot":
-            if rpt_root is None:
-                continue
             from rpt_amd import io as rio
             extra["triangles"] = rio.load_obj(os.path.join(rpt_root, "examples", "teapot.obj")).triangles
             assert extra["triangles"].shape == (2256, 18)
@@ -86,7 +88,7 @@ def test_the_pinning_tools_work_end_to_end_on_a_stand_in_dump(oracle, tmp_path):
         assert np.isfinite(img).all() and img.max() > 0
         img.astype("<f8").tofile(str(d / (name + ".f64")))
         (d / (name + ".txt")).write_text("width %d\nheight %d\nmax_bounces %d\niterations %d\nseed %d\n" % (w, h, b, n, seed))
-    cmd = [sys.executable, os.path.join(ROOT, "scripts", "compare_rust_golden.py"), str(d)] + (["--rpt-root", rpt_root] if rpt_root else [])
+    cmd = [sys.executable, os.path.join(ROOT, "scripts", "compare_rust_golden.py"), str(d), "--rpt-root", rpt_root]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and r.stdout.strip().splitlines()[-1].startswith("pin_oracle: PASS"), r.stdout[-800:] + r.stderr[-800:]
     # a frame that is NOT the oracle's must fail, loudly

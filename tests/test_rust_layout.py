@@ -152,8 +152,8 @@ def test_patch_covers_the_closed_shape_set_and_is_current():
         assert kind in patch, kind
     assert "forbid(unsafe_code)" not in patch  # rpt keeps it: nothing in the patch touches that line
     assert "unsafe" not in "".join(l for l in patch.splitlines() if l.startswith("+") and "//" not in l)
-    ref = "/root/reference"
-    if os.path.isdir(os.path.join(ref, "src")):
+    ref = os.environ.get("RPT_REFERENCE", "")
+    if ref and os.path.isdir(os.path.join(ref, "src")):
         # the committed patch is what the generator produces, and it applies
         import tempfile
         import shutil
@@ -170,17 +170,28 @@ def test_patch_covers_the_closed_shape_set_and_is_current():
 
 
 def test_committed_patch_is_what_the_generator_makes_today(tmp_path):
-    """rust/rpt.patch regenerated from the reference checkout and rust/rpt_additions/ equals the committed file: an edit
-    of gpu.rs / rng.rs / dump_golden.rs (or of the generator) without re-running make_patch.py is caught here, and so is
-    a reference whose anchors moved.  (No reference checkout — the GPU box — nothing to regenerate from: skipped.)"""
-    ref = "/root/reference"
-    if not os.path.isdir(os.path.join(ref, "src")):
-        pytest.skip("no reference checkout here")
+    """The files the committed rust/rpt.patch creates are rust/rpt_additions/ as they are: an edit of gpu.rs / rng.rs /
+    dump_golden.rs without re-running make_patch.py is caught here.  With a reference checkout named by $RPT_REFERENCE,
+    the whole patch regenerated from it equals the committed file too, which also catches an edit of the generator and a
+    reference whose anchors moved (the reference's sources are not part of this repository)."""
+    patch = open(os.path.join(ROOT, "rust", "rpt.patch")).read()
+    created = {}
+    for m in re.finditer(r"^diff -ruN a/(\S+) b/\S+\n--- .*\n\+\+\+ .*\n@@ -0,0 \+1,(\d+) @@\n", patch, flags=re.M):
+        lines = patch[m.end():].split("\n")[:int(m.group(2))]
+        assert all(l.startswith("+") for l in lines), m.group(1)
+        created[m.group(1)] = "\n".join(l[1:] for l in lines) + "\n"
+    assert sorted(created) == ["examples/dump_golden.rs", "src/gpu.rs", "src/rng.rs"], sorted(created)
+    for rel, text in created.items():
+        assert text == open(os.path.join(ROOT, "rust", "rpt_additions", os.path.basename(rel))).read(), \
+            "rust/rpt.patch is stale for %s: run `python rust/make_patch.py <reference checkout>`" % rel
+    ref = os.environ.get("RPT_REFERENCE", "")
+    if not (ref and os.path.isdir(os.path.join(ref, "src"))):
+        return
     out = str(tmp_path / "rpt.patch")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "rust", "make_patch.py"), ref, out], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     fresh, committed = open(out).read(), open(os.path.join(ROOT, "rust", "rpt.patch")).read()
-    assert fresh == committed, "rust/rpt.patch is stale: run `python rust/make_patch.py /root/reference`"
+    assert fresh == committed, "rust/rpt.patch is stale: run `python rust/make_patch.py %s`" % ref
 
 
 def test_philox_stream_of_the_patch_is_the_oracles(oracle):
