@@ -439,6 +439,52 @@ int rptgpu_buffer_variance(rptgpu_buffer* b, double* out_variance);
 /* number of add_samples calls so far */
 int rptgpu_buffer_num_batches(const rptgpu_buffer* b, uint32_t* out);
 
+/* ---- particle systems: the reference's `rpt::ode` (src/ode.rs, src/ode/particle_system.rs) on the device.
+ * Additions within ABI version 7: no earlier struct or signature changed, so a caller detects them by symbol
+ * (dlsym "rptgpu_particles_integrate"), not by version.
+ * A state is n particles: pos and vel are n*3 doubles (x, y, z per particle), as ParticleState's two Vec<DVec3>.
+ * Every result is bit-identical to the reference's f64 arithmetic in its order of operations.
+ * RPTGPU_E_INVALID_ARGUMENT: a NULL pointer with n > 0, n > RPT_PARTICLES_MAX_N, an unknown kind or flag, both
+ * schedule flags, a forced single-workgroup schedule with n > RPT_PARTICLES_SINGLE_MAX, a time that is not finite, a
+ * step that is not finite and > 0, or a (time, step) whose schedule never ends or has more than
+ * RPT_PARTICLES_MAX_STEPS steps — the reference loops for ever on step <= 0 and on any step for which
+ * `time - step == time` (time = 1, step = 1e-17); the library counts the steps with the reference's own f64
+ * decrements before anything runs.  n == 0 returns RPTGPU_OK (after the checks of time and step).  There is no CPU
+ * fallback: without a device the entry points return RPTGPU_E_NO_DEVICE. */
+enum {
+  RPT_PARTICLES_SOLID_GRAVITY = 0, /* SolidGravitySystem (particle_system.rs:42-62)                        */
+  RPT_PARTICLES_MARBLES = 1,       /* MarblesSystem { radius } (particle_system.rs:64-127)                 */
+  RPT_PARTICLES_CIRCLE = 2         /* SimpleCircleSystem, the reference's test system (:27-40)             */
+};
+enum {
+  RPT_PARTICLES_FLAG_SINGLE_GROUP = 1u, /* force one workgroup for the whole call (state in LDS and registers) */
+  RPT_PARTICLES_FLAG_GRID = 2u,         /* force one launch per RK4 stage over a grid of workgroups            */
+  RPT_PARTICLES_SINGLE_MAX = 2048,      /* the most particles the single-workgroup schedule takes; by default it
+                                           runs for n <= 256 and the grid schedule above that                  */
+  RPT_PARTICLES_MAX_N = 715827882,      /* the most particles (points, arguments) of any call: INT_MAX / 3      */
+  RPT_PARTICLES_MAX_STEPS = 67108864    /* the most RK4 steps one rk4_integrate call may take (2^26)           */
+};
+typedef struct RptParticleSystem {
+  uint32_t kind;  /* RPT_PARTICLES_* */
+  uint32_t flags; /* RPT_PARTICLES_FLAG_*, 0 = choose by n */
+  double radius;  /* MarblesSystem::radius; ignored by the other kinds */
+} RptParticleSystem;
+/* ParticleSystem::time_derivative: out_dpos = vel, out_dvel = the accelerations (n*3 doubles each). */
+int rptgpu_particles_time_derivative(int device, const RptParticleSystem* sys, uint64_t n, const double* pos,
+                                     const double* vel, double* out_dpos, double* out_dvel);
+/* ParticleSystem::rk4_integrate(&mut state, time, step) (particle_system.rs:10-24) — named without the digit so that
+ * it reads as one identifier to every symbol scanner of the header: pos and vel are updated in
+ * place.  The state is copied to the device once and back once, whatever the number of steps. */
+int rptgpu_particles_integrate(int device, const RptParticleSystem* sys, uint64_t n, double* pos, double* vel,
+                                   double time, double step);
+/* MonomialSurface { height, exp: 4 }::closest_point (monomial_surface.rs:126-152) with the grid x = i / steps,
+ * i = -steps..=steps (steps = 100 is closest_point, 10000 closest_point_precise): out = n*3 doubles. */
+int rptgpu_monomial_closest_point(int device, double height, uint32_t steps, uint64_t n, const double* points,
+                                  double* out);
+/* diagnostics: the device's restatement of the platform libm's hypot (glibc 2.35, dbl-64), which closest_point uses for
+ * x.hypot(z), evaluated for n argument pairs (host arrays) so that tests can compare it with the host's. */
+int rptgpu_particles_eval_hypot(int device, uint64_t n, const double* x, const double* y, double* out);
+
 /* ---- accounting ---- */
 int rptgpu_get_stats(const rptgpu_scene* h, RptStats* out);
 int rptgpu_reset_stats(rptgpu_scene* h);

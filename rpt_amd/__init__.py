@@ -3,8 +3,9 @@
 `from rpt_amd import *` gives the names a user of the reference crate has after
 `use rpt::*` (reference src/lib.rs:9-21) for everything on the path:
 Scene, Object, Light, Material, Camera, Renderer, Buffer, Filter, Environment, Hdri,
-sphere, plane, cube, polygon, Mesh, KdTree, Triangle, Transformed, hex_color, color_bytes.
-The path tracer itself is HIP (rpt_amd/csrc) behind the C ABI in include/rpt_gpu.h.
+sphere, plane, cube, polygon, Mesh, KdTree, Triangle, Transformed, hex_color, color_bytes,
+and rpt::ode's ParticleState, ParticleSystem, SolidGravitySystem, MarblesSystem.
+The path tracer and the particle systems are HIP (rpt_amd/csrc) behind the C ABI in include/rpt_gpu.h.
 """
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401
@@ -17,6 +18,7 @@ from .io import load_mtl, load_obj, load_obj_with_mtl, load_stl  # noqa: F401
 from .light import Light  # noqa: F401
 from .material import Material  # noqa: F401
 from .object import Object  # noqa: F401
+from .ode import MarblesSystem, ParticleState, ParticleSystem, SolidGravitySystem  # noqa: F401
 from .renderer import Renderer  # noqa: F401
 from .scene import Scene  # noqa: F401
 from . import scenes  # noqa: F401

@@ -34,6 +34,12 @@ RPT_FLAG_GENERAL_TRAVERSAL = 4
 RPT_FLAG_PERSISTENT = 8
 RPT_K_RAYGEN, RPT_K_EXTEND, RPT_K_SHADE, RPT_K_SHADOW, RPT_K_RESOLVE, RPT_K_PATHS, RPT_K_TREE_TRACE, RPT_K_TREE_SORT = range(8)
 RPT_K_COUNT = 8
+RPT_PARTICLES_SOLID_GRAVITY, RPT_PARTICLES_MARBLES, RPT_PARTICLES_CIRCLE = range(3)
+RPT_PARTICLES_FLAG_SINGLE_GROUP = 1
+RPT_PARTICLES_FLAG_GRID = 2
+RPT_PARTICLES_SINGLE_MAX = 2048
+RPT_PARTICLES_MAX_N = 715827882
+RPT_PARTICLES_MAX_STEPS = 1 << 26
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -131,6 +137,11 @@ class RptKdTree(C.Structure):
                 ("refs", C.POINTER(C.c_uint32))]
 
 
+class RptParticleSystem(C.Structure):
+    """include/rpt_gpu.h RptParticleSystem (the reference's rpt::ode systems; detected by symbol within ABI 7)."""
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("radius", f64)]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -170,6 +181,12 @@ SYMBOLS = [
     ("rptgpu_get_stats", C.c_int, [_VP, C.POINTER(RptStats)]),
     ("rptgpu_reset_stats", C.c_int, [_VP]),
     ("rptgpu_kernel_name", C.c_char_p, [C.c_int]),
+    ("rptgpu_particles_time_derivative", C.c_int,
+     [C.c_int, C.POINTER(RptParticleSystem), C.c_uint64, _PD, _PD, _PD, _PD]),
+    ("rptgpu_particles_integrate", C.c_int,
+     [C.c_int, C.POINTER(RptParticleSystem), C.c_uint64, _PD, _PD, f64, f64]),
+    ("rptgpu_monomial_closest_point", C.c_int, [C.c_int, f64, C.c_uint32, C.c_uint64, _PD, _PD]),
+    ("rptgpu_particles_eval_hypot", C.c_int, [C.c_int, C.c_uint64, _PD, _PD, _PD]),
 ]
 
 

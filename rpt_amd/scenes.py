@@ -541,3 +541,96 @@ SCENES = {"room23": polygon_room, "sphere": sphere_scene, "cornell": cornell, "d
           "fractal_teapots": fractal_teapots, "basic": basic, "monomial_glass": monomial_glass, "spheres": spheres, "compound": compound,
           "teapot": teapot, "cylinder": cylinder, "rustacean": rustacean, "pegasus": pegasus, "metal": metal,
           "simple_video": simple_video}
+
+
+# ----------------------------------------------------------------------------- examples/marbles.rs (rpt::ode)
+MARBLES_N = 25     # marbles.rs:34
+MARBLES_R = 0.15   # marbles.rs:51
+MARBLES_COLORS = (0x264653, 0x2A9D8F, 0xE9C46A, 0xF4A261, 0xE76F51)  # marbles.rs:82
+
+
+def marbles_start(seed=123):
+    """The example's start state (marbles.rs:35-50): a 5 x 5 layout at x, z = (i / 5) / 5 - 0.375, (i % 5) / 5 - 0.375,
+    at rest, at heights drawn from [4, 6).  Stand-in: the heights are a fixed seeded numpy draw, not rand's
+    StdRng::seed_from_u64(123) stream."""
+    from .ode import ParticleState
+    heights = np.random.default_rng(seed).uniform(4.0, 6.0, MARBLES_N)
+    pos = [((i // 5) / 5.0 - 0.375, float(heights[i]), (i % 5) / 5.0 - 0.375) for i in range(MARBLES_N)]
+    return ParticleState(pos, np.zeros((MARBLES_N, 3)))
+
+
+_LIBM = None
+
+
+def _libm_hypot(x, y):
+    """the platform libm's hypot, which Rust's f64::hypot calls (Python's math.hypot is CPython's own and differs from
+    glibc's on about 0.6 % of arguments)"""
+    global _LIBM
+    if _LIBM is None:
+        import ctypes
+        import ctypes.util
+        _LIBM = ctypes.CDLL(ctypes.util.find_library("m"))
+        _LIBM.hypot.restype = ctypes.c_double
+        _LIBM.hypot.argtypes = [ctypes.c_double, ctypes.c_double]
+    return _LIBM.hypot(x, y)
+
+
+def marbles_closest_point_precise(point, height=2.0, steps=10000):
+    """MonomialSurface { height, exp: 4 }::closest_point_precise (monomial_surface.rs:155-181) for the marbles' push-out:
+    px = x.hypot(z) through the platform libm, the first strict minimum over the grid (a NaN distance never taken,
+    best_x = -1 when nothing beats 1e18), and IEEE divisions for the normalised (x, z)."""
+    x, y, z = (float(c) for c in point)
+    if math.sqrt((x * x + y * y) + z * z) < 1e-12:
+        return (x, y, z)
+    px, py = _libm_hypot(x, z), y
+    xf = np.arange(-steps, steps + 1, dtype=np.float64) / float(steps)
+    x4 = (xf * xf) * (xf * xf)
+    with np.errstate(over="ignore", invalid="ignore"):
+        dx, dy = px - xf, py - height * x4
+        d2 = dx * dx + dy * dy
+    d2 = np.where(np.isnan(d2), np.inf, d2)
+    i = int(np.argmin(d2))  # the first occurrence of the minimum = the first strict minimum of the sequential scan
+    best_x = float(xf[i]) if d2[i] < 1e18 else -1.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n = np.float64(math.sqrt(x * x + z * z))
+        qx, qz = best_x * float(np.float64(x) / n), best_x * float(np.float64(z) / n)
+    r2 = qx * qx + qz * qz
+    return (qx, height * (r2 * r2), qz)
+
+
+def marbles(state, hdri_size=(2048, 1024), mesh=None, test=False):
+    """One frame of examples/marbles.rs:58-126 for the particle state `state` (a ParticleState of the marbles).
+    Stand-ins, as for the other examples: the analytic monomial_surface(2, 4) for monomial.obj (or `mesh`, or the asset
+    through $RPT_ASSETS), synthetic_hdri for ballroom_8k.hdr.  Each marble is pushed out of the glass by
+    closest_point_precise (marbles_closest_point_precise: libm's hypot, as the reference) and clamped to the table, as
+    the example does before it renders.  `test`: the example's
+    TEST = true branch (an ambient light, 200 x 150, 7 bounces, 1 spp).  The example rebuilds the scene every frame."""
+    scene = Scene()
+    if not test:
+        scene.environment = Environment.Hdri(synthetic_hdri(*hdri_size))
+        scene.add(Light.Object(Object(sphere().scale((1.5, 1.5, 1.5)).translate((0.0, 5.0, 0.0)))
+                               .material(Material.light(hex_color(0xFFFFFF), 15.0))))
+    else:
+        scene.add(Light.Ambient((0.01, 0.01, 0.01)))
+    if mesh is None:
+        mesh = load_asset("monomial.obj")
+    surface = mesh.scale((1.0, 1.0, 1.0)) if mesh is not None else monomial_surface(2.0, 4.0)
+    scene.add(Object(surface).material(Material.clear(1.5, 0.0001)))
+    R = MARBLES_R
+    for i in range(len(state.pos)):
+        pos = [float(c) for c in state.pos[i]]
+        closest = marbles_closest_point_precise(pos)
+        vec = [pos[k] - closest[k] for k in range(3)]
+        length = math.sqrt((vec[0] * vec[0] + vec[1] * vec[1]) + vec[2] * vec[2])
+        if length < R * 1.05:
+            with np.errstate(divide="ignore", invalid="ignore"):  # glm::normalize of a zero vector is NaN
+                pos = [closest[k] + float(np.float64(vec[k]) / np.float64(length)) * R * 1.05 for k in range(3)]
+        pos[1] = pos[1] if pos[1] >= R - 0.06 else R - 0.06  # f64::max: a NaN gives the other operand
+        scene.add(Object(sphere().scale((R, R, R)).translate(tuple(pos)))
+                  .material(Material.specular(hex_color(MARBLES_COLORS[i % len(MARBLES_COLORS)]), 0.1)))
+    scene.add(Object(polygon([(20.0, -0.06, 20.0), (20.0, -0.06, -20.0), (-20.0, -0.06, -20.0), (-20.0, -0.06, 20.0)]))
+              .material(Material.diffuse(hex_color(0xAAAAAA))))
+    camera = Camera.look_at((0.0, 1.0, 6.0), (0.0, 1.0, 0.0), (0.0, 1.0, 0.0), math.pi / 4.0).focus((0.0, 1.0, 0.0), 0.02)
+    if test:
+        return scene, camera, dict(width=200, height=150, max_bounces=7, num_samples=1)
+    return scene, camera, dict(width=800, height=600, max_bounces=9, num_samples=2000)

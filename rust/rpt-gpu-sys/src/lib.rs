@@ -53,6 +53,14 @@ pub mod ffi {
     pub const RPT_COLLECTIVE_GATHER: u32 = 1;
     pub const RPT_COLLECTIVE_REDUCE: u32 = 2;
     pub const RPT_K_COUNT: usize = 8;
+    pub const RPT_PARTICLES_SOLID_GRAVITY: u32 = 0;
+    pub const RPT_PARTICLES_MARBLES: u32 = 1;
+    pub const RPT_PARTICLES_CIRCLE: u32 = 2;
+    pub const RPT_PARTICLES_FLAG_SINGLE_GROUP: u32 = 1;
+    pub const RPT_PARTICLES_FLAG_GRID: u32 = 2;
+    pub const RPT_PARTICLES_SINGLE_MAX: u64 = 2048;
+    pub const RPT_PARTICLES_MAX_N: u64 = 715827882;
+    pub const RPT_PARTICLES_MAX_STEPS: u64 = 67108864;
     pub const RPTGPU_UNIQUE_ID_BYTES: usize = 128;
 
     /// `Material` (rpt src/material.rs:8-26)
@@ -238,6 +246,15 @@ pub mod ffi {
         pub refs: *mut u32,
     }
 
+    /// `RptParticleSystem` (the reference's `rpt::ode` systems; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptParticleSystem {
+        pub kind: u32,
+        pub flags: u32,
+        pub radius: f64,
+    }
+
     /// opaque `rptgpu_scene`
     #[repr(C)]
     pub struct rptgpu_scene {
@@ -281,6 +298,10 @@ pub mod ffi {
         pub fn rptgpu_get_stats(h: *const rptgpu_scene, out: *mut RptStats) -> c_int;
         pub fn rptgpu_reset_stats(h: *mut rptgpu_scene) -> c_int;
         pub fn rptgpu_kernel_name(k: c_int) -> *const c_char;
+        pub fn rptgpu_particles_time_derivative(device: c_int, sys: *const RptParticleSystem, n: u64, pos: *const f64, vel: *const f64, out_dpos: *mut f64, out_dvel: *mut f64) -> c_int;
+        pub fn rptgpu_particles_integrate(device: c_int, sys: *const RptParticleSystem, n: u64, pos: *mut f64, vel: *mut f64, time: f64, step: f64) -> c_int;
+        pub fn rptgpu_monomial_closest_point(device: c_int, height: f64, steps: u32, n: u64, points: *const f64, out: *mut f64) -> c_int;
+        pub fn rptgpu_particles_eval_hypot(device: c_int, n: u64, x: *const f64, y: *const f64, out: *mut f64) -> c_int;
     }
 }
 
@@ -631,6 +652,7 @@ mod layout_tests {
         assert_eq!(size_of::<RptSceneOptions>(), 112);
         assert_eq!(size_of::<RptStats>(), 200);
         assert_eq!(size_of::<RptKdTree>(), 64);
+        assert_eq!(size_of::<RptParticleSystem>(), 16);
     }
 
     #[test]
