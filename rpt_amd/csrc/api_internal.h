@@ -3,7 +3,7 @@
 //   api_common.cpp   errors, the RCCL loader, kernel tables, version / strerror / stats
 //   api_scene.cpp    RptSceneOptions, rptgpu_scene_create[_opts] (flattening, routing, upload), the kd-tree entry points
 //   api_render.cpp   workspace, the wavefront loop and the persistent launch (render_impl), render_batch[_device],
-//                    rptgpu_closest_hit, rptgpu_eval_math
+//                    rptgpu_closest_hit, rptgpu_eval_math; their launch and pass sizes come from render_plan.h
 //   api_comm.cpp     communicator, rptgpu_render_batch_reduce (the library-owned exchange and its failure paths),
 //                    rptgpu_render_batch_emulate_ranks
 //   api_buffer.cpp   the device-resident Buffer

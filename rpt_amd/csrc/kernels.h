@@ -4,14 +4,13 @@
 #include <stdint.h>
 
 #include "device_types.h"
+#include "launch_limits.h"
 
 // meshes per batched run of the flat path kernel (kernels/paths.inc flat_query; api_scene.cpp caps Inst::plane_use with it)
 #ifndef RPT_FLAT_RUN
 #define RPT_FLAT_RUN 6
 #endif
 
-// slots (of REC_FIELDS doubles) per thread of the persistent path kernel's record ring (kernels/paths.inc says why)
-static inline uint32_t rpt_fold_ring_slots(uint32_t max_bounces) { return 3u * max_bounces + 2u; }
 // LDS of one wave of rpt_paths: 160 KB per CU / (2 waves per SIMD x 4 SIMDs); the fold walker's static share of it
 #define RPT_PATHS_WAVE_LDS 20480u
 #define RPT_PATHS_WALKER_LDS 2560u
@@ -23,23 +22,10 @@ static inline uint32_t rpt_fold_ring_slots(uint32_t max_bounces) { return 3u * m
 #define RPT_PARK_K 4
 #endif
 #define RPT_PATHS_PARK_LDS (RPT_PARK_K * 2624u)
-// rpt_paths's 32-bit work counter: a wave's last claim may overshoot the end by its batch (kernels/paths.inc fetch_item), so
-// a caller's RptSceneOptions::paths_batch is capped, and api_render.cpp leaves WAVES_PER_CU_MAX x (64 + BATCH_MAX) items of room
-// per CU (one-wave blocks: the occupancy query's answer is clamped to the same bound)
-// the wavefront pipeline's passes: at most this many paths in flight (32-bit slot indices, queue counters and grids have
-// room for 2^31), and at most this share of the device's free memory for their state
-#ifndef RPT_MAX_PATHS_PER_PASS
-#define RPT_MAX_PATHS_PER_PASS (512ull << 20)
-#endif
-#ifndef RPT_WS_FREE_PERCENT
-#define RPT_WS_FREE_PERCENT 85
-#endif
 // the paths of a depth are re-ordered by ray key in scenes without per-tree queues when there are at least this many
 #ifndef RPT_PATH_REORDER_MIN
 #define RPT_PATH_REORDER_MIN (1u << 20)
 #endif
-#define RPT_PATHS_BATCH_MAX 1024u
-#define RPT_PATHS_WAVES_PER_CU_MAX 32u
 
 // layout of the flat path kernel's dynamic LDS (byte offsets; lrec at 0), see kernels.inc
 struct FlatLayout {

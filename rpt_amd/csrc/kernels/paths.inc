@@ -32,7 +32,7 @@
 // record and, whenever U > 0, folds one, so U + C <= max_bounces (+1 inside an iteration).  Slots between the
 // walker's path and the write position: the walker's own path (<= max_bounces + 1, part of it already folded),
 // the waiting paths' records and headers (each waits with >= 1 record: <= 2 U), the running path (C + 1)
-// — <= 3 max_bounces + 2 = rpt_fold_ring_slots() (kernels.h; api_render.cpp sizes the buffer with it).
+// — <= 3 max_bounces + 2 = rpt_fold_ring_slots() (launch_limits.h; api_render.cpp sizes the buffer with it).
 //
 // Environment lookups are PARKED (round 5; flat scenes whose environment is a texture).  A ray that escapes ends its
 // path with Hdri::get_color (environment.rs:25-52: atan2, acos, four texels) — one round of it per loop iteration for

@@ -1,0 +1,172 @@
+// render_plan.h — how a render call is cut into launches (persistent pipeline) and passes (wavefront pipeline): the
+// arithmetic behind api_render.cpp's drivers, as pure host functions of numbers (tests/cpp/render_plan_check.cpp).
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "device_types.h"
+#include "launch_limits.h"
+
+namespace rptplan {
+
+// the work items of a launch of spp samples per pixel, chunk samples per item
+inline uint64_t work_items(uint32_t npix, uint32_t spp, uint32_t chunk) { return (uint64_t)npix * ((spp + chunk - 1) / chunk); }
+
+// ---- persistent pipeline (rpt_paths): a batch runs as n_launch launches of spp_l samples each
+struct PersistentPlan {
+  uint32_t n_launch, spp_l, chunk; // launches, samples per pixel of each, samples per work item
+  int per_cu;                      // one-wave blocks per CU
+  uint64_t n_items;                // work items of a launch of spp_l samples
+  uint32_t nblocks;
+};
+
+// per_cu: the occupancy query's answer; lbuf_cap: the cap on the per-sample radiance buffer (RPTGPU_LBUF_BYTES), lbuf_held:
+// its bytes already allocated, free_bytes: the device's free memory (< 0: unknown); paths_chunk: RptSceneOptions::paths_chunk;
+// all_flat, obj_filter: the scene is flat and runs the object filter; force_general: RPT_FLAG_GENERAL_TRAVERSAL
+inline PersistentPlan plan_persistent(uint32_t npix, uint32_t iterations, uint32_t max_bounces, int cus, int per_cu,
+                                      uint64_t lbuf_cap, uint64_t lbuf_held, int64_t free_bytes, uint32_t paths_chunk,
+                                      bool all_flat, bool force_general, bool obj_filter) {
+  PersistentPlan pl{};
+  // one launch's per-sample radiance buffer (24 B per sample) stays under the cap: 512 spp at 1080p = 25.5 GB = one
+  // launch; growing, it leaves half of what is free to everyone else
+  uint64_t lbuf_budget = lbuf_cap;
+  if (lbuf_held < lbuf_budget && free_bytes >= 0)
+    lbuf_budget = std::min<uint64_t>(lbuf_budget, std::max<uint64_t>(lbuf_held, (uint64_t)free_bytes / 2));
+  uint64_t spp_max = std::max<uint64_t>(1, lbuf_budget / ((uint64_t)npix * 3 * sizeof(double)));
+  pl.n_launch = (uint32_t)(((uint64_t)iterations + spp_max - 1) / spp_max);
+  pl.spp_l = pl.n_launch ? (iterations + pl.n_launch - 1) / pl.n_launch : 0;
+  // Samples per work item.  paths_chunk = 0 (the default) chooses: 16 — 2 for flat scenes that run the object filter AND
+  // trace long paths (max_bounces >= 4): there the lanes of a wave drift apart in path length and short items keep a wave
+  // on one 8x8 pixel block and re-balance it often (the 23-polygon room at 8 bounces 617 -> 664 Msamples/s, spheres.rs at
+  // 6 bounces 1899 -> 1981); with one or two segments per path every sample costs the same and the per-item bookkeeping
+  // is all a short item adds (basic.rs 13418 -> 9391, the simple_video frame 111 -> 88 frames/s at 2:
+  // profiles/r05_paths_chunk_ab.txt) — halved while a lane would get fewer than 24 items: the launch's tail is one item
+  // long (a rank that owns an eighth of a 1080p frame at 128 spp: x1.056 of the ideal 1/8 with 16 samples per item, x1.014
+  // with 4; profiles/r05_emulated_ranks.txt).
+  uint32_t chunk = paths_chunk;
+  if (chunk == 0u) {
+    chunk = (all_flat && !force_general && obj_filter && max_bounces >= 4u) ? 2u : 16u;
+    const uint64_t lanes = (uint64_t)std::max(1, cus) * 8u * 64u;
+    while (chunk > 1u && work_items(npix, pl.spp_l, chunk) < 24u * lanes) chunk /= 2u;
+  }
+  chunk = std::max(1u, std::min(chunk, std::max(1u, pl.spp_l)));
+  uint64_t n_items = work_items(npix, pl.spp_l, chunk);
+  // 32-bit work counter: every lane of the grid may ask once past the end, and a wave's last guided claim may reach past
+  // it (kernels/paths.inc fetch_item: at most 64 + 256 dead items per wave), so items + 8 x threads must fit (slack: at
+  // most RPT_PATHS_WAVES_PER_CU_MAX one-wave blocks per CU — per_cu is clamped to it — each with up to 64 askers past the
+  // end and one last claim of at most RPT_PATHS_BATCH_MAX, the cap of a caller's paths_batch)
+  const uint64_t item_limit = 0xFFFFFFF0ull - (uint64_t)cus * RPT_PATHS_WAVES_PER_CU_MAX * (64u + RPT_PATHS_BATCH_MAX);
+  if (n_items > item_limit) {
+    chunk = (uint32_t)(((uint64_t)pl.spp_l * npix + item_limit - 1) / item_limit);
+    while ((n_items = work_items(npix, pl.spp_l, chunk)) > item_limit) chunk++;
+  }
+  pl.chunk = chunk;
+  pl.n_items = n_items;
+  pl.per_cu = std::min(per_cu, (int)RPT_PATHS_WAVES_PER_CU_MAX);
+  pl.nblocks = (uint32_t)std::max(1, cus * pl.per_cu);
+  pl.nblocks = (uint32_t)std::min<uint64_t>(pl.nblocks, std::max<uint64_t>(1, (n_items + 63) / 64));
+  return pl;
+}
+
+// ---- wavefront pipeline: paths in flight per pass.  Late bounces keep few paths alive, and a depth's kernels need ~10^5
+// rays to fill 256 CUs, so the more paths start together the better the deep bounces run (C3 stand-in: 4 Mi -> 71, 16 Mi
+// -> 106, 128 Mi -> 128 Msamples/s; 16k-triangle glass 179 -> 324; round 6, with passes of 85 % of the free memory:
+// 786 -> 913, profiles/r06_pass_size_ab.txt).  288 GB of HBM is what makes that affordable.
+// What a path costs: its slot and one 68-byte COLUMN per depth it reaches (PathState::rec) — as many columns as the
+// depths' queues were long, not (max_bounces + 1) per path: the glass's paths average a quarter of their 17 levels.  How
+// many columns a path needs is measured (the first pass of a handle is one sample per pixel with the full pool) and
+// carried with a margin; a pass whose pool runs out at some depth is started over with fewer paths.
+// a path's slot: ray and next ray, hit, object, draw / path id / parent column twice each, last column, per light the
+// shadow state, queue entry and record time, the per-tree query's queue, row and sort words
+inline uint64_t wavefront_slot_bytes(int num_lights, bool has_deep, bool sort_rays, bool path_reorder) {
+  const uint64_t nl = (uint64_t)std::max(1, num_lights);
+  return 2 * 6 * 8 + 4 * 8 + 4 + 6 * 4 + 4 + nl * rptdev::SHADOW_FIELDS * 8 + nl * (8 + 4) +
+         (has_deep ? 12 + 64 + (sort_rays ? 12 + 16 : 0) : 0) + (path_reorder ? 16 + 16 + 4 : 0);
+}
+// a record column: the record and its parent link
+constexpr uint64_t WAVEFRONT_REC_BYTES = rptdev::REC_FIELDS * 8 + 4;
+
+// columns per path of a pass: measured + 10 % + 0.05, the full (max_bounces + 1) until there is a measurement (rounded up
+// to a twentieth, so that the fourth digit of a pass's average does not resize a 100 GB workspace)
+inline double pass_ratio(double rec_ratio, uint32_t max_bounces) {
+  const double full_ratio = (double)max_bounces + 1.0;
+  return rec_ratio > 0.0 ? std::min(full_ratio, std::ceil((rec_ratio * 1.10 + 0.05) * 20.0) / 20.0) : full_ratio;
+}
+
+struct PassInput {
+  uint32_t npix, iterations, remaining; // pixels, samples of the call, samples still to run
+  double rec_ratio, ratio;   // record columns per path measured so far (0: not yet, this pass measures); pass_ratio() of it
+  uint64_t per_slot;         // wavefront_slot_bytes()
+  uint64_t target_paths;     // paths per pass asked for (RPTGPU_TARGET_PATHS); 0 = from the budget
+  uint64_t budget_bytes;     // the workspace cap (RPTGPU_WS_BYTES)
+  int64_t free_bytes;        // the device's free memory (< 0: unknown) ...
+  uint64_t free_percent;     // ... and the share of it a pass may take
+  uint64_t held_slots, held_cols; // the workspace the handle holds (it counts as available)
+  uint64_t fail_paths;       // the smallest pass (paths) whose workspace did not fit so far; 0 = none
+};
+struct PassPlan {
+  uint64_t target;  // paths per pass
+  uint32_t s_chunk; // samples per pixel of this pass
+  uint32_t s_alloc; // samples per pixel the workspace is made for
+};
+
+inline PassPlan plan_pass(const PassInput& in) {
+  PassPlan pp{};
+  const double per_path = (double)in.per_slot + in.ratio * (double)WAVEFRONT_REC_BYTES;
+  pp.target = in.target_paths;
+  if (!pp.target) {
+    uint64_t budget = in.budget_bytes;
+    if (in.free_bytes >= 0) {
+      const uint64_t have = in.held_slots * in.per_slot + in.held_cols * WAVEFRONT_REC_BYTES;
+      budget = std::min<uint64_t>(budget, ((uint64_t)in.free_bytes + have) / 100 * in.free_percent);
+    }
+    pp.target = std::min<uint64_t>(RPT_MAX_PATHS_PER_PASS, std::max<uint64_t>(1ull << 20, (uint64_t)((double)budget / per_path)));
+  }
+  // a size that did not fit before is not tried again (several handles or processes on one GPU see the same `free`
+  // figure; an explicit target_paths may be more than the device holds): allocating and freeing 100+ GB per call costs
+  // seconds
+  if (in.fail_paths) pp.target = std::min<uint64_t>(pp.target, in.fail_paths / 2);
+  pp.s_chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(in.remaining, pp.target / in.npix));
+  if (in.rec_ratio == 0.0 && in.remaining > 1u && pp.s_chunk > 1u) {
+    pp.s_chunk = 1u; // the measuring pass: one sample per pixel, every path with room for all its levels
+  } else if (pp.s_chunk < in.remaining) {
+    // passes of EQUAL size: 256 spp with room for 123 per pass are three passes of 86 / 85 / 85, not 123 / 123 / 10 (the
+    // deep bounces of a 10-spp pass run on a tenth of the rays)
+    const uint32_t n_pass = (in.remaining + pp.s_chunk - 1) / pp.s_chunk;
+    pp.s_chunk = (in.remaining + n_pass - 1) / n_pass;
+  }
+  // The workspace is made for the pass a call of this size runs once the measurement is in — not for this pass's own
+  // size: the first call's passes are 1 + (n - 1) samples, and a workspace of n - 1 would be freed and made again by the
+  // second call (220 GB: six seconds)
+  pp.s_alloc = pp.s_chunk;
+  if (in.rec_ratio > 0.0) pp.s_alloc = (uint32_t)std::max<uint64_t>(pp.s_chunk, std::min<uint64_t>(in.iterations, pp.target / in.npix));
+  return pp;
+}
+
+// the path slots and record columns of the workspace a pass asks for
+inline uint64_t pass_slots(uint32_t npix, const PassPlan& pp) { return (uint64_t)npix * std::max(pp.s_chunk, pp.s_alloc); }
+inline uint64_t pass_rec_cols(uint64_t np, double ratio) {
+  return std::max<uint64_t>(np, std::min<uint64_t>((uint64_t)std::ceil((double)np * ratio), 0xfffffff0ull));
+}
+
+// the workspace of a pass did not fit (several handles or processes on one GPU each see the same `free` figure): the pass
+// shrinks instead of failing the render (a smaller pass is only slower) — first the room ahead goes, then the pass halves
+inline PassPlan shrink_after_oom(PassPlan pp) {
+  if (pp.s_alloc > pp.s_chunk) pp.s_alloc = pp.s_chunk;
+  else { pp.s_chunk = std::max(1u, pp.s_chunk / 2); pp.s_alloc = pp.s_chunk; }
+  return pp;
+}
+inline uint64_t fail_paths_after_oom(uint64_t fail_paths, uint64_t np) { return fail_paths ? std::min<uint64_t>(fail_paths, np) : np; }
+
+// the columns per path measured: the largest average seen ...
+inline double ratio_after_pass(double rec_ratio, uint64_t cols_used, uint32_t n_paths) { return std::max(rec_ratio, (double)cols_used / (double)n_paths); }
+// ... and after a pass whose pool ran out (cols_seen: the columns up to the depth that did not fit, a lower bound of what
+// it needs): room for half as many again
+inline double ratio_after_restart(double rec_ratio, uint64_t cols_seen, uint32_t n_paths, uint32_t max_bounces) {
+  const double seen = (double)cols_seen / (double)n_paths;
+  return std::min((double)max_bounces + 1.0, std::max(rec_ratio, seen) * 1.5);
+}
+
+} // namespace rptplan

@@ -315,7 +315,7 @@ def test_work_item_pools_are_scheduling_only(name, batch):
 def test_work_counter_ends_within_the_bound_the_host_leaves_room_for(batch, monkeypatch, capfd):
     """The KERNEL's own bookkeeping, not a model of it: rpt_paths's 32-bit work counter after a launch, read back
     by the library (RPTGPU_PRINT_LAUNCH).  Every item is claimed (counter >= items) and the claims past the end stay within
-    waves x (64 askers + one last claim of at most the batch) — what api_render.cpp's item_limit leaves room for below
+    waves x (64 askers + one last claim of at most the batch) — what render_plan.h's item_limit leaves room for below
     2^32; the image being the fixture's says every item was rendered exactly once."""
     import re
     monkeypatch.setenv("RPTGPU_PRINT_LAUNCH", "1")
