@@ -674,6 +674,23 @@ class Renderer {
     samples_done_ += iterations;
     buffer.add_samples(colors);
   }
+  // addition: after the caller has changed the placements (Transformed fields) and materials of the Scene's objects and
+  // lights — not their geometry, counts, kinds or the environment, which need a new Renderer — push all of them into the
+  // scene handle this Renderer already holds (rptgpu_scene_set_objects / _lights): the kd-trees, the workspace and
+  // everything else of the handle stay, and the next render equals that of a new Renderer of the changed Scene.
+  // Before the first render there is no handle yet and nothing to push.
+  void update_scene() {
+    if (!handle_) return;
+    Arena arena;
+    std::vector<RptObject> objs;
+    std::vector<RptLight> lights;
+    lower_lists(arena, objs, lights);
+    std::vector<uint32_t> oi(objs.size()), li(lights.size());
+    for (size_t i = 0; i < oi.size(); i++) oi[i] = (uint32_t)i;
+    for (size_t i = 0; i < li.size(); i++) li[i] = (uint32_t)i;
+    check(rptgpu_scene_set_objects(handle_, objs.size(), oi.data(), objs.data()));
+    check(rptgpu_scene_set_lights(handle_, lights.size(), li.data(), lights.data()));
+  }
 
  private:
   void check(int code) {
@@ -684,12 +701,8 @@ class Renderer {
       throw GpuError(code, msg);
     }
   }
-  void ensure_scene() {
-    if (handle_) return;
-    Arena arena;
-    std::vector<RptObject> objs;
+  void lower_lists(Arena& arena, std::vector<RptObject>& objs, std::vector<RptLight>& lights) const {
     for (const Object& o : scene_.objects) objs.push_back({o.shape.lower(arena), o.material_.lower()});
-    std::vector<RptLight> lights;
     for (const Light& l : scene_.lights) {
       RptLight r{};
       r.kind = l.kind;
@@ -698,6 +711,13 @@ class Renderer {
       if (l.kind == RPT_LIGHT_OBJECT) r.object = {l.object->shape.lower(arena), l.object->material_.lower()};
       lights.push_back(r);
     }
+  }
+  void ensure_scene() {
+    if (handle_) return;
+    Arena arena;
+    std::vector<RptObject> objs;
+    std::vector<RptLight> lights;
+    lower_lists(arena, objs, lights);
     RptScene s{};
     s.objects = objs.data(); s.num_objects = objs.size();
     s.lights = lights.data(); s.num_lights = lights.size();

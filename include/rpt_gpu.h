@@ -320,6 +320,28 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
  * ITS struct before the call (rptgpu_scene_options_default[_sized] leaves it set); exactly that many bytes are written. */
 int rptgpu_scene_get_options(const rptgpu_scene* h, RptSceneOptions* out);
 
+/* ---- live updates of a handle's scene: the objects' and lights' placements and materials, for animation (a frame loop
+ * keeps one handle instead of creating one per frame).  Additions within ABI version 7, detected by symbol (dlsym
+ * "rptgpu_scene_set_objects").  After an update every result — frames, rptgpu_closest_hit, rptgpu_buffer_* — is
+ * bit-identical to what a handle freshly created from the updated scene gives.  The kd-trees, triangles, environment
+ * texels, routing and workspace (with what it has learned) stay; device buffers (rptgpu_buffer) and the communicator
+ * of the handle stay valid.  The object, light and environment counts and all geometry are fixed at creation: for new
+ * geometry create a new handle.
+ * Both calls are all or nothing: every entry is checked before anything changes, and a refused call leaves the handle
+ * rendering what it rendered before.  RPTGPU_E_INVALID_ARGUMENT, with a detail naming the entry and the reason: an
+ * index out of range, an index named twice in one call, a shape or light kind or a `transformed` flag that differs
+ * from the one at creation (an untransformed mesh lives in the flat kernel's plane table), a material whose specular
+ * lobe probability lies outside [0, 1] (as rptgpu_scene_create refuses it), a NULL array with n > 0, an abandoned
+ * handle.  A call returns after its uploads on the handle's stream have completed.  Do not call them concurrently
+ * with a render, a buffer sample or another call on the same handle.  n == 0 is a no-op. */
+/* Replace top-level object index[i] with objects[i] (its shape's Transformed fields and its material).
+ * The shape's geometry (triangles, children, plane, monomial parameters) is NOT read: it stays what the handle
+ * was created with.  objects[i].shape.kind and .transformed must equal the object's at creation. */
+int rptgpu_scene_set_objects(rptgpu_scene* h, uint64_t n, const uint32_t* index, const RptObject* objects);
+/* Same for scene.lights: colour / vector of Point, Directional, Ambient; xf + material of Light::Object.
+ * kind must be unchanged; a Light::Object's shape geometry is not read. */
+int rptgpu_scene_set_lights(rptgpu_scene* h, uint64_t n, const uint32_t* index, const RptLight* lights);
+
 /* ---- the hot path: replaces the body of Renderer::sample (renderer.rs:117-129).
  * Writes out_rgb[(y*width+x)*3+c] = mean over `iterations` paths of pixel (x,y), times
  * 2^exposure_value (renderer.rs:141); y = 0 is the top row (renderer.rs:134).  The host then

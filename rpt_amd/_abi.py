@@ -156,6 +156,8 @@ SYMBOLS = [
     ("rptgpu_scene_options_default_sized", C.c_int, [C.POINTER(RptSceneOptions), C.c_uint32]),
     ("rptgpu_scene_create_opts", C.c_int, [C.POINTER(RptScene), C.c_int, C.POINTER(RptSceneOptions), C.POINTER(_VP)]),
     ("rptgpu_scene_get_options", C.c_int, [_VP, C.POINTER(RptSceneOptions)]),
+    ("rptgpu_scene_set_objects", C.c_int, [_VP, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(RptObject)]),
+    ("rptgpu_scene_set_lights", C.c_int, [_VP, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(RptLight)]),
     ("rptgpu_render_batch", C.c_int, [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams), _PD]),
     ("rptgpu_render_batch_device", C.c_int,
      [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams), _VP, C.c_int, _VP]),

@@ -167,6 +167,11 @@ struct rptgpu_scene {
   DevBuf<uint32_t> gen_overflow;
   uint32_t gen_threads = 0;
   std::vector<rptdev::Light> host_lights; // (what launch decisions need of the lights)
+  // what rptgpu_scene_set_objects / _lights recompute from (api_scene.cpp): host copies of what they change, and what
+  // creation knew of each object's geometry
+  std::vector<rptdev::Inst> top_insts;    // insts[0, num_objects + Light::Object shapes) as on the device
+  std::vector<rptdev::Material> host_materials;
+  std::vector<rpthost::ObjectGeom> obj_geom;
   std::vector<uint32_t> cnt_host;  // the per-depth counters read back from the device
   bool has_deep = false;
   int rays_in_kernel = 0;          // RPTGPU_RAYS_IN_KERNEL: rptgpu_closest_hit keeps to rpt_extend_rays also when the scene has deep trees
@@ -235,6 +240,8 @@ const KernelTable* table_for(uint32_t mode, bool ext = false);
 extern const char* const BAD_MODE;
 
 // api_render.cpp
+// StackSpill::zeros_common of a scene with these lights (scheduling: which kernel takes rays with a zero component)
+uint32_t zeros_common(const std::vector<rptdev::Light>& lights);
 void ensure_partition(rptgpu_scene* h, const RptRenderParams& p);
 std::vector<uint32_t> pixel_list(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, uint32_t pi, uint32_t pc);
 const char* bad_params(const RptRenderParams* p);

@@ -143,6 +143,12 @@ void ensure_sort_bufs(rptgpu_scene* h, uint64_t cap) {
   h->sort_bufs = SortBufs{h->sort_kin.p, h->sort_kout.p, h->sort_vin.p, h->sort_tmp.p, bytes};
 }
 
+uint32_t zeros_common(const std::vector<rptdev::Light>& lights) {
+  for (const rptdev::Light& l : lights) // every shadow ray towards an axis-parallel directional light has a zero component
+    if (l.kind == RPT_LIGHT_DIRECTIONAL && (l.vec[0] == 0.0 || l.vec[1] == 0.0 || l.vec[2] == 0.0)) return 1;
+  return 0;
+}
+
 // cap: path slots; rec_cols: columns of the depth-record pool (PathState::rec: one per path and depth REACHED)
 void ensure_workspace(rptgpu_scene* h, uint64_t cap, uint64_t rec_cols) {
   if (cap <= h->ws_cap && rec_cols <= h->ws_rec_cols && h->ray.p) return;
@@ -177,11 +183,9 @@ void ensure_workspace(rptgpu_scene* h, uint64_t cap, uint64_t rec_cols) {
       const uint64_t threads = (uint64_t)std::max(1, h->num_cus * 4) / 4 * RPT_TT_WAVES * 256;
       const uint64_t levels = (uint64_t)(std::max<uint32_t>((uint32_t)rptdev::KD_MAX_STACK, h->max_tree_depth + 1u) - RPT_TT_LEVELS_MIN);
       h->spill_node.alloc(levels * threads); h->spill_ts.alloc(levels * threads); h->spill_bmax.alloc(levels * threads);
-      uint32_t zeros_common = 0; // every shadow ray towards an axis-parallel directional light has a zero component
-      for (const rptdev::Light& l : h->host_lights)
-        if (l.kind == RPT_LIGHT_DIRECTIONAL && (l.vec[0] == 0.0 || l.vec[1] == 0.0 || l.vec[2] == 0.0)) zeros_common = 1;
       h->tree_rays.alloc(8 * cap); // one 64-byte row per position of a query: the rays that enter a tree (StackSpill::rays)
-      h->spill = StackSpill{h->spill_node.p, h->spill_ts.p, h->spill_bmax.p, (uint32_t)threads, zeros_common, h->tree_rays.p};
+      h->spill = StackSpill{h->spill_node.p, h->spill_ts.p, h->spill_bmax.p, (uint32_t)threads, zeros_common(h->host_lights),
+                            h->tree_rays.p};
     }
     ensure_generic(h, h->gen_all);
     if (h->sort_rays) ensure_sort_bufs(h, cap);

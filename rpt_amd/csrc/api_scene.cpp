@@ -387,6 +387,9 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
     for (const rptdev::Inst& in : fs.insts) h->ext_shapes = h->ext_shapes || in.kind == RPT_SHAPE_MONOMIAL;
     for (const rptdev::Light& l : fs.lights) h->light_casts.push_back(l.kind != RPT_LIGHT_AMBIENT ? 1 : 0);
     h->host_lights = fs.lights;
+    h->top_insts.assign(fs.insts.begin(), fs.insts.begin() + fs.num_top_insts);
+    h->host_materials = fs.materials;
+    h->obj_geom = std::move(fs.obj_geom);
     h->insts.upload(fs.insts, h->stream);
     h->trees.upload(fs.trees, h->stream);
     h->nodes.upload(fs.nodes, h->stream);
@@ -417,6 +420,151 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
 }
 
 void rptgpu_scene_destroy(rptgpu_scene* h) { delete h; }
+
+// ---- live updates: new placements and materials for a handle's objects and lights.  Geometry, counts, the environment,
+// the routing and the workspace stay; every record that creation derives from a placement or a material is derived
+// again by the same functions (host_scene.h: set_transform, convert_material, convert_light, fill_object_boxes) and
+// uploaded, so the handle then holds the bits a fresh handle of the updated scene would.  Audit of what else creation
+// derives from the records these calls change:
+//   * the flat kernel's object filter (boxes, grid, obj_always) — recomputed; stale boxes would drop pixels.  Whether
+//     the filter is on stays as decided at creation (scheduling only; objects it must not filter are in obj_always);
+//   * scene_bounds, the path re-order's key grid — recomputed (kept when the new union is not finite: scheduling only);
+//   * StackSpill::zeros_common (directional lights along an axis) — recomputed (scheduling only);
+//   * the plane table (untransformed meshes only: `transformed` may not change), trees, leaf boxes of group children
+//     (in their group's frame), light_casts and num_shadow_lights (by kind: kinds may not change) — unchanged by
+//     construction.
+} // extern "C"
+
+namespace {
+// the checks both calls make before reading an entry; nullptr when they pass
+const char* update_refusal(const rptgpu_scene* h, uint64_t n, const uint32_t* index, const void* entries) {
+  if (h->abandoned)
+    return "an aborted batch's device work never drained on this handle: it takes no update (destroy it)";
+  if (n && (!index || !entries)) return "null index or entry array";
+  return nullptr;
+}
+// entry k names record i of `count`: in range and not named before in this call; "" when fine
+std::string index_refusal(uint64_t k, uint32_t i, size_t count, std::vector<char>& seen, const char* what) {
+  if (i >= count)
+    return "entry " + std::to_string(k) + ": " + what + " index " + std::to_string(i) + " is out of range (the scene has " +
+           std::to_string(count) + ")";
+  if (seen[i]) return "entry " + std::to_string(k) + ": " + what + " " + std::to_string(i) + " is named twice in one call";
+  seen[i] = 1;
+  return "";
+}
+// the shape of entry k against the record it replaces: same kind, same `transformed`
+std::string shape_refusal(uint64_t k, uint32_t i, const RptShape& s, const rptdev::Inst& was, const char* what) {
+  const std::string at = "entry " + std::to_string(k) + " (" + what + " " + std::to_string(i) + "): ";
+  if (s.kind != was.kind)
+    return at + "shape kind " + std::to_string(s.kind) + " differs from the kind at creation (" + std::to_string(was.kind) +
+           "): new geometry needs a new handle";
+  if ((s.transformed ? 1 : 0) != was.has_xf)
+    return at + "the shape is " + (s.transformed ? "" : "not ") + "Transformed and was " + (was.has_xf ? "" : "not ") +
+           "at creation: an untransformed mesh lives in the flat kernel's plane table, so this needs a new handle";
+  return "";
+}
+// upload what an update changed, wait for the copies, then make the host copies the handle's
+void commit_update(rptgpu_scene* h, std::vector<rptdev::Inst>& insts, std::vector<rptdev::Material>* mats,
+                   std::vector<rptdev::Light>* lights) {
+  HIP_TRY(hipSetDevice(h->device));
+  const hipStream_t st = h->stream;
+  if (!insts.empty())
+    HIP_TRY(hipMemcpyAsync(h->insts.p, insts.data(), insts.size() * sizeof(rptdev::Inst), hipMemcpyHostToDevice, st));
+  if (mats && !mats->empty())
+    HIP_TRY(hipMemcpyAsync(h->materials.p, mats->data(), mats->size() * sizeof(rptdev::Material), hipMemcpyHostToDevice, st));
+  if (lights && !lights->empty())
+    HIP_TRY(hipMemcpyAsync(h->lights.p, lights->data(), lights->size() * sizeof(rptdev::Light), hipMemcpyHostToDevice, st));
+  rpthost::ObjectBounds ob;
+  const bool filter = h->all_flat && h->flat_layout.obj_filter;
+  if (mats) { // the objects moved: the object filter and the scene bounds follow them
+    rpthost::fill_object_boxes(insts, h->obj_geom, ob);
+    if (filter) {
+      HIP_TRY(hipMemcpyAsync(h->obj_box.p, ob.obj_lbox.data(), ob.obj_lbox.size() * sizeof(rptdev::LeafBox),
+                             hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(h->obj_grid.p, ob.obj_grid, sizeof ob.obj_grid, hipMemcpyHostToDevice, st));
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(st)); // (the sources are this call's)
+  h->top_insts.swap(insts);
+  if (mats) {
+    h->host_materials.swap(*mats);
+    if (filter) { // (the filter's LDS layout does not depend on the boxes: only the exemptions change)
+      const size_t n = h->obj_geom.size();
+      h->flat_layout.obj_always = ob.obj_always & (n >= 64 ? ~0ull : (1ull << n) - 1ull);
+    }
+    if (ob.scene_bounds_ok) std::memcpy(h->scene_bounds, ob.scene_bounds, sizeof h->scene_bounds);
+  }
+  if (lights) {
+    h->host_lights.swap(*lights);
+    h->spill.zeros_common = zeros_common(h->host_lights);
+  }
+}
+} // namespace
+
+extern "C" {
+
+int rptgpu_scene_set_objects(rptgpu_scene* h, uint64_t n, const uint32_t* index, const RptObject* objects) {
+  if (!h) return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, "rptgpu_scene_set_objects: null handle");
+  const std::string fn = "rptgpu_scene_set_objects: ";
+  if (const char* why = update_refusal(h, n, index, objects)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + why);
+  try {
+    const size_t count = h->obj_geom.size();
+    std::vector<rptdev::Inst> insts = h->top_insts;
+    std::vector<rptdev::Material> mats = h->host_materials;
+    std::vector<char> seen(count, 0);
+    for (uint64_t k = 0; k < n; k++) { // everything is checked before anything changes
+      const uint32_t i = index[k];
+      std::string why = index_refusal(k, i, count, seen, "object");
+      if (why.empty()) why = shape_refusal(k, i, objects[k].shape, insts[i], "object");
+      if (!why.empty()) return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + why);
+      std::string err;
+      if (rpthost::convert_material(objects[k].material, i, mats[i], err) != RPTGPU_OK)
+        return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + "entry " + std::to_string(k) + ": " + err);
+      rpthost::set_transform(insts[i], objects[k].shape);
+    }
+    commit_update(h, insts, &mats, nullptr);
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  } catch (const std::bad_alloc&) {
+    return fail(h, RPTGPU_E_OUT_OF_MEMORY, fn + "host allocation failed");
+  }
+  return RPTGPU_OK;
+}
+
+int rptgpu_scene_set_lights(rptgpu_scene* h, uint64_t n, const uint32_t* index, const RptLight* lights) {
+  if (!h) return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, "rptgpu_scene_set_lights: null handle");
+  const std::string fn = "rptgpu_scene_set_lights: ";
+  if (const char* why = update_refusal(h, n, index, lights)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + why);
+  try {
+    const size_t count = h->host_lights.size();
+    std::vector<rptdev::Inst> insts = h->top_insts;
+    std::vector<rptdev::Light> recs = h->host_lights;
+    std::vector<char> seen(count, 0);
+    for (uint64_t k = 0; k < n; k++) {
+      const uint32_t i = index[k];
+      std::string why = index_refusal(k, i, count, seen, "light");
+      if (why.empty() && lights[k].kind != recs[i].kind)
+        why = "entry " + std::to_string(k) + " (light " + std::to_string(i) + "): light kind " + std::to_string(lights[k].kind) +
+              " differs from the kind at creation (" + std::to_string(recs[i].kind) + ")";
+      if (why.empty() && recs[i].kind == RPT_LIGHT_OBJECT)
+        why = shape_refusal(k, i, lights[k].object.shape, insts[recs[i].inst], "light");
+      if (!why.empty()) return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + why);
+      rptdev::Light dl;
+      std::string err;
+      if (rpthost::convert_light(lights[k], dl, err) != RPTGPU_OK)
+        return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + "entry " + std::to_string(k) + ": " + err);
+      dl.inst = recs[i].inst;
+      if (dl.kind == RPT_LIGHT_OBJECT) rpthost::set_transform(insts[dl.inst], lights[k].object.shape);
+      recs[i] = dl;
+    }
+    commit_update(h, insts, nullptr, &recs);
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  } catch (const std::bad_alloc&) {
+    return fail(h, RPTGPU_E_OUT_OF_MEMORY, fn + "host allocation failed");
+  }
+  return RPTGPU_OK;
+}
 
 // KdBuild -> the malloc'ed arrays of RptKdTree
 static int kdtree_export(const rpthost::KdBuild& kb, RptKdTree* out) {

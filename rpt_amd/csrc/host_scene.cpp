@@ -453,58 +453,6 @@ void fill_leaf_boxes(FlatScene& fs, int tree, int64_t tri_base /* < 0: a GROUP t
   });
 }
 
-// The same filter one level up, for scenes that are a list of many small objects (every tree a single leaf: the flat
-// path kernel, kernels/paths.inc flat_query_filtered).  The reference tests every object of scene.objects against every
-// ray (renderer.rs:211-220); an object's intersect can only accept a hit point that lies on the object, hence inside its
-// bounding_box (the triangles' boxes for a mesh, Transformed::bounding_box shape.rs:153-176 for a placed sphere / cube /
-// mesh), so a ray that does not cross that box — enlarged by a grid step, tested in f32 — inside [t_min, record.time]
-// skips the object's test with nothing changed.  Never filtered: unbounded objects (Plane), boxes that are not finite,
-// meshes with a sliver triangle (see above), placements whose matrices are so ill-conditioned that the world-space
-// point o + t d and the object-space point the test accepted could be a noticeable fraction of a grid step apart.
-void fill_object_boxes(FlatScene& fs, const std::vector<Box>& world, const std::vector<char>& bounded) {
-  const size_t n = world.size();
-  fs.obj_filter_ok = n >= 1 && n <= 64;
-  fs.obj_always = ~0ull;
-  fs.obj_lbox.assign(n, quantise_box(empty_box(), fs.obj_grid, fs.obj_grid + 3, true));
-  if (!fs.obj_filter_ok) return;
-  std::vector<char> ok(n, 0);
-  Box all = empty_box();
-  for (size_t i = 0; i < n; i++) {
-    const rptdev::Inst& in = fs.insts[i];
-    if (in.kind != RPT_SHAPE_SPHERE && in.kind != RPT_SHAPE_CUBE && in.kind != RPT_SHAPE_PLANE && in.kind != RPT_SHAPE_MESH) {
-      fs.obj_filter_ok = false; // a kind the filtered walk does not dispatch per lane (group, monomial surface)
-      return;
-    }
-    bool good = bounded[i] != 0;
-    for (int k = 0; k < 3 && good; k++) good = std::isfinite(world[i].lo[k]) && std::isfinite(world[i].hi[k]) && world[i].lo[k] <= world[i].hi[k];
-    if (good && in.kind == RPT_SHAPE_MESH) {
-      const rptdev::Tree& t = fs.trees[in.tree];
-      for (uint32_t j = 0; j < t.num_prims && good; j++) good = !sliver(fs.trix[t.prim_base + j]);
-    }
-    if (good && in.has_xf) { // condition number (Frobenius) of the placement
-      double a = 0.0, b = 0.0;
-      for (int c = 0; c < 3; c++)
-        for (int r = 0; r < 3; r++) { a += in.fwd[4 * c + r] * in.fwd[4 * c + r]; b += in.inv[4 * c + r] * in.inv[4 * c + r]; }
-      good = std::isfinite(a) && std::isfinite(b) && a * b < 1e8; // cond < 1e4
-    }
-    ok[i] = good ? 1 : 0;
-    if (good) all = merge(all, world[i]);
-  }
-  double bounds[6];
-  for (int k = 0; k < 3; k++) { bounds[k] = all.lo[k]; bounds[3 + k] = all.hi[k]; }
-  for (int k = 0; k < 6; k++)
-    if (!std::isfinite(bounds[k])) return; // nothing to filter: obj_always stays all ones
-  grid_over(bounds, fs.obj_grid, fs.obj_grid + 3);
-  std::memcpy(fs.obj_grid + 6, bounds, sizeof(bounds));
-  fs.obj_always = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (ok[i] && quadric_too_small(fs.insts[i], fs.obj_grid + 3)) ok[i] = 0;
-    if (ok[i]) fs.obj_lbox[i] = quantise_box(world[i], fs.obj_grid, fs.obj_grid + 3, false);
-    if (!ok[i] || fs.obj_lbox[i].w[3]) fs.obj_always |= 1ull << i;
-  }
-  if (n < 64) fs.obj_always &= (1ull << n) - 1ull;
-}
-
 struct Flattener {
   FlatScene& fs;
   std::string& err;
@@ -556,20 +504,14 @@ struct Flattener {
   }
 
   // fills `in` (already placed in fs.insts or a local) from a shape description; returns the
-  // untransformed-or-transformed bounding box through *bbox when the shape is Bounded.
-  int fill_inst(const RptShape& s, rptdev::Inst& in, Box* bbox, bool* bounded, int nesting) {
+  // untransformed-or-transformed bounding box through *bbox when the shape is Bounded; *local_box: the same before
+  // the placement
+  int fill_inst(const RptShape& s, rptdev::Inst& in, Box* bbox, bool* bounded, int nesting, Box* local_box = nullptr) {
     std::memset(&in, 0, sizeof(in));
     in.kind = s.kind;
-    in.has_xf = s.transformed ? 1 : 0;
     in.tree = -1;
     in.material = -1;
-    if (s.transformed) {
-      std::memcpy(in.inv, s.xf.inverse_transform, sizeof(in.inv));
-      std::memcpy(in.nrm, s.xf.normal_transform, sizeof(in.nrm));
-      std::memcpy(in.fwd, s.xf.transform, sizeof(in.fwd));
-      std::memcpy(in.lin, s.xf.linear, sizeof(in.lin));
-      in.scale = s.xf.scale;
-    }
+    set_transform(in, s);
     Box local = empty_box();
     bool is_bounded = true;
     switch (s.kind) {
@@ -684,6 +626,7 @@ struct Flattener {
         return RPTGPU_E_UNSUPPORTED_SHAPE;
     }
     if (bounded) *bounded = is_bounded;
+    if (local_box) *local_box = local;
     if (bbox && is_bounded) *bbox = s.transformed ? transformed_box(local, s.xf.transform) : local;
     return RPTGPU_OK;
   }
@@ -694,6 +637,132 @@ struct Flattener {
 };
 
 } // namespace
+
+void set_transform(rptdev::Inst& in, const RptShape& s) {
+  in.has_xf = s.transformed ? 1 : 0;
+  if (s.transformed) {
+    std::memcpy(in.inv, s.xf.inverse_transform, sizeof(in.inv));
+    std::memcpy(in.nrm, s.xf.normal_transform, sizeof(in.nrm));
+    std::memcpy(in.fwd, s.xf.transform, sizeof(in.fwd));
+    std::memcpy(in.lin, s.xf.linear, sizeof(in.lin));
+    in.scale = s.xf.scale;
+  } else {
+    std::memset(in.inv, 0, sizeof(in.inv));
+    std::memset(in.nrm, 0, sizeof(in.nrm));
+    std::memset(in.fwd, 0, sizeof(in.fwd));
+    std::memset(in.lin, 0, sizeof(in.lin));
+    in.scale = 0.0;
+  }
+}
+
+int convert_material(const RptMaterial& s, uint64_t i, rptdev::Material& m, std::string& err) {
+  { // sample_f's lobe probability (material.rs:233-235) goes to rng.gen_bool(f) (:264), which panics outside
+    // [0, 1] (NaN included); the device has no panic, so such a material is refused here
+    double f0 = (s.index - 1.0) / (s.index + 1.0);
+    f0 = f0 * f0;
+    double mean = ((s.color[0] + s.color[1]) + s.color[2]) / 3.0;
+    double f = (1.0 - s.metallic) * f0 + s.metallic * mean;
+    f = f * (1.0 - 0.2) + 1.0 * 0.2;
+    if (!(f >= 0.0 && f <= 1.0)) {
+      err = "material of object " + std::to_string(i) + ": specular lobe probability " + std::to_string(f) +
+            " is outside [0, 1] (gen_bool would panic, material.rs:264)";
+      return RPTGPU_E_INVALID_ARGUMENT;
+    }
+  }
+  std::memset(&m, 0, sizeof(m));
+  std::memcpy(m.color, s.color, sizeof(m.color));
+  m.index = s.index; m.roughness = s.roughness; m.metallic = s.metallic;
+  m.emittance = s.emittance; m.transparent = s.transparent ? 1 : 0;
+  return RPTGPU_OK;
+}
+
+int convert_light(const RptLight& l, rptdev::Light& dl, std::string& err) {
+  std::memset(&dl, 0, sizeof(dl));
+  dl.kind = l.kind;
+  dl.inst = -1;
+  std::memcpy(dl.color, l.color, sizeof(dl.color));
+  std::memcpy(dl.vec, l.vec, sizeof(dl.vec));
+  switch (l.kind) {
+    case RPT_LIGHT_POINT: case RPT_LIGHT_DIRECTIONAL: case RPT_LIGHT_AMBIENT: break;
+    case RPT_LIGHT_OBJECT:
+      std::memcpy(dl.mat_color, l.object.material.color, sizeof(dl.mat_color));
+      dl.mat_emittance = l.object.material.emittance;
+      break;
+    default: err = "unknown light kind"; return RPTGPU_E_INVALID_ARGUMENT;
+  }
+  return RPTGPU_OK;
+}
+
+Box world_box(const ObjectGeom& g, const rptdev::Inst& in) {
+  if (!g.bounded) return empty_box();
+  return in.has_xf ? transformed_box(g.local, in.fwd) : g.local;
+}
+
+// The same filter one level up, for scenes that are a list of many small objects (every tree a single leaf: the flat
+// path kernel, kernels/paths.inc flat_query_filtered).  The reference tests every object of scene.objects against every
+// ray (renderer.rs:211-220); an object's intersect can only accept a hit point that lies on the object, hence inside its
+// bounding_box (the triangles' boxes for a mesh, Transformed::bounding_box shape.rs:153-176 for a placed sphere / cube /
+// mesh), so a ray that does not cross that box — enlarged by a grid step, tested in f32 — inside [t_min, record.time]
+// skips the object's test with nothing changed.  Never filtered: unbounded objects (Plane), boxes that are not finite,
+// meshes with a sliver triangle (see above), placements whose matrices are so ill-conditioned that the world-space
+// point o + t d and the object-space point the test accepted could be a noticeable fraction of a grid step apart.
+void fill_object_boxes(const std::vector<rptdev::Inst>& insts, const std::vector<ObjectGeom>& geom, ObjectBounds& fs) {
+  fs = ObjectBounds{};
+  const size_t n = geom.size();
+  std::vector<Box> world(n);
+  for (size_t i = 0; i < n; i++) world[i] = world_box(geom[i], insts[i]);
+  { // the scene bounds: every bounded object with a finite box
+    Box all = empty_box();
+    bool any = false;
+    for (size_t i = 0; i < n; i++) {
+      bool good = geom[i].bounded;
+      for (int k = 0; k < 3 && good; k++) good = std::isfinite(world[i].lo[k]) && std::isfinite(world[i].hi[k]) && world[i].lo[k] <= world[i].hi[k];
+      if (good) { all = merge(all, world[i]); any = true; }
+    }
+    fs.scene_bounds_ok = any;
+    for (int k = 0; k < 3 && any; k++) {
+      fs.scene_bounds[k] = all.lo[k]; fs.scene_bounds[3 + k] = all.hi[k];
+      if (!(all.hi[k] > all.lo[k]) || !std::isfinite(all.hi[k] - all.lo[k])) fs.scene_bounds_ok = false;
+    }
+  }
+  fs.obj_filter_ok = n >= 1 && n <= 64;
+  fs.obj_always = ~0ull;
+  fs.obj_lbox.assign(n, quantise_box(empty_box(), fs.obj_grid, fs.obj_grid + 3, true));
+  if (!fs.obj_filter_ok) return;
+  std::vector<char> ok(n, 0);
+  Box all = empty_box();
+  for (size_t i = 0; i < n; i++) {
+    const rptdev::Inst& in = insts[i];
+    if (in.kind != RPT_SHAPE_SPHERE && in.kind != RPT_SHAPE_CUBE && in.kind != RPT_SHAPE_PLANE && in.kind != RPT_SHAPE_MESH) {
+      fs.obj_filter_ok = false; // a kind the filtered walk does not dispatch per lane (group, monomial surface)
+      return;
+    }
+    bool good = geom[i].bounded;
+    for (int k = 0; k < 3 && good; k++) good = std::isfinite(world[i].lo[k]) && std::isfinite(world[i].hi[k]) && world[i].lo[k] <= world[i].hi[k];
+    if (good && in.kind == RPT_SHAPE_MESH) good = !geom[i].sliver;
+    if (good && in.has_xf) { // condition number (Frobenius) of the placement
+      double a = 0.0, b = 0.0;
+      for (int c = 0; c < 3; c++)
+        for (int r = 0; r < 3; r++) { a += in.fwd[4 * c + r] * in.fwd[4 * c + r]; b += in.inv[4 * c + r] * in.inv[4 * c + r]; }
+      good = std::isfinite(a) && std::isfinite(b) && a * b < 1e8; // cond < 1e4
+    }
+    ok[i] = good ? 1 : 0;
+    if (good) all = merge(all, world[i]);
+  }
+  double bounds[6];
+  for (int k = 0; k < 3; k++) { bounds[k] = all.lo[k]; bounds[3 + k] = all.hi[k]; }
+  for (int k = 0; k < 6; k++)
+    if (!std::isfinite(bounds[k])) return; // nothing to filter: obj_always stays all ones
+  grid_over(bounds, fs.obj_grid, fs.obj_grid + 3);
+  std::memcpy(fs.obj_grid + 6, bounds, sizeof(bounds));
+  fs.obj_always = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (ok[i] && quadric_too_small(insts[i], fs.obj_grid + 3)) ok[i] = 0;
+    if (ok[i]) fs.obj_lbox[i] = quantise_box(world[i], fs.obj_grid, fs.obj_grid + 3, false);
+    if (!ok[i] || fs.obj_lbox[i].w[3]) fs.obj_always |= 1ull << i;
+  }
+  if (n < 64) fs.obj_always &= (1ull << n) - 1ull;
+}
 
 int flatten_scene(const RptScene& sc, FlatScene& fs, std::string& err, const BuildOptions* build) {
   if ((sc.num_objects && !sc.objects) || (sc.num_lights && !sc.lights)) {
@@ -708,48 +777,37 @@ int flatten_scene(const RptScene& sc, FlatScene& fs, std::string& err, const Bui
   Flattener fl{fs, err, {}, build, {}};
   fs.num_objects = (int32_t)sc.num_objects;
   fs.insts.resize(sc.num_objects);
-  std::vector<Box> world(sc.num_objects, empty_box()); // Bounded objects: their bounding_box (the object filter's)
-  std::vector<char> world_ok(sc.num_objects, 0);
+  fs.obj_geom.resize(sc.num_objects);
+  std::map<int, bool> tree_sliver; // (instances of one mesh share its tree)
   for (uint64_t i = 0; i < sc.num_objects; i++) {
     rptdev::Inst in;
-    bool bounded = false;
-    int rc = fl.fill_inst(sc.objects[i].shape, in, &world[i], &bounded, 0);
+    ObjectGeom& g = fs.obj_geom[i];
+    int rc = fl.fill_inst(sc.objects[i].shape, in, nullptr, &g.bounded, 0, &g.local);
     if (rc != RPTGPU_OK) return rc;
-    world_ok[i] = bounded ? 1 : 0;
+    if (in.kind == RPT_SHAPE_MESH && sc.num_objects <= 64) { // (read by the object filter only, which takes <= 64 objects)
+      auto it = tree_sliver.find(in.tree);
+      if (it == tree_sliver.end()) {
+        const rptdev::Tree& t = fs.trees[in.tree];
+        bool any = false;
+        for (uint32_t j = 0; j < t.num_prims && !any; j++) any = sliver(fs.trix[t.prim_base + j]);
+        it = tree_sliver.emplace(in.tree, any).first;
+      }
+      g.sliver = it->second;
+    }
     in.material = (int32_t)fs.materials.size();
     fs.insts[i] = in;
     rptdev::Material m;
-    std::memset(&m, 0, sizeof(m));
-    const RptMaterial& s = sc.objects[i].material;
-    { // sample_f's lobe probability (material.rs:233-235) goes to rng.gen_bool(f) (:264), which panics outside
-      // [0, 1] (NaN included); the device has no panic, so such a material is refused here
-      double f0 = (s.index - 1.0) / (s.index + 1.0);
-      f0 = f0 * f0;
-      double mean = ((s.color[0] + s.color[1]) + s.color[2]) / 3.0;
-      double f = (1.0 - s.metallic) * f0 + s.metallic * mean;
-      f = f * (1.0 - 0.2) + 1.0 * 0.2;
-      if (!(f >= 0.0 && f <= 1.0)) {
-        err = "material of object " + std::to_string(i) + ": specular lobe probability " + std::to_string(f) +
-              " is outside [0, 1] (gen_bool would panic, material.rs:264)";
-        return RPTGPU_E_INVALID_ARGUMENT;
-      }
-    }
-    std::memcpy(m.color, s.color, sizeof(m.color));
-    m.index = s.index; m.roughness = s.roughness; m.metallic = s.metallic;
-    m.emittance = s.emittance; m.transparent = s.transparent ? 1 : 0;
+    rc = convert_material(sc.objects[i].material, i, m, err);
+    if (rc != RPTGPU_OK) return rc;
     fs.materials.push_back(m);
   }
   for (uint64_t i = 0; i < sc.num_lights; i++) {
     const RptLight& l = sc.lights[i];
     rptdev::Light dl;
-    std::memset(&dl, 0, sizeof(dl));
-    dl.kind = l.kind;
-    dl.inst = -1;
-    std::memcpy(dl.color, l.color, sizeof(dl.color));
-    std::memcpy(dl.vec, l.vec, sizeof(dl.vec));
+    int rc = convert_light(l, dl, err);
+    if (rc != RPTGPU_OK) return rc;
     switch (l.kind) {
       case RPT_LIGHT_POINT: case RPT_LIGHT_DIRECTIONAL: fs.num_shadow_lights++; break;
-      case RPT_LIGHT_AMBIENT: break;
       case RPT_LIGHT_OBJECT: {
         fs.num_shadow_lights++;
         if (l.object.shape.kind == RPT_SHAPE_PLANE) {
@@ -763,29 +821,14 @@ int flatten_scene(const RptScene& sc, FlatScene& fs, std::string& err, const Bui
         if (rc != RPTGPU_OK) return rc;
         dl.inst = (int32_t)fs.insts.size();
         fs.insts.push_back(in);
-        std::memcpy(dl.mat_color, l.object.material.color, sizeof(dl.mat_color));
-        dl.mat_emittance = l.object.material.emittance;
         break;
       }
-      default: err = "unknown light kind"; return RPTGPU_E_INVALID_ARGUMENT;
+      default: break; // (Ambient)
     }
     fs.lights.push_back(dl);
   }
-  fill_object_boxes(fs, world, world_ok);
-  {
-    Box all = empty_box();
-    bool any = false;
-    for (size_t i = 0; i < world.size(); i++) {
-      bool good = world_ok[i] != 0;
-      for (int k = 0; k < 3 && good; k++) good = std::isfinite(world[i].lo[k]) && std::isfinite(world[i].hi[k]) && world[i].lo[k] <= world[i].hi[k];
-      if (good) { all = merge(all, world[i]); any = true; }
-    }
-    fs.scene_bounds_ok = any;
-    for (int k = 0; k < 3 && any; k++) {
-      fs.scene_bounds[k] = all.lo[k]; fs.scene_bounds[3 + k] = all.hi[k];
-      if (!(all.hi[k] > all.lo[k]) || !std::isfinite(all.hi[k] - all.lo[k])) fs.scene_bounds_ok = false;
-    }
-  }
+  fs.num_top_insts = (uint32_t)fs.insts.size();
+  fill_object_boxes(fs.insts, fs.obj_geom, fs);
   for (auto& g : fl.group_children) { // now place GROUP children and patch prim_base
     fs.trees[g.first].prim_base = (uint32_t)fs.insts.size();
     fs.insts.insert(fs.insts.end(), g.second.begin(), g.second.end());

@@ -37,7 +37,46 @@ struct BuildOptions {
   int build_threads = 0; // RptSceneOptions::build_threads: 0 = the usable cores
 };
 
-struct FlatScene {
+// ---- what the flattening derives from the objects' placements and materials.  One source for rptgpu_scene_create and
+// the live updates of a handle (rptgpu_scene_set_objects / _lights, api_scene.cpp), so an updated handle holds the bits a
+// fresh one of the updated scene would.
+
+// per top-level object, fixed at creation (its geometry does not change under an update): what its world box and the
+// object filter need besides the placement
+struct ObjectGeom {
+  Box local;           // Bounded::bounding_box before Transformed (shape.rs:153-176 transforms it)
+  bool bounded = false; // not a Plane
+  bool sliver = false;  // a mesh with an ill-conditioned triangle: never filtered (fill_object_boxes, host_scene.cpp)
+};
+
+// derived from the top-level objects' world boxes
+struct ObjectBounds {
+  // flat scenes' object filter (kernels/paths.inc flat_query_filtered): one conservative box per TOP-LEVEL object on a
+  // grid over all bounded ones; bit k of obj_always: object k is never filtered.  obj_filter_ok: every object is of a
+  // kind the filtered walk handles (sphere, cube, plane, mesh) and there are at most 64 of them
+  std::vector<rptdev::LeafBox> obj_lbox;
+  double obj_grid[12] = {0, 0, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0}; // qlo[3], qscale[3], bounds[6]
+  uint64_t obj_always = ~0ull;
+  bool obj_filter_ok = false;
+  // union of the world-space boxes of the bounded top-level objects (planes have none): the grid of the path re-order's
+  // sort key (kernels/wavefront.inc rpt_path_keys); ok: there is at least one and it is finite and not flat
+  double scene_bounds[6] = {0, 0, 0, 1, 1, 1};
+  bool scene_bounds_ok = false;
+};
+
+// Transformed's five fields (shape.rs:101-124) into `in`; zeros when the shape is not transformed
+void set_transform(rptdev::Inst& in, const RptShape& s);
+// Material -> its device record; refuses (RPTGPU_E_INVALID_ARGUMENT, `err` names object `i`) a material whose specular lobe
+// probability lies outside [0, 1]
+int convert_material(const RptMaterial& s, uint64_t i, rptdev::Material& m, std::string& err);
+// a light's record without its shape (Light::inst is left -1); RPTGPU_E_INVALID_ARGUMENT for an unknown kind
+int convert_light(const RptLight& l, rptdev::Light& dl, std::string& err);
+// the world box of a top-level object: Bounded::bounding_box through its placement `in` (meaningful when g.bounded)
+Box world_box(const ObjectGeom& g, const rptdev::Inst& in);
+// the object filter's tables and the scene bounds of the top-level objects insts[0, geom.size()), from scratch
+void fill_object_boxes(const std::vector<rptdev::Inst>& insts, const std::vector<ObjectGeom>& geom, ObjectBounds& out);
+
+struct FlatScene : ObjectBounds {
   std::vector<rptdev::Inst> insts;
   std::vector<rptdev::Tree> trees;
   std::vector<uint32_t> tree_depth; // per tree: depth of its deepest leaf
@@ -58,17 +97,8 @@ struct FlatScene {
   int32_t num_objects = 0;
   int32_t num_shadow_lights = 0;
   uint32_t max_tree_depth = 0;
-  // flat scenes' object filter (kernels/paths.inc flat_query_filtered): one conservative box per TOP-LEVEL object on a
-  // grid over all bounded ones; bit k of obj_always: object k is never filtered.  obj_filter_ok: every object is of a
-  // kind the filtered walk handles (sphere, cube, plane, mesh) and there are at most 64 of them
-  std::vector<rptdev::LeafBox> obj_lbox;
-  double obj_grid[12] = {0, 0, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0}; // qlo[3], qscale[3], bounds[6]
-  uint64_t obj_always = ~0ull;
-  bool obj_filter_ok = false;
-  // union of the world-space boxes of the bounded top-level objects (planes have none): the grid of the path re-order's
-  // sort key (kernels/wavefront.inc rpt_path_keys); ok: there is at least one and it is finite and not flat
-  double scene_bounds[6] = {0, 0, 0, 1, 1, 1};
-  bool scene_bounds_ok = false;
+  std::vector<ObjectGeom> obj_geom; // per top-level object (the object filter and scene bounds: ObjectBounds above)
+  uint32_t num_top_insts = 0;       // insts[0, num_top_insts): the objects, then the Light::Object shapes in light order
   uint32_t trees_built_on_device = 0; // how many of the trees kd_build_device made (diagnostics)
   bool nested_mesh = false; // some KdTree<Box<dyn Bounded>> child is a Mesh, a MonomialSurface or another group:
                             // the scene needs the extended kernel builds

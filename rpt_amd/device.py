@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
+from .scene import geometry_mismatch, geometry_snapshot
 
 
 def make_params(width, height, max_bounces, iterations, exposure_value=0.0, seed=0x52505447,
@@ -57,6 +58,46 @@ class GpuScene:
             _abi.check(self.lib.rptgpu_scene_create(C.byref(desc), int(device), C.byref(h)))
         self.handle = h
         self.device = int(device)
+        self._geometry = geometry_snapshot(scene)  # what update() compares a new scene against
+
+    # ---- live updates (rptgpu_scene_set_objects / _lights): new placements and materials, same geometry.  Afterwards
+    # every result equals that of a GpuScene made from the updated scene; the workspace and DeviceBuffers stay.
+    def set_objects(self, indices, objects):
+        """Object indices[k] := objects[k] (a Python Object): its Transformed fields and its material.  The shape's
+        geometry is not read; its kind and whether it is Transformed must be the creation's."""
+        indices, objects = list(indices), list(objects)
+        if len(indices) != len(objects):
+            raise ValueError("set_objects: %d indices for %d objects" % (len(indices), len(objects)))
+        keep = []
+        arr = (_abi.RptObject * max(1, len(objects)))()
+        for k, o in enumerate(objects):
+            o.lower_into(arr[k], keep)
+        idx = (C.c_uint32 * max(1, len(indices)))(*[int(i) for i in indices])
+        _abi.check(self.lib.rptgpu_scene_set_objects(self.handle, len(objects), idx, arr), self.handle)
+
+    def set_lights(self, indices, lights):
+        """Light indices[k] := lights[k] (a Python Light): colour and vector, or a Light::Object's placement and
+        material.  The kind must be the creation's; a Light::Object's shape geometry is not read."""
+        indices, lights = list(indices), list(lights)
+        if len(indices) != len(lights):
+            raise ValueError("set_lights: %d indices for %d lights" % (len(indices), len(lights)))
+        keep = []
+        arr = (_abi.RptLight * max(1, len(lights)))()
+        for k, l in enumerate(lights):
+            l.lower_into(arr[k], keep)
+        idx = (C.c_uint32 * max(1, len(indices)))(*[int(i) for i in indices])
+        _abi.check(self.lib.rptgpu_scene_set_lights(self.handle, len(lights), idx, arr), self.handle)
+
+    def update(self, scene):
+        """Push every object and light of `scene`, a Scene with the geometry of the one this handle was made from (the
+        next frame of an animation).  ValueError, naming the first mismatch, when the counts, the environment or any
+        shape's geometry differ (scene.geometry_mismatch): those need a new GpuScene."""
+        why = geometry_mismatch(self._geometry, scene)
+        if why:
+            raise ValueError("GpuScene.update: %s; a new GpuScene is needed" % why)
+        self.set_objects(range(len(scene.objects)), scene.objects)
+        self.set_lights(range(len(scene.lights)), scene.lights)
+        self._geometry = geometry_snapshot(scene)  # (the same geometry: the newer objects make the identity checks hit)
 
     def options(self):
         """The options the handle runs with (defaults, the caller's, environment overrides) as a dict."""

@@ -61,6 +61,13 @@ class Renderer:
         self._precision = int(mode)
         return self
 
+    def with_gpu_scene(self, gpu_scene):
+        """Render with an existing GpuScene (for example one kept across the frames of an animation and moved with
+        GpuScene.update) instead of creating one from `scene`."""
+        self._gpu = gpu_scene
+        self._device = gpu_scene.device
+        return self
+
     def gpu_scene(self):
         if self._gpu is None:
             self._gpu = GpuScene(self.scene, self._device)

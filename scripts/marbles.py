@@ -1,7 +1,10 @@
-"""examples/marbles.rs: 25 marbles fall into a glass.  Each frame rebuilds the scene from the particle state, renders
+"""examples/marbles.rs: 25 marbles fall into a glass.  Each frame builds the scene from the particle state, renders
 it on the GPU and writes video/image_<frame>.png, then MarblesSystem integrates 1/16 s (625 RK4 steps) on the GPU.
+One scene handle serves the whole run: each frame moves its marbles with GpuScene.update (the same pixels as a new
+handle per frame); --rebuild creates a new handle per frame, as the example does.
 
 Usage: python scripts/marbles.py [--frames 180] [--test] [--width W --height H --spp S --bounces B] [--out video]
+       [--rebuild]
 --test is the example's TEST = true branch (200 x 150, 7 bounces, 1 spp, an ambient light).  Stand-ins (scenes.marbles):
 the analytic monomial_surface(2, 4) for monomial.obj unless $RPT_ASSETS has it, synthetic_hdri for ballroom_8k.hdr.
 """
@@ -15,7 +18,7 @@ import zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from rpt_amd import Renderer, scenes  # noqa: E402
+from rpt_amd import GpuScene, Renderer, scenes  # noqa: E402
 from rpt_amd.ode import MarblesSystem  # noqa: E402
 
 
@@ -40,15 +43,23 @@ def main():
     ap.add_argument("--spp", type=int)
     ap.add_argument("--bounces", type=int)
     ap.add_argument("--out", default="video")
+    ap.add_argument("--rebuild", action="store_true", help="a new scene handle per frame instead of GpuScene.update")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
     state = scenes.marbles_start()
     system = MarblesSystem(scenes.MARBLES_R)
+    gpu = None
     for frame in range(a.frames):
         t0 = time.perf_counter()
         scene, camera, cfg = scenes.marbles(state, test=a.test)
         r = (Renderer(scene, camera).width(a.width or cfg["width"]).height(a.height or cfg["height"])
              .max_bounces(a.bounces or cfg["max_bounces"]).num_samples(a.spp or cfg["num_samples"]))
+        if not a.rebuild:
+            if gpu is None:
+                gpu = GpuScene(scene, 0)
+            else:
+                gpu.update(scene)
+            r.with_gpu_scene(gpu)
         save_png(r.render(), os.path.join(a.out, "image_%d.png" % frame))
         t1 = time.perf_counter()
         system.rk4_integrate(state, 1.0 / 16.0, 1.0 / 10000.0)
