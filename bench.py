@@ -9,7 +9,8 @@ through the last bounce, the reduce over ranks, and the write of the W*H mean co
 `wall_clock_per_frame_ms`.  With N GPUs rank r renders the tiles tile_id % N == r of the SAME frame
 (strong scaling) and rank 0 gathers the f32 pixels each rank owns, one RCCL send / receive group per step.
 
-    python bench.py                      # 1 GPU: the headline (C2) + the other BASELINE configs + live counters
+    python bench.py                      # 1 GPU: the headline (C2) alone, one JSON line
+    python bench.py --full               # the headline + the other BASELINE configs + roofline + live counters + CPU baselines
     python bench.py --gpus N --steps K --warmup W    # N GPUs: bench.py starts its own N ranks (torch.distributed.run,
                                                      # one per GPU); fewer than N visible devices is an error
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -19,7 +20,11 @@ through the last bounce, the reduce over ranks, and the write of the W*H mean co
     python bench.py --dump-outputs DIR               # also write the last timed step's frames as DIR/<scene>.npy, so that
                                                      # two builds can be compared output for output (same arguments, same inputs)
 
-The default 1-GPU run prints ONE JSON line.  Besides the headline it carries
+A run without --full does only what its headline needs: it sets up, runs the warm-up and the timed steps, writes the
+frames when --dump-outputs asks for them, and prints ONE JSON line (value, ms_per_step, step_spread, rays per second,
+scene creation, per_rank, exchange).  With --dump-outputs it also writes the frames the other configs' last timed steps
+leave under --full (see other_frames), rendered once each and untimed, so that both forms write the same files.
+--full adds everything that costs work of its own:
   * `other_configs`: BASELINE configs[2-4] (dragon-class mesh at its 256 spp, fractal spheres, wine glass — mesh and
     glass-spheres variants) at their own frame sizes and 64 spp per step (a step is then a few passes of the size the
     BASELINE sample counts run in),
@@ -30,7 +35,9 @@ The default 1-GPU run prints ONE JSON line.  Besides the headline it carries
   * `roofline` objects whose counter fields (VALU busy, lanes active per VALU instruction, HBM bytes, L2 requests)
     are measured IN THIS RUN: bench.py re-runs one step of each workload under `rocprofv3 --pmc ... --kernel-trace`
     in a child process (no torch, ~10 s per pass) and reads the counters back.  If rocprofv3 is not usable the
-    fields fall back to the newest committed profiles/r*_<scene>_pmc.json and `pmc_source` says so.
+    fields fall back to the newest committed profiles/r*_<scene>_pmc.json and `pmc_source` says so;
+  * `cpu_baseline`: the oracle on this box's host cores, for the headline and every other config.
+--no-other-configs, --no-live-pmc and --no-cpu-baseline leave out one part of --full each.
 """
 import argparse
 import json
@@ -409,6 +416,12 @@ def kernel_table(wl, st, bytes_k):
     return kernels, dominant, kern_n
 
 
+def kernel_launches(wl, st):
+    """launches of every kernel kind in the timed steps (the library's own counters: no run of their own)"""
+    from rpt_amd import _abi
+    return {wl.gpu.lib.rptgpu_kernel_name(k).decode(): int(st.kernel_launches[k]) for k in range(_abi.RPT_K_COUNT)}
+
+
 def roofline_object(wl, st, kernels, dominant, kern_n, bytes_k, pmc, pmc_note, pmc_spp):
     """What bounds the dominant kernel.  This path is branchy scalar f64 whose scenes live in LDS / L2: the roof is the
     f64 VALU — useful lane slots per second — not HBM.  `frac` = VALU busy x lanes active / 64 from the SQ counters;
@@ -692,25 +705,75 @@ MULTI_GPU_OTHER_STEPS, MULTI_GPU_OTHER_WARMUP = 2, 1
 SCALAR_KEYS = {"dragon": "c3_msamples", "fractal_spheres": "c4_msamples", "wine_glass": "c5_mesh_msamples", "glass": "c5_glass_spheres_msamples"}
 
 
+def other_configs(world):
+    """the other configs of a default run with `world` ranks: ((scene, spp per step), ...), timed steps, warm-up steps"""
+    if world == 1:
+        return OTHER_CONFIGS, OTHER_STEPS, OTHER_WARMUP
+    return MULTI_GPU_OTHER_CONFIGS, MULTI_GPU_OTHER_STEPS, MULTI_GPU_OTHER_WARMUP
+
+
+def full_headline(args, wl, st, world):
+    """--full: the headline's roofline object (reference-algorithm accounting from the oracle, counters from child runs
+    under rocprofv3) and its CPU baseline.  Closes the headline's scene before the counter runs, whose child renders the
+    same workload on the same GPU."""
+    bytes_k, osc = accounting(wl, st)
+    kernels, dominant, kern_n = kernel_table(wl, st, bytes_k)
+    live = world == 1 and not args.no_live_pmc
+    pmc, pmc_note = (None, "live counters are collected at N=1 only" if world > 1 else "--no-live-pmc")
+    extra = ["--pipeline", args.pipeline] + (["--width", str(wl.W), "--height", str(wl.H)] if (args.width or args.height) else []) \
+        + (["--bounces", str(wl.B)] if args.bounces is not None else [])
+    if live:
+        wl.gpu.close()  # the child renders the same workload on the same GPU: give the memory back first
+        pmc, pmc_note = live_pmc(args.scene, wl.spp, (PMC_A, PMC_B, PMC_C), extra)
+    roofline = roofline_object(wl, st, kernels, dominant, kern_n, bytes_k, pmc, pmc_note, wl.spp)
+    cpu = None
+    if world == 1 and not args.no_cpu_baseline:
+        cpu = cpu_baseline(wl, osc, 6.0, args.cpu_spp)
+    return {"roofline": roofline, "cpu_baseline": cpu}
+
+
+def other_frames(rk, args, outputs):
+    """--dump-outputs without --full: the frame of every other config that --full's timed steps leave last, rendered once
+    and untimed — the parameters of that last step on a new scene handle.  A frame depends on its parameters alone (every
+    pixel sums its samples in sample order, whatever the schedule, the pass sizes or the calls before it), so the array
+    is the one --full writes, for the GPU time of one step instead of all of them.  Every rank renders; rank 0 keeps the
+    frames in `outputs`."""
+    cfgs, osteps, owarm = other_configs(rk.world)
+    for name, ospp in cfgs:
+        o = Workload(name, args, rk.rank, rk.world, rk.local_rank, rk.backend, spp=ospp, is_headline=False)
+        ostep, _, _, oframe = setup_exchange(rk, o)
+        o.step_no = owarm + osteps - 1
+        ostep()
+        rk.fence()
+        if outputs is not None:
+            outputs[name] = frame_output(oframe.numpy(), o.W, o.H, DUMP_OTHER_PIXELS)
+        o.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 3; 30 frames for simple_video)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--spp", type=int, default=None, help="samples per pixel per step (default: the config's own)")
-    ap.add_argument("--scene", default=None, help="one workload only (default: cornell = the headline, plus the other configs)")
+    ap.add_argument("--scene", default=None, help="one workload only (default: cornell = the headline, plus the other configs under --full)")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--bounces", type=int, default=None)
     ap.add_argument("--pipeline", default="auto", choices=["auto", "persistent", "wavefront"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="headline only")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not re-run a step under rocprofv3 for the counter fields")
+    ap.add_argument("--full", action="store_true",
+                    help="also the other BASELINE configs (default run), the roofline objects with live counters and the CPU "
+                         "baselines; without it the run times the headline and nothing else")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the other configs; without --full, "
+                    "--dump-outputs writes the headline's frame only")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full: do not re-run a step under rocprofv3 for the counter fields")
     ap.add_argument("--cpu-spp", type=int, default=None, help="spp of the CPU-baseline sample (default and minimum: 16)")
     ap.add_argument("--dump-frame", default=None, help="rank 0 saves the last step's reduced f32 frame (.npy)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
-                    help="rank 0 writes the last timed step's frame of every timed workload as DIR/<scene>.npy (f32; large "
-                         "frames as a fixed seeded sample of their pixels)")
+                    help="rank 0 writes the last timed step's frame of the headline and, in a default run, of every other "
+                         "config (timed under --full, rendered once without it) as DIR/<scene>.npy (f32; large frames as a "
+                         "fixed seeded sample of their pixels)")
     ap.add_argument("--fixed-samples", action="store_true", help="every step renders the same samples (tests)")
     ap.add_argument("--emulate-part-of", type=int, default=0, metavar="N",
                     help="single process: render only the tiles rank 0 would own among N ranks (no collective) and report "
@@ -812,19 +875,8 @@ def main():
     if rank == 0:
         total_samples = float(W) * H * spp * args.steps
         value = total_samples / elapsed / 1e6
-        bytes_k, osc = accounting(wl, st)
-        kernels, dominant, kern_n = kernel_table(wl, st, bytes_k)
-        live = world == 1 and not args.no_live_pmc
-        pmc, pmc_note = (None, "live counters are collected at N=1 only" if world > 1 else "--no-live-pmc")
-        extra = ["--pipeline", args.pipeline] + (["--width", str(W), "--height", str(H)] if (args.width or args.height) else []) \
-            + (["--bounces", str(B)] if args.bounces is not None else [])
-        if live:
-            gpu.close()  # the child renders the same workload on the same GPU: give the memory back first
-            pmc, pmc_note = live_pmc(args.scene, spp, (PMC_A, PMC_B, PMC_C), extra)
-        roofline = roofline_object(wl, st, kernels, dominant, kern_n, bytes_k, pmc, pmc_note, spp)
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu = cpu_baseline(wl, osc, 6.0, args.cpu_spp)
+        kern_n = kernel_launches(wl, st)
+        full = full_headline(args, wl, st, world) if args.full else {}
 
         out = {
             "metric": "Msamples/s", "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
@@ -857,8 +909,7 @@ def main():
                        "scene_create_warm_ms": wl.scene_create_warm_ms,
                        "wall_clock_per_frame_ms": (wl.scene_create_warm_ms or wl.scene_create_ms) + elapsed / args.steps * 1e3},
             "step_spread": step_spread(each, float(W) * H * spp),
-            "roofline": roofline,
-            "cpu_baseline": cpu,
+            **full,
             "exchange": exchange_evidence(rk, lib_collective, collective_note, per_rank),
             "per_rank": per_rank,
             "per_rank_is": "HIP-event time per step inside rptgpu_render_batch_reduce on each rank: its own tiles / the gather "
@@ -875,14 +926,11 @@ def main():
                 out["n1_reference"]["speedup_of_this_line"] = out["n1_reference"]["ms_per_step"] / out["ms_per_step"]
     gpu.close()  # (idempotent: at N = 1 with live counters it was closed before the child ran)
 
-    # ---- the other BASELINE configs on the same clock.  N = 1: all four, with counters and CPU baselines.  N > 1: the two
-    # that BASELINE assigns to 8 GPUs, through the same sharded path and exchange as the headline
-    if default_run and not args.no_other_configs:
+    # ---- --full: the other BASELINE configs on the same clock.  N = 1: all four, with counters and CPU baselines.  N > 1:
+    # the two that BASELINE assigns to 8 GPUs, through the same sharded path and exchange as the headline
+    if default_run and args.full and not args.no_other_configs:
         others = []
-        if world == 1:
-            cfgs, osteps, owarm = OTHER_CONFIGS, OTHER_STEPS, OTHER_WARMUP
-        else:
-            cfgs, osteps, owarm = MULTI_GPU_OTHER_CONFIGS, MULTI_GPU_OTHER_STEPS, MULTI_GPU_OTHER_WARMUP
+        cfgs, osteps, owarm = other_configs(world)
         for name, ospp in cfgs:
             t_cfg = time.perf_counter()
             entry = None
@@ -931,6 +979,8 @@ def main():
                 if key and "value" in e:
                     out[key] = e["value"]
                     out[key + "_spp_per_step"] = e["spp"]
+    elif default_run and args.dump_outputs and not args.no_other_configs:
+        other_frames(rk, args, outputs)
     if outputs is not None:
         dump_outputs(args.dump_outputs, outputs)
     if rank == 0:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the evidence of a round (run through gpurun from the repo root):  TAG=r05 bash scripts/gpu_round_final.sh ["scene:trace_spp:pmc_spp ..."]
 #   1. the GPU test suite
-#   2. the DEFAULT bench command (what the driver runs): headline C2 + the other BASELINE configs + live counters
+#   2. bench.py --full: headline C2 + the other BASELINE configs + live counters + CPU baselines
 #   3. rocprofv3 --kernel-trace --stats of the bench command per scene + PMC passes, summarised ON the box (the rocpd
 #      databases do not travel: 64 MiB limit) into gpurun_out/r03final/profiles/
 #   4. per-phase lane-occupancy tables from the -DRPT_PROF build (rpt_amd/lib/librptgpu_prof.so, if present)
@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 export RPT_PROFILE_DST=$REPO/$O/profiles
 mkdir -p $RPT_PROFILE_DST
 timeout 900 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; grep -E "passed|failed" $O/pytest.log | tail -2
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
 # (trace spp of the two configs BASELINE assigns to 8 GPUs = 256, bench.py's MULTI_GPU_OTHER_CONFIGS: their <scene>_bench_line.json is the 1-GPU line of the same
 # workload that an N > 1 bench line carries along as n1_reference)
 LIST=${1:-"cornell:0:512 dragon:32:16 wine_glass:256:4 fractal_spheres:256:4 room23:64:64 glass:64:64"}
@@ -38,7 +38,7 @@ fi
   timeout 1500 python scripts/parity_sweep.py 16 8 6 0x5EED5 ) > $O/parity_sweep.txt 2>&1
 tail -2 $O/parity_sweep.txt
 timeout 300 python bench.py --scene simple_video > $O/simple_video.json 2>/dev/null
-timeout 300 python bench.py --scene fractal_teapots --bounces 8 --spp 64 --steps 2 --warmup 1 --no-live-pmc > $O/fractal_teapots_b8.json 2>/dev/null
+timeout 300 python bench.py --scene fractal_teapots --bounces 8 --spp 64 --steps 2 --warmup 1 --full --no-live-pmc > $O/fractal_teapots_b8.json 2>/dev/null
 TAG=$TAG python - <<'PY'
 import json
 import os

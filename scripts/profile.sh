@@ -15,7 +15,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_${TAG}_${SCENE}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-if [ "$SPP" = "0" ]; then CMD="python $REPO/bench.py --scene $SCENE $EXTRA"; else CMD="python $REPO/bench.py --scene $SCENE --steps 2 --warmup 1 --spp $SPP --no-cpu-baseline $EXTRA"; fi
+if [ "$SPP" = "0" ]; then CMD="python $REPO/bench.py --scene $SCENE --full $EXTRA"; else CMD="python $REPO/bench.py --scene $SCENE --steps 2 --warmup 1 --spp $SPP --full --no-cpu-baseline $EXTRA"; fi
 echo "$CMD" > $OUT/trace_command.txt
 timeout -k 5 240 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- $CMD > $OUT/bench_trace.log 2>&1
 PCMD="python $REPO/bench.py --scene $SCENE --steps 1 --warmup 0 --spp $PSPP --no-cpu-baseline $EXTRA"

@@ -701,6 +701,40 @@ def test_bench_two_ranks_equal_one_rank(tmp_path):
         assert c.shape == (180, 320, 3) and c.dtype == np.float32 and (c.reshape(-1) == a).all()
 
 
+def test_bench_plain_run_dumps_what_full_dumps(tmp_path):
+    """bench.py without --full times the headline and nothing else: no roofline, CPU baseline or other configs on its
+    line.  With --dump-outputs it still writes the other configs' frames, each rendered once with the parameters of the
+    last step --full times; they equal the frames of --full's timed steps bit for bit.  The default run's other configs
+    are cut to two cheap ones here: the C3 mesh (wavefront pipeline) and the glass spheres (persistent)."""
+    import json
+    import subprocess
+    import sys
+    bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py")
+    run = ("import importlib.util; spec = importlib.util.spec_from_file_location('bench_mod', %r); "
+           "b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b); "
+           "b.OTHER_CONFIGS = (('dragon', 4), ('glass', 2)); b.main()" % bench)
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "4", "--width", "320", "--height", "180"]
+    lines = {}
+    for form, extra in (("plain", []), ("full", ["--full", "--no-live-pmc", "--no-cpu-baseline"])):
+        r = subprocess.run([sys.executable, "-c", run] + common + extra + ["--dump-outputs", str(tmp_path / form)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[form] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    assert not {"roofline", "cpu_baseline", "other_configs", "c3_msamples"} & set(plain)
+    assert plain["value"] > 0 and plain["config"]["pipeline"] == "auto -> persistent"
+    assert {"roofline", "other_configs", "c3_msamples", "c5_glass_spheres_msamples"} <= set(full) and full["cpu_baseline"] is None
+    assert [o["workload"].split(" ")[0] for o in full["other_configs"]] == ["dragon", "glass"]
+    assert all(o.get("value", 0) > 0 for o in full["other_configs"])
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert plain[k] == full[k]
+    names = sorted(os.listdir(str(tmp_path / "full")))
+    assert names == sorted(os.listdir(str(tmp_path / "plain"))) == ["cornell.npy", "dragon.npy", "glass.npy"]
+    for n in names:
+        a, b = np.load(str(tmp_path / "plain" / n)), np.load(str(tmp_path / "full" / n))
+        assert a.shape == b.shape and a.dtype == b.dtype == np.float32 and (a == b).all() and a.max() > 0, n
+
+
 @pytest.mark.parametrize("failing_rank", ["1", "all"])
 def test_bench_two_ranks_fall_back_when_the_library_collective_is_unavailable(tmp_path, failing_rank):
     """The set-up of the library's RCCL collective in bench.py, exercised without eight GPUs: two ranks (gloo stand-in,
