@@ -15,7 +15,15 @@
 #define RPT_PATHS_WAVE_LDS 20480u
 #define RPT_PATHS_WALKER_LDS 2560u
 // rpt_paths<KdFlat> (a flat scene WITH its triangles in LDS) also keeps the lanes' stashed camera rays there
+// (kernels/paths.inc RayStash).  RPT_RAY_STASH=2: rpt_paths<KdFlat, false> traces them ahead and stashes their hits
+// as well (RayStashHit); 1: rays only; 0: no stash (A/B builds)
+#ifndef RPT_RAY_STASH
+#define RPT_RAY_STASH 2
+#endif
 #define RPT_PATHS_STASH_LDS 4864u
+#define RPT_PATHS_STASH_HIT_LDS 6656u
+// what the host leaves room for in a KdFlat scene's LDS layout (api_scene.cpp)
+#define RPT_PATHS_STASH_MAX_LDS (RPT_RAY_STASH >= 2 ? RPT_PATHS_STASH_HIT_LDS : RPT_PATHS_STASH_LDS)
 // flat scenes with a texture environment: the lanes' queues of parked lookups, RPT_PARK_K entries each, at the end of the
 // wave's dynamic LDS (kernels/paths.inc ParkLds)
 #ifndef RPT_PARK_K

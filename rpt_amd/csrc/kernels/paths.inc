@@ -33,6 +33,11 @@
 // walker's path and the write position: the walker's own path (<= max_bounces + 1, part of it already folded),
 // the waiting paths' records and headers (each waits with >= 1 record: <= 2 U), the running path (C + 1)
 // — <= 3 max_bounces + 2 = rpt_fold_ring_slots() (launch_limits.h; api_render.cpp sizes the buffer with it).
+// With pre-traced camera rays (PRETRACE below) a lane can end two paths in one iteration: the one whose ray escaped, at
+// the swap, and the stashed one it takes — but that one starts at depth 0 in this iteration, so it either ends there
+// (no record, no header: its sample goes straight to lbuf) or writes its level-0 record.  Still at most one record per
+// iteration, every header written (path_ended) before the fold step of the same iteration, and the bound above stands
+// (tests/test_ray_stash_swap_model.py).
 //
 // Environment lookups are PARKED (round 5; flat scenes whose environment is a texture).  A ray that escapes ends its
 // path with Hdri::get_color (environment.rs:25-52: atan2, acos, four texels) — one round of it per loop iteration for
@@ -450,14 +455,35 @@ RPT_DEV void park_push(ParkLds& park, uint32_t lane, uint32_t& pcnt, uint32_t& p
   }
   pcnt = k + 1u;
 }
-#ifndef RPT_RAY_STASH
-#define RPT_RAY_STASH 1 // rpt_paths<KdFlat>: the next sample's camera ray generated ahead, for all lanes together (0: A/B builds)
-#endif
+// RPT_RAY_STASH (kernels.h): rpt_paths<KdFlat>'s next camera ray generated ahead (1), and traced ahead as well (2)
 struct RayStash { // per lane, [field][lane]: origin, direction, the stream's cached half; work item, sample, draw counter
   double v[7][64];
   uint32_t u[5][64];
 };
 static_assert(sizeof(RayStash) == RPT_PATHS_STASH_LDS, "kernels.h sizes the wave's LDS budget with it");
+// the pre-traced form (rpt_paths<KdFlat, false> under RPT_RAY_STASH=2): RayStash's fields, where v[0..2] holds the hit
+// point o + t d once the ray is traced; v[7..9] the hit's normal, or the environment's colour if the ray escaped; u[5]
+// the object hit (-1: escaped)
+struct RayStashHit {
+  double v[10][64];
+  uint32_t u[6][64];
+};
+static_assert(sizeof(RayStashHit) == RPT_PATHS_STASH_HIT_LDS, "kernels.h sizes the wave's LDS budget with it");
+#ifndef RPT_STASH_REFILL_MIN
+#define RPT_STASH_REFILL_MIN 32 // RayStashHit: the wave also refills once this many lanes have an empty stash
+#endif
+// a path that ends at `depth` with radiance A (path_ended) and the next path's header slot behind its records
+RPT_DEV void end_path(const PersistArgs& pa, const Frame& fr, double* __restrict__ rec, double (*fold_l)[64],
+                      uint32_t (*fold_u)[64], uint32_t lane, uint32_t& fold_st, uint32_t ring, const D3& A, uint32_t depth,
+                      uint32_t s, uint32_t p_local) {
+  const uint32_t b = fold_st >> 16;
+  path_ended(pa, fr, rec, fold_l, fold_u, lane, fold_st, A, depth, b, s, p_local);
+  if (depth != 0u) {
+    uint32_t nb = b + depth + 1u; // the next path's header slot
+    if (nb >= ring) nb -= ring;
+    fold_st = (fold_st & 0xffffu) | (nb << 16);
+  }
+}
 template <class LDS, bool PARK /* environment lookups parked per lane (pa.park_off) */>
 __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame fr, Camera cam, PersistArgs pa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char flat_smem[]; // KdFlat only (dynamic size)
@@ -541,10 +567,21 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
   // keeps the ray of the sample that follows its running one in a per-lane stash (ray, Philox position, work item); a lane
   // whose path ended takes it, and the wave generates — for ALL lanes whose stash is empty, together — only when some
   // lane needs a ray and has none, about every third iteration.  The same rays from the same draws.
+  //
+  // PRETRACE (RPT_RAY_STASH=2, rpt_paths<KdFlat, false>): the stashed ray is also TRACED when it is generated, and a lane
+  // whose ray escaped takes its stash right after the closest hit, so it shades the stashed hit in the same iteration
+  // instead of idling through the shading phases (about 13 of the ~63 lanes that trace a ray on C2).  A lane that
+  // starts an iteration without a running path skips the closest hit and takes its stash there too.  The pre-traces
+  // run in the one closest-hit site: a lane that has a running path and a ray to pre-trace runs the query twice, the
+  // stashed ray first (with its running ray parked in the stash's slots meanwhile), so nothing it holds in registers
+  // lives across a query.  The wave refills when a lane must (as above) or when RPT_STASH_REFILL_MIN lanes could.
   constexpr bool STASH = RPT_RAY_STASH && std::is_same<LDS, KdFlat>::value;
-  __shared__ typename std::conditional<STASH, RayStash, int>::type stash_store;
-  auto& stash = *reinterpret_cast<RayStash*>(&stash_store);
+  constexpr bool PRETRACE = STASH && RPT_RAY_STASH >= 2 && !PARK;
+  using StashT = typename std::conditional<PRETRACE, RayStashHit, RayStash>::type;
+  __shared__ typename std::conditional<STASH, StashT, int>::type stash_store;
+  auto& stash = *reinterpret_cast<StashT*>(&stash_store);
   bool stash_valid = false, exhausted = false; // exhausted: the work counter ran out for this lane
+  bool pend = false; // PRETRACE: the stashed ray is not traced yet
   ItemPool pool{0u, 0u, 0u};
   // parked environment lookups (see the top of this file): park_hd = header slot of a parked path that holds ring slots
   constexpr bool park_on = PARK;
@@ -555,7 +592,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
   for (;;) {
     if constexpr (STASH) {
       // ---- generate ahead, when some lane must: it has no running path and no stashed ray
-      if (__ballot(!in_path && !stash_valid && !exhausted) != 0ull) {
+      bool refill = __ballot(!in_path && !stash_valid && !exhausted) != 0ull;
+      if constexpr (PRETRACE) refill = refill || __popcll(__ballot(!stash_valid && !exhausted)) >= RPT_STASH_REFILL_MIN;
+      if (refill) {
         const bool gen = !stash_valid && !exhausted;
         // the sample after the running one (a lane without a running path has already advanced s)
         uint32_t g_p_local = p_local, g_pixel = pixel, g_s = s + (in_path ? 1u : 0u), g_s_end = s_end;
@@ -573,11 +612,12 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
           stash.u[0][lane] = g_p_local; stash.u[1][lane] = g_pixel; stash.u[2][lane] = g_s; stash.u[3][lane] = g_s_end;
           stash.u[4][lane] = gr.draw;
           stash_valid = true;
+          pend = PRETRACE;
         }
         PROF_PHASE(PF_P_RAYGEN);
       }
-      // ---- a lane whose path ended starts on its stashed ray
-      if (!in_path && stash_valid) {
+      // ---- a lane whose path ended starts on its stashed ray (PRETRACE: after the closest hit)
+      if (!PRETRACE && !in_path && stash_valid) {
         o = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
         d = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
         p_local = stash.u[0][lane]; pixel = stash.u[1][lane]; s = stash.u[2][lane]; s_end = stash.u[3][lane];
@@ -588,7 +628,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         depth = 0;
         in_path = true;
       }
-      done = !in_path && exhausted; // (no stash left either: the take above would have used it)
+      done = !in_path && exhausted && !(PRETRACE && stash_valid); // (without PRETRACE, the take above used any stash left)
       if (__ballot(!done || (fold_st & 0xffffu) != 0u || pcnt != 0u) == 0) break; // (a lane without work still lets its walker finish)
     } else {
       // ---- work hand-out: persistent-thread fetch
@@ -625,24 +665,91 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
     // ---- one path segment: trace_ray's body (renderer.rs:145-174)
     bool ending = false, esc = false; // the path ended in this iteration; with radiance A_end, or (esc) by a parked lookup
     D3 A_end = mk(0, 0, 0);
+    // PRETRACE: the hit a lane shades — its point o + t d; its normal, or the environment's colour if the ray escaped
+    D3 h_pos = mk(0, 0, 0), h_nrm = mk(0, 0, 0);
+    int h_obj = -1;
+    if constexpr (PRETRACE) {
+      // ---- closest hits: pass 0 (only when some lane has both) the pending pre-traces, pass 1 the running paths and
+      // the pre-traces of lanes without one.  Every pass resets what the query writes, so no lane's result of pass 0
+      // lives in registers across the query of pass 1.
+#pragma unroll 1
+      for (uint32_t pass = __ballot(pend && in_path) != 0ull ? 0u : 1u; pass < 2u; pass++) {
+        const bool pre = pend, run = pend || (pass == 1u && in_path);
+        if (pre) { // the stashed ray into the registers, the running one into its slots meanwhile
+          const D3 so = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
+          const D3 sd = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
+          stash.v[0][lane] = o.x; stash.v[1][lane] = o.y; stash.v[2][lane] = o.z;
+          stash.v[3][lane] = d.x; stash.v[4][lane] = d.y; stash.v[5][lane] = d.z;
+          o = so;
+          d = sd;
+        }
+        double t = INF;
+        h_nrm = mk(0, 0, 0);
+        h_obj = -1;
+        if (run) {
+          h_obj = flat_query<false>(sc, &fl, o, d, -INF, t, h_nrm);
+          n_ext++;
+          if (h_obj < 0) h_nrm = env_color(sc, d); // renderer.rs:147
+        }
+        h_pos = o + t * d;
+        if (pre) {
+          const D3 ro = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
+          const D3 rd = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
+          stash.v[0][lane] = h_pos.x; stash.v[1][lane] = h_pos.y; stash.v[2][lane] = h_pos.z;
+          stash.v[3][lane] = d.x; stash.v[4][lane] = d.y; stash.v[5][lane] = d.z;
+          stash.v[7][lane] = h_nrm.x; stash.v[8][lane] = h_nrm.y; stash.v[9][lane] = h_nrm.z;
+          stash.u[5][lane] = (uint32_t)h_obj;
+          o = ro;
+          d = rd;
+          pend = false;
+        }
+      }
+      PROF_PHASE(PF_P_HIT);
+      // ---- the swap: a path whose ray escaped ends here (as in the miss branch below), and a lane without a running
+      // path takes its stashed one — sample, Philox position and hit — into this iteration's shading
+      if (in_path && h_obj < 0 && stash_valid) {
+        end_path(pa, fr, rec, fold_l, fold_u, lane, fold_st, ring, h_nrm, depth, s, p_local);
+        in_path = false;
+      }
+      if (!in_path && stash_valid) {
+        h_pos = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
+        d = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
+        h_nrm = mk(stash.v[7][lane], stash.v[8][lane], stash.v[9][lane]);
+        h_obj = (int)stash.u[5][lane];
+        p_local = stash.u[0][lane]; pixel = stash.u[1][lane]; s = stash.u[2][lane]; s_end = stash.u[3][lane];
+        rng = rng_make(fr.seed, pixel, fr.sample_base + s, 0);
+        rng.draw = stash.u[4][lane];
+        rng.hi = (uint64_t)__double_as_longlong(stash.v[6][lane]);
+        stash_valid = false;
+        depth = 0;
+        in_path = true;
+      }
+      PROF_PHASE(PF_P_RAYGEN);
+    }
     if (in_path) {
       double t;
       D3 nrm;
       int obj;
-      if constexpr (IS_FLAT) {
-        t = INF;
-        nrm = mk(0, 0, 0);
-        if constexpr (FILTERED) obj = flat_query_filtered<false>(sc, &fl, o, d, -INF, t, nrm);
-        else obj = flat_query<false>(sc, &fl, o, d, -INF, t, nrm);
+      if constexpr (PRETRACE) {
+        obj = h_obj;
+        nrm = h_nrm;
       } else {
-        obj = closest_hit<LDS>(sc, o, d, t, nrm, kd_ldsp);
+        if constexpr (IS_FLAT) {
+          t = INF;
+          nrm = mk(0, 0, 0);
+          if constexpr (FILTERED) obj = flat_query_filtered<false>(sc, &fl, o, d, -INF, t, nrm);
+          else obj = flat_query<false>(sc, &fl, o, d, -INF, t, nrm);
+        } else {
+          obj = closest_hit<LDS>(sc, o, d, t, nrm, kd_ldsp);
+        }
+        n_ext++;
+        PROF_PHASE(PF_P_HIT);
       }
-      n_ext++;
-      PROF_PHASE(PF_P_HIT);
       D3 A;
       bool cont = false;
       if (obj < 0) {
         if constexpr (park_on) { esc = true; A = mk(0, 0, 0); }
+        else if constexpr (PRETRACE) A = nrm; // (the environment's colour, looked up at the closest hit)
         else {
 #ifdef RPT_PROF_PARK
           PROF_COUNT(PF_IK_CHILD);
@@ -651,7 +758,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         }
         PROF_PHASE(PF_P_ILLUM); // (-DRPT_PROF builds: the lookup's time shows in the "illuminate" row — in a scene without lights, e.g. glass.rs, it is that row)
       } else {
-        D3 world_pos = o + t * d;
+        D3 world_pos;
+        if constexpr (PRETRACE) world_pos = h_pos;
+        else world_pos = o + t * d;
         const Material* matp;
         if constexpr (IS_FLAT) matp = fl.obj_mat + obj;
         else matp = sc.materials + sc.insts[obj].material;
@@ -775,13 +884,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       }
     }
     if (ending) { // the path ended at this depth with radiance A_end
-      const uint32_t b = fold_st >> 16;
-      path_ended(pa, fr, rec, fold_l, fold_u, lane, fold_st, A_end, depth, b, s, p_local);
-      if (depth != 0u) {
-        uint32_t nb = b + depth + 1u; // the next path's header slot
-        if (nb >= ring) nb -= ring;
-        fold_st = (fold_st & 0xffffu) | (nb << 16);
-      }
+      end_path(pa, fr, rec, fold_l, fold_u, lane, fold_st, ring, A_end, depth, s, p_local);
       s++;
       in_path = false;
     }
