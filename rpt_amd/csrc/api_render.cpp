@@ -202,18 +202,18 @@ void ensure_workspace(rptgpu_scene* h, uint64_t cap, uint64_t rec_cols) {
 // ran (lane time / wave time, of 64), and for loop bodies the iteration count and the lanes per iteration.  One line
 // per slot that was used, machine-readable enough to be committed under profiles/ as it is.
 void print_prof(const KernelTable* kt, const char* what) {
-  static const char* const NAMES[24] = {
+  static const char* const NAMES[25] = {
       "tree_trace refill", "tree_trace node steps", "tree_trace box tests", "tree_trace pop", "tree_trace write-out",
       "tree_trace exact tests", "in-kernel node step", "in-kernel box batch", "in-kernel child test",
       "in-kernel triangle batch", "in-kernel object", "paths fetch", "paths raygen", "paths closest_hit",
       "paths illuminate", "paths visible", "paths nee_bsdf", "paths sample_f", "paths bsdf", "paths record",
-      "paths fold+store", "flat candidate walk", "fold iteration", "rejection round"};
-  unsigned long long t[4][24];
+      "paths fold+store", "flat candidate walk", "fold iteration", "rejection round", "paths fused query"};
+  unsigned long long t[4][25];
   if (!kt->read_prof(t)) return;
   unsigned long long tot = 0;
-  for (int i = 0; i < 24; i++) tot += t[0][i];
+  for (int i = 0; i < 25; i++) tot += t[0][i];
   std::fprintf(stderr, "prof[%s] %-28s %8s %10s %14s %10s\n", what, "phase", "time %", "lanes/64", "iterations", "lanes/64");
-  for (int i = 0; i < 24; i++) {
+  for (int i = 0; i < 25; i++) {
     if (!t[0][i] && !t[2][i]) continue;
     char a[32] = "-", b[32] = "-", c[32] = "-", d[32] = "-";
     if (t[0][i]) {
@@ -311,9 +311,10 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   h->lbuf.alloc(std::max<uint64_t>(1, (uint64_t)pl.spp_l * 3 * npix));
   if (print_launch)
     std::fprintf(stderr, "rpt_paths<%s>: %d blocks/CU x %d CUs -> %u blocks, %u samples per work item, %u launch(es) of %u spp, "
-                 "dynamic LDS %u B per wave (the flat scene's tables)%s\n",
+                 "dynamic LDS %u B per wave (the flat scene's tables)%s%s\n",
                  flat ? (lay.obj_filter ? "KdFlatF" : lay.n_tris ? "KdFlat" : "KdFlatG") : "KdLds", pl.per_cu, h->num_cus, pl.nblocks,
-                 pl.chunk, pl.n_launch, pl.spp_l, flat_lds, park ? " + parked environment lookups" : "");
+                 pl.chunk, pl.n_launch, pl.spp_l, flat_lds, park ? " + parked environment lookups" : "",
+                 flat && lay.n_tris && lay.fuse_query && !park ? ", shadow and bounce rays in one query" : "");
   h->counters.alloc(4);
   h->pcounters.alloc(16);
   HIP_TRY(hipMemsetAsync(h->pcounters.p, 0, 16 * sizeof(unsigned long long), st));

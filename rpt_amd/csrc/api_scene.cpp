@@ -341,7 +341,15 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
           }
           in.plane_idx = packed;
         }
-        lay.off_qtab = (uint32_t)off; off = up16(off + (uint64_t)(cnt[0] + cnt[1] + cnt[2]) * 64 * sizeof(double));
+        const uint64_t qtab_bytes = (uint64_t)(cnt[0] + cnt[1] + cnt[2]) * 64 * sizeof(double);
+        lay.off_qtab = (uint32_t)off; off = up16(off + qtab_bytes);
+        // one light, and it casts shadow rays: rpt_paths<KdFlat> traces a hit's shadow ray and bounce ray in one query,
+        // with the shadow ray's quotients in a second table behind the first — if the wave's share still holds it
+        if (RPT_FUSE_QUERY && RPT_RAY_STASH >= 2 && lay.n_tris && fs.lights.size() == 1 && fs.lights[0].kind != RPT_LIGHT_AMBIENT &&
+            up16(off + qtab_bytes) + RPT_PATHS_STASH_MAX_LDS <= WAVE_LDS) {
+          lay.fuse_query = 1;
+          off = up16(off + qtab_bytes);
+        }
         h->plane_vals.upload(planes, h->stream);
         HIP_TRY(hipStreamSynchronize(h->stream)); // `planes` dies with this block
         lay.plane_vals = h->plane_vals.p;

@@ -20,6 +20,12 @@
 #ifndef RPT_RAY_STASH
 #define RPT_RAY_STASH 2
 #endif
+// RPT_FUSE_QUERY=1: rpt_paths<KdFlat, false, true> traces a hit's shadow ray and bounce ray in one two-ray query
+// (kernels/paths.inc flat_query2) for a flat scene with a plane table and exactly one light, a non-ambient one (C2);
+// the host then keeps a second quotient table behind the first (FlatLayout::fuse_query).  0: the one-ray passes (A/B)
+#ifndef RPT_FUSE_QUERY
+#define RPT_FUSE_QUERY 1
+#endif
 #define RPT_PATHS_STASH_LDS 4864u
 #define RPT_PATHS_STASH_HIT_LDS 6656u
 // what the host leaves room for in a KdFlat scene's LDS layout (api_scene.cpp)
@@ -53,6 +59,9 @@ struct FlatLayout {
   const rptdev::LeafBox* obj_box; // [objects] in device memory
   const double* obj_grid;        // qlo[3], qscale[3], bounds[6] of the grid, device memory
   uint64_t obj_always;
+  // rpt_paths<KdFlat, false, true> (RPT_FUSE_QUERY): the quotient table is doubled, the shadow ray's half right behind
+  // the bounce ray's (api_scene.cpp; kernels/launch.inc selects the fused kernel by it)
+  uint32_t fuse_query;
 };
 
 // buffers of the optional ray sort in front of a per-tree traversal (all sized for the query's n)
@@ -159,7 +168,7 @@ struct KernelTable {
                           double* out);
   // -DRPT_PROF builds: the per-phase table of kernels/prof.inc since the last call ([0] wave cycles, [1] lane cycles,
   // [2] wave iterations, [3] lane iterations); false in regular builds
-  bool (*read_prof)(unsigned long long out[4][24]);
+  bool (*read_prof)(unsigned long long out[4][25]);
   // in-kernel-traversal scenes: the next depth's paths sorted by ray key into the current state arrays (kernels/wavefront.inc)
   void (*path_reorder)(hipStream_t, const rptdev::PathState&, uint32_t n, bool sorted, const SortBufs* sort, uint32_t* order);
 };

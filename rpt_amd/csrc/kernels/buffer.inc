@@ -83,6 +83,9 @@ __global__ void __launch_bounds__(256) rpt_eval_math(int fn, uint64_t n, const d
 template __global__ void rpt_paths<KdLds, false>(Scene, Frame, Camera, PersistArgs);
 template __global__ void rpt_paths<KdFlat, false>(Scene, Frame, Camera, PersistArgs);
 template __global__ void rpt_paths<KdFlat, true>(Scene, Frame, Camera, PersistArgs);
+#if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
+template __global__ void rpt_paths<KdFlat, false, true>(Scene, Frame, Camera, PersistArgs); // (C2: one light)
+#endif
 template __global__ void rpt_paths<KdFlatG, false>(Scene, Frame, Camera, PersistArgs);
 template __global__ void rpt_paths<KdFlatG, true>(Scene, Frame, Camera, PersistArgs);
 template __global__ void rpt_paths<KdFlatF, false>(Scene, Frame, Camera, PersistArgs);

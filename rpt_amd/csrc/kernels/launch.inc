@@ -66,6 +66,10 @@ int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool par
 #define RPT_OCC(L) (park ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<L, true>, 64, lds_bytes) \
                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<L, false>, 64, lds_bytes))
   if (flat && flat->obj_filter) e = RPT_OCC(KdFlatF);
+#if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
+  else if (flat && flat->n_tris && flat->fuse_query && !park)
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<KdFlat, false, true>, 64, lds_bytes);
+#endif
   else if (flat && flat->n_tris) e = RPT_OCC(KdFlat);
   else if (flat) e = RPT_OCC(KdFlatG);
   else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<KdLds, false>, 64, lds_bytes); // (never parks: its stack fills the wave's LDS)
@@ -88,6 +92,11 @@ void launch_paths(hipStream_t st, const Scene& sc, const Frame& fr, const Camera
 #define RPT_GO(L) do { if (park) hipLaunchKernelGGL((rpt_paths<L, true>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa); \
                        else hipLaunchKernelGGL((rpt_paths<L, false>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa); } while (0)
   if (flat && lay.obj_filter) RPT_GO(KdFlatF);
+#if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
+  // one light that casts shadow rays (the host doubled the quotient table for it): the two-ray form (kernels/paths.inc)
+  else if (flat && lay.n_tris && lay.fuse_query && !park)
+    hipLaunchKernelGGL((rpt_paths<KdFlat, false, true>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa);
+#endif
   else if (flat && lay.n_tris) RPT_GO(KdFlat);
   else if (flat) RPT_GO(KdFlatG);
   else hipLaunchKernelGGL((rpt_paths<KdLds, false>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa);
@@ -248,8 +257,8 @@ void launch_eval_math(hipStream_t st, int fn, uint64_t n, const double* x, const
 
 // debug builds with -DRPT_PROF: the per-phase table of kernels/prof.inc accumulated so far (and reset):
 // out[0] wave cycles, [1] lane cycles, [2] wave iterations, [3] lane iterations, PROF_SLOTS slots each
-bool read_prof(unsigned long long out[4][24]) {
-  static_assert(PROF_SLOTS == 24, "kernels.h declares the table with 24 slots");
+bool read_prof(unsigned long long out[4][25]) {
+  static_assert(PROF_SLOTS == 25, "kernels.h declares the table with 25 slots");
 #ifdef RPT_PROF
   static unsigned long long zero[4][PROF_SLOTS];
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof zero) != hipSuccess) return false;

@@ -38,6 +38,12 @@
 // (no record, no header: its sample goes straight to lbuf) or writes its level-0 record.  Still at most one record per
 // iteration, every header written (path_ended) before the fold step of the same iteration, and the bound above stands
 // (tests/test_ray_stash_swap_model.py).
+// With the fused query (FUSE below) an iteration runs: take the hit (the previous iteration's bounce result, or the
+// stashed one: a path whose bounce ray escaped ends here, at the swap, as above) -> shade it and write the record's f,
+// 1/pdf and |wi.n| -> the two-ray query -> the record's A, or the path's end -> one fold step.  The record of level
+// `depth` is the only one written in the iteration, and into the slot it had before, so per lane and iteration the ring
+// sees the same events in the same order as above: at most one record, the headers before the fold step; the bound
+// stands.
 //
 // Environment lookups are PARKED (round 5; flat scenes whose environment is a texture).  A ray that escapes ends its
 // path with Hdri::get_color (environment.rs:25-52: atan2, acos, four texels) — one round of it per loop iteration for
@@ -341,6 +347,129 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
   return obj;
 }
 
+// ------------------------------------------------------------------ a hit's shadow ray and bounce ray in one pass
+// flat_query<false> of the bounce ray (o, db) and flat_query<true> of the shadow ray (o, ds, t_stop) in one walk over the
+// objects (rpt_paths<KdFlat, false, true>; the host keeps a plane table and a second quotient table for it).  Each ray
+// keeps its own record and visits the objects in object order, so every accept is the one its own query makes: the
+// bounce slot's record (rtb, rnb, the object returned) is flat_query<false>'s, and the shadow slot's rts decides
+// visibility as flat_query<true>'s does — it only skips work once rts <= t_stop, and rts never grows again, so
+// `rts > t_stop` comes out the same.  What the shared origin allows is computed once: the plane-table numerators
+// pv - o and each cube's inv * o.  The two rays' slab quotients, wall candidates and cube candidates sit side by side in
+// straight-line code, so that the two dependency chains overlap.
+// A slot that is off (no bounce ray: the path ends at this hit) enters with its record at -inf: no test accepts.
+RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, double t_stop, double& rtb, D3& rnb,
+                        double& rts) {
+  int obj = -1;
+  const int n = sc.num_objects;
+  const uint32_t lane = __lane_id();
+  const uint32_t nx = fl->plane_cnt & 15u, ny = (fl->plane_cnt >> 4) & 15u, nz = (fl->plane_cnt >> 8) & 15u;
+  const uint32_t nq = nx + ny + nz;
+  { // both rays' quotients (pv - o) / d: one numerator, two divisions (the bounce ray's table first, the shadow ray's behind it)
+    const double RPT_C* pv = (const double RPT_C*)fl->plane_vals;
+    double* qb = fl->qtab + lane;
+    double* qs = qb + nq * 64u;
+    for (uint32_t j = 0; j < nx; j++) { const double a = pv[j] - o.x; qb[j * 64u] = a / db.x; qs[j * 64u] = a / ds.x; }
+    for (uint32_t j = 0; j < ny; j++) {
+      const double a = pv[4u + j] - o.y;
+      qb[(nx + j) * 64u] = a / db.y; qs[(nx + j) * 64u] = a / ds.y;
+    }
+    for (uint32_t j = 0; j < nz; j++) {
+      const double a = pv[8u + j] - o.z;
+      qb[(nx + ny + j) * 64u] = a / db.z; qs[(nx + ny + j) * 64u] = a / ds.z;
+    }
+  }
+  int i = 0;
+  while (i < n) {
+    CInst& in = cinst(sc, i);
+    if (in.kind == RPT_SHAPE_MESH && !in.has_xf && in.plane_use) { // a run of table users (flat_query above), both rays
+      uint32_t cb = 0, cs = 0;
+      double mb[FLAT_RUN], ms[FLAT_RUN];
+      const int len = (int)in.plane_use;
+      const double* qtb = fl->qtab + lane;
+      const double* qts = qtb + nq * 64u;
+      switch (len) {
+        case 1: cb = run_slabs<1>(sc, i, qtb, rtb, mb); cs = run_slabs<1>(sc, i, qts, rts, ms); break;
+        case 2: cb = run_slabs<2>(sc, i, qtb, rtb, mb); cs = run_slabs<2>(sc, i, qts, rts, ms); break;
+        case 3: cb = run_slabs<3>(sc, i, qtb, rtb, mb); cs = run_slabs<3>(sc, i, qts, rts, ms); break;
+        case 4: cb = run_slabs<4>(sc, i, qtb, rtb, mb); cs = run_slabs<4>(sc, i, qts, rts, ms); break;
+        case 5: cb = run_slabs<5>(sc, i, qtb, rtb, mb); cs = run_slabs<5>(sc, i, qts, rts, ms); break;
+        default: cb = run_slabs<FLAT_RUN>(sc, i, qtb, rtb, mb); cs = run_slabs<FLAT_RUN>(sc, i, qts, rts, ms); break;
+      }
+      if (rts <= t_stop) cs = 0u; // (the shadow ray is blocked already)
+      while (__ballot((cb | cs) != 0u) != 0ull) {
+        PROF_COUNT(PF_P_CAND);
+        if (cb != 0u) { // the bounce ray's next candidate
+          const int k = __ffs((int)cb) - 1;
+          cb &= cb - 1u;
+          double mt = mb[0];
+#pragma unroll
+          for (int kk = 1; kk < FLAT_RUN; kk++) mt = k == kk ? mb[kk] : mt;
+          if (!(mt > rtb)) {
+            const uint32_t* e = fl->obj_leaf[i + k];
+            LaneTree lt{e[0], e[1]};
+            KdNode nd;
+            nd.split = 0.0; nd.a = e[2]; nd.ib = (e[3] << 2) | 3u;
+            if (kd_leaf<true, false>(sc, lt, sc.refs + lt.ref_base, nd, o, db, EPSILON, -INF, rtb, rnb)) obj = i + k;
+          }
+        }
+        if (cs != 0u) { // the shadow ray's
+          const int k = __ffs((int)cs) - 1;
+          cs &= cs - 1u;
+          double mt = ms[0];
+#pragma unroll
+          for (int kk = 1; kk < FLAT_RUN; kk++) mt = k == kk ? ms[kk] : mt;
+          if (!(mt > rts)) {
+            const uint32_t* e = fl->obj_leaf[i + k];
+            LaneTree lt{e[0], e[1]};
+            KdNode nd;
+            nd.split = 0.0; nd.a = e[2]; nd.ib = (e[3] << 2) | 3u;
+            D3 srn = mk(0, 0, 0);
+            kd_leaf<true, true>(sc, lt, sc.refs + lt.ref_base, nd, o, ds, EPSILON, t_stop, rts, srn);
+            if (rts <= t_stop) cs = 0u;
+          }
+        }
+      }
+      i += len;
+    } else if (in.kind == RPT_SHAPE_CUBE && in.has_xf && i + 1 < n && cinst(sc, i + 1).kind == RPT_SHAPE_CUBE &&
+               cinst(sc, i + 1).has_xf) {
+      // two consecutive Transformed<Cube> (flat_query above): cube by cube, both rays' candidates side by side, each
+      // accepted in object order by its own record
+      CInst* cu[2] = {&in, &cinst(sc, i + 1)};
+#pragma unroll
+      for (int c = 0; c < 2; c++) {
+        const CInst& q = *cu[c];
+        const D3 lo = mat4_mul(q.inv, o, 1.0);
+        const D3 lb = mat4_mul(q.inv, db, 0.0), ls = mat4_mul(q.inv, ds, 0.0);
+        const RcpD bx = rcp_make(lb.x), by = rcp_make(lb.y), bz = rcp_make(lb.z);
+        const RcpD sx = rcp_make(ls.x), sy = rcp_make(ls.y), sz = rcp_make(ls.z);
+        double tb = 0.0, ts = 0.0;
+        D3 nb = mk(0, 0, 0), ns = mk(0, 0, 0);
+        const bool hb = cube_candidate(lo, bx, by, bz, EPSILON, tb, nb);
+        const bool hs = cube_candidate(lo, sx, sy, sz, EPSILON, ts, ns);
+        if (hb && tb < rtb) {
+          rtb = tb;
+          rnb = normalize(mat3_mul(q.nrm, nb)); // Transformed::intersect shape.rs:131-132
+          obj = i + c;
+        }
+        if (hs && ts < rts) rts = ts;
+      }
+      i += 2;
+    } else { // anything else: the object's own test, once per ray
+      if (!(rtb == -INF)) {
+        const RcpD rx = rcp_make(db.x), ry = rcp_make(db.y), rz = rcp_make(db.z);
+        if (isect_inst<KdFlat, false>(sc, in, o, db, rx, ry, rz, EPSILON, -INF, rtb, rnb, (KdFlat*)nullptr)) obj = i;
+      }
+      if (!(rts <= t_stop)) {
+        const RcpD rx = rcp_make(ds.x), ry = rcp_make(ds.y), rz = rcp_make(ds.z);
+        D3 srn = mk(0, 0, 0);
+        isect_inst<KdFlat, true>(sc, in, o, ds, rx, ry, rz, EPSILON, t_stop, rts, srn, (KdFlat*)nullptr);
+      }
+      i++;
+    }
+  }
+  return obj;
+}
+
 template <class LDS> struct PathsLds { using type = LDS; };
 template <> struct PathsLds<KdFlat> { struct type { int unused; }; };
 // KdFlatG: the same kernel with the triangles (vertex normals, light sampling) left in GLOBAL memory, for flat scenes
@@ -484,7 +613,8 @@ RPT_DEV void end_path(const PersistArgs& pa, const Frame& fr, double* __restrict
     fold_st = (fold_st & 0xffffu) | (nb << 16);
   }
 }
-template <class LDS, bool PARK /* environment lookups parked per lane (pa.park_off) */>
+template <class LDS, bool PARK /* environment lookups parked per lane (pa.park_off) */,
+          bool FUSE = false /* a hit's shadow ray and bounce ray in one query (FUSE below) */>
 __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame fr, Camera cam, PersistArgs pa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char flat_smem[]; // KdFlat only (dynamic size)
   __shared__ typename PathsLds<LDS>::type kd_store; // KdLds: the wave's traversal stack (15 KB); KdFlat: unused
@@ -577,6 +707,17 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
   // lives across a query.  The wave refills when a lane must (as above) or when RPT_STASH_REFILL_MIN lanes could.
   constexpr bool STASH = RPT_RAY_STASH && std::is_same<LDS, KdFlat>::value;
   constexpr bool PRETRACE = STASH && RPT_RAY_STASH >= 2 && !PARK;
+  //
+  // FUSE (rpt_paths<KdFlat, false, true>: a flat scene with a plane table and one light, a non-ambient one — C2): a hit's
+  // shadow ray and bounce ray leave from the same point, and the shadow ray's answer only decides whether the light term
+  // is added (renderer.rs:185-201: illuminate draws, then sample_f draws, whatever the shadow ray meets).  So an
+  // iteration takes its hit (the previous iteration's bounce result, or a stashed pre-traced one), shades it — illuminate,
+  // the light term's bsdf, sample_f, the bounce's bsdf, in the reference's order — and then traces BOTH rays in one
+  // two-ray query (flat_query2): it yields this hit's visibility and the next iteration's hit.  The record's f, 1/pdf and
+  // |wi.n| go to the ring before the query and A after it, so no material, normal or wo lives across it.  The pending
+  // pre-traces of a refill run in a pass of their own.  Per lane and iteration the ring sees the same events as without
+  // FUSE (a path that escaped ends when its hit is taken, before the shading), so the bound at the top of this file holds.
+  static_assert(!FUSE || PRETRACE, "the fused form is a form of the pre-traced kernel");
   using StashT = typename std::conditional<PRETRACE, RayStashHit, RayStash>::type;
   __shared__ typename std::conditional<STASH, StashT, int>::type stash_store;
   auto& stash = *reinterpret_cast<StashT*>(&stash_store);
@@ -587,6 +728,8 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
   constexpr bool park_on = PARK;
   ParkLds& park = *reinterpret_cast<ParkLds*>(flat_smem + (park_on ? pa.park_off : 0u));
   uint32_t pcnt = 0, park_hd = 0xffffffffu, park_recs = 0; // entries in the lane's queue; (top of this file); records they hold
+  D3 nx_pos = mk(0, 0, 0), nx_nrm = mk(0, 0, 0); // FUSE: the hit of the running path's bounce ray (as h_pos, h_nrm, h_obj)
+  int nx_obj = -1;
   PROF_INIT(); // -DRPT_PROF builds: wave / lane time per phase, printed by api_render.cpp under RPTGPU_PRINT_PHASES
 
   for (;;) {
@@ -668,7 +811,28 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
     // PRETRACE: the hit a lane shades — its point o + t d; its normal, or the environment's colour if the ray escaped
     D3 h_pos = mk(0, 0, 0), h_nrm = mk(0, 0, 0);
     int h_obj = -1;
-    if constexpr (PRETRACE) {
+    if constexpr (FUSE) {
+      // ---- the running path's hit is its bounce ray's, found by the previous iteration's query; a refill's pending
+      // pre-traces run here, in a pass of their own
+      h_pos = nx_pos; h_nrm = nx_nrm; h_obj = nx_obj;
+      nx_pos = mk(0, 0, 0); nx_nrm = mk(0, 0, 0); nx_obj = -1; // (so that no old value lives across the queries below)
+      if (__ballot(pend) != 0ull) {
+        if (pend) {
+          const D3 so = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
+          const D3 sd = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
+          double t = INF;
+          D3 hn = mk(0, 0, 0);
+          const int ho = flat_query<false>(sc, &fl, so, sd, -INF, t, hn);
+          n_ext++;
+          if (ho < 0) hn = env_color(sc, sd); // renderer.rs:147
+          const D3 hp = so + t * sd;
+          stash.v[0][lane] = hp.x; stash.v[1][lane] = hp.y; stash.v[2][lane] = hp.z;
+          stash.v[7][lane] = hn.x; stash.v[8][lane] = hn.y; stash.v[9][lane] = hn.z;
+          stash.u[5][lane] = (uint32_t)ho;
+          pend = false;
+        }
+      }
+    } else if constexpr (PRETRACE) {
       // ---- closest hits: pass 0 (only when some lane has both) the pending pre-traces, pass 1 the running paths and
       // the pre-traces of lanes without one.  Every pass resets what the query writes, so no lane's result of pass 0
       // lives in registers across the query of pass 1.
@@ -704,6 +868,8 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
           pend = false;
         }
       }
+    }
+    if constexpr (PRETRACE) {
       PROF_PHASE(PF_P_HIT);
       // ---- the swap: a path whose ray escaped ends here (as in the miss branch below), and a lane without a running
       // path takes its stashed one — sample, Philox position and hit — into this iteration's shading
@@ -726,7 +892,65 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       }
       PROF_PHASE(PF_P_RAYGEN);
     }
-    if (in_path) {
+    if constexpr (FUSE) {
+      if (in_path && h_obj < 0) { // the ray escaped and the lane had no stash to take: A is the environment's colour
+        PROF_PHASE(PF_P_ILLUM);
+        ending = true;
+        A_end = h_nrm;
+      } else if (in_path) {
+        const D3 world_pos = h_pos, nrm = h_nrm;
+        const Material& mat = fl.obj_mat[h_obj];
+        const D3 wo = -normalize(d);
+        const D3 color = mat.emittance * ld3(mat.color);
+        D3 intensity, wl;
+        double dist;
+        illuminate(sc, clight(sc, 0), world_pos, rng, intensity, wl, dist); // sample_lights, renderer.rs:177-204
+        n_sh++;
+        PROF_PHASE(PF_P_ILLUM);
+        // the light term, as it is added if the shadow ray gets through (bsdf is pure: evaluating it either way changes nothing)
+        const D3 lt = mk(0, 0, 0) + cmul(bsdf(mat, nrm, wo, wl), intensity) * dot(wl, nrm);
+        PROF_PHASE(PF_P_NEE);
+        D3 wi = wl;
+        double pdf = 1.0;
+        const bool cont = depth < fr.max_bounces && sample_f(mat, nrm, wo, rng, wi, pdf);
+        PROF_PHASE(PF_P_SAMPLE);
+        if (cont) { // the record's f, 1/pdf and |wi.n| now, its A after the query
+          const D3 f = bsdf(mat, nrm, wo, wi);
+          PROF_PHASE(PF_P_BSDF);
+          uint32_t pos = (fold_st >> 16) + 1u + depth; // slot b is the path's header, b + 1 + k its level k
+          if (pos >= ring) pos -= ring;
+          double* r = rec + pos * REC_FIELDS;
+          r[3] = f.x; r[4] = f.y; r[5] = f.z;
+          r[6] = 1.0 / pdf;
+          r[7] = fabs(dot(wi, nrm));
+          PROF_PHASE(PF_P_RECORD);
+        }
+        // ---- the fused query: this hit's visibility towards the light, and the closest hit of its bounce ray
+        double rtb = cont ? INF : -INF, rts = INF;
+        D3 rnb = mk(0, 0, 0);
+        const double t_stop = fmin(dist, 1.7976931348623157e308); // as in visible()
+        d = wi; // (a path that ends here needs d no more: the incoming direction does not live across the query)
+        const int nobj = flat_query2(sc, &fl, world_pos, d, wl, t_stop, rtb, rnb, rts);
+        const bool vis = rts > t_stop; // (false for a NaN hit: see visible(), traversal.inc)
+        PROF_PHASE(PF_P_FUSED);
+        const D3 A = color + (vis ? lt : mk(0, 0, 0));
+        if (cont) {
+          uint32_t pos = (fold_st >> 16) + 1u + depth;
+          if (pos >= ring) pos -= ring;
+          double* r = rec + pos * REC_FIELDS;
+          r[0] = A.x; r[1] = A.y; r[2] = A.z;
+          n_ext++;
+          nx_pos = world_pos + rtb * d;
+          nx_nrm = nobj < 0 ? env_color(sc, d) : rnb; // renderer.rs:147
+          nx_obj = nobj;
+          depth++;
+        } else {
+          ending = true;
+          A_end = A;
+        }
+        PROF_PHASE(PF_P_RECORD);
+      }
+    } else if (in_path) {
       double t;
       D3 nrm;
       int obj;

@@ -11,7 +11,7 @@
 // The first active lane does the bookkeeping (a handful of DS operations), so a mark may sit in divergent code.
 // Regular builds compile all of this to nothing.
 #ifdef RPT_PROF
-constexpr int PROF_SLOTS = 24;
+constexpr int PROF_SLOTS = 25;
 struct ProfLds {
   long long mark[4];
   unsigned long long wt[4][PROF_SLOTS], lt[4][PROF_SLOTS]; // wave cycles, lane cycles
@@ -65,7 +65,7 @@ __device__ __forceinline__ void prof_flush() { // at the end of the kernel, all 
 #define PROF_COUNT(i) prof_count(i)
 #define PROF_FLUSH() prof_flush()
 #else
-constexpr int PROF_SLOTS = 24;
+constexpr int PROF_SLOTS = 25;
 #define PROF_INIT() do { } while (0)
 #define PROF_PHASE(i) do { } while (0)
 #define PROF_COUNT(i) do { } while (0)
@@ -81,5 +81,7 @@ enum {
   PF_P_FETCH = 11, PF_P_RAYGEN = 12, PF_P_HIT = 13, PF_P_ILLUM = 14, PF_P_VIS = 15, PF_P_NEE = 16, PF_P_SAMPLE = 17,
   PF_P_BSDF = 18, PF_P_RECORD = 19, PF_P_FOLD = 20,
   // loops inside rpt_paths<KdFlat> (iteration counts only)
-  PF_P_CAND = 21, PF_P_FOLDIT = 22, PF_P_REJECT = 23
+  PF_P_CAND = 21, PF_P_FOLDIT = 22, PF_P_REJECT = 23,
+  // rpt_paths<KdFlat, false, true>: the two-ray query of a hit's shadow ray and bounce ray (flat_query2)
+  PF_P_FUSED = 24
 };
