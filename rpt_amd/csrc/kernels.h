@@ -26,6 +26,12 @@
 #ifndef RPT_FUSE_QUERY
 #define RPT_FUSE_QUERY 1
 #endif
+// RPT_SHADE_SPLIT=1: in rpt_paths<KdFlat, false, true>, a wave whose light is an untransformed mesh and whose hits are
+// opaque takes every draw of its hits first and then shades them in one straight-line block (kernels/paths.inc
+// hit_draws); 0: the sequence of illuminate, bsdf, sample_f and bsdf (A/B builds)
+#ifndef RPT_SHADE_SPLIT
+#define RPT_SHADE_SPLIT 1
+#endif
 #define RPT_PATHS_STASH_LDS 4864u
 #define RPT_PATHS_STASH_HIT_LDS 6656u
 // what the host leaves room for in a KdFlat scene's LDS layout (api_scene.cpp)
@@ -168,7 +174,7 @@ struct KernelTable {
                           double* out);
   // -DRPT_PROF builds: the per-phase table of kernels/prof.inc since the last call ([0] wave cycles, [1] lane cycles,
   // [2] wave iterations, [3] lane iterations); false in regular builds
-  bool (*read_prof)(unsigned long long out[4][25]);
+  bool (*read_prof)(unsigned long long out[4][27]);
   // in-kernel-traversal scenes: the next depth's paths sorted by ray key into the current state arrays (kernels/wavefront.inc)
   void (*path_reorder)(hipStream_t, const rptdev::PathState&, uint32_t n, bool sorted, const SortBufs* sort, uint32_t* order);
 };

@@ -470,6 +470,112 @@ RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, 
   return obj;
 }
 
+#if RPT_SHADE_SPLIT
+// ------------------------------------------------------------------ a hit's draws first, its shading in one block
+// The fast form of the fused kernel's shading (rpt_paths<KdFlat, false, true>, RPT_SHADE_SPLIT): a wave whose light is
+// an untransformed mesh and whose shading lanes all hit opaque materials (C2).  Every draw of a hit is taken first, in
+// the reference's order and by its own loops: illuminate's triangle index and (u, v) pairs until u + v <= 1, then, if
+// the path goes on, gen_bool(f), u_theta for the specular lobe and +-1 pairs until one is accepted (sample_f).  What
+// the draws decide is kept as their integers, and the shading that follows is one straight-line block.
+// (One loop for the whole sequence, a Philox block per lane and round with each lane stepping through its own state
+// machine, was measured too: the per-round selects of that state cost far more than the blocks it saved, 25 % slower.)
+struct HitDraws {
+  uint64_t tri;   // the light triangle's index
+  uint64_t a, b;  // the (u, v) pair that was kept
+  uint64_t th;    // u_theta's draw (the specular lobe; a dummy 0.5 otherwise)
+  uint64_t qa, qb; // the +-1 pair that was kept
+  bool spec;      // gen_bool(f)
+};
+// sf: sample_f runs (depth < max_bounces); f: sample_f's lobe probability
+RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, HitDraws& o) {
+  o.tri = gen_index_zone(r, n, zone);
+  next2_u64(r, o.a, o.b);
+  while ((o.a >> 11) + (o.b >> 11) >= (1ull << 53) + 2ull) {
+    PROF_COUNT(PF_P_REJECT);
+    next2_u64(r, o.a, o.b);
+  }
+  o.th = 1ull << 63; o.qa = 0; o.qb = 0; o.spec = false;
+  if (!sf) return;
+  o.spec = gen_bool(r, f);
+  if (o.spec) o.th = next_u64(r);
+  for (;;) {
+    PROF_COUNT(PF_P_REJECT);
+    next2_u64(r, o.qa, o.qb);
+    const double x = u52_of(o.qa) * 2.0 + -1.0, y = u52_of(o.qb) * 2.0 + -1.0;
+    const double sum = x * x + y * y;
+    if (o.spec ? sum < 1.0 : sum <= 1.0) break;
+  }
+}
+
+// bsdf() for an opaque material: both directions outside (the reflection case) or zero, its early return a select
+RPT_DEV D3 bsdf_opaque(const Material& m, D3 n, D3 wo, D3 wi) { // material.rs:125-170
+  D3 color = ld3(m.color);
+  double n_dot_wi = dot(n, wi);
+  double n_dot_wo = dot(n, wo);
+  const bool lit = !__builtin_signbit(n_dot_wi) && !__builtin_signbit(n_dot_wo);
+  const D3 one = mk(1, 1, 1);
+  double m2 = m.roughness * m.roughness;
+  D3 h = normalize(wi + wo); // (wi * 1.0 + wo in bsdf)
+  double wo_dot_h = dot(wo, h);
+  double n_dot_h = dot(n, h);
+  double nh2 = pow2(n_dot_h);
+  double dd = rptc_exp((nh2 - 1.0) / (m2 * nh2)) / (m2 * PI * nh2 * nh2);
+  double f0s = pow2((m.index - 1.0) / (m.index + 1.0));
+  D3 f0 = lerp(mk(f0s, f0s, f0s), color, m.metallic);
+  D3 f = f0 + (one - f0) * pow5(1.0 - wo_dot_h);
+  double ga = n_dot_wi * n_dot_h, gb = n_dot_wo * n_dot_h;
+  double g = fmin(ga, gb);
+  g = (2.0 * g) / wo_dot_h;
+  g = fmin(g, 1.0);
+  D3 q = dd * f * g / (4.0 * n_dot_wo * n_dot_wi);
+  D3 diffuse = cmul(one - f, color) / PI;
+  return lit ? q + diffuse : mk(0, 0, 0);
+}
+
+// sample_f() for an opaque material on the drawn values: both lobes' local vectors, the lane's one behind a select
+RPT_DEV void sample_f_opaque(const Material& m, D3 n, D3 wo, double f, const HitDraws& dr, D3& wi, double& pdf) {
+  double m2 = m.roughness * m.roughness; // material.rs:224-313
+  const double u_theta = (double)(dr.th >> 11) * (1.0 / 9007199254740992.0);
+  const double x = u52_of(dr.qa) * 2.0 + -1.0, y = u52_of(dr.qb) * 2.0 + -1.0;
+  const double sum = x * x + y * y;
+  double theta = rptc_atan(sqrt(m2 * -rpt_log(u_theta)));
+  double sin_t, cos_t;
+  rptc_sincos_pio2(theta, &sin_t, &cos_t);
+  double diff = x * x - y * y;
+  double cx = diff / sum, cy = 2.0 * x * y / sum;
+  const D3 loc = dr.spec ? mk(cx * sin_t, cy * sin_t, cos_t) : mk(x, y, sqrt(1.0 - x * x - y * y));
+  const D3 world = local_to_world_mul(n, loc);
+  wi = dr.spec ? -(wo - world * (dot(world, wo) * 2.0)) : world; // -glm::reflect_vec(wo, h)
+  double p = 0.0;
+  {
+    D3 h = normalize(wi + wo);
+    double p_h = beckmann_pdf(m2, n, h);
+    p += f * p_h / (4.0 * fabs(dot(h, wo)));
+  }
+  p += (1.0 - f) * fmax(dot(wi, n), 0.0) * FRAC_1_PI;
+  pdf = p;
+}
+
+// illuminate() of an untransformed mesh light on the drawn values (light.rs:23-47, mesh.rs:84-98, kdtree.rs:138-143)
+RPT_DEV void illuminate_mesh(CLight& l, CTree& tr, const Tri* __restrict__ tp, D3 pos, const HitDraws& dr, D3& intensity,
+                             D3& wi, double& dist) {
+  const double u = (double)(dr.a >> 11) * (1.0 / 9007199254740992.0), v = (double)(dr.b >> 11) * (1.0 / 9007199254740992.0);
+  double w = 1.0 - u - v;
+  D3 v1 = ld3(tp->v), v2 = ld3(tp->v + 3), v3 = ld3(tp->v + 6);
+  D3 n1 = ld3(tp->v + 9), n2 = ld3(tp->v + 12), n3 = ld3(tp->v + 15);
+  double area = 0.5 * length(cross(v2 - v1, v3 - v1));
+  SampleOut s{u * v1 + v * v2 + w * v3, normalize(u * n1 + v * n2 + w * n3), 1.0 / area};
+  s.p = s.p / (double)tr.num_prims;
+  D3 disp = s.v - pos;
+  double len = length(disp);
+  double cosine = fmax(-dot(disp, s.n), 0.0) / len;
+  double surface_area = fmax(cosine, 0.0) / (len * len);
+  intensity = ld3(l.mat_color) * l.mat_emittance * surface_area / s.p;
+  wi = disp / len;
+  dist = len;
+}
+#endif
+
 template <class LDS> struct PathsLds { using type = LDS; };
 template <> struct PathsLds<KdFlat> { struct type { int unused; }; };
 // KdFlatG: the same kernel with the triangles (vertex normals, light sampling) left in GLOBAL memory, for flat scenes
@@ -902,17 +1008,59 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         const Material& mat = fl.obj_mat[h_obj];
         const D3 wo = -normalize(d);
         const D3 color = mat.emittance * ld3(mat.color);
-        D3 intensity, wl;
+        D3 wl, lt, wi;
         double dist;
+        bool cont;
+#if RPT_SHADE_SPLIT
+        // SHADE_SPLIT (hit_draws above): a wave whose light is an untransformed mesh and whose lanes hit opaque
+        // materials only takes every draw of its hits first and then shades them in one straight-line block: illuminate's tail and the light term's bsdf, sample_f's math and the bounce's bsdf, the two chains side
+        // by side, selects in place of branches.  Each value keeps its operations in their order.  A point or
+        // directional light, a transformed light or a glass surface in the wave takes the sequence below.
+        CLight& lg = clight(sc, 0);
+        CInst& li = cinst(sc, lg.inst);
+        if (lg.kind == RPT_LIGHT_OBJECT && li.kind == RPT_SHAPE_MESH && !li.has_xf && __ballot(mat.transparent != 0) == 0ull) {
+          CTree& tr = ctree(sc, li.tree);
+          const D3 mc = ld3(mat.color);
+          const double f0 = pow2((mat.index - 1.0) / (mat.index + 1.0)); // sample_f's lobe probability (material.rs)
+          const double mean = ((mc.x + mc.y) + mc.z) / 3.0;
+          double fs = (1.0 - mat.metallic) * f0 + mat.metallic * mean;
+          fs = fs * (1.0 - 0.2) + 1.0 * 0.2;
+          cont = depth < fr.max_bounces;
+          HitDraws dr;
+          hit_draws(rng, cont, tr.num_prims, tr.sample_zone, fs, dr);
+          n_sh++;
+          PROF_PHASE(PF_P_DRAWS);
+          D3 intensity;
+          illuminate_mesh(lg, tr, sc.tris + tr.prim_base + dr.tri, world_pos, dr, intensity, wl, dist);
+          double pdf;
+          sample_f_opaque(mat, nrm, wo, fs, dr, wi, pdf);
+          lt = mk(0, 0, 0) + cmul(bsdf_opaque(mat, nrm, wo, wl), intensity) * dot(wl, nrm);
+          const D3 f = bsdf_opaque(mat, nrm, wo, wi);
+          PROF_PHASE(PF_P_SHADE);
+          if (cont) { // the record's f, 1/pdf and |wi.n| now, its A after the query
+            uint32_t pos = (fold_st >> 16) + 1u + depth; // slot b is the path's header, b + 1 + k its level k
+            if (pos >= ring) pos -= ring;
+            double* r = rec + pos * REC_FIELDS;
+            r[3] = f.x; r[4] = f.y; r[5] = f.z;
+            r[6] = 1.0 / pdf;
+            r[7] = fabs(dot(wi, nrm));
+          } else {
+            wi = wl;
+          }
+          PROF_PHASE(PF_P_RECORD);
+        } else
+#endif
+        {
+        D3 intensity;
         illuminate(sc, clight(sc, 0), world_pos, rng, intensity, wl, dist); // sample_lights, renderer.rs:177-204
         n_sh++;
         PROF_PHASE(PF_P_ILLUM);
         // the light term, as it is added if the shadow ray gets through (bsdf is pure: evaluating it either way changes nothing)
-        const D3 lt = mk(0, 0, 0) + cmul(bsdf(mat, nrm, wo, wl), intensity) * dot(wl, nrm);
+        lt = mk(0, 0, 0) + cmul(bsdf(mat, nrm, wo, wl), intensity) * dot(wl, nrm);
         PROF_PHASE(PF_P_NEE);
-        D3 wi = wl;
+        wi = wl;
         double pdf = 1.0;
-        const bool cont = depth < fr.max_bounces && sample_f(mat, nrm, wo, rng, wi, pdf);
+        cont = depth < fr.max_bounces && sample_f(mat, nrm, wo, rng, wi, pdf);
         PROF_PHASE(PF_P_SAMPLE);
         if (cont) { // the record's f, 1/pdf and |wi.n| now, its A after the query
           const D3 f = bsdf(mat, nrm, wo, wi);
@@ -924,6 +1072,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
           r[6] = 1.0 / pdf;
           r[7] = fabs(dot(wi, nrm));
           PROF_PHASE(PF_P_RECORD);
+        }
         }
         // ---- the fused query: this hit's visibility towards the light, and the closest hit of its bounce ray
         double rtb = cont ? INF : -INF, rts = INF;

@@ -11,7 +11,7 @@
 // The first active lane does the bookkeeping (a handful of DS operations), so a mark may sit in divergent code.
 // Regular builds compile all of this to nothing.
 #ifdef RPT_PROF
-constexpr int PROF_SLOTS = 25;
+constexpr int PROF_SLOTS = 27;
 struct ProfLds {
   long long mark[4];
   unsigned long long wt[4][PROF_SLOTS], lt[4][PROF_SLOTS]; // wave cycles, lane cycles
@@ -65,7 +65,7 @@ __device__ __forceinline__ void prof_flush() { // at the end of the kernel, all 
 #define PROF_COUNT(i) prof_count(i)
 #define PROF_FLUSH() prof_flush()
 #else
-constexpr int PROF_SLOTS = 25;
+constexpr int PROF_SLOTS = 27;
 #define PROF_INIT() do { } while (0)
 #define PROF_PHASE(i) do { } while (0)
 #define PROF_COUNT(i) do { } while (0)
@@ -83,5 +83,7 @@ enum {
   // loops inside rpt_paths<KdFlat> (iteration counts only)
   PF_P_CAND = 21, PF_P_FOLDIT = 22, PF_P_REJECT = 23,
   // rpt_paths<KdFlat, false, true>: the two-ray query of a hit's shadow ray and bounce ray (flat_query2)
-  PF_P_FUSED = 24
+  PF_P_FUSED = 24,
+  // its fast shading form (RPT_SHADE_SPLIT): a hit's draws, the straight-line shading block
+  PF_P_DRAWS = 25, PF_P_SHADE = 26
 };
