@@ -461,6 +461,32 @@ int rptgpu_buffer_variance(rptgpu_buffer* b, double* out_variance);
 /* number of add_samples calls so far */
 int rptgpu_buffer_num_batches(const rptgpu_buffer* b, uint32_t* out);
 
+/* ---- adaptive sampling on the device-resident Buffer.  Additions within ABI version 7, detected by
+ * symbol (dlsym "rptgpu_buffer_sample_adaptive").  Per pixel p the buffer keeps n_p, the batches p holds, and a Welford
+ * state over their values x (accum / iterations * 2^EV, f64): n += 1, d = x - m, m += d / n, M2 += dot(d, x - m).
+ * After an adaptive round each pixel sampled in it RETIRES when n >= min_batches and (M2 / (n - 1)) / n <= t * t,
+ * t = abs_tol + rel_tol * ((m.x + m.y) + m.z) (a NaN never retires).  A retired pixel is never sampled again, so pixel
+ * p holds exactly batches 0 .. n_p - 1 of the buffer, and image() / variance() are buffer.rs:59-93 with per-pixel
+ * lengths (Buffer::add_sample, buffer.rs:25-30).  Random numbers are keyed by (pixel, sample index), so p's batches are
+ * bit for bit those of full-frame renders at the same sample_index_base. */
+typedef struct RptAdaptive {
+  uint32_t struct_size;    /* sizeof(RptAdaptive) */
+  uint32_t min_batches;    /* >= 2 */
+  double abs_tol, rel_tol; /* finite, >= 0 */
+} RptAdaptive;
+/* One batch of params->iterations samples for the pixels still active (all pixels at first), recorded as one more
+ * batch, then the stopping rule; *out_active = the pixels active afterwards.  No pixel active: nothing is rendered or
+ * recorded, *out_active = 0.  RPTGPU_E_INVALID_ARGUMENT for a bad RptAdaptive (struct_size, min_batches < 2, a
+ * negative or non-finite tolerance — checked first, so also without a buffer), part_count > 1 or a size mismatch.
+ * rptgpu_buffer_sample may be mixed in while every pixel is active and is refused once one has retired. */
+int rptgpu_buffer_sample_adaptive(rptgpu_buffer* b, const RptCamera* camera, const RptRenderParams* params,
+                                  const RptAdaptive* a, uint32_t* out_active);
+/* n_p per pixel: height*width uint32 (host), row-major */
+int rptgpu_buffer_sample_counts(const rptgpu_buffer* b, uint32_t* out_counts);
+/* the sum of each pixel's batch values (samples[index].iter().sum(), buffer.rs:84): height*width*3 doubles (host); the
+ * linear mean of pixel p is its sum / n_p */
+int rptgpu_buffer_totals(const rptgpu_buffer* b, double* out_totals);
+
 /* ---- particle systems: the reference's `rpt::ode` (src/ode.rs, src/ode/particle_system.rs) on the device.
  * Additions within ABI version 7: no earlier struct or signature changed, so a caller detects them by symbol
  * (dlsym "rptgpu_particles_integrate"), not by version.

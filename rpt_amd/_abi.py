@@ -142,6 +142,11 @@ class RptParticleSystem(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("radius", f64)]
 
 
+class RptAdaptive(C.Structure):
+    """include/rpt_gpu.h RptAdaptive (the adaptive buffer's stopping rule; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_batches", C.c_uint32), ("abs_tol", f64), ("rel_tol", f64)]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -180,6 +185,10 @@ SYMBOLS = [
     ("rptgpu_buffer_image", C.c_int, [_VP, C.POINTER(C.c_uint8)]),
     ("rptgpu_buffer_variance", C.c_int, [_VP, _PD]),
     ("rptgpu_buffer_num_batches", C.c_int, [_VP, C.POINTER(C.c_uint32)]),
+    ("rptgpu_buffer_sample_adaptive", C.c_int,
+     [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams), C.POINTER(RptAdaptive), C.POINTER(C.c_uint32)]),
+    ("rptgpu_buffer_sample_counts", C.c_int, [_VP, C.POINTER(C.c_uint32)]),
+    ("rptgpu_buffer_totals", C.c_int, [_VP, _PD]),
     ("rptgpu_get_stats", C.c_int, [_VP, C.POINTER(RptStats)]),
     ("rptgpu_reset_stats", C.c_int, [_VP]),
     ("rptgpu_kernel_name", C.c_char_p, [C.c_int]),

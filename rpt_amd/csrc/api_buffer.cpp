@@ -1,14 +1,27 @@
-// api_buffer.cpp — the device-resident Buffer (buffer.rs:9-93 on the device: add_samples, image, variance; see api_internal.h)
+// api_buffer.cpp — the device-resident Buffer (buffer.rs:9-93 on the device: add_samples, add_sample by adaptive rounds,
+// image, variance; see api_internal.h)
 #include "api_internal.h"
 
 // ------------------------------------------------------------------ device-resident Buffer
 struct rptgpu_buffer {
   rptgpu_scene* h = nullptr;
   uint32_t width = 0, height = 0, radius = 0;
-  std::vector<double*> batches; // one W*H*3 frame per add_samples call, on the device
+  std::vector<double*> batches; // one W*H*3 frame per batch, on the device (zero where a round did not sample a pixel)
   DevBuf<double> total, thr, pix_var;
   DevBuf<const double*> batch_ptrs;
   DevBuf<uint8_t> image;
+  // per pixel: n_p, the batches it holds, and the Welford state of their values (mean m_p, M2_p): DESIGN.md §10
+  DevBuf<uint32_t> counts;
+  DevBuf<double> mean, m2;
+  // adaptive rounds: the active pixels (active[cur], n_active of them, in the order of the round-0 list), the list the
+  // next round compacts into, the compaction's scratch and the round's packed values
+  DevBuf<uint32_t> active[2], block_cnt, active_n;
+  DevBuf<uint8_t> keep;
+  DevBuf<double> packed;
+  int cur = 0;
+  uint32_t n_active = 0;
+  bool listed = false;  // active[cur] has been made (by the first adaptive round)
+  bool retired = false; // some pixel has retired: a full-frame batch would break the prefix property
 };
 
 namespace {
@@ -43,6 +56,15 @@ std::vector<double> byte_thresholds(bool& clean) {
   }
   return thr;
 }
+// what is wrong with an RptAdaptive (nullptr: nothing)
+const char* bad_adaptive(const RptAdaptive* a) {
+  if (!a) return "null RptAdaptive";
+  if (a->struct_size != sizeof(RptAdaptive)) return "RptAdaptive: struct_size is not sizeof(RptAdaptive)";
+  if (a->min_batches < 2) return "RptAdaptive: min_batches < 2";
+  if (!(std::isfinite(a->abs_tol) && a->abs_tol >= 0.0) || !(std::isfinite(a->rel_tol) && a->rel_tol >= 0.0))
+    return "RptAdaptive: abs_tol and rel_tol must be finite and >= 0";
+  return nullptr;
+}
 } // namespace
 
 extern "C" {
@@ -62,9 +84,13 @@ int rptgpu_buffer_create(rptgpu_scene* h, uint32_t width, uint32_t height, uint3
       return fail(h, RPTGPU_E_INVALID_ARGUMENT, "host pow() is not monotone around a u8 threshold");
     }
     b->thr.upload(thr, h->stream);
-    uint64_t n = (uint64_t)width * height * 3;
+    uint64_t npix = (uint64_t)width * height, n = npix * 3;
     b->total.alloc(n);
     HIP_TRY(hipMemsetAsync(b->total.p, 0, n * sizeof(double), h->stream));
+    b->counts.alloc(npix); b->mean.alloc(n); b->m2.alloc(npix);
+    HIP_TRY(hipMemsetAsync(b->counts.p, 0, npix * sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(b->mean.p, 0, n * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(b->m2.p, 0, npix * sizeof(double), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
   } catch (const HipError& e) {
     int code = hip_fail(h, e);
@@ -80,6 +106,8 @@ void rptgpu_buffer_destroy(rptgpu_buffer* b) {
   (void)hipSetDevice(b->h->device);
   for (double* p : b->batches) (void)hipFree(p);
   b->total.release(); b->thr.release(); b->pix_var.release(); b->batch_ptrs.release(); b->image.release();
+  b->counts.release(); b->mean.release(); b->m2.release(); b->active[0].release(); b->active[1].release();
+  b->block_cnt.release(); b->active_n.release(); b->keep.release(); b->packed.release();
   delete b;
 }
 
@@ -88,6 +116,9 @@ int rptgpu_buffer_sample(rptgpu_buffer* b, const RptCamera* camera, const RptRen
   rptgpu_scene* h = b->h;
   if (params->width != b->width || params->height != b->height)
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "Invalid sample dimension"); // buffer.rs:33-36
+  if (b->retired)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "a pixel of this buffer has retired (rptgpu_buffer_sample_adaptive): a "
+                                              "full-frame batch would give it a batch its earlier rounds skipped");
   double* frame = nullptr;
   uint64_t n = (uint64_t)b->width * b->height * 3;
   if (hipSetDevice(h->device) != hipSuccess || hipMalloc((void**)&frame, n * sizeof(double)) != hipSuccess)
@@ -98,7 +129,8 @@ int rptgpu_buffer_sample(rptgpu_buffer* b, const RptCamera* camera, const RptRen
     return rc;
   }
   try {
-    table_for(RPT_PRECISION_F64_STRICT)->buffer_add(h->stream, b->total.p, frame, n);
+    table_for(RPT_PRECISION_F64_STRICT)->buffer_accumulate(h->stream, b->total.p, frame, nullptr, nullptr, b->width * b->height,
+                                                           b->counts.p, b->mean.p, b->m2.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
   } catch (const HipError& e) {
@@ -106,6 +138,107 @@ int rptgpu_buffer_sample(rptgpu_buffer* b, const RptCamera* camera, const RptRen
     return hip_fail(h, e);
   }
   b->batches.push_back(frame);
+  return RPTGPU_OK;
+}
+
+int rptgpu_buffer_sample_adaptive(rptgpu_buffer* b, const RptCamera* camera, const RptRenderParams* params,
+                                  const RptAdaptive* a, uint32_t* out_active) {
+  rptgpu_scene* h = b ? b->h : nullptr;
+  if (const char* why = bad_adaptive(a)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (!b || !camera || !params || !out_active) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
+  if (params->width != b->width || params->height != b->height)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "Invalid sample dimension"); // buffer.rs:33-36
+  if (params->part_count > 1)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "part_count > 1: adaptive rounds render the whole frame on one device");
+  if (const char* why = bad_params(params)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  REFUSE_IF_ABANDONED(h);
+  const uint32_t npix = b->width * b->height;
+  hipStream_t st = h->stream;
+  const KernelTable* kt = table_for(RPT_PRECISION_F64_STRICT);
+  try {
+    HIP_TRY(hipSetDevice(h->device));
+    if (!b->listed) { // round 0: every pixel, in the 8x8-block order of a full-frame render
+      b->active[0].upload(pixel_list(b->width, b->height, 32, 8, 0, 1), st);
+      b->active[1].alloc(npix);
+      b->keep.alloc(npix);
+      b->block_cnt.alloc((npix + RPT_RETIRE_TILE - 1) / RPT_RETIRE_TILE);
+      b->active_n.alloc(1);
+      HIP_TRY(hipStreamSynchronize(st));
+      b->cur = 0;
+      b->n_active = npix;
+      b->listed = true;
+    }
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  } catch (const std::bad_alloc&) {
+    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
+  }
+  if (b->n_active == 0) {
+    *out_active = 0;
+    return RPTGPU_OK;
+  }
+  const uint32_t n = b->n_active;
+  const uint32_t* list = b->active[b->cur].p;
+  double* frame = nullptr;
+  const uint64_t frame_elems = (uint64_t)npix * 3;
+  try {
+    b->packed.alloc((uint64_t)n * 3);
+    HIP_TRY(hipMalloc((void**)&frame, frame_elems * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(frame, 0, frame_elems * sizeof(double), st));
+  } catch (const HipError& e) {
+    if (frame) (void)hipFree(frame);
+    return hip_fail(h, e);
+  }
+  int rc = render_impl(h, camera, params, b->packed.p, false, nullptr, nullptr, true, list, n);
+  if (rc != RPTGPU_OK) {
+    (void)hipFree(frame);
+    return rc;
+  }
+  uint32_t left = 0;
+  try {
+    kt->buffer_accumulate(st, b->total.p, frame, b->packed.p, list, n, b->counts.p, b->mean.p, b->m2.p);
+    kt->buffer_retire(st, list, n, b->counts.p, b->mean.p, b->m2.p, a->min_batches, a->abs_tol, a->rel_tol, b->keep.p,
+                      b->block_cnt.p, b->active[b->cur ^ 1].p, b->active_n.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&left, b->active_n.p, sizeof left, hipMemcpyDeviceToHost, st)); // plans the next round
+    HIP_TRY(hipStreamSynchronize(st));
+  } catch (const HipError& e) {
+    (void)hipFree(frame);
+    return hip_fail(h, e);
+  }
+  b->batches.push_back(frame);
+  b->cur ^= 1;
+  b->n_active = left;
+  if (left < npix) b->retired = true;
+  *out_active = left;
+  return RPTGPU_OK;
+}
+
+int rptgpu_buffer_sample_counts(const rptgpu_buffer* b, uint32_t* out_counts) {
+  if (!b || !out_counts) return RPTGPU_E_INVALID_ARGUMENT;
+  rptgpu_scene* h = b->h;
+  try {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(out_counts, b->counts.p, (uint64_t)b->width * b->height * sizeof(uint32_t),
+                           hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  }
+  return RPTGPU_OK;
+}
+
+int rptgpu_buffer_totals(const rptgpu_buffer* b, double* out_totals) {
+  if (!b || !out_totals) return RPTGPU_E_INVALID_ARGUMENT;
+  rptgpu_scene* h = b->h;
+  try {
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(out_totals, b->total.p, (uint64_t)b->width * b->height * 3 * sizeof(double),
+                           hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  }
   return RPTGPU_OK;
 }
 
@@ -117,8 +250,8 @@ int rptgpu_buffer_image(rptgpu_buffer* b, uint8_t* out_rgb8) {
     HIP_TRY(hipSetDevice(h->device));
     uint64_t n = (uint64_t)b->width * b->height * 3;
     b->image.alloc(n);
-    table_for(RPT_PRECISION_F64_STRICT)->buffer_image(h->stream, b->total.p, b->width, b->height, b->radius,
-                                                      (uint32_t)b->batches.size(), b->thr.p, b->image.p);
+    table_for(RPT_PRECISION_F64_STRICT)->buffer_image(h->stream, b->total.p, b->counts.p, b->width, b->height, b->radius,
+                                                      b->thr.p, b->image.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_rgb8, b->image.p, n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -138,8 +271,8 @@ int rptgpu_buffer_variance(rptgpu_buffer* b, double* out_variance) {
     std::vector<const double*> ptrs(b->batches.begin(), b->batches.end());
     b->batch_ptrs.upload(ptrs, h->stream);
     b->pix_var.alloc(npix);
-    table_for(RPT_PRECISION_F64_STRICT)->buffer_variance(h->stream, b->total.p, b->batch_ptrs.p,
-                                                         (uint32_t)b->batches.size(), npix, b->pix_var.p);
+    table_for(RPT_PRECISION_F64_STRICT)->buffer_variance(h->stream, b->total.p, b->batch_ptrs.p, b->counts.p, npix,
+                                                         b->pix_var.p);
     HIP_TRY(hipGetLastError());
     std::vector<double> pv(npix);
     HIP_TRY(hipMemcpyAsync(pv.data(), b->pix_var.p, npix * sizeof(double), hipMemcpyDeviceToHost, h->stream));

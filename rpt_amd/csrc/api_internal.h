@@ -245,9 +245,12 @@ uint32_t zeros_common(const std::vector<rptdev::Light>& lights);
 void ensure_partition(rptgpu_scene* h, const RptRenderParams& p);
 std::vector<uint32_t> pixel_list(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, uint32_t pi, uint32_t pc);
 const char* bad_params(const RptRenderParams* p);
-// packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list
+// packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list.
+// d_list (device, n_list pixel indices; requires packed and d_out): render exactly those pixels instead of the part's list,
+// without touching the cached partition (the adaptive buffer's active pixels, api_buffer.cpp)
 int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams* p, void* d_out, bool out_f32,
-                double* host_out, hipStream_t user_stream, bool packed = false);
+                double* host_out, hipStream_t user_stream, bool packed = false, const uint32_t* d_list = nullptr,
+                uint32_t n_list = 0);
 
 // A handle whose aborted batch never drained (rptgpu_render_batch_reduce, drain_after_abort): the abandoned stream's
 // kernels may still read and write the workspace, the frame buffers and events, so every call that would enqueue work

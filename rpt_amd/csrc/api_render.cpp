@@ -526,12 +526,14 @@ void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderPar
   }
 }
 
-// packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list
+// packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list;
+// d_list: the n_list pixels of that list instead (the partition cache h->pixels / h->npix / h->part_key stays as it is)
 int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams* p, void* d_out, bool out_f32,
-                double* host_out, hipStream_t user_stream, bool packed) {
+                double* host_out, hipStream_t user_stream, bool packed, const uint32_t* d_list, uint32_t n_list) {
   if (!h || !camera || !p) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
   REFUSE_IF_ABANDONED(h);
   if (const char* why = bad_params(p)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (d_list && (!packed || !d_out || host_out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "a pixel list renders packed into device memory");
   auto t0 = std::chrono::steady_clock::now();
   try {
     HIP_TRY(hipSetDevice(h->device));
@@ -541,8 +543,8 @@ int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams*
     hipStream_t st = h->stream;
     const KernelTable* kt = table_for(p->precision_mode, h->ext_shapes);
     const bool prof = (p->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
-    ensure_partition(h, *p);
-    const uint32_t npix = h->npix;
+    if (!d_list) ensure_partition(h, *p);
+    const uint32_t npix = d_list ? n_list : h->npix;
     const uint64_t frame_elems = (uint64_t)p->width * p->height * 3;
     const size_t out_elem = out_f32 ? sizeof(float) : sizeof(double);
     void* out = d_out;
@@ -561,7 +563,7 @@ int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams*
     if (npix) {
       h->accum.alloc((uint64_t)npix * 3);
       rptdev::Frame fr{};
-      fr.width = p->width; fr.height = p->height; fr.npix = npix; fr.pixels = h->pixels.p;
+      fr.width = p->width; fr.height = p->height; fr.npix = npix; fr.pixels = d_list ? d_list : h->pixels.p;
       fr.max_bounces = p->max_bounces; fr.seed = p->seed; fr.accum = h->accum.p;
       (wavefront ? render_wavefront : render_persistent)(h, kt, *p, fr, make_camera(*camera), out, out_f32, packed, prof);
     }

@@ -47,6 +47,11 @@
 #define RPT_PATH_REORDER_MIN (1u << 20)
 #endif
 
+// the adaptive buffer's retire-and-compact kernels (kernels/buffer.inc): active-list entries per thread and per 256-thread
+// block (the host sizes the per-block counts with it)
+#define RPT_RETIRE_ITEMS 16u
+#define RPT_RETIRE_TILE (RPT_RETIRE_ITEMS * 256u)
+
 // layout of the flat path kernel's dynamic LDS (byte offsets; lrec at 0), see kernels.inc
 struct FlatLayout {
   uint32_t off_tris, off_refs, off_mat, off_leaf;
@@ -166,12 +171,19 @@ struct KernelTable {
   size_t (*sort_temp_bytes)(uint32_t n);
   void (*shadow_sum)(hipStream_t, const rptdev::Scene&, const rptdev::PathState&, const uint32_t* queue, uint32_t n,
                      uint32_t rec_off, const double* srt);
-  // device-resident Buffer (buffer.rs)
-  void (*buffer_add)(hipStream_t, double* total, const double* batch, uint64_t n);
-  void (*buffer_image)(hipStream_t, const double* total, uint32_t w, uint32_t h, uint32_t radius, uint32_t nb,
+  // device-resident Buffer (buffer.rs).  accumulate: one batch into total and the per-pixel statistics — a full frame
+  // (list == nullptr, n = pixels) or the packed values of n listed pixels, scattered into `frame`
+  void (*buffer_accumulate)(hipStream_t, double* total, double* frame, const double* packed, const uint32_t* list,
+                            uint32_t n, uint32_t* counts, double* mean, double* m2);
+  // the stopping rule over the n listed pixels; the survivors into out_list in list order, their number into *out_n
+  // (keep: n bytes, block_cnt: ceil(n / RPT_RETIRE_TILE) words of scratch; n > 0)
+  void (*buffer_retire)(hipStream_t, const uint32_t* list, uint32_t n, const uint32_t* counts, const double* mean,
+                        const double* m2, uint32_t min_batches, double abs_tol, double rel_tol, uint8_t* keep,
+                        uint32_t* block_cnt, uint32_t* out_list, uint32_t* out_n);
+  void (*buffer_image)(hipStream_t, const double* total, const uint32_t* counts, uint32_t w, uint32_t h, uint32_t radius,
                        const double* thr, uint8_t* out);
-  void (*buffer_variance)(hipStream_t, const double* total, const double* const* batches, uint32_t nb, uint64_t npix,
-                          double* out);
+  void (*buffer_variance)(hipStream_t, const double* total, const double* const* batches, const uint32_t* counts,
+                          uint64_t npix, double* out);
   // -DRPT_PROF builds: the per-phase table of kernels/prof.inc since the last call ([0] wave cycles, [1] lane cycles,
   // [2] wave iterations, [3] lane iterations); false in regular builds
   bool (*read_prof)(unsigned long long out[4][27]);

@@ -1,20 +1,116 @@
-// kernels/buffer.inc — device-resident Buffer kernels (add, image, variance).
+// kernels/buffer.inc — device-resident Buffer kernels (accumulate, retire, image, variance).
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
 
 // ------------------------------------------------------------------ device-resident Buffer
-// total += batch, element-wise, in insertion order (samples[index].iter().sum(), buffer.rs:86)
-__global__ void __launch_bounds__(256) rpt_buffer_add(double* __restrict__ total, const double* __restrict__ batch,
-                                                      uint64_t n) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) total[i] = total[i] + batch[i];
+// One batch into the buffer (DESIGN.md §10).  list == nullptr: a full frame `frame`, pixel i at i (rptgpu_buffer_sample);
+// otherwise the n listed pixels of an adaptive round, the i-th one's value at packed[3i..] (rpt_finish's packed output),
+// scattered into `frame` (zero elsewhere).  Per pixel: total += x element-wise in insertion order (samples[index].iter()
+// .sum(), buffer.rs:86) and the Welford update n += 1, d = x - m, m += d / n, M2 += dot(d, x - m).
+__global__ void __launch_bounds__(256) rpt_buffer_accumulate(double* __restrict__ total, double* __restrict__ frame,
+                                                             const double* __restrict__ packed,
+                                                             const uint32_t* __restrict__ list, uint32_t n,
+                                                             uint32_t* __restrict__ counts, double* __restrict__ mean,
+                                                             double* __restrict__ m2) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t p = list ? (uint64_t)list[i] : (uint64_t)i;
+  D3 x;
+  if (list) {
+    x = ld3(packed + 3 * (uint64_t)i);
+    frame[3 * p] = x.x; frame[3 * p + 1] = x.y; frame[3 * p + 2] = x.z;
+  } else {
+    x = ld3(frame + 3 * p);
+  }
+  const D3 t = ld3(total + 3 * p) + x;
+  total[3 * p] = t.x; total[3 * p + 1] = t.y; total[3 * p + 2] = t.z;
+  const uint32_t c = counts[p] + 1u;
+  counts[p] = c;
+  const D3 m0 = ld3(mean + 3 * p);
+  const D3 d = x - m0;
+  const D3 m = m0 + d / (double)c;
+  mean[3 * p] = m.x; mean[3 * p + 1] = m.y; mean[3 * p + 2] = m.z;
+  m2[p] = m2[p] + dot(d, x - m);
+}
+
+// ---- retiring converged pixels: the active list without them, in its own order (the round-0 list's 8x8 blocks);
+// RPT_RETIRE_TILE (kernels.h) list entries per 256-thread block, RPT_RETIRE_ITEMS per thread
+// the stopping rule: n >= min_batches and (M2 / (n - 1)) / n <= t * t, t = abs_tol + rel_tol * ((m.x + m.y) + m.z); a NaN
+// makes the comparison false, so such a pixel stays
+RPT_DEV bool stays_active(uint32_t p, const uint32_t* __restrict__ counts, const double* __restrict__ mean,
+                          const double* __restrict__ m2, uint32_t min_batches, double abs_tol, double rel_tol) {
+  const uint32_t n = counts[p];
+  const D3 m = ld3(mean + 3 * (uint64_t)p);
+  const double e = (m2[p] / ((double)n - 1.0)) / (double)n;
+  const double t = abs_tol + rel_tol * ((m.x + m.y) + m.z);
+  return !(n >= min_batches && e <= t * t);
+}
+// pass 1: the rule for every listed pixel (keep[i]) and how many of a block's RPT_RETIRE_TILE entries stay (block_cnt)
+__global__ void __launch_bounds__(256) rpt_retire_count(const uint32_t* __restrict__ list, uint32_t n,
+                                                        const uint32_t* __restrict__ counts, const double* __restrict__ mean,
+                                                        const double* __restrict__ m2, uint32_t min_batches, double abs_tol,
+                                                        double rel_tol, uint8_t* __restrict__ keep,
+                                                        uint32_t* __restrict__ block_cnt) {
+  __shared__ uint32_t s_cnt[4];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t tile = blockIdx.x * RPT_RETIRE_TILE;
+  uint32_t cnt = 0; // (the same in every lane of a wave)
+  for (uint32_t k = 0; k < RPT_RETIRE_ITEMS; k++) {
+    const uint32_t i = tile + k * 256u + threadIdx.x;
+    bool kp = false;
+    if (i < n) {
+      kp = stays_active(list[i], counts, mean, m2, min_batches, abs_tol, rel_tol);
+      keep[i] = kp ? 1 : 0;
+    }
+    cnt += (uint32_t)__popcll(__ballot(kp));
+  }
+  if (lane == 0) s_cnt[wave] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) block_cnt[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+}
+// pass 2: the block's offset (the kept entries of the blocks before it), then per group of 256 entries a ballot, the
+// lane's rank among the kept lanes below it and an LDS scan over the four waves: every kept entry lands at its rank in
+// the old list's order, whatever the schedule.  The last block writes the new length.
+__global__ void __launch_bounds__(256) rpt_retire_scatter(const uint32_t* __restrict__ list, uint32_t n,
+                                                          const uint8_t* __restrict__ keep,
+                                                          const uint32_t* __restrict__ block_cnt,
+                                                          uint32_t* __restrict__ out_list, uint32_t* __restrict__ out_n) {
+  __shared__ uint32_t s_sum[256];
+  __shared__ uint32_t s_cnt[4];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  uint32_t sum = 0;
+  for (uint32_t j = threadIdx.x; j < blockIdx.x; j += 256u) sum += block_cnt[j];
+  s_sum[threadIdx.x] = sum;
+  __syncthreads();
+  for (uint32_t s = 128u; s > 0; s >>= 1) {
+    if (threadIdx.x < s) s_sum[threadIdx.x] += s_sum[threadIdx.x + s];
+    __syncthreads();
+  }
+  uint32_t off = s_sum[0];
+  const uint32_t tile = blockIdx.x * RPT_RETIRE_TILE;
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (uint32_t k = 0; k < RPT_RETIRE_ITEMS; k++) {
+    const uint32_t i = tile + k * 256u + threadIdx.x;
+    const bool kp = i < n && keep[i] != 0;
+    const uint64_t mask = __ballot(kp);
+    if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint32_t wave_off = 0;
+    for (uint32_t w = 0; w < wave; w++) wave_off += s_cnt[w];
+    if (kp) out_list[off + wave_off + (uint32_t)__popcll(mask & below)] = list[i];
+    off += (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    __syncthreads(); // (s_cnt is written again by the next group)
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *out_n = off;
 }
 
 // Buffer::image: box filter (buffer.rs:75-93) + color_bytes (color.rs:18-24).  thr[k] is the
 // smallest double v in [0,1] with trunc(255 * v^(1/2.2)) >= k, found on the host with the host's
 // own pow: the conversion is a 256-step staircase, so a binary search reproduces it exactly.
-__global__ void __launch_bounds__(256) rpt_buffer_image(const double* __restrict__ total, uint32_t w, uint32_t h,
-                                                        uint32_t radius, uint32_t nbatches,
-                                                        const double* __restrict__ thr, uint8_t* __restrict__ out) {
+// counts[q]: the batches pixel q holds (samples[index].len(): the buffer's batch count in every pixel until one retires)
+__global__ void __launch_bounds__(256) rpt_buffer_image(const double* __restrict__ total,
+                                                        const uint32_t* __restrict__ counts, uint32_t w, uint32_t h,
+                                                        uint32_t radius, const double* __restrict__ thr,
+                                                        uint8_t* __restrict__ out) {
   uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= w * h) return;
   uint32_t y = p / w, x = p - y * w;
@@ -25,7 +121,7 @@ __global__ void __launch_bounds__(256) rpt_buffer_image(const double* __restrict
     for (uint32_t j = j0; j <= y + radius; j++)
       if (i < w && j < h) {
         color = color + ld3(total + 3 * ((uint64_t)j * w + i));
-        count += nbatches;
+        count += counts[(uint64_t)j * w + i];
       }
   D3 c = color / (double)count;
   double v[3] = {c.x, c.y, c.z};
@@ -41,12 +137,15 @@ __global__ void __launch_bounds__(256) rpt_buffer_image(const double* __restrict
   }
 }
 
-// per-pixel sample variance of the batch means (buffer.rs:62-70); the host adds the pixels up
+// per-pixel sample variance of the batch means (buffer.rs:62-70) over the pixel's own counts[p] batches — batches 0 ..
+// counts[p] - 1 of the buffer, since a retired pixel is never sampled again; the host adds the pixels up
 __global__ void __launch_bounds__(256) rpt_buffer_variance(const double* __restrict__ total,
-                                                           const double* const* __restrict__ batches, uint32_t nb,
-                                                           uint64_t npix, double* __restrict__ out) {
+                                                           const double* const* __restrict__ batches,
+                                                           const uint32_t* __restrict__ counts, uint64_t npix,
+                                                           double* __restrict__ out) {
   uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npix) return;
+  const uint32_t nb = counts[p];
   D3 mean = ld3(total + 3 * p) / (double)nb;
   double ss = 0.0;
   for (uint32_t b = 0; b < nb; b++) {

@@ -239,16 +239,27 @@ void launch_path_reorder(hipStream_t st, const PathState& ps, uint32_t n, bool s
   hipLaunchKernelGGL(rpt_path_permute, grid_for(n), dim3(256), 0, st, ps, n, sorted ? order : nullptr);
 }
 
-void launch_buffer_add(hipStream_t st, double* total, const double* batch, uint64_t n) {
-  hipLaunchKernelGGL(rpt_buffer_add, grid_for(n), dim3(256), 0, st, total, batch, n);
+void launch_buffer_accumulate(hipStream_t st, double* total, double* frame, const double* packed, const uint32_t* list,
+                              uint32_t n, uint32_t* counts, double* mean, double* m2) {
+  if (n) hipLaunchKernelGGL(rpt_buffer_accumulate, grid_for(n), dim3(256), 0, st, total, frame, packed, list, n, counts, mean, m2);
 }
-void launch_buffer_image(hipStream_t st, const double* total, uint32_t w, uint32_t h, uint32_t radius, uint32_t nb,
-                         const double* thr, uint8_t* out) {
-  hipLaunchKernelGGL(rpt_buffer_image, grid_for((uint64_t)w * h), dim3(256), 0, st, total, w, h, radius, nb, thr, out);
+void launch_buffer_retire(hipStream_t st, const uint32_t* list, uint32_t n, const uint32_t* counts, const double* mean,
+                          const double* m2, uint32_t min_batches, double abs_tol, double rel_tol, uint8_t* keep,
+                          uint32_t* block_cnt, uint32_t* out_list, uint32_t* out_n) {
+  if (!n) return;
+  const dim3 grid((n + RPT_RETIRE_TILE - 1) / RPT_RETIRE_TILE);
+  hipLaunchKernelGGL(rpt_retire_count, grid, dim3(256), 0, st, list, n, counts, mean, m2, min_batches, abs_tol, rel_tol,
+                     keep, block_cnt);
+  hipLaunchKernelGGL(rpt_retire_scatter, grid, dim3(256), 0, st, list, n, (const uint8_t*)keep, (const uint32_t*)block_cnt,
+                     out_list, out_n);
 }
-void launch_buffer_variance(hipStream_t st, const double* total, const double* const* batches, uint32_t nb,
+void launch_buffer_image(hipStream_t st, const double* total, const uint32_t* counts, uint32_t w, uint32_t h,
+                         uint32_t radius, const double* thr, uint8_t* out) {
+  hipLaunchKernelGGL(rpt_buffer_image, grid_for((uint64_t)w * h), dim3(256), 0, st, total, counts, w, h, radius, thr, out);
+}
+void launch_buffer_variance(hipStream_t st, const double* total, const double* const* batches, const uint32_t* counts,
                             uint64_t npix, double* out) {
-  hipLaunchKernelGGL(rpt_buffer_variance, grid_for(npix), dim3(256), 0, st, total, batches, nb, npix, out);
+  hipLaunchKernelGGL(rpt_buffer_variance, grid_for(npix), dim3(256), 0, st, total, batches, counts, npix, out);
 }
 
 void launch_eval_math(hipStream_t st, int fn, uint64_t n, const double* x, const double* y, double* out) {
@@ -273,5 +284,6 @@ bool read_prof(unsigned long long out[4][27]) {
 const KernelTable TABLE = {launch_raygen, launch_extend, launch_extend_rays, launch_shade,
                            launch_shadow_rays, launch_resolve, launch_finish, launch_scatter_f32, launch_eval_math,
                            paths_max_blocks_per_cu, launch_paths, launch_sum_samples, launch_query, sort_temp_bytes, launch_shadow_sum,
-                           launch_buffer_add, launch_buffer_image, launch_buffer_variance, read_prof, launch_path_reorder};
+                           launch_buffer_accumulate, launch_buffer_retire, launch_buffer_image, launch_buffer_variance,
+                           read_prof, launch_path_reorder};
 #endif // !__HIP_DEVICE_COMPILE__

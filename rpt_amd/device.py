@@ -275,3 +275,28 @@ class DeviceBuffer:
         n = C.c_uint32(0)
         _abi.check(self.gpu.lib.rptgpu_buffer_num_batches(self.handle, C.byref(n)), self.gpu.handle)
         return n.value
+
+    # ---- adaptive sampling (rptgpu_buffer_sample_adaptive)
+    def sample_adaptive(self, camera, params, min_batches=4, abs_tol=0.0, rel_tol=0.01):
+        """One batch for the pixels still active, then the stopping rule -> the number of pixels active afterwards.  Once
+        a pixel has retired, sample() is refused."""
+        cam = camera.lower() if hasattr(camera, "lower") else camera
+        a = _abi.RptAdaptive(C.sizeof(_abi.RptAdaptive), int(min_batches), float(abs_tol), float(rel_tol))
+        n = C.c_uint32(0)
+        _abi.check(self.gpu.lib.rptgpu_buffer_sample_adaptive(self.handle, C.byref(cam), C.byref(params), C.byref(a),
+                                                              C.byref(n)), self.gpu.handle)
+        return n.value
+
+    def sample_counts(self):
+        """(H, W) uint32: the batches each pixel holds."""
+        out = np.empty((self.height, self.width), dtype=np.uint32)
+        _abi.check(self.gpu.lib.rptgpu_buffer_sample_counts(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint32))),
+                   self.gpu.handle)
+        return out
+
+    def totals(self):
+        """(H, W, 3) float64: the sum of each pixel's batch values (the linear mean is totals / sample_counts)."""
+        out = np.empty((self.height, self.width, 3), dtype=np.float64)
+        _abi.check(self.gpu.lib.rptgpu_buffer_totals(self.handle, out.ctypes.data_as(C.POINTER(C.c_double))),
+                   self.gpu.handle)
+        return out

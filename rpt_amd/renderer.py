@@ -105,6 +105,28 @@ class Renderer:
             iteration += steps
             callback(iteration, buffer)
 
+    def adaptive_render(self, callback_interval, callback=None, min_batches=4, abs_tol=0.0, rel_tol=0.01):
+        """iterative_render(on_device=True) that stops sampling converged pixels (DeviceBuffer.sample_adaptive): rounds
+        of callback_interval samples until no pixel is active or num_samples samples per pixel have run;
+        callback(iteration, buffer, active) after each round.  -> the (H, W, 3) uint8 image."""
+        buffer = DeviceBuffer(self.gpu_scene(), self._width, self._height, self._filter)
+        try:
+            iteration = 0
+            active = self._width * self._height
+            self._samples_done = 0
+            while iteration < self._num_samples and active:
+                steps = min(self._num_samples - iteration, int(callback_interval))
+                params = make_params(self._width, self._height, self._max_bounces, steps, self._exposure_value,
+                                     self._seed, self._samples_done, precision=self._precision)
+                active = buffer.sample_adaptive(self.camera, params, min_batches, abs_tol, rel_tol)
+                self._samples_done += steps
+                iteration += steps
+                if callback is not None:
+                    callback(iteration, buffer, active)
+            return buffer.image()
+        finally:
+            buffer.close()
+
     def sample(self, iterations, buffer):  # renderer.rs:117-129 — THE hot path, on the GPU
         params = make_params(self._width, self._height, self._max_bounces, iterations,
                              self._exposure_value, self._seed, self._samples_done,

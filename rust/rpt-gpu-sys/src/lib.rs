@@ -255,6 +255,16 @@ pub mod ffi {
         pub radius: f64,
     }
 
+    /// `RptAdaptive` (the adaptive buffer's stopping rule; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptAdaptive {
+        pub struct_size: u32,
+        pub min_batches: u32,
+        pub abs_tol: f64,
+        pub rel_tol: f64,
+    }
+
     /// opaque `rptgpu_scene`
     #[repr(C)]
     pub struct rptgpu_scene {
@@ -297,6 +307,9 @@ pub mod ffi {
         pub fn rptgpu_buffer_image(b: *mut rptgpu_buffer, out_rgb8: *mut u8) -> c_int;
         pub fn rptgpu_buffer_variance(b: *mut rptgpu_buffer, out_variance: *mut f64) -> c_int;
         pub fn rptgpu_buffer_num_batches(b: *const rptgpu_buffer, out: *mut u32) -> c_int;
+        pub fn rptgpu_buffer_sample_adaptive(b: *mut rptgpu_buffer, camera: *const RptCamera, params: *const RptRenderParams, a: *const RptAdaptive, out_active: *mut u32) -> c_int;
+        pub fn rptgpu_buffer_sample_counts(b: *const rptgpu_buffer, out_counts: *mut u32) -> c_int;
+        pub fn rptgpu_buffer_totals(b: *const rptgpu_buffer, out_totals: *mut f64) -> c_int;
         pub fn rptgpu_get_stats(h: *const rptgpu_scene, out: *mut RptStats) -> c_int;
         pub fn rptgpu_reset_stats(h: *mut rptgpu_scene) -> c_int;
         pub fn rptgpu_kernel_name(k: c_int) -> *const c_char;
@@ -655,6 +668,7 @@ mod layout_tests {
         assert_eq!(size_of::<RptStats>(), 200);
         assert_eq!(size_of::<RptKdTree>(), 64);
         assert_eq!(size_of::<RptParticleSystem>(), 16);
+        assert_eq!(size_of::<RptAdaptive>(), 24);
     }
 
     #[test]
