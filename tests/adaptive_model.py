@@ -2,6 +2,8 @@
 stopping rule, and buffer.rs:59-93 with per-pixel sample lists.  IEEE f64, the C ABI's order of operations."""
 import numpy as np
 
+from rpt_amd.color import color_bytes
+
 
 def dot(a, b):
     return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
@@ -72,6 +74,66 @@ def ref_filtered(pix, w, h, radius):
             assert count != 0, "Pixel found with no samples"
             out[y, x] = [color[0] / count, color[1] / count, color[2] / count]
     return out
+
+
+def filtered_color(totals, counts, w, h, radius):
+    """get_filtered_color (buffer.rs:75-93) for every pixel at once: totals (w*h, 3) the per-pixel sample sums, counts
+    (w*h,) their lengths -> (h, w, 3).  Per pixel the neighbours are added in the reference's order, column i outer and
+    row j inner.  The frame is padded with zeros, so an out-of-frame neighbour adds +0.0: the running sum starts at +0.0
+    and can never become -0.0, hence x + 0.0 == x and the padding changes no bit.  Offsets beyond the frame only ever
+    reach the padding and are left out."""
+    tot = np.asarray(totals, dtype=np.float64).reshape(h, w, 3)
+    cnt = np.asarray(counts, dtype=np.int64).reshape(h, w)
+    rx, ry = min(radius, w - 1), min(radius, h - 1)
+    tp = np.zeros((h + 2 * ry, w + 2 * rx, 3))
+    tp[ry:ry + h, rx:rx + w] = tot
+    cp = np.zeros((h + 2 * ry, w + 2 * rx), dtype=np.int64)
+    cp[ry:ry + h, rx:rx + w] = cnt
+    color = np.zeros((h, w, 3))
+    count = np.zeros((h, w), dtype=np.int64)
+    for i in range(-rx, rx + 1):  # column offset: outer
+        for j in range(-ry, ry + 1):  # row offset: inner
+            color = color + tp[ry + j:ry + j + h, rx + i:rx + i + w]
+            count = count + cp[ry + j:ry + j + h, rx + i:rx + i + w]
+    assert (count != 0).all(), "Pixel found with no samples"
+    return color / count.astype(np.float64)[:, :, None]
+
+
+def filtered_image(totals, counts, w, h, radius):
+    """Buffer::image (buffer.rs:43-56) with per-pixel counts -> (h, w, 3) uint8"""
+    return color_bytes(filtered_color(totals, counts, w, h, radius))
+
+
+def variance(frames, counts):
+    """Buffer::variance (buffer.rs:59-73) over per-pixel sample lists (pixel p holds frames[k][p] for k < counts[p]),
+    vectorised over pixels: mean = total / n, ss summed over the pixel's samples in order as ((dx*dx + dy*dy) + dz*dz),
+    ss / (n - 1), then a SEQUENTIAL sum over the pixels in index order (np.cumsum; np.sum would add pairwise)."""
+    counts = np.asarray(counts)
+    n = counts.astype(np.float64)
+    with np.errstate(all="ignore"):  # n = 1: ss / 0 = 0/0 = NaN, as the reference computes
+        mean = masked_totals(frames, counts) / n[:, None]
+        ss = np.zeros(len(n))
+        for k, F in enumerate(frames):
+            d = F - mean
+            # a pixel without a k-th sample adds +0.0 to an ss that started at +0.0: no bit changes
+            ss = ss + np.where(counts > k, dot(d, d), 0.0)
+        per_pixel = ss / (n - 1.0)
+    return float(np.cumsum(per_pixel)[-1]) / float(len(per_pixel))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def check_against(dev, left, frames, r):
+    """a DeviceBuffer after adaptive rounds over `frames` (left: what each round returned) against the model's run r:
+    per-pixel counts, the active counts, the batches recorded and the totals' bits -> the counts"""
+    counts = dev.sample_counts().ravel()
+    assert np.array_equal(counts, r["counts"])
+    assert left == r["active"]
+    assert dev.num_batches() == sum(1 for k in range(len(frames)) if k == 0 or r["active"][k - 1] > 0)
+    assert np.array_equal(bits(dev.totals().reshape(-1, 3)), bits(masked_totals(frames, counts)))
+    return counts
 
 
 def ref_variance(pix):

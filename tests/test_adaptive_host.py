@@ -73,6 +73,44 @@ def test_add_sample_with_uneven_counts_is_the_reference_buffer(radius):
     assert (np.isnan(v) and np.isnan(rv)) if np.isnan(rv) else v == rv
 
 
+@pytest.mark.parametrize("w,h", [(9, 7), (1, 11), (11, 1), (2, 2), (3, 2)])
+def test_vectorised_references_equal_the_per_pixel_ones(w, h):
+    """filtered_image / variance (numpy, what the full-frame GPU tests use) against ref_filtered / ref_variance (Python
+    floats, pixel by pixel): bit for bit, with uneven counts, all-zero pixels, every radius up to past the frame."""
+    kmax = 5
+    frames, counts = _uneven(40 + w * 13 + h, w, h, kmax)
+    for F in frames:  # pixels whose samples are all zeros, of both signs
+        F[(w * h) // 2] = [0.0, -0.0, 0.0]
+    pix = M.pixel_lists(frames, counts)
+    totals = M.masked_totals(frames, counts)
+    for radius in sorted({0, 1, 2, 3, 4, max(w, h), w + h + 3}):
+        want = M.ref_filtered(pix, w, h, radius)
+        got = M.filtered_color(totals, counts, w, h, radius)
+        assert np.array_equal(M.bits(got), M.bits(want)), radius
+        assert np.array_equal(M.filtered_image(totals, counts, w, h, radius), rpt_amd.color.color_bytes(want))
+    v, rv = M.variance(frames, counts), M.ref_variance(pix)  # some pixel has one sample: NaN
+    assert np.isnan(v) and np.isnan(rv)
+    counts2 = np.maximum(counts, 2)
+    pix2 = M.pixel_lists(frames, counts2)
+    v, rv = M.variance(frames, counts2), M.ref_variance(pix2)
+    assert M.bits(v) == M.bits(rv)
+    buf = rpt_amd.Buffer(w, h)
+    for k in range(kmax):
+        for p in np.nonzero(counts2 > k)[0]:
+            buf.add_sample(p % w, p // w, frames[k][p])
+    assert M.bits(buf.variance()) == M.bits(v)
+
+
+def test_vectorised_variance_sums_the_pixels_in_order():
+    """The pixel sum is sequential, as buffer.rs's loop: values whose pairwise sum rounds differently tell it apart."""
+    P = 4096
+    rng = np.random.default_rng(9)
+    frames = [rng.random((P, 3)) * np.where(np.arange(P) % 3 == 0, 1e6, 1e-6)[:, None] for _ in range(3)]
+    counts = rng.integers(2, 4, size=P)
+    want = M.ref_variance(M.pixel_lists(frames, counts))
+    assert M.bits(M.variance(frames, counts)) == M.bits(want)
+
+
 def test_add_sample_order_and_add_samples_after_uneven_counts():
     """A pixel's samples keep their insertion order whatever the call: add_samples after add_sample appends each
     pixel's value at its own next position."""

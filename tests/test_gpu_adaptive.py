@@ -46,8 +46,8 @@ def frames_of(g, cam, n, **kw):
     return [g.render_batch(cam, params(k, **kw)) for k in range(n)]
 
 
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+bits = M.bits
+check_against = M.check_against
 
 
 def mixed_tolerance(frames, min_batches):
@@ -63,15 +63,6 @@ def adaptive(g, cam, n, min_batches, abs_tol, rel_tol, radius=0, **kw):
     dev = rpt_amd.DeviceBuffer(g, W, H, rpt_amd.Filter.Box(radius))
     left = [dev.sample_adaptive(cam, params(k, **kw), min_batches, abs_tol, rel_tol) for k in range(n)]
     return dev, left
-
-
-def check_against(dev, left, frames, r):
-    counts = dev.sample_counts().ravel()
-    assert np.array_equal(counts, r["counts"])
-    assert left == r["active"]
-    assert dev.num_batches() == sum(1 for k in range(len(frames)) if k == 0 or r["active"][k - 1] > 0)
-    assert np.array_equal(bits(dev.totals().reshape(-1, 3)), bits(M.masked_totals(frames, counts)))
-    return counts
 
 
 @pytest.mark.parametrize("flags", [_abi.RPT_FLAG_PERSISTENT, _abi.RPT_FLAG_WAVEFRONT, _abi.RPT_FLAG_GENERAL_TRAVERSAL])

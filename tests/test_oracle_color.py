@@ -30,6 +30,21 @@ def test_hex_color_and_color_bytes_agree_with_oracle(oracle):
         assert oracle.color_bytes(c) == list(o)
 
 
+def test_color_bytes_next_to_every_threshold_agree_with_oracle(oracle):
+    """The values that tell one gamma implementation from another: a few ulps either side of each of the 255 steps.
+    color_bytes must give there what the oracle's std::pow and the scalar color_byte (math.pow) give."""
+    thr = rpt_amd.color.byte_thresholds()
+    u = thr[1:].view(np.int64)
+    vals = np.concatenate([(u + d).view(np.float64) for d in range(-3, 4)] + [[0.0, -0.0, 1.0, 1.5, np.inf, np.nan]])
+    vals = np.concatenate([vals, np.zeros((-len(vals)) % 3)])
+    ours = color_bytes(vals)
+    assert [int(b) for b in ours] == [rpt_amd.color.color_byte(float(v)) for v in vals]
+    for k in range(255):  # the staircase steps at thr
+        assert ours[3 * 255 + k] == k + 1 and ours[2 * 255 + k] == k
+    for c, o in zip(vals.reshape(-1, 3), ours.reshape(-1, 3)):
+        assert oracle.color_bytes(c) == list(o)
+
+
 def test_truncation_not_rounding(oracle):
     # `as u8` truncates (color.rs:20-22): 0.5^(1/2.2)*255 = 186.08 -> 186; a value just below 1 -> 254
     assert oracle.color_bytes([0.5, 0.999, 1.0]) == [186, 254, 255]
