@@ -202,19 +202,19 @@ void ensure_workspace(rptgpu_scene* h, uint64_t cap, uint64_t rec_cols) {
 // ran (lane time / wave time, of 64), and for loop bodies the iteration count and the lanes per iteration.  One line
 // per slot that was used, machine-readable enough to be committed under profiles/ as it is.
 void print_prof(const KernelTable* kt, const char* what) {
-  static const char* const NAMES[27] = {
+  static const char* const NAMES[29] = {
       "tree_trace refill", "tree_trace node steps", "tree_trace box tests", "tree_trace pop", "tree_trace write-out",
       "tree_trace exact tests", "in-kernel node step", "in-kernel box batch", "in-kernel child test",
       "in-kernel triangle batch", "in-kernel object", "paths fetch", "paths raygen", "paths closest_hit",
       "paths illuminate", "paths visible", "paths nee_bsdf", "paths sample_f", "paths bsdf", "paths record",
       "paths fold+store", "flat candidate walk", "fold iteration", "rejection round", "paths fused query",
-      "paths draws", "paths shade block"};
-  unsigned long long t[4][27];
+      "paths draws", "paths shade block", "pre-trace pass", "pre-trace pass, cubes skipped"};
+  unsigned long long t[4][29];
   if (!kt->read_prof(t)) return;
   unsigned long long tot = 0;
-  for (int i = 0; i < 27; i++) tot += t[0][i];
+  for (int i = 0; i < 29; i++) tot += t[0][i];
   std::fprintf(stderr, "prof[%s] %-28s %8s %10s %14s %10s\n", what, "phase", "time %", "lanes/64", "iterations", "lanes/64");
-  for (int i = 0; i < 27; i++) {
+  for (int i = 0; i < 29; i++) {
     if (!t[0][i] && !t[2][i]) continue;
     char a[32] = "-", b[32] = "-", c[32] = "-", d[32] = "-";
     if (t[0][i]) {
@@ -301,6 +301,21 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   const bool flat = h->all_flat && !h->dscene.force_general;
   FlatLayout lay = flat ? h->flat_layout : FlatLayout{};
   const uint32_t flat_lds = lay.off_end;
+  // the fused kernel's pre-trace pass: this render's screen rectangles of the objects it may skip (host_scene.cpp
+  // pinhole_screen_rect; none under a lens).  An object without a rectangle is always tested.
+  if (RPT_PRETRACE_CULL && lay.pretrace_cull) {
+    for (size_t i = 0; i < h->obj_geom.size() && i < 64 && lay.cull_n < (uint32_t)RPT_CULL_MAX; i++) {
+      uint32_t r[4];
+      if (((lay.cull_always >> i) & 1ull) ||
+          !rpthost::pinhole_screen_rect(rpthost::world_box(h->obj_geom[i], h->top_insts[i]), cam, fr.width, fr.height, r))
+        continue;
+      lay.cull_obj[lay.cull_n] = (uint32_t)i;
+      const bool off = r[0] > r[1] || r[2] > r[3]; // off screen
+      lay.cull_lo[lay.cull_n] = off ? 0xffffffffu : (r[0] | (r[2] << 16));
+      lay.cull_ext[lay.cull_n] = off ? 0u : ((r[1] - r[0]) | ((r[3] - r[2]) << 16));
+      lay.cull_n++;
+    }
+  }
   const rptplan::PersistentPlan pl = rptplan::plan_persistent(
       npix, p.iterations, p.max_bounces, h->num_cus, kt->paths_max_blocks_per_cu(flat ? &lay : nullptr, flat_lds, false),
       h->lbuf_max_bytes, lbuf_held, free_b, h->paths_chunk, h->all_flat, h->dscene.force_general, h->flat_layout.obj_filter);

@@ -92,6 +92,13 @@ void apply_env_overrides(RptSceneOptions& o, bool user_set_build_min) {
   if (const char* e = std::getenv("RPTGPU_WS_BYTES")) { uint64_t u = std::strtoull(e, nullptr, 10); if (u >= (1ull << 20)) o.workspace_bytes = u; }
   if (const char* e = std::getenv("RPTGPU_COMM_TIMEOUT_S")) { double d = std::atof(e); if (d > 0.0) o.comm_timeout_s = d; }
 }
+// bit i: top-level object i is a user of the flat kernel's plane table (the pre-trace pass never skips those)
+uint64_t plane_users(const std::vector<rptdev::Inst>& insts, size_t n) {
+  uint64_t m = 0;
+  for (size_t i = 0; i < n && i < 64; i++)
+    if (insts[i].plane_use) m |= 1ull << i;
+  return m;
+}
 } // namespace
 
 int rptgpu_scene_get_options(const rptgpu_scene* h, RptSceneOptions* out) {
@@ -353,6 +360,15 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
         h->plane_vals.upload(planes, h->stream);
         HIP_TRY(hipStreamSynchronize(h->stream)); // `planes` dies with this block
         lay.plane_vals = h->plane_vals.p;
+        // the fused kernel's pre-trace pass skips, per wave, objects whose screen rectangle holds none of its pending
+        // pixels (kernels/paths.inc cull_skip_mask; the rectangles are the render's: api_render.cpp).  Never skipped: the
+        // plane table's users (their slab run is cheap) and what the object filter exempts (host_scene.cpp
+        // fill_object_boxes: unbounded, not finite, sliver meshes, ill-conditioned placements)
+        if (RPT_PRETRACE_CULL && lay.fuse_query && fs.obj_filter_ok) {
+          const uint64_t every = fs.num_objects >= 64 ? ~0ull : (1ull << fs.num_objects) - 1ull;
+          lay.cull_always = (fs.obj_always | plane_users(fs.insts, (size_t)fs.num_objects)) & every;
+          lay.pretrace_cull = 1;
+        }
       }
       // many small objects and no plane table (a room of polygons rather than C2's five walls): the object filter
       // (host_scene.cpp fill_object_boxes).  RPTGPU_OBJECT_FILTER_MIN: from how many objects (0 = never).  Measured:
@@ -436,6 +452,8 @@ void rptgpu_scene_destroy(rptgpu_scene* h) { delete h; }
 // derives from the records these calls change:
 //   * the flat kernel's object filter (boxes, grid, obj_always) — recomputed; stale boxes would drop pixels.  Whether
 //     the filter is on stays as decided at creation (scheduling only; objects it must not filter are in obj_always);
+//   * the fused flat kernel's pre-trace cull — its exemptions (FlatLayout::cull_always) recomputed with the filter's; its
+//     screen rectangles are made per render from top_insts (api_render.cpp), so they follow by construction;
 //   * scene_bounds, the path re-order's key grid — recomputed (kept when the new union is not finite: scheduling only);
 //   * StackSpill::zeros_common (directional lights along an axis) — recomputed (scheduling only);
 //   * the plane table (untransformed meshes only: `transformed` may not change), trees, leaf boxes of group children
@@ -483,6 +501,7 @@ void commit_update(rptgpu_scene* h, std::vector<rptdev::Inst>& insts, std::vecto
   if (lights && !lights->empty())
     HIP_TRY(hipMemcpyAsync(h->lights.p, lights->data(), lights->size() * sizeof(rptdev::Light), hipMemcpyHostToDevice, st));
   rpthost::ObjectBounds ob;
+  const bool cull = h->all_flat && h->flat_layout.pretrace_cull; // (the fused kernel's pre-trace pass: its exemptions follow too)
   const bool filter = h->all_flat && h->flat_layout.obj_filter;
   if (mats) { // the objects moved: the object filter and the scene bounds follow them
     rpthost::fill_object_boxes(insts, h->obj_geom, ob);
@@ -499,6 +518,10 @@ void commit_update(rptgpu_scene* h, std::vector<rptdev::Inst>& insts, std::vecto
     if (filter) { // (the filter's LDS layout does not depend on the boxes: only the exemptions change)
       const size_t n = h->obj_geom.size();
       h->flat_layout.obj_always = ob.obj_always & (n >= 64 ? ~0ull : (1ull << n) - 1ull);
+    }
+    if (cull) { // (the rectangles themselves are made per render from top_insts: api_render.cpp)
+      const size_t n = h->obj_geom.size();
+      h->flat_layout.cull_always = (ob.obj_always | plane_users(h->top_insts, n)) & (n >= 64 ? ~0ull : (1ull << n) - 1ull);
     }
     if (ob.scene_bounds_ok) std::memcpy(h->scene_bounds, ob.scene_bounds, sizeof h->scene_bounds);
   }

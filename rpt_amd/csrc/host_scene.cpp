@@ -698,6 +698,52 @@ Box world_box(const ObjectGeom& g, const rptdev::Inst& in) {
   return in.has_xf ? transformed_box(g.local, in.fwd) : g.local;
 }
 
+// The fused flat kernel's pre-trace pass (kernels/paths.inc cull_skip_mask) leaves an object's exact test out for a wave
+// none of whose pending camera rays belongs to a pixel of this rectangle.  Why that cannot change a result: the camera
+// ray of pixel (x, y) is eye + t (cam.d D + px R + py U), t > 0, with px = ((2x + 1) - width) / dim + dx and
+// py = ((2 (height - y) - 1) - height) / dim + dy, |dx|, |dy| <= 1 / dim (kernels/paths.inc camera_ray, renderer.rs:132-139;
+// no lens: the origin is the eye).  An object's intersect accepts only a point of the object, hence of its bounding box
+// (fill_object_boxes below), i.e. of the convex hull of the box's eight corners.  Writing a point's offset from the eye
+// as s (cam.d D + px R + py U) by Cramer's rule, s is linear in the point; when s > 0 at all eight corners, the hull's
+// (px, py) lie within the corners' extremes, so the pixel's x is within 1/2 of
+// xc = (px dim + width - 1) / 2 for a px between the corners' extremes, and its y likewise of
+// yc = height - (py dim + height + 1) / 2.  The rectangle is those ranges widened by two pixels on every side, far
+// more than the roundings here and in the exact tests (1e-16 relative; a corner must be at least 1e-6 of the farthest
+// corner's distance in front of the eye, so that a pixel is not a vanishing length at the object).
+bool pinhole_screen_rect(const Box& world, const rptdev::Camera& cam, uint32_t width, uint32_t height, uint32_t rect[4]) {
+  if (cam.aperture > 0.0 || width == 0 || height == 0 || width > 65535u || height > 65535u) return false;
+  const double* D = cam.direction; const double* R = cam.right; const double* U = cam.up;
+  auto det = [](const double* a, const double* b, const double* c) {
+    return a[0] * (b[1] * c[2] - b[2] * c[1]) - a[1] * (b[0] * c[2] - b[2] * c[0]) + a[2] * (b[0] * c[1] - b[1] * c[0]);
+  };
+  const double det0 = det(D, R, U);
+  const double dim = (double)std::max(width, height);
+  if (!std::isfinite(det0) || det0 == 0.0 || !(cam.d > 0.0) || !std::isfinite(cam.d)) return false;
+  double xlo = INFINITY, xhi = -INFINITY, ylo = INFINITY, yhi = -INFINITY, smin = INFINITY, vmax = 0.0;
+  for (int c = 0; c < 8; c++) {
+    double v[3];
+    for (int k = 0; k < 3; k++) v[k] = (((c >> k) & 1) ? world.hi[k] : world.lo[k]) - cam.eye[k];
+    const double s = det(v, R, U) / det0 / cam.d; // the ray parameter of the corner's own ray
+    if (!(s > 0.0) || !std::isfinite(s)) return false;
+    const double px = det(D, v, U) / det0 / s, py = det(D, R, v) / det0 / s;
+    const double xc = (px * dim + (double)width - 1.0) / 2.0, yc = (double)height - (py * dim + (double)height + 1.0) / 2.0;
+    if (!(std::fabs(xc) < 1e9) || !(std::fabs(yc) < 1e9)) return false;
+    xlo = std::min(xlo, xc); xhi = std::max(xhi, xc); ylo = std::min(ylo, yc); yhi = std::max(yhi, yc);
+    smin = std::min(smin, s);
+    vmax = std::max(vmax, std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+  }
+  const double dlen = std::sqrt(D[0] * D[0] + D[1] * D[1] + D[2] * D[2]);
+  if (!(smin * cam.d * dlen >= 1e-6 * vmax)) return false;
+  const double x0 = std::floor(xlo) - 2.0, x1 = std::ceil(xhi) + 2.0, y0 = std::floor(ylo) - 2.0, y1 = std::ceil(yhi) + 2.0;
+  if (x1 < 0.0 || y1 < 0.0 || x0 > (double)(width - 1) || y0 > (double)(height - 1)) { // off screen
+    rect[0] = 1; rect[1] = 0; rect[2] = 1; rect[3] = 0;
+    return true;
+  }
+  rect[0] = (uint32_t)std::max(x0, 0.0); rect[1] = (uint32_t)std::min(x1, (double)(width - 1));
+  rect[2] = (uint32_t)std::max(y0, 0.0); rect[3] = (uint32_t)std::min(y1, (double)(height - 1));
+  return true;
+}
+
 // The same filter one level up, for scenes that are a list of many small objects (every tree a single leaf: the flat
 // path kernel, kernels/paths.inc flat_query_filtered).  The reference tests every object of scene.objects against every
 // ray (renderer.rs:211-220); an object's intersect can only accept a hit point that lies on the object, hence inside its

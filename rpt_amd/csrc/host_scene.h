@@ -73,6 +73,10 @@ int convert_material(const RptMaterial& s, uint64_t i, rptdev::Material& m, std:
 int convert_light(const RptLight& l, rptdev::Light& dl, std::string& err);
 // the world box of a top-level object: Bounded::bounding_box through its placement `in` (meaningful when g.bounded)
 Box world_box(const ObjectGeom& g, const rptdev::Inst& in);
+// The pixels whose pinhole camera rays can hit something inside `world` (an object's bounding box), as an inclusive
+// rectangle rect = {x0, x1, y0, y1} of a width x height frame (x0 > x1: none); false when no rectangle can be given
+// (a lens, a corner not in front of the eye, values that are not finite, a frame beyond 65535 pixels a side)
+bool pinhole_screen_rect(const Box& world, const rptdev::Camera& cam, uint32_t width, uint32_t height, uint32_t rect[4]);
 // the object filter's tables and the scene bounds of the top-level objects insts[0, geom.size()), from scratch
 void fill_object_boxes(const std::vector<rptdev::Inst>& insts, const std::vector<ObjectGeom>& geom, ObjectBounds& out);
 

@@ -32,6 +32,15 @@
 #ifndef RPT_SHADE_SPLIT
 #define RPT_SHADE_SPLIT 1
 #endif
+// RPT_PRETRACE_CULL=1: in rpt_paths<KdFlat, false, true> under a pinhole camera, the pass that pre-traces a refill's
+// camera rays skips, for the whole wave, the exact test of an object outside the plane table when none of the wave's
+// pending pixels lies inside the object's screen rectangle (host_scene.cpp pinhole_screen_rect, computed per render from
+// the camera: FlatLayout::cull_*; kernels/paths.inc flat_query<false, true>); 0: every object's test in every pass
+// (A/B builds).  RPT_CULL_MAX: objects that can carry a rectangle (the first ones that qualify; the others always run)
+#ifndef RPT_PRETRACE_CULL
+#define RPT_PRETRACE_CULL 1
+#endif
+#define RPT_CULL_MAX 4
 #define RPT_PATHS_STASH_LDS 4864u
 #define RPT_PATHS_STASH_HIT_LDS 6656u
 // what the host leaves room for in a KdFlat scene's LDS layout (api_scene.cpp)
@@ -73,6 +82,14 @@ struct FlatLayout {
   // rpt_paths<KdFlat, false, true> (RPT_FUSE_QUERY): the quotient table is doubled, the shadow ray's half right behind
   // the bounce ray's (api_scene.cpp; kernels/launch.inc selects the fused kernel by it)
   uint32_t fuse_query;
+  // rpt_paths<KdFlat, false, true> (RPT_PRETRACE_CULL).  Per scene (api_scene.cpp): pretrace_cull = some object may be
+  // skipped by the pre-trace pass, cull_always = bit k: object k never is (a plane-table user, or exempt from the object
+  // filter).  Per render (api_render.cpp, a pinhole camera): cull_n rectangles, cull_obj[j] the object of rectangle j,
+  // cull_lo[j] = x0 | y0 << 16 its first pixel and cull_ext[j] = (x1 - x0) | (y1 - y0) << 16 its extent beyond that one
+  // (off screen: lo = 0xffffffff, ext = 0, which no pixel of a frame of at most 65535 a side satisfies)
+  uint32_t pretrace_cull, cull_n;
+  uint64_t cull_always;
+  uint32_t cull_obj[RPT_CULL_MAX], cull_lo[RPT_CULL_MAX], cull_ext[RPT_CULL_MAX];
 };
 
 // buffers of the optional ray sort in front of a per-tree traversal (all sized for the query's n)
@@ -186,7 +203,7 @@ struct KernelTable {
                           uint64_t npix, double* out);
   // -DRPT_PROF builds: the per-phase table of kernels/prof.inc since the last call ([0] wave cycles, [1] lane cycles,
   // [2] wave iterations, [3] lane iterations); false in regular builds
-  bool (*read_prof)(unsigned long long out[4][27]);
+  bool (*read_prof)(unsigned long long out[4][29]);
   // in-kernel-traversal scenes: the next depth's paths sorted by ray key into the current state arrays (kernels/wavefront.inc)
   void (*path_reorder)(hipStream_t, const rptdev::PathState&, uint32_t n, bool sorted, const SortBufs* sort, uint32_t* order);
 };

@@ -268,8 +268,8 @@ void launch_eval_math(hipStream_t st, int fn, uint64_t n, const double* x, const
 
 // debug builds with -DRPT_PROF: the per-phase table of kernels/prof.inc accumulated so far (and reset):
 // out[0] wave cycles, [1] lane cycles, [2] wave iterations, [3] lane iterations, PROF_SLOTS slots each
-bool read_prof(unsigned long long out[4][27]) {
-  static_assert(PROF_SLOTS == 27, "kernels.h declares the table with 27 slots");
+bool read_prof(unsigned long long out[4][29]) {
+  static_assert(PROF_SLOTS == 29, "kernels.h declares the table with 29 slots");
 #ifdef RPT_PROF
   static unsigned long long zero[4][PROF_SLOTS];
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof zero) != hipSuccess) return false;

@@ -236,8 +236,44 @@ RPT_DEV int flat_query_filtered(const Scene& sc, const FlatLds* fl, D3 o, D3 d, 
   return obj;
 }
 
-template <bool SHADOW>
-RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_stop, double& rt, D3& rn) {
+#if RPT_PRETRACE_CULL
+// ------------------------------------------------------------------ the pre-trace pass: objects no pending ray can hit
+// The camera rays a refill pre-traces are the one coherent set of rays in rpt_paths<KdFlat, false, true>: the lanes of a
+// wave hold neighbouring pixels of a tile, and most waves' rays pass nowhere near the two cubes of C2 — yet the cube
+// block of flat_query is straight-line code that every pass runs for all of its lanes.  Under a pinhole camera the host
+// hands the kernel, per render, the screen rectangle of each object outside the plane table (host_scene.cpp
+// pinhole_screen_rect says why a camera ray of a pixel outside the rectangle cannot be accepted by the object's exact
+// test).  A lane notes at ray generation which rectangles hold its pixel (cull_near: two packed 16-bit operations; bit j =
+// rectangle j), and the pre-trace pass skips, for the whole wave, an object whose rectangle holds no pending lane's
+// pixel (cull_skip_mask, wave-uniform: bit k = object k).  flat_query<false, true> leaves such an object's test out,
+// which changes nothing: none of the wave's tests of it would have accepted.  A lane inside a test that runs is not
+// masked: the exact test decides, as before.  (The object filter's f32 boxes, tested per pending ray in the pass, were
+// built first: bit-equal, two thirds of the passes skipped the cubes, and 0.9 % slower — profiles/pretrace_cull_ab.txt.)
+typedef unsigned short US2 __attribute__((ext_vector_type(2)));
+RPT_DEV uint32_t cull_near(const FlatLayout& lay, uint32_t pix, uint32_t width) {
+  const uint32_t y = pix / width, x = pix - y * width; // (camera_ray's own quotient)
+  const US2 xy = {(unsigned short)x, (unsigned short)y};
+  uint32_t near = 0u;
+  for (uint32_t j = 0; j < lay.cull_n; j++) { // (wave-uniform) inside: (x - x0, y - y0) <= (x1 - x0, y1 - y0), both halves at once
+    const US2 t = xy - __builtin_bit_cast(US2, lay.cull_lo[j]);
+    const US2 m = __builtin_elementwise_min(t, __builtin_bit_cast(US2, lay.cull_ext[j]));
+    near |= (__builtin_bit_cast(uint32_t, m) == __builtin_bit_cast(uint32_t, t) ? 1u : 0u) << j;
+  }
+  return near;
+}
+// among the lanes that call (the pending ones): the objects whose rectangle holds none of their pixels
+RPT_DEV uint64_t cull_skip_mask(const FlatLayout& lay, uint32_t near) {
+  uint64_t skip = 0ull;
+  for (uint32_t j = 0; j < lay.cull_n; j++) // (wave-uniform)
+    if (__ballot(((near >> j) & 1u) != 0u) == 0ull) skip |= 1ull << (lay.cull_obj[j] & 63u);
+  return skip;
+}
+#endif
+
+// CULL (the pre-trace pass of rpt_paths<KdFlat, false, true>, RPT_PRETRACE_CULL): bit k of the wave-uniform `skip` = no
+// ray of the wave can be accepted by object k (cull_skip_mask), its test is left out
+template <bool SHADOW, bool CULL = false>
+RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_stop, double& rt, D3& rn, uint64_t skip = 0ull) {
   int obj = -1;
   RcpD rwx = rcp_make(d.x), rwy = rcp_make(d.y), rwz = rcp_make(d.z);
   const int n = sc.num_objects;
@@ -316,6 +352,11 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
       // two consecutive Transformed<Cube> (the boxes of C2): both candidates are evaluated in one block — a cube's
       // test depends on the record only through the final `time < record.time` (cube.rs:66) — and then accepted in
       // object order, so the second cube does not wait for the first one's whole chain
+      if (CULL && ((skip >> i) & 3ull) == 3ull) { // (the block as it is when one of the two may be hit)
+        PROF_COUNT(PF_P_PRECULL);
+        i += 2;
+        continue;
+      }
       CInst& in2 = cinst(sc, i + 1);
       D3 lo1 = mat4_mul(in.inv, o, 1.0), ld1 = mat4_mul(in.inv, d, 0.0);
       D3 lo2 = mat4_mul(in2.inv, o, 1.0), ld2 = mat4_mul(in2.inv, d, 0.0);
@@ -339,6 +380,10 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
       if (SHADOW && rt <= t_stop) return obj;
       i += 2;
     } else {
+      if (CULL && ((skip >> i) & 1ull) != 0ull) {
+        i++;
+        continue;
+      }
       if (isect_inst<KdFlat, SHADOW>(sc, in, o, d, rwx, rwy, rwz, EPSILON, t_stop, rt, rn, (KdFlat*)nullptr)) obj = i;
       if (SHADOW && rt <= t_stop) return obj;
       i++;
@@ -829,6 +874,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
   auto& stash = *reinterpret_cast<StashT*>(&stash_store);
   bool stash_valid = false, exhausted = false; // exhausted: the work counter ran out for this lane
   bool pend = false; // PRETRACE: the stashed ray is not traced yet
+#if RPT_PRETRACE_CULL
+  uint32_t near = ~0u; // FUSE: the screen rectangles that hold the pending ray's pixel (cull_near), from its generation to its pre-trace
+#endif
   ItemPool pool{0u, 0u, 0u};
   // parked environment lookups (see the top of this file): park_hd = header slot of a parked path that holds ring slots
   constexpr bool park_on = PARK;
@@ -855,6 +903,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
           D3 go, gd;
           Rng gr;
           camera_ray(fr, cam, dim, g_pixel, g_s, go, gd, gr);
+#if RPT_PRETRACE_CULL
+          if constexpr (FUSE) near = cull_near(pa.flat, g_pixel, fr.width);
+#endif
           stash.v[0][lane] = go.x; stash.v[1][lane] = go.y; stash.v[2][lane] = go.z;
           stash.v[3][lane] = gd.x; stash.v[4][lane] = gd.y; stash.v[5][lane] = gd.z;
           stash.v[6][lane] = __longlong_as_double((long long)gr.hi);
@@ -928,7 +979,13 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
           const D3 sd = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
           double t = INF;
           D3 hn = mk(0, 0, 0);
+#if RPT_PRETRACE_CULL
+          const uint64_t skip = cull_skip_mask(pa.flat, near); // (wave-uniform; 0 without the host's rectangles: every test runs)
+          PROF_COUNT(PF_P_PRETRACE);
+          const int ho = flat_query<false, true>(sc, &fl, so, sd, -INF, t, hn, skip);
+#else
           const int ho = flat_query<false>(sc, &fl, so, sd, -INF, t, hn);
+#endif
           n_ext++;
           if (ho < 0) hn = env_color(sc, sd); // renderer.rs:147
           const D3 hp = so + t * sd;
