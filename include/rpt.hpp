@@ -674,6 +674,35 @@ class Renderer {
     samples_done_ += iterations;
     buffer.add_samples(colors);
   }
+  // addition: the first-hit feature buffers of this renderer's frame (rptgpu_render_aov, include/rpt_gpu.h): per pixel the
+  // SUMS over the hits of num_samples camera rays — the rays render() starts its paths with — and the hit count; the
+  // caller divides.  Row-major, top row first; a vector of a channel not named in `channels` (RPT_AOV_*) stays empty.
+  struct Aovs {
+    std::vector<uint32_t> hits;
+    std::vector<double> depth, normal, albedo, position; // depth: width*height; the others: width*height*3
+    std::vector<int32_t> object;                          // the object the first sample hit, -1: none
+  };
+  Aovs render_aovs(uint32_t channels = RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION | RPT_AOV_OBJECT) {
+    ensure_scene();
+    RptRenderParams p{};
+    p.width = width_; p.height = height_; p.iterations = num_samples_; p.seed = seed_;
+    p.tile_width = 32; p.tile_height = 8; p.part_index = 0; p.part_count = 1;
+    RptCamera cam = camera_.lower();
+    const size_t n = (size_t)width_ * height_;
+    Aovs a;
+    a.hits.resize(n);
+    if (channels & RPT_AOV_DEPTH) a.depth.resize(n);
+    if (channels & RPT_AOV_NORMAL) a.normal.resize(3 * n);
+    if (channels & RPT_AOV_ALBEDO) a.albedo.resize(3 * n);
+    if (channels & RPT_AOV_POSITION) a.position.resize(3 * n);
+    if (channels & RPT_AOV_OBJECT) a.object.resize(n);
+    RptAovBuffers b{};
+    b.struct_size = sizeof(RptAovBuffers); b.channels = channels;
+    b.hits = a.hits.data(); b.depth = a.depth.data(); b.normal = a.normal.data(); b.albedo = a.albedo.data();
+    b.position = a.position.data(); b.object = a.object.data();
+    check(rptgpu_render_aov(handle_, &cam, &p, &b));
+    return a;
+  }
   // addition: after the caller has changed the placements (Transformed fields) and materials of the Scene's objects and
   // lights — not their geometry, counts, kinds or the environment, which need a new Renderer — push all of them into the
   // scene handle this Renderer already holds (rptgpu_scene_set_objects / _lights): the kd-trees, the workspace and

@@ -487,6 +487,42 @@ int rptgpu_buffer_sample_counts(const rptgpu_buffer* b, uint32_t* out_counts);
  * linear mean of pixel p is its sum / n_p */
 int rptgpu_buffer_totals(const rptgpu_buffer* b, double* out_totals);
 
+/* ---- first-hit feature buffers ("AOVs"): what a denoiser, a compositor or a picking tool asks of a frame
+ * besides its colour.  Additions within ABI version 7, detected by symbol (dlsym "rptgpu_render_aov").
+ * One stateless call.  For each pixel p the call owns (the tile partition of RptRenderParams, as in rptgpu_render_batch)
+ * and each sample index s = sample_index_base .. sample_index_base + iterations - 1, in ascending order:
+ *   1. ray = the camera ray of (p, s): renderer.rs:132-139 + Camera::cast_ray (camera.rs:64-81) with the draws of the
+ *      Philox stream (seed, p, s) — the very ray the colour sample (p, s) of rptgpu_render_batch starts with (jitter, then
+ *      the lens disc when aperture > 0);
+ *   2. (t, n, obj) = get_closest_hit(ray) (renderer.rs:211-220): what rptgpu_closest_hit returns for that ray;
+ *   3. if it hit (obj >= 0): hits += 1, depth += t, normal += n, albedo += objects[obj].material.color,
+ *      position += ray.at(t), ray.at(t) = origin + t * dir per component (shape.rs:59-61: one multiply, then one add, never
+ *      contracted).  A miss adds nothing;
+ *   4. object = obj of the call's FIRST sample (s = sample_index_base), -1 on a miss.
+ * All sums are f64, start at +0.0 and add in ascending sample order, so a result is defined to the bit (a lone -0.0
+ * comes out as +0.0 + -0.0 = +0.0).  The outputs are SUMS plus the hit count: the caller divides (mean = sum / hits) and
+ * may add the sums of consecutive calls.  max_bounces, exposure_value and collective are ignored.  Pixels outside the
+ * caller's part get 0 everywhere and object = -1.  After a live update (rptgpu_scene_set_objects) the buffers are those
+ * of a handle freshly created from the updated scene.
+ * RPT_FLAG_WAVEFRONT, RPT_FLAG_PERSISTENT and RPT_FLAG_GENERAL_TRAVERSAL choose the route as they do for a render (one
+ * fused kernel, rpt_aov, or rpt_raygen + the per-tree closest-hit query + rpt_aov_fold in passes) and never change a bit.
+ * RPTGPU_E_INVALID_ARGUMENT, checked before any device work and with a detail naming the reason: a NULL handle / camera /
+ * params / out, a wrong struct_size, an unknown channel bit, hits == NULL, a named channel whose pointer is NULL,
+ * iterations == 0, width * height == 0, a precision_mode other than RPT_PRECISION_F64_STRICT, an abandoned handle. */
+enum { RPT_AOV_DEPTH = 1u, RPT_AOV_NORMAL = 2u, RPT_AOV_ALBEDO = 4u, RPT_AOV_POSITION = 8u, RPT_AOV_OBJECT = 16u };
+typedef struct RptAovBuffers {        /* host arrays, row-major, top row first                                  */
+  uint32_t struct_size;               /* sizeof(RptAovBuffers)                                                  */
+  uint32_t channels;                  /* RPT_AOV_* wanted; a channel not named is not computed, its pointer not */
+                                      /* read, its array not written                                            */
+  uint32_t* hits;                     /* width*height, ALWAYS written, must not be NULL                         */
+  double* depth;                      /* width*height                                                           */
+  double* normal;                     /* width*height*3                                                         */
+  double* albedo;                     /* width*height*3                                                         */
+  double* position;                   /* width*height*3                                                         */
+  int32_t* object;                    /* width*height                                                           */
+} RptAovBuffers;
+int rptgpu_render_aov(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams* params, const RptAovBuffers* out);
+
 /* ---- particle systems: the reference's `rpt::ode` (src/ode.rs, src/ode/particle_system.rs) on the device.
  * Additions within ABI version 7: no earlier struct or signature changed, so a caller detects them by symbol
  * (dlsym "rptgpu_particles_integrate"), not by version.

@@ -9,6 +9,8 @@ The path tracer and the particle systems are HIP (rpt_amd/csrc) behind the C ABI
 """
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401
+from ._abi import (RPT_AOV_ALBEDO, RPT_AOV_ALL, RPT_AOV_DEPTH, RPT_AOV_NORMAL, RPT_AOV_OBJECT,  # noqa: F401
+                   RPT_AOV_POSITION)
 from .buffer import Buffer, Filter  # noqa: F401
 from .camera import Camera  # noqa: F401
 from .color import color_bytes, hex_color  # noqa: F401

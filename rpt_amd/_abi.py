@@ -40,6 +40,8 @@ RPT_PARTICLES_FLAG_GRID = 2
 RPT_PARTICLES_SINGLE_MAX = 2048
 RPT_PARTICLES_MAX_N = 715827882
 RPT_PARTICLES_MAX_STEPS = 1 << 26
+RPT_AOV_DEPTH, RPT_AOV_NORMAL, RPT_AOV_ALBEDO, RPT_AOV_POSITION, RPT_AOV_OBJECT = 1, 2, 4, 8, 16
+RPT_AOV_ALL = 31
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -147,6 +149,13 @@ class RptAdaptive(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_batches", C.c_uint32), ("abs_tol", f64), ("rel_tol", f64)]
 
 
+class RptAovBuffers(C.Structure):
+    """include/rpt_gpu.h RptAovBuffers (rptgpu_render_aov's host arrays; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("channels", C.c_uint32), ("hits", C.POINTER(C.c_uint32)),
+                ("depth", C.POINTER(f64)), ("normal", C.POINTER(f64)), ("albedo", C.POINTER(f64)),
+                ("position", C.POINTER(f64)), ("object", C.POINTER(C.c_int32))]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -189,6 +198,8 @@ SYMBOLS = [
      [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams), C.POINTER(RptAdaptive), C.POINTER(C.c_uint32)]),
     ("rptgpu_buffer_sample_counts", C.c_int, [_VP, C.POINTER(C.c_uint32)]),
     ("rptgpu_buffer_totals", C.c_int, [_VP, _PD]),
+    ("rptgpu_render_aov", C.c_int,
+     [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams), C.POINTER(RptAovBuffers)]),
     ("rptgpu_get_stats", C.c_int, [_VP, C.POINTER(RptStats)]),
     ("rptgpu_reset_stats", C.c_int, [_VP]),
     ("rptgpu_kernel_name", C.c_char_p, [C.c_int]),

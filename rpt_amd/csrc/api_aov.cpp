@@ -1,0 +1,172 @@
+// api_aov.cpp — rptgpu_render_aov: first-hit feature buffers (include/rpt_gpu.h; see api_internal.h).
+// Argument checks, the route (one fused kernel, or raygen + closest-hit query + fold in passes), the device arrays of the
+// requested channels, one copy per channel and one synchronisation.  The kernels: kernels/aov.inc.
+#include "api_internal.h"
+#include "render_plan.h"
+
+namespace {
+
+constexpr uint32_t AOV_ALL = RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION | RPT_AOV_OBJECT;
+
+// what is wrong with an RptAovBuffers (nullptr: nothing)
+const char* bad_aov(const RptAovBuffers* o) {
+  if (!o) return "null RptAovBuffers";
+  if (o->struct_size != sizeof(RptAovBuffers)) return "RptAovBuffers: struct_size is not sizeof(RptAovBuffers)";
+  if (o->channels & ~AOV_ALL) return "RptAovBuffers: channels names an unknown RPT_AOV_* bit";
+  if (!o->hits) return "RptAovBuffers: hits is NULL (it is always written)";
+  if ((o->channels & RPT_AOV_DEPTH) && !o->depth) return "RptAovBuffers: RPT_AOV_DEPTH is named but depth is NULL";
+  if ((o->channels & RPT_AOV_NORMAL) && !o->normal) return "RptAovBuffers: RPT_AOV_NORMAL is named but normal is NULL";
+  if ((o->channels & RPT_AOV_ALBEDO) && !o->albedo) return "RptAovBuffers: RPT_AOV_ALBEDO is named but albedo is NULL";
+  if ((o->channels & RPT_AOV_POSITION) && !o->position) return "RptAovBuffers: RPT_AOV_POSITION is named but position is NULL";
+  if ((o->channels & RPT_AOV_OBJECT) && !o->object) return "RptAovBuffers: RPT_AOV_OBJECT is named but object is NULL";
+  return nullptr;
+}
+// ... and with the fields of RptRenderParams this call reads (max_bounces, exposure_value and collective are ignored)
+const char* bad_aov_params(const RptRenderParams* p) {
+  if (!p) return "null params";
+  if (!p->iterations) return "iterations == 0";
+  if (!p->width || !p->height) return "width * height == 0";
+  if ((uint64_t)p->width * p->height >= (1ull << 31)) return "frame too large";
+  if (p->part_count && p->part_index >= p->part_count) return "part_index >= part_count";
+  if (p->precision_mode != RPT_PRECISION_F64_STRICT) return BAD_MODE;
+  return nullptr;
+}
+
+// the device arrays: the f64 channels first, then hits and object, each 16-byte aligned inside h->aov_out
+rptdev::AovOut device_arrays(rptgpu_scene* h, uint64_t n, uint32_t channels) {
+  const uint64_t words = (n + 3) / 4 * 2; // doubles that hold n 32-bit values, rounded up to 16 bytes
+  uint64_t off = 0, off_depth = 0, off_normal = 0, off_albedo = 0, off_position = 0, off_object = 0;
+  if (channels & RPT_AOV_DEPTH) { off_depth = off; off += (n + 1) / 2 * 2; }
+  if (channels & RPT_AOV_NORMAL) { off_normal = off; off += (3 * n + 1) / 2 * 2; }
+  if (channels & RPT_AOV_ALBEDO) { off_albedo = off; off += (3 * n + 1) / 2 * 2; }
+  if (channels & RPT_AOV_POSITION) { off_position = off; off += (3 * n + 1) / 2 * 2; }
+  const uint64_t off_hits = off;
+  off += words;
+  if (channels & RPT_AOV_OBJECT) { off_object = off; off += words; }
+  h->aov_out.alloc(off);
+  double* base = h->aov_out.p;
+  rptdev::AovOut ao{};
+  ao.channels = channels;
+  ao.hits = (uint32_t*)(base + off_hits);
+  if (channels & RPT_AOV_DEPTH) ao.depth = base + off_depth;
+  if (channels & RPT_AOV_NORMAL) ao.normal = base + off_normal;
+  if (channels & RPT_AOV_ALBEDO) ao.albedo = base + off_albedo;
+  if (channels & RPT_AOV_POSITION) ao.position = base + off_position;
+  if (channels & RPT_AOV_OBJECT) ao.object = (int32_t*)(base + off_object);
+  // every sum starts at +0.0 and every count at 0 (also where the part has no pixel); object = -1
+  HIP_TRY(hipMemsetAsync(base, 0, (off_hits + words) * sizeof(double), h->stream));
+  if (ao.object) HIP_TRY(hipMemsetAsync(ao.object, 0xff, n * sizeof(int32_t), h->stream));
+  return ao;
+}
+
+// Scenes with deep trees (and RPT_FLAG_WAVEFRONT): per pass rpt_raygen into the workspace's ray columns, the depth-0
+// closest-hit query of a render (run_pass, api_render.cpp), rpt_aov_fold.  Passes are sample-major and run in ascending
+// sample order, so a pixel's additions happen in sample order whatever the pass size; a camera ray reaches depth 0
+// only, hence one record column per path for the planner.
+void aov_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const rptdev::Camera& cam,
+                   const rptdev::AovOut& ao) {
+  hipStream_t st = h->stream;
+  const uint32_t npix = fr.npix;
+  rptplan::PassInput in{};
+  in.npix = npix; in.iterations = p.iterations;
+  in.per_slot = rptplan::wavefront_slot_bytes(h->dscene.num_lights, h->has_deep, h->sort_rays, h->path_reorder);
+  in.target_paths = h->target_paths; in.budget_bytes = h->ws_budget_bytes;
+  in.free_percent = RPT_WS_FREE_PERCENT;
+  in.rec_ratio = 1.0; in.ratio = 1.0;
+  const bool by_object = h->has_deep && (!(p.flags & RPT_FLAG_GENERAL_TRAVERSAL) || h->tree_kids);
+  const bool generic_all = h->has_deep && (h->gen_all || h->dscene.force_general);
+  const uint32_t trace_blocks = (uint32_t)std::max(1, h->num_cus * 4);
+  for (uint32_t s0 = 0; s0 < p.iterations;) {
+    in.remaining = p.iterations - s0;
+    in.free_bytes = in.target_paths ? -1 : free_memory();
+    in.held_slots = h->ws_cap; in.held_cols = h->ws_rec_cols;
+    in.fail_paths = h->ws_fail_paths;
+    rptplan::PassPlan pp = rptplan::plan_pass(in);
+    for (;;) {
+      const uint64_t np = rptplan::pass_slots(npix, pp);
+      try {
+        ensure_workspace(h, np, rptplan::pass_rec_cols(np, in.ratio));
+        if (generic_all) ensure_generic(h, true);
+        break;
+      } catch (const HipError& e) {
+        if (e.e != hipErrorOutOfMemory || pp.s_chunk == 1) throw;
+        (void)hipGetLastError();
+        release_workspace(h);
+        h->ws_fail_paths = rptplan::fail_paths_after_oom(h->ws_fail_paths, np);
+        pp = rptplan::shrink_after_oom(pp);
+      }
+    }
+    const uint32_t n_paths = npix * pp.s_chunk;
+    fr.sample_base = p.sample_index_base + s0;
+    const rptdev::PathState ps = path_state(h);
+    if (h->has_deep) {
+      HIP_TRY(hipMemsetAsync(h->tq_ctr.p, 0, 16 * sizeof(uint32_t), st));
+      h->qtune.ctr_set = 0;
+    }
+    kt->raygen(st, fr, cam, ps, n_paths);
+    if (by_object)
+      kt->query(st, h->dscene, ps, nullptr, n_paths, -1, nullptr, nullptr, h->obj_deep.data(), h->obj_tris.data(),
+                h->dscene.num_objects, h->tq.p, h->tq_ctr.p, trace_blocks, h->sort_rays ? &h->sort_bufs : nullptr, nullptr, &h->spill, &h->qtune);
+    else
+      kt->extend(st, h->dscene, ps, nullptr, n_paths);
+    kt->aov_fold(st, h->dscene, fr, ps, ao, pp.s_chunk, s0 == 0);
+    HIP_TRY(hipGetLastError());
+    s0 += pp.s_chunk;
+  }
+}
+
+} // namespace
+
+extern "C" int rptgpu_render_aov(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams* p, const RptAovBuffers* out) {
+  // (the buffers first: a bad RptAovBuffers is refused whatever else is wrong, also without a handle or a device)
+  if (const char* why = bad_aov(out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (const char* why = bad_aov_params(p)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (!camera) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null camera");
+  if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
+  if (h->abandoned)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "an aborted batch's device work never drained on this handle: destroy it");
+  try {
+    HIP_TRY(hipSetDevice(h->device));
+    (void)hipGetLastError(); // (as render_impl: the checks below speak about this call's launches)
+    hipStream_t st = h->stream;
+    const KernelTable* kt = table_for(p->precision_mode, h->ext_shapes);
+    ensure_partition(h, *p);
+    const uint64_t n = (uint64_t)p->width * p->height;
+    const rptdev::AovOut ao = device_arrays(h, n, out->channels);
+    // the route, chosen like a render's: a group with tree children is only walked by the per-tree kernels
+    const bool wavefront = (p->flags & RPT_FLAG_WAVEFRONT) || h->tree_kids ? true
+                           : (p->flags & RPT_FLAG_PERSISTENT)             ? false
+                                                                          : h->has_deep;
+    h->dscene.force_general = (p->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
+    if (h->npix) {
+      rptdev::Frame fr{};
+      fr.width = p->width; fr.height = p->height; fr.npix = h->npix; fr.pixels = h->pixels.p;
+      fr.seed = p->seed; fr.sample_base = p->sample_index_base;
+      const rptdev::Camera cam = make_camera(*camera);
+      if (wavefront) aov_wavefront(h, kt, *p, fr, cam, ao);
+      else kt->aov(st, h->dscene, fr, cam, ao, p->iterations);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out->hits, ao.hits, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (ao.depth) HIP_TRY(hipMemcpyAsync(out->depth, ao.depth, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ao.normal) HIP_TRY(hipMemcpyAsync(out->normal, ao.normal, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ao.albedo) HIP_TRY(hipMemcpyAsync(out->albedo, ao.albedo, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ao.position) HIP_TRY(hipMemcpyAsync(out->position, ao.position, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ao.object) HIP_TRY(hipMemcpyAsync(out->object, ao.object, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    uint32_t gen_overflow = 0; // rpt_tree_generic's flag rides with the call's one synchronisation, as in render_impl
+    if (wavefront && h->has_deep && h->gen_overflow.p)
+      HIP_TRY(hipMemcpyAsync(&gen_overflow, h->gen_overflow.p, sizeof gen_overflow, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (gen_overflow) {
+      (void)hipMemsetAsync(h->gen_overflow.p, 0, sizeof(uint32_t), st);
+      return fail(h, RPTGPU_E_TREE_TOO_DEEP, "rpt_tree_generic: the traversal outgrew the stack sized for this scene (internal error)");
+    }
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  } catch (const std::bad_alloc&) {
+    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
+  } catch (...) {
+    return fail(h, RPTGPU_E_HIP, "unexpected exception");
+  }
+  return RPTGPU_OK;
+}

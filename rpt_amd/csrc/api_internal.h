@@ -7,6 +7,7 @@
 //   api_comm.cpp     communicator, rptgpu_render_batch_reduce (the library-owned exchange and its failure paths),
 //                    rptgpu_render_batch_emulate_ranks
 //   api_buffer.cpp   the device-resident Buffer
+//   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, route choice, pass loop)
 // No compute happens on the host; if there is no HIP device every compute entry point returns RPTGPU_E_NO_DEVICE (there is
 // no CPU fallback by design).
 #pragma once
@@ -146,6 +147,7 @@ struct rptgpu_scene {
   uint64_t lbuf_max_bytes = 32ull << 30; // cap on lbuf (RPTGPU_LBUF_BYTES); larger batches run as several launches
   uint32_t paths_chunk = 0;            // samples per work item (RptSceneOptions::paths_chunk; 0 = chosen per launch)
   DevBuf<unsigned long long> pcounters; // [0] closest-hit rays [1] shadow rays
+  DevBuf<double> aov_out;              // rptgpu_render_aov: the requested channels' full-frame arrays, back to back (api_aov.cpp)
   int num_cus = 0;
   bool prefer_wavefront = false; // scene has real kd-trees: traversal-latency bound
   bool all_flat = false;         // every tree is a single leaf (and the scene fits the LDS tables): the path kernel
@@ -245,6 +247,13 @@ uint32_t zeros_common(const std::vector<rptdev::Light>& lights);
 void ensure_partition(rptgpu_scene* h, const RptRenderParams& p);
 std::vector<uint32_t> pixel_list(uint32_t width, uint32_t height, uint32_t tw, uint32_t th, uint32_t pi, uint32_t pc);
 const char* bad_params(const RptRenderParams* p);
+// the workspace and its views, shared with rptgpu_render_aov's pass loop (api_aov.cpp)
+void ensure_workspace(rptgpu_scene* h, uint64_t cap, uint64_t rec_cols);
+void release_workspace(rptgpu_scene* h);
+void ensure_generic(rptgpu_scene* h, bool all);
+rptdev::PathState path_state(rptgpu_scene* h);
+rptdev::Camera make_camera(const RptCamera& c);
+int64_t free_memory();
 // packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list.
 // d_list (device, n_list pixel indices; requires packed and d_out): render exactly those pixels instead of the part's list,
 // without touching the cached partition (the adaptive buffer's active pixels, api_buffer.cpp)

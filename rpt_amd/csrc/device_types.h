@@ -198,4 +198,16 @@ struct Frame {
   double* accum;            // [npix][3] running sum of L_0 over samples
 };
 
+// rptgpu_render_aov's device outputs (kernels/aov.inc): full-frame arrays indexed by pixel, as RptAovBuffers has them on
+// the host.  Only hits and the arrays of the channels named in `channels` (RPT_AOV_*) exist.
+struct AovOut {
+  uint32_t* hits;   // [width*height]
+  double* depth;    // [width*height]
+  double* normal;   // [width*height][3]
+  double* albedo;   // [width*height][3]
+  double* position; // [width*height][3]
+  int32_t* object;  // [width*height]
+  uint32_t channels;
+};
+
 } // namespace rptdev

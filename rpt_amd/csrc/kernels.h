@@ -206,6 +206,14 @@ struct KernelTable {
   bool (*read_prof)(unsigned long long out[4][29]);
   // in-kernel-traversal scenes: the next depth's paths sorted by ray key into the current state arrays (kernels/wavefront.inc)
   void (*path_reorder)(hipStream_t, const rptdev::PathState&, uint32_t n, bool sorted, const SortBufs* sort, uint32_t* order);
+  // first-hit feature buffers (kernels/aov.inc).  aov: camera ray, closest hit and the ordered fold of `iterations` samples
+  // per pixel of the frame's part in one kernel (Frame::sample_base = the call's first sample).  aov_fold: the hits of a
+  // pass of spp samples per pixel (rpt_raygen's slots, the depth-0 query's records) added to the sums; first = the pass
+  // holds the call's first sample
+  void (*aov)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::Camera&, const rptdev::AovOut&,
+              uint32_t iterations);
+  void (*aov_fold)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::PathState&, const rptdev::AovOut&,
+                   uint32_t spp, bool first);
 };
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)

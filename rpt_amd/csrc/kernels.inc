@@ -18,6 +18,7 @@
 //                  kernels (rpt_rays_init, rpt_tree_enter, rpt_tree_trace, rpt_nest_trace, rpt_tree_generic — the one that
 //                  walks trees inside trees to any depth —, rpt_rays_objects, rpt_shadow_sum)
 //   buffer.inc     device-resident Buffer (buffer.rs)
+//   aov.inc        first-hit feature buffers: rpt_aov (fused) and rpt_aov_fold (behind the per-tree query), DESIGN.md §11
 //   launch.inc     explicit instantiations, host-side launchers, the KernelTable the api_*.cpp files call through
 //
 // Wave64 throughout (gfx950): queue appends and work fetches use one 64-bit ballot + one atomic per wave.
@@ -81,6 +82,7 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/wavefront.inc"
 #include "kernels/paths.inc"
 #include "kernels/buffer.inc"
+#include "kernels/aov.inc"
 #include "kernels/launch.inc"
 
 } // namespace RPT_NS

@@ -266,6 +266,14 @@ void launch_eval_math(hipStream_t st, int fn, uint64_t n, const double* x, const
   hipLaunchKernelGGL(rpt_eval_math, grid_for(n), dim3(256), 0, st, fn, n, x, y, out);
 }
 
+void launch_aov(hipStream_t st, const Scene& sc, const Frame& fr, const Camera& cam, const AovOut& out, uint32_t iterations) {
+  hipLaunchKernelGGL(rpt_aov, grid_for(fr.npix), dim3(256), 0, st, sc, fr, cam, out, iterations);
+}
+void launch_aov_fold(hipStream_t st, const Scene& sc, const Frame& fr, const PathState& ps, const AovOut& out, uint32_t spp,
+                     bool first) {
+  hipLaunchKernelGGL(rpt_aov_fold, grid_for(fr.npix), dim3(256), 0, st, sc, fr, ps, out, spp, first ? 1 : 0);
+}
+
 // debug builds with -DRPT_PROF: the per-phase table of kernels/prof.inc accumulated so far (and reset):
 // out[0] wave cycles, [1] lane cycles, [2] wave iterations, [3] lane iterations, PROF_SLOTS slots each
 bool read_prof(unsigned long long out[4][29]) {
@@ -285,5 +293,5 @@ const KernelTable TABLE = {launch_raygen, launch_extend, launch_extend_rays, lau
                            launch_shadow_rays, launch_resolve, launch_finish, launch_scatter_f32, launch_eval_math,
                            paths_max_blocks_per_cu, launch_paths, launch_sum_samples, launch_query, sort_temp_bytes, launch_shadow_sum,
                            launch_buffer_accumulate, launch_buffer_retire, launch_buffer_image, launch_buffer_variance,
-                           read_prof, launch_path_reorder};
+                           read_prof, launch_path_reorder, launch_aov, launch_aov_fold};
 #endif // !__HIP_DEVICE_COMPILE__

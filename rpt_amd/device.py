@@ -184,6 +184,29 @@ class GpuScene:
         _abi.check(code, self.handle)
         return t, nrm, obj
 
+    def render_aov(self, camera, params, channels=_abi.RPT_AOV_ALL):
+        """First-hit feature buffers (rptgpu_render_aov) -> a dict of numpy arrays: `hits` (H, W) uint32
+        always, and per channel of `channels` (RPT_AOV_*) the f64 SUMS over the hits of params.iterations camera rays per
+        pixel — `depth` (H, W), `normal` / `albedo` / `position` (H, W, 3) — and `object` (H, W) int32, the object the
+        call's first sample hit (-1: none).  A mean is sum / hits."""
+        channels = int(channels)
+        h, w = params.height, params.width
+        arrays = {"hits": np.zeros((h, w), dtype=np.uint32)}
+        for bit, name, shape, dtype in ((_abi.RPT_AOV_DEPTH, "depth", (h, w), np.float64),
+                                        (_abi.RPT_AOV_NORMAL, "normal", (h, w, 3), np.float64),
+                                        (_abi.RPT_AOV_ALBEDO, "albedo", (h, w, 3), np.float64),
+                                        (_abi.RPT_AOV_POSITION, "position", (h, w, 3), np.float64),
+                                        (_abi.RPT_AOV_OBJECT, "object", (h, w), np.int32)):
+            if channels & bit:
+                arrays[name] = np.zeros(shape, dtype=dtype)
+        b = _abi.RptAovBuffers()
+        b.struct_size, b.channels = C.sizeof(_abi.RptAovBuffers), channels
+        for name, a in arrays.items():
+            setattr(b, name, a.ctypes.data_as(dict(_abi.RptAovBuffers._fields_)[name]))
+        cam = camera.lower() if hasattr(camera, "lower") else camera
+        _abi.check(self.lib.rptgpu_render_aov(self.handle, C.byref(cam), C.byref(params), C.byref(b)), self.handle)
+        return arrays
+
     def eval_math(self, fn, x, y=None):
         """include/rpt_math.h evaluated on the device (diagnostics)."""
         x = np.ascontiguousarray(x, dtype=np.float64)

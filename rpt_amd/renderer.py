@@ -127,6 +127,24 @@ class Renderer:
         finally:
             buffer.close()
 
+    def render_aovs(self, channels=_abi.RPT_AOV_ALL):
+        """The first-hit feature buffers of this renderer's frame (width, height, seed, num_samples camera rays per pixel:
+        the rays render() starts its paths with) as MEANS over each pixel's hits: GpuScene.render_aov's dict with `depth`,
+        `normal`, `albedo`, `position` divided by `hits`; a pixel without a hit holds 0, never NaN.  `hits` and `object`
+        are returned as they are."""
+        import numpy as np
+        params = make_params(self._width, self._height, self._max_bounces, self._num_samples, self._exposure_value,
+                             self._seed, 0, precision=self._precision)
+        out = self.gpu_scene().render_aov(self.camera, params, channels)
+        hits = out["hits"]
+        n = np.where(hits > 0, hits, 1).astype(np.float64)
+        for name in ("depth", "normal", "albedo", "position"):
+            if name in out:
+                mean = out[name] / (n if out[name].ndim == 2 else n[..., None])
+                mean[hits == 0] = 0.0
+                out[name] = mean
+        return out
+
     def sample(self, iterations, buffer):  # renderer.rs:117-129 — THE hot path, on the GPU
         params = make_params(self._width, self._height, self._max_bounces, iterations,
                              self._exposure_value, self._seed, self._samples_done,

@@ -61,6 +61,11 @@ pub mod ffi {
     pub const RPT_PARTICLES_SINGLE_MAX: u64 = 2048;
     pub const RPT_PARTICLES_MAX_N: u64 = 715827882;
     pub const RPT_PARTICLES_MAX_STEPS: u64 = 67108864;
+    pub const RPT_AOV_DEPTH: u32 = 1;
+    pub const RPT_AOV_NORMAL: u32 = 2;
+    pub const RPT_AOV_ALBEDO: u32 = 4;
+    pub const RPT_AOV_POSITION: u32 = 8;
+    pub const RPT_AOV_OBJECT: u32 = 16;
     pub const RPTGPU_UNIQUE_ID_BYTES: usize = 128;
 
     /// `Material` (rpt src/material.rs:8-26)
@@ -265,6 +270,19 @@ pub mod ffi {
         pub rel_tol: f64,
     }
 
+    /// `RptAovBuffers` (the host arrays of `rptgpu_render_aov`; detected by symbol within ABI 7)
+    #[repr(C)]
+    pub struct RptAovBuffers {
+        pub struct_size: u32,
+        pub channels: u32,
+        pub hits: *mut u32,
+        pub depth: *mut f64,
+        pub normal: *mut f64,
+        pub albedo: *mut f64,
+        pub position: *mut f64,
+        pub object: *mut i32,
+    }
+
     /// opaque `rptgpu_scene`
     #[repr(C)]
     pub struct rptgpu_scene {
@@ -310,6 +328,7 @@ pub mod ffi {
         pub fn rptgpu_buffer_sample_adaptive(b: *mut rptgpu_buffer, camera: *const RptCamera, params: *const RptRenderParams, a: *const RptAdaptive, out_active: *mut u32) -> c_int;
         pub fn rptgpu_buffer_sample_counts(b: *const rptgpu_buffer, out_counts: *mut u32) -> c_int;
         pub fn rptgpu_buffer_totals(b: *const rptgpu_buffer, out_totals: *mut f64) -> c_int;
+        pub fn rptgpu_render_aov(h: *mut rptgpu_scene, camera: *const RptCamera, params: *const RptRenderParams, out: *const RptAovBuffers) -> c_int;
         pub fn rptgpu_get_stats(h: *const rptgpu_scene, out: *mut RptStats) -> c_int;
         pub fn rptgpu_reset_stats(h: *mut rptgpu_scene) -> c_int;
         pub fn rptgpu_kernel_name(k: c_int) -> *const c_char;
@@ -669,6 +688,7 @@ mod layout_tests {
         assert_eq!(size_of::<RptKdTree>(), 64);
         assert_eq!(size_of::<RptParticleSystem>(), 16);
         assert_eq!(size_of::<RptAdaptive>(), 24);
+        assert_eq!(size_of::<RptAovBuffers>(), 56);
     }
 
     #[test]
