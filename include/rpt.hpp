@@ -703,6 +703,44 @@ class Renderer {
     check(rptgpu_render_aov(handle_, &cam, &p, &b));
     return a;
   }
+  // addition: iterative_render with the Buffer kept on the device (rptgpu_buffer_*), followed by the feature-guided
+  // a-trous filter of rptgpu_buffer_denoise (include/rpt_gpu.h) guided by the first hits of samples 0 .. feature_samples-1.
+  // At least two batches (num_samples > callback_interval), else the library refuses: one batch has no variance.
+  RgbImage denoised_render(uint32_t callback_interval, uint32_t feature_samples = 4, uint32_t levels = 3,
+                           double sigma_color = 2.0, double sigma_normal = 0.1, double sigma_depth = 0.01,
+                           double sigma_albedo = 0.1) {
+    ensure_scene();
+    rptgpu_buffer* buf = nullptr;
+    check(rptgpu_buffer_create(handle_, width_, height_, filter_.radius, &buf));
+    RgbImage img;
+    img.width = width_; img.height = height_;
+    img.data.resize((size_t)width_ * height_ * 3);
+    try {
+      RptCamera cam = camera_.lower();
+      RptRenderParams p{};
+      p.width = width_; p.height = height_; p.max_bounces = max_bounces_; p.exposure_value = ev_; p.seed = seed_;
+      p.tile_width = 32; p.tile_height = 8; p.part_index = 0; p.part_count = 1;
+      samples_done_ = 0;
+      for (uint32_t iteration = 0; iteration < num_samples_;) {
+        p.iterations = std::min(num_samples_ - iteration, callback_interval);
+        p.sample_index_base = samples_done_;
+        check(rptgpu_buffer_sample(buf, &cam, &p));
+        samples_done_ += p.iterations;
+        iteration += p.iterations;
+      }
+      p.iterations = feature_samples; p.sample_index_base = 0;
+      check(rptgpu_buffer_features(buf, &cam, &p));
+      RptDenoise d{};
+      d.struct_size = sizeof(RptDenoise); d.levels = levels;
+      d.sigma_color = sigma_color; d.sigma_normal = sigma_normal; d.sigma_depth = sigma_depth; d.sigma_albedo = sigma_albedo;
+      check(rptgpu_buffer_denoise(buf, &d, nullptr, img.data.data()));
+    } catch (...) {
+      rptgpu_buffer_destroy(buf);
+      throw;
+    }
+    rptgpu_buffer_destroy(buf);
+    return img;
+  }
   // addition: after the caller has changed the placements (Transformed fields) and materials of the Scene's objects and
   // lights — not their geometry, counts, kinds or the environment, which need a new Renderer — push all of them into the
   // scene handle this Renderer already holds (rptgpu_scene_set_objects / _lights): the kd-trees, the workspace and

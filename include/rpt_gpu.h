@@ -523,6 +523,59 @@ typedef struct RptAovBuffers {        /* host arrays, row-major, top row first  
 } RptAovBuffers;
 int rptgpu_render_aov(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams* params, const RptAovBuffers* out);
 
+/* ---- feature-guided denoising of the device-resident Buffer: an edge-avoiding a-trous wavelet filter
+ * (Dammertz et al. 2010) with the variance guidance of SVGF (Schied et al. 2017), run wholly on the device on what the
+ * buffer already holds.  Additions within ABI version 7, detected by symbol (dlsym "rptgpu_buffer_denoise").
+ *
+ * FEATURES.  rptgpu_buffer_features computes what rptgpu_render_aov computes for (camera, params) with the channels
+ * DEPTH | NORMAL | ALBEDO | POSITION — the same sums and hits, by the same two routes, bit for bit — and leaves them in
+ * device arrays the buffer owns; nothing of them travels to the host.  A later call replaces them (a failed one leaves
+ * the buffer without features).  params->width / height must be the buffer's and part_count <= 1; the other refusals are
+ * rptgpu_render_aov's.  The sample range is the caller's: sample_index_base = 0 with a few iterations gives the first
+ * hits of the rays the buffer's first colour samples started with.  rptgpu_buffer_feature_sums copies the held sums out
+ * through an RptAovBuffers (tests, tools); `object` is not held: naming RPT_AOV_OBJECT is refused.
+ *
+ * THE FILTER, defined to the bit.  All arithmetic is IEEE f64, never contracted; exp is rpt_exp of include/rpt_math.h;
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; |a|^2 = dot(a, a); every sum starts at +0.0 and a vector sum adds per
+ * component; taps are visited x-outer / y-inner, both ascending (the box filter's order, buffer.rs:80-81); a tap outside
+ * the frame is skipped (it adds nothing to any sum).
+ *   Inputs of pixel p, with n = (double)n_p and h = the held hit count of p:
+ *     c_p = total_p / n per component;  u_p = (M2_p / (n - 1.0)) / n  (the variance of that mean; M2 sums the channels);
+ *     hit_p = h > 0, and where hit_p, each per component: N_p = normal_p / (double)h, P_p = position_p / (double)h,
+ *     Z_p = depth_p / (double)h, A_p = albedo_p / (double)h.
+ *   Variance prefilter, g(-1) = g(1) = 0.25, g(0) = 0.5, over q = p + (dx, dy), dx, dy in -1..1:
+ *     a = a + (g(dx) * g(dy)) * u_q;  s = s + g(dx) * g(dy);  then v_p = a / s.
+ *   Level l = 0 .. levels - 1, step = 2^l, k(0) = 0.375, k(-1) = k(1) = 0.25, k(-2) = k(2) = 0.0625, over
+ *   q = p + step * (dx, dy), dx, dy in -2..2, with w0 = k(dx) * k(dy):
+ *     the centre tap (dx = dy = 0):  w = w0, no exponent is evaluated;
+ *     any other tap is skipped when hit_q != hit_p; otherwise, with d = c_q - c_p,
+ *       e = |d|^2 / (sigma_color * sigma_color * (v_p + v_q) + 1e-12)      [(sc * sc) * (v_p + v_q), then + 1e-12]
+ *       and where both are hits, with t = 1.0 - dot(N_p, N_q) and D = A_q - A_p:
+ *         en = (t > 0.0 ? t : 0.0) / sigma_normal
+ *         ez = fabs(dot(N_p, P_q - P_p)) / (sigma_depth * Z_p + 1e-12)
+ *         ea = |D|^2 / (sigma_albedo * sigma_albedo)
+ *         e  = e + ((en + ez) + ea);
+ *       the tap is skipped unless e >= 0.0 and e < +inf (a NaN fails both: a NaN or infinite pixel keeps its own value
+ *       and never spreads); else w = w0 * exp(-e);
+ *     a tap that is not skipped adds  C = C + w * c_q,  W = W + w,  V = V + (w * w) * v_q;
+ *     then c'_p = C / W per component and v'_p = V / (W * W); (c', v') are the next level's (c, v); the features stay.
+ *   out_linear = the last level's c', out_linear[(y*width+x)*3+ch]; out_rgb8 = color_bytes of it (color.rs:18-24, through
+ *   the thresholds rptgpu_buffer_image uses).  Either may be NULL, not both.
+ * The buffer's own state (totals, counts, Welford state, batches, features) is not modified: image(), variance() and
+ * totals() give the same bits before and after.  A buffer with retired pixels (uneven n_p) is filtered like any other.
+ * RPTGPU_E_INVALID_ARGUMENT before any device work, with a detail naming the reason: a NULL RptDenoise, a wrong
+ * struct_size, levels outside 1..8, a sigma that is not finite or not > 0 (these first, so also without a buffer); a
+ * NULL buffer; both outputs NULL; no features held; fewer than two batches (every pixel holds min(batches, the count
+ * it retired with >= 2) of them, and one batch has no variance); an abandoned handle (RPTGPU_E_COMM). */
+typedef struct RptDenoise {
+  uint32_t struct_size; /* sizeof(RptDenoise) */
+  uint32_t levels;      /* 1 .. 8: a-trous passes, tap spacing 1, 2, 4, ... */
+  double sigma_color, sigma_normal, sigma_depth, sigma_albedo; /* finite, > 0 */
+} RptDenoise;
+int rptgpu_buffer_features(rptgpu_buffer* b, const RptCamera* camera, const RptRenderParams* params);
+int rptgpu_buffer_feature_sums(const rptgpu_buffer* b, const RptAovBuffers* out);
+int rptgpu_buffer_denoise(rptgpu_buffer* b, const RptDenoise* d, double* out_linear, uint8_t* out_rgb8);
+
 /* ---- particle systems: the reference's `rpt::ode` (src/ode.rs, src/ode/particle_system.rs) on the device.
  * Additions within ABI version 7: no earlier struct or signature changed, so a caller detects them by symbol
  * (dlsym "rptgpu_particles_integrate"), not by version.

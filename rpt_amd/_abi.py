@@ -156,6 +156,12 @@ class RptAovBuffers(C.Structure):
                 ("position", C.POINTER(f64)), ("object", C.POINTER(C.c_int32))]
 
 
+class RptDenoise(C.Structure):
+    """include/rpt_gpu.h RptDenoise (rptgpu_buffer_denoise's parameters; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_uint32), ("sigma_color", f64), ("sigma_normal", f64),
+                ("sigma_depth", f64), ("sigma_albedo", f64)]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -200,6 +206,9 @@ SYMBOLS = [
     ("rptgpu_buffer_totals", C.c_int, [_VP, _PD]),
     ("rptgpu_render_aov", C.c_int,
      [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams), C.POINTER(RptAovBuffers)]),
+    ("rptgpu_buffer_features", C.c_int, [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams)]),
+    ("rptgpu_buffer_feature_sums", C.c_int, [_VP, C.POINTER(RptAovBuffers)]),
+    ("rptgpu_buffer_denoise", C.c_int, [_VP, C.POINTER(RptDenoise), _PD, C.POINTER(C.c_uint8)]),
     ("rptgpu_get_stats", C.c_int, [_VP, C.POINTER(RptStats)]),
     ("rptgpu_reset_stats", C.c_int, [_VP]),
     ("rptgpu_kernel_name", C.c_char_p, [C.c_int]),

@@ -1,10 +1,12 @@
 // api_aov.cpp — rptgpu_render_aov: first-hit feature buffers (include/rpt_gpu.h; see api_internal.h).
 // Argument checks, the route (one fused kernel, or raygen + closest-hit query + fold in passes), the device arrays of the
 // requested channels, one copy per channel and one synchronisation.  The kernels: kernels/aov.inc.
+// The device half (aov_arrays, aov_enqueue, aov_drain) writes into arrays it is handed: rptgpu_render_aov hands it the
+// handle's own and copies them out, rptgpu_buffer_features (api_buffer.cpp) hands it arrays the buffer keeps.
 #include "api_internal.h"
 #include "render_plan.h"
 
-namespace {
+namespace rptapi {
 
 constexpr uint32_t AOV_ALL = RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION | RPT_AOV_OBJECT;
 
@@ -32,8 +34,8 @@ const char* bad_aov_params(const RptRenderParams* p) {
   return nullptr;
 }
 
-// the device arrays: the f64 channels first, then hits and object, each 16-byte aligned inside h->aov_out
-rptdev::AovOut device_arrays(rptgpu_scene* h, uint64_t n, uint32_t channels) {
+// the device arrays: the f64 channels first, then hits and object, each 16-byte aligned inside `arrays`
+rptdev::AovOut aov_arrays(DevBuf<double>& arrays, hipStream_t st, uint64_t n, uint32_t channels) {
   const uint64_t words = (n + 3) / 4 * 2; // doubles that hold n 32-bit values, rounded up to 16 bytes
   uint64_t off = 0, off_depth = 0, off_normal = 0, off_albedo = 0, off_position = 0, off_object = 0;
   if (channels & RPT_AOV_DEPTH) { off_depth = off; off += (n + 1) / 2 * 2; }
@@ -43,8 +45,8 @@ rptdev::AovOut device_arrays(rptgpu_scene* h, uint64_t n, uint32_t channels) {
   const uint64_t off_hits = off;
   off += words;
   if (channels & RPT_AOV_OBJECT) { off_object = off; off += words; }
-  h->aov_out.alloc(off);
-  double* base = h->aov_out.p;
+  arrays.alloc(off);
+  double* base = arrays.p;
   rptdev::AovOut ao{};
   ao.channels = channels;
   ao.hits = (uint32_t*)(base + off_hits);
@@ -54,10 +56,12 @@ rptdev::AovOut device_arrays(rptgpu_scene* h, uint64_t n, uint32_t channels) {
   if (channels & RPT_AOV_POSITION) ao.position = base + off_position;
   if (channels & RPT_AOV_OBJECT) ao.object = (int32_t*)(base + off_object);
   // every sum starts at +0.0 and every count at 0 (also where the part has no pixel); object = -1
-  HIP_TRY(hipMemsetAsync(base, 0, (off_hits + words) * sizeof(double), h->stream));
-  if (ao.object) HIP_TRY(hipMemsetAsync(ao.object, 0xff, n * sizeof(int32_t), h->stream));
+  HIP_TRY(hipMemsetAsync(base, 0, (off_hits + words) * sizeof(double), st));
+  if (ao.object) HIP_TRY(hipMemsetAsync(ao.object, 0xff, n * sizeof(int32_t), st));
   return ao;
 }
+
+namespace {
 
 // Scenes with deep trees (and RPT_FLAG_WAVEFRONT): per pass rpt_raygen into the workspace's ray columns, the depth-0
 // closest-hit query of a render (run_pass, api_render.cpp), rpt_aov_fold.  Passes are sample-major and run in ascending
@@ -117,6 +121,43 @@ void aov_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams
 
 } // namespace
 
+// The route and the kernels of one call into the zeroed arrays `ao`, enqueued on the handle's stream; -> whether
+// rpt_tree_generic's overflow flag has to be read with the call's synchronisation (aov_drain)
+bool aov_enqueue(rptgpu_scene* h, const RptCamera& camera, const RptRenderParams& p, const rptdev::AovOut& ao) {
+  hipStream_t st = h->stream;
+  const KernelTable* kt = table_for(p.precision_mode, h->ext_shapes);
+  // the route, chosen like a render's: a group with tree children is only walked by the per-tree kernels
+  const bool wavefront = (p.flags & RPT_FLAG_WAVEFRONT) || h->tree_kids ? true
+                         : (p.flags & RPT_FLAG_PERSISTENT)             ? false
+                                                                       : h->has_deep;
+  h->dscene.force_general = (p.flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
+  if (h->npix) {
+    rptdev::Frame fr{};
+    fr.width = p.width; fr.height = p.height; fr.npix = h->npix; fr.pixels = h->pixels.p;
+    fr.seed = p.seed; fr.sample_base = p.sample_index_base;
+    const rptdev::Camera cam = make_camera(camera);
+    if (wavefront) aov_wavefront(h, kt, p, fr, cam, ao);
+    else kt->aov(st, h->dscene, fr, cam, ao, p.iterations);
+  }
+  HIP_TRY(hipGetLastError());
+  return wavefront && h->has_deep && h->gen_overflow.p;
+}
+
+// the call's one synchronisation; rpt_tree_generic's flag rides with it, as in render_impl
+int aov_drain(rptgpu_scene* h, bool read_overflow) {
+  hipStream_t st = h->stream;
+  uint32_t gen_overflow = 0;
+  if (read_overflow) HIP_TRY(hipMemcpyAsync(&gen_overflow, h->gen_overflow.p, sizeof gen_overflow, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (gen_overflow) {
+    (void)hipMemsetAsync(h->gen_overflow.p, 0, sizeof(uint32_t), st);
+    return fail(h, RPTGPU_E_TREE_TOO_DEEP, "rpt_tree_generic: the traversal outgrew the stack sized for this scene (internal error)");
+  }
+  return RPTGPU_OK;
+}
+
+} // namespace rptapi
+
 extern "C" int rptgpu_render_aov(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams* p, const RptAovBuffers* out) {
   // (the buffers first: a bad RptAovBuffers is refused whatever else is wrong, also without a handle or a device)
   if (const char* why = bad_aov(out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
@@ -129,38 +170,17 @@ extern "C" int rptgpu_render_aov(rptgpu_scene* h, const RptCamera* camera, const
     HIP_TRY(hipSetDevice(h->device));
     (void)hipGetLastError(); // (as render_impl: the checks below speak about this call's launches)
     hipStream_t st = h->stream;
-    const KernelTable* kt = table_for(p->precision_mode, h->ext_shapes);
     ensure_partition(h, *p);
     const uint64_t n = (uint64_t)p->width * p->height;
-    const rptdev::AovOut ao = device_arrays(h, n, out->channels);
-    // the route, chosen like a render's: a group with tree children is only walked by the per-tree kernels
-    const bool wavefront = (p->flags & RPT_FLAG_WAVEFRONT) || h->tree_kids ? true
-                           : (p->flags & RPT_FLAG_PERSISTENT)             ? false
-                                                                          : h->has_deep;
-    h->dscene.force_general = (p->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
-    if (h->npix) {
-      rptdev::Frame fr{};
-      fr.width = p->width; fr.height = p->height; fr.npix = h->npix; fr.pixels = h->pixels.p;
-      fr.seed = p->seed; fr.sample_base = p->sample_index_base;
-      const rptdev::Camera cam = make_camera(*camera);
-      if (wavefront) aov_wavefront(h, kt, *p, fr, cam, ao);
-      else kt->aov(st, h->dscene, fr, cam, ao, p->iterations);
-    }
-    HIP_TRY(hipGetLastError());
+    const rptdev::AovOut ao = aov_arrays(h->aov_out, st, n, out->channels);
+    const bool read_overflow = aov_enqueue(h, *camera, *p, ao);
     HIP_TRY(hipMemcpyAsync(out->hits, ao.hits, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     if (ao.depth) HIP_TRY(hipMemcpyAsync(out->depth, ao.depth, n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (ao.normal) HIP_TRY(hipMemcpyAsync(out->normal, ao.normal, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (ao.albedo) HIP_TRY(hipMemcpyAsync(out->albedo, ao.albedo, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (ao.position) HIP_TRY(hipMemcpyAsync(out->position, ao.position, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (ao.object) HIP_TRY(hipMemcpyAsync(out->object, ao.object, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    uint32_t gen_overflow = 0; // rpt_tree_generic's flag rides with the call's one synchronisation, as in render_impl
-    if (wavefront && h->has_deep && h->gen_overflow.p)
-      HIP_TRY(hipMemcpyAsync(&gen_overflow, h->gen_overflow.p, sizeof gen_overflow, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (gen_overflow) {
-      (void)hipMemsetAsync(h->gen_overflow.p, 0, sizeof(uint32_t), st);
-      return fail(h, RPTGPU_E_TREE_TOO_DEEP, "rpt_tree_generic: the traversal outgrew the stack sized for this scene (internal error)");
-    }
+    if (int rc = aov_drain(h, read_overflow)) return rc;
   } catch (const HipError& e) {
     return hip_fail(h, e);
   } catch (const std::bad_alloc&) {

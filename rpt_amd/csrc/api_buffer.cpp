@@ -1,5 +1,5 @@
 // api_buffer.cpp — the device-resident Buffer (buffer.rs:9-93 on the device: add_samples, add_sample by adaptive rounds,
-// image, variance; see api_internal.h)
+// image, variance; see api_internal.h), the first-hit features it can hold and the filter they guide
 #include "api_internal.h"
 
 // ------------------------------------------------------------------ device-resident Buffer
@@ -22,6 +22,14 @@ struct rptgpu_buffer {
   uint32_t n_active = 0;
   bool listed = false;  // active[cur] has been made (by the first adaptive round)
   bool retired = false; // some pixel has retired: a full-frame batch would break the prefix property
+  // rptgpu_buffer_features: the sums rptgpu_render_aov would return (depth, normal, albedo, position; hits), kept here
+  DevBuf<double> feat_arrays;
+  rptdev::AovOut feat{};
+  bool has_features = false;
+  // rptgpu_buffer_denoise's working set: 18 f64 columns of width*height (colour + variance twice, normal, position,
+  // albedo, depth), the hit flags, and the outputs before they are copied to the host
+  DevBuf<double> dn_cols, dn_linear;
+  DevBuf<uint8_t> dn_hit, dn_rgb8;
 };
 
 namespace {
@@ -63,6 +71,16 @@ const char* bad_adaptive(const RptAdaptive* a) {
   if (a->min_batches < 2) return "RptAdaptive: min_batches < 2";
   if (!(std::isfinite(a->abs_tol) && a->abs_tol >= 0.0) || !(std::isfinite(a->rel_tol) && a->rel_tol >= 0.0))
     return "RptAdaptive: abs_tol and rel_tol must be finite and >= 0";
+  return nullptr;
+}
+constexpr uint32_t FEATURE_CHANNELS = RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION;
+// what is wrong with an RptDenoise (nullptr: nothing)
+const char* bad_denoise(const RptDenoise* d) {
+  if (!d) return "null RptDenoise";
+  if (d->struct_size != sizeof(RptDenoise)) return "RptDenoise: struct_size is not sizeof(RptDenoise)";
+  if (d->levels < 1 || d->levels > 8) return "RptDenoise: levels outside 1..8";
+  for (double s : {d->sigma_color, d->sigma_normal, d->sigma_depth, d->sigma_albedo})
+    if (!(std::isfinite(s) && s > 0.0)) return "RptDenoise: every sigma must be finite and > 0";
   return nullptr;
 }
 } // namespace
@@ -108,6 +126,7 @@ void rptgpu_buffer_destroy(rptgpu_buffer* b) {
   b->total.release(); b->thr.release(); b->pix_var.release(); b->batch_ptrs.release(); b->image.release();
   b->counts.release(); b->mean.release(); b->m2.release(); b->active[0].release(); b->active[1].release();
   b->block_cnt.release(); b->active_n.release(); b->keep.release(); b->packed.release();
+  b->feat_arrays.release(); b->dn_cols.release(); b->dn_linear.release(); b->dn_hit.release(); b->dn_rgb8.release();
   delete b;
 }
 
@@ -294,6 +313,107 @@ int rptgpu_buffer_variance(rptgpu_buffer* b, double* out_variance) {
 int rptgpu_buffer_num_batches(const rptgpu_buffer* b, uint32_t* out) {
   if (!b || !out) return RPTGPU_E_INVALID_ARGUMENT;
   *out = (uint32_t)b->batches.size();
+  return RPTGPU_OK;
+}
+
+int rptgpu_buffer_features(rptgpu_buffer* b, const RptCamera* camera, const RptRenderParams* params) {
+  rptgpu_scene* h = b ? b->h : nullptr;
+  if (!b) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null buffer");
+  if (const char* why = bad_aov_params(params)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (!camera) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null camera");
+  if (params->width != b->width || params->height != b->height)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "Invalid sample dimension"); // buffer.rs:33-36
+  if (params->part_count > 1)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "part_count > 1: a buffer holds the features of the whole frame");
+  if (h->abandoned)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "an aborted batch's device work never drained on this handle: destroy it");
+  b->has_features = false; // (until the new ones are complete)
+  try {
+    HIP_TRY(hipSetDevice(h->device));
+    (void)hipGetLastError();
+    ensure_partition(h, *params);
+    b->feat = aov_arrays(b->feat_arrays, h->stream, (uint64_t)b->width * b->height, FEATURE_CHANNELS);
+    const bool read_overflow = aov_enqueue(h, *camera, *params, b->feat);
+    if (int rc = aov_drain(h, read_overflow)) return rc;
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  } catch (const std::bad_alloc&) {
+    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
+  } catch (...) {
+    return fail(h, RPTGPU_E_HIP, "unexpected exception");
+  }
+  b->has_features = true;
+  return RPTGPU_OK;
+}
+
+int rptgpu_buffer_feature_sums(const rptgpu_buffer* b, const RptAovBuffers* out) {
+  rptgpu_scene* h = b ? b->h : nullptr;
+  if (const char* why = bad_aov(out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (out->channels & RPT_AOV_OBJECT)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "RptAovBuffers: RPT_AOV_OBJECT is named, but a buffer does not hold `object`");
+  if (!b) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null buffer");
+  if (!b->has_features) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "the buffer holds no features (rptgpu_buffer_features)");
+  REFUSE_IF_ABANDONED(h);
+  try {
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = h->stream;
+    const uint64_t n = (uint64_t)b->width * b->height;
+    const rptdev::AovOut& f = b->feat;
+    HIP_TRY(hipMemcpyAsync(out->hits, f.hits, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (out->channels & RPT_AOV_DEPTH) HIP_TRY(hipMemcpyAsync(out->depth, f.depth, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (out->channels & RPT_AOV_NORMAL) HIP_TRY(hipMemcpyAsync(out->normal, f.normal, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (out->channels & RPT_AOV_ALBEDO) HIP_TRY(hipMemcpyAsync(out->albedo, f.albedo, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (out->channels & RPT_AOV_POSITION) HIP_TRY(hipMemcpyAsync(out->position, f.position, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  }
+  return RPTGPU_OK;
+}
+
+int rptgpu_buffer_denoise(rptgpu_buffer* b, const RptDenoise* d, double* out_linear, uint8_t* out_rgb8) {
+  rptgpu_scene* h = b ? b->h : nullptr;
+  if (const char* why = bad_denoise(d)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (!b) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null buffer");
+  if (!out_linear && !out_rgb8) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "out_linear and out_rgb8 are both NULL");
+  if (!b->has_features) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "the buffer holds no features (rptgpu_buffer_features)");
+  // n_p of every pixel is min(batches, the count it retired with), and a pixel only retires with n_p >= min_batches >= 2
+  if (b->batches.size() < 2)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "a pixel holds fewer than two batches: there is no variance of one batch");
+  REFUSE_IF_ABANDONED(h);
+  try {
+    HIP_TRY(hipSetDevice(h->device));
+    (void)hipGetLastError();
+    hipStream_t st = h->stream;
+    const KernelTable* kt = table_for(RPT_PRECISION_F64_STRICT);
+    const uint64_t n = (uint64_t)b->width * b->height;
+    b->dn_cols.alloc(18 * n);
+    b->dn_hit.alloc(n);
+    if (out_linear) b->dn_linear.alloc(3 * n);
+    if (out_rgb8) b->dn_rgb8.alloc(3 * n);
+    double* col = b->dn_cols.p;
+    double *c[2] = {col, col + 4 * n}, *v[2] = {col + 3 * n, col + 7 * n};
+    double *g_normal = col + 8 * n, *g_position = col + 11 * n, *g_albedo = col + 14 * n, *g_depth = col + 17 * n;
+    kt->denoise_prepare(st, b->total.p, b->counts.p, b->m2.p, b->feat, b->width, b->height, n, c[0], v[0], g_normal, g_position,
+                        g_albedo, g_depth, b->dn_hit.p);
+    rptdev::DenoiseGuide g{};
+    g.normal = g_normal; g.position = g_position; g.albedo = g_albedo; g.depth = g_depth; g.hit = b->dn_hit.p;
+    g.stride = n; g.width = b->width; g.height = b->height;
+    rptdev::DenoiseSigmas sg{};
+    sg.color2 = d->sigma_color * d->sigma_color; sg.normal = d->sigma_normal; sg.depth = d->sigma_depth;
+    sg.albedo2 = d->sigma_albedo * d->sigma_albedo;
+    int cur = 0;
+    for (uint32_t l = 0; l < d->levels; l++, cur ^= 1) kt->denoise_level(st, g, c[cur], v[cur], c[cur ^ 1], v[cur ^ 1], 1u << l, sg);
+    kt->denoise_finish(st, c[cur], n, n, b->thr.p, out_linear ? b->dn_linear.p : nullptr, out_rgb8 ? b->dn_rgb8.p : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (out_linear) HIP_TRY(hipMemcpyAsync(out_linear, b->dn_linear.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, b->dn_rgb8.p, 3 * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  } catch (...) {
+    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
+  }
   return RPTGPU_OK;
 }
 

@@ -7,7 +7,8 @@
 //   api_comm.cpp     communicator, rptgpu_render_batch_reduce (the library-owned exchange and its failure paths),
 //                    rptgpu_render_batch_emulate_ranks
 //   api_buffer.cpp   the device-resident Buffer
-//   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, route choice, pass loop)
+//   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, route choice, pass loop); its device
+//                    half also fills the features a Buffer holds for rptgpu_buffer_denoise
 // No compute happens on the host; if there is no HIP device every compute entry point returns RPTGPU_E_NO_DEVICE (there is
 // no CPU fallback by design).
 #pragma once
@@ -260,6 +261,15 @@ int64_t free_memory();
 int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams* p, void* d_out, bool out_f32,
                 double* host_out, hipStream_t user_stream, bool packed = false, const uint32_t* d_list = nullptr,
                 uint32_t n_list = 0);
+
+// api_aov.cpp: the checks and the device half of rptgpu_render_aov, shared with rptgpu_buffer_features (api_buffer.cpp)
+const char* bad_aov(const RptAovBuffers* o);
+const char* bad_aov_params(const RptRenderParams* p);
+// the arrays of `channels` for n pixels inside `arrays` (grown when too small), zeroed on st (object: -1)
+rptdev::AovOut aov_arrays(DevBuf<double>& arrays, hipStream_t st, uint64_t n, uint32_t channels);
+// the call's route and kernels into `ao` (after ensure_partition); -> aov_drain's read_overflow
+bool aov_enqueue(rptgpu_scene* h, const RptCamera& camera, const RptRenderParams& p, const rptdev::AovOut& ao);
+int aov_drain(rptgpu_scene* h, bool read_overflow);
 
 // A handle whose aborted batch never drained (rptgpu_render_batch_reduce, drain_after_abort): the abandoned stream's
 // kernels may still read and write the workspace, the frame buffers and events, so every call that would enqueue work

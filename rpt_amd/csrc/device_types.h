@@ -210,4 +210,23 @@ struct AovOut {
   uint32_t channels;
 };
 
+// rptgpu_buffer_denoise's working set (kernels/denoise.inc): f64 COLUMNS of `stride` elements indexed by pixel, so that
+// the 64 lanes of a wave (64 consecutive x of one row) read a tap's value as one contiguous segment at any tap spacing.
+// Constant over the levels: the means of the held features and the hit flag.  Per level: colour and variance in, out.
+struct DenoiseGuide {
+  const double* normal;   // [3][stride] N = normal / hits
+  const double* position; // [3][stride] P = position / hits
+  const double* albedo;   // [3][stride] A = albedo / hits
+  const double* depth;    // [stride]    Z = depth / hits
+  const uint8_t* hit;     // [stride]    hits > 0
+  uint64_t stride;
+  uint32_t width, height;
+};
+struct DenoiseSigmas {
+  double color2;  // sigma_color * sigma_color
+  double normal;  // sigma_normal
+  double depth;   // sigma_depth
+  double albedo2; // sigma_albedo * sigma_albedo
+};
+
 } // namespace rptdev

@@ -214,6 +214,17 @@ struct KernelTable {
               uint32_t iterations);
   void (*aov_fold)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::PathState&, const rptdev::AovOut&,
                    uint32_t spp, bool first);
+  // the device Buffer's denoising filter (kernels/denoise.inc; the contract: include/rpt_gpu.h).  prepare: the buffer's
+  // means, prefiltered variance and the means of its held features as columns of `stride` elements.  level: one à-trous
+  // pass at tap spacing `step` from (c_in, v_in) into (c_out, v_out).  finish: the colour columns as [pixel][3] f64 and /
+  // or as bytes through the buffer's thresholds (either output may be null)
+  void (*denoise_prepare)(hipStream_t, const double* total, const uint32_t* counts, const double* m2, const rptdev::AovOut& feat,
+                          uint32_t w, uint32_t h, uint64_t stride, double* c_out, double* v_out, double* g_normal,
+                          double* g_position, double* g_albedo, double* g_depth, uint8_t* g_hit);
+  void (*denoise_level)(hipStream_t, const rptdev::DenoiseGuide&, const double* c_in, const double* v_in, double* c_out,
+                        double* v_out, uint32_t step, const rptdev::DenoiseSigmas&);
+  void (*denoise_finish)(hipStream_t, const double* c_in, uint64_t stride, uint64_t npix, const double* thr, double* out_linear,
+                         uint8_t* out_rgb8);
 };
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)

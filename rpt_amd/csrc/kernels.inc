@@ -19,6 +19,7 @@
 //                  walks trees inside trees to any depth —, rpt_rays_objects, rpt_shadow_sum)
 //   buffer.inc     device-resident Buffer (buffer.rs)
 //   aov.inc        first-hit feature buffers: rpt_aov (fused) and rpt_aov_fold (behind the per-tree query), DESIGN.md §11
+//   denoise.inc    the device Buffer's feature-guided à-trous filter (rpt_denoise_prepare / _level / _finish), DESIGN.md §12
 //   launch.inc     explicit instantiations, host-side launchers, the KernelTable the api_*.cpp files call through
 //
 // Wave64 throughout (gfx950): queue appends and work fetches use one 64-bit ballot + one atomic per wave.
@@ -83,6 +84,7 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/paths.inc"
 #include "kernels/buffer.inc"
 #include "kernels/aov.inc"
+#include "kernels/denoise.inc"
 #include "kernels/launch.inc"
 
 } // namespace RPT_NS

@@ -274,6 +274,23 @@ void launch_aov_fold(hipStream_t st, const Scene& sc, const Frame& fr, const Pat
   hipLaunchKernelGGL(rpt_aov_fold, grid_for(fr.npix), dim3(256), 0, st, sc, fr, ps, out, spp, first ? 1 : 0);
 }
 
+// blocks of 64 x 4 pixels: a wave is 64 consecutive x of one row (kernels/denoise.inc)
+static inline dim3 grid_rows(uint32_t w, uint32_t h) { return dim3((w + 63u) / 64u, (h + 3u) / 4u); }
+void launch_denoise_prepare(hipStream_t st, const double* total, const uint32_t* counts, const double* m2, const AovOut& feat,
+                            uint32_t w, uint32_t h, uint64_t stride, double* c_out, double* v_out, double* g_normal,
+                            double* g_position, double* g_albedo, double* g_depth, uint8_t* g_hit) {
+  hipLaunchKernelGGL(rpt_denoise_prepare, grid_rows(w, h), dim3(64, 4), 0, st, total, counts, m2, feat, w, h, stride, c_out, v_out,
+                     g_normal, g_position, g_albedo, g_depth, g_hit);
+}
+void launch_denoise_level(hipStream_t st, const DenoiseGuide& g, const double* c_in, const double* v_in, double* c_out,
+                          double* v_out, uint32_t step, const DenoiseSigmas& sg) {
+  hipLaunchKernelGGL(rpt_denoise_level, grid_rows(g.width, g.height), dim3(64, 4), 0, st, g, c_in, v_in, c_out, v_out, step, sg);
+}
+void launch_denoise_finish(hipStream_t st, const double* c_in, uint64_t stride, uint64_t npix, const double* thr,
+                           double* out_linear, uint8_t* out_rgb8) {
+  hipLaunchKernelGGL(rpt_denoise_finish, grid_for(npix), dim3(256), 0, st, c_in, stride, npix, thr, out_linear, out_rgb8);
+}
+
 // debug builds with -DRPT_PROF: the per-phase table of kernels/prof.inc accumulated so far (and reset):
 // out[0] wave cycles, [1] lane cycles, [2] wave iterations, [3] lane iterations, PROF_SLOTS slots each
 bool read_prof(unsigned long long out[4][29]) {
@@ -293,5 +310,6 @@ const KernelTable TABLE = {launch_raygen, launch_extend, launch_extend_rays, lau
                            launch_shadow_rays, launch_resolve, launch_finish, launch_scatter_f32, launch_eval_math,
                            paths_max_blocks_per_cu, launch_paths, launch_sum_samples, launch_query, sort_temp_bytes, launch_shadow_sum,
                            launch_buffer_accumulate, launch_buffer_retire, launch_buffer_image, launch_buffer_variance,
-                           read_prof, launch_path_reorder, launch_aov, launch_aov_fold};
+                           read_prof, launch_path_reorder, launch_aov, launch_aov_fold,
+                           launch_denoise_prepare, launch_denoise_level, launch_denoise_finish};
 #endif // !__HIP_DEVICE_COMPILE__

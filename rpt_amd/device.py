@@ -323,3 +323,43 @@ class DeviceBuffer:
         _abi.check(self.gpu.lib.rptgpu_buffer_totals(self.handle, out.ctypes.data_as(C.POINTER(C.c_double))),
                    self.gpu.handle)
         return out
+
+    # ---- feature-guided denoising (rptgpu_buffer_features / _denoise)
+    def features(self, camera, params):
+        """The first-hit features of (camera, params) — GpuScene.render_aov's depth, normal, albedo and position sums and
+        `hits` — computed into device arrays the buffer keeps (nothing comes to the host); they guide denoise().  A later
+        call replaces them."""
+        cam = camera.lower() if hasattr(camera, "lower") else camera
+        _abi.check(self.gpu.lib.rptgpu_buffer_features(self.handle, C.byref(cam), C.byref(params)), self.gpu.handle)
+
+    def feature_sums(self):
+        """The held features read back: GpuScene.render_aov's dict without `object`."""
+        h, w = self.height, self.width
+        arrays = {"hits": np.zeros((h, w), dtype=np.uint32), "depth": np.zeros((h, w)), "normal": np.zeros((h, w, 3)),
+                  "albedo": np.zeros((h, w, 3)), "position": np.zeros((h, w, 3))}
+        b = _abi.RptAovBuffers()
+        b.struct_size = C.sizeof(_abi.RptAovBuffers)
+        b.channels = _abi.RPT_AOV_DEPTH | _abi.RPT_AOV_NORMAL | _abi.RPT_AOV_ALBEDO | _abi.RPT_AOV_POSITION
+        for name, a in arrays.items():
+            setattr(b, name, a.ctypes.data_as(dict(_abi.RptAovBuffers._fields_)[name]))
+        _abi.check(self.gpu.lib.rptgpu_buffer_feature_sums(self.handle, C.byref(b)), self.gpu.handle)
+        return arrays
+
+    def _denoise(self, want_linear, want_bytes, levels, sigma_color, sigma_normal, sigma_depth, sigma_albedo):
+        d = _abi.RptDenoise(C.sizeof(_abi.RptDenoise), int(levels), float(sigma_color), float(sigma_normal),
+                            float(sigma_depth), float(sigma_albedo))
+        lin = np.empty((self.height, self.width, 3), dtype=np.float64) if want_linear else None
+        rgb = np.empty((self.height, self.width, 3), dtype=np.uint8) if want_bytes else None
+        _abi.check(self.gpu.lib.rptgpu_buffer_denoise(
+            self.handle, C.byref(d), lin.ctypes.data_as(C.POINTER(C.c_double)) if want_linear else None,
+            rgb.ctypes.data_as(C.POINTER(C.c_uint8)) if want_bytes else None), self.gpu.handle)
+        return lin, rgb
+
+    def denoise(self, levels=3, sigma_color=2.0, sigma_normal=0.1, sigma_depth=0.01, sigma_albedo=0.1):
+        """The buffer's linear mean through the edge-avoiding a-trous filter of include/rpt_gpu.h, guided by the held
+        features and the per-pixel variance -> (H, W, 3) float64.  The buffer itself is not changed."""
+        return self._denoise(True, False, levels, sigma_color, sigma_normal, sigma_depth, sigma_albedo)[0]
+
+    def denoised_image(self, levels=3, sigma_color=2.0, sigma_normal=0.1, sigma_depth=0.01, sigma_albedo=0.1):
+        """color_bytes of denoise(...) -> (H, W, 3) uint8."""
+        return self._denoise(False, True, levels, sigma_color, sigma_normal, sigma_depth, sigma_albedo)[1]

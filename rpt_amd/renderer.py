@@ -127,6 +127,29 @@ class Renderer:
         finally:
             buffer.close()
 
+    def denoised_render(self, callback_interval, feature_samples=4, **filter):
+        """iterative_render(on_device=True) in batches of callback_interval samples — at least two, else ValueError: one
+        batch has no variance — then the first-hit features of samples 0 .. feature_samples-1 and the feature-guided
+        filter (DeviceBuffer.denoise's keywords in `filter`), all on the device.  -> the (H, W, 3) uint8 image."""
+        if int(callback_interval) < 1 or self._num_samples <= int(callback_interval):
+            raise ValueError("denoised_render: num_samples must exceed callback_interval (at least two batches)")
+        buffer = DeviceBuffer(self.gpu_scene(), self._width, self._height, self._filter)
+        try:
+            iteration = 0
+            self._samples_done = 0
+            while iteration < self._num_samples:
+                steps = min(self._num_samples - iteration, int(callback_interval))
+                params = make_params(self._width, self._height, self._max_bounces, steps, self._exposure_value,
+                                     self._seed, self._samples_done, precision=self._precision)
+                buffer.sample(self.camera, params)
+                self._samples_done += steps
+                iteration += steps
+            buffer.features(self.camera, make_params(self._width, self._height, self._max_bounces, int(feature_samples),
+                                                     self._exposure_value, self._seed, 0, precision=self._precision))
+            return buffer.denoised_image(**filter)
+        finally:
+            buffer.close()
+
     def render_aovs(self, channels=_abi.RPT_AOV_ALL):
         """The first-hit feature buffers of this renderer's frame (width, height, seed, num_samples camera rays per pixel:
         the rays render() starts its paths with) as MEANS over each pixel's hits: GpuScene.render_aov's dict with `depth`,

@@ -283,6 +283,18 @@ pub mod ffi {
         pub object: *mut i32,
     }
 
+    /// `RptDenoise` (the parameters of `rptgpu_buffer_denoise`; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptDenoise {
+        pub struct_size: u32,
+        pub levels: u32,
+        pub sigma_color: f64,
+        pub sigma_normal: f64,
+        pub sigma_depth: f64,
+        pub sigma_albedo: f64,
+    }
+
     /// opaque `rptgpu_scene`
     #[repr(C)]
     pub struct rptgpu_scene {
@@ -329,6 +341,9 @@ pub mod ffi {
         pub fn rptgpu_buffer_sample_counts(b: *const rptgpu_buffer, out_counts: *mut u32) -> c_int;
         pub fn rptgpu_buffer_totals(b: *const rptgpu_buffer, out_totals: *mut f64) -> c_int;
         pub fn rptgpu_render_aov(h: *mut rptgpu_scene, camera: *const RptCamera, params: *const RptRenderParams, out: *const RptAovBuffers) -> c_int;
+        pub fn rptgpu_buffer_features(b: *mut rptgpu_buffer, camera: *const RptCamera, params: *const RptRenderParams) -> c_int;
+        pub fn rptgpu_buffer_feature_sums(b: *const rptgpu_buffer, out: *const RptAovBuffers) -> c_int;
+        pub fn rptgpu_buffer_denoise(b: *mut rptgpu_buffer, d: *const RptDenoise, out_linear: *mut f64, out_rgb8: *mut u8) -> c_int;
         pub fn rptgpu_get_stats(h: *const rptgpu_scene, out: *mut RptStats) -> c_int;
         pub fn rptgpu_reset_stats(h: *mut rptgpu_scene) -> c_int;
         pub fn rptgpu_kernel_name(k: c_int) -> *const c_char;
@@ -689,6 +704,7 @@ mod layout_tests {
         assert_eq!(size_of::<RptParticleSystem>(), 16);
         assert_eq!(size_of::<RptAdaptive>(), 24);
         assert_eq!(size_of::<RptAovBuffers>(), 56);
+        assert_eq!(size_of::<RptDenoise>(), 40);
     }
 
     #[test]
