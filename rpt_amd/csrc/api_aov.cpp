@@ -1,10 +1,10 @@
 // api_aov.cpp — rptgpu_render_aov: first-hit feature buffers (include/rpt_gpu.h; see api_internal.h).
 // Argument checks, the route (one fused kernel, or raygen + closest-hit query + fold in passes), the device arrays of the
 // requested channels, one copy per channel and one synchronisation.  The kernels: kernels/aov.inc.
-// The device half (aov_arrays, aov_enqueue, aov_drain) writes into arrays it is handed: rptgpu_render_aov hands it the
-// handle's own and copies them out, rptgpu_buffer_features (api_buffer.cpp) hands it arrays the buffer keeps.
+// The device half (aov_arrays, aov_enqueue, then drain_call) writes into arrays it is handed: rptgpu_render_aov hands it
+// the handle's own and copies them out (copy_aov_out), rptgpu_buffer_features (api_buffer.cpp) hands it arrays the buffer
+// keeps.
 #include "api_internal.h"
-#include "render_plan.h"
 
 namespace rptapi {
 
@@ -79,38 +79,19 @@ void aov_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams
   in.rec_ratio = 1.0; in.ratio = 1.0;
   const bool by_object = h->has_deep && (!(p.flags & RPT_FLAG_GENERAL_TRAVERSAL) || h->tree_kids);
   const bool generic_all = h->has_deep && (h->gen_all || h->dscene.force_general);
-  const uint32_t trace_blocks = (uint32_t)std::max(1, h->num_cus * 4);
   for (uint32_t s0 = 0; s0 < p.iterations;) {
     in.remaining = p.iterations - s0;
     in.free_bytes = in.target_paths ? -1 : free_memory();
     in.held_slots = h->ws_cap; in.held_cols = h->ws_rec_cols;
     in.fail_paths = h->ws_fail_paths;
-    rptplan::PassPlan pp = rptplan::plan_pass(in);
-    for (;;) {
-      const uint64_t np = rptplan::pass_slots(npix, pp);
-      try {
-        ensure_workspace(h, np, rptplan::pass_rec_cols(np, in.ratio));
-        if (generic_all) ensure_generic(h, true);
-        break;
-      } catch (const HipError& e) {
-        if (e.e != hipErrorOutOfMemory || pp.s_chunk == 1) throw;
-        (void)hipGetLastError();
-        release_workspace(h);
-        h->ws_fail_paths = rptplan::fail_paths_after_oom(h->ws_fail_paths, np);
-        pp = rptplan::shrink_after_oom(pp);
-      }
-    }
+    const rptplan::PassPlan pp = size_pass(h, in, npix, generic_all);
     const uint32_t n_paths = npix * pp.s_chunk;
     fr.sample_base = p.sample_index_base + s0;
     const rptdev::PathState ps = path_state(h);
-    if (h->has_deep) {
-      HIP_TRY(hipMemsetAsync(h->tq_ctr.p, 0, 16 * sizeof(uint32_t), st));
-      h->qtune.ctr_set = 0;
-    }
+    if (h->has_deep) reset_tree_counters(h);
     kt->raygen(st, fr, cam, ps, n_paths);
     if (by_object)
-      kt->query(st, h->dscene, ps, nullptr, n_paths, -1, nullptr, nullptr, h->obj_deep.data(), h->obj_tris.data(),
-                h->dscene.num_objects, h->tq.p, h->tq_ctr.p, trace_blocks, h->sort_rays ? &h->sort_bufs : nullptr, nullptr, &h->spill, &h->qtune);
+      query_closest(h, kt, ps, n_paths, nullptr);
     else
       kt->extend(st, h->dscene, ps, nullptr, n_paths);
     kt->aov_fold(st, h->dscene, fr, ps, ao, pp.s_chunk, s0 == 0);
@@ -122,14 +103,11 @@ void aov_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams
 } // namespace
 
 // The route and the kernels of one call into the zeroed arrays `ao`, enqueued on the handle's stream; -> whether
-// rpt_tree_generic's overflow flag has to be read with the call's synchronisation (aov_drain)
+// rpt_tree_generic's overflow flag has to be read with the call's synchronisation (drain_call)
 bool aov_enqueue(rptgpu_scene* h, const RptCamera& camera, const RptRenderParams& p, const rptdev::AovOut& ao) {
   hipStream_t st = h->stream;
   const KernelTable* kt = table_for(p.precision_mode, h->ext_shapes);
-  // the route, chosen like a render's: a group with tree children is only walked by the per-tree kernels
-  const bool wavefront = (p.flags & RPT_FLAG_WAVEFRONT) || h->tree_kids ? true
-                         : (p.flags & RPT_FLAG_PERSISTENT)             ? false
-                                                                       : h->has_deep;
+  const bool wavefront = use_wavefront(h, p.flags, h->has_deep);
   h->dscene.force_general = (p.flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
   if (h->npix) {
     rptdev::Frame fr{};
@@ -143,17 +121,13 @@ bool aov_enqueue(rptgpu_scene* h, const RptCamera& camera, const RptRenderParams
   return wavefront && h->has_deep && h->gen_overflow.p;
 }
 
-// the call's one synchronisation; rpt_tree_generic's flag rides with it, as in render_impl
-int aov_drain(rptgpu_scene* h, bool read_overflow) {
-  hipStream_t st = h->stream;
-  uint32_t gen_overflow = 0;
-  if (read_overflow) HIP_TRY(hipMemcpyAsync(&gen_overflow, h->gen_overflow.p, sizeof gen_overflow, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (gen_overflow) {
-    (void)hipMemsetAsync(h->gen_overflow.p, 0, sizeof(uint32_t), st);
-    return fail(h, RPTGPU_E_TREE_TOO_DEEP, "rpt_tree_generic: the traversal outgrew the stack sized for this scene (internal error)");
-  }
-  return RPTGPU_OK;
+void copy_aov_out(const rptdev::AovOut& src, uint32_t channels, const RptAovBuffers& dst, uint64_t n, hipStream_t st) {
+  HIP_TRY(hipMemcpyAsync(dst.hits, src.hits, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  if (channels & RPT_AOV_DEPTH) HIP_TRY(hipMemcpyAsync(dst.depth, src.depth, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (channels & RPT_AOV_NORMAL) HIP_TRY(hipMemcpyAsync(dst.normal, src.normal, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (channels & RPT_AOV_ALBEDO) HIP_TRY(hipMemcpyAsync(dst.albedo, src.albedo, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (channels & RPT_AOV_POSITION) HIP_TRY(hipMemcpyAsync(dst.position, src.position, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (channels & RPT_AOV_OBJECT) HIP_TRY(hipMemcpyAsync(dst.object, src.object, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
 }
 
 } // namespace rptapi
@@ -166,27 +140,14 @@ extern "C" int rptgpu_render_aov(rptgpu_scene* h, const RptCamera* camera, const
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   if (h->abandoned)
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "an aborted batch's device work never drained on this handle: destroy it");
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  return guarded(h, h->device, [&]() -> int {
     (void)hipGetLastError(); // (as render_impl: the checks below speak about this call's launches)
     hipStream_t st = h->stream;
     ensure_partition(h, *p);
     const uint64_t n = (uint64_t)p->width * p->height;
     const rptdev::AovOut ao = aov_arrays(h->aov_out, st, n, out->channels);
     const bool read_overflow = aov_enqueue(h, *camera, *p, ao);
-    HIP_TRY(hipMemcpyAsync(out->hits, ao.hits, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (ao.depth) HIP_TRY(hipMemcpyAsync(out->depth, ao.depth, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (ao.normal) HIP_TRY(hipMemcpyAsync(out->normal, ao.normal, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (ao.albedo) HIP_TRY(hipMemcpyAsync(out->albedo, ao.albedo, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (ao.position) HIP_TRY(hipMemcpyAsync(out->position, ao.position, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (ao.object) HIP_TRY(hipMemcpyAsync(out->object, ao.object, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (int rc = aov_drain(h, read_overflow)) return rc;
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  } catch (const std::bad_alloc&) {
-    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  } catch (...) {
-    return fail(h, RPTGPU_E_HIP, "unexpected exception");
-  }
-  return RPTGPU_OK;
+    copy_aov_out(ao, out->channels, *out, n, st);
+    return drain_call(h, read_overflow);
+  });
 }

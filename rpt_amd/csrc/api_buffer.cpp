@@ -6,7 +6,7 @@
 struct rptgpu_buffer {
   rptgpu_scene* h = nullptr;
   uint32_t width = 0, height = 0, radius = 0;
-  std::vector<double*> batches; // one W*H*3 frame per batch, on the device (zero where a round did not sample a pixel)
+  std::vector<DevBuf<double>> batches; // one W*H*3 frame per batch, on the device (zero where a round did not sample a pixel)
   DevBuf<double> total, thr, pix_var;
   DevBuf<const double*> batch_ptrs;
   DevBuf<uint8_t> image;
@@ -30,6 +30,11 @@ struct rptgpu_buffer {
   // albedo, depth), the hit flags, and the outputs before they are copied to the host
   DevBuf<double> dn_cols, dn_linear;
   DevBuf<uint8_t> dn_hit, dn_rgb8;
+
+  ~rptgpu_buffer() {
+    if (h) (void)hipSetDevice(h->device);
+    // every DevBuf frees itself (after this body, on the handle's device)
+  }
 };
 
 namespace {
@@ -93,14 +98,10 @@ int rptgpu_buffer_create(rptgpu_scene* h, uint32_t width, uint32_t height, uint3
   rptgpu_buffer* b = new (std::nothrow) rptgpu_buffer();
   if (!b) return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
   b->h = h; b->width = width; b->height = height; b->radius = filter_radius;
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  const int rc = guarded(h, h->device, [&]() -> int {
     bool clean = true;
     std::vector<double> thr = byte_thresholds(clean);
-    if (!clean) {
-      delete b;
-      return fail(h, RPTGPU_E_INVALID_ARGUMENT, "host pow() is not monotone around a u8 threshold");
-    }
+    if (!clean) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "host pow() is not monotone around a u8 threshold");
     b->thr.upload(thr, h->stream);
     uint64_t npix = (uint64_t)width * height, n = npix * 3;
     b->total.alloc(n);
@@ -110,25 +111,17 @@ int rptgpu_buffer_create(rptgpu_scene* h, uint32_t width, uint32_t height, uint3
     HIP_TRY(hipMemsetAsync(b->mean.p, 0, n * sizeof(double), h->stream));
     HIP_TRY(hipMemsetAsync(b->m2.p, 0, npix * sizeof(double), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-  } catch (const HipError& e) {
-    int code = hip_fail(h, e);
+    return RPTGPU_OK;
+  });
+  if (rc != RPTGPU_OK) {
     delete b;
-    return code;
+    return rc;
   }
   *out = b;
   return RPTGPU_OK;
 }
 
-void rptgpu_buffer_destroy(rptgpu_buffer* b) {
-  if (!b) return;
-  (void)hipSetDevice(b->h->device);
-  for (double* p : b->batches) (void)hipFree(p);
-  b->total.release(); b->thr.release(); b->pix_var.release(); b->batch_ptrs.release(); b->image.release();
-  b->counts.release(); b->mean.release(); b->m2.release(); b->active[0].release(); b->active[1].release();
-  b->block_cnt.release(); b->active_n.release(); b->keep.release(); b->packed.release();
-  b->feat_arrays.release(); b->dn_cols.release(); b->dn_linear.release(); b->dn_hit.release(); b->dn_rgb8.release();
-  delete b;
-}
+void rptgpu_buffer_destroy(rptgpu_buffer* b) { delete b; }
 
 int rptgpu_buffer_sample(rptgpu_buffer* b, const RptCamera* camera, const RptRenderParams* params) {
   if (!b || !camera || !params) return RPTGPU_E_INVALID_ARGUMENT;
@@ -138,26 +131,21 @@ int rptgpu_buffer_sample(rptgpu_buffer* b, const RptCamera* camera, const RptRen
   if (b->retired)
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "a pixel of this buffer has retired (rptgpu_buffer_sample_adaptive): a "
                                               "full-frame batch would give it a batch its earlier rounds skipped");
-  double* frame = nullptr;
-  uint64_t n = (uint64_t)b->width * b->height * 3;
-  if (hipSetDevice(h->device) != hipSuccess || hipMalloc((void**)&frame, n * sizeof(double)) != hipSuccess)
+  DevBuf<double> frame; // the batch's: the buffer's once it is accumulated
+  const uint64_t n = (uint64_t)b->width * b->height * 3;
+  if (hipSetDevice(h->device) != hipSuccess || hipMalloc((void**)&frame.p, n * sizeof(double)) != hipSuccess)
     return fail(h, RPTGPU_E_OUT_OF_MEMORY, "hipMalloc of a batch frame failed");
-  int rc = render_impl(h, camera, params, frame, false, nullptr, nullptr);
-  if (rc != RPTGPU_OK) {
-    (void)hipFree(frame);
-    return rc;
-  }
-  try {
-    table_for(RPT_PRECISION_F64_STRICT)->buffer_accumulate(h->stream, b->total.p, frame, nullptr, nullptr, b->width * b->height,
+  frame.n = n;
+  const int rc = render_impl(h, camera, params, frame.p, false, nullptr, nullptr);
+  if (rc != RPTGPU_OK) return rc;
+  return guarded(h, h->device, [&]() -> int {
+    table_for(RPT_PRECISION_F64_STRICT)->buffer_accumulate(h->stream, b->total.p, frame.p, nullptr, nullptr, b->width * b->height,
                                                            b->counts.p, b->mean.p, b->m2.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
-  } catch (const HipError& e) {
-    (void)hipFree(frame);
-    return hip_fail(h, e);
-  }
-  b->batches.push_back(frame);
-  return RPTGPU_OK;
+    b->batches.push_back(std::move(frame));
+    return RPTGPU_OK;
+  });
 }
 
 int rptgpu_buffer_sample_adaptive(rptgpu_buffer* b, const RptCamera* camera, const RptRenderParams* params,
@@ -174,8 +162,8 @@ int rptgpu_buffer_sample_adaptive(rptgpu_buffer* b, const RptCamera* camera, con
   const uint32_t npix = b->width * b->height;
   hipStream_t st = h->stream;
   const KernelTable* kt = table_for(RPT_PRECISION_F64_STRICT);
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  DevBuf<double> frame; // the round's, zero where it samples no pixel: the buffer's once it is accumulated
+  int rc = guarded(h, h->device, [&]() -> int {
     if (!b->listed) { // round 0: every pixel, in the 8x8-block order of a full-frame render
       b->active[0].upload(pixel_list(b->width, b->height, 32, 8, 0, 1), st);
       b->active[1].alloc(npix);
@@ -187,86 +175,66 @@ int rptgpu_buffer_sample_adaptive(rptgpu_buffer* b, const RptCamera* camera, con
       b->n_active = npix;
       b->listed = true;
     }
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  } catch (const std::bad_alloc&) {
-    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  }
+    if (b->n_active) {
+      b->packed.alloc((uint64_t)b->n_active * 3);
+      frame.alloc((uint64_t)npix * 3);
+      HIP_TRY(hipMemsetAsync(frame.p, 0, (uint64_t)npix * 3 * sizeof(double), st));
+    }
+    return RPTGPU_OK;
+  });
+  if (rc != RPTGPU_OK) return rc;
   if (b->n_active == 0) {
     *out_active = 0;
     return RPTGPU_OK;
   }
   const uint32_t n = b->n_active;
   const uint32_t* list = b->active[b->cur].p;
-  double* frame = nullptr;
-  const uint64_t frame_elems = (uint64_t)npix * 3;
-  try {
-    b->packed.alloc((uint64_t)n * 3);
-    HIP_TRY(hipMalloc((void**)&frame, frame_elems * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(frame, 0, frame_elems * sizeof(double), st));
-  } catch (const HipError& e) {
-    if (frame) (void)hipFree(frame);
-    return hip_fail(h, e);
-  }
-  int rc = render_impl(h, camera, params, b->packed.p, false, nullptr, nullptr, true, list, n);
-  if (rc != RPTGPU_OK) {
-    (void)hipFree(frame);
-    return rc;
-  }
-  uint32_t left = 0;
-  try {
-    kt->buffer_accumulate(st, b->total.p, frame, b->packed.p, list, n, b->counts.p, b->mean.p, b->m2.p);
+  rc = render_impl(h, camera, params, b->packed.p, false, nullptr, nullptr, true, list, n);
+  if (rc != RPTGPU_OK) return rc;
+  return guarded(h, h->device, [&]() -> int {
+    uint32_t left = 0;
+    kt->buffer_accumulate(st, b->total.p, frame.p, b->packed.p, list, n, b->counts.p, b->mean.p, b->m2.p);
     kt->buffer_retire(st, list, n, b->counts.p, b->mean.p, b->m2.p, a->min_batches, a->abs_tol, a->rel_tol, b->keep.p,
                       b->block_cnt.p, b->active[b->cur ^ 1].p, b->active_n.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&left, b->active_n.p, sizeof left, hipMemcpyDeviceToHost, st)); // plans the next round
     HIP_TRY(hipStreamSynchronize(st));
-  } catch (const HipError& e) {
-    (void)hipFree(frame);
-    return hip_fail(h, e);
-  }
-  b->batches.push_back(frame);
-  b->cur ^= 1;
-  b->n_active = left;
-  if (left < npix) b->retired = true;
-  *out_active = left;
-  return RPTGPU_OK;
+    b->batches.push_back(std::move(frame));
+    b->cur ^= 1;
+    b->n_active = left;
+    if (left < npix) b->retired = true;
+    *out_active = left;
+    return RPTGPU_OK;
+  });
 }
 
 int rptgpu_buffer_sample_counts(const rptgpu_buffer* b, uint32_t* out_counts) {
   if (!b || !out_counts) return RPTGPU_E_INVALID_ARGUMENT;
   rptgpu_scene* h = b->h;
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  return guarded(h, h->device, [&]() -> int {
     HIP_TRY(hipMemcpyAsync(out_counts, b->counts.p, (uint64_t)b->width * b->height * sizeof(uint32_t),
                            hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  }
-  return RPTGPU_OK;
+    return RPTGPU_OK;
+  });
 }
 
 int rptgpu_buffer_totals(const rptgpu_buffer* b, double* out_totals) {
   if (!b || !out_totals) return RPTGPU_E_INVALID_ARGUMENT;
   rptgpu_scene* h = b->h;
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  return guarded(h, h->device, [&]() -> int {
     HIP_TRY(hipMemcpyAsync(out_totals, b->total.p, (uint64_t)b->width * b->height * 3 * sizeof(double),
                            hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  }
-  return RPTGPU_OK;
+    return RPTGPU_OK;
+  });
 }
 
 int rptgpu_buffer_image(rptgpu_buffer* b, uint8_t* out_rgb8) {
   if (!b || !out_rgb8) return RPTGPU_E_INVALID_ARGUMENT;
   rptgpu_scene* h = b->h;
   if (b->batches.empty()) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "Pixel found with no samples"); // buffer.rs:89
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  return guarded(h, h->device, [&]() -> int {
     uint64_t n = (uint64_t)b->width * b->height * 3;
     b->image.alloc(n);
     table_for(RPT_PRECISION_F64_STRICT)->buffer_image(h->stream, b->total.p, b->counts.p, b->width, b->height, b->radius,
@@ -274,20 +242,18 @@ int rptgpu_buffer_image(rptgpu_buffer* b, uint8_t* out_rgb8) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_rgb8, b->image.p, n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  }
-  return RPTGPU_OK;
+    return RPTGPU_OK;
+  });
 }
 
 int rptgpu_buffer_variance(rptgpu_buffer* b, double* out_variance) {
   if (!b || !out_variance) return RPTGPU_E_INVALID_ARGUMENT;
   rptgpu_scene* h = b->h;
   if (b->batches.empty()) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "no samples");
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  return guarded(h, h->device, [&]() -> int {
     uint64_t npix = (uint64_t)b->width * b->height;
-    std::vector<const double*> ptrs(b->batches.begin(), b->batches.end());
+    std::vector<const double*> ptrs;
+    for (const DevBuf<double>& frame : b->batches) ptrs.push_back(frame.p);
     b->batch_ptrs.upload(ptrs, h->stream);
     b->pix_var.alloc(npix);
     table_for(RPT_PRECISION_F64_STRICT)->buffer_variance(h->stream, b->total.p, b->batch_ptrs.p, b->counts.p, npix,
@@ -302,12 +268,8 @@ int rptgpu_buffer_variance(rptgpu_buffer* b, double* out_variance) {
       count += 1.0;
     }
     *out_variance = variance / count;
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  } catch (...) {
-    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  }
-  return RPTGPU_OK;
+    return RPTGPU_OK;
+  });
 }
 
 int rptgpu_buffer_num_batches(const rptgpu_buffer* b, uint32_t* out) {
@@ -328,22 +290,15 @@ int rptgpu_buffer_features(rptgpu_buffer* b, const RptCamera* camera, const RptR
   if (h->abandoned)
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "an aborted batch's device work never drained on this handle: destroy it");
   b->has_features = false; // (until the new ones are complete)
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  return guarded(h, h->device, [&]() -> int {
     (void)hipGetLastError();
     ensure_partition(h, *params);
     b->feat = aov_arrays(b->feat_arrays, h->stream, (uint64_t)b->width * b->height, FEATURE_CHANNELS);
     const bool read_overflow = aov_enqueue(h, *camera, *params, b->feat);
-    if (int rc = aov_drain(h, read_overflow)) return rc;
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  } catch (const std::bad_alloc&) {
-    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  } catch (...) {
-    return fail(h, RPTGPU_E_HIP, "unexpected exception");
-  }
-  b->has_features = true;
-  return RPTGPU_OK;
+    if (int rc = drain_call(h, read_overflow)) return rc;
+    b->has_features = true;
+    return RPTGPU_OK;
+  });
 }
 
 int rptgpu_buffer_feature_sums(const rptgpu_buffer* b, const RptAovBuffers* out) {
@@ -354,21 +309,11 @@ int rptgpu_buffer_feature_sums(const rptgpu_buffer* b, const RptAovBuffers* out)
   if (!b) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null buffer");
   if (!b->has_features) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "the buffer holds no features (rptgpu_buffer_features)");
   REFUSE_IF_ABANDONED(h);
-  try {
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = h->stream;
-    const uint64_t n = (uint64_t)b->width * b->height;
-    const rptdev::AovOut& f = b->feat;
-    HIP_TRY(hipMemcpyAsync(out->hits, f.hits, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    if (out->channels & RPT_AOV_DEPTH) HIP_TRY(hipMemcpyAsync(out->depth, f.depth, n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out->channels & RPT_AOV_NORMAL) HIP_TRY(hipMemcpyAsync(out->normal, f.normal, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out->channels & RPT_AOV_ALBEDO) HIP_TRY(hipMemcpyAsync(out->albedo, f.albedo, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (out->channels & RPT_AOV_POSITION) HIP_TRY(hipMemcpyAsync(out->position, f.position, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  }
-  return RPTGPU_OK;
+  return guarded(h, h->device, [&]() -> int {
+    copy_aov_out(b->feat, out->channels, *out, (uint64_t)b->width * b->height, h->stream);
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return RPTGPU_OK;
+  });
 }
 
 int rptgpu_buffer_denoise(rptgpu_buffer* b, const RptDenoise* d, double* out_linear, uint8_t* out_rgb8) {
@@ -381,8 +326,7 @@ int rptgpu_buffer_denoise(rptgpu_buffer* b, const RptDenoise* d, double* out_lin
   if (b->batches.size() < 2)
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "a pixel holds fewer than two batches: there is no variance of one batch");
   REFUSE_IF_ABANDONED(h);
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  return guarded(h, h->device, [&]() -> int {
     (void)hipGetLastError();
     hipStream_t st = h->stream;
     const KernelTable* kt = table_for(RPT_PRECISION_F64_STRICT);
@@ -409,12 +353,8 @@ int rptgpu_buffer_denoise(rptgpu_buffer* b, const RptDenoise* d, double* out_lin
     if (out_linear) HIP_TRY(hipMemcpyAsync(out_linear, b->dn_linear.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (out_rgb8) HIP_TRY(hipMemcpyAsync(out_rgb8, b->dn_rgb8.p, 3 * n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  } catch (...) {
-    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  }
-  return RPTGPU_OK;
+    return RPTGPU_OK;
+  });
 }
 
 } // extern "C" (buffer)

@@ -1,13 +1,17 @@
 // api_internal.h — what the files behind the C ABI of include/rpt_gpu.h share: the handle, device buffers, the error
-// convention, the RCCL binding.  The ABI's implementation is split by concern (round 6; it was one 1 900-line api.cpp):
+// convention and the entry points' frame (guarded), the RCCL binding.  The ABI's implementation is split by concern
+// (round 6; it was one 1 900-line api.cpp):
 //   api_common.cpp   errors, the RCCL loader, kernel tables, version / strerror / stats
 //   api_scene.cpp    RptSceneOptions, rptgpu_scene_create[_opts] (flattening, routing, upload), the kd-tree entry points
 //   api_render.cpp   workspace, the wavefront loop and the persistent launch (render_impl), render_batch[_device],
-//                    rptgpu_closest_hit, rptgpu_eval_math; their launch and pass sizes come from render_plan.h
+//                    rptgpu_closest_hit, rptgpu_eval_math; their launch and pass sizes come from render_plan.h.  Also the
+//                    steps every driver of the wavefront kernels shares: the route (use_wavefront), a pass's size with
+//                    its out-of-memory shrink (size_pass), the per-tree queries (reset_tree_counters, query_closest,
+//                    query_visibility), the profiling event pairs, the end of a call (drain_call)
 //   api_comm.cpp     communicator, rptgpu_render_batch_reduce (the library-owned exchange and its failure paths),
 //                    rptgpu_render_batch_emulate_ranks
 //   api_buffer.cpp   the device-resident Buffer
-//   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, route choice, pass loop); its device
+//   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, pass loop, copy_aov_out); its device
 //                    half also fills the features a Buffer holds for rptgpu_buffer_denoise
 // No compute happens on the host; if there is no HIP device every compute entry point returns RPTGPU_E_NO_DEVICE (there is
 // no CPU fallback by design).
@@ -30,6 +34,7 @@
 #include "device_types.h"
 #include "host_scene.h"
 #include "kernels.h"
+#include "render_plan.h"
 
 namespace rptapi {
 
@@ -54,13 +59,22 @@ constexpr const char* rpt_basename(const char* path) {
     if (_e != hipSuccess) throw HipError{_e, #expr, __LINE__, rptapi::rpt_basename(__FILE__)}; \
   } while (0)
 
-// owning device allocation: released by the destructor, never copied
+// owning device allocation: released by the destructor, moved but never copied
 template <class T> struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
   DevBuf() = default;
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p; n = o.n;
+      o.p = nullptr; o.n = 0;
+    }
+    return *this;
+  }
   ~DevBuf() { release(); }
   void alloc(size_t count) {
     if (count <= n && p) return;
@@ -237,6 +251,21 @@ namespace rptapi {
 // the error convention: every entry point returns an int; the detail goes to the handle (or, without one, to the thread)
 int fail(rptgpu_scene* h, int code, const std::string& detail);
 int hip_fail(rptgpu_scene* h, const HipError& e);
+// The frame of an entry point that uses the device: select it, run the body (-> the call's code), and map what the body
+// throws to a code and a detail in this one place.  h may be null (the detail then goes to the thread).  Argument checks
+// that need no device stand in front of it.
+template <class Body> int guarded(rptgpu_scene* h, int device, Body&& body) {
+  try {
+    HIP_TRY(hipSetDevice(device));
+    return body();
+  } catch (const HipError& e) {
+    return hip_fail(h, e);
+  } catch (const std::bad_alloc&) {
+    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
+  } catch (...) {
+    return fail(h, RPTGPU_E_HIP, "unexpected exception");
+  }
+}
 // ext: the scene contains a shape of the extended set (RPT_SHAPE_MONOMIAL), which only the *_ext builds
 // of the kernels know; everything else runs the base builds
 const KernelTable* table_for(uint32_t mode, bool ext = false);
@@ -255,6 +284,29 @@ void ensure_generic(rptgpu_scene* h, bool all);
 rptdev::PathState path_state(rptgpu_scene* h);
 rptdev::Camera make_camera(const RptCamera& c);
 int64_t free_memory();
+// the route of a call: a group with tree children is only walked by the per-tree kernels of the wavefront pipeline
+// (RPT_FLAG_PERSISTENT is a request such a scene cannot honour, not an error); without a flag, `fallback`
+inline bool use_wavefront(const rptgpu_scene* h, uint32_t flags, bool fallback) {
+  return (flags & RPT_FLAG_WAVEFRONT) || h->tree_kids ? true : (flags & RPT_FLAG_PERSISTENT) ? false : fallback;
+}
+// the next pass of `in` (everything filled) with its workspace made: rptplan::plan_pass, shrunk while the device is out
+// of memory (a pass of one sample per pixel that does not fit rethrows, as does every other error)
+rptplan::PassPlan size_pass(rptgpu_scene* h, const rptplan::PassInput& in, uint32_t npix, bool generic_all);
+// The per-tree pipeline's queries over the workspace (KernelTable::query with what every call takes from the handle):
+// the closest hits of the n rays of `ps`; the visibility of light l's shadow queue (n rays; d_n: its length on the
+// device).  reset_tree_counters: both sets of a tree's counters cleared, before the first query of a pass.
+void reset_tree_counters(rptgpu_scene* h);
+void query_closest(rptgpu_scene* h, const KernelTable* kt, const rptdev::PathState& ps, uint32_t n, const QueryHook* hook);
+void query_visibility(rptgpu_scene* h, const KernelTable* kt, const rptdev::PathState& ps, int l, uint32_t n,
+                      const uint32_t* d_n, const QueryHook* hook);
+// profiling: a launch of `kind` is counted and, when `on` and the pool has room (MAX_EVENT_PAIRS), bracketed with two
+// events of the handle's pool.  begin -> the pair (-1: none); drain_events resolves the pairs once the stream is idle
+int event_pair_begin(rptgpu_scene* h, int kind, bool on);
+void event_pair_end(rptgpu_scene* h, int kind, int pair);
+// The end of a call that ran the wavefront kernels: its last synchronisation.  rpt_tree_generic raises a flag when a
+// traversal outgrows its columns (they are sized from the scene, so that is a bug, not an input): with read_overflow the
+// flag rides with the synchronisation and is cleared, so that the flag of one call never surfaces in the next.
+int drain_call(rptgpu_scene* h, bool read_overflow);
 // packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list.
 // d_list (device, n_list pixel indices; requires packed and d_out): render exactly those pixels instead of the part's list,
 // without touching the cached partition (the adaptive buffer's active pixels, api_buffer.cpp)
@@ -267,9 +319,10 @@ const char* bad_aov(const RptAovBuffers* o);
 const char* bad_aov_params(const RptRenderParams* p);
 // the arrays of `channels` for n pixels inside `arrays` (grown when too small), zeroed on st (object: -1)
 rptdev::AovOut aov_arrays(DevBuf<double>& arrays, hipStream_t st, uint64_t n, uint32_t channels);
-// the call's route and kernels into `ao` (after ensure_partition); -> aov_drain's read_overflow
+// the call's route and kernels into `ao` (after ensure_partition); -> drain_call's read_overflow
 bool aov_enqueue(rptgpu_scene* h, const RptCamera& camera, const RptRenderParams& p, const rptdev::AovOut& ao);
-int aov_drain(rptgpu_scene* h, bool read_overflow);
+// hits and the arrays of `channels` for n pixels from the device to the caller's, on st
+void copy_aov_out(const rptdev::AovOut& src, uint32_t channels, const RptAovBuffers& dst, uint64_t n, hipStream_t st);
 
 // A handle whose aborted batch never drained (rptgpu_render_batch_reduce, drain_after_abort): the abandoned stream's
 // kernels may still read and write the workspace, the frame buffers and events, so every call that would enqueue work

@@ -95,8 +95,7 @@ int rptgpu_particles_time_derivative(int device, const RptParticleSystem* sys, u
   if (n == 0) return RPTGPU_OK;
   if (!pos || !vel || !out_dpos || !out_dvel) return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, "NULL array with n > 0");
   if (int e = check_device(device)) return e;
-  try {
-    HIP_TRY(hipSetDevice(device));
+  return guarded(nullptr, device, [&]() -> int {
     Stream st;
     HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     DevBuf<double> state, out;
@@ -107,11 +106,7 @@ int rptgpu_particles_time_derivative(int device, const RptParticleSystem* sys, u
     else HIP_TRY(rptparticles::launch_derivative(s, (uint32_t)n, state.p, out.p, st.s));
     download(out.p, n, out_dpos, out_dvel, st.s);
     return RPTGPU_OK;
-  } catch (const HipError& e) {
-    return hip_fail(nullptr, e);
-  } catch (const std::bad_alloc&) {
-    return fail(nullptr, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  }
+  });
 }
 
 int rptgpu_particles_integrate(int device, const RptParticleSystem* sys, uint64_t n, double* pos, double* vel,
@@ -126,8 +121,7 @@ int rptgpu_particles_integrate(int device, const RptParticleSystem* sys, uint64_
   if (n == 0) return RPTGPU_OK;
   if (!pos || !vel) return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, "NULL array with n > 0");
   if (int e = check_device(device)) return e;
-  try {
-    HIP_TRY(hipSetDevice(device));
+  return guarded(nullptr, device, [&]() -> int {
     Stream st;
     HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     DevBuf<double> s, ks, a, b;
@@ -154,11 +148,7 @@ int rptgpu_particles_integrate(int device, const RptParticleSystem* sys, uint64_
     }
     download(s.p, n, pos, vel, st.s);
     return RPTGPU_OK;
-  } catch (const HipError& e) {
-    return hip_fail(nullptr, e);
-  } catch (const std::bad_alloc&) {
-    return fail(nullptr, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  }
+  });
 }
 
 int rptgpu_monomial_closest_point(int device, double height, uint32_t steps, uint64_t n, const double* points,
@@ -168,8 +158,7 @@ int rptgpu_monomial_closest_point(int device, double height, uint32_t steps, uin
   if (n == 0) return RPTGPU_OK;
   if (!points || !out) return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, "NULL array with n > 0");
   if (int e = check_device(device)) return e;
-  try {
-    HIP_TRY(hipSetDevice(device));
+  return guarded(nullptr, device, [&]() -> int {
     Stream st;
     HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     DevBuf<double> in, res;
@@ -180,11 +169,7 @@ int rptgpu_monomial_closest_point(int device, double height, uint32_t steps, uin
     HIP_TRY(hipMemcpyAsync(out, res.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st.s));
     HIP_TRY(hipStreamSynchronize(st.s));
     return RPTGPU_OK;
-  } catch (const HipError& e) {
-    return hip_fail(nullptr, e);
-  } catch (const std::bad_alloc&) {
-    return fail(nullptr, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  }
+  });
 }
 
 int rptgpu_particles_eval_hypot(int device, uint64_t n, const double* x, const double* y, double* out) {
@@ -192,8 +177,7 @@ int rptgpu_particles_eval_hypot(int device, uint64_t n, const double* x, const d
   if (n == 0) return RPTGPU_OK;
   if (!x || !y || !out) return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, "NULL array with n > 0");
   if (int e = check_device(device)) return e;
-  try {
-    HIP_TRY(hipSetDevice(device));
+  return guarded(nullptr, device, [&]() -> int {
     Stream st;
     HIP_TRY(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
     DevBuf<double> buf;
@@ -204,11 +188,7 @@ int rptgpu_particles_eval_hypot(int device, uint64_t n, const double* x, const d
     HIP_TRY(hipMemcpyAsync(out, buf.p + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost, st.s));
     HIP_TRY(hipStreamSynchronize(st.s));
     return RPTGPU_OK;
-  } catch (const HipError& e) {
-    return hip_fail(nullptr, e);
-  } catch (const std::bad_alloc&) {
-    return fail(nullptr, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  }
+  });
 }
 
 } // extern "C"

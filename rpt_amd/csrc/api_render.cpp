@@ -1,34 +1,34 @@
 // api_render.cpp — workspace, the wavefront loop and the persistent launch behind every render entry point (their sizes:
 // render_plan.h); rptgpu_render_batch[_device], rptgpu_closest_hit, rptgpu_eval_math (see api_internal.h)
 #include "api_internal.h"
-#include "render_plan.h"
 
 namespace rptapi {
 
-// profiling: bracket a launch with two events from a pool; resolved at the end of the call
+int event_pair_begin(rptgpu_scene* h, int kind, bool on) {
+  h->stats.kernel_launches[kind]++;
+  if (!on || h->ev_used + 2 > MAX_EVENT_PAIRS * 2) return -1;
+  while ((int)h->ev_pool.size() < h->ev_used + 2) {
+    hipEvent_t e;
+    HIP_TRY(hipEventCreate(&e));
+    h->ev_pool.push_back(e);
+  }
+  const int e0 = h->ev_used;
+  h->ev_used += 2;
+  HIP_TRY(hipEventRecord(h->ev_pool[e0], h->stream));
+  return e0;
+}
+void event_pair_end(rptgpu_scene* h, int kind, int e0) {
+  if (e0 < 0) return;
+  HIP_TRY(hipEventRecord(h->ev_pool[e0 + 1], h->stream));
+  h->pending.push_back({kind, e0, e0 + 1});
+}
+
+// profiling: bracket a launch with an event pair; resolved at the end of the call
 struct Bracket {
   rptgpu_scene* h;
-  int kind;
-  bool on;
-  int e0 = -1;
-  Bracket(rptgpu_scene* h_, int kind_, bool on_) : h(h_), kind(kind_), on(on_) {
-    h->stats.kernel_launches[kind]++;
-    if (!on) return;
-    if (h->ev_used + 2 > MAX_EVENT_PAIRS * 2) { on = false; return; }
-    while ((int)h->ev_pool.size() < h->ev_used + 2) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      h->ev_pool.push_back(e);
-    }
-    e0 = h->ev_used;
-    h->ev_used += 2;
-    HIP_TRY(hipEventRecord(h->ev_pool[e0], h->stream));
-  }
-  void done() {
-    if (!on) return;
-    HIP_TRY(hipEventRecord(h->ev_pool[e0 + 1], h->stream));
-    h->pending.push_back({kind, e0, e0 + 1});
-  }
+  int kind, e0;
+  Bracket(rptgpu_scene* h_, int kind_, bool on) : h(h_), kind(kind_), e0(event_pair_begin(h_, kind_, on)) {}
+  void done() { event_pair_end(h, kind, e0); }
 };
 
 // launch_query's accounting hook: phases of a query bracketed with pool events like every other launch
@@ -43,22 +43,10 @@ struct QueryMarks {
 void query_mark(void* ctx, int kind, int end) {
   QueryMarks* q = (QueryMarks*)ctx;
   if (kind < 0 || kind >= RPT_K_COUNT) return;
-  rptgpu_scene* h = q->h;
   if (!end) {
-    h->stats.kernel_launches[kind]++;
-    q->e0[kind] = -1;
-    if (!q->on || h->ev_used + 2 > MAX_EVENT_PAIRS * 2) return;
-    while ((int)h->ev_pool.size() < h->ev_used + 2) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreate(&e));
-      h->ev_pool.push_back(e);
-    }
-    q->e0[kind] = h->ev_used;
-    h->ev_used += 2;
-    HIP_TRY(hipEventRecord(h->ev_pool[q->e0[kind]], h->stream));
-  } else if (q->e0[kind] >= 0) {
-    HIP_TRY(hipEventRecord(h->ev_pool[q->e0[kind] + 1], h->stream));
-    h->pending.push_back({kind, q->e0[kind], q->e0[kind] + 1});
+    q->e0[kind] = event_pair_begin(q->h, kind, q->on);
+  } else {
+    event_pair_end(q->h, kind, q->e0[kind]);
     q->e0[kind] = -1;
   }
 }
@@ -121,18 +109,19 @@ void ensure_generic(rptgpu_scene* h, bool all) {
   h->spill.gen_blocks_all = h->gen_threads / 256u >= blocks_all ? blocks_all : blocks_few;
 }
 
-// rpt_tree_generic raises a flag when a traversal outgrows its columns (they are sized from the scene, so that is a bug,
-// not an input): read and cleared after every batch of queries — a render's and rptgpu_closest_hit's alike, so that the
-// flag of one call never surfaces in the next.  The stream must be idle.
-bool generic_overflowed(rptgpu_scene* h, hipStream_t st) {
-  uint32_t flag = 0;
-  HIP_TRY(hipMemcpyAsync(&flag, h->gen_overflow.p, sizeof flag, hipMemcpyDeviceToHost, st));
+// (a profiled render's event pairs are resolved here, between the synchronisation and the flag: the stream is idle; no
+// other call has any)
+int drain_call(rptgpu_scene* h, bool read_overflow) {
+  hipStream_t st = h->stream;
+  uint32_t gen_overflow = 0;
+  if (read_overflow) HIP_TRY(hipMemcpyAsync(&gen_overflow, h->gen_overflow.p, sizeof gen_overflow, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (flag) {
-    HIP_TRY(hipMemsetAsync(h->gen_overflow.p, 0, sizeof(uint32_t), st));
-    HIP_TRY(hipStreamSynchronize(st));
+  drain_events(h);
+  if (gen_overflow) {
+    (void)hipMemsetAsync(h->gen_overflow.p, 0, sizeof(uint32_t), st);
+    return fail(h, RPTGPU_E_TREE_TOO_DEEP, "rpt_tree_generic: the traversal outgrew the stack sized for this scene (internal error)");
   }
-  return flag != 0;
+  return RPTGPU_OK;
 }
 
 // the keys, values and scratch of the rocPRIM sorts of cap entries (a tree's queue, or a depth's paths)
@@ -238,6 +227,42 @@ void release_workspace(rptgpu_scene* h) {
   h->path_order.release(); h->next_rows.release();
   h->gen_defer.release(); h->gen_frame.release(); h->gen_threads = 0; // rpt_tree_generic's columns (ensure_generic makes them again)
   h->ws_cap = 0; h->ws_rec_cols = 0;
+}
+
+rptplan::PassPlan size_pass(rptgpu_scene* h, const rptplan::PassInput& in, uint32_t npix, bool generic_all) {
+  rptplan::PassPlan pp = rptplan::plan_pass(in);
+  for (;;) {
+    const uint64_t np = rptplan::pass_slots(npix, pp);
+    try {
+      ensure_workspace(h, np, rptplan::pass_rec_cols(np, in.ratio));
+      if (generic_all) ensure_generic(h, true);
+      return pp;
+    } catch (const HipError& e) {
+      if (e.e != hipErrorOutOfMemory || pp.s_chunk == 1) throw;
+      (void)hipGetLastError(); // clear the sticky error before retrying
+      release_workspace(h);
+      h->ws_fail_paths = rptplan::fail_paths_after_oom(h->ws_fail_paths, np);
+      pp = rptplan::shrink_after_oom(pp);
+    }
+  }
+}
+
+void reset_tree_counters(rptgpu_scene* h) {
+  HIP_TRY(hipMemsetAsync(h->tq_ctr.p, 0, 16 * sizeof(uint32_t), h->stream));
+  h->qtune.ctr_set = 0;
+}
+static void tree_query(rptgpu_scene* h, const KernelTable* kt, const rptdev::PathState& ps, const uint32_t* queue, uint32_t n,
+                       int light, double* srt, const uint32_t* d_n, const QueryHook* hook) {
+  kt->query(h->stream, h->dscene, ps, queue, n, light, srt, d_n, h->obj_deep.data(), h->obj_tris.data(), h->dscene.num_objects,
+            h->tq.p, h->tq_ctr.p, (uint32_t)std::max(1, h->num_cus * 4), h->sort_rays ? &h->sort_bufs : nullptr, hook, &h->spill,
+            &h->qtune);
+}
+void query_closest(rptgpu_scene* h, const KernelTable* kt, const rptdev::PathState& ps, uint32_t n, const QueryHook* hook) {
+  tree_query(h, kt, ps, nullptr, n, -1, nullptr, nullptr, hook);
+}
+void query_visibility(rptgpu_scene* h, const KernelTable* kt, const rptdev::PathState& ps, int l, uint32_t n,
+                      const uint32_t* d_n, const QueryHook* hook) {
+  tree_query(h, kt, ps, h->shadow_q.p + (uint64_t)l * ps.cap, n, l, h->srt.p, d_n, hook);
 }
 
 rptdev::Camera make_camera(const RptCamera& c) {
@@ -381,10 +406,7 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
   // per tree and query: 102 of the wine glass's 354 fills per step)
   HIP_TRY(hipMemsetAsync(h->counters.p, 0, 2 * (size_t)nctr * sizeof(uint32_t), st));
   uint32_t cset = 0;
-  if (h->has_deep) {
-    HIP_TRY(hipMemsetAsync(h->tq_ctr.p, 0, 16 * sizeof(uint32_t), st));
-    h->qtune.ctr_set = 0;
-  }
+  if (h->has_deep) reset_tree_counters(h);
   { Bracket b(h, RPT_K_RAYGEN, prof); kt->raygen(st, fr, cam, ps, n_paths); b.done(); }
   h->stats.samples += n_paths;
   uint32_t n_active = n_paths;
@@ -395,7 +417,6 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
   // in-kernel in the general form — unless it has a group with tree children, which only the per-tree pipeline
   // walks (there the flag sends every ray of every such object through rpt_tree_generic)
   const bool by_object = h->has_deep && (!(p.flags & RPT_FLAG_GENERAL_TRAVERSAL) || h->tree_kids);
-  const uint32_t trace_blocks = (uint32_t)std::max(1, h->num_cus * 4);
   for (uint32_t depth = 0; depth <= p.max_bounces && n_active; depth++) {
     if (rec_off + n_active > h->ws_rec_cols) {
       *cols = rec_off + n_active;
@@ -403,8 +424,7 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
     }
     { Bracket b(h, RPT_K_EXTEND, prof);
       if (by_object)
-        kt->query(st, h->dscene, ps, queue, n_active, -1, nullptr, nullptr, h->obj_deep.data(), h->obj_tris.data(),
-                  h->dscene.num_objects, h->tq.p, h->tq_ctr.p, trace_blocks, h->sort_rays ? &h->sort_bufs : nullptr, &qhook, &h->spill, &h->qtune);
+        query_closest(h, kt, ps, n_active, &qhook);
       else
         kt->extend(st, h->dscene, ps, queue, n_active);
       b.done(); }
@@ -432,9 +452,7 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
       Bracket b(h, RPT_K_SHADOW, prof);
       if (by_object) {
         for (int l = 0; l < nlights; l++)
-          if (h->light_casts[l] && cnt[2 + l])
-            kt->query(st, h->dscene, ps, h->shadow_q.p + (uint64_t)l * ps.cap, cnt[2 + l], l, h->srt.p, ctrs + 2 + l, h->obj_deep.data(), h->obj_tris.data(),
-                      h->dscene.num_objects, h->tq.p, h->tq_ctr.p, trace_blocks, h->sort_rays ? &h->sort_bufs : nullptr, &qhook, &h->spill, &h->qtune);
+          if (h->light_casts[l] && cnt[2 + l]) query_visibility(h, kt, ps, l, cnt[2 + l], ctrs + 2 + l, &qhook);
       } else { // one launch for all lights of the depth (the grid's y is the light)
         uint32_t n_max = 0;
         for (int l = 0; l < nlights; l++)
@@ -499,21 +517,7 @@ void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderPar
     in.free_bytes = in.target_paths ? -1 : free_memory();
     in.held_slots = h->ws_cap; in.held_cols = h->ws_rec_cols; // (what the handle holds counts as available)
     in.fail_paths = h->ws_fail_paths;
-    rptplan::PassPlan pp = rptplan::plan_pass(in);
-    for (;;) {
-      const uint64_t np = rptplan::pass_slots(npix, pp);
-      try {
-        ensure_workspace(h, np, rptplan::pass_rec_cols(np, in.ratio));
-        if (generic_all) ensure_generic(h, true);
-        break;
-      } catch (const HipError& e) {
-        if (e.e != hipErrorOutOfMemory || pp.s_chunk == 1) throw;
-        (void)hipGetLastError(); // clear the sticky error before retrying
-        release_workspace(h);
-        h->ws_fail_paths = rptplan::fail_paths_after_oom(h->ws_fail_paths, np);
-        pp = rptplan::shrink_after_oom(pp);
-      }
-    }
+    const rptplan::PassPlan pp = size_pass(h, in, npix, generic_all);
     const uint32_t n_paths = npix * pp.s_chunk;
     fr.sample_base = p.sample_index_base + s0;
     const RptStats stats_at_start = h->stats; // (a pass that is started over counts once)
@@ -550,8 +554,12 @@ int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams*
   if (const char* why = bad_params(p)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (d_list && (!packed || !d_out || host_out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "a pixel list renders packed into device memory");
   auto t0 = std::chrono::steady_clock::now();
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  const int rc = guarded(h, h->device, [&]() -> int {
+    // a call leaves no event pair behind, however it ends (one that ends well has resolved them: drain_call)
+    struct EventPairs {
+      rptgpu_scene* h;
+      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
+    } event_pairs{h};
     // hipGetLastError() reports the thread's LAST failed runtime call, whoever made it (another library in the process,
     // an unchecked clean-up call): start from a clean slate so that the checks below speak about this call's launches
     (void)hipGetLastError();
@@ -569,11 +577,7 @@ int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams*
     }
     if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
     if (!packed) HIP_TRY(hipMemsetAsync(out, 0, frame_elems * out_elem, st));
-    // (a group with tree children is only walked by the per-tree kernels of the wavefront pipeline: RPT_FLAG_PERSISTENT
-    // is a request such a scene cannot honour, not an error)
-    const bool wavefront = (p->flags & RPT_FLAG_WAVEFRONT) || h->tree_kids ? true
-                           : (p->flags & RPT_FLAG_PERSISTENT)             ? false
-                                                                          : h->prefer_wavefront;
+    const bool wavefront = use_wavefront(h, p->flags, h->prefer_wavefront);
     h->dscene.force_general = (p->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
     if (npix) {
       h->accum.alloc((uint64_t)npix * 3);
@@ -584,24 +588,9 @@ int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams*
     }
     HIP_TRY(hipGetLastError());
     if (host_out) HIP_TRY(hipMemcpyAsync(host_out, out, frame_elems * out_elem, hipMemcpyDeviceToHost, st));
-    uint32_t gen_overflow = 0; // (the flag rides with the call's last synchronisation; generic_overflowed() is the stand-alone form)
-    if (wavefront && h->has_deep && h->gen_overflow.p)
-      HIP_TRY(hipMemcpyAsync(&gen_overflow, h->gen_overflow.p, sizeof gen_overflow, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (prof) drain_events(h);
-    if (gen_overflow) {
-      (void)hipMemsetAsync(h->gen_overflow.p, 0, sizeof(uint32_t), st);
-      return fail(h, RPTGPU_E_TREE_TOO_DEEP, "rpt_tree_generic: the traversal outgrew the stack sized for this scene (internal error)");
-    }
-  } catch (const HipError& e) {
-    h->pending.clear();
-    h->ev_used = 0;
-    return hip_fail(h, e);
-  } catch (const std::bad_alloc&) {
-    return fail(h, RPTGPU_E_OUT_OF_MEMORY, "host allocation failed");
-  } catch (...) {
-    return fail(h, RPTGPU_E_HIP, "unexpected exception");
-  }
+    return drain_call(h, wavefront && h->has_deep && h->gen_overflow.p);
+  });
+  if (rc != RPTGPU_OK) return rc;
   h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return RPTGPU_OK;
 }
@@ -628,8 +617,7 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
   if (precision_mode != RPT_PRECISION_F64_STRICT) return fail(h, RPTGPU_E_INVALID_ARGUMENT, BAD_MODE);
   REFUSE_IF_ABANDONED(h);
   if (!n) return RPTGPU_OK;
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  return guarded(h, h->device, [&]() -> int {
     hipStream_t st = h->stream;
     if (h->has_deep && (!h->rays_in_kernel || h->tree_kids)) {
       // a scene with deep trees: the rays take the route a render's rays take — object by object, every deep tree with
@@ -638,7 +626,6 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
       const uint64_t piece = std::min<uint64_t>(n, 4ull << 20);
       ensure_workspace(h, piece, piece);
       const rptdev::PathState ps = path_state(h);
-      const uint32_t trace_blocks = (uint32_t)std::max(1, h->num_cus * 4);
       std::vector<double> soa(6 * piece), hit(4 * piece);
       for (uint64_t base = 0; base < n; base += piece) {
         const uint64_t m = std::min(piece, n - base);
@@ -649,10 +636,8 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
           }
         for (int k = 0; k < 6; k++)
           HIP_TRY(hipMemcpyAsync(ps.ray + (uint64_t)k * ps.cap, soa.data() + (uint64_t)k * m, m * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(h->tq_ctr.p, 0, 16 * sizeof(uint32_t), st));
-        h->qtune.ctr_set = 0;
-        kt->query(st, h->dscene, ps, nullptr, (uint32_t)m, -1, nullptr, nullptr, h->obj_deep.data(), h->obj_tris.data(),
-                  h->dscene.num_objects, h->tq.p, h->tq_ctr.p, trace_blocks, h->sort_rays ? &h->sort_bufs : nullptr, nullptr, &h->spill, &h->qtune);
+        reset_tree_counters(h);
+        query_closest(h, kt, ps, (uint32_t)m, nullptr);
         HIP_TRY(hipGetLastError());
         for (int k = 0; k < 4; k++)
           HIP_TRY(hipMemcpyAsync(hit.data() + (uint64_t)k * m, ps.hit + (uint64_t)k * ps.cap, m * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -663,9 +648,7 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
           for (int k = 0; k < 3; k++) out_normal[3 * (base + i) + k] = hit[(uint64_t)(1 + k) * m + i];
         }
       }
-      if (h->gen_overflow.p && generic_overflowed(h, st))
-        return fail(h, RPTGPU_E_TREE_TOO_DEEP, "rpt_tree_generic: the traversal outgrew the stack sized for this scene (internal error)");
-      return RPTGPU_OK;
+      return drain_call(h, h->gen_overflow.p != nullptr);
     }
     DevBuf<double> d_o, d_d, d_t, d_n;
     DevBuf<int32_t> d_obj;
@@ -678,22 +661,16 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
     HIP_TRY(hipMemcpyAsync(out_normal, d_n.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_object, d_obj.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-  } catch (const HipError& e) {
-    return hip_fail(h, e);
-  } catch (...) {
-    return fail(h, RPTGPU_E_HIP, "unexpected exception");
-  }
-  return RPTGPU_OK;
+    return RPTGPU_OK;
+  });
 }
 
 int rptgpu_eval_math(rptgpu_scene* h, int fn, uint64_t n, const double* x, const double* y, double* out) {
   if (!h || (n && (!x || !out)) || fn < 0 || fn > 7 || (fn >= 6 && n && !y))
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "bad argument");
   if (!n) return RPTGPU_OK;
-  DevBuf<double> dx, dy, dout;
-  int rc = RPTGPU_OK;
-  try {
-    HIP_TRY(hipSetDevice(h->device));
+  return guarded(h, h->device, [&]() -> int {
+    DevBuf<double> dx, dy, dout;
     dx.alloc(n); dy.alloc(n); dout.alloc(n);
     HIP_TRY(hipMemcpyAsync(dx.p, x, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (y) HIP_TRY(hipMemcpyAsync(dy.p, y, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -702,13 +679,8 @@ int rptgpu_eval_math(rptgpu_scene* h, int fn, uint64_t n, const double* x, const
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, dout.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-  } catch (const HipError& e) {
-    rc = hip_fail(h, e);
-  } catch (...) {
-    rc = fail(h, RPTGPU_E_HIP, "unexpected exception");
-  }
-  dx.release(); dy.release(); dout.release();
-  return rc;
+    return RPTGPU_OK;
+  });
 }
 
 } // extern "C"
