@@ -703,6 +703,23 @@ class Renderer {
     check(rptgpu_render_aov(handle_, &cam, &p, &b));
     return a;
   }
+  // addition: path-traced radiance along rays of the caller's own making (rptgpu_trace_rays, include/rpt_gpu.h): light
+  // probes, lightmap texels, other projections.  origins, dirs: xyz per ray, the directions unit vectors; -> rgb per ray,
+  // the mean of num_samples paths of max_bounces bounces times 2^exposure_value.  Ray i draws from the stream (seed,
+  // streams[i] or i, sample) from draw first_draw on, whatever other rays the call holds.
+  std::vector<double> trace_rays(const std::vector<double>& origins, const std::vector<double>& dirs,
+                                 const std::vector<uint32_t>& streams = {}, uint32_t first_draw = 0) {
+    ensure_scene();
+    const size_t n = origins.size() / 3;
+    if (origins.size() != 3 * n || dirs.size() != 3 * n || (!streams.empty() && streams.size() != n))
+      throw std::invalid_argument("trace_rays: origins and dirs hold xyz per ray, streams one id per ray");
+    RptRayQuery q{};
+    q.struct_size = sizeof(RptRayQuery); q.max_bounces = max_bounces_; q.iterations = num_samples_; q.first_draw = first_draw;
+    q.exposure_value = ev_; q.seed = seed_;
+    std::vector<double> rgb(3 * n);
+    check(rptgpu_trace_rays(handle_, n, origins.data(), dirs.data(), streams.empty() ? nullptr : streams.data(), &q, rgb.data()));
+    return rgb;
+  }
   // addition: iterative_render with the Buffer kept on the device (rptgpu_buffer_*), followed by the feature-guided
   // a-trous filter of rptgpu_buffer_denoise (include/rpt_gpu.h) guided by the first hits of samples 0 .. feature_samples-1.
   // At least two batches (num_samples > callback_interval), else the library refuses: one batch has no variance.

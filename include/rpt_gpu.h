@@ -407,6 +407,51 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
                        uint32_t precision_mode, double* out_t, double* out_normal,
                        int32_t* out_object);
 
+/* ---- path-traced radiance along rays the CALLER supplies: light probes, lightmap texels, other projections, rays made
+ * by another program.  Additions within ABI version 7, detected by symbol (dlsym "rptgpu_trace_rays").
+ * Ray i is origins[3i..], dirs[3i..] (f64, xyz interleaved); the direction is used as given, as rptgpu_closest_hit uses
+ * it (normalise it yourself: the estimator, like the reference's trace_ray, expects a unit vector).  out_rgb[3i..] =
+ * (sum over s = 0 .. iterations-1, in that order, of L(i, s)) / iterations * 2^exposure_value, where L(i, s) is
+ * Renderer::trace_ray (renderer.rs:143-175: next-event estimation over every light, the sampled BSDF, the nested
+ * firefly clamp) of ray i with max_bounces bounces — every sample of a ray starts from the same ray.
+ * THE STREAM CONTRACT.  The random numbers of L(i, s) are the Philox4x32-10 stream keyed by `seed` with the counter
+ * (stream id, sample_index_base + s, draw block) — the keying of pixels, with the stream id where the pixel index is —
+ * read from draw `first_draw` on.  The stream id of ray i is streams[i], or i (its index in this call's arrays) when
+ * streams is NULL.  So a ray's result depends on (its origin and direction, seed, its stream id, its sample indices,
+ * first_draw) and on nothing else: not on which other rays share the call, on their order, on how the library cuts the
+ * call into pieces and passes, or on how a caller splits a batch over calls, handles or GPUs.  With the rays a camera
+ * makes (pixel p's ray of sample s, streams[i] = p, first_draw = the draws the camera took: 2, more under a lens) the
+ * result is the frame of rptgpu_render_batch, bit for bit.
+ * The call always runs the wavefront pipeline (flat scenes are walked in-kernel, deep trees through the per-tree
+ * queries), sized and restarted like a render's passes; RPT_FLAG_GENERAL_TRAVERSAL and RPT_FLAG_PROFILE_KERNELS are
+ * honoured, RPT_FLAG_WAVEFRONT changes nothing, and RptStats advances as for a render (samples = n * iterations).
+ * RPTGPU_RAYS_PIECE (environment, read per call; tests): the rays per piece.
+ * RPTGPU_E_INVALID_ARGUMENT, checked before any device work and with a detail naming the reason: a NULL RptRayQuery, a
+ * wrong struct_size, iterations == 0, max_bounces > 254, a precision_mode other than RPT_PRECISION_F64_STRICT,
+ * RPT_FLAG_PERSISTENT (the persistent kernel makes its rays from a camera), NULL origins / dirs / out with n > 0, more
+ * than 2^32 rays without stream ids, a NULL handle; RPTGPU_E_COMM for an abandoned handle.  n == 0 returns RPTGPU_OK. */
+typedef struct RptRayQuery {
+  uint32_t struct_size;       /* sizeof(RptRayQuery) */
+  uint32_t max_bounces;       /* <= 254 */
+  uint32_t iterations;        /* samples per ray, > 0 */
+  uint32_t first_draw;        /* draw index at which every ray's stream continues (0: a fresh stream) */
+  double exposure_value;
+  uint64_t seed;
+  uint64_t sample_index_base; /* index of every ray's first sample */
+  uint32_t precision_mode;    /* RPT_PRECISION_* */
+  uint32_t flags;             /* RPT_FLAG_* */
+} RptRayQuery;
+int rptgpu_trace_rays(rptgpu_scene* h, uint64_t n, const double* origins, const double* dirs,
+                      const uint32_t* streams /* may be NULL */, const RptRayQuery* q, double* out_rgb /* [n][3], host */);
+/* The same with every array in device memory ([n][3] f64 rays and results, [n] u32 stream ids or NULL), read and written
+ * where it lies.  `stream` is the hipStream_t the arrays' producer ran on: the call synchronises it, runs on the handle's
+ * own stream and returns when the results are complete (rptgpu_render_batch_device's rule).  NULL means NO stream, not
+ * the null stream: nothing is waited for.  The handle's stream is non-blocking (it is not ordered with the null stream),
+ * so a caller whose producer ran on the null stream — the default stream of most frameworks — synchronises it itself
+ * before the call (hipStreamSynchronize(0)); GpuScene.trace_rays does. */
+int rptgpu_trace_rays_device(rptgpu_scene* h, uint64_t n, const void* d_origins, const void* d_dirs,
+                             const void* d_streams /* may be NULL */, const RptRayQuery* q, void* d_out_rgb, void* stream);
+
 /* ---- host utility: KdTree::new (kdtree.rs:108-119, construct kdtree.rs:235-345) over n
  * axis-aligned boxes (p_min xyz, p_max xyz interleaved: 6 doubles per box).  Returns the
  * flattened tree through malloc'ed arrays the caller releases with rptgpu_free.

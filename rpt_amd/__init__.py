@@ -6,6 +6,8 @@ Scene, Object, Light, Material, Camera, Renderer, Buffer, Filter, Environment, H
 sphere, plane, cube, polygon, Mesh, KdTree, Triangle, Transformed, hex_color, color_bytes,
 and rpt::ode's ParticleState, ParticleSystem, SolidGravitySystem, MarblesSystem.
 The path tracer and the particle systems are HIP (rpt_amd/csrc) behind the C ABI in include/rpt_gpu.h.
+Beyond the reference: GpuScene.trace_rays runs the path estimator along rays of the caller's own making (numpy arrays,
+or torch tensors on the device).
 """
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401

@@ -162,6 +162,13 @@ class RptDenoise(C.Structure):
                 ("sigma_depth", f64), ("sigma_albedo", f64)]
 
 
+class RptRayQuery(C.Structure):
+    """include/rpt_gpu.h RptRayQuery (rptgpu_trace_rays' parameters; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_bounces", C.c_uint32), ("iterations", C.c_uint32),
+                ("first_draw", C.c_uint32), ("exposure_value", f64), ("seed", C.c_uint64),
+                ("sample_index_base", C.c_uint64), ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -190,6 +197,8 @@ SYMBOLS = [
      [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams), C.c_int, C.POINTER(C.c_float)]),
     ("rptgpu_closest_hit", C.c_int,
      [_VP, C.c_uint64, _PD, _PD, C.c_uint32, _PD, _PD, C.POINTER(C.c_int32)]),
+    ("rptgpu_trace_rays", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(C.c_uint32), C.POINTER(RptRayQuery), _PD]),
+    ("rptgpu_trace_rays_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptRayQuery), _VP, _VP]),
     ("rptgpu_eval_math", C.c_int, [_VP, C.c_int, C.c_uint64, _PD, _PD, _PD]),
     ("rptgpu_kdtree_build", C.c_int, [_PD, C.c_uint64, C.POINTER(RptKdTree)]),
     ("rptgpu_kdtree_build_device", C.c_int, [_PD, C.c_uint64, C.c_int, C.POINTER(RptKdTree)]),

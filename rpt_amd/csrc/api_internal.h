@@ -11,6 +11,7 @@
 //   api_comm.cpp     communicator, rptgpu_render_batch_reduce (the library-owned exchange and its failure paths),
 //                    rptgpu_render_batch_emulate_ranks
 //   api_buffer.cpp   the device-resident Buffer
+//   api_rays.cpp     rptgpu_trace_rays[_device]: the wavefront pipeline over rays the caller supplies, in pieces
 //   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, pass loop, copy_aov_out); its device
 //                    half also fills the features a Buffer holds for rptgpu_buffer_denoise
 // No compute happens on the host; if there is no HIP device every compute entry point returns RPTGPU_E_NO_DEVICE (there is
@@ -162,6 +163,8 @@ struct rptgpu_scene {
   uint64_t lbuf_max_bytes = 32ull << 30; // cap on lbuf (RPTGPU_LBUF_BYTES); larger batches run as several launches
   uint32_t paths_chunk = 0;            // samples per work item (RptSceneOptions::paths_chunk; 0 = chosen per launch)
   DevBuf<unsigned long long> pcounters; // [0] closest-hit rays [1] shadow rays
+  DevBuf<double> rays_o, rays_d, rays_out; // rptgpu_trace_rays: a piece of the host caller's rays and of their results (api_rays.cpp)
+  DevBuf<uint32_t> ray_ids;            // ... and the piece's stream ids (the caller's, or the rays' indices)
   DevBuf<double> aov_out;              // rptgpu_render_aov: the requested channels' full-frame arrays, back to back (api_aov.cpp)
   int num_cus = 0;
   bool prefer_wavefront = false; // scene has real kd-trees: traversal-latency bound
@@ -307,6 +310,21 @@ void event_pair_end(rptgpu_scene* h, int kind, int pair);
 // traversal outgrows its columns (they are sized from the scene, so that is a bug, not an input): with read_overflow the
 // flag rides with the synchronisation and is cleared, so that the flag of one call never surfaces in the next.
 int drain_call(rptgpu_scene* h, bool read_overflow);
+// Where the paths of a wavefront pass start — the one step of run_pass that knows: the pixels of a camera (rpt_raygen), or a
+// piece of the caller's rays (rpt_raygen_rays: fr.npix rays at origins / dirs on the device, [npix][3] f64, their streams
+// continuing at first_draw; ids_out: the piece's stream ids id_base + i are written there, see kernels/wavefront.inc)
+struct RaySource {
+  const rptdev::Camera* cam;
+  const double *origins, *dirs;
+  uint32_t first_draw, id_base;
+  uint32_t* ids_out;
+};
+// the pass planner's input for a call over npix pixels or rays: what its passes share, and the device's state right now
+rptplan::PassInput pass_input(rptgpu_scene* h, uint32_t npix, uint32_t iterations);
+void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in);
+// the wavefront driver: the batch in passes from `src`, then rpt_finish into `out` (api_render.cpp)
+void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const RaySource& src,
+                      void* out, bool out_f32, bool packed, bool prof);
 // packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list.
 // d_list (device, n_list pixel indices; requires packed and d_out): render exactly those pixels instead of the part's list,
 // without touching the cached partition (the adaptive buffer's active pixels, api_buffer.cpp)

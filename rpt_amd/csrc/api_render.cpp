@@ -392,12 +392,13 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   h->stats.shadow_rays_traced += rc[1]; // the persistent kernel traces every shadow ray (a skip there saves no wave time)
 }
 
-// One pass of the wavefront pipeline over n_paths = npix x spp paths: rpt_raygen, per depth { closest-hit query,
+// One pass of the wavefront pipeline over n_paths = npix x spp paths: the ray source's kernel (rpt_raygen for a camera's
+// pixels, rpt_raygen_rays for a piece of the caller's rays — the one step that differs), per depth { closest-hit query,
 // rpt_shade, the visibility queries, rpt_shadow_sum }, rpt_resolve.  *cols: the record columns the pass used.  false: the
 // pool ran out at some depth (*cols: the columns up to and with that depth) — the pass did not resolve, and nothing of it
 // has left the workspace.
 bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, const rptdev::Frame& fr,
-              const rptdev::Camera& cam, uint32_t n_paths, uint32_t spp, bool prof, const QueryHook& qhook, uint64_t* cols) {
+              const RaySource& src, uint32_t n_paths, uint32_t spp, bool prof, const QueryHook& qhook, uint64_t* cols) {
   hipStream_t st = h->stream;
   rptdev::PathState ps = path_state(h);
   const int nlights = h->dscene.num_lights;
@@ -407,7 +408,10 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
   HIP_TRY(hipMemsetAsync(h->counters.p, 0, 2 * (size_t)nctr * sizeof(uint32_t), st));
   uint32_t cset = 0;
   if (h->has_deep) reset_tree_counters(h);
-  { Bracket b(h, RPT_K_RAYGEN, prof); kt->raygen(st, fr, cam, ps, n_paths); b.done(); }
+  { Bracket b(h, RPT_K_RAYGEN, prof);
+    if (src.cam) kt->raygen(st, fr, *src.cam, ps, n_paths);
+    else kt->raygen_rays(st, fr, src.origins, src.dirs, src.first_draw, src.ids_out, src.id_base, ps, n_paths);
+    b.done(); }
   h->stats.samples += n_paths;
   uint32_t n_active = n_paths;
   const uint32_t* const queue = nullptr; // the paths of a depth stand densely in its state arrays: the identity
@@ -483,10 +487,30 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
   return true;
 }
 
+// what the passes of a call over npix pixels (or rays) have in common ...
+rptplan::PassInput pass_input(rptgpu_scene* h, uint32_t npix, uint32_t iterations) {
+  rptplan::PassInput in{};
+  in.npix = npix; in.iterations = iterations;
+  in.per_slot = rptplan::wavefront_slot_bytes(h->dscene.num_lights, h->has_deep, h->sort_rays, h->path_reorder);
+  in.target_paths = h->target_paths; in.budget_bytes = h->ws_budget_bytes;
+  // the share of the free memory a pass may take (round 6: 85 %, was 1/2 — the passes of a 288 GB device were
+  // sized for 140 GB).  RPTGPU_WS_FREE_FRACTION (percent): experiments only
+  in.free_percent = RPT_WS_FREE_PERCENT;
+  if (const char* e = std::getenv("RPTGPU_WS_FREE_FRACTION")) in.free_percent = (uint64_t)std::min(95, std::max(5, std::atoi(e)));
+  return in;
+}
+// ... and what the device and the handle hold right now
+void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in) {
+  in.free_bytes = in.target_paths ? -1 : free_memory();
+  in.held_slots = h->ws_cap; in.held_cols = h->ws_rec_cols; // (what the handle holds counts as available)
+  in.fail_paths = h->ws_fail_paths;
+}
+
 // scenes with deep trees (and RPT_FLAG_WAVEFRONT): the batch runs as passes of many paths in flight, each sized by
-// rptplan::plan_pass; a pass changes nothing outside the workspace before its rpt_resolve
+// rptplan::plan_pass; a pass changes nothing outside the workspace before its rpt_resolve.  Of p it reads iterations,
+// max_bounces, sample_index_base, exposure_value and flags (rptgpu_trace_rays, api_rays.cpp, fills in just those)
 void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr,
-                      const rptdev::Camera& cam, void* out, bool out_f32, bool packed, bool prof) {
+                      const RaySource& src, void* out, bool out_f32, bool packed, bool prof) {
   hipStream_t st = h->stream;
   const uint32_t npix = fr.npix;
   const bool print_launch = std::getenv("RPTGPU_PRINT_LAUNCH") != nullptr;
@@ -495,14 +519,7 @@ void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderPar
     // tests: start from a given (too small) figure instead of measuring, so that passes run out of columns and start over
     if (const char* e = std::getenv("RPTGPU_REC_RATIO")) h->rec_ratio = std::max(0.0, std::atof(e));
   }
-  rptplan::PassInput in{};
-  in.npix = npix; in.iterations = p.iterations;
-  in.per_slot = rptplan::wavefront_slot_bytes(h->dscene.num_lights, h->has_deep, h->sort_rays, h->path_reorder);
-  in.target_paths = h->target_paths; in.budget_bytes = h->ws_budget_bytes;
-  // the share of the free memory a pass may take (round 6: 85 %, was 1/2 — the passes of a 288 GB device were
-  // sized for 140 GB).  RPTGPU_WS_FREE_FRACTION (percent): experiments only
-  in.free_percent = RPT_WS_FREE_PERCENT;
-  if (const char* e = std::getenv("RPTGPU_WS_FREE_FRACTION")) in.free_percent = (uint64_t)std::min(95, std::max(5, std::atoi(e)));
+  rptplan::PassInput in = pass_input(h, npix, p.iterations);
   // (rpt_tree_generic's large grid — whole objects, or under RPT_FLAG_GENERAL_TRAVERSAL everything, go through it: up to
   // several hundred MB of columns for a deep mesh — is part of a pass's workspace: if it does not fit, the pass shrinks)
   const bool generic_all = h->has_deep && (h->gen_all || h->dscene.force_general);
@@ -514,15 +531,13 @@ void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderPar
     in.remaining = p.iterations - s0;
     in.rec_ratio = h->rec_ratio;
     in.ratio = rptplan::pass_ratio(h->rec_ratio, p.max_bounces);
-    in.free_bytes = in.target_paths ? -1 : free_memory();
-    in.held_slots = h->ws_cap; in.held_cols = h->ws_rec_cols; // (what the handle holds counts as available)
-    in.fail_paths = h->ws_fail_paths;
+    pass_input_now(h, in);
     const rptplan::PassPlan pp = size_pass(h, in, npix, generic_all);
     const uint32_t n_paths = npix * pp.s_chunk;
     fr.sample_base = p.sample_index_base + s0;
     const RptStats stats_at_start = h->stats; // (a pass that is started over counts once)
     uint64_t cols = 0;
-    if (!run_pass(h, kt, p, fr, cam, n_paths, pp.s_chunk, prof, qhook, &cols)) {
+    if (!run_pass(h, kt, p, fr, src, n_paths, pp.s_chunk, prof, qhook, &cols)) {
       // more levels per path than the pool was sized for (another camera, a margin too thin): the pass starts over
       // with room for half as many paths again per column budget; nothing of it has left the workspace
       HIP_TRY(hipStreamSynchronize(st));
@@ -584,7 +599,11 @@ int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams*
       rptdev::Frame fr{};
       fr.width = p->width; fr.height = p->height; fr.npix = npix; fr.pixels = d_list ? d_list : h->pixels.p;
       fr.max_bounces = p->max_bounces; fr.seed = p->seed; fr.accum = h->accum.p;
-      (wavefront ? render_wavefront : render_persistent)(h, kt, *p, fr, make_camera(*camera), out, out_f32, packed, prof);
+      const rptdev::Camera cam = make_camera(*camera);
+      RaySource src{};
+      src.cam = &cam;
+      if (wavefront) render_wavefront(h, kt, *p, fr, src, out, out_f32, packed, prof);
+      else render_persistent(h, kt, *p, fr, cam, out, out_f32, packed, prof);
     }
     HIP_TRY(hipGetLastError());
     if (host_out) HIP_TRY(hipMemcpyAsync(host_out, out, frame_elems * out_elem, hipMemcpyDeviceToHost, st));

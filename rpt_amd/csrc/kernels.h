@@ -152,6 +152,10 @@ struct QueryTuning {
 
 struct KernelTable {
   void (*raygen)(hipStream_t, const rptdev::Frame&, const rptdev::Camera&, const rptdev::PathState&, uint32_t n_paths);
+  // rpt_raygen's step for a piece of the caller's rays (rptgpu_trace_rays): fr.npix rays at origins / dirs ([npix][3] f64 on
+  // the device), every stream continuing at first_draw; ids_out (may be null): receives the piece's stream ids id_base + i
+  void (*raygen_rays)(hipStream_t, const rptdev::Frame&, const double* origins, const double* dirs, uint32_t first_draw,
+                      uint32_t* ids_out, uint32_t id_base, const rptdev::PathState&, uint32_t n_paths);
   void (*extend)(hipStream_t, const rptdev::Scene&, const rptdev::PathState&, const uint32_t* queue, uint32_t n);
   void (*extend_rays)(hipStream_t, const rptdev::Scene&, const double* o, const double* d, uint64_t n, double* out_t,
                       double* out_n, int32_t* out_obj);

@@ -26,6 +26,10 @@ static inline dim3 grid_push(uint64_t n) { return dim3((unsigned)((n + PUSH_BLOC
 void launch_raygen(hipStream_t st, const Frame& fr, const Camera& cam, const PathState& ps, uint32_t n_paths) {
   hipLaunchKernelGGL(rpt_raygen, grid_for(n_paths), dim3(256), 0, st, fr, cam, ps, n_paths);
 }
+void launch_raygen_rays(hipStream_t st, const Frame& fr, const double* origins, const double* dirs, uint32_t first_draw,
+                        uint32_t* ids_out, uint32_t id_base, const PathState& ps, uint32_t n_paths) {
+  hipLaunchKernelGGL(rpt_raygen_rays, grid_for(n_paths), dim3(256), 0, st, fr, origins, dirs, first_draw, ids_out, id_base, ps, n_paths);
+}
 void launch_extend(hipStream_t st, const Scene& sc, const PathState& ps, const uint32_t* queue, uint32_t n) {
   hipLaunchKernelGGL(rpt_extend, grid_for(n), dim3(256), 0, st, sc, ps, queue, n);
 }
@@ -306,7 +310,7 @@ bool read_prof(unsigned long long out[4][29]) {
 #endif
 }
 
-const KernelTable TABLE = {launch_raygen, launch_extend, launch_extend_rays, launch_shade,
+const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, launch_extend_rays, launch_shade,
                            launch_shadow_rays, launch_resolve, launch_finish, launch_scatter_f32, launch_eval_math,
                            paths_max_blocks_per_cu, launch_paths, launch_sum_samples, launch_query, sort_temp_bytes, launch_shadow_sum,
                            launch_buffer_accumulate, launch_buffer_retire, launch_buffer_image, launch_buffer_variance,

@@ -191,6 +191,25 @@ __global__ void __launch_bounds__(256) rpt_raygen(Frame fr, Camera cam, PathStat
   ps.pid[slot] = slot; // depth 0: the paths stand in the order of their ids
 }
 
+// The same first step for rays the caller made (rptgpu_trace_rays): slot = s_local * npix + p_local starts on ray p_local of
+// the piece, read as the caller laid it out ([n][3] f64, origins and dirs already offset to the piece) and used as given
+// (no normalisation: rptgpu_closest_hit's rule).  Every sample of a ray starts from the same ray; its stream (fr.pixels[
+// p_local], fr.sample_base + s_local) continues at draw first_draw.  ids_out: the caller named no stream ids — ray i of its
+// WHOLE array has stream i — so the lanes of the first sample write id_base + p_local where rpt_shade will look for it
+// (fr.pixels points at ids_out then).
+__global__ void __launch_bounds__(256) rpt_raygen_rays(Frame fr, const double* __restrict__ origins, const double* __restrict__ dirs,
+                                                       uint32_t first_draw, uint32_t* __restrict__ ids_out, uint32_t id_base,
+                                                       PathState ps, uint32_t n_paths) {
+  uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= n_paths) return;
+  uint32_t s_local = slot / fr.npix, p_local = slot - s_local * fr.npix;
+  st_soa3(ps.ray, ps.cap, slot, ld3(origins + 3 * (uint64_t)p_local));
+  st_soa3(ps.ray + 3 * ps.cap, ps.cap, slot, ld3(dirs + 3 * (uint64_t)p_local));
+  ps.draw[slot] = first_draw;
+  ps.pid[slot] = slot;
+  if (ids_out && s_local == 0) ids_out[p_local] = id_base + p_local;
+}
+
 // closest hit for every queued path.  queue == nullptr means the identity queue (depth 0).
 __global__ void __launch_bounds__(256, RPT_WF_WAVES) rpt_extend(Scene sc, PathState ps, const uint32_t* __restrict__ queue,
                                                   uint32_t n) {

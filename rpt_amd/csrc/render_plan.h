@@ -1,5 +1,6 @@
 // render_plan.h — how a render call is cut into launches (persistent pipeline) and passes (wavefront pipeline): the
-// arithmetic behind api_render.cpp's drivers, as pure host functions of numbers (tests/cpp/render_plan_check.cpp).
+// arithmetic behind api_render.cpp's drivers, as pure host functions of numbers (tests/cpp/render_plan_check.cpp), and the
+// pieces rptgpu_trace_rays cuts its rays into (tests/cpp/rays_piece_check.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -168,5 +169,18 @@ inline double ratio_after_restart(double rec_ratio, uint64_t cols_seen, uint32_t
   const double seen = (double)cols_seen / (double)n_paths;
   return std::min((double)max_bounces + 1.0, std::max(rec_ratio, seen) * 1.5);
 }
+
+// ---- rptgpu_trace_rays: the caller's n rays run through the wavefront pipeline in pieces, each piece the "frame" of its
+// own passes (npix = the piece's rays).  The smallest pass is one sample of every ray of the piece, so a piece holds at
+// most the paths a pass may have — pass_target: plan_pass's target for the scene with room for every level of every path
+// — and then piece x s_chunk <= pass_target <= RPT_MAX_PATHS_PER_PASS: the pass fits the workspace and its slots fit 32
+// bits.  Without a wish a piece is at most RAYS_PIECE_MAX rays, what rptgpu_closest_hit takes at a time (48 B of ray and
+// 24 B of result per ray staged for a host caller).  asked: RPTGPU_RAYS_PIECE (tests; 0 = not set), within the same bound.
+constexpr uint64_t RAYS_PIECE_MAX = 4ull << 20;
+inline uint64_t rays_piece(uint64_t n, uint64_t asked, uint64_t pass_target) {
+  const uint64_t fit = std::max<uint64_t>(1, std::min<uint64_t>(pass_target, RPT_MAX_PATHS_PER_PASS));
+  return std::max<uint64_t>(1, std::min(std::min<uint64_t>(n, asked ? asked : RAYS_PIECE_MAX), fit));
+}
+inline uint64_t rays_piece_count(uint64_t n, uint64_t piece) { return (n + piece - 1) / piece; }
 
 } // namespace rptplan

@@ -184,6 +184,84 @@ class GpuScene:
         _abi.check(code, self.handle)
         return t, nrm, obj
 
+    def trace_rays(self, origins, dirs, max_bounces, samples=1, seed=0x52505447, sample_index_base=0, streams=None,
+                   first_draw=0, exposure_value=0.0, flags=0, out=None):
+        """Path-traced radiance along the caller's rays (rptgpu_trace_rays) -> (n, 3) float64: per ray the
+        mean of `samples` paths of at most max_bounces bounces, times 2^exposure_value.  origins, dirs: (n, 3) float64, the
+        directions unit vectors (they are used as given).  streams: (n,) 32-bit stream ids, default the rays' indices; ray
+        i's random numbers are those of (seed, streams[i], sample_index_base + s) from draw first_draw on, so its result
+        does not depend on the rays around it.  numpy arrays go through host memory; torch tensors on the handle's device
+        are read where they lie (rptgpu_trace_rays_device) and the result is `out` or a new tensor there."""
+        q = _abi.RptRayQuery()
+        q.struct_size = C.sizeof(_abi.RptRayQuery)
+        q.max_bounces, q.iterations, q.first_draw = int(max_bounces), int(samples), int(first_draw)
+        q.exposure_value, q.seed, q.sample_index_base = float(exposure_value), int(seed), int(sample_index_base)
+        q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        if hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr"):
+            return self._trace_rays_torch(origins, dirs, streams, q, out)
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        n = len(o)
+        if len(d) != n:
+            raise ValueError("trace_rays: %d origins for %d directions" % (n, len(d)))
+        ids = None
+        if streams is not None:
+            ids = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
+            if len(ids) != n:
+                raise ValueError("trace_rays: %d stream ids for %d rays" % (len(ids), n))
+        if out is None:
+            out = np.empty((n, 3), dtype=np.float64)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (n, 3) and out.flags.c_contiguous):
+            raise ValueError("trace_rays: out must be a C-contiguous (n, 3) float64 array")
+        PD = C.POINTER(C.c_double)
+        code = self.lib.rptgpu_trace_rays(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD),
+                                          ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None,
+                                          C.byref(q), out.ctypes.data_as(PD))
+        _abi.check(code, self.handle)
+        return out
+
+    def _trace_rays_torch(self, origins, dirs, streams, q, out):
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def rays(t, what):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise ValueError("trace_rays: %s must be a torch tensor on %s, like the other arrays" % (what, dev))
+            return t.to(torch.float64).reshape(-1, 3).contiguous()  # (no copy when it already is all that)
+
+        o, d = rays(origins, "origins"), rays(dirs, "dirs")
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("trace_rays: %d origins for %d directions" % (n, d.shape[0]))
+        ids = None
+        if streams is not None:
+            if not isinstance(streams, torch.Tensor) or streams.device != dev:
+                raise ValueError("trace_rays: streams must be a torch tensor on %s, like the rays" % dev)
+            ids = streams.reshape(-1)
+            if ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                ids = ids.to(torch.int64).to(torch.int32)  # the low 32 bits
+            ids = ids.contiguous()
+            if ids.shape[0] != n:
+                raise ValueError("trace_rays: %d stream ids for %d rays" % (ids.shape[0], n))
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.float64
+                  and tuple(out.shape) == (n, 3) and out.is_contiguous()):
+            raise ValueError("trace_rays: out must be a contiguous (n, 3) float64 tensor on %s" % dev)
+        # The tensors' producer — and the conversions above — ran on torch's current stream; the handle's own stream is
+        # non-blocking, so nothing orders the two by itself.  A stream with a handle is handed to the library, which
+        # waits for it; torch's default stream is the null stream, whose handle 0 is the ABI's "no stream": that one is
+        # waited for here.
+        current = torch.cuda.current_stream(dev)
+        stream = current.cuda_stream
+        if not stream:
+            current.synchronize()
+        code = self.lib.rptgpu_trace_rays_device(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                 C.c_void_p(ids.data_ptr()) if ids is not None else None, C.byref(q),
+                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream or 0))
+        _abi.check(code, self.handle)
+        return out
+
     def render_aov(self, camera, params, channels=_abi.RPT_AOV_ALL):
         """First-hit feature buffers (rptgpu_render_aov) -> a dict of numpy arrays: `hits` (H, W) uint32
         always, and per channel of `channels` (RPT_AOV_*) the f64 SUMS over the hits of params.iterations camera rays per

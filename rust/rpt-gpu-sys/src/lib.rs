@@ -295,6 +295,21 @@ pub mod ffi {
         pub sigma_albedo: f64,
     }
 
+    /// `RptRayQuery` (the parameters of `rptgpu_trace_rays`; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptRayQuery {
+        pub struct_size: u32,
+        pub max_bounces: u32,
+        pub iterations: u32,
+        pub first_draw: u32,
+        pub exposure_value: f64,
+        pub seed: u64,
+        pub sample_index_base: u64,
+        pub precision_mode: u32,
+        pub flags: u32,
+    }
+
     /// opaque `rptgpu_scene`
     #[repr(C)]
     pub struct rptgpu_scene {
@@ -327,6 +342,8 @@ pub mod ffi {
         pub fn rptgpu_render_batch_reduce(h: *mut rptgpu_scene, camera: *const RptCamera, params: *const RptRenderParams, root: c_int, out_rgb32: *mut f32) -> c_int;
         pub fn rptgpu_render_batch_emulate_ranks(h: *mut rptgpu_scene, camera: *const RptCamera, params: *const RptRenderParams, world: c_int, out_rgb32: *mut f32) -> c_int;
         pub fn rptgpu_closest_hit(h: *mut rptgpu_scene, n: u64, origins: *const f64, dirs: *const f64, precision_mode: u32, out_t: *mut f64, out_normal: *mut f64, out_object: *mut i32) -> c_int;
+        pub fn rptgpu_trace_rays(h: *mut rptgpu_scene, n: u64, origins: *const f64, dirs: *const f64, streams: *const u32, q: *const RptRayQuery, out_rgb: *mut f64) -> c_int;
+        pub fn rptgpu_trace_rays_device(h: *mut rptgpu_scene, n: u64, d_origins: *const c_void, d_dirs: *const c_void, d_streams: *const c_void, q: *const RptRayQuery, d_out_rgb: *mut c_void, stream: *mut c_void) -> c_int;
         pub fn rptgpu_kdtree_build(boxes: *const f64, n: u64, out: *mut RptKdTree) -> c_int;
         pub fn rptgpu_kdtree_build_device(boxes: *const f64, n: u64, device: c_int, out: *mut RptKdTree) -> c_int;
         pub fn rptgpu_kdtree_free(tree: *mut RptKdTree);
@@ -705,6 +722,7 @@ mod layout_tests {
         assert_eq!(size_of::<RptAdaptive>(), 24);
         assert_eq!(size_of::<RptAovBuffers>(), 56);
         assert_eq!(size_of::<RptDenoise>(), 40);
+        assert_eq!(size_of::<RptRayQuery>(), 48);
     }
 
     #[test]
