@@ -357,6 +357,30 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
           lay.fuse_query = 1;
           off = up16(off + qtab_bytes);
         }
+        // the fused kernel's tables of what a hit derives from the scene alone (kernels/paths.inc SceneConsts), behind the
+        // quotient tables — if the wave's share holds them too; a scene in which it does not keeps the kernel without them
+        if (RPT_SCENE_CONSTS && lay.fuse_query) {
+          // (as the kernel counts them: scene_consts_fill; RPT_SCENE_CONSTS is the mask of the groups that are built)
+          uint64_t light_tris = 0, cubes = 0;
+          const uint64_t mats = (RPT_SCENE_CONSTS & 1) ? (uint64_t)fs.num_objects : 0u;
+          const rptdev::Light& l0 = fs.lights[0];
+          if ((RPT_SCENE_CONSTS & 2) && l0.kind == RPT_LIGHT_OBJECT && fs.insts[l0.inst].kind == RPT_SHAPE_MESH &&
+              !fs.insts[l0.inst].has_xf)
+            light_tris = fs.trees[fs.insts[l0.inst].tree].num_prims;
+          auto xf_cube = [&](int i) { return i < fs.num_objects && fs.insts[i].kind == RPT_SHAPE_CUBE && fs.insts[i].has_xf; };
+          for (int i = 0; (RPT_SCENE_CONSTS & 4) && i < fs.num_objects;) {
+            if (xf_cube(i) && xf_cube(i + 1)) { cubes += 2; i += 2; }
+            else i++;
+          }
+          // the cubes' normals (back to front), then at off_consts the materials' constants and the light's pdfs
+          const uint64_t base = off + cubes * RPT_CUBE_NORMALS_BYTES; // (a multiple of 16, as `off` is)
+          const uint64_t end = up16(base + mats * RPT_MAT_CONSTS_BYTES + light_tris * sizeof(double));
+          if (end + RPT_PATHS_STASH_MAX_LDS <= WAVE_LDS) {
+            lay.scene_consts = 1;
+            lay.off_consts = (uint32_t)base;
+            off = end;
+          }
+        }
         h->plane_vals.upload(planes, h->stream);
         HIP_TRY(hipStreamSynchronize(h->stream)); // `planes` dies with this block
         lay.plane_vals = h->plane_vals.p;

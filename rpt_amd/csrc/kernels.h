@@ -41,6 +41,20 @@
 #define RPT_PRETRACE_CULL 1
 #endif
 #define RPT_CULL_MAX 4
+// RPT_SCENE_CONSTS=1: rpt_paths<KdFlat, false, true, true> reads what a hit's shading and the two-cube block derive from
+// the scene alone — per object the material's m2, m2 * PI, f0 and 1 - f0, sample_f's lobe probability and gen_bool's
+// integer; per triangle of the mesh light Shape::sample's pdf; per cube of a two-cube block its six world normals —
+// from tables that every wave fills once, in its prologue, with the loop's own expressions (kernels/paths.inc
+// SceneConsts; FlatLayout::scene_consts when the wave's LDS share holds them, else the kernel without them);
+// 0: every hit computes them, the parent's loop (A/B builds).  The value is a mask of the groups that are built:
+// 1 = the materials' constants, 2 = the light's pdfs, 4 = the cubes' normals.  The default leaves the light's pdfs out:
+// with them the kernel spills 293 SGPRs (284 without, 287 before the tables), whichever way their table is addressed —
+// although C2 gains 1.4 % more with them (profiles/scene_consts_ab.txt)
+#ifndef RPT_SCENE_CONSTS
+#define RPT_SCENE_CONSTS 5
+#endif
+#define RPT_MAT_CONSTS_BYTES 88u   // per object (kernels/paths.inc MatConsts)
+#define RPT_CUBE_NORMALS_BYTES 144u // per cube of a two-cube block: [face][3] doubles
 #define RPT_PATHS_STASH_LDS 4864u
 #define RPT_PATHS_STASH_HIT_LDS 6656u
 // what the host leaves room for in a KdFlat scene's LDS layout (api_scene.cpp)
@@ -90,6 +104,11 @@ struct FlatLayout {
   uint32_t pretrace_cull, cull_n;
   uint64_t cull_always;
   uint32_t cull_obj[RPT_CULL_MAX], cull_lo[RPT_CULL_MAX], cull_ext[RPT_CULL_MAX];
+  // rpt_paths<KdFlat, false, true, true> (RPT_SCENE_CONSTS): the wave's tables of per-launch constants behind the quotient
+  // tables (api_scene.cpp; kernels/launch.inc selects the kernel by scene_consts).  off_consts: [objects] MatConsts from
+  // there on and [triangles of the light's mesh] doubles behind them; in front of it, back to front, [cubes in two-cube
+  // blocks, in object order][6][3] doubles (kernels/paths.inc FlatLds::consts)
+  uint32_t scene_consts, off_consts;
 };
 
 // buffers of the optional ray sort in front of a per-tree traversal (all sized for the query's n)

@@ -184,6 +184,9 @@ template __global__ void rpt_paths<KdFlat, false>(Scene, Frame, Camera, PersistA
 template __global__ void rpt_paths<KdFlat, true>(Scene, Frame, Camera, PersistArgs);
 #if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
 template __global__ void rpt_paths<KdFlat, false, true>(Scene, Frame, Camera, PersistArgs); // (C2: one light)
+#if RPT_SCENE_CONSTS
+template __global__ void rpt_paths<KdFlat, false, true, true>(Scene, Frame, Camera, PersistArgs); // (C2: its constants in tables)
+#endif
 #endif
 template __global__ void rpt_paths<KdFlatG, false>(Scene, Frame, Camera, PersistArgs);
 template __global__ void rpt_paths<KdFlatG, true>(Scene, Frame, Camera, PersistArgs);

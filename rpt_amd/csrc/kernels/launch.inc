@@ -71,6 +71,10 @@ int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool par
                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<L, false>, 64, lds_bytes))
   if (flat && flat->obj_filter) e = RPT_OCC(KdFlatF);
 #if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
+#if RPT_SCENE_CONSTS
+  else if (flat && flat->n_tris && flat->fuse_query && !park && flat->scene_consts)
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<KdFlat, false, true, true>, 64, lds_bytes);
+#endif
   else if (flat && flat->n_tris && flat->fuse_query && !park)
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<KdFlat, false, true>, 64, lds_bytes);
 #endif
@@ -97,7 +101,12 @@ void launch_paths(hipStream_t st, const Scene& sc, const Frame& fr, const Camera
                        else hipLaunchKernelGGL((rpt_paths<L, false>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa); } while (0)
   if (flat && lay.obj_filter) RPT_GO(KdFlatF);
 #if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
-  // one light that casts shadow rays (the host doubled the quotient table for it): the two-ray form (kernels/paths.inc)
+  // one light that casts shadow rays (the host doubled the quotient table for it): the two-ray form (kernels/paths.inc),
+  // with a hit's scene constants in the wave's tables where the host found room for them
+#if RPT_SCENE_CONSTS
+  else if (flat && lay.n_tris && lay.fuse_query && !park && lay.scene_consts)
+    hipLaunchKernelGGL((rpt_paths<KdFlat, false, true, true>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa);
+#endif
   else if (flat && lay.n_tris && lay.fuse_query && !park)
     hipLaunchKernelGGL((rpt_paths<KdFlat, false, true>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa);
 #endif

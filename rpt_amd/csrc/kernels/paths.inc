@@ -106,7 +106,119 @@ struct FlatLds {
   const LeafBox* obj_box;            // [objects] conservative boxes (device memory, read through s_load)
   const double* obj_grid;            // qlo[3], qscale[3], bounds[6] (device memory, s_load)
   uint64_t obj_always;
+  // rpt_paths<KdFlat, false, true, true>: what a hit derives from the scene alone, once per wave (SceneConsts below)
+  // — ONE address for the three tables (each one more that the loop keeps costs the kernel scalar registers it has to
+  // spill): [objects] MatConsts from it on, behind them [triangles of the light's mesh] doubles, and in front of it, back
+  // to front, [cubes in two-cube blocks, in object order][face][3] doubles (mat_consts_of, light_pdf_of, cube_nrm_of)
+  const unsigned char* consts;
 };
+// ------------------------------------------------------------------ a hit's scene constants, once per wave
+// SceneConsts (rpt_paths<KdFlat, false, true, true>, RPT_SCENE_CONSTS): the straight-line code of a hit computes values
+// that depend on the material, the light's triangle or the cube alone — fixed for the whole launch.  Every wave computes
+// them once, in its prologue (scene_consts_fill), with the loop's own expressions on the same operands in the same order,
+// so the bits are the loop's; it reads the scene's records from device memory as they stand at the launch, so a live
+// update needs nothing more.  Lane `ob` does object `ob`, lane `k` triangle `k` of the light's mesh, lanes 0-11 the
+// faces of a two-cube block.  (FlatLds::consts says where the three tables lie.)
+// The three groups can be built one by one (A/B builds): RPT_SCENE_CONSTS is a mask, 1 = the materials' constants,
+// 2 = the light's pdfs, 4 = the cubes' normals (kernels.h says which ones the default builds, and why).
+constexpr bool SC_MAT = (RPT_SCENE_CONSTS & 1) != 0, SC_LIGHT = (RPT_SCENE_CONSTS & 2) != 0, SC_CUBE = (RPT_SCENE_CONSTS & 4) != 0;
+struct MatConsts {   // of the material of an object (bsdf_opaque, sample_f_opaque and the kernel's lobe probability)
+  double m2, m2pi;   // roughness^2; m2 * PI (bsdf's Beckmann denominator m2 * PI * nh2 * nh2; beckmann_pdf's PI * m2)
+  double f0s;        // pow2((index - 1) / (index + 1))
+  double f0[3];      // lerp((f0s, f0s, f0s), color, metallic)
+  double omf0[3];    // (1, 1, 1) - f0
+  double fs;         // sample_f's lobe probability
+  uint64_t p_int;    // gen_bool(fs)'s threshold (unused when fs == 1.0: gen_bool then takes no draw)
+};
+static_assert(sizeof(MatConsts) == RPT_MAT_CONSTS_BYTES, "kernels.h sizes the wave's LDS budget with it");
+// a face of the unit cube as cube_candidate names its normals: 2 * axis + (1 if the normal points down the axis)
+RPT_DEV D3 cube_face_normal(uint32_t face) {
+  const double s = (face & 1u) ? -1.0 : 1.0;
+  const uint32_t axis = face >> 1;
+  return mk(axis == 0u ? s : 0.0, axis == 1u ? s : 0.0, axis == 2u ? s : 0.0);
+}
+RPT_DEV const MatConsts* mat_consts_of(const FlatLds* fl, int obj) { return reinterpret_cast<const MatConsts*>(fl->consts) + obj; }
+RPT_DEV const double* light_pdf_of(const Scene& sc, const FlatLds* fl) {
+  return reinterpret_cast<const double*>(fl->consts + (SC_MAT ? (uint32_t)sc.num_objects : 0u) * (uint32_t)sizeof(MatConsts));
+}
+RPT_DEV D3 cube_nrm_of(const FlatLds* fl, uint32_t slot, uint32_t face) { // cube `slot` sits slot + 1 cubes in front of fl->consts
+  return ld3(reinterpret_cast<const double*>(fl->consts) - (slot + 1u) * 18u + face * 3u);
+}
+RPT_DEV bool xf_cube_pair(const Scene& sc, int i) { // flat_query's condition for its two-cube block
+  return cinst(sc, i).kind == RPT_SHAPE_CUBE && cinst(sc, i).has_xf && i + 1 < sc.num_objects &&
+         cinst(sc, i + 1).kind == RPT_SHAPE_CUBE && cinst(sc, i + 1).has_xf;
+}
+// the prologue's part (all 64 lanes, before the barrier; `tris` = the scene's triangles in device memory)
+RPT_DEV void scene_consts_fill(const Scene& sc, const Tri* __restrict__ tris, uint32_t l, unsigned char* consts) {
+  MatConsts* mc = reinterpret_cast<MatConsts*>(consts);
+  double* light_pdf = reinterpret_cast<double*>(consts + (SC_MAT ? (uint32_t)sc.num_objects : 0u) * (uint32_t)sizeof(MatConsts));
+  for (uint32_t ob = l; SC_MAT && ob < (uint32_t)sc.num_objects; ob += 64) {
+    const Material& mat = sc.materials[sc.insts[ob].material];
+    MatConsts c;
+    const D3 color = ld3(mat.color);
+    const D3 one = mk(1, 1, 1);
+    c.m2 = mat.roughness * mat.roughness;
+    c.m2pi = c.m2 * PI;
+    c.f0s = pow2((mat.index - 1.0) / (mat.index + 1.0));
+    const D3 f0 = lerp(mk(c.f0s, c.f0s, c.f0s), color, mat.metallic);
+    const D3 omf0 = one - f0;
+    c.f0[0] = f0.x; c.f0[1] = f0.y; c.f0[2] = f0.z;
+    c.omf0[0] = omf0.x; c.omf0[1] = omf0.y; c.omf0[2] = omf0.z;
+    const double mean = ((color.x + color.y) + color.z) / 3.0;
+    double fs = (1.0 - mat.metallic) * c.f0s + mat.metallic * mean;
+    fs = fs * (1.0 - 0.2) + 1.0 * 0.2;
+    c.fs = fs;
+    c.p_int = (uint64_t)(fs * 18446744073709551616.0);
+    mc[ob] = c;
+  }
+  CLight& lg = clight(sc, 0);
+  CInst& li = cinst(sc, lg.inst);
+  if (SC_LIGHT && lg.kind == RPT_LIGHT_OBJECT && li.kind == RPT_SHAPE_MESH && !li.has_xf) { // illuminate_mesh's light
+    CTree& tr = ctree(sc, li.tree);
+    for (uint32_t k = l; k < tr.num_prims; k += 64) {
+      const Tri* tp = tris + tr.prim_base + k;
+      const D3 v1 = ld3(tp->v), v2 = ld3(tp->v + 3), v3 = ld3(tp->v + 6);
+      const double area = 0.5 * length(cross(v2 - v1, v3 - v1));
+      double p = 1.0 / area;
+      p = p / (double)tr.num_prims;
+      light_pdf[k] = p;
+    }
+  }
+  uint32_t slot = 0;
+  for (int i = 0; SC_CUBE && i < sc.num_objects;) { // the two-cube blocks in the order flat_query meets them
+    if (!xf_cube_pair(sc, i)) { i++; continue; }
+    if (l < 12u) {
+      const uint32_t c = l / 6u, face = l - 6u * c;
+      const D3 w = normalize(mat3_mul(sc.insts[i + (int)c].nrm, cube_face_normal(face))); // Transformed::intersect shape.rs:131-132
+      double* q = reinterpret_cast<double*>(consts) - (slot + c + 1u) * 18u + face * 3u;
+      q[0] = w.x; q[1] = w.y; q[2] = w.z;
+    }
+    slot += 2u;
+    i += 2;
+  }
+}
+// cube_candidate (shapes.inc) with the candidate's normal as its face (cube_face_normal): the same tests in the same order
+RPT_DEV bool cube_candidate_face(D3 o, const RcpD& rdx, const RcpD& rdy, const RcpD& rdz, double t_min, double& time,
+                                 uint32_t& face) {
+  double x1, x2, y1, y2, z1, z2;
+  uint32_t fx = 1u, fy = 3u, fz = 5u; // the ENTRY face along each axis: the normal -1 unless the interval was swapped
+  div6(-0.5 - o.x, 0.5 - o.x, rdx, -0.5 - o.y, 0.5 - o.y, rdy, -0.5 - o.z, 0.5 - o.z, rdz, x1, x2, y1, y2, z1, z2);
+  if (x1 > x2) { double t = x1; x1 = x2; x2 = t; fx = 0u; }
+  if (y1 > y2) { double t = y1; y1 = y2; y2 = t; fy = 2u; }
+  if (z1 > z2) { double t = z1; z1 = z2; z2 = t; fz = 4u; }
+  double start, end;
+  uint32_t sf, ef; // the exit face is the opposite one of the same axis
+  if (x1 > y1 && x1 > z1) { start = x1; sf = fx; }
+  else if (y1 > z1) { start = y1; sf = fy; }
+  else { start = z1; sf = fz; }
+  if (x2 < y2 && x2 < z2) { end = x2; ef = fx ^ 1u; }
+  else if (y2 < z2) { end = y2; ef = fy ^ 1u; }
+  else { end = z2; ef = fz ^ 1u; }
+  if (start > end || end < t_min) return false;
+  if (start < t_min) { time = end; face = ef; }
+  else { time = start; face = sf; }
+  return true;
+}
 // ------------------------------------------------------------------ flat scenes: batched quad tests
 // Renderer::get_closest_hit / the visibility query for a scene whose trees are all single leaves.  The
 // reference tests the objects one after the other; for a run of consecutive untransformed meshes (the
@@ -272,9 +384,12 @@ RPT_DEV uint64_t cull_skip_mask(const FlatLayout& lay, uint32_t near) {
 
 // CULL (the pre-trace pass of rpt_paths<KdFlat, false, true>, RPT_PRETRACE_CULL): bit k of the wave-uniform `skip` = no
 // ray of the wave can be accepted by object k (cull_skip_mask), its test is left out
-template <bool SHADOW, bool CULL = false>
+// CONSTS (rpt_paths<KdFlat, false, true, true>): the two-cube block takes an accepted cube's world normal from the
+// wave's table (SceneConsts above)
+template <bool SHADOW, bool CULL = false, bool CONSTS = false>
 RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_stop, double& rt, D3& rn, uint64_t skip = 0ull) {
   int obj = -1;
+  uint32_t cslot = 0; // CONSTS: the next two-cube block's first cube in the table of normals (cube_nrm_of)
   RcpD rwx = rcp_make(d.x), rwy = rcp_make(d.y), rwz = rcp_make(d.z);
   const int n = sc.num_objects;
   const uint32_t lane = __lane_id();
@@ -355,30 +470,36 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
       if (CULL && ((skip >> i) & 3ull) == 3ull) { // (the block as it is when one of the two may be hit)
         PROF_COUNT(PF_P_PRECULL);
         i += 2;
+        cslot += 2u;
         continue;
       }
       CInst& in2 = cinst(sc, i + 1);
+      constexpr bool TAB = CONSTS && SC_CUBE && !SHADOW; // the accepted normal from the wave's table, by the candidate's face
       D3 lo1 = mat4_mul(in.inv, o, 1.0), ld1 = mat4_mul(in.inv, d, 0.0);
       D3 lo2 = mat4_mul(in2.inv, o, 1.0), ld2 = mat4_mul(in2.inv, d, 0.0);
       RcpD ax = rcp_make(ld1.x), ay = rcp_make(ld1.y), az = rcp_make(ld1.z);
       RcpD bx = rcp_make(ld2.x), by = rcp_make(ld2.y), bz = rcp_make(ld2.z);
       double t1 = 0.0, t2 = 0.0;
       D3 n1 = mk(0, 0, 0), n2 = mk(0, 0, 0);
-      bool c1 = cube_candidate(lo1, ax, ay, az, EPSILON, t1, n1);
-      bool c2 = cube_candidate(lo2, bx, by, bz, EPSILON, t2, n2);
+      uint32_t f1 = 0u, f2 = 0u;
+      bool c1 = TAB ? cube_candidate_face(lo1, ax, ay, az, EPSILON, t1, f1) : cube_candidate(lo1, ax, ay, az, EPSILON, t1, n1);
+      bool c2 = TAB ? cube_candidate_face(lo2, bx, by, bz, EPSILON, t2, f2) : cube_candidate(lo2, bx, by, bz, EPSILON, t2, n2);
       if (c1 && t1 < rt) {
         rt = t1;
-        if (!SHADOW) rn = normalize(mat3_mul(in.nrm, n1)); // Transformed::intersect shape.rs:131-132
+        if constexpr (TAB) rn = cube_nrm_of(fl, cslot, f1);
+        else if (!SHADOW) rn = normalize(mat3_mul(in.nrm, n1)); // Transformed::intersect shape.rs:131-132
         obj = i;
       }
       if (SHADOW && rt <= t_stop) return obj;
       if (c2 && t2 < rt) {
         rt = t2;
-        if (!SHADOW) rn = normalize(mat3_mul(in2.nrm, n2));
+        if constexpr (TAB) rn = cube_nrm_of(fl, cslot + 1u, f2);
+        else if (!SHADOW) rn = normalize(mat3_mul(in2.nrm, n2));
         obj = i + 1;
       }
       if (SHADOW && rt <= t_stop) return obj;
       i += 2;
+      cslot += 2u;
     } else {
       if (CULL && ((skip >> i) & 1ull) != 0ull) {
         i++;
@@ -402,9 +523,13 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
 // pv - o and each cube's inv * o.  The two rays' slab quotients, wall candidates and cube candidates sit side by side in
 // straight-line code, so that the two dependency chains overlap.
 // A slot that is off (no bounce ray: the path ends at this hit) enters with its record at -inf: no test accepts.
+// CONSTS: as in flat_query.
+template <bool CONSTS_>
 RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, double t_stop, double& rtb, D3& rnb,
                         double& rts) {
+  constexpr bool CONSTS = CONSTS_ && SC_CUBE;
   int obj = -1;
+  uint32_t cslot = 0;
   const int n = sc.num_objects;
   const uint32_t lane = __lane_id();
   const uint32_t nx = fl->plane_cnt & 15u, ny = (fl->plane_cnt >> 4) & 15u, nz = (fl->plane_cnt >> 8) & 15u;
@@ -489,16 +614,19 @@ RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, 
         const RcpD sx = rcp_make(ls.x), sy = rcp_make(ls.y), sz = rcp_make(ls.z);
         double tb = 0.0, ts = 0.0;
         D3 nb = mk(0, 0, 0), ns = mk(0, 0, 0);
-        const bool hb = cube_candidate(lo, bx, by, bz, EPSILON, tb, nb);
+        uint32_t fb = 0u;
+        const bool hb = CONSTS ? cube_candidate_face(lo, bx, by, bz, EPSILON, tb, fb) : cube_candidate(lo, bx, by, bz, EPSILON, tb, nb);
         const bool hs = cube_candidate(lo, sx, sy, sz, EPSILON, ts, ns);
         if (hb && tb < rtb) {
           rtb = tb;
-          rnb = normalize(mat3_mul(q.nrm, nb)); // Transformed::intersect shape.rs:131-132
+          if constexpr (CONSTS) rnb = cube_nrm_of(fl, cslot + (uint32_t)c, fb);
+          else rnb = normalize(mat3_mul(q.nrm, nb)); // Transformed::intersect shape.rs:131-132
           obj = i + c;
         }
         if (hs && ts < rts) rts = ts;
       }
       i += 2;
+      cslot += 2u;
     } else { // anything else: the object's own test, once per ray
       if (!(rtb == -INF)) {
         const RcpD rx = rcp_make(db.x), ry = rcp_make(db.y), rz = rcp_make(db.z);
@@ -531,8 +659,10 @@ struct HitDraws {
   uint64_t qa, qb; // the +-1 pair that was kept
   bool spec;      // gen_bool(f)
 };
-// sf: sample_f runs (depth < max_bounces); f: sample_f's lobe probability
-RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, HitDraws& o) {
+// sf: sample_f runs (depth < max_bounces); f: sample_f's lobe probability; mc (CONSTS): the material's constants, with
+// gen_bool(f)'s threshold among them
+template <bool CONSTS = false>
+RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, HitDraws& o, const MatConsts* mc = nullptr) {
   o.tri = gen_index_zone(r, n, zone);
   next2_u64(r, o.a, o.b);
   while ((o.a >> 11) + (o.b >> 11) >= (1ull << 53) + 2ull) {
@@ -541,7 +671,8 @@ RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, Hit
   }
   o.th = 1ull << 63; o.qa = 0; o.qb = 0; o.spec = false;
   if (!sf) return;
-  o.spec = gen_bool(r, f);
+  if constexpr (CONSTS) o.spec = f == 1.0 ? true : next_u64(r) < mc->p_int; // gen_bool: no draw when f == 1.0
+  else o.spec = gen_bool(r, f);
   if (o.spec) o.th = next_u64(r);
   for (;;) {
     PROF_COUNT(PF_P_REJECT);
@@ -553,21 +684,32 @@ RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, Hit
 }
 
 // bsdf() for an opaque material: both directions outside (the reflection case) or zero, its early return a select
-RPT_DEV D3 bsdf_opaque(const Material& m, D3 n, D3 wo, D3 wi) { // material.rs:125-170
+// (CONSTS: m2, m2 * PI, f0 and one - f0 from the material's constants)
+template <bool CONSTS = false>
+RPT_DEV D3 bsdf_opaque(const Material& m, D3 n, D3 wo, D3 wi, const MatConsts* mc = nullptr) { // material.rs:125-170
   D3 color = ld3(m.color);
   double n_dot_wi = dot(n, wi);
   double n_dot_wo = dot(n, wo);
   const bool lit = !__builtin_signbit(n_dot_wi) && !__builtin_signbit(n_dot_wo);
   const D3 one = mk(1, 1, 1);
-  double m2 = m.roughness * m.roughness;
+  double m2, m2pi;
+  D3 f0, omf0;
+  if constexpr (CONSTS) {
+    m2 = mc->m2; m2pi = mc->m2pi;
+    f0 = ld3(mc->f0); omf0 = ld3(mc->omf0);
+  } else {
+    m2 = m.roughness * m.roughness;
+    m2pi = m2 * PI;
+    double f0s = pow2((m.index - 1.0) / (m.index + 1.0));
+    f0 = lerp(mk(f0s, f0s, f0s), color, m.metallic);
+    omf0 = one - f0;
+  }
   D3 h = normalize(wi + wo); // (wi * 1.0 + wo in bsdf)
   double wo_dot_h = dot(wo, h);
   double n_dot_h = dot(n, h);
   double nh2 = pow2(n_dot_h);
-  double dd = rptc_exp((nh2 - 1.0) / (m2 * nh2)) / (m2 * PI * nh2 * nh2);
-  double f0s = pow2((m.index - 1.0) / (m.index + 1.0));
-  D3 f0 = lerp(mk(f0s, f0s, f0s), color, m.metallic);
-  D3 f = f0 + (one - f0) * pow5(1.0 - wo_dot_h);
+  double dd = rptc_exp((nh2 - 1.0) / (m2 * nh2)) / (m2pi * nh2 * nh2);
+  D3 f = f0 + omf0 * pow5(1.0 - wo_dot_h);
   double ga = n_dot_wi * n_dot_h, gb = n_dot_wo * n_dot_h;
   double g = fmin(ga, gb);
   g = (2.0 * g) / wo_dot_h;
@@ -578,8 +720,12 @@ RPT_DEV D3 bsdf_opaque(const Material& m, D3 n, D3 wo, D3 wi) { // material.rs:1
 }
 
 // sample_f() for an opaque material on the drawn values: both lobes' local vectors, the lane's one behind a select
-RPT_DEV void sample_f_opaque(const Material& m, D3 n, D3 wo, double f, const HitDraws& dr, D3& wi, double& pdf) {
-  double m2 = m.roughness * m.roughness; // material.rs:224-313
+template <bool CONSTS = false>
+RPT_DEV void sample_f_opaque(const Material& m, D3 n, D3 wo, double f, const HitDraws& dr, D3& wi, double& pdf,
+                             const MatConsts* mc = nullptr) {
+  double m2; // material.rs:224-313
+  if constexpr (CONSTS) m2 = mc->m2;
+  else m2 = m.roughness * m.roughness;
   const double u_theta = (double)(dr.th >> 11) * (1.0 / 9007199254740992.0);
   const double x = u52_of(dr.qa) * 2.0 + -1.0, y = u52_of(dr.qb) * 2.0 + -1.0;
   const double sum = x * x + y * y;
@@ -594,7 +740,14 @@ RPT_DEV void sample_f_opaque(const Material& m, D3 n, D3 wo, double f, const Hit
   double p = 0.0;
   {
     D3 h = normalize(wi + wo);
-    double p_h = beckmann_pdf(m2, n, h);
+    double p_h;
+    if constexpr (CONSTS) { // beckmann_pdf with its PI * m2 from the table (the product m2 * PI: the same number)
+      double cos_t = fabs(dot(h, n));
+      double sin_t = sqrt(1.0 - cos_t * cos_t);
+      p_h = (1.0 / (mc->m2pi * pow3(cos_t))) * rptc_exp(-pow2(sin_t / cos_t) / m2);
+    } else {
+      p_h = beckmann_pdf(m2, n, h);
+    }
     p += f * p_h / (4.0 * fabs(dot(h, wo)));
   }
   p += (1.0 - f) * fmax(dot(wi, n), 0.0) * FRAC_1_PI;
@@ -602,15 +755,22 @@ RPT_DEV void sample_f_opaque(const Material& m, D3 n, D3 wo, double f, const Hit
 }
 
 // illuminate() of an untransformed mesh light on the drawn values (light.rs:23-47, mesh.rs:84-98, kdtree.rs:138-143)
+// (CONSTS: Shape::sample's pdf of the drawn triangle, (1 / area) / num_prims, from the wave's table)
+template <bool CONSTS = false>
 RPT_DEV void illuminate_mesh(CLight& l, CTree& tr, const Tri* __restrict__ tp, D3 pos, const HitDraws& dr, D3& intensity,
-                             D3& wi, double& dist) {
+                             D3& wi, double& dist, const double* light_pdf = nullptr) {
   const double u = (double)(dr.a >> 11) * (1.0 / 9007199254740992.0), v = (double)(dr.b >> 11) * (1.0 / 9007199254740992.0);
   double w = 1.0 - u - v;
   D3 v1 = ld3(tp->v), v2 = ld3(tp->v + 3), v3 = ld3(tp->v + 6);
   D3 n1 = ld3(tp->v + 9), n2 = ld3(tp->v + 12), n3 = ld3(tp->v + 15);
-  double area = 0.5 * length(cross(v2 - v1, v3 - v1));
-  SampleOut s{u * v1 + v * v2 + w * v3, normalize(u * n1 + v * n2 + w * n3), 1.0 / area};
-  s.p = s.p / (double)tr.num_prims;
+  SampleOut s{u * v1 + v * v2 + w * v3, normalize(u * n1 + v * n2 + w * n3), 0.0};
+  if constexpr (CONSTS) {
+    s.p = light_pdf[dr.tri];
+  } else {
+    double area = 0.5 * length(cross(v2 - v1, v3 - v1));
+    s.p = 1.0 / area;
+    s.p = s.p / (double)tr.num_prims;
+  }
   D3 disp = s.v - pos;
   double len = length(disp);
   double cosine = fmax(-dot(disp, s.n), 0.0) / len;
@@ -765,7 +925,8 @@ RPT_DEV void end_path(const PersistArgs& pa, const Frame& fr, double* __restrict
   }
 }
 template <class LDS, bool PARK /* environment lookups parked per lane (pa.park_off) */,
-          bool FUSE = false /* a hit's shadow ray and bounce ray in one query (FUSE below) */>
+          bool FUSE = false /* a hit's shadow ray and bounce ray in one query (FUSE below) */,
+          bool CONSTS = false /* FUSE with a hit's scene constants in the wave's tables (SceneConsts above) */>
 __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame fr, Camera cam, PersistArgs pa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char flat_smem[]; // KdFlat only (dynamic size)
   __shared__ typename PathsLds<LDS>::type kd_store; // KdLds: the wave's traversal stack (15 KB); KdFlat: unused
@@ -808,6 +969,11 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         double* ob6 = reinterpret_cast<double*>(flat_smem + lay.off_obox) + 6u * ob;
         for (int k = 0; k < 6; k++) ob6[k] = in.bounds[k];
       }
+    }
+    if constexpr (CONSTS) {
+      static_assert(FUSE, "the tables serve the fused form");
+      scene_consts_fill(sc, sc.tris, l, flat_smem + lay.off_consts);
+      fl.consts = flat_smem + lay.off_consts;
     }
     __syncthreads();
     sc.lrec = l_lrec;
@@ -982,9 +1148,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
 #if RPT_PRETRACE_CULL
           const uint64_t skip = cull_skip_mask(pa.flat, near); // (wave-uniform; 0 without the host's rectangles: every test runs)
           PROF_COUNT(PF_P_PRETRACE);
-          const int ho = flat_query<false, true>(sc, &fl, so, sd, -INF, t, hn, skip);
+          const int ho = flat_query<false, true, CONSTS>(sc, &fl, so, sd, -INF, t, hn, skip);
 #else
-          const int ho = flat_query<false>(sc, &fl, so, sd, -INF, t, hn);
+          const int ho = flat_query<false, false, CONSTS>(sc, &fl, so, sd, -INF, t, hn);
 #endif
           n_ext++;
           if (ho < 0) hn = env_color(sc, sd); // renderer.rs:147
@@ -1077,22 +1243,30 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         CInst& li = cinst(sc, lg.inst);
         if (lg.kind == RPT_LIGHT_OBJECT && li.kind == RPT_SHAPE_MESH && !li.has_xf && __ballot(mat.transparent != 0) == 0ull) {
           CTree& tr = ctree(sc, li.tree);
-          const D3 mc = ld3(mat.color);
-          const double f0 = pow2((mat.index - 1.0) / (mat.index + 1.0)); // sample_f's lobe probability (material.rs)
-          const double mean = ((mc.x + mc.y) + mc.z) / 3.0;
-          double fs = (1.0 - mat.metallic) * f0 + mat.metallic * mean;
-          fs = fs * (1.0 - 0.2) + 1.0 * 0.2;
+          constexpr bool CM = CONSTS && SC_MAT, CL = CONSTS && SC_LIGHT;
+          const MatConsts* mcs = CM ? mat_consts_of(&fl, h_obj) : nullptr;
+          double fs;
+          if constexpr (CM) {
+            fs = mcs->fs;
+          } else {
+            const D3 mc = ld3(mat.color);
+            const double f0 = pow2((mat.index - 1.0) / (mat.index + 1.0)); // sample_f's lobe probability (material.rs)
+            const double mean = ((mc.x + mc.y) + mc.z) / 3.0;
+            fs = (1.0 - mat.metallic) * f0 + mat.metallic * mean;
+            fs = fs * (1.0 - 0.2) + 1.0 * 0.2;
+          }
           cont = depth < fr.max_bounces;
           HitDraws dr;
-          hit_draws(rng, cont, tr.num_prims, tr.sample_zone, fs, dr);
+          hit_draws<CM>(rng, cont, tr.num_prims, tr.sample_zone, fs, dr, mcs);
           n_sh++;
           PROF_PHASE(PF_P_DRAWS);
           D3 intensity;
-          illuminate_mesh(lg, tr, sc.tris + tr.prim_base + dr.tri, world_pos, dr, intensity, wl, dist);
+          illuminate_mesh<CL>(lg, tr, sc.tris + tr.prim_base + dr.tri, world_pos, dr, intensity, wl, dist,
+                              CL ? light_pdf_of(sc, &fl) : nullptr);
           double pdf;
-          sample_f_opaque(mat, nrm, wo, fs, dr, wi, pdf);
-          lt = mk(0, 0, 0) + cmul(bsdf_opaque(mat, nrm, wo, wl), intensity) * dot(wl, nrm);
-          const D3 f = bsdf_opaque(mat, nrm, wo, wi);
+          sample_f_opaque<CM>(mat, nrm, wo, fs, dr, wi, pdf, mcs);
+          lt = mk(0, 0, 0) + cmul(bsdf_opaque<CM>(mat, nrm, wo, wl, mcs), intensity) * dot(wl, nrm);
+          const D3 f = bsdf_opaque<CM>(mat, nrm, wo, wi, mcs);
           PROF_PHASE(PF_P_SHADE);
           if (cont) { // the record's f, 1/pdf and |wi.n| now, its A after the query
             uint32_t pos = (fold_st >> 16) + 1u + depth; // slot b is the path's header, b + 1 + k its level k
@@ -1136,7 +1310,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         D3 rnb = mk(0, 0, 0);
         const double t_stop = fmin(dist, 1.7976931348623157e308); // as in visible()
         d = wi; // (a path that ends here needs d no more: the incoming direction does not live across the query)
-        const int nobj = flat_query2(sc, &fl, world_pos, d, wl, t_stop, rtb, rnb, rts);
+        const int nobj = flat_query2<CONSTS>(sc, &fl, world_pos, d, wl, t_stop, rtb, rnb, rts);
         const bool vis = rts > t_stop; // (false for a NaN hit: see visible(), traversal.inc)
         PROF_PHASE(PF_P_FUSED);
         const D3 A = color + (vis ? lt : mk(0, 0, 0));
