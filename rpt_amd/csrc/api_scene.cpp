@@ -357,7 +357,7 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
           lay.fuse_query = 1;
           off = up16(off + qtab_bytes);
         }
-        // the fused kernel's tables of what a hit derives from the scene alone (kernels/paths.inc SceneConsts), behind the
+        // the fused kernel's tables of what a hit derives from the scene alone (kernels/paths_consts.inc SceneConsts), behind the
         // quotient tables — if the wave's share holds them too; a scene in which it does not keeps the kernel without them
         if (RPT_SCENE_CONSTS && lay.fuse_query) {
           // (as the kernel counts them: scene_consts_fill; RPT_SCENE_CONSTS is the mask of the groups that are built)
@@ -385,7 +385,7 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
         HIP_TRY(hipStreamSynchronize(h->stream)); // `planes` dies with this block
         lay.plane_vals = h->plane_vals.p;
         // the fused kernel's pre-trace pass skips, per wave, objects whose screen rectangle holds none of its pending
-        // pixels (kernels/paths.inc cull_skip_mask; the rectangles are the render's: api_render.cpp).  Never skipped: the
+        // pixels (kernels/paths_flat.inc cull_skip_mask; the rectangles are the render's: api_render.cpp).  Never skipped: the
         // plane table's users (their slab run is cheap) and what the object filter exempts (host_scene.cpp
         // fill_object_boxes: unbounded, not finite, sliver meshes, ill-conditioned placements)
         if (RPT_PRETRACE_CULL && lay.fuse_query && fs.obj_filter_ok) {

@@ -698,7 +698,7 @@ Box world_box(const ObjectGeom& g, const rptdev::Inst& in) {
   return in.has_xf ? transformed_box(g.local, in.fwd) : g.local;
 }
 
-// The fused flat kernel's pre-trace pass (kernels/paths.inc cull_skip_mask) leaves an object's exact test out for a wave
+// The fused flat kernel's pre-trace pass (kernels/paths_flat.inc cull_skip_mask) leaves an object's exact test out for a wave
 // none of whose pending camera rays belongs to a pixel of this rectangle.  Why that cannot change a result: the camera
 // ray of pixel (x, y) is eye + t (cam.d D + px R + py U), t > 0, with px = ((2x + 1) - width) / dim + dx and
 // py = ((2 (height - y) - 1) - height) / dim + dy, |dx|, |dy| <= 1 / dim (kernels/paths.inc camera_ray, renderer.rs:132-139;
@@ -745,7 +745,7 @@ bool pinhole_screen_rect(const Box& world, const rptdev::Camera& cam, uint32_t w
 }
 
 // The same filter one level up, for scenes that are a list of many small objects (every tree a single leaf: the flat
-// path kernel, kernels/paths.inc flat_query_filtered).  The reference tests every object of scene.objects against every
+// path kernel, kernels/paths_flat.inc flat_query_filtered).  The reference tests every object of scene.objects against every
 // ray (renderer.rs:211-220); an object's intersect can only accept a hit point that lies on the object, hence inside its
 // bounding_box (the triangles' boxes for a mesh, Transformed::bounding_box shape.rs:153-176 for a placed sphere / cube /
 // mesh), so a ray that does not cross that box — enlarged by a grid step, tested in f32 — inside [t_min, record.time]

@@ -51,7 +51,7 @@ struct ObjectGeom {
 
 // derived from the top-level objects' world boxes
 struct ObjectBounds {
-  // flat scenes' object filter (kernels/paths.inc flat_query_filtered): one conservative box per TOP-LEVEL object on a
+  // flat scenes' object filter (kernels/paths_flat.inc flat_query_filtered): one conservative box per TOP-LEVEL object on a
   // grid over all bounded ones; bit k of obj_always: object k is never filtered.  obj_filter_ok: every object is of a
   // kind the filtered walk handles (sphere, cube, plane, mesh) and there are at most 64 of them
   std::vector<rptdev::LeafBox> obj_lbox;

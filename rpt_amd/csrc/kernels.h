@@ -6,7 +6,7 @@
 #include "device_types.h"
 #include "launch_limits.h"
 
-// meshes per batched run of the flat path kernel (kernels/paths.inc flat_query; api_scene.cpp caps Inst::plane_use with it)
+// meshes per batched run of the flat path kernel (kernels/paths_flat.inc flat_query; api_scene.cpp caps Inst::plane_use with it)
 #ifndef RPT_FLAT_RUN
 #define RPT_FLAT_RUN 6
 #endif
@@ -21,13 +21,13 @@
 #define RPT_RAY_STASH 2
 #endif
 // RPT_FUSE_QUERY=1: rpt_paths<KdFlat, false, true> traces a hit's shadow ray and bounce ray in one two-ray query
-// (kernels/paths.inc flat_query2) for a flat scene with a plane table and exactly one light, a non-ambient one (C2);
+// (kernels/paths_flat.inc flat_query2) for a flat scene with a plane table and exactly one light, a non-ambient one (C2);
 // the host then keeps a second quotient table behind the first (FlatLayout::fuse_query).  0: the one-ray passes (A/B)
 #ifndef RPT_FUSE_QUERY
 #define RPT_FUSE_QUERY 1
 #endif
 // RPT_SHADE_SPLIT=1: in rpt_paths<KdFlat, false, true>, a wave whose light is an untransformed mesh and whose hits are
-// opaque takes every draw of its hits first and then shades them in one straight-line block (kernels/paths.inc
+// opaque takes every draw of its hits first and then shades them in one straight-line block (kernels/paths_shade.inc
 // hit_draws); 0: the sequence of illuminate, bsdf, sample_f and bsdf (A/B builds)
 #ifndef RPT_SHADE_SPLIT
 #define RPT_SHADE_SPLIT 1
@@ -35,7 +35,7 @@
 // RPT_PRETRACE_CULL=1: in rpt_paths<KdFlat, false, true> under a pinhole camera, the pass that pre-traces a refill's
 // camera rays skips, for the whole wave, the exact test of an object outside the plane table when none of the wave's
 // pending pixels lies inside the object's screen rectangle (host_scene.cpp pinhole_screen_rect, computed per render from
-// the camera: FlatLayout::cull_*; kernels/paths.inc flat_query<false, true>); 0: every object's test in every pass
+// the camera: FlatLayout::cull_*; kernels/paths_flat.inc flat_query<false, true>); 0: every object's test in every pass
 // (A/B builds).  RPT_CULL_MAX: objects that can carry a rectangle (the first ones that qualify; the others always run)
 #ifndef RPT_PRETRACE_CULL
 #define RPT_PRETRACE_CULL 1
@@ -44,7 +44,7 @@
 // RPT_SCENE_CONSTS=1: rpt_paths<KdFlat, false, true, true> reads what a hit's shading and the two-cube block derive from
 // the scene alone — per object the material's m2, m2 * PI, f0 and 1 - f0, sample_f's lobe probability and gen_bool's
 // integer; per triangle of the mesh light Shape::sample's pdf; per cube of a two-cube block its six world normals —
-// from tables that every wave fills once, in its prologue, with the loop's own expressions (kernels/paths.inc
+// from tables that every wave fills once, in its prologue, with the loop's own expressions (kernels/paths_consts.inc
 // SceneConsts; FlatLayout::scene_consts when the wave's LDS share holds them, else the kernel without them);
 // 0: every hit computes them, the parent's loop (A/B builds).  The value is a mask of the groups that are built:
 // 1 = the materials' constants, 2 = the light's pdfs, 4 = the cubes' normals.  The default leaves the light's pdfs out:
@@ -53,7 +53,7 @@
 #ifndef RPT_SCENE_CONSTS
 #define RPT_SCENE_CONSTS 5
 #endif
-#define RPT_MAT_CONSTS_BYTES 88u   // per object (kernels/paths.inc MatConsts)
+#define RPT_MAT_CONSTS_BYTES 88u   // per object (kernels/paths_consts.inc MatConsts)
 #define RPT_CUBE_NORMALS_BYTES 144u // per cube of a two-cube block: [face][3] doubles
 #define RPT_PATHS_STASH_LDS 4864u
 #define RPT_PATHS_STASH_HIT_LDS 6656u
@@ -85,7 +85,7 @@ struct FlatLayout {
   // by every mesh whose box uses that plane (the walls of C2 have 30 faces on 6 distinct planes)
   uint32_t off_qtab, plane_cnt;  // plane_cnt: 4 bits per axis; 0 = feature off
   const double* plane_vals;      // [3][4] in device memory
-  // the object filter of flat scenes with many objects and no plane table (kernels/paths.inc flat_query_filtered): a
+  // the object filter of flat scenes with many objects and no plane table (kernels/paths_flat.inc flat_query_filtered): a
   // conservative 16-bit box per top-level object on a grid over all of them, tested in f32 before the object's own
   // (exact) test; bit k of obj_always = object k is never filtered (a Plane, a mesh with a sliver, ...)
   uint32_t obj_filter;           // 0 = off
@@ -107,7 +107,7 @@ struct FlatLayout {
   // rpt_paths<KdFlat, false, true, true> (RPT_SCENE_CONSTS): the wave's tables of per-launch constants behind the quotient
   // tables (api_scene.cpp; kernels/launch.inc selects the kernel by scene_consts).  off_consts: [objects] MatConsts from
   // there on and [triangles of the light's mesh] doubles behind them; in front of it, back to front, [cubes in two-cube
-  // blocks, in object order][6][3] doubles (kernels/paths.inc FlatLds::consts)
+  // blocks, in object order][6][3] doubles (kernels/paths_consts.inc FlatLds::consts)
   uint32_t scene_consts, off_consts;
 };
 

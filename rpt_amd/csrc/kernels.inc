@@ -11,8 +11,13 @@
 //   sampling.inc   Shape::sample, Transformed::sample
 //   material.inc   Material::bsdf / sample_f (material.rs:125-313)
 //   light.inc      Light::illuminate (light.rs:23-47), Environment / Hdri (environment.rs:25-52)
-//   paths.inc      the DEFAULT pipeline for scenes without deep trees: one persistent kernel,
-//                  rpt_paths<KdLds | KdFlat>, the whole path in registers (renderer.rs:117-174)
+//   paths*.inc     the DEFAULT pipeline for scenes without deep trees: one persistent kernel,
+//                  rpt_paths<KdLds | KdFlat>, the whole path in registers (renderer.rs:117-174), in four files:
+//     paths_consts.inc  what a flat scene keeps in the wave's LDS (FlatLds) and the tables of a hit's scene constants
+//     paths_flat.inc    the flat scenes' queries: flat_query, flat_query2 (two rays in one walk), flat_query_filtered
+//     paths_shade.inc   the fused form's draw-first shading: hit_draws, bsdf_opaque, sample_f_opaque, illuminate_mesh
+//     paths.inc         the kernel's contract, work hand-out, record ring, parked lookups, ray stash, the loop itself;
+//                       rpt_sum_samples
 //   wavefront.inc  the pipeline for scenes with deep trees: rpt_raygen / rpt_extend / rpt_shade /
 //                  rpt_shadow / rpt_resolve / rpt_finish over SoA path state, and the per-tree query
 //                  kernels (rpt_rays_init, rpt_tree_enter, rpt_tree_trace, rpt_nest_trace, rpt_tree_generic — the one that
@@ -81,6 +86,9 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/material.inc"
 #include "kernels/light.inc"
 #include "kernels/wavefront.inc"
+#include "kernels/paths_consts.inc"
+#include "kernels/paths_flat.inc"
+#include "kernels/paths_shade.inc"
 #include "kernels/paths.inc"
 #include "kernels/buffer.inc"
 #include "kernels/aov.inc"

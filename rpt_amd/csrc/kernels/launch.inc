@@ -62,26 +62,30 @@ void launch_scatter_f32(hipStream_t st, const float* src, const uint32_t* pixels
 }
 
 static uint32_t paths_park_off(uint32_t lds_bytes) { return (lds_bytes + 15u) & ~15u; }
+// THE choice of rpt_paths' instantiation (occupancy is asked of, and the launch goes to, what this returns).  flat = null:
+// rpt_paths<KdLds>, which never parks (its stack fills the wave's LDS) — callers clear `park` for it.
+static const void* paths_kernel(const FlatLayout* flat, bool park) {
+#define RPT_PK(L) (park ? (const void*)rpt_paths<L, true> : (const void*)rpt_paths<L, false>)
+  if (!flat) return (const void*)rpt_paths<KdLds, false>;
+  if (flat->obj_filter) return RPT_PK(KdFlatF);
+#if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
+  // one light that casts shadow rays (the host doubled the quotient table for it): the two-ray form (kernels/paths.inc
+  // FUSE), with a hit's scene constants in the wave's tables where the host found room for them
+  if (flat->n_tris && flat->fuse_query && !park) {
+#if RPT_SCENE_CONSTS
+    if (flat->scene_consts) return (const void*)rpt_paths<KdFlat, false, true, true>;
+#endif
+    return (const void*)rpt_paths<KdFlat, false, true>;
+  }
+#endif
+  return flat->n_tris ? RPT_PK(KdFlat) : RPT_PK(KdFlatG);
+#undef RPT_PK
+}
 int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool park) {
   if (!flat) park = false;
   if (park) lds_bytes = paths_park_off(lds_bytes) + RPT_PATHS_PARK_LDS;
   int nb = 0; // per instantiation: their static LDS differs (rpt_paths<KdFlat> stashes camera rays)
-  hipError_t e;
-#define RPT_OCC(L) (park ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<L, true>, 64, lds_bytes) \
-                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<L, false>, 64, lds_bytes))
-  if (flat && flat->obj_filter) e = RPT_OCC(KdFlatF);
-#if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
-#if RPT_SCENE_CONSTS
-  else if (flat && flat->n_tris && flat->fuse_query && !park && flat->scene_consts)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<KdFlat, false, true, true>, 64, lds_bytes);
-#endif
-  else if (flat && flat->n_tris && flat->fuse_query && !park)
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<KdFlat, false, true>, 64, lds_bytes);
-#endif
-  else if (flat && flat->n_tris) e = RPT_OCC(KdFlat);
-  else if (flat) e = RPT_OCC(KdFlatG);
-  else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, rpt_paths<KdLds, false>, 64, lds_bytes); // (never parks: its stack fills the wave's LDS)
-#undef RPT_OCC
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, paths_kernel(flat, park), 64, lds_bytes);
   if (e != hipSuccess || nb <= 0) nb = 8;
   return nb;
 }
@@ -97,23 +101,8 @@ void launch_paths(hipStream_t st, const Scene& sc, const Frame& fr, const Camera
   PersistArgs pa{work_counter, rec, ray_counters, lbuf, spp, chunk, n_items, nblocks * 64u, rpt_fold_ring_slots(fr.max_bounces),
                  batch, park ? paths_park_off(lds_bytes) : 0xffffffffu, lay};
   if (park) lds_bytes = paths_park_off(lds_bytes) + RPT_PATHS_PARK_LDS;
-#define RPT_GO(L) do { if (park) hipLaunchKernelGGL((rpt_paths<L, true>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa); \
-                       else hipLaunchKernelGGL((rpt_paths<L, false>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa); } while (0)
-  if (flat && lay.obj_filter) RPT_GO(KdFlatF);
-#if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
-  // one light that casts shadow rays (the host doubled the quotient table for it): the two-ray form (kernels/paths.inc),
-  // with a hit's scene constants in the wave's tables where the host found room for them
-#if RPT_SCENE_CONSTS
-  else if (flat && lay.n_tris && lay.fuse_query && !park && lay.scene_consts)
-    hipLaunchKernelGGL((rpt_paths<KdFlat, false, true, true>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa);
-#endif
-  else if (flat && lay.n_tris && lay.fuse_query && !park)
-    hipLaunchKernelGGL((rpt_paths<KdFlat, false, true>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa);
-#endif
-  else if (flat && lay.n_tris) RPT_GO(KdFlat);
-  else if (flat) RPT_GO(KdFlatG);
-  else hipLaunchKernelGGL((rpt_paths<KdLds, false>), dim3(nblocks), dim3(64), lds_bytes, st, sc, fr, cam, pa);
-#undef RPT_GO
+  void* args[] = {(void*)&sc, (void*)&fr, (void*)&cam, (void*)&pa}; // rpt_paths(Scene, Frame, Camera, PersistArgs)
+  (void)hipLaunchKernel(paths_kernel(flat ? &lay : nullptr, park), dim3(nblocks), dim3(64), args, lds_bytes, st);
 }
 void launch_sum_samples(hipStream_t st, const Frame& fr, const double* lbuf, uint32_t spp, bool first) {
   hipLaunchKernelGGL(rpt_sum_samples, grid_for(fr.npix), dim3(256), 0, st, fr, lbuf, spp, first ? 1 : 0);

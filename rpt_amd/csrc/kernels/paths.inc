@@ -1,4 +1,5 @@
-// kernels/paths.inc — the persistent path kernel rpt_paths<KdLds|KdFlat>, flat_query, rpt_sum_samples.
+// kernels/paths.inc — the persistent path kernel rpt_paths<KdLds|KdFlat>: contract, work hand-out, record ring, parked lookups,
+// ray stash, the loop; rpt_sum_samples.  (Its flat-scene queries, tables and fast shading: paths_flat / _consts / _shade.inc.)
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
 
 // ------------------------------------------------------------------ persistent path kernel
@@ -86,701 +87,6 @@ struct PersistArgs {
 #ifndef RPT_PATHS_WAVES
 #define RPT_PATHS_WAVES 2
 #endif
-// What a flat scene keeps in LDS instead of a traversal stack: its intersection records, triangles, leaf
-// entries and per-object materials (every tree has fewer than 16 primitives), read with ds_read at LDS
-// latency instead of through L1/L2, which the clamp records keep flushing — and, in what is left of the
-// wave's 20 KB stays free (rounds 2-3 kept clamp records there; the fold walker's records live in global memory).
-// (the layout of the wave's dynamic LDS, FlatLayout, is computed on the host: kernels.h, api_scene.cpp)
-struct FlatLds {
-  const TriX* lrec;
-  const Tri* tris;
-  const uint32_t* refs;
-  const Material* obj_mat;           // the material OF object i (not the scene's material table)
-  const uint32_t (*obj_leaf)[4];     // MESH objects: ref_base, prim_base, first entry, entry count of the one leaf
-  double* qtab;                      // [slots][64 lanes]: this ray's quotients (value - o) / d of the shared planes, the x
-                                     // planes' first, then y, then z (as many slots as there are distinct planes)
-  const double* plane_vals;          // [3][4] distinct plane coordinates (device memory, read through s_load)
-  uint32_t plane_cnt;                // 4 bits per axis; 0 = no table
-  // object filter (rpt_paths<KdFlatF>, flat_query_filtered): there obj_leaf[i][3] also carries kind << 8 | has_xf << 16
-  const double* obox;                // [objects][6]: bounds of MESH objects
-  const LeafBox* obj_box;            // [objects] conservative boxes (device memory, read through s_load)
-  const double* obj_grid;            // qlo[3], qscale[3], bounds[6] (device memory, s_load)
-  uint64_t obj_always;
-  // rpt_paths<KdFlat, false, true, true>: what a hit derives from the scene alone, once per wave (SceneConsts below)
-  // — ONE address for the three tables (each one more that the loop keeps costs the kernel scalar registers it has to
-  // spill): [objects] MatConsts from it on, behind them [triangles of the light's mesh] doubles, and in front of it, back
-  // to front, [cubes in two-cube blocks, in object order][face][3] doubles (mat_consts_of, light_pdf_of, cube_nrm_of)
-  const unsigned char* consts;
-};
-// ------------------------------------------------------------------ a hit's scene constants, once per wave
-// SceneConsts (rpt_paths<KdFlat, false, true, true>, RPT_SCENE_CONSTS): the straight-line code of a hit computes values
-// that depend on the material, the light's triangle or the cube alone — fixed for the whole launch.  Every wave computes
-// them once, in its prologue (scene_consts_fill), with the loop's own expressions on the same operands in the same order,
-// so the bits are the loop's; it reads the scene's records from device memory as they stand at the launch, so a live
-// update needs nothing more.  Lane `ob` does object `ob`, lane `k` triangle `k` of the light's mesh, lanes 0-11 the
-// faces of a two-cube block.  (FlatLds::consts says where the three tables lie.)
-// The three groups can be built one by one (A/B builds): RPT_SCENE_CONSTS is a mask, 1 = the materials' constants,
-// 2 = the light's pdfs, 4 = the cubes' normals (kernels.h says which ones the default builds, and why).
-constexpr bool SC_MAT = (RPT_SCENE_CONSTS & 1) != 0, SC_LIGHT = (RPT_SCENE_CONSTS & 2) != 0, SC_CUBE = (RPT_SCENE_CONSTS & 4) != 0;
-struct MatConsts {   // of the material of an object (bsdf_opaque, sample_f_opaque and the kernel's lobe probability)
-  double m2, m2pi;   // roughness^2; m2 * PI (bsdf's Beckmann denominator m2 * PI * nh2 * nh2; beckmann_pdf's PI * m2)
-  double f0s;        // pow2((index - 1) / (index + 1))
-  double f0[3];      // lerp((f0s, f0s, f0s), color, metallic)
-  double omf0[3];    // (1, 1, 1) - f0
-  double fs;         // sample_f's lobe probability
-  uint64_t p_int;    // gen_bool(fs)'s threshold (unused when fs == 1.0: gen_bool then takes no draw)
-};
-static_assert(sizeof(MatConsts) == RPT_MAT_CONSTS_BYTES, "kernels.h sizes the wave's LDS budget with it");
-// a face of the unit cube as cube_candidate names its normals: 2 * axis + (1 if the normal points down the axis)
-RPT_DEV D3 cube_face_normal(uint32_t face) {
-  const double s = (face & 1u) ? -1.0 : 1.0;
-  const uint32_t axis = face >> 1;
-  return mk(axis == 0u ? s : 0.0, axis == 1u ? s : 0.0, axis == 2u ? s : 0.0);
-}
-RPT_DEV const MatConsts* mat_consts_of(const FlatLds* fl, int obj) { return reinterpret_cast<const MatConsts*>(fl->consts) + obj; }
-RPT_DEV const double* light_pdf_of(const Scene& sc, const FlatLds* fl) {
-  return reinterpret_cast<const double*>(fl->consts + (SC_MAT ? (uint32_t)sc.num_objects : 0u) * (uint32_t)sizeof(MatConsts));
-}
-RPT_DEV D3 cube_nrm_of(const FlatLds* fl, uint32_t slot, uint32_t face) { // cube `slot` sits slot + 1 cubes in front of fl->consts
-  return ld3(reinterpret_cast<const double*>(fl->consts) - (slot + 1u) * 18u + face * 3u);
-}
-RPT_DEV bool xf_cube_pair(const Scene& sc, int i) { // flat_query's condition for its two-cube block
-  return cinst(sc, i).kind == RPT_SHAPE_CUBE && cinst(sc, i).has_xf && i + 1 < sc.num_objects &&
-         cinst(sc, i + 1).kind == RPT_SHAPE_CUBE && cinst(sc, i + 1).has_xf;
-}
-// the prologue's part (all 64 lanes, before the barrier; `tris` = the scene's triangles in device memory)
-RPT_DEV void scene_consts_fill(const Scene& sc, const Tri* __restrict__ tris, uint32_t l, unsigned char* consts) {
-  MatConsts* mc = reinterpret_cast<MatConsts*>(consts);
-  double* light_pdf = reinterpret_cast<double*>(consts + (SC_MAT ? (uint32_t)sc.num_objects : 0u) * (uint32_t)sizeof(MatConsts));
-  for (uint32_t ob = l; SC_MAT && ob < (uint32_t)sc.num_objects; ob += 64) {
-    const Material& mat = sc.materials[sc.insts[ob].material];
-    MatConsts c;
-    const D3 color = ld3(mat.color);
-    const D3 one = mk(1, 1, 1);
-    c.m2 = mat.roughness * mat.roughness;
-    c.m2pi = c.m2 * PI;
-    c.f0s = pow2((mat.index - 1.0) / (mat.index + 1.0));
-    const D3 f0 = lerp(mk(c.f0s, c.f0s, c.f0s), color, mat.metallic);
-    const D3 omf0 = one - f0;
-    c.f0[0] = f0.x; c.f0[1] = f0.y; c.f0[2] = f0.z;
-    c.omf0[0] = omf0.x; c.omf0[1] = omf0.y; c.omf0[2] = omf0.z;
-    const double mean = ((color.x + color.y) + color.z) / 3.0;
-    double fs = (1.0 - mat.metallic) * c.f0s + mat.metallic * mean;
-    fs = fs * (1.0 - 0.2) + 1.0 * 0.2;
-    c.fs = fs;
-    c.p_int = (uint64_t)(fs * 18446744073709551616.0);
-    mc[ob] = c;
-  }
-  CLight& lg = clight(sc, 0);
-  CInst& li = cinst(sc, lg.inst);
-  if (SC_LIGHT && lg.kind == RPT_LIGHT_OBJECT && li.kind == RPT_SHAPE_MESH && !li.has_xf) { // illuminate_mesh's light
-    CTree& tr = ctree(sc, li.tree);
-    for (uint32_t k = l; k < tr.num_prims; k += 64) {
-      const Tri* tp = tris + tr.prim_base + k;
-      const D3 v1 = ld3(tp->v), v2 = ld3(tp->v + 3), v3 = ld3(tp->v + 6);
-      const double area = 0.5 * length(cross(v2 - v1, v3 - v1));
-      double p = 1.0 / area;
-      p = p / (double)tr.num_prims;
-      light_pdf[k] = p;
-    }
-  }
-  uint32_t slot = 0;
-  for (int i = 0; SC_CUBE && i < sc.num_objects;) { // the two-cube blocks in the order flat_query meets them
-    if (!xf_cube_pair(sc, i)) { i++; continue; }
-    if (l < 12u) {
-      const uint32_t c = l / 6u, face = l - 6u * c;
-      const D3 w = normalize(mat3_mul(sc.insts[i + (int)c].nrm, cube_face_normal(face))); // Transformed::intersect shape.rs:131-132
-      double* q = reinterpret_cast<double*>(consts) - (slot + c + 1u) * 18u + face * 3u;
-      q[0] = w.x; q[1] = w.y; q[2] = w.z;
-    }
-    slot += 2u;
-    i += 2;
-  }
-}
-// cube_candidate (shapes.inc) with the candidate's normal as its face (cube_face_normal): the same tests in the same order
-RPT_DEV bool cube_candidate_face(D3 o, const RcpD& rdx, const RcpD& rdy, const RcpD& rdz, double t_min, double& time,
-                                 uint32_t& face) {
-  double x1, x2, y1, y2, z1, z2;
-  uint32_t fx = 1u, fy = 3u, fz = 5u; // the ENTRY face along each axis: the normal -1 unless the interval was swapped
-  div6(-0.5 - o.x, 0.5 - o.x, rdx, -0.5 - o.y, 0.5 - o.y, rdy, -0.5 - o.z, 0.5 - o.z, rdz, x1, x2, y1, y2, z1, z2);
-  if (x1 > x2) { double t = x1; x1 = x2; x2 = t; fx = 0u; }
-  if (y1 > y2) { double t = y1; y1 = y2; y2 = t; fy = 2u; }
-  if (z1 > z2) { double t = z1; z1 = z2; z2 = t; fz = 4u; }
-  double start, end;
-  uint32_t sf, ef; // the exit face is the opposite one of the same axis
-  if (x1 > y1 && x1 > z1) { start = x1; sf = fx; }
-  else if (y1 > z1) { start = y1; sf = fy; }
-  else { start = z1; sf = fz; }
-  if (x2 < y2 && x2 < z2) { end = x2; ef = fx ^ 1u; }
-  else if (y2 < z2) { end = y2; ef = fy ^ 1u; }
-  else { end = z2; ef = fz ^ 1u; }
-  if (start > end || end < t_min) return false;
-  if (start < t_min) { time = end; face = ef; }
-  else { time = start; face = sf; }
-  return true;
-}
-// ------------------------------------------------------------------ flat scenes: batched quad tests
-// Renderer::get_closest_hit / the visibility query for a scene whose trees are all single leaves.  The
-// reference tests the objects one after the other; for a run of consecutive untransformed meshes (the
-// five walls of C2) that means five sparsely populated leaf tests per ray, because a ray inside the box
-// passes the (flat) slab of about one wall.  Here the run is handled in two steps with the same outcome:
-//  1. the root slab test of every mesh of the run (uniform, all lanes busy): candidate bit k is set
-//     unless  m_k = max(b_min, t_min) > min(b_max, rt)  (kdtree.rs:130-134) with rt as it is at the
-//     start of the run;
-//  2. each lane walks ITS candidates in object order and runs the leaf test on its own object (the
-//     records sit in LDS, so per-lane addresses cost nothing).  rt can only have decreased since step
-//     1, and for rt' <= rt the reference's condition  m_k > min(b_max, rt')  is  m_k > rt'  whenever
-//     the step-1 test passed (then m_k <= b_max), so re-checking  m_k > rt  before the leaf test
-//     reproduces the reference's decision exactly — every accept happens in the reference's order.
-struct LaneTree {
-  uint32_t ref_base, prim_base;
-};
-constexpr int FLAT_RUN = RPT_FLAT_RUN; // kernels.h: the host caps run lengths with the same constant
-
-// slab tests of a run of N table users starting at object i (N known at compile time: branch-free, interleaved)
-template <int N>
-RPT_DEV uint32_t run_slabs(const Scene& sc, int i, const double* qt, double rt, double (&m)[FLAT_RUN]) {
-  static_assert(N >= 1 && N <= FLAT_RUN, "run length");
-  uint32_t cand = 0;
-#pragma unroll
-  for (int k = 0; k < FLAT_RUN; k++) m[k] = 0.0;
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    const uint32_t ix = cinst(sc, i + k).plane_idx;
-    double fax = qt[((ix >> 0) & 15u) * 64u], fbx = qt[((ix >> 4) & 15u) * 64u];
-    double fay = qt[((ix >> 8) & 15u) * 64u], fby = qt[((ix >> 12) & 15u) * 64u];
-    double faz = qt[((ix >> 16) & 15u) * 64u], fbz = qt[((ix >> 20) & 15u) * 64u];
-    double b_min = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-    double b_max = fmin(fmin(fmax(fax, fbx), fmax(fay, fby)), fmax(faz, fbz));
-    double mm = fmax(b_min, EPSILON);
-    if (!(mm > fmin(b_max, rt))) cand |= 1u << k;
-    m[k] = mm;
-  }
-  return cand;
-}
-
-// ------------------------------------------------------------------ flat scenes with many objects: the object filter
-// A room of 23 polygons, three cubes and three spheres: the reference runs 29 object tests per ray (renderer.rs:211-220),
-// 23 of them a root slab test of six divisions, and a ray passes the box of three or four.  Here every ray is first
-// tested against a conservative 16-bit box of every object, in f32, in one uniform loop (host_scene.cpp
-// fill_object_boxes says why an object whose box the ray misses inside [t_min, record.time] cannot be hit: its test is
-// skipped with nothing changed); then each lane walks ITS candidates in object order and runs the object's own, exact
-// test — the slab test and the leaf of a mesh (kdtree.rs:129-136, 162-171), Transformed<Sphere | Cube | Plane>
-// (shape.rs:128-137) — with the record as it stands, exactly like the reference.  The window is the one at the start
-// of the query (record.time only shrinks: a later, narrower window would reject more, never less).
-struct ObjGrid {
-  double qlo[3], qscale[3];
-};
-template <bool SHADOW>
-RPT_DEV int flat_query_filtered(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_stop, double& rt, D3& rn) {
-  int obj = -1;
-  const int n = sc.num_objects;
-  RcpD rwx = rcp_make(d.x), rwy = rcp_make(d.y), rwz = rcp_make(d.z);
-  uint64_t cand = n >= 64 ? ~0ull : (1ull << n) - 1ull;
-  {
-    const double RPT_C* g = (const double RPT_C*)fl->obj_grid;
-    ObjGrid gr;
-    for (int k = 0; k < 3; k++) { gr.qlo[k] = g[k]; gr.qscale[k] = g[3 + k]; }
-    double fax, fbx, fay, fby, faz, fbz; // where the ray enters the bounds of the grid: the filter counts from there
-    div6(g[6] - o.x, g[9] - o.x, rwx, g[7] - o.y, g[10] - o.y, rwy, g[8] - o.z, g[11] - o.z, rwz, fax, fbx, fay, fby, faz, fbz);
-    const double b_min = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-    const BoxRay br = boxray_make<true>(gr, o, d, fmax(b_min, 0.0));
-    if (br.on) {
-      float wl, wh;
-      box_window(br, EPSILON, SHADOW ? fmin(rt, t_stop) : rt, wl, wh);
-      const LeafBox RPT_C* bx = (const LeafBox RPT_C*)fl->obj_box;
-      uint64_t pass = fl->obj_always;
-      for (int k = 0; k < n; k++) {
-        LeafBox lb;
-        lb.w[0] = bx[k].w[0]; lb.w[1] = bx[k].w[1]; lb.w[2] = bx[k].w[2]; lb.w[3] = 0u;
-        pass |= (leaf_box_pass(lb, br, wl, wh) ? 1ull : 0ull) << k;
-      }
-      cand &= pass;
-    }
-  }
-  while (__ballot(cand != 0ull) != 0ull) {
-    if (cand != 0ull) {
-      PROF_COUNT(PF_P_CAND);
-      const int k = __ffsll((long long)cand) - 1;
-      cand &= cand - 1ull;
-      const uint32_t* e = fl->obj_leaf[k];
-      const uint32_t kind = (e[3] >> 8) & 0xffu;
-      const bool has_xf = ((e[3] >> 16) & 1u) != 0u;
-      const Inst* __restrict__ in = sc.insts + k;
-      bool h = false;
-      if (kind == RPT_SHAPE_MESH) { // KdTree::intersect of a single-leaf tree: root slab, then the leaf
-        D3 lo = o, ld = d;
-        RcpD rx = rwx, ry = rwy, rz = rwz;
-        if (has_xf) {
-          lo = mat4_mul(in->inv, o, 1.0);
-          ld = mat4_mul(in->inv, d, 0.0);
-          rx = rcp_make(ld.x); ry = rcp_make(ld.y); rz = rcp_make(ld.z);
-        }
-        const double* bb = fl->obox + 6 * k;
-        double fax, fbx, fay, fby, faz, fbz;
-        div6(bb[0] - lo.x, bb[3] - lo.x, rx, bb[1] - lo.y, bb[4] - lo.y, ry, bb[2] - lo.z, bb[5] - lo.z, rz, fax, fbx, fay, fby, faz, fbz);
-        const double b_min = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-        const double b_max = fmin(fmin(fmax(fax, fbx), fmax(fay, fby)), fmax(faz, fbz));
-        if (!(fmax(b_min, EPSILON) > fmin(b_max, rt))) { // kdtree.rs:130-134
-          LaneTree lt{e[0], e[1]};
-          KdNode nd;
-          nd.split = 0.0; nd.a = e[2]; nd.ib = ((e[3] & 0xffu) << 2) | 3u;
-          D3 nn = rn;
-          h = kd_leaf<true, SHADOW>(sc, lt, sc.refs + lt.ref_base, nd, lo, ld, EPSILON, t_stop, rt, nn);
-          if (h) rn = (!SHADOW && has_xf) ? normalize(mat3_mul(in->nrm, nn)) : nn; // shape.rs:131-132
-        }
-      } else if (kind == RPT_SHAPE_PLANE) {
-        D3 lo = o, ld = d;
-        if (has_xf) {
-          lo = mat4_mul(in->inv, o, 1.0);
-          ld = mat4_mul(in->inv, d, 0.0);
-        }
-        h = isect_plane(in->plane, lo, ld, EPSILON, rt, rn, !SHADOW);
-        if (!SHADOW && h && has_xf) rn = normalize(mat3_mul(in->nrm, rn));
-      } else { // sphere, cube
-        const ChildM c = ld_child(in);
-        h = isect_child(c, in, o, d, EPSILON, rt, rn, !SHADOW);
-      }
-      if (h) obj = k;
-      if (SHADOW && rt <= t_stop) cand = 0ull;
-    }
-  }
-  return obj;
-}
-
-#if RPT_PRETRACE_CULL
-// ------------------------------------------------------------------ the pre-trace pass: objects no pending ray can hit
-// The camera rays a refill pre-traces are the one coherent set of rays in rpt_paths<KdFlat, false, true>: the lanes of a
-// wave hold neighbouring pixels of a tile, and most waves' rays pass nowhere near the two cubes of C2 — yet the cube
-// block of flat_query is straight-line code that every pass runs for all of its lanes.  Under a pinhole camera the host
-// hands the kernel, per render, the screen rectangle of each object outside the plane table (host_scene.cpp
-// pinhole_screen_rect says why a camera ray of a pixel outside the rectangle cannot be accepted by the object's exact
-// test).  A lane notes at ray generation which rectangles hold its pixel (cull_near: two packed 16-bit operations; bit j =
-// rectangle j), and the pre-trace pass skips, for the whole wave, an object whose rectangle holds no pending lane's
-// pixel (cull_skip_mask, wave-uniform: bit k = object k).  flat_query<false, true> leaves such an object's test out,
-// which changes nothing: none of the wave's tests of it would have accepted.  A lane inside a test that runs is not
-// masked: the exact test decides, as before.  (The object filter's f32 boxes, tested per pending ray in the pass, were
-// built first: bit-equal, two thirds of the passes skipped the cubes, and 0.9 % slower — profiles/pretrace_cull_ab.txt.)
-typedef unsigned short US2 __attribute__((ext_vector_type(2)));
-RPT_DEV uint32_t cull_near(const FlatLayout& lay, uint32_t pix, uint32_t width) {
-  const uint32_t y = pix / width, x = pix - y * width; // (camera_ray's own quotient)
-  const US2 xy = {(unsigned short)x, (unsigned short)y};
-  uint32_t near = 0u;
-  for (uint32_t j = 0; j < lay.cull_n; j++) { // (wave-uniform) inside: (x - x0, y - y0) <= (x1 - x0, y1 - y0), both halves at once
-    const US2 t = xy - __builtin_bit_cast(US2, lay.cull_lo[j]);
-    const US2 m = __builtin_elementwise_min(t, __builtin_bit_cast(US2, lay.cull_ext[j]));
-    near |= (__builtin_bit_cast(uint32_t, m) == __builtin_bit_cast(uint32_t, t) ? 1u : 0u) << j;
-  }
-  return near;
-}
-// among the lanes that call (the pending ones): the objects whose rectangle holds none of their pixels
-RPT_DEV uint64_t cull_skip_mask(const FlatLayout& lay, uint32_t near) {
-  uint64_t skip = 0ull;
-  for (uint32_t j = 0; j < lay.cull_n; j++) // (wave-uniform)
-    if (__ballot(((near >> j) & 1u) != 0u) == 0ull) skip |= 1ull << (lay.cull_obj[j] & 63u);
-  return skip;
-}
-#endif
-
-// CULL (the pre-trace pass of rpt_paths<KdFlat, false, true>, RPT_PRETRACE_CULL): bit k of the wave-uniform `skip` = no
-// ray of the wave can be accepted by object k (cull_skip_mask), its test is left out
-// CONSTS (rpt_paths<KdFlat, false, true, true>): the two-cube block takes an accepted cube's world normal from the
-// wave's table (SceneConsts above)
-template <bool SHADOW, bool CULL = false, bool CONSTS = false>
-RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_stop, double& rt, D3& rn, uint64_t skip = 0ull) {
-  int obj = -1;
-  uint32_t cslot = 0; // CONSTS: the next two-cube block's first cube in the table of normals (cube_nrm_of)
-  RcpD rwx = rcp_make(d.x), rwy = rcp_make(d.y), rwz = rcp_make(d.z);
-  const int n = sc.num_objects;
-  const uint32_t lane = __lane_id();
-  if (fl->plane_cnt) { // every distinct (plane - o) / d once per ray: the operands, hence the bits, of the per-object form
-    const double RPT_C* pv = (const double RPT_C*)fl->plane_vals;
-    const uint32_t nx = fl->plane_cnt & 15u, ny = (fl->plane_cnt >> 4) & 15u, nz = (fl->plane_cnt >> 8) & 15u;
-    for (uint32_t j = 0; j < nx; j++) fl->qtab[j * 64u + lane] = (pv[j] - o.x) / d.x;
-    for (uint32_t j = 0; j < ny; j++) fl->qtab[(nx + j) * 64u + lane] = (pv[4u + j] - o.y) / d.y;
-    for (uint32_t j = 0; j < nz; j++) fl->qtab[(nx + ny + j) * 64u + lane] = (pv[8u + j] - o.z) / d.z;
-  }
-  int i = 0;
-  while (i < n) {
-    CInst& in = cinst(sc, i);
-    if (in.kind == RPT_SHAPE_MESH && !in.has_xf) {
-      uint32_t cand = 0;
-      double m[FLAT_RUN];
-      int len = 0;
-      if (in.plane_use) {
-        // run of `len` table users, known on the host: one straight-line block for all of them (a slot beyond the
-        // run repeats its last object and is masked out), so the six slab evaluations interleave instead of
-        // forming six dependent chains separated by branches
-        len = (int)in.plane_use;
-        const double* qt = fl->qtab + lane;
-        switch (len) { // one straight-line block per run length: no slot is evaluated in vain
-          case 1: cand = run_slabs<1>(sc, i, qt, rt, m); break;
-          case 2: cand = run_slabs<2>(sc, i, qt, rt, m); break;
-          case 3: cand = run_slabs<3>(sc, i, qt, rt, m); break;
-          case 4: cand = run_slabs<4>(sc, i, qt, rt, m); break;
-          case 5: cand = run_slabs<5>(sc, i, qt, rt, m); break;
-          default: cand = run_slabs<FLAT_RUN>(sc, i, qt, rt, m); break;
-        }
-      } else { // no plane table (more than four distinct plane coordinates on some axis): discover the run here
-#pragma unroll
-      for (int k = 0; k < FLAT_RUN; k++) {
-        m[k] = 0.0;
-        if (len == k && i + k < n) { // the run is still growing
-          CInst& q = cinst(sc, i + k);
-          if (q.kind == RPT_SHAPE_MESH && !q.has_xf) {
-            double fax, fbx, fay, fby, faz, fbz; // q.bounds == trees[q.tree].bounds (kdtree.rs:103)
-            div6(q.bounds[0] - o.x, q.bounds[3] - o.x, rwx, q.bounds[1] - o.y, q.bounds[4] - o.y, rwy,
-                 q.bounds[2] - o.z, q.bounds[5] - o.z, rwz, fax, fbx, fay, fby, faz, fbz);
-            double b_min = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-            double b_max = fmin(fmin(fmax(fax, fbx), fmax(fay, fby)), fmax(faz, fbz));
-            double mm = fmax(b_min, EPSILON);
-            if (!(mm > fmin(b_max, rt))) cand |= 1u << k;
-            m[k] = mm;
-            len = k + 1;
-          }
-        }
-      }
-      }
-      while (__ballot(cand != 0u) != 0ull) {
-        if (cand != 0u) {
-          PROF_COUNT(PF_P_CAND);
-          int k = __ffs((int)cand) - 1;
-          cand &= cand - 1u;
-          double mk = m[0];
-#pragma unroll
-          for (int kk = 1; kk < FLAT_RUN; kk++) mk = k == kk ? m[kk] : mk;
-          if (!(mk > rt)) {
-            const uint32_t* e = fl->obj_leaf[i + k];
-            LaneTree lt{e[0], e[1]};
-            KdNode nd;
-            nd.split = 0.0; nd.a = e[2]; nd.ib = (e[3] << 2) | 3u;
-            bool h = kd_leaf<true, SHADOW>(sc, lt, sc.refs + lt.ref_base, nd, o, d, EPSILON, t_stop, rt, rn);
-            if (h) obj = i + k;
-            if (SHADOW && rt <= t_stop) cand = 0u;
-          }
-        }
-      }
-      if (SHADOW && rt <= t_stop) return obj;
-      i += len;
-    } else if (in.kind == RPT_SHAPE_CUBE && in.has_xf && i + 1 < n && cinst(sc, i + 1).kind == RPT_SHAPE_CUBE &&
-               cinst(sc, i + 1).has_xf) {
-      // two consecutive Transformed<Cube> (the boxes of C2): both candidates are evaluated in one block — a cube's
-      // test depends on the record only through the final `time < record.time` (cube.rs:66) — and then accepted in
-      // object order, so the second cube does not wait for the first one's whole chain
-      if (CULL && ((skip >> i) & 3ull) == 3ull) { // (the block as it is when one of the two may be hit)
-        PROF_COUNT(PF_P_PRECULL);
-        i += 2;
-        cslot += 2u;
-        continue;
-      }
-      CInst& in2 = cinst(sc, i + 1);
-      constexpr bool TAB = CONSTS && SC_CUBE && !SHADOW; // the accepted normal from the wave's table, by the candidate's face
-      D3 lo1 = mat4_mul(in.inv, o, 1.0), ld1 = mat4_mul(in.inv, d, 0.0);
-      D3 lo2 = mat4_mul(in2.inv, o, 1.0), ld2 = mat4_mul(in2.inv, d, 0.0);
-      RcpD ax = rcp_make(ld1.x), ay = rcp_make(ld1.y), az = rcp_make(ld1.z);
-      RcpD bx = rcp_make(ld2.x), by = rcp_make(ld2.y), bz = rcp_make(ld2.z);
-      double t1 = 0.0, t2 = 0.0;
-      D3 n1 = mk(0, 0, 0), n2 = mk(0, 0, 0);
-      uint32_t f1 = 0u, f2 = 0u;
-      bool c1 = TAB ? cube_candidate_face(lo1, ax, ay, az, EPSILON, t1, f1) : cube_candidate(lo1, ax, ay, az, EPSILON, t1, n1);
-      bool c2 = TAB ? cube_candidate_face(lo2, bx, by, bz, EPSILON, t2, f2) : cube_candidate(lo2, bx, by, bz, EPSILON, t2, n2);
-      if (c1 && t1 < rt) {
-        rt = t1;
-        if constexpr (TAB) rn = cube_nrm_of(fl, cslot, f1);
-        else if (!SHADOW) rn = normalize(mat3_mul(in.nrm, n1)); // Transformed::intersect shape.rs:131-132
-        obj = i;
-      }
-      if (SHADOW && rt <= t_stop) return obj;
-      if (c2 && t2 < rt) {
-        rt = t2;
-        if constexpr (TAB) rn = cube_nrm_of(fl, cslot + 1u, f2);
-        else if (!SHADOW) rn = normalize(mat3_mul(in2.nrm, n2));
-        obj = i + 1;
-      }
-      if (SHADOW && rt <= t_stop) return obj;
-      i += 2;
-      cslot += 2u;
-    } else {
-      if (CULL && ((skip >> i) & 1ull) != 0ull) {
-        i++;
-        continue;
-      }
-      if (isect_inst<KdFlat, SHADOW>(sc, in, o, d, rwx, rwy, rwz, EPSILON, t_stop, rt, rn, (KdFlat*)nullptr)) obj = i;
-      if (SHADOW && rt <= t_stop) return obj;
-      i++;
-    }
-  }
-  return obj;
-}
-
-// ------------------------------------------------------------------ a hit's shadow ray and bounce ray in one pass
-// flat_query<false> of the bounce ray (o, db) and flat_query<true> of the shadow ray (o, ds, t_stop) in one walk over the
-// objects (rpt_paths<KdFlat, false, true>; the host keeps a plane table and a second quotient table for it).  Each ray
-// keeps its own record and visits the objects in object order, so every accept is the one its own query makes: the
-// bounce slot's record (rtb, rnb, the object returned) is flat_query<false>'s, and the shadow slot's rts decides
-// visibility as flat_query<true>'s does — it only skips work once rts <= t_stop, and rts never grows again, so
-// `rts > t_stop` comes out the same.  What the shared origin allows is computed once: the plane-table numerators
-// pv - o and each cube's inv * o.  The two rays' slab quotients, wall candidates and cube candidates sit side by side in
-// straight-line code, so that the two dependency chains overlap.
-// A slot that is off (no bounce ray: the path ends at this hit) enters with its record at -inf: no test accepts.
-// CONSTS: as in flat_query.
-template <bool CONSTS_>
-RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, double t_stop, double& rtb, D3& rnb,
-                        double& rts) {
-  constexpr bool CONSTS = CONSTS_ && SC_CUBE;
-  int obj = -1;
-  uint32_t cslot = 0;
-  const int n = sc.num_objects;
-  const uint32_t lane = __lane_id();
-  const uint32_t nx = fl->plane_cnt & 15u, ny = (fl->plane_cnt >> 4) & 15u, nz = (fl->plane_cnt >> 8) & 15u;
-  const uint32_t nq = nx + ny + nz;
-  { // both rays' quotients (pv - o) / d: one numerator, two divisions (the bounce ray's table first, the shadow ray's behind it)
-    const double RPT_C* pv = (const double RPT_C*)fl->plane_vals;
-    double* qb = fl->qtab + lane;
-    double* qs = qb + nq * 64u;
-    for (uint32_t j = 0; j < nx; j++) { const double a = pv[j] - o.x; qb[j * 64u] = a / db.x; qs[j * 64u] = a / ds.x; }
-    for (uint32_t j = 0; j < ny; j++) {
-      const double a = pv[4u + j] - o.y;
-      qb[(nx + j) * 64u] = a / db.y; qs[(nx + j) * 64u] = a / ds.y;
-    }
-    for (uint32_t j = 0; j < nz; j++) {
-      const double a = pv[8u + j] - o.z;
-      qb[(nx + ny + j) * 64u] = a / db.z; qs[(nx + ny + j) * 64u] = a / ds.z;
-    }
-  }
-  int i = 0;
-  while (i < n) {
-    CInst& in = cinst(sc, i);
-    if (in.kind == RPT_SHAPE_MESH && !in.has_xf && in.plane_use) { // a run of table users (flat_query above), both rays
-      uint32_t cb = 0, cs = 0;
-      double mb[FLAT_RUN], ms[FLAT_RUN];
-      const int len = (int)in.plane_use;
-      const double* qtb = fl->qtab + lane;
-      const double* qts = qtb + nq * 64u;
-      switch (len) {
-        case 1: cb = run_slabs<1>(sc, i, qtb, rtb, mb); cs = run_slabs<1>(sc, i, qts, rts, ms); break;
-        case 2: cb = run_slabs<2>(sc, i, qtb, rtb, mb); cs = run_slabs<2>(sc, i, qts, rts, ms); break;
-        case 3: cb = run_slabs<3>(sc, i, qtb, rtb, mb); cs = run_slabs<3>(sc, i, qts, rts, ms); break;
-        case 4: cb = run_slabs<4>(sc, i, qtb, rtb, mb); cs = run_slabs<4>(sc, i, qts, rts, ms); break;
-        case 5: cb = run_slabs<5>(sc, i, qtb, rtb, mb); cs = run_slabs<5>(sc, i, qts, rts, ms); break;
-        default: cb = run_slabs<FLAT_RUN>(sc, i, qtb, rtb, mb); cs = run_slabs<FLAT_RUN>(sc, i, qts, rts, ms); break;
-      }
-      if (rts <= t_stop) cs = 0u; // (the shadow ray is blocked already)
-      while (__ballot((cb | cs) != 0u) != 0ull) {
-        PROF_COUNT(PF_P_CAND);
-        if (cb != 0u) { // the bounce ray's next candidate
-          const int k = __ffs((int)cb) - 1;
-          cb &= cb - 1u;
-          double mt = mb[0];
-#pragma unroll
-          for (int kk = 1; kk < FLAT_RUN; kk++) mt = k == kk ? mb[kk] : mt;
-          if (!(mt > rtb)) {
-            const uint32_t* e = fl->obj_leaf[i + k];
-            LaneTree lt{e[0], e[1]};
-            KdNode nd;
-            nd.split = 0.0; nd.a = e[2]; nd.ib = (e[3] << 2) | 3u;
-            if (kd_leaf<true, false>(sc, lt, sc.refs + lt.ref_base, nd, o, db, EPSILON, -INF, rtb, rnb)) obj = i + k;
-          }
-        }
-        if (cs != 0u) { // the shadow ray's
-          const int k = __ffs((int)cs) - 1;
-          cs &= cs - 1u;
-          double mt = ms[0];
-#pragma unroll
-          for (int kk = 1; kk < FLAT_RUN; kk++) mt = k == kk ? ms[kk] : mt;
-          if (!(mt > rts)) {
-            const uint32_t* e = fl->obj_leaf[i + k];
-            LaneTree lt{e[0], e[1]};
-            KdNode nd;
-            nd.split = 0.0; nd.a = e[2]; nd.ib = (e[3] << 2) | 3u;
-            D3 srn = mk(0, 0, 0);
-            kd_leaf<true, true>(sc, lt, sc.refs + lt.ref_base, nd, o, ds, EPSILON, t_stop, rts, srn);
-            if (rts <= t_stop) cs = 0u;
-          }
-        }
-      }
-      i += len;
-    } else if (in.kind == RPT_SHAPE_CUBE && in.has_xf && i + 1 < n && cinst(sc, i + 1).kind == RPT_SHAPE_CUBE &&
-               cinst(sc, i + 1).has_xf) {
-      // two consecutive Transformed<Cube> (flat_query above): cube by cube, both rays' candidates side by side, each
-      // accepted in object order by its own record
-      CInst* cu[2] = {&in, &cinst(sc, i + 1)};
-#pragma unroll
-      for (int c = 0; c < 2; c++) {
-        const CInst& q = *cu[c];
-        const D3 lo = mat4_mul(q.inv, o, 1.0);
-        const D3 lb = mat4_mul(q.inv, db, 0.0), ls = mat4_mul(q.inv, ds, 0.0);
-        const RcpD bx = rcp_make(lb.x), by = rcp_make(lb.y), bz = rcp_make(lb.z);
-        const RcpD sx = rcp_make(ls.x), sy = rcp_make(ls.y), sz = rcp_make(ls.z);
-        double tb = 0.0, ts = 0.0;
-        D3 nb = mk(0, 0, 0), ns = mk(0, 0, 0);
-        uint32_t fb = 0u;
-        const bool hb = CONSTS ? cube_candidate_face(lo, bx, by, bz, EPSILON, tb, fb) : cube_candidate(lo, bx, by, bz, EPSILON, tb, nb);
-        const bool hs = cube_candidate(lo, sx, sy, sz, EPSILON, ts, ns);
-        if (hb && tb < rtb) {
-          rtb = tb;
-          if constexpr (CONSTS) rnb = cube_nrm_of(fl, cslot + (uint32_t)c, fb);
-          else rnb = normalize(mat3_mul(q.nrm, nb)); // Transformed::intersect shape.rs:131-132
-          obj = i + c;
-        }
-        if (hs && ts < rts) rts = ts;
-      }
-      i += 2;
-      cslot += 2u;
-    } else { // anything else: the object's own test, once per ray
-      if (!(rtb == -INF)) {
-        const RcpD rx = rcp_make(db.x), ry = rcp_make(db.y), rz = rcp_make(db.z);
-        if (isect_inst<KdFlat, false>(sc, in, o, db, rx, ry, rz, EPSILON, -INF, rtb, rnb, (KdFlat*)nullptr)) obj = i;
-      }
-      if (!(rts <= t_stop)) {
-        const RcpD rx = rcp_make(ds.x), ry = rcp_make(ds.y), rz = rcp_make(ds.z);
-        D3 srn = mk(0, 0, 0);
-        isect_inst<KdFlat, true>(sc, in, o, ds, rx, ry, rz, EPSILON, t_stop, rts, srn, (KdFlat*)nullptr);
-      }
-      i++;
-    }
-  }
-  return obj;
-}
-
-#if RPT_SHADE_SPLIT
-// ------------------------------------------------------------------ a hit's draws first, its shading in one block
-// The fast form of the fused kernel's shading (rpt_paths<KdFlat, false, true>, RPT_SHADE_SPLIT): a wave whose light is
-// an untransformed mesh and whose shading lanes all hit opaque materials (C2).  Every draw of a hit is taken first, in
-// the reference's order and by its own loops: illuminate's triangle index and (u, v) pairs until u + v <= 1, then, if
-// the path goes on, gen_bool(f), u_theta for the specular lobe and +-1 pairs until one is accepted (sample_f).  What
-// the draws decide is kept as their integers, and the shading that follows is one straight-line block.
-// (One loop for the whole sequence, a Philox block per lane and round with each lane stepping through its own state
-// machine, was measured too: the per-round selects of that state cost far more than the blocks it saved, 25 % slower.)
-struct HitDraws {
-  uint64_t tri;   // the light triangle's index
-  uint64_t a, b;  // the (u, v) pair that was kept
-  uint64_t th;    // u_theta's draw (the specular lobe; a dummy 0.5 otherwise)
-  uint64_t qa, qb; // the +-1 pair that was kept
-  bool spec;      // gen_bool(f)
-};
-// sf: sample_f runs (depth < max_bounces); f: sample_f's lobe probability; mc (CONSTS): the material's constants, with
-// gen_bool(f)'s threshold among them
-template <bool CONSTS = false>
-RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, HitDraws& o, const MatConsts* mc = nullptr) {
-  o.tri = gen_index_zone(r, n, zone);
-  next2_u64(r, o.a, o.b);
-  while ((o.a >> 11) + (o.b >> 11) >= (1ull << 53) + 2ull) {
-    PROF_COUNT(PF_P_REJECT);
-    next2_u64(r, o.a, o.b);
-  }
-  o.th = 1ull << 63; o.qa = 0; o.qb = 0; o.spec = false;
-  if (!sf) return;
-  if constexpr (CONSTS) o.spec = f == 1.0 ? true : next_u64(r) < mc->p_int; // gen_bool: no draw when f == 1.0
-  else o.spec = gen_bool(r, f);
-  if (o.spec) o.th = next_u64(r);
-  for (;;) {
-    PROF_COUNT(PF_P_REJECT);
-    next2_u64(r, o.qa, o.qb);
-    const double x = u52_of(o.qa) * 2.0 + -1.0, y = u52_of(o.qb) * 2.0 + -1.0;
-    const double sum = x * x + y * y;
-    if (o.spec ? sum < 1.0 : sum <= 1.0) break;
-  }
-}
-
-// bsdf() for an opaque material: both directions outside (the reflection case) or zero, its early return a select
-// (CONSTS: m2, m2 * PI, f0 and one - f0 from the material's constants)
-template <bool CONSTS = false>
-RPT_DEV D3 bsdf_opaque(const Material& m, D3 n, D3 wo, D3 wi, const MatConsts* mc = nullptr) { // material.rs:125-170
-  D3 color = ld3(m.color);
-  double n_dot_wi = dot(n, wi);
-  double n_dot_wo = dot(n, wo);
-  const bool lit = !__builtin_signbit(n_dot_wi) && !__builtin_signbit(n_dot_wo);
-  const D3 one = mk(1, 1, 1);
-  double m2, m2pi;
-  D3 f0, omf0;
-  if constexpr (CONSTS) {
-    m2 = mc->m2; m2pi = mc->m2pi;
-    f0 = ld3(mc->f0); omf0 = ld3(mc->omf0);
-  } else {
-    m2 = m.roughness * m.roughness;
-    m2pi = m2 * PI;
-    double f0s = pow2((m.index - 1.0) / (m.index + 1.0));
-    f0 = lerp(mk(f0s, f0s, f0s), color, m.metallic);
-    omf0 = one - f0;
-  }
-  D3 h = normalize(wi + wo); // (wi * 1.0 + wo in bsdf)
-  double wo_dot_h = dot(wo, h);
-  double n_dot_h = dot(n, h);
-  double nh2 = pow2(n_dot_h);
-  double dd = rptc_exp((nh2 - 1.0) / (m2 * nh2)) / (m2pi * nh2 * nh2);
-  D3 f = f0 + omf0 * pow5(1.0 - wo_dot_h);
-  double ga = n_dot_wi * n_dot_h, gb = n_dot_wo * n_dot_h;
-  double g = fmin(ga, gb);
-  g = (2.0 * g) / wo_dot_h;
-  g = fmin(g, 1.0);
-  D3 q = dd * f * g / (4.0 * n_dot_wo * n_dot_wi);
-  D3 diffuse = cmul(one - f, color) / PI;
-  return lit ? q + diffuse : mk(0, 0, 0);
-}
-
-// sample_f() for an opaque material on the drawn values: both lobes' local vectors, the lane's one behind a select
-template <bool CONSTS = false>
-RPT_DEV void sample_f_opaque(const Material& m, D3 n, D3 wo, double f, const HitDraws& dr, D3& wi, double& pdf,
-                             const MatConsts* mc = nullptr) {
-  double m2; // material.rs:224-313
-  if constexpr (CONSTS) m2 = mc->m2;
-  else m2 = m.roughness * m.roughness;
-  const double u_theta = (double)(dr.th >> 11) * (1.0 / 9007199254740992.0);
-  const double x = u52_of(dr.qa) * 2.0 + -1.0, y = u52_of(dr.qb) * 2.0 + -1.0;
-  const double sum = x * x + y * y;
-  double theta = rptc_atan(sqrt(m2 * -rpt_log(u_theta)));
-  double sin_t, cos_t;
-  rptc_sincos_pio2(theta, &sin_t, &cos_t);
-  double diff = x * x - y * y;
-  double cx = diff / sum, cy = 2.0 * x * y / sum;
-  const D3 loc = dr.spec ? mk(cx * sin_t, cy * sin_t, cos_t) : mk(x, y, sqrt(1.0 - x * x - y * y));
-  const D3 world = local_to_world_mul(n, loc);
-  wi = dr.spec ? -(wo - world * (dot(world, wo) * 2.0)) : world; // -glm::reflect_vec(wo, h)
-  double p = 0.0;
-  {
-    D3 h = normalize(wi + wo);
-    double p_h;
-    if constexpr (CONSTS) { // beckmann_pdf with its PI * m2 from the table (the product m2 * PI: the same number)
-      double cos_t = fabs(dot(h, n));
-      double sin_t = sqrt(1.0 - cos_t * cos_t);
-      p_h = (1.0 / (mc->m2pi * pow3(cos_t))) * rptc_exp(-pow2(sin_t / cos_t) / m2);
-    } else {
-      p_h = beckmann_pdf(m2, n, h);
-    }
-    p += f * p_h / (4.0 * fabs(dot(h, wo)));
-  }
-  p += (1.0 - f) * fmax(dot(wi, n), 0.0) * FRAC_1_PI;
-  pdf = p;
-}
-
-// illuminate() of an untransformed mesh light on the drawn values (light.rs:23-47, mesh.rs:84-98, kdtree.rs:138-143)
-// (CONSTS: Shape::sample's pdf of the drawn triangle, (1 / area) / num_prims, from the wave's table)
-template <bool CONSTS = false>
-RPT_DEV void illuminate_mesh(CLight& l, CTree& tr, const Tri* __restrict__ tp, D3 pos, const HitDraws& dr, D3& intensity,
-                             D3& wi, double& dist, const double* light_pdf = nullptr) {
-  const double u = (double)(dr.a >> 11) * (1.0 / 9007199254740992.0), v = (double)(dr.b >> 11) * (1.0 / 9007199254740992.0);
-  double w = 1.0 - u - v;
-  D3 v1 = ld3(tp->v), v2 = ld3(tp->v + 3), v3 = ld3(tp->v + 6);
-  D3 n1 = ld3(tp->v + 9), n2 = ld3(tp->v + 12), n3 = ld3(tp->v + 15);
-  SampleOut s{u * v1 + v * v2 + w * v3, normalize(u * n1 + v * n2 + w * n3), 0.0};
-  if constexpr (CONSTS) {
-    s.p = light_pdf[dr.tri];
-  } else {
-    double area = 0.5 * length(cross(v2 - v1, v3 - v1));
-    s.p = 1.0 / area;
-    s.p = s.p / (double)tr.num_prims;
-  }
-  D3 disp = s.v - pos;
-  double len = length(disp);
-  double cosine = fmax(-dot(disp, s.n), 0.0) / len;
-  double surface_area = fmax(cosine, 0.0) / (len * len);
-  intensity = ld3(l.mat_color) * l.mat_emittance * surface_area / s.p;
-  wi = disp / len;
-  dist = len;
-}
-#endif
-
 template <class LDS> struct PathsLds { using type = LDS; };
 template <> struct PathsLds<KdFlat> { struct type { int unused; }; };
 // KdFlatG: the same kernel with the triangles (vertex normals, light sampling) left in GLOBAL memory, for flat scenes
@@ -858,6 +164,20 @@ RPT_DEV bool fetch_item(const PersistArgs& pa, const Frame& fr, uint32_t lane, b
   }
   return got;
 }
+// ring arithmetic (top of this file): a path with header slot b keeps level k in slot b + 1 + k, and the next path's
+// header comes behind its `depth` records; the running path's header slot is the high half of fold_st
+RPT_DEV uint32_t next_header_slot(uint32_t b, uint32_t depth, uint32_t ring) {
+  uint32_t nb = b + depth + 1u;
+  if (nb >= ring) nb -= ring;
+  return nb;
+}
+RPT_DEV uint32_t rec_slot(uint32_t fold_st, uint32_t depth, uint32_t ring) { // of level `depth` of the running path
+  return next_header_slot(fold_st >> 16, depth, ring);
+}
+// a record's f, 1/pdf and |wi.n| (its A is r[0..2])
+RPT_DEV void rec_store_bsdf(double* r, const D3& f, double inv_pdf, double abscos) {
+  r[3] = f.x; r[4] = f.y; r[5] = f.z; r[6] = inv_pdf; r[7] = abscos;
+}
 // a path of `depth` levels ended with radiance A: the sample itself (depth 0), or the walker's next job — from
 // registers if it is idle, else as a header in the path's slot b (the walker gets there in ring order)
 RPT_DEV void path_ended(const PersistArgs& pa, const Frame& fr, double* __restrict__ rec, double (*fold_l)[64],
@@ -889,9 +209,7 @@ RPT_DEV void park_push(ParkLds& park, uint32_t lane, uint32_t& pcnt, uint32_t& p
   if (depth != 0u) {
     if (park_hd == 0xffffffffu) park_hd = b; // the oldest parked header: where the walker stops
     park_recs += depth;
-    uint32_t nb = b + depth + 1u;
-    if (nb >= ring) nb -= ring;
-    fold_st = (fold_st & 0xffffu) | (nb << 16);
+    fold_st = (fold_st & 0xffffu) | (next_header_slot(b, depth, ring) << 16);
   }
   pcnt = k + 1u;
 }
@@ -909,6 +227,52 @@ struct RayStashHit {
   uint32_t u[6][64];
 };
 static_assert(sizeof(RayStashHit) == RPT_PATHS_STASH_HIT_LDS, "kernels.h sizes the wave's LDS budget with it");
+// the stash's traffic, for either form (S = RayStash | RayStashHit): a ray (origin, direction)
+template <class S> RPT_DEV void stash_put_pos(S& st, uint32_t lane, const D3& o) {
+  st.v[0][lane] = o.x; st.v[1][lane] = o.y; st.v[2][lane] = o.z;
+}
+template <class S> RPT_DEV void stash_put_dir(S& st, uint32_t lane, const D3& d) {
+  st.v[3][lane] = d.x; st.v[4][lane] = d.y; st.v[5][lane] = d.z;
+}
+template <class S> RPT_DEV void stash_put_ray(S& st, uint32_t lane, const D3& o, const D3& d) {
+  stash_put_pos(st, lane, o);
+  stash_put_dir(st, lane, d);
+}
+template <class S> RPT_DEV void stash_take_ray(const S& st, uint32_t lane, D3& o, D3& d) {
+  o = mk(st.v[0][lane], st.v[1][lane], st.v[2][lane]);
+  d = mk(st.v[3][lane], st.v[4][lane], st.v[5][lane]);
+}
+// the two-pass pre-trace: the stashed ray into (o, d), the running one into its slots meanwhile
+template <class S> RPT_DEV void stash_swap_ray(S& st, uint32_t lane, D3& o, D3& d) {
+  D3 so, sd;
+  stash_take_ray(st, lane, so, sd);
+  stash_put_ray(st, lane, o, d);
+  o = so; d = sd;
+}
+// a path's identity (work item, sample) and its Philox position after camera_ray's draws
+template <class S> RPT_DEV void stash_put_path(S& st, uint32_t lane, uint32_t p_local, uint32_t pixel, uint32_t s, uint32_t s_end, const Rng& r) {
+  st.v[6][lane] = __longlong_as_double((long long)r.hi);
+  st.u[0][lane] = p_local; st.u[1][lane] = pixel; st.u[2][lane] = s; st.u[3][lane] = s_end;
+  st.u[4][lane] = r.draw;
+}
+template <class S> RPT_DEV void stash_take_path(const S& st, uint32_t lane, const Frame& fr, uint32_t& p_local, uint32_t& pixel, uint32_t& s,
+                             uint32_t& s_end, Rng& r) {
+  p_local = st.u[0][lane]; pixel = st.u[1][lane]; s = st.u[2][lane]; s_end = st.u[3][lane];
+  r = rng_make(fr.seed, pixel, fr.sample_base + s, 0);
+  r.draw = st.u[4][lane];
+  r.hi = (uint64_t)__double_as_longlong(st.v[6][lane]);
+}
+// a traced ray's hit in place of its origin: the point, the normal (or the environment's colour), the object (-1: escaped)
+RPT_DEV void stash_put_hit(RayStashHit& st, uint32_t lane, const D3& pos, const D3& nrm, int obj) {
+  stash_put_pos(st, lane, pos);
+  st.v[7][lane] = nrm.x; st.v[8][lane] = nrm.y; st.v[9][lane] = nrm.z;
+  st.u[5][lane] = (uint32_t)obj;
+}
+RPT_DEV void stash_take_hit(const RayStashHit& st, uint32_t lane, D3& pos, D3& d, D3& nrm, int& obj) {
+  stash_take_ray(st, lane, pos, d);
+  nrm = mk(st.v[7][lane], st.v[8][lane], st.v[9][lane]);
+  obj = (int)st.u[5][lane];
+}
 #ifndef RPT_STASH_REFILL_MIN
 #define RPT_STASH_REFILL_MIN 32 // RayStashHit: the wave also refills once this many lanes have an empty stash
 #endif
@@ -918,15 +282,65 @@ RPT_DEV void end_path(const PersistArgs& pa, const Frame& fr, double* __restrict
                       uint32_t s, uint32_t p_local) {
   const uint32_t b = fold_st >> 16;
   path_ended(pa, fr, rec, fold_l, fold_u, lane, fold_st, A, depth, b, s, p_local);
-  if (depth != 0u) {
-    uint32_t nb = b + depth + 1u; // the next path's header slot
-    if (nb >= ring) nb -= ring;
-    fold_st = (fold_st & 0xffffu) | (nb << 16);
+  if (depth != 0u) fold_st = (fold_st & 0xffffu) | (next_header_slot(b, depth, ring) << 16);
+}
+// one step of the walker, for a lane that owes one (fold_st's low half): L = A_k + min(1/pdf * (f . L) * |wi.n|, 100)
+// (renderer.rs:162-167), k = the deepest level not yet folded of the oldest path that ended
+template <bool PARK>
+RPT_DEV void walker_step(const PersistArgs& pa, const Frame& fr, const double* __restrict__ rec, double (*fold_l)[64],
+                         uint32_t (*fold_u)[64], uint32_t lane, uint32_t& fold_st, uint32_t ring, uint32_t park_hd,
+                         double probe_chk /* -DRPT_PROBE_NO_RING builds only */) {
+  const uint32_t wk = fold_st & 0xffffu, cb = fold_st >> 16;
+  const uint32_t wD = fold_u[0][lane], wb = fold_u[1][lane];
+  uint32_t pos = wb + wk; // level wk - 1 of the walker's path
+  if (pos >= ring) pos -= ring;
+  const uint32_t nh = next_header_slot(wb, wD, ring); // header slot of the path behind it; == cb when no path waits
+  const bool last = wk == 1u, more = last && nh != cb && (!PARK || nh != park_hd); // (a parked path's header is not written yet)
+  double v[REC_FIELDS], hd[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#ifdef RPT_PROBE_NO_RING
+  (void)pos; // (the headers of waiting paths — 40 B per path that waits, against 64 B per SEGMENT — stay real: the
+             // walker's bookkeeping needs their depth)
+#pragma unroll
+  for (int q = 0; q < REC_FIELDS; q++) v[q] = probe_chk * (double)(q + 1);
+#else
+  {
+    const double* r = rec + pos * REC_FIELDS;
+#pragma unroll
+    for (int q = 0; q < REC_FIELDS; q++) v[q] = r[q];
+  }
+#endif
+  if (more) { // requested together with the record: one round trip
+    const double* r = rec + nh * REC_FIELDS;
+#pragma unroll
+    for (int q = 0; q < 5; q++) hd[q] = r[q];
+  }
+  D3 L = mk(fold_l[0][lane], fold_l[1][lane], fold_l[2][lane]);
+  D3 Ak = mk(v[0], v[1], v[2]);
+  D3 f = mk(v[3], v[4], v[5]);
+  D3 indirect = v[6] * cmul(f, L) * v[7];
+  L = mk(Ak.x + fmin(indirect.x, FIREFLY_CLAMP), Ak.y + fmin(indirect.y, FIREFLY_CLAMP),
+         Ak.z + fmin(indirect.z, FIREFLY_CLAMP));
+  if (!last) {
+    fold_l[0][lane] = L.x; fold_l[1][lane] = L.y; fold_l[2][lane] = L.z;
+    fold_st -= 1u;
+  } else { // level 0 folded: L is the sample (summed by rpt_sum_samples)
+    double* lb = pa.lbuf + (uint64_t)fold_u[2][lane] * 3 * fr.npix + fold_u[3][lane];
+    lb[0] = L.x;
+    lb[fr.npix] = L.y;
+    lb[2 * (uint64_t)fr.npix] = L.z;
+    uint32_t nk = 0u;
+    if (more) { // on to the oldest waiting path
+      const uint64_t sp = (uint64_t)__double_as_longlong(hd[3]);
+      nk = (uint32_t)__double_as_longlong(hd[4]);
+      fold_l[0][lane] = hd[0]; fold_l[1][lane] = hd[1]; fold_l[2][lane] = hd[2];
+      fold_u[0][lane] = nk; fold_u[1][lane] = nh; fold_u[2][lane] = (uint32_t)sp; fold_u[3][lane] = (uint32_t)(sp >> 32);
+    }
+    fold_st = (cb << 16) | nk;
   }
 }
 template <class LDS, bool PARK /* environment lookups parked per lane (pa.park_off) */,
           bool FUSE = false /* a hit's shadow ray and bounce ray in one query (FUSE below) */,
-          bool CONSTS = false /* FUSE with a hit's scene constants in the wave's tables (SceneConsts above) */>
+          bool CONSTS = false /* FUSE with a hit's scene constants in the wave's tables (SceneConsts, paths_consts.inc) */>
 __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame fr, Camera cam, PersistArgs pa) {
   extern __shared__ __attribute__((aligned(16))) unsigned char flat_smem[]; // KdFlat only (dynamic size)
   __shared__ typename PathsLds<LDS>::type kd_store; // KdLds: the wave's traversal stack (15 KB); KdFlat: unused
@@ -1007,6 +421,8 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
   uint32_t n_ext = 0, n_sh = 0;
 #ifdef RPT_PROBE_NO_RING
   double probe_chk = 0.0;
+#else
+  constexpr double probe_chk = 0.0; // (walker_step's unused argument)
 #endif
   const double dim = (double)max(fr.width, fr.height);
   // rpt_paths<KdFlat>: the NEXT sample's camera ray waits in LDS.  Fetch and ray generation are work for the ~14 lanes of
@@ -1072,11 +488,8 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
 #if RPT_PRETRACE_CULL
           if constexpr (FUSE) near = cull_near(pa.flat, g_pixel, fr.width);
 #endif
-          stash.v[0][lane] = go.x; stash.v[1][lane] = go.y; stash.v[2][lane] = go.z;
-          stash.v[3][lane] = gd.x; stash.v[4][lane] = gd.y; stash.v[5][lane] = gd.z;
-          stash.v[6][lane] = __longlong_as_double((long long)gr.hi);
-          stash.u[0][lane] = g_p_local; stash.u[1][lane] = g_pixel; stash.u[2][lane] = g_s; stash.u[3][lane] = g_s_end;
-          stash.u[4][lane] = gr.draw;
+          stash_put_ray(stash, lane, go, gd);
+          stash_put_path(stash, lane, g_p_local, g_pixel, g_s, g_s_end, gr);
           stash_valid = true;
           pend = PRETRACE;
         }
@@ -1084,12 +497,8 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       }
       // ---- a lane whose path ended starts on its stashed ray (PRETRACE: after the closest hit)
       if (!PRETRACE && !in_path && stash_valid) {
-        o = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
-        d = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
-        p_local = stash.u[0][lane]; pixel = stash.u[1][lane]; s = stash.u[2][lane]; s_end = stash.u[3][lane];
-        rng = rng_make(fr.seed, pixel, fr.sample_base + s, 0);
-        rng.draw = stash.u[4][lane];
-        rng.hi = (uint64_t)__double_as_longlong(stash.v[6][lane]);
+        stash_take_ray(stash, lane, o, d);
+        stash_take_path(stash, lane, fr, p_local, pixel, s, s_end, rng);
         stash_valid = false;
         depth = 0;
         in_path = true;
@@ -1102,7 +511,8 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       if (!fetch_item(pa, fr, lane, need, pool, p_local, pixel, s, s_end) && need) done = true;
       if (__ballot(!done || (fold_st & 0xffffu) != 0u || pcnt != 0u) == 0) break; // (a lane without work still lets its walker finish)
       PROF_PHASE(PF_P_FETCH);
-      // ---- ray generation (renderer.rs:132-139, camera.rs:64-81)
+      // ---- ray generation (renderer.rs:132-139, camera.rs:64-81): camera_ray's body, word for word — a change to either goes
+      // into both.  Calling it here costs rpt_paths<KdLds> 16 B of scratch and 6 spilled VGPRs (profiles/paths_split_resources.txt)
       if (!done && !in_path) {
         uint32_t y = pixel / fr.width, x = pixel - y * fr.width;
         double xn = ((double)(2 * x + 1) - (double)fr.width) / dim;
@@ -1141,8 +551,8 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       nx_pos = mk(0, 0, 0); nx_nrm = mk(0, 0, 0); nx_obj = -1; // (so that no old value lives across the queries below)
       if (__ballot(pend) != 0ull) {
         if (pend) {
-          const D3 so = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
-          const D3 sd = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
+          D3 so, sd;
+          stash_take_ray(stash, lane, so, sd);
           double t = INF;
           D3 hn = mk(0, 0, 0);
 #if RPT_PRETRACE_CULL
@@ -1154,10 +564,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
 #endif
           n_ext++;
           if (ho < 0) hn = env_color(sc, sd); // renderer.rs:147
-          const D3 hp = so + t * sd;
-          stash.v[0][lane] = hp.x; stash.v[1][lane] = hp.y; stash.v[2][lane] = hp.z;
-          stash.v[7][lane] = hn.x; stash.v[8][lane] = hn.y; stash.v[9][lane] = hn.z;
-          stash.u[5][lane] = (uint32_t)ho;
+          stash_put_hit(stash, lane, so + t * sd, hn, ho);
           pend = false;
         }
       }
@@ -1168,14 +575,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
 #pragma unroll 1
       for (uint32_t pass = __ballot(pend && in_path) != 0ull ? 0u : 1u; pass < 2u; pass++) {
         const bool pre = pend, run = pend || (pass == 1u && in_path);
-        if (pre) { // the stashed ray into the registers, the running one into its slots meanwhile
-          const D3 so = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
-          const D3 sd = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
-          stash.v[0][lane] = o.x; stash.v[1][lane] = o.y; stash.v[2][lane] = o.z;
-          stash.v[3][lane] = d.x; stash.v[4][lane] = d.y; stash.v[5][lane] = d.z;
-          o = so;
-          d = sd;
-        }
+        if (pre) stash_swap_ray(stash, lane, o, d); // the stashed ray into the registers, the running one into its slots meanwhile
         double t = INF;
         h_nrm = mk(0, 0, 0);
         h_obj = -1;
@@ -1185,15 +585,12 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
           if (h_obj < 0) h_nrm = env_color(sc, d); // renderer.rs:147
         }
         h_pos = o + t * d;
-        if (pre) {
-          const D3 ro = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
-          const D3 rd = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
-          stash.v[0][lane] = h_pos.x; stash.v[1][lane] = h_pos.y; stash.v[2][lane] = h_pos.z;
-          stash.v[3][lane] = d.x; stash.v[4][lane] = d.y; stash.v[5][lane] = d.z;
-          stash.v[7][lane] = h_nrm.x; stash.v[8][lane] = h_nrm.y; stash.v[9][lane] = h_nrm.z;
-          stash.u[5][lane] = (uint32_t)h_obj;
-          o = ro;
-          d = rd;
+        if (pre) { // the running ray back, the traced one's direction into its slots and its hit where its origin was
+          D3 ro, rd;
+          stash_take_ray(stash, lane, ro, rd);
+          stash_put_dir(stash, lane, d);
+          stash_put_hit(stash, lane, h_pos, h_nrm, h_obj);
+          o = ro; d = rd;
           pend = false;
         }
       }
@@ -1207,14 +604,8 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         in_path = false;
       }
       if (!in_path && stash_valid) {
-        h_pos = mk(stash.v[0][lane], stash.v[1][lane], stash.v[2][lane]);
-        d = mk(stash.v[3][lane], stash.v[4][lane], stash.v[5][lane]);
-        h_nrm = mk(stash.v[7][lane], stash.v[8][lane], stash.v[9][lane]);
-        h_obj = (int)stash.u[5][lane];
-        p_local = stash.u[0][lane]; pixel = stash.u[1][lane]; s = stash.u[2][lane]; s_end = stash.u[3][lane];
-        rng = rng_make(fr.seed, pixel, fr.sample_base + s, 0);
-        rng.draw = stash.u[4][lane];
-        rng.hi = (uint64_t)__double_as_longlong(stash.v[6][lane]);
+        stash_take_hit(stash, lane, h_pos, d, h_nrm, h_obj);
+        stash_take_path(stash, lane, fr, p_local, pixel, s, s_end, rng);
         stash_valid = false;
         depth = 0;
         in_path = true;
@@ -1235,7 +626,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         double dist;
         bool cont;
 #if RPT_SHADE_SPLIT
-        // SHADE_SPLIT (hit_draws above): a wave whose light is an untransformed mesh and whose lanes hit opaque
+        // SHADE_SPLIT (hit_draws, paths_shade.inc): a wave whose light is an untransformed mesh and whose lanes hit opaque
         // materials only takes every draw of its hits first and then shades them in one straight-line block: illuminate's tail and the light term's bsdf, sample_f's math and the bounce's bsdf, the two chains side
         // by side, selects in place of branches.  Each value keeps its operations in their order.  A point or
         // directional light, a transformed light or a glass surface in the wave takes the sequence below.
@@ -1269,12 +660,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
           const D3 f = bsdf_opaque<CM>(mat, nrm, wo, wi, mcs);
           PROF_PHASE(PF_P_SHADE);
           if (cont) { // the record's f, 1/pdf and |wi.n| now, its A after the query
-            uint32_t pos = (fold_st >> 16) + 1u + depth; // slot b is the path's header, b + 1 + k its level k
-            if (pos >= ring) pos -= ring;
-            double* r = rec + pos * REC_FIELDS;
-            r[3] = f.x; r[4] = f.y; r[5] = f.z;
-            r[6] = 1.0 / pdf;
-            r[7] = fabs(dot(wi, nrm));
+            rec_store_bsdf(rec + rec_slot(fold_st, depth, ring) * REC_FIELDS, f, 1.0 / pdf, fabs(dot(wi, nrm)));
           } else {
             wi = wl;
           }
@@ -1296,12 +682,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         if (cont) { // the record's f, 1/pdf and |wi.n| now, its A after the query
           const D3 f = bsdf(mat, nrm, wo, wi);
           PROF_PHASE(PF_P_BSDF);
-          uint32_t pos = (fold_st >> 16) + 1u + depth; // slot b is the path's header, b + 1 + k its level k
-          if (pos >= ring) pos -= ring;
-          double* r = rec + pos * REC_FIELDS;
-          r[3] = f.x; r[4] = f.y; r[5] = f.z;
-          r[6] = 1.0 / pdf;
-          r[7] = fabs(dot(wi, nrm));
+          rec_store_bsdf(rec + rec_slot(fold_st, depth, ring) * REC_FIELDS, f, 1.0 / pdf, fabs(dot(wi, nrm)));
           PROF_PHASE(PF_P_RECORD);
         }
         }
@@ -1315,9 +696,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         PROF_PHASE(PF_P_FUSED);
         const D3 A = color + (vis ? lt : mk(0, 0, 0));
         if (cont) {
-          uint32_t pos = (fold_st >> 16) + 1u + depth;
-          if (pos >= ring) pos -= ring;
-          double* r = rec + pos * REC_FIELDS;
+          double* r = rec + rec_slot(fold_st, depth, ring) * REC_FIELDS;
           r[0] = A.x; r[1] = A.y; r[2] = A.z;
           n_ext++;
           nx_pos = world_pos + rtb * d;
@@ -1419,13 +798,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
             probe_chk += ((A.x + A.y) + A.z) + ((f.x + f.y) + f.z) + inv_pdf + abscos;
 #else
             {
-              uint32_t pos = (fold_st >> 16) + 1u + depth; // slot b is the path's header, b + 1 + k its level k
-              if (pos >= ring) pos -= ring;
-              double* r = rec + pos * REC_FIELDS;
+              double* r = rec + rec_slot(fold_st, depth, ring) * REC_FIELDS;
               r[0] = A.x; r[1] = A.y; r[2] = A.z;
-              r[3] = f.x; r[4] = f.y; r[5] = f.z;
-              r[6] = inv_pdf;
-              r[7] = abscos;
+              rec_store_bsdf(r, f, inv_pdf, abscos);
             }
 #endif
             o = world_pos;
@@ -1493,58 +868,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       in_path = false;
     }
     PROF_PHASE(PF_P_RECORD);
-    // ---- one step of the walker for every lane that owes one: L = A_k + min(1/pdf * (f . L) * |wi.n|, 100)
-    // (renderer.rs:162-167), k = the deepest level not yet folded of the oldest path that ended
-    if ((fold_st & 0xffffu) != 0u) {
+    if ((fold_st & 0xffffu) != 0u) { // ---- one step of the walker for every lane that owes one (walker_step)
       PROF_COUNT(PF_P_FOLDIT);
-      const uint32_t wk = fold_st & 0xffffu, cb = fold_st >> 16;
-      const uint32_t wD = fold_u[0][lane], wb = fold_u[1][lane];
-      uint32_t pos = wb + wk; // level wk - 1 of the walker's path
-      if (pos >= ring) pos -= ring;
-      uint32_t nh = wb + wD + 1u; // header slot of the path behind it; == cb when no path waits
-      if (nh >= ring) nh -= ring;
-      const bool last = wk == 1u, more = last && nh != cb && (!park_on || nh != park_hd); // (a parked path's header is not written yet)
-      double v[REC_FIELDS], hd[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-#ifdef RPT_PROBE_NO_RING
-      (void)pos; // (the headers of waiting paths — 40 B per path that waits, against 64 B per SEGMENT — stay real: the
-                 // walker's bookkeeping needs their depth)
-#pragma unroll
-      for (int q = 0; q < REC_FIELDS; q++) v[q] = probe_chk * (double)(q + 1);
-#else
-      {
-        const double* r = rec + pos * REC_FIELDS;
-#pragma unroll
-        for (int q = 0; q < REC_FIELDS; q++) v[q] = r[q];
-      }
-#endif
-      if (more) { // requested together with the record: one round trip
-        const double* r = rec + nh * REC_FIELDS;
-#pragma unroll
-        for (int q = 0; q < 5; q++) hd[q] = r[q];
-      }
-      D3 L = mk(fold_l[0][lane], fold_l[1][lane], fold_l[2][lane]);
-      D3 Ak = mk(v[0], v[1], v[2]);
-      D3 f = mk(v[3], v[4], v[5]);
-      D3 indirect = v[6] * cmul(f, L) * v[7];
-      L = mk(Ak.x + fmin(indirect.x, FIREFLY_CLAMP), Ak.y + fmin(indirect.y, FIREFLY_CLAMP),
-             Ak.z + fmin(indirect.z, FIREFLY_CLAMP));
-      if (!last) {
-        fold_l[0][lane] = L.x; fold_l[1][lane] = L.y; fold_l[2][lane] = L.z;
-        fold_st -= 1u;
-      } else { // level 0 folded: L is the sample (summed by rpt_sum_samples)
-        double* lb = pa.lbuf + (uint64_t)fold_u[2][lane] * 3 * fr.npix + fold_u[3][lane];
-        lb[0] = L.x;
-        lb[fr.npix] = L.y;
-        lb[2 * (uint64_t)fr.npix] = L.z;
-        uint32_t nk = 0u;
-        if (more) { // on to the oldest waiting path
-          const uint64_t sp = (uint64_t)__double_as_longlong(hd[3]);
-          nk = (uint32_t)__double_as_longlong(hd[4]);
-          fold_l[0][lane] = hd[0]; fold_l[1][lane] = hd[1]; fold_l[2][lane] = hd[2];
-          fold_u[0][lane] = nk; fold_u[1][lane] = nh; fold_u[2][lane] = (uint32_t)sp; fold_u[3][lane] = (uint32_t)(sp >> 32);
-        }
-        fold_st = (cb << 16) | nk;
-      }
+      walker_step<PARK>(pa, fr, rec, fold_l, fold_u, lane, fold_st, ring, park_hd, probe_chk);
     }
     PROF_PHASE(PF_P_FOLD);
   }
@@ -1559,7 +885,6 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
     atomicAdd(pa.ray_counters + 1, (unsigned long long)n_sh);
   }
 }
-
 
 // color += trace_ray(...) over the launch's samples in sample order (renderer.rs:136-140); `first`
 // starts the pixel's sum at zero, later launches of the same batch continue it

@@ -1,0 +1,140 @@
+// kernels/paths_shade.inc — the fused rpt_paths' draw-first shading: hit_draws, bsdf_opaque, sample_f_opaque, illuminate_mesh.
+// Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
+
+#if RPT_SHADE_SPLIT
+// ------------------------------------------------------------------ a hit's draws first, its shading in one block
+// The fast form of the fused kernel's shading (rpt_paths<KdFlat, false, true>, RPT_SHADE_SPLIT): a wave whose light is
+// an untransformed mesh and whose shading lanes all hit opaque materials (C2).  Every draw of a hit is taken first, in
+// the reference's order and by its own loops: illuminate's triangle index and (u, v) pairs until u + v <= 1, then, if
+// the path goes on, gen_bool(f), u_theta for the specular lobe and +-1 pairs until one is accepted (sample_f).  What
+// the draws decide is kept as their integers, and the shading that follows is one straight-line block.
+// (One loop for the whole sequence, a Philox block per lane and round with each lane stepping through its own state
+// machine, was measured too: the per-round selects of that state cost far more than the blocks it saved, 25 % slower.)
+struct HitDraws {
+  uint64_t tri;   // the light triangle's index
+  uint64_t a, b;  // the (u, v) pair that was kept
+  uint64_t th;    // u_theta's draw (the specular lobe; a dummy 0.5 otherwise)
+  uint64_t qa, qb; // the +-1 pair that was kept
+  bool spec;      // gen_bool(f)
+};
+// sf: sample_f runs (depth < max_bounces); f: sample_f's lobe probability; mc (CONSTS): the material's constants, with
+// gen_bool(f)'s threshold among them
+template <bool CONSTS = false>
+RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, HitDraws& o, const MatConsts* mc = nullptr) {
+  o.tri = gen_index_zone(r, n, zone);
+  next2_u64(r, o.a, o.b);
+  while ((o.a >> 11) + (o.b >> 11) >= (1ull << 53) + 2ull) {
+    PROF_COUNT(PF_P_REJECT);
+    next2_u64(r, o.a, o.b);
+  }
+  o.th = 1ull << 63; o.qa = 0; o.qb = 0; o.spec = false;
+  if (!sf) return;
+  if constexpr (CONSTS) o.spec = f == 1.0 ? true : next_u64(r) < mc->p_int; // gen_bool: no draw when f == 1.0
+  else o.spec = gen_bool(r, f);
+  if (o.spec) o.th = next_u64(r);
+  for (;;) {
+    PROF_COUNT(PF_P_REJECT);
+    next2_u64(r, o.qa, o.qb);
+    const double x = u52_of(o.qa) * 2.0 + -1.0, y = u52_of(o.qb) * 2.0 + -1.0;
+    const double sum = x * x + y * y;
+    if (o.spec ? sum < 1.0 : sum <= 1.0) break;
+  }
+}
+
+// bsdf() for an opaque material: both directions outside (the reflection case) or zero, its early return a select
+// (CONSTS: m2, m2 * PI, f0 and one - f0 from the material's constants)
+template <bool CONSTS = false>
+RPT_DEV D3 bsdf_opaque(const Material& m, D3 n, D3 wo, D3 wi, const MatConsts* mc = nullptr) { // material.rs:125-170
+  D3 color = ld3(m.color);
+  double n_dot_wi = dot(n, wi);
+  double n_dot_wo = dot(n, wo);
+  const bool lit = !__builtin_signbit(n_dot_wi) && !__builtin_signbit(n_dot_wo);
+  const D3 one = mk(1, 1, 1);
+  double m2, m2pi;
+  D3 f0, omf0;
+  if constexpr (CONSTS) {
+    m2 = mc->m2; m2pi = mc->m2pi;
+    f0 = ld3(mc->f0); omf0 = ld3(mc->omf0);
+  } else {
+    m2 = m.roughness * m.roughness;
+    m2pi = m2 * PI;
+    double f0s = pow2((m.index - 1.0) / (m.index + 1.0));
+    f0 = lerp(mk(f0s, f0s, f0s), color, m.metallic);
+    omf0 = one - f0;
+  }
+  D3 h = normalize(wi + wo); // (wi * 1.0 + wo in bsdf)
+  double wo_dot_h = dot(wo, h);
+  double n_dot_h = dot(n, h);
+  double nh2 = pow2(n_dot_h);
+  double dd = rptc_exp((nh2 - 1.0) / (m2 * nh2)) / (m2pi * nh2 * nh2);
+  D3 f = f0 + omf0 * pow5(1.0 - wo_dot_h);
+  double ga = n_dot_wi * n_dot_h, gb = n_dot_wo * n_dot_h;
+  double g = fmin(ga, gb);
+  g = (2.0 * g) / wo_dot_h;
+  g = fmin(g, 1.0);
+  D3 q = dd * f * g / (4.0 * n_dot_wo * n_dot_wi);
+  D3 diffuse = cmul(one - f, color) / PI;
+  return lit ? q + diffuse : mk(0, 0, 0);
+}
+
+// sample_f() for an opaque material on the drawn values: both lobes' local vectors, the lane's one behind a select
+template <bool CONSTS = false>
+RPT_DEV void sample_f_opaque(const Material& m, D3 n, D3 wo, double f, const HitDraws& dr, D3& wi, double& pdf,
+                             const MatConsts* mc = nullptr) {
+  double m2; // material.rs:224-313
+  if constexpr (CONSTS) m2 = mc->m2;
+  else m2 = m.roughness * m.roughness;
+  const double u_theta = (double)(dr.th >> 11) * (1.0 / 9007199254740992.0);
+  const double x = u52_of(dr.qa) * 2.0 + -1.0, y = u52_of(dr.qb) * 2.0 + -1.0;
+  const double sum = x * x + y * y;
+  double theta = rptc_atan(sqrt(m2 * -rpt_log(u_theta)));
+  double sin_t, cos_t;
+  rptc_sincos_pio2(theta, &sin_t, &cos_t);
+  double diff = x * x - y * y;
+  double cx = diff / sum, cy = 2.0 * x * y / sum;
+  const D3 loc = dr.spec ? mk(cx * sin_t, cy * sin_t, cos_t) : mk(x, y, sqrt(1.0 - x * x - y * y));
+  const D3 world = local_to_world_mul(n, loc);
+  wi = dr.spec ? -(wo - world * (dot(world, wo) * 2.0)) : world; // -glm::reflect_vec(wo, h)
+  double p = 0.0;
+  {
+    D3 h = normalize(wi + wo);
+    double p_h;
+    if constexpr (CONSTS) { // beckmann_pdf with its PI * m2 from the table (the product m2 * PI: the same number)
+      double cos_t = fabs(dot(h, n));
+      double sin_t = sqrt(1.0 - cos_t * cos_t);
+      p_h = (1.0 / (mc->m2pi * pow3(cos_t))) * rptc_exp(-pow2(sin_t / cos_t) / m2);
+    } else {
+      p_h = beckmann_pdf(m2, n, h);
+    }
+    p += f * p_h / (4.0 * fabs(dot(h, wo)));
+  }
+  p += (1.0 - f) * fmax(dot(wi, n), 0.0) * FRAC_1_PI;
+  pdf = p;
+}
+
+// illuminate() of an untransformed mesh light on the drawn values (light.rs:23-47, mesh.rs:84-98, kdtree.rs:138-143)
+// (CONSTS: Shape::sample's pdf of the drawn triangle, (1 / area) / num_prims, from the wave's table)
+template <bool CONSTS = false>
+RPT_DEV void illuminate_mesh(CLight& l, CTree& tr, const Tri* __restrict__ tp, D3 pos, const HitDraws& dr, D3& intensity,
+                             D3& wi, double& dist, const double* light_pdf = nullptr) {
+  const double u = (double)(dr.a >> 11) * (1.0 / 9007199254740992.0), v = (double)(dr.b >> 11) * (1.0 / 9007199254740992.0);
+  double w = 1.0 - u - v;
+  D3 v1 = ld3(tp->v), v2 = ld3(tp->v + 3), v3 = ld3(tp->v + 6);
+  D3 n1 = ld3(tp->v + 9), n2 = ld3(tp->v + 12), n3 = ld3(tp->v + 15);
+  SampleOut s{u * v1 + v * v2 + w * v3, normalize(u * n1 + v * n2 + w * n3), 0.0};
+  if constexpr (CONSTS) {
+    s.p = light_pdf[dr.tri];
+  } else {
+    double area = 0.5 * length(cross(v2 - v1, v3 - v1));
+    s.p = 1.0 / area;
+    s.p = s.p / (double)tr.num_prims;
+  }
+  D3 disp = s.v - pos;
+  double len = length(disp);
+  double cosine = fmax(-dot(disp, s.n), 0.0) / len;
+  double surface_area = fmax(cosine, 0.0) / (len * len);
+  intensity = ld3(l.mat_color) * l.mat_emittance * surface_area / s.p;
+  wi = disp / len;
+  dist = len;
+}
+#endif

@@ -1,4 +1,4 @@
-"""rpt_paths<KdFlat, false, true> (kernels/paths.inc FUSE, flat_query2) on a real MI355X: a hit's shadow ray and bounce
+"""rpt_paths<KdFlat, false, true> (kernels/paths.inc FUSE, paths_flat.inc flat_query2) on a real MI355X: a hit's shadow ray and bounce
 ray are traced in one two-ray query, after illuminate, sample_f and both bsdf evaluations.  Every frame is compared BIT
 for bit with the oracle through the persistent kernel, with the closest-hit and shadow ray counts equal to the oracle's:
 C2 at small odd sizes and bounces 0-8, sample counts that are not a multiple of the work item's chunk, later sample

@@ -391,6 +391,51 @@ def test_texture_environments_through_the_other_instantiations(name):
         g.close()
 
 
+def _thin_lens_scene(kernel):
+    """-> (scene, focused camera): three spheres under a colour environment (rpt_paths<KdFlatG>), the polygon room at the
+    smallest wall count whose objects (four walls and a cube, with the lamp) reach the object filter's threshold (KdFlatF), the
+    small dragon's multi-leaf mesh (KdLds)"""
+    from rpt_amd import Camera, Environment, Material, Object, Scene, hex_color, sphere
+    if kernel == "KdFlatG":
+        scene = Scene()
+        scene.environment = Environment.Color((0.6, 0.7, 0.9))
+        mats = [Material.clear(1.5, 0.0001), Material.metallic_(hex_color(0xFFFFFF), 0.1), Material.diffuse(hex_color(0x6F5D48))]
+        for i in range(3):
+            scene.add(Object(sphere().scale((0.6, 0.6, 0.6)).translate((1.4 * (i - 1), 0.1 * i, -0.8 * i))).material(mats[i]))
+        return scene, Camera.look_at((0.3, 0.8, 5.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 0.7).focus((0.0, 0.0, 0.0), 0.2)
+    if kernel == "KdFlatF":
+        scene, cam = _polygon_room(4)
+        return scene, cam.focus((0.0, 0.0, 0.0), 0.15)
+    scene, cam, _ = small_scenes.small("dragon")
+    return scene, cam.focus(tuple(cam.eye[k] + 3.0 * cam.direction[k] for k in range(3)), 0.05)
+
+
+@pytest.mark.parametrize("kernel", ["KdFlatG", "KdFlatF", "KdLds"])
+def test_thin_lens_camera_through_the_instantiations_without_a_ray_stash(kernel, monkeypatch, capfd):
+    """aperture > 0 where rpt_paths generates its camera rays in the loop itself (kernels/paths.inc: the ray-generation
+    site of the instantiations without a stash repeats camera_ray's body): the persistent kernel's frame is the wavefront
+    pipeline's, bit for bit, and the launch diagnostics name the instantiation."""
+    monkeypatch.setenv("RPTGPU_PRINT_LAUNCH", "1")
+    scene, cam = _thin_lens_scene(kernel)
+    assert cam.aperture > 0.0
+    g = GpuScene(scene, 0)
+    frames = {}
+    try:
+        for flags in (_abi.RPT_FLAG_PERSISTENT, _abi.RPT_FLAG_WAVEFRONT):
+            g.reset_stats()
+            capfd.readouterr()
+            frames[flags] = g.render_batch(cam, make_params(64, 48, 3, 4, seed=131, flags=flags))
+            lines = [ln for ln in capfd.readouterr().err.splitlines() if ln.startswith("rpt_paths<")]
+            if flags == _abi.RPT_FLAG_PERSISTENT:
+                assert g.stats().kernel_launches[_abi.RPT_K_PATHS] >= 1  # the persistent kernel ran
+                assert lines and all(ln.startswith("rpt_paths<%s>" % kernel) for ln in lines), lines
+    finally:
+        g.close()
+    a, b = frames[_abi.RPT_FLAG_PERSISTENT], frames[_abi.RPT_FLAG_WAVEFRONT]
+    assert ((a == b) | (np.isnan(a) & np.isnan(b))).all(), (kernel, np.abs(a - b).max())
+    assert (b != 0).any()
+
+
 @pytest.mark.parametrize("sort", ["0", "1"])
 @pytest.mark.parametrize("name", small_scenes.NAMES)
 def test_per_tree_queries_and_ray_sorting_do_not_change_the_image(name, sort, monkeypatch):
@@ -829,7 +874,7 @@ def test_flat_scenes_batched_leaf_tests_match_the_oracle(oracle, n_walls, transf
         pp = make_params(p.width, p.height, p.max_bounces, p.iterations, p.exposure_value, p.seed, flags=flags)
         img = g.render_batch(cam, pp)
         assert (img == ref).all(), (n_walls, flags, np.abs(img - ref).max())
-    # scenes of 8..64 objects run the flat kernel behind the object filter (paths.inc flat_query_filtered); the same
+    # scenes of 8..64 objects run the flat kernel behind the object filter (paths_flat.inc flat_query_filtered); the same
     # scene without it (the batched runs alone), and with it from the first object on
     for min_objects in ("0", "1"):
         os.environ["RPTGPU_OBJECT_FILTER_MIN"] = min_objects
@@ -852,7 +897,7 @@ def test_flat_scenes_batched_leaf_tests_match_the_oracle(oracle, n_walls, transf
 
 
 def test_object_filter_far_cameras_axis_parallel_rays_and_unfilterable_objects(oracle):
-    # the object filter (host_scene.cpp fill_object_boxes, paths.inc flat_query_filtered) where its f32 arithmetic and
+    # the object filter (host_scene.cpp fill_object_boxes, paths_flat.inc flat_query_filtered) where its f32 arithmetic and
     # its exemptions are stressed: an unbounded Plane among the objects, a sphere a thousand times smaller than the
     # scene, a placement with condition number 1e5 (exempt), a mesh with a sliver (exempt), objects in the corners of
     # the grid, a directional light along an axis (shadow rays with two zero components), cameras inside an object's

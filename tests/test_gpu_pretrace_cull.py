@@ -1,4 +1,4 @@
-"""The pre-trace pass of rpt_paths<KdFlat, false, true> (kernels/paths.inc cull_skip_mask, RPT_PRETRACE_CULL) on a real
+"""The pre-trace pass of rpt_paths<KdFlat, false, true> (kernels/paths_flat.inc cull_skip_mask, RPT_PRETRACE_CULL) on a real
 MI355X: under a pinhole camera a wave none of whose pending pixels lies in a cube's screen rectangle (host_scene.cpp
 pinhole_screen_rect) leaves that cube's exact test out of the pass.  A skipped test is one that would have rejected, so
 every frame must equal the oracle's BIT for bit, with the oracle's closest-hit and shadow ray counts (a skipped object

@@ -1,4 +1,4 @@
-"""rpt_paths<KdFlat, false, true, true> (kernels/paths.inc SceneConsts, RPT_SCENE_CONSTS) on a real MI355X: what a hit
+"""rpt_paths<KdFlat, false, true, true> (kernels/paths_consts.inc SceneConsts, RPT_SCENE_CONSTS) on a real MI355X: what a hit
 derives from the scene alone — the material's m2, f0, lobe probability and gen_bool's integer, a cube's world normals,
 and in builds with that group (-DRPT_SCENE_CONSTS=7) the pdf of the light's triangle — is computed once per wave into
 tables and read from there.  The tables are filled by the

@@ -1,4 +1,4 @@
-"""rpt_paths<KdFlat, false, true>'s fast shading form (kernels/paths.inc hit_draws, RPT_SHADE_SPLIT) on a real MI355X:
+"""rpt_paths<KdFlat, false, true>'s fast shading form (kernels/paths_shade.inc hit_draws, RPT_SHADE_SPLIT) on a real MI355X:
 a wave whose light is an untransformed mesh and whose hits are opaque takes every draw of its hits first (the light
 triangle's index and (u, v) pairs, gen_bool, u_theta and the +-1 pairs) and shades them in one straight-line block.
 Every frame is compared BIT for bit with the oracle, with the closest-hit and shadow ray counts equal to the oracle's:
