@@ -352,11 +352,12 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   h->lbuf.alloc(std::max<uint64_t>(1, (uint64_t)pl.spp_l * 3 * npix));
   if (print_launch)
     std::fprintf(stderr, "rpt_paths<%s>: %d blocks/CU x %d CUs -> %u blocks, %u samples per work item, %u launch(es) of %u spp, "
-                 "dynamic LDS %u B per wave (the flat scene's tables)%s%s%s\n",
+                 "dynamic LDS %u B per wave (the flat scene's tables)%s%s%s%s\n",
                  flat ? (lay.obj_filter ? "KdFlatF" : lay.n_tris ? "KdFlat" : "KdFlatG") : "KdLds", pl.per_cu, h->num_cus, pl.nblocks,
                  pl.chunk, pl.n_launch, pl.spp_l, flat_lds, park ? " + parked environment lookups" : "",
                  flat && lay.n_tris && lay.fuse_query && !park ? ", shadow and bounce rays in one query" : "",
-                 flat && lay.n_tris && lay.fuse_query && !park && lay.scene_consts ? ", a hit's scene constants from the wave's tables" : "");
+                 flat && lay.n_tris && lay.fuse_query && !park && lay.scene_consts ? ", a hit's scene constants from the wave's tables" : "",
+                 RPT_HIT_POOL && flat && lay.n_tris && lay.fuse_query && !park ? ", pre-traced hits in a wave-level pool" : "");
   h->counters.alloc(4);
   h->pcounters.alloc(16);
   HIP_TRY(hipMemsetAsync(h->pcounters.p, 0, 16 * sizeof(unsigned long long), st));

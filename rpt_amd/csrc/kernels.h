@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "device_types.h"
+#include "hit_pool.h"
 #include "launch_limits.h"
 
 // meshes per batched run of the flat path kernel (kernels/paths_flat.inc flat_query; api_scene.cpp caps Inst::plane_use with it)
@@ -47,16 +48,37 @@
 // from tables that every wave fills once, in its prologue, with the loop's own expressions (kernels/paths_consts.inc
 // SceneConsts; FlatLayout::scene_consts when the wave's LDS share holds them, else the kernel without them);
 // 0: every hit computes them, the parent's loop (A/B builds).  The value is a mask of the groups that are built:
-// 1 = the materials' constants, 2 = the light's pdfs, 4 = the cubes' normals.  The default leaves the light's pdfs out:
-// with them the kernel spills 293 SGPRs (284 without, 287 before the tables), whichever way their table is addressed —
-// although C2 gains 1.4 % more with them (profiles/scene_consts_ab.txt)
+// 1 = the materials' constants, 2 = the light's pdfs, 4 = the cubes' normals.  All three are built: the light's pdfs
+// cost the kernel nine more spilled SGPRs (301 against 292), whichever way their table is addressed, and were first
+// left out for that — but its spilled scalars are cold, and on top of the pool of pre-traced hits C2 gains 2.2 % with
+// them (measured at RPT_POOL_REFILL=48), spreads disjoint (profiles/hit_pool_ab.txt; 1.4 % in profiles/scene_consts_ab.txt)
 #ifndef RPT_SCENE_CONSTS
-#define RPT_SCENE_CONSTS 5
+#define RPT_SCENE_CONSTS 7
 #endif
 #define RPT_MAT_CONSTS_BYTES 88u   // per object (kernels/paths_consts.inc MatConsts)
 #define RPT_CUBE_NORMALS_BYTES 144u // per cube of a two-cube block: [face][3] doubles
 #define RPT_PATHS_STASH_LDS 4864u
 #define RPT_PATHS_STASH_HIT_LDS 6656u
+// RPT_HIT_POOL=1: the fused kernels (rpt_paths<KdFlat, false, true[, true]>) keep their pre-traced camera hits in a
+// wave-level FIFO of RPT_POOL_CAP self-contained entries in the place of the per-lane RayStashHit (kernels/paths.inc
+// HitPool, index arithmetic: hit_pool.h): any lane shades any hit, and the wave generates and pre-traces only once
+// RPT_POOL_REFILL slots are free, or when it must, so a pre-trace pass runs at that many lanes instead of half of them.
+// 0: the per-lane stash (A/B builds).  An entry is 100 bytes; the default pool is smaller than the stash it replaces, so
+// a scene that fits the per-lane form fits this one (static_assert below: a larger RPT_POOL_CAP has to go through
+// api_scene.cpp's three fit checks, and a scene without the room has to keep the per-lane form)
+#ifndef RPT_HIT_POOL
+#define RPT_HIT_POOL 1
+#endif
+#ifndef RPT_POOL_CAP
+#define RPT_POOL_CAP 64u
+#endif
+#ifndef RPT_POOL_REFILL
+#define RPT_POOL_REFILL 56u
+#endif
+#define RPT_PATHS_POOL_LDS (RPT_POOL_CAP * 100u)
+static_assert(RPT_POOL_CAP >= 64u && RPT_POOL_REFILL >= 1u && RPT_POOL_REFILL <= RPT_POOL_CAP,
+              "a refill of 64 lanes has to fit an empty pool, and a full pool has to fall to the refill mark");
+static_assert(RPT_PATHS_POOL_LDS <= RPT_PATHS_STASH_HIT_LDS, "the host's fit checks leave room for RayStashHit only");
 // what the host leaves room for in a KdFlat scene's LDS layout (api_scene.cpp)
 #define RPT_PATHS_STASH_MAX_LDS (RPT_RAY_STASH >= 2 ? RPT_PATHS_STASH_HIT_LDS : RPT_PATHS_STASH_LDS)
 // flat scenes with a texture environment: the lanes' queues of parked lookups, RPT_PARK_K entries each, at the end of the

@@ -1,5 +1,5 @@
 // kernels/paths.inc — the persistent path kernel rpt_paths<KdLds|KdFlat>: contract, work hand-out, record ring, parked lookups,
-// ray stash, the loop; rpt_sum_samples.  (Its flat-scene queries, tables and fast shading: paths_flat / _consts / _shade.inc.)
+// ray stash, the fused kernels' wave-level pool of pre-traced hits, the loop; rpt_sum_samples.  (Its flat-scene queries, tables and fast shading: paths_flat / _consts / _shade.inc.)
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
 
 // ------------------------------------------------------------------ persistent path kernel
@@ -45,6 +45,11 @@
 // `depth` is the only one written in the iteration, and into the slot it had before, so per lane and iteration the ring
 // sees the same events in the same order as above: at most one record, the headers before the fold step; the bound
 // stands.
+// With the wave-level pool of pre-traced hits (POOL below, RPT_HIT_POOL: the fused kernels) the pop takes the swap's place:
+// a lane whose bounce ray escaped ends that path when it pops a hit, and the popped path starts at depth 0 in the same
+// iteration — by whichever lane generated it, which the ring, private to the lane that RUNS a path, never sees.  Still at
+// most one record per lane and iteration and every header before the fold step: rpt_fold_ring_slots() and
+// tests/test_ray_stash_swap_model.py hold as they are.
 //
 // Environment lookups are PARKED (round 5; flat scenes whose environment is a texture).  A ray that escapes ends its
 // path with Hdri::get_color (environment.rs:25-52: atan2, acos, four texels) — one round of it per loop iteration for
@@ -273,6 +278,34 @@ RPT_DEV void stash_take_hit(const RayStashHit& st, uint32_t lane, D3& pos, D3& d
   nrm = mk(st.v[7][lane], st.v[8][lane], st.v[9][lane]);
   obj = (int)st.u[5][lane];
 }
+// RPT_HIT_POOL (kernels.h; the fused kernels): the wave's FIFO of pre-traced camera hits, [field][slot] — consecutive
+// ranks of a push or a pop touch consecutive slots, as the lanes of the stash do.  An entry is all a lane needs to go on
+// with the sample: v[0..2] the hit point, v[3..5] the incoming direction, v[6] the stream's cached half, v[7..9] the
+// normal, or the environment's colour if the ray escaped; u: the object (-1: escaped), the work item's p_local, its
+// pixel, the sample, the stream's draw counter.  Head and count are wave-uniform (hit_pool.h has the arithmetic)
+struct HitPool {
+  double v[10][RPT_POOL_CAP];
+  uint32_t u[5][RPT_POOL_CAP];
+};
+static_assert(sizeof(HitPool) == RPT_PATHS_POOL_LDS, "kernels.h sizes the wave's LDS budget with it");
+RPT_DEV void pool_put(HitPool& hp, uint32_t slot, const D3& pos, const D3& d, const D3& nrm, int obj, uint32_t p_local,
+                      uint32_t pixel, uint32_t s, const Rng& r) {
+  hp.v[0][slot] = pos.x; hp.v[1][slot] = pos.y; hp.v[2][slot] = pos.z;
+  hp.v[3][slot] = d.x; hp.v[4][slot] = d.y; hp.v[5][slot] = d.z;
+  hp.v[6][slot] = __longlong_as_double((long long)r.hi);
+  hp.v[7][slot] = nrm.x; hp.v[8][slot] = nrm.y; hp.v[9][slot] = nrm.z;
+  hp.u[0][slot] = (uint32_t)obj; hp.u[1][slot] = p_local; hp.u[2][slot] = pixel; hp.u[3][slot] = s; hp.u[4][slot] = r.draw;
+}
+RPT_DEV void pool_take(const HitPool& hp, uint32_t slot, const Frame& fr, D3& pos, D3& d, D3& nrm, int& obj, uint32_t& p_local,
+                       uint32_t& s, Rng& r) {
+  pos = mk(hp.v[0][slot], hp.v[1][slot], hp.v[2][slot]);
+  d = mk(hp.v[3][slot], hp.v[4][slot], hp.v[5][slot]);
+  nrm = mk(hp.v[7][slot], hp.v[8][slot], hp.v[9][slot]);
+  obj = (int)hp.u[0][slot]; p_local = hp.u[1][slot]; s = hp.u[3][slot];
+  r = rng_make(fr.seed, hp.u[2][slot], fr.sample_base + s, 0);
+  r.draw = hp.u[4][slot];
+  r.hi = (uint64_t)__double_as_longlong(hp.v[6][slot]);
+}
 #ifndef RPT_STASH_REFILL_MIN
 #define RPT_STASH_REFILL_MIN 32 // RayStashHit: the wave also refills once this many lanes have an empty stash
 #endif
@@ -451,9 +484,34 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
   // pre-traces of a refill run in a pass of their own.  Per lane and iteration the ring sees the same events as without
   // FUSE (a path that escaped ends when its hit is taken, before the shading), so the bound at the top of this file holds.
   static_assert(!FUSE || PRETRACE, "the fused form is a form of the pre-traced kernel");
-  using StashT = typename std::conditional<PRETRACE, RayStashHit, RayStash>::type;
+  //
+  // POOL (RPT_HIT_POOL; the fused kernels): the pre-traced hits wait in a FIFO of the WAVE, not in the lane that made
+  // them.  Nothing in the result depends on which lane runs a sample — the Philox stream is keyed by (seed, pixel,
+  // sample), the radiance goes to lbuf[sample][channel][pixel], and the ring is private to whichever lane runs the
+  // path — but with a per-lane stash a hit can only be used by its own lane, so the wave had to refill as soon as ONE
+  // lane had neither a path nor a stash: pre-trace passes of 30 lanes of 64 on C2, at the price of 64.  Here a lane
+  // keeps a generation CURSOR of its own (work item g_p_local, next sample g_s; ~0 = the item ran out), decoupled from
+  // the path it runs (s, p_local, rng), and an entry of the pool is self-contained (HitPool).  At the top of an
+  // iteration the wave refills (hit_pool.h rpt_pool_refill) once RPT_POOL_REFILL slots are free, or when the pool
+  // cannot serve the lanes that need a hit: every lane with work, by ballot rank up to the free slots, fetches an item
+  // if its own ran out (a lane still asks at most once past the end), generates its next sample's camera ray, traces it
+  // and pushes the hit — one straight block, so nothing of a pending ray lives across the loop.  The lanes that need a
+  // hit — no running path, or a bounce ray that escaped: such a path ends first, exactly as at the swap — are ranked
+  // by a ballot and rank r takes entry r of the pool while there is one; a lane that finds none idles this iteration
+  // (its escaped path ends in the shading phase, as before).  Per lane and iteration the ring sees what it saw: at most
+  // one new record, and every header before the fold step; a lane may still end two paths in one iteration, the
+  // escaped one and a depth-0 hit it pops, so the bound at the top of this file and its model
+  // (tests/test_ray_stash_swap_model.py) stand.  The same rays from the same draws; only who runs them changes.
+  constexpr bool POOL = FUSE && RPT_HIT_POOL != 0;
+  using StashT = typename std::conditional<POOL, HitPool, typename std::conditional<PRETRACE, RayStashHit, RayStash>::type>::type;
   __shared__ typename std::conditional<STASH, StashT, int>::type stash_store;
   auto& stash = *reinterpret_cast<StashT*>(&stash_store);
+  // POOL only (the other instantiations carry an empty struct): the lane's generation cursor, the pool's head and count
+  struct PoolState { uint32_t g_p_local = 0, g_s = ~0u; uint32_t head = 0, cnt = 0; }; // (head, cnt: wave-uniform)
+  struct NoPoolState {};
+  [[maybe_unused]] typename std::conditional<POOL, PoolState, NoPoolState>::type ps;
+  // the per-lane stash's state; the POOL instantiations use none of stash_valid, pend and near, nor pixel and s_end above
+  // (the cursor and the entry carry what they held), and the compiler drops them there
   bool stash_valid = false, exhausted = false; // exhausted: the work counter ran out for this lane
   bool pend = false; // PRETRACE: the stashed ray is not traced yet
 #if RPT_PRETRACE_CULL
@@ -469,7 +527,53 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
   PROF_INIT(); // -DRPT_PROF builds: wave / lane time per phase, printed by api_render.cpp under RPTGPU_PRINT_PHASES
 
   for (;;) {
-    if constexpr (STASH) {
+    if constexpr (POOL) {
+      // ---- refill the wave's pool of pre-traced hits (POOL above): fetch, camera ray, pre-trace, push
+      const uint32_t n_need = (uint32_t)__popcll(__ballot(!in_path || nx_obj < 0)); // the lanes that pop in this iteration
+      const uint64_t work_mask = __ballot(!exhausted);
+      if (work_mask != 0ull && rpt_pool_refill(ps.cnt, n_need, RPT_POOL_CAP, RPT_POOL_REFILL)) { // (wave-uniform)
+        // turns go by rank among the lanes with work: when a forced refill finds fewer free slots than such lanes, the low
+        // lanes generate and the high lanes' cursors lag, so at the very end of a launch the high lanes hold the last
+        // part-used items and the last refills are narrower than they could be — a tail of at most 64 items of `chunk`
+        // samples per wave, not measured on its own (the A/B's whole-launch times include it)
+        const bool turn = !exhausted && rpt_pool_rank(work_mask, lane) < rpt_pool_gen_limit(ps.cnt, RPT_POOL_CAP);
+        const bool want_item = turn && ps.g_s == ~0u;
+        uint32_t f_pixel = 0, f_s_end = 0; // (recomputed below: the cursor keeps neither)
+        const bool got = fetch_item(pa, fr, lane, want_item, pool, ps.g_p_local, f_pixel, ps.g_s, f_s_end);
+        if (want_item && !got) exhausted = true;
+        PROF_PHASE(PF_P_FETCH);
+        const bool gen = turn && !exhausted;
+        const uint64_t gen_mask = __ballot(gen);
+        if (gen) {
+          const uint32_t g_pixel = fr.pixels[ps.g_p_local];
+          D3 go, gd;
+          Rng gr;
+          camera_ray(fr, cam, dim, g_pixel, ps.g_s, go, gd, gr);
+          PROF_PHASE(PF_P_RAYGEN);
+          double t = INF;
+          D3 hn = mk(0, 0, 0);
+#if RPT_PRETRACE_CULL
+          const uint64_t skip = cull_skip_mask(pa.flat, cull_near(pa.flat, g_pixel, fr.width)); // (wave-uniform; 0 without the host's rectangles: every test runs)
+          PROF_COUNT(PF_P_PRETRACE);
+          const int ho = flat_query<false, true, CONSTS>(sc, &fl, go, gd, -INF, t, hn, skip);
+#else
+          const int ho = flat_query<false, false, CONSTS>(sc, &fl, go, gd, -INF, t, hn);
+#endif
+          n_ext++;
+          if (ho < 0) hn = env_color(sc, gd); // renderer.rs:147
+          pool_put(stash, rpt_pool_slot(ps.head, ps.cnt + rpt_pool_rank(gen_mask, lane), RPT_POOL_CAP), go + t * gd, gd, hn, ho,
+                   ps.g_p_local, g_pixel, ps.g_s, gr);
+          // the cursor's next sample; the item ends with its chunk, or with the launch's samples
+          ps.g_s++;
+          if (ps.g_s % pa.chunk == 0u || ps.g_s == pa.spp) ps.g_s = ~0u;
+          PROF_PHASE(PF_P_HIT);
+        }
+        rpt_pool_after_push(ps.cnt, gen_mask);
+        __syncthreads(); // (the block is this wave) the pushes, before other lanes pop them
+      }
+      done = !in_path && exhausted; // (this lane's part; the wave goes on while the pool holds a hit)
+      if (ps.cnt == 0u && __ballot(!done || (fold_st & 0xffffu) != 0u) == 0) break; // (a lane without work still lets its walker finish)
+    } else if constexpr (STASH) {
       // ---- generate ahead, when some lane must: it has no running path and no stashed ray
       bool refill = __ballot(!in_path && !stash_valid && !exhausted) != 0ull;
       if constexpr (PRETRACE) refill = refill || __popcll(__ballot(!stash_valid && !exhausted)) >= RPT_STASH_REFILL_MIN;
@@ -549,23 +653,25 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       // pre-traces run here, in a pass of their own
       h_pos = nx_pos; h_nrm = nx_nrm; h_obj = nx_obj;
       nx_pos = mk(0, 0, 0); nx_nrm = mk(0, 0, 0); nx_obj = -1; // (so that no old value lives across the queries below)
-      if (__ballot(pend) != 0ull) {
-        if (pend) {
-          D3 so, sd;
-          stash_take_ray(stash, lane, so, sd);
-          double t = INF;
-          D3 hn = mk(0, 0, 0);
+      if constexpr (!POOL) {
+        if (__ballot(pend) != 0ull) {
+          if (pend) {
+            D3 so, sd;
+            stash_take_ray(stash, lane, so, sd);
+            double t = INF;
+            D3 hn = mk(0, 0, 0);
 #if RPT_PRETRACE_CULL
-          const uint64_t skip = cull_skip_mask(pa.flat, near); // (wave-uniform; 0 without the host's rectangles: every test runs)
-          PROF_COUNT(PF_P_PRETRACE);
-          const int ho = flat_query<false, true, CONSTS>(sc, &fl, so, sd, -INF, t, hn, skip);
+            const uint64_t skip = cull_skip_mask(pa.flat, near); // (wave-uniform; 0 without the host's rectangles: every test runs)
+            PROF_COUNT(PF_P_PRETRACE);
+            const int ho = flat_query<false, true, CONSTS>(sc, &fl, so, sd, -INF, t, hn, skip);
 #else
-          const int ho = flat_query<false, false, CONSTS>(sc, &fl, so, sd, -INF, t, hn);
+            const int ho = flat_query<false, false, CONSTS>(sc, &fl, so, sd, -INF, t, hn);
 #endif
-          n_ext++;
-          if (ho < 0) hn = env_color(sc, sd); // renderer.rs:147
-          stash_put_hit(stash, lane, so + t * sd, hn, ho);
-          pend = false;
+            n_ext++;
+            if (ho < 0) hn = env_color(sc, sd); // renderer.rs:147
+            stash_put_hit(stash, lane, so + t * sd, hn, ho);
+            pend = false;
+          }
         }
       }
     } else if constexpr (PRETRACE) {
@@ -595,7 +701,22 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         }
       }
     }
-    if constexpr (PRETRACE) {
+    if constexpr (POOL) {
+      PROF_PHASE(PF_P_HIT);
+      // ---- the pop, in the place of the swap below: a path whose ray escaped ends here if the pool has a hit for its lane,
+      // and that lane, like a lane without a running path, takes the hit — sample, Philox position and all — into
+      // this iteration's shading
+      const bool need = !in_path || h_obj < 0;
+      const uint64_t need_mask = __ballot(need);
+      if (need && rpt_pool_pop_ok(rpt_pool_rank(need_mask, lane), ps.cnt)) {
+        if (in_path) end_path(pa, fr, rec, fold_l, fold_u, lane, fold_st, ring, h_nrm, depth, s, p_local);
+        pool_take(stash, rpt_pool_slot(ps.head, rpt_pool_rank(need_mask, lane), RPT_POOL_CAP), fr, h_pos, d, h_nrm, h_obj, p_local, s, rng);
+        depth = 0;
+        in_path = true;
+      }
+      rpt_pool_after_pop(ps.head, ps.cnt, need_mask, RPT_POOL_CAP);
+      PROF_PHASE(PF_P_RAYGEN);
+    } else if constexpr (PRETRACE) {
       PROF_PHASE(PF_P_HIT);
       // ---- the swap: a path whose ray escaped ends here (as in the miss branch below), and a lane without a running
       // path takes its stashed one — sample, Philox position and hit — into this iteration's shading
