@@ -720,6 +720,26 @@ class Renderer {
     check(rptgpu_trace_rays(handle_, n, origins.data(), dirs.data(), streams.empty() ? nullptr : streams.data(), &q, rgb.data()));
     return rgb;
   }
+  // addition: light probes baked on the device (rptgpu_bake_probes, include/rpt_gpu.h).  positions: xyz per probe; kind =
+  // RPT_PROBE_SH9 -> 27 doubles per probe, [9][3]: the radiance around it in the spherical harmonics of bands 0-2;
+  // RPT_PROBE_IRRADIANCE (normals: xyz per probe) -> rgb per probe, the irradiance of a surface there.  Each probe is
+  // num_samples paths of max_bounces bounces drawn from the stream (seed, streams[i] or i, sample_index_base + k),
+  // whatever other probes the call holds.
+  std::vector<double> bake_probes(uint32_t kind, const std::vector<double>& positions, const std::vector<double>& normals = {},
+                                  const std::vector<uint32_t>& streams = {}, uint64_t sample_index_base = 0) {
+    ensure_scene();
+    const size_t n = positions.size() / 3;
+    const bool with_normals = kind == RPT_PROBE_IRRADIANCE;
+    if (positions.size() != 3 * n || normals.size() != (with_normals ? 3 * n : 0) || (!streams.empty() && streams.size() != n))
+      throw std::invalid_argument("bake_probes: positions hold xyz per probe, normals too (RPT_PROBE_IRRADIANCE only), streams one id per probe");
+    RptProbeQuery q{};
+    q.struct_size = sizeof(RptProbeQuery); q.kind = kind; q.samples = num_samples_; q.max_bounces = max_bounces_;
+    q.seed = seed_; q.sample_index_base = sample_index_base;
+    std::vector<double> out((kind == RPT_PROBE_SH9 ? 27 : 3) * n);
+    check(rptgpu_bake_probes(handle_, n, positions.data(), with_normals ? normals.data() : nullptr,
+                             streams.empty() ? nullptr : streams.data(), &q, out.data()));
+    return out;
+  }
   // addition: iterative_render with the Buffer kept on the device (rptgpu_buffer_*), followed by the feature-guided
   // a-trous filter of rptgpu_buffer_denoise (include/rpt_gpu.h) guided by the first hits of samples 0 .. feature_samples-1.
   // At least two batches (num_samples > callback_interval), else the library refuses: one batch has no variance.

@@ -452,6 +452,59 @@ int rptgpu_trace_rays(rptgpu_scene* h, uint64_t n, const double* origins, const 
 int rptgpu_trace_rays_device(rptgpu_scene* h, uint64_t n, const void* d_origins, const void* d_dirs,
                              const void* d_streams /* may be NULL */, const RptRayQuery* q, void* d_out_rgb, void* stream);
 
+/* ---- light probes baked on the device: per probe, `samples` directions made from the Philox stream, one path along each
+ * (Renderer::trace_ray, as rptgpu_trace_rays runs it), projected as the directions come back.  Additions within ABI
+ * version 7, detected by symbol (dlsym "rptgpu_bake_probes").  Probe i stands at positions[3i..]; out is [n][9][3] f64 for
+ * RPT_PROBE_SH9 (radiance in the real spherical harmonics of bands 0-2) and [n][3] for RPT_PROBE_IRRADIANCE (the
+ * irradiance of a surface with normal normals[3i..]).  24 B (48 B) in and 216 B (24 B) out per probe, whatever S is.
+ * THE STREAM CONTRACT.  Direction k of probe i is sample sample_index_base + k of the Philox4x32-10 stream keyed by `seed`
+ * (rptgpu_trace_rays' keying); its stream id is streams[i], or i (the probe's index in this call's arrays) when streams is
+ * NULL.  The direction is made from draw 0 on, and the path that leaves along it continues the SAME stream at the draw
+ * where the direction stopped — what a render's first kernel does behind the camera's draws.  So a probe's result depends
+ * on (its position, its normal, seed, its stream id, the sample indices, max_bounces) and on nothing else: not on the other
+ * probes of the call, on their order, on the pieces and passes the library cuts the call into, or on how a caller splits
+ * the PROBES over calls, handles or GPUs.
+ * DIRECTIONS, in plain f64, no contraction, the expressions in the order written:
+ *   RPT_PROBE_SH9         uniform on the sphere without transcendentals: (x1, x2) = UnitDisc (rand_distr 0.4: pairs of
+ *                         gen_range(-1, 1) until x1*x1 + x2*x2 <= 1);  s = x1*x1 + x2*x2;  r = 2.0*sqrt(1.0 - s);
+ *                         d = (x1*r, x2*r, 1.0 - 2.0*s)
+ *   RPT_PROBE_IRRADIANCE  d = Sphere::sample(normal).v (sphere.rs:52-64): cosine-weighted about normalize(normal).  A zero
+ *                         or non-finite normal yields whatever that function yields; it is not refused
+ * The ray is (position, d), used as given.
+ * RESULT.  L_k = Renderer::trace_ray of ray k: what rptgpu_trace_rays returns for it with iterations = 1, exposure_value =
+ * 0 and first_draw = the draws its direction took.  With S = samples and k ascending from sums that start at +0.0:
+ *   RPT_PROBE_SH9         acc[j][c] = acc[j][c] + L_k[c] * Y_j(d_k);  out[j][c] = acc[j][c] * (12.566370614359172 / (double)S)
+ *   RPT_PROBE_IRRADIANCE  acc[c] = acc[c] + L_k[c];                   out[c] = acc[c] * (3.141592653589793 / (double)S)
+ * The basis, in the order (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2), at d = (x, y, z):
+ *   Y0 = 0.28209479177387814                  Y1 = 0.4886025119029199*y            Y2 = 0.4886025119029199*z
+ *   Y3 = 0.4886025119029199*x                 Y4 = 1.0925484305920792*(x*y)        Y5 = 1.0925484305920792*(y*z)
+ *   Y6 = 0.31539156525252005*(3.0*(z*z) - 1.0)  Y7 = 1.0925484305920792*(x*z)      Y8 = 0.5462742152960396*(x*x - y*y)
+ * The call runs the wavefront pipeline as rptgpu_trace_rays does, in pieces of whole probes; RPT_FLAG_GENERAL_TRAVERSAL and
+ * RPT_FLAG_PROFILE_KERNELS are honoured, and RptStats advances as for a render (samples = n * S).  RPTGPU_PROBES_PIECE
+ * (environment, read per call; tests): the probes per piece.
+ * RPTGPU_E_INVALID_ARGUMENT, checked before any device work and with a detail naming the reason: a NULL RptProbeQuery, a
+ * wrong struct_size, an unknown kind, samples == 0, max_bounces > 254, a precision_mode other than
+ * RPT_PRECISION_F64_STRICT, RPT_FLAG_PERSISTENT, NULL positions or out with n > 0, NULL normals with
+ * RPT_PROBE_IRRADIANCE, more than 2^32 probes without stream ids, a NULL handle; RPTGPU_E_COMM for an abandoned handle.
+ * n == 0 returns RPTGPU_OK. */
+enum { RPT_PROBE_SH9 = 0, RPT_PROBE_IRRADIANCE = 1 };
+typedef struct RptProbeQuery {
+  uint32_t struct_size;       /* sizeof(RptProbeQuery) */
+  uint32_t kind;              /* RPT_PROBE_* */
+  uint32_t samples;           /* S: directions per probe, one path each, > 0 */
+  uint32_t max_bounces;       /* <= 254 */
+  uint64_t seed;
+  uint64_t sample_index_base; /* sample index of every probe's first direction */
+  uint32_t precision_mode;    /* RPT_PRECISION_F64_STRICT */
+  uint32_t flags;             /* as RptRayQuery: GENERAL_TRAVERSAL, PROFILE_KERNELS honoured; PERSISTENT refused */
+} RptProbeQuery;
+int rptgpu_bake_probes(rptgpu_scene* h, uint64_t n, const double* positions /* [n][3] */,
+                       const double* normals /* [n][3]; RPT_PROBE_IRRADIANCE only, else NULL */,
+                       const uint32_t* streams /* [n] or NULL */, const RptProbeQuery* q, double* out /* host */);
+/* The same with every array in device memory; `stream` and the synchronisation rule are rptgpu_trace_rays_device's. */
+int rptgpu_bake_probes_device(rptgpu_scene* h, uint64_t n, const void* d_positions, const void* d_normals,
+                              const void* d_streams /* may be NULL */, const RptProbeQuery* q, void* d_out, void* stream);
+
 /* ---- host utility: KdTree::new (kdtree.rs:108-119, construct kdtree.rs:235-345) over n
  * axis-aligned boxes (p_min xyz, p_max xyz interleaved: 6 doubles per box).  Returns the
  * flattened tree through malloc'ed arrays the caller releases with rptgpu_free.

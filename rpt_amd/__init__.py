@@ -7,12 +7,13 @@ sphere, plane, cube, polygon, Mesh, KdTree, Triangle, Transformed, hex_color, co
 and rpt::ode's ParticleState, ParticleSystem, SolidGravitySystem, MarblesSystem.
 The path tracer and the particle systems are HIP (rpt_amd/csrc) behind the C ABI in include/rpt_gpu.h.
 Beyond the reference: GpuScene.trace_rays runs the path estimator along rays of the caller's own making (numpy arrays,
-or torch tensors on the device).
+or torch tensors on the device), and GpuScene.bake_probes turns positions into light probes on the device — SH9 radiance or
+surface irradiance — which sh9_basis / sh9_irradiance (numpy) evaluate.
 """
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401
 from ._abi import (RPT_AOV_ALBEDO, RPT_AOV_ALL, RPT_AOV_DEPTH, RPT_AOV_NORMAL, RPT_AOV_OBJECT,  # noqa: F401
-                   RPT_AOV_POSITION)
+                   RPT_AOV_POSITION, RPT_PROBE_IRRADIANCE, RPT_PROBE_SH9)
 from .buffer import Buffer, Filter  # noqa: F401
 from .camera import Camera  # noqa: F401
 from .color import color_bytes, hex_color  # noqa: F401
@@ -23,6 +24,7 @@ from .light import Light  # noqa: F401
 from .material import Material  # noqa: F401
 from .object import Object  # noqa: F401
 from .ode import MarblesSystem, ParticleState, ParticleSystem, SolidGravitySystem  # noqa: F401
+from .probes import sh9_basis, sh9_irradiance  # noqa: F401
 from .renderer import Renderer  # noqa: F401
 from .scene import Scene  # noqa: F401
 from . import scenes  # noqa: F401

@@ -42,6 +42,7 @@ RPT_PARTICLES_MAX_N = 715827882
 RPT_PARTICLES_MAX_STEPS = 1 << 26
 RPT_AOV_DEPTH, RPT_AOV_NORMAL, RPT_AOV_ALBEDO, RPT_AOV_POSITION, RPT_AOV_OBJECT = 1, 2, 4, 8, 16
 RPT_AOV_ALL = 31
+RPT_PROBE_SH9, RPT_PROBE_IRRADIANCE = 0, 1
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -169,6 +170,13 @@ class RptRayQuery(C.Structure):
                 ("sample_index_base", C.c_uint64), ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class RptProbeQuery(C.Structure):
+    """include/rpt_gpu.h RptProbeQuery (rptgpu_bake_probes' parameters; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_uint32), ("samples", C.c_uint32), ("max_bounces", C.c_uint32),
+                ("seed", C.c_uint64), ("sample_index_base", C.c_uint64), ("precision_mode", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -199,6 +207,8 @@ SYMBOLS = [
      [_VP, C.c_uint64, _PD, _PD, C.c_uint32, _PD, _PD, C.POINTER(C.c_int32)]),
     ("rptgpu_trace_rays", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(C.c_uint32), C.POINTER(RptRayQuery), _PD]),
     ("rptgpu_trace_rays_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptRayQuery), _VP, _VP]),
+    ("rptgpu_bake_probes", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(C.c_uint32), C.POINTER(RptProbeQuery), _PD]),
+    ("rptgpu_bake_probes_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptProbeQuery), _VP, _VP]),
     ("rptgpu_eval_math", C.c_int, [_VP, C.c_int, C.c_uint64, _PD, _PD, _PD]),
     ("rptgpu_kdtree_build", C.c_int, [_PD, C.c_uint64, C.POINTER(RptKdTree)]),
     ("rptgpu_kdtree_build_device", C.c_int, [_PD, C.c_uint64, C.c_int, C.POINTER(RptKdTree)]),

@@ -12,6 +12,7 @@
 //                    rptgpu_render_batch_emulate_ranks
 //   api_buffer.cpp   the device-resident Buffer
 //   api_rays.cpp     rptgpu_trace_rays[_device]: the wavefront pipeline over rays the caller supplies, in pieces
+//   api_probes.cpp   rptgpu_bake_probes[_device]: light probes (SH9 radiance, irradiance) through the same driver, in pieces
 //   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, pass loop, copy_aov_out); its device
 //                    half also fills the features a Buffer holds for rptgpu_buffer_denoise
 // No compute happens on the host; if there is no HIP device every compute entry point returns RPTGPU_E_NO_DEVICE (there is
@@ -164,7 +165,8 @@ struct rptgpu_scene {
   uint32_t paths_chunk = 0;            // samples per work item (RptSceneOptions::paths_chunk; 0 = chosen per launch)
   DevBuf<unsigned long long> pcounters; // [0] closest-hit rays [1] shadow rays
   DevBuf<double> rays_o, rays_d, rays_out; // rptgpu_trace_rays: a piece of the host caller's rays and of their results (api_rays.cpp)
-  DevBuf<uint32_t> ray_ids;            // ... and the piece's stream ids (the caller's, or the rays' indices)
+  DevBuf<uint32_t> ray_ids;            // ... and the piece's stream ids (the caller's, or the rays' indices); rptgpu_bake_probes
+                                       // stages a piece of probes in the same four (api_probes.cpp)
   DevBuf<double> aov_out;              // rptgpu_render_aov: the requested channels' full-frame arrays, back to back (api_aov.cpp)
   int num_cus = 0;
   bool prefer_wavefront = false; // scene has real kd-trees: traversal-latency bound
@@ -313,12 +315,20 @@ int drain_call(rptgpu_scene* h, bool read_overflow);
 // Where the paths of a wavefront pass start — the one step of run_pass that knows: the pixels of a camera (rpt_raygen), or a
 // piece of the caller's rays (rpt_raygen_rays: fr.npix rays at origins / dirs on the device, [npix][3] f64, their streams
 // continuing at first_draw; ids_out: the piece's stream ids id_base + i are written there, see kernels/wavefront.inc)
+// ... or a piece of light probes (rpt_raygen_probes; probe = the RPT_PROBE_* kind, origins = the positions, dirs = the
+// normals).  Probes also choose the two steps behind the depth loop: rpt_resolve_probes into sums of probe_width(kind)
+// words per probe and rpt_finish_probes with probe_scale (api_probes.cpp)
 struct RaySource {
   const rptdev::Camera* cam;
   const double *origins, *dirs;
   uint32_t first_draw, id_base;
   uint32_t* ids_out;
+  int probe = -1;           // < 0: not probes
+  double probe_scale = 0.0; // 4 pi / S or pi / S
 };
+// f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
+inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
+const char* bad_probe_query(const RptProbeQuery* q);
 // the pass planner's input for a call over npix pixels or rays: what its passes share, and the device's state right now
 rptplan::PassInput pass_input(rptgpu_scene* h, uint32_t npix, uint32_t iterations);
 void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in);

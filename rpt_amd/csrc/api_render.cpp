@@ -395,8 +395,8 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
 }
 
 // One pass of the wavefront pipeline over n_paths = npix x spp paths: the ray source's kernel (rpt_raygen for a camera's
-// pixels, rpt_raygen_rays for a piece of the caller's rays — the one step that differs), per depth { closest-hit query,
-// rpt_shade, the visibility queries, rpt_shadow_sum }, rpt_resolve.  *cols: the record columns the pass used.  false: the
+// pixels, rpt_raygen_rays for a piece of the caller's rays, rpt_raygen_probes for a piece of light probes), per depth {
+// closest-hit query, rpt_shade, the visibility queries, rpt_shadow_sum }, rpt_resolve (probes: rpt_resolve_probes).  *cols: the record columns the pass used.  false: the
 // pool ran out at some depth (*cols: the columns up to and with that depth) — the pass did not resolve, and nothing of it
 // has left the workspace.
 bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, const rptdev::Frame& fr,
@@ -412,6 +412,7 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
   if (h->has_deep) reset_tree_counters(h);
   { Bracket b(h, RPT_K_RAYGEN, prof);
     if (src.cam) kt->raygen(st, fr, *src.cam, ps, n_paths);
+    else if (src.probe >= 0) kt->raygen_probes(st, fr, src.origins, src.dirs, (uint32_t)src.probe, src.ids_out, src.id_base, ps, n_paths);
     else kt->raygen_rays(st, fr, src.origins, src.dirs, src.first_draw, src.ids_out, src.id_base, ps, n_paths);
     b.done(); }
   h->stats.samples += n_paths;
@@ -483,7 +484,10 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
       std::swap(ps.ray, ps.ray_next); std::swap(ps.draw, ps.draw_next); std::swap(ps.pid, ps.pid_next); std::swap(ps.col, ps.col_next);
     }
   }
-  { Bracket b(h, RPT_K_RESOLVE, prof); kt->resolve(st, fr, ps, spp); b.done(); }
+  { Bracket b(h, RPT_K_RESOLVE, prof);
+    if (src.probe >= 0) kt->resolve_probes(st, fr, ps, spp, (uint32_t)src.probe);
+    else kt->resolve(st, fr, ps, spp);
+    b.done(); }
   HIP_TRY(hipGetLastError()); // a failed launch is reported here, not by the stream sync
   *cols = rec_off;
   return true;
@@ -525,7 +529,8 @@ void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderPar
   // (rpt_tree_generic's large grid — whole objects, or under RPT_FLAG_GENERAL_TRAVERSAL everything, go through it: up to
   // several hundred MB of columns for a deep mesh — is part of a pass's workspace: if it does not fit, the pass shrinks)
   const bool generic_all = h->has_deep && (h->gen_all || h->dscene.force_general);
-  HIP_TRY(hipMemsetAsync(h->accum.p, 0, (uint64_t)npix * 3 * sizeof(double), st));
+  const uint32_t acc_w = src.probe >= 0 ? probe_width((uint32_t)src.probe) : 3u; // running sums per pixel, ray or probe
+  HIP_TRY(hipMemsetAsync(h->accum.p, 0, (uint64_t)npix * acc_w * sizeof(double), st));
   QueryMarks qm(h, prof);
   const QueryHook qhook{query_mark, &qm};
 
@@ -555,7 +560,8 @@ void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderPar
                    pp.s_chunk, n_paths, (unsigned long long)cols, (unsigned long long)h->ws_rec_cols, (double)cols / (double)n_paths, in.ratio);
     s0 += pp.s_chunk;
   }
-  kt->finish(st, fr, (double)p.iterations, std::pow(2.0, p.exposure_value), out, out_f32, packed);
+  if (src.probe >= 0) kt->finish_probes(st, fr, acc_w, src.probe_scale, (double*)out);
+  else kt->finish(st, fr, (double)p.iterations, std::pow(2.0, p.exposure_value), out, out_f32, packed);
   if (std::getenv("RPTGPU_PRINT_PHASES")) {
     HIP_TRY(hipStreamSynchronize(st));
     print_prof(kt, "wavefront");

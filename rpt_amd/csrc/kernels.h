@@ -270,6 +270,14 @@ struct KernelTable {
                         double* v_out, uint32_t step, const rptdev::DenoiseSigmas&);
   void (*denoise_finish)(hipStream_t, const double* c_in, uint64_t stride, uint64_t npix, const double* thr, double* out_linear,
                          uint8_t* out_rgb8);
+  // light probes (rptgpu_bake_probes; kernels/wavefront.inc), beside raygen_rays / resolve / finish.  raygen_probes: the
+  // first step for fr.npix probes at positions / normals ([npix][3] f64 on the device; normals only read for
+  // RPT_PROBE_IRRADIANCE), ids_out / id_base as raygen_rays.  resolve_probes: a pass's paths into the probes' running sums
+  // (fr.accum, [27 or 3][npix]).  finish_probes: the sums times scale into out, [npix][width]
+  void (*raygen_probes)(hipStream_t, const rptdev::Frame&, const double* positions, const double* normals, uint32_t kind,
+                        uint32_t* ids_out, uint32_t id_base, const rptdev::PathState&, uint32_t n_paths);
+  void (*resolve_probes)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, uint32_t n_samples, uint32_t kind);
+  void (*finish_probes)(hipStream_t, const rptdev::Frame&, uint32_t width, double scale, double* out);
 };
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)

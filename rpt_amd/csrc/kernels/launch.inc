@@ -30,6 +30,10 @@ void launch_raygen_rays(hipStream_t st, const Frame& fr, const double* origins, 
                         uint32_t* ids_out, uint32_t id_base, const PathState& ps, uint32_t n_paths) {
   hipLaunchKernelGGL(rpt_raygen_rays, grid_for(n_paths), dim3(256), 0, st, fr, origins, dirs, first_draw, ids_out, id_base, ps, n_paths);
 }
+void launch_raygen_probes(hipStream_t st, const Frame& fr, const double* positions, const double* normals, uint32_t kind,
+                          uint32_t* ids_out, uint32_t id_base, const PathState& ps, uint32_t n_paths) {
+  hipLaunchKernelGGL(rpt_raygen_probes, grid_for(n_paths), dim3(256), 0, st, fr, positions, normals, kind, ids_out, id_base, ps, n_paths);
+}
 void launch_extend(hipStream_t st, const Scene& sc, const PathState& ps, const uint32_t* queue, uint32_t n) {
   hipLaunchKernelGGL(rpt_extend, grid_for(n), dim3(256), 0, st, sc, ps, queue, n);
 }
@@ -50,6 +54,12 @@ void launch_shadow_rays(hipStream_t st, const Scene& sc, const PathState& ps, co
 }
 void launch_resolve(hipStream_t st, const Frame& fr, const PathState& ps, uint32_t n_samples) {
   hipLaunchKernelGGL(rpt_resolve, grid_for(fr.npix), dim3(256), 0, st, fr, ps, n_samples);
+}
+void launch_resolve_probes(hipStream_t st, const Frame& fr, const PathState& ps, uint32_t n_samples, uint32_t kind) {
+  hipLaunchKernelGGL(rpt_resolve_probes, grid_for(fr.npix), dim3(256), 0, st, fr, ps, n_samples, kind);
+}
+void launch_finish_probes(hipStream_t st, const Frame& fr, uint32_t width, double scale, double* out) {
+  hipLaunchKernelGGL(rpt_finish_probes, grid_for((uint64_t)fr.npix * width), dim3(256), 0, st, fr, width, scale, out);
 }
 void launch_finish(hipStream_t st, const Frame& fr, double iterations, double ev_scale, void* out, bool f32, bool packed) {
   if (f32)
@@ -313,5 +323,6 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            paths_max_blocks_per_cu, launch_paths, launch_sum_samples, launch_query, sort_temp_bytes, launch_shadow_sum,
                            launch_buffer_accumulate, launch_buffer_retire, launch_buffer_image, launch_buffer_variance,
                            read_prof, launch_path_reorder, launch_aov, launch_aov_fold,
-                           launch_denoise_prepare, launch_denoise_level, launch_denoise_finish};
+                           launch_denoise_prepare, launch_denoise_level, launch_denoise_finish,
+                           launch_raygen_probes, launch_resolve_probes, launch_finish_probes};
 #endif // !__HIP_DEVICE_COMPILE__

@@ -210,6 +210,40 @@ __global__ void __launch_bounds__(256) rpt_raygen_rays(Frame fr, const double* _
   if (ids_out && s_local == 0) ids_out[p_local] = id_base + p_local;
 }
 
+// A light probe's direction (rptgpu_bake_probes, include/rpt_gpu.h), drawn from the stream's draw 0 on.  SH9: uniform on the
+// sphere without transcendentals — a point of the unit disc lifted to the sphere; IRRADIANCE: cosine-weighted about
+// normalize(normal), Sphere::sample (sphere.rs:52-64) as it stands.  rng.draw is then where the probe's path continues.
+RPT_DEV D3 probe_direction(uint32_t kind, D3 normal, Rng& rng) {
+  if (kind == RPT_PROBE_IRRADIANCE) return sample_sphere(normal, rng).v;
+  double x1, x2;
+  unit_disc(rng, x1, x2);
+  const double s = x1 * x1 + x2 * x2;
+  const double r = 2.0 * sqrt(1.0 - s);
+  return mk(x1 * r, x2 * r, 1.0 - 2.0 * s);
+}
+
+// The first step for light probes: slot = s_local * npix + p_local is direction fr.sample_base + s_local of probe p_local of
+// the piece (positions and normals [n][3] f64, already offset to the piece; normals only read for IRRADIANCE).  The path
+// leaves the probe's position along the direction and continues the direction's stream where it stopped, as rpt_raygen
+// does behind the camera's draws.  ids_out: as rpt_raygen_rays — fr.pixels points there, so the stream id is computed, not
+// read (the first sample's lanes are only now writing it).
+__global__ void __launch_bounds__(256) rpt_raygen_probes(Frame fr, const double* __restrict__ positions, const double* __restrict__ normals,
+                                                         uint32_t kind, uint32_t* __restrict__ ids_out, uint32_t id_base,
+                                                         PathState ps, uint32_t n_paths) {
+  uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= n_paths) return;
+  uint32_t s_local = slot / fr.npix, p_local = slot - s_local * fr.npix;
+  const uint32_t id = ids_out ? id_base + p_local : fr.pixels[p_local];
+  const D3 normal = kind == RPT_PROBE_IRRADIANCE ? ld3(normals + 3 * (uint64_t)p_local) : mk(0, 0, 0);
+  Rng rng = rng_make(fr.seed, id, fr.sample_base + s_local, 0);
+  const D3 dir = probe_direction(kind, normal, rng);
+  st_soa3(ps.ray, ps.cap, slot, ld3(positions + 3 * (uint64_t)p_local));
+  st_soa3(ps.ray + 3 * ps.cap, ps.cap, slot, dir);
+  ps.draw[slot] = rng.draw;
+  ps.pid[slot] = slot;
+  if (ids_out && s_local == 0) ids_out[p_local] = id;
+}
+
 // closest hit for every queued path.  queue == nullptr means the identity queue (depth 0).
 __global__ void __launch_bounds__(256, RPT_WF_WAVES) rpt_extend(Scene sc, PathState ps, const uint32_t* __restrict__ queue,
                                                   uint32_t n) {
@@ -1329,6 +1363,21 @@ __global__ void __launch_bounds__(256) rpt_shadow_sum(Scene sc, PathState ps, co
   st_rec3(ps, 0, col, emit + color);
 }
 
+// trace_ray's value for the path that ended with record c: L = that record's A, then the records above it back to front
+// along their links (renderer.rs:162-167)
+RPT_DEV D3 fold_path(const PathState& ps, uint32_t c) {
+  D3 L = ld_rec3(ps, 0, c);
+  for (c = ps.rec_parent[c]; c != REC_NONE; c = ps.rec_parent[c]) {
+    D3 A = ld_rec3(ps, 0, c);
+    D3 f = ld_rec3(ps, 3, c);
+    double inv_pdf = ps.rec[(uint64_t)c * REC_FIELDS + 6], abscos = ps.rec[(uint64_t)c * REC_FIELDS + 7];
+    D3 indirect = inv_pdf * cmul(f, L) * abscos;
+    L = mk(A.x + fmin(indirect.x, FIREFLY_CLAMP), A.y + fmin(indirect.y, FIREFLY_CLAMP),
+           A.z + fmin(indirect.z, FIREFLY_CLAMP));
+  }
+  return L;
+}
+
 // fold the depth records of every sample of a pixel, add to the pixel's running sum
 __global__ void __launch_bounds__(256) rpt_resolve(Frame fr, PathState ps, uint32_t n_samples) {
   uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1336,21 +1385,67 @@ __global__ void __launch_bounds__(256) rpt_resolve(Frame fr, PathState ps, uint3
   D3 acc = ld3(fr.accum + 3 * (uint64_t)p);
   for (uint32_t s = 0; s < n_samples; s++) {
     uint64_t slot = (uint64_t)s * fr.npix + p;
-    uint32_t c = ps.last_col[slot];       // the record the path ended with: L = its A
-    D3 L = ld_rec3(ps, 0, c);
-    for (c = ps.rec_parent[c]; c != REC_NONE; c = ps.rec_parent[c]) { // renderer.rs:162-167, back to front along the links
-      D3 A = ld_rec3(ps, 0, c);
-      D3 f = ld_rec3(ps, 3, c);
-      double inv_pdf = ps.rec[(uint64_t)c * REC_FIELDS + 6], abscos = ps.rec[(uint64_t)c * REC_FIELDS + 7];
-      D3 indirect = inv_pdf * cmul(f, L) * abscos;
-      L = mk(A.x + fmin(indirect.x, FIREFLY_CLAMP), A.y + fmin(indirect.y, FIREFLY_CLAMP),
-             A.z + fmin(indirect.z, FIREFLY_CLAMP));
-    }
-    acc = acc + L; // renderer.rs:139
+    acc = acc + fold_path(ps, ps.last_col[slot]); // the record the path ended with; renderer.rs:139
   }
   fr.accum[3 * (uint64_t)p] = acc.x;
   fr.accum[3 * (uint64_t)p + 1] = acc.y;
   fr.accum[3 * (uint64_t)p + 2] = acc.z;
+}
+
+// The real spherical harmonics of bands 0-2 at the unit vector d, in the order (0,0), (1,-1), (1,0), (1,1), (2,-2) .. (2,2)
+// and with the expressions include/rpt_gpu.h fixes (rpt_amd.sh9_basis restates them).
+RPT_DEV void sh9_basis(D3 d, double (&Y)[9]) {
+  const double x = d.x, y = d.y, z = d.z;
+  Y[0] = 0.28209479177387814;
+  Y[1] = 0.4886025119029199 * y;
+  Y[2] = 0.4886025119029199 * z;
+  Y[3] = 0.4886025119029199 * x;
+  Y[4] = 1.0925484305920792 * (x * y);
+  Y[5] = 1.0925484305920792 * (y * z);
+  Y[6] = 0.31539156525252005 * (3.0 * (z * z) - 1.0);
+  Y[7] = 1.0925484305920792 * (x * z);
+  Y[8] = 0.5462742152960396 * (x * x - y * y);
+}
+
+// rpt_resolve for light probes: one thread per probe of the piece, its samples in ascending order.  IRRADIANCE adds every
+// path's radiance to the probe's 3 running sums; SH9 weights it by the nine basis functions of the path's FIRST direction —
+// made again from the stream (the path state's direction was overwritten at the first bounce) — into 27 sums, [9][3].  The
+// sums rest in fr.accum between the passes of a piece, SoA over the piece ([27 or 3][npix]: neighbouring probes, neighbouring
+// words), so the order of additions across a pass border is the order within a pass.
+__global__ void __launch_bounds__(256) rpt_resolve_probes(Frame fr, PathState ps, uint32_t n_samples, uint32_t kind) {
+  uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= fr.npix) return;
+  if (kind == RPT_PROBE_IRRADIANCE) {
+    D3 acc = ld_soa3(fr.accum, fr.npix, p);
+    for (uint32_t s = 0; s < n_samples; s++) acc = acc + fold_path(ps, ps.last_col[(uint64_t)s * fr.npix + p]);
+    st_soa3(fr.accum, fr.npix, p, acc);
+    return;
+  }
+  double acc[27];
+#pragma unroll
+  for (int k = 0; k < 27; k++) acc[k] = fr.accum[(uint64_t)k * fr.npix + p];
+  const uint32_t id = fr.pixels[p];
+  for (uint32_t s = 0; s < n_samples; s++) {
+    const D3 L = fold_path(ps, ps.last_col[(uint64_t)s * fr.npix + p]);
+    Rng rng = rng_make(fr.seed, id, fr.sample_base + s, 0);
+    double Y[9];
+    sh9_basis(probe_direction(RPT_PROBE_SH9, mk(0, 0, 0), rng), Y);
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+      acc[3 * j] = acc[3 * j] + L.x * Y[j];
+      acc[3 * j + 1] = acc[3 * j + 1] + L.y * Y[j];
+      acc[3 * j + 2] = acc[3 * j + 2] + L.z * Y[j];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 27; k++) fr.accum[(uint64_t)k * fr.npix + p] = acc[k];
+}
+// the sums of a piece's probes times `scale` (4 pi / S, pi / S) into the caller's layout, [npix][width]
+__global__ void __launch_bounds__(256) rpt_finish_probes(Frame fr, uint32_t width, double scale, double* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (uint64_t)fr.npix * width) return;
+  const uint64_t p = i / width, k = i - p * width;
+  out[i] = fr.accum[k * fr.npix + p] * scale;
 }
 
 // ------------------------------------------------------------------ re-ordering the paths of a depth (round 6)

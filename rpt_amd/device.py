@@ -262,6 +262,113 @@ class GpuScene:
         _abi.check(code, self.handle)
         return out
 
+    def bake_probes(self, positions, normals=None, *, kind, samples, max_bounces, seed, sample_index_base=0, streams=None,
+                    flags=0, out=None):
+        """Light probes baked on the device (rptgpu_bake_probes): per probe `samples` directions from the
+        Philox stream, one path of at most max_bounces bounces along each.  kind = RPT_PROBE_SH9 -> (n, 9, 3) float64, the
+        radiance around positions[i] in the real spherical harmonics of bands 0-2 (rpt_amd.sh9_basis' order);
+        RPT_PROBE_IRRADIANCE -> (n, 3), the irradiance of a surface at positions[i] with normal normals[i].  positions,
+        normals: (n, 3) float64 (normals only with RPT_PROBE_IRRADIANCE).  streams: (n,) 32-bit stream ids, default the
+        probes' indices; probe i's random numbers are those of (seed, streams[i], sample_index_base + k), so its result does
+        not depend on the probes around it.  numpy arrays go through host memory; torch tensors on the handle's device are
+        read where they lie (rptgpu_bake_probes_device) and the result is `out` or a new tensor there."""
+        kind = int(kind)
+        if kind not in (_abi.RPT_PROBE_SH9, _abi.RPT_PROBE_IRRADIANCE):
+            raise ValueError("bake_probes: kind must be RPT_PROBE_SH9 or RPT_PROBE_IRRADIANCE")
+        if kind == _abi.RPT_PROBE_IRRADIANCE and normals is None:
+            raise ValueError("bake_probes: RPT_PROBE_IRRADIANCE needs normals")
+        if kind == _abi.RPT_PROBE_SH9 and normals is not None:
+            raise ValueError("bake_probes: RPT_PROBE_SH9 takes no normals")
+        q = _abi.RptProbeQuery()
+        q.struct_size = C.sizeof(_abi.RptProbeQuery)
+        q.kind, q.samples, q.max_bounces = kind, int(samples), int(max_bounces)
+        q.seed, q.sample_index_base = int(seed), int(sample_index_base)
+        q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        tail = (9, 3) if kind == _abi.RPT_PROBE_SH9 else (3,)
+        if hasattr(positions, "data_ptr") or hasattr(normals, "data_ptr"):
+            return self._bake_probes_torch(positions, normals, streams, q, tail, out)
+
+        def vectors(a, what):
+            a = np.asarray(a)
+            if a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("bake_probes: %s must be an (n, 3) float64 array" % what)
+            return np.ascontiguousarray(a)
+
+        pos = vectors(positions, "positions")
+        n = len(pos)
+        nrm = None
+        if normals is not None:
+            nrm = vectors(normals, "normals")
+            if len(nrm) != n:
+                raise ValueError("bake_probes: %d normals for %d positions" % (len(nrm), n))
+        ids = None
+        if streams is not None:
+            ids = np.asarray(streams)
+            if ids.ndim != 1 or ids.dtype.kind not in "iu":
+                raise ValueError("bake_probes: streams must be an (n,) integer array")
+            if len(ids) != n:
+                raise ValueError("bake_probes: %d stream ids for %d probes" % (len(ids), n))
+            ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        if out is None:
+            out = np.empty((n,) + tail, dtype=np.float64)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (n,) + tail and out.flags.c_contiguous):
+            raise ValueError("bake_probes: out must be a C-contiguous %s float64 array" % (("n",) + tail,))
+        PD = C.POINTER(C.c_double)
+        code = self.lib.rptgpu_bake_probes(self.handle, n, pos.ctypes.data_as(PD),
+                                           nrm.ctypes.data_as(PD) if nrm is not None else None,
+                                           ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None,
+                                           C.byref(q), out.ctypes.data_as(PD))
+        _abi.check(code, self.handle)
+        return out
+
+    def _bake_probes_torch(self, positions, normals, streams, q, tail, out):
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def vectors(t, what):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise ValueError("bake_probes: %s must be a torch tensor on %s, like the other arrays" % (what, dev))
+            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
+                raise ValueError("bake_probes: %s must be an (n, 3) float64 tensor" % what)
+            return t.contiguous()  # (no copy when it already is)
+
+        pos = vectors(positions, "positions")
+        n = pos.shape[0]
+        nrm = None
+        if normals is not None:
+            nrm = vectors(normals, "normals")
+            if nrm.shape[0] != n:
+                raise ValueError("bake_probes: %d normals for %d positions" % (nrm.shape[0], n))
+        ids = None
+        if streams is not None:
+            if not isinstance(streams, torch.Tensor) or streams.device != dev:
+                raise ValueError("bake_probes: streams must be a torch tensor on %s, like the probes" % dev)
+            if streams.dim() != 1 or streams.dtype.is_floating_point:
+                raise ValueError("bake_probes: streams must be an (n,) integer tensor")
+            ids = streams
+            if ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                ids = ids.to(torch.int64).to(torch.int32)  # the low 32 bits
+            ids = ids.contiguous()
+            if ids.shape[0] != n:
+                raise ValueError("bake_probes: %d stream ids for %d probes" % (ids.shape[0], n))
+        if out is None:
+            out = torch.empty((n,) + tail, dtype=torch.float64, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.float64
+                  and tuple(out.shape) == (n,) + tail and out.is_contiguous()):
+            raise ValueError("bake_probes: out must be a contiguous %s float64 tensor on %s" % ((("n",) + tail), dev))
+        # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
+        # stream is waited for here)
+        current = torch.cuda.current_stream(dev)
+        stream = current.cuda_stream
+        if not stream:
+            current.synchronize()
+        code = self.lib.rptgpu_bake_probes_device(self.handle, n, C.c_void_p(pos.data_ptr()),
+                                                  C.c_void_p(nrm.data_ptr()) if nrm is not None else None,
+                                                  C.c_void_p(ids.data_ptr()) if ids is not None else None, C.byref(q),
+                                                  C.c_void_p(out.data_ptr()), C.c_void_p(stream or 0))
+        _abi.check(code, self.handle)
+        return out
+
     def render_aov(self, camera, params, channels=_abi.RPT_AOV_ALL):
         """First-hit feature buffers (rptgpu_render_aov) -> a dict of numpy arrays: `hits` (H, W) uint32
         always, and per channel of `channels` (RPT_AOV_*) the f64 SUMS over the hits of params.iterations camera rays per

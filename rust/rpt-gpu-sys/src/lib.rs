@@ -66,6 +66,8 @@ pub mod ffi {
     pub const RPT_AOV_ALBEDO: u32 = 4;
     pub const RPT_AOV_POSITION: u32 = 8;
     pub const RPT_AOV_OBJECT: u32 = 16;
+    pub const RPT_PROBE_SH9: u32 = 0;
+    pub const RPT_PROBE_IRRADIANCE: u32 = 1;
     pub const RPTGPU_UNIQUE_ID_BYTES: usize = 128;
 
     /// `Material` (rpt src/material.rs:8-26)
@@ -310,6 +312,20 @@ pub mod ffi {
         pub flags: u32,
     }
 
+    /// `RptProbeQuery` (the parameters of `rptgpu_bake_probes`; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptProbeQuery {
+        pub struct_size: u32,
+        pub kind: u32,
+        pub samples: u32,
+        pub max_bounces: u32,
+        pub seed: u64,
+        pub sample_index_base: u64,
+        pub precision_mode: u32,
+        pub flags: u32,
+    }
+
     /// opaque `rptgpu_scene`
     #[repr(C)]
     pub struct rptgpu_scene {
@@ -344,6 +360,8 @@ pub mod ffi {
         pub fn rptgpu_closest_hit(h: *mut rptgpu_scene, n: u64, origins: *const f64, dirs: *const f64, precision_mode: u32, out_t: *mut f64, out_normal: *mut f64, out_object: *mut i32) -> c_int;
         pub fn rptgpu_trace_rays(h: *mut rptgpu_scene, n: u64, origins: *const f64, dirs: *const f64, streams: *const u32, q: *const RptRayQuery, out_rgb: *mut f64) -> c_int;
         pub fn rptgpu_trace_rays_device(h: *mut rptgpu_scene, n: u64, d_origins: *const c_void, d_dirs: *const c_void, d_streams: *const c_void, q: *const RptRayQuery, d_out_rgb: *mut c_void, stream: *mut c_void) -> c_int;
+        pub fn rptgpu_bake_probes(h: *mut rptgpu_scene, n: u64, positions: *const f64, normals: *const f64, streams: *const u32, q: *const RptProbeQuery, out: *mut f64) -> c_int;
+        pub fn rptgpu_bake_probes_device(h: *mut rptgpu_scene, n: u64, d_positions: *const c_void, d_normals: *const c_void, d_streams: *const c_void, q: *const RptProbeQuery, d_out: *mut c_void, stream: *mut c_void) -> c_int;
         pub fn rptgpu_kdtree_build(boxes: *const f64, n: u64, out: *mut RptKdTree) -> c_int;
         pub fn rptgpu_kdtree_build_device(boxes: *const f64, n: u64, device: c_int, out: *mut RptKdTree) -> c_int;
         pub fn rptgpu_kdtree_free(tree: *mut RptKdTree);
@@ -723,6 +741,7 @@ mod layout_tests {
         assert_eq!(size_of::<RptAovBuffers>(), 56);
         assert_eq!(size_of::<RptDenoise>(), 40);
         assert_eq!(size_of::<RptRayQuery>(), 48);
+        assert_eq!(size_of::<RptProbeQuery>(), 40);
     }
 
     #[test]
