@@ -150,7 +150,7 @@ struct rptgpu_scene {
   DevBuf<uint32_t> rec_parent, last_col;
   DevBuf<double> ray_next;             // dense path state of the NEXT depth (PathState: rpt_shade writes, the host swaps)
   DevBuf<uint32_t> draw_next, pid, pid_next, col, col_next;
-  // in-kernel-traversal scenes: the paths of a depth are re-ordered by ray key (kernels/wavefront.inc rpt_path_keys)
+  // in-kernel-traversal scenes: the paths of a depth are re-ordered by ray key (kernels/wf_sort_key.inc ray_sort_key)
   bool path_reorder = false;
   uint32_t path_reorder_min = RPT_PATH_REORDER_MIN; // ... when a depth has at least this many (RPTGPU_PATH_REORDER_MIN: tests)
   double scene_bounds[6] = {0, 0, 0, 1, 1, 1};

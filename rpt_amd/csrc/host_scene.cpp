@@ -584,7 +584,7 @@ struct Flattener {
       }
       case RPT_SHAPE_GROUP: {
         // KdTree<Box<dyn Bounded>> forwards Bounded through Box (kdtree.rs:14-24), so a group can sit in a group, to
-        // any depth: rpt_tree_generic walks such an object (kernels/wavefront.inc).  Only Shape::sample keeps a limit:
+        // any depth: rpt_tree_generic walks such an object (kernels/tree_generic.inc).  Only Shape::sample keeps a limit:
         // a LIGHT whose shape nests groups deeper than RPT_MAX_NEST is refused (kernels/sampling.inc sample_child)
         if (light_shape && nesting > RPT_MAX_NEST) {
           err = "Light::Object: KdTree<Box<dyn Bounded>> nested more than " + std::to_string(RPT_MAX_NEST + 1) + " levels deep";
@@ -879,7 +879,7 @@ int flatten_scene(const RptScene& sc, FlatScene& fs, std::string& err, const Bui
     fs.trees[g.first].prim_base = (uint32_t)fs.insts.size();
     fs.insts.insert(fs.insts.end(), g.second.begin(), g.second.end());
   }
-  // What rpt_tree_generic needs to walk any object of this scene (kernels/wavefront.inc): deferred far children — a
+  // What rpt_tree_generic needs to walk any object of this scene (kernels/tree_generic.inc): deferred far children — a
   // tree of depth D defers at most D, plus those of the trees suspended above it — and one frame per tree child entered
   {
     std::vector<int> memo_levels(fs.trees.size(), -1), memo_frames(fs.trees.size(), -1);

@@ -59,7 +59,7 @@ struct ObjectBounds {
   uint64_t obj_always = ~0ull;
   bool obj_filter_ok = false;
   // union of the world-space boxes of the bounded top-level objects (planes have none): the grid of the path re-order's
-  // sort key (kernels/wavefront.inc rpt_path_keys); ok: there is at least one and it is finite and not flat
+  // sort key (kernels/wf_sort_key.inc ray_sort_key); ok: there is at least one and it is finite and not flat
   double scene_bounds[6] = {0, 0, 0, 1, 1, 1};
   bool scene_bounds_ok = false;
 };

@@ -151,7 +151,7 @@ struct SortBufs {
 #define RPT_TT_LEVELS_MIN RPT_TT_LEVELS
 // spill area of the traversal stack beyond the LDS levels: [KD_MAX_STACK - RPT_TT_LEVELS_MIN][threads] per array, one
 // column per thread of the traversal grid (api_render.cpp allocates it for scenes with deep trees)
-// rpt_tree_generic's pending work (kernels/wavefront.inc), one column per thread of ITS grid: deferred far children
+// rpt_tree_generic's pending work (kernels/tree_generic.inc), one column per thread of ITS grid: deferred far children
 // (six face parameters, t_split, node) and the suspended leaves of the groups above the tree being walked
 struct GenericStack {
   double* defer;  // [levels][8][threads]

@@ -18,10 +18,17 @@
 //     paths_shade.inc   the fused form's draw-first shading: hit_draws, bsdf_opaque, sample_f_opaque, illuminate_mesh
 //     paths.inc         the kernel's contract, work hand-out, record ring, parked lookups, ray stash, the loop itself;
 //                       rpt_sum_samples
-//   wavefront.inc  the pipeline for scenes with deep trees: rpt_raygen / rpt_extend / rpt_shade /
-//                  rpt_shadow / rpt_resolve / rpt_finish over SoA path state, and the per-tree query
-//                  kernels (rpt_rays_init, rpt_tree_enter, rpt_tree_trace, rpt_nest_trace, rpt_tree_generic — the one that
-//                  walks trees inside trees to any depth —, rpt_rays_objects, rpt_shadow_sum)
+//   the wavefront pipeline — scenes with deep trees; rptgpu_trace_rays and rptgpu_bake_probes for any scene (flat ones
+//   query inside rpt_extend / rpt_shadow_rays) —: one kernel per step of a depth over SoA path state, in six files:
+//     wf_state.inc      access to the SoA path state and the depth records; the queue appends of a wave and of a block
+//     wf_sort_key.inc   the key queued rays and the paths of a depth are sorted by: RPT_SORT_PATTERN, ray_sort_key
+//     tree_query.inc    the per-tree query — closest hit or visibility, object by object —: RayBatch, a shadow ray's stop,
+//                       the slab interval, the entry row, a hit's epilogue; rpt_rays_objects, rpt_tree_enter
+//     tree_trace.inc    its persistent walkers and the steps they share (write-out, queue claim, stack, node step):
+//                       rpt_tree_trace, rpt_nest_trace (a kd-tree of kd-trees)
+//     tree_generic.inc  rpt_tree_generic: any tree, trees inside trees to any depth
+//     wavefront.inc     the path pipeline's kernels: rpt_raygen* / rpt_extend / rpt_shade / rpt_shadow_rays /
+//                       rpt_shadow_sum / rpt_resolve* / rpt_finish* / rpt_path_permute
 //   buffer.inc     device-resident Buffer (buffer.rs)
 //   aov.inc        first-hit feature buffers: rpt_aov (fused) and rpt_aov_fold (behind the per-tree query), DESIGN.md §11
 //   denoise.inc    the device Buffer's feature-guided à-trous filter (rpt_denoise_prepare / _level / _finish), DESIGN.md §12
@@ -85,6 +92,11 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/sampling.inc"
 #include "kernels/material.inc"
 #include "kernels/light.inc"
+#include "kernels/wf_state.inc"
+#include "kernels/wf_sort_key.inc"
+#include "kernels/tree_query.inc"
+#include "kernels/tree_trace.inc"
+#include "kernels/tree_generic.inc"
 #include "kernels/wavefront.inc"
 #include "kernels/paths_consts.inc"
 #include "kernels/paths_flat.inc"

@@ -170,7 +170,7 @@ void launch_query(hipStream_t st, const Scene& sc, const PathState& ps, const ui
       uint32_t* zq = tq + ps.cap;
       uint32_t* fq = tq + 2 * ps.cap;
       // rays with a zero direction component: the tree's second queue and a launch of the ZEROS form where the scene
-      // makes them common, else the general form's queue (kernels/wavefront.inc, rpt_tree_trace).  A kd-tree of kd-trees
+      // makes them common, else the general form's queue (kernels/tree_trace.inc, rpt_tree_trace).  A kd-tree of kd-trees
       // (rpt_nest_trace) takes them in its own loop, whose node step is the general compact one.
       const bool nest = (obj_tris[i] & 15) == 2 && !sc.force_general; // (api_scene.cpp: which objects qualify; extended-shape builds only)
       const bool zeros_launch = spill->zeros_common || nest;

@@ -18,7 +18,7 @@ RPT_DEV D3 operator*(D3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
 // Newton steps on the reciprocal, q = n*r, e = fma(-d,q,n), div_fmas(e,r,q), div_fixup, and when numerator and
 // denominator are in [2^-400, 2^400] nothing is scaled or fixed up, so q = n*r; e = fma(-d,q,n); fma(e,r,q) IS the
 // quotient, bit for bit (div_fast; tests/test_gpu_parity.py::test_shared_reciprocal_division_is_ieee, 10^8 operand
-// pairs).  ONE place uses that form: the node step of rpt_tree_trace (kernels/wavefront.inc), per wave, when every ray of
+// pairs).  ONE place uses that form: the node step of rpt_tree_trace (kernels/tree_trace.inc node_step), per wave, when every ray of
 // the wave and the tree qualify (Tree::split_range_ok, safe_coord).  One caveat there: a ZERO numerator gives a zero of
 // the sign of num * r, which for num = -0.0 (a split of -0.0 seen from an origin coordinate of +0.0) is not the sign
 // IEEE division gives (+0 where it gives -0 for d > 0).  The node step only COMPARES t_split (<= 0, <, >, min / max

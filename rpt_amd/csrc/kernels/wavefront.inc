@@ -1,162 +1,7 @@
-// kernels/wavefront.inc — the multi-kernel wavefront pipeline: path state access, raygen / extend / shade / shadow / resolve / finish, per-tree query kernels.
+// kernels/wavefront.inc — the multi-kernel path pipeline over SoA path state (wf_state.inc): rpt_raygen / _rays / _probes,
+// rpt_extend, rpt_shade, rpt_shadow_rays, rpt_shadow_sum, rpt_resolve / _probes, rpt_finish / _probes, rpt_path_permute.
+// Its closest-hit and visibility queries over deep trees are the per-tree kernels of tree_query / tree_trace / tree_generic.inc.
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
-
-// ------------------------------------------------------------------ state access
-RPT_DEV D3 ld_soa3(const double* base, uint64_t cap, uint64_t slot) {
-  return {base[slot], base[cap + slot], base[2 * cap + slot]};
-}
-RPT_DEV void st_soa3(double* base, uint64_t cap, uint64_t slot, D3 v) {
-  base[slot] = v.x;
-  base[cap + slot] = v.y;
-  base[2 * cap + slot] = v.z;
-}
-RPT_DEV double pack_u32(uint32_t a, uint32_t b) { return __longlong_as_double((long long)((uint64_t)a | ((uint64_t)b << 32))); }
-RPT_DEV void unpack_u32(double v, uint32_t& a, uint32_t& b) {
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  a = (uint32_t)u; b = (uint32_t)(u >> 32);
-}
-// depth records: fields f .. f + 2 of column c (PathState::rec).  A column is ONE 64-byte row — A[3], f[3], 1/pdf, |wi.n|
-// side by side: rpt_shade's lanes write neighbouring rows (as coalesced as a field-major layout), and rpt_resolve, which
-// walks a path's records along their parent links — anywhere in the pool once the paths of a depth are re-ordered —
-// touches one 64-byte sector per record instead of eight.
-RPT_DEV D3 ld_rec3(const PathState& ps, int f, uint64_t c) { const double* r = ps.rec + c * REC_FIELDS + f; return {r[0], r[1], r[2]}; }
-RPT_DEV void st_rec3(const PathState& ps, int f, uint64_t c, D3 v) { double* r = ps.rec + c * REC_FIELDS + f; r[0] = v.x; r[1] = v.y; r[2] = v.z; }
-
-// A shadow ray whose light would add exactly zero — bsdf = 0 because the light is below an opaque surface
-// (material.rs:130-133), or a light sample facing away (light.rs:38-40) — cannot change the pixel whether it is
-// occluded or not: sample_lights adds `bsdf * intensity * cos` (renderer.rs:199) to a sum that starts at +0, and
-// x + (+-0) = x for every x that sum can hold (it is never -0).  The reference still traces it; rpt_shade leaves it
-// out of the light's shadow-ray queue, so no kernel ever sees it, and rpt_shadow_sum may add its zero or not.  NaN
-// or infinite contributions are not zero and are traced.  On closed meshes about half of the hit points face away
-// from a given light: the queues hold 50-70 % of the reference's shadow rays.
-RPT_DEV bool null_contribution(D3 c) { return c.x == 0.0 && c.y == 0.0 && c.z == 0.0; }
-
-// append `slot` to a queue: one 64-bit ballot + one atomic per wave (wave64)
-RPT_DEV void queue_push(bool pred, uint32_t slot, uint32_t* __restrict__ q, uint32_t* __restrict__ count) {
-  uint64_t mask = __ballot(pred);
-  if (mask == 0) return;
-  uint32_t lane = __lane_id();
-  uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u;
-  uint32_t base = 0;
-  if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
-  base = __shfl(base, (int)leader);
-  if (pred) q[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = slot;
-}
-
-// The same for a whole 1024-thread block: ONE global atomic per block (and one more for an optional second counter).
-// A single address takes ~88 atomics per microsecond on this chip; with one atomic per wave the compaction kernels of a
-// 60-Mi-ray depth spent milliseconds queueing on the counter (rpt_shade 6.6 ms, rpt_tree_enter 2.9 ms per launch).
-// Every thread of the block must call this (no early returns before it).
-constexpr int PUSH_BLOCK = 1024; // rpt_tree_enter: a light streaming kernel, the fewer atomics the better
-constexpr int SHADE_BLOCK = 256; // rpt_shade: heavy lanes; 256 / 512 / 1024 -> 104 / 121 / 120 ms on the fractal spheres
-// three waves per SIMD (168 VGPRs): the kernel streams scattered path state and waits half of its cycles.  Round 3's
-// build happened to need exactly 168; round 4's sample_f needed 170 and silently ran at two waves (rpt_shade +10 %,
-// 1-1.5 % of a C3 / C4 / C5 frame) until the bound was written down
-#ifndef RPT_SHADE_WAVES
-#define RPT_SHADE_WAVES 3
-#endif
-                                 // (a whole block waits at the two barriers for its slowest wave)
-// q2 / v2: a second array that gets v2 at the same position (the ray sort's keys beside the queue's entries)
-RPT_DEV void block_queue_push(bool pred, uint32_t slot, uint32_t* __restrict__ q, uint32_t* __restrict__ count,
-                              bool pred2 = false, uint32_t* __restrict__ count2 = nullptr,
-                              uint32_t* __restrict__ q2 = nullptr, uint32_t v2 = 0u) {
-  __shared__ uint32_t s_cnt[PUSH_BLOCK / 64], s_cnt2[PUSH_BLOCK / 64], s_off[PUSH_BLOCK / 64];
-  const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6, nw = (blockDim.x + 63u) >> 6;
-  const uint64_t mask = __ballot(pred), mask2 = __ballot(pred2);
-  if (lane == 0) { s_cnt[wave] = (uint32_t)__popcll(mask); s_cnt2[wave] = (uint32_t)__popcll(mask2); }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t total = 0, total2 = 0;
-    for (uint32_t w = 0; w < nw; w++) { s_off[w] = total; total += s_cnt[w]; total2 += s_cnt2[w]; }
-    uint32_t base = total ? atomicAdd(count, total) : 0u;
-    for (uint32_t w = 0; w < nw; w++) s_off[w] += base;
-    if (count2 && total2) atomicAdd(count2, total2);
-  }
-  __syncthreads();
-  if (pred && q) {
-    const uint32_t pos = s_off[wave] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-    q[pos] = slot;
-    if (q2) q2[pos] = v2;
-  }
-}
-
-// Sort key of a ray about to enter a tree: where it enters the tree's box (7-bit Morton code per axis)
-// and its direction octant, coarse cell first.  Only the ORDER in which queued rays are traversed
-// depends on it — every ray's result is its own — so nothing here needs to be exact.
-// The key is built from 3-bit groups, most significant first, as RPT_SORT_PATTERN spells them: 'p' = the next bit (one
-// per axis) of the entry cell, 'O' = the direction's octant, 'd' = the next bit per axis of the direction inside its
-// octant (|component| / |d|_1).  Keys are 32-bit words and rocPRIM sorts 8 bits per pass: up to ten groups = four passes.
-// Rounds 2-5 sorted 24 bits, "pppppOpp" (a 32^3 cell, the octant, a 4^3 cell inside): three passes.  Round 6 measured
-// what the order is worth to the traversal (profiles/r06_sort_key_ab.txt) — 16 / 18 / 24 bits of that layout:
-// rpt_tree_trace 493 / 484 / 467 ms on the 100k-triangle mesh — and that the DIRECTION is worth more than more cell
-// bits: "pppOdddppp" (30 bits, four passes) 434 ms, +4.7 % on the frame after the fourth pass's cost; the 16k-triangle
-// glass gains 4.5 % in the traversal and pays it back in the sort (+0.9 % on the frame).
-// (Only the rays that ENTER the tree get a key: rpt_tree_enter compacts the pairs, launch_query sorts as many as there are.)
-#ifndef RPT_SORT_PATTERN
-#if !defined(RPT_SORT_PATTERN_ID)
-#define RPT_SORT_PATTERN "pppOdddppp"
-#elif RPT_SORT_PATTERN_ID == 0 // (A/B builds: a quoted string does not survive the build scripts' word splitting)
-#define RPT_SORT_PATTERN "pppppOpp"
-#elif RPT_SORT_PATTERN_ID == 1
-#define RPT_SORT_PATTERN "pOpdpdpdpp"
-#elif RPT_SORT_PATTERN_ID == 2
-#define RPT_SORT_PATTERN "ppOdpdpdpp"
-#elif RPT_SORT_PATTERN_ID == 3
-#define RPT_SORT_PATTERN "pppOddddpp"
-#elif RPT_SORT_PATTERN_ID == 4
-#define RPT_SORT_PATTERN "ppOdddpppp"
-#elif RPT_SORT_PATTERN_ID == 5
-#define RPT_SORT_PATTERN "ppppOdddpp"
-#elif RPT_SORT_PATTERN_ID == 6
-#define RPT_SORT_PATTERN "pppOddpp"
-#elif RPT_SORT_PATTERN_ID == 7
-#define RPT_SORT_PATTERN "ppOddppp"
-#elif RPT_SORT_PATTERN_ID == 8
-#define RPT_SORT_PATTERN "ppppppOddd"
-#elif RPT_SORT_PATTERN_ID == 9
-#define RPT_SORT_PATTERN "pppppOdddp"
-#elif RPT_SORT_PATTERN_ID == 10
-#define RPT_SORT_PATTERN "pppppppOdd"
-#endif
-#endif
-constexpr uint32_t sort_pattern_count(char c) {
-  uint32_t n = 0;
-  for (const char* q = RPT_SORT_PATTERN; *q; q++) n += *q == c ? 1u : 0u;
-  return n;
-}
-constexpr uint32_t SORT_POS_BITS = sort_pattern_count('p'), SORT_DIR_BITS = sort_pattern_count('d');
-constexpr uint32_t SORT_KEY_BITS = 3u * (SORT_POS_BITS + SORT_DIR_BITS + sort_pattern_count('O'));
-static_assert(SORT_KEY_BITS <= 32u && sort_pattern_count('O') <= 1u && SORT_POS_BITS <= 10u && SORT_DIR_BITS <= 10u, "RPT_SORT_PATTERN");
-static_assert(SORT_KEY_BITS == 3u * (sizeof(RPT_SORT_PATTERN) - 1u), "RPT_SORT_PATTERN: only 'p', 'd' and one 'O'");
-template <class TreeT> RPT_DEV uint32_t ray_sort_key(const TreeT& tr, D3 o, D3 d, double t_enter) {
-  constexpr float CELLS = (float)(1u << SORT_POS_BITS), DC = (float)(1u << SORT_DIR_BITS);
-  const float px = (float)((o.x + t_enter * d.x - tr.bounds[0]) / (tr.bounds[3] - tr.bounds[0]));
-  const float py = (float)((o.y + t_enter * d.y - tr.bounds[1]) / (tr.bounds[4] - tr.bounds[1]));
-  const float pz = (float)((o.z + t_enter * d.z - tr.bounds[2]) / (tr.bounds[5] - tr.bounds[2]));
-  const uint32_t ix = (uint32_t)fminf(fmaxf(px * CELLS, 0.0f), CELLS - 1.0f);
-  const uint32_t iy = (uint32_t)fminf(fmaxf(py * CELLS, 0.0f), CELLS - 1.0f);
-  const uint32_t iz = (uint32_t)fminf(fmaxf(pz * CELLS, 0.0f), CELLS - 1.0f);
-  const uint32_t oct = (d.x < 0.0 ? 1u : 0u) | (d.y < 0.0 ? 2u : 0u) | (d.z < 0.0 ? 4u : 0u);
-  uint32_t jx = 0u, jy = 0u, jz = 0u;
-  if constexpr (SORT_DIR_BITS != 0u) { // (scheduling only: nothing here needs to be exact)
-    const float ax = fabsf((float)d.x), ay = fabsf((float)d.y), az = fabsf((float)d.z);
-    const float inv = 1.0f / fmaxf(ax + ay + az, 1e-30f);
-    jx = (uint32_t)fminf(ax * inv * DC, DC - 1.0f); jy = (uint32_t)fminf(ay * inv * DC, DC - 1.0f); jz = (uint32_t)fminf(az * inv * DC, DC - 1.0f);
-  }
-  uint32_t key = 0u, pb = SORT_POS_BITS, db = SORT_DIR_BITS;
-#pragma unroll
-  for (uint32_t g = 0; g < sizeof(RPT_SORT_PATTERN) - 1u; g++) {
-    const char c = RPT_SORT_PATTERN[g];
-    uint32_t grp;
-    if (c == 'O') grp = oct;
-    else if (c == 'p') { pb--; grp = ((ix >> pb) & 1u) | (((iy >> pb) & 1u) << 1) | (((iz >> pb) & 1u) << 2); }
-    else { db--; grp = ((jx >> db) & 1u) | (((jy >> db) & 1u) << 1) | (((jz >> db) & 1u) << 2); }
-    key = (key << 3) | grp;
-  }
-  return key;
-}
-
-struct SceneBox { double bounds[6]; }; // the grid of a key that is not a tree's: the scene's bounded objects (path re-order)
 
 // ------------------------------------------------------------------ kernels
 __global__ void __launch_bounds__(256) rpt_raygen(Frame fr, Camera cam, PathState ps, uint32_t n_paths) {
@@ -279,49 +124,6 @@ __global__ void __launch_bounds__(256) rpt_extend_rays(Scene sc, const double* _
   out_obj[i] = obj;
 }
 
-// Several queue appends of a SHADE_BLOCK-thread block at the price of one: queue q (q < nq <= 32) gets `slot` of every
-// thread whose bit q of `bits` is set; one pair of barriers and one global atomic per queue and block, whatever nq is.
-// q = 0: the next depth's path queue, q = 1: the hit counter (no queue behind it), q = 2 + k: the shadow-ray queue of
-// light first_light + k.  Every thread of the block must call this.
-// Returns the calling thread's position in queue 0 (the next depth's paths) when its bit 0 is set: with dense path state
-// nothing is stored for that queue — the position IS where the thread writes its path's next state (next_queue = nullptr).
-RPT_DEV uint32_t block_multi_push(uint32_t bits, int nq, uint32_t slot, uint32_t* __restrict__ next_queue,
-                              uint32_t* __restrict__ counters, uint32_t* __restrict__ sq, uint64_t cap, int first_light) {
-  constexpr int NW = SHADE_BLOCK / 64;
-  __shared__ uint32_t s_cnt[32][NW], s_off[32][NW];
-  const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
-  for (int q = 0; q < nq; q++) {
-    const uint64_t mask = __ballot((bits >> q) & 1u);
-    if (lane == 0) s_cnt[q][wave] = (uint32_t)__popcll(mask);
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < nq) { // one thread per queue: scan the waves' counts, reserve the block's range
-    const int q = (int)threadIdx.x;
-    uint32_t total = 0;
-    for (int w = 0; w < NW; w++) { s_off[q][w] = total; total += s_cnt[q][w]; }
-    uint32_t* ctr = q < 2 ? counters + q : counters + 2 + first_light + (q - 2);
-    const uint32_t base = total ? atomicAdd(ctr, total) : 0u;
-    for (int w = 0; w < NW; w++) s_off[q][w] += base;
-  }
-  __syncthreads();
-  uint32_t pos0 = 0;
-  for (int q = 0; q < nq; q++) {
-    if (q == 1) continue; // the hit counter has no queue
-    const bool mine = (bits >> q) & 1u;
-    const uint64_t mask = __ballot(mine);
-    if (mine) {
-      const uint32_t pos = s_off[q][wave] + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-      if (q == 0) {
-        pos0 = pos;
-        if (next_queue) next_queue[pos] = slot;
-      } else {
-        (sq + (uint64_t)(first_light + q - 2) * cap)[pos] = slot;
-      }
-    }
-  }
-  return pos0;
-}
-
 // trace_ray's body for one depth (renderer.rs:147-168).
 // sq / counters[2 + l]: per light, the queue of the paths that cast a shadow ray towards it at this depth ([light][cap])
 // and its length: every hit whose light could add something (see null_contribution).  The visibility queries of the
@@ -339,6 +141,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK, RPT_SHADE_WAVES) rpt_shade(Scene 
   bool active = i < n;
   const uint32_t slot = i; // dense state: the path's position at this depth (`queue` is the identity, kept for the signature)
   (void)queue;
+  (void)next_queue;
   uint32_t bits = 0; // bit 0: the path continues, bit 1: it hit something, bit 2 + l: it casts a shadow ray to light l
   uint32_t path = 0, next_draw = 0;
   D3 next_o = mk(0, 0, 0), next_d = mk(0, 0, 0);
@@ -401,8 +204,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK, RPT_SHADE_WAVES) rpt_shade(Scene 
     }
     if (!(bits & 1u)) ps.last_col[path] = (uint32_t)col; // the path ends with this record: where rpt_resolve starts
   }
-  (void)next_queue;
-  const uint32_t j = block_multi_push(bits, 2 + min(sc.num_lights, FAST_LIGHTS), slot, nullptr, counters, sq, ps.cap, 0);
+  const uint32_t j = block_multi_push(bits, 2 + min(sc.num_lights, FAST_LIGHTS), slot, counters, sq, ps.cap, 0);
   if (bits & 1u) { // the survivor's state, at its position in the next depth
     if (ps.next_rows) {
       // in-kernel-traversal scenes (path re-order): one 64-byte row, and the key the re-order sorts by while the ray is
@@ -433,7 +235,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK, RPT_SHADE_WAVES) rpt_shade(Scene 
         const double* sh = ps.shadow + (uint64_t)(l0 + k) * SHADOW_FIELDS * ps.cap;
         if (clight(sc, l0 + k).kind != RPT_LIGHT_AMBIENT && !null_contribution(ld_soa3(sh + 4 * ps.cap, ps.cap, slot))) more |= 4u << k;
       }
-    (void)block_multi_push(more, 2 + nl, slot, nullptr, counters, sq, ps.cap, l0);
+    (void)block_multi_push(more, 2 + nl, slot, counters, sq, ps.cap, l0);
   }
 }
 
@@ -461,882 +263,6 @@ __global__ void __launch_bounds__(256, RPT_WF_WAVES) rpt_shadow_rays(Scene sc, P
   PROF_FLUSH();
 }
 
-
-// =================================================================== deep-tree scenes
-// When the scene has real kd-trees the closest-hit / visibility query is run object by object
-// (the reference's own order, renderer.rs:214-218) so that each deep tree gets (1) COMPACTION —
-// only rays that pass the tree's root slab test are queued for it — and (2) a PERSISTENT
-// traversal whose lanes pull the next queued ray the moment their own ray is finished, instead
-// of idling until the slowest ray of the wave is done (measured: 17 of 64 lanes active per VALU
-// instruction in the one-thread-per-ray form).  The per-ray sequence of decisions, tests and
-// accepts is exactly that of kd_intersect_fast; only the interleaving of rays changes.
-struct RayBatch {
-  const double* o;     // origins  [3][o_stride]
-  uint64_t o_stride;
-  const double* d;     // directions [3][d_stride]
-  uint64_t d_stride;
-  double* rt;          // [slot] closest accepted t so far (record.time)
-  double* rn;          // closest-hit: [3][n_stride] normal ; nullptr for shadow rays
-  uint64_t n_stride;
-  int32_t* obj;        // closest-hit: [slot] object index ; nullptr for shadow rays
-  const double* dist;  // shadow rays: [slot] distance to the light
-  const uint32_t* n_dev; // shadow rays: the length of `queue` lives on the device (rpt_shade's per-light count); the
-                         // launches are sized for the host's upper bound n and threads beyond *n_dev do nothing
-  uint32_t init;         // set for the FIRST kernel of a query (rpt_rays_objects or rpt_tree_enter): the records are new
-                         // (HitRecord::new, shape.rs:83-90) — it starts from them without reading and writes them for
-                         // every ray; a launch and a round trip through HBM of their own until round 5 (rpt_rays_init)
-};
-RPT_DEV uint32_t batch_n(const RayBatch& rb, uint32_t n) { return rb.n_dev ? min(n, *rb.n_dev) : n; }
-constexpr double DBL_MAX_ = 1.7976931348623157e308;
-
-// objects [begin, end) that need no persistent traversal: primitives and shallow trees
-// LDS = KdFlat: the build for runs in which every object is a primitive or a tree of ONE leaf (a polygon()'s quad, a
-// small group) — no traversal code, hence no LDS stack, no scratch and half the registers: the kernel streams ~100 B per
-// ray and, with eight waves per SIMD instead of three, does so nearer the memory's speed (api_scene.cpp marks such objects:
-// obj_tris bit 4).  The table under the wine glass and the plane under the 100k-triangle mesh are such runs.
-template <bool SHADOW, class LDS>
-__global__ void __launch_bounds__(256, (std::is_same<LDS, KdFlat>::value ? 1 : RPT_WF_WAVES)) rpt_rays_objects(Scene sc, RayBatch rb, const uint32_t* __restrict__ queue,
-                                                                      uint32_t n, int begin, int end) {
-  __shared__ typename std::conditional<std::is_same<LDS, KdFlat>::value, int, LDS>::type kd_store;
-  LDS* const kd_ldsp = reinterpret_cast<LDS*>(&kd_store);
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= batch_n(rb, n)) return;
-  uint32_t slot = queue ? queue[i] : i;
-  double rt = rb.init ? INF : rb.rt[slot];
-  double t_stop = -INF;
-  if (SHADOW) {
-    t_stop = fmin(rb.dist[slot], DBL_MAX_);
-    if (rt <= t_stop) return; // already occluded
-  }
-  D3 o = ld_soa3(rb.o, rb.o_stride, slot), d = ld_soa3(rb.d, rb.d_stride, slot);
-  D3 rn = mk(0, 0, 0);
-  int obj = -1;
-  RcpD rwx = rcp_make(d.x), rwy = rcp_make(d.y), rwz = rcp_make(d.z);
-  for (int k = begin; k < end; k++) {
-    if (isect_inst<LDS, SHADOW>(sc, cinst(sc, k), o, d, rwx, rwy, rwz, EPSILON, t_stop, rt, rn, kd_ldsp)) obj = k;
-    if (SHADOW && rt <= t_stop) break;
-  }
-  if (obj >= 0 || rb.init) { // (a new record is written whether or not anything was hit: rt = inf, n = 0, obj = -1)
-    rb.rt[slot] = rt;
-    if (!SHADOW) {
-      st_soa3(rb.rn, rb.n_stride, slot, rn);
-      rb.obj[slot] = obj;
-    }
-  }
-}
-
-// rpt_tree_enter: root slab test of one deep tree (KdTree::intersect, kdtree.rs:130-134) + queue append.
-// zq: the queue of the entering rays that have a zero direction component.  They get their own launch of
-// rpt_tree_trace, the ZEROS build, so that the main one does not carry their special cases through its node loop (5 %
-// on the 100k-triangle mesh).
-// fq: the rays of an IRREGULAR tree (a split plane outside its cell: the compact traversal does not apply) — all of
-// them, without a root test — are handed to rpt_tree_generic, like the NaN-split rays of the ZEROS build.  Traversing
-// them here inlined the general form and gave this streaming kernel 2 KB of scratch per lane.
-template <bool SHADOW>
-__global__ void __launch_bounds__(PUSH_BLOCK) rpt_tree_enter(Scene sc, RayBatch rb, const uint32_t* __restrict__ queue,
-                                                                    uint32_t n, int obj_index, uint32_t* __restrict__ tq,
-                                                                    uint32_t* __restrict__ tq_count,
-                                                                    uint32_t* __restrict__ sort_keys,
-                                                                    uint32_t* __restrict__ zq, uint32_t* __restrict__ zq_count,
-                                                                    uint32_t* __restrict__ fq, uint32_t* __restrict__ fq_count,
-                                                                    double* __restrict__ entry, uint32_t zeros_to_generic) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  bool enqueue = false, zenq = false, fenq = false;
-  uint32_t slot = 0, key = 0;
-  if (i < batch_n(rb, n)) {
-    slot = queue ? queue[i] : i;
-    // every field of the ray is requested at once, before any of them is looked at: the kernel streams ~80 B per ray
-    // and was bound by its chain of dependent loads (record -> distance -> origin / direction: three HBM round trips
-    // per lane), not by bandwidth
-    const double rt_in = rb.init ? INF : rb.rt[slot];
-    const double dist_in = SHADOW ? rb.dist[slot] : 0.0;
-    if (rb.init) { // HitRecord::new (shape.rs:83-90)
-      rb.rt[slot] = INF;
-      if (!SHADOW) {
-        rb.rn[slot] = 0.0; rb.rn[rb.n_stride + slot] = 0.0; rb.rn[2 * rb.n_stride + slot] = 0.0;
-        rb.obj[slot] = -1;
-      }
-    }
-    D3 o = ld_soa3(rb.o, rb.o_stride, slot), d = ld_soa3(rb.d, rb.d_stride, slot);
-    bool skip = false;
-    double rt = rt_in;
-    double t_stop = -INF;
-    if (SHADOW) {
-      t_stop = fmin(dist_in, DBL_MAX_);
-      skip = rt <= t_stop;
-    }
-    if (!skip) {
-      CInst& in = cinst(sc, obj_index);
-      CTree& tr = ctree(sc, in.tree);
-      if (in.has_xf) { // Ray::apply_transform shape.rs:64-71
-        D3 lo = mat4_mul(in.inv, o, 1.0), ld = mat4_mul(in.inv, d, 0.0);
-        o = lo; d = ld;
-      }
-      const bool zero = d.x == 0.0 || d.y == 0.0 || d.z == 0.0;
-      if (tr.regular && !sc.force_general && !tr.generic_only) {
-        double fax = (tr.bounds[0] - o.x) / d.x, fbx = (tr.bounds[3] - o.x) / d.x;
-        double fay = (tr.bounds[1] - o.y) / d.y, fby = (tr.bounds[4] - o.y) / d.y;
-        double faz = (tr.bounds[2] - o.z) / d.z, fbz = (tr.bounds[5] - o.z) / d.z;
-        double b_min = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-        double b_max = fmin(fmin(fmax(fax, fbx), fmax(fay, fby)), fmax(faz, fbz));
-        enqueue = !(fmax(b_min, EPSILON) > fmin(b_max, rt)); // kdtree.rs:131
-        if (enqueue) { // the entering ray as one 64-byte row (StackSpill::rays): what the traversal's refill reads
-          double* e = entry + (uint64_t)i * 8u;
-          e[0] = o.x; e[1] = o.y; e[2] = o.z; e[3] = d.x; e[4] = d.y; e[5] = d.z; e[6] = rt; e[7] = t_stop;
-        }
-        if (zero) { // its own queue — or, where such rays are rare, the general form's (rpt_tree_trace, above)
-          if (zeros_to_generic) fenq = enqueue; else zenq = enqueue;
-          enqueue = false;
-        }
-        if (sort_keys && enqueue) key = ray_sort_key(tr, o, d, fmax(b_min, EPSILON));
-      } else {
-        fenq = true;
-      }
-    }
-  }
-  // the tree's queues (tq, zq) hold POSITIONS in the query — the row of the entry table, and through the query's queue
-  // the slot —, the general form's queue slots (rpt_tree_generic reads the path state)
-  queue_push(zenq, i, zq, zq_count); // few or none in most scenes: one atomic per wave that has any
-  queue_push(fenq, slot, fq, fq_count);
-  // with a sort: (key, position) pairs of the ENTERING rays only, compacted like the queue itself (tq is then the sort's
-  // value input; its output is the tree's queue).  Until round 6 the pairs went out uncompacted — every ray of the query,
-  // the ones that miss the tree's bounds with the largest key — because the sort's length has to be known on the host:
-  // launch_query now reads the count back (a query worth sorting runs for milliseconds), and the sort handles the rays
-  // there are — a tenth of the camera rays of the glass scene.
-  block_queue_push(enqueue, i, tq, tq_count, false, nullptr, sort_keys, key);
-}
-
-// persistent traversal of one deep tree over the queued rays.  Latency-bound (L2/HBM misses on nodes and
-// leaf records), so it runs at its own, higher occupancy: RPT_TT_WAVES waves/SIMD with the first
-// RPT_TT_LEVELS stack levels in LDS (RPT_TT_WAVES * 4 * 64 lanes * 20 B * levels <= 160 KB per CU).
-using KdLdsTT = KdLdsT<RPT_TT_LEVELS, 256>;
-// (An LDS table of the ray's axis-indexed operands in place of the node step's three 3-way selects — 24 instead of 37
-// VALU instructions per step — and the LDS levels as a window over the TOP of the stack were built and measured in round
-// 5: variants/tree_trace_axis_table_top_window.patch.  The step is bound by its dependent child-pair load, not by VALU
-// issue: 1.5 % for a third of the instructions, less than the LDS levels the table costs.)
-using KdLdsTree = KdLdsTT;
-struct TreeTraceLds {
-  KdLdsTree st;
-};
-// ZEROS: the form for the rays with a zero direction component (their own queue, see rpt_tree_enter)
-template <bool TRIS, bool SHADOW, bool ZEROS>
-RPT_DEV void tree_trace_body(TreeTraceLds& tl, const Scene& sc, const RayBatch& rb, const int obj_index,
-                             const uint32_t* __restrict__ queue, const uint32_t* __restrict__ tq,
-                             const uint32_t* __restrict__ tq_count, uint32_t* __restrict__ tq_head,
-                             uint32_t* __restrict__ fq, uint32_t* __restrict__ fq_count, const StackSpill& spill) {
-  KdLdsTree& lds = tl.st;
-  constexpr int L = KdLdsTree::levels;
-  CInst& in = cinst(sc, obj_index);
-  CTree& tr = ctree(sc, in.tree);
-  const KdNode* __restrict__ nodes = sc.nodes + tr.node_base;
-  const uint32_t* __restrict__ refs = sc.refs + tr.ref_base;
-  const uint32_t count = *tq_count;
-  const uint32_t lane = __lane_id(), tix = threadIdx.x;
-  // The traversal stack: the first L deferred children of a lane sit in LDS ([level][thread], bank-conflict free),
-  // deeper ones — rare: most levels of a descent defer nothing — in a global-memory spill area of the same shape, one
-  // column per thread of this (persistent) grid, addressed as GLOBAL memory.  No scratch: a private array indexed by
-  // the stack pointer next to the LDS levels made the compiler select between the two POINTERS and emit flat loads.
-  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t* __restrict__ sp_node = spill.node + gtid;
-  double* __restrict__ sp_ts = spill.ts + gtid;
-  double* __restrict__ sp_bmax = spill.bmax + gtid;
-
-  bool active = false, exhausted = false, found = false;
-  bool fin = false; // the lane's ray is done and hit something: result not yet written out
-  uint32_t slot = 0, node = 0;
-  int sp = 0;
-  D3 o = mk(0, 0, 0), d = mk(0, 0, 1), rn = mk(0, 0, 0);
-  double rt = INF, t_min = EPSILON, t_stop = -INF, b_min = 0.0, b_max = 0.0;
-  BoxRay br{};
-  PROF_INIT();
-  // t_split = (value - o) / d through the ray's refined reciprocals (div_fast, vec.inc: three instructions that ARE the
-  // IEEE quotient when numerator and denominator are in [2^-400, 2^400]).  The range is established per RAY, not per
-  // step: a tree whose splits are all 0 or in [2^-340, 2^399) (Tree::split_range_ok), an origin whose coordinates are,
-  // and direction components in [2^-400, 2^400) make every numerator 0 — exact: 0 * r = 0 with the quotient's sign —
-  // or at least 2^-393.  The choice is per WAVE and refreshed at every refill; both sides give the same bits.
-  // Measured on the 100k-triangle mesh: 188 -> 192 Msamples/s (-> 195 with fmin_raw / fmax_raw, vec.inc).
-  double rcx = 0.0, rcy = 0.0, rcz = 0.0;
-  bool fast_ok = true, wave_fast = false;
-
-  for (;;) {
-    // ---- write out the results of the rays that finished since the last refill.  A lane whose ray is done idles until
-    // the wave refills anyway, so its normal transform (shape.rs:131-132: a 3x3 product, a square root, three divisions)
-    // and its five scattered stores wait until then and run ONCE for all of them instead of in nearly every iteration for
-    // one or two lanes (measured: no difference in kernel time — the block was never waited for)
-    if (__ballot(fin) != 0) {
-      if (fin) {
-        rb.rt[slot] = rt;
-        if (!SHADOW) {
-          if (in.has_xf) rn = normalize(mat3_mul(in.nrm, rn)); // Transformed::intersect shape.rs:131-132
-          st_soa3(rb.rn, rb.n_stride, slot, rn);
-          rb.obj[slot] = obj_index;
-        }
-        fin = false;
-      }
-    }
-    PROF_PHASE(PF_TT_WRITE); // result write-out
-    // ---- refill idle lanes from the tree's queue (one ballot + one atomic per wave)
-    bool need = !active && !exhausted;
-    uint64_t need_mask = __ballot(need);
-    if (need_mask) {
-      uint32_t leader = (uint32_t)__ffsll((long long)need_mask) - 1u;
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(tq_head, (uint32_t)__popcll(need_mask));
-      base = __shfl(base, (int)leader);
-      if (need) {
-        uint32_t idx = base + (uint32_t)__popcll(need_mask & ((1ull << lane) - 1ull));
-        if (idx < count) {
-          const uint32_t pos = tq[idx];
-          const double* __restrict__ e = spill.rays + (uint64_t)pos * 8u; // rpt_tree_enter's row: object-space ray, record, stop
-          slot = queue ? queue[pos] : pos;
-          o = mk(e[0], e[1], e[2]);
-          d = mk(e[3], e[4], e[5]);
-          rt = e[6];
-          if (SHADOW) t_stop = e[7];
-          double fax = (tr.bounds[0] - o.x) / d.x, fbx = (tr.bounds[3] - o.x) / d.x;
-          double fay = (tr.bounds[1] - o.y) / d.y, fby = (tr.bounds[4] - o.y) / d.y;
-          double faz = (tr.bounds[2] - o.z) / d.z, fbz = (tr.bounds[5] - o.z) / d.z;
-          b_min = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-          b_max = fmin(fmin(fmax(fax, fbx), fmax(fay, fby)), fmax(faz, fbz));
-          node = 0; sp = 0; t_min = EPSILON; found = false;
-          rn = mk(0, 0, 0);
-          br = boxray_make<!TRIS>(tr, o, d, fmax(b_min, 0.0));
-          if (!sc.use_leaf_boxes) br.on = false;
-          if constexpr (!ZEROS) {
-            RcpD qx = rcp_make(d.x), qy = rcp_make(d.y), qz = rcp_make(d.z);
-            rcx = qx.r; rcy = qy.r; rcz = qz.r;
-            fast_ok = tr.split_range_ok && qx.ok && qy.ok && qz.ok && safe_coord(o.x) && safe_coord(o.y) && safe_coord(o.z);
-          }
-          active = true;
-        } else {
-          exhausted = true;
-        }
-      }
-      if constexpr (!ZEROS) wave_fast = __ballot(active && !fast_ok) == 0ull;
-    }
-    PROF_PHASE(PF_TT_REFILL);
-    if (__ballot(active) == 0) break;
-
-    // ---- while-while traversal (the loop structure of kd_intersect_fast) until too few lanes
-    // still have a ray; then go back and refill.  Once the queue is exhausted, run to completion.
-    for (;;) {
-      if (active) {
-        KdNode n = nodes[node];
-        uint32_t axis = n.ib & 3u;
-        while (axis != 3u) { // kdtree.rs:172-222, compact form
-          PROF_COUNT(PF_TT_NODE);
-          // both children (adjacent, 32 B) are requested before the split is evaluated: the division and the
-          // decision below run while the load is in flight, and the chosen child is already in registers
-          const KdNode* __restrict__ ch = nodes + n.a; // one address for the adjacent pair
-          KdNode c0 = ch[0], c1 = ch[1];
-          double value = n.split;
-          double o_ax = sel((int)axis, o), d_ax = sel((int)axis, d);
-          double ts;
-          if (!ZEROS && wave_fast) {
-            const double num = value - o_ax, r_ax = axis == 0 ? rcx : (axis == 1 ? rcy : rcz);
-            const double q = num * r_ax;
-            ts = __builtin_fma(__builtin_fma(-d_ax, q, num), r_ax, q);
-          } else {
-            ts = (value - o_ax) / d_ax;
-          }
-          if constexpr (ZEROS) {
-            if (ts != ts) {
-              // 0/0: the origin lies ON the split plane of an axis the ray does not move along (kd_intersect_fast,
-              // traversal.inc).  The ray is handed to rpt_tree_generic, which starts it over in the general form; here
-              // it ends at an empty leaf with nothing found, so nothing of it is written out.
-              fq[atomicAdd(fq_count, 1u)] = slot;
-              n.a = 0u; n.ib = 3u; sp = 0; found = false;
-              break;
-            }
-          }
-          // the decisions as mask arithmetic (| and & on lane masks): `||` / `&&` compile to one masked region and one
-          // branch per operand — thirteen branches per step instead of eight, C3 195 -> 198
-          // (without a zero component d_ax <= 0 IS d_ax < 0: one compare serves `dle` and `neg`)
-          const bool neg = d_ax < 0.0;
-          const bool lt = o_ax < value, eq = o_ax == value, dle = ZEROS ? d_ax <= 0.0 : neg;
-          const bool left_first = lt | (eq & dle);
-          const double lim_hi = fmin_raw(b_max, rt), lim_lo = fmax_raw(b_min, t_min);
-          const bool only_first = (ts > lim_hi) | (ts <= 0.0);
-          const bool only_second = !only_first & (ts < lim_lo);
-          const bool go_left = only_second != left_first;
-          const bool defer = !only_first & !only_second & !(SHADOW & (ts > t_stop));
-          if (defer) {
-            uint32_t far = n.a + (left_first ? 1u : 0u);
-            if (sp < L) { lds.node[sp][tix] = far; lds.ts[sp][tix] = ts; lds.bmax[sp][tix] = b_max; }
-            else {
-              const uint64_t k = (uint64_t)(sp - L) * spill.threads;
-              sp_node[k] = far; sp_ts[k] = ts; sp_bmax[k] = b_max;
-            }
-            sp++;
-          }
-          if (!ZEROS || d_ax != 0.0) { // a zero component: the child's slab interval is the parent's (traversal.inc)
-            if (go_left != neg) b_max = fmin_raw(b_max, ts);
-            else b_min = fmax_raw(b_min, ts);
-          }
-          node = n.a + (go_left ? 0u : 1u);
-          n = go_left ? c0 : c1;
-          axis = n.ib & 3u;
-        }
-        PROF_PHASE(PF_TT_NODE);
-        bool h = false;
-        {
-          if constexpr (TRIS) h = kd_leaf_boxed<SHADOW>(sc, tr, refs, n, o, d, t_min, t_stop, rt, rn, br);
-          else
-            h = kd_leaf<TRIS, SHADOW>(sc, tr, refs, n, o, d, t_min, t_stop, rt, rn, &br);
-        }
-        found = found || h;
-        PROF_PHASE(PF_TT_EXACT); // (kd_leaf_boxed marks the end of its box tests itself)
-        bool finished = SHADOW && rt <= t_stop;
-        if (!finished) { // resume the nearest deferred far child that can still matter (kdtree.rs:213-220)
-          bool resumed = false;
-          while (sp > 0) {
-            PROF_COUNT(PF_TT_POP);
-            sp--;
-            double ts, bm;
-            uint32_t nd;
-            // the LDS entry is read unconditionally (clamped level, volatile) and a spilled one overrides it: with the
-            // two sides in an if / else — or speculated — the compiler selects between the POINTERS and emits flat loads
-            const int spc = min(sp, L - 1);
-            ts = lds_read_f64(&lds.ts[spc][tix]); bm = lds_read_f64(&lds.bmax[spc][tix]);
-            nd = lds_read_u32(&lds.node[spc][tix]);
-            if (sp >= L) {
-              const uint64_t k = (uint64_t)(sp - L) * spill.threads;
-              ts = sp_ts[k]; bm = sp_bmax[k]; nd = sp_node[k];
-            }
-            if (rt < ts) continue;
-            node = nd; b_min = ts; b_max = bm; t_min = ts;
-            resumed = true;
-            break;
-          }
-          finished = !resumed;
-        }
-        PROF_PHASE(PF_TT_POP);
-        if (finished) {
-          fin = found; // written out before the next refill
-          active = false;
-        }
-      }
-      uint32_t n_active = (uint32_t)__popcll(__ballot(active));
-      bool more = __ballot(!exhausted) != 0; // some lane may still get a ray from the queue
-      if (n_active == 0 || (more && n_active < RPT_REFILL_BELOW)) break;
-    }
-  }
-  PROF_FLUSH();
-}
-// The kernel: one pass of the loop above.  ZEROS = false: the tree's queue.  ZEROS = true: the queue of its rays with a
-// zero direction component — launched only for scenes that make such rays common (StackSpill::zeros_common: a
-// directional light along an axis or in a coordinate plane).  Everywhere else rpt_tree_enter hands the few there are to
-// rpt_tree_generic, which is launched anyway: until round 5 every (tree, query) pair paid an 8-us launch of the ZEROS
-// build that found its queue empty (wine glass: 68 per step).  Both forms in ONE launch (the ZEROS pass inlined behind the
-// main one, or called) cost the main loop registers: +1.5 % kernel time on the 100k-triangle mesh, or 0.5 KB of scratch.
-template <bool TRIS, bool SHADOW, bool ZEROS>
-__global__ void __launch_bounds__(256, RPT_TT_WAVES) rpt_tree_trace(Scene sc, RayBatch rb, int obj_index,
-                                                                    const uint32_t* __restrict__ queue,
-                                                                    const uint32_t* __restrict__ tq,
-                                                                    const uint32_t* __restrict__ tq_count,
-                                                                    uint32_t* __restrict__ tq_head,
-                                                                    uint32_t* __restrict__ fq,
-                                                                    uint32_t* __restrict__ fq_count, StackSpill spill) {
-  __shared__ TreeTraceLds tl;
-  tree_trace_body<TRIS, SHADOW, ZEROS>(tl, sc, rb, obj_index, queue, tq, tq_count, tq_head, fq, fq_count, spill);
-}
-
-#ifdef RPT_EXT_SHAPES
-// rpt_nest_trace: rpt_tree_trace for a kd-tree of kd-trees (examples/fractal_teapots.rs: 937 placed copies of a 12-level
-// mesh tree under 7-level group trees), BOTH levels in the one persistent loop.  rpt_tree_trace<false> walks the group's
-// tree and, at a leaf, calls isect_child_mesh for a mesh child: the lanes that have one run their inner traversals side
-// by side and wait for the longest — 7 of 64 lanes per inner node step, because a ray that clips a corner of a child's
-// bounds takes two steps and one through the teapot sixty.  Here a lane is EITHER in the group's tree or in one child's
-// tree (node base, ray, slab interval, box parameters are per-lane state; one stack, the child's entries above sp_in),
-// every pass gives each lane a turn at what IT needs next — node steps, then its leaf — and a lane whose child is
-// done walks on through the group, finishes its ray and takes the next from the queue: nobody waits for a neighbour's
-// child.  Per ray the sequence of tests, the record they see and every operand are those of the nested form, i.e. of
-// the reference's recursion (kdtree.rs:151-223 inside Transformed::intersect shape.rs:128-137 inside kdtree.rs:162-171).
-// The node step is kd_intersect_fast's, zero direction components included, so the queue of the rays that have one (zq)
-// runs through this kernel too; a 0/0 split sends the ray to rpt_tree_generic, which starts it over.  No calls, hence no
-// call frames in scratch (the nested form's chain of out-of-line traversals needs 14 KB per lane): the host sends an
-// object here only when its tree and all its mesh children's trees are regular, none of its children is a group, and
-// the two levels' depths fit one stack (api_scene.cpp); otherwise, and under RPT_FLAG_GENERAL_TRAVERSAL, rpt_tree_trace<false>.
-struct NestTree {
-  uint32_t ref_base, prim_base; // what kd_leaf reads of a mesh tree
-};
-template <bool SHADOW>
-RPT_DEV void nest_trace_body(KdLdsTT& lds, const Scene& sc, const RayBatch& rb, const int obj_index,
-                             const uint32_t* __restrict__ queue, const uint32_t* __restrict__ tq,
-                             const uint32_t* __restrict__ tq_count, uint32_t* __restrict__ tq_head,
-                             uint32_t* __restrict__ fq, uint32_t* __restrict__ fq_count, const StackSpill& spill) {
-  constexpr int L = KdLdsTT::levels;
-  CInst& in = cinst(sc, obj_index);
-  CTree& tr = ctree(sc, in.tree);
-  const uint32_t* __restrict__ refs0 = sc.refs + tr.ref_base;
-  const LeafBox* __restrict__ boxes0 = sc.lbox + tr.ref_base;
-  const Inst* __restrict__ kids = sc.insts + tr.prim_base;
-  const uint32_t count = *tq_count;
-  const uint32_t lane = __lane_id(), tix = threadIdx.x;
-  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t* __restrict__ sp_node = spill.node + gtid;
-  double* __restrict__ sp_ts = spill.ts + gtid;
-  double* __restrict__ sp_bmax = spill.bmax + gtid;
-
-  bool active = false, exhausted = false, found = false, fin = false;
-  uint32_t slot = 0, node = 0;
-  int sp = 0, sp_in = 0;
-  D3 o = mk(0, 0, 0), d = mk(0, 0, 1), rn = mk(0, 0, 0);
-  double rt = INF, t_min = EPSILON, t_stop = -INF, b_min = 0.0, b_max = 0.0;
-  double t0_root = 0.0, t_min_leaf = EPSILON; // the group tree's: where its box parameters count from; t_min at the leaf
-  BoxRay br{};                                // of the tree the lane is in
-  const KdNode* __restrict__ nodes = sc.nodes + tr.node_base;
-  bool inner = false, in_leaf = false;
-  const Inst* __restrict__ child = kids;
-  NestTree ct{0u, 0u};
-  uint32_t lf_first = 0, lf_cnt = 0, lf_base = 0, lf_next = 0, lf_mask = 0;
-  PROF_INIT();
-
-  // the ray in the group's space: rpt_tree_enter's row (read again when a lane comes back from a child: twelve
-  // registers less to carry through the child's traversal)
-  uint32_t pos = 0;
-  auto outer_ray = [&](D3& oo, D3& dd) {
-    const double* __restrict__ e = spill.rays + (uint64_t)pos * 8u;
-    oo = mk(e[0], e[1], e[2]);
-    dd = mk(e[3], e[4], e[5]);
-  };
-
-  for (;;) {
-    if (__ballot(fin) != 0) {
-      if (fin) {
-        rb.rt[slot] = rt;
-        if (!SHADOW) {
-          if (in.has_xf) rn = normalize(mat3_mul(in.nrm, rn)); // Transformed::intersect shape.rs:131-132
-          st_soa3(rb.rn, rb.n_stride, slot, rn);
-          rb.obj[slot] = obj_index;
-        }
-        fin = false;
-      }
-    }
-    PROF_PHASE(PF_TT_WRITE);
-    bool need = !active && !exhausted;
-    uint64_t need_mask = __ballot(need);
-    if (need_mask) {
-      uint32_t leader = (uint32_t)__ffsll((long long)need_mask) - 1u;
-      uint32_t base = 0;
-      if (lane == leader) base = atomicAdd(tq_head, (uint32_t)__popcll(need_mask));
-      base = __shfl(base, (int)leader);
-      if (need) {
-        uint32_t idx = base + (uint32_t)__popcll(need_mask & ((1ull << lane) - 1ull));
-        if (idx < count) {
-          pos = tq[idx];
-          slot = queue ? queue[pos] : pos;
-          outer_ray(o, d);
-          rt = spill.rays[(uint64_t)pos * 8u + 6u];
-          if (SHADOW) t_stop = spill.rays[(uint64_t)pos * 8u + 7u];
-          double fax = (tr.bounds[0] - o.x) / d.x, fbx = (tr.bounds[3] - o.x) / d.x;
-          double fay = (tr.bounds[1] - o.y) / d.y, fby = (tr.bounds[4] - o.y) / d.y;
-          double faz = (tr.bounds[2] - o.z) / d.z, fbz = (tr.bounds[5] - o.z) / d.z;
-          b_min = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-          b_max = fmin(fmin(fmax(fax, fbx), fmax(fay, fby)), fmax(faz, fbz));
-          node = 0; sp = 0; t_min = EPSILON; found = false;
-          rn = mk(0, 0, 0);
-          t0_root = fmax(b_min, 0.0);
-          br = boxray_make<true>(tr, o, d, t0_root);
-          if (!sc.use_leaf_boxes) br.on = false;
-          nodes = sc.nodes + tr.node_base;
-          inner = false; in_leaf = false;
-          active = true;
-        } else {
-          exhausted = true;
-        }
-      }
-    }
-    PROF_PHASE(PF_TT_REFILL);
-    if (__ballot(active) == 0) break;
-
-    for (;;) {
-      if (active) {
-        bool bail = false;
-        if (!in_leaf || inner) { // (a lane in the middle of a group leaf has no node to step through)
-          KdNode n = nodes[node];
-          uint32_t axis = n.ib & 3u;
-          while (axis != 3u) { // kdtree.rs:172-222, compact form (kd_intersect_fast's step: either level)
-            PROF_COUNT(PF_TT_NODE);
-            const KdNode* __restrict__ ch = nodes + n.a; // one address for the adjacent pair
-            KdNode c0 = ch[0], c1 = ch[1];
-            double value = n.split;
-            double o_ax = sel((int)axis, o), d_ax = sel((int)axis, d);
-            double ts = (value - o_ax) / d_ax;
-            if (ts != ts) { bail = true; break; } // 0/0 (a child's ray may have a zero component the group's has not)
-            const bool lt = o_ax < value, eq = o_ax == value, dle = d_ax <= 0.0; // mask arithmetic, as in rpt_tree_trace
-            const bool left_first = lt | (eq & dle);
-            const double lim_hi = fmin_raw(b_max, rt), lim_lo = fmax_raw(b_min, t_min);
-            const bool only_first = (ts > lim_hi) | (ts <= 0.0);
-            const bool only_second = !only_first & (ts < lim_lo);
-            const bool go_left = only_second != left_first;
-            if (!only_first & !only_second & !(SHADOW & (ts > t_stop))) {
-              uint32_t far = n.a + (left_first ? 1u : 0u);
-              if (sp < L) { lds.node[sp][tix] = far; lds.ts[sp][tix] = ts; lds.bmax[sp][tix] = b_max; }
-              else {
-                const uint64_t k = (uint64_t)(sp - L) * spill.threads;
-                sp_node[k] = far; sp_ts[k] = ts; sp_bmax[k] = b_max;
-              }
-              sp++;
-            }
-            bool neg = d_ax < 0.0;
-            if (d_ax != 0.0) {
-              if (go_left != neg) b_max = fmin_raw(b_max, ts);
-              else b_min = fmax_raw(b_min, ts);
-            }
-            node = n.a + (go_left ? 0u : 1u);
-            n = go_left ? c0 : c1;
-            axis = n.ib & 3u;
-          }
-          PROF_PHASE(PF_TT_NODE);
-          if (!bail) {
-            if (inner) { // a leaf of the child's mesh tree
-              D3 nn = mk(0, 0, 0);
-              bool h = kd_leaf<true, SHADOW>(sc, ct, sc.refs + ct.ref_base, n, o, d, t_min, t_stop, rt, nn, &br);
-              if (h) { // Transformed::intersect's epilogue for the hit that stands so far (shape.rs:131-132)
-                found = true;
-                if (!SHADOW) rn = child->has_xf ? normalize(mat3_mul(child->nrm, nn)) : nn;
-              }
-            } else { // a fresh leaf of the group's tree
-              lf_first = n.a; lf_cnt = n.ib >> 2; lf_next = 0; lf_mask = 0;
-              in_leaf = true;
-            }
-          }
-          PROF_PHASE(PF_TT_EXACT);
-        }
-        bool finished = bail || (SHADOW && rt <= t_stop);
-        // the lane's next deferred subtree above `floor`, if the record still reaches it (kdtree.rs:213-220)
-        auto pop_to = [&](int floor) -> bool {
-          while (sp > floor) {
-            PROF_COUNT(PF_TT_POP);
-            sp--;
-            const int spc = min(sp, L - 1);
-            double ts = lds_read_f64(&lds.ts[spc][tix]), bm = lds_read_f64(&lds.bmax[spc][tix]);
-            uint32_t nd = lds_read_u32(&lds.node[spc][tix]);
-            if (sp >= L) {
-              const uint64_t k = (uint64_t)(sp - L) * spill.threads;
-              ts = sp_ts[k]; bm = sp_bmax[k]; nd = sp_node[k];
-            }
-            if (rt < ts) continue;
-            node = nd; b_min = ts; b_max = bm; t_min = ts;
-            return true;
-          }
-          return false;
-        };
-        if (!finished && inner) {
-          if (!pop_to(sp_in)) { // the child is done: back to the group's leaf
-            inner = false;
-            outer_ray(o, d);
-            nodes = sc.nodes + tr.node_base;
-            t_min = t_min_leaf;
-            br = boxray_make<true>(tr, o, d, t0_root);
-            if (!sc.use_leaf_boxes) br.on = false;
-          }
-        }
-        if (!finished && !inner && in_leaf) {
-          // the group's leaf: its children in leaf order (kdtree.rs:162-171) until one is a mesh to walk
-          bool entered = false;
-          while (!entered) {
-            if (lf_mask == 0u) {
-              if (lf_next >= lf_cnt) break; // leaf exhausted
-              lf_base = lf_next;
-              const uint32_t lim = min(lf_cnt - lf_base, 32u);
-              lf_next = lf_base + 32u;
-              uint32_t m = lim >= 32u ? 0xffffffffu : ((1u << lim) - 1u);
-              if (br.on && lf_cnt > 2u) {
-                float wl, wh;
-                box_window(br, t_min, SHADOW ? fmin(rt, t_stop) : rt, wl, wh);
-                uint32_t pass = 0u;
-                for (uint32_t b = 0; b < lim; b += RPT_GBOX_BATCH) {
-                  PROF_COUNT(PF_TT_BOX);
-                  LeafBox w[RPT_GBOX_BATCH];
-#pragma unroll
-                  for (uint32_t k = 0; k < RPT_GBOX_BATCH; k++) w[k] = boxes0[lf_first + lf_base + b + k]; // (unclamped, as in kd_leaf)
-                  uint32_t p = 0u;
-#pragma unroll
-                  for (uint32_t k = 0; k < RPT_GBOX_BATCH; k++) p |= (leaf_box_pass(w[k], br, wl, wh) ? 1u : 0u) << k;
-                  pass |= p << b;
-                }
-                m &= pass;
-              }
-              lf_mask = m;
-              continue;
-            }
-            const uint32_t i = (uint32_t)__ffs((int)lf_mask) - 1u;
-            lf_mask &= lf_mask - 1u;
-            const Inst* __restrict__ c = kids + refs0[lf_first + lf_base + i];
-            const int32_t kind = c->kind;
-            bool h = false;
-            if (kind == RPT_SHAPE_MESH) {
-              const Tree& t1 = sc.trees[c->tree];
-              {
-                D3 lo = o, ld = d;
-                if (c->has_xf) { // Ray::apply_transform shape.rs:64-71
-                  lo = mat4_mul(c->inv, o, 1.0);
-                  ld = mat4_mul(c->inv, d, 0.0);
-                }
-                const double fax = (t1.bounds[0] - lo.x) / ld.x, fbx = (t1.bounds[3] - lo.x) / ld.x;
-                const double fay = (t1.bounds[1] - lo.y) / ld.y, fby = (t1.bounds[4] - lo.y) / ld.y;
-                const double faz = (t1.bounds[2] - lo.z) / ld.z, fbz = (t1.bounds[5] - lo.z) / ld.z;
-                const double bn = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-                const double bx = fmin(fmin(fmax(fax, fbx), fmax(fay, fby)), fmax(faz, fbz));
-                if (!(fmax(bn, t_min) > fmin(bx, rt))) { // kdtree.rs:130-134: walk this child
-                  inner = true;
-                  entered = true;
-                  child = c;
-                  ct.ref_base = t1.ref_base; ct.prim_base = t1.prim_base;
-                  br = boxray_make<false>(t1, lo, ld, fmax(bn, 0.0));
-                  if (!sc.use_leaf_boxes) br.on = false;
-                  o = lo; d = ld;
-                  b_min = bn; b_max = bx;
-                  nodes = sc.nodes + t1.node_base;
-                  t_min_leaf = t_min;
-                  sp_in = sp;
-                  node = 0;
-                }
-              }
-            } else { // a sphere, a cube, a monomial surface (no group children here: the host sees to it)
-              const ChildM cur = ld_child(c);
-              h = isect_child(cur, c, o, d, t_min, rt, rn, !SHADOW);
-            }
-            found = found || h;
-            if (SHADOW && rt <= t_stop) { finished = true; break; }
-          }
-          if (!finished && !entered) { // the group's leaf is exhausted
-            in_leaf = false;
-            finished = !pop_to(0);
-          }
-        }
-        PROF_PHASE(PF_TT_POP);
-        if (finished) {
-          if (bail) { // rpt_tree_generic starts the ray over in the general form; nothing of it is written here
-            fq[atomicAdd(fq_count, 1u)] = slot;
-            found = false;
-          }
-          fin = found;
-          active = false;
-        }
-      }
-      uint32_t n_active = (uint32_t)__popcll(__ballot(active));
-      bool more = __ballot(!exhausted) != 0;
-      if (n_active == 0 || (more && n_active < RPT_REFILL_BELOW)) break;
-    }
-  }
-  PROF_FLUSH();
-}
-// (one launch for the tree's queue and the queue of its rays with a zero direction component, like rpt_tree_trace; the
-// node step here is the general compact one, so both run the same code)
-template <bool SHADOW>
-__global__ void __launch_bounds__(256, RPT_TT_WAVES) rpt_nest_trace(Scene sc, RayBatch rb, int obj_index,
-                                                                    const uint32_t* __restrict__ queue,
-                                                                    const uint32_t* __restrict__ tq,
-                                                                    const uint32_t* __restrict__ zq,
-                                                                    uint32_t* __restrict__ ctr,
-                                                                    uint32_t* __restrict__ fq, StackSpill spill) {
-  __shared__ KdLdsTT lds;
-  for (int pass = 0; pass < 2; pass++) { // (a loop, not two inlined copies: the passes are the same code)
-    if (ctr[2 * pass] != 0u) nest_trace_body<SHADOW>(lds, sc, rb, obj_index, queue, pass ? zq : tq, ctr + 2 * pass, ctr + 2 * pass + 1, fq, ctr + 4, spill);
-  }
-}
-#endif
-
-// ------------------------------------------------------------------ rpt_tree_generic: KdTree::intersect, whatever the tree
-// The per-tree pipeline's kernel of last resort, and the only place where a tree inside a tree is walked to ANY depth.
-// It takes (i) the rays the fast kernels hand on — a 0/0 split (rpt_tree_trace<ZEROS>, rpt_nest_trace), every ray of an
-// irregular tree or under RPT_FLAG_GENERAL_TRAVERSAL — and (ii) every ray of an object the fast kernels are not built
-// for (Tree::generic_only): a group with a group among its children, to any nesting depth (kdtree.rs:14-24 forwards
-// Bounded through Box without limit), a group whose mesh children do not qualify for rpt_nest_trace, a tree deeper than
-// KD_MAX_STACK.  One loop, no calls, nothing private: the reference's recursion (kdtree.rs:129-223 inside
-// Transformed::intersect shape.rs:128-137 inside the leaf loop kdtree.rs:162-171 ...) with its two kinds of pending work
-// kept in global memory, one column per thread of this kernel's (persistent, bounded) grid —
-//   deferred far children  [level][8][thread]: the six carried face parameters, t_split, the node   (the general,
-//                          box-carrying form: exact for irregular trees and NaN splits, kd_intersect_general)
-//   suspended leaves       [frame][12][thread]: a group's leaf loop interrupted by a tree child — the group's ray and
-//                          t_min, where in which leaf to go on, its part of the deferred stack, its `result` so far
-// — so the nesting depth and the tree depth are bounded by what api_render.cpp allocates for the scene (it knows both), not by
-// a template level or a frame in scratch.  Speed is not the point here (no LDS, no box filter): the scenes that need it
-// are rare, the rays handed on a handful.  Per ray: the reference's tests in the reference's order on the one record.
-// (GenericStack: kernels.h)
-// returns KdTree::intersect's result for tree `root` (tris: a Mesh's tree) and the ray (o, d) in ITS space; *overflow is
-// set — and false returned — if the scene outgrew the columns (api_render.cpp sizes them from the scene: cannot happen)
-template <bool SHADOW>
-RPT_DEV bool generic_walk(const Scene& sc, uint32_t root, bool root_tris, D3 o, D3 d, double t_min, const double t_stop,
-                          double& rt, D3& rn, const GenericStack& gs, const uint32_t tid, uint32_t* overflow) {
-  const uint64_t T = gs.threads;
-  double* __restrict__ dcol = gs.defer + tid;
-  double* __restrict__ fcol = gs.frame + tid;
-  uint32_t tidx = root, sp = 0, sp_base = 0, depth = 0;
-  bool tris = root_tris, found = false, result = false;
-  uint32_t node = 0, lf_first = 0, lf_cnt = 0, lf_i = 0;
-  double fax = 0, fay = 0, faz = 0, fbx = 0, fby = 0, fbz = 0;
-  enum { ENTER, DESCEND, LEAF, POP, RETURN };
-  int mode = ENTER;
-  for (;;) {
-    const Tree& tr = sc.trees[tidx];
-    if (mode == ENTER) { // KdTree::intersect kdtree.rs:129-135
-      fax = (tr.bounds[0] - o.x) / d.x; fbx = (tr.bounds[3] - o.x) / d.x;
-      fay = (tr.bounds[1] - o.y) / d.y; fby = (tr.bounds[4] - o.y) / d.y;
-      faz = (tr.bounds[2] - o.z) / d.z; fbz = (tr.bounds[5] - o.z) / d.z;
-      const double b_min = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-      const double b_max = fmin(fmin(fmax(fax, fbx), fmax(fay, fby)), fmax(faz, fbz));
-      if (fmax(b_min, t_min) > fmin(b_max, rt)) { result = false; mode = RETURN; }
-      else { node = 0; found = false; sp_base = sp; mode = DESCEND; }
-    }
-    if (mode == DESCEND) { // intersect_subtree kdtree.rs:151-223, the far child deferred with its own box
-      const KdNode* __restrict__ nodes = sc.nodes + tr.node_base;
-      KdNode n = nodes[node];
-      uint32_t axis = n.ib & 3u;
-      while (axis != 3u) {
-        const double value = n.split;
-        const double o_ax = sel((int)axis, o), d_ax = sel((int)axis, d);
-        const double ts = (value - o_ax) / d_ax;
-        const bool left_first = (o_ax < value) || (o_ax == value && d_ax <= 0.0);
-        const double b_min = fmax(fmax(fmin(fax, fbx), fmin(fay, fby)), fmin(faz, fbz));
-        const double b_max = fmin(fmin(fmax(fax, fbx), fmax(fay, fby)), fmax(faz, fbz));
-        const bool only_first = (ts > fmin(b_max, rt)) || (ts <= 0.0);     // kdtree.rs:207
-        const bool only_second = !only_first && (ts < fmax(b_min, t_min)); // kdtree.rs:209
-        const bool go_left = only_second ? !left_first : left_first;
-        if (!only_first && !only_second) {
-          if (sp >= gs.levels) { *overflow = 1u; return false; }
-          const bool sec_left = !left_first;
-          double* e = dcol + (uint64_t)sp * 8u * T;
-          e[0] = (!sec_left && axis == 0) ? ts : fax;
-          e[T] = (!sec_left && axis == 1) ? ts : fay;
-          e[2 * T] = (!sec_left && axis == 2) ? ts : faz;
-          e[3 * T] = (sec_left && axis == 0) ? ts : fbx;
-          e[4 * T] = (sec_left && axis == 1) ? ts : fby;
-          e[5 * T] = (sec_left && axis == 2) ? ts : fbz;
-          e[6 * T] = ts;
-          e[7 * T] = pack_u32(n.a + (sec_left ? 0u : 1u), 0u);
-          sp++;
-        }
-        if (go_left) {
-          fbx = axis == 0 ? ts : fbx; fby = axis == 1 ? ts : fby; fbz = axis == 2 ? ts : fbz;
-        } else {
-          fax = axis == 0 ? ts : fax; fay = axis == 1 ? ts : fay; faz = axis == 2 ? ts : faz;
-        }
-        node = n.a + (go_left ? 0u : 1u);
-        n = nodes[node];
-        axis = n.ib & 3u;
-      }
-      lf_first = n.a; lf_cnt = n.ib >> 2; lf_i = 0;
-      mode = LEAF;
-    }
-    if (mode == LEAF) { // kdtree.rs:162-171: every object of the leaf, in order, on the one record
-      const uint32_t* __restrict__ refs = sc.refs + tr.ref_base;
-      if (tris) {
-        const TriX* __restrict__ recs = sc.lrec + tr.ref_base + lf_first;
-        const Tri* __restrict__ tp = sc.tris + tr.prim_base;
-        for (uint32_t b = 0; b < lf_cnt; b += 4) {
-          const bool h = tri_batch<SHADOW>(recs + b, tp, refs + lf_first + b, lf_cnt - b, lf_cnt <= 2, o, d, t_min, rt, rn);
-          found = found || h;
-          if (SHADOW && rt <= t_stop) return true;
-        }
-        mode = POP;
-      } else {
-        const Inst* __restrict__ kids = sc.insts + tr.prim_base;
-        mode = POP;
-        while (lf_i < lf_cnt) {
-          const Inst* __restrict__ c = kids + refs[lf_first + lf_i];
-          lf_i++;
-          const ChildM cur = ld_child(c);
-          if (cur.kind == RPT_SHAPE_MESH || cur.kind == RPT_SHAPE_GROUP) {
-            // Transformed<KdTree<..>>::intersect (shape.rs:128-137): suspend this leaf, walk the child's tree with the
-            // ray in the child's space and the same t_min
-            if (depth >= gs.frames) { *overflow = 1u; return false; }
-            double* f = fcol + (uint64_t)depth * 12u * T;
-            f[0] = o.x; f[T] = o.y; f[2 * T] = o.z; f[3 * T] = d.x; f[4 * T] = d.y; f[5 * T] = d.z;
-            f[6 * T] = t_min;
-            f[7 * T] = pack_u32(tidx, (uint32_t)(c - sc.insts));
-            f[8 * T] = pack_u32(lf_first, lf_cnt);
-            f[9 * T] = pack_u32(lf_i, sp_base);
-            f[10 * T] = pack_u32(found ? 1u : 0u, 0u);
-            depth++;
-            if (c->has_xf) { // Ray::apply_transform shape.rs:64-71
-              const D3 lo = mat4_mul(c->inv, o, 1.0), ld = mat4_mul(c->inv, d, 0.0);
-              o = lo; d = ld;
-            }
-            tidx = (uint32_t)c->tree;
-            tris = cur.kind == RPT_SHAPE_MESH;
-            mode = ENTER;
-            break;
-          }
-          const bool h = isect_child(cur, c, o, d, t_min, rt, rn, !SHADOW);
-          found = found || h;
-          if (SHADOW && rt <= t_stop) return true;
-        }
-      }
-    }
-    if (mode == POP) { // the nearest deferred far child of THIS tree that can still matter (kdtree.rs:213-220)
-      mode = RETURN;
-      result = found;
-      while (sp > sp_base) {
-        sp--;
-        const double* e = dcol + (uint64_t)sp * 8u * T;
-        const double ts = e[6 * T];
-        if (rt < ts) continue;
-        fax = e[0]; fay = e[T]; faz = e[2 * T]; fbx = e[3 * T]; fby = e[4 * T]; fbz = e[5 * T];
-        uint32_t nd, unused;
-        unpack_u32(e[7 * T], nd, unused);
-        node = nd;
-        t_min = ts;
-        mode = DESCEND;
-        break;
-      }
-    }
-    if (mode == RETURN) { // this tree's intersect returns `result`
-      if (depth == 0) return result;
-      depth--;
-      const double* f = fcol + (uint64_t)depth * 12u * T;
-      uint32_t ci, fnd, unused;
-      o = mk(f[0], f[T], f[2 * T]); d = mk(f[3 * T], f[4 * T], f[5 * T]);
-      t_min = f[6 * T];
-      unpack_u32(f[7 * T], tidx, ci);
-      unpack_u32(f[8 * T], lf_first, lf_cnt);
-      unpack_u32(f[9 * T], lf_i, sp_base);
-      unpack_u32(f[10 * T], fnd, unused);
-      const Inst* __restrict__ c = sc.insts + ci;
-      if (result && !SHADOW && c->has_xf) rn = normalize(mat3_mul(c->nrm, rn)); // shape.rs:131-132
-      found = fnd != 0u || result;
-      tris = false; // (only a group's leaf is ever suspended)
-      mode = LEAF;
-    }
-  }
-}
-template <bool SHADOW>
-__global__ void __launch_bounds__(256) rpt_tree_generic(Scene sc, RayBatch rb, int obj_index, const uint32_t* __restrict__ fq,
-                                                        const uint32_t* __restrict__ fq_count, GenericStack gs,
-                                                        uint32_t* __restrict__ overflow, uint32_t* __restrict__ zero_next) {
-  // the counters of the NEXT (tree, query) pair — the other of two sets (launch_query): this kernel is the last
-  // launch of every pair, and the set it clears was last used by the pair before.  One memset per pair less.
-  if (zero_next && blockIdx.x == 0 && threadIdx.x < 5u) zero_next[threadIdx.x] = 0u;
-  const uint32_t count = *fq_count;
-  CInst& in = cinst(sc, obj_index);
-  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid >= gs.threads) return; // (the grid never exceeds the columns: api_render.cpp / launch_query)
-  for (uint32_t i = tid; i < count; i += gridDim.x * blockDim.x) {
-    const uint32_t slot = fq[i];
-    D3 o = ld_soa3(rb.o, rb.o_stride, slot), d = ld_soa3(rb.d, rb.d_stride, slot);
-    if (in.has_xf) {
-      D3 lo = mat4_mul(in.inv, o, 1.0), ld = mat4_mul(in.inv, d, 0.0);
-      o = lo; d = ld;
-    }
-    const double t_stop = SHADOW ? fmin(rb.dist[slot], DBL_MAX_) : -INF;
-    double rt = rb.rt[slot];
-    if (SHADOW && rt <= t_stop) continue; // already occluded by an earlier object
-    D3 rn = mk(0, 0, 0);
-    const bool hit = generic_walk<SHADOW>(sc, (uint32_t)in.tree, in.kind == RPT_SHAPE_MESH, o, d, EPSILON, t_stop, rt, rn, gs, tid, overflow);
-    if (hit) {
-      rb.rt[slot] = rt;
-      if (!SHADOW) {
-        if (in.has_xf) rn = normalize(mat3_mul(in.nrm, rn)); // shape.rs:131-132
-        st_soa3(rb.rn, rb.n_stride, slot, rn);
-        rb.obj[slot] = obj_index;
-      }
-    }
-  }
-}
-
 // sample_lights' sum (renderer.rs:186-201) once every shadow ray of the depth has been resolved:
 // lights in scene order, starting from zero; A_k = emission + sum (renderer.rs:153-154)
 __global__ void __launch_bounds__(256) rpt_shadow_sum(Scene sc, PathState ps, const uint32_t* __restrict__ queue, uint32_t n,
@@ -1354,7 +280,7 @@ __global__ void __launch_bounds__(256) rpt_shadow_sum(Scene sc, PathState ps, co
     } else if (!null_contribution(contrib)) {
       // (a contribution that is exactly zero was never queued, rpt_shade: its srt entry is stale or was never written,
       // and adding a zero of either sign would change nothing: the sum starts at +0 and is never -0)
-      double t_stop = fmin(sh[3 * ps.cap + slot], DBL_MAX_);
+      double t_stop = light_stop(sh[3 * ps.cap + slot]);
       if (srt[(uint64_t)l * ps.cap + slot] > t_stop) color = color + contrib; // renderer.rs:197 (false for a NaN hit: visible())
     }
   }
