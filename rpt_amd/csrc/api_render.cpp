@@ -693,7 +693,7 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
 }
 
 int rptgpu_eval_math(rptgpu_scene* h, int fn, uint64_t n, const double* x, const double* y, double* out) {
-  if (!h || (n && (!x || !out)) || fn < 0 || fn > 7 || (fn >= 6 && n && !y))
+  if (!h || (n && (!x || !out)) || fn < 0 || fn > 11 || (fn >= 6 && n && !y))
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "bad argument");
   if (!n) return RPTGPU_OK;
   return guarded(h, h->device, [&]() -> int {

@@ -75,6 +75,13 @@
 #ifndef RPT_POOL_REFILL
 #define RPT_POOL_REFILL 56u
 #endif
+// RPT_DIV_BATCH=1: neighbouring independent f64 divisions are issued as one batch, stage by stage (kernels/vec.inc
+// div_ieee): every quotient keeps the eleven operations of the compiler's own expansion of `/` on the same operands,
+// only their order across the batch's slots changes, so every result keeps its bits.  0: every call site compiles to
+// the plain `/` it was (A/B builds)
+#ifndef RPT_DIV_BATCH
+#define RPT_DIV_BATCH 1
+#endif
 #define RPT_PATHS_POOL_LDS (RPT_POOL_CAP * 100u)
 static_assert(RPT_POOL_CAP >= 64u && RPT_POOL_REFILL >= 1u && RPT_POOL_REFILL <= RPT_POOL_CAP,
               "a refill of 64 lanes has to fit an empty pool, and a full pool has to fall to the refill mark");

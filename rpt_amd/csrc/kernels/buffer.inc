@@ -155,6 +155,28 @@ __global__ void __launch_bounds__(256) rpt_buffer_variance(const double* __restr
   out[p] = ss / ((double)nb - 1.0);
 }
 
+// fn 8-11 of rpt_eval_math: y / x through div_ieee<N> (vec.inc), N = 2, 3, 4, 6.  The n pairs are cut into N blocks of
+// t = n / N; thread i < t fills slot s from block s, at the block's position (i + s * 4099) % t — every slot of a batch
+// from another place, so that a mix-up of slots shows — and writes each quotient where its operands stand.  The
+// n - N * t pairs behind the blocks get the plain quotient
+template <int N> RPT_DEV void eval_div_batch(uint64_t i, uint64_t n, const double* x, const double* y, double* out) {
+  const uint64_t t = n / N;
+  if (i < t) {
+    uint64_t p[N];
+    double nn[N], dd[N], q[N];
+#pragma unroll
+    for (int s = 0; s < N; s++) {
+      p[s] = (uint64_t)s * t + (i + (uint64_t)s * 4099ull) % t;
+      nn[s] = y[p[s]];
+      dd[s] = x[p[s]];
+    }
+    div_ieee<N>(nn, dd, q);
+#pragma unroll
+    for (int s = 0; s < N; s++) out[p[s]] = q[s];
+  }
+  if (i < n - t * N) out[t * N + i] = y[t * N + i] / x[t * N + i];
+}
+
 __global__ void __launch_bounds__(256) rpt_eval_math(int fn, uint64_t n, const double* __restrict__ x,
                                                      const double* __restrict__ y, double* __restrict__ out) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -168,6 +190,10 @@ __global__ void __launch_bounds__(256) rpt_eval_math(int fn, uint64_t n, const d
     case 4: rptc_sincos_pio2(x[i], &s, &c); out[i] = c; break;
     case 5: out[i] = rptc_acos(x[i]); break;
     case 6: out[i] = rptc_atan2(y[i], x[i]); break;
+    case 8: eval_div_batch<2>(i, n, x, y, out); break;
+    case 9: eval_div_batch<3>(i, n, x, y, out); break;
+    case 10: eval_div_batch<4>(i, n, x, y, out); break;
+    case 11: eval_div_batch<6>(i, n, x, y, out); break;
     default: { // 7: y / x through the shared reciprocal wherever the kernels' range predicate allows it
       RcpD rc = rcp_make(x[i]);
       double a = fabs(y[i]);

@@ -741,7 +741,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       } else if (in_path) {
         const D3 world_pos = h_pos, nrm = h_nrm;
         const Material& mat = fl.obj_mat[h_obj];
-        const D3 wo = -normalize(d);
+        const D3 wo = -normalize_b(d);
         const D3 color = mat.emittance * ld3(mat.color);
         D3 wl, lt, wi;
         double dist;

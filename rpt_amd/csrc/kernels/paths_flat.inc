@@ -8,7 +8,7 @@ RPT_DEV bool cube_candidate_face(D3 o, const RcpD& rdx, const RcpD& rdy, const R
                                  uint32_t& face) {
   double x1, x2, y1, y2, z1, z2;
   uint32_t fx = 1u, fy = 3u, fz = 5u; // the ENTRY face along each axis: the normal -1 unless the interval was swapped
-  div6(-0.5 - o.x, 0.5 - o.x, rdx, -0.5 - o.y, 0.5 - o.y, rdy, -0.5 - o.z, 0.5 - o.z, rdz, x1, x2, y1, y2, z1, z2);
+  div6<true>(-0.5 - o.x, 0.5 - o.x, rdx, -0.5 - o.y, 0.5 - o.y, rdy, -0.5 - o.z, 0.5 - o.z, rdz, x1, x2, y1, y2, z1, z2);
   if (x1 > x2) { double t = x1; x1 = x2; x2 = t; fx = 0u; }
   if (y1 > y2) { double t = y1; y1 = y2; y2 = t; fy = 2u; }
   if (z1 > z2) { double t = z1; z1 = z2; z2 = t; fz = 4u; }
@@ -90,13 +90,14 @@ RPT_DEV uint32_t run_slabs(const Scene& sc, int i, const double* qt, double rt, 
   pick_; })
 // the leaf test of MESH object `obj`, a single-leaf tree, from its entry in FlatLds::obj_leaf (step 2 above; the ray in
 // the object's own space).  PACKED: the object filter's entries, which carry kind and has_xf above the count's 8 bits
-template <bool SHADOW, bool PACKED = false>
+// DIVB: the leaf's divisions in batches (shapes.inc tri_batch)
+template <bool SHADOW, bool PACKED = false, bool DIVB = false>
 RPT_DEV bool flat_leaf_test(const Scene& sc, const FlatLds* fl, int obj, D3 o, D3 d, double t_stop, double& rt, D3& rn) {
   const uint32_t* e = fl->obj_leaf[obj];
   LaneTree lt{e[0], e[1]};
   KdNode nd;
   nd.split = 0.0; nd.a = e[2]; nd.ib = ((PACKED ? e[3] & 0xffu : e[3]) << 2) | 3u;
-  return kd_leaf<true, SHADOW>(sc, lt, sc.refs + lt.ref_base, nd, o, d, EPSILON, t_stop, rt, rn);
+  return kd_leaf<true, SHADOW, DIVB>(sc, lt, sc.refs + lt.ref_base, nd, o, d, EPSILON, t_stop, rt, rn);
 }
 // ------------------------------------------------------------------ flat scenes with many objects: the object filter
 // A room of 23 polygons, three cubes and three spheres: the reference runs 29 object tests per ray (renderer.rs:211-220),
@@ -219,11 +220,45 @@ RPT_DEV uint64_t cull_skip_mask(const FlatLayout& lay, uint32_t near) {
 }
 #endif
 
+// an axis' share of the plane table: q[j][lane] = (pv[j] - o) / d for its cnt distinct planes (q: the lane's column).
+// The quotients are independent of each other, so they go two at a time as one batch (vec.inc div_ieee)
+RPT_DEV void plane_quotients(const double RPT_C* pv, uint32_t cnt, double o, double d, double* q) {
+  uint32_t j = 0;
+  for (; j + 2u <= cnt; j += 2u) {
+    const double n2[2] = {pv[j] - o, pv[j + 1u] - o}, d2[2] = {d, d};
+    double t[2];
+    div_ieee<2>(n2, d2, t);
+    q[j * 64u] = t[0]; q[(j + 1u) * 64u] = t[1];
+  }
+  for (; j < cnt; j++) q[j * 64u] = (pv[j] - o) / d;
+}
+// the same for the two rays of flat_query2, which share the numerators: two planes by both rays, a batch of four
+RPT_DEV void plane_quotients2(const double RPT_C* pv, uint32_t cnt, double o, double db, double ds, double* qb, double* qs) {
+  uint32_t j = 0;
+  for (; j + 2u <= cnt; j += 2u) {
+    const double a0 = pv[j] - o, a1 = pv[j + 1u] - o;
+    const double n4[4] = {a0, a0, a1, a1}, d4[4] = {db, ds, db, ds};
+    double t[4];
+    div_ieee<4>(n4, d4, t);
+    qb[j * 64u] = t[0]; qs[j * 64u] = t[1];
+    qb[(j + 1u) * 64u] = t[2]; qs[(j + 1u) * 64u] = t[3];
+  }
+  for (; j < cnt; j++) {
+    const double a = pv[j] - o;
+    const double n2[2] = {a, a}, d2[2] = {db, ds};
+    double t[2];
+    div_ieee<2>(n2, d2, t);
+    qb[j * 64u] = t[0]; qs[j * 64u] = t[1];
+  }
+}
+
 // CULL (the pre-trace pass of rpt_paths<KdFlat, false, true>, RPT_PRETRACE_CULL): bit k of the wave-uniform `skip` = no
 // ray of the wave can be accepted by object k (cull_skip_mask), its test is left out
 // CONSTS (rpt_paths<KdFlat, false, true, true>): the two-cube block takes an accepted cube's world normal from the
 // wave's table (SceneConsts, paths_consts.inc)
-template <bool SHADOW, bool CULL = false, bool CONSTS = false>
+// DIVB: the query's divisions in batches (vec.inc div_ieee) — the fused kernels' pre-trace pass, which is the caller
+// that sets CULL or CONSTS; the other kernels' queries keep the plain form (their registers: vec.inc)
+template <bool SHADOW, bool CULL = false, bool CONSTS = false, bool DIVB = CULL || CONSTS>
 RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_stop, double& rt, D3& rn, uint64_t skip = 0ull) {
   int obj = -1;
   uint32_t cslot = 0; // CONSTS: the next two-cube block's first cube in the table of normals (cube_nrm_of)
@@ -233,9 +268,16 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
   if (fl->plane_cnt) { // every distinct (plane - o) / d once per ray: the operands, hence the bits, of the per-object form
     const double RPT_C* pv = (const double RPT_C*)fl->plane_vals;
     const uint32_t nx = fl->plane_cnt & 15u, ny = (fl->plane_cnt >> 4) & 15u, nz = (fl->plane_cnt >> 8) & 15u;
-    for (uint32_t j = 0; j < nx; j++) fl->qtab[j * 64u + lane] = (pv[j] - o.x) / d.x;
-    for (uint32_t j = 0; j < ny; j++) fl->qtab[(nx + j) * 64u + lane] = (pv[4u + j] - o.y) / d.y;
-    for (uint32_t j = 0; j < nz; j++) fl->qtab[(nx + ny + j) * 64u + lane] = (pv[8u + j] - o.z) / d.z;
+    if constexpr (DIVB && RPT_DIV_BATCH != 0) {
+      double* q = fl->qtab + lane;
+      plane_quotients(pv, nx, o.x, d.x, q);
+      plane_quotients(pv + 4, ny, o.y, d.y, q + nx * 64u);
+      plane_quotients(pv + 8, nz, o.z, d.z, q + (nx + ny) * 64u);
+    } else {
+      for (uint32_t j = 0; j < nx; j++) fl->qtab[j * 64u + lane] = (pv[j] - o.x) / d.x;
+      for (uint32_t j = 0; j < ny; j++) fl->qtab[(nx + j) * 64u + lane] = (pv[4u + j] - o.y) / d.y;
+      for (uint32_t j = 0; j < nz; j++) fl->qtab[(nx + ny + j) * 64u + lane] = (pv[8u + j] - o.z) / d.z;
+    }
   }
   int i = 0;
   while (i < n) {
@@ -259,7 +301,7 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
           CInst& q = cinst(sc, i + k);
           if (q.kind == RPT_SHAPE_MESH && !q.has_xf) {
             double fax, fbx, fay, fby, faz, fbz; // q.bounds == trees[q.tree].bounds (kdtree.rs:103)
-            div6(q.bounds[0] - o.x, q.bounds[3] - o.x, rwx, q.bounds[1] - o.y, q.bounds[4] - o.y, rwy,
+            div6<DIVB>(q.bounds[0] - o.x, q.bounds[3] - o.x, rwx, q.bounds[1] - o.y, q.bounds[4] - o.y, rwy,
                  q.bounds[2] - o.z, q.bounds[5] - o.z, rwz, fax, fbx, fay, fby, faz, fbz);
             double b_min, b_max;
             slab_window(fax, fbx, fay, fby, faz, fbz, b_min, b_max);
@@ -278,7 +320,7 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
           cand &= cand - 1u;
           const double mt = RUN_PICK(m, k);
           if (!(mt > rt)) {
-            if (flat_leaf_test<SHADOW>(sc, fl, i + k, o, d, t_stop, rt, rn)) obj = i + k;
+            if (flat_leaf_test<SHADOW, false, DIVB>(sc, fl, i + k, o, d, t_stop, rt, rn)) obj = i + k;
             if (SHADOW && rt <= t_stop) cand = 0u;
           }
         }
@@ -304,19 +346,19 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
       double t1 = 0.0, t2 = 0.0;
       D3 n1 = mk(0, 0, 0), n2 = mk(0, 0, 0);
       uint32_t f1 = 0u, f2 = 0u;
-      bool c1 = TAB ? cube_candidate_face(lo1, ax, ay, az, EPSILON, t1, f1) : cube_candidate(lo1, ax, ay, az, EPSILON, t1, n1);
-      bool c2 = TAB ? cube_candidate_face(lo2, bx, by, bz, EPSILON, t2, f2) : cube_candidate(lo2, bx, by, bz, EPSILON, t2, n2);
+      bool c1 = TAB ? cube_candidate_face(lo1, ax, ay, az, EPSILON, t1, f1) : cube_candidate<DIVB>(lo1, ax, ay, az, EPSILON, t1, n1);
+      bool c2 = TAB ? cube_candidate_face(lo2, bx, by, bz, EPSILON, t2, f2) : cube_candidate<DIVB>(lo2, bx, by, bz, EPSILON, t2, n2);
       if (c1 && t1 < rt) {
         rt = t1;
         if constexpr (TAB) rn = cube_nrm_of(fl, cslot, f1);
-        else if (!SHADOW) rn = normalize(mat3_mul(in.nrm, n1)); // Transformed::intersect shape.rs:131-132
+        else if (!SHADOW) rn = normalize_t<DIVB>(mat3_mul(in.nrm, n1)); // Transformed::intersect shape.rs:131-132
         obj = i;
       }
       if (SHADOW && rt <= t_stop) return obj;
       if (c2 && t2 < rt) {
         rt = t2;
         if constexpr (TAB) rn = cube_nrm_of(fl, cslot + 1u, f2);
-        else if (!SHADOW) rn = normalize(mat3_mul(in2.nrm, n2));
+        else if (!SHADOW) rn = normalize_t<DIVB>(mat3_mul(in2.nrm, n2));
         obj = i + 1;
       }
       if (SHADOW && rt <= t_stop) return obj;
@@ -343,7 +385,7 @@ RPT_DEV int flat_query(const Scene& sc, const FlatLds* fl, D3 o, D3 d, double t_
 // visibility as flat_query<true>'s does — it only skips work once rts <= t_stop, and rts never grows again, so
 // `rts > t_stop` comes out the same.  What the shared origin allows is computed once: the plane-table numerators
 // pv - o and each cube's inv * o.  The two rays' slab quotients, wall candidates and cube candidates sit side by side in
-// straight-line code, so that the two dependency chains overlap.
+// straight-line code, so that the two dependency chains overlap; its divisions go in batches (vec.inc div_ieee).
 // A slot that is off (no bounce ray: the path ends at this hit) enters with its record at -inf: no test accepts.
 // CONSTS: as in flat_query.
 template <bool CONSTS_>
@@ -360,6 +402,11 @@ RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, 
     const double RPT_C* pv = (const double RPT_C*)fl->plane_vals;
     double* qb = fl->qtab + lane;
     double* qs = qb + nq * 64u;
+#if RPT_DIV_BATCH
+    plane_quotients2(pv, nx, o.x, db.x, ds.x, qb, qs);
+    plane_quotients2(pv + 4, ny, o.y, db.y, ds.y, qb + nx * 64u, qs + nx * 64u);
+    plane_quotients2(pv + 8, nz, o.z, db.z, ds.z, qb + (nx + ny) * 64u, qs + (nx + ny) * 64u);
+#else
     for (uint32_t j = 0; j < nx; j++) { const double a = pv[j] - o.x; qb[j * 64u] = a / db.x; qs[j * 64u] = a / ds.x; }
     for (uint32_t j = 0; j < ny; j++) {
       const double a = pv[4u + j] - o.y;
@@ -369,6 +416,7 @@ RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, 
       const double a = pv[8u + j] - o.z;
       qb[(nx + ny + j) * 64u] = a / db.z; qs[(nx + ny + j) * 64u] = a / ds.z;
     }
+#endif
   }
   int i = 0;
   while (i < n) {
@@ -387,7 +435,7 @@ RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, 
           const int k = __ffs((int)cb) - 1;
           cb &= cb - 1u;
           const double mt = RUN_PICK(mb, k);
-          if (!(mt > rtb) && flat_leaf_test<false>(sc, fl, i + k, o, db, -INF, rtb, rnb)) obj = i + k;
+          if (!(mt > rtb) && flat_leaf_test<false, false, true>(sc, fl, i + k, o, db, -INF, rtb, rnb)) obj = i + k;
         }
         if (cs != 0u) { // the shadow ray's
           const int k = __ffs((int)cs) - 1;
@@ -395,7 +443,7 @@ RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, 
           const double mt = RUN_PICK(ms, k);
           if (!(mt > rts)) {
             D3 srn = mk(0, 0, 0);
-            flat_leaf_test<true>(sc, fl, i + k, o, ds, t_stop, rts, srn);
+            flat_leaf_test<true, false, true>(sc, fl, i + k, o, ds, t_stop, rts, srn);
             if (rts <= t_stop) cs = 0u;
           }
         }
@@ -415,12 +463,12 @@ RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, 
         double tb = 0.0, ts = 0.0;
         D3 nb = mk(0, 0, 0), ns = mk(0, 0, 0);
         uint32_t fb = 0u;
-        const bool hb = CONSTS ? cube_candidate_face(lo, bx, by, bz, EPSILON, tb, fb) : cube_candidate(lo, bx, by, bz, EPSILON, tb, nb);
-        const bool hs = cube_candidate(lo, sx, sy, sz, EPSILON, ts, ns);
+        const bool hb = CONSTS ? cube_candidate_face(lo, bx, by, bz, EPSILON, tb, fb) : cube_candidate<true>(lo, bx, by, bz, EPSILON, tb, nb);
+        const bool hs = cube_candidate<true>(lo, sx, sy, sz, EPSILON, ts, ns);
         if (hb && tb < rtb) {
           rtb = tb;
           if constexpr (CONSTS) rnb = cube_nrm_of(fl, cslot + (uint32_t)c, fb);
-          else rnb = normalize(mat3_mul(q.nrm, nb)); // Transformed::intersect shape.rs:131-132
+          else rnb = normalize_b(mat3_mul(q.nrm, nb)); // Transformed::intersect shape.rs:131-132
           obj = i + c;
         }
         if (hs && ts < rts) rts = ts;

@@ -1,5 +1,6 @@
 // kernels/paths_shade.inc — the fused rpt_paths' draw-first shading: hit_draws, bsdf_opaque, sample_f_opaque, illuminate_mesh.
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
+// These functions serve the fused kernels only, so their divisions go in batches (vec.inc div_ieee: div3, normalize_b).
 
 #if RPT_SHADE_SPLIT
 // ------------------------------------------------------------------ a hit's draws first, its shading in one block
@@ -62,18 +63,30 @@ RPT_DEV D3 bsdf_opaque(const Material& m, D3 n, D3 wo, D3 wi, const MatConsts* m
     f0 = lerp(mk(f0s, f0s, f0s), color, m.metallic);
     omf0 = one - f0;
   }
-  D3 h = normalize(wi + wo); // (wi * 1.0 + wo in bsdf)
+  D3 h = normalize_b(wi + wo); // (wi * 1.0 + wo in bsdf)
   double wo_dot_h = dot(wo, h);
   double n_dot_h = dot(n, h);
   double nh2 = pow2(n_dot_h);
+#if RPT_DIV_BATCH
+  // the exponent of dd and g's quotient wait for nothing of each other: one batch of two
+  double ga = n_dot_wi * n_dot_h, gb = n_dot_wo * n_dot_h;
+  double g = fmin(ga, gb);
+  const double sn[2] = {nh2 - 1.0, 2.0 * g}, sd[2] = {m2 * nh2, wo_dot_h};
+  double sq[2];
+  div_ieee<2>(sn, sd, sq);
+  double dd = rptc_exp(sq[0]) / (m2pi * nh2 * nh2);
+  D3 f = f0 + omf0 * pow5(1.0 - wo_dot_h);
+  g = sq[1];
+#else
   double dd = rptc_exp((nh2 - 1.0) / (m2 * nh2)) / (m2pi * nh2 * nh2);
   D3 f = f0 + omf0 * pow5(1.0 - wo_dot_h);
   double ga = n_dot_wi * n_dot_h, gb = n_dot_wo * n_dot_h;
   double g = fmin(ga, gb);
   g = (2.0 * g) / wo_dot_h;
+#endif
   g = fmin(g, 1.0);
-  D3 q = dd * f * g / (4.0 * n_dot_wo * n_dot_wi);
-  D3 diffuse = cmul(one - f, color) / PI;
+  D3 q = div3(dd * f * g, 4.0 * n_dot_wo * n_dot_wi);
+  D3 diffuse = div3(cmul(one - f, color), PI);
   return lit ? q + diffuse : mk(0, 0, 0);
 }
 
@@ -91,13 +104,16 @@ RPT_DEV void sample_f_opaque(const Material& m, D3 n, D3 wo, double f, const Hit
   double sin_t, cos_t;
   rptc_sincos_pio2(theta, &sin_t, &cos_t);
   double diff = x * x - y * y;
-  double cx = diff / sum, cy = 2.0 * x * y / sum;
+  const double cn[2] = {diff, 2.0 * x * y}, cd[2] = {sum, sum}; // cx = diff / sum, cy = 2xy / sum: one batch
+  double cq[2];
+  div_ieee<2>(cn, cd, cq);
+  const double cx = cq[0], cy = cq[1];
   const D3 loc = dr.spec ? mk(cx * sin_t, cy * sin_t, cos_t) : mk(x, y, sqrt(1.0 - x * x - y * y));
   const D3 world = local_to_world_mul(n, loc);
   wi = dr.spec ? -(wo - world * (dot(world, wo) * 2.0)) : world; // -glm::reflect_vec(wo, h)
   double p = 0.0;
   {
-    D3 h = normalize(wi + wo);
+    D3 h = normalize_b(wi + wo);
     double p_h;
     if constexpr (CONSTS) { // beckmann_pdf with its PI * m2 from the table (the product m2 * PI: the same number)
       double cos_t = fabs(dot(h, n));
@@ -121,7 +137,7 @@ RPT_DEV void illuminate_mesh(CLight& l, CTree& tr, const Tri* __restrict__ tp, D
   double w = 1.0 - u - v;
   D3 v1 = ld3(tp->v), v2 = ld3(tp->v + 3), v3 = ld3(tp->v + 6);
   D3 n1 = ld3(tp->v + 9), n2 = ld3(tp->v + 12), n3 = ld3(tp->v + 15);
-  SampleOut s{u * v1 + v * v2 + w * v3, normalize(u * n1 + v * n2 + w * n3), 0.0};
+  SampleOut s{u * v1 + v * v2 + w * v3, normalize_b(u * n1 + v * n2 + w * n3), 0.0};
   if constexpr (CONSTS) {
     s.p = light_pdf[dr.tri];
   } else {
@@ -131,10 +147,21 @@ RPT_DEV void illuminate_mesh(CLight& l, CTree& tr, const Tri* __restrict__ tp, D
   }
   D3 disp = s.v - pos;
   double len = length(disp);
+#if RPT_DIV_BATCH
+  // cosine and wi = disp / len share the divisor and wait for nothing else: one batch of four
+  const double ln[4] = {fmax(-dot(disp, s.n), 0.0), disp.x, disp.y, disp.z}, ld[4] = {len, len, len, len};
+  double lq[4];
+  div_ieee<4>(ln, ld, lq);
+  double cosine = lq[0];
+  double surface_area = fmax(cosine, 0.0) / (len * len);
+  intensity = div3(ld3(l.mat_color) * l.mat_emittance * surface_area, s.p);
+  wi = mk(lq[1], lq[2], lq[3]);
+#else
   double cosine = fmax(-dot(disp, s.n), 0.0) / len;
   double surface_area = fmax(cosine, 0.0) / (len * len);
   intensity = ld3(l.mat_color) * l.mat_emittance * surface_area / s.p;
   wi = disp / len;
+#endif
   dist = len;
 }
 #endif

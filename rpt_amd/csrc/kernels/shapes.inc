@@ -42,11 +42,12 @@ template <class P> RPT_DEV bool isect_plane(P pl, D3 o, D3 d, double t_min, doub
 
 // Cube::intersect (cube.rs:20-72) in two steps: everything up to the candidate (time, normal), which does not
 // depend on the record, and the accept against record.time.  Split so that two cubes can be evaluated side by side.
+template <bool DIVB = false> // the six slab quotients as one batch (vec.inc div6)
 RPT_DEV bool cube_candidate(D3 o, const RcpD& rdx, const RcpD& rdy, const RcpD& rdz, double t_min, double& time,
                             D3& normal) {
   // compute_interval per axis: (t1, t2) sorted, s = sign of the ENTRY face normal along the axis
   double x1, x2, y1, y2, z1, z2, sx = -1.0, sy = -1.0, sz = -1.0;
-  div6(-0.5 - o.x, 0.5 - o.x, rdx, -0.5 - o.y, 0.5 - o.y, rdy, -0.5 - o.z, 0.5 - o.z, rdz, x1, x2, y1, y2, z1, z2);
+  div6<DIVB>(-0.5 - o.x, 0.5 - o.x, rdx, -0.5 - o.y, 0.5 - o.y, rdy, -0.5 - o.z, 0.5 - o.z, rdz, x1, x2, y1, y2, z1, z2);
   if (x1 > x2) { double t = x1; x1 = x2; x2 = t; sx = 1.0; }
   if (y1 > y2) { double t = y1; y1 = y2; y2 = t; sy = 1.0; }
   if (z1 > z2) { double t = z1; z1 = z2; z2 = t; sz = 1.0; }
@@ -172,6 +173,39 @@ RPT_DEV TriBary tri_bary(const TriX* __restrict__ tx, TriPlane pl, D3 o, D3 d) {
   b.u = 1.0 - b.v - b.w;
   return b;
 }
+// tri_plane of two records, their two `time` divisions as one batch, and tri_bary of two plane hits, the four
+// barycentric quotients as one batch (vec.inc div_ieee): each value is the one the single form computes
+RPT_DEV void tri_plane2(const TriX* __restrict__ ta, const TriX* __restrict__ tb, D3 o, D3 d, TriPlane& pa, TriPlane& pb) {
+  D3 pna = ld3(ta->pn), v1a = ld3(ta->v1), pnb = ld3(tb->pn), v1b = ld3(tb->v1);
+  pa.cosine = dot(pna, d);
+  pb.cosine = dot(pnb, d);
+  const double n[2] = {dot(pna, v1a - o), dot(pnb, v1b - o)}, c[2] = {pa.cosine, pb.cosine};
+  double t[2];
+  div_ieee<2>(n, c, t);
+  pa.time = t[0];
+  pb.time = t[1];
+}
+RPT_DEV void tri_bary2(const TriX* __restrict__ ta, TriPlane pa, const TriX* __restrict__ tb, TriPlane pb, D3 o, D3 d,
+                       TriBary& ba, TriBary& bb) {
+  double n[4], c[4], q[4];
+  const TriX* __restrict__ tx[2] = {ta, tb};
+  const double time[2] = {pa.time, pb.time};
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    D3 v1 = ld3(tx[k]->v1), d0 = ld3(tx[k]->d0), d1 = ld3(tx[k]->d1);
+    D3 d2 = (o + time[k] * d) - v1;
+    double d00 = tx[k]->d00, d01 = tx[k]->d01, d11 = tx[k]->d11;
+    double d20 = dot(d2, d0);
+    double d21 = dot(d2, d1);
+    n[2 * k] = d11 * d20 - d01 * d21;
+    n[2 * k + 1] = d00 * d21 - d01 * d20;
+    c[2 * k] = c[2 * k + 1] = tx[k]->denom;
+  }
+  div_ieee<4>(n, c, q);
+  ba.v = q[0]; ba.w = q[1]; ba.u = 1.0 - ba.v - ba.w;
+  bb.v = q[2]; bb.w = q[3]; bb.u = 1.0 - bb.v - bb.w;
+}
+template <bool DIVB = false> // the two barycentric quotients and the normal's three as batches
 RPT_DEV bool tri_accept(const TriX* __restrict__ tx, const Tri* __restrict__ tris, const uint32_t* __restrict__ refp,
                         TriPlane pl, D3 o, D3 d, double t_min, double& rt, D3& rn, const bool want_n) { // mesh.rs:53-82
   const double time = pl.time;
@@ -181,15 +215,24 @@ RPT_DEV bool tri_accept(const TriX* __restrict__ tx, const Tri* __restrict__ tri
   double d00 = tx->d00, d01 = tx->d01, d11 = tx->d11, denom = tx->denom;
   double d20 = dot(d2, d0);
   double d21 = dot(d2, d1);
-  double v = (d11 * d20 - d01 * d21) / denom;
-  double w = (d00 * d21 - d01 * d20) / denom;
+  double v, w;
+  if constexpr (DIVB) {
+    const double bn[2] = {d11 * d20 - d01 * d21, d00 * d21 - d01 * d20}, bd[2] = {denom, denom};
+    double bq[2];
+    div_ieee<2>(bn, bd, bq);
+    v = bq[0];
+    w = bq[1];
+  } else {
+    v = (d11 * d20 - d01 * d21) / denom;
+    w = (d00 * d21 - d01 * d20) / denom;
+  }
   double u = 1.0 - v - w;
   if ((u >= 0.0) & (v >= 0.0) & (w >= 0.0)) {
     rt = time;
     if (want_n) { // the triangle's index is only needed for its vertex normals
       const Tri* tp = tris + *refp;
       D3 n1 = ld3(tp->v + 9), n2 = ld3(tp->v + 12), n3 = ld3(tp->v + 15);
-      rn = normalize(u * n1 + v * n2 + w * n3);
+      rn = normalize_t<DIVB>(u * n1 + v * n2 + w * n3);
     }
     return true;
   }
@@ -237,18 +280,32 @@ RPT_DEV bool isect_child(const ChildM& c, const Inst* __restrict__ in, D3 o, D3 
 
 // up to four consecutive leaf entries: loads and `time` divisions of all of them are issued
 // before the order-dependent accept step (m = entries left in the leaf, >= 1)
-template <bool SHADOW>
+// DIVB (the fused path kernels): the `time` divisions two by two, a quad's four barycentric quotients and the normal's
+// three as batches (tri_plane2, tri_bary2, normalize_b)
+template <bool SHADOW, bool DIVB_ = false>
 RPT_DEV bool tri_batch(const TriX* __restrict__ recs, const Tri* __restrict__ tris, const uint32_t* __restrict__ refp,
                        uint32_t m, bool pair_only, D3 o, D3 d, double t_min, double& rt, D3& rn) {
+  constexpr bool DIVB = DIVB_ && RPT_DIV_BATCH != 0;
   bool found = false, h;
-  TriPlane p0 = tri_plane(recs, o, d);
-  TriPlane p1 = tri_plane(recs + (m > 1 ? 1u : 0u), o, d);
+  TriPlane p0, p1;
+  if constexpr (DIVB) {
+    tri_plane2(recs, recs + (m > 1 ? 1u : 0u), o, d, p0, p1);
+  } else {
+    p0 = tri_plane(recs, o, d);
+    p1 = tri_plane(recs + (m > 1 ? 1u : 0u), o, d);
+  }
   if (pair_only) { // a quad's two triangles (polygon(), shape.rs:307-313): no second pair to overlap
     if (m > 1) {
       // Both barycentric evaluations (mesh.rs:60-72) in one straight-line block — they depend on the record only
       // through the `time < record.time` guard — then the two accepts in the reference's order.  A value computed
       // for a triangle whose guard fails is simply not used.
-      TriBary b0 = tri_bary(recs, p0, o, d), b1 = tri_bary(recs + 1, p1, o, d);
+      TriBary b0, b1;
+      if constexpr (DIVB) {
+        tri_bary2(recs, p0, recs + 1, p1, o, d, b0, b1);
+      } else {
+        b0 = tri_bary(recs, p0, o, d);
+        b1 = tri_bary(recs + 1, p1, o, d);
+      }
       int win = -1;
       if (!(fabs(p0.cosine) < 1e-8) && !(p0.time < t_min || p0.time >= rt) && b0.u >= 0.0 && b0.v >= 0.0 && b0.w >= 0.0) {
         rt = p0.time;
@@ -262,19 +319,24 @@ RPT_DEV bool tri_batch(const TriX* __restrict__ recs, const Tri* __restrict__ tr
         const Tri* tp = tris + refp[win];
         TriBary b = win ? b1 : b0;
         D3 n1 = ld3(tp->v + 9), n2 = ld3(tp->v + 12), n3 = ld3(tp->v + 15);
-        rn = normalize(b.u * n1 + b.v * n2 + b.w * n3);
+        rn = normalize_t<DIVB>(b.u * n1 + b.v * n2 + b.w * n3);
       }
       return win >= 0;
     }
-    return tri_accept(recs, tris, refp, p0, o, d, t_min, rt, rn, !SHADOW);
+    return tri_accept<DIVB>(recs, tris, refp, p0, o, d, t_min, rt, rn, !SHADOW);
   }
-  TriPlane p2 = tri_plane(recs + (m > 2 ? 2u : 0u), o, d);
-  TriPlane p3 = tri_plane(recs + (m > 3 ? 3u : 0u), o, d);
-  h = tri_accept(recs, tris, refp, p0, o, d, t_min, rt, rn, !SHADOW);
+  TriPlane p2, p3;
+  if constexpr (DIVB) {
+    tri_plane2(recs + (m > 2 ? 2u : 0u), recs + (m > 3 ? 3u : 0u), o, d, p2, p3);
+  } else {
+    p2 = tri_plane(recs + (m > 2 ? 2u : 0u), o, d);
+    p3 = tri_plane(recs + (m > 3 ? 3u : 0u), o, d);
+  }
+  h = tri_accept<DIVB>(recs, tris, refp, p0, o, d, t_min, rt, rn, !SHADOW);
   found = found || h;
-  if (m > 1) { h = tri_accept(recs + 1, tris, refp + 1, p1, o, d, t_min, rt, rn, !SHADOW); found = found || h; }
-  if (m > 2) { h = tri_accept(recs + 2, tris, refp + 2, p2, o, d, t_min, rt, rn, !SHADOW); found = found || h; }
-  if (m > 3) { h = tri_accept(recs + 3, tris, refp + 3, p3, o, d, t_min, rt, rn, !SHADOW); found = found || h; }
+  if (m > 1) { h = tri_accept<DIVB>(recs + 1, tris, refp + 1, p1, o, d, t_min, rt, rn, !SHADOW); found = found || h; }
+  if (m > 2) { h = tri_accept<DIVB>(recs + 2, tris, refp + 2, p2, o, d, t_min, rt, rn, !SHADOW); found = found || h; }
+  if (m > 3) { h = tri_accept<DIVB>(recs + 3, tris, refp + 3, p3, o, d, t_min, rt, rn, !SHADOW); found = found || h; }
   return found;
 }
 
@@ -425,7 +487,7 @@ struct KdNoLds;
 // A GROUP leaf here holds placed spheres, cubes and monomial surfaces only: an object whose group has TREE children (a
 // mesh or another group, to any depth) never reaches these kernels — the per-tree pipeline walks it with rpt_nest_trace
 // or rpt_tree_generic (kernels/tree_trace.inc, tree_generic.inc; api_scene.cpp routes by Tree::tree_kids).
-template <bool TRIS, bool SHADOW, class TreeT>
+template <bool TRIS, bool SHADOW, bool DIVB = false /* tri_batch's */, class TreeT>
 RPT_DEV bool kd_leaf(const Scene& sc, const TreeT& tr, const uint32_t* __restrict__ refs, KdNode n, D3 o, D3 d,
                      double t_min, double t_stop, double& rt, D3& rn, const BoxRay* br = nullptr) {
   bool found = false;
@@ -477,7 +539,7 @@ RPT_DEV bool kd_leaf(const Scene& sc, const TreeT& tr, const uint32_t* __restric
     const Tri* __restrict__ tris = sc.tris + tr.prim_base;
     for (uint32_t b = 0; b < cnt; b += 4) {
       PROF_COUNT(PF_IK_TRI);
-      bool h = tri_batch<SHADOW>(recs + b, tris, refs + first + b, cnt - b, cnt <= 2, o, d, t_min, rt, rn);
+      bool h = tri_batch<SHADOW, DIVB>(recs + b, tris, refs + first + b, cnt - b, cnt <= 2, o, d, t_min, rt, rn);
       found = found || h;
       if (SHADOW && rt <= t_stop) break;
     }

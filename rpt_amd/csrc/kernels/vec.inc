@@ -65,16 +65,76 @@ RPT_DEV bool safe_coord(double x) {
 RPT_DEV double fmin_raw(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 RPT_DEV double fmax_raw(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 RPT_DEV double div_r(double n, const RcpD& rc) { return n / rc.d; }
-// six slab quotients, two per axis (BoundingBox::intersect kdtree.rs:54-68, Cube::intersect cube.rs:20-37)
+// N independent IEEE quotients q[k] = n[k] / d[k], issued as one batch (RPT_DIV_BATCH, kernels.h).  The compiler expands
+// every f64 `/` into ONE dependent chain of eleven instructions, ten deep, and in the path kernels (256 VGPRs, two waves
+// per SIMD) it leaves neighbouring chains one after the other, each paying the wait for VCC in front of v_div_fmas.
+// Here every slot performs that expansion op for op, on the same operands — div_scale(d, d, n), rcp, two Newton steps
+// on the reciprocal, div_scale(n, d, n) with its flag, the product, its residual, div_fmas under that flag,
+// div_fixup(., d, n) — so a slot's result is the bits of n / d for EVERY operand pair, zeros, infinities, NaNs and
+// denormals included (they take the route they take in `/`; no range predicate, unlike div_fast above); but the batch
+// is written stage by stage, all slots' scales, then all reciprocals, and so on, so that the N chains interleave.
+// (tests/test_gpu_div_batch.py: N = 2, 3, 4, 6 against numpy, bit for bit.)  With RPT_DIV_BATCH=0, or in a file that
+// takes vec.inc without kernels.h (particles.hip), the slots are the plain `/` in slot order.
+template <int N> RPT_DEV void div_ieee(const double (&n)[N], const double (&d)[N], double (&q)[N]) {
+#if RPT_DIV_BATCH
+  double ds[N], ns[N], r[N], e[N], m[N];
+  bool f[N], f0;
+#pragma unroll
+  for (int k = 0; k < N; k++) ds[k] = __builtin_amdgcn_div_scale(n[k], d[k], false, &f0);
+#pragma unroll
+  for (int k = 0; k < N; k++) r[k] = __builtin_amdgcn_rcp(ds[k]);
+#pragma unroll
+  for (int k = 0; k < N; k++) e[k] = __builtin_fma(-ds[k], r[k], 1.0);
+#pragma unroll
+  for (int k = 0; k < N; k++) r[k] = __builtin_fma(r[k], e[k], r[k]);
+#pragma unroll
+  for (int k = 0; k < N; k++) e[k] = __builtin_fma(-ds[k], r[k], 1.0);
+#pragma unroll
+  for (int k = 0; k < N; k++) ns[k] = __builtin_amdgcn_div_scale(n[k], d[k], true, &f[k]);
+#pragma unroll
+  for (int k = 0; k < N; k++) r[k] = __builtin_fma(r[k], e[k], r[k]);
+#pragma unroll
+  for (int k = 0; k < N; k++) m[k] = ns[k] * r[k];
+#pragma unroll
+  for (int k = 0; k < N; k++) e[k] = __builtin_fma(-ds[k], m[k], ns[k]);
+#pragma unroll
+  for (int k = 0; k < N; k++) m[k] = __builtin_amdgcn_div_fmas(e[k], r[k], m[k], f[k]);
+#pragma unroll
+  for (int k = 0; k < N; k++) q[k] = __builtin_amdgcn_div_fixup(m[k], d[k], n[k]);
+#else
+#pragma unroll
+  for (int k = 0; k < N; k++) q[k] = n[k] / d[k];
+#endif
+}
+// The batch form costs registers where it stands, and the instantiations of rpt_paths other than the fused ones gain
+// VGPR spills and scratch from it (profiles/div_batch_ab.txt), so the shared helpers take it as a template flag, DIVB,
+// that only the fused kernels' call chain sets: div6<true>, div3 / normalize_b, normalize_t<DIVB>.  Without the flag a
+// helper is the code it always was.
+// six slab quotients, two per axis (BoundingBox::intersect kdtree.rs:54-68, Cube::intersect cube.rs:20-37); DIVB: one batch
+template <bool DIVB = false>
 RPT_DEV void div6(double n0, double n1, const RcpD& rx, double n2, double n3, const RcpD& ry, double n4, double n5,
                   const RcpD& rz, double& q0, double& q1, double& q2, double& q3, double& q4, double& q5) {
-  q0 = div_r(n0, rx); q1 = div_r(n1, rx);
-  q2 = div_r(n2, ry); q3 = div_r(n3, ry);
-  q4 = div_r(n4, rz); q5 = div_r(n5, rz);
+  if constexpr (DIVB) {
+    const double n[6] = {n0, n1, n2, n3, n4, n5}, d[6] = {rx.d, rx.d, ry.d, ry.d, rz.d, rz.d};
+    double q[6];
+    div_ieee<6>(n, d, q);
+    q0 = q[0]; q1 = q[1]; q2 = q[2]; q3 = q[3]; q4 = q[4]; q5 = q[5];
+  } else {
+    q0 = div_r(n0, rx); q1 = div_r(n1, rx);
+    q2 = div_r(n2, ry); q3 = div_r(n3, ry);
+    q4 = div_r(n4, rz); q5 = div_r(n5, rz);
+  }
 }
 RPT_DEV D3 operator/(D3 a, double s) {
   RcpD rc = rcp_make(s);
   return {div_r(a.x, rc), div_r(a.y, rc), div_r(a.z, rc)};
+}
+// a / s with its three quotients as one batch
+RPT_DEV D3 div3(D3 a, double s) {
+  const double n[3] = {a.x, a.y, a.z}, d[3] = {s, s, s};
+  double q[3];
+  div_ieee<3>(n, d, q);
+  return {q[0], q[1], q[2]};
 }
 RPT_DEV D3 cmul(D3 a, D3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
 // nalgebra's 3-vector dot: the three products summed left to right
@@ -82,6 +142,11 @@ RPT_DEV double dot(D3 a, D3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 RPT_DEV double length2(D3 a) { return dot(a, a); }
 RPT_DEV double length(D3 a) { return sqrt(dot(a, a)); }
 RPT_DEV D3 normalize(D3 a) { return a / length(a); }
+RPT_DEV D3 normalize_b(D3 a) { return div3(a, length(a)); }
+template <bool DIVB> RPT_DEV D3 normalize_t(D3 a) {
+  if constexpr (DIVB) return normalize_b(a);
+  else return normalize(a);
+}
 RPT_DEV D3 cross(D3 a, D3 b) {
   return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
