@@ -795,6 +795,14 @@ class Renderer {
     check(rptgpu_scene_set_objects(handle_, objs.size(), oi.data(), objs.data()));
     check(rptgpu_scene_set_lights(handle_, lights.size(), li.data(), lights.data()));
   }
+  // addition: a deforming mesh.  Object `object` of the Scene, a Mesh, gets `triangles` (as many as it has: deformation
+  // keeps the count) in the scene handle this Renderer holds (rptgpu_scene_set_mesh): its records and kd-tree are rebuilt
+  // on the device, everything else of the handle stays, and the next render equals that of a new Renderer of a Scene
+  // whose mesh has these triangles.  Before the first render there is no handle yet and nothing to push.
+  void update_mesh(uint32_t object, const std::vector<RptTriangle>& triangles) {
+    if (!handle_) return;
+    check(rptgpu_scene_set_mesh(handle_, object, triangles.size(), triangles.data()));
+  }
 
  private:
   void check(int code) {

@@ -342,6 +342,28 @@ int rptgpu_scene_set_objects(rptgpu_scene* h, uint64_t n, const uint32_t* index,
  * kind must be unchanged; a Light::Object's shape geometry is not read. */
 int rptgpu_scene_set_lights(rptgpu_scene* h, uint64_t n, const uint32_t* index, const RptLight* lights);
 
+/* ---- a deforming mesh on a live handle (cloth, a character, a surface driven by the particle systems): new triangles
+ * for one mesh, the count unchanged.  Additions within ABI version 7, detected by symbol (dlsym "rptgpu_scene_set_mesh").
+ * `object` is a top-level object whose shape is a Mesh; n must equal its triangle count at creation (deformation, not
+ * re-topology).  The triangles' records are made on the device, the mesh's kd-tree is rebuilt by the builder creation
+ * would use, and everything creation derives from the tree follows, so that afterwards every result — frames under
+ * every flag, rptgpu_closest_hit, rptgpu_render_aov, rptgpu_trace_rays, rptgpu_bake_probes, rptgpu_buffer_* — is
+ * bit-identical to that of a handle freshly created from the scene in which that mesh has the new triangles.  Objects
+ * that share the mesh (one tree) all follow.  Workspace, learned ratios, device buffers and the communicator stay valid.
+ * All or nothing: the new scene is built in a second set of arrays that replaces the first only at the end; a refused or
+ * failed call leaves the handle rendering what it rendered before.  RPTGPU_E_INVALID_ARGUMENT, the detail naming the
+ * reason: a null or abandoned handle, an index out of range, an object that is not a mesh, n different from the count at
+ * creation, a NULL array with n > 0 — and, "needs a new handle": a mesh that is also a Light::Object's shape or a group's
+ * child, a handle whose trees are all single leaves (the flat path kernel's LDS layout and plane table are derived from
+ * the coordinates at creation), and a
+ * deformation that makes the tree of an object walked inside the path kernels deeper than their stacks (fast_max_depth).
+ * The call returns when the handle is ready to render.  Not concurrent with another call on the same handle. */
+int rptgpu_scene_set_mesh(rptgpu_scene* h, uint32_t object, uint64_t n, const RptTriangle* tris);
+/* The same with the triangles on the handle's device ([n][18] f64: v1 v2 v3 n1 n2 n3, as RptTriangle); no triangle goes
+ * through the host.  stream: the producer's, waited for before d_tris is read (as rptgpu_trace_rays_device; NULL: none).
+ * d_tris is only read. */
+int rptgpu_scene_set_mesh_device(rptgpu_scene* h, uint32_t object, uint64_t n, const void* d_tris, void* stream);
+
 /* ---- the hot path: replaces the body of Renderer::sample (renderer.rs:117-129).
  * Writes out_rgb[(y*width+x)*3+c] = mean over `iterations` paths of pixel (x,y), times
  * 2^exposure_value (renderer.rs:141); y = 0 is the top row (renderer.rs:134).  The host then

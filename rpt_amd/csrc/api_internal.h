@@ -13,6 +13,8 @@
 //   api_buffer.cpp   the device-resident Buffer
 //   api_rays.cpp     rptgpu_trace_rays[_device]: the wavefront pipeline over rays the caller supplies, in pieces
 //   api_probes.cpp   rptgpu_bake_probes[_device]: light probes (SH9 radiance, irradiance) through the same driver, in pieces
+//   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
+//                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, pass loop, copy_aov_out); its device
 //                    half also fills the features a Buffer holds for rptgpu_buffer_denoise
 // No compute happens on the host; if there is no HIP device every compute entry point returns RPTGPU_E_NO_DEVICE (there is
@@ -147,6 +149,8 @@ struct rptgpu_scene {
   DevBuf<uint32_t> draw, counters, pixels;
   uint64_t ws_cap = 0;
   uint64_t ws_rec_cols = 0;            // columns of the depth-record pool (PathState::rec)
+  bool ws_stale = false;               // rptgpu_scene_set_mesh made a tree deeper than the traversal columns were sized for:
+                                       // the next ensure_workspace makes them again (api_mesh.cpp)
   DevBuf<uint32_t> rec_parent, last_col;
   DevBuf<double> ray_next;             // dense path state of the NEXT depth (PathState: rpt_shade writes, the host swaps)
   DevBuf<uint32_t> draw_next, pid, pid_next, col, col_next;
@@ -194,6 +198,25 @@ struct rptgpu_scene {
   std::vector<rptdev::Inst> top_insts;    // insts[0, num_objects + Light::Object shapes) as on the device
   std::vector<rptdev::Material> host_materials;
   std::vector<rpthost::ObjectGeom> obj_geom;
+  // what rptgpu_scene_set_mesh rebuilds a tree from (api_mesh.cpp): host copies of the tree records and depths, which
+  // trees a Light::Object's shape or a group's child uses (those are not updated), the arrays' element counts (a DevBuf's n
+  // is its capacity), and the SECOND set of the geometry arrays: an update builds the whole new scene there — the other
+  // trees' records copied device to device, packed as a fresh handle packs them — and the two sets swap at the end
+  std::vector<rptdev::Tree> host_trees;
+  std::vector<uint32_t> tree_depth;
+  std::vector<uint8_t> tree_shared;
+  uint64_t n_insts = 0, n_nodes = 0, n_refs = 0, n_tris = 0;
+  DevBuf<rptdev::Inst> alt_insts;
+  DevBuf<rptdev::Tree> alt_trees;
+  DevBuf<rptdev::KdNode> alt_nodes;
+  DevBuf<uint32_t> alt_refs;
+  DevBuf<rptdev::Tri> alt_tris;
+  DevBuf<rptdev::TriX> alt_trix;
+  DevBuf<rptdev::LeafBox> alt_lbox;
+  DevBuf<double> mesh_src;           // the host entry point's triangles, uploaded
+  DevBuf<rptdev::TriX> mesh_trix;    // the updated mesh's records by triangle index
+  DevBuf<rpthost::Box> mesh_boxes;   // ... and its triangles' boxes
+  DevBuf<uint32_t> mesh_flag;        // [0] some triangle is a sliver
   std::vector<uint32_t> cnt_host;  // the per-depth counters read back from the device
   bool has_deep = false;
   int rays_in_kernel = 0;          // RPTGPU_RAYS_IN_KERNEL: rptgpu_closest_hit keeps to rpt_extend_rays also when the scene has deep trees

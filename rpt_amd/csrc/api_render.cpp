@@ -140,7 +140,7 @@ uint32_t zeros_common(const std::vector<rptdev::Light>& lights) {
 
 // cap: path slots; rec_cols: columns of the depth-record pool (PathState::rec: one per path and depth REACHED)
 void ensure_workspace(rptgpu_scene* h, uint64_t cap, uint64_t rec_cols) {
-  if (cap <= h->ws_cap && rec_cols <= h->ws_rec_cols && h->ray.p) return;
+  if (cap <= h->ws_cap && rec_cols <= h->ws_rec_cols && h->ray.p && !h->ws_stale) return;
   cap = std::max(cap, h->ws_cap);
   rec_cols = std::max(rec_cols, h->ws_rec_cols);
   int nl = std::max(1, h->dscene.num_lights);
@@ -185,6 +185,7 @@ void ensure_workspace(rptgpu_scene* h, uint64_t cap, uint64_t rec_cols) {
   }
   h->ws_cap = cap;
   h->ws_rec_cols = rec_cols;
+  h->ws_stale = false;
 }
 
 // -DRPT_PROF builds (kernels/prof.inc): per phase, the share of the waves' time, the lanes that were active while it

@@ -438,6 +438,13 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
     h->top_insts.assign(fs.insts.begin(), fs.insts.begin() + fs.num_top_insts);
     h->host_materials = fs.materials;
     h->obj_geom = std::move(fs.obj_geom);
+    // (rptgpu_scene_set_mesh, api_mesh.cpp)
+    h->host_trees = fs.trees;
+    h->tree_depth = fs.tree_depth;
+    h->tree_shared.assign(fs.trees.size(), 0);
+    for (size_t i = (size_t)fs.num_objects; i < fs.insts.size(); i++)
+      if (fs.insts[i].kind == RPT_SHAPE_MESH || fs.insts[i].kind == RPT_SHAPE_GROUP) h->tree_shared[fs.insts[i].tree] = 1;
+    h->n_insts = fs.insts.size(); h->n_nodes = fs.nodes.size(); h->n_refs = fs.refs.size(); h->n_tris = fs.tris.size();
     h->insts.upload(fs.insts, h->stream);
     h->trees.upload(fs.trees, h->stream);
     h->nodes.upload(fs.nodes, h->stream);

@@ -8,6 +8,7 @@
 // Compiled with -ffp-contract=off so the split planes are the same doubles the reference
 // computes (medians are sums of two doubles halved).
 #include "host_scene.h"
+#include "mesh_records.h"
 
 #include <algorithm>
 #include <cmath>
@@ -329,12 +330,9 @@ void xf_point(const double* m, const double* v, double* r) {
   for (int k = 0; k < 3; k++) r[k] = ((m[k] * v[0] + m[4 + k] * v[1]) + m[8 + k] * v[2]) + m[12 + k] * 1.0;
 }
 
-Box merge(const Box& a, const Box& b) { // BoundingBox::merge kdtree.rs:46-51
+Box merge(const Box& a, const Box& b) { // BoundingBox::merge kdtree.rs:46-51 (mesh_records.h)
   Box r;
-  for (int k = 0; k < 3; k++) {
-    r.lo[k] = std::fmin(a.lo[k], b.lo[k]);
-    r.hi[k] = std::fmax(a.hi[k], b.hi[k]);
-  }
+  rptrec::merge_box(a.lo, a.hi, b.lo, b.hi, r.lo, r.hi);
   return r;
 }
 
@@ -359,60 +357,14 @@ Box transformed_box(const Box& b, const double* m) { // shape.rs:153-176
   return r;
 }
 
-// mesh.rs:50-51 and :64-69, same expression order as the reference (nalgebra dot = (a+b)+c,
-// normalize = component / norm); this file is compiled with -ffp-contract=off
-void fill_trix(const RptTriangle& t, rptdev::TriX& x) {
-  double d0[3], d1[3], c[3];
-  for (int k = 0; k < 3; k++) { d0[k] = t.v2[k] - t.v1[k]; d1[k] = t.v3[k] - t.v1[k]; }
-  c[0] = d0[1] * d1[2] - d0[2] * d1[1];
-  c[1] = d0[2] * d1[0] - d0[0] * d1[2];
-  c[2] = d0[0] * d1[1] - d0[1] * d1[0];
-  double len = std::sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
-  for (int k = 0; k < 3; k++) { x.pn[k] = c[k] / len; x.v1[k] = t.v1[k]; x.d0[k] = d0[k]; x.d1[k] = d1[k]; }
-  x.d00 = (d0[0] * d0[0] + d0[1] * d0[1]) + d0[2] * d0[2];
-  x.d01 = (d0[0] * d1[0] + d0[1] * d1[1]) + d0[2] * d1[2];
-  x.d11 = (d1[0] * d1[0] + d1[1] * d1[1]) + d1[2] * d1[2];
-  x.denom = x.d00 * x.d11 - x.d01 * x.d01;
-}
-
-// Conservative 16-bit boxes of a mesh's leaf entries (device_types.h LeafBox).  Grid: 65529 steps across the
-// tree's bounds per axis plus two steps of padding on either side; a minimum is rounded down and a maximum up, then
-// both move one more step outwards, so the decoded box contains the triangle's true box with a margin of at least
-// (1 - 1e-12) steps on every side —
-// orders of magnitude more than the rounding of the decode and of the slab arithmetic on the device.  A triangle
-// whose barycentric system is ill-conditioned (sliver: rounding in mesh.rs:64-73 could accept a point that is not
-// near the triangle) or that has a non-finite vertex gets the whole grid, i.e. it is never filtered.  GROUP trees get
-// the boxes of their children the same way (a child's hit point lies on the child, hence in its bounding box).
+// The triangles' records — Tri, TriX (mesh.rs:50-51, :64-69), the triangle's box (mesh.rs:40-45), the conservative leaf
+// boxes and their grid, the sliver rule — are mesh_records.h's: the live mesh update (mesh_update.hip) makes them on the
+// device from the same expressions
+using rptrec::grid_over;
+using rptrec::sliver;
+void fill_trix(const RptTriangle& t, rptdev::TriX& x) { rptrec::fill_trix(t.v1, x); }
 rptdev::LeafBox quantise_box(const Box& b, const double* qlo, const double* qscale, bool full) {
-  uint32_t q[6];
-  for (int k = 0; k < 3 && !full; k++) {
-    double a = std::floor((b.lo[k] - qlo[k]) / qscale[k]) - 1.0;
-    double c = std::ceil((b.hi[k] - qlo[k]) / qscale[k]) + 1.0;
-    if (!(a == a) || !(c == c)) { full = true; break; }
-    q[k] = (uint32_t)std::fmin(std::fmax(a, 0.0), 65535.0);
-    q[3 + k] = (uint32_t)std::fmin(std::fmax(c, 0.0), 65535.0);
-  }
-  if (full) { q[0] = q[1] = q[2] = 0; q[3] = q[4] = q[5] = 65535; }
-  // stored per axis as centre and half-extent (device_types.h): c = floor of the middle, h = hi - c >= c - lo, so
-  // [c - h, c + h] contains [lo, hi] and is at most one step wider on the low side (c - h may be -1: the decode is
-  // arithmetic, nothing clamps it)
-  rptdev::LeafBox lb;
-  for (int k = 0; k < 3; k++) {
-    const uint32_t c = (q[k] + q[3 + k]) >> 1, h = q[3 + k] - c;
-    lb.w[k] = c | (h << 16);
-  }
-  lb.w[3] = full ? 1u : 0u;
-  return lb;
-}
-void grid_over(const double* bounds, double* qlo, double* qscale) {
-  for (int k = 0; k < 3; k++) {
-    double ext = bounds[3 + k] - bounds[k];
-    qscale[k] = (ext > 0.0 && std::isfinite(ext)) ? ext / 65529.0 : 1.0;
-    qlo[k] = bounds[k] - 2.0 * qscale[k];
-  }
-}
-bool sliver(const rptdev::TriX& x) { // ill-conditioned barycentric system, degenerate or NaN: never filtered
-  return !(x.denom > 1e-10 * (x.d00 * x.d11)) || !std::isfinite(x.denom);
+  return rptrec::quantise_box(b.lo, b.hi, qlo, qscale, full);
 }
 
 // Spheres (and monomial surfaces) are tested by solving a polynomial whose coefficients grow with the square of the
@@ -436,9 +388,6 @@ bool quadric_too_small(const rptdev::Inst& in, const double* qscale) {
 void fill_leaf_boxes(FlatScene& fs, int tree, int64_t tri_base /* < 0: a GROUP tree, entries are placed shapes */,
                      const std::vector<Box>& boxes, const std::vector<rptdev::Inst>* kids = nullptr) {
   rptdev::Tree& t = fs.trees[tree];
-  // the grid is two steps larger than the bounds on every side: a coordinate of a primitive maps to [2, 65531], so the
-  // outward rounding below (floor - 1, ceil + 1) never reaches the clamp, i.e. a box on a face of the tree's bounds
-  // keeps its margin too (tests/test_leaf_boxes.py found the case: a vertex on the bounds, a hit exactly there)
   grid_over(t.bounds, t.qlo, t.qscale);
   size_t nrefs = fs.refs.size() - t.ref_base;
   fs.lbox.resize(fs.refs.size());
@@ -462,13 +411,7 @@ struct Flattener {
 
   int add_tree(const std::vector<Box>& boxes, uint32_t prim_base) {
     KdBuild kb;
-    bool on_device = false;
-    if (build && build->device >= 0 && build->device_build_min && boxes.size() >= build->device_build_min) {
-      std::string why; // (a refusal is not an error: the host builder makes the same tree)
-      on_device = kd_build_device(boxes, kb, build->device, why);
-    }
-    if (on_device) fs.trees_built_on_device++;
-    else kd_build(boxes, kb);
+    if (build_kd(boxes, build, kb)) fs.trees_built_on_device++;
     // (a tree deeper than KD_MAX_STACK is no error: the object it belongs to is walked by rpt_tree_generic, api_scene.cpp)
     fs.max_tree_depth = std::max(fs.max_tree_depth, kb.max_depth);
     rptdev::Tree t;
@@ -476,25 +419,7 @@ struct Flattener {
     t.node_base = (uint32_t)fs.nodes.size();
     t.ref_base = (uint32_t)fs.refs.size();
     t.prim_base = prim_base;
-    t.num_prims = (uint32_t)boxes.size();
-    if (t.num_prims) { // uniform.rs (rand 0.8.3) UniformInt::<usize>::sample: ints_to_reject = (MAX - range + 1) % range
-      uint64_t n = t.num_prims;
-      t.sample_zone = 0xFFFFFFFFFFFFFFFFull - (0xFFFFFFFFFFFFFFFFull - n + 1) % n;
-    }
-    t.regular = kb.regular ? 1u : 0u;
-    t.split_range_ok = t.regular;
-    for (const rptdev::KdNode& nd : kb.nodes) {
-      if ((nd.ib & 3u) == 3u) continue;
-      const double a = std::fabs(nd.split);
-      if (!(a == 0.0 || (a >= 0x1p-340 && a < 0x1p399))) t.split_range_ok = 0u;
-    }
-    if (!kb.nodes.empty() && (kb.nodes[0].ib & 3u) == 3u) {
-      t.root_leaf = 1u + (kb.nodes[0].ib >> 2);
-      t.root_first = kb.nodes[0].a;
-    }
-    Box bounds = empty_box(); // KdTree::new bounds fold kdtree.rs:110-113
-    for (const Box& b : boxes) bounds = merge(bounds, b);
-    for (int k = 0; k < 3; k++) { t.bounds[k] = bounds.lo[k]; t.bounds[3 + k] = bounds.hi[k]; }
+    derive_tree(kb, boxes, t);
     // child / ref indices stay tree-relative; kernels add node_base / ref_base
     fs.nodes.insert(fs.nodes.end(), kb.nodes.begin(), kb.nodes.end());
     fs.refs.insert(fs.refs.end(), kb.refs.begin(), kb.refs.end());
@@ -554,10 +479,7 @@ struct Flattener {
               const RptTriangle& t = s.triangles[i];
               std::memcpy(fs.tris[base + i].v, &t, sizeof(double) * 18);
               fill_trix(t, fs.trix[base + i]);
-              for (int k = 0; k < 3; k++) { // glm::min3 / max3, mesh.rs:40-45
-                boxes[i].lo[k] = std::fmin(std::fmin(t.v1[k], t.v2[k]), t.v3[k]);
-                boxes[i].hi[k] = std::fmax(std::fmax(t.v1[k], t.v2[k]), t.v3[k]);
-              }
+              rptrec::tri_box(t.v1, boxes[i].lo, boxes[i].hi); // glm::min3 / max3, mesh.rs:40-45
             }
           });
           int tr = add_tree(boxes, base);
@@ -637,6 +559,46 @@ struct Flattener {
 };
 
 } // namespace
+
+bool build_kd(const std::vector<Box>& boxes, const BuildOptions* build, KdBuild& kb) {
+  struct ThreadsScope { // (restored on every way out)
+    int saved;
+    explicit ThreadsScope(int v) : saved(t_build_threads) { t_build_threads = v; }
+    ~ThreadsScope() { t_build_threads = saved; }
+  } threads_scope(build ? build->build_threads : 0);
+  bool on_device = false;
+  if (build && build->device >= 0 && build->device_build_min && boxes.size() >= build->device_build_min) {
+    std::string why; // (a refusal is not an error: the host builder makes the same tree)
+    on_device = kd_build_device(boxes, kb, build->device, why);
+  }
+  if (!on_device) kd_build(boxes, kb);
+  return on_device;
+}
+
+void derive_tree(const KdBuild& kb, const std::vector<Box>& boxes, rptdev::Tree& t) {
+  t.num_prims = (uint32_t)boxes.size();
+  t.sample_zone = 0;
+  if (t.num_prims) { // uniform.rs (rand 0.8.3) UniformInt::<usize>::sample: ints_to_reject = (MAX - range + 1) % range
+    uint64_t n = t.num_prims;
+    t.sample_zone = 0xFFFFFFFFFFFFFFFFull - (0xFFFFFFFFFFFFFFFFull - n + 1) % n;
+  }
+  t.regular = kb.regular ? 1u : 0u;
+  t.split_range_ok = t.regular;
+  for (const rptdev::KdNode& nd : kb.nodes) {
+    if ((nd.ib & 3u) == 3u) continue;
+    const double a = std::fabs(nd.split);
+    if (!(a == 0.0 || (a >= 0x1p-340 && a < 0x1p399))) t.split_range_ok = 0u;
+  }
+  t.root_leaf = 0u;
+  t.root_first = 0u;
+  if (!kb.nodes.empty() && (kb.nodes[0].ib & 3u) == 3u) {
+    t.root_leaf = 1u + (kb.nodes[0].ib >> 2);
+    t.root_first = kb.nodes[0].a;
+  }
+  Box bounds = empty_box(); // KdTree::new bounds fold kdtree.rs:110-113
+  for (const Box& b : boxes) bounds = merge(bounds, b);
+  for (int k = 0; k < 3; k++) { t.bounds[k] = bounds.lo[k]; t.bounds[3 + k] = bounds.hi[k]; }
+}
 
 void set_transform(rptdev::Inst& in, const RptShape& s) {
   in.has_xf = s.transformed ? 1 : 0;

@@ -37,6 +37,14 @@ struct BuildOptions {
   int build_threads = 0; // RptSceneOptions::build_threads: 0 = the usable cores
 };
 
+// The tree over `boxes` as scene creation builds it: on the device when `build` names one and there are at least
+// device_build_min boxes and the device builder takes them, else on the host (the same tree); -> built on the device
+bool build_kd(const std::vector<Box>& boxes, const BuildOptions* build, KdBuild& kb);
+// What creation derives from a built tree and its primitives' boxes, into `t`: num_prims, sample_zone, regular,
+// split_range_ok, root_leaf / root_first and the bounds (BoundingBox::merge folded in index order, kdtree.rs:110-113).
+// One source for rptgpu_scene_create and rptgpu_scene_set_mesh; node_base, ref_base, prim_base and the leaf grid are the caller's.
+void derive_tree(const KdBuild& kb, const std::vector<Box>& boxes, rptdev::Tree& t);
+
 // ---- what the flattening derives from the objects' placements and materials.  One source for rptgpu_scene_create and
 // the live updates of a handle (rptgpu_scene_set_objects / _lights, api_scene.cpp), so an updated handle holds the bits a
 // fresh one of the updated scene would.

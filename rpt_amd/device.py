@@ -99,6 +99,49 @@ class GpuScene:
         self.set_lights(range(len(scene.lights)), scene.lights)
         self._geometry = geometry_snapshot(scene)  # (the same geometry: the newer objects make the identity checks hit)
 
+    # ---- a deforming mesh (rptgpu_scene_set_mesh[_device]): new triangles for one mesh, the count unchanged.  The mesh's
+    # records and tree are rebuilt on the device; afterwards every result equals that of a GpuScene made from the scene in
+    # which that mesh has the new triangles.  update()'s geometry snapshot is the creation's: update() keeps comparing
+    # placements against the scene the handle was made from.
+    def set_mesh(self, index, triangles):
+        """Object `index` (a top-level Mesh) gets `triangles`: (n, 18) float64 — v1 v2 v3 n1 n2 n3 per row, n the mesh's
+        count at creation — as a numpy array, or as a contiguous torch tensor on the handle's device, which is read there
+        after torch's current stream (no triangle goes through the host).  Other shapes and dtypes raise here."""
+        index = int(index)
+        if index < 0:
+            raise ValueError("set_mesh: object index %d is negative" % index)
+        if isinstance(triangles, np.ndarray) or not hasattr(triangles, "data_ptr"):
+            arr = np.asarray(triangles)
+            if arr.dtype != np.float64:
+                raise TypeError("set_mesh: triangles must be float64, not %s" % arr.dtype)
+            if arr.ndim != 2 or arr.shape[1] != 18:
+                raise ValueError("set_mesh: triangles must have shape (n, 18), not %s" % (tuple(arr.shape),))
+            arr = np.ascontiguousarray(arr)
+            code = self.lib.rptgpu_scene_set_mesh(self.handle, index, arr.shape[0],
+                                                  arr.ctypes.data_as(C.POINTER(_abi.RptTriangle)))
+            _abi.check(code, self.handle)
+            return
+        import torch
+        t = triangles
+        if t.dtype != torch.float64:
+            raise TypeError("set_mesh: triangles must be float64, not %s" % t.dtype)
+        if t.dim() != 2 or t.shape[1] != 18:
+            raise ValueError("set_mesh: triangles must have shape (n, 18), not %s" % (tuple(t.shape),))
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError("set_mesh: the tensor is on %s, the handle on device %d (pass a numpy array for host data)"
+                             % (t.device, self.device))
+        if not t.is_contiguous():
+            raise ValueError("set_mesh: the tensor must be contiguous")
+        # the tensor's producer ran on torch's current stream, which nothing orders with the handle's: a stream with a
+        # handle goes to the library, which waits for it; the null stream (handle 0, the ABI's "no stream") is waited for here
+        current = torch.cuda.current_stream(t.device)
+        stream = current.cuda_stream
+        if not stream:
+            current.synchronize()
+        code = self.lib.rptgpu_scene_set_mesh_device(self.handle, index, int(t.shape[0]), C.c_void_p(t.data_ptr()),
+                                                     C.c_void_p(stream or 0))
+        _abi.check(code, self.handle)
+
     def options(self):
         """The options the handle runs with (defaults, the caller's, environment overrides) as a dict."""
         o = _abi.RptSceneOptions()
