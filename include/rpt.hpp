@@ -803,6 +803,18 @@ class Renderer {
     if (!handle_) return;
     check(rptgpu_scene_set_mesh(handle_, object, triangles.size(), triangles.data()));
   }
+  // addition: a group whose children move.  Object `object` of the Scene, a KdTree of spheres and cubes, gets `children`
+  // (as many as it has, child i of the kind it had, Transformed if it was: only the placements are read) in the scene
+  // handle this Renderer holds (rptgpu_scene_set_group): the children's records and the group's kd-tree are rebuilt on the
+  // device, everything else of the handle stays, and the next render equals that of a new Renderer of a Scene whose
+  // group has these children.  Before the first render there is no handle yet and nothing to push.
+  void update_group(uint32_t object, const std::vector<Shape>& children) {
+    if (!handle_) return;
+    Arena arena;
+    std::vector<RptShape> lowered;
+    for (const Shape& c : children) lowered.push_back(c.lower(arena));
+    check(rptgpu_scene_set_group(handle_, object, lowered.size(), lowered.data()));
+  }
 
  private:
   void check(int code) {

@@ -364,6 +364,32 @@ int rptgpu_scene_set_mesh(rptgpu_scene* h, uint32_t object, uint64_t n, const Rp
  * d_tris is only read. */
 int rptgpu_scene_set_mesh_device(rptgpu_scene* h, uint32_t object, uint64_t n, const void* d_tris, void* stream);
 
+/* ---- a group whose children move on a live handle (instanced bodies: the spheres of a particle system, a swarm): new
+ * placements for the children of one KdTree<Box<dyn Bounded>>.  Additions within ABI version 7, detected by symbol (dlsym
+ * "rptgpu_scene_set_group").  `object` is a top-level object whose shape is a GROUP; n must equal its child count at
+ * creation.  Child i keeps its kind and its `transformed` flag; only the five RptTransform fields change, and they are
+ * taken as given, exactly as creation takes them.  The record of a child that is not transformed is ignored; of each
+ * child the call reads kind, transformed and xf and nothing else.  The children's records and boxes are made on the device, the group's
+ * kd-tree is rebuilt by the builder creation would use, and everything creation derives from the tree follows, so that
+ * afterwards every result — frames under every flag, rptgpu_closest_hit, rptgpu_render_aov, rptgpu_trace_rays,
+ * rptgpu_bake_probes, rptgpu_buffer_* — is bit-identical to that of a handle freshly created from the scene in which the
+ * group has the new children.  Workspace, learned ratios, device buffers and the communicator stay valid.
+ * All or nothing, as rptgpu_scene_set_mesh: a refused or failed call leaves the handle rendering what it rendered
+ * before.  RPTGPU_E_INVALID_ARGUMENT, the detail naming the reason: a null or abandoned handle, an index out of range,
+ * an object that is not a group, n different from the count at creation, a NULL array with n > 0, a child whose kind or
+ * `transformed` flag differs from the creation's — and, "needs a new handle": a group with a MESH, MONOMIAL or GROUP
+ * child (accepted: children that are all SPHERE or CUBE), a handle whose trees are all single leaves (the flat path
+ * kernel), a rebuilt tree deeper than fast_max_depth for a group that is walked inside the path kernels, 32-bit node or
+ * entry index overflow.  n == 0 returns RPTGPU_OK.  The call returns when the handle is ready to render.  Not concurrent
+ * with another call on the same handle. */
+int rptgpu_scene_set_group(rptgpu_scene* h, uint32_t object, uint64_t n, const RptShape* children);
+/* The same with the placements on the handle's device: [n] RptTransform, 51 f64 each (transform[16], linear[9],
+ * inverse_transform[16], normal_transform[9], scale); the kinds and `transformed` flags are the creation's.  stream: the
+ * producer's, waited for before d_transforms is read (as rptgpu_scene_set_mesh_device; NULL: none).  d_transforms is only
+ * read. */
+int rptgpu_scene_set_group_device(rptgpu_scene* h, uint32_t object, uint64_t n,
+                                  const void* d_transforms /* [n] RptTransform, 51 f64 each */, void* stream);
+
 /* ---- the hot path: replaces the body of Renderer::sample (renderer.rs:117-129).
  * Writes out_rgb[(y*width+x)*3+c] = mean over `iterations` paths of pixel (x,y), times
  * 2^exposure_value (renderer.rs:141); y = 0 is the top row (renderer.rs:134).  The host then

@@ -29,4 +29,4 @@ from .renderer import Renderer  # noqa: F401
 from .scene import Scene  # noqa: F401
 from . import scenes  # noqa: F401
 from .shape import (Cube, KdTree, Mesh, MonomialSurface, Plane, Shape, Sphere, Transformed, Triangle,  # noqa: F401
-                    cube, monomial_surface, plane, polygon, sphere)
+                    cube, monomial_surface, plane, polygon, sphere, transform_records)

@@ -195,6 +195,8 @@ SYMBOLS = [
     ("rptgpu_scene_set_lights", C.c_int, [_VP, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(RptLight)]),
     ("rptgpu_scene_set_mesh", C.c_int, [_VP, C.c_uint32, C.c_uint64, C.POINTER(RptTriangle)]),
     ("rptgpu_scene_set_mesh_device", C.c_int, [_VP, C.c_uint32, C.c_uint64, _VP, _VP]),
+    ("rptgpu_scene_set_group", C.c_int, [_VP, C.c_uint32, C.c_uint64, C.POINTER(RptShape)]),
+    ("rptgpu_scene_set_group_device", C.c_int, [_VP, C.c_uint32, C.c_uint64, _VP, _VP]),
     ("rptgpu_render_batch", C.c_int, [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams), _PD]),
     ("rptgpu_render_batch_device", C.c_int,
      [_VP, C.POINTER(RptCamera), C.POINTER(RptRenderParams), _VP, C.c_int, _VP]),

@@ -15,6 +15,8 @@
 //   api_probes.cpp   rptgpu_bake_probes[_device]: light probes (SH9 radiance, irradiance) through the same driver, in pieces
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
+//   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
+//                    way (the kernels: group_update.hip); tree_splice.h holds the spare-set storage both files use
 //   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, pass loop, copy_aov_out); its device
 //                    half also fills the features a Buffer holds for rptgpu_buffer_denoise
 // No compute happens on the host; if there is no HIP device every compute entry point returns RPTGPU_E_NO_DEVICE (there is
@@ -205,6 +207,8 @@ struct rptgpu_scene {
   std::vector<rptdev::Tree> host_trees;
   std::vector<uint32_t> tree_depth;
   std::vector<uint8_t> tree_shared;
+  std::vector<uint8_t> inst_sig;     // per record of insts[]: kind | has_xf << 7 — what rptgpu_scene_set_group holds a group's
+                                     // children to (api_group.cpp; the children's records themselves live on the device only)
   uint64_t n_insts = 0, n_nodes = 0, n_refs = 0, n_tris = 0;
   DevBuf<rptdev::Inst> alt_insts;
   DevBuf<rptdev::Tree> alt_trees;
@@ -213,9 +217,9 @@ struct rptgpu_scene {
   DevBuf<rptdev::Tri> alt_tris;
   DevBuf<rptdev::TriX> alt_trix;
   DevBuf<rptdev::LeafBox> alt_lbox;
-  DevBuf<double> mesh_src;           // the host entry point's triangles, uploaded
+  DevBuf<double> mesh_src;           // the host entry point's triangles, uploaded (rptgpu_scene_set_group: its RptTransform records)
   DevBuf<rptdev::TriX> mesh_trix;    // the updated mesh's records by triangle index
-  DevBuf<rpthost::Box> mesh_boxes;   // ... and its triangles' boxes
+  DevBuf<rpthost::Box> mesh_boxes;   // ... and its triangles' boxes (rptgpu_scene_set_group: the children's)
   DevBuf<uint32_t> mesh_flag;        // [0] some triangle is a sliver
   std::vector<uint32_t> cnt_host;  // the per-depth counters read back from the device
   bool has_deep = false;

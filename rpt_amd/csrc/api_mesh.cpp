@@ -4,29 +4,14 @@
 // the tree by the same functions (derive_tree, mesh_records.h grid_over, fill_object_boxes).  DESIGN.md §9 has the
 // contract, the storage scheme and the audit of what follows from a tree.
 //
-// Storage.  insts, trees, nodes, refs, tris, lrec and lbox exist twice on a handle that has been updated: the set the
-// kernels read and a spare.  An update writes the WHOLE new scene into the spare — the other trees' nodes, entries and
-// records copied device to device, packed in tree order exactly as a fresh handle packs them, the updated tree's region
-// in between at its new size — waits for the stream, and only then swaps the two sets and the host copies.  Nothing the
-// kernels read is written before the swap, so a refusal or a failure leaves the handle as it was; the spare keeps its
-// allocation (grown by an eighth beyond need when it must grow) for the next update.
+// Storage: the spare set of the geometry arrays, written whole and swapped in at the end (tree_splice.h, shared with
+// api_group.cpp).
 #include "api_internal.h"
 #include "mesh_records.h"
 #include "mesh_update.h"
+#include "tree_splice.h"
 
 namespace {
-
-// dst[0, at) = src[0, at); dst[at + new_len, ...) = src[at + old_len, total): the arrays of the other trees around the
-// updated tree's region, device to device
-template <class T> void copy_around(T* dst, const T* src, uint64_t at, uint64_t old_len, uint64_t new_len, uint64_t total, hipStream_t st) {
-  if (at) HIP_TRY(hipMemcpyAsync(dst, src, at * sizeof(T), hipMemcpyDeviceToDevice, st));
-  const uint64_t tail = total - (at + old_len);
-  if (tail) HIP_TRY(hipMemcpyAsync(dst + at + new_len, src + at + old_len, tail * sizeof(T), hipMemcpyDeviceToDevice, st));
-}
-template <class T> void reserve(DevBuf<T>& b, uint64_t need) {
-  if (b.p && b.n >= need) return;
-  b.alloc(need + need / 8); // (slack: a deforming mesh's node and entry counts wander from frame to frame)
-}
 
 int set_mesh(rptgpu_scene* h, uint32_t object, uint64_t n, const void* tris, bool on_device, hipStream_t user_stream,
              const std::string& fn) {
@@ -110,32 +95,16 @@ int set_mesh(rptgpu_scene* h, uint32_t object, uint64_t n, const void* tris, boo
                                                      std::to_string(i) + " is walked inside the path kernels, whose stacks hold " +
                                                      std::to_string(h->opt.fast_max_depth) + ": this needs a new handle");
     // ---- the spare set, packed as a fresh handle packs it
-    const bool last = t + 1 >= h->host_trees.size();
-    const uint64_t old_nn = (last ? h->n_nodes : h->host_trees[t + 1].node_base) - old.node_base;
-    const uint64_t old_nr = (last ? h->n_refs : h->host_trees[t + 1].ref_base) - old.ref_base;
-    const uint64_t nn = kb.nodes.size(), nr = kb.refs.size();
-    const uint64_t nodes_total = h->n_nodes - old_nn + nn, refs_total = h->n_refs - old_nr + nr;
-    if (nodes_total >= 0xffffffffull || refs_total + RPT_LBOX_PAD >= 0xffffffffull)
+    TreeSplice sp;
+    if (!plan_splice(h, t, kb, sp))
       return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + "the scene's trees would outgrow 32-bit node or entry indices");
-    reserve(h->alt_nodes, nodes_total); reserve(h->alt_refs, refs_total); reserve(h->alt_trix, refs_total);
-    reserve(h->alt_lbox, refs_total + RPT_LBOX_PAD);
-    copy_around(h->alt_nodes.p, h->nodes.p, old.node_base, old_nn, nn, h->n_nodes, st);
-    copy_around(h->alt_refs.p, h->refs.p, old.ref_base, old_nr, nr, h->n_refs, st);
-    copy_around(h->alt_trix.p, h->trix.p, old.ref_base, old_nr, nr, h->n_refs, st);
-    copy_around(h->alt_lbox.p, h->lbox.p, old.ref_base, old_nr, nr, h->n_refs + RPT_LBOX_PAD, st); // (with the padding behind the last entry)
-    HIP_TRY(hipMemcpyAsync(h->alt_nodes.p + old.node_base, kb.nodes.data(), nn * sizeof(rptdev::KdNode), hipMemcpyHostToDevice, st));
-    if (nr) HIP_TRY(hipMemcpyAsync(h->alt_refs.p + old.ref_base, kb.refs.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    pack_spare_tree(h, sp, kb, st);
     lap("copies, nodes and entries");
-    HIP_TRY(rptmesh::leaf_records(st, h->alt_refs.p + old.ref_base, (uint32_t)nr, nt, h->mesh_trix.p, h->mesh_boxes.p, grid,
+    HIP_TRY(rptmesh::leaf_records(st, h->alt_refs.p + old.ref_base, (uint32_t)sp.nr, nt, h->mesh_trix.p, h->mesh_boxes.p, grid,
                                   h->alt_trix.p + old.ref_base, h->alt_lbox.p + old.ref_base));
     lap("leaf records");
     // the tree records (the later trees' regions moved) and every instance of this tree (Inst::bounds copies Tree::bounds)
-    std::vector<rptdev::Tree> trees = h->host_trees;
-    trees[t] = tr;
-    for (size_t u = t + 1; u < trees.size(); u++) {
-      trees[u].node_base = (uint32_t)((uint64_t)trees[u].node_base - old_nn + nn);
-      trees[u].ref_base = (uint32_t)((uint64_t)trees[u].ref_base - old_nr + nr);
-    }
+    std::vector<rptdev::Tree> trees = spliced_trees(h, sp, tr);
     std::vector<rptdev::Inst> insts = h->top_insts;
     std::vector<rpthost::ObjectGeom> geom = h->obj_geom;
     for (size_t i = 0; i < count; i++) {
@@ -146,39 +115,15 @@ int set_mesh(rptgpu_scene* h, uint32_t object, uint64_t n, const void* tris, boo
     }
     rpthost::ObjectBounds ob;
     rpthost::fill_object_boxes(insts, geom, ob);
-    std::vector<uint8_t> obj_deep = h->obj_deep, obj_tris = h->obj_tris;
-    h->alt_trees.upload(trees, st);
-    h->alt_insts.alloc(h->n_insts);
-    HIP_TRY(hipMemcpyAsync(h->alt_insts.p, h->insts.p, h->n_insts * sizeof(rptdev::Inst), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->alt_insts.p, insts.data(), insts.size() * sizeof(rptdev::Inst), hipMemcpyHostToDevice, st));
+    pack_spare_insts(h, st);
+    pack_spare_records(h, trees, insts, st);
     HIP_TRY(hipStreamSynchronize(st));
     lap("tree and object records");
     // ---- the swap: from here on nothing fails
-    std::swap(h->insts, h->alt_insts); std::swap(h->trees, h->alt_trees); std::swap(h->nodes, h->alt_nodes);
-    std::swap(h->refs, h->alt_refs); std::swap(h->tris, h->alt_tris); std::swap(h->trix, h->alt_trix); std::swap(h->lbox, h->alt_lbox);
-    rptdev::Scene& d = h->dscene;
-    d.insts = h->insts.p; d.trees = h->trees.p; d.nodes = h->nodes.p; d.refs = h->refs.p; d.tris = h->tris.p; d.lrec = h->trix.p; d.lbox = h->lbox.p;
-    h->n_nodes = nodes_total; h->n_refs = refs_total;
-    h->host_trees.swap(trees);
-    h->tree_depth[t] = depth;
-    h->top_insts.swap(insts);
-    h->obj_geom.swap(geom);
-    if (ob.scene_bounds_ok) std::memcpy(h->scene_bounds, ob.scene_bounds, sizeof h->scene_bounds);
-    // what the routing and the workspace took from the tree at creation (api_scene.cpp); sizes only grow — a column
-    // higher than a fresh handle's holds the same traversal
-    for (size_t i = 0; i < count; i++) {
-      if (h->top_insts[i].kind != RPT_SHAPE_MESH || (size_t)h->top_insts[i].tree != t) continue;
-      if (obj_deep[i]) {
-        obj_deep[i] = (uint8_t)((obj_deep[i] & ~4) | (tr.regular ? 0 : 4)); // an irregular tree: every ray through rpt_tree_generic
-        if (!tr.regular && !h->gen_all) { h->gen_all = true; h->ws_stale = true; }
-        if (depth > h->opt.fast_max_depth) { h->tree_kids = true; h->prefer_wavefront = true; } // only the per-tree pipeline walks it
-      } else {
-        obj_tris[i] = (uint8_t)((obj_tris[i] & ~16) | (tr.root_leaf ? 16 : 0)); // the lean build of rpt_rays_objects takes single leaves only
-      }
-    }
-    h->obj_deep.swap(obj_deep); h->obj_tris.swap(obj_tris);
-    if (depth > h->max_tree_depth) { h->max_tree_depth = depth; h->ws_stale = true; }                  // the spill columns' height
-    if (depth + 1u > h->gen_levels) { h->gen_levels = depth + 1u; h->gen_threads = 0; h->ws_stale = true; } // rpt_tree_generic's
+    swap_spare(h, sp, trees, insts, geom, ob, depth, true);
+    // what the routing and the workspace took from the tree at creation (api_scene.cpp)
+    for (size_t i = 0; i < count; i++)
+      if (h->top_insts[i].kind == RPT_SHAPE_MESH && (size_t)h->top_insts[i].tree == t) reroute_object(h, i, tr, depth);
     return RPTGPU_OK;
   });
 }

@@ -444,6 +444,7 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
     h->tree_shared.assign(fs.trees.size(), 0);
     for (size_t i = (size_t)fs.num_objects; i < fs.insts.size(); i++)
       if (fs.insts[i].kind == RPT_SHAPE_MESH || fs.insts[i].kind == RPT_SHAPE_GROUP) h->tree_shared[fs.insts[i].tree] = 1;
+    for (const rptdev::Inst& in : fs.insts) h->inst_sig.push_back((uint8_t)((in.kind & 0x7f) | (in.has_xf ? 0x80 : 0))); // (rptgpu_scene_set_group, api_group.cpp)
     h->n_insts = fs.insts.size(); h->n_nodes = fs.nodes.size(); h->n_refs = fs.refs.size(); h->n_tris = fs.tris.size();
     h->insts.upload(fs.insts, h->stream);
     h->trees.upload(fs.trees, h->stream);
@@ -488,7 +489,7 @@ void rptgpu_scene_destroy(rptgpu_scene* h) { delete h; }
 //   * scene_bounds, the path re-order's key grid — recomputed (kept when the new union is not finite: scheduling only);
 //   * StackSpill::zeros_common (directional lights along an axis) — recomputed (scheduling only);
 //   * the plane table (untransformed meshes only: `transformed` may not change), trees, leaf boxes of group children
-//     (in their group's frame), light_casts and num_shadow_lights (by kind: kinds may not change) — unchanged by
+//     (in their group's frame: rptgpu_scene_set_group moves those, api_group.cpp), light_casts and num_shadow_lights (by kind: kinds may not change) — unchanged by
 //     construction.
 } // extern "C"
 

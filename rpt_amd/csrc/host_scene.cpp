@@ -9,6 +9,7 @@
 // computes (medians are sums of two doubles halved).
 #include "host_scene.h"
 #include "mesh_records.h"
+#include "shape_records.h"
 
 #include <algorithm>
 #include <cmath>
@@ -325,11 +326,6 @@ void kd_build(const std::vector<Box>& boxes, KdBuild& out, int threads) {
 // ------------------------------------------------------------------------- flattening
 namespace {
 
-// column-major 4x4 * (v,1), accumulated column by column (nalgebra gemv order)
-void xf_point(const double* m, const double* v, double* r) {
-  for (int k = 0; k < 3; k++) r[k] = ((m[k] * v[0] + m[4 + k] * v[1]) + m[8 + k] * v[2]) + m[12 + k] * 1.0;
-}
-
 Box merge(const Box& a, const Box& b) { // BoundingBox::merge kdtree.rs:46-51 (mesh_records.h)
   Box r;
   rptrec::merge_box(a.lo, a.hi, b.lo, b.hi, r.lo, r.hi);
@@ -342,18 +338,9 @@ Box empty_box() { // BoundingBox::default kdtree.rs:35-42
   return b;
 }
 
-Box transformed_box(const Box& b, const double* m) { // shape.rs:153-176
-  Box r = empty_box();
-  for (int ix = 0; ix < 2; ix++)
-    for (int iy = 0; iy < 2; iy++)
-      for (int iz = 0; iz < 2; iz++) {
-        double v[3] = {ix ? b.hi[0] : b.lo[0], iy ? b.hi[1] : b.lo[1], iz ? b.hi[2] : b.lo[2]};
-        double c[3];
-        xf_point(m, v, c);
-        Box p;
-        for (int k = 0; k < 3; k++) p.lo[k] = p.hi[k] = c[k];
-        r = merge(r, p);
-      }
+Box transformed_box(const Box& b, const double* m) { // shape.rs:153-176 (shape_records.h)
+  Box r;
+  rptrec::transformed_box(b.lo, b.hi, m, r.lo, r.hi);
   return r;
 }
 
@@ -367,23 +354,10 @@ rptdev::LeafBox quantise_box(const Box& b, const double* qlo, const double* qsca
   return rptrec::quantise_box(b.lo, b.hi, qlo, qscale, full);
 }
 
-// Spheres (and monomial surfaces) are tested by solving a polynomial whose coefficients grow with the square of the
-// origin's distance in OBJECT units: from far away Sphere::intersect accepts lines that miss the sphere (kernels/
-// shapes.inc boxray_make).  The device bounds the origin's distance to 1e7 grid steps when quadrics are filtered; a
-// sphere whose smallest semi-axis is below 64 steps (1e-3 of the grid) is not filtered at all, nor is a monomial surface.
-bool quadric_too_small(const rptdev::Inst& in, const double* qscale) {
-  if (in.kind == RPT_SHAPE_MONOMIAL) return true;
-  if (in.kind != RPT_SHAPE_SPHERE) return false;
-  double r_min = 1.0; // smallest singular value of the placement >= 1 / ||M^-1||_F
-  if (in.has_xf) {
-    double b = 0.0;
-    for (int c = 0; c < 3; c++)
-      for (int r = 0; r < 3; r++) b += in.inv[4 * c + r] * in.inv[4 * c + r];
-    r_min = 1.0 / std::sqrt(b);
-  }
-  const double step = std::fmax(std::fmax(qscale[0], qscale[1]), qscale[2]);
-  return !(r_min >= 64.0 * step);
-}
+// A placed sphere's or cube's records as a group's child — the kinds' local boxes, Transformed::bounding_box, which
+// quadrics the leaf filter leaves alone — are shape_records.h's: the live group update (group_update.hip) makes them on
+// the device from the same expressions
+using rptrec::quadric_too_small;
 
 void fill_leaf_boxes(FlatScene& fs, int tree, int64_t tri_base /* < 0: a GROUP tree, entries are placed shapes */,
                      const std::vector<Box>& boxes, const std::vector<rptdev::Inst>* kids = nullptr) {
@@ -441,10 +415,8 @@ struct Flattener {
     bool is_bounded = true;
     switch (s.kind) {
       case RPT_SHAPE_SPHERE:
-        for (int k = 0; k < 3; k++) { local.lo[k] = -1.0; local.hi[k] = 1.0; }
-        break;
       case RPT_SHAPE_CUBE:
-        for (int k = 0; k < 3; k++) { local.lo[k] = -0.5; local.hi[k] = 0.5; }
+        rptrec::local_box(s.kind, local.lo, local.hi);
         break;
       case RPT_SHAPE_PLANE:
         for (int k = 0; k < 3; k++) in.plane[k] = s.plane_normal[k];

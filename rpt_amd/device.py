@@ -7,6 +7,7 @@ import numpy as np
 
 from . import _abi
 from .scene import geometry_mismatch, geometry_snapshot
+from .shape import XF_WORDS, KdTree, Transformed, lower_shapes
 
 
 def make_params(width, height, max_bounces, iterations, exposure_value=0.0, seed=0x52505447,
@@ -141,6 +142,71 @@ class GpuScene:
         code = self.lib.rptgpu_scene_set_mesh_device(self.handle, index, int(t.shape[0]), C.c_void_p(t.data_ptr()),
                                                      C.c_void_p(stream or 0))
         _abi.check(code, self.handle)
+
+    # ---- a group whose children move (rptgpu_scene_set_group[_device]): new placements for the children of one
+    # KdTree of spheres and cubes, the count, the kinds and which children are Transformed unchanged.  The children's
+    # records and the group's tree are rebuilt on the device; afterwards every result equals that of a GpuScene made
+    # from the scene in which the group has the new children.  update()'s geometry snapshot stays the creation's.
+    def set_group(self, index, children):
+        """Object `index` (a top-level KdTree of shapes) gets new placements for its children: a sequence of Python
+        shapes (child i of the kind it had at creation, Transformed if it was), or their RptTransform records as an
+        (n, 51) float64 array (rpt_amd.transform_records) — numpy, or a contiguous torch tensor on the handle's device,
+        which is read there after torch's current stream.  Other shapes, dtypes and devices raise here."""
+        index = int(index)
+        if index < 0:
+            raise ValueError("set_group: object index %d is negative" % index)
+        if hasattr(children, "data_ptr"):
+            import torch
+            t = children
+            if t.dtype != torch.float64:
+                raise TypeError("set_group: transform records must be float64, not %s" % t.dtype)
+            if t.dim() != 2 or t.shape[1] != XF_WORDS:
+                raise ValueError("set_group: transform records must have shape (n, %d), not %s" % (XF_WORDS, tuple(t.shape)))
+            if not t.is_cuda or t.device.index != self.device:
+                raise ValueError("set_group: the tensor is on %s, the handle on device %d (pass a numpy array for host data)"
+                                 % (t.device, self.device))
+            if not t.is_contiguous():
+                raise ValueError("set_group: the tensor must be contiguous")
+            current = torch.cuda.current_stream(t.device)  # (as set_mesh: the library waits for a stream with a handle)
+            stream = current.cuda_stream
+            if not stream:
+                current.synchronize()
+            code = self.lib.rptgpu_scene_set_group_device(self.handle, index, int(t.shape[0]), C.c_void_p(t.data_ptr()),
+                                                          C.c_void_p(stream or 0))
+            _abi.check(code, self.handle)
+            return
+        if isinstance(children, np.ndarray):
+            rows = children
+            if rows.dtype != np.float64:
+                raise TypeError("set_group: transform records must be float64, not %s" % rows.dtype)
+            if rows.ndim != 2 or rows.shape[1] != XF_WORDS:
+                raise ValueError("set_group: transform records must have shape (n, %d), not %s" % (XF_WORDS, tuple(rows.shape)))
+            arr, n = self._creation_children(index)
+            if n != rows.shape[0]:
+                raise ValueError("set_group: %d transform records for the %d children of object %d" % (rows.shape[0], n, index))
+            if n:  # the records into the xf fields of the creation's children (kinds and `transformed` as they were)
+                raw = np.frombuffer(arr, dtype=np.uint8).reshape(-1, C.sizeof(_abi.RptShape))[:n]
+                at = _abi.RptShape.xf.offset
+                raw[:, at:at + 8 * XF_WORDS] = np.ascontiguousarray(rows).view(np.uint8).reshape(n, 8 * XF_WORDS)
+        else:
+            children = list(children)
+            keep = []
+            arr, n = lower_shapes(children, keep), len(children)
+        _abi.check(self.lib.rptgpu_scene_set_group(self.handle, index, n, arr), self.handle)
+
+    def _creation_children(self, index):
+        """the children of object `index` as lowered at creation (cached: set_group writes new records into it)"""
+        cache = self.__dict__.setdefault("_group_children", {})
+        if index not in cache:
+            objects = self._geometry.objects
+            shape = objects[index].shape if index < len(objects) else None
+            if isinstance(shape, Transformed):
+                shape = shape.shape
+            if not isinstance(shape, KdTree) or shape.objects is None:
+                raise ValueError("set_group: object %d is not a KdTree of shapes" % index)
+            keep = []
+            cache[index] = (lower_shapes(shape.objects, keep), len(shape.objects), keep)
+        return cache[index][:2]
 
     def options(self):
         """The options the handle runs with (defaults, the caller's, environment overrides) as a dict."""

@@ -222,6 +222,32 @@ class Transformed(Shape):
         s.xf.scale = self.scale_det
 
 
+XF_WORDS = 51  # RptTransform as float64 words: transform[16] linear[9] inverse_transform[16] normal_transform[9] scale
+
+
+def lower_shapes(shapes, keep):
+    """-> an RptShape array holding `shapes` as a KdTree lowers its children"""
+    shapes = list(shapes)
+    arr = (_abi.RptShape * max(1, len(shapes)))()
+    for i, o in enumerate(shapes):
+        o._fill(arr[i], keep)
+    return arr
+
+
+def transform_records(shapes):
+    """The five Transformed fields of each shape as the C ABI takes them: an (n, 51) float64 array of RptTransform
+    records (transform, linear, inverse_transform, normal_transform column-major, then scale) — the lowering exposed, for
+    GpuScene.set_group.  The row of a shape that is not Transformed is zeros (set_group ignores it)."""
+    shapes = list(shapes)
+    arr = lower_shapes(shapes, [])
+    assert C.sizeof(_abi.RptTransform) == 8 * XF_WORDS
+    out = np.zeros((len(shapes), XF_WORDS), dtype=np.float64)
+    for i in range(len(shapes)):
+        if arr[i].transformed:
+            out[i] = np.frombuffer(arr[i].xf, dtype=np.float64, count=XF_WORDS)
+    return out
+
+
 # helper constructors, shape.rs:286-313
 def sphere():
     return Sphere()

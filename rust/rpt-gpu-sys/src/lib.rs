@@ -352,6 +352,8 @@ pub mod ffi {
         pub fn rptgpu_scene_set_lights(h: *mut rptgpu_scene, n: u64, index: *const u32, lights: *const RptLight) -> c_int;
         pub fn rptgpu_scene_set_mesh(h: *mut rptgpu_scene, object: u32, n: u64, tris: *const RptTriangle) -> c_int;
         pub fn rptgpu_scene_set_mesh_device(h: *mut rptgpu_scene, object: u32, n: u64, d_tris: *const c_void, stream: *mut c_void) -> c_int;
+        pub fn rptgpu_scene_set_group(h: *mut rptgpu_scene, object: u32, n: u64, children: *const RptShape) -> c_int;
+        pub fn rptgpu_scene_set_group_device(h: *mut rptgpu_scene, object: u32, n: u64, d_transforms: *const c_void, stream: *mut c_void) -> c_int;
         pub fn rptgpu_render_batch(h: *mut rptgpu_scene, camera: *const RptCamera, params: *const RptRenderParams, out_rgb: *mut f64) -> c_int;
         pub fn rptgpu_render_batch_device(h: *mut rptgpu_scene, camera: *const RptCamera, params: *const RptRenderParams, d_out: *mut c_void, out_is_f32: c_int, stream: *mut c_void) -> c_int;
         pub fn rptgpu_comm_unique_id(out_id: *mut u8) -> c_int;
