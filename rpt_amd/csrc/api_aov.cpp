@@ -74,7 +74,7 @@ void aov_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams
   rptplan::PassInput in{};
   in.npix = npix; in.iterations = p.iterations;
   in.per_slot = rptplan::wavefront_slot_bytes(h->dscene.num_lights, h->has_deep, h->sort_rays, h->path_reorder);
-  in.target_paths = h->target_paths; in.budget_bytes = h->ws_budget_bytes;
+  in.target_paths = h->opt.target_paths; in.budget_bytes = h->opt.workspace_bytes;
   in.free_percent = RPT_WS_FREE_PERCENT;
   in.rec_ratio = 1.0; in.ratio = 1.0;
   const bool by_object = h->has_deep && (!(p.flags & RPT_FLAG_GENERAL_TRAVERSAL) || h->tree_kids);

@@ -5,36 +5,27 @@
 // same functions (derive_tree, mesh_records.h grid_over, shape_records.h quadric_too_small, fill_object_boxes).
 // DESIGN.md §9.2 has the contract and the audit of what follows from the tree.
 //
-// Storage: the spare set of the geometry arrays, written whole and swapped in at the end (tree_splice.h, shared with
-// api_mesh.cpp).  The group's child region of insts keeps its size and place; nodes, refs, lrec and lbox of later trees
-// shift with node_base and ref_base.
+// The call's frame — first refusals, lap timer, the tree's rebuild, the spare set of the geometry arrays (written whole
+// and swapped in at the end), the re-route — is tree_splice.h's, shared with api_mesh.cpp.  The group's child region of
+// insts keeps its size and place; nodes, refs, lrec and lbox of later trees shift with node_base and ref_base.
 #include "api_internal.h"
 #include "group_update.h"
-#include "mesh_records.h"
 #include "tree_splice.h"
 
 namespace {
 
 static_assert(sizeof(RptTransform) == rptgroup::XF_WORDS * sizeof(double), "RptTransform is 51 f64 words");
 
+const RebuildWords GROUP_WORDS = {RPT_SHAPE_GROUP, "a group", "child", "moving the children keeps the count, other children need a new handle", "rebuilt"};
+
 // the host entry: children (d_xf: nullptr); the device entry: d_xf, [n] RptTransform on the device (children: nullptr)
 int set_group(rptgpu_scene* h, uint32_t object, uint64_t n, const RptShape* children, const void* d_xf, bool on_device,
               hipStream_t user_stream, const std::string& fn) {
-  if (!h) return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, fn + "null handle");
-  if (h->abandoned)
-    return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + "an aborted batch's device work never drained on this handle: it takes no update (destroy it)");
-  const size_t count = h->obj_geom.size();
-  const std::string obj = "object " + std::to_string(object);
-  if (object >= count)
-    return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + obj + " is out of range (the scene has " + std::to_string(count) + ")");
-  const rptdev::Inst was = h->top_insts[object];
-  if (was.kind != RPT_SHAPE_GROUP)
-    return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + obj + " is not a group (shape kind " + std::to_string(was.kind) + ")");
-  const size_t t = (size_t)was.tree;
-  const rptdev::Tree old = h->host_trees[t];
-  if (n != old.num_prims)
-    return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + "n = " + std::to_string(n) + " differs from the child count of " + obj +
-                                                 " at creation (" + std::to_string(old.num_prims) + "): moving the children keeps the count, other children need a new handle");
+  RebuildTarget tg;
+  if (int rc = rebuild_target(h, object, n, GROUP_WORDS, fn, tg)) return rc;
+  const size_t t = tg.t;
+  const rptdev::Tree& old = tg.old;
+  const std::string& obj = tg.obj;
   if (n && !(on_device ? d_xf : (const void*)children))
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + (on_device ? "null transform array" : "null children array"));
   for (uint64_t i = 0; i < n && !on_device; i++) { // every child is checked before anything changes
@@ -54,21 +45,11 @@ int set_group(rptgpu_scene* h, uint32_t object, uint64_t n, const RptShape* chil
       return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + "child " + std::to_string(i) + " of " + obj + " is a mesh, a monomial surface or a group (shape kind " +
                                                    std::to_string(kind) + "): its box comes from more than a placement, and only groups of spheres and cubes are moved — this needs a new handle");
   }
-  if (h->all_flat)
-    return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + obj + " is walked inside the flat path kernel, whose LDS layout and plane table are "
-                                                 "derived from the coordinates at creation: this needs a new handle");
+  if (int rc = refuse_all_flat(h, fn, tg)) return rc;
   if (!n) return RPTGPU_OK; // (an empty group has nothing to move)
   return guarded(h, h->device, [&]() -> int {
     const hipStream_t st = h->stream;
-    const bool print = std::getenv("RPTGPU_PRINT_UPDATE") != nullptr; // where the hand-off's time goes (stderr; adds synchronisations)
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-      if (!print) return;
-      HIP_TRY(hipStreamSynchronize(st));
-      auto t1 = std::chrono::steady_clock::now();
-      std::fprintf(stderr, "scene_set_group %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
-      t0 = t1;
-    };
+    UpdateLap lap{st, "scene_set_group"};
     const uint32_t nk = (uint32_t)n;
     const double* src = (const double*)d_xf;
     std::vector<double> staged; // (alive until the stream has drained below)
@@ -87,57 +68,36 @@ int set_group(rptgpu_scene* h, uint32_t object, uint64_t n, const RptShape* chil
     h->mesh_boxes.alloc(n);
     HIP_TRY(rptgroup::child_records(st, src, nk, h->insts.p + old.prim_base, h->alt_insts.p + old.prim_base, h->mesh_boxes.p));
     lap("upload, child records");
-    // ---- the tree: the 48-byte boxes come to the host, where both builders take them, and the bounds are folded in
-    // index order as KdTree::new folds them
-    std::vector<rpthost::Box> boxes(n);
-    HIP_TRY(hipMemcpyAsync(boxes.data(), h->mesh_boxes.p, n * sizeof(rpthost::Box), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    lap("boxes to the host");
-    rpthost::BuildOptions bopt;
-    bopt.device_build_min = (size_t)h->opt.device_build_min;
-    bopt.build_threads = (int)h->opt.build_threads;
-    if (bopt.device_build_min) bopt.device = h->device;
-    rpthost::KdBuild kb;
-    rpthost::build_kd(boxes, &bopt, kb);
-    HIP_TRY(hipSetDevice(h->device));
-    rptdev::Tree tr = old;
-    rpthost::derive_tree(kb, boxes, tr);
-    rptgroup::LeafGrid grid;
-    rptrec::grid_over(tr.bounds, tr.qlo, tr.qscale);
-    std::memcpy(grid.qlo, tr.qlo, sizeof grid.qlo);
-    std::memcpy(grid.qscale, tr.qscale, sizeof grid.qscale);
-    const uint32_t depth = kb.max_depth;
-    lap("kd build");
-    // a group the handle walks inside the path kernels keeps that route; their stacks hold fast_max_depth levels
-    if (!h->obj_deep[object] && depth > h->opt.fast_max_depth)
-      return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + "the rebuilt tree is " + std::to_string(depth) + " levels deep and " + obj +
-                                                   " is walked inside the path kernels, whose stacks hold " +
-                                                   std::to_string(h->opt.fast_max_depth) + ": this needs a new handle");
+    // ---- the tree
+    RebuiltTree rb;
+    rebuild_tree(h, n, old, nullptr, lap, rb);
+    const rptdev::Tree& tr = rb.tr;
+    const std::string why = depth_refusal(h, object, rb.depth, GROUP_WORDS);
+    if (!why.empty()) return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + why);
     // ---- the spare set, packed as a fresh handle packs it
     TreeSplice sp;
-    if (!plan_splice(h, t, kb, sp))
+    if (!plan_splice(h, t, rb.kb, sp))
       return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + "the scene's trees would outgrow 32-bit node or entry indices");
-    pack_spare_tree(h, sp, kb, st);
+    pack_spare_tree(h, sp, rb.kb, st);
     // (a group's lrec slots are unused: zeros, as a fresh handle's)
     if (sp.nr) HIP_TRY(hipMemsetAsync(h->alt_trix.p + old.ref_base, 0, sp.nr * sizeof(rptdev::TriX), st));
     lap("copies, nodes and entries");
     HIP_TRY(rptgroup::leaf_boxes(st, h->alt_refs.p + old.ref_base, (uint32_t)sp.nr, nk, h->alt_insts.p + old.prim_base, h->mesh_boxes.p,
-                                 grid, h->alt_lbox.p + old.ref_base));
+                                 leaf_grid<rptgroup::LeafGrid>(tr), h->alt_lbox.p + old.ref_base));
     lap("leaf boxes");
-    // the tree records (the later trees' regions moved) and the group object itself (Inst::bounds copies Tree::bounds)
+    // the tree records (the later trees' regions moved) and the group object itself
     std::vector<rptdev::Tree> trees = spliced_trees(h, sp, tr);
     std::vector<rptdev::Inst> insts = h->top_insts;
     std::vector<rpthost::ObjectGeom> geom = h->obj_geom;
-    std::memcpy(insts[object].bounds, tr.bounds, sizeof tr.bounds);
-    for (int k = 0; k < 3; k++) { geom[object].local.lo[k] = tr.bounds[k]; geom[object].local.hi[k] = tr.bounds[3 + k]; }
+    set_object_bounds(insts[object], geom[object], tr);
     rpthost::ObjectBounds ob;
     rpthost::fill_object_boxes(insts, geom, ob);
     pack_spare_records(h, trees, insts, st);
     HIP_TRY(hipStreamSynchronize(st));
     lap("tree and object records");
     // ---- the swap: from here on nothing fails
-    swap_spare(h, sp, trees, insts, geom, ob, depth, false);
-    reroute_object(h, object, tr, depth); // what the routing took from the tree at creation (api_scene.cpp)
+    swap_spare(h, sp, trees, insts, geom, ob, rb.depth, false);
+    reroute_object(h, object, tr, rb.depth);
     return RPTGPU_OK;
   });
 }

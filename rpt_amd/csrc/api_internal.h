@@ -2,7 +2,11 @@
 // convention and the entry points' frame (guarded), the RCCL binding.  The ABI's implementation is split by concern
 // (round 6; it was one 1 900-line api.cpp):
 //   api_common.cpp   errors, the RCCL loader, kernel tables, version / strerror / stats
-//   api_scene.cpp    RptSceneOptions, rptgpu_scene_create[_opts] (flattening, routing, upload), the kd-tree entry points
+//   api_scene.cpp    RptSceneOptions, rptgpu_scene_create[_opts] (flatten, open the device, plan, apply, upload), the live
+//                    updates of placements and materials, the kd-tree entry points
+//   scene_plan.h     the plan: every object's route (obj_deep / obj_tris, their bits named in launch_limits.h), the scene's
+//                    flags, the re-route after a live rebuild, and the flat path kernel's LDS layout (flat_layout.h) — pure
+//                    host functions, read by creation and by every live update (tests/cpp/scene_plan_check.cpp)
 //   api_render.cpp   workspace, the wavefront loop and the persistent launch (render_impl), render_batch[_device],
 //                    rptgpu_closest_hit, rptgpu_eval_math; their launch and pass sizes come from render_plan.h.  Also the
 //                    steps every driver of the wavefront kernels shares: the route (use_wavefront), a pass's size with
@@ -16,7 +20,8 @@
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
-//                    way (the kernels: group_update.hip); tree_splice.h holds the spare-set storage both files use
+//                    way (the kernels: group_update.hip); tree_splice.h holds what both files share: the first refusals,
+//                    the lap timer, the tree's rebuild, the spare-set storage, the swap and the re-route
 //   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, pass loop, copy_aov_out); its device
 //                    half also fills the features a Buffer holds for rptgpu_buffer_denoise
 // No compute happens on the host; if there is no HIP device every compute entry point returns RPTGPU_E_NO_DEVICE (there is
@@ -166,9 +171,8 @@ struct rptgpu_scene {
   uint32_t rec_ratio_bounces = 0xffffffffu; // far at this max_bounces (0 = not measured yet: the next pass measures)
   uint64_t ws_fail_paths = 0;          // the smallest pass (paths) whose workspace did not fit on this device so far; 0 = none
   DevBuf<double> prec;                 // persistent kernel: depth records [threads][bounces][8]
-  DevBuf<double> lbuf;                 // persistent kernel: radiance of every sample of a launch [spp][3][npix]
-  uint64_t lbuf_max_bytes = 32ull << 30; // cap on lbuf (RPTGPU_LBUF_BYTES); larger batches run as several launches
-  uint32_t paths_chunk = 0;            // samples per work item (RptSceneOptions::paths_chunk; 0 = chosen per launch)
+  DevBuf<double> lbuf;                 // persistent kernel: radiance of every sample of a launch [spp][3][npix]; opt.lbuf_bytes caps
+                                       // it, larger batches run as several launches
   DevBuf<unsigned long long> pcounters; // [0] closest-hit rays [1] shadow rays
   DevBuf<double> rays_o, rays_d, rays_out; // rptgpu_trace_rays: a piece of the host caller's rays and of their results (api_rays.cpp)
   DevBuf<uint32_t> ray_ids;            // ... and the piece's stream ids (the caller's, or the rays' indices); rptgpu_bake_probes
@@ -182,7 +186,8 @@ struct rptgpu_scene {
   DevBuf<double> plane_vals;       // distinct bounding-plane coordinates of the untransformed meshes [3][4]
   uint32_t flat_lds_bytes = 0;
   bool ext_shapes = false;       // scene has a shape only the *_ext kernel builds implement
-  // deep-tree scenes: per top-level object flags and the buffers of the object-by-object query
+  // deep-tree scenes: per top-level object the route bytes (launch_limits.h; made by scene_plan.h) and the buffers of the
+  // object-by-object query
   std::vector<uint8_t> obj_deep, obj_tris, light_casts;
   // every per-tree object of the scene is one only by the kd-trees-of-kd-trees rule (shallow group, mesh children): for
   // (fractal_teapots at 8 bounces, 3.8 M paths per pass: 60.7 against 56.9 Msamples/s; 7.7 M: 70.6 against 86.7)
@@ -223,19 +228,16 @@ struct rptgpu_scene {
   DevBuf<uint32_t> mesh_flag;        // [0] some triangle is a sliver
   std::vector<uint32_t> cnt_host;  // the per-depth counters read back from the device
   bool has_deep = false;
-  int rays_in_kernel = 0;          // RPTGPU_RAYS_IN_KERNEL: rptgpu_closest_hit keeps to rpt_extend_rays also when the scene has deep trees
   DevBuf<uint32_t> tq, tq_ctr;
   StackSpill spill{};              // the per-tree traversal kernels' stack beyond the LDS levels (kernels.h)
   DevBuf<uint32_t> spill_node;
   DevBuf<double> spill_ts, spill_bmax;
   DevBuf<double> tree_rays;        // [cap][8]: rpt_tree_enter's rows for the traversal kernels' refill
   // optional ray sort in front of the per-tree traversal (RPTGPU_SORT_RAYS)
-  bool sort_rays = false;          // some deep tree is large enough for sorting to pay (obj_deep[i] == 2)
-  int sort_mode = -1;              // RPTGPU_SORT_RAYS: 0 never, 1 every deep tree, default: by footprint
-  uint64_t sort_min_bytes = 8ull << 20;  // RPTGPU_SORT_MIN_BYTES: nodes + leaf records of a tree whose rays are worth sorting
-  RptSceneOptions opt{};           // the handle's knobs: defaults, the caller's RptSceneOptions, environment overrides — fixed at creation
+  bool sort_rays = false;          // some deep tree is large enough for sorting to pay (RPT_DEEP_SORTED in its obj_deep)
+  RptSceneOptions opt{};           // the handle's knobs: defaults, the caller's RptSceneOptions, environment overrides — fixed at creation,
+                                   // and the one copy of each: every reader reads it here
   QueryTuning qtune{0u, 1u << 19};  // launch_query's counter-set toggle; opt.sort_min_rays
-  uint64_t sort_shadow_min_bytes = 8ull << 20; // RPTGPU_SORT_SHADOW_MIN_BYTES: ... whose SHADOW rays are, too
   DevBuf<uint32_t> sort_kin, sort_kout, sort_vin;
   DevBuf<uint8_t> sort_tmp;
   SortBufs sort_bufs{};
@@ -250,9 +252,6 @@ struct rptgpu_scene {
   struct Pending { int kind; int e0, e1; };
   std::vector<Pending> pending;
   int ev_used = 0;
-  uint64_t target_paths = 0;       // RPTGPU_TARGET_PATHS: paths in flight per pass of the wavefront pipeline; 0 = as many as
-                                   // the workspace budget holds (ws_budget_bytes and half of the free HBM), at most 128 Mi
-  uint64_t ws_budget_bytes = 240ull << 30; // RPTGPU_WS_BYTES
   // multi-GPU: the communicator of this handle (rptgpu_comm_init) and its frame buffers
   RcclComm comm = nullptr;
   int comm_rank = 0, comm_world = 1;
@@ -388,6 +387,8 @@ void copy_aov_out(const rptdev::AovOut& src, uint32_t channels, const RptAovBuff
       return fail((h), RPTGPU_E_COMM, "an aborted batch's device work never drained on this handle: destroy it (its "    \
                                       "workspace may still be written by the abandoned stream)");                        \
   } while (0)
-
+// the live updates' refusal of such a handle (api_scene.cpp update_refusal, tree_splice.h rebuild_target)
+constexpr const char* ABANDONED_TAKES_NO_UPDATE =
+    "an aborted batch's device work never drained on this handle: it takes no update (destroy it)";
 
 } // namespace rptapi

@@ -308,7 +308,7 @@ rptdev::PathState path_state(rptgpu_scene* h) {
   ps.ray_next = h->ray_next.p; ps.draw_next = h->draw_next.p; ps.pid_next = h->pid_next.p; ps.col_next = h->col_next.p;
   ps.rec = h->rec.p; ps.rec_parent = h->rec_parent.p; ps.last_col = h->last_col.p;
   ps.shadow = h->shadow.p; ps.cap = h->ws_cap; ps.rec_cap = h->ws_rec_cols;
-  if (h->path_reorder) { // (never with per-tree queues: api_scene.cpp)
+  if (h->path_reorder) { // (never with per-tree queues: scene_plan.h fold_routes)
     ps.sort_keys = h->sort_kin.p; ps.sort_vals = h->sort_vin.p; ps.next_rows = h->next_rows.p;
     std::memcpy(ps.key_bounds, h->scene_bounds, sizeof ps.key_bounds);
   }
@@ -323,7 +323,7 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   const uint32_t npix = fr.npix;
   const bool print_launch = std::getenv("RPTGPU_PRINT_LAUNCH") != nullptr;
   const uint64_t lbuf_held = h->lbuf.n * sizeof(double);
-  const int64_t free_b = lbuf_held < h->lbuf_max_bytes ? free_memory() : -1;
+  const int64_t free_b = lbuf_held < h->opt.lbuf_bytes ? free_memory() : -1;
   const bool flat = h->all_flat && !h->dscene.force_general;
   FlatLayout lay = flat ? h->flat_layout : FlatLayout{};
   const uint32_t flat_lds = lay.off_end;
@@ -344,7 +344,7 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   }
   const rptplan::PersistentPlan pl = rptplan::plan_persistent(
       npix, p.iterations, p.max_bounces, h->num_cus, kt->paths_max_blocks_per_cu(flat ? &lay : nullptr, flat_lds, false),
-      h->lbuf_max_bytes, lbuf_held, free_b, h->paths_chunk, h->all_flat, h->dscene.force_general, h->flat_layout.obj_filter);
+      h->opt.lbuf_bytes, lbuf_held, free_b, h->opt.paths_chunk, h->all_flat, h->dscene.force_general, h->flat_layout.obj_filter);
   // a texture environment: the lanes park their lookups in what the wave's LDS share has left (kernels/paths.inc) —
   // unless that costs a resident wave (a flat scene that fills the share)
   bool park = flat && h->opt.env_park != 0 && h->dscene.env_kind != RPT_ENV_COLOR; // (flat scenes: rpt_paths<KdLds>'s stack fills the share)
@@ -499,7 +499,7 @@ rptplan::PassInput pass_input(rptgpu_scene* h, uint32_t npix, uint32_t iteration
   rptplan::PassInput in{};
   in.npix = npix; in.iterations = iterations;
   in.per_slot = rptplan::wavefront_slot_bytes(h->dscene.num_lights, h->has_deep, h->sort_rays, h->path_reorder);
-  in.target_paths = h->target_paths; in.budget_bytes = h->ws_budget_bytes;
+  in.target_paths = h->opt.target_paths; in.budget_bytes = h->opt.workspace_bytes;
   // the share of the free memory a pass may take (round 6: 85 %, was 1/2 — the passes of a 288 GB device were
   // sized for 140 GB).  RPTGPU_WS_FREE_FRACTION (percent): experiments only
   in.free_percent = RPT_WS_FREE_PERCENT;
@@ -647,7 +647,7 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
   if (!n) return RPTGPU_OK;
   return guarded(h, h->device, [&]() -> int {
     hipStream_t st = h->stream;
-    if (h->has_deep && (!h->rays_in_kernel || h->tree_kids)) {
+    if (h->has_deep && (!h->opt.rays_in_kernel || h->tree_kids)) {
       // a scene with deep trees: the rays take the route a render's rays take — object by object, every deep tree with
       // its own queue, sort and persistent traversal (launch_query) — in pieces of at most 4 Mi rays
       const KernelTable* kt = table_for(precision_mode, h->ext_shapes);

@@ -1,6 +1,8 @@
 // api_scene.cpp — RptSceneOptions (defaults, sized access, validation, environment overrides), rptgpu_scene_create[_opts]
-// (flattening, kd builds, routing between the pipelines, upload), the kd-tree entry points (see api_internal.h)
+// (flattening, kd builds, the plan of scene_plan.h into the handle, upload), rptgpu_scene_set_objects / _lights, the kd-tree
+// entry points (see api_internal.h)
 #include "api_internal.h"
+#include "scene_plan.h"
 
 extern "C" {
 
@@ -92,13 +94,6 @@ void apply_env_overrides(RptSceneOptions& o, bool user_set_build_min) {
   if (const char* e = std::getenv("RPTGPU_WS_BYTES")) { uint64_t u = std::strtoull(e, nullptr, 10); if (u >= (1ull << 20)) o.workspace_bytes = u; }
   if (const char* e = std::getenv("RPTGPU_COMM_TIMEOUT_S")) { double d = std::atof(e); if (d > 0.0) o.comm_timeout_s = d; }
 }
-// bit i: top-level object i is a user of the flat kernel's plane table (the pre-trace pass never skips those)
-uint64_t plane_users(const std::vector<rptdev::Inst>& insts, size_t n) {
-  uint64_t m = 0;
-  for (size_t i = 0; i < n && i < 64; i++)
-    if (insts[i].plane_use) m |= 1ull << i;
-  return m;
-}
 } // namespace
 
 int rptgpu_scene_get_options(const rptgpu_scene* h, RptSceneOptions* out) {
@@ -111,6 +106,62 @@ int rptgpu_scene_get_options(const rptgpu_scene* h, RptSceneOptions* out) {
   return RPTGPU_OK;
 }
 
+} // extern "C"
+
+namespace {
+// what the routing reads of top-level object i (scene_plan.h route_object)
+rptscene::ObjectFacts object_facts(const rpthost::FlatScene& fs, int i) {
+  const rptdev::Inst& in = fs.insts[i];
+  rptscene::ObjectFacts f;
+  f.kind = in.kind;
+  if (in.kind != RPT_SHAPE_MESH && in.kind != RPT_SHAPE_GROUP) return f;
+  const rptdev::Tree& tr = fs.trees[in.tree];
+  const bool last = (size_t)in.tree + 1 >= fs.trees.size();
+  const uint64_t nodes = (last ? fs.nodes.size() : fs.trees[in.tree + 1].node_base) - tr.node_base;
+  const uint64_t refs = (last ? fs.refs.size() : fs.trees[in.tree + 1].ref_base) - tr.ref_base;
+  f.depth = fs.tree_depth[in.tree];
+  f.regular = tr.regular != 0;
+  f.root_leaf = tr.root_leaf != 0;
+  f.bytes = nodes * sizeof(rptdev::KdNode) + refs * (sizeof(uint32_t) + (in.kind == RPT_SHAPE_MESH ? sizeof(rptdev::TriX) : 0));
+  if (in.kind == RPT_SHAPE_GROUP) {
+    f.tree_kids = fs.tree_kids[in.tree];
+    for (uint32_t k = 0; k < tr.num_prims; k++) {
+      const rptdev::Inst& kid = fs.insts[tr.prim_base + k];
+      if (kid.kind != RPT_SHAPE_MESH) continue;
+      f.kids_depth = std::max(f.kids_depth, fs.tree_depth[kid.tree]);
+      f.kids_regular = f.kids_regular && fs.trees[kid.tree].regular;
+    }
+  }
+  return f;
+}
+// what the flat layout reads of the scene (scene_plan.h plan_flat)
+rptscene::FlatInput flat_input(const rpthost::FlatScene& fs, const RptSceneOptions& opt) {
+  rptscene::FlatInput in;
+  in.n_refs = fs.refs.size(); in.n_tris = fs.tris.size();
+  for (int i = 0; i < fs.num_objects; i++) {
+    rptscene::FlatObject o{fs.insts[i].kind, fs.insts[i].has_xf, {}};
+    std::memcpy(o.bounds, fs.insts[i].bounds, sizeof o.bounds);
+    in.objects.push_back(o);
+  }
+  in.n_lights = fs.lights.size();
+  if (!fs.lights.empty()) {
+    const rptdev::Light& l0 = fs.lights[0];
+    in.light0_kind = l0.kind;
+    if (l0.kind == RPT_LIGHT_OBJECT && fs.insts[l0.inst].kind == RPT_SHAPE_MESH && !fs.insts[l0.inst].has_xf) {
+      in.light0_plain_mesh = true;
+      in.light0_tris = fs.trees[fs.insts[l0.inst].tree].num_prims;
+    }
+  }
+  in.obj_filter_ok = fs.obj_filter_ok; in.obj_always = fs.obj_always;
+  in.object_filter_min = opt.object_filter_min;
+  in.tris_global = std::getenv("RPTGPU_FLAT_TRIS_GLOBAL") != nullptr;
+  in.no_plane_table = std::getenv("RPTGPU_NO_PLANE_TABLE") != nullptr;
+  return in;
+}
+} // namespace
+
+extern "C" {
+
 int rptgpu_scene_create(const RptScene* scene, int device, rptgpu_scene** out) {
   return rptgpu_scene_create_opts(scene, device, nullptr, out);
 }
@@ -118,6 +169,7 @@ int rptgpu_scene_create(const RptScene* scene, int device, rptgpu_scene** out) {
 int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOptions* user_opts, rptgpu_scene** out) {
   if (!scene || !out) return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
+  // ---- the options: defaults, the caller's struct, the environment, the ranges
   RptSceneOptions opt;
   options_default_full(&opt);
   bool user_set_build_min = false;
@@ -133,6 +185,7 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
   if (const char* why = options_out_of_range(opt)) // the overrides are held to the same ranges as the fields
     return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, std::string(why) + " (after the RPTGPU_* environment overrides)");
   opt.fast_max_depth = std::min(opt.fast_max_depth, (uint32_t)rptdev::KD_MAX_STACK);
+  // ---- flatten
   rpthost::FlatScene fs;
   std::string err;
   int rc;
@@ -165,6 +218,7 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
   }
   if (rc != RPTGPU_OK) return fail(nullptr, rc, err);
   lap(fs.trees_built_on_device ? "flatten + kd build (device)" : "flatten + kd build");
+  // ---- open the device
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(nullptr, RPTGPU_E_NO_DEVICE, "no HIP device is visible (hipGetDeviceCount); there is no CPU fallback");
@@ -179,257 +233,33 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     h->num_cus = prop.multiProcessorCount;
     lap("device, stream, properties");
-    h->prefer_wavefront = fs.max_tree_depth >= 3;
-    // RPTGPU_FAST_MAX_DEPTH (tests): treat trees deeper than this as too deep for the in-kernel traversals.  The build rule
-    // itself keeps real trees far below 32: both children of a median split hold (n + straddlers) / 2 primitives, so a path
-    // d levels long needs 16 / 0.85^d primitives with an unsplittable sibling at every level, or 16 * 2^d balanced ones.
     h->opt = opt;
-    const uint32_t fast_max_depth = opt.fast_max_depth;
-    h->max_tree_depth = fs.max_tree_depth;
-    const uint32_t deep_depth = opt.deep_depth;
-    h->rays_in_kernel = opt.rays_in_kernel;
-    h->sort_mode = opt.sort_rays;
-    h->sort_min_bytes = opt.sort_min_bytes;
-    h->sort_shadow_min_bytes = opt.sort_shadow_min_bytes;
     h->qtune.sort_min_rays = opt.sort_min_rays;
-    h->paths_chunk = opt.paths_chunk;
-    h->lbuf_max_bytes = opt.lbuf_bytes;
-    h->target_paths = opt.target_paths;
-    h->ws_budget_bytes = opt.workspace_bytes;
+    // ---- the plan (scene_plan.h): every object's route, the scene's flags, the flat kernel's LDS layout
+    std::vector<rptscene::ObjectRoute> routes;
+    for (int i = 0; i < fs.num_objects; i++) routes.push_back(rptscene::route_object(object_facts(fs, i), opt));
+    bool all_root_leaf = true;
+    for (const rptdev::Tree& tr : fs.trees) all_root_leaf = all_root_leaf && tr.root_leaf != 0;
+    const char* env = std::getenv("RPTGPU_PATH_REORDER");
+    const rptscene::SceneRoute sr =
+        rptscene::fold_routes(routes, fs.max_tree_depth, fs.scene_bounds_ok, fs.trees.size(), all_root_leaf, !env || std::atoi(env) != 0);
+    if ((env = std::getenv("RPTGPU_PATH_REORDER_MIN"))) h->path_reorder_min = (uint32_t)std::max(1, std::atoi(env));
+    rptscene::FlatPlan flat;
+    if (sr.all_flat) flat = rptscene::plan_flat(flat_input(fs, opt));
+    // ---- the plan into the handle and the records that go to the device
     for (int i = 0; i < fs.num_objects; i++) {
-      const rptdev::Inst& in = fs.insts[i];
-      bool tree = in.kind == RPT_SHAPE_MESH || in.kind == RPT_SHAPE_GROUP;
-      bool deep = tree && fs.tree_depth[in.tree] >= deep_depth;
-      // A group with TREE children (meshes: fractal_teapots.rs; groups: kdtree.rs:14-24 nests without limit) goes through
-      // the per-tree kernels whatever its own depth — they are the only ones that walk a tree inside a tree: rpt_nest_trace
-      // (two regular levels, one loop) or rpt_tree_generic (anything).  So does a tree deeper than the fast stacks.
-      const bool kids = in.kind == RPT_SHAPE_GROUP && fs.tree_kids[in.tree] != 0;
-      // deeper than the private stacks of the in-kernel traversals (KD_MAX_STACK): the per-tree kernels, whose stack
-      // beyond the LDS levels is a global column as high as the scene's deepest tree (ensure_workspace)
-      const bool too_deep = tree && fs.tree_depth[in.tree] > fast_max_depth;
-      deep = deep || kids || too_deep;
-      h->tree_kids = h->tree_kids || kids || too_deep; // (= some object is for the per-tree pipeline only)
-      // rays entering a large tree are sorted by entry cell and octant first: neighbours in a wave then walk the same
-      // nodes.  Measured with the VALU-bound traversal kernel of round 2: 100k-triangle mesh (66 MB of nodes + leaf
-      // records) 144 -> 172 Msamples/s, 16k-triangle glass (17 MB) 469 -> 528, a 25k-triangle mesh under few bounces
-      // (25 MB) 781 -> 766, two 768-triangle meshes (0.6 MB) 4243 -> 3248: the sort sorts EVERY ray of the depth, the
-      // gain grows with the work of the rays that enter — so by size, with the threshold well below the glass
-      bool sort = false, sort_shadow = false;
-      if (deep) {
-        const rptdev::Tree& tr = fs.trees[in.tree];
-        uint64_t next_node = (size_t)in.tree + 1 < fs.trees.size() ? fs.trees[in.tree + 1].node_base : fs.nodes.size();
-        uint64_t next_ref = (size_t)in.tree + 1 < fs.trees.size() ? fs.trees[in.tree + 1].ref_base : fs.refs.size();
-        uint64_t bytes = (next_node - tr.node_base) * sizeof(rptdev::KdNode) +
-                         (next_ref - tr.ref_base) * (sizeof(uint32_t) + (in.kind == RPT_SHAPE_MESH ? sizeof(rptdev::TriX) : 0));
-        sort = h->sort_mode == 1 || (h->sort_mode < 0 && bytes >= h->sort_min_bytes);
-        // shadow rays point at ONE light from surfaces that the closest-hit pass just visited in sorted order: for a tree
-        // that is not many times the L2s their sort costs more than it gives (16k-triangle glass, ~10 MB: shadow stage
-        // 47.7 -> 42.8 ms per two steps without it; 100k-triangle mesh, ~60 MB: 137 -> 180)
-        sort_shadow = sort && (h->sort_mode == 1 || bytes >= h->sort_shadow_min_bytes);
-      }
-      // which traversal kernel of the per-tree pipeline: 1 rpt_tree_trace<TRIS>, 0 rpt_tree_trace over a group of simple
-      // shapes, 2 a group with mesh children whose two regular levels fit one traversal stack: rpt_nest_trace
-      // (RPTGPU_NEST_TRACE=0: rpt_tree_generic instead), 3 rpt_tree_generic alone (Tree::generic_only)
-      uint8_t trace_kind = in.kind == RPT_SHAPE_MESH ? 1 : 0;
-      bool generic_only = false;
-      if (kids) {
-        const rptdev::Tree& tr = fs.trees[in.tree];
-        uint32_t inner_depth = 0;
-        bool ok = tr.regular && !(fs.tree_kids[in.tree] & 2u); // rpt_nest_trace: no group children, no irregular trees
-        for (uint32_t k = 0; k < tr.num_prims; k++) {
-          const rptdev::Inst& kid = fs.insts[tr.prim_base + k];
-          if (kid.kind == RPT_SHAPE_MESH) {
-            inner_depth = std::max(inner_depth, fs.tree_depth[kid.tree]);
-            ok = ok && fs.trees[kid.tree].regular;
-          }
-        }
-        if (ok && opt.nest_trace != 0 && fs.tree_depth[in.tree] + inner_depth + 2 <= (uint32_t)rptdev::KD_MAX_STACK) trace_kind = 2;
-        else generic_only = true;
-      }
-      if (generic_only) {
-        trace_kind = 3;
-        fs.trees[in.tree].generic_only = 1u;
-        sort = false;
-        sort_shadow = false;
-      }
-      h->sort_rays = h->sort_rays || sort;
-      // obj_deep: 0 in-kernel; 1 per-tree; 2 per-tree with the ray sort; +4: every ray of it goes through rpt_tree_generic
-      // (an irregular tree, an object only that kernel is built for)
-      const bool all_generic = deep && (generic_only || !fs.trees[in.tree].regular);
-      h->gen_all = h->gen_all || all_generic;
-      // +8: the sort serves the closest-hit query only
-      h->obj_deep.push_back(deep ? (uint8_t)((sort ? 2 : 1) | (all_generic ? 4 : 0) | (sort && !sort_shadow ? 8 : 0)) : 0);
-      // bit 4 (shallow objects): a primitive or a tree that is ONE leaf — runs of such objects take the lean build of
-      // rpt_rays_objects (kernels/tree_query.inc)
-      const bool one_leaf = !tree || fs.trees[in.tree].root_leaf != 0;
-      h->obj_tris.push_back((uint8_t)(trace_kind | (!deep && one_leaf ? 16 : 0)));
-      h->has_deep = h->has_deep || deep;
+      h->obj_deep.push_back(routes[i].deep);
+      h->obj_tris.push_back(routes[i].tris);
+      if (routes[i].generic_only) fs.trees[fs.insts[i].tree].generic_only = 1u;
+      if (sr.all_flat && flat.plane_use[i]) { fs.insts[i].plane_idx = flat.plane_idx[i]; fs.insts[i].plane_use = flat.plane_use[i]; }
     }
+    h->has_deep = sr.has_deep; h->tree_kids = sr.tree_kids; h->sort_rays = sr.sort_rays; h->gen_all = sr.gen_all;
+    h->prefer_wavefront = sr.prefer_wavefront;
+    h->path_reorder = sr.path_reorder;
+    h->all_flat = sr.all_flat && flat.flat;
+    h->max_tree_depth = fs.max_tree_depth;
     h->gen_levels = fs.generic_levels; h->gen_frames = fs.generic_frames;
-    // scenes whose trees are all walked inside rpt_extend / rpt_shadow_rays get their paths re-ordered per depth
-    // (RPTGPU_PATH_REORDER: an A/B switch, environment only — scheduling, not results)
     std::memcpy(h->scene_bounds, fs.scene_bounds, sizeof h->scene_bounds);
-    h->path_reorder = !h->has_deep && fs.scene_bounds_ok && !fs.trees.empty();
-    if (const char* e = std::getenv("RPTGPU_PATH_REORDER")) h->path_reorder = h->path_reorder && std::atoi(e) != 0;
-    if (const char* e = std::getenv("RPTGPU_PATH_REORDER_MIN")) h->path_reorder_min = (uint32_t)std::max(1, std::atoi(e));
-    if (h->tree_kids) h->prefer_wavefront = true;
-    h->all_flat = true;
-    for (const rptdev::Tree& tr : fs.trees) h->all_flat = h->all_flat && tr.root_leaf != 0;
-    if (h->all_flat) h->path_reorder = false; // every tree a single leaf: nothing in rpt_extend diverges by where a ray goes
-    if (h->all_flat) { // does the scene fit a wave's share of LDS (160 KB per CU / 8 waves)?
-      constexpr uint32_t WAVE_LDS = RPT_PATHS_WAVE_LDS - RPT_PATHS_WALKER_LDS; // the wave's share less the fold walker's state
-      auto up16 = [](uint64_t v) { return (v + 15) & ~15ull; };
-      uint64_t off = 0;
-      FlatLayout lay{};
-      lay.n_refs = (uint32_t)fs.refs.size();
-      // intersection records, leaf entries and materials are what a query reads; the triangles themselves (vertex
-      // normals of the hit that stands, light sampling) join them only if everything still fits — C2 does (12
-      // triangles), a room of 23 polygons keeps them in global memory and is flat all the same
-      auto assign = [&](bool with_tris) {
-        lay.n_tris = with_tris ? (uint32_t)fs.tris.size() : 0u;
-        off = up16(fs.refs.size() * sizeof(rptdev::TriX));
-        lay.off_tris = (uint32_t)off; off = up16(off + (uint64_t)lay.n_tris * sizeof(rptdev::Tri));
-        lay.off_refs = (uint32_t)off; off = up16(off + fs.refs.size() * sizeof(uint32_t));
-        lay.off_mat = (uint32_t)off;  off = up16(off + (uint64_t)fs.num_objects * sizeof(rptdev::Material));
-        lay.off_leaf = (uint32_t)off; off = up16(off + (uint64_t)fs.num_objects * 16);
-      };
-      assign(true); // (rpt_paths<KdFlat>: that instantiation also stashes camera rays in LDS)
-      if (off + 12 * 64 * sizeof(double) + RPT_PATHS_STASH_MAX_LDS > WAVE_LDS || std::getenv("RPTGPU_FLAT_TRIS_GLOBAL")) assign(false); // (room for the plane table)
-      // shared slab quotients: distinct plane coordinates per axis over the untransformed meshes (bitwise
-      // distinct: -0.0 and 0.0 give differently signed zeros), at most 4 per axis or the feature stays off
-      std::vector<double> planes(12, 0.0);
-      uint32_t cnt[3] = {0, 0, 0};
-      bool planes_ok = true;
-      auto slot_of = [&](int axis, double v) -> int {
-        uint64_t bits;
-        std::memcpy(&bits, &v, 8);
-        for (uint32_t j = 0; j < cnt[axis]; j++) {
-          uint64_t b2;
-          std::memcpy(&b2, &planes[axis * 4 + j], 8);
-          if (b2 == bits) return axis * 4 + (int)j;
-        }
-        if (cnt[axis] == 4) return -1;
-        planes[axis * 4 + cnt[axis]] = v;
-        return axis * 4 + (int)cnt[axis]++;
-      };
-      static const int FACE[6] = {0, 3, 1, 4, 2, 5}; // bounds[] index of the faces in div6's order
-      std::vector<uint32_t> idx(fs.num_objects, 0);
-      for (int i = 0; i < fs.num_objects && planes_ok; i++) {
-        const rptdev::Inst& in = fs.insts[i];
-        if (in.kind != RPT_SHAPE_MESH || in.has_xf) continue;
-        for (int k = 0; k < 6; k++) {
-          int sl = slot_of(FACE[k] % 3, in.bounds[FACE[k]]);
-          if (sl < 0) { planes_ok = false; break; }
-          idx[i] |= (uint32_t)sl << (4 * k);
-        }
-      }
-      if (planes_ok && cnt[0] + cnt[1] + cnt[2] > 0 && !std::getenv("RPTGPU_NO_PLANE_TABLE")) {
-        for (int i = 0; i < fs.num_objects; i++) {
-          rptdev::Inst& in = fs.insts[i];
-          if (in.kind == RPT_SHAPE_MESH && !in.has_xf) { in.plane_idx = idx[i]; in.plane_use = 1; }
-        }
-        // plane_use = number of consecutive table users starting here, capped at the device's run length
-        for (int i = fs.num_objects - 1; i >= 0; i--) {
-          rptdev::Inst& in = fs.insts[i];
-          if (!in.plane_use) continue;
-          uint32_t next = (i + 1 < fs.num_objects) ? fs.insts[i + 1].plane_use : 0u;
-          in.plane_use = std::min<uint32_t>((uint32_t)RPT_FLAT_RUN, 1u + next);
-        }
-        lay.plane_cnt = cnt[0] | (cnt[1] << 4) | (cnt[2] << 8);
-        // the table's slots are packed (x planes, then y, then z): plane_idx goes from axis * 4 + j to that numbering
-        const uint32_t base[3] = {0u, cnt[0], cnt[0] + cnt[1]};
-        for (int i = 0; i < fs.num_objects; i++) {
-          rptdev::Inst& in = fs.insts[i];
-          if (!in.plane_use) continue;
-          uint32_t packed = 0;
-          for (int k = 0; k < 6; k++) {
-            const uint32_t sl = (in.plane_idx >> (4 * k)) & 15u;
-            packed |= (base[sl >> 2] + (sl & 3u)) << (4 * k);
-          }
-          in.plane_idx = packed;
-        }
-        const uint64_t qtab_bytes = (uint64_t)(cnt[0] + cnt[1] + cnt[2]) * 64 * sizeof(double);
-        lay.off_qtab = (uint32_t)off; off = up16(off + qtab_bytes);
-        // one light, and it casts shadow rays: rpt_paths<KdFlat> traces a hit's shadow ray and bounce ray in one query,
-        // with the shadow ray's quotients in a second table behind the first — if the wave's share still holds it
-        if (RPT_FUSE_QUERY && RPT_RAY_STASH >= 2 && lay.n_tris && fs.lights.size() == 1 && fs.lights[0].kind != RPT_LIGHT_AMBIENT &&
-            up16(off + qtab_bytes) + RPT_PATHS_STASH_MAX_LDS <= WAVE_LDS) {
-          lay.fuse_query = 1;
-          off = up16(off + qtab_bytes);
-        }
-        // the fused kernel's tables of what a hit derives from the scene alone (kernels/paths_consts.inc SceneConsts), behind the
-        // quotient tables — if the wave's share holds them too; a scene in which it does not keeps the kernel without them
-        if (RPT_SCENE_CONSTS && lay.fuse_query) {
-          // (as the kernel counts them: scene_consts_fill; RPT_SCENE_CONSTS is the mask of the groups that are built)
-          uint64_t light_tris = 0, cubes = 0;
-          const uint64_t mats = (RPT_SCENE_CONSTS & 1) ? (uint64_t)fs.num_objects : 0u;
-          const rptdev::Light& l0 = fs.lights[0];
-          if ((RPT_SCENE_CONSTS & 2) && l0.kind == RPT_LIGHT_OBJECT && fs.insts[l0.inst].kind == RPT_SHAPE_MESH &&
-              !fs.insts[l0.inst].has_xf)
-            light_tris = fs.trees[fs.insts[l0.inst].tree].num_prims;
-          auto xf_cube = [&](int i) { return i < fs.num_objects && fs.insts[i].kind == RPT_SHAPE_CUBE && fs.insts[i].has_xf; };
-          for (int i = 0; (RPT_SCENE_CONSTS & 4) && i < fs.num_objects;) {
-            if (xf_cube(i) && xf_cube(i + 1)) { cubes += 2; i += 2; }
-            else i++;
-          }
-          // the cubes' normals (back to front), then at off_consts the materials' constants and the light's pdfs
-          const uint64_t base = off + cubes * RPT_CUBE_NORMALS_BYTES; // (a multiple of 16, as `off` is)
-          const uint64_t end = up16(base + mats * RPT_MAT_CONSTS_BYTES + light_tris * sizeof(double));
-          if (end + RPT_PATHS_STASH_MAX_LDS <= WAVE_LDS) {
-            lay.scene_consts = 1;
-            lay.off_consts = (uint32_t)base;
-            off = end;
-          }
-        }
-        h->plane_vals.upload(planes, h->stream);
-        HIP_TRY(hipStreamSynchronize(h->stream)); // `planes` dies with this block
-        lay.plane_vals = h->plane_vals.p;
-        // the fused kernel's pre-trace pass skips, per wave, objects whose screen rectangle holds none of its pending
-        // pixels (kernels/paths_flat.inc cull_skip_mask; the rectangles are the render's: api_render.cpp).  Never skipped: the
-        // plane table's users (their slab run is cheap) and what the object filter exempts (host_scene.cpp
-        // fill_object_boxes: unbounded, not finite, sliver meshes, ill-conditioned placements)
-        if (RPT_PRETRACE_CULL && lay.fuse_query && fs.obj_filter_ok) {
-          const uint64_t every = fs.num_objects >= 64 ? ~0ull : (1ull << fs.num_objects) - 1ull;
-          lay.cull_always = (fs.obj_always | plane_users(fs.insts, (size_t)fs.num_objects)) & every;
-          lay.pretrace_cull = 1;
-        }
-      }
-      // many small objects and no plane table (a room of polygons rather than C2's five walls): the object filter
-      // (host_scene.cpp fill_object_boxes).  RPTGPU_OBJECT_FILTER_MIN: from how many objects (0 = never).  Measured:
-      // 2 objects -5..-11 % (C1, glass spheres), 5 objects +8 % (basic.rs), 6 objects +4 % (spheres.rs), 29 objects +40 %
-      {
-        const int min_objects = opt.object_filter_min;
-        const uint64_t every = fs.num_objects >= 64 ? ~0ull : (1ull << fs.num_objects) - 1ull;
-        if (!lay.plane_cnt && min_objects > 0 && fs.num_objects >= min_objects && fs.obj_filter_ok &&
-            (fs.obj_always & every) != every) {
-          // rpt_paths<KdFlatF> reads triangles from global memory (no plane table here, so `off` is final)
-          const FlatLayout keep = lay;
-          const uint64_t keep_off = off;
-          if (lay.n_tris) assign(false);
-          const uint64_t with_boxes = up16(off + (uint64_t)fs.num_objects * 6 * sizeof(double));
-          if (with_boxes <= WAVE_LDS) {
-            lay.obj_filter = 1;
-            lay.obj_always = fs.obj_always & every;
-            lay.off_obox = (uint32_t)off; off = with_boxes;
-            h->obj_box.upload(fs.obj_lbox, h->stream);
-            std::vector<double> grid(fs.obj_grid, fs.obj_grid + 12);
-            h->obj_grid.upload(grid, h->stream);
-            HIP_TRY(hipStreamSynchronize(h->stream)); // `grid` dies with this block
-            lay.obj_box = h->obj_box.p;
-            lay.obj_grid = h->obj_grid.p;
-          } else {
-            lay = keep;
-            off = keep_off;
-          }
-        }
-      }
-      lay.off_end = (uint32_t)off;
-      if (off > WAVE_LDS) {
-        h->all_flat = false;
-      } else {
-        h->flat_layout = lay;
-      }
-    }
     lap("pipeline choice, flat layout");
     h->ext_shapes = fs.nested_mesh;
     for (const rptdev::Inst& in : fs.insts) h->ext_shapes = h->ext_shapes || in.kind == RPT_SHAPE_MONOMIAL;
@@ -446,6 +276,7 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
       if (fs.insts[i].kind == RPT_SHAPE_MESH || fs.insts[i].kind == RPT_SHAPE_GROUP) h->tree_shared[fs.insts[i].tree] = 1;
     for (const rptdev::Inst& in : fs.insts) h->inst_sig.push_back((uint8_t)((in.kind & 0x7f) | (in.has_xf ? 0x80 : 0))); // (rptgpu_scene_set_group, api_group.cpp)
     h->n_insts = fs.insts.size(); h->n_nodes = fs.nodes.size(); h->n_refs = fs.refs.size(); h->n_tris = fs.tris.size();
+    // ---- upload: the scene and the plan's tables, then the one synchronisation
     h->insts.upload(fs.insts, h->stream);
     h->trees.upload(fs.trees, h->stream);
     h->nodes.upload(fs.nodes, h->stream);
@@ -456,8 +287,17 @@ int rptgpu_scene_create_opts(const RptScene* scene, int device, const RptSceneOp
     h->materials.upload(fs.materials, h->stream);
     h->lights.upload(fs.lights, h->stream);
     h->env_texels.upload(fs.env_texels, h->stream);
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    const std::vector<double> planes(flat.planes, flat.planes + 12), grid(fs.obj_grid, fs.obj_grid + 12);
+    if (flat.lay.plane_cnt) h->plane_vals.upload(planes, h->stream);
+    if (flat.upload_filter) { h->obj_box.upload(fs.obj_lbox, h->stream); h->obj_grid.upload(grid, h->stream); }
+    HIP_TRY(hipStreamSynchronize(h->stream)); // (every source above lives until here)
     lap("device allocation + upload");
+    // ---- the device's view: the flat layout's pointers, dscene
+    if (h->all_flat) {
+      h->flat_layout = flat.lay;
+      h->flat_layout.plane_vals = flat.lay.plane_cnt ? h->plane_vals.p : nullptr;
+      if (flat.upload_filter) { h->flat_layout.obj_box = h->obj_box.p; h->flat_layout.obj_grid = h->obj_grid.p; }
+    }
     rptdev::Scene& d = h->dscene;
     d.insts = h->insts.p; d.trees = h->trees.p; d.nodes = h->nodes.p; d.refs = h->refs.p; d.tris = h->tris.p; d.lrec = h->trix.p; d.lbox = h->lbox.p;
     d.materials = h->materials.p; d.lights = h->lights.p; d.env_texels = h->env_texels.p;
@@ -496,8 +336,7 @@ void rptgpu_scene_destroy(rptgpu_scene* h) { delete h; }
 namespace {
 // the checks both calls make before reading an entry; nullptr when they pass
 const char* update_refusal(const rptgpu_scene* h, uint64_t n, const uint32_t* index, const void* entries) {
-  if (h->abandoned)
-    return "an aborted batch's device work never drained on this handle: it takes no update (destroy it)";
+  if (h->abandoned) return ABANDONED_TAKES_NO_UPDATE;
   if (n && (!index || !entries)) return "null index or entry array";
   return nullptr;
 }
@@ -547,14 +386,11 @@ void commit_update(rptgpu_scene* h, std::vector<rptdev::Inst>& insts, std::vecto
   h->top_insts.swap(insts);
   if (mats) {
     h->host_materials.swap(*mats);
-    if (filter) { // (the filter's LDS layout does not depend on the boxes: only the exemptions change)
-      const size_t n = h->obj_geom.size();
-      h->flat_layout.obj_always = ob.obj_always & (n >= 64 ? ~0ull : (1ull << n) - 1ull);
-    }
-    if (cull) { // (the rectangles themselves are made per render from top_insts: api_render.cpp)
-      const size_t n = h->obj_geom.size();
-      h->flat_layout.cull_always = (ob.obj_always | plane_users(h->top_insts, n)) & (n >= 64 ? ~0ull : (1ull << n) - 1ull);
-    }
+    const size_t n = h->obj_geom.size();
+    // (the filter's LDS layout does not depend on the boxes: only the exemptions change)
+    if (filter) h->flat_layout.obj_always = ob.obj_always & rptscene::every_object(n);
+    if (cull) // (the rectangles themselves are made per render from top_insts: api_render.cpp)
+      h->flat_layout.cull_always = rptscene::cull_always(ob.obj_always, rptscene::plane_users(n, [&](size_t i) { return h->top_insts[i].plane_use; }), n);
     if (ob.scene_bounds_ok) std::memcpy(h->scene_bounds, ob.scene_bounds, sizeof h->scene_bounds);
   }
   if (lights) {

@@ -95,7 +95,7 @@ struct alignas(16) Tree {
   uint64_t sample_zone; // rand 0.8 UniformInt zone for Uniform::from(0..num_prims): u64::MAX - (2^64 - n) % n,
                         // precomputed because a 64-bit modulo costs ~200 device instructions per light sample
   uint32_t mesh_kids;   // GROUP: some child is a MESH (a kd-tree of kd-trees): such an object is walked by the per-tree
-                        // kernels whatever its own depth (api_scene.cpp)
+                        // kernels whatever its own depth (scene_plan.h route_object)
   uint32_t generic_only; // the tree of a top-level object that only rpt_tree_generic walks (a group among a group's
                         // children, mesh children rpt_nest_trace does not take): rpt_tree_enter hands it every ray.
                         // (A tree deeper than KD_MAX_STACK is NOT one: rpt_tree_trace takes it, with the levels

@@ -386,7 +386,7 @@ struct Flattener {
   int add_tree(const std::vector<Box>& boxes, uint32_t prim_base) {
     KdBuild kb;
     if (build_kd(boxes, build, kb)) fs.trees_built_on_device++;
-    // (a tree deeper than KD_MAX_STACK is no error: the object it belongs to is walked by rpt_tree_generic, api_scene.cpp)
+    // (a tree deeper than KD_MAX_STACK is no error: the object it belongs to is walked by the per-tree kernels, scene_plan.h route_object)
     fs.max_tree_depth = std::max(fs.max_tree_depth, kb.max_depth);
     rptdev::Tree t;
     std::memset(&t, 0, sizeof(t));

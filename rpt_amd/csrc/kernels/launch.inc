@@ -153,12 +153,12 @@ void launch_query(hipStream_t st, const Scene& sc, const PathState& ps, const ui
   int i = 0;
   while (i < num_objects) {
     if (obj_deep[i]) {
-      // a tree larger than the L2s: sort its rays first (bit 3: its closest-hit rays only, api_scene.cpp) — unless the query
+      // a tree larger than the L2s: sort its rays first (RPT_DEEP_SORT_CLOSEST: its closest-hit rays only, scene_plan.h route_object) — unless the query
       // is small: below ~10^6 rays rocPRIM sorts by merging, a dozen launches of 5 us each for a traversal of well
       // under a millisecond (the late depths of a long path: 42 of the wine glass's 68 sorts per step).  The default
       // threshold is 2^19 rays: with the queries sized for the rays there are (round 5), 2^20 left the 100k-triangle
       // mesh's mid-size shadow queries unsorted (215.9 -> 218.0 Msamples/s at 2^19; the 16k-triangle glass does not care)
-      const SortBufs* sort = (obj_deep[i] & 3) == 2 && !(shadow && (obj_deep[i] & 8)) && n >= qt->sort_min_rays ? sb : nullptr;
+      const SortBufs* sort = (obj_deep[i] & RPT_DEEP_ROUTE) == RPT_DEEP_SORTED && !(shadow && (obj_deep[i] & RPT_DEEP_SORT_CLOSEST)) && n >= qt->sort_min_rays ? sb : nullptr;
       uint32_t* keys = sort ? sort->keys_in : nullptr;
       uint32_t* enter_q = sort ? sort->vals_in : tq; // tree_enter fills (keys_in, vals_in), the sort fills tq
       mark(RPT_K_TREE_SORT, 0);
@@ -172,7 +172,7 @@ void launch_query(hipStream_t st, const Scene& sc, const PathState& ps, const ui
       // rays with a zero direction component: the tree's second queue and a launch of the ZEROS form where the scene
       // makes them common, else the general form's queue (kernels/tree_trace.inc, rpt_tree_trace).  A kd-tree of kd-trees
       // (rpt_nest_trace) takes them in its own loop, whose node step is the general compact one.
-      const bool nest = (obj_tris[i] & 15) == 2 && !sc.force_general; // (api_scene.cpp: which objects qualify; extended-shape builds only)
+      const bool nest = (obj_tris[i] & RPT_TRACE_KIND) == RPT_TRACE_NEST && !sc.force_general; // (scene_plan.h route_object: which objects qualify; extended-shape builds only)
       const bool zeros_launch = spill->zeros_common || nest;
       const uint32_t ztg = zeros_launch ? 0u : 1u;
       if (shadow) hipLaunchKernelGGL(rpt_tree_enter<true>, grid_push(n), dim3(PUSH_BLOCK), 0, st, sc, rb, queue, n, i, enter_q, ctr, keys, zq, ctr + 2, fq, ctr + 4, spill->rays, ztg);
@@ -188,8 +188,8 @@ void launch_query(hipStream_t st, const Scene& sc, const PathState& ps, const ui
       mark(RPT_K_TREE_SORT, 1);
       mark(RPT_K_TREE_TRACE, 0);
       dim3 tg(trace_blocks / 4 * RPT_TT_WAVES);
-      if ((obj_tris[i] & 15) == 3) { // an object only rpt_tree_generic walks: rpt_tree_enter handed it every ray (fq)
-      } else if ((obj_tris[i] & 15) == 1) {
+      if ((obj_tris[i] & RPT_TRACE_KIND) == RPT_TRACE_GENERIC) { // an object only rpt_tree_generic walks: rpt_tree_enter handed it every ray (fq)
+      } else if ((obj_tris[i] & RPT_TRACE_KIND) == RPT_TRACE_MESH) {
         if (shadow) hipLaunchKernelGGL((rpt_tree_trace<true, true, false>), tg, b, 0, st, sc, rb, i, queue, tq, ctr, ctr + 1, nullptr, nullptr, *spill);
         else hipLaunchKernelGGL((rpt_tree_trace<true, false, false>), tg, b, 0, st, sc, rb, i, queue, tq, ctr, ctr + 1, nullptr, nullptr, *spill);
 #ifdef RPT_EXT_SHAPES
@@ -201,8 +201,8 @@ void launch_query(hipStream_t st, const Scene& sc, const PathState& ps, const ui
         if (shadow) hipLaunchKernelGGL((rpt_tree_trace<false, true, false>), tg, b, 0, st, sc, rb, i, queue, tq, ctr, ctr + 1, nullptr, nullptr, *spill);
         else hipLaunchKernelGGL((rpt_tree_trace<false, false, false>), tg, b, 0, st, sc, rb, i, queue, tq, ctr, ctr + 1, nullptr, nullptr, *spill);
       }
-      if (zeros_launch && !nest && (obj_tris[i] & 15) != 3) {
-        if ((obj_tris[i] & 15) == 1) {
+      if (zeros_launch && !nest && (obj_tris[i] & RPT_TRACE_KIND) != RPT_TRACE_GENERIC) {
+        if ((obj_tris[i] & RPT_TRACE_KIND) == RPT_TRACE_MESH) {
           if (shadow) hipLaunchKernelGGL((rpt_tree_trace<true, true, true>), tg, b, 0, st, sc, rb, i, queue, zq, ctr + 2, ctr + 3, fq, ctr + 4, *spill);
           else hipLaunchKernelGGL((rpt_tree_trace<true, false, true>), tg, b, 0, st, sc, rb, i, queue, zq, ctr + 2, ctr + 3, fq, ctr + 4, *spill);
         } else {
@@ -211,9 +211,9 @@ void launch_query(hipStream_t st, const Scene& sc, const PathState& ps, const ui
         }
       }
       {
-        // a handful of rays (0/0 splits) unless ALL the object's rays come here (obj_deep bit 2: an irregular tree, an
+        // a handful of rays (0/0 splits) unless ALL the object's rays come here (RPT_DEEP_ALL_GENERIC: an irregular tree, an
         // object only rpt_tree_generic is built for) or the general form is forced
-        const dim3 gg(((obj_deep[i] & 4) || sc.force_general) ? spill->gen_blocks_all : spill->gen_blocks_few);
+        const dim3 gg(((obj_deep[i] & RPT_DEEP_ALL_GENERIC) || sc.force_general) ? spill->gen_blocks_all : spill->gen_blocks_few);
         if (shadow) hipLaunchKernelGGL(rpt_tree_generic<true>, gg, b, 0, st, sc, rb, i, fq, ctr + 4, spill->gen, spill->gen_overflow, ctr_next);
         else hipLaunchKernelGGL(rpt_tree_generic<false>, gg, b, 0, st, sc, rb, i, fq, ctr + 4, spill->gen, spill->gen_overflow, ctr_next);
       }
@@ -221,8 +221,8 @@ void launch_query(hipStream_t st, const Scene& sc, const PathState& ps, const ui
       i++;
     } else {
       int j = i;
-      bool flat_run = !sc.force_general; // every object of the run is a primitive or a one-leaf tree (obj_tris bit 4)
-      while (j < num_objects && !obj_deep[j]) { flat_run = flat_run && (obj_tris[j] & 16) != 0; j++; }
+      bool flat_run = !sc.force_general; // every object of the run is a primitive or a one-leaf tree (RPT_TRIS_ONE_LEAF)
+      while (j < num_objects && !obj_deep[j]) { flat_run = flat_run && (obj_tris[j] & RPT_TRIS_ONE_LEAF) != 0; j++; }
       if (flat_run) {
         if (shadow) hipLaunchKernelGGL((rpt_rays_objects<true, KdFlat>), g, b, 0, st, sc, rb, queue, n, i, j);
         else hipLaunchKernelGGL((rpt_rays_objects<false, KdFlat>), g, b, 0, st, sc, rb, queue, n, i, j);

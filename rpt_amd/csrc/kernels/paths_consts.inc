@@ -6,7 +6,7 @@
 // entries and per-object materials (every tree has fewer than 16 primitives), read with ds_read at LDS
 // latency instead of through L1/L2, which the clamp records keep flushing — and, in what is left of the
 // wave's 20 KB stays free (rounds 2-3 kept clamp records there; the fold walker's records live in global memory).
-// (the layout of the wave's dynamic LDS, FlatLayout, is computed on the host: kernels.h, api_scene.cpp)
+// (the layout of the wave's dynamic LDS, FlatLayout, is computed on the host: flat_layout.h, scene_plan.h plan_flat)
 struct FlatLds {
   const TriX* lrec;
   const Tri* tris;

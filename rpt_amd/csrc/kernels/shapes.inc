@@ -486,7 +486,7 @@ struct KdNoLds;
 // the leaf stops at the first such hit — every accept decision up to that point is the reference's.
 // A GROUP leaf here holds placed spheres, cubes and monomial surfaces only: an object whose group has TREE children (a
 // mesh or another group, to any depth) never reaches these kernels — the per-tree pipeline walks it with rpt_nest_trace
-// or rpt_tree_generic (kernels/tree_trace.inc, tree_generic.inc; api_scene.cpp routes by Tree::tree_kids).
+// or rpt_tree_generic (kernels/tree_trace.inc, tree_generic.inc; scene_plan.h route_object routes by FlatScene::tree_kids).
 template <bool TRIS, bool SHADOW, bool DIVB = false /* tri_batch's */, class TreeT>
 RPT_DEV bool kd_leaf(const Scene& sc, const TreeT& tr, const uint32_t* __restrict__ refs, KdNode n, D3 o, D3 d,
                      double t_min, double t_stop, double& rt, D3& rn, const BoxRay* br = nullptr) {

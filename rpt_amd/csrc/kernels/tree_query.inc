@@ -90,8 +90,8 @@ template <bool SHADOW> RPT_DEV void hit_epilogue(const RayBatch& rb, CInst& in, 
 // objects [begin, end) that need no persistent traversal: primitives and shallow trees
 // LDS = KdFlat: the build for runs in which every object is a primitive or a tree of ONE leaf (a polygon()'s quad, a
 // small group) — no traversal code, hence no LDS stack, no scratch and half the registers: the kernel streams ~100 B per
-// ray and, with eight waves per SIMD instead of three, does so nearer the memory's speed (api_scene.cpp marks such objects:
-// obj_tris bit 4).  The table under the wine glass and the plane under the 100k-triangle mesh are such runs.
+// ray and, with eight waves per SIMD instead of three, does so nearer the memory's speed (scene_plan.h route_object marks such objects:
+// RPT_TRIS_ONE_LEAF of obj_tris).  The table under the wine glass and the plane under the 100k-triangle mesh are such runs.
 template <bool SHADOW, class LDS>
 __global__ void __launch_bounds__(256, (std::is_same<LDS, KdFlat>::value ? 1 : RPT_WF_WAVES)) rpt_rays_objects(Scene sc, RayBatch rb, const uint32_t* __restrict__ queue,
                                                                       uint32_t n, int begin, int end) {

@@ -385,7 +385,7 @@ __global__ void __launch_bounds__(256, RPT_TT_WAVES) rpt_tree_trace(Scene sc, Ra
 // runs through this kernel too; a 0/0 split sends the ray to rpt_tree_generic, which starts it over.  No calls, hence no
 // call frames in scratch (the nested form's chain of out-of-line traversals needs 14 KB per lane): the host sends an
 // object here only when its tree and all its mesh children's trees are regular, none of its children is a group, and
-// the two levels' depths fit one stack (api_scene.cpp); otherwise, and under RPT_FLAG_GENERAL_TRAVERSAL, rpt_tree_trace<false>.
+// the two levels' depths fit one stack (scene_plan.h route_object); otherwise, and under RPT_FLAG_GENERAL_TRAVERSAL, rpt_tree_trace<false>.
 struct NestTree {
   uint32_t ref_base, prim_base; // what kd_leaf reads of a mesh tree
 };

@@ -1,5 +1,6 @@
-// tree_splice.h — the spare-set storage of the live updates that rebuild ONE tree of a handle (api_mesh.cpp: a deformed
-// mesh; api_group.cpp: a group's moved children), one copy for both.
+// tree_splice.h — what the live updates that rebuild ONE tree of a handle share (api_mesh.cpp: a deformed mesh;
+// api_group.cpp: a group's moved children), one copy for both: the refusals they make first, the lap timer, the tree's
+// rebuild from its primitives' boxes, the spare-set storage, the swap and the re-route (scene_plan.h).
 //
 // insts, trees, nodes, refs, tris, lrec and lbox exist twice on a handle that has been updated: the set the kernels read
 // and a spare.  An update writes the WHOLE new scene into the spare — the other trees' nodes, entries and records copied
@@ -9,8 +10,118 @@
 // by an eighth beyond need when it must grow) for the next update.
 #pragma once
 #include "api_internal.h"
+#include "mesh_records.h"
+#include "scene_plan.h"
 
 namespace rptapi {
+
+// ---- the frame of a rebuild
+
+// the words in which the two calls' shared refusals differ
+struct RebuildWords {
+  int32_t kind;           // RPT_SHAPE_MESH / RPT_SHAPE_GROUP
+  const char* a_kind;     // "a mesh"
+  const char* counted;    // "triangle": what n counts
+  const char* count_rule; // why n may not change
+  const char* rebuilt;    // "deformed": the new tree, in the depth refusal
+};
+struct RebuildTarget {
+  size_t count = 0, t = 0; // top-level objects; the object's tree
+  rptdev::Tree old{};      // that tree's record
+  std::string obj;         // "object <index>"
+};
+// The refusals both calls make first, in this order: a null handle, an abandoned one, the object's index, its kind, n
+// against the count at creation.  -> RPTGPU_OK and `tg`, or the failure's code
+inline int rebuild_target(rptgpu_scene* h, uint32_t object, uint64_t n, const RebuildWords& w, const std::string& fn, RebuildTarget& tg) {
+  if (!h) return fail(nullptr, RPTGPU_E_INVALID_ARGUMENT, fn + "null handle");
+  if (h->abandoned) return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + ABANDONED_TAKES_NO_UPDATE);
+  tg.count = h->obj_geom.size();
+  tg.obj = "object " + std::to_string(object);
+  if (object >= tg.count)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + tg.obj + " is out of range (the scene has " + std::to_string(tg.count) + ")");
+  const rptdev::Inst& was = h->top_insts[object];
+  if (was.kind != w.kind)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + tg.obj + " is not " + w.a_kind + " (shape kind " + std::to_string(was.kind) + ")");
+  tg.t = (size_t)was.tree;
+  tg.old = h->host_trees[tg.t];
+  if (n != tg.old.num_prims)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + "n = " + std::to_string(n) + " differs from the " + w.counted + " count of " + tg.obj +
+                                                 " at creation (" + std::to_string(tg.old.num_prims) + "): " + w.count_rule);
+  return RPTGPU_OK;
+}
+// ... and last, behind their own checks of the input: a handle whose scene the flat path kernel walks
+inline int refuse_all_flat(rptgpu_scene* h, const std::string& fn, const RebuildTarget& tg) {
+  if (!h->all_flat) return RPTGPU_OK;
+  return fail(h, RPTGPU_E_INVALID_ARGUMENT, fn + tg.obj + " is walked inside the flat path kernel, whose LDS layout and plane table are "
+                                               "derived from the coordinates at creation: this needs a new handle");
+}
+
+// RPTGPU_PRINT_UPDATE=1: where the hand-off's time goes (stderr; adds synchronisations)
+struct UpdateLap {
+  hipStream_t st;
+  const char* call; // "scene_set_mesh"
+  bool print = std::getenv("RPTGPU_PRINT_UPDATE") != nullptr;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  void operator()(const char* what) {
+    if (!print) return;
+    HIP_TRY(hipStreamSynchronize(st));
+    auto t1 = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "%s %-28s %8.3f ms\n", call, what, std::chrono::duration<double, std::milli>(t1 - t0).count());
+    t0 = t1;
+  }
+};
+
+// The tree over the n boxes in h->mesh_boxes (made on the handle's stream): the 48-byte boxes come to the host, where both
+// builders take them (kdbuild.hip numbers its nodes on the host as well) — the builder scene creation would use, by
+// h->opt — and the bounds are folded in index order as KdTree::new folds them.  flag (may be null): receives
+// h->mesh_flag[0] with the same synchronisation.  tr: `old` with what creation derives from a built tree, its leaf grid
+// included
+struct RebuiltTree {
+  rpthost::KdBuild kb;
+  rptdev::Tree tr{};
+  uint32_t depth = 0;
+};
+inline void rebuild_tree(rptgpu_scene* h, uint64_t n, const rptdev::Tree& old, uint32_t* flag, UpdateLap& lap, RebuiltTree& out) {
+  const hipStream_t st = h->stream;
+  std::vector<rpthost::Box> boxes(n);
+  HIP_TRY(hipMemcpyAsync(boxes.data(), h->mesh_boxes.p, n * sizeof(rpthost::Box), hipMemcpyDeviceToHost, st));
+  if (flag) HIP_TRY(hipMemcpyAsync(flag, h->mesh_flag.p, sizeof *flag, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  lap("boxes to the host");
+  rpthost::BuildOptions bopt;
+  bopt.device_build_min = (size_t)h->opt.device_build_min;
+  bopt.build_threads = (int)h->opt.build_threads;
+  if (bopt.device_build_min) bopt.device = h->device;
+  rpthost::build_kd(boxes, &bopt, out.kb);
+  HIP_TRY(hipSetDevice(h->device));
+  out.tr = old;
+  rpthost::derive_tree(out.kb, boxes, out.tr);
+  rptrec::grid_over(out.tr.bounds, out.tr.qlo, out.tr.qscale);
+  out.depth = out.kb.max_depth;
+  lap("kd build");
+}
+// the tree's leaf grid as the record kernels take it (rptmesh::LeafGrid, rptgroup::LeafGrid: the kernels' symbols carry
+// the type's name, so each keeps its own)
+template <class Grid> Grid leaf_grid(const rptdev::Tree& tr) {
+  Grid g;
+  std::memcpy(g.qlo, tr.qlo, sizeof g.qlo);
+  std::memcpy(g.qscale, tr.qscale, sizeof g.qscale);
+  return g;
+}
+// An object the handle walks inside the path kernels keeps that route (scene_plan.h rebuilt_too_deep); "" when object i
+// may take the tree
+inline std::string depth_refusal(const rptgpu_scene* h, size_t i, uint32_t depth, const RebuildWords& w) {
+  if (!rptscene::rebuilt_too_deep(h->obj_deep[i], depth, h->opt.fast_max_depth)) return "";
+  return std::string("the ") + w.rebuilt + " tree is " + std::to_string(depth) + " levels deep and object " + std::to_string(i) +
+         " is walked inside the path kernels, whose stacks hold " + std::to_string(h->opt.fast_max_depth) + ": this needs a new handle";
+}
+// object i's copy of its tree's bounds (Inst::bounds copies Tree::bounds) and its local box
+inline void set_object_bounds(rptdev::Inst& in, rpthost::ObjectGeom& g, const rptdev::Tree& tr) {
+  std::memcpy(in.bounds, tr.bounds, sizeof tr.bounds);
+  for (int k = 0; k < 3; k++) { g.local.lo[k] = tr.bounds[k]; g.local.hi[k] = tr.bounds[3 + k]; }
+}
+
+// ---- the spare set
 
 // dst[0, at) = src[0, at); dst[at + new_len, ...) = src[at + old_len, total): the arrays of the other trees around the
 // updated tree's region, device to device
@@ -101,18 +212,14 @@ inline void swap_spare(rptgpu_scene* h, const TreeSplice& sp, std::vector<rptdev
   if (depth + 1u > h->gen_levels) { h->gen_levels = depth + 1u; h->gen_threads = 0; h->ws_stale = true; } // rpt_tree_generic's
 }
 
-// What the routing took from object i's tree at creation (api_scene.cpp), after the swap.  A per-tree object: the
-// all-generic bit of obj_deep follows `regular` (gen_all sizes a grid and only grows), and a tree beyond fast_max_depth
-// is for the per-tree pipeline only.  An object walked inside the path kernels: the single-leaf bit of obj_tris follows
-// root_leaf (the lean build of rpt_rays_objects takes single leaves only)
+// What the routing took from object i's tree at creation, after the swap: scene_plan.h reroute_object into the handle
+// (a flag that rises makes the workspace stale where it sizes a grid)
 inline void reroute_object(rptgpu_scene* h, size_t i, const rptdev::Tree& tr, uint32_t depth) {
-  if (h->obj_deep[i]) {
-    h->obj_deep[i] = (uint8_t)((h->obj_deep[i] & ~4) | (tr.regular ? 0 : 4)); // an irregular tree: every ray through rpt_tree_generic
-    if (!tr.regular && !h->gen_all) { h->gen_all = true; h->ws_stale = true; }
-    if (depth > h->opt.fast_max_depth) { h->tree_kids = true; h->prefer_wavefront = true; } // only the per-tree pipeline walks it
-  } else {
-    h->obj_tris[i] = (uint8_t)((h->obj_tris[i] & ~16) | (tr.root_leaf ? 16 : 0));
-  }
+  const rptscene::Reroute r = rptscene::reroute_object(h->obj_deep[i], h->obj_tris[i], tr.regular != 0, tr.root_leaf != 0, depth, h->opt.fast_max_depth);
+  h->obj_deep[i] = r.deep;
+  h->obj_tris[i] = r.tris;
+  if (r.gen_all && !h->gen_all) { h->gen_all = true; h->ws_stale = true; }
+  if (r.tree_kids) { h->tree_kids = true; h->prefer_wavefront = true; }
 }
 
 } // namespace rptapi
