@@ -2,8 +2,9 @@
 kernels/shapes.inc leaf_box_pass / boxray_make) restated in numpy, and their one obligation checked on millions of
 (ray, triangle) pairs: **whenever the exact test of mesh.rs:49-82 accepts, the filter passes** — for the widest window
 and for windows that barely contain the hit — including rays that graze edges and vertices, rays almost parallel to
-an axis, triangles at the corners of the grid, slivers, and origins far from the mesh.  (That the DEVICE code is this
-filter is what the bit-exact GPU parity tests show: a filter that dropped an accepted hit would change an image.)"""
+an axis, triangles at the corners of the grid, slivers, and origins far from the mesh.  The DEVICE code — with its
+fmaf, its batches of 32 entries and its five call sites — is tested on the same kinds of rays (tests/leaf_box_rays.py)
+against the oracle in tests/test_gpu_leaf_boxes.py."""
 import numpy as np
 
 from rpt_amd import scenes
@@ -176,6 +177,77 @@ def test_filter_with_axis_parallel_rays_far_origins_and_corner_triangles():
     o = p - d * far
     on, _ = check(tris, o, d, lo, hi, "far origins")
     assert 0.2 < on < 0.95, on   # (the thin axis of these bounds reaches 10^12 of ITS steps first)
+
+
+def _far_population():
+    import leaf_box_rays
+    tris, o, d, u, lo, hi = leaf_box_rays.far_pairs()
+    q, scale, glo, full = quantise(tris, lo, hi)
+    acc, time = exact_hit(tris, o, d)
+    return leaf_box_rays.FAR_BANDS, q, scale, glo, o, d, u, acc, time
+
+
+def _lost(q, scale, glo, o, d, acc, time, far):
+    """accepted hits the filter rejects, over the windows of `check` -> (lost (n,) bool, on (n,) bool)"""
+    lost = np.zeros(len(acc), dtype=bool)
+    for t_lo, t_hi in ((1e-12, np.inf), (time, time), (np.nextafter(time, -np.inf), np.nextafter(time, np.inf))):
+        ok, on = box_pass(q, scale, glo, o, d, t_lo, t_hi, far=far)
+        lost |= acc & ~ok
+    return lost, on
+
+
+def test_far_origins_up_to_1e16_extents_lose_no_hit_and_switch_the_filter_off():
+    # 2 304 triangles x 60 interior-aimed rays from 10^u extents away, u uniform in [0, 16]
+    bands, q, scale, glo, o, d, u, acc, time = _far_population()
+    lost, on = _lost(q, scale, glo, o, d, acc, time, 1e12)
+    for a, b in bands:
+        sel = (u >= a) & (u < b)
+        assert acc[sel].mean() >= 0.05, (a, b, acc[sel].mean())       # the band can lose something
+        assert not lost[sel].any(), (a, b, int(lost[sel].sum()), np.flatnonzero(lost & sel)[:5])
+    # boxray_make's FAR guard: an origin 1e12 grid steps or more from the grid's corner, on any axis, switches it off
+    steps = np.abs(glo - o) / scale
+    beyond = (steps >= 1e12).any(axis=1)
+    assert beyond.sum() > 10000 and not on[beyond].any()
+    assert on[(steps < 1e11).all(axis=1)].mean() > 0.95
+
+
+def test_without_the_far_guard_the_filter_loses_hits_from_beyond_1e12_extents():
+    # the same population with the guard removed (far = 1e300): what the f64 subtraction `u - t0` cancels is then many
+    # grid steps, and accepted hits ARE rejected — so the test above does pin the guard.  (Measured, of 138 240 pairs:
+    # 0 below 1e10 extents, 3 at 1e10 - 1e12, 777 at 1e12 - 1e14, 1 152 at 1e14 - 1e16.)
+    bands, q, scale, glo, o, d, u, acc, time = _far_population()
+    lost, _ = _lost(q, scale, glo, o, d, acc, time, 1e300)
+    counts = [int(lost[(u >= a) & (u < b)].sum()) for a, b in bands]
+    print("lost without the guard, per band:", counts)
+    assert counts[2] + counts[3] >= 100, counts
+
+
+def test_bundles_of_stacked_triangles_lose_no_hit_at_the_tightest_window():
+    # the stacks of tests/leaf_box_rays.py (gaps down to one ulp, exact duplicates, a sliver), every ray against every
+    # triangle of the bundle it is aimed at, with the window (time, time)
+    import leaf_box_rays
+    tris, o, d, lo, hi = leaf_box_rays.bundle_pairs()
+    q, scale, glo, full = quantise(tris, lo, hi)
+    acc, time = exact_hit(tris, o, d)
+    assert acc.sum() > 50000 and 0.0 < full.mean() < 0.2, (int(acc.sum()), full.mean())
+    ok, on = box_pass(q, scale, glo, o, d, time, time)
+    bad = acc & ~ok
+    assert not bad.any(), (int(bad.sum()), np.flatnonzero(bad)[:5])
+    assert on.mean() > 0.99
+    # and it filters: a bundle's rays against ANOTHER bundle's triangles
+    ok, _ = box_pass(np.roll(q, len(q) // 2, axis=0), scale, glo, o, d, 1e-12, np.inf)
+    assert ok.mean() < 0.2, ok.mean()
+
+
+def test_the_device_tests_scenes_have_the_leaves_and_children_they_are_meant_to_have():
+    # what tests/test_gpu_leaf_boxes.py relies on, from the host kd build alone: the bundles leave leaves of every size
+    # class (3-8, 9-16, 17-32, 33-64, more than 64 entries: kd_leaf_boxed's rounds of 32 and batches of 8), and the
+    # group's spheres lie on both sides of quadric_too_small's 64 grid steps
+    import leaf_box_rays
+    counts = leaf_box_rays.leaf_class_counts(leaf_box_rays.mesh_tree(leaf_box_rays.build("bundles").rows))
+    assert min(counts) >= 1, counts
+    g = leaf_box_rays.build("group")
+    assert g.small.sum() >= 20 and (~g.small).sum() >= 20 and len(g.cubes) >= 20 and len(g.small) + len(g.cubes) == 200
 
 
 def test_slivers_are_never_filtered():
