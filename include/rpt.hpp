@@ -740,6 +740,20 @@ class Renderer {
                              streams.empty() ? nullptr : streams.data(), &q, out.data()));
     return out;
   }
+  // addition: a batch of frames in one call (rptgpu_render_views, include/rpt_gpu.h), each from a view of its own — a camera
+  // under RPT_VIEW_PERSPECTIVE (this renderer's frame of that camera), RPT_VIEW_ORTHOGRAPHIC or RPT_VIEW_PANORAMA (a
+  // rendered panorama is an Hdri's texel array).  -> [views][height][width][3], the renderer's size, samples, bounces and
+  // exposure; view v renders with seed + v * seed_stride, whatever other views the call holds.
+  std::vector<double> render_views(const std::vector<RptView>& views, uint64_t seed_stride = 0, uint64_t sample_index_base = 0) {
+    ensure_scene();
+    RptViewQuery q{};
+    q.struct_size = sizeof(RptViewQuery); q.width = width_; q.height = height_; q.max_bounces = max_bounces_;
+    q.iterations = num_samples_; q.exposure_value = ev_; q.seed = seed_; q.seed_stride = seed_stride;
+    q.sample_index_base = sample_index_base;
+    std::vector<double> out(views.size() * (size_t)width_ * height_ * 3);
+    check(rptgpu_render_views(handle_, views.size(), views.data(), &q, out.data()));
+    return out;
+  }
   // addition: iterative_render with the Buffer kept on the device (rptgpu_buffer_*), followed by the feature-guided
   // a-trous filter of rptgpu_buffer_denoise (include/rpt_gpu.h) guided by the first hits of samples 0 .. feature_samples-1.
   // At least two batches (num_samples > callback_interval), else the library refuses: one batch has no variance.

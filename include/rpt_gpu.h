@@ -553,6 +553,88 @@ int rptgpu_bake_probes(rptgpu_scene* h, uint64_t n, const double* positions /* [
 int rptgpu_bake_probes_device(rptgpu_scene* h, uint64_t n, const void* d_positions, const void* d_normals,
                               const void* d_streams /* may be NULL */, const RptProbeQuery* q, void* d_out, void* stream);
 
+/* ---- batches of views: n_views frames of one size in ONE call, each from a camera of its own under one of three
+ * projections — cube-map faces, stereo pairs, turntables, light fields, data sets; orthographic views; and 360-degree
+ * panoramas in exactly Hdri::get_color's convention (environment.rs:25-52), so that a rendered panorama is a valid
+ * RptEnvironment texel array: one scene captured as the environment of another.  Additions within ABI version 7, detected
+ * by symbol (dlsym "rptgpu_render_views").  The rays are made on the device from each pixel's own Philox stream (96 + 16 B
+ * per VIEW in, 24 B per pixel out, whatever the sample count).  With seed_stride == 0 the views of a call share the
+ * launches and the host waits of the wavefront pipeline's depth loop, which a small frame on its own cannot fill; with
+ * seed_stride != 0 every view runs as a piece of its own — the per-view loop behind one call, with the same results and
+ * no such sharing.
+ * out[v][y][x][c], row-major, top row first, v in the order of `views`.
+ * THE STREAM CONTRACT.  Sample s of pixel p = y*width + x of view v draws from the Philox4x32-10 stream keyed by
+ * seed + v*seed_stride (wrapping in 64 bits) with the counter (p, sample_index_base + s, draw block), from draw 0 on; its
+ * path continues the SAME stream behind the camera's draws, as a render's does.  out[v][p] = (sum over s = 0 ..
+ * iterations-1, ascending, from +0.0, of L(v, p, s)) / iterations * 2^exposure_value, where L is Renderer::trace_ray
+ * (renderer.rs:143-175) of the ray below — rptgpu_render_batch's expressions.  A view's pixels depend on that view, the
+ * query and the scene and on nothing else: not on the other views of the call, on their order, or on the pieces and passes
+ * the library cuts the call into.
+ * THE RAY of (v, p, s), in plain f64, no contraction, the expressions in the order written; gen_range(a, b) is the
+ * reference's (rand 0.8 UniformFloat: one draw), normalize(a) = a / sqrt((a.x*a.x + a.y*a.y) + a.z*a.z) component by
+ * component, `right` = normalize(direction x up) (camera.rs:67), a sum of three terms is added left to right:
+ *   RPT_VIEW_PERSPECTIVE   exactly rptgpu_render_batch's ray (renderer.rs:132-139, camera.rs:64-81, the lens included; the
+ *                          camera's constants are made by the host function a render uses): view v is rptgpu_render_batch
+ *                          of its camera with seed + v*seed_stride, bit for bit.
+ *   RPT_VIEW_ORTHOGRAPHIC  px, py and their two gen_range draws as in the perspective case (renderer.rs:132-138; the
+ *                          integers 2*x + 1 and 2*(height - y) - 1 are formed in uint32_t as a render forms them, which
+ *                          is exact for width, height < 2^31);
+ *                          origin = eye + (px*right + py*up) * ortho_scale (the form of camera.rs:74);
+ *                          dir = normalize(direction).  px and py span [-1, 1] over the LONGER image side, so ortho_scale
+ *                          is the half-extent of that side in world units.  fov, aperture, focal_distance: not read.
+ *   RPT_VIEW_PANORAMA      world-aligned at eye: column <-> atan2(z, x) + pi over width-1, row <-> acos(y) over height-1.
+ *                          jx = gen_range(-0.5, 0.5); jy = gen_range(-0.5, 0.5);
+ *                          cx = (double)x + jx; if (cx < 0.0) cx = cx + (double)(width-1); else if (cx > (double)(width-1))
+ *                          cx = cx - (double)(width-1);          (columns 0 and width-1 are the same meridian)
+ *                          cy = fmin(fmax((double)y + jy, 0.0), (double)(height-1));
+ *                          psi = cx / (double)(width-1) - 0.5;   (the azimuth atan2(z, x) in turns)
+ *                          fabs(psi) <= 0.25:  (s, c) = rpt_sincos_pio2(6.283185307179586 * psi)
+ *                          otherwise:          (s, c) = -rpt_sincos_pio2(6.283185307179586 * (psi - copysign(0.5, psi)))
+ *                          (se, ce) = rpt_sincos_pio2((0.5 - cy / (double)(height-1)) * 3.141592653589793);
+ *                          dir = (ce*c, se, ce*s); origin = eye.  Every argument stays within rpt_sincos_pio2's
+ *                          |x| < 3 pi / 4 (include/rpt_math.h).  direction, up, fov, aperture, focal_distance: not read.
+ * The call always runs the wavefront pipeline, as rptgpu_trace_rays does, sized and restarted like a render's passes, over
+ * pieces of consecutive (view, pixel) indices (when seed_stride != 0 a piece stays within one view: a piece's passes run
+ * under one seed, so views with seeds of their own share no launch);
+ * RPT_FLAG_GENERAL_TRAVERSAL and RPT_FLAG_PROFILE_KERNELS are honoured, RPT_FLAG_WAVEFRONT changes nothing, and RptStats
+ * advances as for a render (samples = n_views * width * height * iterations).  RPTGPU_VIEWS_PIECE (environment, read per
+ * call; tests): the indices per piece.
+ * NOT IN SCOPE: the tile partition and multi-GPU (a caller shards the VIEWS over handles: a view's pixels depend on nothing
+ * else), the device-resident Buffer, the feature buffers and the denoiser for views, and the persistent path kernel.
+ * RPTGPU_E_INVALID_ARGUMENT, checked before any device work and with a detail naming the reason: a NULL RptViewQuery, a
+ * wrong struct_size, width, height or iterations == 0, max_bounces > 254, a precision_mode other than
+ * RPT_PRECISION_F64_STRICT, RPT_FLAG_PERSISTENT, width * height > 2^32, NULL views or out with n_views > 0, frames whose
+ * size does not fit 64 bits, an unknown projection, RPT_VIEW_ORTHOGRAPHIC with an ortho_scale that is not finite or <= 0,
+ * RPT_VIEW_ORTHOGRAPHIC or RPT_VIEW_PANORAMA with aperture > 0, RPT_VIEW_PANORAMA with width < 2 or height < 2, a NULL
+ * handle; RPTGPU_E_COMM for an abandoned handle.  n_views == 0 returns RPTGPU_OK. */
+enum { RPT_VIEW_PERSPECTIVE = 0, RPT_VIEW_ORTHOGRAPHIC = 1, RPT_VIEW_PANORAMA = 2 };
+typedef struct RptView {
+  RptCamera camera;
+  uint32_t projection;        /* RPT_VIEW_* */
+  uint32_t _pad;              /* reserved: write 0; not read */
+  double ortho_scale;         /* RPT_VIEW_ORTHOGRAPHIC: half-extent of the longer image side, world units; else not read */
+} RptView;
+typedef struct RptViewQuery {
+  uint32_t struct_size;       /* sizeof(RptViewQuery) */
+  uint32_t width;             /* of every view, > 0 */
+  uint32_t height;
+  uint32_t max_bounces;       /* <= 254 */
+  uint32_t iterations;        /* samples per pixel, > 0 */
+  uint32_t _pad;              /* reserved: write 0; not read */
+  double exposure_value;
+  uint64_t seed;
+  uint64_t seed_stride;       /* view v renders with seed + v*seed_stride (0: every view with `seed`) */
+  uint64_t sample_index_base; /* index of every pixel's first sample */
+  uint32_t precision_mode;    /* RPT_PRECISION_F64_STRICT */
+  uint32_t flags;             /* as RptRayQuery: GENERAL_TRAVERSAL, PROFILE_KERNELS honoured; PERSISTENT refused */
+} RptViewQuery;
+int rptgpu_render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q,
+                        double* out /* [n_views][height][width][3], host */);
+/* The same into device memory, f64 or (out_is_f32 != 0) f32 of the same layout; `views` stays in host memory.  `stream`
+ * and the synchronisation rule are rptgpu_trace_rays_device's. */
+int rptgpu_render_views_device(rptgpu_scene* h, uint64_t n_views, const RptView* views /* host */, const RptViewQuery* q,
+                               void* d_out, int out_is_f32, void* stream);
+
 /* ---- host utility: KdTree::new (kdtree.rs:108-119, construct kdtree.rs:235-345) over n
  * axis-aligned boxes (p_min xyz, p_max xyz interleaved: 6 doubles per box).  Returns the
  * flattened tree through malloc'ed arrays the caller releases with rptgpu_free.

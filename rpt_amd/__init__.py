@@ -8,14 +8,16 @@ and rpt::ode's ParticleState, ParticleSystem, SolidGravitySystem, MarblesSystem.
 The path tracer and the particle systems are HIP (rpt_amd/csrc) behind the C ABI in include/rpt_gpu.h.
 Beyond the reference: GpuScene.trace_rays runs the path estimator along rays of the caller's own making (numpy arrays,
 or torch tensors on the device), and GpuScene.bake_probes turns positions into light probes on the device — SH9 radiance or
-surface irradiance — which sh9_basis / sh9_irradiance (numpy) evaluate.
+surface irradiance — which sh9_basis / sh9_irradiance (numpy) evaluate; GpuScene.render_views renders a batch of frames in one
+call, each from a View: a camera under a perspective, orthographic or panoramic projection (a panorama is an Hdri's texels).
 """
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401
 from ._abi import (RPT_AOV_ALBEDO, RPT_AOV_ALL, RPT_AOV_DEPTH, RPT_AOV_NORMAL, RPT_AOV_OBJECT,  # noqa: F401
-                   RPT_AOV_POSITION, RPT_PROBE_IRRADIANCE, RPT_PROBE_SH9)
+                   RPT_AOV_POSITION, RPT_PROBE_IRRADIANCE, RPT_PROBE_SH9, RPT_VIEW_ORTHOGRAPHIC, RPT_VIEW_PANORAMA,
+                   RPT_VIEW_PERSPECTIVE)
 from .buffer import Buffer, Filter  # noqa: F401
-from .camera import Camera  # noqa: F401
+from .camera import Camera, View  # noqa: F401
 from .color import color_bytes, hex_color  # noqa: F401
 from .device import DeviceBuffer, GpuScene, device_count, make_params  # noqa: F401
 from .environment import Environment, Hdri  # noqa: F401

@@ -43,6 +43,7 @@ RPT_PARTICLES_MAX_STEPS = 1 << 26
 RPT_AOV_DEPTH, RPT_AOV_NORMAL, RPT_AOV_ALBEDO, RPT_AOV_POSITION, RPT_AOV_OBJECT = 1, 2, 4, 8, 16
 RPT_AOV_ALL = 31
 RPT_PROBE_SH9, RPT_PROBE_IRRADIANCE = 0, 1
+RPT_VIEW_PERSPECTIVE, RPT_VIEW_ORTHOGRAPHIC, RPT_VIEW_PANORAMA = 0, 1, 2
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -177,6 +178,19 @@ class RptProbeQuery(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class RptView(C.Structure):
+    """include/rpt_gpu.h RptView (one view of rptgpu_render_views; detected by symbol within ABI 7)."""
+    _fields_ = [("camera", RptCamera), ("projection", C.c_uint32), ("_pad", C.c_uint32), ("ortho_scale", f64)]
+
+
+class RptViewQuery(C.Structure):
+    """include/rpt_gpu.h RptViewQuery (rptgpu_render_views' parameters; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("max_bounces", C.c_uint32),
+                ("iterations", C.c_uint32), ("_pad", C.c_uint32), ("exposure_value", f64), ("seed", C.c_uint64),
+                ("seed_stride", C.c_uint64), ("sample_index_base", C.c_uint64), ("precision_mode", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -213,6 +227,8 @@ SYMBOLS = [
     ("rptgpu_trace_rays_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptRayQuery), _VP, _VP]),
     ("rptgpu_bake_probes", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(C.c_uint32), C.POINTER(RptProbeQuery), _PD]),
     ("rptgpu_bake_probes_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptProbeQuery), _VP, _VP]),
+    ("rptgpu_render_views", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), _PD]),
+    ("rptgpu_render_views_device", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), _VP, C.c_int, _VP]),
     ("rptgpu_eval_math", C.c_int, [_VP, C.c_int, C.c_uint64, _PD, _PD, _PD]),
     ("rptgpu_kdtree_build", C.c_int, [_PD, C.c_uint64, C.POINTER(RptKdTree)]),
     ("rptgpu_kdtree_build_device", C.c_int, [_PD, C.c_uint64, C.c_int, C.POINTER(RptKdTree)]),

@@ -28,3 +28,27 @@ class Camera:
         c.eye[:], c.direction[:], c.up[:] = self.eye, self.direction, self.up
         c.fov, c.aperture, c.focal_distance = self.fov, self.aperture, self.focal_distance
         return c
+
+
+class View:
+    """One view of GpuScene.render_views (include/rpt_gpu.h RptView): a camera under a projection — RPT_VIEW_PERSPECTIVE
+    (the reference's camera, lens included), RPT_VIEW_ORTHOGRAPHIC (parallel rays along camera.direction; ortho_scale is
+    the half-extent of the longer image side in world units) or RPT_VIEW_PANORAMA (360 degrees around camera.eye,
+    world-aligned, in Hdri's texel convention)."""
+
+    def __init__(self, camera, projection=_abi.RPT_VIEW_PERSPECTIVE, ortho_scale=0.0):
+        self.camera, self.projection, self.ortho_scale = camera, int(projection), float(ortho_scale)
+
+    @staticmethod
+    def orthographic(camera, ortho_scale):
+        return View(camera, _abi.RPT_VIEW_ORTHOGRAPHIC, ortho_scale)
+
+    @staticmethod
+    def panorama(eye):
+        return View(Camera(eye=eye), _abi.RPT_VIEW_PANORAMA)
+
+    def lower(self):
+        v = _abi.RptView()
+        v.camera = self.camera.lower() if hasattr(self.camera, "lower") else self.camera
+        v.projection, v.ortho_scale = self.projection, self.ortho_scale
+        return v

@@ -17,6 +17,8 @@
 //   api_buffer.cpp   the device-resident Buffer
 //   api_rays.cpp     rptgpu_trace_rays[_device]: the wavefront pipeline over rays the caller supplies, in pieces
 //   api_probes.cpp   rptgpu_bake_probes[_device]: light probes (SH9 radiance, irradiance) through the same driver, in pieces
+//   api_views.cpp    rptgpu_render_views[_device]: batches of perspective, orthographic and panoramic views through the same
+//                    driver, in pieces of consecutive (view, pixel) indices
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -177,6 +179,7 @@ struct rptgpu_scene {
   DevBuf<double> rays_o, rays_d, rays_out; // rptgpu_trace_rays: a piece of the host caller's rays and of their results (api_rays.cpp)
   DevBuf<uint32_t> ray_ids;            // ... and the piece's stream ids (the caller's, or the rays' indices); rptgpu_bake_probes
                                        // stages a piece of probes in the same four (api_probes.cpp)
+  DevBuf<rptdev::View> view_recs;      // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<double> aov_out;              // rptgpu_render_aov: the requested channels' full-frame arrays, back to back (api_aov.cpp)
   int num_cus = 0;
   bool prefer_wavefront = false; // scene has real kd-trees: traversal-latency bound
@@ -351,6 +354,12 @@ struct RaySource {
   uint32_t* ids_out;
   int probe = -1;           // < 0: not probes
   double probe_scale = 0.0; // 4 pi / S or pi / S
+  // ... or a piece of a batch of views (rpt_raygen_views; api_views.cpp): fr.npix consecutive indices of the call from
+  // view_base on, index j = view * (view_width * view_height) + pixel; views: the call's records on the device; ids_out
+  // receives the pixels
+  const rptdev::View* views = nullptr;
+  uint32_t view_width = 0, view_height = 0;
+  uint64_t view_base = 0;
 };
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }

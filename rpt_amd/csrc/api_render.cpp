@@ -396,7 +396,8 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
 }
 
 // One pass of the wavefront pipeline over n_paths = npix x spp paths: the ray source's kernel (rpt_raygen for a camera's
-// pixels, rpt_raygen_rays for a piece of the caller's rays, rpt_raygen_probes for a piece of light probes), per depth {
+// pixels, rpt_raygen_rays for a piece of the caller's rays, rpt_raygen_probes for a piece of light probes, rpt_raygen_views
+// for a piece of a batch of views), per depth {
 // closest-hit query, rpt_shade, the visibility queries, rpt_shadow_sum }, rpt_resolve (probes: rpt_resolve_probes).  *cols: the record columns the pass used.  false: the
 // pool ran out at some depth (*cols: the columns up to and with that depth) — the pass did not resolve, and nothing of it
 // has left the workspace.
@@ -413,6 +414,7 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
   if (h->has_deep) reset_tree_counters(h);
   { Bracket b(h, RPT_K_RAYGEN, prof);
     if (src.cam) kt->raygen(st, fr, *src.cam, ps, n_paths);
+    else if (src.views) kt->raygen_views(st, fr, src.views, src.view_width, src.view_height, src.view_base, src.ids_out, ps, n_paths);
     else if (src.probe >= 0) kt->raygen_probes(st, fr, src.origins, src.dirs, (uint32_t)src.probe, src.ids_out, src.id_base, ps, n_paths);
     else kt->raygen_rays(st, fr, src.origins, src.dirs, src.first_draw, src.ids_out, src.id_base, ps, n_paths);
     b.done(); }

@@ -1,0 +1,133 @@
+// api_views.cpp — rptgpu_render_views[_device]: a batch of frames in one call, each from a camera of its own under one of
+// three projections (include/rpt_gpu.h; see api_internal.h).  The n_views x width x height pixels of the call
+// are the indices j = view * npix + pixel; they go through the wavefront driver of api_render.cpp in pieces of consecutive
+// j (rptplan::views_piece) — a piece is the "frame" of its own passes, as a piece of rptgpu_trace_rays' rays is —,
+// rpt_raygen_views makes each index's ray from its pixel's own stream (RaySource::views), and everything behind it — the
+// depth loop, the pass planning with its restarts, rpt_resolve, rpt_finish in packed form straight into `out` at j — is a
+// render's.  So the launches of a depth and its one host wait are shared by every view a piece holds.
+#include "api_internal.h"
+
+namespace rptapi {
+
+// what is wrong with an RptViewQuery (nullptr: nothing)
+const char* bad_view_query(const RptViewQuery* q) {
+  if (!q) return "null RptViewQuery";
+  if (q->struct_size != sizeof(RptViewQuery)) return "RptViewQuery: struct_size is not sizeof(RptViewQuery)";
+  if (!q->width || !q->height || !q->iterations) return "RptViewQuery: width, height and iterations must be non-zero";
+  if (q->max_bounces > 254) return "RptViewQuery: max_bounces > 254";
+  if (q->precision_mode != RPT_PRECISION_F64_STRICT) return BAD_MODE;
+  if (q->flags & RPT_FLAG_PERSISTENT)
+    return "RptViewQuery: RPT_FLAG_PERSISTENT — the persistent kernel renders one camera's frame; a batch of views runs the "
+           "wavefront pipeline only";
+  if ((uint64_t)q->width * q->height > (1ull << 32)) return "RptViewQuery: width * height > 2^32 (a pixel is a 32-bit stream id)";
+  return nullptr;
+}
+
+// what is wrong with one view of a call with query q (nullptr: nothing)
+const char* bad_view(const RptView& v, const RptViewQuery& q) {
+  switch (v.projection) {
+    case RPT_VIEW_PERSPECTIVE: return nullptr;
+    case RPT_VIEW_ORTHOGRAPHIC:
+      if (!std::isfinite(v.ortho_scale) || !(v.ortho_scale > 0.0)) return "RptView: RPT_VIEW_ORTHOGRAPHIC needs a finite ortho_scale > 0";
+      if (v.camera.aperture > 0.0) return "RptView: aperture > 0 — only RPT_VIEW_PERSPECTIVE has a lens";
+      return nullptr;
+    case RPT_VIEW_PANORAMA:
+      if (v.camera.aperture > 0.0) return "RptView: aperture > 0 — only RPT_VIEW_PERSPECTIVE has a lens";
+      if (q.width < 2 || q.height < 2) return "RptView: RPT_VIEW_PANORAMA needs width >= 2 and height >= 2";
+      return nullptr;
+    default: return "RptView: unknown projection (RPT_VIEW_PERSPECTIVE = 0, RPT_VIEW_ORTHOGRAPHIC = 1, RPT_VIEW_PANORAMA = 2)";
+  }
+}
+
+namespace {
+
+// out: host memory ([n_views][height][width][3] f64), or — on_device — device memory of f64 or f32 (user_stream: the
+// stream its producer ran on); views is host memory either way
+int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, void* out, bool on_device,
+                 bool out_f32, hipStream_t user_stream) {
+  // (the query first, then the views: both are refused whatever else is wrong, also without a handle or a device)
+  if (const char* why = bad_view_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (n_views && (!views || !out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
+  const uint64_t npix = (uint64_t)q->width * q->height;
+  if (n_views > (1ull << 58) / npix) // (3 values of 8 bytes per index: the frames' size in bytes fits 64 bits)
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "n_views * width * height does not fit: the frames would not fit any memory");
+  for (uint64_t v = 0; v < n_views; v++)
+    if (const char* why = bad_view(views[v], *q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
+  REFUSE_IF_ABANDONED(h);
+  if (!n_views) return RPTGPU_OK;
+  auto t0 = std::chrono::steady_clock::now();
+  const int rc = guarded(h, h->device, [&]() -> int {
+    struct EventPairs { // (as render_impl: a call leaves no event pair behind, however it ends)
+      rptgpu_scene* h;
+      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
+    } event_pairs{h};
+    (void)hipGetLastError();
+    hipStream_t st = h->stream;
+    const KernelTable* kt = table_for(q->precision_mode, h->ext_shapes);
+    const bool prof = (q->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
+    if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
+    h->dscene.force_general = (q->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
+    RptRenderParams p{}; // what render_wavefront reads of it
+    p.max_bounces = q->max_bounces; p.iterations = q->iterations; p.exposure_value = q->exposure_value;
+    p.seed = q->seed; p.sample_index_base = q->sample_index_base; p.precision_mode = q->precision_mode; p.flags = q->flags;
+    // the views' device records: the camera constants by the host function a render uses
+    std::vector<rptdev::View> recs(n_views);
+    for (uint64_t v = 0; v < n_views; v++) {
+      recs[v].cam = make_camera(views[v].camera);
+      recs[v].projection = views[v].projection;
+      recs[v].ortho_scale = views[v].ortho_scale;
+    }
+    h->view_recs.upload(recs, st);
+    // the piece: at most the paths one pass may hold with every level of every path (rptplan::views_piece)
+    const uint64_t n = n_views * npix;
+    rptplan::PassInput in = pass_input(h, 1, q->iterations);
+    in.remaining = q->iterations;
+    in.ratio = (double)q->max_bounces + 1.0;
+    pass_input_now(h, in);
+    uint64_t asked = 0; // tests: pieces of a few pixels
+    if (const char* e = std::getenv("RPTGPU_VIEWS_PIECE")) asked = std::strtoull(e, nullptr, 10);
+    const uint64_t piece = rptplan::views_piece(n, asked, rptplan::plan_pass(in).target);
+    const bool at_views = q->seed_stride != 0; // a piece's Frame carries one seed
+    const size_t out_elem = out_f32 ? sizeof(float) : sizeof(double);
+    h->accum.alloc(3 * piece);
+    h->ray_ids.alloc(piece);
+    if (!on_device) h->rays_out.alloc(3 * piece);
+    for (uint64_t base = 0, m; base < n; base += m) {
+      m = rptplan::views_piece_len(base, n, npix, piece, at_views);
+      void* d_out = on_device ? (void*)((char*)out + 3 * base * out_elem) : (void*)h->rays_out.p;
+      rptdev::Frame fr{};
+      fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = h->ray_ids.p;
+      fr.max_bounces = q->max_bounces; fr.seed = q->seed + (base / npix) * q->seed_stride; fr.accum = h->accum.p;
+      RaySource src{};
+      src.ids_out = h->ray_ids.p;
+      src.views = h->view_recs.p; src.view_width = q->width; src.view_height = q->height; src.view_base = base;
+      render_wavefront(h, kt, p, fr, src, d_out, out_f32, true, prof);
+      HIP_TRY(hipGetLastError());
+      if (!on_device) { // the staging array is the next piece's, too
+        HIP_TRY(hipMemcpyAsync((double*)out + 3 * base, d_out, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+    }
+    return drain_call(h, h->has_deep && h->gen_overflow.p);
+  });
+  if (rc != RPTGPU_OK) return rc;
+  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return RPTGPU_OK;
+}
+
+} // namespace
+} // namespace rptapi
+
+extern "C" {
+
+int rptgpu_render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, double* out) {
+  return render_views(h, n_views, views, q, out, false, false, nullptr);
+}
+
+int rptgpu_render_views_device(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, void* d_out,
+                               int out_is_f32, void* stream) {
+  return render_views(h, n_views, views, q, d_out, true, out_is_f32 != 0, (hipStream_t)stream);
+}
+
+} // extern "C"

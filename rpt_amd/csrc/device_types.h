@@ -149,6 +149,15 @@ struct Camera {
   double aperture, focal_distance;
 };
 
+// one view of rptgpu_render_views (kernels/wavefront.inc rpt_raygen_views): the camera record a render would get, the
+// projection (RPT_VIEW_*) and, for the orthographic one, the half-extent of the longer image side
+struct View {
+  Camera cam;
+  uint32_t projection;
+  uint32_t _pad;
+  double ortho_scale;
+};
+
 // Per-pass wavefront state, SoA over path slots (slot = s_local * npix + pixel_local).
 // REC_FIELDS doubles per depth record: A[3], f[3], 1/pdf, |wi.n|  (the nested clamp of
 // renderer.rs:162-167 is folded back-to-front by the resolve kernel, along the records' parent links).

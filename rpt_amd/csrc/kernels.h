@@ -182,6 +182,11 @@ struct KernelTable {
                         uint32_t* ids_out, uint32_t id_base, const rptdev::PathState&, uint32_t n_paths);
   void (*resolve_probes)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, uint32_t n_samples, uint32_t kind);
   void (*finish_probes)(hipStream_t, const rptdev::Frame&, uint32_t width, double scale, double* out);
+  // a batch of views (rptgpu_render_views; kernels/wavefront.inc), beside raygen / raygen_rays: the first step for the
+  // fr.npix consecutive indices j_base + i of the call, index j = view * (width * height) + pixel; views: the call's
+  // records on the device; ids_out (= fr.pixels) receives the piece's stream ids, the pixels
+  void (*raygen_views)(hipStream_t, const rptdev::Frame&, const rptdev::View* views, uint32_t width, uint32_t height,
+                       uint64_t j_base, uint32_t* ids_out, const rptdev::PathState&, uint32_t n_paths);
 };
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)

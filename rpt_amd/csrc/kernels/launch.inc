@@ -34,6 +34,10 @@ void launch_raygen_probes(hipStream_t st, const Frame& fr, const double* positio
                           uint32_t* ids_out, uint32_t id_base, const PathState& ps, uint32_t n_paths) {
   hipLaunchKernelGGL(rpt_raygen_probes, grid_for(n_paths), dim3(256), 0, st, fr, positions, normals, kind, ids_out, id_base, ps, n_paths);
 }
+void launch_raygen_views(hipStream_t st, const Frame& fr, const View* views, uint32_t width, uint32_t height, uint64_t j_base,
+                         uint32_t* ids_out, const PathState& ps, uint32_t n_paths) {
+  hipLaunchKernelGGL(rpt_raygen_views, grid_for(n_paths), dim3(256), 0, st, fr, views, width, height, j_base, ids_out, ps, n_paths);
+}
 void launch_extend(hipStream_t st, const Scene& sc, const PathState& ps, const uint32_t* queue, uint32_t n) {
   hipLaunchKernelGGL(rpt_extend, grid_for(n), dim3(256), 0, st, sc, ps, queue, n);
 }
@@ -324,5 +328,5 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_buffer_accumulate, launch_buffer_retire, launch_buffer_image, launch_buffer_variance,
                            read_prof, launch_path_reorder, launch_aov, launch_aov_fold,
                            launch_denoise_prepare, launch_denoise_level, launch_denoise_finish,
-                           launch_raygen_probes, launch_resolve_probes, launch_finish_probes};
+                           launch_raygen_probes, launch_resolve_probes, launch_finish_probes, launch_raygen_views};
 #endif // !__HIP_DEVICE_COMPILE__

@@ -1,4 +1,4 @@
-// kernels/wavefront.inc — the multi-kernel path pipeline over SoA path state (wf_state.inc): rpt_raygen / _rays / _probes,
+// kernels/wavefront.inc — the multi-kernel path pipeline over SoA path state (wf_state.inc): rpt_raygen / _rays / _probes / _views,
 // rpt_extend, rpt_shade, rpt_shadow_rays, rpt_shadow_sum, rpt_resolve / _probes, rpt_finish / _probes, rpt_path_permute.
 // Its closest-hit and visibility queries over deep trees are the per-tree kernels of tree_query / tree_trace / tree_generic.inc.
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
@@ -87,6 +87,74 @@ __global__ void __launch_bounds__(256) rpt_raygen_probes(Frame fr, const double*
   ps.draw[slot] = rng.draw;
   ps.pid[slot] = slot;
   if (ids_out && s_local == 0) ids_out[p_local] = id;
+}
+
+// The first step for a batch of views (rptgpu_render_views, include/rpt_gpu.h): slot = s_local * npix + p_local is sample
+// fr.sample_base + s_local of index j = j_base + p_local of the CALL, and j = v * (width * height) + pixel names the view and
+// its pixel.  The ray is made from the pixel's own stream (fr.seed, pixel, sample) from draw 0 on — fr.seed is the seed of
+// every view the piece touches: the host cuts pieces at view boundaries when the views' seeds differ — and the path
+// continues that stream behind the camera's draws, as rpt_raygen's does.  PERSPECTIVE is rpt_raygen's ray, expression for
+// expression; ORTHOGRAPHIC and PANORAMA are the header's.  ids_out (= fr.pixels): the first sample's lanes write the
+// stream id `pixel` where rpt_shade will look for it.
+__global__ void __launch_bounds__(256) rpt_raygen_views(Frame fr, const View* __restrict__ views, uint32_t width, uint32_t height,
+                                                        uint64_t j_base, uint32_t* __restrict__ ids_out, PathState ps, uint32_t n_paths) {
+  uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= n_paths) return;
+  uint32_t s_local = slot / fr.npix, p_local = slot - s_local * fr.npix;
+  const uint64_t npix_view = (uint64_t)width * height, j = j_base + p_local;
+  const uint64_t v = j / npix_view;
+  const uint32_t pixel = (uint32_t)(j - v * npix_view);
+  uint32_t y = pixel / width, x = pixel - y * width;
+  const View& view = views[v];
+  const Camera& cam = view.cam;
+  Rng rng = rng_make(fr.seed, pixel, fr.sample_base + s_local, 0);
+  D3 origin = ld3(cam.eye), dir;
+  if (view.projection == RPT_VIEW_PANORAMA) {
+    double jx = gen_range(rng, -0.5, 0.5);
+    double jy = gen_range(rng, -0.5, 0.5);
+    const double wm = (double)(width - 1), hm = (double)(height - 1);
+    double cx = (double)x + jx;
+    if (cx < 0.0) cx = cx + wm;
+    else if (cx > wm) cx = cx - wm;
+    double cy = (double)y + jy;
+    cy = fmin(fmax(cy, 0.0), hm);
+    // the azimuth in turns, (-1/2, 1/2]: beyond a quarter turn the angle half a turn back, and both results negated
+    const double psi = cx / wm - 0.5;
+    const bool back = fabs(psi) > 0.25;
+    double s, c, se, ce;
+    rptc_sincos_pio2(6.283185307179586 * (back ? psi - copysign(0.5, psi) : psi), &s, &c);
+    if (back) { s = -s; c = -c; }
+    rptc_sincos_pio2((0.5 - cy / hm) * 3.141592653589793, &se, &ce);
+    dir = mk(ce * c, se, ce * s);
+  } else {
+    // renderer.rs:132-138, as rpt_raygen
+    double dim = (double)max(width, height);
+    double xn = ((double)(2 * x + 1) - (double)width) / dim;
+    double yn = ((double)(2 * (height - y) - 1) - (double)height) / dim;
+    double dx = gen_range(rng, -1.0 / dim, 1.0 / dim);
+    double dy = gen_range(rng, -1.0 / dim, 1.0 / dim);
+    double px = xn + dx, py = yn + dy;
+    D3 direction = ld3(cam.direction), up = ld3(cam.up), right = ld3(cam.right);
+    if (view.projection == RPT_VIEW_ORTHOGRAPHIC) {
+      origin = origin + (px * right + py * up) * view.ortho_scale; // the form of camera.rs:74
+      dir = normalize(direction);
+    } else { // Camera::cast_ray camera.rs:64-81
+      D3 new_dir = cam.d * direction + px * right + py * up;
+      if (cam.aperture > 0.0) {
+        D3 focal_point = origin + normalize(new_dir) * cam.focal_distance;
+        double a, b;
+        unit_disc(rng, a, b);
+        origin = origin + (a * right + b * up) * cam.aperture;
+        new_dir = focal_point - origin;
+      }
+      dir = normalize(new_dir);
+    }
+  }
+  st_soa3(ps.ray, ps.cap, slot, origin);
+  st_soa3(ps.ray + 3 * ps.cap, ps.cap, slot, dir);
+  ps.draw[slot] = rng.draw;
+  ps.pid[slot] = slot;
+  if (s_local == 0) ids_out[p_local] = pixel;
 }
 
 // closest hit for every queued path.  queue == nullptr means the identity queue (depth 0).

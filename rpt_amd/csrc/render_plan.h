@@ -1,6 +1,7 @@
 // render_plan.h — how a render call is cut into launches (persistent pipeline) and passes (wavefront pipeline): the
 // arithmetic behind api_render.cpp's drivers, as pure host functions of numbers (tests/cpp/render_plan_check.cpp), and the
-// pieces rptgpu_trace_rays cuts its rays into (tests/cpp/rays_piece_check.cpp).
+// pieces rptgpu_trace_rays cuts its rays into (tests/cpp/rays_piece_check.cpp) and rptgpu_render_views its views' pixels
+// (tests/cpp/views_piece_check.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -182,5 +183,18 @@ inline uint64_t rays_piece(uint64_t n, uint64_t asked, uint64_t pass_target) {
   return std::max<uint64_t>(1, std::min(std::min<uint64_t>(n, asked ? asked : RAYS_PIECE_MAX), fit));
 }
 inline uint64_t rays_piece_count(uint64_t n, uint64_t piece) { return (n + piece - 1) / piece; }
+
+// ---- rptgpu_render_views: n_views frames of npix pixels are the n = n_views * npix indices j = view * npix + pixel of one
+// call, cut into pieces of consecutive j — the "frame" of a piece's passes, as a piece of rays is: rays_piece's bound and
+// wish (asked: RPTGPU_VIEWS_PIECE) hold as they stand (the default cap of RAYS_PIECE_MAX indices was chosen for a host caller's
+// staging; here it also decides how many views share a depth loop — DESIGN.md §15 has what a larger piece measured).  A piece's Frame carries ONE seed, so when the views' seeds differ
+// (at_views: seed_stride != 0) no piece crosses a view boundary; otherwise pieces end inside views and span them.
+inline uint64_t views_piece(uint64_t n, uint64_t asked, uint64_t pass_target) { return rays_piece(n, asked, pass_target); }
+// the length of the piece that starts at index base < n
+inline uint64_t views_piece_len(uint64_t base, uint64_t n, uint64_t npix, uint64_t piece, bool at_views) {
+  uint64_t m = std::min(piece, n - base);
+  if (at_views) m = std::min(m, npix - base % npix);
+  return m;
+}
 
 } // namespace rptplan

@@ -478,6 +478,57 @@ class GpuScene:
         _abi.check(code, self.handle)
         return out
 
+    def render_views(self, views, width, height, max_bounces, samples=1, seed=0x52505447, seed_stride=0,
+                     sample_index_base=0, exposure_value=0.0, flags=0, out=None):
+        """A batch of frames in one call (rptgpu_render_views) -> (n, height, width, 3): per pixel the mean
+        of `samples` paths of at most max_bounces bounces, times 2^exposure_value.  views: a sequence of View (a camera
+        under RPT_VIEW_PERSPECTIVE / _ORTHOGRAPHIC / _PANORAMA), Camera (perspective) or _abi.RptView.  View v renders with
+        seed + v * seed_stride, and pixel p's random numbers are those of (that seed, p, sample_index_base + s): a
+        perspective view is render_batch's frame of its camera, and no view depends on the views around it.  out: None or
+        a C-contiguous float64 numpy array (the frames go through host memory), or a contiguous float64 / float32 torch
+        tensor on the handle's device, which is written where it lies (rptgpu_render_views_device)."""
+        views = list(views)
+        n, width, height = len(views), int(width), int(height)
+        arr = (_abi.RptView * max(n, 1))()
+        for i, v in enumerate(views):
+            if isinstance(v, _abi.RptView):
+                arr[i] = v
+            elif hasattr(v, "projection"):
+                arr[i] = v.lower()
+            elif hasattr(v, "lower"):
+                arr[i].camera, arr[i].projection = v.lower(), _abi.RPT_VIEW_PERSPECTIVE
+            else:
+                raise TypeError("render_views: view %d is a %s, not a View, a Camera or an RptView" % (i, type(v).__name__))
+        q = _abi.RptViewQuery()
+        q.struct_size = C.sizeof(_abi.RptViewQuery)
+        q.width, q.height, q.max_bounces, q.iterations = width, height, int(max_bounces), int(samples)
+        q.exposure_value, q.seed, q.seed_stride = float(exposure_value), int(seed), int(seed_stride)
+        q.sample_index_base, q.precision_mode, q.flags = int(sample_index_base), _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        shape = (n, height, width, 3)
+        if hasattr(out, "data_ptr"):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype in (torch.float64, torch.float32)
+                    and tuple(out.shape) == shape and out.is_contiguous()):
+                raise ValueError("render_views: out must be a contiguous %s float64 or float32 tensor on %s" % (shape, dev))
+            # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's
+            # default stream is waited for here)
+            current = torch.cuda.current_stream(dev)
+            stream = current.cuda_stream
+            if not stream:
+                current.synchronize()
+            code = self.lib.rptgpu_render_views_device(self.handle, n, arr, C.byref(q), C.c_void_p(out.data_ptr()),
+                                                       1 if out.dtype == torch.float32 else 0, C.c_void_p(stream or 0))
+            _abi.check(code, self.handle)
+            return out
+        if out is None:
+            out = np.empty(shape, dtype=np.float64)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == shape and out.flags.c_contiguous):
+            raise ValueError("render_views: out must be a C-contiguous %s float64 array" % (shape,))
+        code = self.lib.rptgpu_render_views(self.handle, n, arr, C.byref(q), out.ctypes.data_as(C.POINTER(C.c_double)))
+        _abi.check(code, self.handle)
+        return out
+
     def render_aov(self, camera, params, channels=_abi.RPT_AOV_ALL):
         """First-hit feature buffers (rptgpu_render_aov) -> a dict of numpy arrays: `hits` (H, W) uint32
         always, and per channel of `channels` (RPT_AOV_*) the f64 SUMS over the hits of params.iterations camera rays per

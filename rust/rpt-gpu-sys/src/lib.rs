@@ -68,6 +68,9 @@ pub mod ffi {
     pub const RPT_AOV_OBJECT: u32 = 16;
     pub const RPT_PROBE_SH9: u32 = 0;
     pub const RPT_PROBE_IRRADIANCE: u32 = 1;
+    pub const RPT_VIEW_PERSPECTIVE: u32 = 0;
+    pub const RPT_VIEW_ORTHOGRAPHIC: u32 = 1;
+    pub const RPT_VIEW_PANORAMA: u32 = 2;
     pub const RPTGPU_UNIQUE_ID_BYTES: usize = 128;
 
     /// `Material` (rpt src/material.rs:8-26)
@@ -326,6 +329,34 @@ pub mod ffi {
         pub flags: u32,
     }
 
+    /// `RptView` (one view of `rptgpu_render_views`; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct RptView {
+        pub camera: RptCamera,
+        pub projection: u32,
+        pub _pad: u32,
+        pub ortho_scale: f64,
+    }
+
+    /// `RptViewQuery` (the parameters of `rptgpu_render_views`; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptViewQuery {
+        pub struct_size: u32,
+        pub width: u32,
+        pub height: u32,
+        pub max_bounces: u32,
+        pub iterations: u32,
+        pub _pad: u32,
+        pub exposure_value: f64,
+        pub seed: u64,
+        pub seed_stride: u64,
+        pub sample_index_base: u64,
+        pub precision_mode: u32,
+        pub flags: u32,
+    }
+
     /// opaque `rptgpu_scene`
     #[repr(C)]
     pub struct rptgpu_scene {
@@ -366,6 +397,8 @@ pub mod ffi {
         pub fn rptgpu_trace_rays_device(h: *mut rptgpu_scene, n: u64, d_origins: *const c_void, d_dirs: *const c_void, d_streams: *const c_void, q: *const RptRayQuery, d_out_rgb: *mut c_void, stream: *mut c_void) -> c_int;
         pub fn rptgpu_bake_probes(h: *mut rptgpu_scene, n: u64, positions: *const f64, normals: *const f64, streams: *const u32, q: *const RptProbeQuery, out: *mut f64) -> c_int;
         pub fn rptgpu_bake_probes_device(h: *mut rptgpu_scene, n: u64, d_positions: *const c_void, d_normals: *const c_void, d_streams: *const c_void, q: *const RptProbeQuery, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+        pub fn rptgpu_render_views(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, out: *mut f64) -> c_int;
+        pub fn rptgpu_render_views_device(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, d_out: *mut c_void, out_is_f32: c_int, stream: *mut c_void) -> c_int;
         pub fn rptgpu_kdtree_build(boxes: *const f64, n: u64, out: *mut RptKdTree) -> c_int;
         pub fn rptgpu_kdtree_build_device(boxes: *const f64, n: u64, device: c_int, out: *mut RptKdTree) -> c_int;
         pub fn rptgpu_kdtree_free(tree: *mut RptKdTree);
@@ -746,6 +779,8 @@ mod layout_tests {
         assert_eq!(size_of::<RptDenoise>(), 40);
         assert_eq!(size_of::<RptRayQuery>(), 48);
         assert_eq!(size_of::<RptProbeQuery>(), 40);
+        assert_eq!(size_of::<RptView>(), 112);
+        assert_eq!(size_of::<RptViewQuery>(), 64);
     }
 
     #[test]
