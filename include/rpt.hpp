@@ -16,6 +16,7 @@
 #include <fstream>
 #include <functional>
 #include <istream>
+#include <limits>
 #include <map>
 #include <memory>
 #include <sstream>
@@ -739,6 +740,43 @@ class Renderer {
     check(rptgpu_bake_probes(handle_, n, positions.data(), with_normals ? normals.data() : nullptr,
                              streams.empty() ? nullptr : streams.data(), &q, out.data()));
     return out;
+  }
+  // addition: visibility of rays of the caller's own making (rptgpu_occluded, include/rpt_gpu.h): line of sight, shadow
+  // masks, form-factor visibility.  origins, dirs: xyz per ray, used as given; max_t: one stop per ray in units of the ray
+  // parameter (empty: +inf).  -> one byte per ray, 1 = something lies at or before max_t — rptgpu_closest_hit's t held against
+  // max_t, found by the query that stops at the first blocker.
+  std::vector<uint8_t> occluded(const std::vector<double>& origins, const std::vector<double>& dirs,
+                                const std::vector<double>& max_t = {}) {
+    ensure_scene();
+    const size_t n = origins.size() / 3;
+    if (origins.size() != 3 * n || dirs.size() != 3 * n || (!max_t.empty() && max_t.size() != n))
+      throw std::invalid_argument("occluded: origins and dirs hold xyz per ray, max_t one stop per ray");
+    RptVisibilityQuery q{};
+    q.struct_size = sizeof(RptVisibilityQuery);
+    std::vector<uint8_t> out(n);
+    check(rptgpu_occluded(handle_, n, origins.data(), dirs.data(), max_t.empty() ? nullptr : max_t.data(), &q, out.data()));
+    return out;
+  }
+  // addition: ambient occlusion baked on the device (rptgpu_bake_ao, include/rpt_gpu.h).  positions, normals: xyz per point
+  // (the rays start AT the positions: lift them off their surface yourself).  -> per point the unoccluded fraction of
+  // num_samples cosine-weighted directions about the normal, each open up to max_distance; bent (may be null): xyz per
+  // point, the visible directions' sum over num_samples.  Point i draws from the stream (seed, streams[i] or i,
+  // sample_index_base + k), whatever other points the call holds.
+  std::vector<double> bake_ao(const std::vector<double>& positions, const std::vector<double>& normals,
+                              double max_distance = std::numeric_limits<double>::infinity(), std::vector<double>* bent = nullptr,
+                              const std::vector<uint32_t>& streams = {}, uint64_t sample_index_base = 0) {
+    ensure_scene();
+    const size_t n = positions.size() / 3;
+    if (positions.size() != 3 * n || normals.size() != 3 * n || (!streams.empty() && streams.size() != n))
+      throw std::invalid_argument("bake_ao: positions and normals hold xyz per point, streams one id per point");
+    RptAoQuery q{};
+    q.struct_size = sizeof(RptAoQuery); q.samples = num_samples_; q.seed = seed_; q.sample_index_base = sample_index_base;
+    q.max_distance = max_distance;
+    std::vector<double> ao(n);
+    if (bent) bent->resize(3 * n);
+    check(rptgpu_bake_ao(handle_, n, positions.data(), normals.data(), streams.empty() ? nullptr : streams.data(), &q, ao.data(),
+                         bent ? bent->data() : nullptr));
+    return ao;
   }
   // addition: a batch of frames in one call (rptgpu_render_views, include/rpt_gpu.h), each from a view of its own — a camera
   // under RPT_VIEW_PERSPECTIVE (this renderer's frame of that camera), RPT_VIEW_ORTHOGRAPHIC or RPT_VIEW_PANORAMA (a

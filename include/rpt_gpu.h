@@ -553,6 +553,78 @@ int rptgpu_bake_probes(rptgpu_scene* h, uint64_t n, const double* positions /* [
 int rptgpu_bake_probes_device(rptgpu_scene* h, uint64_t n, const void* d_positions, const void* d_normals,
                               const void* d_streams /* may be NULL */, const RptProbeQuery* q, void* d_out, void* stream);
 
+/* ---- visibility on its own: "is anything between A and B?" for rays the caller supplies, and ambient occlusion baked from
+ * directions the library draws itself.  Additions within ABI version 7, detected by symbol (dlsym "rptgpu_occluded").  Both
+ * run the query a render's shadow rays run — it stops at the first blocker and makes no normal — and both are DEFINED by
+ * rptgpu_closest_hit, so that a caller may replace "closest hit, then compare t" by them and keep every bit.
+ * OCCLUDED.  Ray i is origins[3i..], dirs[3i..] (f64, xyz interleaved), used as given: no normalisation, t_min = 1e-12, no
+ * origin offset — rptgpu_closest_hit's rules.  max_t[i] is in units of the ray parameter (a distance only for a unit
+ * direction); max_t == NULL means +inf for every ray.  With t_i = what rptgpu_closest_hit returns for ray i (+inf on a
+ * miss; a NaN record — MonomialSurface reports one for a vertical ray over a corner of its box — stays NaN) and
+ *   stop_i = fmin(max_t[i], 1.7976931348623157e308)
+ *   out[i] = (t_i > stop_i) ? 0 : 1                       (sample_lights' test, renderer.rs:191-197, negated)
+ * So a NaN max_t behaves as +inf, a negative max_t (and 0.0) is never occluded, a NaN hit is occluded, a hit exactly at
+ * max_t is occluded; none of these is refused.  A ray's result depends on that ray, its max_t and the scene and on nothing
+ * else: not on the other rays of the call, on their order, or on the pieces the library cuts the call into.
+ * 56 B in (48 B without max_t) and 1 B out per ray.
+ * AMBIENT OCCLUSION.  Point i stands at positions[3i..] with normal normals[3i..]; S = samples.  Direction k of point i is
+ * d_k = Sphere::sample(normals[i]).v (sphere.rs:52-64: cosine-weighted about normalize(normal) — exactly
+ * RPT_PROBE_IRRADIANCE's direction, in its expressions), made from draw 0 of the Philox4x32-10 stream keyed by `seed` with
+ * the counter (stream id, sample_index_base + k, draw block); the stream id is streams[i], or i (the point's index in this
+ * call's arrays) when streams is NULL.  A zero or non-finite normal yields whatever that function yields; it is not refused.
+ * The ray is (positions[i], d_k), used as given: NO origin offset.  A point that lies ON a surface sees that surface only
+ * through the 1e-12 guard on t; a caller whom that does not suit lifts the points off their surface before the call.
+ *   v_k = (t_k > fmin(max_distance, 1.7976931348623157e308)) ? 1 : 0     (t_k as above; NaN max_distance = +inf)
+ *   out_ao[i]      = (double)(v_0 + .. + v_{S-1}) / (double)S            (an integer count: no order dependence)
+ *   out_bent[i][c] = acc[c] / (double)S,  acc[c] = acc[c] + d_k[c] over the visible k, ascending, from +0.0
+ * out_ao is the unoccluded fraction (1.0: open sky); out_bent (may be NULL) is the unnormalised bent normal.  A point's
+ * result depends on (its position, its normal, seed, its stream id, the sample indices, max_distance) and on nothing else:
+ * not on the other points, their order, the pieces and passes, or on how a caller splits the POINTS over calls or GPUs.
+ * 48 B in (52 B with stream ids) and 8 B or 32 B out per point, whatever S is.
+ * ROUTE.  The rays are laid where a depth's shadow rays lie and go through the visibility query of a render: one kernel
+ * that walks the whole scene per ray, or — scenes with deep trees — the per-tree queries (queues, ray sort, persistent
+ * traversal, the generic walker for trees of trees); RPT_FLAG_GENERAL_TRAVERSAL and RPT_FLAG_PROFILE_KERNELS are honoured.
+ * RptStats: shadow_rays and shadow_rays_traced advance by the rays traced (n, or n * S), kernel_launches[RPT_K_SHADOW] by the
+ * queries; samples does not advance.  There is no CPU fallback: RPTGPU_E_NO_DEVICE.  RPTGPU_OCCLUSION_PIECE (environment,
+ * read per call; tests): the rays (rptgpu_occluded) or the points (rptgpu_bake_ao) per piece.
+ * NOT IN SCOPE: a device form of rptgpu_closest_hit; multi-GPU sharding (a caller shards the rays or the points: a result
+ * depends on nothing else); ambient occlusion as a feature buffer of a render or in the device Buffer; distance-weighted
+ * ambient occlusion.
+ * RPTGPU_E_INVALID_ARGUMENT, checked before any device work, with a detail naming the reason and with the output arrays
+ * untouched: a NULL query, a wrong struct_size, samples == 0, reserved != 0, a precision_mode other than
+ * RPT_PRECISION_F64_STRICT, RPT_FLAG_PERSISTENT (the persistent kernel makes its rays from a camera), NULL origins / dirs /
+ * out or positions / normals / out_ao with n > 0, more than 2^32 points without stream ids, a NULL handle; RPTGPU_E_COMM
+ * for an abandoned handle.  n == 0 returns RPTGPU_OK. */
+typedef struct RptVisibilityQuery {
+  uint32_t struct_size;       /* sizeof(RptVisibilityQuery) */
+  uint32_t precision_mode;    /* RPT_PRECISION_F64_STRICT */
+  uint32_t flags;             /* GENERAL_TRAVERSAL, PROFILE_KERNELS honoured; PERSISTENT refused */
+  uint32_t reserved;          /* 0 */
+} RptVisibilityQuery;
+int rptgpu_occluded(rptgpu_scene* h, uint64_t n, const double* origins /* [n][3] */, const double* dirs /* [n][3] */,
+                    const double* max_t /* [n], or NULL: +inf for every ray */, const RptVisibilityQuery* q,
+                    uint8_t* out /* [n], host */);
+/* The same with every array in device memory; `stream` and the synchronisation rule are rptgpu_trace_rays_device's (NULL
+ * means NO stream, not the null stream). */
+int rptgpu_occluded_device(rptgpu_scene* h, uint64_t n, const void* d_origins, const void* d_dirs,
+                           const void* d_max_t /* may be NULL */, const RptVisibilityQuery* q, void* d_out, void* stream);
+typedef struct RptAoQuery {
+  uint32_t struct_size;       /* sizeof(RptAoQuery) */
+  uint32_t samples;           /* S: directions per point, > 0 */
+  uint64_t seed;
+  uint64_t sample_index_base; /* sample index of every point's first direction */
+  double max_distance;        /* in units of the ray parameter = world units (d_k is a unit vector); +inf allowed, NaN = +inf */
+  uint32_t precision_mode;    /* RPT_PRECISION_F64_STRICT */
+  uint32_t flags;             /* as RptVisibilityQuery */
+} RptAoQuery;
+int rptgpu_bake_ao(rptgpu_scene* h, uint64_t n, const double* positions /* [n][3] */, const double* normals /* [n][3] */,
+                   const uint32_t* streams /* [n] or NULL */, const RptAoQuery* q, double* out_ao /* [n], host */,
+                   double* out_bent /* [n][3], host; may be NULL */);
+/* The same with every array in device memory; `stream` as for rptgpu_occluded_device. */
+int rptgpu_bake_ao_device(rptgpu_scene* h, uint64_t n, const void* d_positions, const void* d_normals,
+                          const void* d_streams /* may be NULL */, const RptAoQuery* q, void* d_out_ao,
+                          void* d_out_bent /* may be NULL */, void* stream);
+
 /* ---- batches of views: n_views frames of one size in ONE call, each from a camera of its own under one of three
  * projections — cube-map faces, stereo pairs, turntables, light fields, data sets; orthographic views; and 360-degree
  * panoramas in exactly Hdri::get_color's convention (environment.rs:25-52), so that a rendered panorama is a valid

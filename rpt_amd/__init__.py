@@ -9,7 +9,9 @@ The path tracer and the particle systems are HIP (rpt_amd/csrc) behind the C ABI
 Beyond the reference: GpuScene.trace_rays runs the path estimator along rays of the caller's own making (numpy arrays,
 or torch tensors on the device), and GpuScene.bake_probes turns positions into light probes on the device — SH9 radiance or
 surface irradiance — which sh9_basis / sh9_irradiance (numpy) evaluate; GpuScene.render_views renders a batch of frames in one
-call, each from a View: a camera under a perspective, orthographic or panoramic projection (a panorama is an Hdri's texels).
+call, each from a View: a camera under a perspective, orthographic or panoramic projection (a panorama is an Hdri's texels);
+GpuScene.occluded answers "is anything between here and there?" for the caller's rays with the shadow rays' own query, and
+GpuScene.bake_ao bakes ambient occlusion (and bent normals) from directions drawn on the device.
 """
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401

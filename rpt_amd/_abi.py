@@ -178,6 +178,17 @@ class RptProbeQuery(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class RptVisibilityQuery(C.Structure):
+    """include/rpt_gpu.h RptVisibilityQuery (rptgpu_occluded's parameters; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("precision_mode", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RptAoQuery(C.Structure):
+    """include/rpt_gpu.h RptAoQuery (rptgpu_bake_ao's parameters; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("samples", C.c_uint32), ("seed", C.c_uint64), ("sample_index_base", C.c_uint64),
+                ("max_distance", f64), ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class RptView(C.Structure):
     """include/rpt_gpu.h RptView (one view of rptgpu_render_views; detected by symbol within ABI 7)."""
     _fields_ = [("camera", RptCamera), ("projection", C.c_uint32), ("_pad", C.c_uint32), ("ortho_scale", f64)]
@@ -227,6 +238,10 @@ SYMBOLS = [
     ("rptgpu_trace_rays_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptRayQuery), _VP, _VP]),
     ("rptgpu_bake_probes", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(C.c_uint32), C.POINTER(RptProbeQuery), _PD]),
     ("rptgpu_bake_probes_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptProbeQuery), _VP, _VP]),
+    ("rptgpu_occluded", C.c_int, [_VP, C.c_uint64, _PD, _PD, _PD, C.POINTER(RptVisibilityQuery), C.POINTER(C.c_uint8)]),
+    ("rptgpu_occluded_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptVisibilityQuery), _VP, _VP]),
+    ("rptgpu_bake_ao", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(C.c_uint32), C.POINTER(RptAoQuery), _PD, _PD]),
+    ("rptgpu_bake_ao_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptAoQuery), _VP, _VP, _VP]),
     ("rptgpu_render_views", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), _PD]),
     ("rptgpu_render_views_device", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), _VP, C.c_int, _VP]),
     ("rptgpu_eval_math", C.c_int, [_VP, C.c_int, C.c_uint64, _PD, _PD, _PD]),

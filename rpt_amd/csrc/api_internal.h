@@ -19,6 +19,8 @@
 //   api_probes.cpp   rptgpu_bake_probes[_device]: light probes (SH9 radiance, irradiance) through the same driver, in pieces
 //   api_views.cpp    rptgpu_render_views[_device]: batches of perspective, orthographic and panoramic views through the same
 //                    driver, in pieces of consecutive (view, pixel) indices
+//   api_occlusion.cpp rptgpu_occluded[_device], rptgpu_bake_ao[_device]: the caller's rays, or points x directions made on the
+//                    device, through ONE visibility query of a render per pass (no depth loop), in pieces
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -179,6 +181,7 @@ struct rptgpu_scene {
   DevBuf<double> rays_o, rays_d, rays_out; // rptgpu_trace_rays: a piece of the host caller's rays and of their results (api_rays.cpp)
   DevBuf<uint32_t> ray_ids;            // ... and the piece's stream ids (the caller's, or the rays' indices); rptgpu_bake_probes
                                        // stages a piece of probes in the same four (api_probes.cpp)
+  DevBuf<uint8_t> occ_out;             // rptgpu_occluded: a piece of a host caller's answers (api_occlusion.cpp)
   DevBuf<rptdev::View> view_recs;      // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<double> aov_out;              // rptgpu_render_aov: the requested channels' full-frame arrays, back to back (api_aov.cpp)
   int num_cus = 0;

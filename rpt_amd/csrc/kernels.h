@@ -187,6 +187,20 @@ struct KernelTable {
   // records on the device; ids_out (= fr.pixels) receives the piece's stream ids, the pixels
   void (*raygen_views)(hipStream_t, const rptdev::Frame&, const rptdev::View* views, uint32_t width, uint32_t height,
                        uint64_t j_base, uint32_t* ids_out, const rptdev::PathState&, uint32_t n_paths);
+  // visibility for the caller (rptgpu_occluded, rptgpu_bake_ao; kernels/occlusion.inc): the steps around a visibility query
+  // of "light" 0.  occ_load: n rays of the caller ([n][3] f64 on the device, max_t [n] or null) into ps.ray and column 0 of
+  // ps.shadow, the identity into sq with its length in *sq_count.  raygen_ao: the same for fr.npix points x the pass's
+  // samples (n_slots = npix * samples of the pass; ids: the points' stream ids or null = id_base + i).  occ_store: the
+  // answers in srt's column 0 as bytes.  ao_fold: a pass's answers into the points' running sums (fr.accum, [4][npix]);
+  // last: the sums divided by the call's `samples` into out_ao [npix] and out_bent [npix][3] (may be null)
+  void (*occ_load)(hipStream_t, const double* origins, const double* dirs, const double* max_t, const rptdev::PathState&,
+                   uint32_t* sq, uint32_t* sq_count, uint32_t n);
+  void (*raygen_ao)(hipStream_t, const rptdev::Frame&, const double* positions, const double* normals, const uint32_t* ids,
+                    uint32_t id_base, double max_distance, const rptdev::PathState&, uint32_t* sq, uint32_t* sq_count,
+                    uint32_t n_slots);
+  void (*occ_store)(hipStream_t, const rptdev::PathState&, const double* srt, uint32_t n, uint8_t* out);
+  void (*ao_fold)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, const double* srt, uint32_t n_samples, bool first,
+                  bool last, uint32_t samples, double* out_ao, double* out_bent);
 };
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)

@@ -290,6 +290,25 @@ void launch_aov_fold(hipStream_t st, const Scene& sc, const Frame& fr, const Pat
   hipLaunchKernelGGL(rpt_aov_fold, grid_for(fr.npix), dim3(256), 0, st, sc, fr, ps, out, spp, first ? 1 : 0);
 }
 
+// rptgpu_occluded / rptgpu_bake_ao (kernels/occlusion.inc): rays into light 0's shadow-ray state, answers out of srt
+void launch_occ_load(hipStream_t st, const double* origins, const double* dirs, const double* max_t, const PathState& ps,
+                     uint32_t* sq, uint32_t* sq_count, uint32_t n) {
+  hipLaunchKernelGGL(rpt_occ_load, grid_for(n), dim3(256), 0, st, origins, dirs, max_t, ps, sq, sq_count, n);
+}
+void launch_raygen_ao(hipStream_t st, const Frame& fr, const double* positions, const double* normals, const uint32_t* ids,
+                      uint32_t id_base, double max_distance, const PathState& ps, uint32_t* sq, uint32_t* sq_count, uint32_t n_slots) {
+  hipLaunchKernelGGL(rpt_raygen_ao, grid_for(n_slots), dim3(256), 0, st, fr, positions, normals, ids, id_base, max_distance, ps, sq,
+                     sq_count, n_slots);
+}
+void launch_occ_store(hipStream_t st, const PathState& ps, const double* srt, uint32_t n, uint8_t* out) {
+  hipLaunchKernelGGL(rpt_occ_store, grid_for(n), dim3(256), 0, st, ps, srt, n, out);
+}
+void launch_ao_fold(hipStream_t st, const Frame& fr, const PathState& ps, const double* srt, uint32_t n_samples, bool first,
+                    bool last, uint32_t samples, double* out_ao, double* out_bent) {
+  hipLaunchKernelGGL(rpt_ao_fold, grid_for(fr.npix), dim3(256), 0, st, fr, ps, srt, n_samples, first ? 1 : 0, last ? 1 : 0, samples,
+                     out_ao, out_bent);
+}
+
 // blocks of 64 x 4 pixels: a wave is 64 consecutive x of one row (kernels/denoise.inc)
 static inline dim3 grid_rows(uint32_t w, uint32_t h) { return dim3((w + 63u) / 64u, (h + 3u) / 4u); }
 void launch_denoise_prepare(hipStream_t st, const double* total, const uint32_t* counts, const double* m2, const AovOut& feat,
@@ -328,5 +347,6 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_buffer_accumulate, launch_buffer_retire, launch_buffer_image, launch_buffer_variance,
                            read_prof, launch_path_reorder, launch_aov, launch_aov_fold,
                            launch_denoise_prepare, launch_denoise_level, launch_denoise_finish,
-                           launch_raygen_probes, launch_resolve_probes, launch_finish_probes, launch_raygen_views};
+                           launch_raygen_probes, launch_resolve_probes, launch_finish_probes, launch_raygen_views,
+                           launch_occ_load, launch_raygen_ao, launch_occ_store, launch_ao_fold};
 #endif // !__HIP_DEVICE_COMPILE__

@@ -1,7 +1,7 @@
 // render_plan.h — how a render call is cut into launches (persistent pipeline) and passes (wavefront pipeline): the
 // arithmetic behind api_render.cpp's drivers, as pure host functions of numbers (tests/cpp/render_plan_check.cpp), and the
 // pieces rptgpu_trace_rays cuts its rays into (tests/cpp/rays_piece_check.cpp) and rptgpu_render_views its views' pixels
-// (tests/cpp/views_piece_check.cpp).
+// (tests/cpp/views_piece_check.cpp), rptgpu_occluded its rays and rptgpu_bake_ao its points (tests/cpp/occlusion_piece_check.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -195,6 +195,32 @@ inline uint64_t views_piece_len(uint64_t base, uint64_t n, uint64_t npix, uint64
   uint64_t m = std::min(piece, n - base);
   if (at_views) m = std::min(m, npix - base % npix);
   return m;
+}
+
+// ---- rptgpu_occluded / rptgpu_bake_ao: one visibility query per pass over rays laid into the workspace's slots, so a pass
+// holds at most pass_target rays (plan_pass's target for the scene with ONE record column per path: no depth follows),
+// never more than RPT_MAX_PATHS_PER_PASS (32-bit slots) and never more than OCCLUSION_PIECE_MAX (a host caller stages 56 B
+// per ray; a larger pass has not been measured): occlusion_pass_max.  rptgpu_occluded cuts its n rays into runs of occlusion_piece rays,
+// each one pass.  rptgpu_bake_ao cuts its n points into pieces of ao_piece WHOLE points — a point's running sums live with
+// its piece — and a piece's S directions into passes of ao_pass_samples directions of every point of the piece: points x
+// samples <= the bound, and when S alone exceeds it a piece is one point in several passes.  asked: RPTGPU_OCCLUSION_PIECE
+// (tests; 0 = not set) — rays per piece, or points per piece —, within the same bound.
+constexpr uint64_t OCCLUSION_PIECE_MAX = 16ull << 20;
+inline uint64_t occlusion_pass_max(uint64_t pass_target) {
+  return std::max<uint64_t>(1, std::min<uint64_t>(pass_target, std::min<uint64_t>(RPT_MAX_PATHS_PER_PASS, OCCLUSION_PIECE_MAX)));
+}
+inline uint64_t occlusion_piece(uint64_t n, uint64_t asked, uint64_t pass_target) {
+  const uint64_t fit = occlusion_pass_max(pass_target);
+  return std::max<uint64_t>(1, std::min(std::min<uint64_t>(n, asked ? asked : fit), fit));
+}
+inline uint64_t ao_piece(uint64_t n, uint64_t asked, uint32_t samples, uint64_t pass_target) {
+  const uint64_t fit = occlusion_pass_max(pass_target);
+  const uint64_t want = asked ? asked : std::max<uint64_t>(1, fit / std::max(1u, samples));
+  return std::max<uint64_t>(1, std::min(std::min(n, want), fit));
+}
+// the directions per point of the next pass of a piece of `points` points with `remaining` directions to go
+inline uint32_t ao_pass_samples(uint64_t points, uint32_t remaining, uint64_t pass_target) {
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(remaining, occlusion_pass_max(pass_target) / std::max<uint64_t>(1, points)));
 }
 
 } // namespace rptplan

@@ -478,6 +478,192 @@ class GpuScene:
         _abi.check(code, self.handle)
         return out
 
+    def occluded(self, origins, dirs, max_t=None, flags=0, out=None):
+        """Is anything between the ray's origin and max_t along it?  (rptgpu_occluded) -> (n,) uint8, 1 =
+        occluded: exactly `~(t > fmin(max_t, DBL_MAX))` with t = closest_hit's, found by the shadow-ray query (it stops at
+        the first blocker).  origins, dirs: (n, 3) float64, used as given; max_t: (n,) float64 in units of the ray
+        parameter, None = +inf for every ray.  numpy arrays go through host memory; torch tensors on the handle's device
+        are read where they lie (rptgpu_occluded_device) and the result is `out` or a new tensor there."""
+        q = _abi.RptVisibilityQuery()
+        q.struct_size = C.sizeof(_abi.RptVisibilityQuery)
+        q.precision_mode, q.flags, q.reserved = _abi.RPT_PRECISION_F64_STRICT, int(flags), 0
+        if hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr"):
+            return self._occluded_torch(origins, dirs, max_t, q, out)
+
+        def vectors(a, what):
+            a = np.asarray(a)
+            if a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("occluded: %s must be an (n, 3) float64 array" % what)
+            return np.ascontiguousarray(a)
+
+        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
+        n = len(o)
+        if len(d) != n:
+            raise ValueError("occluded: %d origins for %d directions" % (n, len(d)))
+        mt = None
+        if max_t is not None:
+            mt = np.asarray(max_t)
+            if mt.dtype != np.float64 or mt.shape != (n,):
+                raise ValueError("occluded: max_t must be an (n,) float64 array")
+            mt = np.ascontiguousarray(mt)
+        if out is None:
+            out = np.empty(n, dtype=np.uint8)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.shape == (n,) and out.flags.c_contiguous):
+            raise ValueError("occluded: out must be a C-contiguous (n,) uint8 array")
+        PD = C.POINTER(C.c_double)
+        code = self.lib.rptgpu_occluded(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD),
+                                        mt.ctypes.data_as(PD) if mt is not None else None, C.byref(q),
+                                        out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        _abi.check(code, self.handle)
+        return out
+
+    def _occluded_torch(self, origins, dirs, max_t, q, out):
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def vectors(t, what):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise ValueError("occluded: %s must be a torch tensor on %s, like the other arrays" % (what, dev))
+            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
+                raise ValueError("occluded: %s must be an (n, 3) float64 tensor" % what)
+            return t.contiguous()  # (no copy when it already is)
+
+        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("occluded: %d origins for %d directions" % (n, d.shape[0]))
+        mt = None
+        if max_t is not None:
+            if not isinstance(max_t, torch.Tensor) or max_t.device != dev:
+                raise ValueError("occluded: max_t must be a torch tensor on %s, like the rays" % dev)
+            if max_t.dtype != torch.float64 or tuple(max_t.shape) != (n,):
+                raise ValueError("occluded: max_t must be an (n,) float64 tensor")
+            mt = max_t.contiguous()
+        if out is None:
+            out = torch.empty((n,), dtype=torch.uint8, device=dev)
+        elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.uint8
+                  and tuple(out.shape) == (n,) and out.is_contiguous()):
+            raise ValueError("occluded: out must be a contiguous (n,) uint8 tensor on %s" % dev)
+        # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
+        # stream is waited for here)
+        current = torch.cuda.current_stream(dev)
+        stream = current.cuda_stream
+        if not stream:
+            current.synchronize()
+        code = self.lib.rptgpu_occluded_device(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                               C.c_void_p(mt.data_ptr()) if mt is not None else None, C.byref(q),
+                                               C.c_void_p(out.data_ptr()), C.c_void_p(stream or 0))
+        _abi.check(code, self.handle)
+        return out
+
+    def bake_ao(self, positions, normals, *, samples, seed, max_distance=float("inf"), sample_index_base=0, streams=None,
+                bent_normals=False, flags=0, out=None):
+        """Ambient occlusion baked on the device (rptgpu_bake_ao): per point `samples` cosine-weighted
+        directions about its normal from the Philox stream (RPT_PROBE_IRRADIANCE's), each a visibility query up to
+        max_distance -> (n,) float64, the unoccluded fraction (1.0 = open); with bent_normals=True -> (ao, bent), bent (n, 3)
+        the mean of the visible directions' sum over all `samples` (the unnormalised bent normal).  The rays start AT the
+        positions (no offset: lift points off their surface yourself).  positions, normals: (n, 3) float64.  streams: (n,)
+        32-bit stream ids, default the points' indices.  out: None, an (n,) array for ao, or with bent_normals a pair
+        (ao, bent).  numpy arrays go through host memory; torch tensors on the handle's device are read where they lie
+        (rptgpu_bake_ao_device) and the results are `out` or new tensors there."""
+        q = _abi.RptAoQuery()
+        q.struct_size = C.sizeof(_abi.RptAoQuery)
+        q.samples, q.seed, q.sample_index_base = int(samples), int(seed), int(sample_index_base)
+        q.max_distance, q.precision_mode, q.flags = float(max_distance), _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        out_ao, out_bent = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
+        if out_bent is not None and not bent_normals:
+            raise ValueError("bake_ao: an output for bent normals without bent_normals=True")
+        if hasattr(positions, "data_ptr") or hasattr(normals, "data_ptr"):
+            return self._bake_ao_torch(positions, normals, streams, q, bent_normals, out_ao, out_bent)
+
+        def vectors(a, what):
+            a = np.asarray(a)
+            if a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("bake_ao: %s must be an (n, 3) float64 array" % what)
+            return np.ascontiguousarray(a)
+
+        pos, nrm = vectors(positions, "positions"), vectors(normals, "normals")
+        n = len(pos)
+        if len(nrm) != n:
+            raise ValueError("bake_ao: %d normals for %d positions" % (len(nrm), n))
+        ids = None
+        if streams is not None:
+            ids = np.asarray(streams)
+            if ids.ndim != 1 or ids.dtype.kind not in "iu":
+                raise ValueError("bake_ao: streams must be an (n,) integer array")
+            if len(ids) != n:
+                raise ValueError("bake_ao: %d stream ids for %d points" % (len(ids), n))
+            ids = np.ascontiguousarray(ids, dtype=np.uint32)
+
+        def result(a, shape, what):
+            if a is None:
+                return np.empty(shape, dtype=np.float64)
+            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError("bake_ao: the output for %s must be a C-contiguous %s float64 array" % (what, shape))
+            return a
+
+        out_ao = result(out_ao, (n,), "ao")
+        if bent_normals:
+            out_bent = result(out_bent, (n, 3), "bent normals")
+        PD = C.POINTER(C.c_double)
+        code = self.lib.rptgpu_bake_ao(self.handle, n, pos.ctypes.data_as(PD), nrm.ctypes.data_as(PD),
+                                       ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None, C.byref(q),
+                                       out_ao.ctypes.data_as(PD), out_bent.ctypes.data_as(PD) if bent_normals else None)
+        _abi.check(code, self.handle)
+        return (out_ao, out_bent) if bent_normals else out_ao
+
+    def _bake_ao_torch(self, positions, normals, streams, q, bent_normals, out_ao, out_bent):
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def vectors(t, what):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise ValueError("bake_ao: %s must be a torch tensor on %s, like the other arrays" % (what, dev))
+            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
+                raise ValueError("bake_ao: %s must be an (n, 3) float64 tensor" % what)
+            return t.contiguous()  # (no copy when it already is)
+
+        pos, nrm = vectors(positions, "positions"), vectors(normals, "normals")
+        n = pos.shape[0]
+        if nrm.shape[0] != n:
+            raise ValueError("bake_ao: %d normals for %d positions" % (nrm.shape[0], n))
+        ids = None
+        if streams is not None:
+            if not isinstance(streams, torch.Tensor) or streams.device != dev:
+                raise ValueError("bake_ao: streams must be a torch tensor on %s, like the points" % dev)
+            if streams.dim() != 1 or streams.dtype.is_floating_point:
+                raise ValueError("bake_ao: streams must be an (n,) integer tensor")
+            ids = streams
+            if ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                ids = ids.to(torch.int64).to(torch.int32)  # the low 32 bits
+            ids = ids.contiguous()
+            if ids.shape[0] != n:
+                raise ValueError("bake_ao: %d stream ids for %d points" % (ids.shape[0], n))
+
+        def result(t, shape, what):
+            if t is None:
+                return torch.empty(shape, dtype=torch.float64, device=dev)
+            if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float64
+                    and tuple(t.shape) == shape and t.is_contiguous()):
+                raise ValueError("bake_ao: the output for %s must be a contiguous %s float64 tensor on %s" % (what, shape, dev))
+            return t
+
+        out_ao = result(out_ao, (n,), "ao")
+        if bent_normals:
+            out_bent = result(out_bent, (n, 3), "bent normals")
+        # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
+        # stream is waited for here)
+        current = torch.cuda.current_stream(dev)
+        stream = current.cuda_stream
+        if not stream:
+            current.synchronize()
+        code = self.lib.rptgpu_bake_ao_device(self.handle, n, C.c_void_p(pos.data_ptr()), C.c_void_p(nrm.data_ptr()),
+                                              C.c_void_p(ids.data_ptr()) if ids is not None else None, C.byref(q),
+                                              C.c_void_p(out_ao.data_ptr()),
+                                              C.c_void_p(out_bent.data_ptr()) if bent_normals else None, C.c_void_p(stream or 0))
+        _abi.check(code, self.handle)
+        return (out_ao, out_bent) if bent_normals else out_ao
+
     def render_views(self, views, width, height, max_bounces, samples=1, seed=0x52505447, seed_stride=0,
                      sample_index_base=0, exposure_value=0.0, flags=0, out=None):
         """A batch of frames in one call (rptgpu_render_views) -> (n, height, width, 3): per pixel the mean

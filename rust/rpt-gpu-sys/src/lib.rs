@@ -329,6 +329,29 @@ pub mod ffi {
         pub flags: u32,
     }
 
+    /// `RptVisibilityQuery` (the parameters of `rptgpu_occluded`; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptVisibilityQuery {
+        pub struct_size: u32,
+        pub precision_mode: u32,
+        pub flags: u32,
+        pub reserved: u32,
+    }
+
+    /// `RptAoQuery` (the parameters of `rptgpu_bake_ao`; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptAoQuery {
+        pub struct_size: u32,
+        pub samples: u32,
+        pub seed: u64,
+        pub sample_index_base: u64,
+        pub max_distance: f64,
+        pub precision_mode: u32,
+        pub flags: u32,
+    }
+
     /// `RptView` (one view of `rptgpu_render_views`; detected by symbol within ABI 7)
     #[repr(C)]
     #[derive(Clone, Copy, Debug)]
@@ -397,6 +420,10 @@ pub mod ffi {
         pub fn rptgpu_trace_rays_device(h: *mut rptgpu_scene, n: u64, d_origins: *const c_void, d_dirs: *const c_void, d_streams: *const c_void, q: *const RptRayQuery, d_out_rgb: *mut c_void, stream: *mut c_void) -> c_int;
         pub fn rptgpu_bake_probes(h: *mut rptgpu_scene, n: u64, positions: *const f64, normals: *const f64, streams: *const u32, q: *const RptProbeQuery, out: *mut f64) -> c_int;
         pub fn rptgpu_bake_probes_device(h: *mut rptgpu_scene, n: u64, d_positions: *const c_void, d_normals: *const c_void, d_streams: *const c_void, q: *const RptProbeQuery, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+        pub fn rptgpu_occluded(h: *mut rptgpu_scene, n: u64, origins: *const f64, dirs: *const f64, max_t: *const f64, q: *const RptVisibilityQuery, out: *mut u8) -> c_int;
+        pub fn rptgpu_occluded_device(h: *mut rptgpu_scene, n: u64, d_origins: *const c_void, d_dirs: *const c_void, d_max_t: *const c_void, q: *const RptVisibilityQuery, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+        pub fn rptgpu_bake_ao(h: *mut rptgpu_scene, n: u64, positions: *const f64, normals: *const f64, streams: *const u32, q: *const RptAoQuery, out_ao: *mut f64, out_bent: *mut f64) -> c_int;
+        pub fn rptgpu_bake_ao_device(h: *mut rptgpu_scene, n: u64, d_positions: *const c_void, d_normals: *const c_void, d_streams: *const c_void, q: *const RptAoQuery, d_out_ao: *mut c_void, d_out_bent: *mut c_void, stream: *mut c_void) -> c_int;
         pub fn rptgpu_render_views(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, out: *mut f64) -> c_int;
         pub fn rptgpu_render_views_device(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, d_out: *mut c_void, out_is_f32: c_int, stream: *mut c_void) -> c_int;
         pub fn rptgpu_kdtree_build(boxes: *const f64, n: u64, out: *mut RptKdTree) -> c_int;
@@ -779,6 +806,8 @@ mod layout_tests {
         assert_eq!(size_of::<RptDenoise>(), 40);
         assert_eq!(size_of::<RptRayQuery>(), 48);
         assert_eq!(size_of::<RptProbeQuery>(), 40);
+        assert_eq!(size_of::<RptVisibilityQuery>(), 16);
+        assert_eq!(size_of::<RptAoQuery>(), 40);
         assert_eq!(size_of::<RptView>(), 112);
         assert_eq!(size_of::<RptViewQuery>(), 64);
     }

@@ -10,7 +10,7 @@ B=build/var_$NAME; mkdir -p $B
 COMMON="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
 /opt/rocm/bin/hipcc $COMMON -ffp-contract=off $FLAGS -c kernels_strict.hip -o $B/kernels_strict.o &
 if [ -z "$NOEXT" ]; then /opt/rocm/bin/hipcc $COMMON -ffp-contract=off $FLAGS -c kernels_strict_ext.hip -o $B/kernels_strict_ext.o & else cp build/kernels_strict_ext.o $B/; fi
-API="api_common api_scene api_render api_comm api_buffer api_particles api_aov api_rays api_probes api_views"
+API="api_common api_scene api_render api_comm api_buffer api_particles api_aov api_rays api_probes api_views api_occlusion"
 for a in $API; do /opt/rocm/bin/hipcc $COMMON -ffp-contract=off $FLAGS -x hip -c $a.cpp -o $B/$a.o & done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../lib/librptgpu_$NAME.so $B/kernels_strict.o $(for a in $API; do echo $B/$a.o; done) $B/kernels_strict_ext.o build/host_scene.o build/kdbuild.o build/particles.o
