@@ -792,6 +792,61 @@ class Renderer {
     check(rptgpu_render_views(handle_, views.size(), views.data(), &q, out.data()));
     return out;
   }
+  // addition: the first hit of rays of the caller's own making (rptgpu_first_hits, include/rpt_gpu.h): depth sensors,
+  // picking, collision, points and normals for bake_ao / bake_probes.  origins, dirs: xyz per ray, used as given.  -> per ray
+  // rptgpu_closest_hit's t (+inf on a miss), normal and object (-1 on a miss), position = origin + t * dir and albedo = the
+  // hit object's material colour (both +0.0 on a miss); a vector of a channel not named in `channels` (RPT_HIT_*) stays empty.
+  struct Hits {
+    std::vector<double> t, normal, position, albedo; // t: one per ray; the others: xyz / rgb per ray
+    std::vector<int32_t> object;
+  };
+  Hits first_hits(const std::vector<double>& origins, const std::vector<double>& dirs,
+                  uint32_t channels = RPT_HIT_T | RPT_HIT_NORMAL | RPT_HIT_OBJECT | RPT_HIT_POSITION | RPT_HIT_ALBEDO) {
+    ensure_scene();
+    const size_t n = origins.size() / 3;
+    if (origins.size() != 3 * n || dirs.size() != 3 * n)
+      throw std::invalid_argument("first_hits: origins and dirs hold xyz per ray");
+    RptHitQuery q{};
+    q.struct_size = sizeof(RptHitQuery); q.channels = channels;
+    Hits r;
+    if (!n) return r; // (an empty vector has no address, and a named channel's pointer must not be NULL)
+    if (channels & RPT_HIT_T) r.t.resize(n);
+    if (channels & RPT_HIT_NORMAL) r.normal.resize(3 * n);
+    if (channels & RPT_HIT_OBJECT) r.object.resize(n);
+    if (channels & RPT_HIT_POSITION) r.position.resize(3 * n);
+    if (channels & RPT_HIT_ALBEDO) r.albedo.resize(3 * n);
+    RptHitArrays a{};
+    a.struct_size = sizeof(RptHitArrays);
+    a.t = r.t.data(); a.normal = r.normal.data(); a.object = r.object.data(); a.position = r.position.data();
+    a.albedo = r.albedo.data();
+    check(rptgpu_first_hits(handle_, n, origins.data(), dirs.data(), &q, &a));
+    return r;
+  }
+  // addition: render_aovs for a batch of views (rptgpu_render_views_aov, include/rpt_gpu.h): per (view, pixel) the sums over
+  // the hits of num_samples rays — the rays render_views starts its paths with — and the hit count, [views][height][width]
+  // (x 3); view v draws with seed + v * seed_stride.  A perspective view's buffers are render_aovs' of that camera.
+  Aovs render_views_aov(const std::vector<RptView>& views, uint64_t seed_stride = 0, uint64_t sample_index_base = 0,
+                        uint32_t channels = RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION | RPT_AOV_OBJECT) {
+    ensure_scene();
+    RptViewQuery q{};
+    q.struct_size = sizeof(RptViewQuery); q.width = width_; q.height = height_; q.iterations = num_samples_;
+    q.seed = seed_; q.seed_stride = seed_stride; q.sample_index_base = sample_index_base;
+    const size_t n = views.size() * (size_t)width_ * height_;
+    Aovs a;
+    if (!n) return a; // (an empty vector has no address, and a named channel's pointer must not be NULL)
+    a.hits.resize(n);
+    if (channels & RPT_AOV_DEPTH) a.depth.resize(n);
+    if (channels & RPT_AOV_NORMAL) a.normal.resize(3 * n);
+    if (channels & RPT_AOV_ALBEDO) a.albedo.resize(3 * n);
+    if (channels & RPT_AOV_POSITION) a.position.resize(3 * n);
+    if (channels & RPT_AOV_OBJECT) a.object.resize(n);
+    RptAovBuffers b{};
+    b.struct_size = sizeof(RptAovBuffers); b.channels = channels;
+    b.hits = a.hits.data(); b.depth = a.depth.data(); b.normal = a.normal.data(); b.albedo = a.albedo.data();
+    b.position = a.position.data(); b.object = a.object.data();
+    check(rptgpu_render_views_aov(handle_, views.size(), views.data(), &q, &b));
+    return a;
+  }
   // addition: iterative_render with the Buffer kept on the device (rptgpu_buffer_*), followed by the feature-guided
   // a-trous filter of rptgpu_buffer_denoise (include/rpt_gpu.h) guided by the first hits of samples 0 .. feature_samples-1.
   // At least two batches (num_samples > callback_interval), else the library refuses: one batch has no variance.

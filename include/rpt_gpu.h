@@ -587,8 +587,8 @@ int rptgpu_bake_probes_device(rptgpu_scene* h, uint64_t n, const void* d_positio
  * RptStats: shadow_rays and shadow_rays_traced advance by the rays traced (n, or n * S), kernel_launches[RPT_K_SHADOW] by the
  * queries; samples does not advance.  There is no CPU fallback: RPTGPU_E_NO_DEVICE.  RPTGPU_OCCLUSION_PIECE (environment,
  * read per call; tests): the rays (rptgpu_occluded) or the points (rptgpu_bake_ao) per piece.
- * NOT IN SCOPE: a device form of rptgpu_closest_hit; multi-GPU sharding (a caller shards the rays or the points: a result
- * depends on nothing else); ambient occlusion as a feature buffer of a render or in the device Buffer; distance-weighted
+ * NOT IN SCOPE: multi-GPU sharding (a caller shards the rays or the points: a result depends on nothing else; the device
+ * form of rptgpu_closest_hit is rptgpu_first_hits_device, below); ambient occlusion as a feature buffer of a render or in the device Buffer; distance-weighted
  * ambient occlusion.
  * RPTGPU_E_INVALID_ARGUMENT, checked before any device work, with a detail naming the reason and with the output arrays
  * untouched: a NULL query, a wrong struct_size, samples == 0, reserved != 0, a precision_mode other than
@@ -672,7 +672,8 @@ int rptgpu_bake_ao_device(rptgpu_scene* h, uint64_t n, const void* d_positions, 
  * advances as for a render (samples = n_views * width * height * iterations).  RPTGPU_VIEWS_PIECE (environment, read per
  * call; tests): the indices per piece.
  * NOT IN SCOPE: the tile partition and multi-GPU (a caller shards the VIEWS over handles: a view's pixels depend on nothing
- * else), the device-resident Buffer, the feature buffers and the denoiser for views, and the persistent path kernel.
+ * else), the device-resident Buffer and the denoiser for views, and the persistent path kernel (the views' feature buffers:
+ * rptgpu_render_views_aov, below).
  * RPTGPU_E_INVALID_ARGUMENT, checked before any device work and with a detail naming the reason: a NULL RptViewQuery, a
  * wrong struct_size, width, height or iterations == 0, max_bounces > 254, a precision_mode other than
  * RPT_PRECISION_F64_STRICT, RPT_FLAG_PERSISTENT, width * height > 2^32, NULL views or out with n_views > 0, frames whose
@@ -706,6 +707,83 @@ int rptgpu_render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views,
  * and the synchronisation rule are rptgpu_trace_rays_device's. */
 int rptgpu_render_views_device(rptgpu_scene* h, uint64_t n_views, const RptView* views /* host */, const RptViewQuery* q,
                                void* d_out, int out_is_f32, void* stream);
+
+/* ---- the first hit itself, for rays the caller supplies and for batches of views: distance, normal, object, position and
+ * albedo on host or device memory — depth sensors and lidar, picking, collision against the scene, callers that shade their
+ * own hits, the points and normals rptgpu_bake_ao and rptgpu_bake_probes consume; depth, normal, albedo and object maps of
+ * cube maps, light fields, orthographic and panoramic views.  Additions within ABI version 7, detected by symbol (dlsym
+ * "rptgpu_first_hits", "rptgpu_render_views_aov").  Both are DEFINED by rptgpu_closest_hit and run the closest-hit query of
+ * a render — rpt_extend's closest_hit, or the per-tree query for scenes with deep trees —, so a caller may replace
+ * rptgpu_closest_hit plus host arithmetic by them and keep every bit.
+ * FIRST HITS.  Ray i is origins[3i..], dirs[3i..] (f64, xyz interleaved), used as given: no normalisation, t_min = 1e-12, no
+ * origin offset — rptgpu_closest_hit's rules.  With (t_i, n_i, obj_i) = what rptgpu_closest_hit returns for ray i:
+ *   t[i]           = t_i                  (+inf on a miss; a NaN record — MonomialSurface reports one — stays NaN)
+ *   normal[i][c]   = n_i[c]
+ *   object[i]      = obj_i                (-1 on a miss)
+ *   position[i][c] = origins[i][c] + t_i * dirs[i][c] on a hit (obj_i >= 0): one multiply, then one add, never contracted
+ *                    (Ray::at, shape.rs:59-61 — rptgpu_render_aov's expression); +0.0 on a miss
+ *   albedo[i][c]   = objects[obj_i].material.color[c] on a hit; +0.0 on a miss
+ * A channel that `channels` does not name is not computed, its pointer is not read and its array is not written.  A ray's
+ * result depends on that ray and the scene and on nothing else: not on the other rays of the call, on their order, or on
+ * the pieces the library cuts the call into.  Input and output arrays must not overlap (not checked).  After a live update
+ * (rptgpu_scene_set_objects, _set_mesh, _set_group) the results are those of a handle freshly created from the updated
+ * scene.  48 B in and 8 / 24 / 4 / 24 / 24 B out per ray and channel (100 B with all five).
+ * ROUTE.  Scenes walked in-kernel: ONE kernel (rpt_first_hits) reads the caller's ray, finds its hit and writes the named
+ * channels straight into the caller's arrays; nothing goes through the path state.  Scenes with deep trees: rpt_raygen_rays
+ * lays a piece of the rays into the path state, the per-tree closest-hit query of a render runs over them (queues, ray sort,
+ * persistent traversal, the generic walker for trees of trees), rpt_hits_store writes the named channels.  A host caller's
+ * piece is staged on the device and runs the same kernels: no transpose on the CPU.  RPT_FLAG_GENERAL_TRAVERSAL and
+ * RPT_FLAG_PROFILE_KERNELS are honoured, RPT_FLAG_WAVEFRONT changes nothing.  RptStats: kernel_launches[RPT_K_EXTEND] advances
+ * by the queries (one per piece; kernel_ms[RPT_K_EXTEND] under RPT_FLAG_PROFILE_KERNELS) and total_ms by the call's wall time;
+ * extend_rays, shadow_rays and samples do not advance, as rptgpu_closest_hit advances none of them.  There is no CPU
+ * fallback: RPTGPU_E_NO_DEVICE.  RPTGPU_HITS_PIECE (environment, read per call; tests): the rays per piece.
+ * VIEWS.  rptgpu_render_views_aov is rptgpu_render_aov's sums for every view of a batch: every array of RptAovBuffers is
+ * [n_views][height][width] (x 3 where that struct says so), v in the order of `views`, and every element is written (a
+ * pixel without a hit: 0 everywhere, object = -1).  For view v, pixel p and s = 0 .. iterations-1 ascending, the ray is
+ * EXACTLY the ray rptgpu_render_views makes for (v, p, s) — the expressions of its block above, drawn from the stream keyed
+ * by seed + v*seed_stride with the counter (p, sample_index_base + s, draw block) —, and steps 2 to 4 of rptgpu_render_aov's
+ * contract follow: the sums are f64, start at +0.0 and add in ascending sample order; object is that of the call's first
+ * sample.  max_bounces and exposure_value are not read.  So view v under RPT_VIEW_PERSPECTIVE is rptgpu_render_aov of its
+ * camera over the full frame with seed + v*seed_stride, bit for bit; under the two other projections it is the header's
+ * rays through rptgpu_closest_hit, folded in that order.  A view's buffers depend on that view, the query and the scene and
+ * on nothing else.  The call always runs the wavefront kernels over rptgpu_render_views' pieces of consecutive (view, pixel)
+ * indices (RPTGPU_VIEWS_PIECE; a piece stays within a view when seed_stride != 0), each piece's samples in passes of
+ * rpt_raygen_views, the closest-hit query (rpt_extend, or the per-tree query) and rpt_views_aov_fold, which keeps index j's
+ * sums in the output arrays at j between passes.  RPT_FLAG_GENERAL_TRAVERSAL is honoured and changes no bit; RptStats:
+ * total_ms only.
+ * NOT IN SCOPE: a max_t cut or an early-out in the closest-hit query; primitive ids or barycentrics in the record (the
+ * walkers do not carry them); multi-hit; the tile partition and multi-GPU (a caller shards the rays or the views: a result
+ * depends on nothing else); the device-resident Buffer and the denoiser for views; the persistent kernel; rptgpu_closest_hit
+ * itself, which stays as it is and is not routed through this code.
+ * RPTGPU_E_INVALID_ARGUMENT, checked before any device work, with a detail naming the reason and with the output arrays
+ * untouched.  rptgpu_first_hits: a NULL RptHitQuery or RptHitArrays, a wrong struct_size of either, channels == 0 or an
+ * unknown RPT_HIT_* bit, reserved != 0, a named channel whose pointer is NULL, a precision_mode other than
+ * RPT_PRECISION_F64_STRICT, RPT_FLAG_PERSISTENT (the persistent kernel makes its rays from a camera), NULL origins or dirs
+ * with n > 0, a NULL handle.  rptgpu_render_views_aov: rptgpu_render_views' refusals for the query and the views,
+ * rptgpu_render_aov's for the buffers.  RPTGPU_E_COMM for an abandoned handle.  n == 0 / n_views == 0 returns RPTGPU_OK. */
+enum { RPT_HIT_T = 1u, RPT_HIT_NORMAL = 2u, RPT_HIT_OBJECT = 4u, RPT_HIT_POSITION = 8u, RPT_HIT_ALBEDO = 16u };
+typedef struct RptHitQuery {
+  uint32_t struct_size;       /* sizeof(RptHitQuery) */
+  uint32_t channels;          /* RPT_HIT_* wanted, at least one */
+  uint32_t precision_mode;    /* RPT_PRECISION_F64_STRICT */
+  uint32_t flags;             /* GENERAL_TRAVERSAL, PROFILE_KERNELS honoured; PERSISTENT refused */
+} RptHitQuery;
+typedef struct RptHitArrays {   /* one array per channel; a channel not named: pointer not read, array not written */
+  uint32_t struct_size;       /* sizeof(RptHitArrays) */
+  uint32_t reserved;          /* 0 */
+  double* t;                  /* [n] */
+  double* normal;             /* [n][3] */
+  int32_t* object;            /* [n] */
+  double* position;           /* [n][3] */
+  double* albedo;             /* [n][3] */
+} RptHitArrays;
+int rptgpu_first_hits(rptgpu_scene* h, uint64_t n, const double* origins /* [n][3] */, const double* dirs /* [n][3] */,
+                      const RptHitQuery* q, const RptHitArrays* out /* host arrays */);
+/* The same with every array in device memory (the two structs stay in host memory); `stream` and the synchronisation rule
+ * are rptgpu_trace_rays_device's (NULL means NO stream, not the null stream). */
+int rptgpu_first_hits_device(rptgpu_scene* h, uint64_t n, const void* d_origins, const void* d_dirs, const RptHitQuery* q,
+                             const RptHitArrays* d_out /* device arrays */, void* stream);
+/* (rptgpu_render_views_aov[_device] are declared behind RptAovBuffers, below) */
 
 /* ---- host utility: KdTree::new (kdtree.rs:108-119, construct kdtree.rs:235-345) over n
  * axis-aligned boxes (p_min xyz, p_max xyz interleaved: 6 doubles per box).  Returns the
@@ -823,6 +901,12 @@ typedef struct RptAovBuffers {        /* host arrays, row-major, top row first  
   int32_t* object;                    /* width*height                                                           */
 } RptAovBuffers;
 int rptgpu_render_aov(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams* params, const RptAovBuffers* out);
+/* rptgpu_render_aov's sums for every view of a batch: the contract stands with rptgpu_first_hits, above */
+int rptgpu_render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q,
+                            const RptAovBuffers* out /* host arrays, [n_views][height][width](x 3) */);
+/* The same into device arrays; `views`, q and the struct stay in host memory.  `stream` as for rptgpu_trace_rays_device. */
+int rptgpu_render_views_aov_device(rptgpu_scene* h, uint64_t n_views, const RptView* views /* host */, const RptViewQuery* q,
+                                   const RptAovBuffers* d_out /* device arrays */, void* stream);
 
 /* ---- feature-guided denoising of the device-resident Buffer: an edge-avoiding a-trous wavelet filter
  * (Dammertz et al. 2010) with the variance guidance of SVGF (Schied et al. 2017), run wholly on the device on what the

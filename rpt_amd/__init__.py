@@ -16,7 +16,8 @@ GpuScene.bake_ao bakes ambient occlusion (and bent normals) from directions draw
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401
 from ._abi import (RPT_AOV_ALBEDO, RPT_AOV_ALL, RPT_AOV_DEPTH, RPT_AOV_NORMAL, RPT_AOV_OBJECT,  # noqa: F401
-                   RPT_AOV_POSITION, RPT_PROBE_IRRADIANCE, RPT_PROBE_SH9, RPT_VIEW_ORTHOGRAPHIC, RPT_VIEW_PANORAMA,
+                   RPT_AOV_POSITION, RPT_HIT_ALBEDO, RPT_HIT_ALL, RPT_HIT_NORMAL, RPT_HIT_OBJECT, RPT_HIT_POSITION, RPT_HIT_T,
+                   RPT_PROBE_IRRADIANCE, RPT_PROBE_SH9, RPT_VIEW_ORTHOGRAPHIC, RPT_VIEW_PANORAMA,
                    RPT_VIEW_PERSPECTIVE)
 from .buffer import Buffer, Filter  # noqa: F401
 from .camera import Camera, View  # noqa: F401

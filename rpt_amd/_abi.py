@@ -44,6 +44,8 @@ RPT_AOV_DEPTH, RPT_AOV_NORMAL, RPT_AOV_ALBEDO, RPT_AOV_POSITION, RPT_AOV_OBJECT 
 RPT_AOV_ALL = 31
 RPT_PROBE_SH9, RPT_PROBE_IRRADIANCE = 0, 1
 RPT_VIEW_PERSPECTIVE, RPT_VIEW_ORTHOGRAPHIC, RPT_VIEW_PANORAMA = 0, 1, 2
+RPT_HIT_T, RPT_HIT_NORMAL, RPT_HIT_OBJECT, RPT_HIT_POSITION, RPT_HIT_ALBEDO = 1, 2, 4, 8, 16
+RPT_HIT_ALL = 31
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -202,6 +204,17 @@ class RptViewQuery(C.Structure):
                 ("flags", C.c_uint32)]
 
 
+class RptHitQuery(C.Structure):
+    """include/rpt_gpu.h RptHitQuery (rptgpu_first_hits' parameters; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("channels", C.c_uint32), ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RptHitArrays(C.Structure):
+    """include/rpt_gpu.h RptHitArrays (rptgpu_first_hits' output arrays, host or device; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("t", C.POINTER(f64)), ("normal", C.POINTER(f64)),
+                ("object", C.POINTER(C.c_int32)), ("position", C.POINTER(f64)), ("albedo", C.POINTER(f64))]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -244,6 +257,11 @@ SYMBOLS = [
     ("rptgpu_bake_ao_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptAoQuery), _VP, _VP, _VP]),
     ("rptgpu_render_views", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), _PD]),
     ("rptgpu_render_views_device", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), _VP, C.c_int, _VP]),
+    ("rptgpu_first_hits", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(RptHitQuery), C.POINTER(RptHitArrays)]),
+    ("rptgpu_first_hits_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, C.POINTER(RptHitQuery), C.POINTER(RptHitArrays), _VP]),
+    ("rptgpu_render_views_aov", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(RptAovBuffers)]),
+    ("rptgpu_render_views_aov_device", C.c_int,
+     [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(RptAovBuffers), _VP]),
     ("rptgpu_eval_math", C.c_int, [_VP, C.c_int, C.c_uint64, _PD, _PD, _PD]),
     ("rptgpu_kdtree_build", C.c_int, [_PD, C.c_uint64, C.POINTER(RptKdTree)]),
     ("rptgpu_kdtree_build_device", C.c_int, [_PD, C.c_uint64, C.c_int, C.POINTER(RptKdTree)]),

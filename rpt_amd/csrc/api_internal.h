@@ -21,6 +21,9 @@
 //                    driver, in pieces of consecutive (view, pixel) indices
 //   api_occlusion.cpp rptgpu_occluded[_device], rptgpu_bake_ao[_device]: the caller's rays, or points x directions made on the
 //                    device, through ONE visibility query of a render per pass (no depth loop), in pieces
+//   api_hits.cpp     rptgpu_first_hits[_device], rptgpu_render_views_aov[_device]: the first hit's record for the caller's rays
+//                    (one fused kernel, or the per-tree closest-hit query, in pieces) and rptgpu_render_aov's sums for
+//                    every view of a batch (raygen, closest-hit query and fold in passes over render_views' pieces)
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -182,6 +185,7 @@ struct rptgpu_scene {
   DevBuf<uint32_t> ray_ids;            // ... and the piece's stream ids (the caller's, or the rays' indices); rptgpu_bake_probes
                                        // stages a piece of probes in the same four (api_probes.cpp)
   DevBuf<uint8_t> occ_out;             // rptgpu_occluded: a piece of a host caller's answers (api_occlusion.cpp)
+  DevBuf<double> hits_out;             // rptgpu_first_hits: a piece of a host caller's records, the named channels back to back (api_hits.cpp)
   DevBuf<rptdev::View> view_recs;      // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<double> aov_out;              // rptgpu_render_aov: the requested channels' full-frame arrays, back to back (api_aov.cpp)
   int num_cus = 0;
@@ -364,6 +368,10 @@ struct RaySource {
   uint32_t view_width = 0, view_height = 0;
   uint64_t view_base = 0;
 };
+// api_views.cpp: what is wrong with an RptViewQuery / with one view of a call with query q (nullptr: nothing); shared with
+// rptgpu_render_views_aov (api_hits.cpp)
+const char* bad_view_query(const RptViewQuery* q);
+const char* bad_view(const RptView& v, const RptViewQuery& q);
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
 const char* bad_probe_query(const RptProbeQuery* q);

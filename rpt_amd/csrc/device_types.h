@@ -219,6 +219,17 @@ struct AovOut {
   uint32_t channels;
 };
 
+// rptgpu_first_hits' device outputs (kernels/hits.inc): the arrays of RptHitArrays, offset to the piece and indexed by the
+// ray's position in it.  Only the arrays of the channels named in `channels` (RPT_HIT_*) exist.
+struct HitOut {
+  double* t;        // [n]
+  double* normal;   // [n][3]
+  int32_t* object;  // [n]
+  double* position; // [n][3]
+  double* albedo;   // [n][3]
+  uint32_t channels;
+};
+
 // rptgpu_buffer_denoise's working set (kernels/denoise.inc): f64 COLUMNS of `stride` elements indexed by pixel, so that
 // the 64 lanes of a wave (64 consecutive x of one row) read a tap's value as one contiguous segment at any tap spacing.
 // Constant over the levels: the means of the held features and the hit flag.  Per level: colour and variance in, out.

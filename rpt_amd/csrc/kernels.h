@@ -201,6 +201,17 @@ struct KernelTable {
   void (*occ_store)(hipStream_t, const rptdev::PathState&, const double* srt, uint32_t n, uint8_t* out);
   void (*ao_fold)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, const double* srt, uint32_t n_samples, bool first,
                   bool last, uint32_t samples, double* out_ao, double* out_bent);
+  // first-hit records for the caller (rptgpu_first_hits, rptgpu_render_views_aov; kernels/hits.inc).  first_hits: n rays of
+  // the caller ([n][3] f64 on the device), the closest hit of each and the channels of out.channels into out's arrays at the
+  // ray's index, in one kernel (scenes walked in-kernel).  hits_store: the same channels from the records of the n rays
+  // rpt_raygen_rays laid into ps (one sample), behind the per-tree query.  views_aov_fold: aov_fold for a piece of a batch
+  // of views — a pass's hits (slot = s * n + j) into the sums at index j of out's arrays; first = the pass holds the call's
+  // first sample
+  void (*first_hits)(hipStream_t, const rptdev::Scene&, const double* origins, const double* dirs, uint32_t n,
+                     const rptdev::HitOut& out);
+  void (*hits_store)(hipStream_t, const rptdev::Scene&, const rptdev::PathState&, uint32_t n, const rptdev::HitOut& out);
+  void (*views_aov_fold)(hipStream_t, const rptdev::Scene&, const rptdev::PathState&, const rptdev::AovOut& out, uint32_t n,
+                         uint32_t spp, bool first);
 };
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)

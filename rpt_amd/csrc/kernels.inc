@@ -34,6 +34,8 @@
 //   denoise.inc    the device Buffer's feature-guided à-trous filter (rpt_denoise_prepare / _level / _finish), DESIGN.md §12
 //   occlusion.inc  rptgpu_occluded / rptgpu_bake_ao: the caller's rays into a depth's shadow-ray state and their answers out of it
 //                  (rpt_occ_load, rpt_raygen_ao, rpt_occ_store, rpt_ao_fold), DESIGN.md §16
+//   hits.inc       rptgpu_first_hits / rptgpu_render_views_aov: the closest-hit record into the caller's layout (rpt_first_hits
+//                  fused, rpt_hits_store behind the per-tree query, rpt_views_aov_fold), DESIGN.md §17
 //   launch.inc     explicit instantiations, host-side launchers, the KernelTable the api_*.cpp files call through
 //
 // Wave64 throughout (gfx950): queue appends and work fetches use one 64-bit ballot + one atomic per wave.
@@ -108,6 +110,7 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/aov.inc"
 #include "kernels/denoise.inc"
 #include "kernels/occlusion.inc"
+#include "kernels/hits.inc"
 #include "kernels/launch.inc"
 
 } // namespace RPT_NS

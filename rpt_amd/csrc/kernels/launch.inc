@@ -309,6 +309,18 @@ void launch_ao_fold(hipStream_t st, const Frame& fr, const PathState& ps, const 
                      out_ao, out_bent);
 }
 
+// rptgpu_first_hits / rptgpu_render_views_aov (kernels/hits.inc): the closest-hit record into the caller's layout
+void launch_first_hits(hipStream_t st, const Scene& sc, const double* origins, const double* dirs, uint32_t n, const HitOut& out) {
+  hipLaunchKernelGGL(rpt_first_hits, grid_for(n), dim3(256), 0, st, sc, origins, dirs, n, out);
+}
+void launch_hits_store(hipStream_t st, const Scene& sc, const PathState& ps, uint32_t n, const HitOut& out) {
+  hipLaunchKernelGGL(rpt_hits_store, grid_for(n), dim3(256), 0, st, sc, ps, n, out);
+}
+void launch_views_aov_fold(hipStream_t st, const Scene& sc, const PathState& ps, const AovOut& out, uint32_t n, uint32_t spp,
+                           bool first) {
+  hipLaunchKernelGGL(rpt_views_aov_fold, grid_for(n), dim3(256), 0, st, sc, ps, out, n, spp, first ? 1 : 0);
+}
+
 // blocks of 64 x 4 pixels: a wave is 64 consecutive x of one row (kernels/denoise.inc)
 static inline dim3 grid_rows(uint32_t w, uint32_t h) { return dim3((w + 63u) / 64u, (h + 3u) / 4u); }
 void launch_denoise_prepare(hipStream_t st, const double* total, const uint32_t* counts, const double* m2, const AovOut& feat,
@@ -348,5 +360,6 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            read_prof, launch_path_reorder, launch_aov, launch_aov_fold,
                            launch_denoise_prepare, launch_denoise_level, launch_denoise_finish,
                            launch_raygen_probes, launch_resolve_probes, launch_finish_probes, launch_raygen_views,
-                           launch_occ_load, launch_raygen_ao, launch_occ_store, launch_ao_fold};
+                           launch_occ_load, launch_raygen_ao, launch_occ_store, launch_ao_fold,
+                           launch_first_hits, launch_hits_store, launch_views_aov_fold};
 #endif // !__HIP_DEVICE_COMPILE__

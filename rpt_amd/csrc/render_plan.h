@@ -1,7 +1,8 @@
 // render_plan.h — how a render call is cut into launches (persistent pipeline) and passes (wavefront pipeline): the
 // arithmetic behind api_render.cpp's drivers, as pure host functions of numbers (tests/cpp/render_plan_check.cpp), and the
 // pieces rptgpu_trace_rays cuts its rays into (tests/cpp/rays_piece_check.cpp) and rptgpu_render_views its views' pixels
-// (tests/cpp/views_piece_check.cpp), rptgpu_occluded its rays and rptgpu_bake_ao its points (tests/cpp/occlusion_piece_check.cpp).
+// (tests/cpp/views_piece_check.cpp), rptgpu_occluded its rays and rptgpu_bake_ao its points (tests/cpp/occlusion_piece_check.cpp),
+// rptgpu_first_hits its rays (tests/cpp/hits_piece_check.cpp).
 #pragma once
 #include <stdint.h>
 
@@ -221,6 +222,21 @@ inline uint64_t ao_piece(uint64_t n, uint64_t asked, uint32_t samples, uint64_t 
 // the directions per point of the next pass of a piece of `points` points with `remaining` directions to go
 inline uint32_t ao_pass_samples(uint64_t points, uint32_t remaining, uint64_t pass_target) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(remaining, occlusion_pass_max(pass_target) / std::max<uint64_t>(1, points)));
+}
+
+// ---- rptgpu_first_hits: the caller's n rays in runs of hits_piece consecutive rays, each run one closest-hit query.
+// pass_bound: the rays one query may hold — for scenes with deep trees plan_pass's target with ONE record column per path (the
+// rays are laid into the workspace's slots and no depth follows), for scenes walked in-kernel no bound at all (~0: the fused
+// kernel touches no workspace).  Either way a piece's indices fit 32 bits and it is at most HITS_PIECE_MAX rays, what
+// rptgpu_closest_hit takes at a time: a host caller stages 48 B of ray and up to 100 B of record per ray.  asked:
+// RPTGPU_HITS_PIECE (tests; 0 = not set), within the same bound.  Never 0, so `for (base = 0; base < n; base += piece)` ends.
+constexpr uint64_t HITS_PIECE_MAX = RAYS_PIECE_MAX;
+inline uint64_t hits_pass_max(uint64_t pass_bound) {
+  return std::max<uint64_t>(1, std::min<uint64_t>(pass_bound, std::min<uint64_t>(RPT_MAX_PATHS_PER_PASS, HITS_PIECE_MAX)));
+}
+inline uint64_t hits_piece(uint64_t n, uint64_t asked, uint64_t pass_bound) {
+  const uint64_t fit = hits_pass_max(pass_bound);
+  return std::max<uint64_t>(1, std::min(std::min<uint64_t>(n, asked ? asked : fit), fit));
 }
 
 } // namespace rptplan

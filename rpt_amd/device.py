@@ -675,16 +675,7 @@ class GpuScene:
         tensor on the handle's device, which is written where it lies (rptgpu_render_views_device)."""
         views = list(views)
         n, width, height = len(views), int(width), int(height)
-        arr = (_abi.RptView * max(n, 1))()
-        for i, v in enumerate(views):
-            if isinstance(v, _abi.RptView):
-                arr[i] = v
-            elif hasattr(v, "projection"):
-                arr[i] = v.lower()
-            elif hasattr(v, "lower"):
-                arr[i].camera, arr[i].projection = v.lower(), _abi.RPT_VIEW_PERSPECTIVE
-            else:
-                raise TypeError("render_views: view %d is a %s, not a View, a Camera or an RptView" % (i, type(v).__name__))
+        arr = self._lower_views(views, "render_views")
         q = _abi.RptViewQuery()
         q.struct_size = C.sizeof(_abi.RptViewQuery)
         q.width, q.height, q.max_bounces, q.iterations = width, height, int(max_bounces), int(samples)
@@ -714,6 +705,164 @@ class GpuScene:
         code = self.lib.rptgpu_render_views(self.handle, n, arr, C.byref(q), out.ctypes.data_as(C.POINTER(C.c_double)))
         _abi.check(code, self.handle)
         return out
+
+    _HIT_CHANNELS = ((_abi.RPT_HIT_T, "t", (), np.float64), (_abi.RPT_HIT_NORMAL, "normal", (3,), np.float64),
+                     (_abi.RPT_HIT_OBJECT, "object", (), np.int32), (_abi.RPT_HIT_POSITION, "position", (3,), np.float64),
+                     (_abi.RPT_HIT_ALBEDO, "albedo", (3,), np.float64))
+
+    def first_hits(self, origins, dirs, channels=_abi.RPT_HIT_ALL, flags=0):
+        """The first hit of each of the caller's rays (rptgpu_first_hits) -> a dict with one array per
+        channel of `channels` (RPT_HIT_*): `t` (n,) float64 — closest_hit's, +inf on a miss —, `normal` (n, 3), `object`
+        (n,) int32 (-1 on a miss), `position` (n, 3) = origin + t * dir on a hit and +0.0 on a miss, `albedo` (n, 3) = the
+        hit object's material colour, +0.0 on a miss.  origins, dirs: (n, 3) float64, used as given.  numpy arrays go
+        through host memory; torch tensors on the handle's device are read where they lie (rptgpu_first_hits_device) and
+        the results are new tensors there."""
+        q = _abi.RptHitQuery()
+        q.struct_size, q.channels = C.sizeof(_abi.RptHitQuery), int(channels)
+        q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        a = _abi.RptHitArrays()
+        a.struct_size, a.reserved = C.sizeof(_abi.RptHitArrays), 0
+        named = [c for c in self._HIT_CHANNELS if q.channels & c[0]]
+        if hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr"):
+            return self._first_hits_torch(origins, dirs, q, a, named)
+
+        def vectors(v, what):
+            v = np.asarray(v)
+            if v.dtype != np.float64 or v.ndim != 2 or v.shape[1] != 3:
+                raise ValueError("first_hits: %s must be an (n, 3) float64 array" % what)
+            return np.ascontiguousarray(v)
+
+        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
+        n = len(o)
+        if len(d) != n:
+            raise ValueError("first_hits: %d origins for %d directions" % (n, len(d)))
+        out = {}
+        types = dict(_abi.RptHitArrays._fields_)
+        for _, name, tail, dtype in named:
+            out[name] = np.empty((n,) + tail, dtype=dtype)
+            setattr(a, name, out[name].ctypes.data_as(types[name]))
+        PD = C.POINTER(C.c_double)
+        code = self.lib.rptgpu_first_hits(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD), C.byref(q), C.byref(a))
+        _abi.check(code, self.handle)
+        return out
+
+    def _first_hits_torch(self, origins, dirs, q, a, named):
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def vectors(t, what):
+            if not isinstance(t, torch.Tensor) or t.device != dev:
+                raise ValueError("first_hits: %s must be a torch tensor on %s, like the other array" % (what, dev))
+            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
+                raise ValueError("first_hits: %s must be an (n, 3) float64 tensor" % what)
+            return t.contiguous()  # (no copy when it already is)
+
+        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("first_hits: %d origins for %d directions" % (n, d.shape[0]))
+        out = {}
+        types = dict(_abi.RptHitArrays._fields_)
+        for _, name, tail, dtype in named:
+            # (at least one element: an empty tensor has no address, and a named channel's pointer must not be NULL)
+            room = torch.empty((max(n, 1),) + tail, dtype=torch.int32 if dtype is np.int32 else torch.float64, device=dev)
+            out[name] = room[:n]
+            setattr(a, name, C.cast(C.c_void_p(room.data_ptr()), types[name]))
+        # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
+        # stream is waited for here)
+        current = torch.cuda.current_stream(dev)
+        stream = current.cuda_stream
+        if not stream:
+            current.synchronize()
+        code = self.lib.rptgpu_first_hits_device(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.byref(q),
+                                                 C.byref(a), C.c_void_p(stream or 0))
+        _abi.check(code, self.handle)
+        return out
+
+    def render_views_aov(self, views, width, height, samples=1, seed=0x52505447, seed_stride=0, sample_index_base=0,
+                         channels=_abi.RPT_AOV_ALL, flags=0, out=None):
+        """First-hit feature buffers of a batch of views (rptgpu_render_views_aov) -> a dict as render_aov's
+        with the views as the leading axis: `hits` (n, H, W) uint32 always, and per channel of `channels` (RPT_AOV_*) the
+        f64 sums over the hits of `samples` rays per pixel — `depth` (n, H, W), `normal` / `albedo` / `position` (n, H, W,
+        3) — and `object` (n, H, W) int32.  views, seed, seed_stride, sample_index_base: render_views'; view v's rays are
+        the rays render_views makes for it, so a perspective view is render_aov of its camera with seed + v * seed_stride.
+        out: None (new numpy arrays through host memory) or a dict of C-contiguous numpy arrays with exactly the keys
+        above; or "torch" for new tensors on the handle's device, or a dict of contiguous torch tensors there, written
+        where they lie (rptgpu_render_views_aov_device; `hits` as the 32 bits of an int32 tensor)."""
+        views = list(views)
+        n, width, height, channels = len(views), int(width), int(height), int(channels)
+        arr = self._lower_views(views, "render_views_aov")
+        q = _abi.RptViewQuery()
+        q.struct_size = C.sizeof(_abi.RptViewQuery)
+        q.width, q.height, q.max_bounces, q.iterations = width, height, 0, int(samples)
+        q.exposure_value, q.seed, q.seed_stride = 0.0, int(seed), int(seed_stride)
+        q.sample_index_base, q.precision_mode, q.flags = int(sample_index_base), _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        layout = [("hits", (n, height, width), np.uint32)]
+        for bit, name, tail, dtype in ((_abi.RPT_AOV_DEPTH, "depth", (), np.float64),
+                                       (_abi.RPT_AOV_NORMAL, "normal", (3,), np.float64),
+                                       (_abi.RPT_AOV_ALBEDO, "albedo", (3,), np.float64),
+                                       (_abi.RPT_AOV_POSITION, "position", (3,), np.float64),
+                                       (_abi.RPT_AOV_OBJECT, "object", (), np.int32)):
+            if channels & bit:
+                layout.append((name, (n, height, width) + tail, dtype))
+        b = _abi.RptAovBuffers()
+        b.struct_size, b.channels = C.sizeof(_abi.RptAovBuffers), channels
+        types = dict(_abi.RptAovBuffers._fields_)
+        host = isinstance(out, dict) and all(isinstance(v, np.ndarray) for v in out.values())
+        if out is None or host:
+            arrays = dict(out) if host else {name: np.zeros(shape, dtype=dtype) for name, shape, dtype in layout}
+            if set(arrays) != {name for name, _, _ in layout}:
+                raise ValueError("render_views_aov: out must have exactly the keys %s" % sorted(name for name, _, _ in layout))
+            for name, shape, dtype in layout:
+                v = arrays[name]
+                if not (v.dtype == dtype and v.shape == shape and v.flags.c_contiguous):
+                    raise ValueError("render_views_aov: out[%r] must be a C-contiguous %s %s array" % (name, shape, np.dtype(dtype)))
+            for name, v in arrays.items():
+                setattr(b, name, v.ctypes.data_as(types[name]))
+            _abi.check(self.lib.rptgpu_render_views_aov(self.handle, n, arr, C.byref(q), C.byref(b)), self.handle)
+            return arrays
+        import torch
+        dev = torch.device("cuda", self.device)
+        tdt = {np.uint32: torch.int32, np.int32: torch.int32, np.float64: torch.float64}  # (hits: its 32 bits in an int32 tensor)
+        if isinstance(out, str):
+            if out != "torch":
+                raise ValueError('render_views_aov: out must be None, "torch" or a dict of torch tensors')
+            # (at least one view's worth: an empty tensor has no address, and `hits` must not be NULL)
+            room = {name: torch.zeros((max(n, 1),) + shape[1:], dtype=tdt[dtype], device=dev) for name, shape, dtype in layout}
+            arrays = {name: t[:n] for name, t in room.items()}
+        else:
+            arrays = dict(out)
+            if set(arrays) != {name for name, _, _ in layout}:
+                raise ValueError("render_views_aov: out must have exactly the keys %s" % sorted(name for name, _, _ in layout))
+            for name, shape, dtype in layout:
+                t = arrays[name]
+                if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == tdt[dtype] and tuple(t.shape) == shape
+                        and t.is_contiguous()):
+                    raise ValueError("render_views_aov: out[%r] must be a contiguous %s %s tensor on %s"
+                                     % (name, shape, tdt[dtype], dev))
+        for name, t in (room if isinstance(out, str) else arrays).items():
+            setattr(b, name, C.cast(C.c_void_p(t.data_ptr()), types[name]))
+        current = torch.cuda.current_stream(dev)  # (the null-stream rule of _trace_rays_torch)
+        stream = current.cuda_stream
+        if not stream:
+            current.synchronize()
+        code = self.lib.rptgpu_render_views_aov_device(self.handle, n, arr, C.byref(q), C.byref(b), C.c_void_p(stream or 0))
+        _abi.check(code, self.handle)
+        return arrays
+
+    @staticmethod
+    def _lower_views(views, who):
+        arr = (_abi.RptView * max(len(views), 1))()
+        for i, v in enumerate(views):
+            if isinstance(v, _abi.RptView):
+                arr[i] = v
+            elif hasattr(v, "projection"):
+                arr[i] = v.lower()
+            elif hasattr(v, "lower"):
+                arr[i].camera, arr[i].projection = v.lower(), _abi.RPT_VIEW_PERSPECTIVE
+            else:
+                raise TypeError("%s: view %d is a %s, not a View, a Camera or an RptView" % (who, i, type(v).__name__))
+        return arr
 
     def render_aov(self, camera, params, channels=_abi.RPT_AOV_ALL):
         """First-hit feature buffers (rptgpu_render_aov) -> a dict of numpy arrays: `hits` (H, W) uint32

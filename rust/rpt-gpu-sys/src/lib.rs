@@ -380,6 +380,35 @@ pub mod ffi {
         pub flags: u32,
     }
 
+    pub const RPT_HIT_T: u32 = 1;
+    pub const RPT_HIT_NORMAL: u32 = 2;
+    pub const RPT_HIT_OBJECT: u32 = 4;
+    pub const RPT_HIT_POSITION: u32 = 8;
+    pub const RPT_HIT_ALBEDO: u32 = 16;
+
+    /// `RptHitQuery` (the parameters of `rptgpu_first_hits`; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptHitQuery {
+        pub struct_size: u32,
+        pub channels: u32,
+        pub precision_mode: u32,
+        pub flags: u32,
+    }
+
+    /// `RptHitArrays` (the output arrays of `rptgpu_first_hits`, host or device; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug)]
+    pub struct RptHitArrays {
+        pub struct_size: u32,
+        pub reserved: u32,
+        pub t: *mut f64,
+        pub normal: *mut f64,
+        pub object: *mut i32,
+        pub position: *mut f64,
+        pub albedo: *mut f64,
+    }
+
     /// opaque `rptgpu_scene`
     #[repr(C)]
     pub struct rptgpu_scene {
@@ -439,6 +468,10 @@ pub mod ffi {
         pub fn rptgpu_buffer_sample_adaptive(b: *mut rptgpu_buffer, camera: *const RptCamera, params: *const RptRenderParams, a: *const RptAdaptive, out_active: *mut u32) -> c_int;
         pub fn rptgpu_buffer_sample_counts(b: *const rptgpu_buffer, out_counts: *mut u32) -> c_int;
         pub fn rptgpu_buffer_totals(b: *const rptgpu_buffer, out_totals: *mut f64) -> c_int;
+        pub fn rptgpu_first_hits(h: *mut rptgpu_scene, n: u64, origins: *const f64, dirs: *const f64, q: *const RptHitQuery, out: *const RptHitArrays) -> c_int;
+        pub fn rptgpu_first_hits_device(h: *mut rptgpu_scene, n: u64, d_origins: *const c_void, d_dirs: *const c_void, q: *const RptHitQuery, d_out: *const RptHitArrays, stream: *mut c_void) -> c_int;
+        pub fn rptgpu_render_views_aov(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, out: *const RptAovBuffers) -> c_int;
+        pub fn rptgpu_render_views_aov_device(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, d_out: *const RptAovBuffers, stream: *mut c_void) -> c_int;
         pub fn rptgpu_render_aov(h: *mut rptgpu_scene, camera: *const RptCamera, params: *const RptRenderParams, out: *const RptAovBuffers) -> c_int;
         pub fn rptgpu_buffer_features(b: *mut rptgpu_buffer, camera: *const RptCamera, params: *const RptRenderParams) -> c_int;
         pub fn rptgpu_buffer_feature_sums(b: *const rptgpu_buffer, out: *const RptAovBuffers) -> c_int;
@@ -810,6 +843,8 @@ mod layout_tests {
         assert_eq!(size_of::<RptAoQuery>(), 40);
         assert_eq!(size_of::<RptView>(), 112);
         assert_eq!(size_of::<RptViewQuery>(), 64);
+        assert_eq!(size_of::<RptHitQuery>(), 16);
+        assert_eq!(size_of::<RptHitArrays>(), 48);
     }
 
     #[test]
