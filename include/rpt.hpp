@@ -792,6 +792,19 @@ class Renderer {
     check(rptgpu_render_views(handle_, views.size(), views.data(), &q, out.data()));
     return out;
   }
+  // ... with a seed per view (rptgpu_render_views_seeded): view v renders as with set_seed(seeds[v]) and no stride — a data
+  // set resumed, one view of an earlier job again, seeds of the caller's own generator.  One seed per view.
+  std::vector<double> render_views(const std::vector<RptView>& views, const std::vector<uint64_t>& seeds,
+                                   uint64_t sample_index_base = 0) {
+    ensure_scene();
+    if (seeds.size() != views.size()) throw std::invalid_argument("render_views: one seed per view");
+    RptViewQuery q{};
+    q.struct_size = sizeof(RptViewQuery); q.width = width_; q.height = height_; q.max_bounces = max_bounces_;
+    q.iterations = num_samples_; q.exposure_value = ev_; q.sample_index_base = sample_index_base;
+    std::vector<double> out(views.size() * (size_t)width_ * height_ * 3);
+    check(rptgpu_render_views_seeded(handle_, views.size(), views.data(), &q, seeds.data(), out.data()));
+    return out;
+  }
   // addition: the first hit of rays of the caller's own making (rptgpu_first_hits, include/rpt_gpu.h): depth sensors,
   // picking, collision, points and normals for bake_ao / bake_probes.  origins, dirs: xyz per ray, used as given.  -> per ray
   // rptgpu_closest_hit's t (+inf on a miss), normal and object (-1 on a miss), position = origin + t * dir and albedo = the
@@ -827,6 +840,18 @@ class Renderer {
   // (x 3); view v draws with seed + v * seed_stride.  A perspective view's buffers are render_aovs' of that camera.
   Aovs render_views_aov(const std::vector<RptView>& views, uint64_t seed_stride = 0, uint64_t sample_index_base = 0,
                         uint32_t channels = RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION | RPT_AOV_OBJECT) {
+    return views_aov(views, nullptr, seed_stride, sample_index_base, channels);
+  }
+  // ... with a seed per view (rptgpu_render_views_aov_seeded), as render_views' overload
+  Aovs render_views_aov(const std::vector<RptView>& views, const std::vector<uint64_t>& seeds, uint64_t sample_index_base = 0,
+                        uint32_t channels = RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION | RPT_AOV_OBJECT) {
+    if (seeds.size() != views.size()) throw std::invalid_argument("render_views_aov: one seed per view");
+    return views_aov(views, &seeds, 0, sample_index_base, channels);
+  }
+
+ private:
+  Aovs views_aov(const std::vector<RptView>& views, const std::vector<uint64_t>* seeds, uint64_t seed_stride,
+                 uint64_t sample_index_base, uint32_t channels) {
     ensure_scene();
     RptViewQuery q{};
     q.struct_size = sizeof(RptViewQuery); q.width = width_; q.height = height_; q.iterations = num_samples_;
@@ -844,9 +869,12 @@ class Renderer {
     b.struct_size = sizeof(RptAovBuffers); b.channels = channels;
     b.hits = a.hits.data(); b.depth = a.depth.data(); b.normal = a.normal.data(); b.albedo = a.albedo.data();
     b.position = a.position.data(); b.object = a.object.data();
-    check(rptgpu_render_views_aov(handle_, views.size(), views.data(), &q, &b));
+    if (seeds) check(rptgpu_render_views_aov_seeded(handle_, views.size(), views.data(), &q, seeds->data(), &b));
+    else check(rptgpu_render_views_aov(handle_, views.size(), views.data(), &q, &b));
     return a;
   }
+
+ public:
   // addition: iterative_render with the Buffer kept on the device (rptgpu_buffer_*), followed by the feature-guided
   // a-trous filter of rptgpu_buffer_denoise (include/rpt_gpu.h) guided by the first hits of samples 0 .. feature_samples-1.
   // At least two batches (num_samples > callback_interval), else the library refuses: one batch has no variance.

@@ -630,10 +630,9 @@ int rptgpu_bake_ao_device(rptgpu_scene* h, uint64_t n, const void* d_positions, 
  * panoramas in exactly Hdri::get_color's convention (environment.rs:25-52), so that a rendered panorama is a valid
  * RptEnvironment texel array: one scene captured as the environment of another.  Additions within ABI version 7, detected
  * by symbol (dlsym "rptgpu_render_views").  The rays are made on the device from each pixel's own Philox stream (96 + 16 B
- * per VIEW in, 24 B per pixel out, whatever the sample count).  With seed_stride == 0 the views of a call share the
- * launches and the host waits of the wavefront pipeline's depth loop, which a small frame on its own cannot fill; with
- * seed_stride != 0 every view runs as a piece of its own — the per-view loop behind one call, with the same results and
- * no such sharing.
+ * per VIEW in, 24 B per pixel out, whatever the sample count).  The views of a call share the launches and the host waits
+ * of the wavefront pipeline's depth loop, which a small frame on its own cannot fill — whatever their seeds: where the
+ * views' seeds differ (seed_stride != 0, or the _seeded entry points of rpt_gpu_views_seeded.h) the seed travels with the path.
  * out[v][y][x][c], row-major, top row first, v in the order of `views`.
  * THE STREAM CONTRACT.  Sample s of pixel p = y*width + x of view v draws from the Philox4x32-10 stream keyed by
  * seed + v*seed_stride (wrapping in 64 bits) with the counter (p, sample_index_base + s, draw block), from draw 0 on; its
@@ -666,8 +665,11 @@ int rptgpu_bake_ao_device(rptgpu_scene* h, uint64_t n, const void* d_positions, 
  *                          dir = (ce*c, se, ce*s); origin = eye.  Every argument stays within rpt_sincos_pio2's
  *                          |x| < 3 pi / 4 (include/rpt_math.h).  direction, up, fov, aperture, focal_distance: not read.
  * The call always runs the wavefront pipeline, as rptgpu_trace_rays does, sized and restarted like a render's passes, over
- * pieces of consecutive (view, pixel) indices (when seed_stride != 0 a piece stays within one view: a piece's passes run
- * under one seed, so views with seeds of their own share no launch);
+ * pieces of consecutive (view, pixel) indices (a piece begins and ends wherever the piece size says, inside a view or at
+ * its border, whatever the views' seeds: with seeds that differ, rpt_raygen_views_seeded and rpt_shade_seeded run in
+ * rpt_raygen_views' and rpt_shade's places and read the seed of each index of the piece, 8 B per index more, and the
+ * first of them is launched once for every view a pass's piece holds — RptStats counts at least one RPT_K_RAYGEN launch per
+ * view rendered under a seed of its own, while the depth loop behind it is the piece's and shared);
  * RPT_FLAG_GENERAL_TRAVERSAL and RPT_FLAG_PROFILE_KERNELS are honoured, RPT_FLAG_WAVEFRONT changes nothing, and RptStats
  * advances as for a render (samples = n_views * width * height * iterations).  RPTGPU_VIEWS_PIECE (environment, read per
  * call; tests): the indices per piece.
@@ -707,6 +709,10 @@ int rptgpu_render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views,
  * and the synchronisation rule are rptgpu_trace_rays_device's. */
 int rptgpu_render_views_device(rptgpu_scene* h, uint64_t n_views, const RptView* views /* host */, const RptViewQuery* q,
                                void* d_out, int out_is_f32, void* stream);
+/* A SEED PER VIEW (seeds[v] in place of seed + v*seed_stride: resuming a data set, rendering one view of an earlier job
+ * again, seeds from the caller's own generator): rptgpu_render_views_seeded and rptgpu_render_views_seeded_device, optional
+ * additions within ABI version 7 that are detected by symbol — declared and defined in rpt_gpu_views_seeded.h, which this
+ * file includes at its end. */
 
 /* ---- the first hit itself, for rays the caller supplies and for batches of views: distance, normal, object, position and
  * albedo on host or device memory — depth sensors and lidar, picking, collision against the scene, callers that shade their
@@ -747,8 +753,8 @@ int rptgpu_render_views_device(rptgpu_scene* h, uint64_t n_views, const RptView*
  * camera over the full frame with seed + v*seed_stride, bit for bit; under the two other projections it is the header's
  * rays through rptgpu_closest_hit, folded in that order.  A view's buffers depend on that view, the query and the scene and
  * on nothing else.  The call always runs the wavefront kernels over rptgpu_render_views' pieces of consecutive (view, pixel)
- * indices (RPTGPU_VIEWS_PIECE; a piece stays within a view when seed_stride != 0), each piece's samples in passes of
- * rpt_raygen_views, the closest-hit query (rpt_extend, or the per-tree query) and rpt_views_aov_fold, which keeps index j's
+ * indices (RPTGPU_VIEWS_PIECE; whatever the views' seeds), each piece's samples in passes of
+ * rpt_raygen_views (views with seeds that differ: rpt_raygen_views_seeded), the closest-hit query (rpt_extend, or the per-tree query) and rpt_views_aov_fold, which keeps index j's
  * sums in the output arrays at j between passes.  RPT_FLAG_GENERAL_TRAVERSAL is honoured and changes no bit; RptStats:
  * total_ms only.
  * NOT IN SCOPE: a max_t cut or an early-out in the closest-hit query; primitive ids or barycentrics in the record (the
@@ -907,6 +913,7 @@ int rptgpu_render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* vi
 /* The same into device arrays; `views`, q and the struct stay in host memory.  `stream` as for rptgpu_trace_rays_device. */
 int rptgpu_render_views_aov_device(rptgpu_scene* h, uint64_t n_views, const RptView* views /* host */, const RptViewQuery* q,
                                    const RptAovBuffers* d_out /* device arrays */, void* stream);
+/* A SEED PER VIEW: rptgpu_render_views_aov_seeded and rptgpu_render_views_aov_seeded_device, in rpt_gpu_views_seeded.h. */
 
 /* ---- feature-guided denoising of the device-resident Buffer: an edge-avoiding a-trous wavelet filter
  * (Dammertz et al. 2010) with the variance guidance of SVGF (Schied et al. 2017), run wholly on the device on what the
@@ -1012,6 +1019,9 @@ int rptgpu_get_stats(const rptgpu_scene* h, RptStats* out);
 int rptgpu_reset_stats(rptgpu_scene* h);
 /* name of kernel kind k as it appears in a rocprofv3 kernel trace */
 const char* rptgpu_kernel_name(int k);
+
+/* ---- optional additions within ABI version 7, detected by symbol: a seed per view for the batches of views ---- */
+#include "rpt_gpu_views_seeded.h"
 
 #ifdef __cplusplus
 }

@@ -291,6 +291,18 @@ SYMBOLS = [
     ("rptgpu_monomial_closest_point", C.c_int, [C.c_int, f64, C.c_uint32, C.c_uint64, _PD, _PD]),
     ("rptgpu_particles_eval_hypot", C.c_int, [C.c_int, C.c_uint64, _PD, _PD, _PD]),
 ]
+# ... and every symbol include/rpt_gpu_views_seeded.h declares: the optional additions within ABI 7 that a binding detects by
+# symbol.  This package's own library always has them, so load_library binds them like the rest
+SEEDED_SYMBOLS = [
+    ("rptgpu_render_views_seeded", C.c_int,
+     [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(C.c_uint64), _PD]),
+    ("rptgpu_render_views_seeded_device", C.c_int,
+     [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(C.c_uint64), _VP, C.c_int, _VP]),
+    ("rptgpu_render_views_aov_seeded", C.c_int,
+     [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(C.c_uint64), C.POINTER(RptAovBuffers)]),
+    ("rptgpu_render_views_aov_seeded_device", C.c_int,
+     [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(C.c_uint64), C.POINTER(RptAovBuffers), _VP]),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -315,7 +327,7 @@ def load_library(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % p)
     lib = C.CDLL(p)
-    for name, restype, argtypes in SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + SEEDED_SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

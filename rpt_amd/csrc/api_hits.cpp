@@ -1,4 +1,4 @@
-// api_hits.cpp — rptgpu_first_hits[_device] and rptgpu_render_views_aov[_device]: the first hit's record for the caller
+// api_hits.cpp — rptgpu_first_hits[_device] and rptgpu_render_views_aov[_seeded][_device]: the first hit's record for the caller
 // (include/rpt_gpu.h; see api_internal.h).  Both run ONE closest-hit query of a render per piece or pass —
 // closest_hit<KdLdsW> inside a kernel for scenes walked in-kernel, query_closest for scenes with deep trees, chosen as
 // render_wavefront's run_pass chooses — and carry its record into the caller's layout (kernels/hits.inc): the channels of a
@@ -183,13 +183,15 @@ RptAovBuffers aov_buffers_at(const RptAovBuffers& a, uint64_t base) {
 }
 
 // out's arrays: host memory, or — on_device — device memory (user_stream: the stream their producer ran on); views and the
-// structs are host memory either way
-int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, const RptAovBuffers* out,
-                     bool on_device, hipStream_t user_stream) {
+// structs are host memory either way.  seeded: the _seeded entry points — view v's seed is seeds[v] (host memory), and
+// q's seed and seed_stride are not read
+int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, bool seeded,
+                     const uint64_t* seeds, const RptAovBuffers* out, bool on_device, hipStream_t user_stream) {
   // (the query, the buffers, then the views: each is refused whatever else is wrong, also without a handle or a device)
   if (const char* why = bad_view_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (const char* why = bad_aov(out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (n_views && !views) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
+  if (seeded && n_views && !seeds) return fail(h, RPTGPU_E_INVALID_ARGUMENT, NULL_SEEDS);
   const uint64_t npix = (uint64_t)q->width * q->height;
   if (n_views > (1ull << 58) / npix) // (3 values of 8 bytes per index: an array's size in bytes fits 64 bits)
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "n_views * width * height does not fit: the frames would not fit any memory");
@@ -213,6 +215,10 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
       recs[v].ortho_scale = views[v].ortho_scale;
     }
     h->view_recs.upload(recs, st);
+    // views with seeds of their own: the first step alone reads a seed here (no rpt_shade follows it)
+    const std::vector<uint64_t> seed_list = view_seed_list(n_views, *q, seeded ? seeds : nullptr);
+    const bool per_view = !seed_list.empty();
+    if (per_view) h->view_seeds.upload(seed_list, st);
     // the piece: at most the rays one pass may hold; a camera ray reaches depth 0 only, hence one record column per path
     const uint64_t n = n_views * npix;
     rptplan::PassInput in = pass_input(h, 1, q->iterations);
@@ -222,8 +228,9 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
     uint64_t asked = 0; // tests: pieces of a few pixels
     if (const char* e = std::getenv("RPTGPU_VIEWS_PIECE")) asked = std::strtoull(e, nullptr, 10);
     const uint64_t piece = rptplan::views_piece(n, asked, rptplan::plan_pass(in).target);
-    const bool at_views = q->seed_stride != 0; // a piece's Frame carries one seed
+    const bool at_views = false; // a piece spans views whatever their seeds
     h->ray_ids.alloc(piece);
+    if (per_view) h->ray_seeds.alloc(piece);
     rptdev::AovOut stage{};
     if (!on_device) stage = aov_arrays(h->aov_out, st, piece, ch);
     for (uint64_t base = 0, m; base < n; base += m) {
@@ -237,7 +244,7 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
       }
       rptdev::Frame fr{};
       fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = h->ray_ids.p;
-      fr.seed = q->seed + (base / npix) * q->seed_stride;
+      fr.seed = per_view ? 0 : q->seed;
       rptplan::PassInput pin = pass_input(h, (uint32_t)m, q->iterations);
       pin.rec_ratio = 1.0; pin.ratio = 1.0;
       // passes are sample-major and run in ascending sample order, so an index's additions happen in sample order whatever
@@ -250,7 +257,9 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
         fr.sample_base = q->sample_index_base + s0;
         const rptdev::PathState ps = path_state(h);
         if (h->has_deep) reset_tree_counters(h);
-        kt->raygen_views(st, fr, h->view_recs.p, q->width, q->height, base, h->ray_ids.p, ps, n_paths);
+        if (per_view)
+          kt->raygen_views_seeded(st, fr, h->view_recs.p, q->width, q->height, base, h->ray_ids.p, h->view_seeds.p, h->ray_seeds.p, 0, (uint32_t)m, ps, n_paths);
+        else kt->raygen_views(st, fr, h->view_recs.p, q->width, q->height, base, h->ray_ids.p, ps, n_paths);
         if (by_object) query_closest(h, kt, ps, n_paths, nullptr);
         else kt->extend(st, h->dscene, ps, nullptr, n_paths);
         kt->views_aov_fold(st, h->dscene, ps, ao, (uint32_t)m, pp.s_chunk, s0 == 0);
@@ -282,12 +291,22 @@ int rptgpu_first_hits_device(rptgpu_scene* h, uint64_t n, const void* d_origins,
 
 int rptgpu_render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q,
                             const RptAovBuffers* out) {
-  return render_views_aov(h, n_views, views, q, out, false, nullptr);
+  return render_views_aov(h, n_views, views, q, false, nullptr, out, false, nullptr);
+}
+
+int rptgpu_render_views_aov_seeded(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q,
+                                   const uint64_t* seeds, const RptAovBuffers* out) {
+  return render_views_aov(h, n_views, views, q, true, seeds, out, false, nullptr);
 }
 
 int rptgpu_render_views_aov_device(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q,
                                    const RptAovBuffers* d_out, void* stream) {
-  return render_views_aov(h, n_views, views, q, d_out, true, (hipStream_t)stream);
+  return render_views_aov(h, n_views, views, q, false, nullptr, d_out, true, (hipStream_t)stream);
+}
+
+int rptgpu_render_views_aov_seeded_device(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q,
+                                          const uint64_t* seeds, const RptAovBuffers* d_out, void* stream) {
+  return render_views_aov(h, n_views, views, q, true, seeds, d_out, true, (hipStream_t)stream);
 }
 
 } // extern "C"

@@ -17,11 +17,11 @@
 //   api_buffer.cpp   the device-resident Buffer
 //   api_rays.cpp     rptgpu_trace_rays[_device]: the wavefront pipeline over rays the caller supplies, in pieces
 //   api_probes.cpp   rptgpu_bake_probes[_device]: light probes (SH9 radiance, irradiance) through the same driver, in pieces
-//   api_views.cpp    rptgpu_render_views[_device]: batches of perspective, orthographic and panoramic views through the same
-//                    driver, in pieces of consecutive (view, pixel) indices
+//   api_views.cpp    rptgpu_render_views[_seeded][_device]: batches of perspective, orthographic and panoramic views through the
+//                    same driver, in pieces of consecutive (view, pixel) indices, with one seed or a seed per view
 //   api_occlusion.cpp rptgpu_occluded[_device], rptgpu_bake_ao[_device]: the caller's rays, or points x directions made on the
 //                    device, through ONE visibility query of a render per pass (no depth loop), in pieces
-//   api_hits.cpp     rptgpu_first_hits[_device], rptgpu_render_views_aov[_device]: the first hit's record for the caller's rays
+//   api_hits.cpp     rptgpu_first_hits[_device], rptgpu_render_views_aov[_seeded][_device]: the first hit's record for the caller's rays
 //                    (one fused kernel, or the per-tree closest-hit query, in pieces) and rptgpu_render_aov's sums for
 //                    every view of a batch (raygen, closest-hit query and fold in passes over render_views' pieces)
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
@@ -187,6 +187,8 @@ struct rptgpu_scene {
   DevBuf<uint8_t> occ_out;             // rptgpu_occluded: a piece of a host caller's answers (api_occlusion.cpp)
   DevBuf<double> hits_out;             // rptgpu_first_hits: a piece of a host caller's records, the named channels back to back (api_hits.cpp)
   DevBuf<rptdev::View> view_recs;      // rptgpu_render_views: the call's views (api_views.cpp)
+  DevBuf<uint64_t> view_seeds;         // ... their seeds, when the views have seeds of their own,
+  DevBuf<uint64_t> ray_seeds;          // ... and then the seed of each index of a piece, beside ray_ids
   DevBuf<double> aov_out;              // rptgpu_render_aov: the requested channels' full-frame arrays, back to back (api_aov.cpp)
   int num_cus = 0;
   bool prefer_wavefront = false; // scene has real kd-trees: traversal-latency bound
@@ -367,11 +369,20 @@ struct RaySource {
   const rptdev::View* views = nullptr;
   uint32_t view_width = 0, view_height = 0;
   uint64_t view_base = 0;
+  // ... whose views have seeds of their own (rpt_raygen_views_seeded, rpt_shade_seeded): view_seeds, the call's seeds on the
+  // device, one per view; seeds_out receives the seed of each index of the piece, where rpt_shade_seeded reads it.  The
+  // piece's Frame::seed is not read then.  nullptr: every view's seed is the Frame's
+  const uint64_t* view_seeds = nullptr;
+  uint64_t* seeds_out = nullptr;
 };
 // api_views.cpp: what is wrong with an RptViewQuery / with one view of a call with query q (nullptr: nothing); shared with
 // rptgpu_render_views_aov (api_hits.cpp)
 const char* bad_view_query(const RptViewQuery* q);
 const char* bad_view(const RptView& v, const RptViewQuery& q);
+// the seeds of a call's views as the drivers take them: the caller's (the _seeded entry points), or seed + v * seed_stride in
+// wrapping u64 arithmetic; empty: every view has the query's seed (seed_stride == 0), the one-seed route
+constexpr const char* NULL_SEEDS = "null seeds: the _seeded entry points take one seed per view";
+std::vector<uint64_t> view_seed_list(uint64_t n_views, const RptViewQuery& q, const uint64_t* seeds);
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
 const char* bad_probe_query(const RptProbeQuery* q);

@@ -397,7 +397,7 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
 
 // One pass of the wavefront pipeline over n_paths = npix x spp paths: the ray source's kernel (rpt_raygen for a camera's
 // pixels, rpt_raygen_rays for a piece of the caller's rays, rpt_raygen_probes for a piece of light probes, rpt_raygen_views
-// for a piece of a batch of views), per depth {
+// for a piece of a batch of views — with a seed per view: rpt_raygen_views_seeded, and rpt_shade_seeded for rpt_shade), per depth {
 // closest-hit query, rpt_shade, the visibility queries, rpt_shadow_sum }, rpt_resolve (probes: rpt_resolve_probes).  *cols: the record columns the pass used.  false: the
 // pool ran out at some depth (*cols: the columns up to and with that depth) — the pass did not resolve, and nothing of it
 // has left the workspace.
@@ -412,7 +412,19 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
   HIP_TRY(hipMemsetAsync(h->counters.p, 0, 2 * (size_t)nctr * sizeof(uint32_t), st));
   uint32_t cset = 0;
   if (h->has_deep) reset_tree_counters(h);
-  { Bracket b(h, RPT_K_RAYGEN, prof);
+  if (src.views && src.view_seeds) {
+    // one launch for every view the piece holds: the raygen count of RptStats stays at least the number of views rendered
+    // under seeds of their own, as it was when such a view was a piece — the depth loop behind it is the piece's, shared
+    const uint64_t npix_view = (uint64_t)src.view_width * src.view_height;
+    for (uint32_t p_lo = 0, p_len; p_lo < fr.npix; p_lo += p_len) {
+      const uint64_t j = src.view_base + p_lo;
+      p_len = (uint32_t)std::min<uint64_t>(fr.npix - p_lo, (j / npix_view + 1) * npix_view - j);
+      Bracket b(h, RPT_K_RAYGEN, prof);
+      kt->raygen_views_seeded(st, fr, src.views, src.view_width, src.view_height, src.view_base, src.ids_out, src.view_seeds,
+                              src.seeds_out, p_lo, p_len, ps, p_len * spp);
+      b.done();
+    }
+  } else { Bracket b(h, RPT_K_RAYGEN, prof);
     if (src.cam) kt->raygen(st, fr, *src.cam, ps, n_paths);
     else if (src.views) kt->raygen_views(st, fr, src.views, src.view_width, src.view_height, src.view_base, src.ids_out, ps, n_paths);
     else if (src.probe >= 0) kt->raygen_probes(st, fr, src.origins, src.dirs, (uint32_t)src.probe, src.ids_out, src.id_base, ps, n_paths);
@@ -443,7 +455,9 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
     uint32_t* const ctrs_next = h->counters.p + (size_t)(cset ^ 1u) * nctr;
     cset ^= 1u;
     { Bracket b(h, RPT_K_SHADE, prof);
-      kt->shade(st, h->dscene, fr, ps, queue, n_active, depth, next, ctrs, h->shadow_q.p, ctrs_next, nctr, (uint32_t)rec_off); b.done(); }
+      if (src.view_seeds) kt->shade_seeded(st, h->dscene, fr, ps, queue, n_active, depth, next, ctrs, h->shadow_q.p, ctrs_next, nctr, (uint32_t)rec_off, src.seeds_out);
+      else kt->shade(st, h->dscene, fr, ps, queue, n_active, depth, next, ctrs, h->shadow_q.p, ctrs_next, nctr, (uint32_t)rec_off);
+      b.done(); }
     // The depth's counts come back right after rpt_shade — the one point of a depth where the host waits — so the
     // visibility queries are sized for the shadow rays there ARE (50-70 % of the paths on closed meshes: less to
     // sort, smaller grids, and a light without a single ray at this depth costs no launch at all) and the next

@@ -1,10 +1,12 @@
-// api_views.cpp — rptgpu_render_views[_device]: a batch of frames in one call, each from a camera of its own under one of
+// api_views.cpp — rptgpu_render_views[_seeded][_device]: a batch of frames in one call, each from a camera of its own under one of
 // three projections (include/rpt_gpu.h; see api_internal.h).  The n_views x width x height pixels of the call
 // are the indices j = view * npix + pixel; they go through the wavefront driver of api_render.cpp in pieces of consecutive
 // j (rptplan::views_piece) — a piece is the "frame" of its own passes, as a piece of rptgpu_trace_rays' rays is —,
 // rpt_raygen_views makes each index's ray from its pixel's own stream (RaySource::views), and everything behind it — the
 // depth loop, the pass planning with its restarts, rpt_resolve, rpt_finish in packed form straight into `out` at j — is a
-// render's.  So the launches of a depth and its one host wait are shared by every view a piece holds.
+// render's.  So the launches of a depth and its one host wait are shared by every view a piece holds — whatever the views'
+// seeds: where they differ (rptgpu_render_views_seeded[_device], or a seed stride) the seed travels with the path
+// (RaySource::view_seeds: rpt_raygen_views_seeded, rpt_shade_seeded), and pieces are cut where the one-seed route cuts them.
 #include "api_internal.h"
 
 namespace rptapi {
@@ -39,15 +41,27 @@ const char* bad_view(const RptView& v, const RptViewQuery& q) {
   }
 }
 
+std::vector<uint64_t> view_seed_list(uint64_t n_views, const RptViewQuery& q, const uint64_t* seeds) {
+  if (seeds) return std::vector<uint64_t>(seeds, seeds + n_views);
+  std::vector<uint64_t> list;
+  if (q.seed_stride) {
+    list.resize(n_views);
+    for (uint64_t v = 0; v < n_views; v++) list[v] = q.seed + v * q.seed_stride; // (wraps: u64)
+  }
+  return list;
+}
+
 namespace {
 
 // out: host memory ([n_views][height][width][3] f64), or — on_device — device memory of f64 or f32 (user_stream: the
-// stream its producer ran on); views is host memory either way
-int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, void* out, bool on_device,
-                 bool out_f32, hipStream_t user_stream) {
+// stream its producer ran on); views is host memory either way.  seeded: the _seeded entry points — view v's seed is
+// seeds[v] (host memory), and q's seed and seed_stride are not read
+int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, bool seeded, const uint64_t* seeds,
+                 void* out, bool on_device, bool out_f32, hipStream_t user_stream) {
   // (the query first, then the views: both are refused whatever else is wrong, also without a handle or a device)
   if (const char* why = bad_view_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (n_views && (!views || !out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
+  if (seeded && n_views && !seeds) return fail(h, RPTGPU_E_INVALID_ARGUMENT, NULL_SEEDS);
   const uint64_t npix = (uint64_t)q->width * q->height;
   if (n_views > (1ull << 58) / npix) // (3 values of 8 bytes per index: the frames' size in bytes fits 64 bits)
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "n_views * width * height does not fit: the frames would not fit any memory");
@@ -79,6 +93,9 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
       recs[v].ortho_scale = views[v].ortho_scale;
     }
     h->view_recs.upload(recs, st);
+    const std::vector<uint64_t> seed_list = view_seed_list(n_views, *q, seeded ? seeds : nullptr);
+    const bool per_view = !seed_list.empty(); // the seed travels with the path
+    if (per_view) h->view_seeds.upload(seed_list, st);
     // the piece: at most the paths one pass may hold with every level of every path (rptplan::views_piece)
     const uint64_t n = n_views * npix;
     rptplan::PassInput in = pass_input(h, 1, q->iterations);
@@ -88,20 +105,22 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
     uint64_t asked = 0; // tests: pieces of a few pixels
     if (const char* e = std::getenv("RPTGPU_VIEWS_PIECE")) asked = std::strtoull(e, nullptr, 10);
     const uint64_t piece = rptplan::views_piece(n, asked, rptplan::plan_pass(in).target);
-    const bool at_views = q->seed_stride != 0; // a piece's Frame carries one seed
+    const bool at_views = false; // a piece spans views whatever their seeds
     const size_t out_elem = out_f32 ? sizeof(float) : sizeof(double);
     h->accum.alloc(3 * piece);
     h->ray_ids.alloc(piece);
+    if (per_view) h->ray_seeds.alloc(piece);
     if (!on_device) h->rays_out.alloc(3 * piece);
     for (uint64_t base = 0, m; base < n; base += m) {
       m = rptplan::views_piece_len(base, n, npix, piece, at_views);
       void* d_out = on_device ? (void*)((char*)out + 3 * base * out_elem) : (void*)h->rays_out.p;
       rptdev::Frame fr{};
       fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = h->ray_ids.p;
-      fr.max_bounces = q->max_bounces; fr.seed = q->seed + (base / npix) * q->seed_stride; fr.accum = h->accum.p;
+      fr.max_bounces = q->max_bounces; fr.seed = per_view ? 0 : q->seed; fr.accum = h->accum.p;
       RaySource src{};
       src.ids_out = h->ray_ids.p;
       src.views = h->view_recs.p; src.view_width = q->width; src.view_height = q->height; src.view_base = base;
+      if (per_view) { src.view_seeds = h->view_seeds.p; src.seeds_out = h->ray_seeds.p; }
       render_wavefront(h, kt, p, fr, src, d_out, out_f32, true, prof);
       HIP_TRY(hipGetLastError());
       if (!on_device) { // the staging array is the next piece's, too
@@ -122,12 +141,22 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
 extern "C" {
 
 int rptgpu_render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, double* out) {
-  return render_views(h, n_views, views, q, out, false, false, nullptr);
+  return render_views(h, n_views, views, q, false, nullptr, out, false, false, nullptr);
+}
+
+int rptgpu_render_views_seeded(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q,
+                               const uint64_t* seeds, double* out) {
+  return render_views(h, n_views, views, q, true, seeds, out, false, false, nullptr);
 }
 
 int rptgpu_render_views_device(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, void* d_out,
                                int out_is_f32, void* stream) {
-  return render_views(h, n_views, views, q, d_out, true, out_is_f32 != 0, (hipStream_t)stream);
+  return render_views(h, n_views, views, q, false, nullptr, d_out, true, out_is_f32 != 0, (hipStream_t)stream);
+}
+
+int rptgpu_render_views_seeded_device(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q,
+                                      const uint64_t* seeds, void* d_out, int out_is_f32, void* stream) {
+  return render_views(h, n_views, views, q, true, seeds, d_out, true, out_is_f32 != 0, (hipStream_t)stream);
 }
 
 } // extern "C"

@@ -212,6 +212,18 @@ struct KernelTable {
   void (*hits_store)(hipStream_t, const rptdev::Scene&, const rptdev::PathState&, uint32_t n, const rptdev::HitOut& out);
   void (*views_aov_fold)(hipStream_t, const rptdev::Scene&, const rptdev::PathState&, const rptdev::AovOut& out, uint32_t n,
                          uint32_t spp, bool first);
+  // a batch of views with a seed per view (rptgpu_render_views_seeded, and rptgpu_render_views with a seed stride;
+  // kernels/wavefront.inc).  raygen_views_seeded: raygen_views with view v's stream seeded by view_seeds[v] ([views of the
+  // call] on the device) instead of fr.seed; seeds_out ([fr.npix]) receives the seed of each index of the piece.  One
+  // launch covers the piece's indices p_lo .. p_lo + p_len - 1 (p_lo + p_len <= fr.npix, p_len > 0) with n_paths = p_len x
+  // the pass's samples, in the slots s * fr.npix + index: the whole piece is (0, fr.npix).
+  // shade_seeded: shade with the stream of the path of index i seeded by seeds[i] — raygen_views_seeded's seeds_out
+  void (*raygen_views_seeded)(hipStream_t, const rptdev::Frame&, const rptdev::View* views, uint32_t width, uint32_t height,
+                              uint64_t j_base, uint32_t* ids_out, const uint64_t* view_seeds, uint64_t* seeds_out,
+                              uint32_t p_lo, uint32_t p_len, const rptdev::PathState&, uint32_t n_paths);
+  void (*shade_seeded)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::PathState&, const uint32_t* queue,
+                       uint32_t n, uint32_t depth, uint32_t* next_queue, uint32_t* counters, uint32_t* sq, uint32_t* zero_next,
+                       uint32_t zero_n, uint32_t rec_off, const uint64_t* seeds);
 };
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)

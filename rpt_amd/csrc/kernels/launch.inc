@@ -38,6 +38,12 @@ void launch_raygen_views(hipStream_t st, const Frame& fr, const View* views, uin
                          uint32_t* ids_out, const PathState& ps, uint32_t n_paths) {
   hipLaunchKernelGGL(rpt_raygen_views, grid_for(n_paths), dim3(256), 0, st, fr, views, width, height, j_base, ids_out, ps, n_paths);
 }
+void launch_raygen_views_seeded(hipStream_t st, const Frame& fr, const View* views, uint32_t width, uint32_t height, uint64_t j_base,
+                                uint32_t* ids_out, const uint64_t* view_seeds, uint64_t* seeds_out, uint32_t p_lo, uint32_t p_len,
+                                const PathState& ps, uint32_t n_paths) {
+  hipLaunchKernelGGL(rpt_raygen_views_seeded, grid_for(n_paths), dim3(256), 0, st, fr, views, width, height, j_base, ids_out,
+                     view_seeds, seeds_out, p_lo, p_len, ps, n_paths);
+}
 void launch_extend(hipStream_t st, const Scene& sc, const PathState& ps, const uint32_t* queue, uint32_t n) {
   hipLaunchKernelGGL(rpt_extend, grid_for(n), dim3(256), 0, st, sc, ps, queue, n);
 }
@@ -50,6 +56,12 @@ void launch_shade(hipStream_t st, const Scene& sc, const Frame& fr, const PathSt
                   uint32_t zero_n, uint32_t rec_off) {
   hipLaunchKernelGGL(rpt_shade, dim3((unsigned)((n + SHADE_BLOCK - 1) / SHADE_BLOCK)), dim3(SHADE_BLOCK), 0, st, sc, fr, ps, queue, n, depth,
                      next_queue, counters, sq, zero_next, zero_n, rec_off);
+}
+void launch_shade_seeded(hipStream_t st, const Scene& sc, const Frame& fr, const PathState& ps, const uint32_t* queue,
+                         uint32_t n, uint32_t depth, uint32_t* next_queue, uint32_t* counters, uint32_t* sq, uint32_t* zero_next,
+                         uint32_t zero_n, uint32_t rec_off, const uint64_t* seeds) {
+  hipLaunchKernelGGL(rpt_shade_seeded, dim3((unsigned)((n + SHADE_BLOCK - 1) / SHADE_BLOCK)), dim3(SHADE_BLOCK), 0, st, sc, fr, ps, queue, n,
+                     depth, next_queue, counters, sq, zero_next, zero_n, rec_off, seeds);
 }
 // visibility of ONE light for the paths in its shadow-ray queue, whole scene in the kernel (n: host-side bound of the queue length)
 void launch_shadow_rays(hipStream_t st, const Scene& sc, const PathState& ps, const uint32_t* sq_all, const uint32_t* sq_counts,
@@ -361,5 +373,6 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_denoise_prepare, launch_denoise_level, launch_denoise_finish,
                            launch_raygen_probes, launch_resolve_probes, launch_finish_probes, launch_raygen_views,
                            launch_occ_load, launch_raygen_ao, launch_occ_store, launch_ao_fold,
-                           launch_first_hits, launch_hits_store, launch_views_aov_fold};
+                           launch_first_hits, launch_hits_store, launch_views_aov_fold,
+                           launch_raygen_views_seeded, launch_shade_seeded};
 #endif // !__HIP_DEVICE_COMPILE__

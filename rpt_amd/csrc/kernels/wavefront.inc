@@ -1,5 +1,5 @@
-// kernels/wavefront.inc — the multi-kernel path pipeline over SoA path state (wf_state.inc): rpt_raygen / _rays / _probes / _views,
-// rpt_extend, rpt_shade, rpt_shadow_rays, rpt_shadow_sum, rpt_resolve / _probes, rpt_finish / _probes, rpt_path_permute.
+// kernels/wavefront.inc — the multi-kernel path pipeline over SoA path state (wf_state.inc): rpt_raygen / _rays / _probes / _views
+// [_seeded] (wf_raygen_views.inc), rpt_extend, rpt_shade [_seeded] (wf_shade.inc), rpt_shadow_rays, rpt_shadow_sum, rpt_resolve / _probes, rpt_finish / _probes, rpt_path_permute.
 // Its closest-hit and visibility queries over deep trees are the per-tree kernels of tree_query / tree_trace / tree_generic.inc.
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
 
@@ -89,73 +89,14 @@ __global__ void __launch_bounds__(256) rpt_raygen_probes(Frame fr, const double*
   if (ids_out && s_local == 0) ids_out[p_local] = id;
 }
 
-// The first step for a batch of views (rptgpu_render_views, include/rpt_gpu.h): slot = s_local * npix + p_local is sample
-// fr.sample_base + s_local of index j = j_base + p_local of the CALL, and j = v * (width * height) + pixel names the view and
-// its pixel.  The ray is made from the pixel's own stream (fr.seed, pixel, sample) from draw 0 on — fr.seed is the seed of
-// every view the piece touches: the host cuts pieces at view boundaries when the views' seeds differ — and the path
-// continues that stream behind the camera's draws, as rpt_raygen's does.  PERSPECTIVE is rpt_raygen's ray, expression for
-// expression; ORTHOGRAPHIC and PANORAMA are the header's.  ids_out (= fr.pixels): the first sample's lanes write the
-// stream id `pixel` where rpt_shade will look for it.
-__global__ void __launch_bounds__(256) rpt_raygen_views(Frame fr, const View* __restrict__ views, uint32_t width, uint32_t height,
-                                                        uint64_t j_base, uint32_t* __restrict__ ids_out, PathState ps, uint32_t n_paths) {
-  uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-  if (slot >= n_paths) return;
-  uint32_t s_local = slot / fr.npix, p_local = slot - s_local * fr.npix;
-  const uint64_t npix_view = (uint64_t)width * height, j = j_base + p_local;
-  const uint64_t v = j / npix_view;
-  const uint32_t pixel = (uint32_t)(j - v * npix_view);
-  uint32_t y = pixel / width, x = pixel - y * width;
-  const View& view = views[v];
-  const Camera& cam = view.cam;
-  Rng rng = rng_make(fr.seed, pixel, fr.sample_base + s_local, 0);
-  D3 origin = ld3(cam.eye), dir;
-  if (view.projection == RPT_VIEW_PANORAMA) {
-    double jx = gen_range(rng, -0.5, 0.5);
-    double jy = gen_range(rng, -0.5, 0.5);
-    const double wm = (double)(width - 1), hm = (double)(height - 1);
-    double cx = (double)x + jx;
-    if (cx < 0.0) cx = cx + wm;
-    else if (cx > wm) cx = cx - wm;
-    double cy = (double)y + jy;
-    cy = fmin(fmax(cy, 0.0), hm);
-    // the azimuth in turns, (-1/2, 1/2]: beyond a quarter turn the angle half a turn back, and both results negated
-    const double psi = cx / wm - 0.5;
-    const bool back = fabs(psi) > 0.25;
-    double s, c, se, ce;
-    rptc_sincos_pio2(6.283185307179586 * (back ? psi - copysign(0.5, psi) : psi), &s, &c);
-    if (back) { s = -s; c = -c; }
-    rptc_sincos_pio2((0.5 - cy / hm) * 3.141592653589793, &se, &ce);
-    dir = mk(ce * c, se, ce * s);
-  } else {
-    // renderer.rs:132-138, as rpt_raygen
-    double dim = (double)max(width, height);
-    double xn = ((double)(2 * x + 1) - (double)width) / dim;
-    double yn = ((double)(2 * (height - y) - 1) - (double)height) / dim;
-    double dx = gen_range(rng, -1.0 / dim, 1.0 / dim);
-    double dy = gen_range(rng, -1.0 / dim, 1.0 / dim);
-    double px = xn + dx, py = yn + dy;
-    D3 direction = ld3(cam.direction), up = ld3(cam.up), right = ld3(cam.right);
-    if (view.projection == RPT_VIEW_ORTHOGRAPHIC) {
-      origin = origin + (px * right + py * up) * view.ortho_scale; // the form of camera.rs:74
-      dir = normalize(direction);
-    } else { // Camera::cast_ray camera.rs:64-81
-      D3 new_dir = cam.d * direction + px * right + py * up;
-      if (cam.aperture > 0.0) {
-        D3 focal_point = origin + normalize(new_dir) * cam.focal_distance;
-        double a, b;
-        unit_disc(rng, a, b);
-        origin = origin + (a * right + b * up) * cam.aperture;
-        new_dir = focal_point - origin;
-      }
-      dir = normalize(new_dir);
-    }
-  }
-  st_soa3(ps.ray, ps.cap, slot, origin);
-  st_soa3(ps.ray + 3 * ps.cap, ps.cap, slot, dir);
-  ps.draw[slot] = rng.draw;
-  ps.pid[slot] = slot;
-  if (s_local == 0) ids_out[p_local] = pixel;
-}
+// rpt_raygen_views and rpt_raygen_views_seeded: kernels/wf_raygen_views.inc, once for every seed source (RPT_WF_SEEDED 0: the Frame's seed; 1: a
+// seed per view, carried per index of the piece)
+#define RPT_WF_SEEDED 0
+#include "wf_raygen_views.inc"
+#undef RPT_WF_SEEDED
+#define RPT_WF_SEEDED 1
+#include "wf_raygen_views.inc"
+#undef RPT_WF_SEEDED
 
 // closest hit for every queued path.  queue == nullptr means the identity queue (depth 0).
 __global__ void __launch_bounds__(256, RPT_WF_WAVES) rpt_extend(Scene sc, PathState ps, const uint32_t* __restrict__ queue,
@@ -192,120 +133,14 @@ __global__ void __launch_bounds__(256) rpt_extend_rays(Scene sc, const double* _
   out_obj[i] = obj;
 }
 
-// trace_ray's body for one depth (renderer.rs:147-168).
-// sq / counters[2 + l]: per light, the queue of the paths that cast a shadow ray towards it at this depth ([light][cap])
-// and its length: every hit whose light could add something (see null_contribution).  The visibility queries of the
-// depth run over these queues, not over the path queue.
-__global__ void __launch_bounds__(SHADE_BLOCK, RPT_SHADE_WAVES) rpt_shade(Scene sc, Frame fr, PathState ps, const uint32_t* __restrict__ queue,
-                                                 uint32_t n, uint32_t depth, uint32_t* __restrict__ next_queue,
-                                                 uint32_t* __restrict__ counters /* [0]=next count, [1]=hits, [2+l]=shadow rays of light l */,
-                                                 uint32_t* __restrict__ sq, uint32_t* __restrict__ zero_next, uint32_t zero_n,
-                                                 uint32_t rec_off /* first record column of this depth: path i of the queue writes column rec_off + i */) {
-  constexpr int FAST_LIGHTS = 30; // lights whose queue bit fits the one combined append (bits 2..31)
-  // the NEXT depth's counters — the other of two sets (api_render.cpp): the host has read them back (it waits for every
-  // depth's counts) before this launch, and nothing touches them until the next depth's rpt_shade.  One memset per depth less.
-  if (blockIdx.x == 0 && zero_next) for (uint32_t k = threadIdx.x; k < zero_n; k += blockDim.x) zero_next[k] = 0u;
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  bool active = i < n;
-  const uint32_t slot = i; // dense state: the path's position at this depth (`queue` is the identity, kept for the signature)
-  (void)queue;
-  (void)next_queue;
-  uint32_t bits = 0; // bit 0: the path continues, bit 1: it hit something, bit 2 + l: it casts a shadow ray to light l
-  uint32_t path = 0, next_draw = 0;
-  D3 next_o = mk(0, 0, 0), next_d = mk(0, 0, 0);
-  const uint64_t col = (uint64_t)rec_off + i; // this path's record of this depth; linked to its record one depth up
-  if (active) {
-    path = ps.pid[slot];
-    ps.rec_parent[col] = depth ? ps.col[slot] : REC_NONE;
-    D3 o = ld_soa3(ps.ray, ps.cap, slot);
-    D3 d = ld_soa3(ps.ray + 3 * ps.cap, ps.cap, slot);
-    int obj = ps.hit_obj[slot];
-    // the hit record, the stream position and the pixel are requested together with the ray, before the hit / miss
-    // branch: one round trip to the path state instead of three
-    const double t = ps.hit[slot];
-    const D3 nrm = ld_soa3(ps.hit + ps.cap, ps.cap, slot);
-    const uint32_t s_local = path / fr.npix, p_local = path - s_local * fr.npix;
-    const uint32_t pixel = fr.pixels[p_local], draw0 = ps.draw[slot];
-    if (obj < 0) { // renderer.rs:147
-      D3 e = env_color(sc, d);
-      st_rec3(ps, 0, col, e);
-    } else {
-      bits |= 2u;
-      Rng rng = rng_make(fr.seed, pixel, fr.sample_base + s_local, draw0);
-      D3 world_pos = o + t * d;                  // renderer.rs:149
-      const Material& mat = sc.materials[sc.insts[obj].material];
-      D3 wo = -normalize(d);                     // renderer.rs:151
-      D3 emit = mat.emittance * ld3(mat.color);  // renderer.rs:153
-      st_rec3(ps, 0, col, emit);
-      // sample_lights (renderer.rs:177-204): everything except the visibility test
-      for (int l = 0; l < sc.num_lights; l++) {
-        CLight& light = clight(sc, l);
-        double* sh = ps.shadow + (uint64_t)l * SHADOW_FIELDS * ps.cap;
-        if (light.kind == RPT_LIGHT_AMBIENT) {
-          st_soa3(sh + 4 * ps.cap, ps.cap, slot, cmul(ld3(light.color), ld3(mat.color)));
-        } else {
-          D3 intensity, wi;
-          double dist;
-          illuminate(sc, light, world_pos, rng, intensity, wi, dist);
-          D3 f = bsdf(mat, nrm, wo, wi);
-          const D3 contrib = cmul(f, intensity) * dot(wi, nrm); // renderer.rs:199
-          st_soa3(sh, ps.cap, slot, wi);
-          sh[3 * ps.cap + slot] = dist;
-          st_soa3(sh + 4 * ps.cap, ps.cap, slot, contrib);
-          if (l < FAST_LIGHTS && !null_contribution(contrib)) bits |= 4u << l;
-        }
-      }
-      st_soa3(ps.ray, ps.cap, slot, world_pos); // origin of the shadow rays and of the next ray
-      if (depth < fr.max_bounces) {             // renderer.rs:155
-        D3 wi;
-        double pdf;
-        if (sample_f(mat, nrm, wo, rng, wi, pdf)) {
-          D3 f = bsdf(mat, nrm, wo, wi);
-          st_rec3(ps, 3, col, f);
-          ps.rec[col * REC_FIELDS + 6] = 1.0 / pdf;
-          ps.rec[col * REC_FIELDS + 7] = fabs(dot(wi, nrm));
-          next_o = world_pos; next_d = wi;
-          bits |= 1u;
-        }
-      }
-      next_draw = rng.draw;
-    }
-    if (!(bits & 1u)) ps.last_col[path] = (uint32_t)col; // the path ends with this record: where rpt_resolve starts
-  }
-  const uint32_t j = block_multi_push(bits, 2 + min(sc.num_lights, FAST_LIGHTS), slot, counters, sq, ps.cap, 0);
-  if (bits & 1u) { // the survivor's state, at its position in the next depth
-    if (ps.next_rows) {
-      // in-kernel-traversal scenes (path re-order): one 64-byte row, and the key the re-order sorts by while the ray is
-      // in registers
-      double* row = ps.next_rows + (uint64_t)j * 8u;
-      row[0] = next_o.x; row[1] = next_o.y; row[2] = next_o.z; row[3] = next_d.x; row[4] = next_d.y; row[5] = next_d.z;
-      row[6] = pack_u32(next_draw, path);
-      row[7] = pack_u32((uint32_t)col, 0u);
-      SceneBox box;
-#pragma unroll
-      for (int k = 0; k < 6; k++) box.bounds[k] = ps.key_bounds[k];
-      ps.sort_keys[j] = ray_sort_key(box, next_o, next_d, 0.0);
-      ps.sort_vals[j] = j;
-    } else {
-      st_soa3(ps.ray_next, ps.cap, j, next_o);
-      st_soa3(ps.ray_next + 3 * ps.cap, ps.cap, j, next_d);
-      ps.draw_next[j] = next_draw;
-      ps.pid_next[j] = path;
-      ps.col_next[j] = (uint32_t)col;
-    }
-  }
-  // scenes with more lights than one append holds: the rest in further appends, from the stored contributions
-  for (int l0 = FAST_LIGHTS; l0 < sc.num_lights; l0 += FAST_LIGHTS) {
-    const int nl = min(sc.num_lights - l0, FAST_LIGHTS);
-    uint32_t more = 0;
-    if (bits & 2u)
-      for (int k = 0; k < nl; k++) {
-        const double* sh = ps.shadow + (uint64_t)(l0 + k) * SHADOW_FIELDS * ps.cap;
-        if (clight(sc, l0 + k).kind != RPT_LIGHT_AMBIENT && !null_contribution(ld_soa3(sh + 4 * ps.cap, ps.cap, slot))) more |= 4u << k;
-      }
-    (void)block_multi_push(more, 2 + nl, slot, counters, sq, ps.cap, l0);
-  }
-}
+// rpt_shade and rpt_shade_seeded: kernels/wf_shade.inc, once for every seed source (RPT_WF_SEEDED 0: the Frame's seed; 1: a
+// seed per view, carried per index of the piece)
+#define RPT_WF_SEEDED 0
+#include "wf_shade.inc"
+#undef RPT_WF_SEEDED
+#define RPT_WF_SEEDED 1
+#include "wf_shade.inc"
+#undef RPT_WF_SEEDED
 
 // The visibility test of sample_lights (renderer.rs:191-197) for the paths queued for the depth's lights (rpt_shade's
 // per-light queues: hits whose light can add something), scenes without deep trees: one thread per shadow ray, the

@@ -665,17 +665,20 @@ class GpuScene:
         return (out_ao, out_bent) if bent_normals else out_ao
 
     def render_views(self, views, width, height, max_bounces, samples=1, seed=0x52505447, seed_stride=0,
-                     sample_index_base=0, exposure_value=0.0, flags=0, out=None):
+                     sample_index_base=0, exposure_value=0.0, flags=0, out=None, seeds=None):
         """A batch of frames in one call (rptgpu_render_views) -> (n, height, width, 3): per pixel the mean
         of `samples` paths of at most max_bounces bounces, times 2^exposure_value.  views: a sequence of View (a camera
         under RPT_VIEW_PERSPECTIVE / _ORTHOGRAPHIC / _PANORAMA), Camera (perspective) or _abi.RptView.  View v renders with
         seed + v * seed_stride, and pixel p's random numbers are those of (that seed, p, sample_index_base + s): a
-        perspective view is render_batch's frame of its camera, and no view depends on the views around it.  out: None or
+        perspective view is render_batch's frame of its camera, and no view depends on the views around it.  seeds: one
+        seed per view instead (a sequence of ints or a numpy uint64 array of len(views); rptgpu_render_views_seeded) — view
+        v renders exactly as with seed = seeds[v] and seed_stride = 0; not together with a non-zero seed_stride.  out: None or
         a C-contiguous float64 numpy array (the frames go through host memory), or a contiguous float64 / float32 torch
         tensor on the handle's device, which is written where it lies (rptgpu_render_views_device)."""
         views = list(views)
         n, width, height = len(views), int(width), int(height)
         arr = self._lower_views(views, "render_views")
+        seed_arr = self._lower_seeds(seeds, n, seed_stride, "render_views")
         q = _abi.RptViewQuery()
         q.struct_size = C.sizeof(_abi.RptViewQuery)
         q.width, q.height, q.max_bounces, q.iterations = width, height, int(max_bounces), int(samples)
@@ -694,15 +697,22 @@ class GpuScene:
             stream = current.cuda_stream
             if not stream:
                 current.synchronize()
-            code = self.lib.rptgpu_render_views_device(self.handle, n, arr, C.byref(q), C.c_void_p(out.data_ptr()),
-                                                       1 if out.dtype == torch.float32 else 0, C.c_void_p(stream or 0))
+            tail = (C.c_void_p(out.data_ptr()), 1 if out.dtype == torch.float32 else 0, C.c_void_p(stream or 0))
+            if seed_arr is None:
+                code = self.lib.rptgpu_render_views_device(self.handle, n, arr, C.byref(q), *tail)
+            else:
+                code = self.lib.rptgpu_render_views_seeded_device(self.handle, n, arr, C.byref(q), seed_arr, *tail)
             _abi.check(code, self.handle)
             return out
         if out is None:
             out = np.empty(shape, dtype=np.float64)
         elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == shape and out.flags.c_contiguous):
             raise ValueError("render_views: out must be a C-contiguous %s float64 array" % (shape,))
-        code = self.lib.rptgpu_render_views(self.handle, n, arr, C.byref(q), out.ctypes.data_as(C.POINTER(C.c_double)))
+        if seed_arr is None:
+            code = self.lib.rptgpu_render_views(self.handle, n, arr, C.byref(q), out.ctypes.data_as(C.POINTER(C.c_double)))
+        else:
+            code = self.lib.rptgpu_render_views_seeded(self.handle, n, arr, C.byref(q), seed_arr,
+                                                       out.ctypes.data_as(C.POINTER(C.c_double)))
         _abi.check(code, self.handle)
         return out
 
@@ -780,18 +790,20 @@ class GpuScene:
         return out
 
     def render_views_aov(self, views, width, height, samples=1, seed=0x52505447, seed_stride=0, sample_index_base=0,
-                         channels=_abi.RPT_AOV_ALL, flags=0, out=None):
+                         channels=_abi.RPT_AOV_ALL, flags=0, out=None, seeds=None):
         """First-hit feature buffers of a batch of views (rptgpu_render_views_aov) -> a dict as render_aov's
         with the views as the leading axis: `hits` (n, H, W) uint32 always, and per channel of `channels` (RPT_AOV_*) the
         f64 sums over the hits of `samples` rays per pixel — `depth` (n, H, W), `normal` / `albedo` / `position` (n, H, W,
         3) — and `object` (n, H, W) int32.  views, seed, seed_stride, sample_index_base: render_views'; view v's rays are
         the rays render_views makes for it, so a perspective view is render_aov of its camera with seed + v * seed_stride.
+        seeds: one seed per view instead, as render_views' (rptgpu_render_views_aov_seeded).
         out: None (new numpy arrays through host memory) or a dict of C-contiguous numpy arrays with exactly the keys
         above; or "torch" for new tensors on the handle's device, or a dict of contiguous torch tensors there, written
         where they lie (rptgpu_render_views_aov_device; `hits` as the 32 bits of an int32 tensor)."""
         views = list(views)
         n, width, height, channels = len(views), int(width), int(height), int(channels)
         arr = self._lower_views(views, "render_views_aov")
+        seed_arr = self._lower_seeds(seeds, n, seed_stride, "render_views_aov")
         q = _abi.RptViewQuery()
         q.struct_size = C.sizeof(_abi.RptViewQuery)
         q.width, q.height, q.max_bounces, q.iterations = width, height, 0, int(samples)
@@ -819,7 +831,11 @@ class GpuScene:
                     raise ValueError("render_views_aov: out[%r] must be a C-contiguous %s %s array" % (name, shape, np.dtype(dtype)))
             for name, v in arrays.items():
                 setattr(b, name, v.ctypes.data_as(types[name]))
-            _abi.check(self.lib.rptgpu_render_views_aov(self.handle, n, arr, C.byref(q), C.byref(b)), self.handle)
+            if seed_arr is None:
+                code = self.lib.rptgpu_render_views_aov(self.handle, n, arr, C.byref(q), C.byref(b))
+            else:
+                code = self.lib.rptgpu_render_views_aov_seeded(self.handle, n, arr, C.byref(q), seed_arr, C.byref(b))
+            _abi.check(code, self.handle)
             return arrays
         import torch
         dev = torch.device("cuda", self.device)
@@ -846,9 +862,31 @@ class GpuScene:
         stream = current.cuda_stream
         if not stream:
             current.synchronize()
-        code = self.lib.rptgpu_render_views_aov_device(self.handle, n, arr, C.byref(q), C.byref(b), C.c_void_p(stream or 0))
+        if seed_arr is None:
+            code = self.lib.rptgpu_render_views_aov_device(self.handle, n, arr, C.byref(q), C.byref(b), C.c_void_p(stream or 0))
+        else:
+            code = self.lib.rptgpu_render_views_aov_seeded_device(self.handle, n, arr, C.byref(q), seed_arr, C.byref(b),
+                                                                  C.c_void_p(stream or 0))
         _abi.check(code, self.handle)
         return arrays
+
+    @staticmethod
+    def _lower_seeds(seeds, n, seed_stride, who):
+        """seeds=None -> None; else the n seeds as a ctypes uint64 array (at least one element: it has an address)"""
+        if seeds is None:
+            return None
+        if int(seed_stride) != 0:
+            raise ValueError("%s: seeds and a non-zero seed_stride exclude each other" % who)
+        if isinstance(seeds, np.ndarray) and seeds.dtype != np.uint64:
+            raise ValueError("%s: a numpy array of seeds must be uint64" % who)
+        values = [int(s) for s in seeds]
+        if len(values) != n:
+            raise ValueError("%s: %d seeds for %d views" % (who, len(values), n))
+        if any(not 0 <= s < 1 << 64 for s in values):
+            raise ValueError("%s: a seed must fit 64 bits unsigned" % who)
+        arr = (C.c_uint64 * max(n, 1))()
+        arr[:n] = values
+        return arr
 
     @staticmethod
     def _lower_views(views, who):

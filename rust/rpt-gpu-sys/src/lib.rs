@@ -484,6 +484,14 @@ pub mod ffi {
         pub fn rptgpu_monomial_closest_point(device: c_int, height: f64, steps: u32, n: u64, points: *const f64, out: *mut f64) -> c_int;
         pub fn rptgpu_particles_eval_hypot(device: c_int, n: u64, x: *const f64, y: *const f64, out: *mut f64) -> c_int;
     }
+    // include/rpt_gpu_views_seeded.h: a seed per view for the batches of views — optional additions within ABI 7 (a library
+    // without them is detected with dlsym("rptgpu_render_views_seeded"); this crate links them like the rest)
+    extern "C" {
+        pub fn rptgpu_render_views_seeded(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, out: *mut f64) -> c_int;
+        pub fn rptgpu_render_views_seeded_device(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, d_out: *mut c_void, out_is_f32: c_int, stream: *mut c_void) -> c_int;
+        pub fn rptgpu_render_views_aov_seeded(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, out: *const RptAovBuffers) -> c_int;
+        pub fn rptgpu_render_views_aov_seeded_device(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, d_out: *const RptAovBuffers, stream: *mut c_void) -> c_int;
+    }
 }
 
 pub use ffi::{RptCamera, RptMaterial, RptRenderParams, RptSceneOptions, RptStats, RptTransform, RptTriangle};

@@ -4,12 +4,15 @@ copy, or scripts/build_variant.sh on that commit), else through this one.
 
 Workloads: 16 and 64 perspective views (a 4x4 and an 8x8 light field: the scene's camera moved sideways and up in steps
 of 2 % of its distance from the origin) of scenes.fractal_spheres and scenes.cornell at 480x270, 8 bounces, 4 spp, every
-view with the same seed, frames in device memory — and the same batch with seed_stride = 1 (`batched_stride`): every view a
-piece of its own, nothing shared between views.  The loop is timed on both routes a render offers: the library's own
-choice (flags 0: the persistent kernel for the Cornell box) and RPT_FLAG_WAVEFRONT.  After two warm-up calls of each kind,
-five alternating repeats of host wall time around the synchronous calls: median, min and max, and views per second from
-the median.  All frames must be bit-equal between the variants (the strided batch: to the loop with the same seeds), and finite:
-the script exits with status 1 after writing its lines when they are not.  No threshold: the figures are recorded as they come.
+view with the same seed, frames in device memory — and the same batch with a seed per view: seed_stride = 1 on this build
+(`batched_stride`: the seed travels with the path, pieces span views) beside the same call on the --parent-lib build
+(`batched_stride_parent`: every view a piece of its own there, nothing shared between views), and seeds that are no
+arithmetic sequence through rptgpu_render_views_seeded_device (`batched_seeds`).  The loop is timed on both routes a render
+offers: the library's own choice (flags 0: the persistent kernel for the Cornell box) and RPT_FLAG_WAVEFRONT.  After two
+warm-up calls of each kind, five alternating repeats of host wall time around the synchronous calls: median, min and max,
+and views per second from the median.  All frames must be bit-equal between the variants (the batches with a seed per view:
+to the loop with the same seeds), and finite: the script exits with status 1 after writing its lines when they are not.  No
+threshold: the figures are recorded as they come.
 
 Then one 2048x1024 panorama of scenes.wine_glass at 16 spp beside rptgpu_trace_rays_device on as many rays made by the
 caller (the texel centres' directions, made with torch), both under RPT_FLAG_PROFILE_KERNELS: wall, the summed kernel_ms
@@ -48,6 +51,7 @@ class RawScene:
         self.h = C.c_void_p()
         self.lib.rptgpu_scene_create.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
         self.lib.rptgpu_render_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self.lib.rptgpu_render_views_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         self.lib.rptgpu_scene_destroy.argtypes = [C.c_void_p]
         self.lib.rptgpu_scene_destroy.restype = None
         rc = self.lib.rptgpu_scene_create(C.byref(self.desc), 0, C.byref(self.h))
@@ -58,6 +62,11 @@ class RawScene:
         rc = self.lib.rptgpu_render_batch_device(self.h, C.byref(cam), C.byref(p), C.c_void_p(d_ptr), 0, None)
         if rc != 0:
             raise RuntimeError("rptgpu_render_batch_device: %d" % rc)
+
+    def render_views_device(self, n, views, q, d_ptr):
+        rc = self.lib.rptgpu_render_views_device(self.h, n, views, C.byref(q), C.c_void_p(d_ptr), 0, None)
+        if rc != 0:
+            raise RuntimeError("rptgpu_render_views_device: %d" % rc)
 
     def close(self):
         self.lib.rptgpu_scene_destroy(self.h)
@@ -73,6 +82,18 @@ def light_field(camera, n):
     step = 0.02 * float(np.linalg.norm(eye))
     return [Camera(tuple(eye + (i - 0.5 * (k - 1)) * step * right + (j - 0.5 * (k - 1)) * step * up), camera.direction,
                    camera.up, camera.fov, 0.0, 0.0) for j in range(k) for i in range(k)]
+
+
+def scattered_seeds(n):
+    """n seeds that are no arithmetic sequence: SplitMix64's outputs from SEED on"""
+    out, x, mask = [], SEED, (1 << 64) - 1
+    for _ in range(n):
+        x = (x + 0x9E3779B97F4A7C15) & mask
+        z = x
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & mask
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & mask
+        out.append(z ^ (z >> 31))
+    return out
 
 
 def summary(wall, n_views):
@@ -113,22 +134,39 @@ def bench_views(name, scene, camera, n_views, parent_lib, dev):
         for v, cam in enumerate(lowered):
             loop.render_device(cam, p, out[v].data_ptr())
 
-    # every view with a seed of its own (seed_stride = 1): a piece's Frame carries one seed, so each view is a piece of its
-    # own and the call is the per-view loop behind one entry point — measured beside the others, checked against the loop
-    # with the same seeds (rendered once, untimed)
-    frames["batched_stride"] = torch.zeros_like(frames["batched"])
+    # every view with a seed of its own: seed_stride = 1 on this build, where the seed travels with the path and the views
+    # share their launches, beside the same call on the loop's build (the parent's: each view a piece of its own), and seeds
+    # that are no arithmetic sequence — measured beside the others, checked against the loop with the same seeds (rendered
+    # once, untimed)
+    for v in ("batched_stride", "batched_stride_parent", "batched_seeds"):
+        frames[v] = torch.zeros_like(frames["batched"])
+    seeds = scattered_seeds(n_views)
+    arr = GpuScene._lower_views(cams, "views_bench")
+    q = _abi.RptViewQuery()
+    q.struct_size, q.width, q.height, q.max_bounces, q.iterations = C.sizeof(_abi.RptViewQuery), W, H, BOUNCES, SPP
+    q.seed, q.seed_stride, q.precision_mode = SEED, 1, _abi.RPT_PRECISION_F64_STRICT
 
     def batched_stride():
         g.render_views(cams, W, H, BOUNCES, samples=SPP, seed=SEED, seed_stride=1, out=frames["batched_stride"])
 
-    runs = {"batched": batched, "batched_stride": batched_stride, "looped": lambda: looped(0, "looped"),
+    def batched_stride_parent():
+        loop.render_views_device(n_views, arr, q, frames["batched_stride_parent"].data_ptr())
+
+    def batched_seeds():
+        g.render_views(cams, W, H, BOUNCES, samples=SPP, seeds=seeds, out=frames["batched_seeds"])
+
+    runs = {"batched": batched, "batched_stride": batched_stride, "batched_stride_parent": batched_stride_parent,
+            "batched_seeds": batched_seeds, "looped": lambda: looped(0, "looped"),
             "looped_wavefront": lambda: looped(_abi.RPT_FLAG_WAVEFRONT, "looped_wavefront")}
     wall, _ = alternate(runs)
     equal = bool(torch.equal(frames["batched"], frames["looped"]) and torch.equal(frames["batched"], frames["looped_wavefront"]))
     want = torch.zeros_like(frames["batched"])
     for v, cam in enumerate(lowered):
         loop.render_device(cam, make_params(W, H, BOUNCES, SPP, seed=SEED + v), want[v].data_ptr())
-    equal = equal and bool(torch.equal(frames["batched_stride"], want))
+    equal = equal and bool(torch.equal(frames["batched_stride"], want) and torch.equal(frames["batched_stride_parent"], want))
+    for v, cam in enumerate(lowered):
+        loop.render_device(cam, make_params(W, H, BOUNCES, SPP, seed=seeds[v]), want[v].data_ptr())
+    equal = equal and bool(torch.equal(frames["batched_seeds"], want))
     res = dict(bench="views", scene=name, views=n_views, width=W, height=H, spp=SPP, max_bounces=BOUNCES, repeats=REPEATS,
                loop_library="parent" if parent_lib else "this", gpu=torch.cuda.get_device_name(0),
                views_piece=os.environ.get("RPTGPU_VIEWS_PIECE", "default"),
@@ -137,6 +175,10 @@ def bench_views(name, scene, camera, n_views, parent_lib, dev):
     for v in ("looped", "looped_wavefront"):
         res["batched_over_" + v] = round(res["runs"]["batched"]["views_per_s"] / res["runs"][v]["views_per_s"], 3)
         res["batched_stride_over_" + v] = round(res["runs"]["batched_stride"]["views_per_s"] / res["runs"][v]["views_per_s"], 3)
+    vps = {v: res["runs"][v]["views_per_s"] for v in runs}
+    res["batched_stride_over_batched_stride_parent"] = round(vps["batched_stride"] / vps["batched_stride_parent"], 3)
+    res["batched_stride_over_batched"] = round(vps["batched_stride"] / vps["batched"], 3)
+    res["batched_seeds_over_batched"] = round(vps["batched_seeds"] / vps["batched"], 3)
     loop.close()
     g.close()
     return res
