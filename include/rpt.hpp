@@ -848,6 +848,49 @@ class Renderer {
     if (seeds.size() != views.size()) throw std::invalid_argument("render_views_aov: one seed per view");
     return views_aov(views, &seeds, 0, sample_index_base, channels);
   }
+  // addition: a denoised frame per view in one call (rptgpu_render_views_denoised, include/rpt_gpu_views_denoised.h): per
+  // view what denoised_render builds from a device Buffer — `batches` batches of num_samples paths per pixel, batch b from
+  // sample sample_index_base + b * num_samples, features from the first hits of feature_samples samples from
+  // feature_sample_index_base, the a-trous filter —, for the whole batch of views in shared passes.  seeds: one per view, or
+  // empty: view v renders with seed + v * seed_stride.  -> `denoised` [views][height][width][3], and where asked for its
+  // color_bytes (`rgb8`), the unfiltered mean of the batches (`mean`) and the variance of that mean (`variance`,
+  // [views][height][width]).
+  struct DenoisedViews {
+    std::vector<double> denoised, mean, variance;
+    std::vector<uint8_t> rgb8;
+  };
+  DenoisedViews render_views_denoised(const std::vector<RptView>& views, uint32_t batches, const std::vector<uint64_t>& seeds = {},
+                                      uint64_t seed_stride = 0, uint64_t sample_index_base = 0, uint32_t feature_samples = 4,
+                                      uint64_t feature_sample_index_base = 0, uint32_t levels = 3, double sigma_color = 2.0,
+                                      double sigma_normal = 0.1, double sigma_depth = 0.01, double sigma_albedo = 0.1,
+                                      bool want_rgb8 = false, bool want_mean = false, bool want_variance = false) {
+    ensure_scene();
+    if (!seeds.empty() && seeds.size() != views.size()) throw std::invalid_argument("render_views_denoised: one seed per view");
+    if (!seeds.empty() && seed_stride) throw std::invalid_argument("render_views_denoised: seeds and a seed stride exclude each other");
+    RptViewQuery q{};
+    q.struct_size = sizeof(RptViewQuery); q.width = width_; q.height = height_; q.max_bounces = max_bounces_;
+    q.iterations = num_samples_; q.exposure_value = ev_; q.seed = seed_; q.seed_stride = seed_stride;
+    q.sample_index_base = sample_index_base;
+    RptViewDenoise d{};
+    d.struct_size = sizeof(RptViewDenoise); d.batches = batches; d.feature_iterations = feature_samples;
+    d.feature_sample_index_base = feature_sample_index_base;
+    d.filter = RptDenoise{sizeof(RptDenoise), levels, sigma_color, sigma_normal, sigma_depth, sigma_albedo};
+    const size_t n = views.size() * (size_t)width_ * height_;
+    DenoisedViews r;
+    if (!n) return r; // (an empty vector has no address, and `denoised` must not be NULL)
+    r.denoised.resize(3 * n);
+    if (want_rgb8) r.rgb8.resize(3 * n);
+    if (want_mean) r.mean.resize(3 * n);
+    if (want_variance) r.variance.resize(n);
+    RptViewDenoiseOut o{};
+    o.struct_size = sizeof(RptViewDenoiseOut);
+    o.denoised = r.denoised.data();
+    o.rgb8 = want_rgb8 ? r.rgb8.data() : nullptr;
+    o.mean = want_mean ? r.mean.data() : nullptr;
+    o.variance = want_variance ? r.variance.data() : nullptr;
+    check(rptgpu_render_views_denoised(handle_, views.size(), views.data(), &q, seeds.empty() ? nullptr : seeds.data(), &d, &o));
+    return r;
+  }
 
  private:
   Aovs views_aov(const std::vector<RptView>& views, const std::vector<uint64_t>* seeds, uint64_t seed_stride,

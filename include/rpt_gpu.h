@@ -674,8 +674,9 @@ int rptgpu_bake_ao_device(rptgpu_scene* h, uint64_t n, const void* d_positions, 
  * advances as for a render (samples = n_views * width * height * iterations).  RPTGPU_VIEWS_PIECE (environment, read per
  * call; tests): the indices per piece.
  * NOT IN SCOPE: the tile partition and multi-GPU (a caller shards the VIEWS over handles: a view's pixels depend on nothing
- * else), the device-resident Buffer and the denoiser for views, and the persistent path kernel (the views' feature buffers:
- * rptgpu_render_views_aov, below).
+ * else), the device-resident Buffer for views, and the persistent path kernel (the views' feature buffers:
+ * rptgpu_render_views_aov, below; a denoised frame per view — batches, features and the filter of rptgpu_buffer_denoise over
+ * the whole batch of views —: rpt_gpu_views_denoised.h, which this file includes at its end).
  * RPTGPU_E_INVALID_ARGUMENT, checked before any device work and with a detail naming the reason: a NULL RptViewQuery, a
  * wrong struct_size, width, height or iterations == 0, max_bounces > 254, a precision_mode other than
  * RPT_PRECISION_F64_STRICT, RPT_FLAG_PERSISTENT, width * height > 2^32, NULL views or out with n_views > 0, frames whose
@@ -1022,6 +1023,8 @@ const char* rptgpu_kernel_name(int k);
 
 /* ---- optional additions within ABI version 7, detected by symbol: a seed per view for the batches of views ---- */
 #include "rpt_gpu_views_seeded.h"
+/* ---- ... and a denoised frame per view of a batch ---- */
+#include "rpt_gpu_views_denoised.h"
 
 #ifdef __cplusplus
 }

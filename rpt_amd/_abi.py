@@ -191,6 +191,18 @@ class RptAoQuery(C.Structure):
                 ("max_distance", f64), ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class RptViewDenoise(C.Structure):
+    """include/rpt_gpu_views_denoised.h RptViewDenoise (rptgpu_render_views_denoised's batches, features and filter)."""
+    _fields_ = [("struct_size", C.c_uint32), ("batches", C.c_uint32), ("feature_iterations", C.c_uint32), ("_pad", C.c_uint32),
+                ("feature_sample_index_base", C.c_uint64), ("filter", RptDenoise)]
+
+
+class RptViewDenoiseOut(C.Structure):
+    """include/rpt_gpu_views_denoised.h RptViewDenoiseOut (rptgpu_render_views_denoised's output arrays; any may be NULL)."""
+    _fields_ = [("struct_size", C.c_uint32), ("_pad", C.c_uint32), ("denoised", C.POINTER(f64)), ("rgb8", C.POINTER(C.c_uint8)),
+                ("mean", C.POINTER(f64)), ("variance", C.POINTER(f64))]
+
+
 class RptView(C.Structure):
     """include/rpt_gpu.h RptView (one view of rptgpu_render_views; detected by symbol within ABI 7)."""
     _fields_ = [("camera", RptCamera), ("projection", C.c_uint32), ("_pad", C.c_uint32), ("ortho_scale", f64)]
@@ -303,6 +315,15 @@ SEEDED_SYMBOLS = [
     ("rptgpu_render_views_aov_seeded_device", C.c_int,
      [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(C.c_uint64), C.POINTER(RptAovBuffers), _VP]),
 ]
+# ... and every symbol include/rpt_gpu_views_denoised.h declares, optional in the same way
+DENOISED_SYMBOLS = [
+    ("rptgpu_render_views_denoised", C.c_int,
+     [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(C.c_uint64), C.POINTER(RptViewDenoise),
+      C.POINTER(RptViewDenoiseOut)]),
+    ("rptgpu_render_views_denoised_device", C.c_int,
+     [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(C.c_uint64), C.POINTER(RptViewDenoise),
+      C.POINTER(RptViewDenoiseOut), _VP]),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -327,7 +348,7 @@ def load_library(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % p)
     lib = C.CDLL(p)
-    for name, restype, argtypes in SYMBOLS + SEEDED_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + SEEDED_SYMBOLS + DENOISED_SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

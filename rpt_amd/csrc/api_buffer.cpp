@@ -37,9 +37,9 @@ struct rptgpu_buffer {
   }
 };
 
-namespace {
+namespace rptapi {
 // color_bytes (color.rs:18-24) as the host computes it; the device reproduces it from thresholds
-inline int color_byte_host(double v) {
+static inline int color_byte_host(double v) {
   double t = std::pow(std::fmin(std::fmax(v, 0.0), 1.0), 1.0 / 2.2) * 255.0;
   return !(t > 0.0) ? 0 : (t >= 255.0 ? 255 : (int)t);
 }
@@ -70,7 +70,7 @@ std::vector<double> byte_thresholds(bool& clean) {
   return thr;
 }
 // what is wrong with an RptAdaptive (nullptr: nothing)
-const char* bad_adaptive(const RptAdaptive* a) {
+static const char* bad_adaptive(const RptAdaptive* a) {
   if (!a) return "null RptAdaptive";
   if (a->struct_size != sizeof(RptAdaptive)) return "RptAdaptive: struct_size is not sizeof(RptAdaptive)";
   if (a->min_batches < 2) return "RptAdaptive: min_batches < 2";
@@ -78,7 +78,6 @@ const char* bad_adaptive(const RptAdaptive* a) {
     return "RptAdaptive: abs_tol and rel_tol must be finite and >= 0";
   return nullptr;
 }
-constexpr uint32_t FEATURE_CHANNELS = RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION;
 // what is wrong with an RptDenoise (nullptr: nothing)
 const char* bad_denoise(const RptDenoise* d) {
   if (!d) return "null RptDenoise";
@@ -88,7 +87,7 @@ const char* bad_denoise(const RptDenoise* d) {
     if (!(std::isfinite(s) && s > 0.0)) return "RptDenoise: every sigma must be finite and > 0";
   return nullptr;
 }
-} // namespace
+} // namespace rptapi
 
 extern "C" {
 

@@ -182,6 +182,8 @@ RptAovBuffers aov_buffers_at(const RptAovBuffers& a, uint64_t base) {
   return b;
 }
 
+} // namespace
+
 // out's arrays: host memory, or — on_device — device memory (user_stream: the stream their producer ran on); views and the
 // structs are host memory either way.  seeded: the _seeded entry points — view v's seed is seeds[v] (host memory), and
 // q's seed and seed_stride are not read
@@ -274,7 +276,6 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
   });
 }
 
-} // namespace
 } // namespace rptapi
 
 extern "C" {

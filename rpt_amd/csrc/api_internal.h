@@ -19,6 +19,8 @@
 //   api_probes.cpp   rptgpu_bake_probes[_device]: light probes (SH9 radiance, irradiance) through the same driver, in pieces
 //   api_views.cpp    rptgpu_render_views[_seeded][_device]: batches of perspective, orthographic and panoramic views through the
 //                    same driver, in pieces of consecutive (view, pixel) indices, with one seed or a seed per view
+//   api_views_denoise.cpp rptgpu_render_views_denoised[_device]: per batch the views driver into a device frame and one
+//                    rpt_buffer_accumulate over all views, then the views' feature sums and the filter, one launch per step
 //   api_occlusion.cpp rptgpu_occluded[_device], rptgpu_bake_ao[_device]: the caller's rays, or points x directions made on the
 //                    device, through ONE visibility query of a render per pass (no depth loop), in pieces
 //   api_hits.cpp     rptgpu_first_hits[_device], rptgpu_render_views_aov[_seeded][_device]: the first hit's record for the caller's rays
@@ -189,6 +191,12 @@ struct rptgpu_scene {
   DevBuf<rptdev::View> view_recs;      // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<uint64_t> view_seeds;         // ... their seeds, when the views have seeds of their own,
   DevBuf<uint64_t> ray_seeds;          // ... and then the seed of each index of a piece, beside ray_ids
+  // rptgpu_render_views_denoised's working set over the batch's n_views * width * height indices (api_views_denoise.cpp;
+  // the bytes: rptplan::views_denoise_plan), grown on demand: the Buffer's per-pixel state, one batch's frame, the feature
+  // sums, the filter's columns and hit flags, color_bytes' thresholds, and a host caller's outputs before they are copied
+  DevBuf<double> vd_total, vd_mean, vd_m2, vd_stage, vd_feat, vd_cols, vd_thr, vd_linear, vd_out_mean, vd_out_var;
+  DevBuf<uint32_t> vd_counts;
+  DevBuf<uint8_t> vd_hit, vd_rgb8;
   DevBuf<double> aov_out;              // rptgpu_render_aov: the requested channels' full-frame arrays, back to back (api_aov.cpp)
   int num_cus = 0;
   bool prefer_wavefront = false; // scene has real kd-trees: traversal-latency bound
@@ -383,6 +391,13 @@ const char* bad_view(const RptView& v, const RptViewQuery& q);
 // wrapping u64 arithmetic; empty: every view has the query's seed (seed_stride == 0), the one-seed route
 constexpr const char* NULL_SEEDS = "null seeds: the _seeded entry points take one seed per view";
 std::vector<uint64_t> view_seed_list(uint64_t n_views, const RptViewQuery& q, const uint64_t* seeds);
+// the drivers behind rptgpu_render_views[_seeded][_device] (api_views.cpp) and rptgpu_render_views_aov[_seeded][_device]
+// (api_hits.cpp), argument checks included; rptgpu_render_views_denoised (api_views_denoise.cpp) runs both into device arrays
+// of its own.  out / out's arrays: host memory, or — on_device — device memory; seeded: view v's seed is seeds[v] (host)
+int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, bool seeded, const uint64_t* seeds,
+                 void* out, bool on_device, bool out_f32, hipStream_t user_stream);
+int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, bool seeded,
+                     const uint64_t* seeds, const RptAovBuffers* out, bool on_device, hipStream_t user_stream);
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
 const char* bad_probe_query(const RptProbeQuery* q);
@@ -408,6 +423,13 @@ rptdev::AovOut aov_arrays(DevBuf<double>& arrays, hipStream_t st, uint64_t n, ui
 bool aov_enqueue(rptgpu_scene* h, const RptCamera& camera, const RptRenderParams& p, const rptdev::AovOut& ao);
 // hits and the arrays of `channels` for n pixels from the device to the caller's, on st
 void copy_aov_out(const rptdev::AovOut& src, uint32_t channels, const RptAovBuffers& dst, uint64_t n, hipStream_t st);
+
+// api_buffer.cpp: what the Buffer's filter shares with the views' (api_views_denoise.cpp) — what is wrong with an RptDenoise
+// (nullptr: nothing), the features the filter reads, and color_bytes' staircase for the device (thr[k]: the smallest v in
+// [0, 1] whose byte is >= k; clean: the host's conversion is a step function around every threshold)
+const char* bad_denoise(const RptDenoise* d);
+constexpr uint32_t FEATURE_CHANNELS = RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION;
+std::vector<double> byte_thresholds(bool& clean);
 
 // A handle whose aborted batch never drained (rptgpu_render_batch_reduce, drain_after_abort): the abandoned stream's
 // kernels may still read and write the workspace, the frame buffers and events, so every call that would enqueue work

@@ -51,8 +51,6 @@ std::vector<uint64_t> view_seed_list(uint64_t n_views, const RptViewQuery& q, co
   return list;
 }
 
-namespace {
-
 // out: host memory ([n_views][height][width][3] f64), or — on_device — device memory of f64 or f32 (user_stream: the
 // stream its producer ran on); views is host memory either way.  seeded: the _seeded entry points — view v's seed is
 // seeds[v] (host memory), and q's seed and seed_stride are not read
@@ -135,7 +133,6 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
   return RPTGPU_OK;
 }
 
-} // namespace
 } // namespace rptapi
 
 extern "C" {

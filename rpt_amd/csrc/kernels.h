@@ -224,6 +224,20 @@ struct KernelTable {
   void (*shade_seeded)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::PathState&, const uint32_t* queue,
                        uint32_t n, uint32_t depth, uint32_t* next_queue, uint32_t* counters, uint32_t* sq, uint32_t* zero_next,
                        uint32_t zero_n, uint32_t rec_off, const uint64_t* seeds);
+  // the filter over a batch of views of one size (rptgpu_render_views_denoised; kernels/denoise.inc):
+  // denoise_prepare / _level / _finish with every array and column holding n_views * w * h elements, view after view
+  // (stride = that product), ONE launch each for the whole batch (the view in blockIdx.z; batches of more than 65535 views
+  // take one launch per 65535), taps bounded by the view's own frame.  views_finish also gives the filter's unfiltered
+  // inputs: out_mean = total / n ([index][3]) and out_variance = (M2 / (n - 1)) / n; any of its four outputs may be null
+  void (*denoise_views_prepare)(hipStream_t, const double* total, const uint32_t* counts, const double* m2,
+                                const rptdev::AovOut& feat, uint32_t w, uint32_t h, uint64_t n_views, uint64_t stride, double* c_out,
+                                double* v_out, double* g_normal, double* g_position, double* g_albedo, double* g_depth,
+                                uint8_t* g_hit);
+  void (*denoise_views_level)(hipStream_t, const rptdev::DenoiseGuide&, uint64_t n_views, const double* c_in, const double* v_in,
+                              double* c_out, double* v_out, uint32_t step, const rptdev::DenoiseSigmas&);
+  void (*denoise_views_finish)(hipStream_t, const double* c_in, uint64_t stride, uint64_t n, const double* thr, double* out_linear,
+                               uint8_t* out_rgb8, const double* total, const uint32_t* counts, const double* m2, double* out_mean,
+                               double* out_variance);
 };
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)

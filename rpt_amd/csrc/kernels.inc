@@ -31,7 +31,8 @@
 //                       rpt_shadow_sum / rpt_resolve* / rpt_finish* / rpt_path_permute
 //   buffer.inc     device-resident Buffer (buffer.rs)
 //   aov.inc        first-hit feature buffers: rpt_aov (fused) and rpt_aov_fold (behind the per-tree query), DESIGN.md §11
-//   denoise.inc    the device Buffer's feature-guided à-trous filter (rpt_denoise_prepare / _level / _finish), DESIGN.md §12
+//   denoise.inc    the device Buffer's feature-guided à-trous filter (rpt_denoise_prepare / _level / _finish), DESIGN.md §12,
+//                  and, from the same text, the filter over a batch of views (rpt_denoise_views_prepare / _level / _finish), §18
 //   occlusion.inc  rptgpu_occluded / rptgpu_bake_ao: the caller's rays into a depth's shadow-ray state and their answers out of it
 //                  (rpt_occ_load, rpt_raygen_ao, rpt_occ_store, rpt_ao_fold), DESIGN.md §16
 //   hits.inc       rptgpu_first_hits / rptgpu_render_views_aov: the closest-hit record into the caller's layout (rpt_first_hits
@@ -108,7 +109,14 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/paths.inc"
 #include "kernels/buffer.inc"
 #include "kernels/aov.inc"
+// the Buffer's filter kernels and rpt_denoise_views_*: kernels/denoise.inc, once per frame layout (RPT_DN_VIEWS 0: one camera's
+// frame; 1: a batch of views, one launch for all of them)
+#define RPT_DN_VIEWS 0
 #include "kernels/denoise.inc"
+#undef RPT_DN_VIEWS
+#define RPT_DN_VIEWS 1
+#include "kernels/denoise.inc"
+#undef RPT_DN_VIEWS
 #include "kernels/occlusion.inc"
 #include "kernels/hits.inc"
 #include "kernels/launch.inc"

@@ -7,6 +7,16 @@
 // its taps in the contract's order (dx outer, dy inner, ascending) and adds in that order: the result is defined to
 // the bit whatever the schedule.  The tap loops are NOT unrolled: the body holds an inlined exp, and 25 copies of it
 // would be an instruction-cache problem for no arithmetic saved.
+//
+// ONE text, included twice by kernels.inc: RPT_DN_VIEWS 0 gives the Buffer's three kernels, one camera's frame per launch; 1
+// gives rpt_denoise_views_prepare / _level / _finish (rptgpu_render_views_denoised, DESIGN.md §18), one launch for a batch of
+// views of one size.  There the arrays and columns hold n_views * w * h elements, view after view; a block's view is view0 +
+// blockIdx.z, a pixel's index is view * (w * h) + y * w + x, and x, y and every tap's bounds are those of the view's own
+// frame: a tap never reads another view.  (Why not a template: wf_raygen_views.inc.)
+#if RPT_DN_VIEWS
+#define RPT_DN_KERNEL(name) rpt_denoise_views_##name
+#else
+#define RPT_DN_KERNEL(name) rpt_denoise_##name
 
 // the kernel of a level, k = [1/16, 1/4, 3/8, 1/4, 1/16], and of the variance prefilter, g = [1/4, 1/2, 1/4]
 RPT_DEV double atrous_k(int d) { return d == 0 ? 0.375 : ((d == 1 || d == -1) ? 0.25 : 0.0625); }
@@ -16,18 +26,28 @@ RPT_DEV double mean_variance(const uint32_t* __restrict__ counts, const double* 
   const double n = (double)counts[q];
   return (m2[q] / (n - 1.0)) / n;
 }
+#endif
 
 // the filter's inputs as columns: c = total / n, v = the 3x3 prefilter of the neighbours' mean_variance (taps outside
 // the frame skipped, dx outer / dy inner), the means of the held feature sums and the hit flag (0 everywhere for a miss)
-__global__ void __launch_bounds__(256) rpt_denoise_prepare(const double* __restrict__ total, const uint32_t* __restrict__ counts,
+__global__ void __launch_bounds__(256) RPT_DN_KERNEL(prepare)(const double* __restrict__ total, const uint32_t* __restrict__ counts,
                                                            const double* __restrict__ m2, AovOut feat, uint32_t w, uint32_t h,
                                                            uint64_t stride, double* __restrict__ c_out, double* __restrict__ v_out,
                                                            double* __restrict__ g_normal, double* __restrict__ g_position,
                                                            double* __restrict__ g_albedo, double* __restrict__ g_depth,
-                                                           uint8_t* __restrict__ g_hit) {
+                                                           uint8_t* __restrict__ g_hit
+#if RPT_DN_VIEWS
+                                                           , uint32_t view0 /* the launch's first view */
+#endif
+                                                           ) {
   const uint32_t x = blockIdx.x * 64u + threadIdx.x, y = blockIdx.y * 4u + threadIdx.y;
   if (x >= w || y >= h) return;
+#if RPT_DN_VIEWS
+  const uint64_t base = ((uint64_t)view0 + blockIdx.z) * ((uint64_t)w * h); // the view's first element
+  const uint64_t p = base + (uint64_t)y * w + x;
+#else
   const uint64_t p = (uint64_t)y * w + x;
+#endif
   const D3 c = ld3(total + 3 * p) / (double)counts[p];
   c_out[p] = c.x; c_out[stride + p] = c.y; c_out[2 * stride + p] = c.z;
   double acc = 0.0, ws = 0.0;
@@ -38,7 +58,11 @@ __global__ void __launch_bounds__(256) rpt_denoise_prepare(const double* __restr
       const int64_t qy = (int64_t)y + dy;
       if (qy < 0 || qy >= (int64_t)h) continue;
       const double wgt = prefilter_g(dx) * prefilter_g(dy);
+#if RPT_DN_VIEWS
+      acc = acc + wgt * mean_variance(counts, m2, base + (uint64_t)qy * w + (uint64_t)qx);
+#else
       acc = acc + wgt * mean_variance(counts, m2, (uint64_t)qy * w + (uint64_t)qx);
+#endif
       ws = ws + wgt;
     }
   }
@@ -62,13 +86,22 @@ __global__ void __launch_bounds__(256) rpt_denoise_prepare(const double* __restr
 
 // one level: taps q = p + step * (dx, dy), dx, dy in -2..2.  The centre tap weighs k(0) k(0) without an exponent; any
 // other tap is skipped when hit_q != hit_p or when its exponent e is not in [0, +inf) (a NaN fails both comparisons)
-__global__ void __launch_bounds__(256) rpt_denoise_level(DenoiseGuide g, const double* __restrict__ c_in,
+__global__ void __launch_bounds__(256) RPT_DN_KERNEL(level)(DenoiseGuide g, const double* __restrict__ c_in,
                                                          const double* __restrict__ v_in, double* __restrict__ c_out,
-                                                         double* __restrict__ v_out, uint32_t step, DenoiseSigmas sg) {
+                                                         double* __restrict__ v_out, uint32_t step, DenoiseSigmas sg
+#if RPT_DN_VIEWS
+                                                         , uint32_t view0 /* the launch's first view */
+#endif
+                                                         ) {
   const uint32_t x = blockIdx.x * 64u + threadIdx.x, y = blockIdx.y * 4u + threadIdx.y;
   if (x >= g.width || y >= g.height) return;
   const uint64_t np = g.stride;
+#if RPT_DN_VIEWS
+  const uint64_t base = ((uint64_t)view0 + blockIdx.z) * ((uint64_t)g.width * g.height); // the view's first element
+  const uint64_t p = base + (uint64_t)y * g.width + x;
+#else
   const uint64_t p = (uint64_t)y * g.width + x;
+#endif
   const D3 cp = ld_soa3(c_in, np, p);
   const double vp = v_in[p];
   const bool hit_p = g.hit[p] != 0;
@@ -90,7 +123,11 @@ __global__ void __launch_bounds__(256) rpt_denoise_level(DenoiseGuide g, const d
     for (int dy = -2; dy <= 2; dy++) {
       const int64_t qy = (int64_t)y + (int64_t)dy * (int64_t)step;
       if (qy < 0 || qy >= (int64_t)g.height) continue;
+#if RPT_DN_VIEWS
+      const uint64_t q = base + (uint64_t)qy * g.width + (uint64_t)qx;
+#else
       const uint64_t q = (uint64_t)qy * g.width + (uint64_t)qx;
+#endif
       const D3 cq = ld_soa3(c_in, np, q);
       const double vq = v_in[q];
       double wgt = atrous_k(dx) * atrous_k(dy);
@@ -123,12 +160,27 @@ __global__ void __launch_bounds__(256) rpt_denoise_level(DenoiseGuide g, const d
 }
 
 // the last level's colour columns as the caller's arrays: [pixel][3] f64, and / or color_bytes of it through the
-// buffer's staircase (thr[k]: the smallest v in [0, 1] whose byte is >= k, as rpt_buffer_image uses it)
-__global__ void __launch_bounds__(256) rpt_denoise_finish(const double* __restrict__ c_in, uint64_t stride, uint64_t npix,
+// buffer's staircase (thr[k]: the smallest v in [0, 1] whose byte is >= k, as rpt_buffer_image uses it).
+// rpt_denoise_views_finish: over the batch's npix = n_views * w * h elements, and beside them the filter's two unfiltered
+// inputs for the caller, either may be null: out_mean = c_p = total / n as [pixel][3], out_variance = u_p (mean_variance)
+__global__ void __launch_bounds__(256) RPT_DN_KERNEL(finish)(const double* __restrict__ c_in, uint64_t stride, uint64_t npix,
                                                           const double* __restrict__ thr, double* __restrict__ out_linear,
-                                                          uint8_t* __restrict__ out_rgb8) {
+                                                          uint8_t* __restrict__ out_rgb8
+#if RPT_DN_VIEWS
+                                                          , const double* __restrict__ total, const uint32_t* __restrict__ counts,
+                                                          const double* __restrict__ m2, double* __restrict__ out_mean,
+                                                          double* __restrict__ out_variance
+#endif
+                                                          ) {
   const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npix) return;
+#if RPT_DN_VIEWS
+  if (out_mean) {
+    const D3 c = ld3(total + 3 * p) / (double)counts[p];
+    out_mean[3 * p] = c.x; out_mean[3 * p + 1] = c.y; out_mean[3 * p + 2] = c.z;
+  }
+  if (out_variance) out_variance[p] = mean_variance(counts, m2, p);
+#endif
   const double v[3] = {c_in[p], c_in[stride + p], c_in[2 * stride + p]};
   for (int ch = 0; ch < 3; ch++) {
     if (out_linear) out_linear[3 * p + ch] = v[ch];
@@ -144,3 +196,4 @@ __global__ void __launch_bounds__(256) rpt_denoise_finish(const double* __restri
     }
   }
 }
+#undef RPT_DN_KERNEL

@@ -349,6 +349,32 @@ void launch_denoise_finish(hipStream_t st, const double* c_in, uint64_t stride, 
                            double* out_linear, uint8_t* out_rgb8) {
   hipLaunchKernelGGL(rpt_denoise_finish, grid_for(npix), dim3(256), 0, st, c_in, stride, npix, thr, out_linear, out_rgb8);
 }
+// the same over a batch of views: the view in blockIdx.z, at most 65535 views per launch
+constexpr uint64_t DN_VIEWS_PER_LAUNCH = 65535u;
+void launch_denoise_views_prepare(hipStream_t st, const double* total, const uint32_t* counts, const double* m2, const AovOut& feat,
+                                  uint32_t w, uint32_t h, uint64_t n_views, uint64_t stride, double* c_out, double* v_out,
+                                  double* g_normal, double* g_position, double* g_albedo, double* g_depth, uint8_t* g_hit) {
+  for (uint64_t v0 = 0; v0 < n_views; v0 += DN_VIEWS_PER_LAUNCH) {
+    dim3 grid = grid_rows(w, h);
+    grid.z = (unsigned)std::min(DN_VIEWS_PER_LAUNCH, n_views - v0);
+    hipLaunchKernelGGL(rpt_denoise_views_prepare, grid, dim3(64, 4), 0, st, total, counts, m2, feat, w, h, stride, c_out, v_out,
+                       g_normal, g_position, g_albedo, g_depth, g_hit, (uint32_t)v0);
+  }
+}
+void launch_denoise_views_level(hipStream_t st, const DenoiseGuide& g, uint64_t n_views, const double* c_in, const double* v_in,
+                                double* c_out, double* v_out, uint32_t step, const DenoiseSigmas& sg) {
+  for (uint64_t v0 = 0; v0 < n_views; v0 += DN_VIEWS_PER_LAUNCH) {
+    dim3 grid = grid_rows(g.width, g.height);
+    grid.z = (unsigned)std::min(DN_VIEWS_PER_LAUNCH, n_views - v0);
+    hipLaunchKernelGGL(rpt_denoise_views_level, grid, dim3(64, 4), 0, st, g, c_in, v_in, c_out, v_out, step, sg, (uint32_t)v0);
+  }
+}
+void launch_denoise_views_finish(hipStream_t st, const double* c_in, uint64_t stride, uint64_t n, const double* thr,
+                                 double* out_linear, uint8_t* out_rgb8, const double* total, const uint32_t* counts,
+                                 const double* m2, double* out_mean, double* out_variance) {
+  hipLaunchKernelGGL(rpt_denoise_views_finish, grid_for(n), dim3(256), 0, st, c_in, stride, n, thr, out_linear, out_rgb8, total,
+                     counts, m2, out_mean, out_variance);
+}
 
 // debug builds with -DRPT_PROF: the per-phase table of kernels/prof.inc accumulated so far (and reset):
 // out[0] wave cycles, [1] lane cycles, [2] wave iterations, [3] lane iterations, PROF_SLOTS slots each
@@ -374,5 +400,6 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_raygen_probes, launch_resolve_probes, launch_finish_probes, launch_raygen_views,
                            launch_occ_load, launch_raygen_ao, launch_occ_store, launch_ao_fold,
                            launch_first_hits, launch_hits_store, launch_views_aov_fold,
-                           launch_raygen_views_seeded, launch_shade_seeded};
+                           launch_raygen_views_seeded, launch_shade_seeded,
+                           launch_denoise_views_prepare, launch_denoise_views_level, launch_denoise_views_finish};
 #endif // !__HIP_DEVICE_COMPILE__

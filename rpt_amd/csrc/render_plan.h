@@ -1,7 +1,7 @@
 // render_plan.h — how a render call is cut into launches (persistent pipeline) and passes (wavefront pipeline): the
 // arithmetic behind api_render.cpp's drivers, as pure host functions of numbers (tests/cpp/render_plan_check.cpp), and the
 // pieces rptgpu_trace_rays cuts its rays into (tests/cpp/rays_piece_check.cpp) and rptgpu_render_views its views' pixels
-// (tests/cpp/views_piece_check.cpp), rptgpu_occluded its rays and rptgpu_bake_ao its points (tests/cpp/occlusion_piece_check.cpp),
+// (tests/cpp/views_piece_check.cpp; the working set of rptgpu_render_views_denoised: views_denoise_plan_check.cpp), rptgpu_occluded its rays and rptgpu_bake_ao its points (tests/cpp/occlusion_piece_check.cpp),
 // rptgpu_first_hits its rays (tests/cpp/hits_piece_check.cpp).
 #pragma once
 #include <stdint.h>
@@ -238,5 +238,35 @@ inline uint64_t hits_piece(uint64_t n, uint64_t asked, uint64_t pass_bound) {
   const uint64_t fit = hits_pass_max(pass_bound);
   return std::max<uint64_t>(1, std::min(std::min<uint64_t>(n, asked ? asked : fit), fit));
 }
+
+// ---- rptgpu_render_views_denoised: the batch's n = n_views * npix indices hold their state, a batch's frame, the feature
+// sums and the filter's columns at once (tests/cpp/views_denoise_plan_check.cpp).  n must fit 32 bits less one:
+// rpt_buffer_accumulate indexes in uint32_t and its launch covers n rounded up to 256.  Bytes per array group, for the
+// caller to report and for DESIGN.md §18's figure; `outputs` only for a host caller, whose results are staged on the device.
+constexpr uint64_t VIEWS_DENOISE_MAX_N = 0xffffffffull;
+struct ViewsDenoisePlan {
+  uint64_t n;        // indices of the batch; 0: the batch does not fit (or there is nothing to do)
+  uint64_t state;    // total [n][3], mean [n][3], M2 [n] f64 and counts [n] u32
+  uint64_t staging;  // one batch's frame [n][3] f64
+  uint64_t features; // hits [n] u32 (padded to a double), depth [n], normal, albedo, position [n][3] f64
+  uint64_t columns;  // 18 f64 columns of n and the hit flags [n] u8
+  uint64_t outputs;  // a host caller's requested outputs: denoised 24, rgb8 3, mean 24, variance 8 B per index
+  uint64_t bytes() const { return state + staging + features + columns + outputs; }
+};
+inline ViewsDenoisePlan views_denoise_plan(uint64_t n_views, uint64_t npix, bool host, bool denoised, bool rgb8, bool mean,
+                                           bool variance) {
+  ViewsDenoisePlan p{};
+  if (!n_views || !npix || n_views > VIEWS_DENOISE_MAX_N / npix) return p; // (the quotient first: the product may not fit 64 bits)
+  const uint64_t n = n_views * npix;
+  p.n = n;
+  p.state = n * (24 + 24 + 8 + 4);
+  p.staging = n * 24;
+  p.features = ((n + 1) / 2 * 2 + 3 * ((3 * n + 1) / 2 * 2) + (n + 3) / 4 * 2) * 8; // aov_arrays' layout (api_aov.cpp)
+  p.columns = n * (18 * 8 + 1);
+  if (host) p.outputs = n * ((denoised ? 24u : 0u) + (rgb8 ? 3u : 0u) + (mean ? 24u : 0u) + (variance ? 8u : 0u));
+  return p;
+}
+// the samples base .. base + count - 1 (count >= 1) are all 64-bit indices
+inline bool sample_range_fits(uint64_t base, uint64_t count) { return count - 1 <= ~0ull - base; }
 
 } // namespace rptplan

@@ -870,6 +870,94 @@ class GpuScene:
         _abi.check(code, self.handle)
         return arrays
 
+    _DENOISED_OUTPUTS = (("denoised", (3,), np.float64), ("rgb8", (3,), np.uint8), ("mean", (3,), np.float64),
+                         ("variance", (), np.float64))
+
+    def render_views_denoised(self, views, width, height, max_bounces, samples, batches, seed=0x52505447, seed_stride=0,
+                              seeds=None, sample_index_base=0, feature_samples=4, feature_sample_index_base=0, levels=3,
+                              sigma_color=2.0, sigma_normal=0.1, sigma_depth=0.01, sigma_albedo=0.1, exposure_value=0.0,
+                              flags=0, want=("denoised",), out=None):
+        """A denoised frame per view in one call (rptgpu_render_views_denoised) -> a dict with one array per
+        name of `want`, the views as the leading axis: `denoised` (n, H, W, 3) float64, `rgb8` (n, H, W, 3) uint8 (its
+        color_bytes), `mean` (n, H, W, 3) float64 (the unfiltered mean of the batches) and `variance` (n, H, W) float64 (the
+        unfiltered variance of that mean).  Per view this is DeviceBuffer.sample `batches` times — `samples` paths per pixel
+        each, batch b from sample sample_index_base + b * samples —, .features with feature_samples first-hit samples from
+        feature_sample_index_base, and .denoise with levels and the sigmas: a perspective view's `denoised` has that Buffer's
+        bits.  views, seed, seed_stride, seeds: render_views'.  `want` must name `denoised` or `rgb8`.
+        out: None (new numpy arrays through host memory) or a dict of C-contiguous numpy arrays with exactly the keys of
+        `want`; or "torch" for new tensors on the handle's device, or a dict of contiguous torch tensors there, written where
+        they lie (rptgpu_render_views_denoised_device)."""
+        views = list(views)
+        n, width, height = len(views), int(width), int(height)
+        arr = self._lower_views(views, "render_views_denoised")
+        seed_arr = self._lower_seeds(seeds, n, seed_stride, "render_views_denoised")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        known = [name for name, _, _ in self._DENOISED_OUTPUTS]
+        if not want or len(set(want)) != len(want) or any(w not in known for w in want):
+            raise ValueError("render_views_denoised: want must name each of %s at most once, and one at least" % (known,))
+        if "denoised" not in want and "rgb8" not in want:
+            raise ValueError("render_views_denoised: want must name `denoised` or `rgb8`")
+        q = _abi.RptViewQuery()
+        q.struct_size = C.sizeof(_abi.RptViewQuery)
+        q.width, q.height, q.max_bounces, q.iterations = width, height, int(max_bounces), int(samples)
+        q.exposure_value, q.seed, q.seed_stride = float(exposure_value), int(seed), int(seed_stride)
+        q.sample_index_base, q.precision_mode, q.flags = int(sample_index_base), _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        d = _abi.RptViewDenoise()
+        d.struct_size, d.batches, d.feature_iterations = C.sizeof(_abi.RptViewDenoise), int(batches), int(feature_samples)
+        d.feature_sample_index_base = int(feature_sample_index_base)
+        d.filter.struct_size, d.filter.levels = C.sizeof(_abi.RptDenoise), int(levels)
+        d.filter.sigma_color, d.filter.sigma_normal = float(sigma_color), float(sigma_normal)
+        d.filter.sigma_depth, d.filter.sigma_albedo = float(sigma_depth), float(sigma_albedo)
+        layout = [(name, (n, height, width) + tail, dtype) for name, tail, dtype in self._DENOISED_OUTPUTS if name in want]
+        o = _abi.RptViewDenoiseOut()
+        o.struct_size = C.sizeof(_abi.RptViewDenoiseOut)
+        types = dict(_abi.RptViewDenoiseOut._fields_)
+        host = isinstance(out, dict) and all(isinstance(v, np.ndarray) for v in out.values())
+        if out is None or host:
+            # (at least one view's worth: an empty array's address may be NULL, and a wanted output's pointer must not be)
+            room = None if host else {name: np.empty((max(n, 1),) + shape[1:], dtype=dtype) for name, shape, dtype in layout}
+            arrays = dict(out) if host else {name: a[:n] for name, a in room.items()}
+            if set(arrays) != set(want):
+                raise ValueError("render_views_denoised: out must have exactly the keys %s" % sorted(want))
+            for name, shape, dtype in layout:
+                v = arrays[name]
+                if not (v.dtype == dtype and v.shape == shape and v.flags.c_contiguous):
+                    raise ValueError("render_views_denoised: out[%r] must be a C-contiguous %s %s array"
+                                     % (name, shape, np.dtype(dtype)))
+            for name, v in (arrays if host else room).items():
+                setattr(o, name, v.ctypes.data_as(types[name]))
+            code = self.lib.rptgpu_render_views_denoised(self.handle, n, arr, C.byref(q), seed_arr, C.byref(d), C.byref(o))
+            _abi.check(code, self.handle)
+            return arrays
+        import torch
+        dev = torch.device("cuda", self.device)
+        tdt = {np.uint8: torch.uint8, np.float64: torch.float64}
+        if isinstance(out, str):
+            if out != "torch":
+                raise ValueError('render_views_denoised: out must be None, "torch" or a dict of arrays or tensors')
+            room = {name: torch.empty((max(n, 1),) + shape[1:], dtype=tdt[dtype], device=dev) for name, shape, dtype in layout}
+            arrays = {name: t[:n] for name, t in room.items()}
+        else:
+            arrays = room = dict(out)
+            if set(arrays) != set(want):
+                raise ValueError("render_views_denoised: out must have exactly the keys %s" % sorted(want))
+            for name, shape, dtype in layout:
+                t = arrays[name]
+                if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == tdt[dtype] and tuple(t.shape) == shape
+                        and t.is_contiguous()):
+                    raise ValueError("render_views_denoised: out[%r] must be a contiguous %s %s tensor on %s"
+                                     % (name, shape, tdt[dtype], dev))
+        for name, t in room.items():
+            setattr(o, name, C.cast(C.c_void_p(t.data_ptr()), types[name]))
+        current = torch.cuda.current_stream(dev)  # (the null-stream rule of _trace_rays_torch)
+        stream = current.cuda_stream
+        if not stream:
+            current.synchronize()
+        code = self.lib.rptgpu_render_views_denoised_device(self.handle, n, arr, C.byref(q), seed_arr, C.byref(d), C.byref(o),
+                                                            C.c_void_p(stream or 0))
+        _abi.check(code, self.handle)
+        return arrays
+
     @staticmethod
     def _lower_seeds(seeds, n, seed_stride, who):
         """seeds=None -> None; else the n seeds as a ctypes uint64 array (at least one element: it has an address)"""

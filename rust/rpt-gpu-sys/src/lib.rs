@@ -492,6 +492,36 @@ pub mod ffi {
         pub fn rptgpu_render_views_aov_seeded(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, out: *const RptAovBuffers) -> c_int;
         pub fn rptgpu_render_views_aov_seeded_device(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, d_out: *const RptAovBuffers, stream: *mut c_void) -> c_int;
     }
+
+    // include/rpt_gpu_views_denoised.h: a denoised frame per view of a batch — optional additions within ABI 7 (a library
+    // without them is detected with dlsym("rptgpu_render_views_denoised"); this crate links them like the rest)
+    /// `RptViewDenoise` (the batches, features and filter of `rptgpu_render_views_denoised`)
+    #[repr(C)]
+    #[derive(Copy, Clone, Debug)]
+    pub struct RptViewDenoise {
+        pub struct_size: u32,
+        pub batches: u32,
+        pub feature_iterations: u32,
+        pub _pad: u32,
+        pub feature_sample_index_base: u64,
+        pub filter: RptDenoise,
+    }
+    /// `RptViewDenoiseOut` (the output arrays of `rptgpu_render_views_denoised`, host or device; any may be null, not both
+    /// `denoised` and `rgb8`)
+    #[repr(C)]
+    #[derive(Copy, Clone, Debug)]
+    pub struct RptViewDenoiseOut {
+        pub struct_size: u32,
+        pub _pad: u32,
+        pub denoised: *mut f64,
+        pub rgb8: *mut u8,
+        pub mean: *mut f64,
+        pub variance: *mut f64,
+    }
+    extern "C" {
+        pub fn rptgpu_render_views_denoised(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, d: *const RptViewDenoise, out: *const RptViewDenoiseOut) -> c_int;
+        pub fn rptgpu_render_views_denoised_device(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, d: *const RptViewDenoise, d_out: *const RptViewDenoiseOut, stream: *mut c_void) -> c_int;
+    }
 }
 
 pub use ffi::{RptCamera, RptMaterial, RptRenderParams, RptSceneOptions, RptStats, RptTransform, RptTriangle};
@@ -853,6 +883,8 @@ mod layout_tests {
         assert_eq!(size_of::<RptViewQuery>(), 64);
         assert_eq!(size_of::<RptHitQuery>(), 16);
         assert_eq!(size_of::<RptHitArrays>(), 48);
+        assert_eq!(size_of::<RptViewDenoise>(), 64);
+        assert_eq!(size_of::<RptViewDenoiseOut>(), 40);
     }
 
     #[test]
