@@ -331,6 +331,17 @@ void rptgpu_scene_destroy(rptgpu_scene* h) { delete h; }
 //   * the plane table (untransformed meshes only: `transformed` may not change), trees, leaf boxes of group children
 //     (in their group's frame: rptgpu_scene_set_group moves those, api_group.cpp), light_casts and num_shadow_lights (by kind: kinds may not change) — unchanged by
 //     construction.
+// ... and of what the entry points added since read that an update (these two, rptgpu_scene_set_mesh, _set_group) changes
+// (tests/test_gpu_update_matrix.py holds each to a fresh handle's bits after every kind of update):
+//   * rptgpu_occluded, rptgpu_bake_ao — insts through rpt_shadow_rays or the per-tree query; per call has_deep, tree_kids and
+//     gen_all choose between them; their one-column workspace request re-sizes a warm handle only through ws_stale;
+//   * rptgpu_first_hits, rptgpu_render_views_aov — the same route (query_by_object) and request; materials for the albedo;
+//   * rptgpu_render_views[_seeded] — insts, materials and lights through the wavefront kernels; rec_ratio, measured on the
+//     scene as it was, sizes the record pool (a pass that runs out starts over); view_recs, view_seeds and ray_seeds are
+//     written per call;
+//   * rptgpu_render_views_denoised — both of the above into vd_* arrays sized per call;
+//   * rptgpu_buffer_features, _denoise, _sample_adaptive — a Buffer renders through the handle as it is at the call: on a flat
+//     scene the path kernel with the filter's boxes, grid and obj_always above.
 } // extern "C"
 
 namespace {

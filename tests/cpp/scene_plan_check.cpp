@@ -3,6 +3,7 @@
 // the live updates' depth refusal carried before the planner existed (transcribed below over the same plain inputs), over
 // the enumerated boundaries of every rule, and pinned to a few literal layouts derived by hand from device_types.h.
 // Usage: scene_plan_check <section>; prints "ok <checks>" or one "FAIL" line per failed check (exit status 1).
+// scene_plan_check live <7 numbers> prints the route of one tree and its re-route after a live rebuild (see live() below).
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -616,8 +617,28 @@ static void literal() {
   CHECK(plane_users(7, [&](size_t i) { return pl.plane_use[i]; }) == 0x1f && cull_always(0x60 | 1ull << 9, 0x3, 7) == 0x63);
 }
 
+// ---- one live rebuild, for tests/test_update_cases_host.py: scene_plan_check live <kind> <depth> <regular> <deep_depth>
+// <fast_max_depth> <new depth> <new regular> prints the creation's route of such a tree under the default options with these
+// two depths (deep tris tree_kids gen_all), then what reroute_object makes of it after the rebuild (deep tris gen_all
+// tree_kids) and rebuilt_too_deep; a tree is one leaf where its depth is 0
+static int live(int argc, char** argv) {
+  if (argc != 9) { std::printf("FAIL live takes 7 numbers\n"); return 2; }
+  RptSceneOptions o = options();
+  ObjectFacts f;
+  f.kind = std::atoi(argv[2]); f.depth = (uint32_t)std::atoi(argv[3]); f.regular = std::atoi(argv[4]) != 0; f.root_leaf = f.depth == 0;
+  o.deep_depth = (uint32_t)std::atoi(argv[5]); o.fast_max_depth = (uint32_t)std::atoi(argv[6]);
+  const uint32_t depth = (uint32_t)std::atoi(argv[7]);
+  const bool regular = std::atoi(argv[8]) != 0;
+  const ObjectRoute r = route_object(f, o);
+  const Reroute n = reroute_object(r.deep, r.tris, regular, depth == 0, depth, o.fast_max_depth);
+  std::printf("ok %d %d %d %d %d %d %d %d %d\n", r.deep, r.tris, (int)r.tree_kids, (int)r.gen_all, n.deep, n.tris, (int)n.gen_all,
+              (int)n.tree_kids, (int)rebuilt_too_deep(r.deep, depth, o.fast_max_depth));
+  return 0;
+}
+
 int main(int argc, char** argv) {
   const char* s = argc > 1 ? argv[1] : "";
+  if (!std::strcmp(s, "live")) return live(argc, argv);
   if (!std::strcmp(s, "routing")) routing();
   else if (!std::strcmp(s, "rerouting")) rerouting();
   else if (!std::strcmp(s, "planes")) planes();
