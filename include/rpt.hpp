@@ -835,6 +835,50 @@ class Renderer {
     check(rptgpu_first_hits(handle_, n, origins.data(), dirs.data(), &q, &a));
     return r;
   }
+  // addition: the vertices of the paths trace_rays runs (rptgpu_trace_vertices, include/rpt_gpu_vertices.h): where each of a
+  // ray's num_samples paths bounced, what it picked up there and with which factors it went on.  With S = num_samples and
+  // V = max_bounces + 1: length [n][S]; per vertex [n][S][V] (x 3 for the vectors); rgb [n][3] = trace_rays' result.  Entries
+  // behind a path's last vertex are +0.0 (object -1, draw 0); a vector of a channel not named in `channels` (RPT_VERTEX_*)
+  // stays empty.  The header states the fold that turns radiance, bsdf, inv_pdf and abs_cos back into rgb.
+  struct Vertices {
+    std::vector<uint32_t> length, draw;
+    std::vector<int32_t> object;
+    std::vector<double> t, inv_pdf, abs_cos;                        // one per vertex
+    std::vector<double> normal, position, direction, radiance, bsdf; // xyz / rgb per vertex
+    std::vector<double> rgb;                                        // rgb per ray
+  };
+  Vertices trace_vertices(const std::vector<double>& origins, const std::vector<double>& dirs, uint32_t channels = 4095u,
+                          const std::vector<uint32_t>& streams = {}, uint32_t first_draw = 0, uint64_t sample_index_base = 0) {
+    ensure_scene();
+    const size_t n = origins.size() / 3;
+    if (origins.size() != 3 * n || dirs.size() != 3 * n || (!streams.empty() && streams.size() != n))
+      throw std::invalid_argument("trace_vertices: origins and dirs hold xyz per ray, streams one id per ray");
+    RptVertexQuery q{};
+    q.struct_size = sizeof(RptVertexQuery); q.max_bounces = max_bounces_; q.iterations = num_samples_; q.first_draw = first_draw;
+    q.exposure_value = ev_; q.seed = seed_; q.sample_index_base = sample_index_base; q.channels = channels;
+    Vertices r;
+    if (!n) return r; // (an empty vector has no address, and a named channel's pointer must not be NULL)
+    const size_t paths = n * (size_t)num_samples_, v = paths * ((size_t)max_bounces_ + 1);
+    if (channels & RPT_VERTEX_LENGTH) r.length.resize(paths);
+    if (channels & RPT_VERTEX_T) r.t.resize(v);
+    if (channels & RPT_VERTEX_NORMAL) r.normal.resize(3 * v);
+    if (channels & RPT_VERTEX_OBJECT) r.object.resize(v);
+    if (channels & RPT_VERTEX_POSITION) r.position.resize(3 * v);
+    if (channels & RPT_VERTEX_DIRECTION) r.direction.resize(3 * v);
+    if (channels & RPT_VERTEX_DRAW) r.draw.resize(v);
+    if (channels & RPT_VERTEX_RADIANCE) r.radiance.resize(3 * v);
+    if (channels & RPT_VERTEX_BSDF) r.bsdf.resize(3 * v);
+    if (channels & RPT_VERTEX_INV_PDF) r.inv_pdf.resize(v);
+    if (channels & RPT_VERTEX_ABS_COS) r.abs_cos.resize(v);
+    if (channels & RPT_VERTEX_RGB) r.rgb.resize(3 * n);
+    RptVertexArrays a{};
+    a.struct_size = sizeof(RptVertexArrays);
+    a.length = r.length.data(); a.t = r.t.data(); a.normal = r.normal.data(); a.object = r.object.data();
+    a.position = r.position.data(); a.direction = r.direction.data(); a.draw = r.draw.data(); a.radiance = r.radiance.data();
+    a.bsdf = r.bsdf.data(); a.inv_pdf = r.inv_pdf.data(); a.abs_cos = r.abs_cos.data(); a.rgb = r.rgb.data();
+    check(rptgpu_trace_vertices(handle_, n, origins.data(), dirs.data(), streams.empty() ? nullptr : streams.data(), &q, &a));
+    return r;
+  }
   // addition: render_aovs for a batch of views (rptgpu_render_views_aov, include/rpt_gpu.h): per (view, pixel) the sums over
   // the hits of num_samples rays — the rays render_views starts its paths with — and the hit count, [views][height][width]
   // (x 3); view v draws with seed + v * seed_stride.  A perspective view's buffers are render_aovs' of that camera.

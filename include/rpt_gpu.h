@@ -1025,6 +1025,8 @@ const char* rptgpu_kernel_name(int k);
 #include "rpt_gpu_views_seeded.h"
 /* ---- ... and a denoised frame per view of a batch ---- */
 #include "rpt_gpu_views_denoised.h"
+/* ---- ... and the vertices of the paths rptgpu_trace_rays runs ---- */
+#include "rpt_gpu_vertices.h"
 
 #ifdef __cplusplus
 }

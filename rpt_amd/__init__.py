@@ -11,7 +11,8 @@ or torch tensors on the device), and GpuScene.bake_probes turns positions into l
 surface irradiance — which sh9_basis / sh9_irradiance (numpy) evaluate; GpuScene.render_views renders a batch of frames in one
 call, each from a View: a camera under a perspective, orthographic or panoramic projection (a panorama is an Hdri's texels);
 GpuScene.occluded answers "is anything between here and there?" for the caller's rays with the shadow rays' own query, and
-GpuScene.bake_ao bakes ambient occlusion (and bent normals) from directions drawn on the device.
+GpuScene.bake_ao bakes ambient occlusion (and bent normals) from directions drawn on the device; GpuScene.trace_vertices gives
+the vertices of the paths trace_rays runs — where each bounced, what it picked up there and with what it went on.
 """
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401
@@ -19,10 +20,13 @@ from ._abi import (RPT_AOV_ALBEDO, RPT_AOV_ALL, RPT_AOV_DEPTH, RPT_AOV_NORMAL, R
                    RPT_AOV_POSITION, RPT_HIT_ALBEDO, RPT_HIT_ALL, RPT_HIT_NORMAL, RPT_HIT_OBJECT, RPT_HIT_POSITION, RPT_HIT_T,
                    RPT_PROBE_IRRADIANCE, RPT_PROBE_SH9, RPT_VIEW_ORTHOGRAPHIC, RPT_VIEW_PANORAMA,
                    RPT_VIEW_PERSPECTIVE)
+from ._abi import (RPT_VERTEX_ABS_COS, RPT_VERTEX_ALL, RPT_VERTEX_BSDF, RPT_VERTEX_DIRECTION, RPT_VERTEX_DRAW,  # noqa: F401
+                   RPT_VERTEX_INV_PDF, RPT_VERTEX_LENGTH, RPT_VERTEX_NORMAL, RPT_VERTEX_OBJECT, RPT_VERTEX_POSITION,
+                   RPT_VERTEX_RADIANCE, RPT_VERTEX_RGB, RPT_VERTEX_T)
 from .buffer import Buffer, Filter  # noqa: F401
 from .camera import Camera, View  # noqa: F401
 from .color import color_bytes, hex_color  # noqa: F401
-from .device import DeviceBuffer, GpuScene, device_count, make_params  # noqa: F401
+from .device import DeviceBuffer, GpuScene, PathVertices, device_count, make_params  # noqa: F401
 from .environment import Environment, Hdri  # noqa: F401
 from .io import load_mtl, load_obj, load_obj_with_mtl, load_stl  # noqa: F401
 from .light import Light  # noqa: F401

@@ -46,6 +46,9 @@ RPT_PROBE_SH9, RPT_PROBE_IRRADIANCE = 0, 1
 RPT_VIEW_PERSPECTIVE, RPT_VIEW_ORTHOGRAPHIC, RPT_VIEW_PANORAMA = 0, 1, 2
 RPT_HIT_T, RPT_HIT_NORMAL, RPT_HIT_OBJECT, RPT_HIT_POSITION, RPT_HIT_ALBEDO = 1, 2, 4, 8, 16
 RPT_HIT_ALL = 31
+(RPT_VERTEX_LENGTH, RPT_VERTEX_T, RPT_VERTEX_NORMAL, RPT_VERTEX_OBJECT, RPT_VERTEX_POSITION, RPT_VERTEX_DIRECTION, RPT_VERTEX_DRAW,
+ RPT_VERTEX_RADIANCE, RPT_VERTEX_BSDF, RPT_VERTEX_INV_PDF, RPT_VERTEX_ABS_COS, RPT_VERTEX_RGB) = (1 << k for k in range(12))
+RPT_VERTEX_ALL = 4095
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -227,6 +230,22 @@ class RptHitArrays(C.Structure):
                 ("object", C.POINTER(C.c_int32)), ("position", C.POINTER(f64)), ("albedo", C.POINTER(f64))]
 
 
+class RptVertexQuery(C.Structure):
+    """include/rpt_gpu_vertices.h RptVertexQuery (rptgpu_trace_vertices' parameters: RptRayQuery's and the channels)."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_bounces", C.c_uint32), ("iterations", C.c_uint32),
+                ("first_draw", C.c_uint32), ("exposure_value", f64), ("seed", C.c_uint64),
+                ("sample_index_base", C.c_uint64), ("precision_mode", C.c_uint32), ("flags", C.c_uint32),
+                ("channels", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RptVertexArrays(C.Structure):
+    """include/rpt_gpu_vertices.h RptVertexArrays (rptgpu_trace_vertices' output arrays, host or device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("length", C.POINTER(C.c_uint32)), ("t", C.POINTER(f64)),
+                ("normal", C.POINTER(f64)), ("object", C.POINTER(C.c_int32)), ("position", C.POINTER(f64)),
+                ("direction", C.POINTER(f64)), ("draw", C.POINTER(C.c_uint32)), ("radiance", C.POINTER(f64)),
+                ("bsdf", C.POINTER(f64)), ("inv_pdf", C.POINTER(f64)), ("abs_cos", C.POINTER(f64)), ("rgb", C.POINTER(f64))]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -324,6 +343,13 @@ DENOISED_SYMBOLS = [
      [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.POINTER(C.c_uint64), C.POINTER(RptViewDenoise),
       C.POINTER(RptViewDenoiseOut), _VP]),
 ]
+# ... and every symbol include/rpt_gpu_vertices.h declares, optional in the same way
+VERTICES_SYMBOLS = [
+    ("rptgpu_trace_vertices", C.c_int,
+     [_VP, C.c_uint64, _PD, _PD, C.POINTER(C.c_uint32), C.POINTER(RptVertexQuery), C.POINTER(RptVertexArrays)]),
+    ("rptgpu_trace_vertices_device", C.c_int,
+     [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptVertexQuery), C.POINTER(RptVertexArrays), _VP]),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -348,7 +374,7 @@ def load_library(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % p)
     lib = C.CDLL(p)
-    for name, restype, argtypes in SYMBOLS + SEEDED_SYMBOLS + DENOISED_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + SEEDED_SYMBOLS + DENOISED_SYMBOLS + VERTICES_SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes

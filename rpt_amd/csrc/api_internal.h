@@ -26,6 +26,8 @@
 //   api_hits.cpp     rptgpu_first_hits[_device], rptgpu_render_views_aov[_seeded][_device]: the first hit's record for the caller's rays
 //                    (one fused kernel, or the per-tree closest-hit query, in pieces) and rptgpu_render_aov's sums for
 //                    every view of a batch (raygen, closest-hit query and fold in passes over render_views' pieces)
+//   api_vertices.cpp rptgpu_trace_vertices[_device]: api_rays.cpp's pieces with a vertex sink in their RaySource — run_pass then
+//                    also carries every path's vertices into the caller's arrays (kernels/wf_vertices.inc)
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -188,7 +190,8 @@ struct rptgpu_scene {
                                        // stages a piece of probes in the same four (api_probes.cpp)
   DevBuf<uint8_t> occ_out;             // rptgpu_occluded: a piece of a host caller's answers (api_occlusion.cpp)
   DevBuf<double> hits_out;             // rptgpu_first_hits: a piece of a host caller's records, the named channels back to back (api_hits.cpp)
-  DevBuf<rptdev::View> view_recs;      // rptgpu_render_views: the call's views (api_views.cpp)
+  DevBuf<double> vertices_out;         // rptgpu_trace_vertices: a piece of a host caller's records, the named channels back to back (api_vertices.cpp)
+  DevBuf<rptdev::View> view_recs;     // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<uint64_t> view_seeds;         // ... their seeds, when the views have seeds of their own,
   DevBuf<uint64_t> ray_seeds;          // ... and then the seed of each index of a piece, beside ray_ids
   // rptgpu_render_views_denoised's working set over the batch's n_views * width * height indices (api_views_denoise.cpp;
@@ -382,6 +385,9 @@ struct RaySource {
   // piece's Frame::seed is not read then.  nullptr: every view's seed is the Frame's
   const uint64_t* view_seeds = nullptr;
   uint64_t* seeds_out = nullptr;
+  // rptgpu_trace_vertices (api_vertices.cpp): where the vertices of the piece's paths go — the caller's arrays or their
+  // staging, offset to the piece; run_pass fills in s_first per pass.  nullptr (every other call): nothing is launched for it
+  const rptdev::VertexOut* vertices = nullptr;
 };
 // api_views.cpp: what is wrong with an RptViewQuery / with one view of a call with query q (nullptr: nothing); shared with
 // rptgpu_render_views_aov (api_hits.cpp)

@@ -412,6 +412,11 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
   HIP_TRY(hipMemsetAsync(h->counters.p, 0, 2 * (size_t)nctr * sizeof(uint32_t), st));
   uint32_t cset = 0;
   if (h->has_deep) reset_tree_counters(h);
+  rptdev::VertexOut vertices{}; // (rptgpu_trace_vertices only) the sink with this pass's first sample, counted from the call's
+  if (src.vertices) {
+    vertices = *src.vertices;
+    vertices.s_first = (uint32_t)(fr.sample_base - p.sample_index_base);
+  }
   if (src.views && src.view_seeds) {
     // one launch for every view the piece holds: the raygen count of RptStats stays at least the number of views rendered
     // under seeds of their own, as it was when such a view was a piece — the depth loop behind it is the piece's, shared
@@ -450,6 +455,9 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
       else
         kt->extend(st, h->dscene, ps, queue, n_active);
       b.done(); }
+    // rptgpu_trace_vertices: the depth's hits and rays into the caller's arrays while the rays still are the ones the query
+    // ran for (rpt_shade puts the hit position where the origin is).  A pass that starts over writes the same entries again
+    if (src.vertices) kt->vertices_store(st, fr, ps, n_active, depth, vertices);
     h->stats.extend_rays += n_active;
     uint32_t* const ctrs = h->counters.p + (size_t)cset * nctr;       // this depth's counters (cleared by the depth before)
     uint32_t* const ctrs_next = h->counters.p + (size_t)(cset ^ 1u) * nctr;
@@ -501,6 +509,8 @@ bool run_pass(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, 
       std::swap(ps.ray, ps.ray_next); std::swap(ps.draw, ps.draw_next); std::swap(ps.pid, ps.pid_next); std::swap(ps.col, ps.col_next);
     }
   }
+  // ... and, now that every path of the pass has ended (last_col is final), what the records hold of each and the filler
+  if (src.vertices) kt->vertices_fold(st, fr, ps, n_paths, vertices);
   { Bracket b(h, RPT_K_RESOLVE, prof);
     if (src.probe >= 0) kt->resolve_probes(st, fr, ps, spp, (uint32_t)src.probe);
     else kt->resolve(st, fr, ps, spp);

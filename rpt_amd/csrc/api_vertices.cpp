@@ -1,0 +1,225 @@
+// api_vertices.cpp — rptgpu_trace_vertices[_device]: the vertices of the paths rptgpu_trace_rays runs (include/
+// rpt_gpu_vertices.h; see api_internal.h).  The call IS api_rays.cpp's — the same pieces through the same
+// driver, the same rpt_raygen_rays, depth loop, restarts, rpt_resolve and rpt_finish — with one thing more in the piece's
+// RaySource: the vertex sink.  run_pass (api_render.cpp) then launches rpt_vertices_store behind every depth's closest-hit
+// query and rpt_vertices_fold at the end of every pass that resolved (kernels/wf_vertices.inc); the filler behind the paths'
+// last vertices is laid down here, per piece, before its passes.  A host caller's records are
+// staged piece by piece in an array the handle keeps (rptplan::vertices_piece bounds it); a device caller's are written where
+// they lie.
+#include "api_internal.h"
+
+namespace rptapi {
+namespace {
+
+constexpr uint32_t VERTEX_ALL = RPT_VERTEX_LENGTH | RPT_VERTEX_T | RPT_VERTEX_NORMAL | RPT_VERTEX_OBJECT | RPT_VERTEX_POSITION |
+                                RPT_VERTEX_DIRECTION | RPT_VERTEX_DRAW | RPT_VERTEX_RADIANCE | RPT_VERTEX_BSDF |
+                                RPT_VERTEX_INV_PDF | RPT_VERTEX_ABS_COS | RPT_VERTEX_RGB;
+// render_plan.h counts a vertex's bytes by bit position
+static_assert(RPT_VERTEX_LENGTH == 1u << 0 && RPT_VERTEX_T == 1u << 1 && RPT_VERTEX_NORMAL == 1u << 2 && RPT_VERTEX_OBJECT == 1u << 3 &&
+              RPT_VERTEX_POSITION == 1u << 4 && RPT_VERTEX_DIRECTION == 1u << 5 && RPT_VERTEX_DRAW == 1u << 6 &&
+              RPT_VERTEX_RADIANCE == 1u << 7 && RPT_VERTEX_BSDF == 1u << 8 && RPT_VERTEX_INV_PDF == 1u << 9 &&
+              RPT_VERTEX_ABS_COS == 1u << 10 && RPT_VERTEX_RGB == 1u << 11 && VERTEX_ALL == (1u << rptplan::VERTICES_CHANNEL_BITS) - 1u,
+              "rptplan::VERTICES_VERTEX_BYTES is indexed by the RPT_VERTEX_* bit positions");
+static_assert(rptplan::vertices_vertex_bytes(VERTEX_ALL) == 152 && rptplan::vertices_path_bytes(VERTEX_ALL) == 4, "a vertex with every channel");
+
+// what is wrong with an RptVertexQuery / with the RptVertexArrays of a call that names `channels` (nullptr: nothing)
+const char* bad_vertex_query(const RptVertexQuery* q) {
+  if (!q) return "null RptVertexQuery";
+  if (q->struct_size != sizeof(RptVertexQuery)) return "RptVertexQuery: struct_size is not sizeof(RptVertexQuery)";
+  if (!q->iterations) return "RptVertexQuery: iterations == 0";
+  if (q->max_bounces > 254) return "RptVertexQuery: max_bounces > 254";
+  if (q->precision_mode != RPT_PRECISION_F64_STRICT) return BAD_MODE;
+  if (q->flags & RPT_FLAG_PERSISTENT)
+    return "RptVertexQuery: RPT_FLAG_PERSISTENT — the persistent kernel keeps a path in registers and leaves no vertices behind; "
+           "path vertices run the wavefront pipeline only";
+  if (!q->channels) return "RptVertexQuery: channels == 0 (name at least one RPT_VERTEX_* channel)";
+  if (q->channels & ~VERTEX_ALL) return "RptVertexQuery: channels names an unknown RPT_VERTEX_* bit";
+  if (q->reserved) return "RptVertexQuery: reserved != 0";
+  return nullptr;
+}
+const char* bad_vertex_arrays(const RptVertexArrays* o, uint32_t ch) {
+  if (!o) return "null RptVertexArrays";
+  if (o->struct_size != sizeof(RptVertexArrays)) return "RptVertexArrays: struct_size is not sizeof(RptVertexArrays)";
+  if (o->reserved) return "RptVertexArrays: reserved != 0";
+  if ((ch & RPT_VERTEX_LENGTH) && !o->length) return "RptVertexArrays: RPT_VERTEX_LENGTH is named but length is NULL";
+  if ((ch & RPT_VERTEX_T) && !o->t) return "RptVertexArrays: RPT_VERTEX_T is named but t is NULL";
+  if ((ch & RPT_VERTEX_NORMAL) && !o->normal) return "RptVertexArrays: RPT_VERTEX_NORMAL is named but normal is NULL";
+  if ((ch & RPT_VERTEX_OBJECT) && !o->object) return "RptVertexArrays: RPT_VERTEX_OBJECT is named but object is NULL";
+  if ((ch & RPT_VERTEX_POSITION) && !o->position) return "RptVertexArrays: RPT_VERTEX_POSITION is named but position is NULL";
+  if ((ch & RPT_VERTEX_DIRECTION) && !o->direction) return "RptVertexArrays: RPT_VERTEX_DIRECTION is named but direction is NULL";
+  if ((ch & RPT_VERTEX_DRAW) && !o->draw) return "RptVertexArrays: RPT_VERTEX_DRAW is named but draw is NULL";
+  if ((ch & RPT_VERTEX_RADIANCE) && !o->radiance) return "RptVertexArrays: RPT_VERTEX_RADIANCE is named but radiance is NULL";
+  if ((ch & RPT_VERTEX_BSDF) && !o->bsdf) return "RptVertexArrays: RPT_VERTEX_BSDF is named but bsdf is NULL";
+  if ((ch & RPT_VERTEX_INV_PDF) && !o->inv_pdf) return "RptVertexArrays: RPT_VERTEX_INV_PDF is named but inv_pdf is NULL";
+  if ((ch & RPT_VERTEX_ABS_COS) && !o->abs_cos) return "RptVertexArrays: RPT_VERTEX_ABS_COS is named but abs_cos is NULL";
+  if ((ch & RPT_VERTEX_RGB) && !o->rgb) return "RptVertexArrays: RPT_VERTEX_RGB is named but rgb is NULL";
+  return nullptr;
+}
+
+// The per-vertex and per-path channels in the order of both structs' pointers — length, t, normal, object, position,
+// direction, draw, radiance, bsdf, inv_pdf, abs_cos —: elements per vertex (or path) and bytes per element.  The three places
+// that walk the channels — the caller's arrays offset to a piece, the staging layout, the copy out — walk this table
+struct Row { uint32_t bit, width, elem; bool per_path; };
+constexpr int N_ROWS = 11;
+constexpr Row ROWS[N_ROWS] = {{RPT_VERTEX_LENGTH, 1, 4, true},   {RPT_VERTEX_T, 1, 8, false},        {RPT_VERTEX_NORMAL, 3, 8, false},
+                              {RPT_VERTEX_OBJECT, 1, 4, false},  {RPT_VERTEX_POSITION, 3, 8, false}, {RPT_VERTEX_DIRECTION, 3, 8, false},
+                              {RPT_VERTEX_DRAW, 1, 4, false},    {RPT_VERTEX_RADIANCE, 3, 8, false}, {RPT_VERTEX_BSDF, 3, 8, false},
+                              {RPT_VERTEX_INV_PDF, 1, 8, false}, {RPT_VERTEX_ABS_COS, 1, 8, false}};
+struct Ptrs { char* p[N_ROWS]; };
+Ptrs ptrs_of(const RptVertexArrays& a, uint32_t ch) { // (only the named channels' members are read)
+  Ptrs p{};
+  if (ch & RPT_VERTEX_LENGTH) p.p[0] = (char*)a.length;
+  if (ch & RPT_VERTEX_T) p.p[1] = (char*)a.t;
+  if (ch & RPT_VERTEX_NORMAL) p.p[2] = (char*)a.normal;
+  if (ch & RPT_VERTEX_OBJECT) p.p[3] = (char*)a.object;
+  if (ch & RPT_VERTEX_POSITION) p.p[4] = (char*)a.position;
+  if (ch & RPT_VERTEX_DIRECTION) p.p[5] = (char*)a.direction;
+  if (ch & RPT_VERTEX_DRAW) p.p[6] = (char*)a.draw;
+  if (ch & RPT_VERTEX_RADIANCE) p.p[7] = (char*)a.radiance;
+  if (ch & RPT_VERTEX_BSDF) p.p[8] = (char*)a.bsdf;
+  if (ch & RPT_VERTEX_INV_PDF) p.p[9] = (char*)a.inv_pdf;
+  if (ch & RPT_VERTEX_ABS_COS) p.p[10] = (char*)a.abs_cos;
+  return p;
+}
+rptdev::VertexOut sink_of(const Ptrs& p, const RptVertexQuery& q) {
+  rptdev::VertexOut vo{};
+  vo.length = (uint32_t*)p.p[0]; vo.t = (double*)p.p[1]; vo.normal = (double*)p.p[2]; vo.object = (int32_t*)p.p[3];
+  vo.position = (double*)p.p[4]; vo.direction = (double*)p.p[5]; vo.draw = (uint32_t*)p.p[6]; vo.radiance = (double*)p.p[7];
+  vo.bsdf = (double*)p.p[8]; vo.inv_pdf = (double*)p.p[9]; vo.abs_cos = (double*)p.p[10];
+  vo.channels = q.channels; vo.iterations = q.iterations; vo.stride = q.max_bounces + 1u;
+  return vo;
+}
+// bytes of channel k for `rays` rays of a call with `iterations` samples and `stride` vertices per path
+uint64_t channel_bytes(int k, uint64_t rays, uint32_t iterations, uint32_t stride) {
+  return rays * iterations * (ROWS[k].per_path ? 1u : stride) * ROWS[k].width * ROWS[k].elem;
+}
+
+// the caller's arrays of the named channels from ray `base` on (a channel that is not named: its pointer is not read)
+Ptrs vertex_arrays_at(const RptVertexArrays& a, const RptVertexQuery& q, uint64_t base) {
+  const Ptrs all = ptrs_of(a, q.channels);
+  Ptrs at{};
+  for (int k = 0; k < N_ROWS; k++)
+    if (q.channels & ROWS[k].bit) at.p[k] = all.p[k] + channel_bytes(k, base, q.iterations, q.max_bounces + 1u);
+  return at;
+}
+// a host caller's piece of records on the device: the named channels of `piece` rays back to back inside `arrays`, each
+// 16-byte aligned
+Ptrs vertex_staging(DevBuf<double>& arrays, const RptVertexQuery& q, uint64_t piece) {
+  uint64_t off[N_ROWS] = {0}, total = 0; // in doubles
+  for (int k = 0; k < N_ROWS; k++)
+    if (q.channels & ROWS[k].bit) { off[k] = total; total += (channel_bytes(k, piece, q.iterations, q.max_bounces + 1u) + 15) / 16 * 2; }
+  arrays.alloc(total);
+  Ptrs at{};
+  for (int k = 0; k < N_ROWS; k++)
+    if (q.channels & ROWS[k].bit) at.p[k] = (char*)(arrays.p + off[k]);
+  return at;
+}
+
+// on_device: origins, dirs, streams and out's arrays are device pointers (user_stream: the stream their producer ran on)
+int trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const double* dirs, const uint32_t* streams,
+                   const RptVertexQuery* q, const RptVertexArrays* out, bool on_device, hipStream_t user_stream) {
+  // (the query first, then the arrays: both are refused whatever else is wrong, also without a handle or a device)
+  if (const char* why = bad_vertex_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (const char* why = bad_vertex_arrays(out, q->channels)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (n && (!origins || !dirs)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
+  if (!streams && n > (1ull << 32))
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "more than 2^32 rays without stream ids (a stream id has 32 bits)");
+  if (!rptplan::vertices_fit(n, q->iterations, q->max_bounces))
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, "n * iterations * (max_bounces + 1) does not fit: 2^56 vertices or more would not fit any memory");
+  if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
+  REFUSE_IF_ABANDONED(h);
+  if (!n) return RPTGPU_OK;
+  auto t0 = std::chrono::steady_clock::now();
+  const int rc = guarded(h, h->device, [&]() -> int {
+    struct EventPairs { // (as render_impl: a call leaves no event pair behind, however it ends)
+      rptgpu_scene* h;
+      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
+    } event_pairs{h};
+    (void)hipGetLastError();
+    hipStream_t st = h->stream;
+    const KernelTable* kt = table_for(q->precision_mode, h->ext_shapes);
+    const bool prof = (q->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
+    const uint32_t ch = q->channels, stride = q->max_bounces + 1u;
+    const bool want_rgb = (ch & RPT_VERTEX_RGB) != 0;
+    if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
+    h->dscene.force_general = (q->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
+    RptRenderParams p{}; // what render_wavefront reads of it
+    p.max_bounces = q->max_bounces; p.iterations = q->iterations; p.exposure_value = q->exposure_value;
+    p.seed = q->seed; p.sample_index_base = q->sample_index_base; p.precision_mode = q->precision_mode; p.flags = q->flags;
+    // the piece: rptgpu_trace_rays' (at most the paths one pass may hold with every level of every path), and for a host
+    // caller what the staging of the named channels allows (rptplan::vertices_piece)
+    rptplan::PassInput in = pass_input(h, 1, q->iterations);
+    in.remaining = q->iterations;
+    in.ratio = (double)q->max_bounces + 1.0;
+    pass_input_now(h, in);
+    uint64_t asked = 0; // tests: pieces of a few rays
+    if (const char* e = std::getenv("RPTGPU_VERTICES_PIECE")) asked = std::strtoull(e, nullptr, 10);
+    const uint64_t piece = rptplan::vertices_piece(n, asked, rptplan::plan_pass(in).target, !on_device, q->iterations, q->max_bounces, ch);
+    h->accum.alloc(3 * piece);
+    // rpt_finish writes a piece's means somewhere: the caller's rgb, or (a host caller, or RGB not named) the handle's array
+    if (!on_device || !want_rgb) h->rays_out.alloc(3 * piece);
+    if (!on_device) { h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece); }
+    if (!on_device || !streams) h->ray_ids.alloc(piece);
+    Ptrs stage{};
+    if (!on_device) stage = vertex_staging(h->vertices_out, *q, piece);
+    for (uint64_t base = 0; base < n; base += piece) {
+      const uint64_t m = std::min(piece, n - base);
+      const double *d_o = origins + 3 * base, *d_d = dirs + 3 * base;
+      const uint32_t* d_ids = streams ? streams + base : h->ray_ids.p;
+      double* d_rgb = on_device && want_rgb ? out->rgb + 3 * base : h->rays_out.p;
+      const Ptrs mine = vertex_arrays_at(*out, *q, base);
+      if (!on_device) {
+        HIP_TRY(hipMemcpyAsync(h->rays_o.p, d_o, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_d, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
+        if (streams) HIP_TRY(hipMemcpyAsync(h->ray_ids.p, d_ids, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        d_o = h->rays_o.p; d_d = h->rays_d.p; d_ids = h->ray_ids.p;
+      }
+      const Ptrs& where = on_device ? mine : stage;
+      const rptdev::VertexOut sink = sink_of(where, *q);
+      // the filler — +0.0, OBJECT -1, DRAW 0 — over the piece's entries of every named per-vertex channel, in front of the
+      // piece's first pass: the kernels write d < len only, so behind a path's last vertex this is what stays.  (Streaming
+      // fills instead of 8- to 24-byte stores a path's stride apart: RPT_VERTICES_FILL_IN_KERNEL=1 builds that form.)
+#if !RPT_VERTICES_FILL_IN_KERNEL
+      for (int k = 0; k < N_ROWS; k++)
+        if ((ch & ROWS[k].bit) && !ROWS[k].per_path)
+          HIP_TRY(hipMemsetAsync(where.p[k], ROWS[k].bit == RPT_VERTEX_OBJECT ? 0xff : 0, channel_bytes(k, m, q->iterations, stride), st));
+#endif
+      rptdev::Frame fr{};
+      fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = d_ids;
+      fr.max_bounces = q->max_bounces; fr.seed = q->seed; fr.accum = h->accum.p;
+      RaySource src{nullptr, d_o, d_d, q->first_draw, (uint32_t)base, streams ? nullptr : h->ray_ids.p};
+      src.vertices = &sink;
+      render_wavefront(h, kt, p, fr, src, d_rgb, false, true, prof);
+      HIP_TRY(hipGetLastError());
+      if (!on_device) { // the staging arrays are the next piece's, too
+        for (int k = 0; k < N_ROWS; k++)
+          if (ch & ROWS[k].bit)
+            HIP_TRY(hipMemcpyAsync(mine.p[k], stage.p[k], channel_bytes(k, m, q->iterations, stride), hipMemcpyDeviceToHost, st));
+        if (want_rgb) HIP_TRY(hipMemcpyAsync(out->rgb + 3 * base, d_rgb, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+      }
+    }
+    return drain_call(h, h->has_deep && h->gen_overflow.p);
+  });
+  if (rc != RPTGPU_OK) return rc;
+  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return RPTGPU_OK;
+}
+
+} // namespace
+} // namespace rptapi
+
+extern "C" {
+
+int rptgpu_trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const double* dirs, const uint32_t* streams,
+                          const RptVertexQuery* q, const RptVertexArrays* out) {
+  return trace_vertices(h, n, origins, dirs, streams, q, out, false, nullptr);
+}
+
+int rptgpu_trace_vertices_device(rptgpu_scene* h, uint64_t n, const void* d_origins, const void* d_dirs, const void* d_streams,
+                                 const RptVertexQuery* q, const RptVertexArrays* d_out, void* stream) {
+  return trace_vertices(h, n, (const double*)d_origins, (const double*)d_dirs, (const uint32_t*)d_streams, q, d_out, true,
+                        (hipStream_t)stream);
+}
+
+} // extern "C"

@@ -230,6 +230,28 @@ struct HitOut {
   uint32_t channels;
 };
 
+// rptgpu_trace_vertices' device outputs (kernels/wf_vertices.inc): the arrays of RptVertexArrays, offset to the piece.  Path
+// (p, s) — ray p of the piece, sample s of the call — has its length at [p * iterations + s] and vertex d at
+// [(p * iterations + s) * stride + d] (x 3 for the vector channels).  Only the arrays of the channels named in `channels`
+// (RPT_VERTEX_*) exist.
+struct VertexOut {
+  uint32_t* length;
+  double* t;
+  double* normal;
+  int32_t* object;
+  double* position;
+  double* direction;
+  uint32_t* draw;
+  double* radiance;
+  double* bsdf;
+  double* inv_pdf;
+  double* abs_cos;
+  uint32_t channels;
+  uint32_t iterations; // samples per ray of the call
+  uint32_t stride;     // max_bounces + 1: the vertices an array holds per path
+  uint32_t s_first;    // the pass's first sample, counted from the call's
+};
+
 // rptgpu_buffer_denoise's working set (kernels/denoise.inc): f64 COLUMNS of `stride` elements indexed by pixel, so that
 // the 64 lanes of a wave (64 consecutive x of one row) read a tap's value as one contiguous segment at any tap spacing.
 // Constant over the levels: the means of the held features and the hit flag.  Per level: colour and variance in, out.

@@ -32,6 +32,13 @@
 #define RPT_PATH_REORDER_MIN (1u << 20)
 #endif
 
+// RPT_VERTICES_FILL_IN_KERNEL=1: rpt_vertices_fold also writes the filler behind a path's last vertex, entry by entry, and the
+// host lays none down (A/B builds: the first form of rptgpu_trace_vertices, DESIGN.md §19 has its numbers); 0: the host fills a
+// piece's arrays with streaming fills before its first pass (api_vertices.cpp)
+#ifndef RPT_VERTICES_FILL_IN_KERNEL
+#define RPT_VERTICES_FILL_IN_KERNEL 0
+#endif
+
 // the adaptive buffer's retire-and-compact kernels (kernels/buffer.inc): active-list entries per thread and per 256-thread
 // block (the host sizes the per-block counts with it)
 #define RPT_RETIRE_ITEMS 16u
@@ -238,6 +245,13 @@ struct KernelTable {
   void (*denoise_views_finish)(hipStream_t, const double* c_in, uint64_t stride, uint64_t n, const double* thr, double* out_linear,
                                uint8_t* out_rgb8, const double* total, const uint32_t* counts, const double* m2, double* out_mean,
                                double* out_variance);
+  // path vertices for the caller (rptgpu_trace_vertices; kernels/wf_vertices.inc), beside raygen_rays' passes.  vertices_store:
+  // the geometry and stream position of the n paths of depth `depth` (dense slots, behind the closest-hit query, in front of
+  // shade) into out's arrays at (ray, sample, depth).  vertices_fold: at the end of a pass of n_paths paths, every path's
+  // record chain — radiance, BSDF, 1/pdf, |cos|, the length — and the filler behind its last vertex
+  void (*vertices_store)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, uint32_t n, uint32_t depth,
+                         const rptdev::VertexOut& out);
+  void (*vertices_fold)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, uint32_t n_paths, const rptdev::VertexOut& out);
 };
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)

@@ -37,6 +37,8 @@
 //                  (rpt_occ_load, rpt_raygen_ao, rpt_occ_store, rpt_ao_fold), DESIGN.md §16
 //   hits.inc       rptgpu_first_hits / rptgpu_render_views_aov: the closest-hit record into the caller's layout (rpt_first_hits
 //                  fused, rpt_hits_store behind the per-tree query, rpt_views_aov_fold), DESIGN.md §17
+//   wf_vertices.inc rptgpu_trace_vertices: the vertices of a wavefront pass's paths into the caller's layout (rpt_vertices_store per
+//                  depth, rpt_vertices_fold at the end of the pass), DESIGN.md §19
 //   launch.inc     explicit instantiations, host-side launchers, the KernelTable the api_*.cpp files call through
 //
 // Wave64 throughout (gfx950): queue appends and work fetches use one 64-bit ballot + one atomic per wave.
@@ -119,6 +121,7 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #undef RPT_DN_VIEWS
 #include "kernels/occlusion.inc"
 #include "kernels/hits.inc"
+#include "kernels/wf_vertices.inc"
 #include "kernels/launch.inc"
 
 } // namespace RPT_NS

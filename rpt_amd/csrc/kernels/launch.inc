@@ -333,6 +333,14 @@ void launch_views_aov_fold(hipStream_t st, const Scene& sc, const PathState& ps,
   hipLaunchKernelGGL(rpt_views_aov_fold, grid_for(n), dim3(256), 0, st, sc, ps, out, n, spp, first ? 1 : 0);
 }
 
+// rptgpu_trace_vertices (kernels/wf_vertices.inc): a pass's vertices into the caller's layout
+void launch_vertices_store(hipStream_t st, const Frame& fr, const PathState& ps, uint32_t n, uint32_t depth, const VertexOut& out) {
+  hipLaunchKernelGGL(rpt_vertices_store, grid_for(n), dim3(256), 0, st, fr, ps, n, depth, out);
+}
+void launch_vertices_fold(hipStream_t st, const Frame& fr, const PathState& ps, uint32_t n_paths, const VertexOut& out) {
+  hipLaunchKernelGGL(rpt_vertices_fold, grid_for(n_paths), dim3(256), 0, st, fr, ps, n_paths, out);
+}
+
 // blocks of 64 x 4 pixels: a wave is 64 consecutive x of one row (kernels/denoise.inc)
 static inline dim3 grid_rows(uint32_t w, uint32_t h) { return dim3((w + 63u) / 64u, (h + 3u) / 4u); }
 void launch_denoise_prepare(hipStream_t st, const double* total, const uint32_t* counts, const double* m2, const AovOut& feat,
@@ -401,5 +409,6 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_occ_load, launch_raygen_ao, launch_occ_store, launch_ao_fold,
                            launch_first_hits, launch_hits_store, launch_views_aov_fold,
                            launch_raygen_views_seeded, launch_shade_seeded,
-                           launch_denoise_views_prepare, launch_denoise_views_level, launch_denoise_views_finish};
+                           launch_denoise_views_prepare, launch_denoise_views_level, launch_denoise_views_finish,
+                           launch_vertices_store, launch_vertices_fold};
 #endif // !__HIP_DEVICE_COMPILE__

@@ -239,6 +239,45 @@ inline uint64_t hits_piece(uint64_t n, uint64_t asked, uint64_t pass_bound) {
   return std::max<uint64_t>(1, std::min(std::min<uint64_t>(n, asked ? asked : fit), fit));
 }
 
+// ---- rptgpu_trace_vertices: rptgpu_trace_rays' pieces (rays_piece's bound and default hold as they stand; asked:
+// RPTGPU_VERTICES_PIECE) — and for a host caller, whose records are staged on the device piece by piece, also at most the rays
+// whose named channels fit VERTICES_STAGING_MAX bytes: piece x iterations x (max_bounces + 1) x vertices_vertex_bytes, plus
+// vertices_path_bytes per path.  A piece is never empty: one ray whose records alone exceed the cap is still a piece.
+// The cap's value is a CHOICE nobody has measured: 1 GiB is 7 M vertices with every channel, large enough that a piece's
+// passes have the paths to fill the device and small against its memory.
+constexpr uint64_t VERTICES_STAGING_MAX = 1ull << 30;
+// bytes per vertex / per path of the channels named in `channels`, by the bit positions of RPT_VERTEX_* (include/
+// rpt_gpu_vertices.h; api_vertices.cpp holds the two to each other): LENGTH is per path, RGB per ray (rays_piece's 24 B)
+constexpr uint32_t VERTICES_CHANNEL_BITS = 12;
+constexpr uint32_t VERTICES_VERTEX_BYTES[VERTICES_CHANNEL_BITS] = {0, 8, 24, 4, 24, 24, 4, 24, 24, 8, 8, 0};
+constexpr uint64_t vertices_vertex_bytes(uint32_t channels) {
+  uint64_t b = 0;
+  for (uint32_t k = 0; k < VERTICES_CHANNEL_BITS; k++)
+    if (channels >> k & 1u) b += VERTICES_VERTEX_BYTES[k];
+  return b;
+}
+constexpr uint64_t vertices_path_bytes(uint32_t channels) { return (channels & 1u) ? 4u : 0u; }
+// the staged bytes of `rays` rays (saturating: a product that does not fit is more than any cap)
+inline uint64_t vertices_staging_bytes(uint64_t rays, uint32_t iterations, uint32_t max_bounces, uint32_t channels) {
+  const uint64_t per_ray = (uint64_t)iterations * (((uint64_t)max_bounces + 1) * vertices_vertex_bytes(channels) + vertices_path_bytes(channels));
+  return per_ray && rays > ~0ull / per_ray ? ~0ull : rays * per_ray;
+}
+inline uint64_t vertices_piece(uint64_t n, uint64_t asked, uint64_t pass_target, bool host, uint32_t iterations,
+                               uint32_t max_bounces, uint32_t channels) {
+  uint64_t piece = rays_piece(n, asked, pass_target);
+  if (host) {
+    const uint64_t per_ray = vertices_staging_bytes(1, iterations, max_bounces, channels);
+    if (per_ray) piece = std::max<uint64_t>(1, std::min(piece, VERTICES_STAGING_MAX / per_ray));
+  }
+  return piece;
+}
+// n * iterations * (max_bounces + 1) vertices: every per-vertex array (24 B per vertex at most) fits a 64-bit byte index
+constexpr uint64_t VERTICES_MAX = 1ull << 56;
+inline bool vertices_fit(uint64_t n, uint32_t iterations, uint32_t max_bounces) {
+  const uint64_t per_ray = (uint64_t)iterations * ((uint64_t)max_bounces + 1); // < 2^40
+  return !per_ray || n <= (VERTICES_MAX - 1) / per_ray; // n * per_ray < 2^56
+}
+
 // ---- rptgpu_render_views_denoised: the batch's n = n_views * npix indices hold their state, a batch's frame, the feature
 // sums and the filter's columns at once (tests/cpp/views_denoise_plan_check.cpp).  n must fit 32 bits less one:
 // rpt_buffer_accumulate indexes in uint32_t and its launch covers n rounded up to 256.  Bytes per array group, for the

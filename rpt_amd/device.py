@@ -43,6 +43,23 @@ def device_count():
     return n.value
 
 
+class PathVertices:
+    """GpuScene.trace_vertices' result: `channels` (the RPT_VERTEX_* bits that were asked for) and one attribute per channel
+    — length, t, normal, object, position, direction, draw, radiance, bsdf, inv_pdf, abs_cos, rgb — holding its array (numpy,
+    or torch on the device), or None when the channel was not named."""
+    NAMES = ("length", "t", "normal", "object", "position", "direction", "draw", "radiance", "bsdf", "inv_pdf", "abs_cos", "rgb")
+    __slots__ = ("channels",) + NAMES
+
+    def __init__(self, channels):
+        self.channels = int(channels)
+        for name in self.NAMES:
+            setattr(self, name, None)
+
+    def arrays(self):
+        """{name: array} of the channels that were named"""
+        return {name: getattr(self, name) for name in self.NAMES if getattr(self, name) is not None}
+
+
 class GpuScene:
     """Owns one `rptgpu_scene*` (device-resident flattened scene + kd-trees)."""
 
@@ -786,6 +803,104 @@ class GpuScene:
             current.synchronize()
         code = self.lib.rptgpu_first_hits_device(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.byref(q),
                                                  C.byref(a), C.c_void_p(stream or 0))
+        _abi.check(code, self.handle)
+        return out
+
+    # rptgpu_trace_vertices' channels: (bit, name, "path" | "vertex" | "ray", shape behind it, dtype)
+    _VERTEX_CHANNELS = ((_abi.RPT_VERTEX_LENGTH, "length", "path", (), np.uint32), (_abi.RPT_VERTEX_T, "t", "vertex", (), np.float64),
+                        (_abi.RPT_VERTEX_NORMAL, "normal", "vertex", (3,), np.float64),
+                        (_abi.RPT_VERTEX_OBJECT, "object", "vertex", (), np.int32),
+                        (_abi.RPT_VERTEX_POSITION, "position", "vertex", (3,), np.float64),
+                        (_abi.RPT_VERTEX_DIRECTION, "direction", "vertex", (3,), np.float64),
+                        (_abi.RPT_VERTEX_DRAW, "draw", "vertex", (), np.uint32),
+                        (_abi.RPT_VERTEX_RADIANCE, "radiance", "vertex", (3,), np.float64),
+                        (_abi.RPT_VERTEX_BSDF, "bsdf", "vertex", (3,), np.float64),
+                        (_abi.RPT_VERTEX_INV_PDF, "inv_pdf", "vertex", (), np.float64),
+                        (_abi.RPT_VERTEX_ABS_COS, "abs_cos", "vertex", (), np.float64),
+                        (_abi.RPT_VERTEX_RGB, "rgb", "ray", (3,), np.float64))
+
+    def trace_vertices(self, origins, dirs, max_bounces, channels=_abi.RPT_VERTEX_ALL, streams=None, samples=1, seed=0x52505447,
+                       sample_index_base=0, first_draw=0, exposure_value=0.0, flags=0):
+        """The vertices of the paths trace_rays runs along the caller's rays (rptgpu_trace_vertices) -> a
+        PathVertices: one array per channel of `channels` (RPT_VERTEX_*), None for a channel that is not named.  With n
+        rays, S = samples and B = max_bounces: `length` (n, S) uint32; per vertex (n, S, B + 1) [+ (3,)]: `t`, `normal`,
+        `object` (int32), `position`, `direction`, `draw` (uint32), `radiance`, `bsdf`, `inv_pdf`, `abs_cos`; `rgb` (n, 3),
+        trace_rays' result for the same arguments.  Entries behind a path's last vertex hold +0.0 (`object` -1, `draw` 0).
+        origins, dirs: (n, 3) float64, used as given; streams, seed, sample_index_base, first_draw: trace_rays' stream
+        contract.  numpy arrays go through host memory; torch tensors on the handle's device are read where they lie
+        (rptgpu_trace_vertices_device) and the results are new tensors there (`length` and `draw` as int32: the same bits)."""
+        q = _abi.RptVertexQuery()
+        q.struct_size = C.sizeof(_abi.RptVertexQuery)
+        q.max_bounces, q.iterations, q.first_draw = int(max_bounces), int(samples), int(first_draw)
+        q.exposure_value, q.seed, q.sample_index_base = float(exposure_value), int(seed), int(sample_index_base)
+        q.precision_mode, q.flags, q.channels, q.reserved = _abi.RPT_PRECISION_F64_STRICT, int(flags), int(channels), 0
+        a = _abi.RptVertexArrays()
+        a.struct_size, a.reserved = C.sizeof(_abi.RptVertexArrays), 0
+        named = [c for c in self._VERTEX_CHANNELS if q.channels & c[0]]
+        torch_in = hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr")
+        if torch_in:
+            import torch
+            dev = torch.device("cuda", self.device)
+
+            def vectors(t, what):
+                if not isinstance(t, torch.Tensor) or t.device != dev:
+                    raise ValueError("trace_vertices: %s must be a torch tensor on %s, like the other array" % (what, dev))
+                if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
+                    raise ValueError("trace_vertices: %s must be an (n, 3) float64 tensor" % what)
+                return t.contiguous()  # (no copy when it already is)
+        else:
+            def vectors(v, what):
+                v = np.asarray(v)
+                if v.dtype != np.float64 or v.ndim != 2 or v.shape[1] != 3:
+                    raise ValueError("trace_vertices: %s must be an (n, 3) float64 array" % what)
+                return np.ascontiguousarray(v)
+
+        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
+        n = int(o.shape[0])
+        if int(d.shape[0]) != n:
+            raise ValueError("trace_vertices: %d origins for %d directions" % (n, int(d.shape[0])))
+        ids = None
+        if streams is not None:
+            if torch_in:
+                if not isinstance(streams, torch.Tensor) or streams.device != dev:
+                    raise ValueError("trace_vertices: streams must be a torch tensor on %s, like the rays" % dev)
+                ids = streams.reshape(-1)
+                if ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
+                    ids = ids.to(torch.int64).to(torch.int32)  # the low 32 bits
+                ids = ids.contiguous()
+            else:
+                ids = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
+            if int(ids.shape[0]) != n:
+                raise ValueError("trace_vertices: %d stream ids for %d rays" % (int(ids.shape[0]), n))
+        heads = {"path": (n, q.iterations), "vertex": (n, q.iterations, q.max_bounces + 1), "ray": (n,)}
+        types = dict(_abi.RptVertexArrays._fields_)
+        out = PathVertices(q.channels)
+        for _, name, kind, tail, dtype in named:
+            shape = heads[kind] + tail
+            if torch_in:
+                # (at least one element: an empty tensor has no address, and a named channel's pointer must not be NULL)
+                room = torch.empty(max(int(np.prod(shape)), 1), dtype=torch.float64 if dtype is np.float64 else torch.int32, device=dev)
+                setattr(out, name, room[:int(np.prod(shape))].reshape(shape))
+                setattr(a, name, C.cast(C.c_void_p(room.data_ptr()), types[name]))
+            else:
+                arr = np.empty(shape, dtype=dtype)
+                setattr(out, name, arr)
+                setattr(a, name, arr.ctypes.data_as(types[name]))
+        if torch_in:
+            # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
+            # stream is waited for here)
+            current = torch.cuda.current_stream(dev)
+            stream = current.cuda_stream
+            if not stream:
+                current.synchronize()
+            code = self.lib.rptgpu_trace_vertices_device(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                         C.c_void_p(ids.data_ptr()) if ids is not None else None, C.byref(q),
+                                                         C.byref(a), C.c_void_p(stream or 0))
+        else:
+            PD = C.POINTER(C.c_double)
+            code = self.lib.rptgpu_trace_vertices(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD),
+                                                  ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None,
+                                                  C.byref(q), C.byref(a))
         _abi.check(code, self.handle)
         return out
 

@@ -522,6 +522,62 @@ pub mod ffi {
         pub fn rptgpu_render_views_denoised(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, d: *const RptViewDenoise, out: *const RptViewDenoiseOut) -> c_int;
         pub fn rptgpu_render_views_denoised_device(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, d: *const RptViewDenoise, d_out: *const RptViewDenoiseOut, stream: *mut c_void) -> c_int;
     }
+
+    // include/rpt_gpu_vertices.h: the vertices of the paths rptgpu_trace_rays runs — optional additions within ABI 7 (a
+    // library without them is detected with dlsym("rptgpu_trace_vertices"); this crate links them like the rest)
+    // the RPT_VERTEX_* channel bits, in the order of RptVertexArrays' pointers
+    pub const RPT_VERTEX_LENGTH: u32 = 1 << 0;
+    pub const RPT_VERTEX_T: u32 = 1 << 1;
+    pub const RPT_VERTEX_NORMAL: u32 = 1 << 2;
+    pub const RPT_VERTEX_OBJECT: u32 = 1 << 3;
+    pub const RPT_VERTEX_POSITION: u32 = 1 << 4;
+    pub const RPT_VERTEX_DIRECTION: u32 = 1 << 5;
+    pub const RPT_VERTEX_DRAW: u32 = 1 << 6;
+    pub const RPT_VERTEX_RADIANCE: u32 = 1 << 7;
+    pub const RPT_VERTEX_BSDF: u32 = 1 << 8;
+    pub const RPT_VERTEX_INV_PDF: u32 = 1 << 9;
+    pub const RPT_VERTEX_ABS_COS: u32 = 1 << 10;
+    pub const RPT_VERTEX_RGB: u32 = 1 << 11;
+    /// `RptVertexQuery` (the parameters of `rptgpu_trace_vertices`: `RptRayQuery`'s fields, then the channels)
+    #[repr(C)]
+    #[derive(Copy, Clone, Debug)]
+    pub struct RptVertexQuery {
+        pub struct_size: u32,
+        pub max_bounces: u32,
+        pub iterations: u32,
+        pub first_draw: u32,
+        pub exposure_value: f64,
+        pub seed: u64,
+        pub sample_index_base: u64,
+        pub precision_mode: u32,
+        pub flags: u32,
+        pub channels: u32,
+        pub reserved: u32,
+    }
+    /// `RptVertexArrays` (the output arrays of `rptgpu_trace_vertices`, host or device; a channel that is not named: its
+    /// pointer is not read).  Per-vertex arrays are `[n][iterations][max_bounces + 1]` (x 3 for the vectors)
+    #[repr(C)]
+    #[derive(Copy, Clone, Debug)]
+    pub struct RptVertexArrays {
+        pub struct_size: u32,
+        pub reserved: u32,
+        pub length: *mut u32,
+        pub t: *mut f64,
+        pub normal: *mut f64,
+        pub object: *mut i32,
+        pub position: *mut f64,
+        pub direction: *mut f64,
+        pub draw: *mut u32,
+        pub radiance: *mut f64,
+        pub bsdf: *mut f64,
+        pub inv_pdf: *mut f64,
+        pub abs_cos: *mut f64,
+        pub rgb: *mut f64,
+    }
+    extern "C" {
+        pub fn rptgpu_trace_vertices(h: *mut rptgpu_scene, n: u64, origins: *const f64, dirs: *const f64, streams: *const u32, q: *const RptVertexQuery, out: *const RptVertexArrays) -> c_int;
+        pub fn rptgpu_trace_vertices_device(h: *mut rptgpu_scene, n: u64, d_origins: *const c_void, d_dirs: *const c_void, d_streams: *const c_void, q: *const RptVertexQuery, d_out: *const RptVertexArrays, stream: *mut c_void) -> c_int;
+    }
 }
 
 pub use ffi::{RptCamera, RptMaterial, RptRenderParams, RptSceneOptions, RptStats, RptTransform, RptTriangle};
