@@ -781,13 +781,17 @@ class Renderer {
   // addition: a batch of frames in one call (rptgpu_render_views, include/rpt_gpu.h), each from a view of its own — a camera
   // under RPT_VIEW_PERSPECTIVE (this renderer's frame of that camera), RPT_VIEW_ORTHOGRAPHIC or RPT_VIEW_PANORAMA (a
   // rendered panorama is an Hdri's texel array).  -> [views][height][width][3], the renderer's size, samples, bounces and
-  // exposure; view v renders with seed + v * seed_stride, whatever other views the call holds.
-  std::vector<double> render_views(const std::vector<RptView>& views, uint64_t seed_stride = 0, uint64_t sample_index_base = 0) {
+  // exposure; view v renders with seed + v * seed_stride, whatever other views the call holds.  flags: RPT_FLAG_* of the
+  // query — RPT_FLAG_VIEWS_PERSISTENT (include/rpt_gpu_views_persistent.h) runs the batch in the persistent path kernel,
+  // the same bits by another route, where views_persistent_supported() says the library reads it.
+  static bool views_persistent_supported() { return rptgpu_views_persistent_supported() == 1; }
+  std::vector<double> render_views(const std::vector<RptView>& views, uint64_t seed_stride = 0, uint64_t sample_index_base = 0,
+                                   uint32_t flags = 0) {
     ensure_scene();
     RptViewQuery q{};
     q.struct_size = sizeof(RptViewQuery); q.width = width_; q.height = height_; q.max_bounces = max_bounces_;
     q.iterations = num_samples_; q.exposure_value = ev_; q.seed = seed_; q.seed_stride = seed_stride;
-    q.sample_index_base = sample_index_base;
+    q.sample_index_base = sample_index_base; q.flags = flags;
     std::vector<double> out(views.size() * (size_t)width_ * height_ * 3);
     check(rptgpu_render_views(handle_, views.size(), views.data(), &q, out.data()));
     return out;
@@ -795,12 +799,12 @@ class Renderer {
   // ... with a seed per view (rptgpu_render_views_seeded): view v renders as with set_seed(seeds[v]) and no stride — a data
   // set resumed, one view of an earlier job again, seeds of the caller's own generator.  One seed per view.
   std::vector<double> render_views(const std::vector<RptView>& views, const std::vector<uint64_t>& seeds,
-                                   uint64_t sample_index_base = 0) {
+                                   uint64_t sample_index_base = 0, uint32_t flags = 0) {
     ensure_scene();
     if (seeds.size() != views.size()) throw std::invalid_argument("render_views: one seed per view");
     RptViewQuery q{};
     q.struct_size = sizeof(RptViewQuery); q.width = width_; q.height = height_; q.max_bounces = max_bounces_;
-    q.iterations = num_samples_; q.exposure_value = ev_; q.sample_index_base = sample_index_base;
+    q.iterations = num_samples_; q.exposure_value = ev_; q.sample_index_base = sample_index_base; q.flags = flags;
     std::vector<double> out(views.size() * (size_t)width_ * height_ * 3);
     check(rptgpu_render_views_seeded(handle_, views.size(), views.data(), &q, seeds.data(), out.data()));
     return out;

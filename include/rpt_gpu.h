@@ -175,10 +175,14 @@ enum {
   RPT_FLAG_WAVEFRONT = 2u,       /* force the multi-kernel wavefront pipeline (raygen / extend / shade /
                                     shadow / resolve; path state in HBM, lean 4-waves/SIMD traversal
                                     kernels with LDS stacks) */
-  RPT_FLAG_PERSISTENT = 8u       /* force the persistent path kernel (whole path in registers).
+  RPT_FLAG_PERSISTENT = 8u,      /* force the persistent path kernel (whole path in registers).
                                     With neither flag the library picks: wavefront when the scene has
                                     real kd-trees (depth >= 3: traversal latency dominates and wants
                                     occupancy), persistent otherwise.  Both give the same bits. */
+  RPT_FLAG_VIEWS_PERSISTENT = 16u /* RptViewQuery::flags of rptgpu_render_views[_seeded][_device] only: the batch of views
+                                    in the persistent path kernel — an OPTIONAL addition within ABI 7, read only by a
+                                    library that exports rptgpu_views_persistent_supported (rpt_gpu_views_persistent.h,
+                                    included at the end of this file; a library without it ignores the bit) */
 };
 
 /* ---- what Renderer carries into sample(): src/renderer.rs:18-42 + the call argument ----
@@ -664,7 +668,8 @@ int rptgpu_bake_ao_device(rptgpu_scene* h, uint64_t n, const void* d_positions, 
  *                          (se, ce) = rpt_sincos_pio2((0.5 - cy / (double)(height-1)) * 3.141592653589793);
  *                          dir = (ce*c, se, ce*s); origin = eye.  Every argument stays within rpt_sincos_pio2's
  *                          |x| < 3 pi / 4 (include/rpt_math.h).  direction, up, fov, aperture, focal_distance: not read.
- * The call always runs the wavefront pipeline, as rptgpu_trace_rays does, sized and restarted like a render's passes, over
+ * The call runs the wavefront pipeline (always, unless a library with rpt_gpu_views_persistent.h is asked for the persistent
+ * kernel with RPT_FLAG_VIEWS_PERSISTENT: that file, included at the end of this one), as rptgpu_trace_rays does, sized and restarted like a render's passes, over
  * pieces of consecutive (view, pixel) indices (a piece begins and ends wherever the piece size says, inside a view or at
  * its border, whatever the views' seeds: with seeds that differ, rpt_raygen_views_seeded and rpt_shade_seeded run in
  * rpt_raygen_views' and rpt_shade's places and read the seed of each index of the piece, 8 B per index more, and the
@@ -674,7 +679,7 @@ int rptgpu_bake_ao_device(rptgpu_scene* h, uint64_t n, const void* d_positions, 
  * advances as for a render (samples = n_views * width * height * iterations).  RPTGPU_VIEWS_PIECE (environment, read per
  * call; tests): the indices per piece.
  * NOT IN SCOPE: the tile partition and multi-GPU (a caller shards the VIEWS over handles: a view's pixels depend on nothing
- * else), the device-resident Buffer for views, and the persistent path kernel (the views' feature buffers:
+ * else), the device-resident Buffer for views, and the persistent path kernel as the default route (the views' feature buffers:
  * rptgpu_render_views_aov, below; a denoised frame per view — batches, features and the filter of rptgpu_buffer_denoise over
  * the whole batch of views —: rpt_gpu_views_denoised.h, which this file includes at its end).
  * RPTGPU_E_INVALID_ARGUMENT, checked before any device work and with a detail naming the reason: a NULL RptViewQuery, a
@@ -1027,6 +1032,8 @@ const char* rptgpu_kernel_name(int k);
 #include "rpt_gpu_views_denoised.h"
 /* ---- ... and the vertices of the paths rptgpu_trace_rays runs ---- */
 #include "rpt_gpu_vertices.h"
+/* ---- ... and a batch of views in the persistent path kernel, on request ---- */
+#include "rpt_gpu_views_persistent.h"
 
 #ifdef __cplusplus
 }

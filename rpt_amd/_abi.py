@@ -32,6 +32,7 @@ RPT_FLAG_PROFILE_KERNELS = 1
 RPT_FLAG_WAVEFRONT = 2
 RPT_FLAG_GENERAL_TRAVERSAL = 4
 RPT_FLAG_PERSISTENT = 8
+RPT_FLAG_VIEWS_PERSISTENT = 16  # include/rpt_gpu_views_persistent.h: RptViewQuery.flags of render_views (views_persistent_supported())
 RPT_K_RAYGEN, RPT_K_EXTEND, RPT_K_SHADE, RPT_K_SHADOW, RPT_K_RESOLVE, RPT_K_PATHS, RPT_K_TREE_TRACE, RPT_K_TREE_SORT = range(8)
 RPT_K_COUNT = 8
 RPT_PARTICLES_SOLID_GRAVITY, RPT_PARTICLES_MARBLES, RPT_PARTICLES_CIRCLE = range(3)
@@ -350,6 +351,11 @@ VERTICES_SYMBOLS = [
     ("rptgpu_trace_vertices_device", C.c_int,
      [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptVertexQuery), C.POINTER(RptVertexArrays), _VP]),
 ]
+# ... and the symbol include/rpt_gpu_views_persistent.h declares, optional in the same way: a library without it ignores
+# RPT_FLAG_VIEWS_PERSISTENT and runs the wavefront pipeline (views_persistent_supported)
+VIEWS_PERSISTENT_SYMBOLS = [
+    ("rptgpu_views_persistent_supported", C.c_int, []),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -374,7 +380,7 @@ def load_library(path=None):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950). "
             "There is no CPU fallback." % p)
     lib = C.CDLL(p)
-    for name, restype, argtypes in SYMBOLS + SEEDED_SYMBOLS + DENOISED_SYMBOLS + VERTICES_SYMBOLS:
+    for name, restype, argtypes in SYMBOLS + SEEDED_SYMBOLS + DENOISED_SYMBOLS + VERTICES_SYMBOLS + VIEWS_PERSISTENT_SYMBOLS:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -383,6 +389,18 @@ def load_library(path=None):
     if path is None:
         _lib = lib
     return lib
+
+
+def views_persistent_supported(lib=None):
+    """Does the library read RPT_FLAG_VIEWS_PERSISTENT (include/rpt_gpu_views_persistent.h)?  Detected by symbol, as a C
+    caller does with dlsym: a library without it is still ABI 7, ignores the bit and runs the wavefront pipeline."""
+    lib = lib or load_library()
+    try:
+        fn = lib.rptgpu_views_persistent_supported
+    except AttributeError:
+        return False
+    fn.restype, fn.argtypes = C.c_int, []
+    return fn() == 1
 
 
 def check(code, handle=None):

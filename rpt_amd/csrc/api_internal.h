@@ -48,6 +48,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -194,6 +195,7 @@ struct rptgpu_scene {
   DevBuf<rptdev::View> view_recs;     // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<uint64_t> view_seeds;         // ... their seeds, when the views have seeds of their own,
   DevBuf<uint64_t> ray_seeds;          // ... and then the seed of each index of a piece, beside ray_ids
+  DevBuf<uint32_t> view_of;            // ... in the persistent kernel: the view of each index of a piece (ViewRays::view_of)
   // rptgpu_render_views_denoised's working set over the batch's n_views * width * height indices (api_views_denoise.cpp;
   // the bytes: rptplan::views_denoise_plan), grown on demand: the Buffer's per-pixel state, one batch's frame, the feature
   // sums, the filter's columns and hit flags, color_bytes' thresholds, and a host caller's outputs before they are copied
@@ -385,13 +387,19 @@ struct RaySource {
   // piece's Frame::seed is not read then.  nullptr: every view's seed is the Frame's
   const uint64_t* view_seeds = nullptr;
   uint64_t* seeds_out = nullptr;
+  // ... or that piece in the persistent kernel (render_persistent -> rpt_paths_views, RPT_FLAG_VIEWS_PERSISTENT): views,
+  // view_width, view_height and view_base as above, view_seeds one seed per view of the call WHATEVER the seed stride, and
+  // view_of the view of each index of the piece counted from the piece's first (rpt_views_ids wrote it, and the pixels
+  // into the piece's Frame::pixels)
+  const uint32_t* view_of = nullptr;
   // rptgpu_trace_vertices (api_vertices.cpp): where the vertices of the piece's paths go — the caller's arrays or their
   // staging, offset to the piece; run_pass fills in s_first per pass.  nullptr (every other call): nothing is launched for it
   const rptdev::VertexOut* vertices = nullptr;
 };
 // api_views.cpp: what is wrong with an RptViewQuery / with one view of a call with query q (nullptr: nothing); shared with
 // rptgpu_render_views_aov (api_hits.cpp)
-const char* bad_view_query(const RptViewQuery* q);
+// views_persistent_ok: the call takes RPT_FLAG_VIEWS_PERSISTENT (rptgpu_render_views and its forms); the others refuse it by name
+const char* bad_view_query(const RptViewQuery* q, bool views_persistent_ok = false);
 const char* bad_view(const RptView& v, const RptViewQuery& q);
 // the seeds of a call's views as the drivers take them: the caller's (the _seeded entry points), or seed + v * seed_stride in
 // wrapping u64 arithmetic; empty: every view has the query's seed (seed_stride == 0), the one-seed route
@@ -413,6 +421,10 @@ void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in);
 // the wavefront driver: the batch in passes from `src`, then rpt_finish into `out` (api_render.cpp)
 void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const RaySource& src,
                       void* out, bool out_f32, bool packed, bool prof);
+// the persistent driver: the batch in launches of rpt_paths (src.cam) or rpt_paths_views (src.views), rpt_sum_samples behind
+// each, then rpt_finish into `out` (api_render.cpp)
+void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const RaySource& src,
+                       void* out, bool out_f32, bool packed, bool prof);
 // packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list.
 // d_list (device, n_list pixel indices; requires packed and d_out): render exactly those pixels instead of the part's list,
 // without touching the cached partition (the adaptive buffer's active pixels, api_buffer.cpp)

@@ -316,11 +316,19 @@ rptdev::PathState path_state(rptgpu_scene* h) {
 }
 
 // the default pipeline: one persistent kernel, the whole path in registers; the batch runs as launches of at most
-// spp_l samples per pixel (rptplan::plan_persistent)
+// spp_l samples per pixel (rptplan::plan_persistent).  The rays are src's: a camera's pixels (src.cam: rpt_paths), or a
+// piece of a batch of views (src.views with view_seeds and view_of: rpt_paths_views — fr is the piece's, its pixels
+// rpt_views_ids' — api_views.cpp)
 void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr,
-                       const rptdev::Camera& cam, void* out, bool out_f32, bool packed, bool prof) {
+                       const RaySource& src, void* out, bool out_f32, bool packed, bool prof) {
   hipStream_t st = h->stream;
   const uint32_t npix = fr.npix;
+  const bool views = src.views != nullptr;
+  rptdev::ViewRays vr{};
+  if (views) {
+    const uint64_t v0 = src.view_base / ((uint64_t)src.view_width * src.view_height); // the piece's first view
+    vr = rptdev::ViewRays{src.views + v0, src.view_seeds + v0, src.view_of, src.view_width, src.view_height};
+  }
   const bool print_launch = std::getenv("RPTGPU_PRINT_LAUNCH") != nullptr;
   const uint64_t lbuf_held = h->lbuf.n * sizeof(double);
   const int64_t free_b = lbuf_held < h->opt.lbuf_bytes ? free_memory() : -1;
@@ -328,8 +336,10 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   FlatLayout lay = flat ? h->flat_layout : FlatLayout{};
   const uint32_t flat_lds = lay.off_end;
   // the fused kernel's pre-trace pass: this render's screen rectangles of the objects it may skip (host_scene.cpp
-  // pinhole_screen_rect; none under a lens).  An object without a rectangle is always tested.
-  if (RPT_PRETRACE_CULL && lay.pretrace_cull) {
+  // pinhole_screen_rect; none under a lens).  An object without a rectangle is always tested.  A piece of views gets none
+  // (cull_n = 0: every test runs — the rectangles are one camera's)
+  if (RPT_PRETRACE_CULL && lay.pretrace_cull && !views) {
+    const rptdev::Camera& cam = *src.cam;
     for (size_t i = 0; i < h->obj_geom.size() && i < 64 && lay.cull_n < (uint32_t)RPT_CULL_MAX; i++) {
       uint32_t r[4];
       if (((lay.cull_always >> i) & 1ull) ||
@@ -343,18 +353,21 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
     }
   }
   const rptplan::PersistentPlan pl = rptplan::plan_persistent(
-      npix, p.iterations, p.max_bounces, h->num_cus, kt->paths_max_blocks_per_cu(flat ? &lay : nullptr, flat_lds, false),
+      npix, p.iterations, p.max_bounces, h->num_cus, (views ? kt->paths_views_max_blocks_per_cu : kt->paths_max_blocks_per_cu)(flat ? &lay : nullptr, flat_lds, false),
       h->opt.lbuf_bytes, lbuf_held, free_b, h->opt.paths_chunk, h->all_flat, h->dscene.force_general, h->flat_layout.obj_filter);
   // a texture environment: the lanes park their lookups in what the wave's LDS share has left (kernels/paths.inc) —
   // unless that costs a resident wave (a flat scene that fills the share)
   bool park = flat && h->opt.env_park != 0 && h->dscene.env_kind != RPT_ENV_COLOR; // (flat scenes: rpt_paths<KdLds>'s stack fills the share)
-  if (park && kt->paths_max_blocks_per_cu(&lay, flat_lds, true) < pl.per_cu) park = false;
+  if (park && (views ? kt->paths_views_max_blocks_per_cu : kt->paths_max_blocks_per_cu)(&lay, flat_lds, true) < pl.per_cu) park = false;
+  // (a piece of views: render_views cut it so that every launch fits the work counter — rptplan::views_items)
+  if (views && rptplan::views_items(npix, pl.spp_l, pl.chunk, pl.nblocks, RPT_PATHS_BATCH_MAX).capped)
+    throw std::runtime_error("rpt_paths_views: the piece's work items do not fit the 32-bit work counter (internal error)");
   h->prec.alloc((uint64_t)rpt_fold_ring_slots(p.max_bounces) * rptdev::REC_FIELDS * ((uint64_t)pl.nblocks * 64));
   h->lbuf.alloc(std::max<uint64_t>(1, (uint64_t)pl.spp_l * 3 * npix));
   if (print_launch)
-    std::fprintf(stderr, "rpt_paths<%s>: %d blocks/CU x %d CUs -> %u blocks, %u samples per work item, %u launch(es) of %u spp, "
+    std::fprintf(stderr, "%s<%s>: %d blocks/CU x %d CUs -> %u blocks, %u samples per work item, %u launch(es) of %u spp, "
                  "dynamic LDS %u B per wave (the flat scene's tables)%s%s%s%s\n",
-                 flat ? (lay.obj_filter ? "KdFlatF" : lay.n_tris ? "KdFlat" : "KdFlatG") : "KdLds", pl.per_cu, h->num_cus, pl.nblocks,
+                 views ? "rpt_paths_views" : "rpt_paths", flat ? (lay.obj_filter ? "KdFlatF" : lay.n_tris ? "KdFlat" : "KdFlatG") : "KdLds", pl.per_cu, h->num_cus, pl.nblocks,
                  pl.chunk, pl.n_launch, pl.spp_l, flat_lds, park ? " + parked environment lookups" : "",
                  flat && lay.n_tris && lay.fuse_query && !park ? ", shadow and bounce rays in one query" : "",
                  flat && lay.n_tris && lay.fuse_query && !park && lay.scene_consts ? ", a hit's scene constants from the wave's tables" : "",
@@ -368,8 +381,12 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
     fr.sample_base = p.sample_index_base + s0;
     HIP_TRY(hipMemsetAsync(h->counters.p, 0, sizeof(uint32_t), st));
     { Bracket b(h, RPT_K_PATHS, prof);
-      kt->paths(st, h->dscene, fr, cam, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
-                pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
+      if (views)
+        kt->paths_views(st, h->dscene, fr, vr, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
+                        pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
+      else
+        kt->paths(st, h->dscene, fr, *src.cam, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
+                  pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
       b.done(); }
     kt->sum_samples(st, fr, h->lbuf.p, spp, s0 == 0);
     if (print_launch) { // diagnostics: where the 32-bit work counter ended (kernels/paths.inc fetch_item)
@@ -638,7 +655,7 @@ int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams*
       RaySource src{};
       src.cam = &cam;
       if (wavefront) render_wavefront(h, kt, *p, fr, src, out, out_f32, packed, prof);
-      else render_persistent(h, kt, *p, fr, cam, out, out_f32, packed, prof);
+      else render_persistent(h, kt, *p, fr, src, out, out_f32, packed, prof);
     }
     HIP_TRY(hipGetLastError());
     if (host_out) HIP_TRY(hipMemcpyAsync(host_out, out, frame_elems * out_elem, hipMemcpyDeviceToHost, st));

@@ -7,12 +7,15 @@
 // render's.  So the launches of a depth and its one host wait are shared by every view a piece holds — whatever the views'
 // seeds: where they differ (rptgpu_render_views_seeded[_device], or a seed stride) the seed travels with the path
 // (RaySource::view_seeds: rpt_raygen_views_seeded, rpt_shade_seeded), and pieces are cut where the one-seed route cuts them.
+// Under RPT_FLAG_VIEWS_PERSISTENT (include/rpt_gpu_views_persistent.h) the same pieces go through the
+// persistent driver instead: rpt_views_ids names each index's pixel and view, rpt_paths_views runs the piece's launches of at
+// most spp_l samples, and rpt_sum_samples and the packed rpt_finish behind them are a render's.  The same bits.
 #include "api_internal.h"
 
 namespace rptapi {
 
 // what is wrong with an RptViewQuery (nullptr: nothing)
-const char* bad_view_query(const RptViewQuery* q) {
+const char* bad_view_query(const RptViewQuery* q, bool views_persistent_ok) {
   if (!q) return "null RptViewQuery";
   if (q->struct_size != sizeof(RptViewQuery)) return "RptViewQuery: struct_size is not sizeof(RptViewQuery)";
   if (!q->width || !q->height || !q->iterations) return "RptViewQuery: width, height and iterations must be non-zero";
@@ -21,6 +24,13 @@ const char* bad_view_query(const RptViewQuery* q) {
   if (q->flags & RPT_FLAG_PERSISTENT)
     return "RptViewQuery: RPT_FLAG_PERSISTENT — the persistent kernel renders one camera's frame; a batch of views runs the "
            "wavefront pipeline only";
+  if (q->flags & RPT_FLAG_VIEWS_PERSISTENT) {
+    if (!views_persistent_ok)
+      return "RptViewQuery: RPT_FLAG_VIEWS_PERSISTENT — only rptgpu_render_views and its _seeded and _device forms run a batch "
+             "of views in the persistent kernel";
+    if (q->flags & RPT_FLAG_WAVEFRONT)
+      return "RptViewQuery: RPT_FLAG_VIEWS_PERSISTENT | RPT_FLAG_WAVEFRONT — the two flags name different routes";
+  }
   if ((uint64_t)q->width * q->height > (1ull << 32)) return "RptViewQuery: width * height > 2^32 (a pixel is a 32-bit stream id)";
   return nullptr;
 }
@@ -57,7 +67,7 @@ std::vector<uint64_t> view_seed_list(uint64_t n_views, const RptViewQuery& q, co
 int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, bool seeded, const uint64_t* seeds,
                  void* out, bool on_device, bool out_f32, hipStream_t user_stream) {
   // (the query first, then the views: both are refused whatever else is wrong, also without a handle or a device)
-  if (const char* why = bad_view_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (const char* why = bad_view_query(q, true)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (n_views && (!views || !out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
   if (seeded && n_views && !seeds) return fail(h, RPTGPU_E_INVALID_ARGUMENT, NULL_SEEDS);
   const uint64_t npix = (uint64_t)q->width * q->height;
@@ -91,7 +101,12 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
       recs[v].ortho_scale = views[v].ortho_scale;
     }
     h->view_recs.upload(recs, st);
-    const std::vector<uint64_t> seed_list = view_seed_list(n_views, *q, seeded ? seeds : nullptr);
+    // the persistent kernel on request — unless the scene has a group with tree children, which only the wavefront
+    // pipeline walks (use_wavefront: such a scene cannot honour the request, as for a render)
+    const bool persistent = (q->flags & RPT_FLAG_VIEWS_PERSISTENT) && !use_wavefront(h, 0, false);
+    std::vector<uint64_t> seed_list = view_seed_list(n_views, *q, seeded ? seeds : nullptr);
+    // rpt_paths_views always reads a seed per view (its key is per lane): views that share the query's seed get equal ones
+    if (persistent && seed_list.empty()) seed_list.assign(n_views, q->seed);
     const bool per_view = !seed_list.empty(); // the seed travels with the path
     if (per_view) h->view_seeds.upload(seed_list, st);
     // the piece: at most the paths one pass may hold with every level of every path (rptplan::views_piece)
@@ -102,12 +117,17 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
     pass_input_now(h, in);
     uint64_t asked = 0; // tests: pieces of a few pixels
     if (const char* e = std::getenv("RPTGPU_VIEWS_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    const uint64_t piece = rptplan::views_piece(n, asked, rptplan::plan_pass(in).target);
+    uint64_t piece = rptplan::views_piece(n, asked, rptplan::plan_pass(in).target);
+    if (persistent) { // ... and what a launch's work counter holds, at the most resident blocks any instantiation has
+      const uint32_t blocks_max = (uint32_t)std::max(1, h->num_cus) * RPT_PATHS_WAVES_PER_CU_MAX;
+      piece = std::max<uint64_t>(1, rptplan::views_items(piece, q->iterations, 1, blocks_max, RPT_PATHS_BATCH_MAX).m);
+    }
     const bool at_views = false; // a piece spans views whatever their seeds
     const size_t out_elem = out_f32 ? sizeof(float) : sizeof(double);
     h->accum.alloc(3 * piece);
     h->ray_ids.alloc(piece);
-    if (per_view) h->ray_seeds.alloc(piece);
+    if (per_view && !persistent) h->ray_seeds.alloc(piece);
+    if (persistent) h->view_of.alloc(piece);
     if (!on_device) h->rays_out.alloc(3 * piece);
     for (uint64_t base = 0, m; base < n; base += m) {
       m = rptplan::views_piece_len(base, n, npix, piece, at_views);
@@ -119,14 +139,20 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
       src.ids_out = h->ray_ids.p;
       src.views = h->view_recs.p; src.view_width = q->width; src.view_height = q->height; src.view_base = base;
       if (per_view) { src.view_seeds = h->view_seeds.p; src.seeds_out = h->ray_seeds.p; }
-      render_wavefront(h, kt, p, fr, src, d_out, out_f32, true, prof);
+      if (persistent) {
+        src.view_of = h->view_of.p;
+        kt->views_ids(st, base, npix, (uint32_t)m, h->ray_ids.p, h->view_of.p);
+        render_persistent(h, kt, p, fr, src, d_out, out_f32, true, prof);
+      } else {
+        render_wavefront(h, kt, p, fr, src, d_out, out_f32, true, prof);
+      }
       HIP_TRY(hipGetLastError());
       if (!on_device) { // the staging array is the next piece's, too
         HIP_TRY(hipMemcpyAsync((double*)out + 3 * base, d_out, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
-    return drain_call(h, h->has_deep && h->gen_overflow.p);
+    return drain_call(h, !persistent && h->has_deep && h->gen_overflow.p);
   });
   if (rc != RPTGPU_OK) return rc;
   h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -155,5 +181,7 @@ int rptgpu_render_views_seeded_device(rptgpu_scene* h, uint64_t n_views, const R
                                       const uint64_t* seeds, void* d_out, int out_is_f32, void* stream) {
   return render_views(h, n_views, views, q, true, seeds, d_out, true, out_is_f32 != 0, (hipStream_t)stream);
 }
+
+int rptgpu_views_persistent_supported(void) { return 1; }
 
 } // extern "C"

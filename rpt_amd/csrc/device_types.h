@@ -157,6 +157,16 @@ struct View {
   uint32_t _pad;
   double ortho_scale;
 };
+// where rpt_paths_views' camera rays come from (kernels/paths_views.inc; rptgpu_render_views under
+// RPT_FLAG_VIEWS_PERSISTENT): a piece of the call's indices j = view * (width * height) + pixel.  views and seeds start at the
+// piece's FIRST view; view_of[i] is the view of the piece's index i counted from there (rpt_views_ids fills it, and the
+// pixels into Frame::pixels).  seeds holds one seed per view whatever the call's seed stride: the kernel's key is per lane
+struct ViewRays {
+  const View* views;
+  const uint64_t* seeds;
+  const uint32_t* view_of; // [Frame::npix]
+  uint32_t width, height;  // of every view
+};
 
 // Per-pass wavefront state, SoA over path slots (slot = s_local * npix + pixel_local).
 // REC_FIELDS doubles per depth record: A[3], f[3], 1/pdf, |wi.n|  (the nested clamp of

@@ -252,7 +252,29 @@ struct KernelTable {
   void (*vertices_store)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, uint32_t n, uint32_t depth,
                          const rptdev::VertexOut& out);
   void (*vertices_fold)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, uint32_t n_paths, const rptdev::VertexOut& out);
+  // a batch of views in the persistent kernel (rpt_paths_views, kernels/paths_views.inc; compiled in a translation unit of
+  // its own, kernels_views_strict[_ext].hip): paths_max_blocks_per_cu and paths for the SAME instantiation of that kernel,
+  // the rays a piece's ViewRays instead of a Camera; views_ids: the ids of a piece of n consecutive indices from j_base on —
+  // pixels[i] the index's pixel in its view (the piece's Frame::pixels), view_of[i] its view counted from the piece's
+  // first (ViewRays::view_of)
+  int (*paths_views_max_blocks_per_cu)(const FlatLayout* flat, uint32_t lds_bytes, bool park);
+  void (*paths_views)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::ViewRays&, uint32_t* work_counter,
+                      double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk, uint32_t n_items,
+                      uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);
+  void (*views_ids)(hipStream_t, uint64_t j_base, uint64_t npix_view, uint32_t n, uint32_t* pixels, uint32_t* view_of);
 };
+// the views' translation units: what the tables above point to
+#define RPT_VIEWS_TU_DECLS(NS)                                                                                                    \
+  namespace NS {                                                                                                                  \
+  int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool park);                                             \
+  void launch_paths(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::ViewRays&, uint32_t* work_counter,     \
+                    double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk, uint32_t n_items,  \
+                    uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);           \
+  void launch_views_ids(hipStream_t, uint64_t j_base, uint64_t npix_view, uint32_t n, uint32_t* pixels, uint32_t* view_of);       \
+  }
+RPT_VIEWS_TU_DECLS(rpt_strict_views)
+RPT_VIEWS_TU_DECLS(rpt_strict_ext_views)
+#undef RPT_VIEWS_TU_DECLS
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)
 // the same with the extended shape set (RPT_SHAPE_MONOMIAL, trees of trees) compiled in

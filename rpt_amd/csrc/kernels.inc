@@ -16,8 +16,9 @@
 //     paths_consts.inc  what a flat scene keeps in the wave's LDS (FlatLds) and the tables of a hit's scene constants
 //     paths_flat.inc    the flat scenes' queries: flat_query, flat_query2 (two rays in one walk), flat_query_filtered
 //     paths_shade.inc   the fused form's draw-first shading: hit_draws, bsdf_opaque, sample_f_opaque, illuminate_mesh
-//     paths.inc         the kernel's contract, work hand-out, record ring, parked lookups, ray stash, the loop itself;
-//                       rpt_sum_samples
+//     paths.inc         the kernel's contract, work hand-out, record ring, parked lookups, ray stash; rpt_sum_samples
+//     paths_loop.inc    the loop itself: one text, compiled as rpt_paths (paths.inc) and as rpt_paths_views (paths_views.inc)
+//     paths_views.inc   rpt_paths_views, the kernel over a piece of a batch of views: its ids, camera ray and per-lane key
 //   the wavefront pipeline — scenes with deep trees; rptgpu_trace_rays and rptgpu_bake_probes for any scene (flat ones
 //   query inside rpt_extend / rpt_shadow_rays) —: one kernel per step of a depth over SoA path state, in six files:
 //     wf_state.inc      access to the SoA path state and the depth records; the queue appends of a wave and of a block
@@ -49,7 +50,9 @@
 #include <cstring>
 #include <type_traits>
 
+#ifndef RPT_VIEWS_TU
 #include <rocprim/device/device_radix_sort.hpp>
+#endif
 
 #include "../../include/rpt_gpu.h"
 #include "../../include/rpt_math.h"
@@ -62,6 +65,10 @@ namespace RPT_NS {
 using namespace rptdev;
 
 #define RPT_DEV __device__ __forceinline__
+// the namespace of this build's views' translation unit: RPT_NS + _views (kernels.h declares what launch.inc takes from it)
+#define RPT_CAT2_(a, b) a##b
+#define RPT_CAT2(a, b) RPT_CAT2_(a, b)
+#define RPT_NS_VIEWS RPT_CAT2(RPT_NS, _views)
 
 // Scene tables that a whole wave indexes uniformly (top-level instances, trees, lights) are read
 // through the CONSTANT address space: the scene is immutable while a kernel runs, and only then
@@ -99,16 +106,24 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/sampling.inc"
 #include "kernels/material.inc"
 #include "kernels/light.inc"
+#ifndef RPT_VIEWS_TU
 #include "kernels/wf_state.inc"
 #include "kernels/wf_sort_key.inc"
 #include "kernels/tree_query.inc"
 #include "kernels/tree_trace.inc"
 #include "kernels/tree_generic.inc"
 #include "kernels/wavefront.inc"
+#endif
 #include "kernels/paths_consts.inc"
 #include "kernels/paths_flat.inc"
 #include "kernels/paths_shade.inc"
 #include "kernels/paths.inc"
+#ifdef RPT_VIEWS_TU
+// the views' translation units (kernels_views_strict[_ext].hip, RPT_NS = rpt_strict[_ext]_views): what rpt_paths needs, then
+// rpt_paths_views, its instantiations and its launchers — and nothing else, so that the code objects of kernels_strict[_ext]
+// stay what they were (DESIGN.md §15.2)
+#include "kernels/paths_views.inc"
+#else
 #include "kernels/buffer.inc"
 #include "kernels/aov.inc"
 // the Buffer's filter kernels and rpt_denoise_views_*: kernels/denoise.inc, once per frame layout (RPT_DN_VIEWS 0: one camera's
@@ -123,5 +138,6 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/hits.inc"
 #include "kernels/wf_vertices.inc"
 #include "kernels/launch.inc"
+#endif // RPT_VIEWS_TU
 
 } // namespace RPT_NS

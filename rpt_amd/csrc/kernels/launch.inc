@@ -87,49 +87,10 @@ void launch_scatter_f32(hipStream_t st, const float* src, const uint32_t* pixels
   if (n) hipLaunchKernelGGL(rpt_scatter_f32, grid_for(n), dim3(256), 0, st, src, pixels, n, dst);
 }
 
-static uint32_t paths_park_off(uint32_t lds_bytes) { return (lds_bytes + 15u) & ~15u; }
-// THE choice of rpt_paths' instantiation (occupancy is asked of, and the launch goes to, what this returns).  flat = null:
-// rpt_paths<KdLds>, which never parks (its stack fills the wave's LDS) — callers clear `park` for it.
-static const void* paths_kernel(const FlatLayout* flat, bool park) {
-#define RPT_PK(L) (park ? (const void*)rpt_paths<L, true> : (const void*)rpt_paths<L, false>)
-  if (!flat) return (const void*)rpt_paths<KdLds, false>;
-  if (flat->obj_filter) return RPT_PK(KdFlatF);
-#if RPT_FUSE_QUERY && RPT_RAY_STASH >= 2
-  // one light that casts shadow rays (the host doubled the quotient table for it): the two-ray form (kernels/paths.inc
-  // FUSE), with a hit's scene constants in the wave's tables where the host found room for them
-  if (flat->n_tris && flat->fuse_query && !park) {
-#if RPT_SCENE_CONSTS
-    if (flat->scene_consts) return (const void*)rpt_paths<KdFlat, false, true, true>;
-#endif
-    return (const void*)rpt_paths<KdFlat, false, true>;
-  }
-#endif
-  return flat->n_tris ? RPT_PK(KdFlat) : RPT_PK(KdFlatG);
-#undef RPT_PK
-}
-int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool park) {
-  if (!flat) park = false;
-  if (park) lds_bytes = paths_park_off(lds_bytes) + RPT_PATHS_PARK_LDS;
-  int nb = 0; // per instantiation: their static LDS differs (rpt_paths<KdFlat> stashes camera rays)
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, paths_kernel(flat, park), 64, lds_bytes);
-  if (e != hipSuccess || nb <= 0) nb = 8;
-  return nb;
-}
-void launch_paths(hipStream_t st, const Scene& sc, const Frame& fr, const Camera& cam, uint32_t* work_counter,
-                  double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk,
-                  uint32_t n_items /* npix * ceil(spp / chunk), checked against the 32-bit work counter by the caller */,
-                  uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch) {
-  if (!flat) park = false; // (rpt_paths<KdLds> has no room for the queues)
-  // items a wave claims with one atomic on the work counter: 1/32 of its share of the launch, within [16, 256]
-  // (RptSceneOptions::paths_batch = 0)
-  if (batch == 0u) batch = std::min(256u, std::max(n_items / (std::max(1u, nblocks) * 32u), 16u));
-  batch = std::min(batch, (uint32_t)RPT_PATHS_BATCH_MAX); // a caller's own value: what the host's bound on n_items leaves room for
-  PersistArgs pa{work_counter, rec, ray_counters, lbuf, spp, chunk, n_items, nblocks * 64u, rpt_fold_ring_slots(fr.max_bounces),
-                 batch, park ? paths_park_off(lds_bytes) : 0xffffffffu, lay};
-  if (park) lds_bytes = paths_park_off(lds_bytes) + RPT_PATHS_PARK_LDS;
-  void* args[] = {(void*)&sc, (void*)&fr, (void*)&cam, (void*)&pa}; // rpt_paths(Scene, Frame, Camera, PersistArgs)
-  (void)hipLaunchKernel(paths_kernel(flat ? &lay : nullptr, park), dim3(nblocks), dim3(64), args, lds_bytes, st);
-}
+// paths_kernel, paths_max_blocks_per_cu, launch_paths: kernels/launch_paths.inc, shared with the views' translation unit
+#define RPT_PATHS_VIEWS 0
+#include "launch_paths.inc"
+#undef RPT_PATHS_VIEWS
 void launch_sum_samples(hipStream_t st, const Frame& fr, const double* lbuf, uint32_t spp, bool first) {
   hipLaunchKernelGGL(rpt_sum_samples, grid_for(fr.npix), dim3(256), 0, st, fr, lbuf, spp, first ? 1 : 0);
 }
@@ -410,5 +371,6 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_first_hits, launch_hits_store, launch_views_aov_fold,
                            launch_raygen_views_seeded, launch_shade_seeded,
                            launch_denoise_views_prepare, launch_denoise_views_level, launch_denoise_views_finish,
-                           launch_vertices_store, launch_vertices_fold};
+                           launch_vertices_store, launch_vertices_fold,
+                           RPT_NS_VIEWS::paths_max_blocks_per_cu, RPT_NS_VIEWS::launch_paths, RPT_NS_VIEWS::launch_views_ids};
 #endif // !__HIP_DEVICE_COMPILE__

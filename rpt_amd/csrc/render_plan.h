@@ -198,6 +198,43 @@ inline uint64_t views_piece_len(uint64_t base, uint64_t n, uint64_t npix, uint64
   return m;
 }
 
+// ---- rptgpu_render_views under RPT_FLAG_VIEWS_PERSISTENT: a piece's m indices are the "pixels" of rpt_paths_views'
+// launches (kernels/paths_views.inc), a launch of spp samples in items of `chunk` samples of one index.  The kernel's work
+// counter has 32 bits, and beside the launch's items it counts the dead claims past the end (kernels/paths.inc fetch_item:
+// per one-wave block at most 64 askers and one last claim of at most batch_max items), so a launch needs
+//   work_items(m, spp, chunk) + nblocks * (64 + batch_max) <= 2^32 - 1          (tests/cpp/views_items_check.cpp)
+constexpr uint64_t VIEWS_COUNTER_MAX = 0xffffffffull;
+inline uint64_t views_dead_room(uint32_t nblocks, uint32_t batch_max) { return (uint64_t)nblocks * (64ull + batch_max); }
+struct ViewsItems {
+  uint64_t m;       // the piece's length, capped so that the launch fits the counter; 0: not even one index fits
+  uint64_t n_items; // work items of a launch over m indices
+  bool capped;      // m is less than was asked for
+};
+inline ViewsItems views_items(uint64_t m, uint32_t spp, uint32_t chunk, uint32_t nblocks, uint32_t batch_max) {
+  ViewsItems vi{};
+  chunk = std::max(1u, chunk);
+  const uint64_t per_index = ((uint64_t)spp + chunk - 1) / chunk, room = views_dead_room(nblocks, batch_max);
+  const uint64_t fit = room >= VIEWS_COUNTER_MAX || !per_index ? 0 : (VIEWS_COUNTER_MAX - room) / per_index;
+  vi.m = std::min(m, std::min<uint64_t>(fit, 0xffffffffull)); // (Frame::npix has 32 bits)
+  vi.capped = vi.m < m;
+  vi.n_items = vi.m * per_index;
+  return vi;
+}
+// item i of a launch over m indices (fetch_item's arithmetic): its index of the piece and its samples [s_first, s_end)
+struct ViewsItem { uint64_t index; uint32_t s_first, s_end; };
+inline ViewsItem views_item(uint64_t item, uint64_t m, uint32_t spp, uint32_t chunk) {
+  const uint64_t c = item / m;
+  const uint32_t s_first = (uint32_t)(c * chunk);
+  return ViewsItem{item - c * m, s_first, (uint32_t)std::min<uint64_t>((uint64_t)s_first + chunk, spp)};
+}
+// index i of the piece that starts at the call's index j_base: its view and its pixel there (rpt_views_ids' arithmetic;
+// view_local: counted from the piece's first view, ViewRays::view_of)
+struct ViewsIndex { uint64_t view; uint32_t pixel, view_local; };
+inline ViewsIndex views_index(uint64_t j_base, uint64_t i, uint64_t npix_view) {
+  const uint64_t j = j_base + i, v = j / npix_view;
+  return ViewsIndex{v, (uint32_t)(j - v * npix_view), (uint32_t)(v - j_base / npix_view)};
+}
+
 // ---- rptgpu_occluded / rptgpu_bake_ao: one visibility query per pass over rays laid into the workspace's slots, so a pass
 // holds at most pass_target rays (plan_pass's target for the scene with ONE record column per path: no depth follows),
 // never more than RPT_MAX_PATHS_PER_PASS (32-bit slots) and never more than OCCLUSION_PIECE_MAX (a host caller stages 56 B

@@ -49,6 +49,9 @@ pub mod ffi {
     pub const RPT_FLAG_WAVEFRONT: u32 = 2;
     pub const RPT_FLAG_GENERAL_TRAVERSAL: u32 = 4;
     pub const RPT_FLAG_PERSISTENT: u32 = 8;
+    /// include/rpt_gpu_views_persistent.h: in `RptViewQuery::flags` of `rptgpu_render_views[_seeded][_device]`, run the batch
+    /// in the persistent path kernel (read where `rptgpu_views_persistent_supported` exists and returns 1)
+    pub const RPT_FLAG_VIEWS_PERSISTENT: u32 = 16;
     pub const RPT_COLLECTIVE_DEFAULT: u32 = 0;
     pub const RPT_COLLECTIVE_GATHER: u32 = 1;
     pub const RPT_COLLECTIVE_REDUCE: u32 = 2;
@@ -521,6 +524,12 @@ pub mod ffi {
     extern "C" {
         pub fn rptgpu_render_views_denoised(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, d: *const RptViewDenoise, out: *const RptViewDenoiseOut) -> c_int;
         pub fn rptgpu_render_views_denoised_device(h: *mut rptgpu_scene, n_views: u64, views: *const RptView, q: *const RptViewQuery, seeds: *const u64, d: *const RptViewDenoise, d_out: *const RptViewDenoiseOut, stream: *mut c_void) -> c_int;
+    }
+
+    // include/rpt_gpu_views_persistent.h: RPT_FLAG_VIEWS_PERSISTENT's detection — an optional addition within ABI 7 (a library
+    // without it ignores the flag and is detected with dlsym("rptgpu_views_persistent_supported"); this crate links it like the rest)
+    extern "C" {
+        pub fn rptgpu_views_persistent_supported() -> c_int;
     }
 
     // include/rpt_gpu_vertices.h: the vertices of the paths rptgpu_trace_rays runs — optional additions within ABI 7 (a
