@@ -5,7 +5,9 @@ RGB is rptgpu_trace_rays' output (and, one sample of the oracle's own camera ray
 exported factors in numpy is RGB; every vertex is rptgpu_first_hits of the ray that ends there, and that ray starts where the
 vertex before it lies; rptgpu_trace_rays continued from a vertex with the stream at the exported draw returns the suffix of
 the fold.  The rays are test_gpu_trace_rays' — the oracle's camera rays at that file's sizes, so the paths are a real
-frame's —, at the scenes' own max_bounces, 3 samples from sample index 5."""
+frame's —, at the scenes' own max_bounces, 3 samples from sample index 5.
+(Restated device calls cannot see a factor that every one of them multiplies by a zero suffix, nor a draw counter that is off
+in all of them alike: tests/test_gpu_vertices_oracle.py holds the same vertices to the oracle's records and functions.)"""
 import functools
 
 import numpy as np
