@@ -707,16 +707,19 @@ class Renderer {
   // addition: path-traced radiance along rays of the caller's own making (rptgpu_trace_rays, include/rpt_gpu.h): light
   // probes, lightmap texels, other projections.  origins, dirs: xyz per ray, the directions unit vectors; -> rgb per ray,
   // the mean of num_samples paths of max_bounces bounces times 2^exposure_value.  Ray i draws from the stream (seed,
-  // streams[i] or i, sample) from draw first_draw on, whatever other rays the call holds.
+  // streams[i] or i, sample) from draw first_draw on, whatever other rays the call holds.  flags: RPT_FLAG_* of the query —
+  // RPT_FLAG_RAYS_PERSISTENT (include/rpt_gpu_rays_persistent.h) runs the rays, and bake_probes' probes, in the persistent
+  // path kernel, the same bits by another route, where rays_persistent_supported() says the library reads it.
+  static bool rays_persistent_supported() { return rptgpu_rays_persistent_supported() == 1; }
   std::vector<double> trace_rays(const std::vector<double>& origins, const std::vector<double>& dirs,
-                                 const std::vector<uint32_t>& streams = {}, uint32_t first_draw = 0) {
+                                 const std::vector<uint32_t>& streams = {}, uint32_t first_draw = 0, uint32_t flags = 0) {
     ensure_scene();
     const size_t n = origins.size() / 3;
     if (origins.size() != 3 * n || dirs.size() != 3 * n || (!streams.empty() && streams.size() != n))
       throw std::invalid_argument("trace_rays: origins and dirs hold xyz per ray, streams one id per ray");
     RptRayQuery q{};
     q.struct_size = sizeof(RptRayQuery); q.max_bounces = max_bounces_; q.iterations = num_samples_; q.first_draw = first_draw;
-    q.exposure_value = ev_; q.seed = seed_;
+    q.exposure_value = ev_; q.seed = seed_; q.flags = flags;
     std::vector<double> rgb(3 * n);
     check(rptgpu_trace_rays(handle_, n, origins.data(), dirs.data(), streams.empty() ? nullptr : streams.data(), &q, rgb.data()));
     return rgb;
@@ -725,9 +728,9 @@ class Renderer {
   // RPT_PROBE_SH9 -> 27 doubles per probe, [9][3]: the radiance around it in the spherical harmonics of bands 0-2;
   // RPT_PROBE_IRRADIANCE (normals: xyz per probe) -> rgb per probe, the irradiance of a surface there.  Each probe is
   // num_samples paths of max_bounces bounces drawn from the stream (seed, streams[i] or i, sample_index_base + k),
-  // whatever other probes the call holds.
+  // whatever other probes the call holds.  flags: as trace_rays' (RPT_FLAG_RAYS_PERSISTENT).
   std::vector<double> bake_probes(uint32_t kind, const std::vector<double>& positions, const std::vector<double>& normals = {},
-                                  const std::vector<uint32_t>& streams = {}, uint64_t sample_index_base = 0) {
+                                  const std::vector<uint32_t>& streams = {}, uint64_t sample_index_base = 0, uint32_t flags = 0) {
     ensure_scene();
     const size_t n = positions.size() / 3;
     const bool with_normals = kind == RPT_PROBE_IRRADIANCE;
@@ -735,7 +738,7 @@ class Renderer {
       throw std::invalid_argument("bake_probes: positions hold xyz per probe, normals too (RPT_PROBE_IRRADIANCE only), streams one id per probe");
     RptProbeQuery q{};
     q.struct_size = sizeof(RptProbeQuery); q.kind = kind; q.samples = num_samples_; q.max_bounces = max_bounces_;
-    q.seed = seed_; q.sample_index_base = sample_index_base;
+    q.seed = seed_; q.sample_index_base = sample_index_base; q.flags = flags;
     std::vector<double> out((kind == RPT_PROBE_SH9 ? 27 : 3) * n);
     check(rptgpu_bake_probes(handle_, n, positions.data(), with_normals ? normals.data() : nullptr,
                              streams.empty() ? nullptr : streams.data(), &q, out.data()));

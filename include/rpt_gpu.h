@@ -179,10 +179,15 @@ enum {
                                     With neither flag the library picks: wavefront when the scene has
                                     real kd-trees (depth >= 3: traversal latency dominates and wants
                                     occupancy), persistent otherwise.  Both give the same bits. */
-  RPT_FLAG_VIEWS_PERSISTENT = 16u /* RptViewQuery::flags of rptgpu_render_views[_seeded][_device] only: the batch of views
+  RPT_FLAG_VIEWS_PERSISTENT = 16u, /* RptViewQuery::flags of rptgpu_render_views[_seeded][_device] only: the batch of views
                                     in the persistent path kernel — an OPTIONAL addition within ABI 7, read only by a
                                     library that exports rptgpu_views_persistent_supported (rpt_gpu_views_persistent.h,
                                     included at the end of this file; a library without it ignores the bit) */
+  RPT_FLAG_RAYS_PERSISTENT = 32u /* RptRayQuery::flags of rptgpu_trace_rays[_device] and RptProbeQuery::flags of
+                                    rptgpu_bake_probes[_device] only: the call's paths in the persistent path kernel — an
+                                    OPTIONAL addition within ABI 7, read only by a library that exports
+                                    rptgpu_rays_persistent_supported (rpt_gpu_rays_persistent.h, included at the end of this
+                                    file; a library without it ignores the bit) */
 };
 
 /* ---- what Renderer carries into sample(): src/renderer.rs:18-42 + the call argument ----
@@ -474,9 +479,11 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
  * call into pieces and passes, or on how a caller splits a batch over calls, handles or GPUs.  With the rays a camera
  * makes (pixel p's ray of sample s, streams[i] = p, first_draw = the draws the camera took: 2, more under a lens) the
  * result is the frame of rptgpu_render_batch, bit for bit.
- * The call always runs the wavefront pipeline (flat scenes are walked in-kernel, deep trees through the per-tree
- * queries), sized and restarted like a render's passes; RPT_FLAG_GENERAL_TRAVERSAL and RPT_FLAG_PROFILE_KERNELS are
- * honoured, RPT_FLAG_WAVEFRONT changes nothing, and RptStats advances as for a render (samples = n * iterations).
+ * The call runs the wavefront pipeline (flat scenes are walked in-kernel, deep trees through the per-tree queries), sized
+ * and restarted like a render's passes; RPT_FLAG_GENERAL_TRAVERSAL and RPT_FLAG_PROFILE_KERNELS are honoured,
+ * RPT_FLAG_WAVEFRONT changes nothing, and RptStats advances as for a render (samples = n * iterations).  The one exception:
+ * a library with rpt_gpu_rays_persistent.h (included at the end of this file) runs the persistent kernel instead when it is
+ * asked to with RPT_FLAG_RAYS_PERSISTENT.
  * RPTGPU_RAYS_PIECE (environment, read per call; tests): the rays per piece.
  * RPTGPU_E_INVALID_ARGUMENT, checked before any device work and with a detail naming the reason: a NULL RptRayQuery, a
  * wrong struct_size, iterations == 0, max_bounces > 254, a precision_mode other than RPT_PRECISION_F64_STRICT,
@@ -1034,6 +1041,8 @@ const char* rptgpu_kernel_name(int k);
 #include "rpt_gpu_vertices.h"
 /* ---- ... and a batch of views in the persistent path kernel, on request ---- */
 #include "rpt_gpu_views_persistent.h"
+/* ---- ... and caller-supplied rays and light probes in the persistent path kernel, on request ---- */
+#include "rpt_gpu_rays_persistent.h"
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,7 @@ RPT_FLAG_WAVEFRONT = 2
 RPT_FLAG_GENERAL_TRAVERSAL = 4
 RPT_FLAG_PERSISTENT = 8
 RPT_FLAG_VIEWS_PERSISTENT = 16  # include/rpt_gpu_views_persistent.h: RptViewQuery.flags of render_views (views_persistent_supported())
+RPT_FLAG_RAYS_PERSISTENT = 32  # include/rpt_gpu_rays_persistent.h: RptRayQuery.flags of trace_rays, RptProbeQuery.flags of bake_probes (rays_persistent_supported())
 RPT_K_RAYGEN, RPT_K_EXTEND, RPT_K_SHADE, RPT_K_SHADOW, RPT_K_RESOLVE, RPT_K_PATHS, RPT_K_TREE_TRACE, RPT_K_TREE_SORT = range(8)
 RPT_K_COUNT = 8
 RPT_PARTICLES_SOLID_GRAVITY, RPT_PARTICLES_MARBLES, RPT_PARTICLES_CIRCLE = range(3)
@@ -356,6 +357,12 @@ VERTICES_SYMBOLS = [
 VIEWS_PERSISTENT_SYMBOLS = [
     ("rptgpu_views_persistent_supported", C.c_int, []),
 ]
+# ... and the symbol include/rpt_gpu_rays_persistent.h declares, optional in the same way: a library without it ignores
+# RPT_FLAG_RAYS_PERSISTENT and runs the wavefront pipeline (rays_persistent_supported) — and load_library tolerates such a
+# library (an older build, for a comparison)
+RAYS_PERSISTENT_SYMBOLS = [
+    ("rptgpu_rays_persistent_supported", C.c_int, []),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -384,6 +391,13 @@ def load_library(path=None):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
+    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS:
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_persistent_supported() says no)
+        fn.restype = restype
+        fn.argtypes = argtypes
     if lib.rptgpu_abi_version() != ABI_VERSION:
         raise ImportError("rpt_amd: ABI version mismatch")
     if path is None:
@@ -397,6 +411,18 @@ def views_persistent_supported(lib=None):
     lib = lib or load_library()
     try:
         fn = lib.rptgpu_views_persistent_supported
+    except AttributeError:
+        return False
+    fn.restype, fn.argtypes = C.c_int, []
+    return fn() == 1
+
+
+def rays_persistent_supported(lib=None):
+    """Does the library read RPT_FLAG_RAYS_PERSISTENT (include/rpt_gpu_rays_persistent.h)?  Detected by symbol, as a C
+    caller does with dlsym: a library without it is still ABI 7, ignores the bit and runs the wavefront pipeline."""
+    lib = lib or load_library()
+    try:
+        fn = lib.rptgpu_rays_persistent_supported
     except AttributeError:
         return False
     fn.restype, fn.argtypes = C.c_int, []

@@ -392,6 +392,9 @@ struct RaySource {
   // view_of the view of each index of the piece counted from the piece's first (rpt_views_ids wrote it, and the pixels
   // into the piece's Frame::pixels)
   const uint32_t* view_of = nullptr;
+  // ... or a piece of the caller's rays or probes in the persistent kernel (render_persistent -> rpt_paths_rays,
+  // RPT_FLAG_RAYS_PERSISTENT): origins, dirs, first_draw, probe and probe_scale as above with cam and views null; the piece's
+  // Frame::pixels holds the stream ids already (the caller's, or rpt_rays_ids'), and ids_out and id_base are not read
   // rptgpu_trace_vertices (api_vertices.cpp): where the vertices of the piece's paths go — the caller's arrays or their
   // staging, offset to the piece; run_pass fills in s_first per pass.  nullptr (every other call): nothing is launched for it
   const rptdev::VertexOut* vertices = nullptr;
@@ -415,14 +418,21 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
 const char* bad_probe_query(const RptProbeQuery* q);
+// the piece of a call of rptgpu_trace_rays / rptgpu_bake_probes under RPT_FLAG_RAYS_PERSISTENT: `piece` (rptplan::rays_piece's)
+// capped by the persistent kernel's work counter at the most resident blocks any instantiation has
+inline uint64_t handle_rays_persistent_piece(const rptgpu_scene* h, uint64_t piece, uint32_t iterations) {
+  const uint32_t blocks_max = (uint32_t)std::max(1, h->num_cus) * RPT_PATHS_WAVES_PER_CU_MAX;
+  return rptplan::rays_persistent_piece(piece, iterations, blocks_max, RPT_PATHS_BATCH_MAX);
+}
 // the pass planner's input for a call over npix pixels or rays: what its passes share, and the device's state right now
 rptplan::PassInput pass_input(rptgpu_scene* h, uint32_t npix, uint32_t iterations);
 void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in);
 // the wavefront driver: the batch in passes from `src`, then rpt_finish into `out` (api_render.cpp)
 void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const RaySource& src,
                       void* out, bool out_f32, bool packed, bool prof);
-// the persistent driver: the batch in launches of rpt_paths (src.cam) or rpt_paths_views (src.views), rpt_sum_samples behind
-// each, then rpt_finish into `out` (api_render.cpp)
+// the persistent driver: the batch in launches of rpt_paths (src.cam), rpt_paths_views (src.views) or rpt_paths_rays
+// (src.origins alone), rpt_sum_samples behind each, then rpt_finish into `out` — probes (src.probe >= 0): rpt_project_probes
+// and rpt_finish_probes in their places (api_render.cpp)
 void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const RaySource& src,
                        void* out, bool out_f32, bool packed, bool prof);
 // packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list.

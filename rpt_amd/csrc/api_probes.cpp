@@ -5,6 +5,9 @@
 // rpt_raygen_probes draws the directions (RaySource::probe), rpt_resolve_probes projects the paths' radiance into the
 // piece's running sums and rpt_finish_probes scales them into the caller's layout.  The depth loop, the pass planning with
 // its restarts and the piece arithmetic (rptplan::rays_piece) are the ray call's, unchanged.
+// Under RPT_FLAG_RAYS_PERSISTENT (include/rpt_gpu_rays_persistent.h) the same pieces go through the persistent
+// driver instead: rpt_paths_rays draws each direction where it hands out its work, rpt_project_probes adds a launch's samples
+// to the sums with rpt_resolve_probes' expressions, and rpt_finish_probes is the one above.  The same bits.
 #include "api_internal.h"
 
 namespace rptapi {
@@ -20,6 +23,8 @@ const char* bad_probe_query(const RptProbeQuery* q) {
   if (q->flags & RPT_FLAG_PERSISTENT)
     return "RptProbeQuery: RPT_FLAG_PERSISTENT — the persistent kernel makes its rays from a camera; light probes run the "
            "wavefront pipeline only";
+  if ((q->flags & RPT_FLAG_RAYS_PERSISTENT) && (q->flags & RPT_FLAG_WAVEFRONT))
+    return "RptProbeQuery: RPT_FLAG_RAYS_PERSISTENT | RPT_FLAG_WAVEFRONT — the two flags name different routes";
   return nullptr;
 }
 
@@ -63,7 +68,11 @@ int bake_probes(rptgpu_scene* h, uint64_t n, const double* positions, const doub
     pass_input_now(h, in);
     uint64_t asked = 0; // tests: pieces of a few probes
     if (const char* e = std::getenv("RPTGPU_PROBES_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    const uint64_t piece = rptplan::rays_piece(n, asked, rptplan::plan_pass(in).target);
+    uint64_t piece = rptplan::rays_piece(n, asked, rptplan::plan_pass(in).target);
+    // the persistent kernel on request, as in api_rays.cpp: not for a scene only the wavefront pipeline walks, and in
+    // pieces a launch's work counter holds
+    const bool persistent = (q->flags & RPT_FLAG_RAYS_PERSISTENT) && !use_wavefront(h, 0, false);
+    if (persistent) piece = handle_rays_persistent_piece(h, piece, q->samples);
     h->accum.alloc((uint64_t)width * piece);
     if (!on_device) {
       h->rays_o.alloc(3 * piece);
@@ -88,14 +97,19 @@ int bake_probes(rptgpu_scene* h, uint64_t n, const double* positions, const doub
       fr.max_bounces = q->max_bounces; fr.seed = q->seed; fr.accum = h->accum.p;
       RaySource src{nullptr, d_pos, d_nrm, 0u, (uint32_t)base, streams ? nullptr : h->ray_ids.p};
       src.probe = (int)q->kind; src.probe_scale = scale;
-      render_wavefront(h, kt, p, fr, src, d_out, false, true, prof);
+      if (persistent) { // (the ids the wavefront's first step would write: the kernel reads them from the first launch on)
+        if (!streams) kt->rays_ids(st, (uint32_t)base, (uint32_t)m, h->ray_ids.p);
+        render_persistent(h, kt, p, fr, src, d_out, false, true, prof);
+      } else {
+        render_wavefront(h, kt, p, fr, src, d_out, false, true, prof);
+      }
       HIP_TRY(hipGetLastError());
       if (!on_device) { // the staging arrays are the next piece's, too
         HIP_TRY(hipMemcpyAsync(out + (uint64_t)width * base, d_out, (uint64_t)width * m * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
-    return drain_call(h, h->has_deep && h->gen_overflow.p);
+    return drain_call(h, !persistent && h->has_deep && h->gen_overflow.p);
   });
   if (rc != RPTGPU_OK) return rc;
   h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

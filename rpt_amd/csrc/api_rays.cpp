@@ -3,6 +3,9 @@
 // the "frame" of its own passes, its rays are the pixels, rpt_raygen_rays is the passes' first step (RaySource) and
 // everything behind it — the depth loop, the pass planning with its restarts, rpt_resolve, rpt_finish in packed form —
 // is a render's.  A host caller's piece is staged in arrays the handle keeps; a device caller's is read where it lies.
+// Under RPT_FLAG_RAYS_PERSISTENT (include/rpt_gpu_rays_persistent.h) the same pieces, staged the same way,
+// go through the persistent driver instead: rpt_paths_rays reads each ray where it hands out its work, and rpt_sum_samples
+// and the packed rpt_finish behind its launches are a render's.  The same bits.
 #include "api_internal.h"
 
 namespace rptapi {
@@ -17,6 +20,8 @@ const char* bad_ray_query(const RptRayQuery* q) {
   if (q->flags & RPT_FLAG_PERSISTENT)
     return "RptRayQuery: RPT_FLAG_PERSISTENT — the persistent kernel makes its rays from a camera; caller-supplied rays run "
            "the wavefront pipeline only";
+  if ((q->flags & RPT_FLAG_RAYS_PERSISTENT) && (q->flags & RPT_FLAG_WAVEFRONT))
+    return "RptRayQuery: RPT_FLAG_RAYS_PERSISTENT | RPT_FLAG_WAVEFRONT — the two flags name different routes";
   return nullptr;
 }
 
@@ -55,7 +60,12 @@ int trace_rays(rptgpu_scene* h, uint64_t n, const double* origins, const double*
     pass_input_now(h, in);
     uint64_t asked = 0; // tests: pieces of a few rays
     if (const char* e = std::getenv("RPTGPU_RAYS_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    const uint64_t piece = rptplan::rays_piece(n, asked, rptplan::plan_pass(in).target);
+    uint64_t piece = rptplan::rays_piece(n, asked, rptplan::plan_pass(in).target);
+    // the persistent kernel on request — unless the scene has a group with tree children, which only the wavefront
+    // pipeline walks (use_wavefront: such a scene cannot honour the request, as for a render); a piece is then also at
+    // most what a launch's work counter holds
+    const bool persistent = (q->flags & RPT_FLAG_RAYS_PERSISTENT) && !use_wavefront(h, 0, false);
+    if (persistent) piece = handle_rays_persistent_piece(h, piece, q->iterations);
     h->accum.alloc(3 * piece);
     if (!on_device) { h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece); h->rays_out.alloc(3 * piece); }
     if (!on_device || !streams) h->ray_ids.alloc(piece);
@@ -74,14 +84,19 @@ int trace_rays(rptgpu_scene* h, uint64_t n, const double* origins, const double*
       fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = d_ids;
       fr.max_bounces = q->max_bounces; fr.seed = q->seed; fr.accum = h->accum.p;
       const RaySource src{nullptr, d_o, d_d, q->first_draw, (uint32_t)base, streams ? nullptr : h->ray_ids.p};
-      render_wavefront(h, kt, p, fr, src, d_out, false, true, prof);
+      if (persistent) { // (the ids the wavefront's first step would write: the kernel reads them from the first launch on)
+        if (!streams) kt->rays_ids(st, (uint32_t)base, (uint32_t)m, h->ray_ids.p);
+        render_persistent(h, kt, p, fr, src, d_out, false, true, prof);
+      } else {
+        render_wavefront(h, kt, p, fr, src, d_out, false, true, prof);
+      }
       HIP_TRY(hipGetLastError());
       if (!on_device) { // the staging arrays are the next piece's, too
         HIP_TRY(hipMemcpyAsync(out + 3 * base, d_out, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
-    return drain_call(h, h->has_deep && h->gen_overflow.p);
+    return drain_call(h, !persistent && h->has_deep && h->gen_overflow.p);
   });
   if (rc != RPTGPU_OK) return rc;
   h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -103,5 +118,7 @@ int rptgpu_trace_rays_device(rptgpu_scene* h, uint64_t n, const void* d_origins,
   return trace_rays(h, n, (const double*)d_origins, (const double*)d_dirs, (const uint32_t*)d_streams, q, (double*)d_out_rgb, true,
                     (hipStream_t)stream);
 }
+
+int rptgpu_rays_persistent_supported(void) { return 1; }
 
 } // extern "C"

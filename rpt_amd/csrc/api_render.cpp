@@ -318,12 +318,20 @@ rptdev::PathState path_state(rptgpu_scene* h) {
 // the default pipeline: one persistent kernel, the whole path in registers; the batch runs as launches of at most
 // spp_l samples per pixel (rptplan::plan_persistent).  The rays are src's: a camera's pixels (src.cam: rpt_paths), or a
 // piece of a batch of views (src.views with view_seeds and view_of: rpt_paths_views — fr is the piece's, its pixels
-// rpt_views_ids' — api_views.cpp)
+// rpt_views_ids' — api_views.cpp), or a piece of the caller's rays or light probes (src.origins with cam and views null:
+// rpt_paths_rays — fr is the piece's, its pixels the stream ids; probes, src.probe >= 0, project each launch's samples into
+// the piece's running sums with rpt_project_probes where rpt_sum_samples stands and end with rpt_finish_probes —
+// api_rays.cpp, api_probes.cpp)
 void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr,
                        const RaySource& src, void* out, bool out_f32, bool packed, bool prof) {
   hipStream_t st = h->stream;
   const uint32_t npix = fr.npix;
   const bool views = src.views != nullptr;
+  const bool rays = !views && !src.cam && src.origins != nullptr; // (probes too: src.probe >= 0)
+  const bool probes = rays && src.probe >= 0;
+  const rptdev::CallerRays cr{src.origins, src.dirs, src.first_draw, probes ? (int32_t)src.probe : -1};
+  const char* const kname = views ? "rpt_paths_views" : rays ? "rpt_paths_rays" : "rpt_paths";
+  const auto max_blocks = views ? kt->paths_views_max_blocks_per_cu : rays ? kt->paths_rays_max_blocks_per_cu : kt->paths_max_blocks_per_cu;
   rptdev::ViewRays vr{};
   if (views) {
     const uint64_t v0 = src.view_base / ((uint64_t)src.view_width * src.view_height); // the piece's first view
@@ -337,8 +345,8 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   const uint32_t flat_lds = lay.off_end;
   // the fused kernel's pre-trace pass: this render's screen rectangles of the objects it may skip (host_scene.cpp
   // pinhole_screen_rect; none under a lens).  An object without a rectangle is always tested.  A piece of views gets none
-  // (cull_n = 0: every test runs — the rectangles are one camera's)
-  if (RPT_PRETRACE_CULL && lay.pretrace_cull && !views) {
+  // (cull_n = 0: every test runs — the rectangles are one camera's), and so does a piece of the caller's rays
+  if (RPT_PRETRACE_CULL && lay.pretrace_cull && !views && !rays) {
     const rptdev::Camera& cam = *src.cam;
     for (size_t i = 0; i < h->obj_geom.size() && i < 64 && lay.cull_n < (uint32_t)RPT_CULL_MAX; i++) {
       uint32_t r[4];
@@ -353,21 +361,22 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
     }
   }
   const rptplan::PersistentPlan pl = rptplan::plan_persistent(
-      npix, p.iterations, p.max_bounces, h->num_cus, (views ? kt->paths_views_max_blocks_per_cu : kt->paths_max_blocks_per_cu)(flat ? &lay : nullptr, flat_lds, false),
+      npix, p.iterations, p.max_bounces, h->num_cus, max_blocks(flat ? &lay : nullptr, flat_lds, false),
       h->opt.lbuf_bytes, lbuf_held, free_b, h->opt.paths_chunk, h->all_flat, h->dscene.force_general, h->flat_layout.obj_filter);
   // a texture environment: the lanes park their lookups in what the wave's LDS share has left (kernels/paths.inc) —
   // unless that costs a resident wave (a flat scene that fills the share)
   bool park = flat && h->opt.env_park != 0 && h->dscene.env_kind != RPT_ENV_COLOR; // (flat scenes: rpt_paths<KdLds>'s stack fills the share)
-  if (park && (views ? kt->paths_views_max_blocks_per_cu : kt->paths_max_blocks_per_cu)(&lay, flat_lds, true) < pl.per_cu) park = false;
-  // (a piece of views: render_views cut it so that every launch fits the work counter — rptplan::views_items)
-  if (views && rptplan::views_items(npix, pl.spp_l, pl.chunk, pl.nblocks, RPT_PATHS_BATCH_MAX).capped)
-    throw std::runtime_error("rpt_paths_views: the piece's work items do not fit the 32-bit work counter (internal error)");
+  if (park && max_blocks(&lay, flat_lds, true) < pl.per_cu) park = false;
+  // (a piece of views: render_views cut it so that every launch fits the work counter — rptplan::views_items; a piece of
+  // rays or probes: api_rays.cpp / api_probes.cpp, in the same way — rptplan::rays_persistent_piece)
+  if ((views || rays) && rptplan::views_items(npix, pl.spp_l, pl.chunk, pl.nblocks, RPT_PATHS_BATCH_MAX).capped)
+    throw std::runtime_error(std::string(kname) + ": the piece's work items do not fit the 32-bit work counter (internal error)");
   h->prec.alloc((uint64_t)rpt_fold_ring_slots(p.max_bounces) * rptdev::REC_FIELDS * ((uint64_t)pl.nblocks * 64));
   h->lbuf.alloc(std::max<uint64_t>(1, (uint64_t)pl.spp_l * 3 * npix));
   if (print_launch)
     std::fprintf(stderr, "%s<%s>: %d blocks/CU x %d CUs -> %u blocks, %u samples per work item, %u launch(es) of %u spp, "
                  "dynamic LDS %u B per wave (the flat scene's tables)%s%s%s%s\n",
-                 views ? "rpt_paths_views" : "rpt_paths", flat ? (lay.obj_filter ? "KdFlatF" : lay.n_tris ? "KdFlat" : "KdFlatG") : "KdLds", pl.per_cu, h->num_cus, pl.nblocks,
+                 kname, flat ? (lay.obj_filter ? "KdFlatF" : lay.n_tris ? "KdFlat" : "KdFlatG") : "KdLds", pl.per_cu, h->num_cus, pl.nblocks,
                  pl.chunk, pl.n_launch, pl.spp_l, flat_lds, park ? " + parked environment lookups" : "",
                  flat && lay.n_tris && lay.fuse_query && !park ? ", shadow and bounce rays in one query" : "",
                  flat && lay.n_tris && lay.fuse_query && !park && lay.scene_consts ? ", a hit's scene constants from the wave's tables" : "",
@@ -375,6 +384,8 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   h->counters.alloc(4);
   h->pcounters.alloc(16);
   HIP_TRY(hipMemsetAsync(h->pcounters.p, 0, 16 * sizeof(unsigned long long), st));
+  // probes: the piece's running sums start at zero, as render_wavefront starts them (rpt_project_probes continues them)
+  if (probes) HIP_TRY(hipMemsetAsync(h->accum.p, 0, (uint64_t)npix * probe_width((uint32_t)src.probe) * sizeof(double), st));
   for (uint32_t s0 = 0; s0 < p.iterations; s0 += pl.spp_l) {
     const uint32_t spp = std::min(pl.spp_l, p.iterations - s0);
     const uint64_t items = rptplan::work_items(npix, spp, pl.chunk);
@@ -384,11 +395,15 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
       if (views)
         kt->paths_views(st, h->dscene, fr, vr, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
                         pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
+      else if (rays)
+        kt->paths_rays(st, h->dscene, fr, cr, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
+                       pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
       else
         kt->paths(st, h->dscene, fr, *src.cam, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
                   pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
       b.done(); }
-    kt->sum_samples(st, fr, h->lbuf.p, spp, s0 == 0);
+    if (probes) kt->project_probes(st, fr, h->lbuf.p, spp, (uint32_t)src.probe);
+    else kt->sum_samples(st, fr, h->lbuf.p, spp, s0 == 0);
     if (print_launch) { // diagnostics: where the 32-bit work counter ended (kernels/paths.inc fetch_item)
       uint32_t ended = 0;
       HIP_TRY(hipMemcpyAsync(&ended, h->counters.p, sizeof ended, hipMemcpyDeviceToHost, st));
@@ -401,11 +416,12 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
     }
   }
   HIP_TRY(hipGetLastError());
-  kt->finish(st, fr, (double)p.iterations, std::pow(2.0, p.exposure_value), out, out_f32, packed);
+  if (probes) kt->finish_probes(st, fr, probe_width((uint32_t)src.probe), src.probe_scale, (double*)out);
+  else kt->finish(st, fr, (double)p.iterations, std::pow(2.0, p.exposure_value), out, out_f32, packed);
   unsigned long long rc[16] = {0};
   HIP_TRY(hipMemcpyAsync(rc, h->pcounters.p, sizeof rc, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  if (std::getenv("RPTGPU_PRINT_PHASES")) print_prof(kt, "rpt_paths");
+  if (std::getenv("RPTGPU_PRINT_PHASES")) print_prof(kt, kname);
   h->stats.samples += (uint64_t)npix * p.iterations;
   h->stats.extend_rays += rc[0];
   h->stats.shadow_rays += rc[1];

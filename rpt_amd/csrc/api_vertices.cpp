@@ -32,6 +32,9 @@ const char* bad_vertex_query(const RptVertexQuery* q) {
   if (q->flags & RPT_FLAG_PERSISTENT)
     return "RptVertexQuery: RPT_FLAG_PERSISTENT — the persistent kernel keeps a path in registers and leaves no vertices behind; "
            "path vertices run the wavefront pipeline only";
+  if (q->flags & RPT_FLAG_RAYS_PERSISTENT)
+    return "RptVertexQuery: RPT_FLAG_RAYS_PERSISTENT — only rptgpu_trace_rays, rptgpu_bake_probes and their _device forms run "
+           "in the persistent kernel, which leaves no vertices behind";
   if (!q->channels) return "RptVertexQuery: channels == 0 (name at least one RPT_VERTEX_* channel)";
   if (q->channels & ~VERTEX_ALL) return "RptVertexQuery: channels names an unknown RPT_VERTEX_* bit";
   if (q->reserved) return "RptVertexQuery: reserved != 0";

@@ -167,6 +167,17 @@ struct ViewRays {
   const uint32_t* view_of; // [Frame::npix]
   uint32_t width, height;  // of every view
 };
+// where rpt_paths_rays' rays come from (kernels/paths_rays.inc; rptgpu_trace_rays and rptgpu_bake_probes under
+// RPT_FLAG_RAYS_PERSISTENT): a piece of the caller's rays or probes, its arrays [Frame::npix][3] f64 already offset to the
+// piece.  kind < 0: rays — origins and dirs as given, the stream standing at draw first_draw; kind = RPT_PROBE_*: probes —
+// origins the positions, dirs the normals (read for RPT_PROBE_IRRADIANCE only), the direction drawn from draw 0 on.  The
+// stream id of index i is Frame::pixels[i] (the caller's, or rpt_rays_ids')
+struct CallerRays {
+  const double* origins;
+  const double* dirs;
+  uint32_t first_draw;
+  int32_t kind;
+};
 
 // Per-pass wavefront state, SoA over path slots (slot = s_local * npix + pixel_local).
 // REC_FIELDS doubles per depth record: A[3], f[3], 1/pdf, |wi.n|  (the nested clamp of

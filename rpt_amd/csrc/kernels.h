@@ -262,6 +262,17 @@ struct KernelTable {
                       double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk, uint32_t n_items,
                       uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);
   void (*views_ids)(hipStream_t, uint64_t j_base, uint64_t npix_view, uint32_t n, uint32_t* pixels, uint32_t* view_of);
+  // the caller's rays and light probes in the persistent kernel (rpt_paths_rays, kernels/paths_rays.inc; compiled in a
+  // translation unit of its own, kernels_rays_strict[_ext].hip): paths_max_blocks_per_cu and paths for the SAME instantiation
+  // of that kernel, the rays a piece's CallerRays.  rays_ids: ids[i] = id_base + i for the piece's n indices (a caller
+  // without stream ids).  project_probes: a launch's samples (lbuf, [spp][3][npix] as rpt_paths writes it) into the probes'
+  // running sums (fr.accum, [27 or 3][npix]: resolve_probes' sums, finish_probes behind the last launch)
+  int (*paths_rays_max_blocks_per_cu)(const FlatLayout* flat, uint32_t lds_bytes, bool park);
+  void (*paths_rays)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::CallerRays&, uint32_t* work_counter,
+                     double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk, uint32_t n_items,
+                     uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);
+  void (*rays_ids)(hipStream_t, uint32_t id_base, uint32_t n, uint32_t* ids);
+  void (*project_probes)(hipStream_t, const rptdev::Frame&, const double* lbuf, uint32_t spp, uint32_t kind);
 };
 // the views' translation units: what the tables above point to
 #define RPT_VIEWS_TU_DECLS(NS)                                                                                                    \
@@ -275,6 +286,19 @@ struct KernelTable {
 RPT_VIEWS_TU_DECLS(rpt_strict_views)
 RPT_VIEWS_TU_DECLS(rpt_strict_ext_views)
 #undef RPT_VIEWS_TU_DECLS
+// ... and the rays' translation units
+#define RPT_RAYS_TU_DECLS(NS)                                                                                                     \
+  namespace NS {                                                                                                                  \
+  int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool park);                                             \
+  void launch_paths(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::CallerRays&, uint32_t* work_counter,   \
+                    double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk, uint32_t n_items,  \
+                    uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);           \
+  void launch_rays_ids(hipStream_t, uint32_t id_base, uint32_t n, uint32_t* ids);                                                 \
+  void launch_project_probes(hipStream_t, const rptdev::Frame&, const double* lbuf, uint32_t spp, uint32_t kind);                 \
+  }
+RPT_RAYS_TU_DECLS(rpt_strict_rays)
+RPT_RAYS_TU_DECLS(rpt_strict_ext_rays)
+#undef RPT_RAYS_TU_DECLS
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)
 // the same with the extended shape set (RPT_SHAPE_MONOMIAL, trees of trees) compiled in

@@ -17,8 +17,12 @@
 //     paths_flat.inc    the flat scenes' queries: flat_query, flat_query2 (two rays in one walk), flat_query_filtered
 //     paths_shade.inc   the fused form's draw-first shading: hit_draws, bsdf_opaque, sample_f_opaque, illuminate_mesh
 //     paths.inc         the kernel's contract, work hand-out, record ring, parked lookups, ray stash; rpt_sum_samples
-//     paths_loop.inc    the loop itself: one text, compiled as rpt_paths (paths.inc) and as rpt_paths_views (paths_views.inc)
+//     paths_loop.inc    the loop itself: one text, compiled as rpt_paths (paths.inc), as rpt_paths_views (paths_views.inc) and
+//                       as rpt_paths_rays (paths_rays.inc)
 //     paths_views.inc   rpt_paths_views, the kernel over a piece of a batch of views: its ids, camera ray and per-lane key
+//     paths_rays.inc    rpt_paths_rays, the kernel over a piece of the caller's rays or light probes: its ray; rpt_rays_ids,
+//                       rpt_project_probes
+//     probe_dir.inc     a light probe's direction and the SH9 basis, shared by both routes of rptgpu_bake_probes
 //   the wavefront pipeline — scenes with deep trees; rptgpu_trace_rays and rptgpu_bake_probes for any scene (flat ones
 //   query inside rpt_extend / rpt_shadow_rays) —: one kernel per step of a depth over SoA path state, in six files:
 //     wf_state.inc      access to the SoA path state and the depth records; the queue appends of a wave and of a block
@@ -50,7 +54,11 @@
 #include <cstring>
 #include <type_traits>
 
-#ifndef RPT_VIEWS_TU
+// a translation unit of one form of the persistent kernel alone (the views': RPT_VIEWS_TU; the caller's rays': RPT_RAYS_TU)
+#if defined(RPT_VIEWS_TU) || defined(RPT_RAYS_TU)
+#define RPT_FORM_TU 1
+#endif
+#ifndef RPT_FORM_TU
 #include <rocprim/device/device_radix_sort.hpp>
 #endif
 
@@ -69,6 +77,11 @@ using namespace rptdev;
 #define RPT_CAT2_(a, b) a##b
 #define RPT_CAT2(a, b) RPT_CAT2_(a, b)
 #define RPT_NS_VIEWS RPT_CAT2(RPT_NS, _views)
+#define RPT_NS_RAYS RPT_CAT2(RPT_NS, _rays) // ... and of its rays' translation unit
+// the forms of the persistent kernel's loop (kernels/paths_loop.inc, RPT_PATHS_FORM): where a work item's ray comes from
+#define RPT_PATHS_FORM_CAMERA 0 // rpt_paths: a camera's pixels
+#define RPT_PATHS_FORM_VIEWS 1  // rpt_paths_views: a piece of a batch of views (paths_views.inc)
+#define RPT_PATHS_FORM_RAYS 2   // rpt_paths_rays: a piece of the caller's rays or light probes (paths_rays.inc)
 
 // Scene tables that a whole wave indexes uniformly (top-level instances, trees, lights) are read
 // through the CONSTANT address space: the scene is immutable while a kernel runs, and only then
@@ -106,7 +119,7 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/sampling.inc"
 #include "kernels/material.inc"
 #include "kernels/light.inc"
-#ifndef RPT_VIEWS_TU
+#ifndef RPT_FORM_TU
 #include "kernels/wf_state.inc"
 #include "kernels/wf_sort_key.inc"
 #include "kernels/tree_query.inc"
@@ -118,7 +131,12 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/paths_flat.inc"
 #include "kernels/paths_shade.inc"
 #include "kernels/paths.inc"
-#ifdef RPT_VIEWS_TU
+#if defined(RPT_RAYS_TU)
+// the rays' translation units (kernels_rays_strict[_ext].hip, RPT_NS = rpt_strict[_ext]_rays), in the same way: rpt_paths_rays,
+// rpt_rays_ids, rpt_project_probes and their launchers (DESIGN.md §13.1)
+#include "kernels/probe_dir.inc"
+#include "kernels/paths_rays.inc"
+#elif defined(RPT_VIEWS_TU)
 // the views' translation units (kernels_views_strict[_ext].hip, RPT_NS = rpt_strict[_ext]_views): what rpt_paths needs, then
 // rpt_paths_views, its instantiations and its launchers — and nothing else, so that the code objects of kernels_strict[_ext]
 // stay what they were (DESIGN.md §15.2)
@@ -138,6 +156,6 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/hits.inc"
 #include "kernels/wf_vertices.inc"
 #include "kernels/launch.inc"
-#endif // RPT_VIEWS_TU
+#endif // RPT_FORM_TU
 
 } // namespace RPT_NS

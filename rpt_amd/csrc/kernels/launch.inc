@@ -87,10 +87,11 @@ void launch_scatter_f32(hipStream_t st, const float* src, const uint32_t* pixels
   if (n) hipLaunchKernelGGL(rpt_scatter_f32, grid_for(n), dim3(256), 0, st, src, pixels, n, dst);
 }
 
-// paths_kernel, paths_max_blocks_per_cu, launch_paths: kernels/launch_paths.inc, shared with the views' translation unit
-#define RPT_PATHS_VIEWS 0
+// paths_kernel, paths_max_blocks_per_cu, launch_paths: kernels/launch_paths.inc, shared with the views' and the rays'
+// translation units
+#define RPT_PATHS_FORM RPT_PATHS_FORM_CAMERA
 #include "launch_paths.inc"
-#undef RPT_PATHS_VIEWS
+#undef RPT_PATHS_FORM
 void launch_sum_samples(hipStream_t st, const Frame& fr, const double* lbuf, uint32_t spp, bool first) {
   hipLaunchKernelGGL(rpt_sum_samples, grid_for(fr.npix), dim3(256), 0, st, fr, lbuf, spp, first ? 1 : 0);
 }
@@ -372,5 +373,7 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_raygen_views_seeded, launch_shade_seeded,
                            launch_denoise_views_prepare, launch_denoise_views_level, launch_denoise_views_finish,
                            launch_vertices_store, launch_vertices_fold,
-                           RPT_NS_VIEWS::paths_max_blocks_per_cu, RPT_NS_VIEWS::launch_paths, RPT_NS_VIEWS::launch_views_ids};
+                           RPT_NS_VIEWS::paths_max_blocks_per_cu, RPT_NS_VIEWS::launch_paths, RPT_NS_VIEWS::launch_views_ids,
+                           RPT_NS_RAYS::paths_max_blocks_per_cu, RPT_NS_RAYS::launch_paths, RPT_NS_RAYS::launch_rays_ids,
+                           RPT_NS_RAYS::launch_project_probes};
 #endif // !__HIP_DEVICE_COMPILE__

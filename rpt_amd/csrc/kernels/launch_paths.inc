@@ -1,9 +1,13 @@
 // kernels/launch_paths.inc — the choice of the persistent path kernel's instantiation, its occupancy query and its launch: ONE
-// text for rpt_paths (launch.inc; the rays are a Camera's) and, with RPT_PATHS_VIEWS 1, for rpt_paths_views (the views'
-// translation unit, kernels.inc under RPT_VIEWS_TU; the rays are a ViewRays').  Host pass only.
-#if RPT_PATHS_VIEWS
+// text for rpt_paths (launch.inc; the rays are a Camera's) and, by RPT_PATHS_FORM (kernels.inc), for rpt_paths_views (the
+// views' translation unit, kernels.inc under RPT_VIEWS_TU; the rays are a ViewRays') and rpt_paths_rays (the rays'
+// translation unit, RPT_RAYS_TU; the rays are a CallerRays').  Host pass only.
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VIEWS
 #define RPT_PATHS_FN rpt_paths_views
 #define RPT_PATHS_RAYS ViewRays
+#elif RPT_PATHS_FORM == RPT_PATHS_FORM_RAYS
+#define RPT_PATHS_FN rpt_paths_rays
+#define RPT_PATHS_RAYS CallerRays
 #else
 #define RPT_PATHS_FN rpt_paths
 #define RPT_PATHS_RAYS Camera
@@ -48,7 +52,7 @@ void launch_paths(hipStream_t st, const Scene& sc, const Frame& fr, const RPT_PA
   PersistArgs pa{work_counter, rec, ray_counters, lbuf, spp, chunk, n_items, nblocks * 64u, rpt_fold_ring_slots(fr.max_bounces),
                  batch, park ? paths_park_off(lds_bytes) : 0xffffffffu, lay};
   if (park) lds_bytes = paths_park_off(lds_bytes) + RPT_PATHS_PARK_LDS;
-  void* args[] = {(void*)&sc, (void*)&fr, (void*)&rays, (void*)&pa}; // the kernel's (Scene, Frame, Camera | ViewRays, PersistArgs)
+  void* args[] = {(void*)&sc, (void*)&fr, (void*)&rays, (void*)&pa}; // the kernel's (Scene, Frame, Camera | ViewRays | CallerRays, PersistArgs)
   (void)hipLaunchKernel(paths_kernel(flat ? &lay : nullptr, park), dim3(nblocks), dim3(64), args, lds_bytes, st);
 }
 #undef RPT_PATHS_FN

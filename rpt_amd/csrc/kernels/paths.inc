@@ -371,13 +371,14 @@ RPT_DEV void walker_step(const PersistArgs& pa, const Frame& fr, const double* _
     fold_st = (cb << 16) | nk;
   }
 }
-// the loop itself: kernels/paths_loop.inc, one text for rpt_paths (a camera's frame) and rpt_paths_views (a piece of a batch of
-// views, kernels/paths_views.inc, in a translation unit of its own)
-#define RPT_PATHS_VIEWS 0
+// the loop itself: kernels/paths_loop.inc, one text for rpt_paths (a camera's frame), rpt_paths_views (a piece of a batch of
+// views, kernels/paths_views.inc) and rpt_paths_rays (a piece of the caller's rays or probes, kernels/paths_rays.inc), the last
+// two in translation units of their own
+#define RPT_PATHS_FORM RPT_PATHS_FORM_CAMERA
 #include "paths_loop.inc"
-#undef RPT_PATHS_VIEWS
+#undef RPT_PATHS_FORM
 
-#ifndef RPT_VIEWS_TU // (the views' translation unit compiles rpt_paths_views alone)
+#ifndef RPT_FORM_TU // (a form's translation unit compiles that form's kernels alone)
 // color += trace_ray(...) over the launch's samples in sample order (renderer.rs:136-140); `first`
 // starts the pixel's sum at zero, later launches of the same batch continue it
 __global__ void __launch_bounds__(256) rpt_sum_samples(Frame fr, const double* __restrict__ lbuf, uint32_t spp, int first) {

@@ -1,19 +1,34 @@
-// kernels/paths_loop.inc — the persistent path kernel's loop: ONE text, included twice.  RPT_PATHS_VIEWS 0 (paths.inc):
-// rpt_paths, whose work items are pixels of one camera's frame.  RPT_PATHS_VIEWS 1 (paths_views.inc): rpt_paths_views, whose
-// work items are indices of a piece of a batch of views (rptgpu_render_views under RPT_FLAG_VIEWS_PERSISTENT, DESIGN.md
-// §15.2): item p_local is index j = the piece's base + p_local of the call, fr.pixels[p_local] its pixel in its view — the
-// stream id, as for a frame — and vr.view_of[p_local] its view, counted from the piece's first.  The camera ray is
-// views_camera_ray's (rpt_raygen_views' ray, expression for expression) and the stream's key is the view's seed, taken at
-// ray generation and again wherever a path comes back from the stash or the pool (views_rekey): the key is per lane.
-// Everything else is the same text.  The two forms differ by the preprocessor, not by a template parameter, and are compiled
-// in different translation units (kernels.inc, RPT_VIEWS_TU): rpt_paths' instantiations keep their names, their instructions
-// and their place in their code object (DESIGN.md §15.2 has what sharing one cost).
+// kernels/paths_loop.inc — the persistent path kernel's loop: ONE text, included once per form (RPT_PATHS_FORM, kernels.inc).
+// RPT_PATHS_FORM_CAMERA (paths.inc): rpt_paths, whose work items are pixels of one camera's frame.
+// RPT_PATHS_FORM_VIEWS (paths_views.inc): rpt_paths_views, whose work items are indices of a piece of a batch of views
+// (rptgpu_render_views under RPT_FLAG_VIEWS_PERSISTENT, DESIGN.md §15.2): item p_local is index j = the piece's base + p_local
+// of the call, fr.pixels[p_local] its pixel in its view — the stream id, as for a frame — and vr.view_of[p_local] its view,
+// counted from the piece's first.  The camera ray is views_camera_ray's (rpt_raygen_views' ray, expression for expression)
+// and the stream's key is the view's seed, taken at ray generation and again wherever a path comes back from the stash or
+// the pool (views_rekey): the key is per lane.
+// RPT_PATHS_FORM_RAYS (paths_rays.inc): rpt_paths_rays, whose work items are rays or light probes of a piece of the caller's
+// (rptgpu_trace_rays / rptgpu_bake_probes under RPT_FLAG_RAYS_PERSISTENT, DESIGN.md §13.1): item p_local is ray or probe
+// p_local of the piece, fr.pixels[p_local] its stream id, the key the Frame's seed as for a render; the ray is caller_ray's —
+// read where the caller left it, or drawn as a probe's direction — behind all three hand-out forms.
+// Everything else is the same text.  The forms differ by the preprocessor, not by a template parameter, and are compiled
+// in different translation units (kernels.inc, RPT_VIEWS_TU / RPT_RAYS_TU): rpt_paths' instantiations keep their names, their
+// instructions and their place in their code object (DESIGN.md §15.2 has what sharing one cost).
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
+// the ray of sample smp of work item pl (stream id px) into (ro, rd), its stream behind the ray's draws into rr
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VIEWS
+#define RPT_PATHS_RAY(pl, px, smp, ro, rd, rr) views_camera_ray(fr, vr, pl, px, smp, ro, rd, rr)
+#elif RPT_PATHS_FORM == RPT_PATHS_FORM_RAYS
+#define RPT_PATHS_RAY(pl, px, smp, ro, rd, rr) caller_ray(fr, cr, pl, px, smp, ro, rd, rr)
+#else
+#define RPT_PATHS_RAY(pl, px, smp, ro, rd, rr) camera_ray(fr, cam, dim, px, smp, ro, rd, rr)
+#endif
 template <class LDS, bool PARK /* environment lookups parked per lane (pa.park_off) */,
           bool FUSE = false /* a hit's shadow ray and bounce ray in one query (FUSE below) */,
           bool CONSTS = false /* FUSE with a hit's scene constants in the wave's tables (SceneConsts, paths_consts.inc) */>
-#if RPT_PATHS_VIEWS
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VIEWS
 __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths_views(Scene sc, Frame fr, ViewRays vr, PersistArgs pa) {
+#elif RPT_PATHS_FORM == RPT_PATHS_FORM_RAYS
+__global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths_rays(Scene sc, Frame fr, CallerRays cr, PersistArgs pa) {
 #else
 __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame fr, Camera cam, PersistArgs pa) {
 #endif
@@ -99,7 +114,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
 #else
   constexpr double probe_chk = 0.0; // (walker_step's unused argument)
 #endif
-#if !RPT_PATHS_VIEWS
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_CAMERA
   const double dim = (double)max(fr.width, fr.height);
 #endif
   // rpt_paths<KdFlat>: the NEXT sample's camera ray waits in LDS.  Fetch and ray generation are work for the ~14 lanes of
@@ -192,11 +207,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
           const uint32_t g_pixel = fr.pixels[ps.g_p_local];
           D3 go, gd;
           Rng gr;
-#if RPT_PATHS_VIEWS
-          views_camera_ray(fr, vr, ps.g_p_local, g_pixel, ps.g_s, go, gd, gr);
-#else
-          camera_ray(fr, cam, dim, g_pixel, ps.g_s, go, gd, gr);
-#endif
+          RPT_PATHS_RAY(ps.g_p_local, g_pixel, ps.g_s, go, gd, gr);
           PROF_PHASE(PF_P_RAYGEN);
           double t = INF;
           D3 hn = mk(0, 0, 0);
@@ -236,11 +247,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         if (gen && !exhausted) {
           D3 go, gd;
           Rng gr;
-#if RPT_PATHS_VIEWS
-          views_camera_ray(fr, vr, g_p_local, g_pixel, g_s, go, gd, gr);
-#else
-          camera_ray(fr, cam, dim, g_pixel, g_s, go, gd, gr);
-#endif
+          RPT_PATHS_RAY(g_p_local, g_pixel, g_s, go, gd, gr);
 #if RPT_PRETRACE_CULL
           if constexpr (FUSE) near = cull_near(pa.flat, g_pixel, fr.width);
 #endif
@@ -255,7 +262,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       if (!PRETRACE && !in_path && stash_valid) {
         stash_take_ray(stash, lane, o, d);
         stash_take_path(stash, lane, fr, p_local, pixel, s, s_end, rng);
-#if RPT_PATHS_VIEWS
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VIEWS
         views_rekey(vr, p_local, rng);
 #endif
         stash_valid = false;
@@ -272,9 +279,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       PROF_PHASE(PF_P_FETCH);
       // ---- ray generation (renderer.rs:132-139, camera.rs:64-81): camera_ray's body, word for word — a change to either goes
       // into both.  Calling it here costs rpt_paths<KdLds> 16 B of scratch and 6 spilled VGPRs (profiles/paths_split_resources.txt)
-#if RPT_PATHS_VIEWS
-      if (!done && !in_path) { // (the views' ray: a device function of its own, paths_views.inc)
-        views_camera_ray(fr, vr, p_local, pixel, s, o, d, rng);
+#if RPT_PATHS_FORM != RPT_PATHS_FORM_CAMERA
+      if (!done && !in_path) { // (the views' or the caller's ray: a device function of its own, paths_views.inc / paths_rays.inc)
+        RPT_PATHS_RAY(p_local, pixel, s, o, d, rng);
         depth = 0;
         in_path = true;
       }
@@ -374,7 +381,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       if (need && rpt_pool_pop_ok(rpt_pool_rank(need_mask, lane), ps.cnt)) {
         if (in_path) end_path(pa, fr, rec, fold_l, fold_u, lane, fold_st, ring, h_nrm, depth, s, p_local);
         pool_take(stash, rpt_pool_slot(ps.head, rpt_pool_rank(need_mask, lane), RPT_POOL_CAP), fr, h_pos, d, h_nrm, h_obj, p_local, s, rng);
-#if RPT_PATHS_VIEWS
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VIEWS
         views_rekey(vr, p_local, rng);
 #endif
         depth = 0;
@@ -393,7 +400,7 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       if (!in_path && stash_valid) {
         stash_take_hit(stash, lane, h_pos, d, h_nrm, h_obj);
         stash_take_path(stash, lane, fr, p_local, pixel, s, s_end, rng);
-#if RPT_PATHS_VIEWS
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VIEWS
         views_rekey(vr, p_local, rng);
 #endif
         stash_valid = false;
@@ -675,3 +682,4 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
     atomicAdd(pa.ray_counters + 1, (unsigned long long)n_sh);
   }
 }
+#undef RPT_PATHS_RAY

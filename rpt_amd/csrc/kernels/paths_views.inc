@@ -81,9 +81,9 @@ RPT_DEV void views_camera_ray(const Frame& fr, const ViewRays& vr, uint32_t p_lo
   rr = rng;
 }
 
-#define RPT_PATHS_VIEWS 1
+#define RPT_PATHS_FORM RPT_PATHS_FORM_VIEWS
 #include "paths_loop.inc"
-#undef RPT_PATHS_VIEWS
+#undef RPT_PATHS_FORM
 
 // every instantiation paths_kernel() can pick (kernels/launch_paths.inc), as rpt_paths' own (kernels/buffer.inc)
 template __global__ void rpt_paths_views<KdLds, false>(Scene, Frame, ViewRays, PersistArgs);
@@ -102,9 +102,9 @@ template __global__ void rpt_paths_views<KdFlatF, true>(Scene, Frame, ViewRays, 
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 // the launchers the kernel tables point to (kernels.h)
-#define RPT_PATHS_VIEWS 1
+#define RPT_PATHS_FORM RPT_PATHS_FORM_VIEWS
 #include "launch_paths.inc"
-#undef RPT_PATHS_VIEWS
+#undef RPT_PATHS_FORM
 void launch_views_ids(hipStream_t st, uint64_t j_base, uint64_t npix_view, uint32_t n, uint32_t* pixels, uint32_t* view_of) {
   hipLaunchKernelGGL(rpt_views_ids, dim3((n + 255u) / 256u), dim3(256), 0, st, j_base, npix_view, n, pixels, view_of);
 }

@@ -235,6 +235,15 @@ inline ViewsIndex views_index(uint64_t j_base, uint64_t i, uint64_t npix_view) {
   return ViewsIndex{v, (uint32_t)(j - v * npix_view), (uint32_t)(v - j_base / npix_view)};
 }
 
+// ---- rptgpu_trace_rays / rptgpu_bake_probes under RPT_FLAG_RAYS_PERSISTENT: a piece's m rays or probes are the "pixels" of
+// rpt_paths_rays' launches (kernels/paths_rays.inc), so the piece rays_piece gives is additionally capped by what the work
+// counter holds — views_items' arithmetic with npix = m, at chunk 1 (the most items a launch of `iterations` samples can have)
+// and the most resident blocks any instantiation has: whatever launch plan render_persistent then runs over the piece fits
+// (tests/cpp/rays_items_check.cpp).  Never 0: one ray is still a piece (render_persistent throws if even that overflows)
+inline uint64_t rays_persistent_piece(uint64_t piece, uint32_t iterations, uint32_t blocks_max, uint32_t batch_max) {
+  return std::max<uint64_t>(1, views_items(piece, iterations, 1, blocks_max, batch_max).m);
+}
+
 // ---- rptgpu_occluded / rptgpu_bake_ao: one visibility query per pass over rays laid into the workspace's slots, so a pass
 // holds at most pass_target rays (plan_pass's target for the scene with ONE record column per path: no depth follows),
 // never more than RPT_MAX_PATHS_PER_PASS (32-bit slots) and never more than OCCLUSION_PIECE_MAX (a host caller stages 56 B

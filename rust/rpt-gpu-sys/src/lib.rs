@@ -52,6 +52,10 @@ pub mod ffi {
     /// include/rpt_gpu_views_persistent.h: in `RptViewQuery::flags` of `rptgpu_render_views[_seeded][_device]`, run the batch
     /// in the persistent path kernel (read where `rptgpu_views_persistent_supported` exists and returns 1)
     pub const RPT_FLAG_VIEWS_PERSISTENT: u32 = 16;
+    /// include/rpt_gpu_rays_persistent.h: in `RptRayQuery::flags` of `rptgpu_trace_rays[_device]` and `RptProbeQuery::flags` of
+    /// `rptgpu_bake_probes[_device]`, run the call's paths in the persistent path kernel (read where
+    /// `rptgpu_rays_persistent_supported` exists and returns 1)
+    pub const RPT_FLAG_RAYS_PERSISTENT: u32 = 32;
     pub const RPT_COLLECTIVE_DEFAULT: u32 = 0;
     pub const RPT_COLLECTIVE_GATHER: u32 = 1;
     pub const RPT_COLLECTIVE_REDUCE: u32 = 2;
@@ -530,6 +534,12 @@ pub mod ffi {
     // without it ignores the flag and is detected with dlsym("rptgpu_views_persistent_supported"); this crate links it like the rest)
     extern "C" {
         pub fn rptgpu_views_persistent_supported() -> c_int;
+    }
+
+    // include/rpt_gpu_rays_persistent.h: RPT_FLAG_RAYS_PERSISTENT's detection — an optional addition within ABI 7 (a library
+    // without it ignores the flag and is detected with dlsym("rptgpu_rays_persistent_supported"); this crate links it like the rest)
+    extern "C" {
+        pub fn rptgpu_rays_persistent_supported() -> c_int;
     }
 
     // include/rpt_gpu_vertices.h: the vertices of the paths rptgpu_trace_rays runs — optional additions within ABI 7 (a
