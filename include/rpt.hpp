@@ -854,15 +854,19 @@ class Renderer {
     std::vector<double> normal, position, direction, radiance, bsdf; // xyz / rgb per vertex
     std::vector<double> rgb;                                        // rgb per ray
   };
+  // flags: RPT_FLAG_* of the query — RPT_FLAG_VERTICES_PERSISTENT (include/rpt_gpu_vertices_persistent.h) runs the paths in the
+  // persistent path kernel, the same bytes by another route, where vertices_persistent_supported() says the library reads it.
+  static bool vertices_persistent_supported() { return rptgpu_vertices_persistent_supported() == 1; }
   Vertices trace_vertices(const std::vector<double>& origins, const std::vector<double>& dirs, uint32_t channels = 4095u,
-                          const std::vector<uint32_t>& streams = {}, uint32_t first_draw = 0, uint64_t sample_index_base = 0) {
+                          const std::vector<uint32_t>& streams = {}, uint32_t first_draw = 0, uint64_t sample_index_base = 0,
+                          uint32_t flags = 0) {
     ensure_scene();
     const size_t n = origins.size() / 3;
     if (origins.size() != 3 * n || dirs.size() != 3 * n || (!streams.empty() && streams.size() != n))
       throw std::invalid_argument("trace_vertices: origins and dirs hold xyz per ray, streams one id per ray");
     RptVertexQuery q{};
     q.struct_size = sizeof(RptVertexQuery); q.max_bounces = max_bounces_; q.iterations = num_samples_; q.first_draw = first_draw;
-    q.exposure_value = ev_; q.seed = seed_; q.sample_index_base = sample_index_base; q.channels = channels;
+    q.exposure_value = ev_; q.seed = seed_; q.sample_index_base = sample_index_base; q.channels = channels; q.flags = flags;
     Vertices r;
     if (!n) return r; // (an empty vector has no address, and a named channel's pointer must not be NULL)
     const size_t paths = n * (size_t)num_samples_, v = paths * ((size_t)max_bounces_ + 1);

@@ -183,11 +183,16 @@ enum {
                                     in the persistent path kernel — an OPTIONAL addition within ABI 7, read only by a
                                     library that exports rptgpu_views_persistent_supported (rpt_gpu_views_persistent.h,
                                     included at the end of this file; a library without it ignores the bit) */
-  RPT_FLAG_RAYS_PERSISTENT = 32u /* RptRayQuery::flags of rptgpu_trace_rays[_device] and RptProbeQuery::flags of
-                                    rptgpu_bake_probes[_device] only: the call's paths in the persistent path kernel — an
-                                    OPTIONAL addition within ABI 7, read only by a library that exports
-                                    rptgpu_rays_persistent_supported (rpt_gpu_rays_persistent.h, included at the end of this
-                                    file; a library without it ignores the bit) */
+  RPT_FLAG_RAYS_PERSISTENT = 32u, /* RptRayQuery::flags of rptgpu_trace_rays[_device] and RptProbeQuery::flags of
+                                     rptgpu_bake_probes[_device] only: the call's paths in the persistent path kernel — an
+                                     OPTIONAL addition within ABI 7, read only by a library that exports
+                                     rptgpu_rays_persistent_supported (rpt_gpu_rays_persistent.h, included at the end of this
+                                     file; a library without it ignores the bit) */
+  RPT_FLAG_VERTICES_PERSISTENT = 64u /* RptVertexQuery::flags of rptgpu_trace_vertices[_device] only: the call's paths in the
+                                    persistent path kernel, which then writes each vertex where it makes it — an OPTIONAL
+                                    addition within ABI 7, read only by a library that exports
+                                    rptgpu_vertices_persistent_supported (rpt_gpu_vertices_persistent.h, included at the end
+                                    of this file; a library without it ignores the bit) */
 };
 
 /* ---- what Renderer carries into sample(): src/renderer.rs:18-42 + the call argument ----
@@ -1043,6 +1048,8 @@ const char* rptgpu_kernel_name(int k);
 #include "rpt_gpu_views_persistent.h"
 /* ---- ... and caller-supplied rays and light probes in the persistent path kernel, on request ---- */
 #include "rpt_gpu_rays_persistent.h"
+/* ---- ... and the vertices of those rays' paths from the persistent path kernel, on request ---- */
+#include "rpt_gpu_vertices_persistent.h"
 
 #ifdef __cplusplus
 }

@@ -30,7 +30,8 @@
  * an RptProbeQuery stays refused.  Which route is faster depends on the scene and on how coherent the rays are (DESIGN.md
  * §13.1 and §14.1 have the measurements).
  * RPTGPU_E_INVALID_ARGUMENT, before any device work and with the arrays untouched: the flag together with
- * RPT_FLAG_WAVEFRONT; the flag in a call of rptgpu_trace_vertices[_device], which has no such route.  No other call reads
+ * RPT_FLAG_WAVEFRONT; the flag in a call of rptgpu_trace_vertices[_device], which has a flag of its own
+ * (RPT_FLAG_VERTICES_PERSISTENT, rpt_gpu_vertices_persistent.h).  No other call reads
  * the bit.
  * (The constant stands with the other RPT_FLAG_* in rpt_gpu.h: RPT_FLAG_RAYS_PERSISTENT = 32u.) */
 

@@ -57,10 +57,12 @@
  * re-ordering of a depth's paths, on the traversal route (RPT_FLAG_GENERAL_TRAVERSAL).  After a live update (rptgpu_scene_set_
  * objects / _lights / _mesh / _group) they are those of a fresh handle on the updated scene.
  *
- * ROUTE AND STATS.  The call always runs the wavefront pipeline, as rptgpu_trace_rays does; RPT_FLAG_GENERAL_TRAVERSAL and
+ * ROUTE AND STATS.  The call runs the wavefront pipeline, as rptgpu_trace_rays does; RPT_FLAG_GENERAL_TRAVERSAL and
  * RPT_FLAG_PROFILE_KERNELS are honoured, RPT_FLAG_WAVEFRONT changes nothing, RPT_FLAG_PERSISTENT is refused.  RptStats
  * advances exactly as for rptgpu_trace_rays (samples = n * iterations; the two kernels that carry the records out are not
- * counted under any RPT_K_* kind).  There is no CPU fallback.  RPTGPU_VERTICES_PIECE (environment, read per call; tests):
+ * counted under any RPT_K_* kind).  A library with rpt_gpu_vertices_persistent.h (included at the end of rpt_gpu.h) runs the
+ * persistent kernel instead when it is asked to with RPT_FLAG_VERTICES_PERSISTENT: the same bytes in every array, the
+ * stats of that kernel.  There is no CPU fallback.  RPTGPU_VERTICES_PIECE (environment, read per call; tests):
  * the rays per piece.
  *
  * RPTGPU_E_INVALID_ARGUMENT, checked before any device work, with a detail naming the reason and every array untouched:
@@ -72,8 +74,8 @@
  * returns RPTGPU_OK.
  *
  * NOT IN SCOPE.  Views or camera pixels as the ray source (a caller makes those rays itself: tests/views_model.py shows
- * how); primitive ids or barycentrics; the shadow rays' own records (only their sum, inside RADIANCE); light probes; the
- * persistent kernel; multi-GPU; the device Buffer. */
+ * how); primitive ids or barycentrics; the shadow rays' own records (only their sum, inside RADIANCE); light probes;
+ * multi-GPU; the device Buffer.  (The persistent kernel: on request, rpt_gpu_vertices_persistent.h.) */
 enum {
   RPT_VERTEX_LENGTH = 1u, RPT_VERTEX_T = 2u, RPT_VERTEX_NORMAL = 4u, RPT_VERTEX_OBJECT = 8u, RPT_VERTEX_POSITION = 16u,
   RPT_VERTEX_DIRECTION = 32u, RPT_VERTEX_DRAW = 64u, RPT_VERTEX_RADIANCE = 128u, RPT_VERTEX_BSDF = 256u,
@@ -88,7 +90,7 @@ typedef struct RptVertexQuery {
   uint64_t seed;
   uint64_t sample_index_base; /* index of every ray's first sample */
   uint32_t precision_mode;    /* RPT_PRECISION_* */
-  uint32_t flags;             /* as RptRayQuery: GENERAL_TRAVERSAL, PROFILE_KERNELS honoured; PERSISTENT refused */
+  uint32_t flags;             /* as RptRayQuery: GENERAL_TRAVERSAL, PROFILE_KERNELS honoured; PERSISTENT refused; VERTICES_PERSISTENT */
   uint32_t channels;          /* RPT_VERTEX_* wanted, at least one */
   uint32_t reserved;          /* 0 */
 } RptVertexQuery;

@@ -34,6 +34,7 @@ RPT_FLAG_GENERAL_TRAVERSAL = 4
 RPT_FLAG_PERSISTENT = 8
 RPT_FLAG_VIEWS_PERSISTENT = 16  # include/rpt_gpu_views_persistent.h: RptViewQuery.flags of render_views (views_persistent_supported())
 RPT_FLAG_RAYS_PERSISTENT = 32  # include/rpt_gpu_rays_persistent.h: RptRayQuery.flags of trace_rays, RptProbeQuery.flags of bake_probes (rays_persistent_supported())
+RPT_FLAG_VERTICES_PERSISTENT = 64  # include/rpt_gpu_vertices_persistent.h: RptVertexQuery.flags of trace_vertices (vertices_persistent_supported())
 RPT_K_RAYGEN, RPT_K_EXTEND, RPT_K_SHADE, RPT_K_SHADOW, RPT_K_RESOLVE, RPT_K_PATHS, RPT_K_TREE_TRACE, RPT_K_TREE_SORT = range(8)
 RPT_K_COUNT = 8
 RPT_PARTICLES_SOLID_GRAVITY, RPT_PARTICLES_MARBLES, RPT_PARTICLES_CIRCLE = range(3)
@@ -363,6 +364,11 @@ VIEWS_PERSISTENT_SYMBOLS = [
 RAYS_PERSISTENT_SYMBOLS = [
     ("rptgpu_rays_persistent_supported", C.c_int, []),
 ]
+# ... and the symbol include/rpt_gpu_vertices_persistent.h declares, optional in the same way: a library without it ignores
+# RPT_FLAG_VERTICES_PERSISTENT and runs the wavefront pipeline (vertices_persistent_supported)
+VERTICES_PERSISTENT_SYMBOLS = [
+    ("rptgpu_vertices_persistent_supported", C.c_int, []),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -391,11 +397,11 @@ def load_library(path=None):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
-    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS:
+    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS:
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_persistent_supported() says no)
+            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported() say no)
         fn.restype = restype
         fn.argtypes = argtypes
     if lib.rptgpu_abi_version() != ABI_VERSION:
@@ -423,6 +429,18 @@ def rays_persistent_supported(lib=None):
     lib = lib or load_library()
     try:
         fn = lib.rptgpu_rays_persistent_supported
+    except AttributeError:
+        return False
+    fn.restype, fn.argtypes = C.c_int, []
+    return fn() == 1
+
+
+def vertices_persistent_supported(lib=None):
+    """Does the library read RPT_FLAG_VERTICES_PERSISTENT (include/rpt_gpu_vertices_persistent.h)?  Detected by symbol, as a C
+    caller does with dlsym: a library without it is still ABI 7, ignores the bit and runs the wavefront pipeline."""
+    lib = lib or load_library()
+    try:
+        fn = lib.rptgpu_vertices_persistent_supported
     except AttributeError:
         return False
     fn.restype, fn.argtypes = C.c_int, []

@@ -396,7 +396,9 @@ struct RaySource {
   // RPT_FLAG_RAYS_PERSISTENT): origins, dirs, first_draw, probe and probe_scale as above with cam and views null; the piece's
   // Frame::pixels holds the stream ids already (the caller's, or rpt_rays_ids'), and ids_out and id_base are not read
   // rptgpu_trace_vertices (api_vertices.cpp): where the vertices of the piece's paths go — the caller's arrays or their
-  // staging, offset to the piece; run_pass fills in s_first per pass.  nullptr (every other call): nothing is launched for it
+  // staging, offset to the piece; run_pass fills in s_first per pass.  nullptr (every other call): nothing is launched for it.
+  // With origins alone, as for rpt_paths_rays, render_persistent launches rpt_paths_vertices instead (RPT_FLAG_VERTICES_PERSISTENT),
+  // which writes the vertices itself; s_first is then set per launch
   const rptdev::VertexOut* vertices = nullptr;
 };
 // api_views.cpp: what is wrong with an RptViewQuery / with one view of a call with query q (nullptr: nothing); shared with
@@ -430,8 +432,8 @@ void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in);
 // the wavefront driver: the batch in passes from `src`, then rpt_finish into `out` (api_render.cpp)
 void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const RaySource& src,
                       void* out, bool out_f32, bool packed, bool prof);
-// the persistent driver: the batch in launches of rpt_paths (src.cam), rpt_paths_views (src.views) or rpt_paths_rays
-// (src.origins alone), rpt_sum_samples behind each, then rpt_finish into `out` — probes (src.probe >= 0): rpt_project_probes
+// the persistent driver: the batch in launches of rpt_paths (src.cam), rpt_paths_views (src.views), rpt_paths_rays
+// (src.origins alone) or rpt_paths_vertices (src.origins with src.vertices), rpt_sum_samples behind each, then rpt_finish into `out` — probes (src.probe >= 0): rpt_project_probes
 // and rpt_finish_probes in their places (api_render.cpp)
 void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const RaySource& src,
                        void* out, bool out_f32, bool packed, bool prof);

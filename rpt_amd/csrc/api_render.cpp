@@ -321,7 +321,8 @@ rptdev::PathState path_state(rptgpu_scene* h) {
 // rpt_views_ids' — api_views.cpp), or a piece of the caller's rays or light probes (src.origins with cam and views null:
 // rpt_paths_rays — fr is the piece's, its pixels the stream ids; probes, src.probe >= 0, project each launch's samples into
 // the piece's running sums with rpt_project_probes where rpt_sum_samples stands and end with rpt_finish_probes —
-// api_rays.cpp, api_probes.cpp)
+// api_rays.cpp, api_probes.cpp), or such a piece of rays with a vertex sink (src.vertices: rpt_paths_vertices, which also
+// writes every path's vertices into the sink's arrays, s_first set per launch as run_pass sets it per pass — api_vertices.cpp)
 void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr,
                        const RaySource& src, void* out, bool out_f32, bool packed, bool prof) {
   hipStream_t st = h->stream;
@@ -329,9 +330,15 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   const bool views = src.views != nullptr;
   const bool rays = !views && !src.cam && src.origins != nullptr; // (probes too: src.probe >= 0)
   const bool probes = rays && src.probe >= 0;
+  const bool vertices = rays && !probes && src.vertices != nullptr;
   const rptdev::CallerRays cr{src.origins, src.dirs, src.first_draw, probes ? (int32_t)src.probe : -1};
-  const char* const kname = views ? "rpt_paths_views" : rays ? "rpt_paths_rays" : "rpt_paths";
-  const auto max_blocks = views ? kt->paths_views_max_blocks_per_cu : rays ? kt->paths_rays_max_blocks_per_cu : kt->paths_max_blocks_per_cu;
+  const char* const kname = views ? "rpt_paths_views" : vertices ? "rpt_paths_vertices" : rays ? "rpt_paths_rays" : "rpt_paths";
+  const auto max_blocks = views      ? kt->paths_views_max_blocks_per_cu
+                          : vertices ? kt->paths_vertices_max_blocks_per_cu
+                          : rays     ? kt->paths_rays_max_blocks_per_cu
+                                     : kt->paths_max_blocks_per_cu;
+  // (rpt_paths_vertices has the plain hand-out only: neither the fused query nor the pool, whatever the layout offers)
+  const bool fused_forms = !vertices;
   rptdev::ViewRays vr{};
   if (views) {
     const uint64_t v0 = src.view_base / ((uint64_t)src.view_width * src.view_height); // the piece's first view
@@ -378,9 +385,9 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
                  "dynamic LDS %u B per wave (the flat scene's tables)%s%s%s%s\n",
                  kname, flat ? (lay.obj_filter ? "KdFlatF" : lay.n_tris ? "KdFlat" : "KdFlatG") : "KdLds", pl.per_cu, h->num_cus, pl.nblocks,
                  pl.chunk, pl.n_launch, pl.spp_l, flat_lds, park ? " + parked environment lookups" : "",
-                 flat && lay.n_tris && lay.fuse_query && !park ? ", shadow and bounce rays in one query" : "",
-                 flat && lay.n_tris && lay.fuse_query && !park && lay.scene_consts ? ", a hit's scene constants from the wave's tables" : "",
-                 RPT_HIT_POOL && flat && lay.n_tris && lay.fuse_query && !park ? ", pre-traced hits in a wave-level pool" : "");
+                 fused_forms && flat && lay.n_tris && lay.fuse_query && !park ? ", shadow and bounce rays in one query" : "",
+                 fused_forms && flat && lay.n_tris && lay.fuse_query && !park && lay.scene_consts ? ", a hit's scene constants from the wave's tables" : "",
+                 fused_forms && RPT_HIT_POOL && flat && lay.n_tris && lay.fuse_query && !park ? ", pre-traced hits in a wave-level pool" : "");
   h->counters.alloc(4);
   h->pcounters.alloc(16);
   HIP_TRY(hipMemsetAsync(h->pcounters.p, 0, 16 * sizeof(unsigned long long), st));
@@ -395,7 +402,12 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
       if (views)
         kt->paths_views(st, h->dscene, fr, vr, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
                         pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
-      else if (rays)
+      else if (vertices) {
+        rptdev::VertexOut vo = *src.vertices; // (the launch's first sample, counted from the call's)
+        vo.s_first = s0;
+        kt->paths_vertices(st, h->dscene, fr, cr, vo, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
+                           pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
+      } else if (rays)
         kt->paths_rays(st, h->dscene, fr, cr, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
                        pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
       else

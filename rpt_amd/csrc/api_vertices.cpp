@@ -6,6 +6,9 @@
 // last vertices is laid down here, per piece, before its passes.  A host caller's records are
 // staged piece by piece in an array the handle keeps (rptplan::vertices_piece bounds it); a device caller's are written where
 // they lie.
+// Under RPT_FLAG_VERTICES_PERSISTENT (include/rpt_gpu_vertices_persistent.h) the same pieces, staged and
+// filled the same way, go through the persistent driver instead: rpt_paths_vertices writes each vertex where it makes it, and
+// rpt_sum_samples and the packed rpt_finish behind its launches are a render's.  The same bytes.
 #include "api_internal.h"
 
 namespace rptapi {
@@ -35,6 +38,8 @@ const char* bad_vertex_query(const RptVertexQuery* q) {
   if (q->flags & RPT_FLAG_RAYS_PERSISTENT)
     return "RptVertexQuery: RPT_FLAG_RAYS_PERSISTENT — only rptgpu_trace_rays, rptgpu_bake_probes and their _device forms run "
            "in the persistent kernel, which leaves no vertices behind";
+  if ((q->flags & RPT_FLAG_VERTICES_PERSISTENT) && (q->flags & RPT_FLAG_WAVEFRONT))
+    return "RptVertexQuery: RPT_FLAG_VERTICES_PERSISTENT | RPT_FLAG_WAVEFRONT — the two flags name different routes";
   if (!q->channels) return "RptVertexQuery: channels == 0 (name at least one RPT_VERTEX_* channel)";
   if (q->channels & ~VERTEX_ALL) return "RptVertexQuery: channels names an unknown RPT_VERTEX_* bit";
   if (q->reserved) return "RptVertexQuery: reserved != 0";
@@ -157,7 +162,14 @@ int trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const dou
     pass_input_now(h, in);
     uint64_t asked = 0; // tests: pieces of a few rays
     if (const char* e = std::getenv("RPTGPU_VERTICES_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    const uint64_t piece = rptplan::vertices_piece(n, asked, rptplan::plan_pass(in).target, !on_device, q->iterations, q->max_bounces, ch);
+    // the persistent kernel on request — unless the scene has a group with tree children, which only the wavefront
+    // pipeline walks (use_wavefront: such a scene cannot honour the request, as for rptgpu_trace_rays); a piece is then also at
+    // most what a launch's work counter holds (handle_rays_persistent_piece's bound)
+    const bool persistent = (q->flags & RPT_FLAG_VERTICES_PERSISTENT) && !use_wavefront(h, 0, false);
+    const uint64_t piece =
+        persistent ? rptplan::vertices_persistent_piece(n, asked, rptplan::plan_pass(in).target, !on_device, q->iterations, q->max_bounces, ch,
+                                                        (uint32_t)std::max(1, h->num_cus) * RPT_PATHS_WAVES_PER_CU_MAX, RPT_PATHS_BATCH_MAX)
+                   : rptplan::vertices_piece(n, asked, rptplan::plan_pass(in).target, !on_device, q->iterations, q->max_bounces, ch);
     h->accum.alloc(3 * piece);
     // rpt_finish writes a piece's means somewhere: the caller's rgb, or (a host caller, or RGB not named) the handle's array
     if (!on_device || !want_rgb) h->rays_out.alloc(3 * piece);
@@ -192,7 +204,12 @@ int trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const dou
       fr.max_bounces = q->max_bounces; fr.seed = q->seed; fr.accum = h->accum.p;
       RaySource src{nullptr, d_o, d_d, q->first_draw, (uint32_t)base, streams ? nullptr : h->ray_ids.p};
       src.vertices = &sink;
-      render_wavefront(h, kt, p, fr, src, d_rgb, false, true, prof);
+      if (persistent) { // (the ids the wavefront's first step would write: the kernel reads them from the first launch on)
+        if (!streams) kt->rays_ids(st, (uint32_t)base, (uint32_t)m, h->ray_ids.p);
+        render_persistent(h, kt, p, fr, src, d_rgb, false, true, prof);
+      } else {
+        render_wavefront(h, kt, p, fr, src, d_rgb, false, true, prof);
+      }
       HIP_TRY(hipGetLastError());
       if (!on_device) { // the staging arrays are the next piece's, too
         for (int k = 0; k < N_ROWS; k++)
@@ -202,7 +219,7 @@ int trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const dou
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
-    return drain_call(h, h->has_deep && h->gen_overflow.p);
+    return drain_call(h, !persistent && h->has_deep && h->gen_overflow.p);
   });
   if (rc != RPTGPU_OK) return rc;
   h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -224,5 +241,7 @@ int rptgpu_trace_vertices_device(rptgpu_scene* h, uint64_t n, const void* d_orig
   return trace_vertices(h, n, (const double*)d_origins, (const double*)d_dirs, (const uint32_t*)d_streams, q, d_out, true,
                         (hipStream_t)stream);
 }
+
+int rptgpu_vertices_persistent_supported(void) { return 1; }
 
 } // extern "C"

@@ -273,6 +273,14 @@ struct KernelTable {
                      uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);
   void (*rays_ids)(hipStream_t, uint32_t id_base, uint32_t n, uint32_t* ids);
   void (*project_probes)(hipStream_t, const rptdev::Frame&, const double* lbuf, uint32_t spp, uint32_t kind);
+  // the caller's rays in the persistent kernel with their paths' vertices exported (rpt_paths_vertices, kernels/
+  // paths_vertices.inc; compiled in a translation unit of its own, kernels_vertices_strict[_ext].hip, with the ray stash off):
+  // paths_max_blocks_per_cu and paths for the SAME instantiation of that kernel, `out` the piece's sink with the launch's s_first
+  int (*paths_vertices_max_blocks_per_cu)(const FlatLayout* flat, uint32_t lds_bytes, bool park);
+  void (*paths_vertices)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::CallerRays&, const rptdev::VertexOut& out,
+                         uint32_t* work_counter, double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp,
+                         uint32_t chunk, uint32_t n_items, uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes,
+                         bool park, uint32_t batch);
 };
 // the views' translation units: what the tables above point to
 #define RPT_VIEWS_TU_DECLS(NS)                                                                                                    \
@@ -299,6 +307,18 @@ RPT_VIEWS_TU_DECLS(rpt_strict_ext_views)
 RPT_RAYS_TU_DECLS(rpt_strict_rays)
 RPT_RAYS_TU_DECLS(rpt_strict_ext_rays)
 #undef RPT_RAYS_TU_DECLS
+// ... and the vertices' translation units
+#define RPT_VERTICES_TU_DECLS(NS)                                                                                                 \
+  namespace NS {                                                                                                                  \
+  int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool park);                                             \
+  void launch_paths(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::CallerRays&, const rptdev::VertexOut&, \
+                    uint32_t* work_counter, double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp,            \
+                    uint32_t chunk, uint32_t n_items, uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes,     \
+                    bool park, uint32_t batch);                                                                                   \
+  }
+RPT_VERTICES_TU_DECLS(rpt_strict_vertices)
+RPT_VERTICES_TU_DECLS(rpt_strict_ext_vertices)
+#undef RPT_VERTICES_TU_DECLS
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)
 // the same with the extended shape set (RPT_SHAPE_MONOMIAL, trees of trees) compiled in

@@ -18,10 +18,12 @@
 //     paths_shade.inc   the fused form's draw-first shading: hit_draws, bsdf_opaque, sample_f_opaque, illuminate_mesh
 //     paths.inc         the kernel's contract, work hand-out, record ring, parked lookups, ray stash; rpt_sum_samples
 //     paths_loop.inc    the loop itself: one text, compiled as rpt_paths (paths.inc), as rpt_paths_views (paths_views.inc) and
-//                       as rpt_paths_rays (paths_rays.inc)
+//                       as rpt_paths_rays (paths_rays.inc) and as rpt_paths_vertices (paths_vertices.inc)
 //     paths_views.inc   rpt_paths_views, the kernel over a piece of a batch of views: its ids, camera ray and per-lane key
 //     paths_rays.inc    rpt_paths_rays, the kernel over a piece of the caller's rays or light probes: its ray; rpt_rays_ids,
 //                       rpt_project_probes
+//     paths_vertices.inc rpt_paths_vertices, rpt_paths_rays with the paths' vertices written where the loop has them: its
+//                       ray and the three stores of a vertex
 //     probe_dir.inc     a light probe's direction and the SH9 basis, shared by both routes of rptgpu_bake_probes
 //   the wavefront pipeline — scenes with deep trees; rptgpu_trace_rays and rptgpu_bake_probes for any scene (flat ones
 //   query inside rpt_extend / rpt_shadow_rays) —: one kernel per step of a depth over SoA path state, in six files:
@@ -54,8 +56,9 @@
 #include <cstring>
 #include <type_traits>
 
-// a translation unit of one form of the persistent kernel alone (the views': RPT_VIEWS_TU; the caller's rays': RPT_RAYS_TU)
-#if defined(RPT_VIEWS_TU) || defined(RPT_RAYS_TU)
+// a translation unit of one form of the persistent kernel alone (the views': RPT_VIEWS_TU; the caller's rays': RPT_RAYS_TU;
+// the caller's rays' with their vertices: RPT_VERTICES_TU)
+#if defined(RPT_VIEWS_TU) || defined(RPT_RAYS_TU) || defined(RPT_VERTICES_TU)
 #define RPT_FORM_TU 1
 #endif
 #ifndef RPT_FORM_TU
@@ -78,10 +81,12 @@ using namespace rptdev;
 #define RPT_CAT2(a, b) RPT_CAT2_(a, b)
 #define RPT_NS_VIEWS RPT_CAT2(RPT_NS, _views)
 #define RPT_NS_RAYS RPT_CAT2(RPT_NS, _rays) // ... and of its rays' translation unit
+#define RPT_NS_VERTICES RPT_CAT2(RPT_NS, _vertices) // ... and of its vertices' translation unit
 // the forms of the persistent kernel's loop (kernels/paths_loop.inc, RPT_PATHS_FORM): where a work item's ray comes from
 #define RPT_PATHS_FORM_CAMERA 0 // rpt_paths: a camera's pixels
 #define RPT_PATHS_FORM_VIEWS 1  // rpt_paths_views: a piece of a batch of views (paths_views.inc)
 #define RPT_PATHS_FORM_RAYS 2   // rpt_paths_rays: a piece of the caller's rays or light probes (paths_rays.inc)
+#define RPT_PATHS_FORM_VERTICES 3 // rpt_paths_vertices: a piece of the caller's rays, the paths' vertices exported (paths_vertices.inc)
 
 // Scene tables that a whole wave indexes uniformly (top-level instances, trees, lights) are read
 // through the CONSTANT address space: the scene is immutable while a kernel runs, and only then
@@ -131,7 +136,11 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/paths_flat.inc"
 #include "kernels/paths_shade.inc"
 #include "kernels/paths.inc"
-#if defined(RPT_RAYS_TU)
+#if defined(RPT_VERTICES_TU)
+// the vertices' translation units (kernels_vertices_strict[_ext].hip, RPT_NS = rpt_strict[_ext]_vertices, the ray stash off):
+// rpt_paths_vertices and its launchers (DESIGN.md §19.1)
+#include "kernels/paths_vertices.inc"
+#elif defined(RPT_RAYS_TU)
 // the rays' translation units (kernels_rays_strict[_ext].hip, RPT_NS = rpt_strict[_ext]_rays), in the same way: rpt_paths_rays,
 // rpt_rays_ids, rpt_project_probes and their launchers (DESIGN.md §13.1)
 #include "kernels/probe_dir.inc"

@@ -375,5 +375,6 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_vertices_store, launch_vertices_fold,
                            RPT_NS_VIEWS::paths_max_blocks_per_cu, RPT_NS_VIEWS::launch_paths, RPT_NS_VIEWS::launch_views_ids,
                            RPT_NS_RAYS::paths_max_blocks_per_cu, RPT_NS_RAYS::launch_paths, RPT_NS_RAYS::launch_rays_ids,
-                           RPT_NS_RAYS::launch_project_probes};
+                           RPT_NS_RAYS::launch_project_probes,
+                           RPT_NS_VERTICES::paths_max_blocks_per_cu, RPT_NS_VERTICES::launch_paths};
 #endif // !__HIP_DEVICE_COMPILE__

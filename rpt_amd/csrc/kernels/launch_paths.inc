@@ -1,12 +1,16 @@
 // kernels/launch_paths.inc — the choice of the persistent path kernel's instantiation, its occupancy query and its launch: ONE
 // text for rpt_paths (launch.inc; the rays are a Camera's) and, by RPT_PATHS_FORM (kernels.inc), for rpt_paths_views (the
 // views' translation unit, kernels.inc under RPT_VIEWS_TU; the rays are a ViewRays') and rpt_paths_rays (the rays'
-// translation unit, RPT_RAYS_TU; the rays are a CallerRays').  Host pass only.
+// translation unit, RPT_RAYS_TU; the rays are a CallerRays') and rpt_paths_vertices (the vertices' translation unit,
+// RPT_VERTICES_TU; a CallerRays and, behind it, the launch's VertexOut).  Host pass only.
 #if RPT_PATHS_FORM == RPT_PATHS_FORM_VIEWS
 #define RPT_PATHS_FN rpt_paths_views
 #define RPT_PATHS_RAYS ViewRays
 #elif RPT_PATHS_FORM == RPT_PATHS_FORM_RAYS
 #define RPT_PATHS_FN rpt_paths_rays
+#define RPT_PATHS_RAYS CallerRays
+#elif RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
+#define RPT_PATHS_FN rpt_paths_vertices
 #define RPT_PATHS_RAYS CallerRays
 #else
 #define RPT_PATHS_FN rpt_paths
@@ -40,7 +44,11 @@ int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool par
   if (e != hipSuccess || nb <= 0) nb = 8;
   return nb;
 }
-void launch_paths(hipStream_t st, const Scene& sc, const Frame& fr, const RPT_PATHS_RAYS& rays, uint32_t* work_counter,
+void launch_paths(hipStream_t st, const Scene& sc, const Frame& fr, const RPT_PATHS_RAYS& rays,
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
+                  const VertexOut& vertices,
+#endif
+                  uint32_t* work_counter,
                   double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk,
                   uint32_t n_items /* npix * ceil(spp / chunk), checked against the 32-bit work counter by the caller */,
                   uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch) {
@@ -52,7 +60,11 @@ void launch_paths(hipStream_t st, const Scene& sc, const Frame& fr, const RPT_PA
   PersistArgs pa{work_counter, rec, ray_counters, lbuf, spp, chunk, n_items, nblocks * 64u, rpt_fold_ring_slots(fr.max_bounces),
                  batch, park ? paths_park_off(lds_bytes) : 0xffffffffu, lay};
   if (park) lds_bytes = paths_park_off(lds_bytes) + RPT_PATHS_PARK_LDS;
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
+  void* args[] = {(void*)&sc, (void*)&fr, (void*)&rays, (void*)&vertices, (void*)&pa}; // the kernel's (Scene, Frame, CallerRays, VertexOut, PersistArgs)
+#else
   void* args[] = {(void*)&sc, (void*)&fr, (void*)&rays, (void*)&pa}; // the kernel's (Scene, Frame, Camera | ViewRays | CallerRays, PersistArgs)
+#endif
   (void)hipLaunchKernel(paths_kernel(flat ? &lay : nullptr, park), dim3(nblocks), dim3(64), args, lds_bytes, st);
 }
 #undef RPT_PATHS_FN

@@ -10,14 +10,19 @@
 // (rptgpu_trace_rays / rptgpu_bake_probes under RPT_FLAG_RAYS_PERSISTENT, DESIGN.md §13.1): item p_local is ray or probe
 // p_local of the piece, fr.pixels[p_local] its stream id, the key the Frame's seed as for a render; the ray is caller_ray's —
 // read where the caller left it, or drawn as a probe's direction — behind all three hand-out forms.
+// RPT_PATHS_FORM_VERTICES (paths_vertices.inc): rpt_paths_vertices, rpt_paths_rays over the caller's rays (never probes) with
+// one argument more, the vertex sink (rptgpu_trace_vertices under RPT_FLAG_VERTICES_PERSISTENT, DESIGN.md §19.1): every value
+// a vertex holds is written where the loop has it in a register — the hit behind the closest-hit query (vertex_hit), a
+// record's values where they go to the ring (vertex_record), the last vertex's radiance and the path's length where the path
+// ends (vertex_end).  The plain hand-out only: its translation units compile with the ray stash off.
 // Everything else is the same text.  The forms differ by the preprocessor, not by a template parameter, and are compiled
-// in different translation units (kernels.inc, RPT_VIEWS_TU / RPT_RAYS_TU): rpt_paths' instantiations keep their names, their
-// instructions and their place in their code object (DESIGN.md §15.2 has what sharing one cost).
+// in different translation units (kernels.inc, RPT_VIEWS_TU / RPT_RAYS_TU / RPT_VERTICES_TU): rpt_paths' instantiations keep
+// their names, their instructions and their place in their code object (DESIGN.md §15.2 has what sharing one cost).
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
 // the ray of sample smp of work item pl (stream id px) into (ro, rd), its stream behind the ray's draws into rr
 #if RPT_PATHS_FORM == RPT_PATHS_FORM_VIEWS
 #define RPT_PATHS_RAY(pl, px, smp, ro, rd, rr) views_camera_ray(fr, vr, pl, px, smp, ro, rd, rr)
-#elif RPT_PATHS_FORM == RPT_PATHS_FORM_RAYS
+#elif RPT_PATHS_FORM == RPT_PATHS_FORM_RAYS || RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
 #define RPT_PATHS_RAY(pl, px, smp, ro, rd, rr) caller_ray(fr, cr, pl, px, smp, ro, rd, rr)
 #else
 #define RPT_PATHS_RAY(pl, px, smp, ro, rd, rr) camera_ray(fr, cam, dim, px, smp, ro, rd, rr)
@@ -29,6 +34,8 @@ template <class LDS, bool PARK /* environment lookups parked per lane (pa.park_o
 __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths_views(Scene sc, Frame fr, ViewRays vr, PersistArgs pa) {
 #elif RPT_PATHS_FORM == RPT_PATHS_FORM_RAYS
 __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths_rays(Scene sc, Frame fr, CallerRays cr, PersistArgs pa) {
+#elif RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
+__global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths_vertices(Scene sc, Frame fr, CallerRays cr, VertexOut vo, PersistArgs pa) {
 #else
 __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame fr, Camera cam, PersistArgs pa) {
 #endif
@@ -143,6 +150,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
   // pre-traces of a refill run in a pass of their own.  Per lane and iteration the ring sees the same events as without
   // FUSE (a path that escaped ends when its hit is taken, before the shading), so the bound at the top of this file holds.
   static_assert(!FUSE || PRETRACE, "the fused form is a form of the pre-traced kernel");
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
+  static_assert(!STASH, "a stashed hit keeps its position, not its t: the vertices' form hands out work the plain way");
+#endif
   //
   // POOL (RPT_HIT_POOL; the fused kernels): the pre-traced hits wait in a FIFO of the WAVE, not in the lane that made
   // them.  Nothing in the result depends on which lane runs a sample — the Philox stream is keyed by (seed, pixel,
@@ -523,6 +533,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
           obj = closest_hit<LDS>(sc, o, d, t, nrm, kd_ldsp);
         }
         n_ext++;
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
+        vertex_hit(vo, vertex_index(vo, p_local, s, depth), o, d, t, nrm, obj, rng.draw);
+#endif
         PROF_PHASE(PF_P_HIT);
       }
       D3 A;
@@ -600,6 +613,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
               rec_store_bsdf(r, f, inv_pdf, abscos);
             }
 #endif
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
+            vertex_record(vo, vertex_index(vo, p_local, s, depth), A, f, inv_pdf, abscos);
+#endif
             o = world_pos;
             d = wi;
             depth++;
@@ -645,6 +661,11 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
         }
         __syncthreads();
         for (uint32_t k = 0; __ballot(k < pcnt) != 0ull; k++) { // the older path first
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
+          if (k < pcnt)
+            vertex_end(vo, park.u[k][3][lane], park.u[k][2][lane], park.u[k][0][lane],
+                       mk(park.d[k][0][lane], park.d[k][1][lane], park.d[k][2][lane]));
+#endif
           if (k < pcnt)
             path_ended(pa, fr, rec, fold_l, fold_u, lane, fold_st, mk(park.d[k][0][lane], park.d[k][1][lane], park.d[k][2][lane]),
                        park.u[k][0][lane], park.u[k][1][lane], park.u[k][2][lane], park.u[k][3][lane]);
@@ -660,6 +681,9 @@ __global__ void __launch_bounds__(64, RPT_PATHS_WAVES) rpt_paths(Scene sc, Frame
       }
     }
     if (ending) { // the path ended at this depth with radiance A_end
+#if RPT_PATHS_FORM == RPT_PATHS_FORM_VERTICES
+      vertex_end(vo, p_local, s, depth, A_end);
+#endif
       end_path(pa, fr, rec, fold_l, fold_u, lane, fold_st, ring, A_end, depth, s, p_local);
       s++;
       in_path = false;

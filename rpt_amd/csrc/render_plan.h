@@ -317,6 +317,15 @@ inline uint64_t vertices_piece(uint64_t n, uint64_t asked, uint64_t pass_target,
   }
   return piece;
 }
+// ... under RPT_FLAG_VERTICES_PERSISTENT (include/rpt_gpu_vertices_persistent.h): the piece is the smaller of vertices_piece —
+// the staging cap of a host caller's named channels holds as it stands — and what rpt_paths_vertices' 32-bit work counter
+// holds (rays_persistent_piece).  The second only ever cuts the first, so both caps hold and a piece is never empty
+// (tests/cpp/vertices_persistent_piece_check.cpp)
+inline uint64_t vertices_persistent_piece(uint64_t n, uint64_t asked, uint64_t pass_target, bool host, uint32_t iterations,
+                                          uint32_t max_bounces, uint32_t channels, uint32_t blocks_max, uint32_t batch_max) {
+  return rays_persistent_piece(vertices_piece(n, asked, pass_target, host, iterations, max_bounces, channels), iterations, blocks_max,
+                               batch_max);
+}
 // n * iterations * (max_bounces + 1) vertices: every per-vertex array (24 B per vertex at most) fits a 64-bit byte index
 constexpr uint64_t VERTICES_MAX = 1ull << 56;
 inline bool vertices_fit(uint64_t n, uint32_t iterations, uint32_t max_bounces) {

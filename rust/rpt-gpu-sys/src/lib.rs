@@ -56,6 +56,10 @@ pub mod ffi {
     /// `rptgpu_bake_probes[_device]`, run the call's paths in the persistent path kernel (read where
     /// `rptgpu_rays_persistent_supported` exists and returns 1)
     pub const RPT_FLAG_RAYS_PERSISTENT: u32 = 32;
+    /// include/rpt_gpu_vertices_persistent.h: in `RptVertexQuery::flags` of `rptgpu_trace_vertices[_device]`, run the call's
+    /// paths in the persistent path kernel, which writes each vertex where it makes it (read where
+    /// `rptgpu_vertices_persistent_supported` exists and returns 1)
+    pub const RPT_FLAG_VERTICES_PERSISTENT: u32 = 64;
     pub const RPT_COLLECTIVE_DEFAULT: u32 = 0;
     pub const RPT_COLLECTIVE_GATHER: u32 = 1;
     pub const RPT_COLLECTIVE_REDUCE: u32 = 2;
@@ -540,6 +544,13 @@ pub mod ffi {
     // without it ignores the flag and is detected with dlsym("rptgpu_rays_persistent_supported"); this crate links it like the rest)
     extern "C" {
         pub fn rptgpu_rays_persistent_supported() -> c_int;
+    }
+
+    // include/rpt_gpu_vertices_persistent.h: RPT_FLAG_VERTICES_PERSISTENT's detection — an optional addition within ABI 7 (a
+    // library without it ignores the flag and is detected with dlsym("rptgpu_vertices_persistent_supported"); this crate links
+    // it like the rest)
+    extern "C" {
+        pub fn rptgpu_vertices_persistent_supported() -> c_int;
     }
 
     // include/rpt_gpu_vertices.h: the vertices of the paths rptgpu_trace_rays runs — optional additions within ABI 7 (a
