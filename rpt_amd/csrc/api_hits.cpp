@@ -76,24 +76,6 @@ void copy_hits_out(const rptdev::HitOut& src, const rptdev::HitOut& dst, uint64_
   if (ch & RPT_HIT_ALBEDO) HIP_TRY(hipMemcpyAsync(dst.albedo, src.albedo, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
 }
 
-// the frame of the entry points behind their argument checks (as api_occlusion.cpp's)
-template <class Body> int hits_call(rptgpu_scene* h, hipStream_t user_stream, Body&& body) {
-  auto t0 = std::chrono::steady_clock::now();
-  const int rc = guarded(h, h->device, [&]() -> int {
-    struct EventPairs { // (as render_impl: a call leaves no event pair behind, however it ends)
-      rptgpu_scene* h;
-      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
-    } event_pairs{h};
-    (void)hipGetLastError();
-    if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
-    body();
-    return drain_call(h, h->has_deep && h->gen_overflow.p);
-  });
-  if (rc != RPTGPU_OK) return rc;
-  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return RPTGPU_OK;
-}
-
 // (run_pass's decision: per-tree queries for scenes with deep trees — under RPT_FLAG_GENERAL_TRAVERSAL only where a group
 // with tree children leaves no other walker)
 bool query_by_object(const rptgpu_scene* h, uint32_t flags) {
@@ -110,7 +92,7 @@ int first_hits(rptgpu_scene* h, uint64_t n, const double* origins, const double*
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n) return RPTGPU_OK;
-  return hits_call(h, user_stream, [&]() {
+  return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
     const KernelTable* kt = table_for(q->precision_mode, h->ext_shapes);
     const bool prof = (q->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
@@ -166,6 +148,7 @@ int first_hits(rptgpu_scene* h, uint64_t n, const double* origins, const double*
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
+    return h->has_deep && h->gen_overflow.p;
   });
 }
 
@@ -202,7 +185,7 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n_views) return RPTGPU_OK;
-  return hits_call(h, user_stream, [&]() {
+  return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
     const KernelTable* kt = table_for(q->precision_mode, h->ext_shapes);
     const uint32_t ch = out->channels;
@@ -273,6 +256,7 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
+    return h->has_deep && h->gen_overflow.p;
   });
 }
 

@@ -1,5 +1,6 @@
 // api_internal.h — what the files behind the C ABI of include/rpt_gpu.h share: the handle, device buffers, the error
-// convention and the entry points' frame (guarded), the RCCL binding.  The ABI's implementation is split by concern
+// convention and the entry points' frames (guarded; device_call around a call's kernels), the steps the calls over pieces
+// share, the RCCL binding.  The ABI's implementation is split by concern
 // (round 6; it was one 1 900-line api.cpp):
 //   api_common.cpp   errors, the RCCL loader, kernel tables, version / strerror / stats
 //   api_scene.cpp    RptSceneOptions, rptgpu_scene_create[_opts] (flatten, open the device, plan, apply, upload), the live
@@ -15,8 +16,9 @@
 //   api_comm.cpp     communicator, rptgpu_render_batch_reduce (the library-owned exchange and its failure paths),
 //                    rptgpu_render_batch_emulate_ranks
 //   api_buffer.cpp   the device-resident Buffer
-//   api_rays.cpp     rptgpu_trace_rays[_device]: the wavefront pipeline over rays the caller supplies, in pieces
-//   api_probes.cpp   rptgpu_bake_probes[_device]: light probes (SH9 radiance, irradiance) through the same driver, in pieces
+//   api_rays.cpp     rptgpu_trace_rays[_device]: the path drivers over rays the caller supplies, in pieces — and that piece
+//                    loop itself (trace_ray_pieces), which the next file and api_vertices.cpp run too
+//   api_probes.cpp   rptgpu_bake_probes[_device]: light probes (SH9 radiance, irradiance) through the same loop
 //   api_views.cpp    rptgpu_render_views[_seeded][_device]: batches of perspective, orthographic and panoramic views through the
 //                    same driver, in pieces of consecutive (view, pixel) indices, with one seed or a seed per view
 //   api_views_denoise.cpp rptgpu_render_views_denoised[_device]: per batch the views driver into a device frame and one
@@ -26,8 +28,8 @@
 //   api_hits.cpp     rptgpu_first_hits[_device], rptgpu_render_views_aov[_seeded][_device]: the first hit's record for the caller's rays
 //                    (one fused kernel, or the per-tree closest-hit query, in pieces) and rptgpu_render_aov's sums for
 //                    every view of a batch (raygen, closest-hit query and fold in passes over render_views' pieces)
-//   api_vertices.cpp rptgpu_trace_vertices[_device]: api_rays.cpp's pieces with a vertex sink in their RaySource — run_pass then
-//                    also carries every path's vertices into the caller's arrays (kernels/wf_vertices.inc)
+//   api_vertices.cpp rptgpu_trace_vertices[_device]: api_rays.cpp's loop with a vertex sink in each piece's RaySource — the
+//                    drivers then also carry every path's vertices into the caller's arrays
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -47,6 +49,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -363,42 +366,67 @@ void event_pair_end(rptgpu_scene* h, int kind, int pair);
 // traversal outgrows its columns (they are sized from the scene, so that is a bug, not an input): with read_overflow the
 // flag rides with the synchronisation and is cleared, so that the flag of one call never surfaces in the next.
 int drain_call(rptgpu_scene* h, bool read_overflow);
-// Where the paths of a wavefront pass start — the one step of run_pass that knows: the pixels of a camera (rpt_raygen), or a
-// piece of the caller's rays (rpt_raygen_rays: fr.npix rays at origins / dirs on the device, [npix][3] f64, their streams
-// continuing at first_draw; ids_out: the piece's stream ids id_base + i are written there, see kernels/wavefront.inc)
-// ... or a piece of light probes (rpt_raygen_probes; probe = the RPT_PROBE_* kind, origins = the positions, dirs = the
-// normals).  Probes also choose the two steps behind the depth loop: rpt_resolve_probes into sums of probe_width(kind)
-// words per probe and rpt_finish_probes with probe_scale (api_probes.cpp)
+// The frame of an entry point that runs kernels on the handle's stream, behind its argument checks (h is not null): guarded
+// around the call's clock, a clean slate, the wait for the caller's stream (user_stream: the one the call's device inputs were
+// produced on; nullptr: none, or the body waits itself, where it has to do something first), the body, drain_call.  The
+// body enqueues the call's work and returns drain_call's read_overflow — whether this call ran rpt_tree_generic.  A call that
+// fails leaves RptStats::total_ms as it was.
+template <class Body> int device_call(rptgpu_scene* h, hipStream_t user_stream, Body&& body) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = guarded(h, h->device, [&]() -> int {
+    // a call leaves no event pair behind, however it ends (one that ends well has resolved them: drain_call)
+    struct EventPairs {
+      rptgpu_scene* h;
+      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
+    } event_pairs{h};
+    // hipGetLastError() reports the thread's LAST failed runtime call, whoever made it (another library in the process,
+    // an unchecked clean-up call): start from a clean slate so that the body's checks speak about this call's launches
+    (void)hipGetLastError();
+    if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
+    const bool read_overflow = body();
+    return drain_call(h, read_overflow);
+  });
+  if (rc != RPTGPU_OK) return rc;
+  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return RPTGPU_OK;
+}
+// Where the paths of a driver's batch start: a camera's pixels, or a piece of one of three kinds, told apart by which
+// pointers are set.  Both drivers read it; each line names the fields its form reads, and every other field keeps its default.
+//   a camera (render_impl)       cam.  Wavefront: rpt_raygen.  Persistent: rpt_paths.
+//   the caller's rays (api_rays.cpp)  origins, dirs ([fr.npix][3] f64 on the device), first_draw (where every stream continues).
+//                                Wavefront: rpt_raygen_rays, which also writes the piece's stream ids id_base + i to ids_out
+//                                (nullptr: the caller named them, and they lie in Frame::pixels).  Persistent: rpt_paths_rays;
+//                                Frame::pixels holds the ids already (the caller's, or rpt_rays_ids'), ids_out and id_base are
+//                                not read.
+//   ... with vertices (api_vertices.cpp)  the same, and vertices: where the vertices of the piece's paths go — the caller's arrays
+//                                or their staging, offset to the piece; s_first is filled in per pass or launch.
+//                                Wavefront: rpt_vertices_store and rpt_vertices_fold beside the ray call's kernels.
+//                                Persistent: rpt_paths_vertices, which writes them itself.
+//   light probes (api_probes.cpp)  probe (the RPT_PROBE_* kind), origins = the positions, dirs = the normals (nullptr for
+//                                RPT_PROBE_SH9), probe_scale (4 pi / S or pi / S), ids_out and id_base as for rays.
+//                                Wavefront: rpt_raygen_probes, rpt_resolve_probes into sums of probe_width(kind) words per
+//                                probe, rpt_finish_probes.  Persistent: rpt_paths_rays, rpt_project_probes, rpt_finish_probes.
+//   a batch of views (api_views.cpp)  views (the call's records on the device), view_width, view_height, view_base: the piece
+//                                is the fr.npix consecutive indices from view_base on, index j = view * (view_width *
+//                                view_height) + pixel.  view_seeds (nullptr: every view's seed is the Frame's): the call's
+//                                seeds on the device, one per view; Frame::seed is not read then.
+//                                Wavefront: rpt_raygen_views writes the pixels to ids_out; with view_seeds
+//                                rpt_raygen_views_seeded also writes each index's seed to seeds_out, where rpt_shade_seeded
+//                                reads it.  Persistent: rpt_paths_views; view_seeds always, view_of the view of each index
+//                                counted from the piece's first (rpt_views_ids wrote it, and the pixels into Frame::pixels).
 struct RaySource {
   const rptdev::Camera* cam;
   const double *origins, *dirs;
   uint32_t first_draw, id_base;
   uint32_t* ids_out;
   int probe = -1;           // < 0: not probes
-  double probe_scale = 0.0; // 4 pi / S or pi / S
-  // ... or a piece of a batch of views (rpt_raygen_views; api_views.cpp): fr.npix consecutive indices of the call from
-  // view_base on, index j = view * (view_width * view_height) + pixel; views: the call's records on the device; ids_out
-  // receives the pixels
+  double probe_scale = 0.0;
   const rptdev::View* views = nullptr;
   uint32_t view_width = 0, view_height = 0;
   uint64_t view_base = 0;
-  // ... whose views have seeds of their own (rpt_raygen_views_seeded, rpt_shade_seeded): view_seeds, the call's seeds on the
-  // device, one per view; seeds_out receives the seed of each index of the piece, where rpt_shade_seeded reads it.  The
-  // piece's Frame::seed is not read then.  nullptr: every view's seed is the Frame's
   const uint64_t* view_seeds = nullptr;
   uint64_t* seeds_out = nullptr;
-  // ... or that piece in the persistent kernel (render_persistent -> rpt_paths_views, RPT_FLAG_VIEWS_PERSISTENT): views,
-  // view_width, view_height and view_base as above, view_seeds one seed per view of the call WHATEVER the seed stride, and
-  // view_of the view of each index of the piece counted from the piece's first (rpt_views_ids wrote it, and the pixels
-  // into the piece's Frame::pixels)
   const uint32_t* view_of = nullptr;
-  // ... or a piece of the caller's rays or probes in the persistent kernel (render_persistent -> rpt_paths_rays,
-  // RPT_FLAG_RAYS_PERSISTENT): origins, dirs, first_draw, probe and probe_scale as above with cam and views null; the piece's
-  // Frame::pixels holds the stream ids already (the caller's, or rpt_rays_ids'), and ids_out and id_base are not read
-  // rptgpu_trace_vertices (api_vertices.cpp): where the vertices of the piece's paths go — the caller's arrays or their
-  // staging, offset to the piece; run_pass fills in s_first per pass.  nullptr (every other call): nothing is launched for it.
-  // With origins alone, as for rpt_paths_rays, render_persistent launches rpt_paths_vertices instead (RPT_FLAG_VERTICES_PERSISTENT),
-  // which writes the vertices itself; s_first is then set per launch
   const rptdev::VertexOut* vertices = nullptr;
 };
 // api_views.cpp: what is wrong with an RptViewQuery / with one view of a call with query q (nullptr: nothing); shared with
@@ -420,23 +448,81 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
 const char* bad_probe_query(const RptProbeQuery* q);
-// the piece of a call of rptgpu_trace_rays / rptgpu_bake_probes under RPT_FLAG_RAYS_PERSISTENT: `piece` (rptplan::rays_piece's)
-// capped by the persistent kernel's work counter at the most resident blocks any instantiation has
-inline uint64_t handle_rays_persistent_piece(const rptgpu_scene* h, uint64_t piece, uint32_t iterations) {
-  const uint32_t blocks_max = (uint32_t)std::max(1, h->num_cus) * RPT_PATHS_WAVES_PER_CU_MAX;
-  return rptplan::rays_persistent_piece(piece, iterations, blocks_max, RPT_PATHS_BATCH_MAX);
-}
 // the pass planner's input for a call over npix pixels or rays: what its passes share, and the device's state right now
 rptplan::PassInput pass_input(rptgpu_scene* h, uint32_t npix, uint32_t iterations);
 void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in);
+
+// ---- what the calls that run a path driver over PIECES share (api_rays.cpp, api_probes.cpp, api_vertices.cpp, api_views.cpp):
+// a piece of rays, probes or (view, pixel) indices is the "frame" of its own passes or launches
+// the RptRenderParams of such a call, from its query q: what render_wavefront reads of it, and render_persistent
+template <class Query> RptRenderParams piece_params(const Query& q, uint32_t iterations, double exposure_value) {
+  RptRenderParams p{};
+  p.max_bounces = q.max_bounces; p.iterations = iterations; p.exposure_value = exposure_value;
+  p.seed = q.seed; p.sample_index_base = q.sample_index_base; p.precision_mode = q.precision_mode; p.flags = q.flags;
+  return p;
+}
+// the paths one pass may hold with every level of every path: what bounds a piece (rptplan::rays_piece and its kin take it)
+inline uint64_t piece_pass_target(rptgpu_scene* h, uint32_t iterations, uint32_t max_bounces) {
+  rptplan::PassInput in = pass_input(h, 1, iterations);
+  in.remaining = iterations;
+  in.ratio = (double)max_bounces + 1.0;
+  pass_input_now(h, in);
+  return rptplan::plan_pass(in).target;
+}
+// the persistent kernel on request (`flag`: the call's RPT_FLAG_*_PERSISTENT) — unless the scene has a group with tree
+// children, which only the wavefront pipeline walks (use_wavefront: such a scene cannot honour the request, as for a render)
+inline bool piece_persistent(const rptgpu_scene* h, uint32_t flags, uint32_t flag) {
+  return (flags & flag) && !use_wavefront(h, 0, false);
+}
+// ... whose pieces are also at most what a launch's 32-bit work counter holds, at the most resident blocks any
+// instantiation has: `piece` (the planner's), capped
+inline uint64_t persistent_piece(const rptgpu_scene* h, uint64_t piece, uint32_t iterations) {
+  return rptplan::rays_persistent_piece(piece, iterations, (uint32_t)std::max(1, h->num_cus) * RPT_PATHS_WAVES_PER_CU_MAX, RPT_PATHS_BATCH_MAX);
+}
+// the Frame of a piece of m items whose stream ids lie (or will lie) at `pixels`
+inline rptdev::Frame piece_frame(rptgpu_scene* h, const RptRenderParams& p, const uint32_t* pixels, uint64_t m) {
+  rptdev::Frame fr{};
+  fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = pixels;
+  fr.max_bounces = p.max_bounces; fr.seed = p.seed; fr.accum = h->accum.p;
+  return fr;
+}
 // the wavefront driver: the batch in passes from `src`, then rpt_finish into `out` (api_render.cpp)
 void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const RaySource& src,
                       void* out, bool out_f32, bool packed, bool prof);
-// the persistent driver: the batch in launches of rpt_paths (src.cam), rpt_paths_views (src.views), rpt_paths_rays
-// (src.origins alone) or rpt_paths_vertices (src.origins with src.vertices), rpt_sum_samples behind each, then rpt_finish into `out` — probes (src.probe >= 0): rpt_project_probes
-// and rpt_finish_probes in their places (api_render.cpp)
+// the persistent driver: the batch in launches of the form of the persistent kernel src asks for (KernelTable::paths),
+// rpt_sum_samples behind each, then rpt_finish into `out` — probes: rpt_project_probes and rpt_finish_probes in their places
+// (api_render.cpp)
 void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr, const RaySource& src,
                        void* out, bool out_f32, bool packed, bool prof);
+// a piece through the driver of its call's route, the results packed into `out` in the order of the piece's items
+inline void render_piece(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, const rptdev::Frame& fr, const RaySource& src,
+                         void* out, bool out_f32, bool persistent) {
+  const bool prof = (p.flags & RPT_FLAG_PROFILE_KERNELS) != 0;
+  if (persistent) render_persistent(h, kt, p, fr, src, out, out_f32, true, prof);
+  else render_wavefront(h, kt, p, fr, src, out, out_f32, true, prof);
+  HIP_TRY(hipGetLastError());
+}
+// A call over n rays or probes of the caller, and the loop that runs it in pieces (api_rays.cpp; rptgpu_trace_rays,
+// rptgpu_bake_probes, rptgpu_trace_vertices and their _device forms).  on_device: a, b, streams and out are device pointers,
+// read and written where they lie; else a piece at a time is staged in arrays the handle keeps.
+struct RayPieces {
+  uint64_t n;
+  const double *a, *b;     // [n][3] each: origins and directions, or positions and normals; b may be null (it is not read then)
+  const uint32_t* streams; // [n] stream ids; nullptr: item i has id i
+  bool on_device;
+  uint64_t piece;          // items per piece
+  bool persistent;         // the route (piece_persistent); the piece is then persistent_piece's
+  RptRenderParams p;       // piece_params
+  uint32_t first_draw;
+  uint32_t width;          // f64 words of an item's result: 3, or probe_width(kind)
+  double* out;             // [n][width]; nullptr: the call does not return them (they stay in the handle's array)
+  int probe = -1;          // light probes: the RPT_PROBE_* kind and its RaySource::probe_scale
+  double probe_scale = 0.0;
+};
+// before(base, m, src): the piece's RaySource is complete but for what the call adds, its inputs are on the device;
+// after(base, m): the piece's work is enqueued, a host caller's results are not yet copied out.  Either may be empty.
+void trace_ray_pieces(rptgpu_scene* h, const RayPieces& c, const std::function<void(uint64_t, uint64_t, RaySource&)>& before,
+                      const std::function<void(uint64_t, uint64_t)>& after);
 // packed (with d_out, f32 or f64): d_out receives only this part's pixels, [npix][3] in the order of the part's pixel list.
 // d_list (device, n_list pixel indices; requires packed and d_out): render exactly those pixels instead of the part's list,
 // without touching the cached partition (the adaptive buffer's active pixels, api_buffer.cpp)

@@ -78,24 +78,6 @@ struct Occlusion {
   }
 };
 
-// the frame of both entry points behind their argument checks
-template <class Body> int occlusion_call(rptgpu_scene* h, hipStream_t user_stream, Body&& body) {
-  auto t0 = std::chrono::steady_clock::now();
-  const int rc = guarded(h, h->device, [&]() -> int {
-    struct EventPairs { // (as render_impl: a call leaves no event pair behind, however it ends)
-      rptgpu_scene* h;
-      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
-    } event_pairs{h};
-    (void)hipGetLastError();
-    if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
-    body();
-    return drain_call(h, h->has_deep && h->gen_overflow.p);
-  });
-  if (rc != RPTGPU_OK) return rc;
-  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return RPTGPU_OK;
-}
-
 // on_device: origins, dirs, max_t and out are device pointers (user_stream: the stream their producer ran on)
 int occluded(rptgpu_scene* h, uint64_t n, const double* origins, const double* dirs, const double* max_t,
              const RptVisibilityQuery* q, uint8_t* out, bool on_device, hipStream_t user_stream) {
@@ -105,7 +87,7 @@ int occluded(rptgpu_scene* h, uint64_t n, const double* origins, const double* d
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n) return RPTGPU_OK;
-  return occlusion_call(h, user_stream, [&]() {
+  return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
     Occlusion oc(h, q->precision_mode, q->flags);
     const uint64_t piece = rptplan::occlusion_piece(n, oc.asked, oc.pass_target);
@@ -133,6 +115,7 @@ int occluded(rptgpu_scene* h, uint64_t n, const double* origins, const double* d
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
+    return h->has_deep && h->gen_overflow.p;
   });
 }
 
@@ -146,7 +129,7 @@ int bake_ao(rptgpu_scene* h, uint64_t n, const double* positions, const double* 
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n) return RPTGPU_OK;
-  return occlusion_call(h, user_stream, [&]() {
+  return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
     Occlusion oc(h, q->precision_mode, q->flags);
     const uint32_t S = q->samples;
@@ -188,6 +171,7 @@ int bake_ao(rptgpu_scene* h, uint64_t n, const double* positions, const double* 
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
+    return h->has_deep && h->gen_overflow.p;
   });
 }
 

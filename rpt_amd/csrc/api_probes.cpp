@@ -1,7 +1,8 @@
 // api_probes.cpp — rptgpu_bake_probes[_device]: light probes baked on the device (include/rpt_gpu.h; see
 // api_internal.h).  A probe is `samples` paths whose first rays the library makes itself, so the call is rptgpu_trace_rays'
-// with another first step and another last one: the probes go through the wavefront driver of api_render.cpp in pieces of
-// whole probes — a piece is the "frame" of its own passes, its probes are the pixels, the samples are the iterations —,
+// with another first step and another last one, and runs api_rays.cpp's piece loop (trace_ray_pieces) with a probe kind in
+// its description: the probes go through the wavefront driver of api_render.cpp in pieces of whole probes — a piece is the
+// "frame" of its own passes, its probes are the pixels, the samples are the iterations —,
 // rpt_raygen_probes draws the directions (RaySource::probe), rpt_resolve_probes projects the paths' radiance into the
 // piece's running sums and rpt_finish_probes scales them into the caller's layout.  The depth loop, the pass planning with
 // its restarts and the piece arithmetic (rptplan::rays_piece) are the ray call's, unchanged.
@@ -43,77 +44,22 @@ int bake_probes(rptgpu_scene* h, uint64_t n, const double* positions, const doub
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n) return RPTGPU_OK;
-  auto t0 = std::chrono::steady_clock::now();
-  const int rc = guarded(h, h->device, [&]() -> int {
-    struct EventPairs { // (as render_impl: a call leaves no event pair behind, however it ends)
-      rptgpu_scene* h;
-      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
-    } event_pairs{h};
-    (void)hipGetLastError();
-    hipStream_t st = h->stream;
-    const KernelTable* kt = table_for(q->precision_mode, h->ext_shapes);
-    const bool prof = (q->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
+  return device_call(h, user_stream, [&]() {
     const bool with_normals = q->kind == RPT_PROBE_IRRADIANCE;
-    const uint32_t width = probe_width(q->kind);
-    if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
-    h->dscene.force_general = (q->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
-    RptRenderParams p{}; // what render_wavefront reads of it
-    p.max_bounces = q->max_bounces; p.iterations = q->samples; p.seed = q->seed;
-    p.sample_index_base = q->sample_index_base; p.precision_mode = q->precision_mode; p.flags = q->flags;
     // the piece: whole probes, at most the paths one pass may hold with every level of every path — a pass is at least
     // one sample of every probe of the piece (rptplan::rays_piece, as it stands)
-    rptplan::PassInput in = pass_input(h, 1, q->samples);
-    in.remaining = q->samples;
-    in.ratio = (double)q->max_bounces + 1.0;
-    pass_input_now(h, in);
     uint64_t asked = 0; // tests: pieces of a few probes
     if (const char* e = std::getenv("RPTGPU_PROBES_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    uint64_t piece = rptplan::rays_piece(n, asked, rptplan::plan_pass(in).target);
-    // the persistent kernel on request, as in api_rays.cpp: not for a scene only the wavefront pipeline walks, and in
-    // pieces a launch's work counter holds
-    const bool persistent = (q->flags & RPT_FLAG_RAYS_PERSISTENT) && !use_wavefront(h, 0, false);
-    if (persistent) piece = handle_rays_persistent_piece(h, piece, q->samples);
-    h->accum.alloc((uint64_t)width * piece);
-    if (!on_device) {
-      h->rays_o.alloc(3 * piece);
-      if (with_normals) h->rays_d.alloc(3 * piece);
-      h->rays_out.alloc((uint64_t)width * piece);
-    }
-    if (!on_device || !streams) h->ray_ids.alloc(piece);
+    uint64_t piece = rptplan::rays_piece(n, asked, piece_pass_target(h, q->samples, q->max_bounces));
+    const bool persistent = piece_persistent(h, q->flags, RPT_FLAG_RAYS_PERSISTENT);
+    if (persistent) piece = persistent_piece(h, piece, q->samples);
     const double scale = (with_normals ? 3.141592653589793 : 12.566370614359172) / (double)q->samples;
-    for (uint64_t base = 0; base < n; base += piece) {
-      const uint64_t m = std::min(piece, n - base);
-      const double *d_pos = positions + 3 * base, *d_nrm = with_normals ? normals + 3 * base : nullptr;
-      const uint32_t* d_ids = streams ? streams + base : h->ray_ids.p;
-      double* d_out = out + (uint64_t)width * base;
-      if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(h->rays_o.p, d_pos, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
-        if (with_normals) HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_nrm, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
-        if (streams) HIP_TRY(hipMemcpyAsync(h->ray_ids.p, d_ids, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        d_pos = h->rays_o.p; d_nrm = with_normals ? h->rays_d.p : nullptr; d_ids = h->ray_ids.p; d_out = h->rays_out.p;
-      }
-      rptdev::Frame fr{};
-      fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = d_ids;
-      fr.max_bounces = q->max_bounces; fr.seed = q->seed; fr.accum = h->accum.p;
-      RaySource src{nullptr, d_pos, d_nrm, 0u, (uint32_t)base, streams ? nullptr : h->ray_ids.p};
-      src.probe = (int)q->kind; src.probe_scale = scale;
-      if (persistent) { // (the ids the wavefront's first step would write: the kernel reads them from the first launch on)
-        if (!streams) kt->rays_ids(st, (uint32_t)base, (uint32_t)m, h->ray_ids.p);
-        render_persistent(h, kt, p, fr, src, d_out, false, true, prof);
-      } else {
-        render_wavefront(h, kt, p, fr, src, d_out, false, true, prof);
-      }
-      HIP_TRY(hipGetLastError());
-      if (!on_device) { // the staging arrays are the next piece's, too
-        HIP_TRY(hipMemcpyAsync(out + (uint64_t)width * base, d_out, (uint64_t)width * m * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-      }
-    }
-    return drain_call(h, !persistent && h->has_deep && h->gen_overflow.p);
+    // (the normals are staged and read for RPT_PROBE_IRRADIANCE only; a probe's streams start at draw 0, and it has no exposure)
+    trace_ray_pieces(h, RayPieces{n, positions, with_normals ? normals : nullptr, streams, on_device, piece, persistent,
+                                  piece_params(*q, q->samples, 0.0), 0u, probe_width(q->kind), out, (int)q->kind, scale},
+                     nullptr, nullptr);
+    return !persistent && h->has_deep && h->gen_overflow.p;
   });
-  if (rc != RPTGPU_OK) return rc;
-  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return RPTGPU_OK;
 }
 
 } // namespace

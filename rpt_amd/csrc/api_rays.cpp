@@ -1,8 +1,10 @@
 // api_rays.cpp — rptgpu_trace_rays[_device]: the full path estimator for rays the caller supplies (include/rpt_gpu.h,
-// DESIGN.md §13; see api_internal.h).  The rays go through the wavefront driver of api_render.cpp in pieces: a piece is
-// the "frame" of its own passes, its rays are the pixels, rpt_raygen_rays is the passes' first step (RaySource) and
-// everything behind it — the depth loop, the pass planning with its restarts, rpt_resolve, rpt_finish in packed form —
-// is a render's.  A host caller's piece is staged in arrays the handle keeps; a device caller's is read where it lies.
+// DESIGN.md §13; see api_internal.h), and the piece loop it shares with rptgpu_bake_probes (api_probes.cpp) and
+// rptgpu_trace_vertices (api_vertices.cpp): trace_ray_pieces.  The rays go through the wavefront driver of api_render.cpp in
+// pieces: a piece is the "frame" of its own passes, its rays are the pixels, rpt_raygen_rays is the passes' first step
+// (RaySource) and everything behind it — the depth loop, the pass planning with its restarts, rpt_resolve, rpt_finish in
+// packed form — is a render's.  A host caller's piece is staged in arrays the handle keeps; a device caller's is read where
+// it lies.
 // Under RPT_FLAG_RAYS_PERSISTENT (include/rpt_gpu_rays_persistent.h) the same pieces, staged the same way,
 // go through the persistent driver instead: rpt_paths_rays reads each ray where it hands out its work, and rpt_sum_samples
 // and the packed rpt_finish behind its launches are a render's.  The same bits.
@@ -25,6 +27,46 @@ const char* bad_ray_query(const RptRayQuery* q) {
   return nullptr;
 }
 
+void trace_ray_pieces(rptgpu_scene* h, const RayPieces& c, const std::function<void(uint64_t, uint64_t, RaySource&)>& before,
+                      const std::function<void(uint64_t, uint64_t)>& after) {
+  hipStream_t st = h->stream;
+  const KernelTable* kt = table_for(c.p.precision_mode, h->ext_shapes);
+  h->dscene.force_general = (c.p.flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
+  const uint64_t piece = c.piece, w = c.width;
+  h->accum.alloc(w * piece);
+  // the drivers write a piece's results somewhere: the device caller's array, or the handle's
+  if (!c.on_device || !c.out) h->rays_out.alloc(w * piece);
+  if (!c.on_device) {
+    h->rays_o.alloc(3 * piece);
+    if (c.b) h->rays_d.alloc(3 * piece);
+  }
+  if (!c.on_device || !c.streams) h->ray_ids.alloc(piece);
+  for (uint64_t base = 0; base < c.n; base += piece) {
+    const uint64_t m = std::min(piece, c.n - base);
+    const double *d_a = c.a + 3 * base, *d_b = c.b ? c.b + 3 * base : nullptr;
+    const uint32_t* d_ids = c.streams ? c.streams + base : h->ray_ids.p;
+    double* d_out = c.on_device && c.out ? c.out + w * base : h->rays_out.p;
+    if (!c.on_device) {
+      HIP_TRY(hipMemcpyAsync(h->rays_o.p, d_a, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
+      if (c.b) HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_b, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
+      if (c.streams) HIP_TRY(hipMemcpyAsync(h->ray_ids.p, d_ids, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      d_a = h->rays_o.p; d_b = c.b ? h->rays_d.p : nullptr; d_ids = h->ray_ids.p;
+    }
+    const rptdev::Frame fr = piece_frame(h, c.p, d_ids, m);
+    RaySource src{nullptr, d_a, d_b, c.first_draw, (uint32_t)base, c.streams ? nullptr : h->ray_ids.p};
+    src.probe = c.probe; src.probe_scale = c.probe_scale;
+    if (before) before(base, m, src);
+    // (the ids the wavefront's first step would write: the persistent kernel reads them from the first launch on)
+    if (c.persistent && !c.streams) kt->rays_ids(st, (uint32_t)base, (uint32_t)m, h->ray_ids.p);
+    render_piece(h, kt, c.p, fr, src, d_out, false, c.persistent);
+    if (after) after(base, m);
+    if (!c.on_device) { // the staging arrays are the next piece's, too
+      if (c.out) HIP_TRY(hipMemcpyAsync(c.out + w * base, d_out, w * m * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+  }
+}
+
 namespace {
 
 // on_device: origins, dirs, streams and out are device pointers (user_stream: the stream their producer ran on)
@@ -38,69 +80,18 @@ int trace_rays(rptgpu_scene* h, uint64_t n, const double* origins, const double*
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n) return RPTGPU_OK;
-  auto t0 = std::chrono::steady_clock::now();
-  const int rc = guarded(h, h->device, [&]() -> int {
-    struct EventPairs { // (as render_impl: a call leaves no event pair behind, however it ends)
-      rptgpu_scene* h;
-      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
-    } event_pairs{h};
-    (void)hipGetLastError();
-    hipStream_t st = h->stream;
-    const KernelTable* kt = table_for(q->precision_mode, h->ext_shapes);
-    const bool prof = (q->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
-    if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
-    h->dscene.force_general = (q->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
-    RptRenderParams p{}; // what render_wavefront reads of it
-    p.max_bounces = q->max_bounces; p.iterations = q->iterations; p.exposure_value = q->exposure_value;
-    p.seed = q->seed; p.sample_index_base = q->sample_index_base; p.precision_mode = q->precision_mode; p.flags = q->flags;
+  return device_call(h, user_stream, [&]() {
     // the piece: at most the paths one pass may hold with every level of every path (rptplan::rays_piece)
-    rptplan::PassInput in = pass_input(h, 1, q->iterations);
-    in.remaining = q->iterations;
-    in.ratio = (double)q->max_bounces + 1.0;
-    pass_input_now(h, in);
     uint64_t asked = 0; // tests: pieces of a few rays
     if (const char* e = std::getenv("RPTGPU_RAYS_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    uint64_t piece = rptplan::rays_piece(n, asked, rptplan::plan_pass(in).target);
-    // the persistent kernel on request — unless the scene has a group with tree children, which only the wavefront
-    // pipeline walks (use_wavefront: such a scene cannot honour the request, as for a render); a piece is then also at
-    // most what a launch's work counter holds
-    const bool persistent = (q->flags & RPT_FLAG_RAYS_PERSISTENT) && !use_wavefront(h, 0, false);
-    if (persistent) piece = handle_rays_persistent_piece(h, piece, q->iterations);
-    h->accum.alloc(3 * piece);
-    if (!on_device) { h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece); h->rays_out.alloc(3 * piece); }
-    if (!on_device || !streams) h->ray_ids.alloc(piece);
-    for (uint64_t base = 0; base < n; base += piece) {
-      const uint64_t m = std::min(piece, n - base);
-      const double *d_o = origins + 3 * base, *d_d = dirs + 3 * base;
-      const uint32_t* d_ids = streams ? streams + base : h->ray_ids.p;
-      double* d_out = out + 3 * base;
-      if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(h->rays_o.p, d_o, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_d, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
-        if (streams) HIP_TRY(hipMemcpyAsync(h->ray_ids.p, d_ids, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        d_o = h->rays_o.p; d_d = h->rays_d.p; d_ids = h->ray_ids.p; d_out = h->rays_out.p;
-      }
-      rptdev::Frame fr{};
-      fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = d_ids;
-      fr.max_bounces = q->max_bounces; fr.seed = q->seed; fr.accum = h->accum.p;
-      const RaySource src{nullptr, d_o, d_d, q->first_draw, (uint32_t)base, streams ? nullptr : h->ray_ids.p};
-      if (persistent) { // (the ids the wavefront's first step would write: the kernel reads them from the first launch on)
-        if (!streams) kt->rays_ids(st, (uint32_t)base, (uint32_t)m, h->ray_ids.p);
-        render_persistent(h, kt, p, fr, src, d_out, false, true, prof);
-      } else {
-        render_wavefront(h, kt, p, fr, src, d_out, false, true, prof);
-      }
-      HIP_TRY(hipGetLastError());
-      if (!on_device) { // the staging arrays are the next piece's, too
-        HIP_TRY(hipMemcpyAsync(out + 3 * base, d_out, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-      }
-    }
-    return drain_call(h, !persistent && h->has_deep && h->gen_overflow.p);
+    uint64_t piece = rptplan::rays_piece(n, asked, piece_pass_target(h, q->iterations, q->max_bounces));
+    const bool persistent = piece_persistent(h, q->flags, RPT_FLAG_RAYS_PERSISTENT);
+    if (persistent) piece = persistent_piece(h, piece, q->iterations);
+    trace_ray_pieces(h, RayPieces{n, origins, dirs, streams, on_device, piece, persistent,
+                                  piece_params(*q, q->iterations, q->exposure_value), q->first_draw, 3, out},
+                     nullptr, nullptr);
+    return !persistent && h->has_deep && h->gen_overflow.p;
   });
-  if (rc != RPTGPU_OK) return rc;
-  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return RPTGPU_OK;
 }
 
 } // namespace

@@ -315,35 +315,50 @@ rptdev::PathState path_state(rptgpu_scene* h) {
   return ps;
 }
 
+// the form of the persistent kernel that runs src (RaySource says which fields name which source), and what
+// render_persistent does differently for it
+static int paths_form(const RaySource& src) {
+  if (src.views) return RPT_PATHS_FORM_VIEWS;
+  if (src.cam || !src.origins) return RPT_PATHS_FORM_CAMERA;
+  return src.probe < 0 && src.vertices ? RPT_PATHS_FORM_VERTICES : RPT_PATHS_FORM_RAYS;
+}
+struct PathsFormProps {
+  const char* kname;
+  bool fused_forms; // the kernel has the fused query and the hit pool where the layout offers them
+  bool cull_rects;  // its rays are one camera's: the pre-trace pass gets that camera's screen rectangles
+  bool piece;       // fr is a piece its caller cut to the work counter: checked here
+  bool probes;      // src.probe >= 0 means light probes
+};
+static constexpr PathsFormProps PATHS_FORM_PROPS[RPT_PATHS_FORM_COUNT] = {
+    {"rpt_paths", true, true, false, false},
+    {"rpt_paths_views", true, false, true, false},
+    {"rpt_paths_rays", true, false, true, true},
+    // (the plain hand-out only: neither the fused query nor the pool, whatever the layout offers)
+    {"rpt_paths_vertices", false, false, true, false}};
+
 // the default pipeline: one persistent kernel, the whole path in registers; the batch runs as launches of at most
-// spp_l samples per pixel (rptplan::plan_persistent).  The rays are src's: a camera's pixels (src.cam: rpt_paths), or a
-// piece of a batch of views (src.views with view_seeds and view_of: rpt_paths_views — fr is the piece's, its pixels
-// rpt_views_ids' — api_views.cpp), or a piece of the caller's rays or light probes (src.origins with cam and views null:
-// rpt_paths_rays — fr is the piece's, its pixels the stream ids; probes, src.probe >= 0, project each launch's samples into
-// the piece's running sums with rpt_project_probes where rpt_sum_samples stands and end with rpt_finish_probes —
-// api_rays.cpp, api_probes.cpp), or such a piece of rays with a vertex sink (src.vertices: rpt_paths_vertices, which also
-// writes every path's vertices into the sink's arrays, s_first set per launch as run_pass sets it per pass — api_vertices.cpp)
+// spp_l samples per pixel (rptplan::plan_persistent) of the form src asks for — fr is the frame, or the piece of a call's
+// views, rays or probes with its ids in fr.pixels (api_views.cpp, api_rays.cpp) — with rpt_sum_samples behind each and
+// rpt_finish at the end.  Probes project each launch's samples into the piece's running sums with rpt_project_probes where
+// rpt_sum_samples stands and end with rpt_finish_probes; a vertex sink's s_first is set per launch, as run_pass sets it per pass
 void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr,
                        const RaySource& src, void* out, bool out_f32, bool packed, bool prof) {
   hipStream_t st = h->stream;
   const uint32_t npix = fr.npix;
-  const bool views = src.views != nullptr;
-  const bool rays = !views && !src.cam && src.origins != nullptr; // (probes too: src.probe >= 0)
-  const bool probes = rays && src.probe >= 0;
-  const bool vertices = rays && !probes && src.vertices != nullptr;
+  const PathsForm& form = kt->paths[paths_form(src)];
+  const PathsFormProps& fp = PATHS_FORM_PROPS[paths_form(src)];
+  const char* const kname = fp.kname;
+  const bool probes = fp.probes && src.probe >= 0;
+  const bool fused_forms = fp.fused_forms;
+  // the launches' rays, whichever the form reads
   const rptdev::CallerRays cr{src.origins, src.dirs, src.first_draw, probes ? (int32_t)src.probe : -1};
-  const char* const kname = views ? "rpt_paths_views" : vertices ? "rpt_paths_vertices" : rays ? "rpt_paths_rays" : "rpt_paths";
-  const auto max_blocks = views      ? kt->paths_views_max_blocks_per_cu
-                          : vertices ? kt->paths_vertices_max_blocks_per_cu
-                          : rays     ? kt->paths_rays_max_blocks_per_cu
-                                     : kt->paths_max_blocks_per_cu;
-  // (rpt_paths_vertices has the plain hand-out only: neither the fused query nor the pool, whatever the layout offers)
-  const bool fused_forms = !vertices;
+  rptdev::VertexOut vo = src.vertices ? *src.vertices : rptdev::VertexOut{};
   rptdev::ViewRays vr{};
-  if (views) {
+  if (src.views) {
     const uint64_t v0 = src.view_base / ((uint64_t)src.view_width * src.view_height); // the piece's first view
     vr = rptdev::ViewRays{src.views + v0, src.view_seeds + v0, src.view_of, src.view_width, src.view_height};
   }
+  const PathsRays from{src.cam, &vr, &cr, &vo};
   const bool print_launch = std::getenv("RPTGPU_PRINT_LAUNCH") != nullptr;
   const uint64_t lbuf_held = h->lbuf.n * sizeof(double);
   const int64_t free_b = lbuf_held < h->opt.lbuf_bytes ? free_memory() : -1;
@@ -353,7 +368,7 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
   // the fused kernel's pre-trace pass: this render's screen rectangles of the objects it may skip (host_scene.cpp
   // pinhole_screen_rect; none under a lens).  An object without a rectangle is always tested.  A piece of views gets none
   // (cull_n = 0: every test runs — the rectangles are one camera's), and so does a piece of the caller's rays
-  if (RPT_PRETRACE_CULL && lay.pretrace_cull && !views && !rays) {
+  if (RPT_PRETRACE_CULL && lay.pretrace_cull && fp.cull_rects) {
     const rptdev::Camera& cam = *src.cam;
     for (size_t i = 0; i < h->obj_geom.size() && i < 64 && lay.cull_n < (uint32_t)RPT_CULL_MAX; i++) {
       uint32_t r[4];
@@ -368,15 +383,14 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
     }
   }
   const rptplan::PersistentPlan pl = rptplan::plan_persistent(
-      npix, p.iterations, p.max_bounces, h->num_cus, max_blocks(flat ? &lay : nullptr, flat_lds, false),
+      npix, p.iterations, p.max_bounces, h->num_cus, form.max_blocks_per_cu(flat ? &lay : nullptr, flat_lds, false),
       h->opt.lbuf_bytes, lbuf_held, free_b, h->opt.paths_chunk, h->all_flat, h->dscene.force_general, h->flat_layout.obj_filter);
   // a texture environment: the lanes park their lookups in what the wave's LDS share has left (kernels/paths.inc) —
   // unless that costs a resident wave (a flat scene that fills the share)
   bool park = flat && h->opt.env_park != 0 && h->dscene.env_kind != RPT_ENV_COLOR; // (flat scenes: rpt_paths<KdLds>'s stack fills the share)
-  if (park && max_blocks(&lay, flat_lds, true) < pl.per_cu) park = false;
-  // (a piece of views: render_views cut it so that every launch fits the work counter — rptplan::views_items; a piece of
-  // rays or probes: api_rays.cpp / api_probes.cpp, in the same way — rptplan::rays_persistent_piece)
-  if ((views || rays) && rptplan::views_items(npix, pl.spp_l, pl.chunk, pl.nblocks, RPT_PATHS_BATCH_MAX).capped)
+  if (park && form.max_blocks_per_cu(&lay, flat_lds, true) < pl.per_cu) park = false;
+  // (a piece: its caller cut it so that every launch fits the work counter — persistent_piece, api_internal.h)
+  if (fp.piece && rptplan::views_items(npix, pl.spp_l, pl.chunk, pl.nblocks, RPT_PATHS_BATCH_MAX).capped)
     throw std::runtime_error(std::string(kname) + ": the piece's work items do not fit the 32-bit work counter (internal error)");
   h->prec.alloc((uint64_t)rpt_fold_ring_slots(p.max_bounces) * rptdev::REC_FIELDS * ((uint64_t)pl.nblocks * 64));
   h->lbuf.alloc(std::max<uint64_t>(1, (uint64_t)pl.spp_l * 3 * npix));
@@ -399,20 +413,10 @@ void render_persistent(rptgpu_scene* h, const KernelTable* kt, const RptRenderPa
     fr.sample_base = p.sample_index_base + s0;
     HIP_TRY(hipMemsetAsync(h->counters.p, 0, sizeof(uint32_t), st));
     { Bracket b(h, RPT_K_PATHS, prof);
-      if (views)
-        kt->paths_views(st, h->dscene, fr, vr, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
-                        pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
-      else if (vertices) {
-        rptdev::VertexOut vo = *src.vertices; // (the launch's first sample, counted from the call's)
-        vo.s_first = s0;
-        kt->paths_vertices(st, h->dscene, fr, cr, vo, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
-                           pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
-      } else if (rays)
-        kt->paths_rays(st, h->dscene, fr, cr, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
-                       pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
-      else
-        kt->paths(st, h->dscene, fr, *src.cam, h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items,
-                  pl.nblocks, lay, flat, flat_lds, park, h->opt.paths_batch);
+      vo.s_first = s0; // (the launch's first sample, counted from the call's)
+      form.launch(st, h->dscene, fr, from,
+                  PathsLaunch{h->counters.p, h->prec.p, h->pcounters.p, h->lbuf.p, spp, pl.chunk, (uint32_t)items, pl.nblocks, &lay, flat,
+                              flat_lds, park, h->opt.paths_batch});
       b.done(); }
     if (probes) kt->project_probes(st, fr, h->lbuf.p, spp, (uint32_t)src.probe);
     else kt->sum_samples(st, fr, h->lbuf.p, spp, s0 == 0);
@@ -586,7 +590,7 @@ void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in) {
 
 // scenes with deep trees (and RPT_FLAG_WAVEFRONT): the batch runs as passes of many paths in flight, each sized by
 // rptplan::plan_pass; a pass changes nothing outside the workspace before its rpt_resolve.  Of p it reads iterations,
-// max_bounces, sample_index_base, exposure_value and flags (rptgpu_trace_rays, api_rays.cpp, fills in just those)
+// max_bounces, sample_index_base, exposure_value and flags (the calls over pieces fill in little more: piece_params)
 void render_wavefront(rptgpu_scene* h, const KernelTable* kt, const RptRenderParams& p, rptdev::Frame fr,
                       const RaySource& src, void* out, bool out_f32, bool packed, bool prof) {
   hipStream_t st = h->stream;
@@ -648,16 +652,8 @@ int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams*
   REFUSE_IF_ABANDONED(h);
   if (const char* why = bad_params(p)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (d_list && (!packed || !d_out || host_out)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "a pixel list renders packed into device memory");
-  auto t0 = std::chrono::steady_clock::now();
-  const int rc = guarded(h, h->device, [&]() -> int {
-    // a call leaves no event pair behind, however it ends (one that ends well has resolved them: drain_call)
-    struct EventPairs {
-      rptgpu_scene* h;
-      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
-    } event_pairs{h};
-    // hipGetLastError() reports the thread's LAST failed runtime call, whoever made it (another library in the process,
-    // an unchecked clean-up call): start from a clean slate so that the checks below speak about this call's launches
-    (void)hipGetLastError();
+  // (the frame gets no caller's stream: the partition and the frame's array are made first, and the body waits itself)
+  return device_call(h, nullptr, [&]() {
     hipStream_t st = h->stream;
     const KernelTable* kt = table_for(p->precision_mode, h->ext_shapes);
     const bool prof = (p->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
@@ -687,11 +683,8 @@ int render_impl(rptgpu_scene* h, const RptCamera* camera, const RptRenderParams*
     }
     HIP_TRY(hipGetLastError());
     if (host_out) HIP_TRY(hipMemcpyAsync(host_out, out, frame_elems * out_elem, hipMemcpyDeviceToHost, st));
-    return drain_call(h, wavefront && h->has_deep && h->gen_overflow.p);
+    return wavefront && h->has_deep && h->gen_overflow.p;
   });
-  if (rc != RPTGPU_OK) return rc;
-  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return RPTGPU_OK;
 }
 
 } // namespace rptapi

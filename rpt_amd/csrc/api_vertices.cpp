@@ -1,11 +1,11 @@
 // api_vertices.cpp — rptgpu_trace_vertices[_device]: the vertices of the paths rptgpu_trace_rays runs (include/
-// rpt_gpu_vertices.h; see api_internal.h).  The call IS api_rays.cpp's — the same pieces through the same
-// driver, the same rpt_raygen_rays, depth loop, restarts, rpt_resolve and rpt_finish — with one thing more in the piece's
-// RaySource: the vertex sink.  run_pass (api_render.cpp) then launches rpt_vertices_store behind every depth's closest-hit
-// query and rpt_vertices_fold at the end of every pass that resolved (kernels/wf_vertices.inc); the filler behind the paths'
-// last vertices is laid down here, per piece, before its passes.  A host caller's records are
-// staged piece by piece in an array the handle keeps (rptplan::vertices_piece bounds it); a device caller's are written where
-// they lie.
+// rpt_gpu_vertices.h; see api_internal.h).  The call runs api_rays.cpp's piece loop (trace_ray_pieces) — the
+// same pieces through the same driver, the same rpt_raygen_rays, depth loop, restarts, rpt_resolve and rpt_finish — and adds,
+// through the loop's two hooks, one thing to the piece's RaySource: the vertex sink.  run_pass (api_render.cpp) then launches
+// rpt_vertices_store behind every depth's closest-hit query and rpt_vertices_fold at the end of every pass that resolved
+// (kernels/wf_vertices.inc); the filler behind the paths' last vertices is laid down here, per piece, before its passes.  A
+// host caller's records are staged piece by piece in an array the handle keeps (rptplan::vertices_piece bounds it) and copied
+// out behind the piece; a device caller's are written where they lie.
 // Under RPT_FLAG_VERTICES_PERSISTENT (include/rpt_gpu_vertices_persistent.h) the same pieces, staged and
 // filled the same way, go through the persistent driver instead: rpt_paths_vertices writes each vertex where it makes it, and
 // rpt_sum_samples and the packed rpt_finish behind its launches are a render's.  The same bytes.
@@ -137,93 +137,48 @@ int trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const dou
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n) return RPTGPU_OK;
-  auto t0 = std::chrono::steady_clock::now();
-  const int rc = guarded(h, h->device, [&]() -> int {
-    struct EventPairs { // (as render_impl: a call leaves no event pair behind, however it ends)
-      rptgpu_scene* h;
-      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
-    } event_pairs{h};
-    (void)hipGetLastError();
+  return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
-    const KernelTable* kt = table_for(q->precision_mode, h->ext_shapes);
-    const bool prof = (q->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
     const uint32_t ch = q->channels, stride = q->max_bounces + 1u;
-    const bool want_rgb = (ch & RPT_VERTEX_RGB) != 0;
-    if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
-    h->dscene.force_general = (q->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
-    RptRenderParams p{}; // what render_wavefront reads of it
-    p.max_bounces = q->max_bounces; p.iterations = q->iterations; p.exposure_value = q->exposure_value;
-    p.seed = q->seed; p.sample_index_base = q->sample_index_base; p.precision_mode = q->precision_mode; p.flags = q->flags;
     // the piece: rptgpu_trace_rays' (at most the paths one pass may hold with every level of every path), and for a host
-    // caller what the staging of the named channels allows (rptplan::vertices_piece)
-    rptplan::PassInput in = pass_input(h, 1, q->iterations);
-    in.remaining = q->iterations;
-    in.ratio = (double)q->max_bounces + 1.0;
-    pass_input_now(h, in);
+    // caller what the staging of the named channels allows (rptplan::vertices_piece); in the persistent kernel also at most
+    // what a launch's work counter holds (rptplan::vertices_persistent_piece is this composition)
     uint64_t asked = 0; // tests: pieces of a few rays
     if (const char* e = std::getenv("RPTGPU_VERTICES_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    // the persistent kernel on request — unless the scene has a group with tree children, which only the wavefront
-    // pipeline walks (use_wavefront: such a scene cannot honour the request, as for rptgpu_trace_rays); a piece is then also at
-    // most what a launch's work counter holds (handle_rays_persistent_piece's bound)
-    const bool persistent = (q->flags & RPT_FLAG_VERTICES_PERSISTENT) && !use_wavefront(h, 0, false);
-    const uint64_t piece =
-        persistent ? rptplan::vertices_persistent_piece(n, asked, rptplan::plan_pass(in).target, !on_device, q->iterations, q->max_bounces, ch,
-                                                        (uint32_t)std::max(1, h->num_cus) * RPT_PATHS_WAVES_PER_CU_MAX, RPT_PATHS_BATCH_MAX)
-                   : rptplan::vertices_piece(n, asked, rptplan::plan_pass(in).target, !on_device, q->iterations, q->max_bounces, ch);
-    h->accum.alloc(3 * piece);
-    // rpt_finish writes a piece's means somewhere: the caller's rgb, or (a host caller, or RGB not named) the handle's array
-    if (!on_device || !want_rgb) h->rays_out.alloc(3 * piece);
-    if (!on_device) { h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece); }
-    if (!on_device || !streams) h->ray_ids.alloc(piece);
-    Ptrs stage{};
+    uint64_t piece = rptplan::vertices_piece(n, asked, piece_pass_target(h, q->iterations, q->max_bounces), !on_device, q->iterations,
+                                             q->max_bounces, ch);
+    const bool persistent = piece_persistent(h, q->flags, RPT_FLAG_VERTICES_PERSISTENT);
+    if (persistent) piece = persistent_piece(h, piece, q->iterations);
+    Ptrs stage{}, mine{};
     if (!on_device) stage = vertex_staging(h->vertices_out, *q, piece);
-    for (uint64_t base = 0; base < n; base += piece) {
-      const uint64_t m = std::min(piece, n - base);
-      const double *d_o = origins + 3 * base, *d_d = dirs + 3 * base;
-      const uint32_t* d_ids = streams ? streams + base : h->ray_ids.p;
-      double* d_rgb = on_device && want_rgb ? out->rgb + 3 * base : h->rays_out.p;
-      const Ptrs mine = vertex_arrays_at(*out, *q, base);
-      if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(h->rays_o.p, d_o, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_d, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
-        if (streams) HIP_TRY(hipMemcpyAsync(h->ray_ids.p, d_ids, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        d_o = h->rays_o.p; d_d = h->rays_d.p; d_ids = h->ray_ids.p;
-      }
-      const Ptrs& where = on_device ? mine : stage;
-      const rptdev::VertexOut sink = sink_of(where, *q);
-      // the filler — +0.0, OBJECT -1, DRAW 0 — over the piece's entries of every named per-vertex channel, in front of the
-      // piece's first pass: the kernels write d < len only, so behind a path's last vertex this is what stays.  (Streaming
-      // fills instead of 8- to 24-byte stores a path's stride apart: RPT_VERTICES_FILL_IN_KERNEL=1 builds that form.)
+    rptdev::VertexOut sink{};
+    // rpt_finish writes a piece's means somewhere: the caller's rgb, or (RGB not named) the handle's array
+    const RayPieces c{n, origins, dirs, streams, on_device, piece, persistent, piece_params(*q, q->iterations, q->exposure_value),
+                      q->first_draw, 3, (ch & RPT_VERTEX_RGB) ? out->rgb : nullptr};
+    trace_ray_pieces(
+        h, c,
+        [&](uint64_t base, uint64_t m, RaySource& src) {
+          mine = vertex_arrays_at(*out, *q, base);
+          const Ptrs& where = on_device ? mine : stage;
+          sink = sink_of(where, *q);
+          src.vertices = &sink;
+          // the filler — +0.0, OBJECT -1, DRAW 0 — over the piece's entries of every named per-vertex channel, in front of the
+          // piece's first pass: the kernels write d < len only, so behind a path's last vertex this is what stays.  (Streaming
+          // fills instead of 8- to 24-byte stores a path's stride apart: RPT_VERTICES_FILL_IN_KERNEL=1 builds that form.)
 #if !RPT_VERTICES_FILL_IN_KERNEL
-      for (int k = 0; k < N_ROWS; k++)
-        if ((ch & ROWS[k].bit) && !ROWS[k].per_path)
-          HIP_TRY(hipMemsetAsync(where.p[k], ROWS[k].bit == RPT_VERTEX_OBJECT ? 0xff : 0, channel_bytes(k, m, q->iterations, stride), st));
+          for (int k = 0; k < N_ROWS; k++)
+            if ((ch & ROWS[k].bit) && !ROWS[k].per_path)
+              HIP_TRY(hipMemsetAsync(where.p[k], ROWS[k].bit == RPT_VERTEX_OBJECT ? 0xff : 0, channel_bytes(k, m, q->iterations, stride), st));
 #endif
-      rptdev::Frame fr{};
-      fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = d_ids;
-      fr.max_bounces = q->max_bounces; fr.seed = q->seed; fr.accum = h->accum.p;
-      RaySource src{nullptr, d_o, d_d, q->first_draw, (uint32_t)base, streams ? nullptr : h->ray_ids.p};
-      src.vertices = &sink;
-      if (persistent) { // (the ids the wavefront's first step would write: the kernel reads them from the first launch on)
-        if (!streams) kt->rays_ids(st, (uint32_t)base, (uint32_t)m, h->ray_ids.p);
-        render_persistent(h, kt, p, fr, src, d_rgb, false, true, prof);
-      } else {
-        render_wavefront(h, kt, p, fr, src, d_rgb, false, true, prof);
-      }
-      HIP_TRY(hipGetLastError());
-      if (!on_device) { // the staging arrays are the next piece's, too
-        for (int k = 0; k < N_ROWS; k++)
-          if (ch & ROWS[k].bit)
-            HIP_TRY(hipMemcpyAsync(mine.p[k], stage.p[k], channel_bytes(k, m, q->iterations, stride), hipMemcpyDeviceToHost, st));
-        if (want_rgb) HIP_TRY(hipMemcpyAsync(out->rgb + 3 * base, d_rgb, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-      }
-    }
-    return drain_call(h, !persistent && h->has_deep && h->gen_overflow.p);
+        },
+        [&](uint64_t, uint64_t m) {
+          if (on_device) return;
+          for (int k = 0; k < N_ROWS; k++)
+            if (ch & ROWS[k].bit)
+              HIP_TRY(hipMemcpyAsync(mine.p[k], stage.p[k], channel_bytes(k, m, q->iterations, stride), hipMemcpyDeviceToHost, st));
+        });
+    return !persistent && h->has_deep && h->gen_overflow.p;
   });
-  if (rc != RPTGPU_OK) return rc;
-  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return RPTGPU_OK;
 }
 
 } // namespace

@@ -10,6 +10,9 @@
 // Under RPT_FLAG_VIEWS_PERSISTENT (include/rpt_gpu_views_persistent.h) the same pieces go through the
 // persistent driver instead: rpt_views_ids names each index's pixel and view, rpt_paths_views runs the piece's launches of at
 // most spp_l samples, and rpt_sum_samples and the packed rpt_finish behind them are a render's.  The same bits.
+// The loop over the pieces is this file's own — its indices are made on the device, not staged —; the steps it shares with
+// api_rays.cpp's loop are api_internal.h's (piece_params, piece_pass_target, piece_persistent, persistent_piece, piece_frame,
+// render_piece).
 #include "api_internal.h"
 
 namespace rptapi {
@@ -78,21 +81,11 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n_views) return RPTGPU_OK;
-  auto t0 = std::chrono::steady_clock::now();
-  const int rc = guarded(h, h->device, [&]() -> int {
-    struct EventPairs { // (as render_impl: a call leaves no event pair behind, however it ends)
-      rptgpu_scene* h;
-      ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
-    } event_pairs{h};
-    (void)hipGetLastError();
+  return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
     const KernelTable* kt = table_for(q->precision_mode, h->ext_shapes);
-    const bool prof = (q->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
-    if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
     h->dscene.force_general = (q->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
-    RptRenderParams p{}; // what render_wavefront reads of it
-    p.max_bounces = q->max_bounces; p.iterations = q->iterations; p.exposure_value = q->exposure_value;
-    p.seed = q->seed; p.sample_index_base = q->sample_index_base; p.precision_mode = q->precision_mode; p.flags = q->flags;
+    const RptRenderParams p = piece_params(*q, q->iterations, q->exposure_value);
     // the views' device records: the camera constants by the host function a render uses
     std::vector<rptdev::View> recs(n_views);
     for (uint64_t v = 0; v < n_views; v++) {
@@ -101,9 +94,7 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
       recs[v].ortho_scale = views[v].ortho_scale;
     }
     h->view_recs.upload(recs, st);
-    // the persistent kernel on request — unless the scene has a group with tree children, which only the wavefront
-    // pipeline walks (use_wavefront: such a scene cannot honour the request, as for a render)
-    const bool persistent = (q->flags & RPT_FLAG_VIEWS_PERSISTENT) && !use_wavefront(h, 0, false);
+    const bool persistent = piece_persistent(h, q->flags, RPT_FLAG_VIEWS_PERSISTENT);
     std::vector<uint64_t> seed_list = view_seed_list(n_views, *q, seeded ? seeds : nullptr);
     // rpt_paths_views always reads a seed per view (its key is per lane): views that share the query's seed get equal ones
     if (persistent && seed_list.empty()) seed_list.assign(n_views, q->seed);
@@ -111,17 +102,10 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
     if (per_view) h->view_seeds.upload(seed_list, st);
     // the piece: at most the paths one pass may hold with every level of every path (rptplan::views_piece)
     const uint64_t n = n_views * npix;
-    rptplan::PassInput in = pass_input(h, 1, q->iterations);
-    in.remaining = q->iterations;
-    in.ratio = (double)q->max_bounces + 1.0;
-    pass_input_now(h, in);
     uint64_t asked = 0; // tests: pieces of a few pixels
     if (const char* e = std::getenv("RPTGPU_VIEWS_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    uint64_t piece = rptplan::views_piece(n, asked, rptplan::plan_pass(in).target);
-    if (persistent) { // ... and what a launch's work counter holds, at the most resident blocks any instantiation has
-      const uint32_t blocks_max = (uint32_t)std::max(1, h->num_cus) * RPT_PATHS_WAVES_PER_CU_MAX;
-      piece = std::max<uint64_t>(1, rptplan::views_items(piece, q->iterations, 1, blocks_max, RPT_PATHS_BATCH_MAX).m);
-    }
+    uint64_t piece = rptplan::views_piece(n, asked, piece_pass_target(h, q->iterations, q->max_bounces));
+    if (persistent) piece = persistent_piece(h, piece, q->iterations); // (rptplan::views_items at one sample per item)
     const bool at_views = false; // a piece spans views whatever their seeds
     const size_t out_elem = out_f32 ? sizeof(float) : sizeof(double);
     h->accum.alloc(3 * piece);
@@ -132,9 +116,8 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
     for (uint64_t base = 0, m; base < n; base += m) {
       m = rptplan::views_piece_len(base, n, npix, piece, at_views);
       void* d_out = on_device ? (void*)((char*)out + 3 * base * out_elem) : (void*)h->rays_out.p;
-      rptdev::Frame fr{};
-      fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = h->ray_ids.p;
-      fr.max_bounces = q->max_bounces; fr.seed = per_view ? 0 : q->seed; fr.accum = h->accum.p;
+      rptdev::Frame fr = piece_frame(h, p, h->ray_ids.p, m);
+      if (per_view) fr.seed = 0;
       RaySource src{};
       src.ids_out = h->ray_ids.p;
       src.views = h->view_recs.p; src.view_width = q->width; src.view_height = q->height; src.view_base = base;
@@ -142,21 +125,15 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
       if (persistent) {
         src.view_of = h->view_of.p;
         kt->views_ids(st, base, npix, (uint32_t)m, h->ray_ids.p, h->view_of.p);
-        render_persistent(h, kt, p, fr, src, d_out, out_f32, true, prof);
-      } else {
-        render_wavefront(h, kt, p, fr, src, d_out, out_f32, true, prof);
       }
-      HIP_TRY(hipGetLastError());
+      render_piece(h, kt, p, fr, src, d_out, out_f32, persistent);
       if (!on_device) { // the staging array is the next piece's, too
         HIP_TRY(hipMemcpyAsync((double*)out + 3 * base, d_out, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
-    return drain_call(h, !persistent && h->has_deep && h->gen_overflow.p);
+    return !persistent && h->has_deep && h->gen_overflow.p;
   });
-  if (rc != RPTGPU_OK) return rc;
-  h->stats.total_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return RPTGPU_OK;
 }
 
 } // namespace rptapi

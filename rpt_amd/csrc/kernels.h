@@ -102,6 +102,42 @@ struct QueryTuning {
   uint32_t sort_min_rays;
 };
 
+// the forms of the persistent kernel's loop (kernels/paths_loop.inc, RPT_PATHS_FORM): where a work item's ray comes from.  The
+// device pass reads them in the kernels' text; the host indexes KernelTable::paths with them
+#define RPT_PATHS_FORM_CAMERA 0 // rpt_paths: a camera's pixels
+#define RPT_PATHS_FORM_VIEWS 1  // rpt_paths_views: a piece of a batch of views (paths_views.inc)
+#define RPT_PATHS_FORM_RAYS 2   // rpt_paths_rays: a piece of the caller's rays or light probes (paths_rays.inc)
+#define RPT_PATHS_FORM_VERTICES 3 // rpt_paths_vertices: a piece of the caller's rays, the paths' vertices exported (paths_vertices.inc)
+#define RPT_PATHS_FORM_COUNT 4
+// a launch's rays: every form reads its own members and no other — CAMERA cam, VIEWS views, RAYS rays, VERTICES rays and
+// vertices (the piece's sink with the launch's s_first)
+struct PathsRays {
+  const rptdev::Camera* cam;
+  const rptdev::ViewRays* views;
+  const rptdev::CallerRays* rays;
+  const rptdev::VertexOut* vertices;
+};
+// ... and what a launch of any form takes besides (lds_bytes: the flat scene's tables; park: RPT_PATHS_PARK_LDS more behind
+// them for parked environment lookups)
+struct PathsLaunch {
+  uint32_t* work_counter;
+  double* rec;
+  unsigned long long* ray_counters;
+  double* lbuf;
+  uint32_t spp, chunk, n_items, nblocks;
+  const FlatLayout* lay;
+  bool flat;
+  uint32_t lds_bytes;
+  bool park;
+  uint32_t batch; // work items a wave claims at a time; 0 = by the launch's size
+};
+// one form of the persistent kernel, compiled in a translation unit of its own (CAMERA: with everything else):
+// max_blocks_per_cu — resident 64-thread blocks per CU — and launch for the SAME instantiation of that form's kernel
+struct PathsForm {
+  int (*max_blocks_per_cu)(const FlatLayout* flat /* null: not a flat scene */, uint32_t lds_bytes, bool park);
+  void (*launch)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const PathsRays&, const PathsLaunch&);
+};
+
 struct KernelTable {
   void (*raygen)(hipStream_t, const rptdev::Frame&, const rptdev::Camera&, const rptdev::PathState&, uint32_t n_paths);
   // rpt_raygen's step for a piece of the caller's rays (rptgpu_trace_rays): fr.npix rays at origins / dirs ([npix][3] f64 on
@@ -126,13 +162,8 @@ struct KernelTable {
   // multi-GPU gather, root side: one rank's packed pixels into their places in the full f32 frame
   void (*scatter_f32)(hipStream_t, const float* src, const uint32_t* pixels, uint32_t n, float* dst);
   void (*eval_math)(hipStream_t, int fn, uint64_t n, const double* x, const double* y, double* out);
-  // persistent per-pixel kernel: resident 64-thread blocks per CU, and the launch
-  // (lds_bytes: the flat scene's tables; park: RPT_PATHS_PARK_LDS more behind them for parked environment lookups)
-  int (*paths_max_blocks_per_cu)(const FlatLayout* flat /* null: not a flat scene */, uint32_t lds_bytes, bool park);
-  void (*paths)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::Camera&,
-                uint32_t* work_counter, double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp,
-                uint32_t chunk, uint32_t n_items, uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes,
-                bool park, uint32_t batch /* work items a wave claims at a time; 0 = by the launch's size */);
+  // the persistent kernel, one element per form: [RPT_PATHS_FORM_COUNT], indexed by RPT_PATHS_FORM_*
+  const PathsForm* paths;
   // pixel sums of a launch's samples, in sample order
   void (*sum_samples)(hipStream_t, const rptdev::Frame&, const double* lbuf, uint32_t spp, bool first);
   // deep-tree scenes: one closest-hit (light < 0) or visibility (light >= 0) query of a depth, run
@@ -252,73 +283,32 @@ struct KernelTable {
   void (*vertices_store)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, uint32_t n, uint32_t depth,
                          const rptdev::VertexOut& out);
   void (*vertices_fold)(hipStream_t, const rptdev::Frame&, const rptdev::PathState&, uint32_t n_paths, const rptdev::VertexOut& out);
-  // a batch of views in the persistent kernel (rpt_paths_views, kernels/paths_views.inc; compiled in a translation unit of
-  // its own, kernels_views_strict[_ext].hip): paths_max_blocks_per_cu and paths for the SAME instantiation of that kernel,
-  // the rays a piece's ViewRays instead of a Camera; views_ids: the ids of a piece of n consecutive indices from j_base on —
-  // pixels[i] the index's pixel in its view (the piece's Frame::pixels), view_of[i] its view counted from the piece's
-  // first (ViewRays::view_of)
-  int (*paths_views_max_blocks_per_cu)(const FlatLayout* flat, uint32_t lds_bytes, bool park);
-  void (*paths_views)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::ViewRays&, uint32_t* work_counter,
-                      double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk, uint32_t n_items,
-                      uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);
+  // beside the persistent kernel's forms (kernels/paths_views.inc, kernels/paths_rays.inc).  views_ids: the ids of a piece of n
+  // consecutive indices of a batch of views from j_base on — pixels[i] the index's pixel in its view (the piece's
+  // Frame::pixels), view_of[i] its view counted from the piece's first (ViewRays::view_of).  rays_ids: ids[i] = id_base + i for
+  // the piece's n indices (a caller without stream ids).  project_probes: a launch's samples (lbuf, [spp][3][npix] as rpt_paths
+  // writes it) into the probes' running sums (fr.accum, [27 or 3][npix]: resolve_probes' sums, finish_probes behind the last launch)
   void (*views_ids)(hipStream_t, uint64_t j_base, uint64_t npix_view, uint32_t n, uint32_t* pixels, uint32_t* view_of);
-  // the caller's rays and light probes in the persistent kernel (rpt_paths_rays, kernels/paths_rays.inc; compiled in a
-  // translation unit of its own, kernels_rays_strict[_ext].hip): paths_max_blocks_per_cu and paths for the SAME instantiation
-  // of that kernel, the rays a piece's CallerRays.  rays_ids: ids[i] = id_base + i for the piece's n indices (a caller
-  // without stream ids).  project_probes: a launch's samples (lbuf, [spp][3][npix] as rpt_paths writes it) into the probes'
-  // running sums (fr.accum, [27 or 3][npix]: resolve_probes' sums, finish_probes behind the last launch)
-  int (*paths_rays_max_blocks_per_cu)(const FlatLayout* flat, uint32_t lds_bytes, bool park);
-  void (*paths_rays)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::CallerRays&, uint32_t* work_counter,
-                     double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk, uint32_t n_items,
-                     uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);
   void (*rays_ids)(hipStream_t, uint32_t id_base, uint32_t n, uint32_t* ids);
   void (*project_probes)(hipStream_t, const rptdev::Frame&, const double* lbuf, uint32_t spp, uint32_t kind);
-  // the caller's rays in the persistent kernel with their paths' vertices exported (rpt_paths_vertices, kernels/
-  // paths_vertices.inc; compiled in a translation unit of its own, kernels_vertices_strict[_ext].hip, with the ray stash off):
-  // paths_max_blocks_per_cu and paths for the SAME instantiation of that kernel, `out` the piece's sink with the launch's s_first
-  int (*paths_vertices_max_blocks_per_cu)(const FlatLayout* flat, uint32_t lds_bytes, bool park);
-  void (*paths_vertices)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::CallerRays&, const rptdev::VertexOut& out,
-                         uint32_t* work_counter, double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp,
-                         uint32_t chunk, uint32_t n_items, uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes,
-                         bool park, uint32_t batch);
 };
-// the views' translation units: what the tables above point to
-#define RPT_VIEWS_TU_DECLS(NS)                                                                                                    \
-  namespace NS {                                                                                                                  \
-  int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool park);                                             \
-  void launch_paths(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::ViewRays&, uint32_t* work_counter,     \
-                    double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk, uint32_t n_items,  \
-                    uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);           \
-  void launch_views_ids(hipStream_t, uint64_t j_base, uint64_t npix_view, uint32_t n, uint32_t* pixels, uint32_t* view_of);       \
+// the forms' translation units (kernels_<form>_strict[_ext].hip): what the tables above point to — kernels/launch_paths.inc's
+// two functions, and what else the form's file launches
+#define RPT_FORM_TU_DECLS_NS(NS, ...)                                                                                  \
+  namespace NS {                                                                                                       \
+  int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool park);                                  \
+  void launch_paths(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const PathsRays&, const PathsLaunch&);    \
+  __VA_ARGS__                                                                                                          \
   }
-RPT_VIEWS_TU_DECLS(rpt_strict_views)
-RPT_VIEWS_TU_DECLS(rpt_strict_ext_views)
-#undef RPT_VIEWS_TU_DECLS
-// ... and the rays' translation units
-#define RPT_RAYS_TU_DECLS(NS)                                                                                                     \
-  namespace NS {                                                                                                                  \
-  int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool park);                                             \
-  void launch_paths(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::CallerRays&, uint32_t* work_counter,   \
-                    double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp, uint32_t chunk, uint32_t n_items,  \
-                    uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes, bool park, uint32_t batch);           \
-  void launch_rays_ids(hipStream_t, uint32_t id_base, uint32_t n, uint32_t* ids);                                                 \
-  void launch_project_probes(hipStream_t, const rptdev::Frame&, const double* lbuf, uint32_t spp, uint32_t kind);                 \
-  }
-RPT_RAYS_TU_DECLS(rpt_strict_rays)
-RPT_RAYS_TU_DECLS(rpt_strict_ext_rays)
-#undef RPT_RAYS_TU_DECLS
-// ... and the vertices' translation units
-#define RPT_VERTICES_TU_DECLS(NS)                                                                                                 \
-  namespace NS {                                                                                                                  \
-  int paths_max_blocks_per_cu(const FlatLayout* flat, uint32_t lds_bytes, bool park);                                             \
-  void launch_paths(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::CallerRays&, const rptdev::VertexOut&, \
-                    uint32_t* work_counter, double* rec, unsigned long long* ray_counters, double* lbuf, uint32_t spp,            \
-                    uint32_t chunk, uint32_t n_items, uint32_t nblocks, const FlatLayout& lay, bool flat, uint32_t lds_bytes,     \
-                    bool park, uint32_t batch);                                                                                   \
-  }
-RPT_VERTICES_TU_DECLS(rpt_strict_vertices)
-RPT_VERTICES_TU_DECLS(rpt_strict_ext_vertices)
-#undef RPT_VERTICES_TU_DECLS
+#define RPT_FORM_TU_DECLS(FORM, ...) \
+  RPT_FORM_TU_DECLS_NS(rpt_strict_##FORM, __VA_ARGS__) RPT_FORM_TU_DECLS_NS(rpt_strict_ext_##FORM, __VA_ARGS__)
+RPT_FORM_TU_DECLS(views, void launch_views_ids(hipStream_t, uint64_t j_base, uint64_t npix_view, uint32_t n, uint32_t* pixels,
+                                               uint32_t* view_of);)
+RPT_FORM_TU_DECLS(rays, void launch_rays_ids(hipStream_t, uint32_t id_base, uint32_t n, uint32_t* ids);
+                  void launch_project_probes(hipStream_t, const rptdev::Frame&, const double* lbuf, uint32_t spp, uint32_t kind);)
+RPT_FORM_TU_DECLS(vertices, )
+#undef RPT_FORM_TU_DECLS
+#undef RPT_FORM_TU_DECLS_NS
 
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)
 // the same with the extended shape set (RPT_SHAPE_MONOMIAL, trees of trees) compiled in

@@ -12,18 +12,20 @@
 //   material.inc   Material::bsdf / sample_f (material.rs:125-313)
 //   light.inc      Light::illuminate (light.rs:23-47), Environment / Hdri (environment.rs:25-52)
 //   paths*.inc     the DEFAULT pipeline for scenes without deep trees: one persistent kernel,
-//                  rpt_paths<KdLds | KdFlat>, the whole path in registers (renderer.rs:117-174), in four files:
+//                  rpt_paths<KdLds | KdFlat>, the whole path in registers (renderer.rs:117-174), in these files:
 //     paths_consts.inc  what a flat scene keeps in the wave's LDS (FlatLds) and the tables of a hit's scene constants
 //     paths_flat.inc    the flat scenes' queries: flat_query, flat_query2 (two rays in one walk), flat_query_filtered
 //     paths_shade.inc   the fused form's draw-first shading: hit_draws, bsdf_opaque, sample_f_opaque, illuminate_mesh
 //     paths.inc         the kernel's contract, work hand-out, record ring, parked lookups, ray stash; rpt_sum_samples
-//     paths_loop.inc    the loop itself: one text, compiled as rpt_paths (paths.inc), as rpt_paths_views (paths_views.inc) and
-//                       as rpt_paths_rays (paths_rays.inc) and as rpt_paths_vertices (paths_vertices.inc)
+//     paths_loop.inc    the loop itself: one text, compiled once per form of the kernel (RPT_PATHS_FORM_*, kernels.h) — as
+//                       rpt_paths by paths.inc and, each in a translation unit of its own, by the three files below
 //     paths_views.inc   rpt_paths_views, the kernel over a piece of a batch of views: its ids, camera ray and per-lane key
 //     paths_rays.inc    rpt_paths_rays, the kernel over a piece of the caller's rays or light probes: its ray; rpt_rays_ids,
 //                       rpt_project_probes
 //     paths_vertices.inc rpt_paths_vertices, rpt_paths_rays with the paths' vertices written where the loop has them: its
 //                       ray and the three stores of a vertex
+//     launch_paths.inc  the host side of a form: which instantiation, its occupancy, its launch — one text, included where
+//                       the form's kernel is, with one signature for all forms (kernels.h PathsForm, KernelTable::paths)
 //     probe_dir.inc     a light probe's direction and the SH9 basis, shared by both routes of rptgpu_bake_probes
 //   the wavefront pipeline — scenes with deep trees; rptgpu_trace_rays and rptgpu_bake_probes for any scene (flat ones
 //   query inside rpt_extend / rpt_shadow_rays) —: one kernel per step of a depth over SoA path state, in six files:
@@ -82,12 +84,6 @@ using namespace rptdev;
 #define RPT_NS_VIEWS RPT_CAT2(RPT_NS, _views)
 #define RPT_NS_RAYS RPT_CAT2(RPT_NS, _rays) // ... and of its rays' translation unit
 #define RPT_NS_VERTICES RPT_CAT2(RPT_NS, _vertices) // ... and of its vertices' translation unit
-// the forms of the persistent kernel's loop (kernels/paths_loop.inc, RPT_PATHS_FORM): where a work item's ray comes from
-#define RPT_PATHS_FORM_CAMERA 0 // rpt_paths: a camera's pixels
-#define RPT_PATHS_FORM_VIEWS 1  // rpt_paths_views: a piece of a batch of views (paths_views.inc)
-#define RPT_PATHS_FORM_RAYS 2   // rpt_paths_rays: a piece of the caller's rays or light probes (paths_rays.inc)
-#define RPT_PATHS_FORM_VERTICES 3 // rpt_paths_vertices: a piece of the caller's rays, the paths' vertices exported (paths_vertices.inc)
-
 // Scene tables that a whole wave indexes uniformly (top-level instances, trees, lights) are read
 // through the CONSTANT address space: the scene is immutable while a kernel runs, and only then
 // does the compiler turn a uniform-address load into an s_load (SGPR destination, scalar cache)

@@ -87,8 +87,8 @@ void launch_scatter_f32(hipStream_t st, const float* src, const uint32_t* pixels
   if (n) hipLaunchKernelGGL(rpt_scatter_f32, grid_for(n), dim3(256), 0, st, src, pixels, n, dst);
 }
 
-// paths_kernel, paths_max_blocks_per_cu, launch_paths: kernels/launch_paths.inc, shared with the views' and the rays'
-// translation units
+// paths_kernel, paths_max_blocks_per_cu, launch_paths: kernels/launch_paths.inc, shared with the other forms' translation
+// units
 #define RPT_PATHS_FORM RPT_PATHS_FORM_CAMERA
 #include "launch_paths.inc"
 #undef RPT_PATHS_FORM
@@ -361,9 +361,19 @@ bool read_prof(unsigned long long out[4][29]) {
 #endif
 }
 
+// the persistent kernel's forms, in the order of RPT_PATHS_FORM_* (kernels.h): this translation unit's rpt_paths, then the
+// forms' own translation units
+static const PathsForm PATHS_FORMS[] = {{paths_max_blocks_per_cu, launch_paths},
+                                        {RPT_NS_VIEWS::paths_max_blocks_per_cu, RPT_NS_VIEWS::launch_paths},
+                                        {RPT_NS_RAYS::paths_max_blocks_per_cu, RPT_NS_RAYS::launch_paths},
+                                        {RPT_NS_VERTICES::paths_max_blocks_per_cu, RPT_NS_VERTICES::launch_paths}};
+static_assert(sizeof PATHS_FORMS / sizeof PATHS_FORMS[0] == RPT_PATHS_FORM_COUNT, "one element per form of the persistent kernel");
+static_assert(RPT_PATHS_FORM_CAMERA == 0 && RPT_PATHS_FORM_VIEWS == 1 && RPT_PATHS_FORM_RAYS == 2 && RPT_PATHS_FORM_VERTICES == 3,
+              "PATHS_FORMS is indexed by the form");
+
 const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, launch_extend_rays, launch_shade,
                            launch_shadow_rays, launch_resolve, launch_finish, launch_scatter_f32, launch_eval_math,
-                           paths_max_blocks_per_cu, launch_paths, launch_sum_samples, launch_query, sort_temp_bytes, launch_shadow_sum,
+                           PATHS_FORMS, launch_sum_samples, launch_query, sort_temp_bytes, launch_shadow_sum,
                            launch_buffer_accumulate, launch_buffer_retire, launch_buffer_image, launch_buffer_variance,
                            read_prof, launch_path_reorder, launch_aov, launch_aov_fold,
                            launch_denoise_prepare, launch_denoise_level, launch_denoise_finish,
@@ -373,8 +383,5 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_raygen_views_seeded, launch_shade_seeded,
                            launch_denoise_views_prepare, launch_denoise_views_level, launch_denoise_views_finish,
                            launch_vertices_store, launch_vertices_fold,
-                           RPT_NS_VIEWS::paths_max_blocks_per_cu, RPT_NS_VIEWS::launch_paths, RPT_NS_VIEWS::launch_views_ids,
-                           RPT_NS_RAYS::paths_max_blocks_per_cu, RPT_NS_RAYS::launch_paths, RPT_NS_RAYS::launch_rays_ids,
-                           RPT_NS_RAYS::launch_project_probes,
-                           RPT_NS_VERTICES::paths_max_blocks_per_cu, RPT_NS_VERTICES::launch_paths};
+                           RPT_NS_VIEWS::launch_views_ids, RPT_NS_RAYS::launch_rays_ids, RPT_NS_RAYS::launch_project_probes};
 #endif // !__HIP_DEVICE_COMPILE__

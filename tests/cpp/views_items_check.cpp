@@ -126,7 +126,7 @@ static void edge() {
   const uint64_t room = views_dead_room(2048, BATCH);
   CHECK(views_items(MAX32 - room, 1, 1, 2048, BATCH).m == MAX32 - room && !views_items(MAX32 - room, 1, 1, 2048, BATCH).capped);
   CHECK(views_items(MAX32 - room + 1, 1, 1, 2048, BATCH).capped);
-  // what the host asks with (api_views.cpp): the call's samples in items of one, every block a device may hold
+  // what the host asks with (api_internal.h persistent_piece): the call's samples in items of one, every block a device may hold
   const ViewsItems host = views_items(RAYS_PIECE_MAX, 4, 1, 256 * RPT_PATHS_WAVES_PER_CU_MAX, BATCH);
   CHECK(!host.capped && host.n_items == 4 * RAYS_PIECE_MAX);
 }
