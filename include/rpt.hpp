@@ -842,6 +842,38 @@ class Renderer {
     check(rptgpu_first_hits(handle_, n, origins.data(), dirs.data(), &q, &a));
     return r;
   }
+  // addition: the surface element behind those first hits (rptgpu_hit_surface, include/rpt_gpu_hit_surface.h): which triangle
+  // of its mesh (`primitive`, in the mesh's triangle order, -1 without one), where on it (`barycentric`: u, v, w per ray, the
+  // weights of v1, v2, v3; +0.0 without a triangle) and which direct child of a hit group (`child`, -1 otherwise), beside
+  // rptgpu_closest_hit's t and object to join on; a vector of a channel not named in `channels` (RPT_SURFACE_*) stays empty.
+  struct HitSurfaces {
+    std::vector<double> t, barycentric;
+    std::vector<int32_t> object, child, primitive;
+  };
+  HitSurfaces hit_surface(const std::vector<double>& origins, const std::vector<double>& dirs,
+                          uint32_t channels = RPT_SURFACE_T | RPT_SURFACE_OBJECT | RPT_SURFACE_CHILD | RPT_SURFACE_PRIMITIVE |
+                                              RPT_SURFACE_BARYCENTRIC,
+                          uint32_t flags = 0) {
+    ensure_scene();
+    const size_t n = origins.size() / 3;
+    if (origins.size() != 3 * n || dirs.size() != 3 * n)
+      throw std::invalid_argument("hit_surface: origins and dirs hold xyz per ray");
+    RptSurfaceQuery q{};
+    q.struct_size = sizeof(RptSurfaceQuery); q.channels = channels; q.flags = flags;
+    HitSurfaces r;
+    if (!n) return r; // (an empty vector has no address, and a named channel's pointer must not be NULL)
+    if (channels & RPT_SURFACE_T) r.t.resize(n);
+    if (channels & RPT_SURFACE_OBJECT) r.object.resize(n);
+    if (channels & RPT_SURFACE_CHILD) r.child.resize(n);
+    if (channels & RPT_SURFACE_PRIMITIVE) r.primitive.resize(n);
+    if (channels & RPT_SURFACE_BARYCENTRIC) r.barycentric.resize(3 * n);
+    RptSurfaceArrays a{};
+    a.struct_size = sizeof(RptSurfaceArrays);
+    a.t = r.t.data(); a.object = r.object.data(); a.child = r.child.data(); a.primitive = r.primitive.data();
+    a.barycentric = r.barycentric.data();
+    check(rptgpu_hit_surface(handle_, n, origins.data(), dirs.data(), &q, &a));
+    return r;
+  }
   // addition: the vertices of the paths trace_rays runs (rptgpu_trace_vertices, include/rpt_gpu_vertices.h): where each of a
   // ray's num_samples paths bounced, what it picked up there and with which factors it went on.  With S = num_samples and
   // V = max_bounces + 1: length [n][S]; per vertex [n][S][V] (x 3 for the vectors); rgb [n][3] = trace_rays' result.  Entries

@@ -775,8 +775,8 @@ int rptgpu_render_views_device(rptgpu_scene* h, uint64_t n_views, const RptView*
  * rpt_raygen_views (views with seeds that differ: rpt_raygen_views_seeded), the closest-hit query (rpt_extend, or the per-tree query) and rpt_views_aov_fold, which keeps index j's
  * sums in the output arrays at j between passes.  RPT_FLAG_GENERAL_TRAVERSAL is honoured and changes no bit; RptStats:
  * total_ms only.
- * NOT IN SCOPE: a max_t cut or an early-out in the closest-hit query; primitive ids or barycentrics in the record (the
- * walkers do not carry them); multi-hit; the tile partition and multi-GPU (a caller shards the rays or the views: a result
+ * NOT IN SCOPE: a max_t cut or an early-out in the closest-hit query; multi-hit (primitive ids, barycentrics and a group's
+ * child are a call of their own that joins on T and OBJECT: rptgpu_hit_surface, rpt_gpu_hit_surface.h); the tile partition and multi-GPU (a caller shards the rays or the views: a result
  * depends on nothing else); the device-resident Buffer and the denoiser for views; the persistent kernel; rptgpu_closest_hit
  * itself, which stays as it is and is not routed through this code.
  * RPTGPU_E_INVALID_ARGUMENT, checked before any device work, with a detail naming the reason and with the output arrays
@@ -1050,6 +1050,8 @@ const char* rptgpu_kernel_name(int k);
 #include "rpt_gpu_rays_persistent.h"
 /* ---- ... and the vertices of those rays' paths from the persistent path kernel, on request ---- */
 #include "rpt_gpu_vertices_persistent.h"
+/* ---- ... and the triangle, group child and barycentrics behind a ray's first hit ---- */
+#include "rpt_gpu_hit_surface.h"
 
 #ifdef __cplusplus
 }

@@ -74,8 +74,8 @@
  * returns RPTGPU_OK.
  *
  * NOT IN SCOPE.  Views or camera pixels as the ray source (a caller makes those rays itself: tests/views_model.py shows
- * how); primitive ids or barycentrics; the shadow rays' own records (only their sum, inside RADIANCE); light probes;
- * multi-GPU; the device Buffer.  (The persistent kernel: on request, rpt_gpu_vertices_persistent.h.) */
+ * how); primitive ids or barycentrics per vertex (for a ray's first hit: rptgpu_hit_surface, rpt_gpu_hit_surface.h); the
+ * shadow rays' own records (only their sum, inside RADIANCE); light probes; multi-GPU; the device Buffer.  (The persistent kernel: on request, rpt_gpu_vertices_persistent.h.) */
 enum {
   RPT_VERTEX_LENGTH = 1u, RPT_VERTEX_T = 2u, RPT_VERTEX_NORMAL = 4u, RPT_VERTEX_OBJECT = 8u, RPT_VERTEX_POSITION = 16u,
   RPT_VERTEX_DIRECTION = 32u, RPT_VERTEX_DRAW = 64u, RPT_VERTEX_RADIANCE = 128u, RPT_VERTEX_BSDF = 256u,

@@ -12,7 +12,9 @@ surface irradiance — which sh9_basis / sh9_irradiance (numpy) evaluate; GpuSce
 call, each from a View: a camera under a perspective, orthographic or panoramic projection (a panorama is an Hdri's texels);
 GpuScene.occluded answers "is anything between here and there?" for the caller's rays with the shadow rays' own query, and
 GpuScene.bake_ao bakes ambient occlusion (and bent normals) from directions drawn on the device; GpuScene.trace_vertices gives
-the vertices of the paths trace_rays runs — where each bounced, what it picked up there and with what it went on.
+the vertices of the paths trace_rays runs — where each bounced, what it picked up there and with what it went on;
+GpuScene.hit_surface names the triangle, the barycentrics and the group's child behind a ray's first hit, and
+surface.interpolate carries a per-vertex attribute there.
 """
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401
@@ -23,6 +25,8 @@ from ._abi import (RPT_AOV_ALBEDO, RPT_AOV_ALL, RPT_AOV_DEPTH, RPT_AOV_NORMAL, R
 from ._abi import (RPT_VERTEX_ABS_COS, RPT_VERTEX_ALL, RPT_VERTEX_BSDF, RPT_VERTEX_DIRECTION, RPT_VERTEX_DRAW,  # noqa: F401
                    RPT_VERTEX_INV_PDF, RPT_VERTEX_LENGTH, RPT_VERTEX_NORMAL, RPT_VERTEX_OBJECT, RPT_VERTEX_POSITION,
                    RPT_VERTEX_RADIANCE, RPT_VERTEX_RGB, RPT_VERTEX_T)
+from ._abi import (RPT_SURFACE_ALL, RPT_SURFACE_BARYCENTRIC, RPT_SURFACE_CHILD, RPT_SURFACE_OBJECT,  # noqa: F401
+                   RPT_SURFACE_PRIMITIVE, RPT_SURFACE_T)
 from .buffer import Buffer, Filter  # noqa: F401
 from .camera import Camera, View  # noqa: F401
 from .color import color_bytes, hex_color  # noqa: F401
@@ -37,5 +41,6 @@ from .probes import sh9_basis, sh9_irradiance  # noqa: F401
 from .renderer import Renderer  # noqa: F401
 from .scene import Scene  # noqa: F401
 from . import scenes  # noqa: F401
+from . import surface  # noqa: F401
 from .shape import (Cube, KdTree, Mesh, MonomialSurface, Plane, Shape, Sphere, Transformed, Triangle,  # noqa: F401
                     cube, monomial_surface, plane, polygon, sphere, transform_records)

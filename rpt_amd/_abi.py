@@ -52,6 +52,9 @@ RPT_HIT_ALL = 31
 (RPT_VERTEX_LENGTH, RPT_VERTEX_T, RPT_VERTEX_NORMAL, RPT_VERTEX_OBJECT, RPT_VERTEX_POSITION, RPT_VERTEX_DIRECTION, RPT_VERTEX_DRAW,
  RPT_VERTEX_RADIANCE, RPT_VERTEX_BSDF, RPT_VERTEX_INV_PDF, RPT_VERTEX_ABS_COS, RPT_VERTEX_RGB) = (1 << k for k in range(12))
 RPT_VERTEX_ALL = 4095
+# include/rpt_gpu_hit_surface.h: RptSurfaceQuery.channels of hit_surface (hit_surface_supported())
+RPT_SURFACE_T, RPT_SURFACE_OBJECT, RPT_SURFACE_CHILD, RPT_SURFACE_PRIMITIVE, RPT_SURFACE_BARYCENTRIC = 1, 2, 4, 8, 16
+RPT_SURFACE_ALL = 31
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -249,6 +252,17 @@ class RptVertexArrays(C.Structure):
                 ("bsdf", C.POINTER(f64)), ("inv_pdf", C.POINTER(f64)), ("abs_cos", C.POINTER(f64)), ("rgb", C.POINTER(f64))]
 
 
+class RptSurfaceQuery(C.Structure):
+    """include/rpt_gpu_hit_surface.h RptSurfaceQuery (rptgpu_hit_surface's parameters: RptHitQuery's fields)."""
+    _fields_ = [("struct_size", C.c_uint32), ("channels", C.c_uint32), ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RptSurfaceArrays(C.Structure):
+    """include/rpt_gpu_hit_surface.h RptSurfaceArrays (rptgpu_hit_surface's output arrays, host or device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("t", C.POINTER(f64)), ("object", C.POINTER(C.c_int32)),
+                ("child", C.POINTER(C.c_int32)), ("primitive", C.POINTER(C.c_int32)), ("barycentric", C.POINTER(f64))]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -369,6 +383,13 @@ RAYS_PERSISTENT_SYMBOLS = [
 VERTICES_PERSISTENT_SYMBOLS = [
     ("rptgpu_vertices_persistent_supported", C.c_int, []),
 ]
+# ... and every symbol include/rpt_gpu_hit_surface.h declares, optional in the same way: load_library tolerates a library
+# without them (an older build, for a comparison), and hit_surface_supported() says which it is
+HIT_SURFACE_SYMBOLS = [
+    ("rptgpu_hit_surface", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(RptSurfaceQuery), C.POINTER(RptSurfaceArrays)]),
+    ("rptgpu_hit_surface_device", C.c_int,
+     [_VP, C.c_uint64, _VP, _VP, C.POINTER(RptSurfaceQuery), C.POINTER(RptSurfaceArrays), _VP]),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -397,11 +418,11 @@ def load_library(path=None):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
-    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS:
+    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS:
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported() say no)
+            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported() say no)
         fn.restype = restype
         fn.argtypes = argtypes
     if lib.rptgpu_abi_version() != ABI_VERSION:
@@ -445,6 +466,13 @@ def vertices_persistent_supported(lib=None):
         return False
     fn.restype, fn.argtypes = C.c_int, []
     return fn() == 1
+
+
+def hit_surface_supported(lib=None):
+    """Does the library export rptgpu_hit_surface[_device] (include/rpt_gpu_hit_surface.h)?  Detected by symbol, as a C
+    caller does with dlsym: a library without them is still ABI 7."""
+    lib = lib or load_library()
+    return all(hasattr(lib, name) for name, _, _ in HIT_SURFACE_SYMBOLS)
 
 
 def check(code, handle=None):

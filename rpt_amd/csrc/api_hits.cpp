@@ -82,6 +82,50 @@ bool query_by_object(const rptgpu_scene* h, uint32_t flags) {
   return h->has_deep && (!(flags & RPT_FLAG_GENERAL_TRAVERSAL) || h->tree_kids);
 }
 
+} // namespace
+
+HitPieces plan_hit_pieces(rptgpu_scene* h, uint64_t n, uint32_t flags, const char* piece_env) {
+  HitPieces hp{};
+  h->dscene.force_general = (flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
+  hp.by_object = query_by_object(h, flags);
+  uint64_t bound = ~0ull; // the fused kernel touches no workspace
+  if (hp.by_object) {
+    rptplan::PassInput in = pass_input(h, 1, 1);
+    in.remaining = 1;
+    in.ratio = 1.0; // no depth follows the rays: one record column is all ensure_workspace is asked for
+    pass_input_now(h, in);
+    bound = rptplan::plan_pass(in).target;
+  }
+  uint64_t asked = 0; // tests: pieces of a few rays
+  if (const char* e = std::getenv(piece_env)) asked = std::strtoull(e, nullptr, 10);
+  hp.piece = rptplan::hits_piece(n, asked, bound);
+  if (hp.by_object) {
+    ensure_workspace(h, hp.piece, 1);
+    if (h->gen_all || h->dscene.force_general) ensure_generic(h, true); // (as render_wavefront's size_pass)
+    hp.ps = path_state(h);
+  }
+  return hp;
+}
+
+void hit_piece(rptgpu_scene* h, const KernelTable* kt, const HitPieces& hp, const double* d_o, const double* d_d, uint32_t m,
+               const rptdev::HitOut& ho, bool prof) {
+  hipStream_t st = h->stream;
+  if (hp.by_object) {
+    rptdev::Frame fr{};
+    fr.width = m; fr.height = 1; fr.npix = m;
+    kt->raygen_rays(st, fr, d_o, d_d, 0, nullptr, 0, hp.ps, m); // one sample: slot = the ray's position in the piece
+    reset_tree_counters(h);
+  }
+  const int pair = event_pair_begin(h, RPT_K_EXTEND, prof);
+  if (hp.by_object) query_closest(h, kt, hp.ps, m, nullptr);
+  else kt->first_hits(st, h->dscene, d_o, d_d, m, ho);
+  event_pair_end(h, RPT_K_EXTEND, pair);
+  if (hp.by_object) kt->hits_store(st, h->dscene, hp.ps, m, ho);
+  HIP_TRY(hipGetLastError());
+}
+
+namespace {
+
 // on_device: origins, dirs and out's arrays are device pointers (user_stream: the stream their producer ran on)
 int first_hits(rptgpu_scene* h, uint64_t n, const double* origins, const double* dirs, const RptHitQuery* q,
                const RptHitArrays* out, bool on_device, hipStream_t user_stream) {
@@ -97,25 +141,8 @@ int first_hits(rptgpu_scene* h, uint64_t n, const double* origins, const double*
     const KernelTable* kt = table_for(q->precision_mode, h->ext_shapes);
     const bool prof = (q->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
     const uint32_t ch = q->channels;
-    h->dscene.force_general = (q->flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
-    const bool by_object = query_by_object(h, q->flags);
-    uint64_t bound = ~0ull; // the fused kernel touches no workspace
-    if (by_object) {
-      rptplan::PassInput in = pass_input(h, 1, 1);
-      in.remaining = 1;
-      in.ratio = 1.0; // no depth follows the rays: one record column is all ensure_workspace is asked for
-      pass_input_now(h, in);
-      bound = rptplan::plan_pass(in).target;
-    }
-    uint64_t asked = 0; // tests: pieces of a few rays
-    if (const char* e = std::getenv("RPTGPU_HITS_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    const uint64_t piece = rptplan::hits_piece(n, asked, bound);
-    rptdev::PathState ps{};
-    if (by_object) {
-      ensure_workspace(h, piece, 1);
-      if (h->gen_all || h->dscene.force_general) ensure_generic(h, true); // (as render_wavefront's size_pass)
-      ps = path_state(h);
-    }
+    const HitPieces hp = plan_hit_pieces(h, n, q->flags, "RPTGPU_HITS_PIECE");
+    const uint64_t piece = hp.piece;
     rptdev::HitOut stage{};
     if (!on_device) {
       h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece);
@@ -130,19 +157,7 @@ int first_hits(rptgpu_scene* h, uint64_t n, const double* origins, const double*
         HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_d, 3 * (uint64_t)m * sizeof(double), hipMemcpyHostToDevice, st));
         d_o = h->rays_o.p; d_d = h->rays_d.p;
       }
-      const rptdev::HitOut& ho = on_device ? mine : stage;
-      if (by_object) {
-        rptdev::Frame fr{};
-        fr.width = m; fr.height = 1; fr.npix = m;
-        kt->raygen_rays(st, fr, d_o, d_d, 0, nullptr, 0, ps, m); // one sample: slot = the ray's position in the piece
-        reset_tree_counters(h);
-      }
-      const int pair = event_pair_begin(h, RPT_K_EXTEND, prof);
-      if (by_object) query_closest(h, kt, ps, m, nullptr);
-      else kt->first_hits(st, h->dscene, d_o, d_d, m, ho);
-      event_pair_end(h, RPT_K_EXTEND, pair);
-      if (by_object) kt->hits_store(st, h->dscene, ps, m, ho);
-      HIP_TRY(hipGetLastError());
+      hit_piece(h, kt, hp, d_o, d_d, m, on_device ? mine : stage, prof);
       if (!on_device) { // the staging arrays are the next piece's, too
         copy_hits_out(stage, mine, m, st);
         HIP_TRY(hipStreamSynchronize(st));

@@ -30,6 +30,8 @@
 //                    every view of a batch (raygen, closest-hit query and fold in passes over render_views' pieces)
 //   api_vertices.cpp rptgpu_trace_vertices[_device]: api_rays.cpp's loop with a vertex sink in each piece's RaySource — the
 //                    drivers then also carry every path's vertices into the caller's arrays
+//   api_surface.cpp  rptgpu_hit_surface[_device]: api_hits.cpp's first-hit query per piece (plan_hit_pieces, hit_piece), then
+//                    rpt_hit_surface, the resolve walk that names the triangle, the barycentrics and the group's child
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -61,6 +63,7 @@
 #include "host_scene.h"
 #include "kernels.h"
 #include "render_plan.h"
+#include "surface_plan.h"
 
 namespace rptapi {
 
@@ -194,6 +197,9 @@ struct rptgpu_scene {
                                        // stages a piece of probes in the same four (api_probes.cpp)
   DevBuf<uint8_t> occ_out;             // rptgpu_occluded: a piece of a host caller's answers (api_occlusion.cpp)
   DevBuf<double> hits_out;             // rptgpu_first_hits: a piece of a host caller's records, the named channels back to back (api_hits.cpp)
+  DevBuf<double> surface_out;          // rptgpu_hit_surface: the handle's pair of T and OBJECT and a piece of a host caller's records (api_surface.cpp, surface_plan.h layout)
+  DevBuf<double> surf_defer, surf_frame; // ... and rpt_hit_surface's columns (surface_plan.h columns), as high as gen_levels / gen_frames
+  rptsurface::Columns surf_cols{};
   DevBuf<double> vertices_out;         // rptgpu_trace_vertices: a piece of a host caller's records, the named channels back to back (api_vertices.cpp)
   DevBuf<rptdev::View> view_recs;     // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<uint64_t> view_seeds;         // ... their seeds, when the views have seeds of their own,
@@ -445,6 +451,19 @@ int render_views(rptgpu_scene* h, uint64_t n_views, const RptView* views, const 
                  void* out, bool on_device, bool out_f32, hipStream_t user_stream);
 int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* q, bool seeded,
                      const uint64_t* seeds, const RptAovBuffers* out, bool on_device, hipStream_t user_stream);
+// api_hits.cpp: rptgpu_first_hits' query, piece by piece, as rptgpu_hit_surface runs it too (api_surface.cpp).  plan_hit_pieces:
+// the call's route (flags: its RPT_FLAG_GENERAL_TRAVERSAL into the scene record), the rays per piece (piece_env: the
+// environment variable that overrides it, read per call) and, for the per-tree query, the workspace and its path state.
+// hit_piece: the query over m rays at d_o / d_d on the device and the channels of `ho` — rpt_first_hits, or rpt_raygen_rays,
+// the per-tree query and rpt_hits_store; one RPT_K_EXTEND launch is counted (timed when prof)
+struct HitPieces {
+  bool by_object;
+  uint64_t piece;
+  rptdev::PathState ps;
+};
+HitPieces plan_hit_pieces(rptgpu_scene* h, uint64_t n, uint32_t flags, const char* piece_env);
+void hit_piece(rptgpu_scene* h, const KernelTable* kt, const HitPieces& hp, const double* d_o, const double* d_d, uint32_t m,
+               const rptdev::HitOut& ho, bool prof);
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
 const char* bad_probe_query(const RptProbeQuery* q);

@@ -251,6 +251,18 @@ struct HitOut {
   uint32_t channels;
 };
 
+// rptgpu_hit_surface's resolve pass (kernels/hit_surface.inc): the first-hit query's t and object of the piece's rays — the
+// caller's arrays where it named them, else the handle's scratch pair — and the arrays of RptSurfaceArrays the pass writes,
+// offset to the piece.  Only the arrays of the channels named in `channels` (RPT_SURFACE_CHILD / _PRIMITIVE / _BARYCENTRIC) exist.
+struct SurfaceOut {
+  const double* t;       // [n] read
+  const int32_t* object; // [n] read
+  int32_t* child;        // [n]
+  int32_t* primitive;    // [n]
+  double* barycentric;   // [n][3]
+  uint32_t channels;
+};
+
 // rptgpu_trace_vertices' device outputs (kernels/wf_vertices.inc): the arrays of RptVertexArrays, offset to the piece.  Path
 // (p, s) — ray p of the piece, sample s of the call — has its length at [p * iterations + s] and vertex d at
 // [(p * iterations + s) * stride + d] (x 3 for the vector channels).  Only the arrays of the channels named in `channels`

@@ -310,6 +310,20 @@ RPT_FORM_TU_DECLS(vertices, )
 #undef RPT_FORM_TU_DECLS
 #undef RPT_FORM_TU_DECLS_NS
 
+// rptgpu_hit_surface's resolve pass (kernels/hit_surface.inc), in translation units of its own (kernels_surface_strict[_ext].hip)
+// and outside the tables: n rays of the caller ([n][3] f64 on the device), out.t / out.object the first-hit query's answers for
+// them; the named channels of out are written.  gs: the walk's columns, blocks * 256 <= gs.threads.  groups_from_inf: some group
+// of the scene holds a MonomialSurface (a group's walk then starts from +inf).  *overflow is raised if a walk outgrows gs
+#define RPT_SURFACE_TU_DECLS(NS)                                                                                          \
+  namespace NS {                                                                                                          \
+  void launch_hit_surface(hipStream_t, const rptdev::Scene&, const double* origins, const double* dirs, uint32_t n,       \
+                          const rptdev::SurfaceOut& out, const GenericStack& gs, bool groups_from_inf, uint32_t* overflow, \
+                          uint32_t blocks);                                                                               \
+  }
+RPT_SURFACE_TU_DECLS(rpt_strict_surface)
+RPT_SURFACE_TU_DECLS(rpt_strict_ext_surface)
+#undef RPT_SURFACE_TU_DECLS
+
 namespace rpt_strict { extern const KernelTable TABLE; } // -ffp-contract=off (parity mode)
 // the same with the extended shape set (RPT_SHAPE_MONOMIAL, trees of trees) compiled in
 namespace rpt_strict_ext { extern const KernelTable TABLE; }

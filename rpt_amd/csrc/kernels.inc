@@ -48,6 +48,8 @@
 //                  fused, rpt_hits_store behind the per-tree query, rpt_views_aov_fold), DESIGN.md §17
 //   wf_vertices.inc rptgpu_trace_vertices: the vertices of a wavefront pass's paths into the caller's layout (rpt_vertices_store per
 //                  depth, rpt_vertices_fold at the end of the pass), DESIGN.md §19
+//   hit_surface.inc rptgpu_hit_surface: the triangle, barycentrics and group child behind a first hit — rpt_hit_surface, a
+//                  resolve walk of the hit object alone, in translation units of its own (kernels_surface_strict[_ext].hip), §21
 //   launch.inc     explicit instantiations, host-side launchers, the KernelTable the api_*.cpp files call through
 //
 // Wave64 throughout (gfx950): queue appends and work fetches use one 64-bit ballot + one atomic per wave.
@@ -63,7 +65,7 @@
 #if defined(RPT_VIEWS_TU) || defined(RPT_RAYS_TU) || defined(RPT_VERTICES_TU)
 #define RPT_FORM_TU 1
 #endif
-#ifndef RPT_FORM_TU
+#if !defined(RPT_FORM_TU) && !defined(RPT_SURFACE_TU)
 #include <rocprim/device/device_radix_sort.hpp>
 #endif
 
@@ -117,6 +119,14 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/rng.inc"
 #include "kernels/shapes.inc"
 #include "kernels/traversal.inc"
+#if defined(RPT_SURFACE_TU)
+// the surface resolve's translation units (kernels_surface_strict[_ext].hip, RPT_NS = rpt_strict[_ext]_surface): the shapes, a
+// tree's steps and rpt_hit_surface with its launcher — no path kernel, no table (DESIGN.md §21)
+#include "kernels/wf_state.inc"
+#include "kernels/wf_sort_key.inc"
+#include "kernels/tree_query.inc"
+#include "kernels/hit_surface.inc"
+#else
 #include "kernels/sampling.inc"
 #include "kernels/material.inc"
 #include "kernels/light.inc"
@@ -162,5 +172,6 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/wf_vertices.inc"
 #include "kernels/launch.inc"
 #endif // RPT_FORM_TU
+#endif // RPT_SURFACE_TU
 
 } // namespace RPT_NS

@@ -750,46 +750,74 @@ class GpuScene:
         a = _abi.RptHitArrays()
         a.struct_size, a.reserved = C.sizeof(_abi.RptHitArrays), 0
         named = [c for c in self._HIT_CHANNELS if q.channels & c[0]]
-        if hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr"):
-            return self._first_hits_torch(origins, dirs, q, a, named)
+        return self._ray_records("first_hits", origins, dirs, q, a, named)
 
-        def vectors(v, what):
+    _SURFACE_CHANNELS = ((_abi.RPT_SURFACE_T, "t", (), np.float64), (_abi.RPT_SURFACE_OBJECT, "object", (), np.int32),
+                         (_abi.RPT_SURFACE_CHILD, "child", (), np.int32), (_abi.RPT_SURFACE_PRIMITIVE, "primitive", (), np.int32),
+                         (_abi.RPT_SURFACE_BARYCENTRIC, "barycentric", (3,), np.float64))
+
+    def hit_surface(self, origins, dirs, channels=_abi.RPT_SURFACE_ALL, flags=0):
+        """The surface element behind the first hit of each of the caller's rays (rptgpu_hit_surface) -> a
+        dict with one array per channel of `channels` (RPT_SURFACE_*): `t` (n,) float64 and `object` (n,) int32 —
+        closest_hit's, to join on —, `child` (n,) int32 — the hit group's direct child in the caller's order, else -1 —,
+        `primitive` (n,) int32 — the hit triangle's index in its mesh in the caller's order, else -1 —, `barycentric`
+        (n, 3) float64 — the weights (u, v, w) of v1, v2, v3 as Triangle::intersect computed them, +0.0 without a
+        triangle (rpt_amd.surface.interpolate takes the last two).  origins, dirs: (n, 3) float64, used as given.  numpy
+        arrays go through host memory; torch tensors on the handle's device are read where they lie
+        (rptgpu_hit_surface_device) and the results are new tensors there."""
+        if not _abi.hit_surface_supported(self.lib):
+            raise _abi.RptGpuError(_abi.RPTGPU_E_INVALID_ARGUMENT, "this library does not export rptgpu_hit_surface")
+        q = _abi.RptSurfaceQuery()
+        q.struct_size, q.channels = C.sizeof(_abi.RptSurfaceQuery), int(channels)
+        q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        a = _abi.RptSurfaceArrays()
+        a.struct_size, a.reserved = C.sizeof(_abi.RptSurfaceArrays), 0
+        named = [c for c in self._SURFACE_CHANNELS if q.channels & c[0]]
+        return self._ray_records("hit_surface", origins, dirs, q, a, named)
+
+    def _ray_records(self, what, origins, dirs, q, a, named):
+        """first_hits' and hit_surface's common half: the rays checked, one new array per named channel with its address
+        in `a`, then rptgpu_<what> — or, for torch tensors, rptgpu_<what>_device."""
+        if hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr"):
+            return self._ray_records_torch(what, origins, dirs, q, a, named)
+
+        def vectors(v, name):
             v = np.asarray(v)
             if v.dtype != np.float64 or v.ndim != 2 or v.shape[1] != 3:
-                raise ValueError("first_hits: %s must be an (n, 3) float64 array" % what)
+                raise ValueError("%s: %s must be an (n, 3) float64 array" % (what, name))
             return np.ascontiguousarray(v)
 
         o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
         n = len(o)
         if len(d) != n:
-            raise ValueError("first_hits: %d origins for %d directions" % (n, len(d)))
+            raise ValueError("%s: %d origins for %d directions" % (what, n, len(d)))
         out = {}
-        types = dict(_abi.RptHitArrays._fields_)
+        types = dict(type(a)._fields_)
         for _, name, tail, dtype in named:
             out[name] = np.empty((n,) + tail, dtype=dtype)
             setattr(a, name, out[name].ctypes.data_as(types[name]))
         PD = C.POINTER(C.c_double)
-        code = self.lib.rptgpu_first_hits(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD), C.byref(q), C.byref(a))
+        code = getattr(self.lib, "rptgpu_" + what)(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD), C.byref(q), C.byref(a))
         _abi.check(code, self.handle)
         return out
 
-    def _first_hits_torch(self, origins, dirs, q, a, named):
+    def _ray_records_torch(self, what, origins, dirs, q, a, named):
         import torch
         dev = torch.device("cuda", self.device)
 
-        def vectors(t, what):
+        def vectors(t, name):
             if not isinstance(t, torch.Tensor) or t.device != dev:
-                raise ValueError("first_hits: %s must be a torch tensor on %s, like the other array" % (what, dev))
+                raise ValueError("%s: %s must be a torch tensor on %s, like the other array" % (what, name, dev))
             if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
-                raise ValueError("first_hits: %s must be an (n, 3) float64 tensor" % what)
+                raise ValueError("%s: %s must be an (n, 3) float64 tensor" % (what, name))
             return t.contiguous()  # (no copy when it already is)
 
         o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
         n = o.shape[0]
         if d.shape[0] != n:
-            raise ValueError("first_hits: %d origins for %d directions" % (n, d.shape[0]))
+            raise ValueError("%s: %d origins for %d directions" % (what, n, d.shape[0]))
         out = {}
-        types = dict(_abi.RptHitArrays._fields_)
+        types = dict(type(a)._fields_)
         for _, name, tail, dtype in named:
             # (at least one element: an empty tensor has no address, and a named channel's pointer must not be NULL)
             room = torch.empty((max(n, 1),) + tail, dtype=torch.int32 if dtype is np.int32 else torch.float64, device=dev)
@@ -801,8 +829,8 @@ class GpuScene:
         stream = current.cuda_stream
         if not stream:
             current.synchronize()
-        code = self.lib.rptgpu_first_hits_device(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()), C.byref(q),
-                                                 C.byref(a), C.c_void_p(stream or 0))
+        code = getattr(self.lib, "rptgpu_%s_device" % what)(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                            C.byref(q), C.byref(a), C.c_void_p(stream or 0))
         _abi.check(code, self.handle)
         return out
 
