@@ -840,6 +840,16 @@ void rptgpu_kdtree_free(RptKdTree* tree);
  * (host arrays).  fn: 0 exp, 1 log, 2 atan, 3 sin, 4 cos (|x| < 3pi/4), 5 acos, 6 atan2(y, x),
  * 7 y / x computed through the kernels' shared-reciprocal division (must equal IEEE y / x).
  * 8-11 y / x computed in the kernels' batches of 2, 3, 4 and 6 interleaved divisions (must equal IEEE y / x).
+ * 12, 13 the draws of a hit in the persistent kernel's draw-first shading (illuminate's triangle index and (u, v) pair,
+ * then gen_bool(f), u_theta and the +-1 pair of sample_f): 12 as the kernels take them, 13 the same sequence drawn one
+ * next_u64 at a time (must be equal).  x and out hold raw 64-bit words, nine per element, n = 9 * elements (y is not
+ * read; words behind the last whole element come back 0).  In, x[9e + k]: 0 seed, 1 pixel (< 2^32), 2 sample, 3 the
+ * stream's draw counter at the hit (< 2^31; the cached half of an odd counter is derived on the device), 4 the light's
+ * triangle count (1 .. 2^32 - 1), 5 its sampling zone (>= 2^62), 6 f as an f64 in [0, 1], 7 flags: bit 0 sample_f
+ * runs (the path goes on), bit 1 gen_bool's threshold comes from a table of the material's constants, as the kernels
+ * that hold one have it, 8 unused.  Out, out[9e + k]: 0 the triangle's index, 1-2 the (u, v) pair kept, 3 u_theta's
+ * draw (2^63 when none is taken), 4-5 the +-1 pair kept, 6 gen_bool's answer (0 / 1), 7 the counter behind the hit,
+ * 8 the half cached there (0 when the counter is even).  Elements outside these ranges: RPTGPU_E_INVALID_ARGUMENT.
  * Lets the parity tests show that the kernels' transcendental functions are bit-identical to
  * the host's. */
 int rptgpu_eval_math(rptgpu_scene* h, int fn, uint64_t n, const double* x, const double* y,

@@ -758,9 +758,20 @@ int rptgpu_closest_hit(rptgpu_scene* h, uint64_t n, const double* origins, const
 }
 
 int rptgpu_eval_math(rptgpu_scene* h, int fn, uint64_t n, const double* x, const double* y, double* out) {
-  if (!h || (n && (!x || !out)) || fn < 0 || fn > 11 || (fn >= 6 && n && !y))
+  if (!h || (n && (!x || !out)) || fn < 0 || fn > 13 || (fn >= 6 && fn <= 11 && n && !y))
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "bad argument");
   if (!n) return RPTGPU_OK;
+  if (fn >= 12) { // a hit's draws: an element whose rejection loops could not end is refused here
+    for (uint64_t e = 0; e < n / 9; e++) {
+      uint64_t w[9];
+      memcpy(w, x + e * 9, sizeof w);
+      double f;
+      memcpy(&f, &w[6], sizeof f);
+      if (w[1] > 0xFFFFFFFFull || w[3] > 0x7FFFFFFFull || !w[4] || w[4] > 0xFFFFFFFFull || w[5] < (1ull << 62) || !(f >= 0.0 && f <= 1.0) ||
+          w[7] > 3ull)
+        return fail(h, RPTGPU_E_INVALID_ARGUMENT, "bad argument");
+    }
+  }
   return guarded(h, h->device, [&]() -> int {
     DevBuf<double> dx, dy, dout;
     dx.alloc(n); dy.alloc(n); dout.alloc(n);

@@ -21,6 +21,13 @@
 #ifndef RPT_DIV_BATCH
 #define RPT_DIV_BATCH 1
 #endif
+// RPT_DRAW_PLAN=1: hit_draws (kernels/paths_shade.inc) takes a hit's single draws — the light triangle's index, gen_bool(f),
+// u_theta — out of Philox blocks that every lane computes together with the pair next to them (kernels/rng.inc
+// philox_block2, draw_window): the stream is random-access, so only WHEN a block is computed changes, never which draw feeds
+// which value.  0: one next_u64 per single draw, a block at the lanes whose draw counter is even (A/B builds)
+#ifndef RPT_DRAW_PLAN
+#define RPT_DRAW_PLAN 1
+#endif
 // flat scenes with a texture environment: the lanes' queues of parked lookups, RPT_PARK_K entries each, at the end of the
 // wave's dynamic LDS (kernels/paths.inc ParkLds)
 #ifndef RPT_PARK_K

@@ -177,12 +177,67 @@ template <int N> RPT_DEV void eval_div_batch(uint64_t i, uint64_t n, const doubl
   if (i < n - t * N) out[t * N + i] = y[t * N + i] / x[t * N + i];
 }
 
+#if RPT_SHADE_SPLIT
+// fn 12 and 13 of rpt_eval_math: a hit's draws (paths_shade.inc hit_draws).  The arrays hold raw 64-bit words, nine per
+// element (include/rpt_gpu.h has the layout); thread e < n / 9 runs element e.  hit_draws_reference is the reference's
+// sequence written with next_u64 alone, one draw per call
+RPT_DEV void hit_draws_reference(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, HitDraws& o) {
+  for (;;) {
+    const uint64_t v = next_u64(r);
+    if (v * n <= zone) { o.tri = __umul64hi(v, n); break; }
+  }
+  do {
+    o.a = next_u64(r);
+    o.b = next_u64(r);
+  } while (uv_rejected(o.a, o.b));
+  o.th = 1ull << 63; o.qa = 0; o.qb = 0; o.spec = false;
+  if (!sf) return;
+  o.spec = f == 1.0 ? true : next_u64(r) < (uint64_t)(f * 18446744073709551616.0);
+  if (o.spec) o.th = next_u64(r);
+  for (;;) {
+    o.qa = next_u64(r);
+    o.qb = next_u64(r);
+    const double px = u52_of(o.qa) * 2.0 + -1.0, py = u52_of(o.qb) * 2.0 + -1.0;
+    const double sum = px * px + py * py;
+    if (o.spec ? sum < 1.0 : sum <= 1.0) break;
+  }
+}
+RPT_DEV void eval_hit_draws(bool reference, uint64_t e, uint64_t n, const double* x, double* out) {
+  if (e < n - n / 9 * 9) out[n / 9 * 9 + e] = 0.0; // the words behind the last whole element
+  if (e >= n / 9) return;
+  uint64_t in[9];
+#pragma unroll
+  for (int k = 0; k < 9; k++) in[k] = (uint64_t)__double_as_longlong(x[e * 9 + k]);
+  Rng r = rng_make(in[0], (uint32_t)in[1], in[2], (uint32_t)in[3]);
+  const double f = __longlong_as_double((long long)in[6]);
+  const bool sf = in[7] & 1ull;
+  HitDraws o;
+  if (reference) {
+    hit_draws_reference(r, sf, in[4], in[5], f, o);
+  } else if (in[7] & 2ull) { // as the kernels with the material's constants call it
+    MatConsts mc{};
+    mc.fs = f;
+    mc.p_int = f == 1.0 ? 0ull : (uint64_t)(f * 18446744073709551616.0);
+    hit_draws<true>(r, sf, in[4], in[5], f, o, &mc);
+  } else {
+    hit_draws<false>(r, sf, in[4], in[5], f, o);
+  }
+  const uint64_t res[9] = {o.tri, o.a, o.b, o.th, o.qa, o.qb, o.spec ? 1ull : 0ull, (uint64_t)r.draw, (r.draw & 1u) ? r.hi : 0ull};
+#pragma unroll
+  for (int k = 0; k < 9; k++) out[e * 9 + k] = __longlong_as_double((long long)res[k]);
+}
+#endif
+
 __global__ void __launch_bounds__(256) rpt_eval_math(int fn, uint64_t n, const double* __restrict__ x,
                                                      const double* __restrict__ y, double* __restrict__ out) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   double s, c;
   switch (fn) {
+#if RPT_SHADE_SPLIT
+    case 12: eval_hit_draws(false, i, n, x, out); break;
+    case 13: eval_hit_draws(true, i, n, x, out); break;
+#endif
     case 0: out[i] = rptc_exp(x[i]); break; // (0, 2-6: the converged forms the kernels call, math_converged.h)
     case 1: out[i] = rpt_log(x[i]); break;
     case 2: out[i] = rptc_atan(x[i]); break;

@@ -18,8 +18,69 @@ struct HitDraws {
   uint64_t qa, qb; // the +-1 pair that was kept
   bool spec;      // gen_bool(f)
 };
+RPT_DEV bool uv_rejected(uint64_t a, uint64_t b) { return (a >> 11) + (b >> 11) >= (1ull << 53) + 2ull; } // u + v > 1
 // sf: sample_f runs (depth < max_bounces); f: sample_f's lobe probability; mc (CONSTS): the material's constants, with
 // gen_bool(f)'s threshold among them
+#if RPT_DRAW_PLAN
+// The single draws among them — the index, gen_bool's, u_theta's — are not drawn one by one (next_u64 computes a block
+// at the lanes whose counter is even, and the wave pays a whole block issue for it): they come out of blocks that every
+// lane computes together with the pair behind them (rng.inc: the stream is random-access).  Which draw feeds which value,
+// and where the stream stands afterwards, is what the sequence of calls gives (RPT_DRAW_PLAN 0, below).
+template <bool CONSTS = false>
+RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, HitDraws& o, const MatConsts* mc = nullptr) {
+  // the index and the first (u, v) pair are draws d, d + 1, d + 2.  Block (d + 1) >> 1 holds all three of an odd lane
+  // (with its cached half) and the first two of an even lane, which is then where an odd lane is in front of a pair: the
+  // one loop below serves the even lanes' first pair and everybody's redraws, a block per round
+  {
+    uint64_t lo, hi;
+    philox_block(r.k0, r.k1, r.pixel, r.slo, r.shi, (r.draw + 1u) >> 1, lo, hi);
+    const bool odd = r.draw & 1u;
+    const uint64_t vi = odd ? r.hi : lo;
+    bool need, redraw; // need: the lane has no accepted pair yet; redraw: the round it needs follows a rejected pair
+    if (__ballot(vi * n > zone) != 0ull) { // some lane's index draw lies outside the zone (below 2^-60 per draw, and
+      o.tri = gen_index_zone(r, n, zone);  // never for a power of two): the wave takes the sequence of calls
+      next2_u64(r, o.a, o.b);
+      need = uv_rejected(o.a, o.b);
+      redraw = true;
+    } else {
+      o.tri = __umul64hi(vi, n);
+      o.a = lo; o.b = hi;
+      need = odd ? uv_rejected(lo, hi) : true;
+      redraw = odd;
+      r.hi = hi; // an even lane stands at d + 1 with that draw cached, an odd one at d + 3 with nothing to cache
+      r.draw += odd ? 3u : 1u;
+    }
+    while (need) {
+      if (redraw) PROF_COUNT(PF_P_REJECT);
+      next2_u64(r, o.a, o.b);
+      need = uv_rejected(o.a, o.b);
+      redraw = true;
+    }
+  }
+  o.th = 1ull << 63; o.qa = 0; o.qb = 0; o.spec = false;
+  if (!sf) return;
+  // gen_bool(f) — no draw when f == 1.0 —, u_theta for the specular lobe and the first +-1 pair: three or four draws
+  // from the window's front
+  const DrawWindow w = draw_window(r);
+  const bool gb = f != 1.0;
+  uint64_t p_int;
+  if constexpr (CONSTS) p_int = mc->p_int;
+  else p_int = (uint64_t)(f * 18446744073709551616.0);
+  o.spec = gb ? w.w0 < p_int : true;
+  const bool four = gb && o.spec; // both single draws in front of the pair; else exactly one of them
+  if (o.spec) o.th = gb ? w.w1 : w.w0;
+  o.qa = four ? w.w2 : w.w1;
+  o.qb = four ? w.w3 : w.w2;
+  draw_take(r, w, four ? 4u : 3u);
+  for (;;) {
+    PROF_COUNT(PF_P_REJECT);
+    const double x = u52_of(o.qa) * 2.0 + -1.0, y = u52_of(o.qb) * 2.0 + -1.0;
+    const double sum = x * x + y * y;
+    if (o.spec ? sum < 1.0 : sum <= 1.0) break;
+    next2_u64(r, o.qa, o.qb);
+  }
+}
+#else
 template <bool CONSTS = false>
 RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, HitDraws& o, const MatConsts* mc = nullptr) {
   o.tri = gen_index_zone(r, n, zone);
@@ -41,6 +102,7 @@ RPT_DEV void hit_draws(Rng& r, bool sf, uint64_t n, uint64_t zone, double f, Hit
     if (o.spec ? sum < 1.0 : sum <= 1.0) break;
   }
 }
+#endif
 
 // bsdf() for an opaque material: both directions outside (the reflection case) or zero, its early return a select
 // (CONSTS: m2, m2 * PI, f0 and one - f0 from the material's constants)

@@ -71,6 +71,47 @@ RPT_DEV void next2_u64(Rng& r, uint64_t& a, uint64_t& b) {
   }
   r.draw += 2u;
 }
+// Blocks j and j + 1 of a stream in one straight-line run: the two chains' rounds side by side under one key schedule, as
+// div_ieee's slots (vec.inc).  Each chain is philox_block's, operation for operation.
+RPT_DEV void philox_block2(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t j, uint64_t& lo0,
+                           uint64_t& hi0, uint64_t& lo1, uint64_t& hi1) {
+  uint32_t a0 = c0, a1 = c1, a2 = c2, a3 = j, b0 = c0, b1 = c1, b2 = c2, b3 = j + 1u;
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    uint64_t p0 = (uint64_t)0xD2511F53u * a0, q0 = (uint64_t)0xD2511F53u * b0;
+    uint64_t p1 = (uint64_t)0xCD9E8D57u * a2, q1 = (uint64_t)0xCD9E8D57u * b2;
+    uint32_t n0 = (uint32_t)(p1 >> 32) ^ a1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ a3 ^ k1;
+    uint32_t m0 = (uint32_t)(q1 >> 32) ^ b1 ^ k0, m2 = (uint32_t)(q0 >> 32) ^ b3 ^ k1;
+    a0 = n0; a1 = (uint32_t)p1; a2 = n2; a3 = (uint32_t)p0;
+    b0 = m0; b1 = (uint32_t)q1; b2 = m2; b3 = (uint32_t)q0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  lo0 = ((uint64_t)a1 << 32) | a0;
+  hi0 = ((uint64_t)a3 << 32) | a2;
+  lo1 = ((uint64_t)b1 << 32) | b0;
+  hi1 = ((uint64_t)b3 << 32) | b2;
+}
+// The stream is random-access: draw k is half k & 1 of block k >> 1, and a lane whose counter d is odd holds draw d in
+// `hi`.  A window is the draws d .. d + 3 of every lane of the wave out of ONE issue of blocks (d + 1) >> 1 and the
+// next one: an even lane's are the four halves, an odd lane's its cached half and the first three.  `tail`, the second
+// block's second half, is draw d + 3 of an even lane and draw d + 4 of an odd one — so it is the half to cache
+// whenever the counter behind what the caller consumes, d + 3 or d + 4, is odd (draw_take).  The stream itself is
+// left where it was: a caller consumes with draw_take.
+struct DrawWindow {
+  uint64_t w0, w1, w2, w3, tail;
+};
+RPT_DEV DrawWindow draw_window(const Rng& r) {
+  uint64_t l0, h0, l1, h1;
+  philox_block2(r.k0, r.k1, r.pixel, r.slo, r.shi, (r.draw + 1u) >> 1, l0, h0, l1, h1);
+  const bool odd = r.draw & 1u;
+  return DrawWindow{odd ? r.hi : l0, odd ? l0 : h0, odd ? h0 : l1, odd ? l1 : h1, h1};
+}
+// the window's first `count` draws are consumed, count = 3 or 4: the stream as that many next_u64 calls leave it
+RPT_DEV void draw_take(Rng& r, const DrawWindow& w, uint32_t count) {
+  r.draw += count;
+  r.hi = w.tail;
+}
 // rand 0.8 Standard f64: 53 bits in [0,1)
 RPT_DEV double gen_f64(Rng& r) { return (double)(next_u64(r) >> 11) * (1.0 / 9007199254740992.0); }
 // 52-bit mantissa trick: [1,2) - 1
