@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _abi
+from . import _abi, _marshal
 from .scene import geometry_mismatch, geometry_snapshot
 from .shape import XF_WORDS, KdTree, Transformed, lower_shapes
 
@@ -34,6 +34,11 @@ def scene_options(**fields):
             raise TypeError("RptSceneOptions has no field %r" % k)
         setattr(o, k, v)
     return o
+
+
+def _lower_camera(camera):
+    """a Camera lowered; an RptCamera as it is"""
+    return camera.lower() if hasattr(camera, "lower") else camera
 
 
 def device_count():
@@ -128,37 +133,9 @@ class GpuScene:
         index = int(index)
         if index < 0:
             raise ValueError("set_mesh: object index %d is negative" % index)
-        if isinstance(triangles, np.ndarray) or not hasattr(triangles, "data_ptr"):
-            arr = np.asarray(triangles)
-            if arr.dtype != np.float64:
-                raise TypeError("set_mesh: triangles must be float64, not %s" % arr.dtype)
-            if arr.ndim != 2 or arr.shape[1] != 18:
-                raise ValueError("set_mesh: triangles must have shape (n, 18), not %s" % (tuple(arr.shape),))
-            arr = np.ascontiguousarray(arr)
-            code = self.lib.rptgpu_scene_set_mesh(self.handle, index, arr.shape[0],
-                                                  arr.ctypes.data_as(C.POINTER(_abi.RptTriangle)))
-            _abi.check(code, self.handle)
-            return
-        import torch
-        t = triangles
-        if t.dtype != torch.float64:
-            raise TypeError("set_mesh: triangles must be float64, not %s" % t.dtype)
-        if t.dim() != 2 or t.shape[1] != 18:
-            raise ValueError("set_mesh: triangles must have shape (n, 18), not %s" % (tuple(t.shape),))
-        if not t.is_cuda or t.device.index != self.device:
-            raise ValueError("set_mesh: the tensor is on %s, the handle on device %d (pass a numpy array for host data)"
-                             % (t.device, self.device))
-        if not t.is_contiguous():
-            raise ValueError("set_mesh: the tensor must be contiguous")
-        # the tensor's producer ran on torch's current stream, which nothing orders with the handle's: a stream with a
-        # handle goes to the library, which waits for it; the null stream (handle 0, the ABI's "no stream") is waited for here
-        current = torch.cuda.current_stream(t.device)
-        stream = current.cuda_stream
-        if not stream:
-            current.synchronize()
-        code = self.lib.rptgpu_scene_set_mesh_device(self.handle, index, int(t.shape[0]), C.c_void_p(t.data_ptr()),
-                                                     C.c_void_p(stream or 0))
-        _abi.check(code, self.handle)
+        m = _marshal.pick(self.device, triangles)
+        rows = m.rows(triangles, 18, "set_mesh", "triangles")
+        self._call("rptgpu_scene_set_mesh", m, index, int(rows.shape[0]), m.pointer(rows, C.POINTER(_abi.RptTriangle)))
 
     # ---- a group whose children move (rptgpu_scene_set_group[_device]): new placements for the children of one
     # KdTree of spheres and cubes, the count, the kinds and which children are Transformed unchanged.  The children's
@@ -172,44 +149,24 @@ class GpuScene:
         index = int(index)
         if index < 0:
             raise ValueError("set_group: object index %d is negative" % index)
-        if hasattr(children, "data_ptr"):
-            import torch
-            t = children
-            if t.dtype != torch.float64:
-                raise TypeError("set_group: transform records must be float64, not %s" % t.dtype)
-            if t.dim() != 2 or t.shape[1] != XF_WORDS:
-                raise ValueError("set_group: transform records must have shape (n, %d), not %s" % (XF_WORDS, tuple(t.shape)))
-            if not t.is_cuda or t.device.index != self.device:
-                raise ValueError("set_group: the tensor is on %s, the handle on device %d (pass a numpy array for host data)"
-                                 % (t.device, self.device))
-            if not t.is_contiguous():
-                raise ValueError("set_group: the tensor must be contiguous")
-            current = torch.cuda.current_stream(t.device)  # (as set_mesh: the library waits for a stream with a handle)
-            stream = current.cuda_stream
-            if not stream:
-                current.synchronize()
-            code = self.lib.rptgpu_scene_set_group_device(self.handle, index, int(t.shape[0]), C.c_void_p(t.data_ptr()),
-                                                          C.c_void_p(stream or 0))
-            _abi.check(code, self.handle)
-            return
+        m = _marshal.pick(self.device, children)
+        if m.suffix:  # records on the device: the library reads them there
+            rows = m.rows(children, XF_WORDS, "set_group", "transform records")
+            return self._call("rptgpu_scene_set_group", m, index, int(rows.shape[0]), m.pointer(rows, None))
         if isinstance(children, np.ndarray):
-            rows = children
-            if rows.dtype != np.float64:
-                raise TypeError("set_group: transform records must be float64, not %s" % rows.dtype)
-            if rows.ndim != 2 or rows.shape[1] != XF_WORDS:
-                raise ValueError("set_group: transform records must have shape (n, %d), not %s" % (XF_WORDS, tuple(rows.shape)))
+            rows = m.rows(children, XF_WORDS, "set_group", "transform records")
             arr, n = self._creation_children(index)
             if n != rows.shape[0]:
                 raise ValueError("set_group: %d transform records for the %d children of object %d" % (rows.shape[0], n, index))
             if n:  # the records into the xf fields of the creation's children (kinds and `transformed` as they were)
                 raw = np.frombuffer(arr, dtype=np.uint8).reshape(-1, C.sizeof(_abi.RptShape))[:n]
                 at = _abi.RptShape.xf.offset
-                raw[:, at:at + 8 * XF_WORDS] = np.ascontiguousarray(rows).view(np.uint8).reshape(n, 8 * XF_WORDS)
+                raw[:, at:at + 8 * XF_WORDS] = rows.view(np.uint8).reshape(n, 8 * XF_WORDS)
         else:
             children = list(children)
             keep = []
             arr, n = lower_shapes(children, keep), len(children)
-        _abi.check(self.lib.rptgpu_scene_set_group(self.handle, index, n, arr), self.handle)
+        self._call("rptgpu_scene_set_group", m, index, n, arr)
 
     def _creation_children(self, index):
         """the children of object `index` as lowered at creation (cached: set_group writes new records into it)"""
@@ -246,14 +203,14 @@ class GpuScene:
     def render_batch(self, camera, params):
         """Renderer::sample's output: (H*W, 3) float64 means, row-major, top row first."""
         out = np.empty((params.height * params.width, 3), dtype=np.float64)
-        cam = camera.lower() if hasattr(camera, "lower") else camera
+        cam = _lower_camera(camera)
         code = self.lib.rptgpu_render_batch(self.handle, C.byref(cam), C.byref(params),
                                             out.ctypes.data_as(C.POINTER(C.c_double)))
         _abi.check(code, self.handle)
         return out
 
     def render_batch_device(self, camera, params, d_ptr, out_is_f32=False, stream=None):
-        cam = camera.lower() if hasattr(camera, "lower") else camera
+        cam = _lower_camera(camera)
         code = self.lib.rptgpu_render_batch_device(self.handle, C.byref(cam), C.byref(params),
                                                    C.c_void_p(d_ptr), 1 if out_is_f32 else 0,
                                                    C.c_void_p(stream or 0))
@@ -278,7 +235,7 @@ class GpuScene:
     def render_batch_reduce(self, camera, params, root=0, out=None):
         """Renderer::sample on every rank: this rank's tiles, the owned pixels gathered on `root` over RCCL
         (params.collective = RPT_COLLECTIVE_REDUCE: ncclReduce(sum) of zero-filled frames), result in host memory on root.  `out`: float32 array of width*height*3 (allocated if None on root)."""
-        cam = camera.lower() if hasattr(camera, "lower") else camera
+        cam = _lower_camera(camera)
         if out is None:
             out = np.empty(params.height * params.width * 3, dtype=np.float32)
         code = self.lib.rptgpu_render_batch_reduce(self.handle, C.byref(cam), C.byref(params), int(root),
@@ -288,7 +245,7 @@ class GpuScene:
 
     def render_batch_emulate_ranks(self, camera, params, world, out=None):
         """Diagnostics: the frame as `world` ranks' gather would assemble it, on this one GPU (include/rpt_gpu.h)."""
-        cam = camera.lower() if hasattr(camera, "lower") else camera
+        cam = _lower_camera(camera)
         if out is None:
             out = np.empty(params.height * params.width * 3, dtype=np.float32)
         code = self.lib.rptgpu_render_batch_emulate_ranks(self.handle, C.byref(cam), C.byref(params), int(world),
@@ -296,18 +253,35 @@ class GpuScene:
         _abi.check(code, self.handle)
         return out
 
+    # ---- the array calls.  Each is one body written against a backend of _marshal.py — _marshal.HOST for numpy arrays, the
+    # device backend for torch tensors on the handle's device —, which checks the arrays, allocates the results and says
+    # in which form the symbol takes a pointer; _call appends the backend's suffix and stream argument.
+    def _call(self, name, m, *args):
+        """rptgpu_<name>, or for the device backend rptgpu_<name>_device with the stream behind the arguments"""
+        _abi.check(getattr(self.lib, name + m.suffix)(self.handle, *args, *m.stream_args()), self.handle)
+
+    _RAYS = ("origins", "dirs", "{a} origins for {b} directions")
+    _POINTS = ("positions", "normals", "{b} normals for {a} positions")
+
+    @staticmethod
+    def _pair(m, a, b, who, names, coerce=False):
+        """two (n, 3) float64 arrays of one length, named by _RAYS or _POINTS -> (n, the two as the backend takes them)"""
+        a, b = m.vectors(a, who, names[0], coerce), m.vectors(b, who, names[1], coerce)
+        n = int(a.shape[0])
+        if int(b.shape[0]) != n:
+            raise ValueError(who + ": " + names[2].format(a=n, b=int(b.shape[0])))
+        return n, a, b
+
     def closest_hit(self, origins, dirs, precision=_abi.RPT_PRECISION_F64_STRICT):
-        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
-        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        m = _marshal.HOST  # (numpy only)
+        # the call's contract: anything that reshapes to (n, 3) doubles, and the directions' count is the library's to check
+        o, d = m.vectors(origins, "closest_hit", "origins", coerce=True), m.vectors(dirs, "closest_hit", "dirs", coerce=True)
         n = len(o)
-        t = np.empty(n, dtype=np.float64)
-        nrm = np.empty((n, 3), dtype=np.float64)
-        obj = np.empty(n, dtype=np.int32)
+        t, nrm, obj = (m.result(None, shape, dtype, "closest_hit", "") for shape, dtype in
+                       (((n,), np.float64), ((n, 3), np.float64), ((n,), np.int32)))
         PD = C.POINTER(C.c_double)
-        code = self.lib.rptgpu_closest_hit(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD),
-                                           int(precision), t.ctypes.data_as(PD), nrm.ctypes.data_as(PD),
-                                           obj.ctypes.data_as(C.POINTER(C.c_int32)))
-        _abi.check(code, self.handle)
+        self._call("rptgpu_closest_hit", m, n, m.pointer(o, PD), m.pointer(d, PD), int(precision), m.pointer(t, PD),
+                   m.pointer(nrm, PD), m.pointer(obj, C.POINTER(C.c_int32)))
         return t, nrm, obj
 
     def trace_rays(self, origins, dirs, max_bounces, samples=1, seed=0x52505447, sample_index_base=0, streams=None,
@@ -323,69 +297,15 @@ class GpuScene:
         q.max_bounces, q.iterations, q.first_draw = int(max_bounces), int(samples), int(first_draw)
         q.exposure_value, q.seed, q.sample_index_base = float(exposure_value), int(seed), int(sample_index_base)
         q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
-        if hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr"):
-            return self._trace_rays_torch(origins, dirs, streams, q, out)
-        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
-        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
-        n = len(o)
-        if len(d) != n:
-            raise ValueError("trace_rays: %d origins for %d directions" % (n, len(d)))
-        ids = None
-        if streams is not None:
-            ids = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
-            if len(ids) != n:
-                raise ValueError("trace_rays: %d stream ids for %d rays" % (len(ids), n))
-        if out is None:
-            out = np.empty((n, 3), dtype=np.float64)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (n, 3) and out.flags.c_contiguous):
-            raise ValueError("trace_rays: out must be a C-contiguous (n, 3) float64 array")
+        m = _marshal.pick(self.device, origins, dirs)
+        # the call's contract: rays of any dtype that reshape to (n, 3), and ids of any dtype and shape that flatten to n
+        n, o, d = self._pair(m, origins, dirs, "trace_rays", self._RAYS, coerce=True)
+        ids = m.stream_ids(streams, n, "trace_rays", "rays", strict=False)
+        # (no room behind `out`: with n = 0 the library gets the address numpy or torch give, NULL for an empty tensor)
+        out = m.result(out, (n, 3), np.float64, "trace_rays", "out")
         PD = C.POINTER(C.c_double)
-        code = self.lib.rptgpu_trace_rays(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD),
-                                          ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None,
-                                          C.byref(q), out.ctypes.data_as(PD))
-        _abi.check(code, self.handle)
-        return out
-
-    def _trace_rays_torch(self, origins, dirs, streams, q, out):
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def rays(t, what):
-            if not isinstance(t, torch.Tensor) or t.device != dev:
-                raise ValueError("trace_rays: %s must be a torch tensor on %s, like the other arrays" % (what, dev))
-            return t.to(torch.float64).reshape(-1, 3).contiguous()  # (no copy when it already is all that)
-
-        o, d = rays(origins, "origins"), rays(dirs, "dirs")
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError("trace_rays: %d origins for %d directions" % (n, d.shape[0]))
-        ids = None
-        if streams is not None:
-            if not isinstance(streams, torch.Tensor) or streams.device != dev:
-                raise ValueError("trace_rays: streams must be a torch tensor on %s, like the rays" % dev)
-            ids = streams.reshape(-1)
-            if ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
-                ids = ids.to(torch.int64).to(torch.int32)  # the low 32 bits
-            ids = ids.contiguous()
-            if ids.shape[0] != n:
-                raise ValueError("trace_rays: %d stream ids for %d rays" % (ids.shape[0], n))
-        if out is None:
-            out = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.float64
-                  and tuple(out.shape) == (n, 3) and out.is_contiguous()):
-            raise ValueError("trace_rays: out must be a contiguous (n, 3) float64 tensor on %s" % dev)
-        # The tensors' producer — and the conversions above — ran on torch's current stream; the handle's own stream is
-        # non-blocking, so nothing orders the two by itself.  A stream with a handle is handed to the library, which
-        # waits for it; torch's default stream is the null stream, whose handle 0 is the ABI's "no stream": that one is
-        # waited for here.
-        current = torch.cuda.current_stream(dev)
-        stream = current.cuda_stream
-        if not stream:
-            current.synchronize()
-        code = self.lib.rptgpu_trace_rays_device(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                                                 C.c_void_p(ids.data_ptr()) if ids is not None else None, C.byref(q),
-                                                 C.c_void_p(out.data_ptr()), C.c_void_p(stream or 0))
-        _abi.check(code, self.handle)
+        self._call("rptgpu_trace_rays", m, n, m.pointer(o, PD), m.pointer(d, PD), m.pointer(ids, C.POINTER(C.c_uint32)),
+                   C.byref(q), m.pointer(out, PD))
         return out
 
     def bake_probes(self, positions, normals=None, *, kind, samples, max_bounces, seed, sample_index_base=0, streams=None,
@@ -411,88 +331,18 @@ class GpuScene:
         q.seed, q.sample_index_base = int(seed), int(sample_index_base)
         q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
         tail = (9, 3) if kind == _abi.RPT_PROBE_SH9 else (3,)
-        if hasattr(positions, "data_ptr") or hasattr(normals, "data_ptr"):
-            return self._bake_probes_torch(positions, normals, streams, q, tail, out)
-
-        def vectors(a, what):
-            a = np.asarray(a)
-            if a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 3:
-                raise ValueError("bake_probes: %s must be an (n, 3) float64 array" % what)
-            return np.ascontiguousarray(a)
-
-        pos = vectors(positions, "positions")
-        n = len(pos)
-        nrm = None
-        if normals is not None:
-            nrm = vectors(normals, "normals")
-            if len(nrm) != n:
-                raise ValueError("bake_probes: %d normals for %d positions" % (len(nrm), n))
-        ids = None
-        if streams is not None:
-            ids = np.asarray(streams)
-            if ids.ndim != 1 or ids.dtype.kind not in "iu":
-                raise ValueError("bake_probes: streams must be an (n,) integer array")
-            if len(ids) != n:
-                raise ValueError("bake_probes: %d stream ids for %d probes" % (len(ids), n))
-            ids = np.ascontiguousarray(ids, dtype=np.uint32)
-        if out is None:
-            out = np.empty((n,) + tail, dtype=np.float64)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == (n,) + tail and out.flags.c_contiguous):
-            raise ValueError("bake_probes: out must be a C-contiguous %s float64 array" % (("n",) + tail,))
+        m = _marshal.pick(self.device, positions, normals)
+        # the call's contract: (n, 3) float64 as they come, and ids that are one-dimensional and integer
+        if normals is None:
+            pos, nrm = m.vectors(positions, "bake_probes", "positions"), None
+            n = int(pos.shape[0])
+        else:
+            n, pos, nrm = self._pair(m, positions, normals, "bake_probes", self._POINTS)
+        ids = m.stream_ids(streams, n, "bake_probes", "probes", strict=True)
+        out = m.result(out, (n,) + tail, np.float64, "bake_probes", "out")
         PD = C.POINTER(C.c_double)
-        code = self.lib.rptgpu_bake_probes(self.handle, n, pos.ctypes.data_as(PD),
-                                           nrm.ctypes.data_as(PD) if nrm is not None else None,
-                                           ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None,
-                                           C.byref(q), out.ctypes.data_as(PD))
-        _abi.check(code, self.handle)
-        return out
-
-    def _bake_probes_torch(self, positions, normals, streams, q, tail, out):
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def vectors(t, what):
-            if not isinstance(t, torch.Tensor) or t.device != dev:
-                raise ValueError("bake_probes: %s must be a torch tensor on %s, like the other arrays" % (what, dev))
-            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
-                raise ValueError("bake_probes: %s must be an (n, 3) float64 tensor" % what)
-            return t.contiguous()  # (no copy when it already is)
-
-        pos = vectors(positions, "positions")
-        n = pos.shape[0]
-        nrm = None
-        if normals is not None:
-            nrm = vectors(normals, "normals")
-            if nrm.shape[0] != n:
-                raise ValueError("bake_probes: %d normals for %d positions" % (nrm.shape[0], n))
-        ids = None
-        if streams is not None:
-            if not isinstance(streams, torch.Tensor) or streams.device != dev:
-                raise ValueError("bake_probes: streams must be a torch tensor on %s, like the probes" % dev)
-            if streams.dim() != 1 or streams.dtype.is_floating_point:
-                raise ValueError("bake_probes: streams must be an (n,) integer tensor")
-            ids = streams
-            if ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
-                ids = ids.to(torch.int64).to(torch.int32)  # the low 32 bits
-            ids = ids.contiguous()
-            if ids.shape[0] != n:
-                raise ValueError("bake_probes: %d stream ids for %d probes" % (ids.shape[0], n))
-        if out is None:
-            out = torch.empty((n,) + tail, dtype=torch.float64, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.float64
-                  and tuple(out.shape) == (n,) + tail and out.is_contiguous()):
-            raise ValueError("bake_probes: out must be a contiguous %s float64 tensor on %s" % ((("n",) + tail), dev))
-        # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
-        # stream is waited for here)
-        current = torch.cuda.current_stream(dev)
-        stream = current.cuda_stream
-        if not stream:
-            current.synchronize()
-        code = self.lib.rptgpu_bake_probes_device(self.handle, n, C.c_void_p(pos.data_ptr()),
-                                                  C.c_void_p(nrm.data_ptr()) if nrm is not None else None,
-                                                  C.c_void_p(ids.data_ptr()) if ids is not None else None, C.byref(q),
-                                                  C.c_void_p(out.data_ptr()), C.c_void_p(stream or 0))
-        _abi.check(code, self.handle)
+        self._call("rptgpu_bake_probes", m, n, m.pointer(pos, PD), m.pointer(nrm, PD), m.pointer(ids, C.POINTER(C.c_uint32)),
+                   C.byref(q), m.pointer(out, PD))
         return out
 
     def occluded(self, origins, dirs, max_t=None, flags=0, out=None):
@@ -504,73 +354,13 @@ class GpuScene:
         q = _abi.RptVisibilityQuery()
         q.struct_size = C.sizeof(_abi.RptVisibilityQuery)
         q.precision_mode, q.flags, q.reserved = _abi.RPT_PRECISION_F64_STRICT, int(flags), 0
-        if hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr"):
-            return self._occluded_torch(origins, dirs, max_t, q, out)
-
-        def vectors(a, what):
-            a = np.asarray(a)
-            if a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 3:
-                raise ValueError("occluded: %s must be an (n, 3) float64 array" % what)
-            return np.ascontiguousarray(a)
-
-        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
-        n = len(o)
-        if len(d) != n:
-            raise ValueError("occluded: %d origins for %d directions" % (n, len(d)))
-        mt = None
-        if max_t is not None:
-            mt = np.asarray(max_t)
-            if mt.dtype != np.float64 or mt.shape != (n,):
-                raise ValueError("occluded: max_t must be an (n,) float64 array")
-            mt = np.ascontiguousarray(mt)
-        if out is None:
-            out = np.empty(n, dtype=np.uint8)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.shape == (n,) and out.flags.c_contiguous):
-            raise ValueError("occluded: out must be a C-contiguous (n,) uint8 array")
+        m = _marshal.pick(self.device, origins, dirs)
+        n, o, d = self._pair(m, origins, dirs, "occluded", self._RAYS)  # the call's contract: (n, 3) float64 as they come
+        mt = m.scalars(max_t, n, "occluded", "max_t")
+        out = m.result(out, (n,), np.uint8, "occluded", "out")
         PD = C.POINTER(C.c_double)
-        code = self.lib.rptgpu_occluded(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD),
-                                        mt.ctypes.data_as(PD) if mt is not None else None, C.byref(q),
-                                        out.ctypes.data_as(C.POINTER(C.c_uint8)))
-        _abi.check(code, self.handle)
-        return out
-
-    def _occluded_torch(self, origins, dirs, max_t, q, out):
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def vectors(t, what):
-            if not isinstance(t, torch.Tensor) or t.device != dev:
-                raise ValueError("occluded: %s must be a torch tensor on %s, like the other arrays" % (what, dev))
-            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
-                raise ValueError("occluded: %s must be an (n, 3) float64 tensor" % what)
-            return t.contiguous()  # (no copy when it already is)
-
-        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError("occluded: %d origins for %d directions" % (n, d.shape[0]))
-        mt = None
-        if max_t is not None:
-            if not isinstance(max_t, torch.Tensor) or max_t.device != dev:
-                raise ValueError("occluded: max_t must be a torch tensor on %s, like the rays" % dev)
-            if max_t.dtype != torch.float64 or tuple(max_t.shape) != (n,):
-                raise ValueError("occluded: max_t must be an (n,) float64 tensor")
-            mt = max_t.contiguous()
-        if out is None:
-            out = torch.empty((n,), dtype=torch.uint8, device=dev)
-        elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.uint8
-                  and tuple(out.shape) == (n,) and out.is_contiguous()):
-            raise ValueError("occluded: out must be a contiguous (n,) uint8 tensor on %s" % dev)
-        # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
-        # stream is waited for here)
-        current = torch.cuda.current_stream(dev)
-        stream = current.cuda_stream
-        if not stream:
-            current.synchronize()
-        code = self.lib.rptgpu_occluded_device(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                                               C.c_void_p(mt.data_ptr()) if mt is not None else None, C.byref(q),
-                                               C.c_void_p(out.data_ptr()), C.c_void_p(stream or 0))
-        _abi.check(code, self.handle)
+        self._call("rptgpu_occluded", m, n, m.pointer(o, PD), m.pointer(d, PD), m.pointer(mt, PD), C.byref(q),
+                   m.pointer(out, C.POINTER(C.c_uint8)))
         return out
 
     def bake_ao(self, positions, normals, *, samples, seed, max_distance=float("inf"), sample_index_base=0, streams=None,
@@ -590,95 +380,15 @@ class GpuScene:
         out_ao, out_bent = (out if isinstance(out, (tuple, list)) else (out, None)) if out is not None else (None, None)
         if out_bent is not None and not bent_normals:
             raise ValueError("bake_ao: an output for bent normals without bent_normals=True")
-        if hasattr(positions, "data_ptr") or hasattr(normals, "data_ptr"):
-            return self._bake_ao_torch(positions, normals, streams, q, bent_normals, out_ao, out_bent)
-
-        def vectors(a, what):
-            a = np.asarray(a)
-            if a.dtype != np.float64 or a.ndim != 2 or a.shape[1] != 3:
-                raise ValueError("bake_ao: %s must be an (n, 3) float64 array" % what)
-            return np.ascontiguousarray(a)
-
-        pos, nrm = vectors(positions, "positions"), vectors(normals, "normals")
-        n = len(pos)
-        if len(nrm) != n:
-            raise ValueError("bake_ao: %d normals for %d positions" % (len(nrm), n))
-        ids = None
-        if streams is not None:
-            ids = np.asarray(streams)
-            if ids.ndim != 1 or ids.dtype.kind not in "iu":
-                raise ValueError("bake_ao: streams must be an (n,) integer array")
-            if len(ids) != n:
-                raise ValueError("bake_ao: %d stream ids for %d points" % (len(ids), n))
-            ids = np.ascontiguousarray(ids, dtype=np.uint32)
-
-        def result(a, shape, what):
-            if a is None:
-                return np.empty(shape, dtype=np.float64)
-            if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.shape == shape and a.flags.c_contiguous):
-                raise ValueError("bake_ao: the output for %s must be a C-contiguous %s float64 array" % (what, shape))
-            return a
-
-        out_ao = result(out_ao, (n,), "ao")
-        if bent_normals:
-            out_bent = result(out_bent, (n, 3), "bent normals")
+        m = _marshal.pick(self.device, positions, normals)
+        # the call's contract: (n, 3) float64 as they come, and ids that are one-dimensional and integer
+        n, pos, nrm = self._pair(m, positions, normals, "bake_ao", self._POINTS)
+        ids = m.stream_ids(streams, n, "bake_ao", "points", strict=True)
+        out_ao = m.result(out_ao, (n,), np.float64, "bake_ao", "the output for ao")
+        out_bent = m.result(out_bent, (n, 3), np.float64, "bake_ao", "the output for bent normals") if bent_normals else None
         PD = C.POINTER(C.c_double)
-        code = self.lib.rptgpu_bake_ao(self.handle, n, pos.ctypes.data_as(PD), nrm.ctypes.data_as(PD),
-                                       ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None, C.byref(q),
-                                       out_ao.ctypes.data_as(PD), out_bent.ctypes.data_as(PD) if bent_normals else None)
-        _abi.check(code, self.handle)
-        return (out_ao, out_bent) if bent_normals else out_ao
-
-    def _bake_ao_torch(self, positions, normals, streams, q, bent_normals, out_ao, out_bent):
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def vectors(t, what):
-            if not isinstance(t, torch.Tensor) or t.device != dev:
-                raise ValueError("bake_ao: %s must be a torch tensor on %s, like the other arrays" % (what, dev))
-            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
-                raise ValueError("bake_ao: %s must be an (n, 3) float64 tensor" % what)
-            return t.contiguous()  # (no copy when it already is)
-
-        pos, nrm = vectors(positions, "positions"), vectors(normals, "normals")
-        n = pos.shape[0]
-        if nrm.shape[0] != n:
-            raise ValueError("bake_ao: %d normals for %d positions" % (nrm.shape[0], n))
-        ids = None
-        if streams is not None:
-            if not isinstance(streams, torch.Tensor) or streams.device != dev:
-                raise ValueError("bake_ao: streams must be a torch tensor on %s, like the points" % dev)
-            if streams.dim() != 1 or streams.dtype.is_floating_point:
-                raise ValueError("bake_ao: streams must be an (n,) integer tensor")
-            ids = streams
-            if ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
-                ids = ids.to(torch.int64).to(torch.int32)  # the low 32 bits
-            ids = ids.contiguous()
-            if ids.shape[0] != n:
-                raise ValueError("bake_ao: %d stream ids for %d points" % (ids.shape[0], n))
-
-        def result(t, shape, what):
-            if t is None:
-                return torch.empty(shape, dtype=torch.float64, device=dev)
-            if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float64
-                    and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError("bake_ao: the output for %s must be a contiguous %s float64 tensor on %s" % (what, shape, dev))
-            return t
-
-        out_ao = result(out_ao, (n,), "ao")
-        if bent_normals:
-            out_bent = result(out_bent, (n, 3), "bent normals")
-        # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
-        # stream is waited for here)
-        current = torch.cuda.current_stream(dev)
-        stream = current.cuda_stream
-        if not stream:
-            current.synchronize()
-        code = self.lib.rptgpu_bake_ao_device(self.handle, n, C.c_void_p(pos.data_ptr()), C.c_void_p(nrm.data_ptr()),
-                                              C.c_void_p(ids.data_ptr()) if ids is not None else None, C.byref(q),
-                                              C.c_void_p(out_ao.data_ptr()),
-                                              C.c_void_p(out_bent.data_ptr()) if bent_normals else None, C.c_void_p(stream or 0))
-        _abi.check(code, self.handle)
+        self._call("rptgpu_bake_ao", m, n, m.pointer(pos, PD), m.pointer(nrm, PD), m.pointer(ids, C.POINTER(C.c_uint32)),
+                   C.byref(q), m.pointer(out_ao, PD), m.pointer(out_bent, PD))
         return (out_ao, out_bent) if bent_normals else out_ao
 
     def render_views(self, views, width, height, max_bounces, samples=1, seed=0x52505447, seed_stride=0,
@@ -692,50 +402,30 @@ class GpuScene:
         v renders exactly as with seed = seeds[v] and seed_stride = 0; not together with a non-zero seed_stride.  out: None or
         a C-contiguous float64 numpy array (the frames go through host memory), or a contiguous float64 / float32 torch
         tensor on the handle's device, which is written where it lies (rptgpu_render_views_device)."""
-        views = list(views)
-        n, width, height = len(views), int(width), int(height)
-        arr = self._lower_views(views, "render_views")
-        seed_arr = self._lower_seeds(seeds, n, seed_stride, "render_views")
-        q = _abi.RptViewQuery()
-        q.struct_size = C.sizeof(_abi.RptViewQuery)
-        q.width, q.height, q.max_bounces, q.iterations = width, height, int(max_bounces), int(samples)
-        q.exposure_value, q.seed, q.seed_stride = float(exposure_value), int(seed), int(seed_stride)
-        q.sample_index_base, q.precision_mode, q.flags = int(sample_index_base), _abi.RPT_PRECISION_F64_STRICT, int(flags)
-        shape = (n, height, width, 3)
-        if hasattr(out, "data_ptr"):
-            import torch
-            dev = torch.device("cuda", self.device)
-            if not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype in (torch.float64, torch.float32)
-                    and tuple(out.shape) == shape and out.is_contiguous()):
-                raise ValueError("render_views: out must be a contiguous %s float64 or float32 tensor on %s" % (shape, dev))
-            # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's
-            # default stream is waited for here)
-            current = torch.cuda.current_stream(dev)
-            stream = current.cuda_stream
-            if not stream:
-                current.synchronize()
-            tail = (C.c_void_p(out.data_ptr()), 1 if out.dtype == torch.float32 else 0, C.c_void_p(stream or 0))
-            if seed_arr is None:
-                code = self.lib.rptgpu_render_views_device(self.handle, n, arr, C.byref(q), *tail)
-            else:
-                code = self.lib.rptgpu_render_views_seeded_device(self.handle, n, arr, C.byref(q), seed_arr, *tail)
-            _abi.check(code, self.handle)
-            return out
-        if out is None:
-            out = np.empty(shape, dtype=np.float64)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == shape and out.flags.c_contiguous):
-            raise ValueError("render_views: out must be a C-contiguous %s float64 array" % (shape,))
-        if seed_arr is None:
-            code = self.lib.rptgpu_render_views(self.handle, n, arr, C.byref(q), out.ctypes.data_as(C.POINTER(C.c_double)))
-        else:
-            code = self.lib.rptgpu_render_views_seeded(self.handle, n, arr, C.byref(q), seed_arr,
-                                                       out.ctypes.data_as(C.POINTER(C.c_double)))
-        _abi.check(code, self.handle)
+        n, arr, seed_arr, q = self._view_query("render_views", views, width, height, max_bounces, samples, exposure_value, seed,
+                                               seed_stride, seeds, sample_index_base, flags)
+        m = _marshal.pick(self.device, out)
+        # the ABI's difference: the device symbols also write float32 frames and say which behind the address
+        dtypes = (np.float64, np.float32) if m.suffix else np.float64
+        out = m.result(out, (n, int(height), int(width), 3), dtypes, "render_views", "out")
+        f32 = (1 if out.element_size() == 4 else 0,) if m.suffix else ()
+        seeded = ("_seeded", seed_arr) if seed_arr is not None else ("",)
+        self._call("rptgpu_render_views" + seeded[0], m, n, arr, C.byref(q), *seeded[1:], m.pointer(out, C.POINTER(C.c_double)),
+                   *f32)
         return out
 
-    _HIT_CHANNELS = ((_abi.RPT_HIT_T, "t", (), np.float64), (_abi.RPT_HIT_NORMAL, "normal", (3,), np.float64),
-                     (_abi.RPT_HIT_OBJECT, "object", (), np.int32), (_abi.RPT_HIT_POSITION, "position", (3,), np.float64),
-                     (_abi.RPT_HIT_ALBEDO, "albedo", (3,), np.float64))
+    def _view_query(self, who, views, width, height, max_bounces, samples, exposure_value, seed, seed_stride, seeds,
+                    sample_index_base, flags):
+        """the render_views* calls' common half -> (n, the lowered views, the lowered seeds or None, their RptViewQuery)"""
+        views = list(views)
+        arr = self._lower_views(views, who)
+        seed_arr = self._lower_seeds(seeds, len(views), seed_stride, who)
+        q = _abi.RptViewQuery()
+        q.struct_size = C.sizeof(_abi.RptViewQuery)
+        q.width, q.height, q.max_bounces, q.iterations = int(width), int(height), int(max_bounces), int(samples)
+        q.exposure_value, q.seed, q.seed_stride = float(exposure_value), int(seed), int(seed_stride)
+        q.sample_index_base, q.precision_mode, q.flags = int(sample_index_base), _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        return len(views), arr, seed_arr, q
 
     def first_hits(self, origins, dirs, channels=_abi.RPT_HIT_ALL, flags=0):
         """The first hit of each of the caller's rays (rptgpu_first_hits) -> a dict with one array per
@@ -747,14 +437,7 @@ class GpuScene:
         q = _abi.RptHitQuery()
         q.struct_size, q.channels = C.sizeof(_abi.RptHitQuery), int(channels)
         q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
-        a = _abi.RptHitArrays()
-        a.struct_size, a.reserved = C.sizeof(_abi.RptHitArrays), 0
-        named = [c for c in self._HIT_CHANNELS if q.channels & c[0]]
-        return self._ray_records("first_hits", origins, dirs, q, a, named)
-
-    _SURFACE_CHANNELS = ((_abi.RPT_SURFACE_T, "t", (), np.float64), (_abi.RPT_SURFACE_OBJECT, "object", (), np.int32),
-                         (_abi.RPT_SURFACE_CHILD, "child", (), np.int32), (_abi.RPT_SURFACE_PRIMITIVE, "primitive", (), np.int32),
-                         (_abi.RPT_SURFACE_BARYCENTRIC, "barycentric", (3,), np.float64))
+        return self._ray_records("first_hits", origins, dirs, q, _abi.RptHitArrays(), _marshal.HIT_CHANNELS)
 
     def hit_surface(self, origins, dirs, channels=_abi.RPT_SURFACE_ALL, flags=0):
         """The surface element behind the first hit of each of the caller's rays (rptgpu_hit_surface) -> a
@@ -770,82 +453,20 @@ class GpuScene:
         q = _abi.RptSurfaceQuery()
         q.struct_size, q.channels = C.sizeof(_abi.RptSurfaceQuery), int(channels)
         q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
-        a = _abi.RptSurfaceArrays()
-        a.struct_size, a.reserved = C.sizeof(_abi.RptSurfaceArrays), 0
-        named = [c for c in self._SURFACE_CHANNELS if q.channels & c[0]]
-        return self._ray_records("hit_surface", origins, dirs, q, a, named)
+        return self._ray_records("hit_surface", origins, dirs, q, _abi.RptSurfaceArrays(), _marshal.SURFACE_CHANNELS)
 
-    def _ray_records(self, what, origins, dirs, q, a, named):
-        """first_hits' and hit_surface's common half: the rays checked, one new array per named channel with its address
-        in `a`, then rptgpu_<what> — or, for torch tensors, rptgpu_<what>_device."""
-        if hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr"):
-            return self._ray_records_torch(what, origins, dirs, q, a, named)
-
-        def vectors(v, name):
-            v = np.asarray(v)
-            if v.dtype != np.float64 or v.ndim != 2 or v.shape[1] != 3:
-                raise ValueError("%s: %s must be an (n, 3) float64 array" % (what, name))
-            return np.ascontiguousarray(v)
-
-        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
-        n = len(o)
-        if len(d) != n:
-            raise ValueError("%s: %d origins for %d directions" % (what, n, len(d)))
-        out = {}
-        types = dict(type(a)._fields_)
-        for _, name, tail, dtype in named:
-            out[name] = np.empty((n,) + tail, dtype=dtype)
-            setattr(a, name, out[name].ctypes.data_as(types[name]))
+    def _ray_records(self, who, origins, dirs, q, a, table):
+        """first_hits' and hit_surface's common half: the rays checked, one new array per channel that q names with its
+        address in `a`, then rptgpu_<who>"""
+        a.struct_size, a.reserved = C.sizeof(a), 0
+        m = _marshal.pick(self.device, origins, dirs)
+        n, o, d = self._pair(m, origins, dirs, who, self._RAYS)  # the call's contract: (n, 3) float64 as they come
+        out = m.fill(a, _marshal.layout(table, q.channels, (n,)), who)
         PD = C.POINTER(C.c_double)
-        code = getattr(self.lib, "rptgpu_" + what)(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD), C.byref(q), C.byref(a))
-        _abi.check(code, self.handle)
+        self._call("rptgpu_" + who, m, n, m.pointer(o, PD), m.pointer(d, PD), C.byref(q), C.byref(a))
         return out
 
-    def _ray_records_torch(self, what, origins, dirs, q, a, named):
-        import torch
-        dev = torch.device("cuda", self.device)
-
-        def vectors(t, name):
-            if not isinstance(t, torch.Tensor) or t.device != dev:
-                raise ValueError("%s: %s must be a torch tensor on %s, like the other array" % (what, name, dev))
-            if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
-                raise ValueError("%s: %s must be an (n, 3) float64 tensor" % (what, name))
-            return t.contiguous()  # (no copy when it already is)
-
-        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError("%s: %d origins for %d directions" % (what, n, d.shape[0]))
-        out = {}
-        types = dict(type(a)._fields_)
-        for _, name, tail, dtype in named:
-            # (at least one element: an empty tensor has no address, and a named channel's pointer must not be NULL)
-            room = torch.empty((max(n, 1),) + tail, dtype=torch.int32 if dtype is np.int32 else torch.float64, device=dev)
-            out[name] = room[:n]
-            setattr(a, name, C.cast(C.c_void_p(room.data_ptr()), types[name]))
-        # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
-        # stream is waited for here)
-        current = torch.cuda.current_stream(dev)
-        stream = current.cuda_stream
-        if not stream:
-            current.synchronize()
-        code = getattr(self.lib, "rptgpu_%s_device" % what)(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                                                            C.byref(q), C.byref(a), C.c_void_p(stream or 0))
-        _abi.check(code, self.handle)
-        return out
-
-    # rptgpu_trace_vertices' channels: (bit, name, "path" | "vertex" | "ray", shape behind it, dtype)
-    _VERTEX_CHANNELS = ((_abi.RPT_VERTEX_LENGTH, "length", "path", (), np.uint32), (_abi.RPT_VERTEX_T, "t", "vertex", (), np.float64),
-                        (_abi.RPT_VERTEX_NORMAL, "normal", "vertex", (3,), np.float64),
-                        (_abi.RPT_VERTEX_OBJECT, "object", "vertex", (), np.int32),
-                        (_abi.RPT_VERTEX_POSITION, "position", "vertex", (3,), np.float64),
-                        (_abi.RPT_VERTEX_DIRECTION, "direction", "vertex", (3,), np.float64),
-                        (_abi.RPT_VERTEX_DRAW, "draw", "vertex", (), np.uint32),
-                        (_abi.RPT_VERTEX_RADIANCE, "radiance", "vertex", (3,), np.float64),
-                        (_abi.RPT_VERTEX_BSDF, "bsdf", "vertex", (3,), np.float64),
-                        (_abi.RPT_VERTEX_INV_PDF, "inv_pdf", "vertex", (), np.float64),
-                        (_abi.RPT_VERTEX_ABS_COS, "abs_cos", "vertex", (), np.float64),
-                        (_abi.RPT_VERTEX_RGB, "rgb", "ray", (3,), np.float64))
+    _VERTEX_CHANNELS = _marshal.VERTEX_CHANNELS  # (scripts read it under this name)
 
     def trace_vertices(self, origins, dirs, max_bounces, channels=_abi.RPT_VERTEX_ALL, streams=None, samples=1, seed=0x52505447,
                        sample_index_base=0, first_draw=0, exposure_value=0.0, flags=0):
@@ -864,72 +485,18 @@ class GpuScene:
         q.precision_mode, q.flags, q.channels, q.reserved = _abi.RPT_PRECISION_F64_STRICT, int(flags), int(channels), 0
         a = _abi.RptVertexArrays()
         a.struct_size, a.reserved = C.sizeof(_abi.RptVertexArrays), 0
-        named = [c for c in self._VERTEX_CHANNELS if q.channels & c[0]]
-        torch_in = hasattr(origins, "data_ptr") or hasattr(dirs, "data_ptr")
-        if torch_in:
-            import torch
-            dev = torch.device("cuda", self.device)
-
-            def vectors(t, what):
-                if not isinstance(t, torch.Tensor) or t.device != dev:
-                    raise ValueError("trace_vertices: %s must be a torch tensor on %s, like the other array" % (what, dev))
-                if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
-                    raise ValueError("trace_vertices: %s must be an (n, 3) float64 tensor" % what)
-                return t.contiguous()  # (no copy when it already is)
-        else:
-            def vectors(v, what):
-                v = np.asarray(v)
-                if v.dtype != np.float64 or v.ndim != 2 or v.shape[1] != 3:
-                    raise ValueError("trace_vertices: %s must be an (n, 3) float64 array" % what)
-                return np.ascontiguousarray(v)
-
-        o, d = vectors(origins, "origins"), vectors(dirs, "dirs")
-        n = int(o.shape[0])
-        if int(d.shape[0]) != n:
-            raise ValueError("trace_vertices: %d origins for %d directions" % (n, int(d.shape[0])))
-        ids = None
-        if streams is not None:
-            if torch_in:
-                if not isinstance(streams, torch.Tensor) or streams.device != dev:
-                    raise ValueError("trace_vertices: streams must be a torch tensor on %s, like the rays" % dev)
-                ids = streams.reshape(-1)
-                if ids.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)):
-                    ids = ids.to(torch.int64).to(torch.int32)  # the low 32 bits
-                ids = ids.contiguous()
-            else:
-                ids = np.ascontiguousarray(streams, dtype=np.uint32).reshape(-1)
-            if int(ids.shape[0]) != n:
-                raise ValueError("trace_vertices: %d stream ids for %d rays" % (int(ids.shape[0]), n))
+        m = _marshal.pick(self.device, origins, dirs)
+        # the call's contract: (n, 3) float64 rays as they come, but trace_rays' ids: any dtype and shape that flattens to n
+        n, o, d = self._pair(m, origins, dirs, "trace_vertices", self._RAYS)
+        ids = m.stream_ids(streams, n, "trace_vertices", "rays", strict=False)
         heads = {"path": (n, q.iterations), "vertex": (n, q.iterations, q.max_bounces + 1), "ray": (n,)}
-        types = dict(_abi.RptVertexArrays._fields_)
+        fields = [(name, heads[kind] + tail, dtype) for bit, name, kind, tail, dtype in self._VERTEX_CHANNELS if q.channels & bit]
         out = PathVertices(q.channels)
-        for _, name, kind, tail, dtype in named:
-            shape = heads[kind] + tail
-            if torch_in:
-                # (at least one element: an empty tensor has no address, and a named channel's pointer must not be NULL)
-                room = torch.empty(max(int(np.prod(shape)), 1), dtype=torch.float64 if dtype is np.float64 else torch.int32, device=dev)
-                setattr(out, name, room[:int(np.prod(shape))].reshape(shape))
-                setattr(a, name, C.cast(C.c_void_p(room.data_ptr()), types[name]))
-            else:
-                arr = np.empty(shape, dtype=dtype)
-                setattr(out, name, arr)
-                setattr(a, name, arr.ctypes.data_as(types[name]))
-        if torch_in:
-            # (the null-stream rule of _trace_rays_torch: a stream with a handle is the library's to wait for, torch's default
-            # stream is waited for here)
-            current = torch.cuda.current_stream(dev)
-            stream = current.cuda_stream
-            if not stream:
-                current.synchronize()
-            code = self.lib.rptgpu_trace_vertices_device(self.handle, n, C.c_void_p(o.data_ptr()), C.c_void_p(d.data_ptr()),
-                                                         C.c_void_p(ids.data_ptr()) if ids is not None else None, C.byref(q),
-                                                         C.byref(a), C.c_void_p(stream or 0))
-        else:
-            PD = C.POINTER(C.c_double)
-            code = self.lib.rptgpu_trace_vertices(self.handle, n, o.ctypes.data_as(PD), d.ctypes.data_as(PD),
-                                                  ids.ctypes.data_as(C.POINTER(C.c_uint32)) if ids is not None else None,
-                                                  C.byref(q), C.byref(a))
-        _abi.check(code, self.handle)
+        for name, array in m.fill(a, fields, "trace_vertices").items():
+            setattr(out, name, array)
+        PD = C.POINTER(C.c_double)
+        self._call("rptgpu_trace_vertices", m, n, m.pointer(o, PD), m.pointer(d, PD), m.pointer(ids, C.POINTER(C.c_uint32)),
+                   C.byref(q), C.byref(a))
         return out
 
     def render_views_aov(self, views, width, height, samples=1, seed=0x52505447, seed_stride=0, sample_index_base=0,
@@ -943,78 +510,16 @@ class GpuScene:
         out: None (new numpy arrays through host memory) or a dict of C-contiguous numpy arrays with exactly the keys
         above; or "torch" for new tensors on the handle's device, or a dict of contiguous torch tensors there, written
         where they lie (rptgpu_render_views_aov_device; `hits` as the 32 bits of an int32 tensor)."""
-        views = list(views)
-        n, width, height, channels = len(views), int(width), int(height), int(channels)
-        arr = self._lower_views(views, "render_views_aov")
-        seed_arr = self._lower_seeds(seeds, n, seed_stride, "render_views_aov")
-        q = _abi.RptViewQuery()
-        q.struct_size = C.sizeof(_abi.RptViewQuery)
-        q.width, q.height, q.max_bounces, q.iterations = width, height, 0, int(samples)
-        q.exposure_value, q.seed, q.seed_stride = 0.0, int(seed), int(seed_stride)
-        q.sample_index_base, q.precision_mode, q.flags = int(sample_index_base), _abi.RPT_PRECISION_F64_STRICT, int(flags)
-        layout = [("hits", (n, height, width), np.uint32)]
-        for bit, name, tail, dtype in ((_abi.RPT_AOV_DEPTH, "depth", (), np.float64),
-                                       (_abi.RPT_AOV_NORMAL, "normal", (3,), np.float64),
-                                       (_abi.RPT_AOV_ALBEDO, "albedo", (3,), np.float64),
-                                       (_abi.RPT_AOV_POSITION, "position", (3,), np.float64),
-                                       (_abi.RPT_AOV_OBJECT, "object", (), np.int32)):
-            if channels & bit:
-                layout.append((name, (n, height, width) + tail, dtype))
+        n, arr, seed_arr, q = self._view_query("render_views_aov", views, width, height, 0, samples, 0.0, seed, seed_stride, seeds,
+                                               sample_index_base, flags)
         b = _abi.RptAovBuffers()
-        b.struct_size, b.channels = C.sizeof(_abi.RptAovBuffers), channels
-        types = dict(_abi.RptAovBuffers._fields_)
-        host = isinstance(out, dict) and all(isinstance(v, np.ndarray) for v in out.values())
-        if out is None or host:
-            arrays = dict(out) if host else {name: np.zeros(shape, dtype=dtype) for name, shape, dtype in layout}
-            if set(arrays) != {name for name, _, _ in layout}:
-                raise ValueError("render_views_aov: out must have exactly the keys %s" % sorted(name for name, _, _ in layout))
-            for name, shape, dtype in layout:
-                v = arrays[name]
-                if not (v.dtype == dtype and v.shape == shape and v.flags.c_contiguous):
-                    raise ValueError("render_views_aov: out[%r] must be a C-contiguous %s %s array" % (name, shape, np.dtype(dtype)))
-            for name, v in arrays.items():
-                setattr(b, name, v.ctypes.data_as(types[name]))
-            if seed_arr is None:
-                code = self.lib.rptgpu_render_views_aov(self.handle, n, arr, C.byref(q), C.byref(b))
-            else:
-                code = self.lib.rptgpu_render_views_aov_seeded(self.handle, n, arr, C.byref(q), seed_arr, C.byref(b))
-            _abi.check(code, self.handle)
-            return arrays
-        import torch
-        dev = torch.device("cuda", self.device)
-        tdt = {np.uint32: torch.int32, np.int32: torch.int32, np.float64: torch.float64}  # (hits: its 32 bits in an int32 tensor)
-        if isinstance(out, str):
-            if out != "torch":
-                raise ValueError('render_views_aov: out must be None, "torch" or a dict of torch tensors')
-            # (at least one view's worth: an empty tensor has no address, and `hits` must not be NULL)
-            room = {name: torch.zeros((max(n, 1),) + shape[1:], dtype=tdt[dtype], device=dev) for name, shape, dtype in layout}
-            arrays = {name: t[:n] for name, t in room.items()}
-        else:
-            arrays = dict(out)
-            if set(arrays) != {name for name, _, _ in layout}:
-                raise ValueError("render_views_aov: out must have exactly the keys %s" % sorted(name for name, _, _ in layout))
-            for name, shape, dtype in layout:
-                t = arrays[name]
-                if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == tdt[dtype] and tuple(t.shape) == shape
-                        and t.is_contiguous()):
-                    raise ValueError("render_views_aov: out[%r] must be a contiguous %s %s tensor on %s"
-                                     % (name, shape, tdt[dtype], dev))
-        for name, t in (room if isinstance(out, str) else arrays).items():
-            setattr(b, name, C.cast(C.c_void_p(t.data_ptr()), types[name]))
-        current = torch.cuda.current_stream(dev)  # (the null-stream rule of _trace_rays_torch)
-        stream = current.cuda_stream
-        if not stream:
-            current.synchronize()
-        if seed_arr is None:
-            code = self.lib.rptgpu_render_views_aov_device(self.handle, n, arr, C.byref(q), C.byref(b), C.c_void_p(stream or 0))
-        else:
-            code = self.lib.rptgpu_render_views_aov_seeded_device(self.handle, n, arr, C.byref(q), seed_arr, C.byref(b),
-                                                                  C.c_void_p(stream or 0))
-        _abi.check(code, self.handle)
+        b.struct_size, b.channels = C.sizeof(_abi.RptAovBuffers), int(channels)
+        m, out = _marshal.pick_out(self.device, out, "render_views_aov")
+        # the call's contract: new arrays are zero-initialised
+        arrays = m.fill(b, _marshal.aov_layout(b.channels, (n, int(height), int(width))), "render_views_aov", out, zero=True)
+        seeded = ("_seeded", seed_arr) if seed_arr is not None else ("",)
+        self._call("rptgpu_render_views_aov" + seeded[0], m, n, arr, C.byref(q), *seeded[1:], C.byref(b))
         return arrays
-
-    _DENOISED_OUTPUTS = (("denoised", (3,), np.float64), ("rgb8", (3,), np.uint8), ("mean", (3,), np.float64),
-                         ("variance", (), np.float64))
 
     def render_views_denoised(self, views, width, height, max_bounces, samples, batches, seed=0x52505447, seed_stride=0,
                               seeds=None, sample_index_base=0, feature_samples=4, feature_sample_index_base=0, levels=3,
@@ -1030,75 +535,28 @@ class GpuScene:
         out: None (new numpy arrays through host memory) or a dict of C-contiguous numpy arrays with exactly the keys of
         `want`; or "torch" for new tensors on the handle's device, or a dict of contiguous torch tensors there, written where
         they lie (rptgpu_render_views_denoised_device)."""
-        views = list(views)
-        n, width, height = len(views), int(width), int(height)
-        arr = self._lower_views(views, "render_views_denoised")
-        seed_arr = self._lower_seeds(seeds, n, seed_stride, "render_views_denoised")
+        n, arr, seed_arr, q = self._view_query("render_views_denoised", views, width, height, max_bounces, samples, exposure_value,
+                                               seed, seed_stride, seeds, sample_index_base, flags)
         want = (want,) if isinstance(want, str) else tuple(want)
-        known = [name for name, _, _ in self._DENOISED_OUTPUTS]
+        known = [name for name, _, _ in _marshal.DENOISED_OUTPUTS]
         if not want or len(set(want)) != len(want) or any(w not in known for w in want):
             raise ValueError("render_views_denoised: want must name each of %s at most once, and one at least" % (known,))
         if "denoised" not in want and "rgb8" not in want:
             raise ValueError("render_views_denoised: want must name `denoised` or `rgb8`")
-        q = _abi.RptViewQuery()
-        q.struct_size = C.sizeof(_abi.RptViewQuery)
-        q.width, q.height, q.max_bounces, q.iterations = width, height, int(max_bounces), int(samples)
-        q.exposure_value, q.seed, q.seed_stride = float(exposure_value), int(seed), int(seed_stride)
-        q.sample_index_base, q.precision_mode, q.flags = int(sample_index_base), _abi.RPT_PRECISION_F64_STRICT, int(flags)
         d = _abi.RptViewDenoise()
         d.struct_size, d.batches, d.feature_iterations = C.sizeof(_abi.RptViewDenoise), int(batches), int(feature_samples)
         d.feature_sample_index_base = int(feature_sample_index_base)
         d.filter.struct_size, d.filter.levels = C.sizeof(_abi.RptDenoise), int(levels)
         d.filter.sigma_color, d.filter.sigma_normal = float(sigma_color), float(sigma_normal)
         d.filter.sigma_depth, d.filter.sigma_albedo = float(sigma_depth), float(sigma_albedo)
-        layout = [(name, (n, height, width) + tail, dtype) for name, tail, dtype in self._DENOISED_OUTPUTS if name in want]
         o = _abi.RptViewDenoiseOut()
         o.struct_size = C.sizeof(_abi.RptViewDenoiseOut)
-        types = dict(_abi.RptViewDenoiseOut._fields_)
-        host = isinstance(out, dict) and all(isinstance(v, np.ndarray) for v in out.values())
-        if out is None or host:
-            # (at least one view's worth: an empty array's address may be NULL, and a wanted output's pointer must not be)
-            room = None if host else {name: np.empty((max(n, 1),) + shape[1:], dtype=dtype) for name, shape, dtype in layout}
-            arrays = dict(out) if host else {name: a[:n] for name, a in room.items()}
-            if set(arrays) != set(want):
-                raise ValueError("render_views_denoised: out must have exactly the keys %s" % sorted(want))
-            for name, shape, dtype in layout:
-                v = arrays[name]
-                if not (v.dtype == dtype and v.shape == shape and v.flags.c_contiguous):
-                    raise ValueError("render_views_denoised: out[%r] must be a C-contiguous %s %s array"
-                                     % (name, shape, np.dtype(dtype)))
-            for name, v in (arrays if host else room).items():
-                setattr(o, name, v.ctypes.data_as(types[name]))
-            code = self.lib.rptgpu_render_views_denoised(self.handle, n, arr, C.byref(q), seed_arr, C.byref(d), C.byref(o))
-            _abi.check(code, self.handle)
-            return arrays
-        import torch
-        dev = torch.device("cuda", self.device)
-        tdt = {np.uint8: torch.uint8, np.float64: torch.float64}
-        if isinstance(out, str):
-            if out != "torch":
-                raise ValueError('render_views_denoised: out must be None, "torch" or a dict of arrays or tensors')
-            room = {name: torch.empty((max(n, 1),) + shape[1:], dtype=tdt[dtype], device=dev) for name, shape, dtype in layout}
-            arrays = {name: t[:n] for name, t in room.items()}
-        else:
-            arrays = room = dict(out)
-            if set(arrays) != set(want):
-                raise ValueError("render_views_denoised: out must have exactly the keys %s" % sorted(want))
-            for name, shape, dtype in layout:
-                t = arrays[name]
-                if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == tdt[dtype] and tuple(t.shape) == shape
-                        and t.is_contiguous()):
-                    raise ValueError("render_views_denoised: out[%r] must be a contiguous %s %s tensor on %s"
-                                     % (name, shape, tdt[dtype], dev))
-        for name, t in room.items():
-            setattr(o, name, C.cast(C.c_void_p(t.data_ptr()), types[name]))
-        current = torch.cuda.current_stream(dev)  # (the null-stream rule of _trace_rays_torch)
-        stream = current.cuda_stream
-        if not stream:
-            current.synchronize()
-        code = self.lib.rptgpu_render_views_denoised_device(self.handle, n, arr, C.byref(q), seed_arr, C.byref(d), C.byref(o),
-                                                            C.c_void_p(stream or 0))
-        _abi.check(code, self.handle)
+        m, out = _marshal.pick_out(self.device, out, "render_views_denoised")
+        head = (n, int(height), int(width))
+        fields = [(name, head + tail, dtype) for name, tail, dtype in _marshal.DENOISED_OUTPUTS if name in want]
+        arrays = m.fill(o, fields, "render_views_denoised", out)
+        # (seeds or NULL: one symbol)
+        self._call("rptgpu_render_views_denoised", m, n, arr, C.byref(q), seed_arr, C.byref(d), C.byref(o))
         return arrays
 
     @staticmethod
@@ -1138,21 +596,10 @@ class GpuScene:
         always, and per channel of `channels` (RPT_AOV_*) the f64 SUMS over the hits of params.iterations camera rays per
         pixel — `depth` (H, W), `normal` / `albedo` / `position` (H, W, 3) — and `object` (H, W) int32, the object the
         call's first sample hit (-1: none).  A mean is sum / hits."""
-        channels = int(channels)
-        h, w = params.height, params.width
-        arrays = {"hits": np.zeros((h, w), dtype=np.uint32)}
-        for bit, name, shape, dtype in ((_abi.RPT_AOV_DEPTH, "depth", (h, w), np.float64),
-                                        (_abi.RPT_AOV_NORMAL, "normal", (h, w, 3), np.float64),
-                                        (_abi.RPT_AOV_ALBEDO, "albedo", (h, w, 3), np.float64),
-                                        (_abi.RPT_AOV_POSITION, "position", (h, w, 3), np.float64),
-                                        (_abi.RPT_AOV_OBJECT, "object", (h, w), np.int32)):
-            if channels & bit:
-                arrays[name] = np.zeros(shape, dtype=dtype)
         b = _abi.RptAovBuffers()
-        b.struct_size, b.channels = C.sizeof(_abi.RptAovBuffers), channels
-        for name, a in arrays.items():
-            setattr(b, name, a.ctypes.data_as(dict(_abi.RptAovBuffers._fields_)[name]))
-        cam = camera.lower() if hasattr(camera, "lower") else camera
+        b.struct_size, b.channels = C.sizeof(_abi.RptAovBuffers), int(channels)
+        arrays = _marshal.HOST.fill(b, _marshal.aov_layout(b.channels, (params.height, params.width)), "render_aov", zero=True)
+        cam = _lower_camera(camera)
         _abi.check(self.lib.rptgpu_render_aov(self.handle, C.byref(cam), C.byref(params), C.byref(b)), self.handle)
         return arrays
 
@@ -1230,7 +677,7 @@ class DeviceBuffer:
 
     def sample(self, camera, params):
         """Renderer::sample + Buffer::add_samples on the device."""
-        cam = camera.lower() if hasattr(camera, "lower") else camera
+        cam = _lower_camera(camera)
         _abi.check(self.gpu.lib.rptgpu_buffer_sample(self.handle, C.byref(cam), C.byref(params)), self.gpu.handle)
 
     def image(self):
@@ -1252,7 +699,7 @@ class DeviceBuffer:
     def sample_adaptive(self, camera, params, min_batches=4, abs_tol=0.0, rel_tol=0.01):
         """One batch for the pixels still active, then the stopping rule -> the number of pixels active afterwards.  Once
         a pixel has retired, sample() is refused."""
-        cam = camera.lower() if hasattr(camera, "lower") else camera
+        cam = _lower_camera(camera)
         a = _abi.RptAdaptive(C.sizeof(_abi.RptAdaptive), int(min_batches), float(abs_tol), float(rel_tol))
         n = C.c_uint32(0)
         _abi.check(self.gpu.lib.rptgpu_buffer_sample_adaptive(self.handle, C.byref(cam), C.byref(params), C.byref(a),
@@ -1278,19 +725,14 @@ class DeviceBuffer:
         """The first-hit features of (camera, params) — GpuScene.render_aov's depth, normal, albedo and position sums and
         `hits` — computed into device arrays the buffer keeps (nothing comes to the host); they guide denoise().  A later
         call replaces them."""
-        cam = camera.lower() if hasattr(camera, "lower") else camera
+        cam = _lower_camera(camera)
         _abi.check(self.gpu.lib.rptgpu_buffer_features(self.handle, C.byref(cam), C.byref(params)), self.gpu.handle)
 
     def feature_sums(self):
         """The held features read back: GpuScene.render_aov's dict without `object`."""
-        h, w = self.height, self.width
-        arrays = {"hits": np.zeros((h, w), dtype=np.uint32), "depth": np.zeros((h, w)), "normal": np.zeros((h, w, 3)),
-                  "albedo": np.zeros((h, w, 3)), "position": np.zeros((h, w, 3))}
         b = _abi.RptAovBuffers()
-        b.struct_size = C.sizeof(_abi.RptAovBuffers)
-        b.channels = _abi.RPT_AOV_DEPTH | _abi.RPT_AOV_NORMAL | _abi.RPT_AOV_ALBEDO | _abi.RPT_AOV_POSITION
-        for name, a in arrays.items():
-            setattr(b, name, a.ctypes.data_as(dict(_abi.RptAovBuffers._fields_)[name]))
+        b.struct_size, b.channels = C.sizeof(_abi.RptAovBuffers), _abi.RPT_AOV_ALL & ~_abi.RPT_AOV_OBJECT
+        arrays = _marshal.HOST.fill(b, _marshal.aov_layout(b.channels, (self.height, self.width)), "feature_sums", zero=True)
         _abi.check(self.gpu.lib.rptgpu_buffer_feature_sums(self.handle, C.byref(b)), self.gpu.handle)
         return arrays
 

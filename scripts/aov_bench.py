@@ -34,14 +34,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from rpt_amd import GpuScene, _abi, make_params, scenes  # noqa: E402
+from rpt_amd import GpuScene, _abi, _marshal, make_params, scenes  # noqa: E402
 
 CONFIGS = {"cornell": 16, "wine_glass": 4}  # scene: spp
 SEED = 0x52505447
 REPEATS = 3
 CHANNEL_SETS = {"aov_all": _abi.RPT_AOV_ALL, "aov_dn": _abi.RPT_AOV_DEPTH | _abi.RPT_AOV_NORMAL}
-CHANNEL_BYTES = {_abi.RPT_AOV_DEPTH: 8, _abi.RPT_AOV_NORMAL: 24, _abi.RPT_AOV_ALBEDO: 24, _abi.RPT_AOV_POSITION: 24,
-                 _abi.RPT_AOV_OBJECT: 4}
+CHANNEL_BYTES = {bit: np.dtype(dtype).itemsize * (tail + (1,))[0] for bit, _, tail, dtype in _marshal.AOV_CHANNELS}
 
 
 def bytes_per_pixel(channels):
