@@ -874,6 +874,50 @@ class Renderer {
     check(rptgpu_hit_surface(handle_, n, origins.data(), dirs.data(), &q, &a));
     return r;
   }
+  // addition: a lightmap baked on the device (rptgpu_bake_lightmap, include/rpt_gpu_lightmap.h): the triangles' uv charts
+  // rasterised into a map_width x map_height map — the texel's centre decides, the lowest triangle index owns it —, and at every
+  // owned texel bake_probes' irradiance and / or bake_ao's occlusion for the renderer's num_samples, max_bounces and seed, from
+  // stream stream_base + y * map_width + x, the gutters filled by `dilate` rounds.  positions: world space, xyz per vertex,
+  // three vertices per triangle; normals: the same, or empty (flat: Triangle::from_vertices'); uvs: (u, v) per vertex.  -> one
+  // vector per channel of `channels` (RPT_LIGHTMAP_*), row-major from v = 0, the others empty; owner -1 and +0.0 where no
+  // triangle covers a texel.  `position` is the gather point, lifted by offset * normal.
+  struct Lightmap {
+    std::vector<double> irradiance, ao, barycentric, position, normal;
+    std::vector<int32_t> owner;
+  };
+  Lightmap bake_lightmap(const std::vector<double>& positions, const std::vector<double>& normals, const std::vector<double>& uvs,
+                         uint32_t map_width, uint32_t map_height, uint32_t channels = RPT_LIGHTMAP_IRRADIANCE | RPT_LIGHTMAP_OWNER,
+                         double offset = 0.0, uint32_t dilate = 0, double max_distance = std::numeric_limits<double>::infinity(),
+                         uint32_t stream_base = 0, uint64_t sample_index_base = 0, uint32_t flags = 0) {
+    ensure_scene();
+    const size_t n = positions.size() / 9;
+    if (positions.size() != 9 * n || (!normals.empty() && normals.size() != 9 * n) || uvs.size() != 6 * n)
+      throw std::invalid_argument("bake_lightmap: positions and normals hold three xyz per triangle, uvs three (u, v)");
+    RptLightmapQuery q{};
+    q.struct_size = sizeof(RptLightmapQuery); q.channels = channels; q.width = map_width; q.height = map_height;
+    q.samples = num_samples_; q.max_bounces = max_bounces_; q.dilate = dilate; q.stream_base = stream_base; q.seed = seed_;
+    q.sample_index_base = sample_index_base; q.offset = offset; q.max_distance = max_distance; q.flags = flags;
+    const size_t texels = (size_t)map_width * map_height;
+    Lightmap r;
+    if (!texels) { // (an empty vector has no address; the library refuses an empty map by name)
+      RptLightmapArrays none{};
+      none.struct_size = sizeof(RptLightmapArrays);
+      check(rptgpu_bake_lightmap(handle_, n, positions.data(), normals.empty() ? nullptr : normals.data(), uvs.data(), &q, &none));
+      return r;
+    }
+    if (channels & RPT_LIGHTMAP_IRRADIANCE) r.irradiance.resize(3 * texels);
+    if (channels & RPT_LIGHTMAP_AO) r.ao.resize(texels);
+    if (channels & RPT_LIGHTMAP_OWNER) r.owner.resize(texels);
+    if (channels & RPT_LIGHTMAP_BARYCENTRIC) r.barycentric.resize(3 * texels);
+    if (channels & RPT_LIGHTMAP_POSITION) r.position.resize(3 * texels);
+    if (channels & RPT_LIGHTMAP_NORMAL) r.normal.resize(3 * texels);
+    RptLightmapArrays a{};
+    a.struct_size = sizeof(RptLightmapArrays);
+    a.irradiance = r.irradiance.data(); a.ao = r.ao.data(); a.owner = r.owner.data(); a.barycentric = r.barycentric.data();
+    a.position = r.position.data(); a.normal = r.normal.data();
+    check(rptgpu_bake_lightmap(handle_, n, positions.data(), normals.empty() ? nullptr : normals.data(), uvs.data(), &q, &a));
+    return r;
+  }
   // addition: the vertices of the paths trace_rays runs (rptgpu_trace_vertices, include/rpt_gpu_vertices.h): where each of a
   // ray's num_samples paths bounced, what it picked up there and with which factors it went on.  With S = num_samples and
   // V = max_bounces + 1: length [n][S]; per vertex [n][S][V] (x 3 for the vectors); rgb [n][3] = trace_rays' result.  Entries

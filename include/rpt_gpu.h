@@ -1062,6 +1062,8 @@ const char* rptgpu_kernel_name(int k);
 #include "rpt_gpu_vertices_persistent.h"
 /* ---- ... and the triangle, group child and barycentrics behind a ray's first hit ---- */
 #include "rpt_gpu_hit_surface.h"
+/* ---- ... and a lightmap baked from a mesh's UV charts: irradiance and ambient occlusion per texel ---- */
+#include "rpt_gpu_lightmap.h"
 
 #ifdef __cplusplus
 }

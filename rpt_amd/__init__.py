@@ -14,7 +14,8 @@ GpuScene.occluded answers "is anything between here and there?" for the caller's
 GpuScene.bake_ao bakes ambient occlusion (and bent normals) from directions drawn on the device; GpuScene.trace_vertices gives
 the vertices of the paths trace_rays runs — where each bounced, what it picked up there and with what it went on;
 GpuScene.hit_surface names the triangle, the barycentrics and the group's child behind a ray's first hit, and
-surface.interpolate carries a per-vertex attribute there.
+surface.interpolate carries a per-vertex attribute there; GpuScene.bake_lightmap rasterises a mesh's UV charts into a map and
+gathers irradiance and ambient occlusion at the covered texels, gutters filled (lightmap.load_obj_texcoords reads the uvs).
 """
 from . import glm  # noqa: F401
 from ._abi import RptGpuError  # noqa: F401
@@ -27,6 +28,8 @@ from ._abi import (RPT_VERTEX_ABS_COS, RPT_VERTEX_ALL, RPT_VERTEX_BSDF, RPT_VERT
                    RPT_VERTEX_RADIANCE, RPT_VERTEX_RGB, RPT_VERTEX_T)
 from ._abi import (RPT_SURFACE_ALL, RPT_SURFACE_BARYCENTRIC, RPT_SURFACE_CHILD, RPT_SURFACE_OBJECT,  # noqa: F401
                    RPT_SURFACE_PRIMITIVE, RPT_SURFACE_T)
+from ._abi import (RPT_LIGHTMAP_ALL, RPT_LIGHTMAP_AO, RPT_LIGHTMAP_BARYCENTRIC, RPT_LIGHTMAP_IRRADIANCE,  # noqa: F401
+                   RPT_LIGHTMAP_NORMAL, RPT_LIGHTMAP_OWNER, RPT_LIGHTMAP_POSITION)
 from .buffer import Buffer, Filter  # noqa: F401
 from .camera import Camera, View  # noqa: F401
 from .color import color_bytes, hex_color  # noqa: F401
@@ -42,5 +45,6 @@ from .renderer import Renderer  # noqa: F401
 from .scene import Scene  # noqa: F401
 from . import scenes  # noqa: F401
 from . import surface  # noqa: F401
+from . import lightmap  # noqa: F401
 from .shape import (Cube, KdTree, Mesh, MonomialSurface, Plane, Shape, Sphere, Transformed, Triangle,  # noqa: F401
                     cube, monomial_surface, plane, polygon, sphere, transform_records)

@@ -55,6 +55,10 @@ RPT_VERTEX_ALL = 4095
 # include/rpt_gpu_hit_surface.h: RptSurfaceQuery.channels of hit_surface (hit_surface_supported())
 RPT_SURFACE_T, RPT_SURFACE_OBJECT, RPT_SURFACE_CHILD, RPT_SURFACE_PRIMITIVE, RPT_SURFACE_BARYCENTRIC = 1, 2, 4, 8, 16
 RPT_SURFACE_ALL = 31
+# include/rpt_gpu_lightmap.h: RptLightmapQuery.channels of bake_lightmap (lightmap_supported())
+(RPT_LIGHTMAP_IRRADIANCE, RPT_LIGHTMAP_AO, RPT_LIGHTMAP_OWNER, RPT_LIGHTMAP_BARYCENTRIC, RPT_LIGHTMAP_POSITION,
+ RPT_LIGHTMAP_NORMAL) = 1, 2, 4, 8, 16, 32
+RPT_LIGHTMAP_ALL = 63
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -263,6 +267,21 @@ class RptSurfaceArrays(C.Structure):
                 ("child", C.POINTER(C.c_int32)), ("primitive", C.POINTER(C.c_int32)), ("barycentric", C.POINTER(f64))]
 
 
+class RptLightmapQuery(C.Structure):
+    """include/rpt_gpu_lightmap.h RptLightmapQuery (rptgpu_bake_lightmap's parameters)."""
+    _fields_ = [("struct_size", C.c_uint32), ("channels", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("samples", C.c_uint32), ("max_bounces", C.c_uint32), ("dilate", C.c_uint32), ("stream_base", C.c_uint32),
+                ("seed", C.c_uint64), ("sample_index_base", C.c_uint64), ("offset", f64), ("max_distance", f64),
+                ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RptLightmapArrays(C.Structure):
+    """include/rpt_gpu_lightmap.h RptLightmapArrays (rptgpu_bake_lightmap's output arrays, host or device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("irradiance", C.POINTER(f64)), ("ao", C.POINTER(f64)),
+                ("owner", C.POINTER(C.c_int32)), ("barycentric", C.POINTER(f64)), ("position", C.POINTER(f64)),
+                ("normal", C.POINTER(f64))]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -390,6 +409,13 @@ HIT_SURFACE_SYMBOLS = [
     ("rptgpu_hit_surface_device", C.c_int,
      [_VP, C.c_uint64, _VP, _VP, C.POINTER(RptSurfaceQuery), C.POINTER(RptSurfaceArrays), _VP]),
 ]
+# ... and every symbol include/rpt_gpu_lightmap.h declares, optional in the same way (lightmap_supported())
+LIGHTMAP_SYMBOLS = [
+    ("rptgpu_bake_lightmap", C.c_int,
+     [_VP, C.c_uint64, _PD, _PD, _PD, C.POINTER(RptLightmapQuery), C.POINTER(RptLightmapArrays)]),
+    ("rptgpu_bake_lightmap_device", C.c_int,
+     [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptLightmapQuery), C.POINTER(RptLightmapArrays), _VP]),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -418,11 +444,11 @@ def load_library(path=None):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
-    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS:
+    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS + LIGHTMAP_SYMBOLS:
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported() say no)
+            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported(), lightmap_supported() say no)
         fn.restype = restype
         fn.argtypes = argtypes
     if lib.rptgpu_abi_version() != ABI_VERSION:
@@ -473,6 +499,13 @@ def hit_surface_supported(lib=None):
     caller does with dlsym: a library without them is still ABI 7."""
     lib = lib or load_library()
     return all(hasattr(lib, name) for name, _, _ in HIT_SURFACE_SYMBOLS)
+
+
+def lightmap_supported(lib=None):
+    """Does the library export rptgpu_bake_lightmap[_device] (include/rpt_gpu_lightmap.h)?  Detected by symbol, as a C
+    caller does with dlsym: a library without them is still ABI 7."""
+    lib = lib or load_library()
+    return all(hasattr(lib, name) for name, _, _ in LIGHTMAP_SYMBOLS)
 
 
 def check(code, handle=None):

@@ -15,6 +15,9 @@ HIT_CHANNELS = ((_abi.RPT_HIT_T, "t", (), np.float64), (_abi.RPT_HIT_NORMAL, "no
 SURFACE_CHANNELS = ((_abi.RPT_SURFACE_T, "t", (), np.float64), (_abi.RPT_SURFACE_OBJECT, "object", (), np.int32),
                     (_abi.RPT_SURFACE_CHILD, "child", (), np.int32), (_abi.RPT_SURFACE_PRIMITIVE, "primitive", (), np.int32),
                     (_abi.RPT_SURFACE_BARYCENTRIC, "barycentric", (3,), np.float64))
+LIGHTMAP_CHANNELS = ((_abi.RPT_LIGHTMAP_IRRADIANCE, "irradiance", (3,), np.float64), (_abi.RPT_LIGHTMAP_AO, "ao", (), np.float64),
+                     (_abi.RPT_LIGHTMAP_OWNER, "owner", (), np.int32), (_abi.RPT_LIGHTMAP_BARYCENTRIC, "barycentric", (3,), np.float64),
+                     (_abi.RPT_LIGHTMAP_POSITION, "position", (3,), np.float64), (_abi.RPT_LIGHTMAP_NORMAL, "normal", (3,), np.float64))
 # rptgpu_trace_vertices': (bit, name, "path" | "vertex" | "ray", shape behind it, dtype)
 VERTEX_CHANNELS = ((_abi.RPT_VERTEX_LENGTH, "length", "path", (), np.uint32), (_abi.RPT_VERTEX_T, "t", "vertex", (), np.float64),
                    (_abi.RPT_VERTEX_NORMAL, "normal", "vertex", (3,), np.float64),
@@ -62,8 +65,8 @@ class _Backend:
         return owner[:count].reshape(shape), owner
 
     def fill(self, struct, fields, who, out=None, zero=False):
-        """The pointers of an output struct (RptHitArrays, RptSurfaceArrays, RptVertexArrays, RptAovBuffers,
-        RptViewDenoiseOut) from `fields`, [(name, shape, dtype)] -> {name: array}: new arrays with room behind them, or
+        """The pointers of an output struct (RptHitArrays, RptSurfaceArrays, RptLightmapArrays, RptVertexArrays,
+        RptAovBuffers, RptViewDenoiseOut) from `fields`, [(name, shape, dtype)] -> {name: array}: new arrays with room behind them, or
         the caller's `out`, a dict with exactly these names, checked and written where they lie."""
         if out is None:
             rooms = {name: self.room(shape, dtype, zero) for name, shape, dtype in fields}
@@ -116,6 +119,13 @@ class _Host(_Backend):
             raise TypeError("%s: %s must be float64, not %s" % (who, what, a.dtype))
         if a.ndim != 2 or a.shape[1] != width:
             raise ValueError("%s: %s must have shape (n, %d), not %s" % (who, what, width, tuple(a.shape)))
+        return np.ascontiguousarray(a)
+
+    def records(self, a, tail, who, what):
+        """bake_lightmap's (n,) + tail float64 records -> a contiguous array of that shape"""
+        a = np.asarray(a)
+        if a.dtype != np.float64 or a.ndim != 1 + len(tail) or tuple(a.shape[1:]) != tuple(tail):
+            raise ValueError("%s: %s must be an (n, %s) float64 array" % (who, what, ", ".join(str(t) for t in tail)))
         return np.ascontiguousarray(a)
 
     def new(self, count, dtype, zero):
@@ -197,6 +207,13 @@ class _Device(_Backend):
         if not a.is_contiguous():
             raise ValueError("%s: the tensor must be contiguous" % who)
         return a
+
+    def records(self, a, tail, who, what):
+        """bake_lightmap's (n,) + tail float64 records -> a contiguous tensor of that shape (no copy when it already is)"""
+        self.here(a, who, what)
+        if a.dtype != self.torch.float64 or a.dim() != 1 + len(tail) or tuple(a.shape[1:]) != tuple(tail):
+            raise ValueError("%s: %s must be an (n, %s) float64 tensor" % (who, what, ", ".join(str(t) for t in tail)))
+        return a.contiguous()
 
     def new(self, count, dtype, zero):
         return (self.torch.zeros if zero else self.torch.empty)(count, dtype=self.dtypes[np.dtype(dtype)], device=self.dev)

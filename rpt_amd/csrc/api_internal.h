@@ -32,6 +32,10 @@
 //                    drivers then also carry every path's vertices into the caller's arrays
 //   api_surface.cpp  rptgpu_hit_surface[_device]: api_hits.cpp's first-hit query per piece (plan_hit_pieces, hit_piece), then
 //                    rpt_hit_surface, the resolve walk that names the triangle, the barycentrics and the group's child
+//   api_lightmap.cpp rptgpu_bake_lightmap[_device]: the triangles' uv charts rasterised into an owner map, then per piece of
+//                    texels the interpolation and compaction, the probe and AO calls' own device work over the compacted
+//                    points (enqueue_probes, enqueue_ao), the scatter; the dilation over the whole map (the kernels:
+//                    kernels_lightmap.hip; the sizes: lightmap_plan.h)
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -64,6 +68,8 @@
 #include "kernels.h"
 #include "render_plan.h"
 #include "surface_plan.h"
+#include "lightmap_plan.h"
+#include "lightmap.h"
 
 namespace rptapi {
 
@@ -200,6 +206,12 @@ struct rptgpu_scene {
   DevBuf<double> surface_out;          // rptgpu_hit_surface: the handle's pair of T and OBJECT and a piece of a host caller's records (api_surface.cpp, surface_plan.h layout)
   DevBuf<double> surf_defer, surf_frame; // ... and rpt_hit_surface's columns (surface_plan.h columns), as high as gen_levels / gen_frames
   rptsurface::Columns surf_cols{};
+  // rptgpu_bake_lightmap (api_lightmap.cpp): the owner map of the call, the list of triangles with large boxes, a piece's scan
+  // with its scratch, its compacted arrays (lightmap_plan.h compact), the dilation's second copy and its filled flags, and
+  // a host caller's triangles and named channels, staged whole
+  DevBuf<uint32_t> lm_owner, lm_large, lm_scan;
+  DevBuf<uint8_t> lm_scan_tmp, lm_filled;
+  DevBuf<double> lm_compact, lm_pong, lm_tris, lm_stage;
   DevBuf<double> vertices_out;         // rptgpu_trace_vertices: a piece of a host caller's records, the named channels back to back (api_vertices.cpp)
   DevBuf<rptdev::View> view_recs;     // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<uint64_t> view_seeds;         // ... their seeds, when the views have seeds of their own,
@@ -467,6 +479,13 @@ void hit_piece(rptgpu_scene* h, const KernelTable* kt, const HitPieces& hp, cons
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
 const char* bad_probe_query(const RptProbeQuery* q);
+// the device work of rptgpu_bake_probes (api_probes.cpp) and rptgpu_bake_ao (api_occlusion.cpp) behind their checks, n > 0:
+// the bodies of their device_calls -> drain_call's read_overflow.  rptgpu_bake_lightmap runs both inside its own device_call
+// over its compacted texels (on_device, with stream ids and outputs given: they then stage nothing)
+bool enqueue_probes(rptgpu_scene* h, uint64_t n, const double* positions, const double* normals, const uint32_t* streams,
+                    const RptProbeQuery* q, double* out, bool on_device);
+bool enqueue_ao(rptgpu_scene* h, uint64_t n, const double* positions, const double* normals, const uint32_t* streams,
+                const RptAoQuery* q, double* out_ao, double* out_bent, bool on_device);
 // the pass planner's input for a call over npix pixels or rays: what its passes share, and the device's state right now
 rptplan::PassInput pass_input(rptgpu_scene* h, uint32_t npix, uint32_t iterations);
 void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in);

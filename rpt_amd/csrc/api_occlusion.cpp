@@ -119,6 +119,58 @@ int occluded(rptgpu_scene* h, uint64_t n, const double* origins, const double* d
   });
 }
 
+} // namespace
+
+// rptgpu_bake_ao's device work, behind its checks (n > 0): the body of its device_call, which rptgpu_bake_lightmap runs
+// inside its own (api_lightmap.cpp) -> drain_call's read_overflow
+bool enqueue_ao(rptgpu_scene* h, uint64_t n, const double* positions, const double* normals, const uint32_t* streams,
+                const RptAoQuery* q, double* out_ao, double* out_bent, bool on_device) {
+  hipStream_t st = h->stream;
+  Occlusion oc(h, q->precision_mode, q->flags);
+  const uint32_t S = q->samples;
+  const uint64_t piece = rptplan::ao_piece(n, oc.asked, S, oc.pass_target);
+  // (a pass of m <= piece points holds m * ao_pass_samples(m, ...) <= min(m * S, the pass bound) slots)
+  const rptdev::PathState ps = oc.workspace(std::min<uint64_t>(piece * S, rptplan::occlusion_pass_max(oc.pass_target)));
+  h->accum.alloc(4 * piece); // per point: the count of visible directions and their sum, [4][points] (rpt_ao_fold)
+  if (!on_device) {
+    h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece); h->rays_out.alloc(4 * piece);
+    if (streams) h->ray_ids.alloc(piece);
+  }
+  for (uint64_t base = 0; base < n; base += piece) {
+    const uint64_t m = std::min(piece, n - base);
+    const double *d_pos = positions + 3 * base, *d_nrm = normals + 3 * base;
+    const uint32_t* d_ids = streams ? streams + base : nullptr;
+    double *d_ao = out_ao + base, *d_bent = out_bent ? out_bent + 3 * base : nullptr;
+    if (!on_device) {
+      HIP_TRY(hipMemcpyAsync(h->rays_o.p, d_pos, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_nrm, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
+      if (streams) HIP_TRY(hipMemcpyAsync(h->ray_ids.p, d_ids, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      d_pos = h->rays_o.p; d_nrm = h->rays_d.p; d_ids = streams ? h->ray_ids.p : nullptr;
+      d_ao = h->rays_out.p; d_bent = out_bent ? h->rays_out.p + piece : nullptr;
+    }
+    rptdev::Frame fr{};
+    fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.seed = q->seed; fr.accum = h->accum.p;
+    for (uint32_t s0 = 0; s0 < S;) { // the piece's passes: s_pass directions of every point
+      const uint32_t s_pass = rptplan::ao_pass_samples(m, S - s0, oc.pass_target);
+      const uint32_t n_slots = (uint32_t)(m * s_pass);
+      fr.sample_base = q->sample_index_base + s0;
+      oc.kt->raygen_ao(st, fr, d_pos, d_nrm, d_ids, (uint32_t)base, q->max_distance, ps, h->shadow_q.p, oc.queue_length(), n_slots);
+      oc.query(ps, n_slots);
+      oc.kt->ao_fold(st, fr, ps, h->srt.p, s_pass, s0 == 0, s0 + s_pass == S, S, d_ao, d_bent);
+      HIP_TRY(hipGetLastError());
+      s0 += s_pass;
+    }
+    if (!on_device) { // the staging arrays are the next piece's, too
+      HIP_TRY(hipMemcpyAsync(out_ao + base, d_ao, m * sizeof(double), hipMemcpyDeviceToHost, st));
+      if (out_bent) HIP_TRY(hipMemcpyAsync(out_bent + 3 * base, d_bent, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+  }
+  return h->has_deep && h->gen_overflow.p;
+}
+
+namespace {
+
 // on_device: positions, normals, streams and both outputs are device pointers
 int bake_ao(rptgpu_scene* h, uint64_t n, const double* positions, const double* normals, const uint32_t* streams,
             const RptAoQuery* q, double* out_ao, double* out_bent, bool on_device, hipStream_t user_stream) {
@@ -129,50 +181,7 @@ int bake_ao(rptgpu_scene* h, uint64_t n, const double* positions, const double* 
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n) return RPTGPU_OK;
-  return device_call(h, user_stream, [&]() {
-    hipStream_t st = h->stream;
-    Occlusion oc(h, q->precision_mode, q->flags);
-    const uint32_t S = q->samples;
-    const uint64_t piece = rptplan::ao_piece(n, oc.asked, S, oc.pass_target);
-    // (a pass of m <= piece points holds m * ao_pass_samples(m, ...) <= min(m * S, the pass bound) slots)
-    const rptdev::PathState ps = oc.workspace(std::min<uint64_t>(piece * S, rptplan::occlusion_pass_max(oc.pass_target)));
-    h->accum.alloc(4 * piece); // per point: the count of visible directions and their sum, [4][points] (rpt_ao_fold)
-    if (!on_device) {
-      h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece); h->rays_out.alloc(4 * piece);
-      if (streams) h->ray_ids.alloc(piece);
-    }
-    for (uint64_t base = 0; base < n; base += piece) {
-      const uint64_t m = std::min(piece, n - base);
-      const double *d_pos = positions + 3 * base, *d_nrm = normals + 3 * base;
-      const uint32_t* d_ids = streams ? streams + base : nullptr;
-      double *d_ao = out_ao + base, *d_bent = out_bent ? out_bent + 3 * base : nullptr;
-      if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(h->rays_o.p, d_pos, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_nrm, 3 * m * sizeof(double), hipMemcpyHostToDevice, st));
-        if (streams) HIP_TRY(hipMemcpyAsync(h->ray_ids.p, d_ids, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        d_pos = h->rays_o.p; d_nrm = h->rays_d.p; d_ids = streams ? h->ray_ids.p : nullptr;
-        d_ao = h->rays_out.p; d_bent = out_bent ? h->rays_out.p + piece : nullptr;
-      }
-      rptdev::Frame fr{};
-      fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.seed = q->seed; fr.accum = h->accum.p;
-      for (uint32_t s0 = 0; s0 < S;) { // the piece's passes: s_pass directions of every point
-        const uint32_t s_pass = rptplan::ao_pass_samples(m, S - s0, oc.pass_target);
-        const uint32_t n_slots = (uint32_t)(m * s_pass);
-        fr.sample_base = q->sample_index_base + s0;
-        oc.kt->raygen_ao(st, fr, d_pos, d_nrm, d_ids, (uint32_t)base, q->max_distance, ps, h->shadow_q.p, oc.queue_length(), n_slots);
-        oc.query(ps, n_slots);
-        oc.kt->ao_fold(st, fr, ps, h->srt.p, s_pass, s0 == 0, s0 + s_pass == S, S, d_ao, d_bent);
-        HIP_TRY(hipGetLastError());
-        s0 += s_pass;
-      }
-      if (!on_device) { // the staging arrays are the next piece's, too
-        HIP_TRY(hipMemcpyAsync(out_ao + base, d_ao, m * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (out_bent) HIP_TRY(hipMemcpyAsync(out_bent + 3 * base, d_bent, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-      }
-    }
-    return h->has_deep && h->gen_overflow.p;
-  });
+  return device_call(h, user_stream, [&]() { return enqueue_ao(h, n, positions, normals, streams, q, out_ao, out_bent, on_device); });
 }
 
 } // namespace

@@ -29,6 +29,26 @@ const char* bad_probe_query(const RptProbeQuery* q) {
   return nullptr;
 }
 
+// the call's device work, behind its checks (n > 0): the body of its device_call, which rptgpu_bake_lightmap runs inside its
+// own (api_lightmap.cpp) -> drain_call's read_overflow
+bool enqueue_probes(rptgpu_scene* h, uint64_t n, const double* positions, const double* normals, const uint32_t* streams,
+                    const RptProbeQuery* q, double* out, bool on_device) {
+  const bool with_normals = q->kind == RPT_PROBE_IRRADIANCE;
+  // the piece: whole probes, at most the paths one pass may hold with every level of every path — a pass is at least
+  // one sample of every probe of the piece (rptplan::rays_piece, as it stands)
+  uint64_t asked = 0; // tests: pieces of a few probes
+  if (const char* e = std::getenv("RPTGPU_PROBES_PIECE")) asked = std::strtoull(e, nullptr, 10);
+  uint64_t piece = rptplan::rays_piece(n, asked, piece_pass_target(h, q->samples, q->max_bounces));
+  const bool persistent = piece_persistent(h, q->flags, RPT_FLAG_RAYS_PERSISTENT);
+  if (persistent) piece = persistent_piece(h, piece, q->samples);
+  const double scale = (with_normals ? 3.141592653589793 : 12.566370614359172) / (double)q->samples;
+  // (the normals are staged and read for RPT_PROBE_IRRADIANCE only; a probe's streams start at draw 0, and it has no exposure)
+  trace_ray_pieces(h, RayPieces{n, positions, with_normals ? normals : nullptr, streams, on_device, piece, persistent,
+                                piece_params(*q, q->samples, 0.0), 0u, probe_width(q->kind), out, (int)q->kind, scale},
+                   nullptr, nullptr);
+  return !persistent && h->has_deep && h->gen_overflow.p;
+}
+
 namespace {
 
 // on_device: positions, normals, streams and out are device pointers (user_stream: the stream their producer ran on)
@@ -44,22 +64,7 @@ int bake_probes(rptgpu_scene* h, uint64_t n, const double* positions, const doub
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
   if (!n) return RPTGPU_OK;
-  return device_call(h, user_stream, [&]() {
-    const bool with_normals = q->kind == RPT_PROBE_IRRADIANCE;
-    // the piece: whole probes, at most the paths one pass may hold with every level of every path — a pass is at least
-    // one sample of every probe of the piece (rptplan::rays_piece, as it stands)
-    uint64_t asked = 0; // tests: pieces of a few probes
-    if (const char* e = std::getenv("RPTGPU_PROBES_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    uint64_t piece = rptplan::rays_piece(n, asked, piece_pass_target(h, q->samples, q->max_bounces));
-    const bool persistent = piece_persistent(h, q->flags, RPT_FLAG_RAYS_PERSISTENT);
-    if (persistent) piece = persistent_piece(h, piece, q->samples);
-    const double scale = (with_normals ? 3.141592653589793 : 12.566370614359172) / (double)q->samples;
-    // (the normals are staged and read for RPT_PROBE_IRRADIANCE only; a probe's streams start at draw 0, and it has no exposure)
-    trace_ray_pieces(h, RayPieces{n, positions, with_normals ? normals : nullptr, streams, on_device, piece, persistent,
-                                  piece_params(*q, q->samples, 0.0), 0u, probe_width(q->kind), out, (int)q->kind, scale},
-                     nullptr, nullptr);
-    return !persistent && h->has_deep && h->gen_overflow.p;
-  });
+  return device_call(h, user_stream, [&]() { return enqueue_probes(h, n, positions, normals, streams, q, out, on_device); });
 }
 
 } // namespace

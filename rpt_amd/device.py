@@ -455,6 +455,48 @@ class GpuScene:
         q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
         return self._ray_records("hit_surface", origins, dirs, q, _abi.RptSurfaceArrays(), _marshal.SURFACE_CHANNELS)
 
+    def bake_lightmap(self, triangles, uvs, width, height, *, normals=None, samples=0, max_bounces=0, seed, offset=0.0, dilate=0,
+                      channels=_abi.RPT_LIGHTMAP_IRRADIANCE | _abi.RPT_LIGHTMAP_OWNER, max_distance=float("inf"), stream_base=0,
+                      sample_index_base=0, flags=0):
+        """A lightmap baked on the device (rptgpu_bake_lightmap) -> a dict with one array per channel of
+        `channels` (RPT_LIGHTMAP_*), each (height, width) or (height, width, 3), row 0 at v = 0: `irradiance` and `ao` —
+        bake_probes' RPT_PROBE_IRRADIANCE and bake_ao's results at the texel centres the triangles' uv charts cover, from
+        stream id stream_base + y * width + x, gutters filled by `dilate` rounds —, `owner` int32 (the lowest index of a
+        triangle that covers the centre, -1 without one), `barycentric`, `position` (the gather point, lifted by offset *
+        normal) and `normal`; +0.0 where nobody owns a texel.  triangles: world-space (n, 3, 3) float64 positions, with
+        `normals` (n, 3, 3) or None (flat, Triangle.from_vertices'), or a Mesh's (n, 18) rows, positions and normals in one;
+        uvs: (n, 3, 2).  numpy arrays go through host memory; torch tensors on the handle's device are read where they
+        lie (rptgpu_bake_lightmap_device) and the results are new tensors there."""
+        if not _abi.lightmap_supported(self.lib):
+            raise _abi.RptGpuError(_abi.RPTGPU_E_INVALID_ARGUMENT, "this library does not export rptgpu_bake_lightmap")
+        who = "bake_lightmap"
+        q = _abi.RptLightmapQuery()
+        q.struct_size, q.channels = C.sizeof(_abi.RptLightmapQuery), int(channels)
+        q.width, q.height, q.samples, q.max_bounces = int(width), int(height), int(samples), int(max_bounces)
+        q.dilate, q.stream_base, q.seed, q.sample_index_base = int(dilate), int(stream_base), int(seed), int(sample_index_base)
+        q.offset, q.max_distance = float(offset), float(max_distance)
+        q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        a = _abi.RptLightmapArrays()
+        a.struct_size, a.reserved = C.sizeof(a), 0
+        m = _marshal.pick(self.device, triangles, uvs, normals)
+        if not hasattr(triangles, "shape"):
+            triangles = np.asarray(triangles)
+        if len(triangles.shape) == 2:  # a Mesh's rows: v1 v2 v3 n1 n2 n3
+            if normals is not None:
+                raise ValueError("bake_lightmap: (n, 18) triangle rows hold their normals; pass no normals beside them")
+            rows = m.records(triangles, (18,), who, "triangles")
+            pos, nrm = rows[:, :9].reshape(-1, 3, 3), rows[:, 9:].reshape(-1, 3, 3)
+        else:
+            pos, nrm = triangles, normals
+        pos = m.records(pos, (3, 3), who, "triangles")
+        n = int(pos.shape[0])
+        nrm = m.counted(m.records(nrm, (3, 3), who, "normals"), n, who, "normals", "triangles") if nrm is not None else None
+        uv = m.counted(m.records(uvs, (3, 2), who, "uvs"), n, who, "uvs", "triangles")
+        out = m.fill(a, _marshal.layout(_marshal.LIGHTMAP_CHANNELS, q.channels, (q.height, q.width)), who)
+        PD = C.POINTER(C.c_double)
+        self._call("rptgpu_bake_lightmap", m, n, m.pointer(pos, PD), m.pointer(nrm, PD), m.pointer(uv, PD), C.byref(q), C.byref(a))
+        return out
+
     def _ray_records(self, who, origins, dirs, q, a, table):
         """first_hits' and hit_surface's common half: the rays checked, one new array per channel that q names with its
         address in `a`, then rptgpu_<who>"""

@@ -1,0 +1,48 @@
+"""What a caller of GpuScene.bake_lightmap needs beside it (include/rpt_gpu_lightmap.h): the texture
+coordinates of an OBJ's triangles, in the order load_obj makes the triangles, and a bake turned into bytes to look at.
+numpy only."""
+import numpy as np
+
+from .color import color_bytes
+from .io import _at, _lines, _open, _parse_index
+
+
+def load_obj_texcoords(file):
+    """-> (n_tris, 3, 2) float64: the `vt` of every triangle load_obj(file) makes, in its order — faces fan-triangulated
+    (io.rs:181-198: corners 0, i, i + 1), indices by _parse_index (1-based, or negative from the end of what was read so
+    far) and looked up with _at (out of range raises IndexError, as the reference panics).  ValueError if any face corner
+    has no `vt` index: such a mesh has no chart to bake into.  A `vt` line's third coordinate is not read."""
+    f, own = _open(file, "r")
+    try:
+        n_vertices, texcoords, out = 0, [], []
+        for tokens in _lines(f):
+            if tokens[0] == "v":
+                n_vertices += 1
+            elif tokens[0] == "vt":
+                try:
+                    texcoords.append((float(tokens[1]), float(tokens[2])))
+                except (ValueError, IndexError):
+                    raise ValueError("Failed to parse texture coordinate in .OBJ")
+            elif tokens[0] == "f":
+                vti = []
+                for vertex in tokens[1:]:
+                    args = (vertex.split("/") + ["", "", ""])[:3]
+                    if _parse_index(args[0], n_vertices) is None:
+                        raise ValueError("Invalid vertex index")
+                    t = _parse_index(args[1], len(texcoords))
+                    if t is None:
+                        raise ValueError("load_obj_texcoords: face corner %r has no vt index" % vertex)
+                    vti.append(t)
+                for i in range(1, len(vti) - 1):
+                    out.append((_at(texcoords, vti[0]), _at(texcoords, vti[i]), _at(texcoords, vti[i + 1])))
+        return np.array(out, dtype=np.float64).reshape(-1, 3, 2)
+    finally:
+        if own:
+            f.close()
+
+
+def to_rgb8(irradiance, albedo=(1.0, 1.0, 1.0), exposure=0.0):
+    """(H, W, 3) uint8 to look at a bake: the radiance a diffuse surface of `albedo` sends out under `irradiance`,
+    albedo / pi * irradiance * 2^exposure, through color_bytes."""
+    radiance = np.asarray(irradiance, dtype=np.float64) * (np.asarray(albedo, dtype=np.float64) / np.pi * 2.0 ** float(exposure))
+    return color_bytes(radiance)
