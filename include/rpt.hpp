@@ -781,6 +781,24 @@ class Renderer {
                          bent ? bent->data() : nullptr));
     return ao;
   }
+  // addition: direct light baked on the device (rptgpu_bake_direct, include/rpt_gpu_direct.h).  positions, normals: xyz per
+  // point (the rays start AT the positions: lift them off their surface yourself).  -> xyz per point: the mean over
+  // num_samples rounds of next-event estimation — every non-ambient light sampled in scene order, intensity * (wi . n)
+  // added where the light faces the normal and is seen —, irradiance without the Lambertian 1/pi.  Point i draws from the
+  // stream (seed, streams[i] or i, sample_index_base + k), whatever other points the call holds.
+  std::vector<double> bake_direct(const std::vector<double>& positions, const std::vector<double>& normals,
+                                  const std::vector<uint32_t>& streams = {}, uint64_t sample_index_base = 0, uint32_t flags = 0) {
+    ensure_scene();
+    const size_t n = positions.size() / 3;
+    if (positions.size() != 3 * n || normals.size() != 3 * n || (!streams.empty() && streams.size() != n))
+      throw std::invalid_argument("bake_direct: positions and normals hold xyz per point, streams one id per point");
+    RptDirectQuery q{};
+    q.struct_size = sizeof(RptDirectQuery); q.samples = num_samples_; q.seed = seed_; q.sample_index_base = sample_index_base;
+    q.flags = flags;
+    std::vector<double> out(3 * n);
+    check(rptgpu_bake_direct(handle_, n, positions.data(), normals.data(), streams.empty() ? nullptr : streams.data(), &q, out.data()));
+    return out;
+  }
   // addition: a batch of frames in one call (rptgpu_render_views, include/rpt_gpu.h), each from a view of its own — a camera
   // under RPT_VIEW_PERSPECTIVE (this renderer's frame of that camera), RPT_VIEW_ORTHOGRAPHIC or RPT_VIEW_PANORAMA (a
   // rendered panorama is an Hdri's texel array).  -> [views][height][width][3], the renderer's size, samples, bounces and

@@ -204,6 +204,12 @@ class RptAoQuery(C.Structure):
                 ("max_distance", f64), ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class RptDirectQuery(C.Structure):
+    """include/rpt_gpu_direct.h RptDirectQuery (rptgpu_bake_direct's parameters; detected by symbol within ABI 7)."""
+    _fields_ = [("struct_size", C.c_uint32), ("samples", C.c_uint32), ("seed", C.c_uint64), ("sample_index_base", C.c_uint64),
+                ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class RptViewDenoise(C.Structure):
     """include/rpt_gpu_views_denoised.h RptViewDenoise (rptgpu_render_views_denoised's batches, features and filter)."""
     _fields_ = [("struct_size", C.c_uint32), ("batches", C.c_uint32), ("feature_iterations", C.c_uint32), ("_pad", C.c_uint32),
@@ -416,6 +422,13 @@ LIGHTMAP_SYMBOLS = [
     ("rptgpu_bake_lightmap_device", C.c_int,
      [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptLightmapQuery), C.POINTER(RptLightmapArrays), _VP]),
 ]
+# ... and every symbol include/rpt_gpu_direct.h declares, optional in the same way (direct_supported())
+DIRECT_SYMBOLS = [
+    ("rptgpu_bake_direct", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(C.c_uint32), C.POINTER(RptDirectQuery), _PD]),
+    ("rptgpu_bake_direct_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptDirectQuery), _VP, _VP]),
+    ("rptgpu_bake_lightmap_direct", C.c_int, [_VP, C.c_uint64, _PD, _PD, _PD, C.POINTER(RptLightmapQuery), _PD]),
+    ("rptgpu_bake_lightmap_direct_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptLightmapQuery), _VP, _VP]),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -444,11 +457,11 @@ def load_library(path=None):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
-    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS + LIGHTMAP_SYMBOLS:
+    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS + LIGHTMAP_SYMBOLS + DIRECT_SYMBOLS:
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported(), lightmap_supported() say no)
+            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported(), lightmap_supported(), direct_supported() say no)
         fn.restype = restype
         fn.argtypes = argtypes
     if lib.rptgpu_abi_version() != ABI_VERSION:
@@ -506,6 +519,13 @@ def lightmap_supported(lib=None):
     caller does with dlsym: a library without them is still ABI 7."""
     lib = lib or load_library()
     return all(hasattr(lib, name) for name, _, _ in LIGHTMAP_SYMBOLS)
+
+
+def direct_supported(lib=None):
+    """Does the library export rptgpu_bake_direct[_device] and rptgpu_bake_lightmap_direct[_device]
+    (include/rpt_gpu_direct.h)?  Detected by symbol, as a C caller does with dlsym: a library without them is still ABI 7."""
+    lib = lib or load_library()
+    return all(hasattr(lib, name) for name, _, _ in DIRECT_SYMBOLS)
 
 
 def check(code, handle=None):

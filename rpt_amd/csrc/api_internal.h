@@ -25,6 +25,9 @@
 //                    rpt_buffer_accumulate over all views, then the views' feature sums and the filter, one launch per step
 //   api_occlusion.cpp rptgpu_occluded[_device], rptgpu_bake_ao[_device]: the caller's rays, or points x directions made on the
 //                    device, through ONE visibility query of a render per pass (no depth loop), in pieces
+//   api_direct.cpp   rptgpu_bake_direct[_device], rptgpu_bake_lightmap_direct[_device]: next-event estimation at the caller's
+//                    points — every light's sample per (sample, point) slot made on the device, the visibility queries of a
+//                    depth over the lights' queues, the fold — in the AO call's pieces and passes
 //   api_hits.cpp     rptgpu_first_hits[_device], rptgpu_render_views_aov[_seeded][_device]: the first hit's record for the caller's rays
 //                    (one fused kernel, or the per-tree closest-hit query, in pieces) and rptgpu_render_aov's sums for
 //                    every view of a batch (raygen, closest-hit query and fold in passes over render_views' pieces)
@@ -489,6 +492,82 @@ bool enqueue_ao(rptgpu_scene* h, uint64_t n, const double* positions, const doub
 // the pass planner's input for a call over npix pixels or rays: what its passes share, and the device's state right now
 rptplan::PassInput pass_input(rptgpu_scene* h, uint32_t npix, uint32_t iterations);
 void pass_input_now(rptgpu_scene* h, rptplan::PassInput& in);
+// rptgpu_bake_direct's device work in the same way (api_direct.cpp): its device_call's body, which
+// rptgpu_bake_lightmap_direct runs over its compacted texels
+bool enqueue_direct(rptgpu_scene* h, uint64_t n, const double* positions, const double* normals, const uint32_t* streams,
+                    const RptDirectQuery* q, double* out, bool on_device);
+// the lightmap pipeline (api_lightmap.cpp) with enqueue_direct as its one gather, into `direct` ([H][W][3]): the driver
+// behind rptgpu_bake_lightmap_direct[_device] (api_direct.cpp), argument checks included
+int bake_lightmap_direct(rptgpu_scene* h, uint64_t n_tris, const double* positions, const double* normals, const double* uvs,
+                         const RptLightmapQuery* q, double* direct, bool on_device, hipStream_t user_stream);
+
+// what the drivers of rptgpu_occluded, rptgpu_bake_ao (api_occlusion.cpp) and rptgpu_bake_direct (api_direct.cpp) share: the
+// route, the pass bound, the workspace, and the query itself
+struct Occlusion {
+  rptgpu_scene* h;
+  const KernelTable* kt;
+  bool prof, by_object;
+  uint64_t pass_target; // rays a pass may hold
+  uint64_t asked;       // piece_env's value (0: not set)
+
+  Occlusion(rptgpu_scene* h_, uint32_t precision_mode, uint32_t flags, const char* piece_env)
+      : h(h_), kt(table_for(precision_mode, h_->ext_shapes)), prof((flags & RPT_FLAG_PROFILE_KERNELS) != 0) {
+    h->dscene.force_general = (flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
+    // (run_pass's decision: per-tree queries for scenes with deep trees — under RPT_FLAG_GENERAL_TRAVERSAL only where a
+    // group with tree children leaves no other walker)
+    by_object = h->has_deep && (!(flags & RPT_FLAG_GENERAL_TRAVERSAL) || h->tree_kids);
+    rptplan::PassInput in = pass_input(h, 1, 1);
+    in.remaining = 1;
+    in.ratio = 1.0; // no depth follows the rays: one record column is all ensure_workspace is asked for
+    pass_input_now(h, in);
+    pass_target = rptplan::plan_pass(in).target;
+    asked = 0;
+    if (const char* e = std::getenv(piece_env)) asked = std::strtoull(e, nullptr, 10);
+  }
+  // slots for `cap` rays.  ensure_workspace sizes the shadow state, the queues and srt for max(1, lights) columns, so a
+  // scene without lights has the column 0 the visibility calls use
+  rptdev::PathState workspace(uint64_t cap) {
+    ensure_workspace(h, cap, 1);
+    if (h->has_deep && (h->gen_all || h->dscene.force_general)) ensure_generic(h, true); // (as render_wavefront's size_pass)
+    return path_state(h);
+  }
+  uint32_t* queue_length() const { return h->counters.p + 2; } // where rpt_shade counts light 0's shadow rays
+  // the visibility of the n rays laid into light 0's shadow state: srt's column 0
+  void query(const rptdev::PathState& ps, uint32_t n) {
+    const int pair = event_pair_begin(h, RPT_K_SHADOW, prof);
+    if (by_object) {
+      reset_tree_counters(h);
+      query_visibility(h, kt, ps, 0, n, queue_length(), nullptr);
+    } else {
+      kt->shadow_rays(h->stream, h->dscene, ps, h->shadow_q.p, queue_length(), n, 1, h->srt.p);
+    }
+    event_pair_end(h, RPT_K_SHADOW, pair);
+    h->stats.shadow_rays += n;
+    h->stats.shadow_rays_traced += n;
+  }
+  // the visibility of every light's queued rays, as a depth of run_pass asks for it: cnt[l] rays stand in light l's queue
+  // (queue_length() + l on the device); srt's column l receives the queued slots' answers.  -> the rays traced
+  uint64_t query_lights(const rptdev::PathState& ps, const uint32_t* cnt) {
+    const int nlights = h->dscene.num_lights;
+    uint64_t traced = 0;
+    uint32_t n_max = 0;
+    for (int l = 0; l < nlights; l++) {
+      traced += cnt[l];
+      n_max = std::max(n_max, cnt[l]);
+    }
+    if (!n_max) return 0;
+    const int pair = event_pair_begin(h, RPT_K_SHADOW, prof);
+    if (by_object) {
+      reset_tree_counters(h);
+      for (int l = 0; l < nlights; l++)
+        if (cnt[l]) query_visibility(h, kt, ps, l, cnt[l], queue_length() + l, nullptr);
+    } else { // one launch for all lights (the grid's y is the light; an empty queue costs its blocks one load)
+      kt->shadow_rays(h->stream, h->dscene, ps, h->shadow_q.p, queue_length(), n_max, nlights, h->srt.p);
+    }
+    event_pair_end(h, RPT_K_SHADOW, pair);
+    return traced;
+  }
+};
 
 // ---- what the calls that run a path driver over PIECES share (api_rays.cpp, api_probes.cpp, api_vertices.cpp, api_views.cpp):
 // a piece of rays, probes or (view, pixel) indices is the "frame" of its own passes or launches

@@ -6,6 +6,8 @@
 // (enqueue_probes, enqueue_ao: their drivers, not copies) and rpt_lightmap_scatter; at the end rpt_lightmap_dilate, one launch
 // per round and channel over the whole map.  A device caller's arrays are written where they lie; a host caller's triangles
 // and named channels are staged whole in arrays the handle keeps.
+// rptgpu_bake_lightmap_direct[_device] (include/rpt_gpu_direct.h; the entry points: api_direct.cpp) is the same
+// pipeline — run_lightmap — with rptgpu_bake_direct's device work, enqueue_direct, as the one gather of its one channel.
 #include "api_internal.h"
 
 namespace rptapi {
@@ -121,19 +123,24 @@ void dilate_map(rptgpu_scene* h, uint32_t width, uint32_t height, uint32_t round
   if (ao && s1 != ao) HIP_TRY(hipMemcpyAsync(ao, s1, n * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
 }
 
-// on_device: positions, normals, uvs and out's arrays are device pointers (user_stream: the stream their producer ran on)
-int bake_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, const double* normals, const double* uvs,
-                  const RptLightmapQuery* q, const RptLightmapArrays* out, bool on_device, hipStream_t user_stream) {
-  // (the query first, then the arrays: both are refused whatever else is wrong, also without a handle or a device)
-  if (const char* why = bad_lightmap_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
-  if (const char* why = bad_lightmap_arrays(out, q->channels)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+// the checks both forms of the call make behind their query and arrays
+int bad_lightmap_call(rptgpu_scene* h, uint64_t n_tris, const double* positions, const double* uvs) {
   if (n_tris > rptlightmap::TRIS_MAX) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "more than 2^31 - 1 triangles (an owner is an int32)");
   if (n_tris && (!positions || !uvs)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
+  return RPTGPU_OK;
+}
+
+// The pipeline behind the checks.  ch: the channels to make, theirs: the caller's arrays for them.  direct: the gather of the
+// IRRADIANCE slot — the only channel then — is enqueue_direct instead of enqueue_probes (rptgpu_bake_lightmap_direct: q's
+// channels, max_bounces and max_distance are not read)
+int run_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, const double* normals, const double* uvs,
+                 const RptLightmapQuery* q, uint32_t ch, const MapArrays& theirs, bool direct, bool on_device,
+                 hipStream_t user_stream) {
   return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
-    const uint32_t ch = q->channels, W = q->width, H = q->height;
+    const uint32_t W = q->width, H = q->height, max_bounces = direct ? 0u : q->max_bounces;
     const uint64_t n = rptlightmap::texels(W, H);
     const bool irr = (ch & RPT_LIGHTMAP_IRRADIANCE) != 0, ao = (ch & RPT_LIGHTMAP_AO) != 0, gather = irr || ao;
     bool overflow = false;
@@ -150,7 +157,6 @@ int bake_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, con
       tris.positions = d; tris.normals = normals ? d + wp : nullptr; tris.uvs = d + wp + wn;
     }
     // where the map's channels lie on the device: the caller's arrays, or the handle's staging
-    const MapArrays theirs = caller_arrays(*out, ch);
     MapArrays dev = theirs;
     if (!on_device) {
       h->lm_stage.alloc(stage_words(n, ch));
@@ -165,7 +171,7 @@ int bake_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, con
     // 2. the pieces
     uint64_t asked = 0; // tests: pieces of a few texels
     if (const char* e = std::getenv("RPTGPU_LIGHTMAP_PIECE")) asked = std::strtoull(e, nullptr, 10);
-    const uint64_t fit = gather ? std::min<uint64_t>(piece_pass_target(h, q->samples, q->max_bounces), RPT_MAX_PATHS_PER_PASS)
+    const uint64_t fit = gather ? std::min<uint64_t>(piece_pass_target(h, q->samples, max_bounces), RPT_MAX_PATHS_PER_PASS)
                                 : rptlightmap::PIECE_MAX;
     const uint64_t piece = rptlightmap::piece(n, asked, fit);
     const rptlightmap::Compact lay = rptlightmap::compact(piece, irr, ao);
@@ -188,12 +194,15 @@ int bake_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, con
       if (ao) c_ao = h->lm_compact.p + lay.ao;
     }
     RptProbeQuery pq{};
-    pq.struct_size = sizeof(RptProbeQuery); pq.kind = RPT_PROBE_IRRADIANCE; pq.samples = q->samples; pq.max_bounces = q->max_bounces;
+    pq.struct_size = sizeof(RptProbeQuery); pq.kind = RPT_PROBE_IRRADIANCE; pq.samples = q->samples; pq.max_bounces = max_bounces;
     pq.seed = q->seed; pq.sample_index_base = q->sample_index_base; pq.precision_mode = q->precision_mode; pq.flags = q->flags;
     RptAoQuery aq{};
     aq.struct_size = sizeof(RptAoQuery); aq.samples = q->samples; aq.seed = q->seed; aq.sample_index_base = q->sample_index_base;
     aq.max_distance = q->max_distance; aq.precision_mode = q->precision_mode;
     aq.flags = q->flags & ~(uint32_t)RPT_FLAG_RAYS_PERSISTENT; // (the AO gather has no persistent form: the same bits)
+    RptDirectQuery dq{};
+    dq.struct_size = sizeof(RptDirectQuery); dq.samples = q->samples; dq.seed = q->seed; dq.sample_index_base = q->sample_index_base;
+    dq.precision_mode = q->precision_mode; dq.flags = q->flags & ~(uint32_t)RPT_FLAG_RAYS_PERSISTENT;
     const rptlightmap::RawOut raw{dev.owner, dev.barycentric, dev.position, dev.normal};
     for (uint64_t base = 0; base < n; base += piece) {
       const uint32_t m = (uint32_t)rptlightmap::piece_len(base, n, piece);
@@ -205,7 +214,8 @@ int bake_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, con
       HIP_TRY(hipMemcpyAsync(&owned, h->lm_scan.p + (m - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
       if (owned) {
-        if (irr) overflow |= enqueue_probes(h, owned, c_point, c_normal, c_ids, &pq, c_irr, true);
+        if (direct) overflow |= enqueue_direct(h, owned, c_point, c_normal, c_ids, &dq, c_irr, true);
+        else if (irr) overflow |= enqueue_probes(h, owned, c_point, c_normal, c_ids, &pq, c_irr, true);
         if (ao) overflow |= enqueue_ao(h, owned, c_point, c_normal, c_ids, &aq, c_ao, nullptr, true);
       }
       if (irr) HIP_TRY(rptlightmap::scatter(st, h->lm_owner.p, base, m, h->lm_scan.p, c_irr, 3, dev.irradiance));
@@ -230,7 +240,46 @@ int bake_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, con
   });
 }
 
+// on_device: positions, normals, uvs and out's arrays are device pointers (user_stream: the stream their producer ran on)
+int bake_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, const double* normals, const double* uvs,
+                  const RptLightmapQuery* q, const RptLightmapArrays* out, bool on_device, hipStream_t user_stream) {
+  // (the query first, then the arrays: both are refused whatever else is wrong, also without a handle or a device)
+  if (const char* why = bad_lightmap_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (const char* why = bad_lightmap_arrays(out, q->channels)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (const int rc = bad_lightmap_call(h, n_tris, positions, uvs)) return rc;
+  return run_lightmap(h, n_tris, positions, normals, uvs, q, q->channels, caller_arrays(*out, q->channels), false, on_device,
+                      user_stream);
+}
+
 } // namespace
+
+// what is wrong with the RptLightmapQuery of rptgpu_bake_lightmap_direct, which reads neither channels nor max_bounces nor
+// max_distance (nullptr: nothing)
+static const char* bad_lightmap_direct_query(const RptLightmapQuery* q) {
+  if (!q) return "null RptLightmapQuery";
+  if (q->struct_size != sizeof(RptLightmapQuery)) return "RptLightmapQuery: struct_size is not sizeof(RptLightmapQuery)";
+  if (!q->width || !q->height) return "RptLightmapQuery: width == 0 or height == 0";
+  if (!rptlightmap::streams_fit(q->width, q->height, q->stream_base))
+    return "RptLightmapQuery: width * height + stream_base > 2^32 (a texel's stream id has 32 bits)";
+  if (!q->samples) return "RptLightmapQuery: samples == 0";
+  if (!std::isfinite(q->offset)) return "RptLightmapQuery: offset is not finite";
+  if (q->precision_mode != RPT_PRECISION_F64_STRICT) return BAD_MODE;
+  if (q->flags & RPT_FLAG_PERSISTENT)
+    return "RPT_FLAG_PERSISTENT — the persistent kernel makes its rays from a camera; a lightmap's direct light runs the "
+           "wavefront pipeline's shadow-ray query only";
+  return nullptr;
+}
+
+int bake_lightmap_direct(rptgpu_scene* h, uint64_t n_tris, const double* positions, const double* normals, const double* uvs,
+                         const RptLightmapQuery* q, double* direct, bool on_device, hipStream_t user_stream) {
+  if (const char* why = bad_lightmap_direct_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (!direct) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null out");
+  if (const int rc = bad_lightmap_call(h, n_tris, positions, uvs)) return rc;
+  MapArrays theirs{};
+  theirs.irradiance = direct;
+  return run_lightmap(h, n_tris, positions, normals, uvs, q, RPT_LIGHTMAP_IRRADIANCE, theirs, true, on_device, user_stream);
+}
+
 } // namespace rptapi
 
 extern "C" {

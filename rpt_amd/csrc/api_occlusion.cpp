@@ -33,51 +33,6 @@ static const char* bad_ao_query(const RptAoQuery* q) {
 
 namespace {
 
-// what both calls' drivers share: the route, the pass bound, the workspace, and the query itself
-struct Occlusion {
-  rptgpu_scene* h;
-  const KernelTable* kt;
-  bool prof, by_object;
-  uint64_t pass_target; // rays a pass may hold
-  uint64_t asked;       // RPTGPU_OCCLUSION_PIECE (0: not set)
-
-  Occlusion(rptgpu_scene* h_, uint32_t precision_mode, uint32_t flags)
-      : h(h_), kt(table_for(precision_mode, h_->ext_shapes)), prof((flags & RPT_FLAG_PROFILE_KERNELS) != 0) {
-    h->dscene.force_general = (flags & RPT_FLAG_GENERAL_TRAVERSAL) ? 1 : 0;
-    // (run_pass's decision: per-tree queries for scenes with deep trees — under RPT_FLAG_GENERAL_TRAVERSAL only where a
-    // group with tree children leaves no other walker)
-    by_object = h->has_deep && (!(flags & RPT_FLAG_GENERAL_TRAVERSAL) || h->tree_kids);
-    rptplan::PassInput in = pass_input(h, 1, 1);
-    in.remaining = 1;
-    in.ratio = 1.0; // no depth follows the rays: one record column is all ensure_workspace is asked for
-    pass_input_now(h, in);
-    pass_target = rptplan::plan_pass(in).target;
-    asked = 0;
-    if (const char* e = std::getenv("RPTGPU_OCCLUSION_PIECE")) asked = std::strtoull(e, nullptr, 10);
-  }
-  // slots for `cap` rays.  ensure_workspace sizes the shadow state, the queues and srt for max(1, lights) columns, so a
-  // scene without lights has the column 0 these calls use
-  rptdev::PathState workspace(uint64_t cap) {
-    ensure_workspace(h, cap, 1);
-    if (h->has_deep && (h->gen_all || h->dscene.force_general)) ensure_generic(h, true); // (as render_wavefront's size_pass)
-    return path_state(h);
-  }
-  uint32_t* queue_length() const { return h->counters.p + 2; } // where rpt_shade counts light 0's shadow rays
-  // the visibility of the n rays laid into light 0's shadow state: srt's column 0
-  void query(const rptdev::PathState& ps, uint32_t n) {
-    const int pair = event_pair_begin(h, RPT_K_SHADOW, prof);
-    if (by_object) {
-      reset_tree_counters(h);
-      query_visibility(h, kt, ps, 0, n, queue_length(), nullptr);
-    } else {
-      kt->shadow_rays(h->stream, h->dscene, ps, h->shadow_q.p, queue_length(), n, 1, h->srt.p);
-    }
-    event_pair_end(h, RPT_K_SHADOW, pair);
-    h->stats.shadow_rays += n;
-    h->stats.shadow_rays_traced += n;
-  }
-};
-
 // on_device: origins, dirs, max_t and out are device pointers (user_stream: the stream their producer ran on)
 int occluded(rptgpu_scene* h, uint64_t n, const double* origins, const double* dirs, const double* max_t,
              const RptVisibilityQuery* q, uint8_t* out, bool on_device, hipStream_t user_stream) {
@@ -89,7 +44,7 @@ int occluded(rptgpu_scene* h, uint64_t n, const double* origins, const double* d
   if (!n) return RPTGPU_OK;
   return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
-    Occlusion oc(h, q->precision_mode, q->flags);
+    Occlusion oc(h, q->precision_mode, q->flags, "RPTGPU_OCCLUSION_PIECE");
     const uint64_t piece = rptplan::occlusion_piece(n, oc.asked, oc.pass_target);
     const rptdev::PathState ps = oc.workspace(piece);
     if (!on_device) {
@@ -126,7 +81,7 @@ int occluded(rptgpu_scene* h, uint64_t n, const double* origins, const double* d
 bool enqueue_ao(rptgpu_scene* h, uint64_t n, const double* positions, const double* normals, const uint32_t* streams,
                 const RptAoQuery* q, double* out_ao, double* out_bent, bool on_device) {
   hipStream_t st = h->stream;
-  Occlusion oc(h, q->precision_mode, q->flags);
+  Occlusion oc(h, q->precision_mode, q->flags, "RPTGPU_OCCLUSION_PIECE");
   const uint32_t S = q->samples;
   const uint64_t piece = rptplan::ao_piece(n, oc.asked, S, oc.pass_target);
   // (a pass of m <= piece points holds m * ao_pass_samples(m, ...) <= min(m * S, the pass bound) slots)

@@ -298,6 +298,16 @@ struct KernelTable {
   void (*views_ids)(hipStream_t, uint64_t j_base, uint64_t npix_view, uint32_t n, uint32_t* pixels, uint32_t* view_of);
   void (*rays_ids)(hipStream_t, uint32_t id_base, uint32_t n, uint32_t* ids);
   void (*project_probes)(hipStream_t, const rptdev::Frame&, const double* lbuf, uint32_t spp, uint32_t kind);
+  // direct light at the caller's points (rptgpu_bake_direct; kernels/direct.inc): the steps around the visibility queries of
+  // every light.  raygen_direct: for fr.npix points x the pass's samples (n_slots, ids and id_base as raygen_ao) each light's
+  // sample into its column of ps.shadow and the slot into the queues (sq, [light][cap]) of the lights that can add something,
+  // their lengths in counters[2 + light], which the caller cleared.  direct_fold: a pass's answers into the points' running
+  // sums (fr.accum, [3][npix]), sample-major; last: the sums divided by the call's `samples` into out [npix][3]
+  void (*raygen_direct)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const double* positions, const double* normals,
+                        const uint32_t* ids, uint32_t id_base, const rptdev::PathState&, uint32_t* sq, uint32_t* counters,
+                        uint32_t n_slots);
+  void (*direct_fold)(hipStream_t, const rptdev::Scene&, const rptdev::Frame&, const rptdev::PathState&, const double* srt,
+                      uint32_t n_samples, bool first, bool last, uint32_t samples, double* out);
 };
 // the forms' translation units (kernels_<form>_strict[_ext].hip): what the tables above point to — kernels/launch_paths.inc's
 // two functions, and what else the form's file launches

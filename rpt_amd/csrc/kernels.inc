@@ -44,6 +44,9 @@
 //                  and, from the same text, the filter over a batch of views (rpt_denoise_views_prepare / _level / _finish), §18
 //   occlusion.inc  rptgpu_occluded / rptgpu_bake_ao: the caller's rays into a depth's shadow-ray state and their answers out of it
 //                  (rpt_occ_load, rpt_raygen_ao, rpt_occ_store, rpt_ao_fold), DESIGN.md §16
+//   direct.inc     rptgpu_bake_direct: sample_lights at the caller's points — every light's sample, contribution and shadow ray of a
+//                  (sample, point) slot into a depth's shadow-ray state, and the fold over samples and lights (rpt_raygen_direct,
+//                  rpt_direct_fold), DESIGN.md §23
 //   hits.inc       rptgpu_first_hits / rptgpu_render_views_aov: the closest-hit record into the caller's layout (rpt_first_hits
 //                  fused, rpt_hits_store behind the per-tree query, rpt_views_aov_fold), DESIGN.md §17
 //   wf_vertices.inc rptgpu_trace_vertices: the vertices of a wavefront pass's paths into the caller's layout (rpt_vertices_store per
@@ -168,6 +171,7 @@ constexpr double FIREFLY_CLAMP = 100.0; // renderer.rs:15
 #include "kernels/denoise.inc"
 #undef RPT_DN_VIEWS
 #include "kernels/occlusion.inc"
+#include "kernels/direct.inc"
 #include "kernels/hits.inc"
 #include "kernels/wf_vertices.inc"
 #include "kernels/launch.inc"

@@ -283,6 +283,20 @@ void launch_ao_fold(hipStream_t st, const Frame& fr, const PathState& ps, const 
                      out_ao, out_bent);
 }
 
+// rptgpu_bake_direct (kernels/direct.inc): every light's sample of a slot into the shadow-ray state, the fold out of srt
+void launch_raygen_direct(hipStream_t st, const Scene& sc, const Frame& fr, const double* positions, const double* normals,
+                          const uint32_t* ids, uint32_t id_base, const PathState& ps, uint32_t* sq, uint32_t* counters,
+                          uint32_t n_slots) {
+  // (a thread takes DIRECT_GROUPS slots: its wave's runs of 64)
+  hipLaunchKernelGGL(rpt_raygen_direct, grid_for(((uint64_t)n_slots + DIRECT_GROUPS - 1) / DIRECT_GROUPS), dim3(256), 0, st, sc, fr,
+                     positions, normals, ids, id_base, ps, sq, counters, n_slots);
+}
+void launch_direct_fold(hipStream_t st, const Scene& sc, const Frame& fr, const PathState& ps, const double* srt,
+                        uint32_t n_samples, bool first, bool last, uint32_t samples, double* out) {
+  hipLaunchKernelGGL(rpt_direct_fold, grid_for(fr.npix), dim3(256), 0, st, sc, fr, ps, srt, n_samples, first ? 1 : 0,
+                     last ? 1 : 0, samples, out);
+}
+
 // rptgpu_first_hits / rptgpu_render_views_aov (kernels/hits.inc): the closest-hit record into the caller's layout
 void launch_first_hits(hipStream_t st, const Scene& sc, const double* origins, const double* dirs, uint32_t n, const HitOut& out) {
   hipLaunchKernelGGL(rpt_first_hits, grid_for(n), dim3(256), 0, st, sc, origins, dirs, n, out);
@@ -383,5 +397,6 @@ const KernelTable TABLE = {launch_raygen, launch_raygen_rays, launch_extend, lau
                            launch_raygen_views_seeded, launch_shade_seeded,
                            launch_denoise_views_prepare, launch_denoise_views_level, launch_denoise_views_finish,
                            launch_vertices_store, launch_vertices_fold,
-                           RPT_NS_VIEWS::launch_views_ids, RPT_NS_RAYS::launch_rays_ids, RPT_NS_RAYS::launch_project_probes};
+                           RPT_NS_VIEWS::launch_views_ids, RPT_NS_RAYS::launch_rays_ids, RPT_NS_RAYS::launch_project_probes,
+                           launch_raygen_direct, launch_direct_fold};
 #endif // !__HIP_DEVICE_COMPILE__

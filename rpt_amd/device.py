@@ -391,6 +391,30 @@ class GpuScene:
                    C.byref(q), m.pointer(out_ao, PD), m.pointer(out_bent, PD))
         return (out_ao, out_bent) if bent_normals else out_ao
 
+    def bake_direct(self, positions, normals, *, samples, seed, sample_index_base=0, streams=None, flags=0, out=None):
+        """Direct light baked on the device (rptgpu_bake_direct): per point `samples` rounds of the
+        renderer's next-event estimation — every non-ambient light of the scene sampled in scene order on the point's Philox
+        stream, `intensity * (wi . n)` added where the light faces the normal and the shadow ray reaches it — -> (n, 3)
+        float64, the mean: irradiance without the Lambertian 1/pi, so `bsdf * out` is a surface's direct term.  The rays
+        start AT the positions (no offset: lift points off their surface yourself).  positions, normals: (n, 3) float64.
+        streams: (n,) 32-bit stream ids, default the points' indices.  numpy arrays go through host memory; torch tensors on
+        the handle's device are read where they lie (rptgpu_bake_direct_device) and the result is `out` or a new tensor
+        there."""
+        if not _abi.direct_supported(self.lib):
+            raise _abi.RptGpuError(_abi.RPTGPU_E_INVALID_ARGUMENT, "this library does not export rptgpu_bake_direct")
+        q = _abi.RptDirectQuery()
+        q.struct_size = C.sizeof(_abi.RptDirectQuery)
+        q.samples, q.seed, q.sample_index_base = int(samples), int(seed), int(sample_index_base)
+        q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        m = _marshal.pick(self.device, positions, normals)
+        n, pos, nrm = self._pair(m, positions, normals, "bake_direct", self._POINTS)
+        ids = m.stream_ids(streams, n, "bake_direct", "points", strict=True)
+        out = m.result(out, (n, 3), np.float64, "bake_direct", "out")
+        PD = C.POINTER(C.c_double)
+        self._call("rptgpu_bake_direct", m, n, m.pointer(pos, PD), m.pointer(nrm, PD), m.pointer(ids, C.POINTER(C.c_uint32)),
+                   C.byref(q), m.pointer(out, PD))
+        return out
+
     def render_views(self, views, width, height, max_bounces, samples=1, seed=0x52505447, seed_stride=0,
                      sample_index_base=0, exposure_value=0.0, flags=0, out=None, seeds=None):
         """A batch of frames in one call (rptgpu_render_views) -> (n, height, width, 3): per pixel the mean
@@ -479,11 +503,43 @@ class GpuScene:
         a = _abi.RptLightmapArrays()
         a.struct_size, a.reserved = C.sizeof(a), 0
         m = _marshal.pick(self.device, triangles, uvs, normals)
+        n, pos, nrm, uv = self._lightmap_triangles(m, triangles, normals, uvs, who)
+        out = m.fill(a, _marshal.layout(_marshal.LIGHTMAP_CHANNELS, q.channels, (q.height, q.width)), who)
+        PD = C.POINTER(C.c_double)
+        self._call("rptgpu_bake_lightmap", m, n, m.pointer(pos, PD), m.pointer(nrm, PD), m.pointer(uv, PD), C.byref(q), C.byref(a))
+        return out
+
+    def bake_lightmap_direct(self, triangles, uvs, width, height, *, normals=None, samples, seed, offset=0.0, dilate=0,
+                             stream_base=0, sample_index_base=0, flags=0):
+        """The direct light of a lightmap, baked on the device (rptgpu_bake_lightmap_direct) -> (height,
+        width, 3) float64: at every texel bake_lightmap owns, bake_direct's result at that texel's gather point and normal
+        from stream id stream_base + y * width + x; +0.0 where nobody owns a texel; gutters filled by `dilate` rounds.
+        triangles, normals, uvs, offset: bake_lightmap's.  numpy arrays go through host memory; torch tensors on the
+        handle's device are read where they lie (rptgpu_bake_lightmap_direct_device) and the result is a new tensor there."""
+        if not _abi.direct_supported(self.lib):
+            raise _abi.RptGpuError(_abi.RPTGPU_E_INVALID_ARGUMENT, "this library does not export rptgpu_bake_lightmap_direct")
+        who = "bake_lightmap_direct"
+        q = _abi.RptLightmapQuery()
+        q.struct_size = C.sizeof(_abi.RptLightmapQuery)
+        q.width, q.height, q.samples = int(width), int(height), int(samples)
+        q.dilate, q.stream_base, q.seed, q.sample_index_base = int(dilate), int(stream_base), int(seed), int(sample_index_base)
+        q.offset, q.precision_mode, q.flags = float(offset), _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        m = _marshal.pick(self.device, triangles, uvs, normals)
+        n, pos, nrm, uv = self._lightmap_triangles(m, triangles, normals, uvs, who)
+        out = m.result(None, (q.height, q.width, 3), np.float64, who, "out")
+        PD = C.POINTER(C.c_double)
+        self._call("rptgpu_bake_lightmap_direct", m, n, m.pointer(pos, PD), m.pointer(nrm, PD), m.pointer(uv, PD), C.byref(q),
+                   m.pointer(out, PD))
+        return out
+
+    @staticmethod
+    def _lightmap_triangles(m, triangles, normals, uvs, who):
+        """the lightmap calls' common half: the triangles checked -> (n, positions, normals or None, uvs)"""
         if not hasattr(triangles, "shape"):
             triangles = np.asarray(triangles)
         if len(triangles.shape) == 2:  # a Mesh's rows: v1 v2 v3 n1 n2 n3
             if normals is not None:
-                raise ValueError("bake_lightmap: (n, 18) triangle rows hold their normals; pass no normals beside them")
+                raise ValueError("%s: (n, 18) triangle rows hold their normals; pass no normals beside them" % who)
             rows = m.records(triangles, (18,), who, "triangles")
             pos, nrm = rows[:, :9].reshape(-1, 3, 3), rows[:, 9:].reshape(-1, 3, 3)
         else:
@@ -492,10 +548,7 @@ class GpuScene:
         n = int(pos.shape[0])
         nrm = m.counted(m.records(nrm, (3, 3), who, "normals"), n, who, "normals", "triangles") if nrm is not None else None
         uv = m.counted(m.records(uvs, (3, 2), who, "uvs"), n, who, "uvs", "triangles")
-        out = m.fill(a, _marshal.layout(_marshal.LIGHTMAP_CHANNELS, q.channels, (q.height, q.width)), who)
-        PD = C.POINTER(C.c_double)
-        self._call("rptgpu_bake_lightmap", m, n, m.pointer(pos, PD), m.pointer(nrm, PD), m.pointer(uv, PD), C.byref(q), C.byref(a))
-        return out
+        return n, pos, nrm, uv
 
     def _ray_records(self, who, origins, dirs, q, a, table):
         """first_hits' and hit_surface's common half: the rays checked, one new array per channel that q names with its

@@ -608,6 +608,25 @@ pub mod ffi {
         pub fn rptgpu_trace_vertices(h: *mut rptgpu_scene, n: u64, origins: *const f64, dirs: *const f64, streams: *const u32, q: *const RptVertexQuery, out: *const RptVertexArrays) -> c_int;
         pub fn rptgpu_trace_vertices_device(h: *mut rptgpu_scene, n: u64, d_origins: *const c_void, d_dirs: *const c_void, d_streams: *const c_void, q: *const RptVertexQuery, d_out: *const RptVertexArrays, stream: *mut c_void) -> c_int;
     }
+
+    // include/rpt_gpu_direct.h: direct light (next-event estimation) at the caller's points — optional additions within ABI 7
+    // (a library without them is detected with dlsym("rptgpu_bake_direct"); this crate links them like the rest).  The
+    // lightmap form, rptgpu_bake_lightmap_direct, takes an RptLightmapQuery: like rptgpu_bake_lightmap it is not bound here
+    /// `RptDirectQuery` (the parameters of `rptgpu_bake_direct`, include/rpt_gpu_direct.h; detected by symbol within ABI 7)
+    #[repr(C)]
+    #[derive(Clone, Copy, Debug, Default)]
+    pub struct RptDirectQuery {
+        pub struct_size: u32,
+        pub samples: u32,
+        pub seed: u64,
+        pub sample_index_base: u64,
+        pub precision_mode: u32,
+        pub flags: u32,
+    }
+    extern "C" {
+        pub fn rptgpu_bake_direct(h: *mut rptgpu_scene, n: u64, positions: *const f64, normals: *const f64, streams: *const u32, q: *const RptDirectQuery, out: *mut f64) -> c_int;
+        pub fn rptgpu_bake_direct_device(h: *mut rptgpu_scene, n: u64, d_positions: *const c_void, d_normals: *const c_void, d_streams: *const c_void, q: *const RptDirectQuery, d_out: *mut c_void, stream: *mut c_void) -> c_int;
+    }
 }
 
 pub use ffi::{RptCamera, RptMaterial, RptRenderParams, RptSceneOptions, RptStats, RptTransform, RptTriangle};
@@ -965,6 +984,7 @@ mod layout_tests {
         assert_eq!(size_of::<RptProbeQuery>(), 40);
         assert_eq!(size_of::<RptVisibilityQuery>(), 16);
         assert_eq!(size_of::<RptAoQuery>(), 40);
+        assert_eq!(size_of::<RptDirectQuery>(), 32);
         assert_eq!(size_of::<RptView>(), 112);
         assert_eq!(size_of::<RptViewQuery>(), 64);
         assert_eq!(size_of::<RptHitQuery>(), 16);
