@@ -1064,6 +1064,8 @@ const char* rptgpu_kernel_name(int k);
 #include "rpt_gpu_hit_surface.h"
 /* ---- ... and a lightmap baked from a mesh's UV charts: irradiance and ambient occlusion per texel ---- */
 #include "rpt_gpu_lightmap.h"
+/* ---- ... and such a map denoised with a filter guided by its own owner, position and normal channels ---- */
+#include "rpt_gpu_lightmap_filter.h"
 /* ---- ... and direct lighting (next-event estimation) at caller points and lightmap texels ---- */
 #include "rpt_gpu_direct.h"
 

@@ -288,6 +288,20 @@ class RptLightmapArrays(C.Structure):
                 ("normal", C.POINTER(f64))]
 
 
+class RptLightmapFilter(C.Structure):
+    """include/rpt_gpu_lightmap_filter.h RptLightmapFilter (rptgpu_filter_lightmap's parameters)."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("words", C.c_uint32),
+                ("levels", C.c_uint32), ("dilate", C.c_uint32), ("sigma_normal", f64), ("sigma_plane", f64),
+                ("sigma_distance", f64), ("sigma_color", f64)]
+
+
+class RptLightmapFilterArrays(C.Structure):
+    """include/rpt_gpu_lightmap_filter.h RptLightmapFilterArrays (rptgpu_filter_lightmap's arrays, host or device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("owner", C.POINTER(C.c_int32)), ("position", C.POINTER(f64)),
+                ("normal", C.POINTER(f64)), ("values", C.POINTER(f64)), ("variance", C.POINTER(f64)), ("out", C.POINTER(f64)),
+                ("out_variance", C.POINTER(f64))]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -422,6 +436,11 @@ LIGHTMAP_SYMBOLS = [
     ("rptgpu_bake_lightmap_device", C.c_int,
      [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptLightmapQuery), C.POINTER(RptLightmapArrays), _VP]),
 ]
+# ... and every symbol include/rpt_gpu_lightmap_filter.h declares, optional in the same way (lightmap_filter_supported())
+LIGHTMAP_FILTER_SYMBOLS = [
+    ("rptgpu_filter_lightmap", C.c_int, [_VP, C.POINTER(RptLightmapFilter), C.POINTER(RptLightmapFilterArrays)]),
+    ("rptgpu_filter_lightmap_device", C.c_int, [_VP, C.POINTER(RptLightmapFilter), C.POINTER(RptLightmapFilterArrays), _VP]),
+]
 # ... and every symbol include/rpt_gpu_direct.h declares, optional in the same way (direct_supported())
 DIRECT_SYMBOLS = [
     ("rptgpu_bake_direct", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.POINTER(C.c_uint32), C.POINTER(RptDirectQuery), _PD]),
@@ -457,11 +476,11 @@ def load_library(path=None):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
-    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS + LIGHTMAP_SYMBOLS + DIRECT_SYMBOLS:
+    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS + LIGHTMAP_SYMBOLS + LIGHTMAP_FILTER_SYMBOLS + DIRECT_SYMBOLS:
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported(), lightmap_supported(), direct_supported() say no)
+            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported(), lightmap_supported(), lightmap_filter_supported(), direct_supported() say no)
         fn.restype = restype
         fn.argtypes = argtypes
     if lib.rptgpu_abi_version() != ABI_VERSION:
@@ -519,6 +538,13 @@ def lightmap_supported(lib=None):
     caller does with dlsym: a library without them is still ABI 7."""
     lib = lib or load_library()
     return all(hasattr(lib, name) for name, _, _ in LIGHTMAP_SYMBOLS)
+
+
+def lightmap_filter_supported(lib=None):
+    """Does the library export rptgpu_filter_lightmap[_device] (include/rpt_gpu_lightmap_filter.h)?  Detected by symbol, as
+    a C caller does with dlsym: a library without them is still ABI 7."""
+    lib = lib or load_library()
+    return all(hasattr(lib, name) for name, _, _ in LIGHTMAP_FILTER_SYMBOLS)
 
 
 def direct_supported(lib=None):

@@ -39,6 +39,9 @@
 //                    texels the interpolation and compaction, the probe and AO calls' own device work over the compacted
 //                    points (enqueue_probes, enqueue_ao), the scatter; the dilation over the whole map (the kernels:
 //                    kernels_lightmap.hip; the sizes: lightmap_plan.h)
+//   api_lightmap_filter.cpp rptgpu_filter_lightmap[_device]: a baked map through the geometry-guided a-trous filter — the
+//                    guides as columns, one launch per level, the columns written back, then api_lightmap.cpp's dilation
+//                    rounds (the kernels: kernels_lightmap_filter.hip; the sizes: lightmap_filter_plan.h)
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -73,6 +76,8 @@
 #include "surface_plan.h"
 #include "lightmap_plan.h"
 #include "lightmap.h"
+#include "lightmap_filter_plan.h"
+#include "lightmap_filter.h"
 
 namespace rptapi {
 
@@ -215,6 +220,9 @@ struct rptgpu_scene {
   DevBuf<uint32_t> lm_owner, lm_large, lm_scan;
   DevBuf<uint8_t> lm_scan_tmp, lm_filled;
   DevBuf<double> lm_compact, lm_pong, lm_tris, lm_stage;
+  // rptgpu_filter_lightmap (api_lightmap_filter.cpp): the filter's columns with the dilation's second copy inside them
+  // (lightmap_filter_plan.h workspace) and a host caller's arrays, staged whole (stage)
+  DevBuf<double> lf_ws, lf_stage;
   DevBuf<double> vertices_out;         // rptgpu_trace_vertices: a piece of a host caller's records, the named channels back to back (api_vertices.cpp)
   DevBuf<rptdev::View> view_recs;     // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<uint64_t> view_seeds;         // ... their seeds, when the views have seeds of their own,

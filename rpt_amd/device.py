@@ -532,6 +532,54 @@ class GpuScene:
                    m.pointer(out, PD))
         return out
 
+    def filter_lightmap(self, values, owner, position, normal, *, sigma_distance, sigma_plane, sigma_normal=0.1, levels=3,
+                        variance=None, sigma_color=2.0, dilate=0):
+        """A baked lightmap denoised on the device (rptgpu_filter_lightmap) -> `out`, shaped like `values`,
+        or (out, out_variance) when `variance` is given.  values: the UNDILATED map, (height, width, 3) float64
+        (bake_lightmap's `irradiance`, bake_lightmap_direct's result) or (height, width) (`ao`); owner (height, width) int32,
+        position and normal (height, width, 3): the same bake's channels, the filter's guides.  `levels` a-trous passes with
+        tap spacing 1, 2, 4, ... weigh a tap by exp(-e), e the sum of (1 - N_p . N_q) / sigma_normal, |N_p . (P_q - P_p)| /
+        sigma_plane and |P_q - P_p|^2 / (sigma_distance * spacing)^2 — sigma_distance in world units per texel, a few of
+        lightmap.texel_extent's — and, with `variance` (height, width), the variance of each texel's mean (lightmap.batch_variance),
+        of the squared difference of the values over sigma_color^2 times the variances' sum.  A texel nobody owns takes
+        part in nothing; `dilate` rounds of bake_lightmap's gutter fill follow.  numpy arrays go through host memory; torch
+        tensors on the handle's device are read where they lie (rptgpu_filter_lightmap_device) and the results are new
+        tensors there."""
+        if not _abi.lightmap_filter_supported(self.lib):
+            raise _abi.RptGpuError(_abi.RPTGPU_E_INVALID_ARGUMENT, "this library does not export rptgpu_filter_lightmap")
+        who = "filter_lightmap"
+        values, owner, position, normal = (x if hasattr(x, "shape") else np.asarray(x) for x in (values, owner, position, normal))
+        m = _marshal.pick(self.device, values, owner, position, normal, variance)
+        if len(owner.shape) != 2:
+            raise ValueError("%s: owner must be a (height, width) int32 array" % who)
+        height, width = int(owner.shape[0]), int(owner.shape[1])
+        words = 3 if len(values.shape) == 3 else 1
+        shape = (height, width, 3) if words == 3 else (height, width)
+        f = _abi.RptLightmapFilter()
+        f.struct_size, f.width, f.height, f.words = C.sizeof(f), width, height, words
+        f.levels, f.dilate = int(levels), int(dilate)
+        f.sigma_normal, f.sigma_plane, f.sigma_distance = float(sigma_normal), float(sigma_plane), float(sigma_distance)
+        f.sigma_color = float(sigma_color)
+        a = _abi.RptLightmapFilterArrays()
+        a.struct_size, a.reserved = C.sizeof(a), 0
+        # (m.result with an array: held to that shape, dtype and C order, and returned as it is)
+        ins = {"owner": m.result(owner, (height, width), np.int32, who, "owner"),
+               "position": m.result(position, (height, width, 3), np.float64, who, "position"),
+               "normal": m.result(normal, (height, width, 3), np.float64, who, "normal"),
+               "values": m.result(values, shape, np.float64, who, "values")}
+        outs = {"out": m.room(shape, np.float64)}
+        if variance is not None:
+            ins["variance"] = m.result(variance, (height, width), np.float64, who, "variance")
+            outs["out_variance"] = m.room((height, width), np.float64)
+        types = dict(_abi.RptLightmapFilterArrays._fields_)
+        for name, arr in ins.items():
+            setattr(a, name, m.field(arr, types[name]))
+        for name, (view, room) in outs.items():
+            setattr(a, name, m.field(room, types[name]))
+        self._call("rptgpu_filter_lightmap", m, C.byref(f), C.byref(a))
+        out = outs["out"][0]
+        return (out, outs["out_variance"][0]) if variance is not None else out
+
     @staticmethod
     def _lightmap_triangles(m, triangles, normals, uvs, who):
         """the lightmap calls' common half: the triangles checked -> (n, positions, normals or None, uvs)"""

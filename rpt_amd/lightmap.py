@@ -1,5 +1,6 @@
 """What a caller of GpuScene.bake_lightmap needs beside it (include/rpt_gpu_lightmap.h): the texture
-coordinates of an OBJ's triangles, in the order load_obj makes the triangles, and a bake turned into bytes to look at.
+coordinates of an OBJ's triangles, in the order load_obj makes the triangles, a bake turned into bytes to look at, and what
+GpuScene.filter_lightmap wants beside a bake: the world size of a texel and a variance from several bakes.
 numpy only."""
 import numpy as np
 
@@ -39,6 +40,41 @@ def load_obj_texcoords(file):
     finally:
         if own:
             f.close()
+
+
+def texel_extent(position, owner):
+    """The median world distance between horizontally adjacent owned texels of a bake: `position` (H, W, 3) and `owner`
+    (H, W) of bake_lightmap.  GpuScene.filter_lightmap's sigma_distance is a few of these.  ValueError when no two owned
+    texels are neighbours in a row."""
+    position = np.asarray(position, dtype=np.float64)
+    owned = np.asarray(owner) >= 0
+    pair = owned[:, 1:] & owned[:, :-1]
+    if not pair.any():
+        raise ValueError("texel_extent: no two owned texels are neighbours in a row")
+    d = position[:, 1:] - position[:, :-1]
+    return float(np.median(np.sqrt((d * d).sum(axis=-1))[pair]))
+
+
+def batch_variance(bakes):
+    """-> (mean, variance): from B >= 2 bakes of one map, each (H, W) or (H, W, 3) — the same call with
+    sample_index_base advanced by `samples` from bake to bake, so that their samples are independent —, the mean over the
+    bakes per texel and the variance of THAT MEAN per texel, summed over the components: Welford's recurrence (the device
+    Buffer's), M2 / (B - 1) / B.  What GpuScene.filter_lightmap takes as `values` and `variance`."""
+    bakes = [np.asarray(b, dtype=np.float64) for b in bakes]
+    if len(bakes) < 2:
+        raise ValueError("batch_variance: a variance takes two bakes at least")
+    flat = bakes[0].ndim == 2
+    mean = np.zeros(bakes[0].shape if not flat else bakes[0].shape + (1,))
+    m2 = np.zeros(mean.shape[:2])
+    with np.errstate(all="ignore"):
+        for k, b in enumerate(bakes):
+            x = b.reshape(mean.shape)
+            d = x - mean
+            mean = mean + d / np.float64(k + 1)
+            m2 = m2 + (d * (x - mean)).sum(axis=-1)
+        n = np.float64(len(bakes))
+        variance = (m2 / (n - 1.0)) / n
+    return (mean[..., 0] if flat else mean), variance
 
 
 def to_rgb8(irradiance, albedo=(1.0, 1.0, 1.0), exposure=0.0):
