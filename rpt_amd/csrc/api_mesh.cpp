@@ -72,6 +72,10 @@ int set_mesh(rptgpu_scene* h, uint32_t object, uint64_t n, const void* tris, boo
     for (size_t i = 0; i < count; i++) {
       if (!uses_tree(i)) continue;
       set_object_bounds(insts[i], geom[i], tr);
+      // the shadow window's mark (scene_plan.h axis_flat_mesh) speaks of the triangles at creation: a deformed mesh loses
+      // it.  (Only the flat path kernel reads it, and refuse_all_flat keeps this call off its handles: the mark of a
+      // scene that did not fit the kernel's LDS is what is cleared here, so that no record keeps a statement that is stale.)
+      insts[i].plane_idx &= ~RPT_PLANE_AXIS_FLAT;
       if (count <= 64) geom[i].sliver = any_sliver != 0; // (as flatten_scene: read by the object filter only, which takes <= 64 objects)
     }
     rpthost::ObjectBounds ob;

@@ -192,19 +192,20 @@ void ensure_workspace(rptgpu_scene* h, uint64_t cap, uint64_t rec_cols) {
 // ran (lane time / wave time, of 64), and for loop bodies the iteration count and the lanes per iteration.  One line
 // per slot that was used, machine-readable enough to be committed under profiles/ as it is.
 void print_prof(const KernelTable* kt, const char* what) {
-  static const char* const NAMES[29] = {
+  static const char* const NAMES[30] = {
       "tree_trace refill", "tree_trace node steps", "tree_trace box tests", "tree_trace pop", "tree_trace write-out",
       "tree_trace exact tests", "in-kernel node step", "in-kernel box batch", "in-kernel child test",
       "in-kernel triangle batch", "in-kernel object", "paths fetch", "paths raygen", "paths closest_hit",
       "paths illuminate", "paths visible", "paths nee_bsdf", "paths sample_f", "paths bsdf", "paths record",
       "paths fold+store", "flat candidate walk", "fold iteration", "rejection round", "paths fused query",
-      "paths draws", "paths shade block", "pre-trace pass", "pre-trace pass, cubes skipped"};
-  unsigned long long t[4][29];
+      "paths draws", "paths shade block", "pre-trace pass", "pre-trace pass, cubes skipped",
+      "fused query, shadow leaf test"};
+  unsigned long long t[4][30];
   if (!kt->read_prof(t)) return;
   unsigned long long tot = 0;
-  for (int i = 0; i < 29; i++) tot += t[0][i];
+  for (int i = 0; i < 30; i++) tot += t[0][i];
   std::fprintf(stderr, "prof[%s] %-28s %8s %10s %14s %10s\n", what, "phase", "time %", "lanes/64", "iterations", "lanes/64");
-  for (int i = 0; i < 29; i++) {
+  for (int i = 0; i < 30; i++) {
     if (!t[0][i] && !t[2][i]) continue;
     char a[32] = "-", b[32] = "-", c[32] = "-", d[32] = "-";
     if (t[0][i]) {

@@ -141,6 +141,15 @@ rptscene::FlatInput flat_input(const rpthost::FlatScene& fs, const RptSceneOptio
   for (int i = 0; i < fs.num_objects; i++) {
     rptscene::FlatObject o{fs.insts[i].kind, fs.insts[i].has_xf, {}};
     std::memcpy(o.bounds, fs.insts[i].bounds, sizeof o.bounds);
+    if (o.kind == RPT_SHAPE_MESH) { // a single-leaf tree's records, for the shadow window's mark (axis_flat_mesh)
+      const rptdev::Tree& tr = fs.trees[fs.insts[i].tree];
+      o.single_leaf = tr.root_leaf != 0;
+      const size_t first = (size_t)tr.ref_base + tr.root_first; // (kernels/shapes.inc kd_leaf: lrec + ref_base + the leaf's first entry)
+      if (o.single_leaf && first + (tr.root_leaf - 1u) <= fs.lrec.size()) {
+        o.recs = fs.lrec.data() + first;
+        o.n_recs = tr.root_leaf - 1u;
+      }
+    }
     in.objects.push_back(o);
   }
   in.n_lights = fs.lights.size();

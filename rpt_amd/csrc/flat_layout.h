@@ -48,6 +48,36 @@
 #ifndef RPT_SCENE_CONSTS
 #define RPT_SCENE_CONSTS 7
 #endif
+// RPT_SHADOW_WINDOW=1: in the two-ray query (kernels/paths_flat.inc flat_query2) the shadow ray drops, right after a run's
+// slab tests, every candidate that is an AXIS-FLAT plane-table user (scene_plan.h axis_flat_mesh: a single-leaf untransformed
+// mesh that lies in one axis plane: the walls of C2) whose slab entry mm lies beyond the light:
+// rpt_shadow_window_beyond(mm, t_stop) below, which implies mm > t_stop * (1 + 2^-40).  Such an object can only be hit
+// beyond t_stop, which never changes `rts > t_stop` (the proof stands at scene_plan.h axis_flat_mesh).  The host marks the
+// objects in bit 24 of Inst::plane_idx, above the six 4-bit slots.  0: every candidate is walked, the parent's kernels
+// instruction for instruction (A/B builds)
+#ifndef RPT_SHADOW_WINDOW
+#define RPT_SHADOW_WINDOW 1
+#endif
+#define RPT_PLANE_AXIS_FLAT (1u << 24) // Inst::plane_idx: the object is axis-flat
+#if defined(__HIPCC__)
+#define RPT_LAYOUT_FN __host__ __device__ inline
+#else
+#define RPT_LAYOUT_FN inline
+#endif
+// The rule's comparison, one copy for the kernel and the host check (tests/cpp/shadow_window_check.cpp): mm, which is
+// max(q, EPSILON) and so a positive double or +inf, lies more than 2^13 representable doubles above t_stop.  Doubles of one
+// sign are ordered like their bit patterns, and 2^13 steps up from a normal t_stop > 0 are at least t_stop * 2^-40, so true
+// implies  mm > t_stop * (1 + 2^-40)  for every t_stop that is not a NaN: a t_stop that is subnormal, a zero or negative is
+// below EPSILON <= mm; t_stop = +inf and a NaN with a clear sign bit have the larger pattern (false); for DBL_MAX, true needs
+// a pattern above +inf's.  A NaN t_stop with its sign bit set may give true: `rts > t_stop` is then false whatever rts is.
+// The comparison is made on the patterns because the product t_stop * (1 + 2^-40), one more double alive across the run's
+// slab tests, cost the extended views kernel 24 VGPR spills (profiles/shadow_window_ab.txt); this form keeps no value.
+RPT_LAYOUT_FN bool rpt_shadow_window_beyond(double mm, double t_stop) {
+  uint64_t a, b;
+  __builtin_memcpy(&a, &mm, 8);
+  __builtin_memcpy(&b, &t_stop, 8);
+  return (int64_t)(a - b) > (int64_t)8192;
+}
 #define RPT_MAT_CONSTS_BYTES 88u   // per object (kernels/paths_consts.inc MatConsts)
 #define RPT_CUBE_NORMALS_BYTES 144u // per cube of a two-cube block: [face][3] doubles
 #define RPT_PATHS_STASH_LDS 4864u

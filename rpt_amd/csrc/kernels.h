@@ -197,7 +197,7 @@ struct KernelTable {
                           uint64_t npix, double* out);
   // -DRPT_PROF builds: the per-phase table of kernels/prof.inc since the last call ([0] wave cycles, [1] lane cycles,
   // [2] wave iterations, [3] lane iterations); false in regular builds
-  bool (*read_prof)(unsigned long long out[4][29]);
+  bool (*read_prof)(unsigned long long out[4][30]);
   // in-kernel-traversal scenes: the next depth's paths sorted by ray key into the current state arrays (kernels/wavefront.inc)
   void (*path_reorder)(hipStream_t, const rptdev::PathState&, uint32_t n, bool sorted, const SortBufs* sort, uint32_t* order);
   // first-hit feature buffers (kernels/aov.inc).  aov: camera ray, closest hit and the ordered fold of `iterations` samples

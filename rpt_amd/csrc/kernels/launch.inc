@@ -362,8 +362,8 @@ void launch_denoise_views_finish(hipStream_t st, const double* c_in, uint64_t st
 
 // debug builds with -DRPT_PROF: the per-phase table of kernels/prof.inc accumulated so far (and reset):
 // out[0] wave cycles, [1] lane cycles, [2] wave iterations, [3] lane iterations, PROF_SLOTS slots each
-bool read_prof(unsigned long long out[4][29]) {
-  static_assert(PROF_SLOTS == 29, "kernels.h declares the table with 29 slots");
+bool read_prof(unsigned long long out[4][30]) {
+  static_assert(PROF_SLOTS == 30, "kernels.h declares the table with 30 slots");
 #ifdef RPT_PROF
   static unsigned long long zero[4][PROF_SLOTS];
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof zero) != hipSuccess) return false;

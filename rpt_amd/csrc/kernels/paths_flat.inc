@@ -70,6 +70,23 @@ RPT_DEV uint32_t run_slabs(const Scene& sc, int i, const double* qt, double rt, 
   }
   return cand;
 }
+// The shadow ray's window (RPT_SHADOW_WINDOW, flat_layout.h): of the run's N table users, those that are axis-flat
+// (RPT_PLANE_AXIS_FLAT in plane_idx: the host verified, bit for bit, that the mesh lies in one axis plane — scene_plan.h
+// axis_flat_mesh, with the proof) and whose slab entry m[k] lies beyond the light (rpt_shadow_window_beyond: more than 2^13
+// doubles above t_stop, hence m[k] > t_stop * (1 + 2^-40)).  Every time such an object's leaf can accept is
+// >= m[k] * (1 - 2^-50) > t_stop, so the shadow ray leaves it out: rts could only become a value above t_stop, and
+// `rts > t_stop` is all the shadow slot returns.  The marks are wave-uniform scalars of records run_slabs has just read,
+// m[] is run_slabs' own, and the comparison keeps no value alive.  0 when the switch is off
+template <int N>
+RPT_DEV uint32_t run_beyond(const Scene& sc, int i, const double (&m)[FLAT_RUN], double t_stop) {
+  uint32_t drop = 0;
+  if constexpr (RPT_SHADOW_WINDOW != 0) {
+#pragma unroll
+    for (int k = 0; k < N; k++)
+      if ((cinst(sc, i + k).plane_idx & RPT_PLANE_AXIS_FLAT) != 0u && rpt_shadow_window_beyond(m[k], t_stop)) drop |= 1u << k;
+  }
+  return drop;
+}
 // run_slabs<len> of one ray, or of two side by side: the statement(s) with LEN = the run's length as a compile-time
 // constant — one straight-line block per run length, no slot is evaluated in vain.  (A macro: the same switch as a
 // function over a lambda cost the fused kernels SGPR spills, profiles/paths_split_resources.txt.)
@@ -427,7 +444,8 @@ RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, 
       const int len = (int)in.plane_use;
       const double* qtb = fl->qtab + lane;
       const double* qts = qtb + nq * 64u;
-      RUN_SLABS_LEN(len, cb = run_slabs<LEN>(sc, i, qtb, rtb, mb); cs = run_slabs<LEN>(sc, i, qts, rts, ms))
+      RUN_SLABS_LEN(len, cb = run_slabs<LEN>(sc, i, qtb, rtb, mb); cs = run_slabs<LEN>(sc, i, qts, rts, ms);
+                    cs &= ~run_beyond<LEN>(sc, i, ms, t_stop)) // (flat walls beyond the light)
       if (rts <= t_stop) cs = 0u; // (the shadow ray is blocked already)
       while (__ballot((cb | cs) != 0u) != 0ull) {
         PROF_COUNT(PF_P_CAND);
@@ -442,6 +460,7 @@ RPT_DEV int flat_query2(const Scene& sc, const FlatLds* fl, D3 o, D3 db, D3 ds, 
           cs &= cs - 1u;
           const double mt = RUN_PICK(ms, k);
           if (!(mt > rts)) {
+            PROF_COUNT(PF_P_SHLEAF);
             D3 srn = mk(0, 0, 0);
             flat_leaf_test<true, false, true>(sc, fl, i + k, o, ds, t_stop, rts, srn);
             if (rts <= t_stop) cs = 0u;

@@ -11,7 +11,7 @@
 // The first active lane does the bookkeeping (a handful of DS operations), so a mark may sit in divergent code.
 // Regular builds compile all of this to nothing.
 #ifdef RPT_PROF
-constexpr int PROF_SLOTS = 29;
+constexpr int PROF_SLOTS = 30;
 struct ProfLds {
   long long mark[4];
   unsigned long long wt[4][PROF_SLOTS], lt[4][PROF_SLOTS]; // wave cycles, lane cycles
@@ -65,7 +65,7 @@ __device__ __forceinline__ void prof_flush() { // at the end of the kernel, all 
 #define PROF_COUNT(i) prof_count(i)
 #define PROF_FLUSH() prof_flush()
 #else
-constexpr int PROF_SLOTS = 29;
+constexpr int PROF_SLOTS = 30;
 #define PROF_INIT() do { } while (0)
 #define PROF_PHASE(i) do { } while (0)
 #define PROF_COUNT(i) do { } while (0)
@@ -87,5 +87,7 @@ enum {
   // its fast shading form (RPT_SHADE_SPLIT): a hit's draws, the straight-line shading block
   PF_P_DRAWS = 25, PF_P_SHADE = 26,
   // its pre-trace pass (RPT_PRETRACE_CULL; iteration counts only): passes run, passes that skipped the two-cube block
-  PF_P_PRETRACE = 27, PF_P_PRECULL = 28
+  PF_P_PRETRACE = 27, PF_P_PRECULL = 28,
+  // the shadow ray's leaf tests in the table runs of flat_query2 (iteration counts only; RPT_SHADOW_WINDOW drops the ones beyond the light)
+  PF_P_SHLEAF = 29
 };

@@ -156,9 +156,65 @@ template <class Use> uint64_t plane_users(size_t n, Use plane_use) {
 // fill_object_boxes: unbounded, not finite, sliver meshes, ill-conditioned placements)
 inline uint64_t cull_always(uint64_t obj_always, uint64_t users, size_t n) { return (obj_always | users) & every_object(n); }
 
+// ---- axis-flat meshes: the shadow ray's window in the two-ray query (RPT_SHADOW_WINDOW, kernels/paths_flat.inc flat_query2)
+//
+// An object is AXIS-FLAT when all of this holds, bit for bit:
+//   (1) it is an untransformed mesh whose tree is a single leaf, and `recs` are all n >= 1 of that leaf's records;
+//   (2) on one axis k, bounds[k] and bounds[3 + k] are the same finite double c;
+//   (3) every record has v1[k] == c (the same bits), pn zero (either sign) on the two other axes, pn[k] finite with
+//       2^-100 <= |pn[k]| <= 2^100, and v1 finite on all three axes.
+// What follows for a ray (o, d), with a = fl(c - o_k), q = fl(a / d_k) the plane table's quotient of the object's slab on
+// axis k, and Triangle::intersect's time = fl(dot(pn, v1 - o) / dot(pn, d)) (kernels/shapes.inc tri_plane, built with
+// -ffp-contract=off, mesh.rs:50-58):
+//   * both dot products add two zero products to the axis' own: time = fl(fl(pn_k * a) / fl(pn_k * d_k)).  (A product
+//     0 * x is a zero unless x is infinite or NaN; then time is NaN and the test accepts nothing.)
+//   * an ACCEPT needs |fl(pn_k * d_k)| >= 1e-8 and time >= EPSILON (shapes.inc tri_accept).  With neither product
+//     overflowing or underflowing, time and q are the exact a / d_k under three and one roundings: time >= q * (1 - u)^2
+//     / (1 + u)^2 > q * (1 - 2^-50) for q > 0, u = 2^-53.  fl(pn_k * a) underflows: |time| < 2^-1022 / 1e-8 < EPSILON, no
+//     accept.  fl(pn_k * d_k) underflows: below 1e-8, no accept; it overflows: time is a zero, no accept.  fl(pn_k * a)
+//     overflows: time is infinite, and `time >= rt` rejects +inf as `time < t_min` does -inf.  q overflows to +inf where
+//     time does not: then time > DBL_MAX * (1 - 2^-50), and the rule below drops the candidate only if t_stop lies more
+//     than 2^13 doubles below +inf, that is t_stop <= DBL_MAX * (1 - 2^-41) < time.
+//   * a slab candidate of such an object has b_min == b_max == q (run_slabs: the window is inside [q, q] and not empty), so
+//     its mm = max(q, EPSILON), and every time the object's leaf can accept has  time >= mm * (1 - 2^-50):  for
+//     q <= EPSILON that is time >= EPSILON.  (q NaN, 0 / 0: time is NaN as well, nothing is accepted.)
+// The rule (flat_query2): the shadow ray drops a candidate of an axis-flat object when mm lies more than 2^13 doubles above
+// t_stop (flat_layout.h rpt_shadow_window_beyond, which says why that implies  mm > t_stop * (1 + 2^-40)  for every t_stop
+// but a NaN).  Then every time it could accept is > t_stop * (1 + 2^-40) * (1 - 2^-50) > t_stop: the object could only set
+// rts to a value above t_stop.  That changes nothing the query returns, which is `rts > t_stop` alone: an object at or
+// before t_stop is accepted with or without the dropped one in front of it (an accept needs time < rts, and rts > t_stop
+// either way), one beyond t_stop leaves rts > t_stop, and the early exits test rts <= t_stop.  mm is never a NaN (fmax
+// with EPSILON), and under a NaN t_stop `rts > t_stop` is false whatever was dropped.  A directional light's
+// t_stop = DBL_MAX has nothing 2^13 doubles above it: no drop.  A quad in the light's own plane (the light's shape where
+// it is an object too) has q within a few ulp of t_stop, far inside the margin: it is never dropped, and the reference's
+// behaviour at the light stays what it is.
+// An object that fails any part of (1)-(3) is simply not marked, and the exact test runs as before.
+inline bool axis_flat_mesh(int32_t kind, int32_t has_xf, bool single_leaf, const double bounds[6], const rptdev::TriX* recs, size_t n) {
+  if (kind != RPT_SHAPE_MESH || has_xf || !single_leaf || !recs || n == 0) return false;
+  auto bits = [](double v) { uint64_t b; std::memcpy(&b, &v, 8); return b; };
+  auto finite = [&](double v) { return ((bits(v) >> 52) & 0x7ffu) != 0x7ffu; };
+  for (int k = 0; k < 3; k++) {
+    const double c = bounds[k];
+    if (bits(c) != bits(bounds[3 + k]) || !finite(c)) continue;
+    bool ok = true;
+    for (size_t j = 0; j < n && ok; j++) {
+      const rptdev::TriX& t = recs[j];
+      const double p = t.pn[k] < 0.0 ? -t.pn[k] : t.pn[k];
+      ok = bits(t.v1[k]) == bits(c) && t.pn[(k + 1) % 3] == 0.0 && t.pn[(k + 2) % 3] == 0.0 && finite(t.pn[k]) &&
+           p >= 0x1p-100 && p <= 0x1p100 && finite(t.v1[0]) && finite(t.v1[1]) && finite(t.v1[2]);
+    }
+    if (ok) return true;
+  }
+  return false;
+}
+
 struct FlatObject {
   int32_t kind, has_xf; // Inst's
   double bounds[6];     // MESH: Inst::bounds
+  // MESH: the tree is one leaf, and its records (FlatScene::lrec from Tree::ref_base + root_first on) — what axis_flat_mesh reads
+  bool single_leaf = false;
+  const rptdev::TriX* recs = nullptr;
+  size_t n_recs = 0;
 };
 struct FlatInput {
   uint64_t n_refs = 0, n_tris = 0;
@@ -248,6 +304,8 @@ inline FlatPlan plan_flat(const FlatInput& in) {
         const uint32_t sl = (pl.plane_idx[i] >> (4 * k)) & 15u;
         packed |= (base[sl >> 2] + (sl & 3u)) << (4 * k);
       }
+      const FlatObject& o = in.objects[i]; // (above the slots' 24 bits: the shadow window's mark, axis_flat_mesh)
+      if (axis_flat_mesh(o.kind, o.has_xf, o.single_leaf, o.bounds, o.recs, o.n_recs)) packed |= RPT_PLANE_AXIS_FLAT;
       pl.plane_idx[i] = packed;
     }
     const uint64_t qtab_bytes = (uint64_t)(cnt[0] + cnt[1] + cnt[2]) * 64 * sizeof(double);
