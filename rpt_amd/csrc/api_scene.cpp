@@ -351,6 +351,21 @@ void rptgpu_scene_destroy(rptgpu_scene* h) { delete h; }
 //   * rptgpu_render_views_denoised — both of the above into vd_* arrays sized per call;
 //   * rptgpu_buffer_features, _denoise, _sample_adaptive — a Buffer renders through the handle as it is at the call: on a flat
 //     scene the path kernel with the filter's boxes, grid and obj_always above.
+// ... and of the entry points added after those (tests/test_gpu_update_newer.py holds each to a fresh handle's bits over the
+// same cases, warm before every update; none needed a change):
+//   * rptgpu_hit_surface — rptgpu_first_hits' query, then rpt_hit_surface on columns of its own (surf_cols, surf_defer /
+//     surf_frame).  They are sized from gen_levels, which swap_spare raises with a deeper tree: ensure_surface_columns compares
+//     per call and makes them again, so no stale flag is needed; the walk reads insts, trees and lrec through dscene;
+//   * rptgpu_bake_lightmap — the raster reads the caller's triangles only (its raw channels do not change with the scene); the
+//     gathers run rptgpu_bake_probes' and rptgpu_bake_ao's drivers over the compacted arrays the handle keeps (lm_compact,
+//     lm_scan): written per call, sized by the map, and the drivers' workspace follows ws_stale like every other;
+//   * rptgpu_bake_direct, rptgpu_bake_lightmap_direct — lights and num_shadow_lights per call; the shadow queues lie in the
+//     workspace (Occlusion::workspace: ensure_workspace, so ws_stale) and are walked by the route has_deep picks at the call;
+//   * rptgpu_filter_lightmap — reads its arguments and scratch of its own (lf_stage, lf_ws, sized per call): nothing of the
+//     scene, and none of the arrays a rebuild swaps;
+//   * RPT_FLAG_RAYS_PERSISTENT (rays, probes), RPT_FLAG_VIEWS_PERSISTENT, RPT_FLAG_VERTICES_PERSISTENT — piece_persistent reads
+//     tree_kids per call: once reroute_object has raised it (a rebuilt tree beyond fast_max_depth) the request is dropped and
+//     the wavefront pipeline runs, as on a fresh handle of that scene; tree_kids never falls, so it stays dropped.
 } // extern "C"
 
 namespace {

@@ -187,3 +187,90 @@ def test_the_rebuilds_take_the_routes_the_cases_say(planner):
             assert bool(r["new_gen_all"]) == (route == "per_tree" and not new["regular"]), (route, step.name, r)
             if route == "in_kernel":  # walked inside the kernels: only the one-leaf bit follows the tree
                 assert r["new_deep"] == 0 and bool(r["new_tris"] & 16) == (new["max_depth"] == 0), (step.name, r)
+
+
+# ---- the inputs of tests/test_gpu_update_newer.py: each can SEE the updates it is run across (a comparison of two wrong
+# answers that agree would pass otherwise).  Every figure is the oracle's and is printed (-rP)
+MOVING = [n for n in C.NAMES if C.cases()[n].moves]
+
+
+def test_the_chart_owns_and_leaves_texels():
+    import lightmap_model
+    for name in C.NAMES:
+        tris, uvs, w, h, offset = C.chart(name)
+        assert tris.shape == (2, 3, 3) and uvs.shape == (2, 3, 2) and (w, h) == (13, 7) == (C.LM_W, C.LM_H)
+        assert not tris.flags.writeable and not uvs.flags.writeable
+        lo, hi = (np.array(v) for v in C.cases()[name].aim[0])
+        v = tris.reshape(-1, 3)
+        assert (v[:, 0].min(), v[:, 0].max(), v[:, 2].min(), v[:, 2].max()) == (lo[0], hi[0], lo[2], hi[2])      # the box's x-z extent
+        assert len(set(v[:, 1].tolist())) == 1 and lo[1] < v[0, 1] < hi[1]                                        # level, inside it
+        assert offset == 1e-3 * np.abs(tris).max() > 0.0
+        raw = lightmap_model.raw(tris, None, uvs, w, h, offset=offset)
+        owned = raw["owner"] >= 0
+        assert owned.sum() >= 40 and (~owned).sum() >= 10, (name, int(owned.sum()))
+        assert (raw["owner"] == 0).sum() >= 10 and (raw["owner"] == 1).sum() >= 10                                # both triangles own some
+        assert not owned[0].any() and not owned[-1].any() and not owned[:, 0].any() and not owned[:, -1].any()   # a gutter on every side
+        assert (raw["normal"][owned] == np.array([0.0, 1.0, 0.0])).all()                                          # the normal is up
+        assert C.chart_texels(name)[1] is not None and len(C.chart_texels(name)[4]) == owned.sum()
+    assert (C.LM_SAMPLES, C.PROBE_SAMPLES, C.DIRECT_SAMPLES) == (4, 6, 5)
+    ids, base = C.streams("lights")
+    assert len(set(ids.tolist())) == C.N_RAYS and (ids != np.arange(C.N_RAYS)).all() and base == C.points("lights")[2][0] != 0
+
+
+@pytest.mark.parametrize("name", C.NAMES)
+def test_ambient_occlusion_at_the_chart_sees_every_step_that_moves_geometry(name, oracle):
+    """at max_distance = inf, the bake's first reach (the half-diagonal's figures are printed beside it): the unoccluded
+    fraction is neither 0 nor 1 at every texel, before the update and after each step, and a step that moves geometry changes
+    it on at least one texel (objects_filtered's second step takes away a sphere three units from the chart: one texel of
+    55 sees it, at inf only); lights and materials change it nowhere"""
+    c = C.cases()[name]
+    ao = C.chart_ao(name)
+    said = []
+    for step, a in ao.items():
+        differ = {far: int((a[far] != ao[None][far]).sum()) for far in ("inf", "half")}
+        said.append("%s, %s: unoccluded %.2f (inf) %.2f (half); texels that differ from the creation's: %d (inf) %d (half) of %d"
+                    % (name, step or "at creation", a["inf"].mean(), a["half"].mean(), differ["inf"], differ["half"], len(a["inf"])))
+        assert not (a["inf"] == 0.0).all() and not (a["inf"] == 1.0).all(), said[-1]
+        if step is not None:
+            assert (differ["inf"] >= 1) if c.moves else (differ["inf"] == 0 and differ["half"] == 0), said[-1]
+    assert len(ao) == len(c.steps)  # (the creation's scene and every step but the return)
+    print("\n".join(said))
+
+
+@pytest.mark.parametrize("name", C.NAMES)
+def test_the_direct_light_at_the_points_changes_where_the_table_says(name, oracle):
+    d = C.direct_at_points(name)
+    assert sorted(C.DIRECT_CHANGES[name]) == sorted(k for k in d if k is not None)
+    assert (d[None] != 0.0).any(axis=1).sum() >= 2 and (d[None] == 0.0).all(axis=1).sum() >= 2  # lit points, and dark ones
+    said = []
+    for step, want in C.DIRECT_CHANGES[name].items():
+        changed = C.share(d[None], d[step])
+        said.append("%s, %s: bake_direct changes at %.1f %% of the points; %d of 16 are lit" % (name, step, 100.0 * changed, (d[step] != 0.0).any(axis=1).sum()))
+        assert (changed > 0.0) == want, said[-1]
+    if name == "lights":
+        assert C.DIRECT_CHANGES[name] == {"moved": True}
+    if name == "materials_deeper":
+        assert C.DIRECT_CHANGES[name] == {"glass and mirror": False}  # a shadow ray stops at any object
+    print("\n".join(said))
+
+
+@pytest.mark.parametrize("name", C.MESH_CASES)
+def test_the_rays_end_on_triangles_of_the_updated_mesh(name, oracle):
+    """Every step of a mesh case is a set_mesh of object 0, the return to the knot too, and after each the GPU test holds
+    hit_surface's named triangles to surface_model.restate.  The floor — 10 % of the 600 rays end on a triangle of the
+    updated mesh — is asked of the case: of the step after which most rays do.  Per step it cannot hold with the matrix's
+    rays: mesh_deeper's `one leaf` is 1 536 copies of ONE triangle, which none of them hits (0 %), and its `clustered` draws
+    the knot together (9.3 %; 10.3 % in mesh_past_fast_stacks, whose rays are other draws).  A step with rays on the mesh
+    must show some; every share is printed"""
+    found = C.on_updated_mesh(name)
+    c = C.cases()[name]
+    assert sorted(found) == sorted(s.name for s in c.steps) and name.startswith("mesh_") and c.updated == (0,)
+    level = np.arange(C.N_RAYS) % 4 == 0
+    print("\n".join("%s, %s: %.1f %% of the rays end on a triangle of the updated mesh (%.1f %% are level rays that do)"
+                    % (name, k, 100.0 * v.mean(), 100.0 * (v & level).mean()) for k, v in found.items()))
+    assert max(v.mean() for v in found.values()) >= 0.10
+    for k, v in found.items():
+        if k not in ("one leaf", "two leaves"):
+            assert v.mean() >= 0.05, k
+    if name == "mesh_from_two_leaves":
+        assert c.level and found["the knot"].mean() >= 0.10 and (found["the knot"] & level).mean() >= 0.05

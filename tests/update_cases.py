@@ -9,7 +9,10 @@ scene and the lit scene (test_gpu_scene_update).
 
 Every case has 600 rays (three 256-thread blocks, the last one partial; test_gpu_occlusion.N_RAYS), 16 points for ambient
 occlusion and three views at 37 x 21 (777 pixels: four blocks, the last one partial).  Half of the rays aim at the boxes
-the updated object lies in before and after the update, the other half anywhere; no direction is a unit vector."""
+the updated object lies in before and after the update, the other half anywhere; no direction is a unit vector.
+
+tests/test_gpu_update_newer.py runs the entry points added later over the same cases, rays, points and views, with one
+lightmap chart per case (`chart`: 91 texels), sample counts and stream ids of its own further down."""
 import functools
 import math
 
@@ -255,6 +258,43 @@ def views(name):
     return lens, View.orthographic(plain, L * math.tan(c.fov / 2.0)), View.panorama(tuple(eye + 0.6 * L * direction))
 
 
+# ---- the inputs of tests/test_gpu_update_newer.py: one chart for the lightmap calls, the sample counts, the stream ids
+LM_SAMPLES, PROBE_SAMPLES, DIRECT_SAMPLES = 4, 6, 5
+LM_W, LM_H = 13, 7          # tests/test_gpu_lightmap.py's small map: 91 texels
+NEWER_SEED = 0x4E57
+# where the chart lies in the case's first aim box, as a share of that box's height from its floor: chosen with the oracle so
+# that the texels' ambient occlusion is neither all 0 nor all 1 and changes with every step that moves geometry
+# (tests/test_update_cases_host.py holds each to it and prints what it measures)
+CHART_HEIGHT = {"objects_flat": 0.5, "objects_filtered": 0.25, "lights": 0.5, "materials_deeper": 0.25, "mesh_same_depth": 0.25,
+                "mesh_deeper": 0.25, "mesh_past_fast_stacks": 0.25, "group_in_kernel": 0.25, "group_per_tree": 0.25,
+                "mesh_then_objects": 0.25, "mesh_from_two_leaves": 0.15}
+
+
+@functools.lru_cache(maxsize=None)
+def chart(name):
+    """(triangles (2, 3, 3), uvs (2, 3, 2), width, height, offset): one chart of two triangles — a horizontal quad over the
+    x-z extent of the case's first aim box at CHART_HEIGHT, its normal up (Triangle::from_vertices' of these vertex orders) —
+    laid over texels 1..11 x 1..5 of the 13 x 7 map: 55 texel centres inside, a gutter of one texel on every side; offset:
+    1e-3 of the largest coordinate"""
+    lo, hi = (np.array(v, dtype=np.float64) for v in cases()[name].aim[0])
+    y = lo[1] + CHART_HEIGHT[name] * (hi[1] - lo[1])
+    a, b, c, d = (lo[0], y, lo[2]), (hi[0], y, lo[2]), (hi[0], y, hi[2]), (lo[0], y, hi[2])
+    tris = np.array([[a, d, c], [a, c, b]], dtype=np.float64)
+    u0, u1, v0, v1 = 1.0 / LM_W, (LM_W - 1.0) / LM_W, 1.0 / LM_H, (LM_H - 1.0) / LM_H
+    ua, ub, uc, ud = (u0, v0), (u1, v0), (u1, v1), (u0, v1)
+    uvs = np.array([[ua, ud, uc], [ua, uc, ub]], dtype=np.float64)
+    return _frozen(tris, uvs) + (LM_W, LM_H, 1e-3 * float(np.abs(tris).max()))
+
+
+@functools.lru_cache(maxsize=None)
+def streams(name):
+    """(a stream id per ray (600,) uint32 — points(name)'s ids, ray i's moved on by 1000 for every 16 rays before it, so none
+    occurs twice and none is an index —, the lightmap calls' stream_base: the first of those ids)"""
+    ids = points(name)[2]
+    k = np.arange(N_RAYS, dtype=np.uint32)
+    return _frozen(ids[k % N_POINTS] + np.uint32(1000) * (k // N_POINTS)) + (int(ids[0]),)
+
+
 def frame_params(seed=SEEDS[0], base=BASE):
     """view 0 of the views calls as a render_batch (and an oracle) frame"""
     return make_params(W, H, BOUNCES, SPP, seed=seed, sample_index_base=base)
@@ -300,4 +340,105 @@ def shares(name):
                           "t": share(before["t"], after["t"]), "occluded": share(before["object"] >= 0, after["object"] >= 0),
                           "albedo": share(before["albedo"], after["albedo"]),
                           "frame": share(before["frame"], after["frame"])}
+    return out
+
+
+# ---- what the oracle says about the inputs of tests/test_gpu_update_newer.py (tests/test_update_cases_host.py holds the
+# floors; every function here runs on the CPU)
+def _scenes_of(name):
+    """[(None, scene0)] + [(step name, its scene)] for the steps that are no return"""
+    c = cases()[name]
+    return [(None, c.scene0)] + [(s.name, s.scene) for s in c.steps if not s.back]
+
+
+@functools.lru_cache(maxsize=None)
+def chart_texels(name):
+    """the chart by tests/lightmap_model.py: (its four raw channels, the owned texels (H, W) bool, their gather points, their
+    unit normals, their stream ids: stream_base + y * width + x)"""
+    import lightmap_model
+    tris, uvs, w, h, offset = chart(name)
+    raw = lightmap_model.raw(tris, None, uvs, w, h, offset=offset)
+    owned = raw["owner"] >= 0
+    ys, xs = np.nonzero(owned)
+    ids = (streams(name)[1] + ys * w + xs).astype(np.uint32)
+    return (raw, owned) + _frozen(np.ascontiguousarray(raw["position"][owned]), np.ascontiguousarray(raw["normal"][owned]), ids)
+
+
+@functools.lru_cache(maxsize=None)
+def chart_ao(name):
+    """the unoccluded fraction at the chart's owned texels as include/rpt_gpu.h defines bake_ao — RPT_PROBE_IRRADIANCE's
+    directions (test_gpu_probes.directions: the oracle's stream and Sphere::sample), the oracle's closest_hit,
+    test_gpu_occlusion.fold — -> {None or step name: {"inf": ao, "half": ao}}: LM_SAMPLES directions from sample BASE on, at
+    max_distance = inf and at half the aim box's diagonal"""
+    from oracle import oracle_ffi as oracle
+    import test_gpu_occlusion as occ
+    import test_gpu_probes as probes
+    _, _, pos, nrm, ids = chart_texels(name)
+    half = points(name)[3]
+    d, _ = probes.directions(probes.IRR, nrm, ids, NEWER_SEED, LM_SAMPLES, BASE)
+    out = {}
+    for step, scene in _scenes_of(name):
+        t = oracle.OracleScene(scene).closest_hit(np.repeat(pos, LM_SAMPLES, axis=0), d.reshape(-1, 3))[0].reshape(len(pos), LM_SAMPLES)
+        out[step] = {"inf": occ.fold(d, t, math.inf)[0], "half": occ.fold(d, t, half)[0]}
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def direct_at_points(name):
+    """rptgpu_bake_direct at points(name) by tests/direct_model.py with the oracle's illuminate and closest_hit ->
+    {None or step name: (16, 3)}: DIRECT_SAMPLES samples from sample BASE on, on the points' stream ids"""
+    from oracle import oracle_ffi as oracle
+    import direct_cases
+    import direct_model
+    pos, nrm, ids, _ = points(name)
+    out = {}
+    for step, scene in _scenes_of(name):
+        osc = oracle.OracleScene(scene)
+        out[step] = direct_model.direct(scene.lights, pos, nrm, DIRECT_SAMPLES, NEWER_SEED, lambda o, d: osc.closest_hit(o, d)[0],
+                                        sample_index_base=BASE, streams=ids, illuminate=direct_cases.oracle_illuminate)
+    return out
+
+
+# does bake_direct at points(name) change its bits from scene0 to the step's scene?  By direct_at_points (the host test holds
+# this table to the model; the GPU test asserts what it says).  materials_deeper: a shadow ray stops at any object, glass
+# too.  objects_filtered's sphere and mesh_same_depth's gentle sine stand in none of the 16 points' 5 samples' way to a light
+DIRECT_CHANGES = {
+    "objects_flat": {"moved": True, "outside": True, "not finite": True},
+    "objects_filtered": {"outside the grid": True, "not finite": False},
+    "lights": {"moved": True},
+    "materials_deeper": {"glass and mirror": False},
+    "mesh_same_depth": {"sine": False},
+    "mesh_deeper": {"clustered": True, "one leaf": True},
+    "mesh_past_fast_stacks": {"clustered": True},
+    "group_in_kernel": {"jitter": True, "clustered": True, "coincident": True},
+    "group_per_tree": {"jitter": True, "clustered": True, "coincident": True},
+    "mesh_then_objects": {"set_mesh": True, "update": True},
+    "mesh_from_two_leaves": {"the knot": True},
+}
+MESH_CASES = [n for n in NAMES if n.startswith("mesh_")]  # object 0, the knot, gets new triangles
+
+
+@functools.lru_cache(maxsize=None)
+def on_updated_mesh(name):
+    """per step of a mesh case, the return to the knot too — every one of them is a set_mesh —: the rays(name) whose oracle
+    record is a triangle's of the UPDATED mesh (object 0): some row of it gives the oracle's t to the bit with all three
+    weights >= 0 (surface_model.tri_records in the mesh's frame, as tests/test_hit_surface_host.py holds it) ->
+    {step name: (600,) bool}"""
+    from oracle import oracle_ffi as oracle
+    import surface_model
+    o, d, _ = rays(name)
+    out = {}
+    for step, scene in [(s.name, s.scene) for s in cases()[name].steps]:
+        t, _, obj = oracle.OracleScene(scene).closest_hit(o, d)
+        (_, _, chain, mesh), = [m for m in surface_model.meshes_of(scene) if m[0] == 0]
+        rows = np.unique(mesh.triangles, axis=0)  # (ONE_LEAF and TWO_LEAVES repeat their rows)
+        found = np.zeros(N_RAYS, dtype=bool)
+        for i in np.flatnonzero(obj == 0):
+            lo, ld = o[i:i + 1], d[i:i + 1]
+            for xf in chain:
+                if xf is not None:
+                    lo, ld = surface_model.local_rays(xf, lo, ld)
+            time, uvw, _ = surface_model.tri_records(rows, np.repeat(lo, len(rows), 0), np.repeat(ld, len(rows), 0))
+            found[i] = ((surface_model.bits(time) == surface_model.bits(t[i:i + 1])) & (uvw >= 0.0).all(axis=1)).any()
+        out[step] = found
     return out
