@@ -1068,6 +1068,8 @@ const char* rptgpu_kernel_name(int k);
 #include "rpt_gpu_lightmap_filter.h"
 /* ---- ... and direct lighting (next-event estimation) at caller points and lightmap texels ---- */
 #include "rpt_gpu_direct.h"
+/* ---- ... and a baked lightmap read back at the first hits of the caller's rays ---- */
+#include "rpt_gpu_lightmap_lookup.h"
 
 #ifdef __cplusplus
 }

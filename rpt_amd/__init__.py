@@ -28,6 +28,8 @@ from ._abi import (RPT_VERTEX_ABS_COS, RPT_VERTEX_ALL, RPT_VERTEX_BSDF, RPT_VERT
                    RPT_VERTEX_RADIANCE, RPT_VERTEX_RGB, RPT_VERTEX_T)
 from ._abi import (RPT_SURFACE_ALL, RPT_SURFACE_BARYCENTRIC, RPT_SURFACE_CHILD, RPT_SURFACE_OBJECT,  # noqa: F401
                    RPT_SURFACE_PRIMITIVE, RPT_SURFACE_T)
+from ._abi import (RPT_LOOKUP_ALL, RPT_LOOKUP_BILINEAR, RPT_LOOKUP_BINDING, RPT_LOOKUP_COVERED, RPT_LOOKUP_NEAREST,  # noqa: F401
+                   RPT_LOOKUP_OBJECT, RPT_LOOKUP_T, RPT_LOOKUP_UV, RPT_LOOKUP_VALUE)
 from ._abi import (RPT_LIGHTMAP_ALL, RPT_LIGHTMAP_AO, RPT_LIGHTMAP_BARYCENTRIC, RPT_LIGHTMAP_IRRADIANCE,  # noqa: F401
                    RPT_LIGHTMAP_NORMAL, RPT_LIGHTMAP_OWNER, RPT_LIGHTMAP_POSITION)
 from .buffer import Buffer, Filter  # noqa: F401

@@ -59,6 +59,10 @@ RPT_SURFACE_ALL = 31
 (RPT_LIGHTMAP_IRRADIANCE, RPT_LIGHTMAP_AO, RPT_LIGHTMAP_OWNER, RPT_LIGHTMAP_BARYCENTRIC, RPT_LIGHTMAP_POSITION,
  RPT_LIGHTMAP_NORMAL) = 1, 2, 4, 8, 16, 32
 RPT_LIGHTMAP_ALL = 63
+# include/rpt_gpu_lightmap_lookup.h: RptLookupQuery.channels and .filter of lookup_lightmap (lightmap_lookup_supported())
+(RPT_LOOKUP_T, RPT_LOOKUP_OBJECT, RPT_LOOKUP_BINDING, RPT_LOOKUP_COVERED, RPT_LOOKUP_UV, RPT_LOOKUP_VALUE) = 1, 2, 4, 8, 16, 32
+RPT_LOOKUP_ALL = 63
+RPT_LOOKUP_NEAREST, RPT_LOOKUP_BILINEAR = 0, 1
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -302,6 +306,31 @@ class RptLightmapFilterArrays(C.Structure):
                 ("out_variance", C.POINTER(f64))]
 
 
+class RptLightmapBinding(C.Structure):
+    """include/rpt_gpu_lightmap_lookup.h RptLightmapBinding (one map tied to one top-level mesh object)."""
+    _fields_ = [("struct_size", C.c_uint32), ("object", C.c_uint32), ("n_tris", C.c_uint32), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("components", C.c_uint32), ("reserved", C.c_uint32), ("uvs", C.POINTER(f64)),
+                ("map", C.POINTER(f64)), ("valid", C.POINTER(C.c_uint8))]
+
+
+class RptLookupQuery(C.Structure):
+    """include/rpt_gpu_lightmap_lookup.h RptLookupQuery (rptgpu_lookup_lightmap's parameters)."""
+    _fields_ = [("struct_size", C.c_uint32), ("channels", C.c_uint32), ("filter", C.c_uint32), ("fallback", V3),
+                ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RptLookupArrays(C.Structure):
+    """include/rpt_gpu_lightmap_lookup.h RptLookupArrays (rptgpu_lookup_lightmap's output arrays, host or device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("t", C.POINTER(f64)), ("object", C.POINTER(C.c_int32)),
+                ("binding", C.POINTER(C.c_int32)), ("covered", C.POINTER(C.c_uint8)), ("uv", C.POINTER(f64)),
+                ("value", C.POINTER(f64))]
+
+
+class RptViewsLightmapQuery(C.Structure):
+    """include/rpt_gpu_lightmap_lookup.h RptViewsLightmapQuery (rptgpu_render_views_lightmapped's parameters beside RptViewQuery)."""
+    _fields_ = [("struct_size", C.c_uint32), ("filter", C.c_uint32), ("unbound_irradiance", V3)]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -448,6 +477,17 @@ DIRECT_SYMBOLS = [
     ("rptgpu_bake_lightmap_direct", C.c_int, [_VP, C.c_uint64, _PD, _PD, _PD, C.POINTER(RptLightmapQuery), _PD]),
     ("rptgpu_bake_lightmap_direct_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, C.POINTER(RptLightmapQuery), _VP, _VP]),
 ]
+# ... and every symbol include/rpt_gpu_lightmap_lookup.h declares, optional in the same way (lightmap_lookup_supported())
+LIGHTMAP_LOOKUP_SYMBOLS = [
+    ("rptgpu_lookup_lightmap", C.c_int, [_VP, C.c_uint64, _PD, _PD, C.c_uint32, C.POINTER(RptLightmapBinding),
+                                         C.POINTER(RptLookupQuery), C.POINTER(RptLookupArrays)]),
+    ("rptgpu_lookup_lightmap_device", C.c_int, [_VP, C.c_uint64, _VP, _VP, C.c_uint32, C.POINTER(RptLightmapBinding),
+                                                C.POINTER(RptLookupQuery), C.POINTER(RptLookupArrays), _VP]),
+    ("rptgpu_render_views_lightmapped", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.c_uint32,
+                                                  C.POINTER(RptLightmapBinding), C.POINTER(RptViewsLightmapQuery), _PD]),
+    ("rptgpu_render_views_lightmapped_device", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.c_uint32,
+                                                         C.POINTER(RptLightmapBinding), C.POINTER(RptViewsLightmapQuery), _VP, _VP]),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -476,11 +516,11 @@ def load_library(path=None):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
-    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS + LIGHTMAP_SYMBOLS + LIGHTMAP_FILTER_SYMBOLS + DIRECT_SYMBOLS:
+    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS + LIGHTMAP_SYMBOLS + LIGHTMAP_FILTER_SYMBOLS + DIRECT_SYMBOLS + LIGHTMAP_LOOKUP_SYMBOLS:
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported(), lightmap_supported(), lightmap_filter_supported(), direct_supported() say no)
+            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported(), lightmap_supported(), lightmap_filter_supported(), direct_supported(), lightmap_lookup_supported() say no)
         fn.restype = restype
         fn.argtypes = argtypes
     if lib.rptgpu_abi_version() != ABI_VERSION:
@@ -552,6 +592,13 @@ def direct_supported(lib=None):
     (include/rpt_gpu_direct.h)?  Detected by symbol, as a C caller does with dlsym: a library without them is still ABI 7."""
     lib = lib or load_library()
     return all(hasattr(lib, name) for name, _, _ in DIRECT_SYMBOLS)
+
+
+def lightmap_lookup_supported(lib=None):
+    """Does the library export rptgpu_lookup_lightmap[_device] (include/rpt_gpu_lightmap_lookup.h)?  Detected by symbol, as a
+    C caller does with dlsym: a library without them is still ABI 7."""
+    lib = lib or load_library()
+    return all(hasattr(lib, name) for name, _, _ in LIGHTMAP_LOOKUP_SYMBOLS)
 
 
 def check(code, handle=None):

@@ -18,6 +18,9 @@ SURFACE_CHANNELS = ((_abi.RPT_SURFACE_T, "t", (), np.float64), (_abi.RPT_SURFACE
 LIGHTMAP_CHANNELS = ((_abi.RPT_LIGHTMAP_IRRADIANCE, "irradiance", (3,), np.float64), (_abi.RPT_LIGHTMAP_AO, "ao", (), np.float64),
                      (_abi.RPT_LIGHTMAP_OWNER, "owner", (), np.int32), (_abi.RPT_LIGHTMAP_BARYCENTRIC, "barycentric", (3,), np.float64),
                      (_abi.RPT_LIGHTMAP_POSITION, "position", (3,), np.float64), (_abi.RPT_LIGHTMAP_NORMAL, "normal", (3,), np.float64))
+LOOKUP_CHANNELS = ((_abi.RPT_LOOKUP_T, "t", (), np.float64), (_abi.RPT_LOOKUP_OBJECT, "object", (), np.int32),
+                   (_abi.RPT_LOOKUP_BINDING, "binding", (), np.int32), (_abi.RPT_LOOKUP_COVERED, "covered", (), np.uint8),
+                   (_abi.RPT_LOOKUP_UV, "uv", (2,), np.float64), (_abi.RPT_LOOKUP_VALUE, "value", (3,), np.float64))
 # rptgpu_trace_vertices': (bit, name, "path" | "vertex" | "ray", shape behind it, dtype)
 VERTEX_CHANNELS = ((_abi.RPT_VERTEX_LENGTH, "length", "path", (), np.uint32), (_abi.RPT_VERTEX_T, "t", "vertex", (), np.float64),
                    (_abi.RPT_VERTEX_NORMAL, "normal", "vertex", (3,), np.float64),
@@ -128,6 +131,13 @@ class _Host(_Backend):
             raise ValueError("%s: %s must be an (n, %s) float64 array" % (who, what, ", ".join(str(t) for t in tail)))
         return np.ascontiguousarray(a)
 
+    def flags(self, a, shape, who, what):
+        """a lightmap binding's valid map: `shape` bytes or bools -> contiguous uint8"""
+        a = np.asarray(a)
+        if a.dtype not in (np.uint8, np.bool_) or a.shape != tuple(shape):
+            raise ValueError("%s: %s must be a %s uint8 or bool array" % (who, what, tuple(shape)))
+        return np.ascontiguousarray(a).view(np.uint8)
+
     def new(self, count, dtype, zero):
         return (np.zeros if zero else np.empty)(count, dtype=dtype)
 
@@ -214,6 +224,13 @@ class _Device(_Backend):
         if a.dtype != self.torch.float64 or a.dim() != 1 + len(tail) or tuple(a.shape[1:]) != tuple(tail):
             raise ValueError("%s: %s must be an (n, %s) float64 tensor" % (who, what, ", ".join(str(t) for t in tail)))
         return a.contiguous()
+
+    def flags(self, a, shape, who, what):
+        """a lightmap binding's valid map: `shape` bytes or bools -> a contiguous uint8 tensor"""
+        self.here(a, who, what)
+        if a.dtype not in (self.torch.uint8, self.torch.bool) or tuple(a.shape) != tuple(shape):
+            raise ValueError("%s: %s must be a %s uint8 or bool tensor" % (who, what, tuple(shape)))
+        return a.to(self.torch.uint8).contiguous()
 
     def new(self, count, dtype, zero):
         return (self.torch.zeros if zero else self.torch.empty)(count, dtype=self.dtypes[np.dtype(dtype)], device=self.dev)

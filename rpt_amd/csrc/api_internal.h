@@ -42,6 +42,10 @@
 //   api_lightmap_filter.cpp rptgpu_filter_lightmap[_device]: a baked map through the geometry-guided a-trous filter — the
 //                    guides as columns, one launch per level, the columns written back, then api_lightmap.cpp's dilation
 //                    rounds (the kernels: kernels_lightmap_filter.hip; the sizes: lightmap_filter_plan.h)
+//   api_lightmap_lookup.cpp rptgpu_lookup_lightmap[_device]: a baked map read back at the caller's rays' first hits — per piece
+//                    api_hits.cpp's first-hit query and api_surface.cpp's resolve walk into arrays the handle keeps, then
+//                    rpt_lightmap_lookup, one lane per ray (the kernel: kernels_lightmap_lookup.hip; the sizes:
+//                    lightmap_lookup_plan.h)
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -78,6 +82,9 @@
 #include "lightmap.h"
 #include "lightmap_filter_plan.h"
 #include "lightmap_filter.h"
+#include "lightmap_lookup_plan.h"
+#include "lightmap_lookup.h"
+#include "lightmap_views.h"
 
 namespace rptapi {
 
@@ -223,6 +230,11 @@ struct rptgpu_scene {
   // rptgpu_filter_lightmap (api_lightmap_filter.cpp): the filter's columns with the dilation's second copy inside them
   // (lightmap_filter_plan.h workspace) and a host caller's arrays, staged whole (stage)
   DevBuf<double> lf_ws, lf_stage;
+  // rptgpu_lookup_lightmap (api_lightmap_lookup.cpp): a piece's arrays (lightmap_lookup_plan.h layout), the call's binding
+  // records and object-to-binding table, and a host caller's uvs, maps and valid bytes, staged whole (stage_binding)
+  DevBuf<double> lk_piece, lk_stage;
+  DevBuf<rptlookup::Binding> lk_bindings;
+  DevBuf<int32_t> lk_table;
   DevBuf<double> vertices_out;         // rptgpu_trace_vertices: a piece of a host caller's records, the named channels back to back (api_vertices.cpp)
   DevBuf<rptdev::View> view_recs;     // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<uint64_t> view_seeds;         // ... their seeds, when the views have seeds of their own,
@@ -487,6 +499,14 @@ struct HitPieces {
 HitPieces plan_hit_pieces(rptgpu_scene* h, uint64_t n, uint32_t flags, const char* piece_env);
 void hit_piece(rptgpu_scene* h, const KernelTable* kt, const HitPieces& hp, const double* d_o, const double* d_d, uint32_t m,
                const rptdev::HitOut& ho, bool prof);
+// api_surface.cpp: rptgpu_hit_surface's resolve walk, piece by piece, as rptgpu_lookup_lightmap runs it too
+// (api_lightmap_lookup.cpp).  ensure_surface_columns: rpt_hit_surface's columns for pieces of `piece` rays (and the overflow
+// flag); group_holds_monomial: the walk's groups_from_inf; surface_walk_piece: the walk over m rays at d_o / d_d whose T and
+// OBJECT stand in `so`, into so's named channels
+GenericStack ensure_surface_columns(rptgpu_scene* h, uint64_t piece);
+bool group_holds_monomial(const rptgpu_scene* h);
+void surface_walk_piece(rptgpu_scene* h, const double* d_o, const double* d_d, uint32_t m, const rptdev::SurfaceOut& so,
+                        const GenericStack& gs, bool from_inf);
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
 const char* bad_probe_query(const RptProbeQuery* q);

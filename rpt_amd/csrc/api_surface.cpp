@@ -79,6 +79,9 @@ void copy_surface_out(const PieceArrays& src, const PieceArrays& dst, uint32_t c
     HIP_TRY(hipMemcpyAsync(dst.barycentric, src.barycentric, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
 }
 
+} // namespace
+
+// (these three: also rptgpu_lookup_lightmap's, api_lightmap_lookup.cpp — declared in api_internal.h)
 // rpt_hit_surface's columns for pieces of `piece` rays, as high as the scene needs now (a live rebuild may have raised
 // gen_levels: taller columns hold the same walk), and the flag a walk raises if it outgrows them
 GenericStack ensure_surface_columns(rptgpu_scene* h, uint64_t piece) {
@@ -104,6 +107,17 @@ bool group_holds_monomial(const rptgpu_scene* h) {
     if ((h->inst_sig[i] & 0x7f) == RPT_SHAPE_MONOMIAL) return true;
   return false;
 }
+
+// the resolve walk over m rays at d_o / d_d whose T and OBJECT stand in `so`, into so's named channels
+void surface_walk_piece(rptgpu_scene* h, const double* d_o, const double* d_d, uint32_t m, const rptdev::SurfaceOut& so,
+                        const GenericStack& gs, bool from_inf) {
+  const uint32_t blocks = rptsurface::launch_blocks(m, h->surf_cols);
+  if (h->ext_shapes) rpt_strict_ext_surface::launch_hit_surface(h->stream, h->dscene, d_o, d_d, m, so, gs, from_inf, h->gen_overflow.p, blocks);
+  else rpt_strict_surface::launch_hit_surface(h->stream, h->dscene, d_o, d_d, m, so, gs, from_inf, h->gen_overflow.p, blocks);
+  HIP_TRY(hipGetLastError());
+}
+
+namespace {
 
 // on_device: origins, dirs and out's arrays are device pointers (user_stream: the stream their producer ran on)
 int hit_surface(rptgpu_scene* h, uint64_t n, const double* origins, const double* dirs, const RptSurfaceQuery* q,
@@ -158,10 +172,7 @@ int hit_surface(rptgpu_scene* h, uint64_t n, const double* origins, const double
         so.t = dev.t; so.object = dev.object;
         so.child = dev.child; so.primitive = dev.primitive; so.barycentric = dev.barycentric;
         so.channels = ch & (RPT_SURFACE_CHILD | RPT_SURFACE_PRIMITIVE | RPT_SURFACE_BARYCENTRIC);
-        const uint32_t blocks = rptsurface::launch_blocks(m, h->surf_cols);
-        if (h->ext_shapes) rpt_strict_ext_surface::launch_hit_surface(st, h->dscene, d_o, d_d, m, so, gs, from_inf, h->gen_overflow.p, blocks);
-        else rpt_strict_surface::launch_hit_surface(st, h->dscene, d_o, d_d, m, so, gs, from_inf, h->gen_overflow.p, blocks);
-        HIP_TRY(hipGetLastError());
+        surface_walk_piece(h, d_o, d_d, m, so, gs, from_inf);
       }
       if (!on_device) { // the staging arrays are the next piece's, too
         copy_surface_out(mine_dev, theirs, ch, m, st);

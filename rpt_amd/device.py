@@ -479,6 +479,100 @@ class GpuScene:
         q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
         return self._ray_records("hit_surface", origins, dirs, q, _abi.RptSurfaceArrays(), _marshal.SURFACE_CHANNELS)
 
+    _FILTERS = {"nearest": _abi.RPT_LOOKUP_NEAREST, "bilinear": _abi.RPT_LOOKUP_BILINEAR}
+
+    def lookup_lightmap(self, origins, dirs, bindings, *, filter="bilinear", fallback=(0.0, 0.0, 0.0),
+                        channels=_abi.RPT_LOOKUP_ALL, flags=0):
+        """Baked lightmaps read back at the first hit of each of the caller's rays (rptgpu_lookup_lightmap) ->
+        a dict with one array per channel of `channels` (RPT_LOOKUP_*): `t` (n,) float64 and `object` (n,) int32 —
+        closest_hit's, to join on —, `binding` (n,) int32 — the index in `bindings` of the lightmap.Binding that names the
+        hit object, -1 for a miss, an object nobody names, a mesh inside a group —, `covered` (n,) uint8, `uv` (n, 2) —
+        the hit triangle's uvs under hit_surface's barycentrics, surface.interpolate's order — and `value` (n, 3): the
+        map's texel there under `filter` ("nearest", or "bilinear": clamp to edge, taps that are not valid left out and
+        the weights renormalised), a one-component map's scalar three times, `fallback` where the ray is not covered.
+        origins, dirs: (n, 3) float64, used as given.  numpy arrays go through host memory; torch tensors on the
+        handle's device — rays and every binding's arrays alike — are read where they lie
+        (rptgpu_lookup_lightmap_device) and the results are new tensors there."""
+        if not _abi.lightmap_lookup_supported(self.lib):
+            raise _abi.RptGpuError(_abi.RPTGPU_E_INVALID_ARGUMENT, "this library does not export rptgpu_lookup_lightmap")
+        who = "lookup_lightmap"
+        if filter not in self._FILTERS:
+            raise ValueError('%s: filter must be "nearest" or "bilinear", not %r' % (who, filter))
+        q = _abi.RptLookupQuery()
+        q.struct_size, q.channels, q.filter = C.sizeof(_abi.RptLookupQuery), int(channels), self._FILTERS[filter]
+        q.fallback = _abi.V3(*(float(x) for x in fallback))
+        q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        bindings = list(bindings)
+        m = _marshal.pick(self.device, origins, dirs, *(x for b in bindings for x in (b.uvs, b.map, b.valid)))
+        recs, keep = self._lower_bindings(m, bindings, who)
+        a = _abi.RptLookupArrays()
+        a.struct_size, a.reserved = C.sizeof(a), 0
+        n, o, d = self._pair(m, origins, dirs, who, self._RAYS)
+        out = m.fill(a, _marshal.layout(_marshal.LOOKUP_CHANNELS, q.channels, (n,)), who)
+        PD = C.POINTER(C.c_double)
+        self._call("rptgpu_lookup_lightmap", m, n, m.pointer(o, PD), m.pointer(d, PD), len(bindings), recs, C.byref(q), C.byref(a))
+        del keep
+        return out
+
+    def render_views_lightmapped(self, views, width, height, bindings, *, samples=1, seed, seed_stride=0, sample_index_base=0,
+                                 exposure_value=0.0, filter="bilinear", unbound_irradiance=(0.0, 0.0, 0.0), flags=0, out=None):
+        """A batch of views shaded from baked lightmaps (rptgpu_render_views_lightmapped) -> (n, height, width,
+        3) float64.  views, width, height, samples, seed, seed_stride, sample_index_base, exposure_value: render_views' —
+        the ray of (view, pixel, sample) is exactly that call's.  Per sample a miss gives the environment's colour and a
+        hit on an object of material m gives m.emittance * m.color + m.color / pi * I, with I lookup_lightmap's `value`
+        under `filter` where the ray is covered and `unbound_irradiance` elsewhere; a pixel is the mean over its samples
+        times 2^exposure_value.  bindings: lightmap.Binding records of numpy arrays — the frames then come through host
+        memory — or of torch tensors on the handle's device, which are read where they lie and give a new tensor there
+        (rptgpu_render_views_lightmapped_device; out="torch" asks for that form when there is no binding to tell)."""
+        if not _abi.lightmap_lookup_supported(self.lib):
+            raise _abi.RptGpuError(_abi.RPTGPU_E_INVALID_ARGUMENT, "this library does not export rptgpu_render_views_lightmapped")
+        who = "render_views_lightmapped"
+        if filter not in self._FILTERS:
+            raise ValueError('%s: filter must be "nearest" or "bilinear", not %r' % (who, filter))
+        if out not in (None, "torch"):
+            raise ValueError('%s: out must be None or "torch"' % who)
+        n, arr, _, qv = self._view_query(who, views, width, height, 0, samples, exposure_value, seed, seed_stride, None,
+                                         sample_index_base, flags)
+        q = _abi.RptViewsLightmapQuery()
+        q.struct_size, q.filter = C.sizeof(q), self._FILTERS[filter]
+        q.unbound_irradiance = _abi.V3(*(float(x) for x in unbound_irradiance))
+        bindings = list(bindings)
+        m = _marshal._Device(self.device) if out == "torch" else \
+            _marshal.pick(self.device, *(x for b in bindings for x in (b.uvs, b.map, b.valid)))
+        recs, keep = self._lower_bindings(m, bindings, who)
+        frames = m.result(None, (n, int(height), int(width), 3), np.float64, who, "out")
+        self._call("rptgpu_render_views_lightmapped", m, n, arr, C.byref(qv), len(bindings), recs, C.byref(q),
+                   m.pointer(frames, C.POINTER(C.c_double)))
+        del keep
+        return frames
+
+    @staticmethod
+    def _lower_bindings(m, bindings, who):
+        """lightmap.Binding records -> (an RptLightmapBinding array or None, the arrays its pointers point into)"""
+        if not bindings:
+            return None, []
+        recs, keep = (_abi.RptLightmapBinding * len(bindings))(), []
+        types = dict(_abi.RptLightmapBinding._fields_)
+        for k, (b, r) in enumerate(zip(bindings, recs)):
+            what = "bindings[%d]." % k
+            uvs = m.records(b.uvs, (3, 2), who, what + "uvs")
+            tex = b.map if hasattr(b.map, "shape") else np.asarray(b.map)
+            if len(tex.shape) not in (2, 3) or (len(tex.shape) == 3 and int(tex.shape[2]) != 3):
+                raise ValueError("%s: %smap must be an (H, W) or (H, W, 3) float64 array" % (who, what))
+            height, width = int(tex.shape[0]), int(tex.shape[1])
+            tex = m.result(tex, tuple(int(x) for x in tex.shape), np.float64, who, what + "map")
+            r.struct_size, r.object, r.n_tris = C.sizeof(r), int(b.object), int(uvs.shape[0])
+            r.width, r.height, r.components, r.reserved = width, height, 3 if len(tex.shape) == 3 else 1, 0
+            # (an empty array has no address the library would take: it refuses NULL uvs, and width or height of 0)
+            r.uvs = m.field(uvs, types["uvs"]) if r.n_tris else None
+            r.map = m.field(tex, types["map"]) if width and height else None
+            keep += [uvs, tex]
+            if b.valid is not None:
+                valid = m.flags(b.valid, (height, width), who, what + "valid")
+                r.valid = m.field(valid, types["valid"]) if width and height else None
+                keep.append(valid)
+        return recs, keep
+
     def bake_lightmap(self, triangles, uvs, width, height, *, normals=None, samples=0, max_bounces=0, seed, offset=0.0, dilate=0,
                       channels=_abi.RPT_LIGHTMAP_IRRADIANCE | _abi.RPT_LIGHTMAP_OWNER, max_distance=float("inf"), stream_base=0,
                       sample_index_base=0, flags=0):

@@ -42,6 +42,18 @@ def load_obj_texcoords(file):
             f.close()
 
 
+class Binding:
+    """One baked map tied to one object of a scene, for GpuScene.lookup_lightmap (include/rpt_gpu_lightmap_lookup.h,
+    DESIGN.md §25): `object`, the index of a top-level object whose shape is a mesh (plain or Transformed); `uvs`
+    (n_tris, 3, 2) float64 in the mesh's own triangle order; `map` (H, W) or (H, W, 3) float64, row 0 at v = 0 as
+    bake_lightmap writes it; `valid` (H, W) uint8 or bool, non-zero where the texel holds a value (a bake's owner >= 0), or
+    None: every texel does.  numpy arrays or torch tensors on the handle's device, all of one kind; they are checked by
+    the call."""
+
+    def __init__(self, object, uvs, map, valid=None):
+        self.object, self.uvs, self.map, self.valid = int(object), uvs, map, valid
+
+
 def texel_extent(position, owner):
     """The median world distance between horizontally adjacent owned texels of a bake: `position` (H, W, 3) and `owner`
     (H, W) of bake_lightmap.  GpuScene.filter_lightmap's sigma_distance is a few of these.  ValueError when no two owned
