@@ -1070,6 +1070,8 @@ const char* rptgpu_kernel_name(int k);
 #include "rpt_gpu_direct.h"
 /* ---- ... and a baked lightmap read back at the first hits of the caller's rays ---- */
 #include "rpt_gpu_lightmap_lookup.h"
+/* ---- ... and a grid of baked SH9 probes read at points, at first hits and in views shaded from both ---- */
+#include "rpt_gpu_probe_volume.h"
 
 #ifdef __cplusplus
 }

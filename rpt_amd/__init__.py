@@ -28,6 +28,8 @@ from ._abi import (RPT_VERTEX_ABS_COS, RPT_VERTEX_ALL, RPT_VERTEX_BSDF, RPT_VERT
                    RPT_VERTEX_RADIANCE, RPT_VERTEX_RGB, RPT_VERTEX_T)
 from ._abi import (RPT_SURFACE_ALL, RPT_SURFACE_BARYCENTRIC, RPT_SURFACE_CHILD, RPT_SURFACE_OBJECT,  # noqa: F401
                    RPT_SURFACE_PRIMITIVE, RPT_SURFACE_T)
+from ._abi import (RPT_VOLUME_ALL, RPT_VOLUME_COVERED, RPT_VOLUME_INSIDE, RPT_VOLUME_NORMAL, RPT_VOLUME_OBJECT,  # noqa: F401
+                   RPT_VOLUME_POINT, RPT_VOLUME_POSITION, RPT_VOLUME_T, RPT_VOLUME_VALUE)
 from ._abi import (RPT_LOOKUP_ALL, RPT_LOOKUP_BILINEAR, RPT_LOOKUP_BINDING, RPT_LOOKUP_COVERED, RPT_LOOKUP_NEAREST,  # noqa: F401
                    RPT_LOOKUP_OBJECT, RPT_LOOKUP_T, RPT_LOOKUP_UV, RPT_LOOKUP_VALUE)
 from ._abi import (RPT_LIGHTMAP_ALL, RPT_LIGHTMAP_AO, RPT_LIGHTMAP_BARYCENTRIC, RPT_LIGHTMAP_IRRADIANCE,  # noqa: F401
@@ -42,7 +44,8 @@ from .light import Light  # noqa: F401
 from .material import Material  # noqa: F401
 from .object import Object  # noqa: F401
 from .ode import MarblesSystem, ParticleState, ParticleSystem, SolidGravitySystem  # noqa: F401
-from .probes import sh9_basis, sh9_irradiance  # noqa: F401
+from .probes import ProbeVolume, sh9_basis, sh9_irradiance  # noqa: F401
+from . import probes  # noqa: F401
 from .renderer import Renderer  # noqa: F401
 from .scene import Scene  # noqa: F401
 from . import scenes  # noqa: F401

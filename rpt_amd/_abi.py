@@ -63,6 +63,11 @@ RPT_LIGHTMAP_ALL = 63
 (RPT_LOOKUP_T, RPT_LOOKUP_OBJECT, RPT_LOOKUP_BINDING, RPT_LOOKUP_COVERED, RPT_LOOKUP_UV, RPT_LOOKUP_VALUE) = 1, 2, 4, 8, 16, 32
 RPT_LOOKUP_ALL = 63
 RPT_LOOKUP_NEAREST, RPT_LOOKUP_BILINEAR = 0, 1
+# include/rpt_gpu_probe_volume.h: RptVolumeQuery.channels of sample_ / lookup_probe_volume (probe_volume_supported())
+(RPT_VOLUME_T, RPT_VOLUME_OBJECT, RPT_VOLUME_POSITION, RPT_VOLUME_NORMAL, RPT_VOLUME_VALUE, RPT_VOLUME_COVERED,
+ RPT_VOLUME_INSIDE) = 1, 2, 4, 8, 16, 32, 64
+RPT_VOLUME_ALL = 127
+RPT_VOLUME_POINT = RPT_VOLUME_VALUE | RPT_VOLUME_COVERED | RPT_VOLUME_INSIDE  # what a point has: no ray, no hit
 
 f64 = C.c_double
 V3 = f64 * 3
@@ -331,6 +336,30 @@ class RptViewsLightmapQuery(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("filter", C.c_uint32), ("unbound_irradiance", V3)]
 
 
+class RptProbeVolume(C.Structure):
+    """include/rpt_gpu_probe_volume.h RptProbeVolume (a regular grid of SH9 probes)."""
+    _fields_ = [("struct_size", C.c_uint32), ("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32), ("reserved", C.c_uint32),
+                ("origin", V3), ("spacing", V3), ("coeffs", C.POINTER(f64)), ("valid", C.POINTER(C.c_uint8))]
+
+
+class RptVolumeQuery(C.Structure):
+    """include/rpt_gpu_probe_volume.h RptVolumeQuery (rptgpu_sample_ / rptgpu_lookup_probe_volume's parameters)."""
+    _fields_ = [("struct_size", C.c_uint32), ("channels", C.c_uint32), ("normal_bias", f64), ("fallback", V3),
+                ("precision_mode", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RptVolumeArrays(C.Structure):
+    """include/rpt_gpu_probe_volume.h RptVolumeArrays (the two calls' output arrays, host or device)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("t", C.POINTER(f64)), ("object", C.POINTER(C.c_int32)),
+                ("position", C.POINTER(f64)), ("normal", C.POINTER(f64)), ("value", C.POINTER(f64)),
+                ("covered", C.POINTER(C.c_uint8)), ("inside", C.POINTER(C.c_uint8))]
+
+
+class RptViewsProbeLitQuery(C.Structure):
+    """include/rpt_gpu_probe_volume.h RptViewsProbeLitQuery (rptgpu_render_views_probe_lit's parameters beside RptViewQuery)."""
+    _fields_ = [("struct_size", C.c_uint32), ("filter", C.c_uint32), ("normal_bias", f64), ("unbound_irradiance", V3)]
+
+
 # every symbol include/rpt_gpu.h declares: (name, restype, argtypes)
 _VP = C.c_void_p
 _PD = C.POINTER(f64)
@@ -488,6 +517,18 @@ LIGHTMAP_LOOKUP_SYMBOLS = [
     ("rptgpu_render_views_lightmapped_device", C.c_int, [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.c_uint32,
                                                          C.POINTER(RptLightmapBinding), C.POINTER(RptViewsLightmapQuery), _VP, _VP]),
 ]
+# ... and every symbol include/rpt_gpu_probe_volume.h declares, optional in the same way (probe_volume_supported())
+_VOLUME_ARGS = [C.POINTER(RptProbeVolume), C.POINTER(RptVolumeQuery), C.POINTER(RptVolumeArrays)]
+_VIEWS_PROBE_LIT_ARGS = [_VP, C.c_uint64, C.POINTER(RptView), C.POINTER(RptViewQuery), C.c_uint32, C.POINTER(RptLightmapBinding),
+                         C.POINTER(RptProbeVolume), C.POINTER(RptViewsProbeLitQuery)]
+PROBE_VOLUME_SYMBOLS = [
+    ("rptgpu_sample_probe_volume", C.c_int, [_VP, C.c_uint64, _PD, _PD] + _VOLUME_ARGS),
+    ("rptgpu_sample_probe_volume_device", C.c_int, [_VP, C.c_uint64, _VP, _VP] + _VOLUME_ARGS + [_VP]),
+    ("rptgpu_lookup_probe_volume", C.c_int, [_VP, C.c_uint64, _PD, _PD] + _VOLUME_ARGS),
+    ("rptgpu_lookup_probe_volume_device", C.c_int, [_VP, C.c_uint64, _VP, _VP] + _VOLUME_ARGS + [_VP]),
+    ("rptgpu_render_views_probe_lit", C.c_int, _VIEWS_PROBE_LIT_ARGS + [_PD]),
+    ("rptgpu_render_views_probe_lit_device", C.c_int, _VIEWS_PROBE_LIT_ARGS + [_VP, _VP]),
+]
 
 
 class RptGpuError(RuntimeError):
@@ -516,11 +557,11 @@ def load_library(path=None):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
-    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS + LIGHTMAP_SYMBOLS + LIGHTMAP_FILTER_SYMBOLS + DIRECT_SYMBOLS + LIGHTMAP_LOOKUP_SYMBOLS:
+    for name, restype, argtypes in RAYS_PERSISTENT_SYMBOLS + VERTICES_PERSISTENT_SYMBOLS + HIT_SURFACE_SYMBOLS + LIGHTMAP_SYMBOLS + LIGHTMAP_FILTER_SYMBOLS + DIRECT_SYMBOLS + LIGHTMAP_LOOKUP_SYMBOLS + PROBE_VOLUME_SYMBOLS:
         try:
             fn = getattr(lib, name)
         except AttributeError:
-            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported(), lightmap_supported(), lightmap_filter_supported(), direct_supported(), lightmap_lookup_supported() say no)
+            continue  # (an older library, by path or RPTGPU_LIB: still ABI 7 — rays_ / vertices_persistent_supported(), hit_surface_supported(), lightmap_supported(), lightmap_filter_supported(), direct_supported(), lightmap_lookup_supported(), probe_volume_supported() say no)
         fn.restype = restype
         fn.argtypes = argtypes
     if lib.rptgpu_abi_version() != ABI_VERSION:
@@ -592,6 +633,13 @@ def direct_supported(lib=None):
     (include/rpt_gpu_direct.h)?  Detected by symbol, as a C caller does with dlsym: a library without them is still ABI 7."""
     lib = lib or load_library()
     return all(hasattr(lib, name) for name, _, _ in DIRECT_SYMBOLS)
+
+
+def probe_volume_supported(lib=None):
+    """Does the library export rptgpu_sample_probe_volume and the other five symbols of include/rpt_gpu_probe_volume.h?
+    Detected by symbol, as a C caller does with dlsym: a library without them is still ABI 7."""
+    lib = lib or load_library()
+    return all(hasattr(lib, name) for name, _, _ in PROBE_VOLUME_SYMBOLS)
 
 
 def lightmap_lookup_supported(lib=None):

@@ -21,6 +21,10 @@ LIGHTMAP_CHANNELS = ((_abi.RPT_LIGHTMAP_IRRADIANCE, "irradiance", (3,), np.float
 LOOKUP_CHANNELS = ((_abi.RPT_LOOKUP_T, "t", (), np.float64), (_abi.RPT_LOOKUP_OBJECT, "object", (), np.int32),
                    (_abi.RPT_LOOKUP_BINDING, "binding", (), np.int32), (_abi.RPT_LOOKUP_COVERED, "covered", (), np.uint8),
                    (_abi.RPT_LOOKUP_UV, "uv", (2,), np.float64), (_abi.RPT_LOOKUP_VALUE, "value", (3,), np.float64))
+VOLUME_CHANNELS = ((_abi.RPT_VOLUME_T, "t", (), np.float64), (_abi.RPT_VOLUME_OBJECT, "object", (), np.int32),
+                   (_abi.RPT_VOLUME_POSITION, "position", (3,), np.float64), (_abi.RPT_VOLUME_NORMAL, "normal", (3,), np.float64),
+                   (_abi.RPT_VOLUME_VALUE, "value", (3,), np.float64), (_abi.RPT_VOLUME_COVERED, "covered", (), np.uint8),
+                   (_abi.RPT_VOLUME_INSIDE, "inside", (), np.uint8))
 # rptgpu_trace_vertices': (bit, name, "path" | "vertex" | "ray", shape behind it, dtype)
 VERTEX_CHANNELS = ((_abi.RPT_VERTEX_LENGTH, "length", "path", (), np.uint32), (_abi.RPT_VERTEX_T, "t", "vertex", (), np.float64),
                    (_abi.RPT_VERTEX_NORMAL, "normal", "vertex", (3,), np.float64),

@@ -46,6 +46,11 @@
 //                    api_hits.cpp's first-hit query and api_surface.cpp's resolve walk into arrays the handle keeps, then
 //                    rpt_lightmap_lookup, one lane per ray (the kernel: kernels_lightmap_lookup.hip; the sizes:
 //                    lightmap_lookup_plan.h)
+//   api_probe_volume.cpp rptgpu_sample_probe_volume[_device], rptgpu_lookup_probe_volume[_device]: a grid of SH9 probes read at the
+//                    caller's points (one kernel per piece) and at the first hits of its rays (api_hits.cpp's query, then one
+//                    kernel), and rptgpu_render_views_probe_lit[_device] through api_lightmap_lookup.cpp's views driver with
+//                    the volume's step (the kernels: kernels_probe_volume.hip, kernels_probe_volume_views.hip; the sizes:
+//                    probe_volume_plan.h)
 //   api_mesh.cpp     rptgpu_scene_set_mesh[_device]: a deformed mesh's records and tree into the second set of the geometry
 //                    arrays, then the swap (the kernels: mesh_update.hip)
 //   api_group.cpp    rptgpu_scene_set_group[_device]: a group's moved children — their records, the group's tree — the same
@@ -85,6 +90,8 @@
 #include "lightmap_lookup_plan.h"
 #include "lightmap_lookup.h"
 #include "lightmap_views.h"
+#include "probe_volume_plan.h"
+#include "probe_volume.h"
 
 namespace rptapi {
 
@@ -235,6 +242,9 @@ struct rptgpu_scene {
   DevBuf<double> lk_piece, lk_stage;
   DevBuf<rptlookup::Binding> lk_bindings;
   DevBuf<int32_t> lk_table;
+  // rptgpu_sample_probe_volume, rptgpu_lookup_probe_volume, rptgpu_render_views_probe_lit (api_probe_volume.cpp): a piece's
+  // arrays (probe_volume_plan.h layout) and a host caller's coefficients and valid bytes, staged whole (stage_volume)
+  DevBuf<double> pv_piece, pv_stage;
   DevBuf<double> vertices_out;         // rptgpu_trace_vertices: a piece of a host caller's records, the named channels back to back (api_vertices.cpp)
   DevBuf<rptdev::View> view_recs;     // rptgpu_render_views: the call's views (api_views.cpp)
   DevBuf<uint64_t> view_seeds;         // ... their seeds, when the views have seeds of their own,
@@ -507,6 +517,35 @@ GenericStack ensure_surface_columns(rptgpu_scene* h, uint64_t piece);
 bool group_holds_monomial(const rptgpu_scene* h);
 void surface_walk_piece(rptgpu_scene* h, const double* d_o, const double* d_d, uint32_t m, const rptdev::SurfaceOut& so,
                         const GenericStack& gs, bool from_inf);
+// api_lightmap_lookup.cpp: what rptgpu_render_views_probe_lit (api_probe_volume.cpp) shares with
+// rptgpu_render_views_lightmapped.  bad_bindings / bad_bindings_for: what is wrong with the bindings by themselves / against
+// the handle's scene (empty: nothing); stage_bindings: a host caller's bindings' arrays inside one allocation -> the words, or
+// ~0 when no allocation holds them (BINDINGS_TOO_LARGE); upload_bindings: the call's binding records and object-to-binding
+// table on the device, into `rays` (table and recs are the caller's: the uploads read them until the call's last
+// synchronisation)
+std::string bad_bindings(uint32_t n_bindings, const RptLightmapBinding* b);
+std::string bad_bindings_for(const rptgpu_scene* h, uint32_t n_bindings, const RptLightmapBinding* b);
+uint64_t stage_bindings(uint32_t n_bindings, const RptLightmapBinding* bindings, bool on_device, std::vector<rptlookup::Staged>& staged);
+constexpr const char* BINDINGS_TOO_LARGE = "the bindings' maps do not fit: no allocation holds them";
+void upload_bindings(rptgpu_scene* h, uint32_t n_bindings, const RptLightmapBinding* bindings, bool on_device,
+                     const std::vector<rptlookup::Staged>& staged, uint64_t stage_words, std::vector<int32_t>& table,
+                     std::vector<rptlookup::Binding>& recs, rptlookup::Rays& rays);
+// ... and the driver the two calls share (api_lightmap_lookup.cpp): rptgpu_render_views' refusals of qv, then bad_own_query — what
+// is wrong with the call's own query (nullptr: nothing) —, then out, the views, the bindings, the handle; `lit` is read only
+// when bad_own_query is nullptr.  volume == nullptr: rptgpu_render_views_lightmapped
+struct ViewsLit {
+  uint32_t filter;                // RPT_LOOKUP_NEAREST / _BILINEAR
+  const double* unbound;          // [3] I of a hit nothing covers
+  const RptProbeVolume* volume;   // checked by the caller (api_probe_volume.cpp bad_volume), or nullptr
+  double normal_bias;             // the volume rule's
+};
+int render_views_lit(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* qv, uint32_t n_bindings,
+                     const RptLightmapBinding* bindings, const char* bad_own_query, const ViewsLit& lit, double* out, bool on_device,
+                     hipStream_t user_stream);
+// api_probe_volume.cpp: the volume as the kernels read it — a device caller's arrays as they are, a host caller's staged
+// whole on the handle's stream —, and RPTGPU_VOLUME_PIECE's value (0: not set)
+rptvolume::Volume upload_volume(rptgpu_scene* h, const RptProbeVolume& v, double normal_bias, bool on_device);
+uint64_t asked_volume_piece();
 // f64 words of a probe's result and of its running sums: [9][3] SH coefficients, or an RGB irradiance
 inline uint32_t probe_width(uint32_t kind) { return kind == RPT_PROBE_SH9 ? 27u : 3u; }
 const char* bad_probe_query(const RptProbeQuery* q);

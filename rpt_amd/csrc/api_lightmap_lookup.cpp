@@ -46,6 +46,9 @@ const char* bad_lookup_arrays(const RptLookupArrays* o, uint32_t channels) {
   if ((channels & RPT_LOOKUP_VALUE) && !o->value) return "RptLookupArrays: RPT_LOOKUP_VALUE is named but value is NULL";
   return nullptr;
 }
+} // namespace
+
+// (the bindings' checks and uploads are rptgpu_render_views_probe_lit's too: api_internal.h, api_probe_volume.cpp)
 // what is wrong with the bindings by themselves (empty: nothing)
 std::string bad_bindings(uint32_t n_bindings, const RptLightmapBinding* b) {
   if (n_bindings && !b) return "null bindings with n_bindings > 0";
@@ -79,6 +82,8 @@ std::string bad_bindings_for(const rptgpu_scene* h, uint32_t n_bindings, const R
   }
   return "";
 }
+
+namespace {
 
 // the arrays of a piece on the device, and the caller's
 struct PieceArrays {
@@ -121,6 +126,8 @@ void copy_lookup_out(const PieceArrays& src, const PieceArrays& dst, uint32_t ch
   if (ch & RPT_LOOKUP_UV) HIP_TRY(hipMemcpyAsync(dst.uv, src.uv, 2 * m * sizeof(double), hipMemcpyDeviceToHost, st));
   if (ch & RPT_LOOKUP_VALUE) HIP_TRY(hipMemcpyAsync(dst.value, src.value, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
 }
+
+} // namespace
 
 // the call's binding records and object-to-binding table on the device (a host caller's arrays staged whole), into `rays`.
 // table and recs are the caller's: the uploads read them until the call's last synchronisation
@@ -165,7 +172,9 @@ uint64_t stage_bindings(uint32_t n_bindings, const RptLightmapBinding* bindings,
     }
   return words;
 }
-constexpr const char* TOO_LARGE = "the bindings' maps do not fit: no allocation holds them";
+
+namespace {
+constexpr const char* TOO_LARGE = BINDINGS_TOO_LARGE;
 
 // on_device: origins, dirs, out's arrays and every binding's uvs / map / valid are device pointers
 int lookup_lightmap(rptgpu_scene* h, uint64_t n, const double* origins, const double* dirs, uint32_t n_bindings,
@@ -264,12 +273,18 @@ const char* bad_views_lightmap_query(const RptViewsLightmapQuery* q) {
   return nullptr;
 }
 
-// on_device: out and every binding's uvs / map / valid are device pointers; views and the structs are host memory either way
-int render_views_lightmapped(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* qv, uint32_t n_bindings,
-                             const RptLightmapBinding* bindings, const RptViewsLightmapQuery* q, double* out, bool on_device,
-                             hipStream_t user_stream) {
+} // namespace
+
+// The one driver behind rptgpu_render_views_lightmapped[_device] and rptgpu_render_views_probe_lit[_device] (api_internal.h).
+// on_device: out, every binding's uvs / map / valid and the volume's coeffs / valid are device pointers; views and the structs
+// are host memory either way.  lit.volume == nullptr: the lightmapped call, as it always ran.  With a volume: the first-hit
+// query also writes NORMAL and POSITION (into the handle's pv_piece), rpt_views_probe_lit_merge stands in front of the fold,
+// and without bindings the resolve walk and the lookup are not run
+int render_views_lit(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* qv, uint32_t n_bindings,
+                     const RptLightmapBinding* bindings, const char* bad_own_query, const ViewsLit& lit, double* out, bool on_device,
+                     hipStream_t user_stream) {
   if (const char* why = bad_view_query(qv)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
-  if (const char* why = bad_views_lightmap_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (bad_own_query) return fail(h, RPTGPU_E_INVALID_ARGUMENT, bad_own_query);
   if (!out) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null out");
   if (n_views && !views) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
   const uint64_t npix = (uint64_t)qv->width * qv->height;
@@ -283,7 +298,7 @@ int render_views_lightmapped(rptgpu_scene* h, uint64_t n_views, const RptView* v
   }
   std::vector<rptlookup::Staged> staged;
   const uint64_t stage_words = stage_bindings(n_bindings, bindings, on_device, staged);
-  if (stage_words == ~0ull) return fail(h, RPTGPU_E_INVALID_ARGUMENT, TOO_LARGE);
+  if (stage_words == ~0ull) return fail(h, RPTGPU_E_INVALID_ARGUMENT, BINDINGS_TOO_LARGE);
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   {
     const std::string why = bad_bindings_for(h, n_bindings, bindings);
@@ -300,6 +315,8 @@ int render_views_lightmapped(rptgpu_scene* h, uint64_t n_views, const RptView* v
     hipStream_t st = h->stream;
     const KernelTable* kt = table_for(qv->precision_mode, h->ext_shapes);
     const bool prof = (qv->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
+    const bool with_volume = lit.volume != nullptr;
+    const bool fetch = !with_volume || n_bindings != 0; // (a volume without bindings: no ray is covered by a lightmap)
     // the views' device records: the camera constants by the host function a render uses (as rptgpu_render_views)
     for (uint64_t v = 0; v < n_views; v++) {
       view_recs[v].cam = make_camera(views[v].camera);
@@ -316,6 +333,7 @@ int render_views_lightmapped(rptgpu_scene* h, uint64_t n_views, const RptView* v
     uint64_t piece = rptplan::views_piece(n, asked, piece_pass_target(h, 1, 0));
     HitPieces hp = plan_hit_pieces(h, piece, qv->flags, "RPTGPU_LOOKUP_PIECE");
     piece = std::min(piece, hp.piece);
+    if (with_volume) piece = rptvolume::piece(piece, asked_volume_piece(), piece); // (RPTGPU_VOLUME_PIECE caps it too)
     ensure_workspace(h, piece, 1); // rpt_raygen_views' columns (the per-tree query's own, where that route runs)
     const rptdev::PathState ps = path_state(h);
     if (hp.by_object) hp.ps = ps;
@@ -327,17 +345,40 @@ int render_views_lightmapped(rptgpu_scene* h, uint64_t n_views, const RptView* v
     const rptlookup::Layout lay = rptlookup::layout(piece, CH, false);
     h->lk_piece.alloc(lay.words);
     const PieceArrays dev = lookup_arrays_in(h->lk_piece.p, lay);
-    const GenericStack gs = ensure_surface_columns(h, piece);
-    const bool from_inf = group_holds_monomial(h);
+    // the first hit's record: T and OBJECT in the lookup's arrays — with a volume all four of the query's in the volume's
+    rptdev::HitOut ho{};
+    ho.channels = RPT_HIT_T | RPT_HIT_OBJECT; ho.t = dev.t; ho.object = dev.object;
+    if (with_volume) {
+      const rptvolume::Layout vlay = rptvolume::layout(piece, 0, true, true);
+      h->pv_piece.alloc(vlay.words);
+      double* base = h->pv_piece.p;
+      ho.channels |= RPT_HIT_NORMAL | RPT_HIT_POSITION;
+      ho.t = base + vlay.t; ho.object = (int32_t*)(base + vlay.object);
+      ho.normal = base + vlay.normal; ho.position = base + vlay.position;
+    }
+    GenericStack gs{};
+    bool from_inf = false;
     rptlookup::Rays rays{};
-    upload_bindings(h, n_bindings, bindings, on_device, staged, stage_words, table, recs, rays);
-    rays.filter = q->filter;
-    rays.channels = CH;
-    rays.object = dev.object; rays.primitive = dev.primitive; rays.barycentric = dev.barycentric;
-    rays.covered = dev.covered; rays.value = dev.value;
+    if (fetch) {
+      gs = ensure_surface_columns(h, piece);
+      from_inf = group_holds_monomial(h);
+      upload_bindings(h, n_bindings, bindings, on_device, staged, stage_words, table, recs, rays);
+      rays.filter = lit.filter;
+      rays.channels = CH;
+      rays.object = ho.object; rays.primitive = dev.primitive; rays.barycentric = dev.barycentric;
+      rays.covered = dev.covered; rays.value = dev.value;
+    }
+    rptvolume::Volume dv{};
+    rptvolumeviews::Merge mg{};
+    if (with_volume) {
+      dv = upload_volume(h, *lit.volume, lit.normal_bias, on_device);
+      mg.dirs = h->rays_d.p; mg.object = ho.object; mg.normal = ho.normal; mg.position = ho.position;
+      mg.lightmaps = fetch ? 1u : 0u;
+      mg.covered = dev.covered; mg.value = dev.value;
+    }
     rptlookupviews::Sample smp{};
-    smp.object = dev.object; smp.dirs = h->rays_d.p; smp.covered = dev.covered; smp.value = dev.value;
-    smp.unbound[0] = q->unbound_irradiance[0]; smp.unbound[1] = q->unbound_irradiance[1]; smp.unbound[2] = q->unbound_irradiance[2];
+    smp.object = ho.object; smp.dirs = h->rays_d.p; smp.covered = dev.covered; smp.value = dev.value;
+    smp.unbound[0] = lit.unbound[0]; smp.unbound[1] = lit.unbound[1]; smp.unbound[2] = lit.unbound[2];
     smp.iterations = (double)qv->iterations;
     smp.ev_scale = std::pow(2.0, qv->exposure_value);
     for (uint64_t base = 0; base < n; base += piece) {
@@ -355,14 +396,16 @@ int render_views_lightmapped(rptgpu_scene* h, uint64_t n_views, const RptView* v
         HIP_TRY(hipGetLastError());
         HIP_TRY(rptlookupviews::gather_rays(st, ps.ray, ps.cap, m, h->rays_o.p, h->rays_d.p));
         // 2. the ray form's steps: the first hit, the surface element, the fetch
-        rptdev::HitOut ho{};
-        ho.channels = RPT_HIT_T | RPT_HIT_OBJECT; ho.t = dev.t; ho.object = dev.object;
         hit_piece(h, kt, hp, h->rays_o.p, h->rays_d.p, m, ho, prof);
-        rptdev::SurfaceOut so{};
-        so.t = dev.t; so.object = dev.object; so.primitive = dev.primitive; so.barycentric = dev.barycentric;
-        so.channels = RPT_SURFACE_PRIMITIVE | RPT_SURFACE_BARYCENTRIC;
-        surface_walk_piece(h, h->rays_o.p, h->rays_d.p, m, so, gs, from_inf);
-        HIP_TRY(rptlookup::lookup(st, m, rays));
+        if (fetch) {
+          rptdev::SurfaceOut so{};
+          so.t = ho.t; so.object = ho.object; so.primitive = dev.primitive; so.barycentric = dev.barycentric;
+          so.channels = RPT_SURFACE_PRIMITIVE | RPT_SURFACE_BARYCENTRIC;
+          surface_walk_piece(h, h->rays_o.p, h->rays_d.p, m, so, gs, from_inf);
+          HIP_TRY(rptlookup::lookup(st, m, rays));
+        }
+        // ... and the volume where no lightmap covers the hit, into the lookup's arrays
+        if (with_volume) HIP_TRY(rptvolumeviews::merge(st, m, dv, mg));
         // 3. the sample into the frame's sums
         smp.first = s == 0; smp.last = s + 1 == qv->iterations;
         HIP_TRY(rptlookupviews::fold(st, h->dscene, m, smp, frame));
@@ -372,8 +415,19 @@ int render_views_lightmapped(rptgpu_scene* h, uint64_t n_views, const RptView* v
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
-    return h->gen_overflow.p != nullptr;
+    return (fetch || h->has_deep) && h->gen_overflow.p;
   });
+}
+
+namespace {
+
+int render_views_lightmapped(rptgpu_scene* h, uint64_t n_views, const RptView* views, const RptViewQuery* qv, uint32_t n_bindings,
+                             const RptLightmapBinding* bindings, const RptViewsLightmapQuery* q, double* out, bool on_device,
+                             hipStream_t user_stream) {
+  const char* why = bad_views_lightmap_query(q);
+  ViewsLit lit{};
+  if (!why) { lit.filter = q->filter; lit.unbound = q->unbound_irradiance; }
+  return render_views_lit(h, n_views, views, qv, n_bindings, bindings, why, lit, out, on_device, user_stream);
 }
 
 } // namespace

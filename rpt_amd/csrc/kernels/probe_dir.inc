@@ -1,5 +1,5 @@
 // kernels/probe_dir.inc — what the two routes of rptgpu_bake_probes share: a light probe's direction from its stream and the SH9
-// basis.  Included by wavefront.inc (rpt_raygen_probes, rpt_resolve_probes) and by paths_rays.inc (rpt_paths_rays,
+// basis (kernels/sh9_basis.inc).  Included by wavefront.inc (rpt_raygen_probes, rpt_resolve_probes) and by paths_rays.inc (rpt_paths_rays,
 // rpt_project_probes): ONE text, so the two routes cannot drift apart.
 // Part of kernels.inc (included inside namespace RPT_NS; see that file for the build variants).
 
@@ -15,17 +15,5 @@ RPT_DEV D3 probe_direction(uint32_t kind, D3 normal, Rng& rng) {
   return mk(x1 * r, x2 * r, 1.0 - 2.0 * s);
 }
 
-// The real spherical harmonics of bands 0-2 at the unit vector d, in the order (0,0), (1,-1), (1,0), (1,1), (2,-2) .. (2,2)
-// and with the expressions include/rpt_gpu.h fixes (rpt_amd.sh9_basis restates them).
-RPT_DEV void sh9_basis(D3 d, double (&Y)[9]) {
-  const double x = d.x, y = d.y, z = d.z;
-  Y[0] = 0.28209479177387814;
-  Y[1] = 0.4886025119029199 * y;
-  Y[2] = 0.4886025119029199 * z;
-  Y[3] = 0.4886025119029199 * x;
-  Y[4] = 1.0925484305920792 * (x * y);
-  Y[5] = 1.0925484305920792 * (y * z);
-  Y[6] = 0.31539156525252005 * (3.0 * (z * z) - 1.0);
-  Y[7] = 1.0925484305920792 * (x * z);
-  Y[8] = 0.5462742152960396 * (x * x - y * y);
-}
+// sh9_basis, in a file of its own: the probe volume's kernels (kernels/probe_volume.inc) take it without this file's sampler
+#include "sh9_basis.inc"

@@ -546,6 +546,108 @@ class GpuScene:
         del keep
         return frames
 
+    def _volume_call(self, name, who, a, b, names, volume, normal_bias, fallback, channels, flags):
+        """sample_probe_volume's and lookup_probe_volume's one body: the query, the volume, the pair of (n, 3) inputs, the
+        named channels' arrays -> the dict"""
+        if not _abi.probe_volume_supported(self.lib):
+            raise _abi.RptGpuError(_abi.RPTGPU_E_INVALID_ARGUMENT, "this library does not export " + name)
+        q = _abi.RptVolumeQuery()
+        q.struct_size, q.channels, q.normal_bias = C.sizeof(q), int(channels), float(normal_bias)
+        q.fallback = _abi.V3(*(float(x) for x in fallback))
+        q.precision_mode, q.flags = _abi.RPT_PRECISION_F64_STRICT, int(flags)
+        m = _marshal.pick(self.device, a, b, volume.coeffs, volume.valid)
+        rec, keep = self._lower_volume(m, volume, who)
+        arrays = _abi.RptVolumeArrays()
+        arrays.struct_size, arrays.reserved = C.sizeof(arrays), 0
+        n, a, b = self._pair(m, a, b, who, names)
+        out = m.fill(arrays, _marshal.layout(_marshal.VOLUME_CHANNELS, q.channels, (n,)), who)
+        PD = C.POINTER(C.c_double)
+        self._call(name, m, n, m.pointer(a, PD), m.pointer(b, PD), C.byref(rec), C.byref(q), C.byref(arrays))
+        del keep
+        return out
+
+    def sample_probe_volume(self, positions, normals, volume, *, normal_bias=0.0, fallback=(0.0, 0.0, 0.0),
+                            channels=_abi.RPT_VOLUME_POINT):
+        """The irradiance a grid of baked SH9 probes gives at the caller's points (rptgpu_sample_probe_volume)
+        -> a dict with one array per channel of `channels`: `value` (n, 3) float64 — the eight probes around positions[i] +
+        normal_bias * normals[i], interpolated trilinearly (clamped to the grid, probes that are not valid left out and
+        the weights renormalised) and convolved with the clamped cosine about normals[i], used as given; `fallback` where
+        the point is not covered —, `covered` (n,) uint8 and `inside` (n,) uint8, 1 where the point lies within the grid.
+        No ray is traced: the handle supplies the device.  volume: a probes.ProbeVolume.  numpy arrays go through host
+        memory; torch tensors on the handle's device — points and the volume's arrays alike — are read where they lie
+        (rptgpu_sample_probe_volume_device) and the results are new tensors there."""
+        return self._volume_call("rptgpu_sample_probe_volume", "sample_probe_volume", positions, normals, self._POINTS, volume,
+                                 normal_bias, fallback, channels, 0)
+
+    def lookup_probe_volume(self, origins, dirs, volume, *, normal_bias=0.0, fallback=(0.0, 0.0, 0.0),
+                            channels=_abi.RPT_VOLUME_ALL, flags=0):
+        """The same at the first hit of each of the caller's rays (rptgpu_lookup_probe_volume) -> a dict: `t`,
+        `object`, `position` — first_hits' —, `normal` — first_hits' faced to the ray —, and sample_probe_volume's `value`,
+        `covered`, `inside` at that position and normal.  A miss is not covered: `value` is `fallback`, `position` and
+        `normal` are zero.  origins, dirs: (n, 3) float64, used as given; numpy or torch as for sample_probe_volume."""
+        return self._volume_call("rptgpu_lookup_probe_volume", "lookup_probe_volume", origins, dirs, self._RAYS, volume,
+                                 normal_bias, fallback, channels, flags)
+
+    def render_views_probe_lit(self, views, width, height, bindings, volume, *, samples=1, seed, seed_stride=0,
+                               sample_index_base=0, exposure_value=0.0, filter="bilinear", normal_bias=0.0,
+                               unbound_irradiance=(0.0, 0.0, 0.0), flags=0, out=None):
+        """render_views_lightmapped with one change (rptgpu_render_views_probe_lit): the irradiance of a hit is
+        the bound lightmap's where that covers it, else lookup_probe_volume's `value` cut at zero where `volume` covers it,
+        else `unbound_irradiance`.  So what moves on a live handle, and has no chart that stays true, is lit by the probes.
+        bindings may be empty.  numpy arrays — the frames then come through host memory — or torch tensors on the
+        handle's device, bindings and volume alike, which give a new tensor there (out="torch" is not needed: the volume
+        tells)."""
+        if not _abi.probe_volume_supported(self.lib):
+            raise _abi.RptGpuError(_abi.RPTGPU_E_INVALID_ARGUMENT, "this library does not export rptgpu_render_views_probe_lit")
+        who = "render_views_probe_lit"
+        if filter not in self._FILTERS:
+            raise ValueError('%s: filter must be "nearest" or "bilinear", not %r' % (who, filter))
+        if out not in (None, "torch"):
+            raise ValueError('%s: out must be None or "torch"' % who)
+        n, arr, _, qv = self._view_query(who, views, width, height, 0, samples, exposure_value, seed, seed_stride, None,
+                                         sample_index_base, flags)
+        q = _abi.RptViewsProbeLitQuery()
+        q.struct_size, q.filter, q.normal_bias = C.sizeof(q), self._FILTERS[filter], float(normal_bias)
+        q.unbound_irradiance = _abi.V3(*(float(x) for x in unbound_irradiance))
+        bindings = list(bindings)
+        m = _marshal._Device(self.device) if out == "torch" else \
+            _marshal.pick(self.device, volume.coeffs, volume.valid, *(x for b in bindings for x in (b.uvs, b.map, b.valid)))
+        recs, keep = self._lower_bindings(m, bindings, who)
+        rec, keep_volume = self._lower_volume(m, volume, who)
+        frames = m.result(None, (n, int(height), int(width), 3), np.float64, who, "out")
+        self._call("rptgpu_render_views_probe_lit", m, n, arr, C.byref(qv), len(bindings), recs, C.byref(rec), C.byref(q),
+                   m.pointer(frames, C.POINTER(C.c_double)))
+        del keep, keep_volume
+        return frames
+
+    @staticmethod
+    def _lower_volume(m, volume, who):
+        """a probes.ProbeVolume -> (an RptProbeVolume, the arrays its pointers point into)"""
+        nx, ny, nz = volume.counts
+        count = nx * ny * nz
+        c = volume.coeffs if hasattr(volume.coeffs, "shape") else np.asarray(volume.coeffs)
+        shape = tuple(int(x) for x in c.shape)
+        if min(nx, ny, nz) < 0 or shape not in ((nz, ny, nx, 9, 3), (count, 9, 3)):
+            raise ValueError("%s: volume.coeffs must be a (nz, ny, nx, 9, 3) or (nx * ny * nz, 9, 3) float64 array for counts %s"
+                             % (who, (nx, ny, nz)))
+        coeffs = m.result(c, shape, np.float64, who, "volume.coeffs")
+        types = dict(_abi.RptProbeVolume._fields_)
+        r = _abi.RptProbeVolume()
+        r.struct_size, r.nx, r.ny, r.nz, r.reserved = C.sizeof(r), nx, ny, nz, 0
+        r.origin, r.spacing = _abi.V3(*volume.origin), _abi.V3(*volume.spacing)
+        # (an empty array has no address the library would take: it refuses a count of 0 before it looks)
+        r.coeffs = m.field(coeffs, types["coeffs"]) if count else None
+        keep = [coeffs]
+        if volume.valid is not None:
+            v = volume.valid if hasattr(volume.valid, "shape") else np.asarray(volume.valid)
+            vshape = tuple(int(x) for x in v.shape)
+            if vshape not in ((nz, ny, nx), (count,)):
+                raise ValueError("%s: volume.valid must be a (nz, ny, nx) or (nx * ny * nz,) uint8 or bool array" % who)
+            valid = m.flags(v, vshape, who, "volume.valid")
+            r.valid = m.field(valid, types["valid"]) if count else None
+            keep.append(valid)
+        return r, keep
+
     @staticmethod
     def _lower_bindings(m, bindings, who):
         """lightmap.Binding records -> (an RptLightmapBinding array or None, the arrays its pointers point into)"""

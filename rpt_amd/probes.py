@@ -37,3 +37,42 @@ def sh9_irradiance(coeffs, normals):
         raise ValueError("sh9_irradiance: coeffs must be (..., 9, 3)")
     y = sh9_basis(normals) * _BAND
     return np.einsum("...j,...jc->...c", y, c)
+
+
+class ProbeVolume:
+    """A regular grid of SH9 probes, for GpuScene.sample_probe_volume, lookup_probe_volume and render_views_probe_lit
+    (include/rpt_gpu_probe_volume.h).  counts = (nx, ny, nz); probe (i, j, k) stands at origin + (i, j, k) *
+    spacing and has index (k * ny + j) * nx + i; coeffs is (nz, ny, nx, 9, 3) float64 — or (n, 9, 3) in index order, what
+    bake_probes(kind=RPT_PROBE_SH9) returns for positions() —; valid (nz, ny, nx) or (n,) uint8 or bool, non-zero where the
+    probe holds a value, or None: every probe does.  numpy arrays or torch tensors on the handle's device, both of one
+    kind; the calls check them."""
+
+    def __init__(self, origin, spacing, counts, coeffs, valid=None):
+        self.origin = tuple(float(x) for x in origin)
+        self.spacing = tuple(float(x) for x in spacing)
+        self.counts = tuple(int(x) for x in counts)
+        if len(self.origin) != 3 or len(self.spacing) != 3 or len(self.counts) != 3:
+            raise ValueError("ProbeVolume: origin, spacing and counts have three entries each")
+        self.coeffs, self.valid = coeffs, valid
+
+    @staticmethod
+    def positions(origin, spacing, counts):
+        """The probes' positions -> (nx * ny * nz, 3) float64 in index order: x runs fastest, then y, then z; each
+        coordinate is origin + index * spacing, one multiply and one add."""
+        nx, ny, nz = (int(c) for c in counts)
+        o, h = np.asarray(origin, dtype=np.float64), np.asarray(spacing, dtype=np.float64)
+        k, j, i = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+        idx = np.stack([i.reshape(-1), j.reshape(-1), k.reshape(-1)], axis=1).astype(np.float64)
+        return o + idx * h
+
+    @classmethod
+    def bake(cls, gpu_scene, origin, spacing, counts, *, samples, max_bounces, seed, flags=0, device=False):
+        """bake_probes(kind=RPT_PROBE_SH9) over positions(origin, spacing, counts), wrapped: probe p's stream id is p.
+        device=True: the positions go to the handle's device as a torch tensor and the coefficients stay there."""
+        from ._abi import RPT_PROBE_SH9
+        pos = cls.positions(origin, spacing, counts)
+        if device:
+            import torch
+            pos = torch.from_numpy(pos).to(torch.device("cuda", int(gpu_scene.device)))
+        coeffs = gpu_scene.bake_probes(pos, kind=RPT_PROBE_SH9, samples=samples, max_bounces=max_bounces, seed=seed, flags=flags)
+        return cls(origin, spacing, counts, coeffs)
