@@ -141,7 +141,6 @@ extern "C" int rptgpu_render_aov(rptgpu_scene* h, const RptCamera* camera, const
   if (h->abandoned)
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "an aborted batch's device work never drained on this handle: destroy it");
   return guarded(h, h->device, [&]() -> int {
-    (void)hipGetLastError(); // (as render_impl: the checks below speak about this call's launches)
     hipStream_t st = h->stream;
     ensure_partition(h, *p);
     const uint64_t n = (uint64_t)p->width * p->height;

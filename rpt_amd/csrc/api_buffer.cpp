@@ -290,7 +290,6 @@ int rptgpu_buffer_features(rptgpu_buffer* b, const RptCamera* camera, const RptR
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "an aborted batch's device work never drained on this handle: destroy it");
   b->has_features = false; // (until the new ones are complete)
   return guarded(h, h->device, [&]() -> int {
-    (void)hipGetLastError();
     ensure_partition(h, *params);
     b->feat = aov_arrays(b->feat_arrays, h->stream, (uint64_t)b->width * b->height, FEATURE_CHANNELS);
     const bool read_overflow = aov_enqueue(h, *camera, *params, b->feat);
@@ -326,7 +325,6 @@ int rptgpu_buffer_denoise(rptgpu_buffer* b, const RptDenoise* d, double* out_lin
     return fail(h, RPTGPU_E_INVALID_ARGUMENT, "a pixel holds fewer than two batches: there is no variance of one batch");
   REFUSE_IF_ABANDONED(h);
   return guarded(h, h->device, [&]() -> int {
-    (void)hipGetLastError();
     hipStream_t st = h->stream;
     const KernelTable* kt = table_for(RPT_PRECISION_F64_STRICT);
     const uint64_t n = (uint64_t)b->width * b->height;

@@ -364,9 +364,12 @@ int hip_fail(rptgpu_scene* h, const HipError& e);
 // The frame of an entry point that uses the device: select it, run the body (-> the call's code), and map what the body
 // throws to a code and a detail in this one place.  h may be null (the detail then goes to the thread).  Argument checks
 // that need no device stand in front of it.
+// hipGetLastError() reports the thread's LAST failed runtime call, whoever made it (another library in the process, an
+// unchecked clean-up call): the body starts from a clean slate, so that its checks speak about this call's launches.
 template <class Body> int guarded(rptgpu_scene* h, int device, Body&& body) {
   try {
     HIP_TRY(hipSetDevice(device));
+    (void)hipGetLastError();
     return body();
   } catch (const HipError& e) {
     return hip_fail(h, e);
@@ -418,7 +421,7 @@ void event_pair_end(rptgpu_scene* h, int kind, int pair);
 // flag rides with the synchronisation and is cleared, so that the flag of one call never surfaces in the next.
 int drain_call(rptgpu_scene* h, bool read_overflow);
 // The frame of an entry point that runs kernels on the handle's stream, behind its argument checks (h is not null): guarded
-// around the call's clock, a clean slate, the wait for the caller's stream (user_stream: the one the call's device inputs were
+// around the call's clock, the wait for the caller's stream (user_stream: the one the call's device inputs were
 // produced on; nullptr: none, or the body waits itself, where it has to do something first), the body, drain_call.  The
 // body enqueues the call's work and returns drain_call's read_overflow — whether this call ran rpt_tree_generic.  A call that
 // fails leaves RptStats::total_ms as it was.
@@ -430,9 +433,6 @@ template <class Body> int device_call(rptgpu_scene* h, hipStream_t user_stream, 
       rptgpu_scene* h;
       ~EventPairs() { h->pending.clear(); h->ev_used = 0; }
     } event_pairs{h};
-    // hipGetLastError() reports the thread's LAST failed runtime call, whoever made it (another library in the process,
-    // an unchecked clean-up call): start from a clean slate so that the body's checks speak about this call's launches
-    (void)hipGetLastError();
     if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
     const bool read_overflow = body();
     return drain_call(h, read_overflow);

@@ -58,7 +58,6 @@ int render_views_denoised(rptgpu_scene* h, uint64_t n_views, const RptView* view
   const bool seeded = seeds != nullptr;
   // the working set and the state's start: every sum at +0.0, every count at 0
   int rc = guarded(h, h->device, [&]() -> int {
-    (void)hipGetLastError();
     if (user_stream) HIP_TRY(hipStreamSynchronize(user_stream));
     if (!h->vd_thr.p) {
       bool clean = true;

@@ -707,6 +707,31 @@ def test_error_paths_on_device(built):
     ge.close()
 
 
+def test_another_callers_failed_hip_call_is_not_reported_as_this_calls(built):
+    """hipGetLastError() reports the thread's LAST failed runtime call, whoever made it, until somebody reads it: every
+    entry point starts from a clean slate (api_internal.h guarded).  A call of the process's own HIP runtime with an
+    out-of-range ordinal — refused before any device is touched — stands for another library's failed call here.
+    rptgpu_closest_hit, whose only check behind its launch is hipGetLastError, used to report such a failure as its own
+    ("invalid device ordinal" from a call that names no ordinal)."""
+    import ctypes
+    scene, cam, p, g = built("sphere")
+    with open("/proc/self/maps") as f:
+        paths = sorted({ln.split()[-1] for ln in f if "libamdhip64" in ln})
+    assert paths, "the HIP runtime is loaded"
+    hip = ctypes.CDLL(paths[0])  # (loaded already: the same runtime, not a second one)
+    rs = np.random.RandomState(2)
+    o, d = rs.uniform(-3.0, 3.0, (64, 3)) + (0.0, 3.0, 6.0), rs.standard_normal((64, 3)) - (0.0, 0.4, 1.0)
+    want = g.closest_hit(o, d)
+    assert (want[2] >= 0).any()
+    assert hip.hipSetDevice(1 << 20) != 0
+    got = g.closest_hit(o, d)
+    assert all((a.view(np.int64 if a.dtype == np.float64 else np.int32) == b.view(np.int64 if b.dtype == np.float64 else np.int32)).all()
+               for a, b in zip(got, want))
+    assert hip.hipSetDevice(1 << 20) != 0
+    small = make_params(16, 9, 1, 1, seed=3)
+    assert (g.render_batch(cam, small) == g.render_batch(cam, small)).all()
+
+
 def test_bench_two_ranks_equal_one_rank(tmp_path):
     """bench.py's N>1 path on the real GPU: two ranks (gloo stands in for RCCL, both on device 0)
     shard the tiles and reduce; the reduced f32 frame equals the single-rank frame bit for bit."""
