@@ -1,6 +1,7 @@
 // api_aov.cpp — rptgpu_render_aov: first-hit feature buffers (include/rpt_gpu.h; see api_internal.h).
 // Argument checks, the route (one fused kernel, or raygen + closest-hit query + fold in passes), the device arrays of the
-// requested channels, one copy per channel and one synchronisation.  The kernels: kernels/aov.inc.
+// requested channels (RptAovBuffers' table: render_plan.h AOV_ROWS, channel_plan.h), one copy per channel and one
+// synchronisation.  The kernels: kernels/aov.inc.
 // The device half (aov_arrays, aov_enqueue, then drain_call) writes into arrays it is handed: rptgpu_render_aov hands it
 // the handle's own and copies them out (copy_aov_out), rptgpu_buffer_features (api_buffer.cpp) hands it arrays the buffer
 // keeps.
@@ -15,13 +16,9 @@ const char* bad_aov(const RptAovBuffers* o) {
   if (!o) return "null RptAovBuffers";
   if (o->struct_size != sizeof(RptAovBuffers)) return "RptAovBuffers: struct_size is not sizeof(RptAovBuffers)";
   if (o->channels & ~AOV_ALL) return "RptAovBuffers: channels names an unknown RPT_AOV_* bit";
-  if (!o->hits) return "RptAovBuffers: hits is NULL (it is always written)";
-  if ((o->channels & RPT_AOV_DEPTH) && !o->depth) return "RptAovBuffers: RPT_AOV_DEPTH is named but depth is NULL";
-  if ((o->channels & RPT_AOV_NORMAL) && !o->normal) return "RptAovBuffers: RPT_AOV_NORMAL is named but normal is NULL";
-  if ((o->channels & RPT_AOV_ALBEDO) && !o->albedo) return "RptAovBuffers: RPT_AOV_ALBEDO is named but albedo is NULL";
-  if ((o->channels & RPT_AOV_POSITION) && !o->position) return "RptAovBuffers: RPT_AOV_POSITION is named but position is NULL";
-  if ((o->channels & RPT_AOV_OBJECT) && !o->object) return "RptAovBuffers: RPT_AOV_OBJECT is named but object is NULL";
-  return nullptr;
+  if (!o->hits) return rptplan::AOV_ROWS[rptplan::AOV_R_HITS].null_text; // (in front of the channels, whatever its row's bit)
+  const rptchan::Row* r = rptchan::first_null(rptplan::AOV_ROWS, o->channels, o);
+  return r ? r->null_text : nullptr;
 }
 // ... and with the fields of RptRenderParams this call reads (max_bounces, exposure_value and collective are ignored)
 const char* bad_aov_params(const RptRenderParams* p) {
@@ -34,29 +31,31 @@ const char* bad_aov_params(const RptRenderParams* p) {
   return nullptr;
 }
 
-// the device arrays: the f64 channels first, then hits and object, each 16-byte aligned inside `arrays`
-rptdev::AovOut aov_arrays(DevBuf<double>& arrays, hipStream_t st, uint64_t n, uint32_t channels) {
-  const uint64_t words = (n + 3) / 4 * 2; // doubles that hold n 32-bit values, rounded up to 16 bytes
-  uint64_t off = 0, off_depth = 0, off_normal = 0, off_albedo = 0, off_position = 0, off_object = 0;
-  if (channels & RPT_AOV_DEPTH) { off_depth = off; off += (n + 1) / 2 * 2; }
-  if (channels & RPT_AOV_NORMAL) { off_normal = off; off += (3 * n + 1) / 2 * 2; }
-  if (channels & RPT_AOV_ALBEDO) { off_albedo = off; off += (3 * n + 1) / 2 * 2; }
-  if (channels & RPT_AOV_POSITION) { off_position = off; off += (3 * n + 1) / 2 * 2; }
-  const uint64_t off_hits = off;
-  off += words;
-  if (channels & RPT_AOV_OBJECT) { off_object = off; off += words; }
-  arrays.alloc(off);
-  double* base = arrays.p;
+// the kernels' struct from the arrays of rptplan::AOV_ROWS (a channel that is not named: nullptr), and back
+rptdev::AovOut aov_out(const ChannelPtrs& p, uint32_t channels) {
   rptdev::AovOut ao{};
   ao.channels = channels;
-  ao.hits = (uint32_t*)(base + off_hits);
-  if (channels & RPT_AOV_DEPTH) ao.depth = base + off_depth;
-  if (channels & RPT_AOV_NORMAL) ao.normal = base + off_normal;
-  if (channels & RPT_AOV_ALBEDO) ao.albedo = base + off_albedo;
-  if (channels & RPT_AOV_POSITION) ao.position = base + off_position;
-  if (channels & RPT_AOV_OBJECT) ao.object = (int32_t*)(base + off_object);
+  ao.depth = p.at<double>(rptplan::AOV_R_DEPTH); ao.normal = p.at<double>(rptplan::AOV_R_NORMAL);
+  ao.albedo = p.at<double>(rptplan::AOV_R_ALBEDO); ao.position = p.at<double>(rptplan::AOV_R_POSITION);
+  ao.hits = p.at<uint32_t>(rptplan::AOV_R_HITS); ao.object = p.at<int32_t>(rptplan::AOV_R_OBJECT);
+  return ao;
+}
+static ChannelPtrs aov_rows(const rptdev::AovOut& ao) {
+  ChannelPtrs p{};
+  p.p[rptplan::AOV_R_DEPTH] = (char*)ao.depth; p.p[rptplan::AOV_R_NORMAL] = (char*)ao.normal;
+  p.p[rptplan::AOV_R_ALBEDO] = (char*)ao.albedo; p.p[rptplan::AOV_R_POSITION] = (char*)ao.position;
+  p.p[rptplan::AOV_R_HITS] = (char*)ao.hits; p.p[rptplan::AOV_R_OBJECT] = (char*)ao.object;
+  return p;
+}
+
+// the device arrays of `channels` and hits for n pixels inside `arrays` (rptplan::AOV_ROWS' layout)
+rptdev::AovOut aov_arrays(DevBuf<double>& arrays, hipStream_t st, uint64_t n, uint32_t channels) {
+  const rptchan::Layout lay = rptchan::layout(rptplan::AOV_ROWS, channels | rptplan::AOV_HITS, n);
+  arrays.alloc(lay.words);
+  const rptdev::AovOut ao = aov_out(ptrs_in(arrays.p, lay), channels);
   // every sum starts at +0.0 and every count at 0 (also where the part has no pixel); object = -1
-  HIP_TRY(hipMemsetAsync(base, 0, (off_hits + words) * sizeof(double), st));
+  const uint64_t sums_and_hits = lay.off[rptplan::AOV_R_HITS] + rptchan::row_words(rptplan::AOV_ROWS[rptplan::AOV_R_HITS], n);
+  HIP_TRY(hipMemsetAsync(arrays.p, 0, sums_and_hits * sizeof(double), st));
   if (ao.object) HIP_TRY(hipMemsetAsync(ao.object, 0xff, n * sizeof(int32_t), st));
   return ao;
 }
@@ -121,13 +120,9 @@ bool aov_enqueue(rptgpu_scene* h, const RptCamera& camera, const RptRenderParams
   return wavefront && h->has_deep && h->gen_overflow.p;
 }
 
-void copy_aov_out(const rptdev::AovOut& src, uint32_t channels, const RptAovBuffers& dst, uint64_t n, hipStream_t st) {
-  HIP_TRY(hipMemcpyAsync(dst.hits, src.hits, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  if (channels & RPT_AOV_DEPTH) HIP_TRY(hipMemcpyAsync(dst.depth, src.depth, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (channels & RPT_AOV_NORMAL) HIP_TRY(hipMemcpyAsync(dst.normal, src.normal, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (channels & RPT_AOV_ALBEDO) HIP_TRY(hipMemcpyAsync(dst.albedo, src.albedo, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (channels & RPT_AOV_POSITION) HIP_TRY(hipMemcpyAsync(dst.position, src.position, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (channels & RPT_AOV_OBJECT) HIP_TRY(hipMemcpyAsync(dst.object, src.object, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+void copy_aov_out(const rptdev::AovOut& src, uint32_t channels, const ChannelPtrs& dst, uint64_t n, hipStream_t st) {
+  copy_out(rptplan::AOV_ROWS, aov_rows(src), dst, rptplan::AOV_HITS, n, st); // hits first
+  copy_out(rptplan::AOV_ROWS, aov_rows(src), dst, channels, n, st);
 }
 
 } // namespace rptapi
@@ -146,7 +141,7 @@ extern "C" int rptgpu_render_aov(rptgpu_scene* h, const RptCamera* camera, const
     const uint64_t n = (uint64_t)p->width * p->height;
     const rptdev::AovOut ao = aov_arrays(h->aov_out, st, n, out->channels);
     const bool read_overflow = aov_enqueue(h, *camera, *p, ao);
-    copy_aov_out(ao, out->channels, *out, n, st);
+    copy_aov_out(ao, out->channels, ptrs_at(rptplan::AOV_ROWS, out, out->channels | rptplan::AOV_HITS, 0), n, st);
     return drain_call(h, read_overflow);
   });
 }

@@ -308,7 +308,7 @@ int rptgpu_buffer_feature_sums(const rptgpu_buffer* b, const RptAovBuffers* out)
   if (!b->has_features) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "the buffer holds no features (rptgpu_buffer_features)");
   REFUSE_IF_ABANDONED(h);
   return guarded(h, h->device, [&]() -> int {
-    copy_aov_out(b->feat, out->channels, *out, (uint64_t)b->width * b->height, h->stream);
+    copy_aov_out(b->feat, out->channels, ptrs_at(rptplan::AOV_ROWS, out, out->channels | rptplan::AOV_HITS, 0), (uint64_t)b->width * b->height, h->stream);
     HIP_TRY(hipStreamSynchronize(h->stream));
     return RPTGPU_OK;
   });

@@ -71,6 +71,30 @@ const KernelTable* table_for(uint32_t /*mode: RPT_PRECISION_F64_STRICT is the on
 }
 const char* const BAD_MODE = "unknown precision_mode (RPT_PRECISION_F64_STRICT = 0 is the only mode; F64_FAST was removed in ABI v4)";
 
+ChannelPtrs ptrs_at(rptchan::Table t, const void* arrays, uint32_t channels, const rptchan::Counts& base) {
+  ChannelPtrs at{};
+  for (int k = 0; k < t.n; k++)
+    if ((channels & t.rows[k].bit) && t.rows[k].member != rptchan::NO_MEMBER)
+      at.p[k] = rptchan::member_of(t.rows[k], arrays) + rptchan::row_bytes(t.rows[k], base);
+  return at;
+}
+ChannelPtrs ptrs_in(double* base, const rptchan::Layout& l) {
+  ChannelPtrs in{};
+  for (int k = 0; k < rptchan::MAX_ROWS; k++)
+    if (l.off[k] != rptchan::ABSENT) in.p[k] = (char*)(base + l.off[k]);
+  return in;
+}
+void copy_out(rptchan::Table t, const ChannelPtrs& src, const ChannelPtrs& dst, uint32_t channels, const rptchan::Counts& c, hipStream_t st) {
+  rptchan::by_bit(t, channels, [&](int k) {
+    HIP_TRY(hipMemcpyAsync(dst.p[k], src.p[k], rptchan::row_bytes(t.rows[k], c), hipMemcpyDeviceToHost, st));
+  });
+}
+void stage_rays(rptgpu_scene* h, const double*& a, const double*& b, uint32_t m) {
+  HIP_TRY(hipMemcpyAsync(h->rays_o.p, a, 3 * (uint64_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->rays_d.p, b, 3 * (uint64_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  a = h->rays_o.p; b = h->rays_d.p;
+}
+
 } // namespace rptapi
 
 extern "C" {

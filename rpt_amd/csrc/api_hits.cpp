@@ -11,69 +11,25 @@ namespace rptapi {
 
 constexpr uint32_t HIT_ALL = RPT_HIT_T | RPT_HIT_NORMAL | RPT_HIT_OBJECT | RPT_HIT_POSITION | RPT_HIT_ALBEDO;
 
-// what is wrong with an RptHitQuery / with the RptHitArrays of a call that names `channels` (nullptr: nothing)
+// what is wrong with an RptHitQuery (nullptr: nothing)
 static const char* bad_hit_query(const RptHitQuery* q) {
-  if (!q) return "null RptHitQuery";
-  if (q->struct_size != sizeof(RptHitQuery)) return "RptHitQuery: struct_size is not sizeof(RptHitQuery)";
-  if (!q->channels) return "RptHitQuery: channels == 0 (name at least one RPT_HIT_* channel)";
-  if (q->channels & ~HIT_ALL) return "RptHitQuery: channels names an unknown RPT_HIT_* bit";
+  if (const char* why = bad_channel_query(q, RPT_QUERY_TEXTS(RptHitQuery, RPT_HIT), HIT_ALL)) return why;
   if (q->precision_mode != RPT_PRECISION_F64_STRICT) return BAD_MODE;
   if (q->flags & RPT_FLAG_PERSISTENT)
     return "RPT_FLAG_PERSISTENT — the persistent kernel makes its rays from a camera; first hits run the closest-hit query only";
   return nullptr;
 }
-static const char* bad_hit_arrays(const RptHitArrays* o, uint32_t channels) {
-  if (!o) return "null RptHitArrays";
-  if (o->struct_size != sizeof(RptHitArrays)) return "RptHitArrays: struct_size is not sizeof(RptHitArrays)";
-  if (o->reserved) return "RptHitArrays: reserved != 0";
-  if ((channels & RPT_HIT_T) && !o->t) return "RptHitArrays: RPT_HIT_T is named but t is NULL";
-  if ((channels & RPT_HIT_NORMAL) && !o->normal) return "RptHitArrays: RPT_HIT_NORMAL is named but normal is NULL";
-  if ((channels & RPT_HIT_OBJECT) && !o->object) return "RptHitArrays: RPT_HIT_OBJECT is named but object is NULL";
-  if ((channels & RPT_HIT_POSITION) && !o->position) return "RptHitArrays: RPT_HIT_POSITION is named but position is NULL";
-  if ((channels & RPT_HIT_ALBEDO) && !o->albedo) return "RptHitArrays: RPT_HIT_ALBEDO is named but albedo is NULL";
-  return nullptr;
-}
 
 namespace {
 
-// the arrays of the named channels from ray `base` on (a channel that is not named: its pointer is not read)
-rptdev::HitOut hit_arrays_at(const RptHitArrays& a, uint32_t channels, uint64_t base) {
+// the kernels' struct from the arrays of rptplan::HIT_ROWS (a channel that is not named: nullptr, and not read)
+rptdev::HitOut hit_out(const ChannelPtrs& p, uint32_t channels) {
   rptdev::HitOut ho{};
   ho.channels = channels;
-  if (channels & RPT_HIT_T) ho.t = a.t + base;
-  if (channels & RPT_HIT_NORMAL) ho.normal = a.normal + 3 * base;
-  if (channels & RPT_HIT_OBJECT) ho.object = a.object + base;
-  if (channels & RPT_HIT_POSITION) ho.position = a.position + 3 * base;
-  if (channels & RPT_HIT_ALBEDO) ho.albedo = a.albedo + 3 * base;
+  ho.t = p.at<double>(rptplan::HIT_R_T); ho.normal = p.at<double>(rptplan::HIT_R_NORMAL);
+  ho.position = p.at<double>(rptplan::HIT_R_POSITION); ho.albedo = p.at<double>(rptplan::HIT_R_ALBEDO);
+  ho.object = p.at<int32_t>(rptplan::HIT_R_OBJECT);
   return ho;
-}
-// a host caller's piece of records on the device: the named channels of `piece` rays back to back inside `arrays`, the f64
-// channels first, each 16-byte aligned
-rptdev::HitOut hit_staging(DevBuf<double>& arrays, uint64_t piece, uint32_t channels) {
-  const uint64_t one = (piece + 1) / 2 * 2, three = (3 * piece + 1) / 2 * 2;
-  uint64_t off = 0, off_t = 0, off_normal = 0, off_position = 0, off_albedo = 0, off_object = 0;
-  if (channels & RPT_HIT_T) { off_t = off; off += one; }
-  if (channels & RPT_HIT_NORMAL) { off_normal = off; off += three; }
-  if (channels & RPT_HIT_POSITION) { off_position = off; off += three; }
-  if (channels & RPT_HIT_ALBEDO) { off_albedo = off; off += three; }
-  if (channels & RPT_HIT_OBJECT) { off_object = off; off += (piece + 3) / 4 * 2; }
-  arrays.alloc(off);
-  rptdev::HitOut ho{};
-  ho.channels = channels;
-  if (channels & RPT_HIT_T) ho.t = arrays.p + off_t;
-  if (channels & RPT_HIT_NORMAL) ho.normal = arrays.p + off_normal;
-  if (channels & RPT_HIT_POSITION) ho.position = arrays.p + off_position;
-  if (channels & RPT_HIT_ALBEDO) ho.albedo = arrays.p + off_albedo;
-  if (channels & RPT_HIT_OBJECT) ho.object = (int32_t*)(arrays.p + off_object);
-  return ho;
-}
-void copy_hits_out(const rptdev::HitOut& src, const rptdev::HitOut& dst, uint64_t m, hipStream_t st) {
-  const uint32_t ch = src.channels;
-  if (ch & RPT_HIT_T) HIP_TRY(hipMemcpyAsync(dst.t, src.t, m * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_HIT_NORMAL) HIP_TRY(hipMemcpyAsync(dst.normal, src.normal, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_HIT_OBJECT) HIP_TRY(hipMemcpyAsync(dst.object, src.object, m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_HIT_POSITION) HIP_TRY(hipMemcpyAsync(dst.position, src.position, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_HIT_ALBEDO) HIP_TRY(hipMemcpyAsync(dst.albedo, src.albedo, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
 }
 
 // (run_pass's decision: per-tree queries for scenes with deep trees — under RPT_FLAG_GENERAL_TRAVERSAL only where a group
@@ -131,7 +87,8 @@ int first_hits(rptgpu_scene* h, uint64_t n, const double* origins, const double*
                const RptHitArrays* out, bool on_device, hipStream_t user_stream) {
   // (the query first, then the arrays: both are refused whatever else is wrong, also without a handle or a device)
   if (const char* why = bad_hit_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
-  if (const char* why = bad_hit_arrays(out, q->channels)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (const char* why = bad_channel_arrays(out, RPT_ARRAYS_TEXTS(RptHitArrays), rptplan::HIT_ROWS, q->channels))
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (n && (!origins || !dirs)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
@@ -143,41 +100,26 @@ int first_hits(rptgpu_scene* h, uint64_t n, const double* origins, const double*
     const uint32_t ch = q->channels;
     const HitPieces hp = plan_hit_pieces(h, n, q->flags, "RPTGPU_HITS_PIECE");
     const uint64_t piece = hp.piece;
-    rptdev::HitOut stage{};
+    ChannelPtrs stage{}; // a host caller's piece of records on the device
     if (!on_device) {
       h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece);
-      stage = hit_staging(h->hits_out, piece, ch);
+      const rptchan::Layout lay = rptchan::layout(rptplan::HIT_ROWS, ch, piece);
+      h->hits_out.alloc(lay.words);
+      stage = ptrs_in(h->hits_out.p, lay);
     }
     for (uint64_t base = 0; base < n; base += piece) {
       const uint32_t m = (uint32_t)std::min(piece, n - base);
       const double *d_o = origins + 3 * base, *d_d = dirs + 3 * base;
-      const rptdev::HitOut mine = hit_arrays_at(*out, ch, base);
-      if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(h->rays_o.p, d_o, 3 * (uint64_t)m * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_d, 3 * (uint64_t)m * sizeof(double), hipMemcpyHostToDevice, st));
-        d_o = h->rays_o.p; d_d = h->rays_d.p;
-      }
-      hit_piece(h, kt, hp, d_o, d_d, m, on_device ? mine : stage, prof);
+      const ChannelPtrs mine = ptrs_at(rptplan::HIT_ROWS, out, ch, base);
+      if (!on_device) stage_rays(h, d_o, d_d, m);
+      hit_piece(h, kt, hp, d_o, d_d, m, hit_out(on_device ? mine : stage, ch), prof);
       if (!on_device) { // the staging arrays are the next piece's, too
-        copy_hits_out(stage, mine, m, st);
+        copy_out(rptplan::HIT_ROWS, stage, mine, ch, m, st);
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
     return h->has_deep && h->gen_overflow.p;
   });
-}
-
-// rptgpu_render_aov's arrays from index `base` of the call on
-RptAovBuffers aov_buffers_at(const RptAovBuffers& a, uint64_t base) {
-  RptAovBuffers b = a;
-  const uint32_t ch = a.channels;
-  b.hits = a.hits + base;
-  b.depth = (ch & RPT_AOV_DEPTH) ? a.depth + base : nullptr;
-  b.normal = (ch & RPT_AOV_NORMAL) ? a.normal + 3 * base : nullptr;
-  b.albedo = (ch & RPT_AOV_ALBEDO) ? a.albedo + 3 * base : nullptr;
-  b.position = (ch & RPT_AOV_POSITION) ? a.position + 3 * base : nullptr;
-  b.object = (ch & RPT_AOV_OBJECT) ? a.object + base : nullptr;
-  return b;
 }
 
 } // namespace
@@ -235,13 +177,8 @@ int render_views_aov(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
     if (!on_device) stage = aov_arrays(h->aov_out, st, piece, ch);
     for (uint64_t base = 0, m; base < n; base += m) {
       m = rptplan::views_piece_len(base, n, npix, piece, at_views);
-      const RptAovBuffers mine = aov_buffers_at(*out, base);
-      rptdev::AovOut ao = stage;
-      if (on_device) {
-        ao.channels = ch;
-        ao.hits = mine.hits; ao.depth = mine.depth; ao.normal = mine.normal; ao.albedo = mine.albedo;
-        ao.position = mine.position; ao.object = mine.object;
-      }
+      const ChannelPtrs mine = ptrs_at(rptplan::AOV_ROWS, out, ch | rptplan::AOV_HITS, base);
+      const rptdev::AovOut ao = on_device ? aov_out(mine, ch) : stage;
       rptdev::Frame fr{};
       fr.width = (uint32_t)m; fr.height = 1; fr.npix = (uint32_t)m; fr.pixels = h->ray_ids.p;
       fr.seed = per_view ? 0 : q->seed;

@@ -58,6 +58,9 @@
 //                    the lap timer, the tree's rebuild, the spare-set storage, the swap and the re-route
 //   api_aov.cpp      rptgpu_render_aov: first-hit feature buffers (argument checks, pass loop, copy_aov_out); its device
 //                    half also fills the features a Buffer holds for rptgpu_buffer_denoise
+//   channel_plan.h   what the calls that return named channels into the caller's arrays share (hits, AOVs, vertices, hit
+//                    surfaces, lightmaps, lookups, probe volumes): one table per output struct beside its planner, and the
+//                    null check, the staging layout, the piece offsets and the copy out that walk it
 // No compute happens on the host; if there is no HIP device every compute entry point returns RPTGPU_E_NO_DEVICE (there is
 // no CPU fallback by design).
 #pragma once
@@ -383,6 +386,47 @@ template <class Body> int guarded(rptgpu_scene* h, int device, Body&& body) {
 // of the kernels know; everything else runs the base builds
 const KernelTable* table_for(uint32_t mode, bool ext = false);
 extern const char* const BAD_MODE;
+
+// ---- the entry points that return named channels into the caller's arrays (channel_plan.h: one table per output struct,
+// beside the struct's planner).  What every such call refuses in its query and its arrays, as string literals made from the
+// struct's name and its channels' prefix: a null struct, a wrong struct_size, no channel, an unknown bit; reserved != 0, and
+// the lowest named channel whose array is NULL.  A driver's own checks stand between and behind these, in its own order
+struct QueryTexts { const char *null, *size, *none, *unknown; };
+#define RPT_QUERY_TEXTS(Struct, PREFIX)                                                                                         \
+  rptapi::QueryTexts { "null " #Struct, #Struct ": struct_size is not sizeof(" #Struct ")",                                     \
+                       #Struct ": channels == 0 (name at least one " #PREFIX "_* channel)", #Struct ": channels names an unknown " #PREFIX "_* bit" }
+template <class Q> const char* bad_query_struct(const Q* q, const QueryTexts& t) {
+  return !q ? t.null : q->struct_size != sizeof(Q) ? t.size : nullptr;
+}
+template <class Q> const char* bad_query_channels(const Q& q, const QueryTexts& t, uint32_t all) {
+  return !q.channels ? t.none : (q.channels & ~all) ? t.unknown : nullptr;
+}
+template <class Q> const char* bad_channel_query(const Q* q, const QueryTexts& t, uint32_t all) {
+  const char* why = bad_query_struct(q, t);
+  return why ? why : bad_query_channels(*q, t, all);
+}
+struct ArraysTexts { const char *null, *size, *reserved; };
+#define RPT_ARRAYS_TEXTS(Struct) \
+  rptapi::ArraysTexts { "null " #Struct, #Struct ": struct_size is not sizeof(" #Struct ")", #Struct ": reserved != 0" }
+template <class A> const char* bad_channel_arrays(const A* o, const ArraysTexts& t, rptchan::Table rows, uint32_t channels) {
+  if (!o) return t.null;
+  if (o->struct_size != sizeof(A)) return t.size;
+  if (o->reserved) return t.reserved;
+  const rptchan::Row* r = rptchan::first_null(rows, channels, o);
+  return r ? r->null_text : nullptr;
+}
+// a table's arrays by row (nullptr: not there): the caller's, from `base` items on — only the named channels' members are
+// read —; those of layout l inside an allocation of the handle; and the copy of `channels` from the device to the host, c
+// items each, in ascending bit order (api_common.cpp)
+struct ChannelPtrs {
+  char* p[rptchan::MAX_ROWS];
+  template <class T> T* at(int k) const { return (T*)p[k]; }
+};
+ChannelPtrs ptrs_at(rptchan::Table t, const void* arrays, uint32_t channels, const rptchan::Counts& base);
+ChannelPtrs ptrs_in(double* base, const rptchan::Layout& l);
+void copy_out(rptchan::Table t, const ChannelPtrs& src, const ChannelPtrs& dst, uint32_t channels, const rptchan::Counts& c, hipStream_t st);
+// a piece of a host caller's m rays (or points and their directions) into the handle's rays_o / rays_d -> where it lies
+void stage_rays(rptgpu_scene* h, const double*& a, const double*& b, uint32_t m);
 
 // api_render.cpp
 // StackSpill::zeros_common of a scene with these lights (scheduling: which kernel takes rays with a zero component)
@@ -721,8 +765,10 @@ const char* bad_aov_params(const RptRenderParams* p);
 rptdev::AovOut aov_arrays(DevBuf<double>& arrays, hipStream_t st, uint64_t n, uint32_t channels);
 // the call's route and kernels into `ao` (after ensure_partition); -> drain_call's read_overflow
 bool aov_enqueue(rptgpu_scene* h, const RptCamera& camera, const RptRenderParams& p, const rptdev::AovOut& ao);
-// hits and the arrays of `channels` for n pixels from the device to the caller's, on st
-void copy_aov_out(const rptdev::AovOut& src, uint32_t channels, const RptAovBuffers& dst, uint64_t n, hipStream_t st);
+// the kernels' struct from the arrays of rptplan::AOV_ROWS; hits and the arrays of `channels` for n pixels from the device
+// to the caller's (ptrs_at of its RptAovBuffers), on st
+rptdev::AovOut aov_out(const ChannelPtrs& p, uint32_t channels);
+void copy_aov_out(const rptdev::AovOut& src, uint32_t channels, const ChannelPtrs& dst, uint64_t n, hipStream_t st);
 
 // api_buffer.cpp: what the Buffer's filter shares with the views' (api_views_denoise.cpp) — what is wrong with an RptDenoise
 // (nullptr: nothing), the features the filter reads, and color_bytes' staircase for the device (thr[k]: the smallest v in

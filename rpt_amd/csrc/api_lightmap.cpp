@@ -5,7 +5,8 @@
 // texel order —, the count read back, the device work of rptgpu_bake_probes and rptgpu_bake_ao over the compacted arrays
 // (enqueue_probes, enqueue_ao: their drivers, not copies) and rpt_lightmap_scatter; at the end rpt_lightmap_dilate, one launch
 // per round and channel over the whole map.  A device caller's arrays are written where they lie; a host caller's triangles
-// and named channels are staged whole in arrays the handle keeps.
+// and named channels are staged whole in arrays the handle keeps (RptLightmapArrays' channel table: lightmap_plan.h ROWS,
+// channel_plan.h).
 // rptgpu_bake_lightmap_direct[_device] (include/rpt_gpu_direct.h; the entry points: api_direct.cpp) is the same
 // pipeline — run_lightmap — with rptgpu_bake_direct's device work, enqueue_direct, as the one gather of its one channel.
 #include "api_internal.h"
@@ -16,12 +17,9 @@ constexpr uint32_t LIGHTMAP_ALL = RPT_LIGHTMAP_IRRADIANCE | RPT_LIGHTMAP_AO | RP
                                   RPT_LIGHTMAP_POSITION | RPT_LIGHTMAP_NORMAL;
 constexpr uint32_t LIGHTMAP_GATHERS = RPT_LIGHTMAP_IRRADIANCE | RPT_LIGHTMAP_AO;
 
-// what is wrong with an RptLightmapQuery / with the RptLightmapArrays of a call that names `channels` (nullptr: nothing)
+// what is wrong with an RptLightmapQuery (nullptr: nothing)
 static const char* bad_lightmap_query(const RptLightmapQuery* q) {
-  if (!q) return "null RptLightmapQuery";
-  if (q->struct_size != sizeof(RptLightmapQuery)) return "RptLightmapQuery: struct_size is not sizeof(RptLightmapQuery)";
-  if (!q->channels) return "RptLightmapQuery: channels == 0 (name at least one RPT_LIGHTMAP_* channel)";
-  if (q->channels & ~LIGHTMAP_ALL) return "RptLightmapQuery: channels names an unknown RPT_LIGHTMAP_* bit";
+  if (const char* why = bad_channel_query(q, RPT_QUERY_TEXTS(RptLightmapQuery, RPT_LIGHTMAP), LIGHTMAP_ALL)) return why;
   if (!q->width || !q->height) return "RptLightmapQuery: width == 0 or height == 0";
   if (!rptlightmap::streams_fit(q->width, q->height, q->stream_base))
     return "RptLightmapQuery: width * height + stream_base > 2^32 (a texel's stream id has 32 bits)";
@@ -37,69 +35,8 @@ static const char* bad_lightmap_query(const RptLightmapQuery* q) {
     return "RptLightmapQuery: RPT_FLAG_RAYS_PERSISTENT | RPT_FLAG_WAVEFRONT — the two flags name different routes";
   return nullptr;
 }
-static const char* bad_lightmap_arrays(const RptLightmapArrays* o, uint32_t channels) {
-  if (!o) return "null RptLightmapArrays";
-  if (o->struct_size != sizeof(RptLightmapArrays)) return "RptLightmapArrays: struct_size is not sizeof(RptLightmapArrays)";
-  if (o->reserved) return "RptLightmapArrays: reserved != 0";
-  if ((channels & RPT_LIGHTMAP_IRRADIANCE) && !o->irradiance)
-    return "RptLightmapArrays: RPT_LIGHTMAP_IRRADIANCE is named but irradiance is NULL";
-  if ((channels & RPT_LIGHTMAP_AO) && !o->ao) return "RptLightmapArrays: RPT_LIGHTMAP_AO is named but ao is NULL";
-  if ((channels & RPT_LIGHTMAP_OWNER) && !o->owner) return "RptLightmapArrays: RPT_LIGHTMAP_OWNER is named but owner is NULL";
-  if ((channels & RPT_LIGHTMAP_BARYCENTRIC) && !o->barycentric)
-    return "RptLightmapArrays: RPT_LIGHTMAP_BARYCENTRIC is named but barycentric is NULL";
-  if ((channels & RPT_LIGHTMAP_POSITION) && !o->position)
-    return "RptLightmapArrays: RPT_LIGHTMAP_POSITION is named but position is NULL";
-  if ((channels & RPT_LIGHTMAP_NORMAL) && !o->normal) return "RptLightmapArrays: RPT_LIGHTMAP_NORMAL is named but normal is NULL";
-  return nullptr;
-}
 
 namespace {
-
-// the channels' arrays of the whole map (a channel that is not named: nullptr)
-struct MapArrays {
-  double *irradiance, *ao;
-  int32_t* owner;
-  double *barycentric, *position, *normal;
-};
-MapArrays caller_arrays(const RptLightmapArrays& a, uint32_t ch) {
-  MapArrays m{};
-  if (ch & RPT_LIGHTMAP_IRRADIANCE) m.irradiance = a.irradiance;
-  if (ch & RPT_LIGHTMAP_AO) m.ao = a.ao;
-  if (ch & RPT_LIGHTMAP_OWNER) m.owner = a.owner;
-  if (ch & RPT_LIGHTMAP_BARYCENTRIC) m.barycentric = a.barycentric;
-  if (ch & RPT_LIGHTMAP_POSITION) m.position = a.position;
-  if (ch & RPT_LIGHTMAP_NORMAL) m.normal = a.normal;
-  return m;
-}
-// a host caller's channels inside the handle's staging allocation: the f64 arrays back to back, the owners last
-uint64_t stage_words(uint64_t n, uint32_t ch) {
-  uint64_t w = 0;
-  if (ch & RPT_LIGHTMAP_IRRADIANCE) w += 3 * n;
-  if (ch & RPT_LIGHTMAP_AO) w += n;
-  if (ch & RPT_LIGHTMAP_BARYCENTRIC) w += 3 * n;
-  if (ch & RPT_LIGHTMAP_POSITION) w += 3 * n;
-  if (ch & RPT_LIGHTMAP_NORMAL) w += 3 * n;
-  if (ch & RPT_LIGHTMAP_OWNER) w += (n + 1) / 2;
-  return w;
-}
-MapArrays staged_arrays(double* base, uint64_t n, uint32_t ch) {
-  MapArrays m{};
-  if (ch & RPT_LIGHTMAP_IRRADIANCE) { m.irradiance = base; base += 3 * n; }
-  if (ch & RPT_LIGHTMAP_AO) { m.ao = base; base += n; }
-  if (ch & RPT_LIGHTMAP_BARYCENTRIC) { m.barycentric = base; base += 3 * n; }
-  if (ch & RPT_LIGHTMAP_POSITION) { m.position = base; base += 3 * n; }
-  if (ch & RPT_LIGHTMAP_NORMAL) { m.normal = base; base += 3 * n; }
-  if (ch & RPT_LIGHTMAP_OWNER) m.owner = (int32_t*)base;
-  return m;
-}
-void copy_map_out(const MapArrays& src, const MapArrays& dst, uint64_t n, hipStream_t st) {
-  if (src.irradiance) HIP_TRY(hipMemcpyAsync(dst.irradiance, src.irradiance, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (src.ao) HIP_TRY(hipMemcpyAsync(dst.ao, src.ao, n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (src.owner) HIP_TRY(hipMemcpyAsync(dst.owner, src.owner, n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (src.barycentric) HIP_TRY(hipMemcpyAsync(dst.barycentric, src.barycentric, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (src.position) HIP_TRY(hipMemcpyAsync(dst.position, src.position, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (src.normal) HIP_TRY(hipMemcpyAsync(dst.normal, src.normal, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st));
-}
 
 // `rounds` rounds of the dilation over the map's IRRADIANCE and AO (nullptr: not named), with the filled flags of the call
 // — flags: two arrays of n, [0] the state before the first round.  Each round is one launch per channel from the round's
@@ -136,7 +73,7 @@ int bad_lightmap_call(rptgpu_scene* h, uint64_t n_tris, const double* positions,
 // IRRADIANCE slot — the only channel then — is enqueue_direct instead of enqueue_probes (rptgpu_bake_lightmap_direct: q's
 // channels, max_bounces and max_distance are not read)
 int run_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, const double* normals, const double* uvs,
-                 const RptLightmapQuery* q, uint32_t ch, const MapArrays& theirs, bool direct, bool on_device,
+                 const RptLightmapQuery* q, uint32_t ch, const ChannelPtrs& theirs, bool direct, bool on_device,
                  hipStream_t user_stream) {
   return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
@@ -157,11 +94,14 @@ int run_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, cons
       tris.positions = d; tris.normals = normals ? d + wp : nullptr; tris.uvs = d + wp + wn;
     }
     // where the map's channels lie on the device: the caller's arrays, or the handle's staging
-    MapArrays dev = theirs;
+    ChannelPtrs map = theirs;
     if (!on_device) {
-      h->lm_stage.alloc(stage_words(n, ch));
-      dev = staged_arrays(h->lm_stage.p, n, ch);
+      const rptchan::Layout lay = rptchan::layout(rptlightmap::ROWS, ch, n);
+      h->lm_stage.alloc(lay.words);
+      map = ptrs_in(h->lm_stage.p, lay);
     }
+    // (a channel that is not named: nullptr)
+    double *const map_irr = map.at<double>(rptlightmap::R_IRRADIANCE), *const map_ao = map.at<double>(rptlightmap::R_AO);
 
     // 1. the owner map
     h->lm_owner.alloc(n);
@@ -203,7 +143,8 @@ int run_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, cons
     RptDirectQuery dq{};
     dq.struct_size = sizeof(RptDirectQuery); dq.samples = q->samples; dq.seed = q->seed; dq.sample_index_base = q->sample_index_base;
     dq.precision_mode = q->precision_mode; dq.flags = q->flags & ~(uint32_t)RPT_FLAG_RAYS_PERSISTENT;
-    const rptlightmap::RawOut raw{dev.owner, dev.barycentric, dev.position, dev.normal};
+    const rptlightmap::RawOut raw{map.at<int32_t>(rptlightmap::R_OWNER), map.at<double>(rptlightmap::R_BARYCENTRIC),
+                                  map.at<double>(rptlightmap::R_POSITION), map.at<double>(rptlightmap::R_NORMAL)};
     for (uint64_t base = 0; base < n; base += piece) {
       const uint32_t m = (uint32_t)rptlightmap::piece_len(base, n, piece);
       if (gather) HIP_TRY(rptlightmap::scan_owned(st, h->lm_owner.p, base, m, h->lm_scan.p, h->lm_scan_tmp.p, scan_bytes));
@@ -218,8 +159,8 @@ int run_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, cons
         else if (irr) overflow |= enqueue_probes(h, owned, c_point, c_normal, c_ids, &pq, c_irr, true);
         if (ao) overflow |= enqueue_ao(h, owned, c_point, c_normal, c_ids, &aq, c_ao, nullptr, true);
       }
-      if (irr) HIP_TRY(rptlightmap::scatter(st, h->lm_owner.p, base, m, h->lm_scan.p, c_irr, 3, dev.irradiance));
-      if (ao) HIP_TRY(rptlightmap::scatter(st, h->lm_owner.p, base, m, h->lm_scan.p, c_ao, 1, dev.ao));
+      if (irr) HIP_TRY(rptlightmap::scatter(st, h->lm_owner.p, base, m, h->lm_scan.p, c_irr, 3, map_irr));
+      if (ao) HIP_TRY(rptlightmap::scatter(st, h->lm_owner.p, base, m, h->lm_scan.p, c_ao, 1, map_ao));
     }
 
     // 3. the gutters
@@ -230,10 +171,10 @@ int run_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, cons
       h->lm_filled.alloc(2 * n);
       h->lm_pong.alloc(((irr ? 3 : 0) + (ao ? 1 : 0)) * n);
       HIP_TRY(rptlightmap::filled_from_owner(st, h->lm_owner.p, n, h->lm_filled.p));
-      dilate_map(h, W, H, rounds, dev.irradiance, dev.ao, h->lm_filled.p);
+      dilate_map(h, W, H, rounds, map_irr, map_ao, h->lm_filled.p);
     }
     if (!on_device) {
-      copy_map_out(dev, theirs, n, st);
+      copy_out(rptlightmap::ROWS, map, theirs, ch, n, st);
       HIP_TRY(hipStreamSynchronize(st));
     }
     return overflow;
@@ -245,9 +186,10 @@ int bake_lightmap(rptgpu_scene* h, uint64_t n_tris, const double* positions, con
                   const RptLightmapQuery* q, const RptLightmapArrays* out, bool on_device, hipStream_t user_stream) {
   // (the query first, then the arrays: both are refused whatever else is wrong, also without a handle or a device)
   if (const char* why = bad_lightmap_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
-  if (const char* why = bad_lightmap_arrays(out, q->channels)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (const char* why = bad_channel_arrays(out, RPT_ARRAYS_TEXTS(RptLightmapArrays), rptlightmap::ROWS, q->channels))
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (const int rc = bad_lightmap_call(h, n_tris, positions, uvs)) return rc;
-  return run_lightmap(h, n_tris, positions, normals, uvs, q, q->channels, caller_arrays(*out, q->channels), false, on_device,
+  return run_lightmap(h, n_tris, positions, normals, uvs, q, q->channels, ptrs_at(rptlightmap::ROWS, out, q->channels, 0), false, on_device,
                       user_stream);
 }
 
@@ -275,8 +217,8 @@ int bake_lightmap_direct(rptgpu_scene* h, uint64_t n_tris, const double* positio
   if (const char* why = bad_lightmap_direct_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (!direct) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null out");
   if (const int rc = bad_lightmap_call(h, n_tris, positions, uvs)) return rc;
-  MapArrays theirs{};
-  theirs.irradiance = direct;
+  ChannelPtrs theirs{};
+  theirs.p[rptlightmap::R_IRRADIANCE] = (char*)direct;
   return run_lightmap(h, n_tris, positions, normals, uvs, q, RPT_LIGHTMAP_IRRADIANCE, theirs, true, on_device, user_stream);
 }
 

@@ -3,7 +3,7 @@
 // OBJECT (api_hits.cpp plan_hit_pieces / hit_piece) and rptgpu_hit_surface's resolve walk for PRIMITIVE and BARYCENTRIC
 // (api_surface.cpp surface_walk_piece), both unchanged, into arrays the handle keeps; then rpt_lightmap_lookup
 // (kernels/lightmap_lookup.inc), one lane per ray.  The binding records and the object-to-binding table are made here per
-// call; the sizes — a piece's arrays, a host caller's staging — are lightmap_lookup_plan.h's.
+// call; the sizes — a piece's arrays, a host caller's staging — and RptLookupArrays' channel table are lightmap_lookup_plan.h's.
 // rptgpu_render_views_lightmapped[_device]: the same three steps per sample over rptgpu_render_views' own rays
 // (rpt_raygen_views[_seeded], unchanged, then rpt_views_rays_gather), and rpt_views_lightmapped_fold into the frame
 // (kernels/lightmap_views.inc).
@@ -20,30 +20,15 @@ static_assert(rptlookup::CH_T == RPT_LOOKUP_T && rptlookup::CH_OBJECT == RPT_LOO
 
 namespace {
 
-// what is wrong with an RptLookupQuery / with the RptLookupArrays of a call that names `channels` (nullptr: nothing)
+// what is wrong with an RptLookupQuery (nullptr: nothing)
 const char* bad_lookup_query(const RptLookupQuery* q) {
-  if (!q) return "null RptLookupQuery";
-  if (q->struct_size != sizeof(RptLookupQuery)) return "RptLookupQuery: struct_size is not sizeof(RptLookupQuery)";
-  if (!q->channels) return "RptLookupQuery: channels == 0 (name at least one RPT_LOOKUP_* channel)";
-  if (q->channels & ~LOOKUP_ALL) return "RptLookupQuery: channels names an unknown RPT_LOOKUP_* bit";
+  if (const char* why = bad_channel_query(q, RPT_QUERY_TEXTS(RptLookupQuery, RPT_LOOKUP), LOOKUP_ALL)) return why;
   if (q->filter != RPT_LOOKUP_NEAREST && q->filter != RPT_LOOKUP_BILINEAR)
     return "RptLookupQuery: filter is neither RPT_LOOKUP_NEAREST nor RPT_LOOKUP_BILINEAR";
   if (q->precision_mode != RPT_PRECISION_F64_STRICT) return BAD_MODE;
   if (q->flags & RPT_FLAG_PERSISTENT)
     return "RPT_FLAG_PERSISTENT — the persistent kernel makes its rays from a camera; a lightmap lookup runs the closest-hit "
            "query, a resolve walk and a fetch only";
-  return nullptr;
-}
-const char* bad_lookup_arrays(const RptLookupArrays* o, uint32_t channels) {
-  if (!o) return "null RptLookupArrays";
-  if (o->struct_size != sizeof(RptLookupArrays)) return "RptLookupArrays: struct_size is not sizeof(RptLookupArrays)";
-  if (o->reserved) return "RptLookupArrays: reserved != 0";
-  if ((channels & RPT_LOOKUP_T) && !o->t) return "RptLookupArrays: RPT_LOOKUP_T is named but t is NULL";
-  if ((channels & RPT_LOOKUP_OBJECT) && !o->object) return "RptLookupArrays: RPT_LOOKUP_OBJECT is named but object is NULL";
-  if ((channels & RPT_LOOKUP_BINDING) && !o->binding) return "RptLookupArrays: RPT_LOOKUP_BINDING is named but binding is NULL";
-  if ((channels & RPT_LOOKUP_COVERED) && !o->covered) return "RptLookupArrays: RPT_LOOKUP_COVERED is named but covered is NULL";
-  if ((channels & RPT_LOOKUP_UV) && !o->uv) return "RptLookupArrays: RPT_LOOKUP_UV is named but uv is NULL";
-  if ((channels & RPT_LOOKUP_VALUE) && !o->value) return "RptLookupArrays: RPT_LOOKUP_VALUE is named but value is NULL";
   return nullptr;
 }
 } // namespace
@@ -82,52 +67,6 @@ std::string bad_bindings_for(const rptgpu_scene* h, uint32_t n_bindings, const R
   }
   return "";
 }
-
-namespace {
-
-// the arrays of a piece on the device, and the caller's
-struct PieceArrays {
-  double* t;
-  int32_t* object;
-  int32_t* primitive;
-  double* barycentric;
-  int32_t* binding;
-  uint8_t* covered;
-  double* uv;
-  double* value;
-};
-PieceArrays lookup_arrays_at(const RptLookupArrays& a, uint32_t ch, uint64_t base) {
-  PieceArrays p{};
-  if (ch & RPT_LOOKUP_T) p.t = a.t + base;
-  if (ch & RPT_LOOKUP_OBJECT) p.object = a.object + base;
-  if (ch & RPT_LOOKUP_BINDING) p.binding = a.binding + base;
-  if (ch & RPT_LOOKUP_COVERED) p.covered = a.covered + base;
-  if (ch & RPT_LOOKUP_UV) p.uv = a.uv + 2 * base;
-  if (ch & RPT_LOOKUP_VALUE) p.value = a.value + 3 * base;
-  return p;
-}
-PieceArrays lookup_arrays_in(double* base, const rptlookup::Layout& l) {
-  PieceArrays p{};
-  if (l.has & RPT_LOOKUP_T) p.t = base + l.t;
-  if (l.has & RPT_LOOKUP_OBJECT) p.object = (int32_t*)(base + l.object);
-  if (l.has & rptlookup::IN_PRIMITIVE) p.primitive = (int32_t*)(base + l.primitive);
-  if (l.has & rptlookup::IN_BARYCENTRIC) p.barycentric = base + l.barycentric;
-  if (l.has & RPT_LOOKUP_BINDING) p.binding = (int32_t*)(base + l.binding);
-  if (l.has & RPT_LOOKUP_COVERED) p.covered = (uint8_t*)(base + l.covered);
-  if (l.has & RPT_LOOKUP_UV) p.uv = base + l.uv;
-  if (l.has & RPT_LOOKUP_VALUE) p.value = base + l.value;
-  return p;
-}
-void copy_lookup_out(const PieceArrays& src, const PieceArrays& dst, uint32_t ch, uint64_t m, hipStream_t st) {
-  if (ch & RPT_LOOKUP_T) HIP_TRY(hipMemcpyAsync(dst.t, src.t, m * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_LOOKUP_OBJECT) HIP_TRY(hipMemcpyAsync(dst.object, src.object, m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_LOOKUP_BINDING) HIP_TRY(hipMemcpyAsync(dst.binding, src.binding, m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_LOOKUP_COVERED) HIP_TRY(hipMemcpyAsync(dst.covered, src.covered, m, hipMemcpyDeviceToHost, st));
-  if (ch & RPT_LOOKUP_UV) HIP_TRY(hipMemcpyAsync(dst.uv, src.uv, 2 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_LOOKUP_VALUE) HIP_TRY(hipMemcpyAsync(dst.value, src.value, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-}
-
-} // namespace
 
 // the call's binding records and object-to-binding table on the device (a host caller's arrays staged whole), into `rays`.
 // table and recs are the caller's: the uploads read them until the call's last synchronisation
@@ -182,7 +121,8 @@ int lookup_lightmap(rptgpu_scene* h, uint64_t n, const double* origins, const do
                     hipStream_t user_stream) {
   // (the query, the arrays, the bindings by themselves: refused whatever else is wrong, also without a handle or a device)
   if (const char* why = bad_lookup_query(q)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
-  if (const char* why = bad_lookup_arrays(out, q->channels)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (const char* why = bad_channel_arrays(out, RPT_ARRAYS_TEXTS(RptLookupArrays), rptlookup::ROWS, q->channels))
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (n && (!origins || !dirs)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
   {
     const std::string why = bad_bindings(n_bindings, bindings);
@@ -211,7 +151,7 @@ int lookup_lightmap(rptgpu_scene* h, uint64_t n, const double* origins, const do
     const uint64_t piece = hp.piece;
     const rptlookup::Layout lay = rptlookup::layout(piece, ch, on_device);
     h->lk_piece.alloc(lay.words);
-    const PieceArrays mine = lookup_arrays_in(h->lk_piece.p, lay);
+    const ChannelPtrs mine = ptrs_in(h->lk_piece.p, lay);
     if (!on_device) { h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece); }
     GenericStack gs{};
     bool from_inf = false;
@@ -227,36 +167,33 @@ int lookup_lightmap(rptgpu_scene* h, uint64_t n, const double* origins, const do
     for (uint64_t base = 0; base < n; base += piece) {
       const uint32_t m = (uint32_t)std::min(piece, n - base);
       const double *d_o = origins + 3 * base, *d_d = dirs + 3 * base;
-      const PieceArrays theirs = lookup_arrays_at(*out, ch, base);
-      if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(h->rays_o.p, d_o, 3 * (uint64_t)m * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(h->rays_d.p, d_d, 3 * (uint64_t)m * sizeof(double), hipMemcpyHostToDevice, st));
-        d_o = h->rays_o.p; d_d = h->rays_d.p;
-      }
-      // where this piece's results lie on the device: the caller's arrays (device callers), else the handle's
-      PieceArrays dev = on_device ? theirs : mine;
-      if (lay.has & RPT_LOOKUP_T) dev.t = mine.t;
-      if (lay.has & RPT_LOOKUP_OBJECT) dev.object = mine.object;
-      dev.primitive = mine.primitive; dev.barycentric = mine.barycentric;
+      const ChannelPtrs theirs = ptrs_at(rptlookup::ROWS, out, ch, base);
+      if (!on_device) stage_rays(h, d_o, d_d, m);
+      // where this piece's results lie on the device: the caller's arrays (device callers), else the handle's — the
+      // kernels' structs from the arrays of rptlookup::ROWS
+      const ChannelPtrs& dev = on_device ? theirs : mine;
+      double* const t = (lay.has & RPT_LOOKUP_T ? mine : dev).at<double>(rptlookup::R_T);
+      int32_t* const object = (lay.has & RPT_LOOKUP_OBJECT ? mine : dev).at<int32_t>(rptlookup::R_OBJECT);
+      rptdev::SurfaceOut so{};
+      so.t = t; so.object = object;
+      so.primitive = mine.at<int32_t>(rptlookup::R_PRIMITIVE); so.barycentric = mine.at<double>(rptlookup::R_BARYCENTRIC);
+      so.channels = RPT_SURFACE_PRIMITIVE | RPT_SURFACE_BARYCENTRIC;
       // 1. rptgpu_first_hits' query for T | OBJECT — what the caller named of the two, and both where the fetch follows
       rptdev::HitOut ho{};
-      if (dev.t) { ho.channels |= RPT_HIT_T; ho.t = dev.t; }
-      if (dev.object) { ho.channels |= RPT_HIT_OBJECT; ho.object = dev.object; }
+      if (t) { ho.channels |= RPT_HIT_T; ho.t = t; }
+      if (object) { ho.channels |= RPT_HIT_OBJECT; ho.object = object; }
       hit_piece(h, kt, hp, d_o, d_d, m, ho, prof);
       if (fetch) {
         // 2. rptgpu_hit_surface's resolve walk for PRIMITIVE | BARYCENTRIC
-        rptdev::SurfaceOut so{};
-        so.t = dev.t; so.object = dev.object;
-        so.primitive = dev.primitive; so.barycentric = dev.barycentric;
-        so.channels = RPT_SURFACE_PRIMITIVE | RPT_SURFACE_BARYCENTRIC;
         surface_walk_piece(h, d_o, d_d, m, so, gs, from_inf);
         // 3. the fetch
-        rays.object = dev.object; rays.primitive = dev.primitive; rays.barycentric = dev.barycentric;
-        rays.binding = dev.binding; rays.covered = dev.covered; rays.uv = dev.uv; rays.value = dev.value;
+        rays.object = object; rays.primitive = so.primitive; rays.barycentric = so.barycentric;
+        rays.binding = dev.at<int32_t>(rptlookup::R_BINDING); rays.covered = dev.at<uint8_t>(rptlookup::R_COVERED);
+        rays.uv = dev.at<double>(rptlookup::R_UV); rays.value = dev.at<double>(rptlookup::R_VALUE);
         HIP_TRY(rptlookup::lookup(st, m, rays));
       }
       if (!on_device) { // the staging arrays are the next piece's, too
-        copy_lookup_out(mine, theirs, ch, m, st);
+        copy_out(rptlookup::ROWS, mine, theirs, ch, m, st);
         HIP_TRY(hipStreamSynchronize(st));
       }
     }
@@ -344,17 +281,20 @@ int render_views_lit(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
     constexpr uint32_t CH = RPT_LOOKUP_VALUE | RPT_LOOKUP_COVERED;
     const rptlookup::Layout lay = rptlookup::layout(piece, CH, false);
     h->lk_piece.alloc(lay.words);
-    const PieceArrays dev = lookup_arrays_in(h->lk_piece.p, lay);
+    const ChannelPtrs mine = ptrs_in(h->lk_piece.p, lay);
+    int32_t* const primitive = mine.at<int32_t>(rptlookup::R_PRIMITIVE);
+    double *const barycentric = mine.at<double>(rptlookup::R_BARYCENTRIC), *const value = mine.at<double>(rptlookup::R_VALUE);
+    uint8_t* const covered = mine.at<uint8_t>(rptlookup::R_COVERED);
     // the first hit's record: T and OBJECT in the lookup's arrays — with a volume all four of the query's in the volume's
     rptdev::HitOut ho{};
-    ho.channels = RPT_HIT_T | RPT_HIT_OBJECT; ho.t = dev.t; ho.object = dev.object;
+    ho.channels = RPT_HIT_T | RPT_HIT_OBJECT; ho.t = mine.at<double>(rptlookup::R_T); ho.object = mine.at<int32_t>(rptlookup::R_OBJECT);
     if (with_volume) {
       const rptvolume::Layout vlay = rptvolume::layout(piece, 0, true, true);
       h->pv_piece.alloc(vlay.words);
-      double* base = h->pv_piece.p;
+      const ChannelPtrs vol = ptrs_in(h->pv_piece.p, vlay);
       ho.channels |= RPT_HIT_NORMAL | RPT_HIT_POSITION;
-      ho.t = base + vlay.t; ho.object = (int32_t*)(base + vlay.object);
-      ho.normal = base + vlay.normal; ho.position = base + vlay.position;
+      ho.t = vol.at<double>(rptvolume::R_T); ho.object = vol.at<int32_t>(rptvolume::R_OBJECT);
+      ho.normal = vol.at<double>(rptvolume::R_NORMAL); ho.position = vol.at<double>(rptvolume::R_POSITION);
     }
     GenericStack gs{};
     bool from_inf = false;
@@ -365,8 +305,8 @@ int render_views_lit(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
       upload_bindings(h, n_bindings, bindings, on_device, staged, stage_words, table, recs, rays);
       rays.filter = lit.filter;
       rays.channels = CH;
-      rays.object = ho.object; rays.primitive = dev.primitive; rays.barycentric = dev.barycentric;
-      rays.covered = dev.covered; rays.value = dev.value;
+      rays.object = ho.object; rays.primitive = primitive; rays.barycentric = barycentric;
+      rays.covered = covered; rays.value = value;
     }
     rptvolume::Volume dv{};
     rptvolumeviews::Merge mg{};
@@ -374,10 +314,10 @@ int render_views_lit(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
       dv = upload_volume(h, *lit.volume, lit.normal_bias, on_device);
       mg.dirs = h->rays_d.p; mg.object = ho.object; mg.normal = ho.normal; mg.position = ho.position;
       mg.lightmaps = fetch ? 1u : 0u;
-      mg.covered = dev.covered; mg.value = dev.value;
+      mg.covered = covered; mg.value = value;
     }
     rptlookupviews::Sample smp{};
-    smp.object = ho.object; smp.dirs = h->rays_d.p; smp.covered = dev.covered; smp.value = dev.value;
+    smp.object = ho.object; smp.dirs = h->rays_d.p; smp.covered = covered; smp.value = value;
     smp.unbound[0] = lit.unbound[0]; smp.unbound[1] = lit.unbound[1]; smp.unbound[2] = lit.unbound[2];
     smp.iterations = (double)qv->iterations;
     smp.ev_scale = std::pow(2.0, qv->exposure_value);
@@ -399,7 +339,7 @@ int render_views_lit(rptgpu_scene* h, uint64_t n_views, const RptView* views, co
         hit_piece(h, kt, hp, h->rays_o.p, h->rays_d.p, m, ho, prof);
         if (fetch) {
           rptdev::SurfaceOut so{};
-          so.t = ho.t; so.object = ho.object; so.primitive = dev.primitive; so.barycentric = dev.barycentric;
+          so.t = ho.t; so.object = ho.object; so.primitive = primitive; so.barycentric = barycentric;
           so.channels = RPT_SURFACE_PRIMITIVE | RPT_SURFACE_BARYCENTRIC;
           surface_walk_piece(h, h->rays_o.p, h->rays_d.p, m, so, gs, from_inf);
           HIP_TRY(rptlookup::lookup(st, m, rays));

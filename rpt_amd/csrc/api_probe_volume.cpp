@@ -6,7 +6,7 @@
 // rpt_probe_volume_lookup, one lane per ray (kernels/probe_volume.inc).  Views: rptgpu_render_views_lightmapped's own driver
 // (api_lightmap_lookup.cpp render_views_lit) with a volume: NORMAL and POSITION added to the query's channels and
 // rpt_views_probe_lit_merge (kernels/probe_volume_views.inc) in front of the fold.  The checks of a volume's numbers, the pieces and the sizes — a
-// piece's arrays, a host caller's staging — are probe_volume_plan.h's.
+// piece's arrays, a host caller's staging — and RptVolumeArrays' channel table are probe_volume_plan.h's.
 #include "api_internal.h"
 
 namespace rptapi {
@@ -20,13 +20,9 @@ static_assert(rptvolume::CH_T == RPT_VOLUME_T && rptvolume::CH_OBJECT == RPT_VOL
 
 namespace {
 
-// what is wrong with an RptVolumeQuery of a call that knows the channels `known` / with an RptProbeVolume / with the
-// RptVolumeArrays of a call that names `channels` (nullptr: nothing)
+// what is wrong with an RptVolumeQuery of a call that knows the channels `known` / with an RptProbeVolume (nullptr: nothing)
 const char* bad_volume_query(const RptVolumeQuery* q, uint32_t known) {
-  if (!q) return "null RptVolumeQuery";
-  if (q->struct_size != sizeof(RptVolumeQuery)) return "RptVolumeQuery: struct_size is not sizeof(RptVolumeQuery)";
-  if (!q->channels) return "RptVolumeQuery: channels == 0 (name at least one RPT_VOLUME_* channel)";
-  if (q->channels & ~VOLUME_ALL) return "RptVolumeQuery: channels names an unknown RPT_VOLUME_* bit";
+  if (const char* why = bad_channel_query(q, RPT_QUERY_TEXTS(RptVolumeQuery, RPT_VOLUME), VOLUME_ALL)) return why;
   if (q->channels & ~known)
     return "RptVolumeQuery: channels names a channel of the ray form (a point has VALUE, COVERED and INSIDE only)";
   if (!std::isfinite(q->normal_bias)) return "RptVolumeQuery: normal_bias is not finite";
@@ -45,19 +41,6 @@ const char* bad_volume(const RptProbeVolume* v) {
   bool fits;
   (void)rptvolume::probe_count(v->nx, v->ny, v->nz, fits);
   if (!fits) return "RptProbeVolume: nx * ny * nz probes do not fit: no allocation holds their coefficients";
-  return nullptr;
-}
-const char* bad_volume_arrays(const RptVolumeArrays* o, uint32_t channels) {
-  if (!o) return "null RptVolumeArrays";
-  if (o->struct_size != sizeof(RptVolumeArrays)) return "RptVolumeArrays: struct_size is not sizeof(RptVolumeArrays)";
-  if (o->reserved) return "RptVolumeArrays: reserved != 0";
-  if ((channels & RPT_VOLUME_T) && !o->t) return "RptVolumeArrays: RPT_VOLUME_T is named but t is NULL";
-  if ((channels & RPT_VOLUME_OBJECT) && !o->object) return "RptVolumeArrays: RPT_VOLUME_OBJECT is named but object is NULL";
-  if ((channels & RPT_VOLUME_POSITION) && !o->position) return "RptVolumeArrays: RPT_VOLUME_POSITION is named but position is NULL";
-  if ((channels & RPT_VOLUME_NORMAL) && !o->normal) return "RptVolumeArrays: RPT_VOLUME_NORMAL is named but normal is NULL";
-  if ((channels & RPT_VOLUME_VALUE) && !o->value) return "RptVolumeArrays: RPT_VOLUME_VALUE is named but value is NULL";
-  if ((channels & RPT_VOLUME_COVERED) && !o->covered) return "RptVolumeArrays: RPT_VOLUME_COVERED is named but covered is NULL";
-  if ((channels & RPT_VOLUME_INSIDE) && !o->inside) return "RptVolumeArrays: RPT_VOLUME_INSIDE is named but inside is NULL";
   return nullptr;
 }
 
@@ -91,55 +74,6 @@ uint64_t asked_volume_piece() { // tests: pieces of a few points
 
 namespace {
 
-// the arrays of a piece on the device, and the caller's
-struct PieceArrays {
-  double* t;
-  int32_t* object;
-  double* position;
-  double* normal;
-  double* value;
-  uint8_t* covered;
-  uint8_t* inside;
-};
-PieceArrays volume_arrays_at(const RptVolumeArrays& a, uint32_t ch, uint64_t base) {
-  PieceArrays p{};
-  if (ch & RPT_VOLUME_T) p.t = a.t + base;
-  if (ch & RPT_VOLUME_OBJECT) p.object = a.object + base;
-  if (ch & RPT_VOLUME_POSITION) p.position = a.position + 3 * base;
-  if (ch & RPT_VOLUME_NORMAL) p.normal = a.normal + 3 * base;
-  if (ch & RPT_VOLUME_VALUE) p.value = a.value + 3 * base;
-  if (ch & RPT_VOLUME_COVERED) p.covered = a.covered + base;
-  if (ch & RPT_VOLUME_INSIDE) p.inside = a.inside + base;
-  return p;
-}
-PieceArrays volume_arrays_in(double* base, const rptvolume::Layout& l) {
-  PieceArrays p{};
-  if (l.has & RPT_VOLUME_T) p.t = base + l.t;
-  if (l.has & RPT_VOLUME_OBJECT) p.object = (int32_t*)(base + l.object);
-  if (l.has & RPT_VOLUME_POSITION) p.position = base + l.position;
-  if (l.has & RPT_VOLUME_NORMAL) p.normal = base + l.normal;
-  if (l.has & RPT_VOLUME_VALUE) p.value = base + l.value;
-  if (l.has & RPT_VOLUME_COVERED) p.covered = (uint8_t*)(base + l.covered);
-  if (l.has & RPT_VOLUME_INSIDE) p.inside = (uint8_t*)(base + l.inside);
-  return p;
-}
-void copy_volume_out(const PieceArrays& src, const PieceArrays& dst, uint32_t ch, uint64_t m, hipStream_t st) {
-  if (ch & RPT_VOLUME_T) HIP_TRY(hipMemcpyAsync(dst.t, src.t, m * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_VOLUME_OBJECT) HIP_TRY(hipMemcpyAsync(dst.object, src.object, m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_VOLUME_POSITION) HIP_TRY(hipMemcpyAsync(dst.position, src.position, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_VOLUME_NORMAL) HIP_TRY(hipMemcpyAsync(dst.normal, src.normal, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_VOLUME_VALUE) HIP_TRY(hipMemcpyAsync(dst.value, src.value, 3 * m * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (ch & RPT_VOLUME_COVERED) HIP_TRY(hipMemcpyAsync(dst.covered, src.covered, m, hipMemcpyDeviceToHost, st));
-  if (ch & RPT_VOLUME_INSIDE) HIP_TRY(hipMemcpyAsync(dst.inside, src.inside, m, hipMemcpyDeviceToHost, st));
-}
-
-// a piece of a host caller's points or rays into the handle's pair -> where the piece lies on the device
-void stage_inputs(rptgpu_scene* h, const double*& a, const double*& b, uint32_t m) {
-  HIP_TRY(hipMemcpyAsync(h->rays_o.p, a, 3 * (uint64_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->rays_d.p, b, 3 * (uint64_t)m * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  a = h->rays_o.p; b = h->rays_d.p;
-}
-
 // rays == false: a, b are the points and their directions; true: the rays' origins and directions.
 // on_device: a, b, out's arrays and the volume's coeffs / valid are device pointers
 int read_probe_volume(rptgpu_scene* h, bool rays, uint64_t n, const double* a, const double* b, const RptProbeVolume* volume,
@@ -147,7 +81,8 @@ int read_probe_volume(rptgpu_scene* h, bool rays, uint64_t n, const double* a, c
   // (the query, the volume, the arrays: refused whatever else is wrong, also without a handle or a device)
   if (const char* why = bad_volume_query(q, rays ? VOLUME_ALL : rptvolume::CH_POINT)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (const char* why = bad_volume(volume)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
-  if (const char* why = bad_volume_arrays(out, q->channels)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
+  if (const char* why = bad_channel_arrays(out, RPT_ARRAYS_TEXTS(RptVolumeArrays), rptvolume::ROWS, q->channels))
+    return fail(h, RPTGPU_E_INVALID_ARGUMENT, why);
   if (n && (!a || !b)) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null argument");
   if (!h) return fail(h, RPTGPU_E_INVALID_ARGUMENT, "null handle");
   REFUSE_IF_ABANDONED(h);
@@ -168,40 +103,43 @@ int read_probe_volume(rptgpu_scene* h, bool rays, uint64_t n, const double* a, c
     const bool prof = (q->flags & RPT_FLAG_PROFILE_KERNELS) != 0;
     const rptvolume::Layout lay = rptvolume::layout(piece, ch, rays, on_device);
     h->pv_piece.alloc(lay.words);
-    const PieceArrays mine = volume_arrays_in(h->pv_piece.p, lay);
+    const ChannelPtrs mine = ptrs_in(h->pv_piece.p, lay);
     if (!on_device) { h->rays_o.alloc(3 * piece); h->rays_d.alloc(3 * piece); }
     const rptvolume::Volume dv = upload_volume(h, *volume, q->normal_bias, on_device);
     for (uint64_t base = 0; base < n; base += piece) {
       const uint32_t m = (uint32_t)std::min(piece, n - base);
       const double *d_a = a + 3 * base, *d_b = b + 3 * base;
-      const PieceArrays theirs = volume_arrays_at(*out, ch, base);
-      if (!on_device) stage_inputs(h, d_a, d_b, m);
+      using namespace rptvolume; // (the rows of ROWS)
+      const ChannelPtrs theirs = ptrs_at(ROWS, out, ch, base);
+      if (!on_device) stage_rays(h, d_a, d_b, m);
       // where this piece's results go on the device: the caller's arrays (device callers), else the handle's
-      const PieceArrays dev = on_device ? theirs : mine;
+      const ChannelPtrs& dev = on_device ? theirs : mine;
       if (rays) {
         // 1. rptgpu_first_hits' query for T | OBJECT | NORMAL | POSITION, into the handle's arrays
         rptdev::HitOut ho{};
         ho.channels = RPT_HIT_T | RPT_HIT_OBJECT | RPT_HIT_NORMAL | RPT_HIT_POSITION;
-        ho.t = mine.t; ho.object = mine.object; ho.normal = mine.normal; ho.position = mine.position;
+        ho.t = mine.at<double>(R_T); ho.object = mine.at<int32_t>(R_OBJECT);
+        ho.normal = mine.at<double>(R_NORMAL); ho.position = mine.at<double>(R_POSITION);
         hit_piece(h, kt, hp, d_a, d_b, m, ho, prof);
         // 2. the facing, the rule, the named channels (a host caller's four hit channels: in place)
         rptvolume::Hits r{};
-        r.dirs = d_b; r.t = mine.t; r.object = mine.object; r.normal = mine.normal; r.position = mine.position;
+        r.dirs = d_b; r.t = ho.t; r.object = ho.object; r.normal = ho.normal; r.position = ho.position;
         r.fallback[0] = q->fallback[0]; r.fallback[1] = q->fallback[1]; r.fallback[2] = q->fallback[2];
         r.channels = ch;
-        r.o_t = dev.t; r.o_object = dev.object; r.o_position = dev.position; r.o_normal = dev.normal;
-        r.o_value = dev.value; r.o_covered = dev.covered; r.o_inside = dev.inside;
+        r.o_t = dev.at<double>(R_T); r.o_object = dev.at<int32_t>(R_OBJECT);
+        r.o_position = dev.at<double>(R_POSITION); r.o_normal = dev.at<double>(R_NORMAL);
+        r.o_value = dev.at<double>(R_VALUE); r.o_covered = dev.at<uint8_t>(R_COVERED); r.o_inside = dev.at<uint8_t>(R_INSIDE);
         HIP_TRY(rptvolume::lookup(st, m, dv, r));
       } else {
         rptvolume::Points p{};
         p.positions = d_a; p.normals = d_b;
         p.fallback[0] = q->fallback[0]; p.fallback[1] = q->fallback[1]; p.fallback[2] = q->fallback[2];
         p.channels = ch;
-        p.value = dev.value; p.covered = dev.covered; p.inside = dev.inside;
+        p.value = dev.at<double>(R_VALUE); p.covered = dev.at<uint8_t>(R_COVERED); p.inside = dev.at<uint8_t>(R_INSIDE);
         HIP_TRY(rptvolume::sample(st, m, dv, p));
       }
       if (!on_device) { // the staging arrays are the next piece's, too
-        copy_volume_out(mine, theirs, ch, m, st);
+        copy_out(ROWS, mine, theirs, ch, m, st);
         HIP_TRY(hipStreamSynchronize(st));
       }
     }

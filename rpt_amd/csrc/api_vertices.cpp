@@ -5,7 +5,8 @@
 // rpt_vertices_store behind every depth's closest-hit query and rpt_vertices_fold at the end of every pass that resolved
 // (kernels/wf_vertices.inc); the filler behind the paths' last vertices is laid down here, per piece, before its passes.  A
 // host caller's records are staged piece by piece in an array the handle keeps (rptplan::vertices_piece bounds it) and copied
-// out behind the piece; a device caller's are written where they lie.
+// out behind the piece; a device caller's are written where they lie.  RptVertexArrays' channel table: render_plan.h
+// VERTEX_ROWS (channel_plan.h).
 // Under RPT_FLAG_VERTICES_PERSISTENT (include/rpt_gpu_vertices_persistent.h) the same pieces, staged and
 // filled the same way, go through the persistent driver instead: rpt_paths_vertices writes each vertex where it makes it, and
 // rpt_sum_samples and the packed rpt_finish behind its launches are a render's.  The same bytes.
@@ -25,10 +26,13 @@ static_assert(RPT_VERTEX_LENGTH == 1u << 0 && RPT_VERTEX_T == 1u << 1 && RPT_VER
               "rptplan::VERTICES_VERTEX_BYTES is indexed by the RPT_VERTEX_* bit positions");
 static_assert(rptplan::vertices_vertex_bytes(VERTEX_ALL) == 152 && rptplan::vertices_path_bytes(VERTEX_ALL) == 4, "a vertex with every channel");
 
+using rptplan::VERTEX_ROWS;
+constexpr int N_ROWS = sizeof VERTEX_ROWS / sizeof VERTEX_ROWS[0];
+
 // what is wrong with an RptVertexQuery / with the RptVertexArrays of a call that names `channels` (nullptr: nothing)
 const char* bad_vertex_query(const RptVertexQuery* q) {
-  if (!q) return "null RptVertexQuery";
-  if (q->struct_size != sizeof(RptVertexQuery)) return "RptVertexQuery: struct_size is not sizeof(RptVertexQuery)";
+  const QueryTexts texts = RPT_QUERY_TEXTS(RptVertexQuery, RPT_VERTEX);
+  if (const char* why = bad_query_struct(q, texts)) return why;
   if (!q->iterations) return "RptVertexQuery: iterations == 0";
   if (q->max_bounces > 254) return "RptVertexQuery: max_bounces > 254";
   if (q->precision_mode != RPT_PRECISION_F64_STRICT) return BAD_MODE;
@@ -40,87 +44,25 @@ const char* bad_vertex_query(const RptVertexQuery* q) {
            "in the persistent kernel, which leaves no vertices behind";
   if ((q->flags & RPT_FLAG_VERTICES_PERSISTENT) && (q->flags & RPT_FLAG_WAVEFRONT))
     return "RptVertexQuery: RPT_FLAG_VERTICES_PERSISTENT | RPT_FLAG_WAVEFRONT — the two flags name different routes";
-  if (!q->channels) return "RptVertexQuery: channels == 0 (name at least one RPT_VERTEX_* channel)";
-  if (q->channels & ~VERTEX_ALL) return "RptVertexQuery: channels names an unknown RPT_VERTEX_* bit";
+  if (const char* why = bad_query_channels(*q, texts, VERTEX_ALL)) return why;
   if (q->reserved) return "RptVertexQuery: reserved != 0";
   return nullptr;
 }
 const char* bad_vertex_arrays(const RptVertexArrays* o, uint32_t ch) {
-  if (!o) return "null RptVertexArrays";
-  if (o->struct_size != sizeof(RptVertexArrays)) return "RptVertexArrays: struct_size is not sizeof(RptVertexArrays)";
-  if (o->reserved) return "RptVertexArrays: reserved != 0";
-  if ((ch & RPT_VERTEX_LENGTH) && !o->length) return "RptVertexArrays: RPT_VERTEX_LENGTH is named but length is NULL";
-  if ((ch & RPT_VERTEX_T) && !o->t) return "RptVertexArrays: RPT_VERTEX_T is named but t is NULL";
-  if ((ch & RPT_VERTEX_NORMAL) && !o->normal) return "RptVertexArrays: RPT_VERTEX_NORMAL is named but normal is NULL";
-  if ((ch & RPT_VERTEX_OBJECT) && !o->object) return "RptVertexArrays: RPT_VERTEX_OBJECT is named but object is NULL";
-  if ((ch & RPT_VERTEX_POSITION) && !o->position) return "RptVertexArrays: RPT_VERTEX_POSITION is named but position is NULL";
-  if ((ch & RPT_VERTEX_DIRECTION) && !o->direction) return "RptVertexArrays: RPT_VERTEX_DIRECTION is named but direction is NULL";
-  if ((ch & RPT_VERTEX_DRAW) && !o->draw) return "RptVertexArrays: RPT_VERTEX_DRAW is named but draw is NULL";
-  if ((ch & RPT_VERTEX_RADIANCE) && !o->radiance) return "RptVertexArrays: RPT_VERTEX_RADIANCE is named but radiance is NULL";
-  if ((ch & RPT_VERTEX_BSDF) && !o->bsdf) return "RptVertexArrays: RPT_VERTEX_BSDF is named but bsdf is NULL";
-  if ((ch & RPT_VERTEX_INV_PDF) && !o->inv_pdf) return "RptVertexArrays: RPT_VERTEX_INV_PDF is named but inv_pdf is NULL";
-  if ((ch & RPT_VERTEX_ABS_COS) && !o->abs_cos) return "RptVertexArrays: RPT_VERTEX_ABS_COS is named but abs_cos is NULL";
+  if (const char* why = bad_channel_arrays(o, RPT_ARRAYS_TEXTS(RptVertexArrays), VERTEX_ROWS, ch)) return why;
+  // (no row: rpt_finish writes the means through the ray call's own output; the highest bit, so the last check)
   if ((ch & RPT_VERTEX_RGB) && !o->rgb) return "RptVertexArrays: RPT_VERTEX_RGB is named but rgb is NULL";
   return nullptr;
 }
 
-// The per-vertex and per-path channels in the order of both structs' pointers — length, t, normal, object, position,
-// direction, draw, radiance, bsdf, inv_pdf, abs_cos —: elements per vertex (or path) and bytes per element.  The three places
-// that walk the channels — the caller's arrays offset to a piece, the staging layout, the copy out — walk this table
-struct Row { uint32_t bit, width, elem; bool per_path; };
-constexpr int N_ROWS = 11;
-constexpr Row ROWS[N_ROWS] = {{RPT_VERTEX_LENGTH, 1, 4, true},   {RPT_VERTEX_T, 1, 8, false},        {RPT_VERTEX_NORMAL, 3, 8, false},
-                              {RPT_VERTEX_OBJECT, 1, 4, false},  {RPT_VERTEX_POSITION, 3, 8, false}, {RPT_VERTEX_DIRECTION, 3, 8, false},
-                              {RPT_VERTEX_DRAW, 1, 4, false},    {RPT_VERTEX_RADIANCE, 3, 8, false}, {RPT_VERTEX_BSDF, 3, 8, false},
-                              {RPT_VERTEX_INV_PDF, 1, 8, false}, {RPT_VERTEX_ABS_COS, 1, 8, false}};
-struct Ptrs { char* p[N_ROWS]; };
-Ptrs ptrs_of(const RptVertexArrays& a, uint32_t ch) { // (only the named channels' members are read)
-  Ptrs p{};
-  if (ch & RPT_VERTEX_LENGTH) p.p[0] = (char*)a.length;
-  if (ch & RPT_VERTEX_T) p.p[1] = (char*)a.t;
-  if (ch & RPT_VERTEX_NORMAL) p.p[2] = (char*)a.normal;
-  if (ch & RPT_VERTEX_OBJECT) p.p[3] = (char*)a.object;
-  if (ch & RPT_VERTEX_POSITION) p.p[4] = (char*)a.position;
-  if (ch & RPT_VERTEX_DIRECTION) p.p[5] = (char*)a.direction;
-  if (ch & RPT_VERTEX_DRAW) p.p[6] = (char*)a.draw;
-  if (ch & RPT_VERTEX_RADIANCE) p.p[7] = (char*)a.radiance;
-  if (ch & RPT_VERTEX_BSDF) p.p[8] = (char*)a.bsdf;
-  if (ch & RPT_VERTEX_INV_PDF) p.p[9] = (char*)a.inv_pdf;
-  if (ch & RPT_VERTEX_ABS_COS) p.p[10] = (char*)a.abs_cos;
-  return p;
-}
-rptdev::VertexOut sink_of(const Ptrs& p, const RptVertexQuery& q) {
+// the kernels' struct from the arrays of VERTEX_ROWS, which stand in the order of its pointers
+rptdev::VertexOut sink_of(const ChannelPtrs& p, const RptVertexQuery& q) {
   rptdev::VertexOut vo{};
   vo.length = (uint32_t*)p.p[0]; vo.t = (double*)p.p[1]; vo.normal = (double*)p.p[2]; vo.object = (int32_t*)p.p[3];
   vo.position = (double*)p.p[4]; vo.direction = (double*)p.p[5]; vo.draw = (uint32_t*)p.p[6]; vo.radiance = (double*)p.p[7];
   vo.bsdf = (double*)p.p[8]; vo.inv_pdf = (double*)p.p[9]; vo.abs_cos = (double*)p.p[10];
   vo.channels = q.channels; vo.iterations = q.iterations; vo.stride = q.max_bounces + 1u;
   return vo;
-}
-// bytes of channel k for `rays` rays of a call with `iterations` samples and `stride` vertices per path
-uint64_t channel_bytes(int k, uint64_t rays, uint32_t iterations, uint32_t stride) {
-  return rays * iterations * (ROWS[k].per_path ? 1u : stride) * ROWS[k].width * ROWS[k].elem;
-}
-
-// the caller's arrays of the named channels from ray `base` on (a channel that is not named: its pointer is not read)
-Ptrs vertex_arrays_at(const RptVertexArrays& a, const RptVertexQuery& q, uint64_t base) {
-  const Ptrs all = ptrs_of(a, q.channels);
-  Ptrs at{};
-  for (int k = 0; k < N_ROWS; k++)
-    if (q.channels & ROWS[k].bit) at.p[k] = all.p[k] + channel_bytes(k, base, q.iterations, q.max_bounces + 1u);
-  return at;
-}
-// a host caller's piece of records on the device: the named channels of `piece` rays back to back inside `arrays`, each
-// 16-byte aligned
-Ptrs vertex_staging(DevBuf<double>& arrays, const RptVertexQuery& q, uint64_t piece) {
-  uint64_t off[N_ROWS] = {0}, total = 0; // in doubles
-  for (int k = 0; k < N_ROWS; k++)
-    if (q.channels & ROWS[k].bit) { off[k] = total; total += (channel_bytes(k, piece, q.iterations, q.max_bounces + 1u) + 15) / 16 * 2; }
-  arrays.alloc(total);
-  Ptrs at{};
-  for (int k = 0; k < N_ROWS; k++)
-    if (q.channels & ROWS[k].bit) at.p[k] = (char*)(arrays.p + off[k]);
-  return at;
 }
 
 // on_device: origins, dirs, streams and out's arrays are device pointers (user_stream: the stream their producer ran on)
@@ -139,7 +81,8 @@ int trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const dou
   if (!n) return RPTGPU_OK;
   return device_call(h, user_stream, [&]() {
     hipStream_t st = h->stream;
-    const uint32_t ch = q->channels, stride = q->max_bounces + 1u;
+    const uint32_t ch = q->channels;
+    const auto counts = [&](uint64_t rays) { return rptplan::vertex_counts(rays, q->iterations, q->max_bounces); };
     // the piece: rptgpu_trace_rays' (at most the paths one pass may hold with every level of every path), and for a host
     // caller what the staging of the named channels allows (rptplan::vertices_piece); in the persistent kernel also at most
     // what a launch's work counter holds (rptplan::vertices_persistent_piece is this composition)
@@ -149,8 +92,12 @@ int trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const dou
                                              q->max_bounces, ch);
     const bool persistent = piece_persistent(h, q->flags, RPT_FLAG_VERTICES_PERSISTENT);
     if (persistent) piece = persistent_piece(h, piece, q->iterations);
-    Ptrs stage{}, mine{};
-    if (!on_device) stage = vertex_staging(h->vertices_out, *q, piece);
+    ChannelPtrs stage{}, mine{};
+    if (!on_device) { // a host caller's piece of records on the device
+      const rptchan::Layout lay = rptchan::layout(VERTEX_ROWS, ch, counts(piece));
+      h->vertices_out.alloc(lay.words);
+      stage = ptrs_in(h->vertices_out.p, lay);
+    }
     rptdev::VertexOut sink{};
     // rpt_finish writes a piece's means somewhere: the caller's rgb, or (RGB not named) the handle's array
     const RayPieces c{n, origins, dirs, streams, on_device, piece, persistent, piece_params(*q, q->iterations, q->exposure_value),
@@ -158,8 +105,8 @@ int trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const dou
     trace_ray_pieces(
         h, c,
         [&](uint64_t base, uint64_t m, RaySource& src) {
-          mine = vertex_arrays_at(*out, *q, base);
-          const Ptrs& where = on_device ? mine : stage;
+          mine = ptrs_at(VERTEX_ROWS, out, ch, counts(base));
+          const ChannelPtrs& where = on_device ? mine : stage;
           sink = sink_of(where, *q);
           src.vertices = &sink;
           // the filler — +0.0, OBJECT -1, DRAW 0 — over the piece's entries of every named per-vertex channel, in front of the
@@ -167,15 +114,13 @@ int trace_vertices(rptgpu_scene* h, uint64_t n, const double* origins, const dou
           // fills instead of 8- to 24-byte stores a path's stride apart: RPT_VERTICES_FILL_IN_KERNEL=1 builds that form.)
 #if !RPT_VERTICES_FILL_IN_KERNEL
           for (int k = 0; k < N_ROWS; k++)
-            if ((ch & ROWS[k].bit) && !ROWS[k].per_path)
-              HIP_TRY(hipMemsetAsync(where.p[k], ROWS[k].bit == RPT_VERTEX_OBJECT ? 0xff : 0, channel_bytes(k, m, q->iterations, stride), st));
+            if ((ch & VERTEX_ROWS[k].bit) && !VERTEX_ROWS[k].per_path)
+              HIP_TRY(hipMemsetAsync(where.p[k], VERTEX_ROWS[k].bit == RPT_VERTEX_OBJECT ? 0xff : 0,
+                                     rptchan::row_bytes(VERTEX_ROWS[k], counts(m)), st));
 #endif
         },
         [&](uint64_t, uint64_t m) {
-          if (on_device) return;
-          for (int k = 0; k < N_ROWS; k++)
-            if (ch & ROWS[k].bit)
-              HIP_TRY(hipMemcpyAsync(mine.p[k], stage.p[k], channel_bytes(k, m, q->iterations, stride), hipMemcpyDeviceToHost, st));
+          if (!on_device) copy_out(VERTEX_ROWS, stage, mine, ch, counts(m), st);
         });
     return !persistent && h->has_deep && h->gen_overflow.p;
   });

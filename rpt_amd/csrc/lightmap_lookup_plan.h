@@ -1,13 +1,20 @@
-// lightmap_lookup_plan.h — the host-only arithmetic of rptgpu_lookup_lightmap (api_lightmap_lookup.cpp): a piece's
-// arrays inside one allocation of the handle — what rpt_hit_surface leaves for rpt_lightmap_lookup, and a host caller's staged
-// channels —, a host caller's bindings staged whole, and the launch's grid.  No HIP, no handle:
+// lightmap_lookup_plan.h — the host-only arithmetic of rptgpu_lookup_lightmap (api_lightmap_lookup.cpp):
+// RptLookupArrays' channel table (channel_plan.h) and which of its arrays the handle keeps for a piece — what rpt_hit_surface
+// leaves for rpt_lightmap_lookup, and a host caller's staged channels —, a host caller's bindings staged whole, and the
+// launch's grid.  No HIP, no handle:
 // tests/cpp/lightmap_lookup_plan_check.cpp builds it alone, with the host sanitizers too.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "../../include/rpt_gpu.h"
+#include "channel_plan.h"
+
 namespace rptlookup {
+using rptchan::even;
+using rptchan::i32_words;
+using rptchan::u8_words;
 
 constexpr uint32_t BLOCK = 256;
 
@@ -21,40 +28,38 @@ inline bool needs_lookup(uint32_t channels) { return (channels & CH_KERNEL) != 0
 // the blocks of a launch over m rays, one lane per ray
 inline uint32_t launch_blocks(uint64_t m) { return (uint32_t)std::max<uint64_t>(1, (m + BLOCK - 1) / BLOCK); }
 
-inline uint64_t even(uint64_t w) { return (w + 1) / 2 * 2; }
-inline uint64_t i32_words(uint64_t count) { return even((count + 1) / 2); } // `count` int32 values, in f64 words
-inline uint64_t u8_words(uint64_t count) { return even((count + 7) / 8); }  // `count` bytes, in f64 words
-
-// ---- a piece's arrays inside ONE f64 allocation: offsets in f64 words, each array 16-byte aligned, the f64 arrays first.
-// `has` names what lies there.  The hit's own four — T, OBJECT, and rpt_hit_surface's PRIMITIVE and BARYCENTRIC (bits of their
-// own here: the caller never sees them) — are there whenever the lookup kernel runs; T and OBJECT too when a host caller named
-// them, and NOT when a device caller did: the query then writes the caller's arrays and the kernels read those.  BINDING,
-// COVERED, UV, VALUE are there for a host caller that named them (its staging)
+// ---- RptLookupArrays' channels in staging order (channel_plan.h) — BARYCENTRIC stands between T and UV —, and a piece's
+// arrays inside one allocation of the handle.  `has` names what lies there.  The hit's own four — T, OBJECT, and
+// rpt_hit_surface's PRIMITIVE and BARYCENTRIC (rows with bits of their own here: the caller never sees them) — are there
+// whenever the lookup kernel runs; T and OBJECT too when a host caller named them, and NOT when a device caller did: the query
+// then writes the caller's arrays and the kernels read those.  BINDING, COVERED, UV, VALUE are there for a host caller that
+// named them (its staging)
 constexpr uint32_t IN_PRIMITIVE = 64u, IN_BARYCENTRIC = 128u;
-struct Layout {
-  uint64_t t, barycentric, uv, value, object, primitive, binding, covered; // valid where `has` names the array
-  uint32_t has;
-  uint64_t words;
+enum { R_T, R_BARYCENTRIC, R_UV, R_VALUE, R_OBJECT, R_PRIMITIVE, R_BINDING, R_COVERED };
+constexpr rptchan::Row ROWS[] = {RPT_CHANNEL_ROW(RptLookupArrays, RPT_LOOKUP_T, t, 1, 8, 0),
+                                 RPT_INTERNAL_ROW(IN_BARYCENTRIC, 3, 8),
+                                 RPT_CHANNEL_ROW(RptLookupArrays, RPT_LOOKUP_UV, uv, 2, 8, 0),
+                                 RPT_CHANNEL_ROW(RptLookupArrays, RPT_LOOKUP_VALUE, value, 3, 8, 0),
+                                 RPT_CHANNEL_ROW(RptLookupArrays, RPT_LOOKUP_OBJECT, object, 1, 4, 0),
+                                 RPT_INTERNAL_ROW(IN_PRIMITIVE, 1, 4),
+                                 RPT_CHANNEL_ROW(RptLookupArrays, RPT_LOOKUP_BINDING, binding, 1, 4, 0),
+                                 RPT_CHANNEL_ROW(RptLookupArrays, RPT_LOOKUP_COVERED, covered, 1, 1, 0)};
+struct Layout : rptchan::Layout {
+  uint64_t t, barycentric, uv, value, object, primitive, binding, covered; // the rows' offsets by name (0: not there)
 };
 inline Layout layout(uint64_t piece, uint32_t channels, bool on_device) {
-  Layout l{};
   uint32_t has = on_device ? 0u : (channels & CH_ALL);
   if (needs_lookup(channels)) {
     has |= IN_PRIMITIVE | IN_BARYCENTRIC;
     if (!on_device || !(channels & CH_T)) has |= CH_T;
     if (!on_device || !(channels & CH_OBJECT)) has |= CH_OBJECT;
   }
-  uint64_t off = 0;
-  if (has & CH_T) { l.t = off; off += even(piece); }
-  if (has & IN_BARYCENTRIC) { l.barycentric = off; off += even(3 * piece); }
-  if (has & CH_UV) { l.uv = off; off += even(2 * piece); }
-  if (has & CH_VALUE) { l.value = off; off += even(3 * piece); }
-  if (has & CH_OBJECT) { l.object = off; off += i32_words(piece); }
-  if (has & IN_PRIMITIVE) { l.primitive = off; off += i32_words(piece); }
-  if (has & CH_BINDING) { l.binding = off; off += i32_words(piece); }
-  if (has & CH_COVERED) { l.covered = off; off += u8_words(piece); }
-  l.has = has;
-  l.words = off;
+  Layout l{};
+  static_cast<rptchan::Layout&>(l) = rptchan::layout(ROWS, has, piece);
+  l.t = rptchan::off_or_0(l, R_T); l.barycentric = rptchan::off_or_0(l, R_BARYCENTRIC);
+  l.uv = rptchan::off_or_0(l, R_UV); l.value = rptchan::off_or_0(l, R_VALUE); l.object = rptchan::off_or_0(l, R_OBJECT);
+  l.primitive = rptchan::off_or_0(l, R_PRIMITIVE); l.binding = rptchan::off_or_0(l, R_BINDING);
+  l.covered = rptchan::off_or_0(l, R_COVERED);
   return l;
 }
 

@@ -1,12 +1,15 @@
 // lightmap_plan.h — the host-only arithmetic of rptgpu_bake_lightmap (api_lightmap.cpp): the clamp of a
 // triangle's texel-space extent to the range of texels rpt_lightmap_owners tests (kernels/lightmap.inc compiles the same
-// function for the device), the pieces the map is cut into, and the layout of a piece's compacted probe arrays inside one
-// allocation.  No HIP, no handle: tests/cpp/lightmap_plan_check.cpp builds it alone, with the host sanitizers too.
+// function for the device), the pieces the map is cut into, the layout of a piece's compacted probe arrays inside one
+// allocation, and RptLightmapArrays' channel table (channel_plan.h).  No HIP, no handle: tests/cpp/lightmap_plan_check.cpp builds it alone, with the host sanitizers too.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
 #include <cmath>
+
+#include "../../include/rpt_gpu.h"
+#include "channel_plan.h"
 
 #ifndef RPT_LIGHTMAP_HD
 #define RPT_LIGHTMAP_HD
@@ -92,5 +95,14 @@ inline Compact compact(uint64_t piece, bool irradiance, bool ao) {
   c.words = off;
   return c;
 }
+
+// ---- RptLightmapArrays' channels in staging order (channel_plan.h): a host caller's whole map, the owners last
+enum { R_IRRADIANCE, R_AO, R_BARYCENTRIC, R_POSITION, R_NORMAL, R_OWNER };
+constexpr rptchan::Row ROWS[] = {RPT_CHANNEL_ROW(RptLightmapArrays, RPT_LIGHTMAP_IRRADIANCE, irradiance, 3, 8, 0),
+                                 RPT_CHANNEL_ROW(RptLightmapArrays, RPT_LIGHTMAP_AO, ao, 1, 8, 0),
+                                 RPT_CHANNEL_ROW(RptLightmapArrays, RPT_LIGHTMAP_BARYCENTRIC, barycentric, 3, 8, 0),
+                                 RPT_CHANNEL_ROW(RptLightmapArrays, RPT_LIGHTMAP_POSITION, position, 3, 8, 0),
+                                 RPT_CHANNEL_ROW(RptLightmapArrays, RPT_LIGHTMAP_NORMAL, normal, 3, 8, 0),
+                                 RPT_CHANNEL_ROW(RptLightmapArrays, RPT_LIGHTMAP_OWNER, owner, 1, 4, 0)};
 
 } // namespace rptlightmap

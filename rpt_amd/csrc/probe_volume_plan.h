@@ -1,7 +1,8 @@
 // probe_volume_plan.h — the host-only arithmetic of rptgpu_sample_probe_volume, rptgpu_lookup_probe_volume and
 // rptgpu_render_views_probe_lit (api_probe_volume.cpp): the checks of a volume's numbers, the points or rays
-// per piece, a piece's arrays inside one allocation of the handle — what the first-hit query leaves for rpt_probe_volume_lookup,
-// and a host caller's staged channels —, a host caller's volume staged whole, and the launch's grid.  No HIP, no handle:
+// per piece, RptVolumeArrays' channel table (channel_plan.h) and which of its arrays the handle keeps for a piece — what the
+// first-hit query leaves for rpt_probe_volume_lookup, and a host caller's staged channels —, a host caller's volume staged
+// whole, and the launch's grid.  No HIP, no handle:
 // tests/cpp/probe_volume_plan_check.cpp builds it alone, with the host sanitizers too.
 #pragma once
 #include <stdint.h>
@@ -9,7 +10,12 @@
 #include <algorithm>
 #include <cmath>
 
+#include "../../include/rpt_gpu.h"
+#include "channel_plan.h"
+
 namespace rptvolume {
+using rptchan::even;
+using rptchan::u8_words;
 
 constexpr uint32_t BLOCK = 256;
 
@@ -22,10 +28,6 @@ constexpr uint32_t CH_HIT = CH_T | CH_OBJECT | CH_POSITION | CH_NORMAL;
 
 // the blocks of a launch over m points, one lane per point
 inline uint32_t launch_blocks(uint64_t m) { return (uint32_t)std::max<uint64_t>(1, (m + BLOCK - 1) / BLOCK); }
-
-inline uint64_t even(uint64_t w) { return (w + 1) / 2 * 2; }
-inline uint64_t i32_words(uint64_t count) { return even((count + 1) / 2); } // `count` int32 values, in f64 words
-inline uint64_t u8_words(uint64_t count) { return even((count + 7) / 8); }  // `count` bytes, in f64 words
 
 // ---- the volume's numbers: what is wrong with them (nullptr: nothing), in the header's order.  The pointers are the caller's
 // business (api_probe_volume.cpp); PROBES_MAX keeps 27 f64 per probe inside 2^60 words
@@ -53,30 +55,31 @@ inline uint64_t piece(uint64_t n, uint64_t asked, uint64_t bound) {
   return std::max<uint64_t>(1, std::min(p, n));
 }
 
-// ---- a piece's arrays inside ONE f64 allocation: offsets in f64 words, each array 16-byte aligned, the f64 arrays first.
+// ---- RptVolumeArrays' channels in staging order (channel_plan.h), and a piece's arrays inside one allocation of the handle.
 // `has` names what lies there.  The first-hit query's four — T, OBJECT, NORMAL, POSITION — are there whenever a ray form
 // runs (`rays`): the query writes them and rpt_probe_volume_lookup reads them; a host caller's T, OBJECT, POSITION and NORMAL
 // are those same arrays, rewritten in place by the lane that read them.  VALUE, COVERED, INSIDE are there for a host caller
 // that named them (its staging)
-struct Layout {
-  uint64_t t, position, normal, value, object, covered, inside; // valid where `has` names the array
-  uint32_t has;
-  uint64_t words;
+enum { R_T, R_POSITION, R_NORMAL, R_VALUE, R_OBJECT, R_COVERED, R_INSIDE };
+constexpr rptchan::Row ROWS[] = {RPT_CHANNEL_ROW(RptVolumeArrays, RPT_VOLUME_T, t, 1, 8, 0),
+                                 RPT_CHANNEL_ROW(RptVolumeArrays, RPT_VOLUME_POSITION, position, 3, 8, 0),
+                                 RPT_CHANNEL_ROW(RptVolumeArrays, RPT_VOLUME_NORMAL, normal, 3, 8, 0),
+                                 RPT_CHANNEL_ROW(RptVolumeArrays, RPT_VOLUME_VALUE, value, 3, 8, 0),
+                                 RPT_CHANNEL_ROW(RptVolumeArrays, RPT_VOLUME_OBJECT, object, 1, 4, 0),
+                                 RPT_CHANNEL_ROW(RptVolumeArrays, RPT_VOLUME_COVERED, covered, 1, 1, 0),
+                                 RPT_CHANNEL_ROW(RptVolumeArrays, RPT_VOLUME_INSIDE, inside, 1, 1, 0)};
+struct Layout : rptchan::Layout {
+  uint64_t t, position, normal, value, object, covered, inside; // the rows' offsets by name (0: not there)
 };
 inline Layout layout(uint64_t piece, uint32_t channels, bool rays, bool on_device) {
-  Layout l{};
   uint32_t has = on_device ? 0u : (channels & CH_POINT);
   if (rays) has |= CH_HIT;
-  uint64_t off = 0;
-  if (has & CH_T) { l.t = off; off += even(piece); }
-  if (has & CH_POSITION) { l.position = off; off += even(3 * piece); }
-  if (has & CH_NORMAL) { l.normal = off; off += even(3 * piece); }
-  if (has & CH_VALUE) { l.value = off; off += even(3 * piece); }
-  if (has & CH_OBJECT) { l.object = off; off += i32_words(piece); }
-  if (has & CH_COVERED) { l.covered = off; off += u8_words(piece); }
-  if (has & CH_INSIDE) { l.inside = off; off += u8_words(piece); }
-  l.has = has;
-  l.words = off;
+  Layout l{};
+  static_cast<rptchan::Layout&>(l) = rptchan::layout(ROWS, has, piece);
+  l.t = rptchan::off_or_0(l, R_T); l.position = rptchan::off_or_0(l, R_POSITION);
+  l.normal = rptchan::off_or_0(l, R_NORMAL); l.value = rptchan::off_or_0(l, R_VALUE);
+  l.object = rptchan::off_or_0(l, R_OBJECT); l.covered = rptchan::off_or_0(l, R_COVERED);
+  l.inside = rptchan::off_or_0(l, R_INSIDE);
   return l;
 }
 

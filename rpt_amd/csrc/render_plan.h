@@ -9,6 +9,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "../../include/rpt_gpu.h"
+#include "channel_plan.h"
 #include "device_types.h"
 #include "launch_limits.h"
 
@@ -285,6 +287,43 @@ inline uint64_t hits_piece(uint64_t n, uint64_t asked, uint64_t pass_bound) {
   return std::max<uint64_t>(1, std::min(std::min<uint64_t>(n, asked ? asked : fit), fit));
 }
 
+// RptHitArrays' channels in staging order (channel_plan.h): a host caller's piece of records, OBJECT behind the f64 channels
+enum { HIT_R_T, HIT_R_NORMAL, HIT_R_POSITION, HIT_R_ALBEDO, HIT_R_OBJECT };
+constexpr rptchan::Row HIT_ROWS[] = {RPT_CHANNEL_ROW(RptHitArrays, RPT_HIT_T, t, 1, 8, 0),
+                                     RPT_CHANNEL_ROW(RptHitArrays, RPT_HIT_NORMAL, normal, 3, 8, 0),
+                                     RPT_CHANNEL_ROW(RptHitArrays, RPT_HIT_POSITION, position, 3, 8, 0),
+                                     RPT_CHANNEL_ROW(RptHitArrays, RPT_HIT_ALBEDO, albedo, 3, 8, 0),
+                                     RPT_CHANNEL_ROW(RptHitArrays, RPT_HIT_OBJECT, object, 1, 4, 0)};
+// ... and RptAovBuffers' (rptgpu_render_aov, rptgpu_render_views_aov).  hits is no channel — it is always written —: a row
+// with a bit of its own that every walker of the table adds to the caller's, between the f64 arrays and OBJECT
+constexpr uint32_t AOV_HITS = 1u << 31;
+enum { AOV_R_DEPTH, AOV_R_NORMAL, AOV_R_ALBEDO, AOV_R_POSITION, AOV_R_HITS, AOV_R_OBJECT };
+constexpr rptchan::Row AOV_ROWS[] = {RPT_CHANNEL_ROW(RptAovBuffers, RPT_AOV_DEPTH, depth, 1, 8, 0),
+                                     RPT_CHANNEL_ROW(RptAovBuffers, RPT_AOV_NORMAL, normal, 3, 8, 0),
+                                     RPT_CHANNEL_ROW(RptAovBuffers, RPT_AOV_ALBEDO, albedo, 3, 8, 0),
+                                     RPT_CHANNEL_ROW(RptAovBuffers, RPT_AOV_POSITION, position, 3, 8, 0),
+                                     rptchan::Row{AOV_HITS, 1, 4, 0, (uint32_t)offsetof(RptAovBuffers, hits),
+                                                  "RptAovBuffers: hits is NULL (it is always written)"},
+                                     RPT_CHANNEL_ROW(RptAovBuffers, RPT_AOV_OBJECT, object, 1, 4, 0)};
+
+// RptVertexArrays' channels in the order of the struct's pointers, which is their staging order (channel_plan.h): per vertex,
+// but LENGTH per path.  (RGB is no row: rpt_finish writes a piece's means through the ray call's own output.)
+constexpr rptchan::Row VERTEX_ROWS[] = {RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_LENGTH, length, 1, 4, 1),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_T, t, 1, 8, 0),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_NORMAL, normal, 3, 8, 0),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_OBJECT, object, 1, 4, 0),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_POSITION, position, 3, 8, 0),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_DIRECTION, direction, 3, 8, 0),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_DRAW, draw, 1, 4, 0),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_RADIANCE, radiance, 3, 8, 0),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_BSDF, bsdf, 3, 8, 0),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_INV_PDF, inv_pdf, 1, 8, 0),
+                                        RPT_CHANNEL_ROW(RptVertexArrays, RPT_VERTEX_ABS_COS, abs_cos, 1, 8, 0)};
+// a call's counts for `rays` rays: vertices and paths
+inline rptchan::Counts vertex_counts(uint64_t rays, uint32_t iterations, uint32_t max_bounces) {
+  return rptchan::Counts(rays * iterations * ((uint64_t)max_bounces + 1), rays * iterations);
+}
+
 // ---- rptgpu_trace_vertices: rptgpu_trace_rays' pieces (rays_piece's bound and default hold as they stand; asked:
 // RPTGPU_VERTICES_PIECE) — and for a host caller, whose records are staged on the device piece by piece, also at most the rays
 // whose named channels fit VERTICES_STAGING_MAX bytes: piece x iterations x (max_bounces + 1) x vertices_vertex_bytes, plus
@@ -355,7 +394,7 @@ inline ViewsDenoisePlan views_denoise_plan(uint64_t n_views, uint64_t npix, bool
   p.n = n;
   p.state = n * (24 + 24 + 8 + 4);
   p.staging = n * 24;
-  p.features = ((n + 1) / 2 * 2 + 3 * ((3 * n + 1) / 2 * 2) + (n + 3) / 4 * 2) * 8; // aov_arrays' layout (api_aov.cpp)
+  p.features = rptchan::layout(AOV_ROWS, RPT_AOV_DEPTH | RPT_AOV_NORMAL | RPT_AOV_ALBEDO | RPT_AOV_POSITION | AOV_HITS, n).words * 8; // aov_arrays'
   p.columns = n * (18 * 8 + 1);
   if (host) p.outputs = n * ((denoised ? 24u : 0u) + (rgb8 ? 3u : 0u) + (mean ? 24u : 0u) + (variance ? 8u : 0u));
   return p;

@@ -1,10 +1,14 @@
 // surface_plan.h — the host-only arithmetic of rptgpu_hit_surface (api_surface.cpp): the columns of
-// rpt_hit_surface's walk (kernels/hit_surface.inc), the handle's scratch pair for T and OBJECT, and a host caller's staging
-// layout.  No HIP, no handle: tests/cpp/surface_plan_check.cpp builds it alone, with the host sanitizers too.
+// rpt_hit_surface's walk (kernels/hit_surface.inc), RptSurfaceArrays' channel table (channel_plan.h) and which of its arrays
+// the handle keeps for a piece: the scratch pair for T and OBJECT, a host caller's staging.  No HIP, no handle:
+// tests/cpp/surface_plan_check.cpp builds it alone, with the host sanitizers too.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
+
+#include "../../include/rpt_gpu.h"
+#include "channel_plan.h"
 
 namespace rptsurface {
 
@@ -46,31 +50,29 @@ constexpr uint32_t CH_T = 1u, CH_OBJECT = 2u, CH_CHILD = 4u, CH_PRIMITIVE = 8u, 
 // does the call need the resolve walk at all?  (T and OBJECT are the first-hit query's)
 inline bool needs_walk(uint32_t channels) { return (channels & (CH_CHILD | CH_PRIMITIVE | CH_BARYCENTRIC)) != 0; }
 
-// ---- a piece's arrays inside ONE f64 allocation: offsets in f64 words, each array 16-byte aligned, the f64 channels first.
+// ---- RptSurfaceArrays' channels in staging order (channel_plan.h), and a piece's arrays inside one allocation of the handle.
 // `stage`: which of the caller's channels are staged there (a host caller: all it named; a device caller: none).  T and
 // OBJECT are always present for a piece that walks — the walk reads them —: staged, or as the handle's scratch pair
-struct Layout {
-  uint64_t t, barycentric, object, child, primitive; // valid where `has` names the channel
-  uint32_t has;
-  uint64_t words;
+enum { R_T, R_BARYCENTRIC, R_OBJECT, R_CHILD, R_PRIMITIVE };
+constexpr rptchan::Row ROWS[] = {RPT_CHANNEL_ROW(RptSurfaceArrays, RPT_SURFACE_T, t, 1, 8, 0),
+                                 RPT_CHANNEL_ROW(RptSurfaceArrays, RPT_SURFACE_BARYCENTRIC, barycentric, 3, 8, 0),
+                                 RPT_CHANNEL_ROW(RptSurfaceArrays, RPT_SURFACE_OBJECT, object, 1, 4, 0),
+                                 RPT_CHANNEL_ROW(RptSurfaceArrays, RPT_SURFACE_CHILD, child, 1, 4, 0),
+                                 RPT_CHANNEL_ROW(RptSurfaceArrays, RPT_SURFACE_PRIMITIVE, primitive, 1, 4, 0)};
+struct Layout : rptchan::Layout {
+  uint64_t t, barycentric, object, child, primitive; // the rows' offsets by name (0: not there)
 };
-inline uint64_t even(uint64_t w) { return (w + 1) / 2 * 2; }
-inline uint64_t i32_words(uint64_t piece) { return even((piece + 1) / 2); } // `piece` int32 values, in f64 words
 inline Layout layout(uint64_t piece, uint32_t channels, bool on_device) {
-  Layout l{};
   uint32_t has = on_device ? 0u : (channels & CH_ALL);
   if (needs_walk(channels)) { // the scratch pair, where the caller's own arrays do not serve (not named, or host memory)
     if (!on_device || !(channels & CH_T)) has |= CH_T;
     if (!on_device || !(channels & CH_OBJECT)) has |= CH_OBJECT;
   }
-  uint64_t off = 0;
-  if (has & CH_T) { l.t = off; off += even(piece); }
-  if (has & CH_BARYCENTRIC) { l.barycentric = off; off += even(3 * piece); }
-  if (has & CH_OBJECT) { l.object = off; off += i32_words(piece); }
-  if (has & CH_CHILD) { l.child = off; off += i32_words(piece); }
-  if (has & CH_PRIMITIVE) { l.primitive = off; off += i32_words(piece); }
-  l.has = has;
-  l.words = off;
+  Layout l{};
+  static_cast<rptchan::Layout&>(l) = rptchan::layout(ROWS, has, piece);
+  l.t = rptchan::off_or_0(l, R_T); l.barycentric = rptchan::off_or_0(l, R_BARYCENTRIC);
+  l.object = rptchan::off_or_0(l, R_OBJECT); l.child = rptchan::off_or_0(l, R_CHILD);
+  l.primitive = rptchan::off_or_0(l, R_PRIMITIVE);
   return l;
 }
 

@@ -126,6 +126,27 @@ def test_pieces_order_and_company_change_nothing(name, monkeypatch):
     assert differing(got, {k: v[sub][::-1] for k, v in want.items()}) == []
 
 
+def seven(want):
+    """seven rays of a case: four that hit and three that miss, in the case's order"""
+    hit = want["object"] >= 0
+    return np.sort(np.concatenate([np.flatnonzero(hit)[:4], np.flatnonzero(~hit)[:3]]))
+
+
+def test_one_channel_of_a_host_caller_in_pieces_of_three(monkeypatch):
+    """7 rays in pieces of 3 — the last holds one —, POSITION alone (not the first channel, three components), against the
+    same rays in one piece with every channel: a wrong staging offset, component count or row of the channel table shows"""
+    o, d, want = case("cornell")
+    idx = seven(want)
+    o, d = np.ascontiguousarray(o[idx]), np.ascontiguousarray(d[idx])
+    g = gpu("cornell")
+    whole = g.first_hits(o, d)
+    monkeypatch.setenv("RPTGPU_HITS_PIECE", "3")
+    g.reset_stats()
+    assert differing(g.first_hits(o, d, channels=_abi.RPT_HIT_POSITION), {"position": whole["position"]}) == []
+    assert g.stats().kernel_launches[_abi.RPT_K_EXTEND] == 3
+    assert differing(whole, {k: v[idx] for k, v in want.items()}) == []
+
+
 # ---- 4. device arrays
 @pytest.mark.parametrize("name", ["cornell", "wine_glass", "nested_groups"])
 def test_device_arrays_give_the_host_calls_bits(name, monkeypatch):

@@ -406,6 +406,23 @@ def test_pieces_order_and_company_change_nothing(name, monkeypatch):
         assert differing(g.hit_surface(o[i:i + 1], d[i:i + 1]), {k: v[i:i + 1] for k, v in want.items()}) == []
 
 
+def test_one_channel_of_a_host_caller_in_pieces_of_three(monkeypatch):
+    """7 rays in pieces of 3 — the last holds one —, BARYCENTRIC alone (not the first channel, three components), against the
+    same rays in one piece with every channel: a wrong staging offset, component count or row of the channel table shows"""
+    o, d, _, _, _, want = case("cornell", "box")
+    hit = want["primitive"] >= 0
+    idx = np.sort(np.concatenate([np.flatnonzero(hit)[:4], np.flatnonzero(~hit)[:3]]))
+    assert len(idx) == 7
+    o, d = np.ascontiguousarray(o[idx]), np.ascontiguousarray(d[idx])
+    g = gpu("cornell")
+    whole = g.hit_surface(o, d)
+    monkeypatch.setenv("RPTGPU_SURFACE_PIECE", "3")
+    g.reset_stats()
+    assert differing(g.hit_surface(o, d, channels=_abi.RPT_SURFACE_BARYCENTRIC), {"barycentric": whole["barycentric"]}) == []
+    assert g.stats().kernel_launches[_abi.RPT_K_EXTEND] == 3
+    assert differing(whole, {k: v[idx] for k, v in want.items()}) == []
+
+
 # ---- 7. a channel that is not named is not written
 @pytest.mark.parametrize("name", ["wine_glass", "fractal_spheres"])
 def test_every_single_channel_and_nothing_else(name):

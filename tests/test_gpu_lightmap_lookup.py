@@ -200,6 +200,24 @@ def test_a_subset_of_channels_is_the_full_calls_and_unnamed_arrays_keep_their_se
     del keep
 
 
+def test_one_channel_of_a_host_caller_in_pieces_of_three(monkeypatch):
+    """7 rays in pieces of 3 — the last holds one —, VALUE alone (not the first channel, three components), against the same
+    rays in one piece with every channel: a wrong staging offset, component count or row of the channel table shows"""
+    name = "cornell"
+    want = model(name, "large", L.BILINEAR)
+    covered = want["covered"] != 0
+    idx = np.sort(np.concatenate([np.flatnonzero(covered)[:4], np.flatnonzero(~covered)[:3]]))
+    assert len(idx) == 7
+    g = gpu(name)
+    whole = lookup(g, name, "large", L.BILINEAR, idx)
+    monkeypatch.setenv("RPTGPU_LOOKUP_PIECE", "3")
+    g.reset_stats()
+    got = lookup(g, name, "large", L.BILINEAR, idx, channels=_abi.RPT_LOOKUP_VALUE)
+    assert sorted(got) == ["value"] and differing(got, whole, ("value",)) == []
+    assert g.stats().kernel_launches[_abi.RPT_K_EXTEND] == 3
+    assert differing(whole, {k: v[idx] for k, v in want.items()}) == []
+
+
 @pytest.mark.parametrize("name", ["cornell", "mixed"])
 def test_device_tensors_give_the_host_calls_bits(name, monkeypatch):
     o, d, _ = case(name)

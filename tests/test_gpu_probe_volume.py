@@ -289,6 +289,25 @@ def test_the_ray_forms_pieces_subsets_and_device_form(name, monkeypatch):
     assert differing({k: v.cpu().numpy() for k, v in got.items()}, want, ("t", "value")) == []
 
 
+def test_one_channel_of_a_host_caller_in_pieces_of_three(monkeypatch):
+    """7 rays in pieces of 3 — the last holds one —, NORMAL alone (not the first channel, three components), against the same
+    rays in one piece with every channel: a wrong staging offset, component count or row of the channel table shows"""
+    name = "cornell"
+    o, d, hits = rays(name)
+    hit = hits["object"] >= 0
+    idx = np.sort(np.concatenate([np.flatnonzero(hit)[:4], np.flatnonzero(~hit)[:3]]))
+    assert len(idx) == 7
+    o, d = np.ascontiguousarray(o[idx]), np.ascontiguousarray(d[idx])
+    vol, g = scene_volume(name, "half"), gpu(name)
+    whole = g.lookup_probe_volume(o, d, vol, normal_bias=0.5, fallback=FALLBACK)
+    monkeypatch.setenv("RPTGPU_VOLUME_PIECE", "3")
+    g.reset_stats()
+    got = g.lookup_probe_volume(o, d, vol, normal_bias=0.5, fallback=FALLBACK, channels=_abi.RPT_VOLUME_NORMAL)
+    assert sorted(got) == ["normal"] and differing(got, whole, ("normal",)) == []
+    assert g.stats().kernel_launches[_abi.RPT_K_EXTEND] == 3
+    assert differing(whole, PV.lookup(vol, d, {k: v[idx] for k, v in hits.items()}, 0.5, FALLBACK), RAY_NAMES) == []
+
+
 def test_empty_calls_and_refusals_on_a_live_handle():
     g = gpu("cornell")
     vol = volume((3, 2, 2), None)

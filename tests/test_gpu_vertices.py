@@ -298,6 +298,20 @@ def test_channel_subsets(channels, device):
             assert (outs[k] == 7).all(), k
 
 
+def test_one_channel_of_a_host_caller_in_pieces_of_three(monkeypatch):
+    """7 rays in pieces of 3 — the last holds one —, NORMAL alone (not the first channel, three components), against the same
+    rays in one piece with every channel: a wrong staging offset, component count or row of the channel table shows"""
+    name = "cornell"
+    p, o, d, streams = rays(name)
+    g = R.gpu(name)
+    o, d, streams = (np.ascontiguousarray(x[:7]) for x in (o, d, streams))
+    whole = vertices(g, name, o, d, streams).arrays()
+    monkeypatch.setenv("RPTGPU_VERTICES_PIECE", "3")
+    got = vertices(g, name, o, d, streams, channels=_abi.RPT_VERTEX_NORMAL).arrays()
+    assert differing(got, {"normal": whole["normal"]}) == []
+    assert differing(whole, {k: a[:7] for k, a in base(name).arrays().items()}) == []
+
+
 def test_the_filler():
     v = base("glass")
     n, S, V = v.t.shape

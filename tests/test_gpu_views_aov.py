@@ -171,6 +171,21 @@ def test_device_arrays_channels_and_flags(name, monkeypatch):
     assert sorted(hits_only) == ["hits"] and np.array_equal(hits_only["hits"], base["hits"])
 
 
+def test_one_channel_of_a_host_caller_in_pieces_of_three(monkeypatch):
+    """a view of 7 x 1 pixels in pieces of 3 — the last holds one —, NORMAL alone (not the first channel, three components),
+    against the same view in one piece with every channel: a wrong staging offset, component count or row of the channel
+    table shows"""
+    name = "cornell"
+    g = gpu(name)
+    view = cameras(name)[0]
+    kw = dict(samples=SPP, seed=small_scenes.small(name)[2].seed, sample_index_base=BASE)
+    whole = g.render_views_aov([view], 7, 1, **kw)
+    assert whole["hits"].max() > 0
+    monkeypatch.setenv("RPTGPU_VIEWS_PIECE", "3")
+    got = g.render_views_aov([view], 7, 1, channels=_abi.RPT_AOV_NORMAL, **kw)
+    assert aov_model.mismatches({k: got[k] for k in ("hits", "normal")}, {k: whole[k] for k in ("hits", "normal")}) == []
+
+
 def test_nothing_to_do_and_refusals_on_a_live_handle():
     name = "cornell"
     w, h = SIZES[name]
